@@ -2,6 +2,7 @@
 """Headline benchmark: any-hit shadow rays at 3840x2160 on the ~1M-triangle scene (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config city_4k] [--kernel V] [--scaling strong|weak]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one frame of synthetic input: one shadow-mask dispatch
 (ray generation + BVH traversal + mask write) with the BVH, the G-buffer positions and the mask
@@ -14,13 +15,26 @@ once per GPU, disjoint output), torch.distributed (gloo) is only the barrier / m
   --scaling weak   every rank traces a full frame of its own (rank r = frame r of a camera path).
 
 Timing: a time-based pre-warm (back-to-back launches until the clocks have ramped), W untimed warm-up steps, then
-exactly K steps between barrier + synchronize on both sides; `value` = rays / (max over ranks of that wall time).
-HIP events on the launch stream bracket the K launches (`ms_per_frame_gpu_mean`, the roofline's launch duration); right
-after the timed region the same launch runs again with an event pair per frame: `ms_per_frame_gpu_median` is the figure
-the reference's on-screen counter shows (RayTracedShadows.cpp:263-265).
+exactly K steps between barrier + synchronize on both sides; `value` = rays / (max over ranks of that wall time) and
+`ms_per_step` = that wall time / K.  HIP events on the launch stream bracket the K launches (`ms_per_frame_gpu_mean`, the
+roofline's launch duration); with --full, right after the timed region the same launch runs again with an event pair per
+frame: `ms_per_frame_gpu_median` is the figure the reference's on-screen counter shows (RayTracedShadows.cpp:263-265,
+SURVEY.md 8d).
 
-Rank 0 prints ONE JSON line.  Before timing, every rank checks its GPU mask against the CPU oracle
-on every pixel it owns (the correctness gate of SURVEY.md 8d); a mismatch aborts.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up (inputs; the kernel, launch options
+and split table rts_ctx_autotune picks), pre-warm, W warm-up steps, the K timed steps, the outputs if asked for, the line.
+
+  --dump-outputs DIR  after the timed steps: the shadow mask the last timed step wrote (what a caller of the dispatch receives),
+                      as DIR/shadow_mask.npy (float32, H x W; N > 1 --scaling strong: the whole frame assembled from the ranks'
+                      stripes).  Inputs are seeded, so equal arguments give equal inputs.  Above 64 MB (--scaling weak, N frames)
+                      a fixed seeded sample is written instead: shadow_mask_sample.npy + the flat indices in shadow_mask_sample_index.npy.
+  --full              everything else on top: the rocprofv3 counter passes, the parity gate
+                      (before timing, every rank checks its GPU mask against the CPU oracle on every pixel it owns -- the
+                      correctness gate of SURVEY.md 8d; a mismatch aborts), per-launch event medians, the shader-clock and
+                      dispatch-floor probes, two frames in flight, the roofline, the CPU baseline and the secondary workloads.
+                      The --no-* options switch parts of it off.
+
+The `roofline` below is part of --full.
 
 `roofline` (N = 1): two bounds the dominant kernel is actually under, each a fraction <= 1 --
   hbm         bytes that crossed the L2's memory side per launch (rocprofv3 FETCH_SIZE / WRITE_SIZE, separate --pmc
@@ -425,8 +439,10 @@ def pick_kernel(args, config, say):
         return -1, args.options, None
 
 
-def measure(ctx, step, steps, warmup, prewarm_seconds, barrier=None, probe_rows=0):
-    """The timed region of the contract: time-based pre-warm, W untimed steps, exactly K steps between synchronisations."""
+def measure(ctx, step, steps, warmup, prewarm_seconds, barrier=None, probe_rows=0, per_launch=True, after_timed=None):
+    """The timed region of the contract: time-based pre-warm, W untimed steps, exactly K steps between synchronisations.
+    `after_timed` runs right after the K steps have finished (untimed: the outputs of the last one).  per_launch=False (a plain
+    run) stops there: no run with an event pair per launch, no clock probe."""
     t0 = time.perf_counter()
     prewarm_launches = 0
     while time.perf_counter() - t0 < prewarm_seconds:
@@ -447,9 +463,13 @@ def measure(ctx, step, steps, warmup, prewarm_seconds, barrier=None, probe_rows=
     ctx.timer_mark(1)
     ctx.synchronize()
     wall = time.perf_counter() - t0
+    if after_timed:
+        after_timed()
     if barrier:
         barrier()
     events_ms = ctx.timer_between_ms(0, 1)                       # ... their span / K = the average launch duration of the timed region
+    if not per_launch:
+        return {"wall": wall, "kernel_ms": float(events_ms), "median_ms": None, "prewarm_launches": prewarm_launches, "clock_mhz": None}
     # per-launch figures (the reference's on-screen counter brackets every frame, cpp:572-594) from a run of the same launch right
     # after the timed region: an event between two launches costs the queue 1-2 us, so the timed region carries none inside
     n_single = max(10, min(steps, 100))
@@ -500,6 +520,46 @@ def parity_gate(ctx, oracle, wl, rows, step, d_mask, threads, who):
     return V, L, got
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def gather_masks(mask, dist, N, rank, striped):
+    """The mask(s) a caller of the timed dispatch receives, on rank 0: the frame (N > 1 strong: assembled from every rank's
+    own rows), or one frame per rank stacked (N > 1 weak).  Collective for N > 1; None on the other ranks."""
+    if not dist:
+        return mask
+    import torch
+    from raytracedshadows_amd import partition
+    mine = torch.from_numpy(mask)
+    seen = [torch.zeros_like(mine) for _ in range(N)]
+    dist.all_gather(seen, mine)
+    if rank != 0:
+        return None
+    frames = [t.numpy() for t in seen]
+    if not striped:
+        return np.stack(frames)
+    H = mask.shape[0]
+    out = np.zeros_like(mask)
+    for r in range(N):
+        for b, e in partition.stripe_rows(H, N, r, band=BAND, interleaved=True):
+            out[b:e] = frames[r][b:e]
+    return out
+
+
+def dump_outputs(directory, mask, rank):
+    """--dump-outputs: the mask as float32 (0/1, or the count of unoccluded samples); above 64 MB a fixed seeded sample."""
+    if rank != 0 or mask is None:
+        return
+    os.makedirs(directory, exist_ok=True)
+    if mask.size * 4 <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, "shadow_mask.npy"), mask.astype(np.float32))
+        return
+    n = DUMP_LIMIT_BYTES // (4 + 8) // 2
+    idx = np.sort(np.random.default_rng(0).choice(mask.size, n, replace=False))
+    np.save(os.path.join(directory, "shadow_mask_sample.npy"), mask.reshape(-1)[idx].astype(np.float32))
+    np.save(os.path.join(directory, "shadow_mask_sample_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -520,6 +580,11 @@ def main():
                     help="skip the dispatch-floor and shader-clock probes (profiler runs: only the timed kernel is launched)")
     ap.add_argument("--save-counters", default="", help="write the live counter passes to this JSON file (the committed fallback "
                                                           "profiles/**/counters_<config>.json that is used when rocprofv3 is not available)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the shadow mask of the last one to DIR/shadow_mask.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the counters, parity gate, probes, roofline, CPU baseline and secondary workloads "
+                         "(a plain run only sets up, warms up and times the steps)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--tune-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -527,6 +592,8 @@ def main():
         return pmc_child(args)
     if args.tune_child:
         return tune_child(args)
+    if not args.full:                     # a plain run: only what the headline figure needs
+        args.no_cpu_baseline = args.no_pmc = args.no_secondary = args.no_probes = True
 
     # stdout carries exactly ONE JSON line (rank 0): everything else any library prints to fd 1 (gloo announces
     # its connections there) goes to stderr
@@ -650,20 +717,27 @@ def main():
         else:
             c.trace_shadow_mask_device(wl.constants, d_pos, W, H, d_mask, light=wl.light)
 
-    # ---- correctness gate: GPU mask == CPU oracle mask, every pixel this rank owns -----------------
-    import oracle  # the checker; never on the measured path
-    olight = oracle.light_from_product(wl.light, wl.constants)
-    V, L, got = parity_gate(ctx, oracle, wl, my_rows, one_step, d_mask, host_threads, f"rank {rank}")
-    say(f"parity gate: {my_rays} rays bit-exact vs oracle (V/ray {V / my_rays:.2f}, L/ray {L / my_rays:.2f})")
-    alg_bytes_per_step = 32 * V + 16 * L + 17 * (my_rays // max(1, spp))
-    kname = ctx.last_kernel_name()
+    # ---- correctness gate (--full): GPU mask == CPU oracle mask, every pixel this rank owns -----------------
+    if args.full:
+        import oracle  # the checker; never on the measured path
+        olight = oracle.light_from_product(wl.light, wl.constants)
+        V, L, got = parity_gate(ctx, oracle, wl, my_rows, one_step, d_mask, host_threads, f"rank {rank}")
+        say(f"parity gate: {my_rays} rays bit-exact vs oracle (V/ray {V / my_rays:.2f}, L/ray {L / my_rays:.2f})")
+        alg_bytes_per_step = 32 * V + 16 * L + 17 * (my_rays // max(1, spp))
+        kname = ctx.last_kernel_name()
+        packet_kernel = kname.startswith("shadowMaskPacketKernel")
+    else:
+        packet_kernel = False
 
     # ---- timed region (pre-warm, W warm-up steps, exactly K steps between barrier + synchronize) --------------------
-    packet_kernel = kname.startswith("shadowMaskPacketKernel")
+    last_mask = np.zeros((H, W), np.uint8) if args.dump_outputs else None
     probe_rows = ((H + 7) // 8) if (packet_kernel and not striped and not args.no_probes) else 0
     m = measure(ctx, one_step, args.steps, args.warmup, args.prewarm_seconds, barrier=dist.barrier if dist else None,
-                probe_rows=probe_rows)
+                probe_rows=probe_rows, per_launch=args.full,
+                after_timed=(lambda: ctx.d2h(last_mask, d_mask)) if last_mask is not None else None)
     wall, kernel_ms, median_ms, clock_mhz, prewarm_launches = m["wall"], m["kernel_ms"], m["median_ms"], m["clock_mhz"], m["prewarm_launches"]
+    if not args.full:
+        kname = ctx.last_kernel_name()
 
     # ---- extra (not the headline): TWO frames in flight -- consecutive frames on two streams into two masks, so that the
     #      tail of one frame's dispatch (the last waves of a launch keep a few CUs busy) runs beside the next frame's bulk,
@@ -733,7 +807,7 @@ def main():
         g2 = [torch.zeros_like(t2) for _ in range(N)]
         dist.all_gather(g2, t2)
         wall2 = max(float(x[0]) for x in g2)
-        t = torch.tensor([wall, kernel_ms, median_ms, floor_ms, float(kernel_id), float(ctx.get_option("packet_share")),
+        t = torch.tensor([wall, kernel_ms, float("nan") if median_ms is None else median_ms, floor_ms, float(kernel_id), float(ctx.get_option("packet_share")),
                           float(split_table["split_tiles"] if split_table else 0), float(split_table["front_tiles"] if split_table else 0)], dtype=torch.float64)
         gathered = [torch.zeros_like(t) for _ in range(N)]
         dist.all_gather(gathered, t)
@@ -741,6 +815,8 @@ def main():
         wall = max(g[0] for g in per_rank)                          # MAX over ranks
     else:
         per_rank = [[wall, kernel_ms, median_ms, floor_ms, float(kernel_id), 0.0, 0.0, 0.0]]
+    if last_mask is not None:
+        dump_outputs(args.dump_outputs, gather_masks(last_mask, dist, N, rank, striped), rank)
 
     frames_per_step = N if (args.scaling == "weak" and N > 1) else 1
     total_rays = rays_per_frame * frames_per_step * args.steps
@@ -762,7 +838,7 @@ def main():
                    "launch_options": kernel_opts,
                    "split_table": dict(split_table, plan=split_plan) if split_table else None,
                    "bvh_bytes": int(wl.packed.nbytes),
-                   "ms_per_frame_gpu_median": round(max(g[2] for g in per_rank), 4),
+                   "ms_per_frame_gpu_median": round(max(g[2] for g in per_rank), 4) if args.full else None,
                    "ms_per_frame_gpu_mean": round(max(g[1] for g in per_rank) / args.steps, 4),
                    "dispatch_floor_ms": None if args.no_probes else round(max(g[3] for g in per_rank), 4),
                    "prewarm_launches": prewarm_launches, "device_ordinals": ordinals},
@@ -775,41 +851,42 @@ def main():
                     "overlap: one frame's tail beside the next frame's bulk); `value` above is one frame at a time"}
     if N > 1:
         result["config"]["per_rank"] = [{"rank": r, "device": ordinals[r], "wall_ms_per_step": round(g[0] / args.steps * 1e3, 4),
-                                         "gpu_median_ms": round(g[2], 4), "dispatch_floor_ms": None if args.no_probes else round(g[3], 4),
+                                         "gpu_median_ms": round(g[2], 4) if args.full else None, "dispatch_floor_ms": None if args.no_probes else round(g[3], 4),
                                          "tuned_on_its_own_stripe": {"kernel": int(g[4]), "packet_share": int(g[5]),
                                                                      "split_tiles": int(g[6]), "front_tiles": int(g[7])}}
                                         for r, g in enumerate(per_rank)]
 
-    # ---- roofline (N = 1) -------------------------------------------------------------------------------------------
-    roof = {"algorithmic_bytes_per_launch": int(alg_bytes_per_step),
-            "algorithmic_GBps": round(alg_bytes_per_step / avg_launch_s / 1e9, 1),
-            "avg_launch_ms": round(avg_launch_s * 1e3, 5), "median_launch_ms": round(median_ms, 5), "kernel": kname,
-            "shader_clock_mhz": round(clock_mhz, 1) if clock_mhz else None,
-            "shader_clock_source": "stamps of 10-50 launches of the same dispatch right after the timed region (first wave of every tile row); "
-                                   "the timed launches carry no probe" if clock_mhz else None,
-            "note": "frac = the larger of two measured bounds (see the module docstring); algorithmic_* is SURVEY 8d's "
-                    "cache-oblivious 32V+16L+17 B/ray from the oracle's exact visit counts, informational; packet_bytes is the same "
-                    "model at the granularity this kernel fetches at (once per wave), a fraction of the HBM peak <= 1"}
-    if counters and args.save_counters:
-        rec = dict(counters, source_hash=source_hash(), workload=args.config, kernel=kname)
-        with open(args.save_counters, "w") as fh:
-            json.dump(rec, fh, indent=1)
-    if N == 1 and counters is None and not args.no_pmc:
-        counters = committed_counters(kname, args.config, say)
-    roof.update(roofline_bounds(counters, avg_launch_s, clock_mhz))
-    if N == 1 and packet_kernel:
-        try:
-            pm = packet_model(oracle, wl, kname)
-            pm["achieved"] = round(pm["bytes_per_launch"] / avg_launch_s / 1e9, 1)
-            pm["peak"], pm["unit"] = HBM_PEAK_GBS, "GB/s"
-            pm["frac"] = round(pm["achieved"] / HBM_PEAK_GBS, 4)
-            roof["packet_bytes"] = pm
-            if roof.get("valu_issue"):
-                roof["valu_issue"]["lane_fill_members"] = pm["lane_fill_members"]
-            headline_fraction(roof, pm["lane_fill_members"])
-        except Exception as e:
-            say(f"packet model failed: {e!r}")
-    result["roofline"] = roof
+    # ---- roofline (--full) ------------------------------------------------------------------------------------------
+    if args.full:
+        roof = {"algorithmic_bytes_per_launch": int(alg_bytes_per_step),
+                "algorithmic_GBps": round(alg_bytes_per_step / avg_launch_s / 1e9, 1),
+                "avg_launch_ms": round(avg_launch_s * 1e3, 5), "median_launch_ms": round(median_ms, 5), "kernel": kname,
+                "shader_clock_mhz": round(clock_mhz, 1) if clock_mhz else None,
+                "shader_clock_source": "stamps of 10-50 launches of the same dispatch right after the timed region (first wave of every tile row); "
+                                       "the timed launches carry no probe" if clock_mhz else None,
+                "note": "frac = the larger of two measured bounds (see the module docstring); algorithmic_* is SURVEY 8d's "
+                        "cache-oblivious 32V+16L+17 B/ray from the oracle's exact visit counts, informational; packet_bytes is the same "
+                        "model at the granularity this kernel fetches at (once per wave), a fraction of the HBM peak <= 1"}
+        if counters and args.save_counters:
+            rec = dict(counters, source_hash=source_hash(), workload=args.config, kernel=kname)
+            with open(args.save_counters, "w") as fh:
+                json.dump(rec, fh, indent=1)
+        if N == 1 and counters is None and not args.no_pmc:
+            counters = committed_counters(kname, args.config, say)
+        roof.update(roofline_bounds(counters, avg_launch_s, clock_mhz))
+        if N == 1 and packet_kernel:
+            try:
+                pm = packet_model(oracle, wl, kname)
+                pm["achieved"] = round(pm["bytes_per_launch"] / avg_launch_s / 1e9, 1)
+                pm["peak"], pm["unit"] = HBM_PEAK_GBS, "GB/s"
+                pm["frac"] = round(pm["achieved"] / HBM_PEAK_GBS, 4)
+                roof["packet_bytes"] = pm
+                if roof.get("valu_issue"):
+                    roof["valu_issue"]["lane_fill_members"] = pm["lane_fill_members"]
+                headline_fraction(roof, pm["lane_fill_members"])
+            except Exception as e:
+                say(f"packet model failed: {e!r}")
+        result["roofline"] = roof
 
     # ---- CPU baseline (rank 0, N == 1 only): the oracle on the host cores, same frame ---------------
     if rank == 0 and N == 1 and not args.no_cpu_baseline:

@@ -1,5 +1,5 @@
-import sys, time, numpy as np
-sys.path.insert(0, '/root/repo')
+import os, sys, time, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from raytracedshadows_amd import api, workloads
 cfg = sys.argv[1]
 wl = workloads.prepare_config(cfg, cache=True)

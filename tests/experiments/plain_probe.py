@@ -1,8 +1,9 @@
 """Experiment (GPU box): lifetimes and hardware slots of the probe waves (first wave of every tile row) of the EVERYDAY
 instantiation -- the one that is timed and has no other stamps."""
+import os
 import sys
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from raytracedshadows_amd import api, workloads
 cfg = sys.argv[1] if len(sys.argv) > 1 else "city_4k"
 wl = workloads.prepare_config(cfg, cache=True)

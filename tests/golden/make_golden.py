@@ -10,6 +10,7 @@
   against regressions and the HIP kernels against the oracle -- they are not reference outputs.
 * obj_cases.json: a tricky OBJ text + what the REFERENCE's own parser (oracle/_ref, built from
   /root/reference/External/zeux_objparser by oracle/Makefile) returns for it.
+* obj_cornell_ref.npz: what the same parser reads from the cornell scene's OBJ text (vertex bits per face corner).
 """
 import ctypes as C
 import json
@@ -74,6 +75,24 @@ def obj_cases():
     print("obj_cases.json:", st, len(v), len(vt), len(vn), len(f))
 
 
+def obj_cornell():
+    """obj_cornell_ref.npz: the vertex positions the REFERENCE parser (oracle/_ref) reads from the cornell scene's OBJ text,
+    one row per face corner -- what tests/test_obj.py compares the product's reader against when oracle/_ref is absent."""
+    from raytracedshadows_amd import scenes
+    ref = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libzeux_objparser_ref.so"))
+    ref.ref_obj_parse.argtypes = [C.c_char_p] + [C.POINTER(C.c_uint64)] * 4 + [C.c_void_p] * 4
+    path = scenes.cornell().write_obj(os.path.join(HERE, "_tmp_cornell.obj"))
+    sizes = [C.c_uint64(0) for _ in range(4)]
+    assert ref.ref_obj_parse(path.encode(), *[C.byref(s) for s in sizes], None, None, None, None) == 0
+    v = np.zeros(sizes[0].value, np.float32)
+    f = np.zeros(sizes[3].value, np.int32)
+    ref.ref_obj_parse(path.encode(), *[C.byref(s) for s in sizes], v.ctypes.data, None, None, f.ctypes.data)
+    os.remove(path)
+    corners = v.reshape(-1, 3)[f.reshape(-1, 3)[:, 0]]
+    np.savez_compressed(os.path.join(HERE, "obj_cornell_ref.npz"), corner_bits=corners.view(np.uint32))
+    print("obj_cornell_ref.npz:", corners.shape)
+
+
 def masks():
     import oracle
     from raytracedshadows_amd import api, scenes
@@ -96,4 +115,5 @@ def masks():
 
 if __name__ == "__main__":
     obj_cases()
+    obj_cornell()
     masks()

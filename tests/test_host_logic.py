@@ -339,3 +339,30 @@ def test_bench_carries_a_planned_tile_order_as_text():
     text = bench.splits_arg({"tile_order": {"xcd_square": 32, "life_block": 16}, "ordered_tiles": 129600})
     assert text == "order:32:16" and bench.parse_splits(text) == {"tile_order": {"xcd_square": 32, "life_block": 16}}
     assert bench.parse_splits("order:32") == {"tile_order": {"xcd_square": 32, "life_block": 0}}
+
+
+def test_bench_dump_outputs_writes_the_mask_as_float32_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: one frame's mask as float32 (counts of unoccluded samples kept exactly); more than 64 MB (one
+    frame per rank) becomes a fixed seeded sample with its flat indices, the same on every run."""
+    import importlib.util, os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    mask = (np.arange(2160 * 3840) % 17).astype(np.uint8).reshape(2160, 3840)
+    assert bench.gather_masks(mask, None, 1, 0, False) is mask
+    bench.dump_outputs(str(tmp_path / "one"), mask, 0)
+    got = np.load(tmp_path / "one" / "shadow_mask.npy")
+    assert got.dtype == np.float32 and got.shape == mask.shape and (got == mask).all()
+    bench.dump_outputs(str(tmp_path / "other_rank"), mask, 1)
+    assert not (tmp_path / "other_rank").exists()
+    frames = np.stack([mask, mask[::-1], mask[:, ::-1]])
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), frames, 0)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["shadow_mask_sample.npy", "shadow_mask_sample_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    val, idx = np.load(tmp_path / "a" / files[0]), np.load(tmp_path / "a" / files[1])
+    assert val.dtype == np.float32 and idx.dtype == np.float64
+    assert (val == frames.reshape(-1)[idx.astype(np.int64)]).all()
+    assert (idx == np.load(tmp_path / "b" / files[1])).all() and (val == np.load(tmp_path / "b" / files[0])).all()

@@ -2,7 +2,8 @@
 
 tests/golden/obj_cases.json holds what the REFERENCE parser (External/zeux_objparser, compiled from
 its own source into oracle/_ref by oracle/Makefile) returns for a tricky OBJ text and for a list of
-number spellings; when oracle/_ref is present the same comparison is also made live on a generated mesh."""
+number spellings, and tests/golden/obj_cornell_ref.npz what it reads from a generated mesh; when oracle/_ref is present the
+mesh comparison is also made live."""
 import ctypes as C
 import json
 import os
@@ -76,17 +77,23 @@ def test_written_scene_round_trips_exactly(tmp_path):
     assert np.allclose(np.linalg.norm(n, axis=1), 1.0, atol=1e-5)        # generated normals (cpp:826-851)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref not built (needs /root/reference at build time)")
 def test_live_against_reference_parser(tmp_path):
-    ref = C.CDLL(REF)
-    ref.ref_obj_parse.argtypes = [C.c_char_p] + [C.POINTER(C.c_uint64)] * 4 + [C.c_void_p] * 4
+    """The cornell mesh's OBJ text: the product's reader against what the reference parser read from it (stored), and against
+    the parser itself when oracle/_ref is built."""
     sc = scenes.cornell()
     path = sc.write_obj(str(tmp_path / "c.obj"))
+    stored = np.load(os.path.join(HERE, "golden", "obj_cornell_ref.npz"))["corner_bits"]
+    verts, _, _, _ = api.obj_load(path)
+    assert verts.shape[0] == stored.shape[0]
+    assert (verts[:, :3].view(np.uint32) == stored).all()
+    if not os.path.exists(REF):
+        return
+    ref = C.CDLL(REF)
+    ref.ref_obj_parse.argtypes = [C.c_char_p] + [C.POINTER(C.c_uint64)] * 4 + [C.c_void_p] * 4
     sizes = [C.c_uint64(0) for _ in range(4)]
     assert ref.ref_obj_parse(path.encode(), *[C.byref(s) for s in sizes], None, None, None, None) == 0
     v = np.zeros(sizes[0].value, np.float32)
     f = np.zeros(sizes[3].value, np.int32)
     ref.ref_obj_parse(path.encode(), *[C.byref(s) for s in sizes], v.ctypes.data, None, None, f.ctypes.data)
     want = v.reshape(-1, 3)[f.reshape(-1, 3)[:, 0]]
-    verts, _, _, _ = api.obj_load(path)
     assert (verts[:, :3].view(np.uint32) == want.view(np.uint32)).all()

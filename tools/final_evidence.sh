@@ -7,19 +7,19 @@ cd $REPO
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/gputests.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/gputests.log; tail -3 $OUT/gputests.log
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -1 $OUT/smoke.log
 # the driver's command (headline + the secondary workloads in one line), then the long form with the counters saved
-timeout -k 10 500 python bench.py --steps 20 --warmup 5 > $OUT/bench_city4k_20_5.json 2> $OUT/bench_city4k_20_5.err; echo "bench 20/5 rc=$?"; cut -c1-260 $OUT/bench_city4k_20_5.json
-timeout -k 10 500 python bench.py --no-secondary --save-counters $OUT/counters_city_4k.json > $OUT/bench_city4k.json 2> $OUT/bench_city4k.err; echo "bench rc=$?"
+timeout -k 10 500 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_city4k_20_5.json 2> $OUT/bench_city4k_20_5.err; echo "bench 20/5 rc=$?"; cut -c1-260 $OUT/bench_city4k_20_5.json
+timeout -k 10 500 python bench.py --full --no-secondary --save-counters $OUT/counters_city_4k.json > $OUT/bench_city4k.json 2> $OUT/bench_city4k.err; echo "bench rc=$?"
 for CFG in courtyard_4k atrium_1080p cornell_256 city_4k_soft16 courtyard_4k_soft16 city_4k_soft16_pp courtyard_4k_soft16_pp city_4k_directional; do
-  timeout -k 10 500 python bench.py --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err; echo "bench $CFG rc=$?"; cut -c1-200 $OUT/bench_$CFG.json
+  timeout -k 10 500 python bench.py --full --config $CFG > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err; echo "bench $CFG rc=$?"; cut -c1-200 $OUT/bench_$CFG.json
 done
 # the two packet families side by side on the three scenes (same protocol, kernel forced)
 for CFG in city_4k courtyard_4k atrium_1080p; do for K in 3 8; do
-  timeout -k 10 300 python bench.py --config $CFG --kernel $K --no-secondary --no-pmc --no-cpu-baseline 2>/dev/null | python -c "
+  timeout -k 10 300 python bench.py --full --config $CFG --kernel $K --no-secondary --no-pmc --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$CFG', d['config']['kernel'], d['value'], 'Mrays/s', d['config']['ms_per_frame_gpu_median'], 'ms', d['roofline']['shader_clock_mhz'], 'MHz')" >> $OUT/packet_vs_wide_ab.log
 done; done; cat $OUT/packet_vs_wide_ab.log
 # multi-rank flow on the one device (2 and 4 ranks share GPU 0): striped frame
 for N in 2 4; do
-  RTS_BENCH_SINGLE_DEVICE=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 2955$N bench.py --gpus $N --steps 20 --warmup 5 > $OUT/bench_${N}rank_shared_device.json 2> $OUT/bench_${N}rank_shared_device.err; echo "bench $N ranks rc=$?"
+  RTS_BENCH_SINGLE_DEVICE=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 2955$N bench.py --full --gpus $N --steps 20 --warmup 5 > $OUT/bench_${N}rank_shared_device.json 2> $OUT/bench_${N}rank_shared_device.err; echo "bench $N ranks rc=$?"
 done
 # rocprofv3 kernel trace + stats of the same command (probes off: only the timed kernel runs)
 KID=$(python -c "import json; print({'shadowMaskPacketKernel<1,wide>': 8}.get(json.load(open('$OUT/bench_city4k.json'))['config']['kernel'], 3))")

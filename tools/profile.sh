@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--no-cpu-baseline --no-pmc --no-probes $*"
+ARGS="--full --no-cpu-baseline --no-pmc --no-probes $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $REPO/bench.py --steps 200 --warmup 20 $ARGS > $OUT/trace.json 2> $OUT/trace.err
 echo "trace rc=$?"
 i=0
@@ -21,7 +21,7 @@ for PMC in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_REQ_sum TCC
 done
 # calibration of FETCH_SIZE / WRITE_SIZE: same dispatch, 1-triangle BVH => reads = the 132.7 MB position stream
 for PMC in "FETCH_SIZE" "WRITE_SIZE"; do
-  rocprofv3 --pmc $PMC --output-format csv -d $OUT/calib_$PMC -- python3 $REPO/bench.py --steps 5 --warmup 2 --prewarm-seconds 0 --no-cpu-baseline --no-pmc --config calib_4k > $OUT/calib_$PMC.json 2> $OUT/calib_$PMC.err
+  rocprofv3 --pmc $PMC --output-format csv -d $OUT/calib_$PMC -- python3 $REPO/bench.py --steps 5 --warmup 2 --prewarm-seconds 0 --full --no-cpu-baseline --no-pmc --config calib_4k > $OUT/calib_$PMC.json 2> $OUT/calib_$PMC.err
   echo "calib $PMC rc=$?"
 done
 cd $REPO

@@ -2,7 +2,8 @@
     python tools/tile_shapes.py city_4k courtyard_4k atrium_1080p"""
 import ctypes as C, sys, os, time
 import numpy as np
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
 from raytracedshadows_amd import workloads
 import oracle
 _o = oracle._o
