@@ -138,6 +138,35 @@ int rts_bvh_build_device_ex(rts_ctx* ctx, const float* vertices, size_t vertex_f
                             const uint32_t* indices, uint32_t prim_count, int algorithm, uint32_t radius,
                             rts_vec4u* out_packed, size_t out_capacity_vec4, int install, float* build_ms);
 
+/* ---- refit: moving geometry keeps its tree (an extension: the reference's geometry is static) ----------------------------
+ * A refit keeps a stream's topology -- every tag and link word, hence every node index -- and recomputes its boxes and leaf
+ * data from new vertex positions for the same prim_count: leaf e0 = v1 - v0, e1 = v2 - v0 and tail v0 (.d = 0) as the builder
+ * writes them (BVHBuilder.cpp:324-341), inner bboxMin / bboxMax = the per-axis minimum / maximum over the vertices of the
+ * triangles in the node's subtree [i, link(i)) (END: N), taken in the total order of the order-preserving integer encoding
+ * (-0.0 < +0.0): no reduction order changes a byte, and with no -0.0 coordinate a refit with the vertices a stream was built
+ * from returns it unchanged.  Refused, with nothing changed: a NaN / Inf vertex referenced by the indices -> RTS_ERR_NONFINITE;
+ * an index outside vertex_floats, count_vec4 != 5 * prim_count - 2 or (device form) prim_count != the installed stream's ->
+ * RTS_ERR_INVALID_ARG; a stream that is not a pre-order binary tree with the reference's miss links -> RTS_ERR_BAD_BVH.
+ * Edges that overflow to +-Inf from finite vertices are not an error (as for a build).  DESIGN.md 4.9. */
+
+/* Host, in place on a caller's blob (any producer's): the CPU form, and the checker of the device form. */
+int rts_bvh_refit(const float* vertices, size_t vertex_floats, uint32_t stride_floats, const uint32_t* indices,
+                  uint32_t prim_count, rts_vec4u* packed, size_t count_vec4);
+/* The context's installed stream, on the device, in place.  vertices / indices: host or device pointers as in
+ * rts_bvh_build_device_ex.  out_packed (host, nullable) receives the refitted stream; refit_ms (nullable): device time;
+ * cost_ratio (nullable): the SAH cost proxy -- sum over inner nodes of surfaceArea(box) / surfaceArea(root), surfaceArea as
+ * BVHBuilder.cpp:24-28 -- after this refit, divided by the same for the stream as it was installed (taken at the first refit):
+ * how far the tree has degraded, for a renderer that decides when to rebuild instead (a heuristic: no exactness claim).
+ * The context ends as rts_ctx_set_bvh of the refitted bytes would leave it ("bvh_finite" / "bvh_ordered" / "bvh_enclosed"
+ * decided again; the private copy of kernel 8 refreshed in place, dropped with the split table when the flags no longer
+ * allow it, derived when they allow it again), except that the split table, the planned tile order, every option and the
+ * stream's allocation are kept: they hold node indices and tile coordinates, which a refit does not change.  What depends on
+ * the topology alone (the check, the schedule, the cost baseline) is derived at the first refit after an install and kept
+ * until the next one: a steady refit per frame allocates nothing.  Synchronous, default stream, like rts_bvh_build_device. */
+int rts_ctx_refit_bvh_device(rts_ctx* ctx, const float* vertices, size_t vertex_floats, uint32_t stride_floats,
+                             const uint32_t* indices, uint32_t prim_count, rts_vec4u* out_packed,
+                             size_t out_capacity_vec4, float* refit_ms, float* cost_ratio);
+
 /* ---- consumer: replaces the bind-group + dispatch of
  *      RayTracedShadowsApp::renderShadowMaskCompute (Source/RayTracedShadows.cpp:570-595) and the
  *      BVH upload (Source/RayTracedShadows.cpp:1039-1044) ---------------------- */
@@ -182,6 +211,7 @@ int rts_ctx_set_bvh(rts_ctx* ctx, const rts_vec4u* packed, size_t count_vec4);
  *   "lds_pad"       experiment: extra dynamic LDS bytes per one-wave packet workgroup (throttles occupancy; default 0)
  *   "wave_stats"    diagnostics, see rts_ctx_read_wave_stats
  *   "clock_probe"   diagnostics, see rts_ctx_read_clock_probe
+ *   "refit_treelet" nodes per workgroup of the device refit's treelet pass, 32..2048 (default 1024; speed only)
  *   "builder_scratch" set 0: release the working memory the GPU builders keep between builds; get: MiB held
  *   get only: "bvh_finite", "bvh_ordered", "bvh_enclosed" (what the installed stream allows: decided by one kernel over all
  *   nodes at upload / adoption), "wide_nodes", "wide_levels" (size of the private copy, 0 = none) */

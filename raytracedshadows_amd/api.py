@@ -120,6 +120,10 @@ _sig("rts_bvh_build_device", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_ui
      C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_float))
 _sig("rts_bvh_build_device_ex", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int,
      C.c_uint32, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_float))
+_sig("rts_bvh_refit", C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t)
+_sig("rts_ctx_refit_bvh_device", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32,
+     C.c_void_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float))
+_sig("rtsh_ctx_read_private_copy", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t))
 _sig("rts_device_count", C.c_int, C.POINTER(C.c_int))
 _sig("rts_ctx_create", C.c_int, C.c_int, C.POINTER(C.c_void_p))
 _sig("rts_ctx_destroy", C.c_int, C.c_void_p)
@@ -258,14 +262,9 @@ class BVHBuilder:
         return self
 
 
-def bvh_build_device(ctx, vertices, stride, indices, prim_count, install=False, want_packed=True, algorithm="sah",
-                     radius=0):
-    """BVH build on the GPU.  "sah" (default): BVHBuilder's own split rule for every node, level by level on the device
-    -- ``radius`` is then the range size above which the median split is used, 0 = the reference's 1 000 000.  Over the
-    Morton order: "ploc" (locally-ordered clustering, ``radius`` neighbours each way, 0 = 16), "lbvh" (Karras hierarchy),
-    "ploc_sah" (PLOC below 65 536 clusters, full-sweep SAH over the clusters on the host above).
-    ``vertices`` may be ``(device pointer, number of floats)`` and ``indices`` a device pointer: geometry that already lives on
-    the context's device is used in place.  Returns (packed or None, device milliseconds)."""
+def _geometry(vertices, stride, indices, prim_count):
+    """The geometry arguments of the device entries: ``vertices`` an array or ``(device pointer, number of floats)``,
+    ``indices`` an array or a device pointer.  Returns (vertex pointer, number of floats, index pointer, arrays to keep alive)."""
     import numbers
 
     def device_pointer(v):                           # a plain or numpy integer, or a ctypes pointer value
@@ -291,6 +290,18 @@ def bvh_build_device(ctx, vertices, stride, indices, prim_count, install=False, 
         if indices.ndim == 0 or indices.size < 3 * prim_count:       # C reads 3 * prim_count words from this array
             raise ValueError(f"indices: {indices.size} entries for {prim_count} triangles")
         i_ptr = _ptr(indices)
+    return v_ptr, v_floats, i_ptr, (vertices, indices)
+
+
+def bvh_build_device(ctx, vertices, stride, indices, prim_count, install=False, want_packed=True, algorithm="sah",
+                     radius=0):
+    """BVH build on the GPU.  "sah" (default): BVHBuilder's own split rule for every node, level by level on the device
+    -- ``radius`` is then the range size above which the median split is used, 0 = the reference's 1 000 000.  Over the
+    Morton order: "ploc" (locally-ordered clustering, ``radius`` neighbours each way, 0 = 16), "lbvh" (Karras hierarchy),
+    "ploc_sah" (PLOC below 65 536 clusters, full-sweep SAH over the clusters on the host above).
+    ``vertices`` may be ``(device pointer, number of floats)`` and ``indices`` a device pointer: geometry that already lives on
+    the context's device is used in place.  Returns (packed or None, device milliseconds)."""
+    v_ptr, v_floats, i_ptr, _keep = _geometry(vertices, stride, indices, prim_count)
     n = packed_count(prim_count)
     packed = np.zeros((max(n, 1), 4), dtype=np.uint32) if want_packed else None
     ms = C.c_float(0)
@@ -299,6 +310,42 @@ def bvh_build_device(ctx, vertices, stride, indices, prim_count, install=False, 
                                         algo, radius, _ptr(packed) if want_packed else None, n if want_packed else 0,
                                         int(install), C.byref(ms)), "rts_bvh_build_device_ex")
     return (packed[:n] if want_packed else None), float(ms.value)
+
+
+def bvh_refit(packed, vertices, stride, indices, prim_count):
+    """rts_bvh_refit on the host: a new array holding ``packed``'s topology with boxes and leaf data recomputed from the new
+    vertices (include/rts.h).  Host arrays only: ``(device pointer, floats)`` geometry raises ValueError --
+    the device form is :func:`bvh_refit_device`."""
+    v_ptr, v_floats, i_ptr, _keep = _geometry(vertices, stride, indices, prim_count)
+    if isinstance(vertices, tuple) or not isinstance(_keep[1], np.ndarray):
+        raise ValueError("bvh_refit is the host form: vertices and indices must be host arrays (see bvh_refit_device)")
+    out = np.array(np.asarray(packed, dtype=np.uint32).reshape(-1, 4), dtype=np.uint32, order="C")
+    _check(_lib.rts_bvh_refit(v_ptr, v_floats, stride, i_ptr, prim_count, _ptr(out), out.shape[0]), "rts_bvh_refit")
+    return out
+
+
+def bvh_refit_device(ctx, vertices, stride, indices, prim_count, want_packed=False):
+    """rts_ctx_refit_bvh_device: the context's installed stream refitted in place on the device (geometry as in
+    :func:`bvh_build_device`).  Returns (packed or None, device milliseconds, cost_ratio)."""
+    v_ptr, v_floats, i_ptr, _keep = _geometry(vertices, stride, indices, prim_count)
+    n = packed_count(prim_count)
+    packed = np.zeros((max(n, 1), 4), dtype=np.uint32) if want_packed else None
+    ms, ratio = C.c_float(0), C.c_float(0)
+    _check(_lib.rts_ctx_refit_bvh_device(ctx.handle, v_ptr, v_floats, stride, i_ptr, prim_count,
+                                         _ptr(packed) if want_packed else None, n if want_packed else 0,
+                                         C.byref(ms), C.byref(ratio)), "rts_ctx_refit_bvh_device")
+    return (packed[:n] if want_packed else None), float(ms.value), float(ratio.value)
+
+
+def read_private_copy(ctx):
+    """rtsh_ctx_read_private_copy (diagnostics): the private copy of kernel 8 as bytes -- wide nodes, triangle records,
+    parents -- or an empty array when the stream has none."""
+    size = C.c_size_t(0)
+    _check(_lib.rtsh_ctx_read_private_copy(ctx.handle, None, 0, C.byref(size)), "rtsh_ctx_read_private_copy")
+    out = np.zeros(size.value, np.uint8)
+    if size.value:
+        _check(_lib.rtsh_ctx_read_private_copy(ctx.handle, _ptr(out), out.size, C.byref(size)), "rtsh_ctx_read_private_copy")
+    return out
 
 
 class ShadowContext:

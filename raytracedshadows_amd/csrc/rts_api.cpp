@@ -2,7 +2,9 @@
 // pointers and (a) the host BVH producer, (b) the HIP traversal kernels.
 #include "../../include/rts.h"
 #include "bvh_builder.h"
+#include "bvh_refit.h"
 #include "rts_device.h"
+#include "rts_refit.h"
 
 #include <algorithm>
 #include <chrono>
@@ -79,6 +81,22 @@ struct rts_ctx {
     };
     const Planning* planning = nullptr;
     uint32_t lastBlocksX = 0, lastBlocksY = 0; int lastVariant = 0; bool lastGrid2d = false;   // of the last mask dispatch
+    // refit (rts_ctx_refit_bvh_device): what depends on the installed stream's topology alone is derived at its first refit
+    // and kept until the next install (rts_ctx_set_bvh, the GPU builders' install) -- a refit per frame then allocates
+    // nothing and reads back one status block
+    struct Refit {
+        bool valid = false;                  // topology verdict and schedule below belong to the installed stream
+        int topology = RTS_OK;               // RTS_ERR_BAD_BVH: not a pre-order tree with the reference's miss links
+        uint32_t treelet = 0;                // treelet size the schedule was made for
+        uint32_t nRoots = 0, nTop = 0, nLevels = 0;
+        void* d_sched = nullptr; size_t schedCap = 0;      // treelet roots, top nodes by height, level offsets
+        void* d_geom = nullptr; size_t geomCap = 0;        // staging of host-pointer vertices / indices
+        rts::RefitStatus* d_status = nullptr;
+        bool haveBaseline = false;           // cost proxy of the stream as installed (taken before the first refit's writes)
+        double baseline = 0;
+        hipEvent_t ev[2] = { nullptr, nullptr };
+    } refit;
+    int refitTreelet = 1024;                 // option "refit_treelet": nodes per treelet workgroup (speed only)
 };
 
 namespace {
@@ -86,6 +104,7 @@ namespace {
 inline int hipStatus(hipError_t e) { return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e; }
 }
 namespace rts {   // rts_wide.hip
+int deviceOf(const void* p);            // rts_lbvh.hip
 hipError_t validateStreamDevice(const void* d_packed, uint32_t P, uint32_t* d_word, uint32_t* flagsOut);
 size_t wideScratchBytes(uint32_t P);
 hipError_t buildWideDevice(const void* d_packed, uint32_t P, void* d_wide, void* d_tris, void* d_parents, void* d_scratch,
@@ -148,6 +167,8 @@ int fillParams(rts_ctx* ctx, TraceParams& p) {
     return RTS_OK;
 }
 
+int deriveWideCopy(rts_ctx* c);
+
 // The stream in c->d_bvh has just been installed (uploaded or adopted): what the kernels may assume about it is decided
 // on the device (one kernel over all nodes), then the private copy of the wide kernel is derived from it.  A stream that
 // breaks the layout rules is refused (RTS_ERR_BAD_BVH) and the context is left without a BVH.
@@ -162,19 +183,91 @@ int finishInstall(rts_ctx* c, bool freeOnRefusal) {
     c->bvhFinite = !(flags & 2u);
     c->bvhOrdered = !(flags & 4u);
     c->bvhEnclosed = !(flags & 8u);
+    return deriveWideCopy(c);
+}
+
+// what the stream's flags allow: a private copy of kernel 8 (byte offsets inside it are 32-bit: 192 bytes per triangle)
+bool wideAllowed(const rts_ctx* c) {
+    return c->bvhFinite && c->bvhOrdered && c->bvhEnclosed && c->P >= 2 && c->P <= (1u << 24);
+}
+
+// the private copy of kernel 8, derived in full from the installed stream (when the option and the flags allow one)
+int deriveWideCopy(rts_ctx* c) {
     c->wideCount = 0; c->wideLevels = 0;
-    // (byte offsets inside the private copy are 32-bit: 192 bytes per triangle)
-    if (!c->wideCopy || !c->bvhFinite || !c->bvhOrdered || !c->bvhEnclosed || c->P < 2 || c->P > (1u << 24)) return RTS_OK;
+    if (!c->wideCopy || !wideAllowed(c)) return RTS_OK;
     int s = ensure(&c->d_wide, &c->wideCap, (size_t)c->P * 200 + 256);
     c->d_tris = s == RTS_OK ? (char*)c->d_wide + (size_t)c->P * 128 : nullptr;
     c->d_parents = s == RTS_OK ? (char*)c->d_wide + (size_t)c->P * 192 : nullptr;
     void* scratch = s == RTS_OK ? rts_ctx_scratch(c, rts::wideScratchBytes(c->P)) : nullptr;
     if (!scratch) return RTS_OK;                      // no memory for the copy: the stackless kernels need none
     // (trees deeper than 512 levels -- chains of single-triangle splits -- keep the stackless kernels)
-    e = rts::buildWideDevice(c->d_bvh, c->P, c->d_wide, c->d_tris, c->d_parents, scratch, 512, &c->wideCount, &c->wideLevels);
+    hipError_t e = rts::buildWideDevice(c->d_bvh, c->P, c->d_wide, c->d_tris, c->d_parents, scratch, 512, &c->wideCount, &c->wideLevels);
     // a failure here only costs the private copy: the stream itself is installed and valid, the stackless kernels need
     // nothing else.  (Returning the error would leave the caller of the adopt path freeing a stream the context still holds.)
     if (e != hipSuccess) { c->wideCount = 0; c->wideLevels = 0; (void)hipGetLastError(); }
+    return RTS_OK;
+}
+
+// a new stream is being installed: what the refit derived from the old one goes (its buffers stay for reuse)
+void dropRefit(rts_ctx* c) {
+    c->refit.valid = false;
+    c->refit.haveBaseline = false;
+}
+
+// The refit schedule of the installed stream, from its tag and link words (read back once): the topology check of the host
+// form, then the treelet roots -- nodes whose subtree [i, end(i)) has at most T nodes and whose parent's has more -- and the
+// inner nodes above them, grouped by height (a treelet root has height 0).
+int refitSchedule(rts_ctx* c, uint32_t T) {
+    rts_ctx::Refit& R = c->refit;
+    const uint32_t P = c->P, N = 2 * P - 1;
+    std::vector<uint32_t> sched;
+    uint32_t nRoots = 0, nTop = 0, nLevels = 0;
+    try {
+        std::vector<rts_vec4u> nodes((size_t)2 * N);
+        RTS_HIP(hipMemcpy(nodes.data(), c->d_bvh, nodes.size() * 16, hipMemcpyDeviceToHost));
+        std::vector<uint32_t> end;
+        R.topology = rts::refitTopology(nodes.data(), P, &end);
+        R.valid = true; R.treelet = T; R.nRoots = R.nTop = R.nLevels = 0;
+        if (R.topology != RTS_OK) return RTS_OK;
+        std::vector<uint32_t> parent(N, rts::kRefitEnd), height(N, 0);
+        for (uint32_t i = 0; i < N; ++i)
+            if (nodes[2 * (size_t)i].d == rts::kRefitEnd) { parent[i + 1] = i; parent[nodes[2 * (size_t)i + 3].d] = i; }
+        std::vector<uint32_t> roots, top;
+        for (uint32_t i = 0; i < N; ++i) {
+            const uint32_t size = end[i] - i;
+            if (size > T) top.push_back(i);
+            else if (i == 0 || end[parent[i]] - parent[i] > T) roots.push_back(i);
+        }
+        for (size_t t = top.size(); t-- > 0;) {          // children before parents: reverse index order
+            const uint32_t i = top[t], right = nodes[2 * (size_t)i + 3].d;
+            height[i] = 1 + std::max(height[i + 1], height[right]);
+            nLevels = std::max(nLevels, height[i]);
+        }
+        std::vector<uint32_t> levelOff(nLevels + 1, 0);
+        for (uint32_t i : top) ++levelOff[height[i]];     // counts per height 1..H at [h], then exclusive offsets at [h - 1]
+        for (uint32_t h = 1, run = 0; h <= nLevels; ++h) { const uint32_t n = levelOff[h]; levelOff[h - 1] = run; run += n; }
+        if (nLevels) levelOff[nLevels] = (uint32_t)top.size();
+        std::vector<uint32_t> byHeight(top.size());
+        std::vector<uint32_t> fill(levelOff.begin(), levelOff.end());
+        for (uint32_t i : top) byHeight[fill[height[i] - 1]++] = i;
+        nRoots = (uint32_t)roots.size(); nTop = (uint32_t)top.size();
+        sched.reserve(roots.size() + top.size() + levelOff.size());
+        sched.insert(sched.end(), roots.begin(), roots.end());
+        sched.insert(sched.end(), byHeight.begin(), byHeight.end());
+        sched.insert(sched.end(), levelOff.begin(), levelOff.end());
+    } catch (...) {
+        R.valid = false;
+        return RTS_ERR_CAPACITY;                          // no exception crosses the C ABI
+    }
+    R.valid = false;                                      // (until the schedule is on the device)
+    int s = ensure(&R.d_sched, &R.schedCap, sched.size() * 4);
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(R.d_sched, sched.data(), sched.size() * 4, hipMemcpyHostToDevice));
+    if (!R.d_status) RTS_HIP(hipMalloc((void**)&R.d_status, sizeof(rts::RefitStatus)));
+    for (hipEvent_t& e : R.ev) if (!e) RTS_HIP(hipEventCreate(&e));
+    if (rts::refitLdsBytes(T) > 65536) RTS_HIP(rts::refitSetLds(T));
+    R.nRoots = nRoots; R.nTop = nTop; R.nLevels = nLevels;
+    R.valid = true;
     return RTS_OK;
 }
 
@@ -273,6 +366,10 @@ int rts_ctx_destroy(rts_ctx* c) {
     if (c->d_word) (void)hipFree(c->d_word);
     if (c->d_clockProbe) (void)hipFree(c->d_clockProbe);
     if (c->d_pieceClock) (void)hipFree(c->d_pieceClock);
+    if (c->refit.d_sched) (void)hipFree(c->refit.d_sched);
+    if (c->refit.d_geom) (void)hipFree(c->refit.d_geom);
+    if (c->refit.d_status) (void)hipFree(c->refit.d_status);
+    for (hipEvent_t e : c->refit.ev) if (e) (void)hipEventDestroy(e);
     clearSplits(c);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -295,6 +392,7 @@ int rts_ctx_set_bvh(rts_ctx* c, const rts_vec4u* packed, size_t count) {
     hipError_t e = hipMemcpy(d, packed, count * 16, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); return hipStatus(e); }
     c->d_bvh = d; c->bvhVec4 = count; c->P = P;
+    dropRefit(c);
     clearSplits(c);                      // (a split table holds node indices of the stream it was planned on)
     if (c->tileOrderPlanned) (void)rts_ctx_set_tile_order(c, nullptr, 0);   // (... a planned tile order the lives of its tiles)
     return finishInstall(c, true);       // finite / ordered / enclosed are decided on the device; private wide copy
@@ -311,6 +409,10 @@ int rts_ctx_set_option(rts_ctx* c, const char* key, int value) {
     if (!strcmp(key, "lds_pad")) { if (value < 0 || value > 65536) return RTS_ERR_INVALID_ARG; c->ldsPad = value; return RTS_OK; }
     if (!strcmp(key, "packet_share")) { if (value < 0 || value > 16) return RTS_ERR_INVALID_ARG; c->packetShare = value; return RTS_OK; }
     if (!strcmp(key, "wide_copy")) { c->wideCopy = value ? 1 : 0; return RTS_OK; }      // takes effect at the next upload / build
+    if (!strcmp(key, "refit_treelet")) {            // nodes per treelet workgroup of the device refit (LDS: 52 bytes per node)
+        if (value < 32 || value > 2048) return RTS_ERR_INVALID_ARG;
+        c->refitTreelet = value; return RTS_OK;
+    }
     if (!strcmp(key, "builder_scratch")) {          // 0: release the working memory the GPU builders keep between builds
         if (value != 0) return RTS_ERR_INVALID_ARG;
         RTS_HIP(hipSetDevice(c->device));
@@ -368,6 +470,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "bvh_ordered")) { *value = c->bvhOrdered ? 1 : 0; return RTS_OK; }
     if (!strcmp(key, "bvh_enclosed")) { *value = c->bvhEnclosed ? 1 : 0; return RTS_OK; }
     if (!strcmp(key, "wide_copy")) { *value = c->wideCopy; return RTS_OK; }
+    if (!strcmp(key, "refit_treelet")) { *value = c->refitTreelet; return RTS_OK; }
     if (!strcmp(key, "builder_scratch")) { *value = (int)(c->scratchBytes >> 20); return RTS_OK; }     // MiB held
     if (!strcmp(key, "wide_lane")) { *value = c->wideLane; return RTS_OK; }
     if (!strcmp(key, "soft_split")) { *value = c->softSplit; return RTS_OK; }
@@ -699,11 +802,92 @@ int rts_ctx_adopt_device_bvh(rts_ctx* c, void* d_packed, size_t count, uint32_t 
     if (c->d_bvh) { void* old = c->d_bvh; c->d_bvh = nullptr; c->bvhVec4 = 0; c->P = 0; RTS_HIP(hipFree(old)); }
     c->d_bvh = d_packed;
     c->bvhVec4 = count; c->P = P;
+    dropRefit(c);
     clearSplits(c);
     if (c->tileOrderPlanned) (void)rts_ctx_set_tile_order(c, nullptr, 0);
     // the same checks as for an uploaded stream, on the device: layout, finiteness (edges of finite vertices can
     // overflow), box order, enclosure.  A refused stream stays the caller's to free.
     return finishInstall(c, false);
+}
+
+int rts_ctx_refit_bvh_device(rts_ctx* c, const float* vertices, size_t vertex_floats, uint32_t stride, const uint32_t* indices,
+                             uint32_t P, rts_vec4u* out_packed, size_t out_cap, float* refit_ms, float* cost_ratio) {
+    if (!c || !vertices || !indices || P == 0 || stride < 3) return RTS_ERR_INVALID_ARG;
+    if (!c->d_bvh) return RTS_ERR_NO_BVH;
+    if (P != c->P) return RTS_ERR_INVALID_ARG;
+    if (out_packed && out_cap < c->bvhVec4) return RTS_ERR_CAPACITY;
+    RTS_HIP(hipSetDevice(c->device));
+    // geometry on the context's device is used where it lies (its indices are checked by the check kernel); host geometry
+    // is staged in a buffer the context keeps
+    const int vertsOn = rts::deviceOf(vertices), idxOn = rts::deviceOf(indices);
+    if ((vertsOn >= 0 && vertsOn != c->device) || (idxOn >= 0 && idxOn != c->device)) return RTS_ERR_INVALID_ARG;
+    if (idxOn < 0)
+        for (size_t i = 0; i < (size_t)3 * P; ++i)
+            if ((size_t)indices[i] * stride + 3 > vertex_floats) return RTS_ERR_INVALID_ARG;
+    rts_ctx::Refit& R = c->refit;
+    const uint32_t T = (uint32_t)c->refitTreelet;
+    if (!R.valid || (R.topology == RTS_OK && R.treelet != T)) { int s = refitSchedule(c, T); if (s != RTS_OK) return s; }
+    if (R.topology != RTS_OK) return R.topology;
+    const size_t vBytes = vertsOn >= 0 ? 0 : ((vertex_floats * 4 + 255) & ~(size_t)255), iBytes = idxOn >= 0 ? 0 : (size_t)P * 12;
+    if (vBytes + iBytes) { int s = ensure(&R.d_geom, &R.geomCap, vBytes + iBytes); if (s != RTS_OK) return s; }
+    const float* d_verts = vertices;
+    const uint32_t* d_idx = indices;
+    if (vertsOn < 0) { RTS_HIP(hipMemcpy(R.d_geom, vertices, vertex_floats * 4, hipMemcpyHostToDevice)); d_verts = (const float*)R.d_geom; }
+    if (idxOn < 0) { d_idx = (const uint32_t*)((char*)R.d_geom + vBytes); RTS_HIP(hipMemcpy((void*)d_idx, indices, iBytes, hipMemcpyHostToDevice)); }
+
+    const uint32_t* sched = (const uint32_t*)R.d_sched;
+    rts::RefitLaunch L{};
+    L.d_packed = c->d_bvh; L.P = P;
+    L.verts = d_verts; L.vertexFloats = vertex_floats; L.stride = stride; L.indices = d_idx;
+    L.roots = sched; L.nRoots = R.nRoots; L.treelet = T;
+    L.top = sched + R.nRoots; L.levelOff = sched + R.nRoots + R.nTop; L.nLevels = R.nLevels;
+    L.d_wide = c->d_wide; L.wideCount = c->wideCount; L.d_tris = c->d_tris; L.d_parents = (const uint32_t*)c->d_parents;
+    L.status = R.d_status;
+    L.baseline = !R.haveBaseline;
+    RTS_HIP(hipEventRecord(R.ev[0], nullptr));
+    RTS_HIP(rts::refitLaunch(L));
+    RTS_HIP(hipEventRecord(R.ev[1], nullptr));
+    rts::RefitStatus st{};
+    RTS_HIP(hipMemcpy(&st, R.d_status, sizeof(st), hipMemcpyDeviceToHost));      // (the one read-back of a steady refit)
+    if (L.baseline) { R.baseline = st.baseRootArea > 0 ? st.baseCost / st.baseRootArea : 0.0; R.haveBaseline = true; }
+    if (st.err) return (st.err & rts::REFIT_ERR_INDEX) ? RTS_ERR_INVALID_ARG : RTS_ERR_NONFINITE;   // nothing was written
+
+    // the context as rts_ctx_set_bvh of the refitted bytes would leave it -- but the split table, the tile order, the options,
+    // the allocation and the cost baseline are kept (they hold node indices and tile coordinates only)
+    const bool allowedBefore = wideAllowed(c);
+    c->bvhFinite = !(st.valid & 2u);
+    c->bvhOrdered = !(st.valid & 4u);
+    c->bvhEnclosed = !(st.valid & 8u);
+    if (c->wideCount && !wideAllowed(c)) {          // edges overflowed: the copy (refreshed above) goes, and the table that needs it
+        c->wideCount = 0; c->wideLevels = 0;
+        clearSplits(c);
+    } else if (!c->wideCount && !allowedBefore && wideAllowed(c)) {
+        int s = deriveWideCopy(c);
+        if (s != RTS_OK) return s;
+    }
+    if (out_packed) RTS_HIP(hipMemcpy(out_packed, c->d_bvh, c->bvhVec4 * 16, hipMemcpyDeviceToHost));
+    if (refit_ms) RTS_HIP(hipEventElapsedTime(refit_ms, R.ev[0], R.ev[1]));
+    if (cost_ratio) {
+        const double now = st.rootArea > 0 ? st.cost / st.rootArea : 0.0;
+        *cost_ratio = R.baseline > 0 ? (float)(now / R.baseline) : 1.0f;
+    }
+    return RTS_OK;
+}
+
+// Diagnostics (tests): the private copy of kernel 8 -- wide_nodes x 128 bytes of wide nodes, P x 64 bytes of triangle records,
+// (2P - 1) x 4 bytes of parents, in that order; *bytes = its size (0: no copy).  `out` NULL: the size only.
+int rtsh_ctx_read_private_copy(rts_ctx* c, void* out, size_t capacity, size_t* bytes) {
+    if (!c || !bytes) return RTS_ERR_INVALID_ARG;
+    const size_t wideB = (size_t)c->wideCount * 128, trisB = c->wideCount ? (size_t)c->P * 64 : 0,
+                 parB = c->wideCount ? ((size_t)2 * c->P - 1) * 4 : 0;
+    *bytes = wideB + trisB + parB;
+    if (!out || !*bytes) return RTS_OK;
+    if (capacity < *bytes) return RTS_ERR_CAPACITY;
+    RTS_HIP(hipSetDevice(c->device));
+    RTS_HIP(hipMemcpy(out, c->d_wide, wideB, hipMemcpyDeviceToHost));
+    RTS_HIP(hipMemcpy((char*)out + wideB, c->d_tris, trisB, hipMemcpyDeviceToHost));
+    RTS_HIP(hipMemcpy((char*)out + wideB + trisB, c->d_parents, parB, hipMemcpyDeviceToHost));
+    return RTS_OK;
 }
 
 // used by the harness (rts_primary.hip): the device copy of the packed stream, NULL before rts_ctx_set_bvh

@@ -920,12 +920,17 @@ __global__ void checkIndicesKernel(const uint32_t* idx, uint32_t n, uint32_t str
     if (i < n && (size_t)idx[i] * stride + 3 > vertexFloats) flags[1] = 1;
 }
 
+} // namespace
+namespace rts {
 // ordinal of the device a pointer's memory lives on, -1 for host memory (pageable, pinned or managed: those are copied)
+// (also used by the refit, rts_api.cpp)
 int deviceOf(const void* p) {
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return -1; }
     return a.type == hipMemoryTypeDevice ? a.device : -1;
 }
+} // namespace rts
+namespace {
 
 struct DeviceArena {            // working buffers: carved out of the context's scratch buffer; what does not fit (and what
     char* slab = nullptr;       // must outlive the build) is a hipMalloc of its own, freed whatever path leaves the function
@@ -992,7 +997,7 @@ extern "C" int rts_bvh_build_device_ex(rts_ctx* ctx, const float* vertices, size
     hipError_t e0 = hipSetDevice(rts_ctx_device_ordinal(ctx));
     if (e0 != hipSuccess) return RTS_ERR_HIP + (int)e0;
     // geometry that already lives on the context's device is used where it lies (no copy; its indices are checked by a kernel)
-    const int vertsOn = deviceOf(vertices), idxOn = deviceOf(indices);
+    const int vertsOn = rts::deviceOf(vertices), idxOn = rts::deviceOf(indices);
     if ((vertsOn >= 0 && vertsOn != rts_ctx_device_ordinal(ctx)) || (idxOn >= 0 && idxOn != rts_ctx_device_ordinal(ctx))) return RTS_ERR_INVALID_ARG;
     if (idxOn < 0)
         for (size_t i = 0; i < (size_t)3 * P; ++i)

@@ -224,13 +224,18 @@ __global__ void emitWideKernel(StreamView s, const uint32_t* parents, const uint
 
 // flagsOut: bit 0 structure broken, 1 non-finite float, 2 unordered box, 3 not an enclosing pre-order tree (see validateKernel)
 // (default stream; the copies are synchronous)
-hipError_t validateStreamDevice(const void* d_packed, uint32_t P, uint32_t* d_word, uint32_t* flagsOut) {
+// ... the same, asynchronous on the default stream: the flags stay in d_word (the refit reads them with its own status)
+hipError_t validateStreamAsync(const void* d_packed, uint32_t P, uint32_t* d_word) {
     StreamView s{ (const uint32_t*)d_packed, P, 2 * P - 1 };
-    hipError_t e = hipMemset(d_word, 0, 4);
+    hipError_t e = hipMemsetAsync(d_word, 0, 4, nullptr);
     if (e != hipSuccess) return e;
     const uint64_t threads = (uint64_t)s.N + P;
     hipLaunchKernelGGL(validateKernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, nullptr, s, d_word);
-    e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t validateStreamDevice(const void* d_packed, uint32_t P, uint32_t* d_word, uint32_t* flagsOut) {
+    hipError_t e = validateStreamAsync(d_packed, P, d_word);
     if (e != hipSuccess) return e;
     return hipMemcpy(flagsOut, d_word, 4, hipMemcpyDeviceToHost);
 }

@@ -1,0 +1,286 @@
+"""GPU: the device refit (rts_ctx_refit_bvh_device) against the host refit, and the context it leaves behind.
+
+The host form (rts_bvh_refit, tests/test_refit.py) is the checker: the device form must produce the same bytes for any
+geometry, from host or device pointers.  After a refit the context must trace exactly as the oracle does over the refitted
+stream, with the split table, the planned tile order and the private copy of kernel 8 carried over where the flags allow."""
+import numpy as np
+import pytest
+
+import oracle
+from raytracedshadows_amd import api, scenes, workloads
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = api.ShadowContext(0)
+    yield c
+    c.close()
+
+
+def _soup(n, seed):
+    rs = np.random.RandomState(seed)
+    c = rs.random_sample((n, 1, 3)) * 40
+    return (c + (rs.random_sample((n, 3, 3)) - 0.5) * 1.5).astype(np.float32).reshape(-1, 3), np.arange(3 * n, dtype=np.uint32)
+
+
+def _wave(v, phase, amp=None):
+    """The vertices of one animation frame: a travelling wave in y (stride 3 or 8)."""
+    w = v.copy()
+    span = float(np.ptp(v[:, 0])) + 1.0
+    amp = 0.01 * span if amp is None else amp
+    w[:, 1] += (amp * np.sin(6.0 * v[:, 0] / span + phase) * np.cos(4.0 * v[:, 2] / span - phase)).astype(np.float32)
+    return w
+
+
+def _on_device(ctx, a):
+    d = ctx.malloc(a.nbytes)
+    ctx.h2d(d, np.ascontiguousarray(a))
+    return d
+
+
+def _state(ctx):
+    return {k: ctx.get_option(k) for k in ("bvh_finite", "bvh_ordered", "bvh_enclosed", "wide_nodes", "wide_levels")}
+
+
+def _mask_bad(ctx, wl, packed, light=None, d_pos=None, d_mask=None):
+    """Mask bytes that differ from the oracle traced over `packed` (device pointers when given, else the host entry)."""
+    light = wl.light if light is None else light
+    want, _, _ = oracle.shadow_mask(packed, wl.constants.as_array(), oracle.light_from_product(light, wl.constants),
+                                    wl.positions, wl.W, wl.H)
+    if d_pos is None:
+        got = ctx.trace_shadow_mask(wl.constants, wl.positions, wl.W, wl.H, light=light)
+    else:
+        ctx.h2d(d_mask, np.full(wl.W * wl.H, 77, np.uint8))
+        ctx.trace_shadow_mask_device(wl.constants, d_pos, wl.W, wl.H, d_mask, light=light)
+        ctx.synchronize()
+        got = np.empty((wl.H, wl.W), np.uint8)
+        ctx.d2h(got, d_mask)
+    return int((got != want).sum())
+
+
+def _geometry(name):
+    if name.startswith("soup"):
+        v, idx = _soup(int(name[4:]), int(name[4:]) % 97)
+        return v, 3, idx
+    v, idx = scenes.SCENES[name]().flat()
+    return v, 8, idx
+
+
+@pytest.mark.parametrize("name", ["soup1", "soup2", "soup3", "soup17", "soup1000", "soup30011", "soup150001",
+                                  "cornell", "atrium", "city", "courtyard"])
+def test_device_refit_equals_host_refit(ctx, name):
+    v, stride, idx = _geometry(name)
+    P = idx.size // 3
+    packed, _ = api.bvh_build_device(ctx, v, stride, idx, P, install=True)
+    # the build's own vertices: the stream comes back unchanged (no -0.0 in these meshes)
+    assert not (v.view(np.uint32) == 0x80000000).any()
+    same, ms, ratio = api.bvh_refit_device(ctx, v, stride, idx, P, want_packed=True)
+    assert np.array_equal(same, packed) and abs(ratio - 1.0) < 1e-5 and ms > 0
+    d_v, d_i = _on_device(ctx, v), _on_device(ctx, idx)
+    try:
+        for frame, (verts, ind) in enumerate([(v, idx), ((d_v, v.size), idx), (v, d_i), ((d_v, v.size), d_i)]):
+            w = _wave(v, 0.7 * (frame + 1))
+            if isinstance(verts, tuple):
+                ctx.h2d(d_v, w)
+                verts = (d_v, v.size)
+            else:
+                verts = w
+            got, _, _ = api.bvh_refit_device(ctx, verts, stride, ind, P, want_packed=True)
+            want = api.bvh_refit(packed, w, stride, idx, P)
+            assert np.array_equal(got, want), f"frame {frame}: {int((got != want).any(1).sum())} vec4 differ"
+    finally:
+        ctx.free(d_v)
+        ctx.free(d_i)
+
+
+@pytest.mark.parametrize("algo", ["lbvh", "ploc", "ploc_sah", "sah"])
+def test_refit_of_every_builders_stream_is_the_identity(ctx, algo):
+    v, idx = _soup(30011, 5)
+    packed, _ = api.bvh_build_device(ctx, v, 3, idx, 30011, install=True, algorithm=algo)
+    got, _, ratio = api.bvh_refit_device(ctx, v, 3, idx, 30011, want_packed=True)
+    assert np.array_equal(got, packed) and abs(ratio - 1.0) < 1e-5
+
+
+@pytest.mark.parametrize("name", ["atrium", "soup30011"])
+def test_private_copy_after_refit_equals_a_fresh_install(ctx, name):
+    v, stride, idx = _geometry(name)
+    P = idx.size // 3
+    packed = api.BVHBuilder().build(v, stride, idx, P).m_packedNodes
+    ctx.set_bvh(packed)
+    assert ctx.get_option("wide_nodes") > 0
+    for phase in (0.5, 1.9):
+        got, _, _ = api.bvh_refit_device(ctx, _wave(v, phase), stride, idx, P, want_packed=True)
+    with api.ShadowContext(0) as fresh:
+        fresh.set_bvh(got)
+        assert _state(ctx) == _state(fresh)
+        a, b = api.read_private_copy(ctx), api.read_private_copy(fresh)
+        assert a.size > 0 and np.array_equal(a, b)
+
+
+@pytest.fixture(scope="module")
+def small():
+    return {"cornell": workloads.prepare("cornell", 256, 256, via_obj=False),
+            "atrium": workloads.prepare("atrium", 640, 360, via_obj=False)}
+
+
+@pytest.mark.parametrize("name", ["cornell", "atrium"])
+def test_masks_after_refit_every_kernel(ctx, small, name):
+    wl = small[name]
+    ctx.set_bvh(wl.packed)
+    got, _, _ = api.bvh_refit_device(ctx, _wave(wl.vertices, 2.3), 8, wl.indices, wl.prim_count, want_packed=True)
+    assert ctx.get_option("wide_nodes") > 0
+    try:
+        for kernel in (-1, 3, 7, 8, 9):
+            ctx.set_option("kernel", kernel)
+            assert _mask_bad(ctx, wl, got) == 0, f"kernel {kernel}"
+        # two interleaved stripes, and 16 jittered light samples
+        want, _, _ = oracle.shadow_mask(got, wl.constants.as_array(), oracle.light_from_product(wl.light, wl.constants),
+                                        wl.positions, wl.W, wl.H)
+        d_pos, d_mask = _on_device(ctx, wl.positions), ctx.malloc(wl.W * wl.H)
+        ctx.set_option("kernel", -1)
+        ctx.h2d(d_mask, np.full(wl.W * wl.H, 77, np.uint8))
+        for stripe in range(2):
+            ctx.trace_shadow_mask_stripes_device(wl.constants, d_pos, wl.W, wl.H, d_mask, 32, 2, stripe, light=wl.light)
+        ctx.synchronize()
+        m = np.empty((wl.H, wl.W), np.uint8)
+        ctx.d2h(m, d_mask)
+        assert int((m != want).sum()) == 0
+        soft = workloads.relight(wl, spp=16)
+        for kernel in (3, 8):
+            ctx.set_option("kernel", kernel)
+            assert _mask_bad(ctx, soft, got, d_pos=d_pos, d_mask=d_mask) == 0, f"16 samples, kernel {kernel}"
+        ctx.free(d_pos)
+        ctx.free(d_mask)
+    finally:
+        ctx.set_option("kernel", -1)
+
+
+def test_city_4k_after_refit_auto_kernel(ctx):
+    wl = workloads.prepare("city", 3840, 2160, via_obj=False)
+    ctx.set_bvh(wl.packed)
+    got, ms, _ = api.bvh_refit_device(ctx, _wave(wl.vertices, 1.1), 8, wl.indices, wl.prim_count, want_packed=True)
+    assert np.array_equal(got, api.bvh_refit(wl.packed, _wave(wl.vertices, 1.1), 8, wl.indices, wl.prim_count))
+    assert _mask_bad(ctx, wl, got) == 0
+
+
+def test_split_table_and_tile_order_survive_a_refit(ctx, small):
+    wl = small["cornell"]
+    ctx.set_bvh(wl.packed)
+    d_pos, d_mask = _on_device(ctx, wl.positions), ctx.malloc(wl.W * wl.H)
+    try:
+        for kernel, front in ((3, 1.0 / 3.0), (8, 1.0)):
+            ctx.set_option("kernel", kernel)
+            ctx.set_bvh(wl.packed)
+            ctx.plan_splits(wl.constants, d_pos, wl.W, wl.H, d_mask, light=wl.light, min_life_us=4.0, piece_us=2.0,
+                            max_pieces=8, front_share=front)
+            table = [ctx.get_option(k) for k in ("split_tiles", "front_tiles", "split_pieces")]
+            assert sum(table) > 0
+            for phase in (0.4, 1.3):
+                got, _, _ = api.bvh_refit_device(ctx, _wave(wl.vertices, phase), 8, wl.indices, wl.prim_count, want_packed=True)
+                assert [ctx.get_option(k) for k in ("split_tiles", "front_tiles", "split_pieces")] == table
+                assert _mask_bad(ctx, wl, got, d_pos=d_pos, d_mask=d_mask) == 0, f"kernel {kernel}, front share {front}"
+        soft = api.Light.make(api.Light.POINT, wl.scene.light_point, scenes.jitter_offsets(4, 0.5, 1))
+        ctx.set_bvh(wl.packed)
+        ordered = ctx.plan_tile_order(wl.constants, d_pos, wl.W, wl.H, d_mask, light=soft)
+        assert ordered and ctx.get_option("tile_order_planned") == 1
+        got, _, _ = api.bvh_refit_device(ctx, _wave(wl.vertices, 0.9), 8, wl.indices, wl.prim_count, want_packed=True)
+        assert ctx.get_option("tile_order_tiles") == ordered and ctx.get_option("tile_order_planned") == 1
+        assert _mask_bad(ctx, wl, got, light=soft, d_pos=d_pos, d_mask=d_mask) == 0
+    finally:
+        ctx.set_tile_order(None)
+        ctx.clear_splits()
+        ctx.set_option("kernel", -1)
+        ctx.free(d_pos)
+        ctx.free(d_mask)
+
+
+def test_edge_overflow_drops_the_copy_and_table_and_a_sane_refit_restores_it(ctx, small):
+    wl = small["cornell"]
+    ctx.set_bvh(wl.packed)
+    d_pos, d_mask = _on_device(ctx, wl.positions), ctx.malloc(wl.W * wl.H)
+    try:
+        ctx.set_option("kernel", 8)
+        tiles, _ = ctx.plan_splits(wl.constants, d_pos, wl.W, wl.H, d_mask, light=wl.light, min_life_us=4.0, piece_us=2.0,
+                                   max_pieces=8, front_share=1.0 / 3.0)
+        assert tiles
+        w = wl.vertices.copy()
+        w[0, 0], w[1, 0] = np.float32(-3e38), np.float32(3e38)                  # finite vertices, e0.x = +Inf
+        got, _, _ = api.bvh_refit_device(ctx, w, 8, wl.indices, wl.prim_count, want_packed=True)
+        assert np.array_equal(got, api.bvh_refit(wl.packed, w, 8, wl.indices, wl.prim_count))
+        assert np.isinf(got[:, :3].view(np.float32)).any()
+        with api.ShadowContext(0) as fresh:
+            fresh.set_bvh(got)
+            assert _state(ctx) == _state(fresh) and ctx.get_option("bvh_finite") == 0
+        assert ctx.get_option("wide_nodes") == 0 and ctx.get_option("split_tiles") == 0
+        for kernel in (-1, 3, 8):
+            ctx.set_option("kernel", kernel)
+            assert _mask_bad(ctx, wl, got, d_pos=d_pos, d_mask=d_mask) == 0, f"kernel {kernel}"
+        got, _, _ = api.bvh_refit_device(ctx, _wave(wl.vertices, 0.3), 8, wl.indices, wl.prim_count, want_packed=True)
+        assert ctx.get_option("wide_nodes") > 0
+        with api.ShadowContext(0) as fresh:
+            fresh.set_bvh(got)
+            assert _state(ctx) == _state(fresh)
+            assert np.array_equal(api.read_private_copy(ctx), api.read_private_copy(fresh))
+        ctx.set_option("kernel", 8)
+        assert _mask_bad(ctx, wl, got, d_pos=d_pos, d_mask=d_mask) == 0
+    finally:
+        ctx.set_option("kernel", -1)
+        ctx.free(d_pos)
+        ctx.free(d_mask)
+
+
+def test_refit_errors_change_nothing(small):
+    wl = small["cornell"]
+    with api.ShadowContext(0) as c:
+        with pytest.raises(api.RtsError) as e:
+            api.bvh_refit_device(c, wl.vertices, 8, wl.indices, wl.prim_count)
+        assert e.value.status == 4                                              # RTS_ERR_NO_BVH
+        c.set_bvh(wl.packed)
+        with pytest.raises(api.RtsError) as e:
+            api.bvh_refit_device(c, wl.vertices, 8, wl.indices, wl.prim_count - 3)
+        assert e.value.status == 1                                              # prim_count != the stream's
+        moved, _, _ = api.bvh_refit_device(c, _wave(wl.vertices, 0.8), 8, wl.indices, wl.prim_count, want_packed=True)
+        copy_before = api.read_private_copy(c)
+        for bad in (np.nan, np.inf):
+            w = _wave(wl.vertices, 2.0)
+            w[wl.indices[7], 2] = bad
+            with pytest.raises(api.RtsError) as e:
+                api.bvh_refit_device(c, w, 8, wl.indices, wl.prim_count)
+            assert e.value.status == 3                                          # RTS_ERR_NONFINITE
+        d_i = _on_device(c, np.where(np.arange(wl.indices.size) == 11, wl.vertices.shape[0], wl.indices).astype(np.uint32))
+        with pytest.raises(api.RtsError) as e:                                  # a device index out of range
+            api.bvh_refit_device(c, _wave(wl.vertices, 2.0), 8, d_i, wl.prim_count)
+        assert e.value.status == 1
+        c.free(d_i)
+        assert np.array_equal(api.read_private_copy(c), copy_before)
+        assert _mask_bad(c, wl, moved) == 0                                     # the previous stream is still the one traced
+        c.set_option("kernel", 8)
+        assert _mask_bad(c, wl, moved) == 0
+
+
+def test_thirty_frames_and_the_cost_ratio(ctx, small):
+    wl = small["atrium"]
+    ctx.set_bvh(wl.packed)
+    _, _, ratio = api.bvh_refit_device(ctx, wl.vertices, 8, wl.indices, wl.prim_count)
+    assert abs(ratio - 1.0) < 1e-5
+    d_v = _on_device(ctx, wl.vertices)
+    try:
+        for f in range(30):
+            w = _wave(wl.vertices, 0.2 * f, amp=0.02 * float(np.ptp(wl.vertices[:, 0])))
+            ctx.h2d(d_v, w)
+            got, _, ratio = api.bvh_refit_device(ctx, (d_v, w.size), 8, wl.indices, wl.prim_count, want_packed=(f == 29))
+        assert np.array_equal(got, api.bvh_refit(wl.packed, w, 8, wl.indices, wl.prim_count))
+        for kernel in (-1, 8):
+            ctx.set_option("kernel", kernel)
+            assert _mask_bad(ctx, wl, got) == 0
+        scrambled = wl.vertices.copy()
+        scrambled[:, :3] = wl.vertices[np.random.RandomState(3).permutation(wl.vertices.shape[0]), :3]
+        _, _, ratio = api.bvh_refit_device(ctx, scrambled, 8, wl.indices, wl.prim_count)
+        assert ratio > 1.0
+        _, _, ratio = api.bvh_refit_device(ctx, wl.vertices, 8, wl.indices, wl.prim_count)
+        assert abs(ratio - 1.0) < 1e-5                                          # the baseline is the installed stream's
+    finally:
+        ctx.set_option("kernel", -1)
+        ctx.free(d_v)
