@@ -238,7 +238,9 @@ int rts_trace_shadow_mask_device(rts_ctx* ctx, const rts_constants* constants, c
 /* Interleaved row stripes in ONE dispatch (multi-GPU strong scaling): the frame is cut
  * into bands of band_rows rows (a multiple of the kernel's workgroup height: 8 for the default packet kernel, 16 or 32 for
  * the others -- 32 always works) dealt round-robin to n_stripes devices; this call
- * traces the bands stripe, stripe + n_stripes, ... and touches no other row of d_mask. */
+ * traces the bands stripe, stripe + n_stripes, ... and touches no other row of d_mask.  A stripe that owns no band (a frame
+ * of fewer bands than n_stripes) launches nothing; the tuning and planning calls for its dispatch return RTS_OK and tune,
+ * plan and write nothing (no split table, no tile order, launch options unchanged, *ms = 0). */
 int rts_trace_shadow_mask_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light,
                                          const float* d_positions, uint32_t W, uint32_t H, uint32_t band_rows,
                                          uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, void* stream);
@@ -325,7 +327,10 @@ int rts_ctx_autotune_stripes(rts_ctx* ctx, const rts_constants* constants, const
  *
  * rts_ctx_plan_splits measures and installs the table for ONE dispatch geometry (frame size and row range, or stripe):
  *   1. wave statistics of the dispatch (one launch with "wave_stats"), or the caller's statistics of an EARLIER frame
- *      (prev_stats / prev_realtime as rts_ctx_read_wave_stats / rts_ctx_read_wave_realtime return them, prev_waves entries);
+ *      (prev_stats / prev_realtime as rts_ctx_read_wave_stats / rts_ctx_read_wave_realtime return them, prev_waves entries).
+ *      Records with end <= start and tiles right of the dispatch are ignored; statistics that name a tile below the
+ *      dispatch, or one tile in two records, are refused (RTS_ERR_INVALID_ARG, no table).  A tile without a record is
+ *      launched as usual: the table covers the whole dispatch -- no tile rows -- only when every one of its tiles has one;
  *   2. the tiles whose wave lived longer than min_life_us and ended later than end_after_us (the longest max_tiles of
  *      them) are walked once more, alone, with
  *      their visited node indices logged; tile t gets S = ceil(life / piece_us) pieces (2 .. max_pieces), its ranges cut at

@@ -166,6 +166,14 @@ def split_front_order(life_us, tiles, first_record=0, xcd_square=0, life_block=0
     return out
 
 
+def stripe_rows(height, band_rows, n_stripes, stripe):
+    """rtsh_stripe_rows: the virtual rows of one interleaved stripe's dispatch (host logic, no device) -- band_rows x the
+    bands the stripe owns, 0 for a stripe without a band."""
+    rows = C.c_uint32(0)
+    _check(_lib.rtsh_stripe_rows(height, band_rows, n_stripes, stripe, C.byref(rows)), "rtsh_stripe_rows")
+    return int(rows.value)
+
+
 class SplitPlan(C.Structure):
     """rts_split_plan (include/rts.h)."""
     _fields_ = [("min_life_us", C.c_float), ("end_after_us", C.c_float), ("piece_us", C.c_float), ("front_life_us", C.c_float), ("front_share", C.c_float), ("max_pieces", C.c_uint32), ("max_tiles", C.c_uint32),
@@ -180,6 +188,7 @@ _sig("rts_ctx_clear_splits", C.c_int, C.c_void_p)
 _sig("rts_ctx_plan_tile_order", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_uint32, C.c_uint32,
      C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32))
 _sig("rtsh_split_front_order", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rtsh_stripe_rows", C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32))
 _sig("rts_selftest_reciprocal", C.c_int, C.c_void_p, C.c_void_p)
 _sig("rts_ctx_get_split_plan", C.c_int, C.c_void_p, C.POINTER(SplitPlan))
 _sig("rts_ctx_autotune_stripes", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

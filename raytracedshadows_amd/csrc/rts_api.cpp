@@ -495,6 +495,20 @@ static int planRefused(const char* why) {
     return RTS_ERR_INVALID_ARG;
 }
 
+// Virtual rows of one interleaved stripe's dispatch: band_rows times the number of bands stripe, stripe + n_stripes, ... it
+// owns (the last one may be cut by H: guarded in-kernel).  0 when the stripe owns no band (stripe >= bands): nothing to launch.
+static uint32_t stripeRows(uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe) {
+    const uint32_t bands = (uint32_t)(((uint64_t)H + band_rows - 1) / band_rows);
+    return stripe < bands ? ((bands - stripe - 1) / n_stripes + 1) * band_rows : 0u;
+}
+
+// Test hook (tests/test_host_logic.py): stripeRows, host only.
+extern "C" int rtsh_stripe_rows(uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint32_t* rows) {
+    if (!rows || band_rows == 0 || n_stripes == 0 || stripe >= n_stripes) return RTS_ERR_INVALID_ARG;
+    *rows = stripeRows(H, band_rows, n_stripes, stripe);
+    return RTS_OK;
+}
+
 static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
                          uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint32_t band_rows,
                          uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, void* stream) {
@@ -523,10 +537,8 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
     // measured slower or equal on every BASELINE config and are kept as selectable variants only.)
     int variant = c->variant;
     uint32_t rows = row_end - row_begin;
-    if (n_stripes > 1) {                        // virtual rows = whole owned bands (partial last band guarded in-kernel)
-        const uint32_t bands = (H + band_rows - 1) / band_rows;
-        rows = ((bands - stripe + n_stripes - 1) / n_stripes) * band_rows;
-    }
+    if (n_stripes > 1) rows = stripeRows(H, band_rows, n_stripes, stripe);     // virtual rows = whole owned bands
+    if (rows == 0) return RTS_OK;                                                 // (a stripe without a band: no launch)
     const uint64_t pixels = (uint64_t)W * rows;
     // Big one-sample dispatches of a stream with a private copy take the WIDE packet (a static rule from what rts_ctx_autotune
     // picks on the 4K frames: city 0.153 against 0.164 ms, courtyard 0.562 against 0.630; at 1080p and for soft shadows the
@@ -940,7 +952,7 @@ static int measureDispatch(rts_ctx* c, const rts_constants* k, const rts_light* 
     uint64_t* keep = c->d_waveStats; const size_t keepBytes = c->waveStatsBytes;
     c->d_waveStats = nullptr; c->waveStatsBytes = 0;
     uint32_t rows = row_end - row_begin;
-    if (n_stripes > 1) { const uint32_t bands = (H + band_rows - 1) / band_rows; rows = ((bands - stripe + n_stripes - 1) / n_stripes) * band_rows; }
+    if (n_stripes > 1) rows = stripeRows(H, band_rows, n_stripes, stripe);
     const size_t tiles = (size_t)((W + 7) / 8) * ((rows + 7) / 8);
     const size_t waves = tiles * perTile;                             // (soft shadows, "soft_split": 4 waves per tile)
     hipError_t e = hipMalloc((void**)&c->d_waveStats, waves * 64);
@@ -954,9 +966,9 @@ static int measureDispatch(rts_ctx* c, const rts_constants* k, const rts_light* 
         if (status == RTS_OK) e = hipDeviceSynchronize();
         if (status == RTS_OK && e == hipSuccess && (size_t)c->lastBlocksX * c->lastBlocksY != tiles) status = planRefused("not a dispatch of 8x8 tiles");
         if (status == RTS_OK && e == hipSuccess) {
-            stats.resize(waves * 4); rt.resize(waves * 4);
-            e = hipMemcpy(stats.data(), c->d_waveStats, waves * 32, hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(rt.data(), c->d_waveStats + waves * 4, waves * 32, hipMemcpyDeviceToHost);
+            try { stats.resize(waves * 4); rt.resize(waves * 4); } catch (...) { status = RTS_ERR_CAPACITY; }   // (no exception crosses the C ABI)
+            if (status == RTS_OK) e = hipMemcpy(stats.data(), c->d_waveStats, waves * 32, hipMemcpyDeviceToHost);
+            if (status == RTS_OK && e == hipSuccess) e = hipMemcpy(rt.data(), c->d_waveStats + waves * 4, waves * 32, hipMemcpyDeviceToHost);
         }
     }
     if (c->d_waveStats) (void)hipFree(c->d_waveStats);
@@ -1061,7 +1073,7 @@ static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* l
     RTS_HIP(hipSetDevice(c->device));
     clearSplits(c);
     if (!c->wideCount) return RTS_OK;                                            // pieces walk the private copy: none, no table
-    if (n_stripes > 1 && stripe >= (H + band_rows - 1) / band_rows) return RTS_OK;   // a stripe without a band: nothing to launch, no table
+    if (n_stripes > 1 && !stripeRows(H, band_rows, n_stripes, stripe)) return RTS_OK;   // a stripe without a band: nothing to launch, no table
     const uint32_t maxPieces = plan->max_pieces < 2 ? 2 : (plan->max_pieces > 64 ? 64 : plan->max_pieces);
     const uint32_t maxTiles = plan->max_tiles ? (plan->max_tiles > 65536u ? 65536u : plan->max_tiles) : 4096u;
     const uint32_t logCap = 16384;
@@ -1120,6 +1132,20 @@ static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* l
             if (us > plan->min_life_us && (float)(r1 - began) * 0.01f > plan->end_after_us) sel.push_back({ us, bx | (by << 16) });
             else if (frontLife > 0.f && us > frontLife) front.push_back({ B > 1 ? blockLife[(bx / B) | ((by / B) << 16)] : us, bx | (by << 16) });
         }
+        // the dispatch this table belongs to (what traceMaskImpl will compute for the same arguments)
+        const uint32_t rows = n_stripes > 1 ? stripeRows(H, band_rows, n_stripes, stripe) : row_end - row_begin;
+        const uint32_t keyBlocksY = (rows + 7) / 8;
+        if (blocksY > keyBlocksY) return planRefused("statistics of another dispatch");
+        {                                                                       // (the caller's statistics may name a tile twice)
+            std::vector<uint32_t> named(((size_t)blocksX * keyBlocksY + 31) / 32, 0u);
+            for (size_t i = 0; i < waves; ++i) {
+                const uint32_t bx = (uint32_t)(stats[i * 4 + 3] >> 48), by = (uint32_t)(stats[i * 4 + 3] >> 32) & 0xFFFFu;
+                if (rt[i * 4 + 1] <= rt[i * 4] || bx >= blocksX) continue;
+                const size_t id = (size_t)by * blocksX + bx;
+                if (named[id >> 5] & (1u << (id & 31u))) return planRefused("statistics that name a tile twice");
+                named[id >> 5] |= 1u << (id & 31u);
+            }
+        }
         if (sel.empty() && front.empty()) return RTS_OK;
         const auto longer = [](const Sel& a, const Sel& b) { return a.us > b.us || (a.us == b.us && a.tile < b.tile); };
         std::sort(sel.begin(), sel.end(), longer);
@@ -1140,11 +1166,6 @@ static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* l
             provisional[(size_t)t * 8 + 3] = t | (1u << 24);                       // (dword 4: the walk starts at the root, offset 0)
         }
         if (plan->xcd_square) dealOverXcds(front, nPieces, plan->xcd_square);
-        // the dispatch this table belongs to (what traceMaskImpl will compute for the same arguments)
-        uint32_t rows = row_end - row_begin;
-        if (n_stripes > 1) { const uint32_t bands = (H + band_rows - 1) / band_rows; rows = ((bands - stripe + n_stripes - 1) / n_stripes) * band_rows; }
-        const uint32_t keyBlocksY = (rows + 7) / 8;
-        if (blocksY > keyBlocksY) return planRefused("statistics of another dispatch");
         std::vector<uint32_t> bitmap(((size_t)blocksX * keyBlocksY + 31) / 32 + 1, 0u);
         std::vector<uint32_t> frontRecords((size_t)F * 8, 0u);                   // {tile, 0, END, 0 = "front tile", 0...}
         for (uint32_t t = 0; t < T + F; ++t) {
@@ -1204,7 +1225,9 @@ static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* l
         t.d_skipMap = (uint32_t*)d_map; t.d_pieces = (uint32_t*)d_pieces;
         t.d_frontMap = (uint32_t*)d_front; t.frontStride = frontStride;
         t.nPieces = nPieces + F; t.pieceRows = (nPieces + F + blocksX - 1) / blocksX; t.nTiles = T; t.nFront = F;
-        t.allTiles = (size_t)T + F == waves && waves == (size_t)blocksX * keyBlocksY;   // every tile has a record: no tile rows are launched
+        size_t covered = 0;                                                    // tiles with a record (the skip bitmap's bits)
+        for (uint32_t w : bitmap) covered += (size_t)__builtin_popcount(w);
+        t.allTiles = covered == (size_t)blocksX * keyBlocksY;                  // every tile has a record: no tile rows are launched
         t.plan = *plan; t.plan.prev_stats = nullptr; t.plan.prev_realtime = nullptr; t.plan.prev_waves = 0;
         if (tiles_out) *tiles_out = T + F;
         if (pieces_out) *pieces_out = nPieces + F;
@@ -1228,6 +1251,7 @@ static int planTileOrderImpl(rts_ctx* c, const rts_constants* k, const rts_light
     int status = rts_ctx_set_tile_order(c, nullptr, 0);
     if (status != RTS_OK) return status;
     if (c->blockWaves != 1 || c->swizzle) return RTS_OK;                           // (one tile per workgroup only)
+    if (n_stripes > 1 && !stripeRows(H, band_rows, n_stripes, stripe)) return RTS_OK;   // a stripe without a band: nothing to order
     const uint32_t perTile = (light && light->nsamples > 1 && c->softSplit) ? 4u : 1u;
     std::vector<uint64_t> stats, rt;
     status = measureDispatch(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, stats, rt, perTile);
@@ -1282,6 +1306,12 @@ static int autotuneImpl(rts_ctx* c, const rts_constants* k, const rts_light* lig
     RTS_HIP(hipSetDevice(c->device));
     clearSplits(c);
     int status = RTS_OK;
+    if (n_stripes > 1 && !stripeRows(H, band_rows, n_stripes, stripe)) {        // a stripe without a band: nothing to time, nothing tuned
+        if (c->tileOrderPlanned) status = rts_ctx_set_tile_order(c, nullptr, 0);
+        if (chosen) *chosen = c->variant;
+        if (ms_out) *ms_out = 0.f;
+        return status;
+    }
     int reps = 5;                              // (nine for the tables of a dispatch below 0.1 ms: its launches are cheap, its noise is not)
     auto median5 = [&](float* out) {          // two untimed launches, then the median of five (or nine)
         float times[9];

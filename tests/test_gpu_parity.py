@@ -1287,3 +1287,275 @@ def test_plain_c_caller_of_the_consumer_seam(tmp_path):
     r = subprocess.run([exe, str(blob)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert r.stdout.count(" ok ") == 2 * (1 + api.ShadowContext(0).get_option("kernel_count"))
+
+
+# ---- split tables planned from the CALLER's wave statistics (rts_split_plan.prev_stats) --------------------------------------
+def _poisoned_trace(ctx, wl, d_pos, d_mask, stripes=None, light=None, poison=9):
+    """The mask of one device dispatch -- the full frame, or one interleaved stripe (band_rows, n_stripes, stripe) -- traced into
+    a mask filled with `poison` (not a legal output), and the rows the dispatch owns."""
+    W, H = wl.W, wl.H
+    light = wl.light if light is None else light
+    got = np.full((H, W), poison, np.uint8)
+    ctx.h2d(d_mask, got)
+    own = np.zeros(H, bool)
+    if stripes is None:
+        ctx.trace_shadow_mask_device(wl.constants, d_pos, W, H, d_mask, light=light)
+        own[:] = True
+    else:
+        ctx.trace_shadow_mask_stripes_device(wl.constants, d_pos, W, H, d_mask, *stripes, light=light)
+        for b, e in partition.stripe_rows(H, stripes[1], stripes[2], band=stripes[0], interleaved=True):
+            own[b:e] = True
+    ctx.synchronize()
+    ctx.d2h(got, d_mask)
+    return got, own
+
+
+def _measured_stats(ctx, wl, stripes=None):
+    """(stats, realtime) of one plain dispatch of `wl` (or of one of its stripes), as rts_ctx_read_wave_stats / _realtime
+    return them: what a caller hands to rts_ctx_plan_splits as an earlier frame's statistics."""
+    rows = wl.H if stripes is None else api.stripe_rows(wl.H, *stripes)
+    waves = ((wl.W + 7) // 8) * ((rows + 7) // 8)
+    d_pos, d_mask = ctx.malloc(wl.positions.nbytes), ctx.malloc(wl.W * wl.H)
+    ctx.clear_splits()
+    ctx.set_option("wave_stats", waves)
+    try:
+        ctx.h2d(d_pos, wl.positions)
+        _poisoned_trace(ctx, wl, d_pos, d_mask, stripes)
+        st, rt = ctx.read_wave_stats(waves), ctx.read_wave_realtime(waves)
+    finally:
+        ctx.set_option("wave_stats", 0)
+        ctx.free(d_pos)
+        ctx.free(d_mask)
+    assert (rt[:, 1] > rt[:, 0]).all()
+    return st, rt
+
+
+def _tile_of(st):
+    return (st[:, 3] >> np.uint64(48)).astype(np.int64), ((st[:, 3] >> np.uint64(32)) & np.uint64(0xFFFF)).astype(np.int64)
+
+
+def _record_of(st, bx, by):
+    x, y = _tile_of(st)
+    hit = np.nonzero((x == bx) & (y == by))[0]
+    assert hit.size == 1, (bx, by, hit)
+    return int(hit[0])
+
+
+def _plan_from_caller_stats(ctx, wl, want, d_pos, d_mask, prev, what, stripes=None, omitted=None, **plan):
+    """Plans from `prev`; the call either installs a table (RTS_OK) or refuses (RTS_ERR_INVALID_ARG) and then leaves none.
+    Either way the traced dispatch equals the oracle in every byte it owns and leaves the poison in every other."""
+    try:
+        ctx.plan_splits(wl.constants, d_pos, wl.W, wl.H, d_mask, light=wl.light, prev=prev, stripes=stripes, **plan)
+        status = 0
+    except api.RtsError as e:
+        status = e.status
+    assert status in (0, 1), (what, status)
+    if status:
+        assert ctx.get_option("split_tiles") == 0 and ctx.get_option("front_tiles") == 0 and ctx.split_plan() is None, what
+    got, own = _poisoned_trace(ctx, wl, d_pos, d_mask, stripes)
+    bad = (got != want) & own[:, None]
+    detail = ""
+    if bad.any() and omitted is not None:                   # (what a launch without tile rows leaves: the missing tile unwritten)
+        tile = np.zeros_like(bad)
+        tile[8 * omitted[1]:8 * omitted[1] + 8, 8 * omitted[0]:8 * omitted[0] + 8] = True
+        tile &= own[:, None]
+        detail = (f"; the bytes that differ are exactly the omitted tile {omitted}'s {int(tile.sum())} pixels: {bool((bad == tile).all())}, "
+                  f"all still at the poison: {bool((got[bad] == 9).all())}")
+    assert not bad.any(), f"{what}: status {status}, {int(bad.sum())} bytes differ from the oracle{detail}"
+    assert (got[~own] == 9).all(), f"{what}: bytes outside the dispatch's rows written"
+    return status
+
+
+@pytest.mark.parametrize("scene,W,H,edge", [("atrium", 640, 360, (40, 44)), ("cornell", 250, 131, (31, 16))])
+def test_split_tables_from_corrupted_caller_statistics(ctx, scene, W, H, edge):
+    """rts_split_plan.prev_stats is the caller's: it may name a tile twice and leave another out, carry unclocked records, be
+    shorter than the dispatch, come from a wider or taller frame or from another stripe.  The planner installs a table or
+    refuses (and then has none); a table is less well balanced, never wrong -- no tile is left unwritten, in particular when
+    the table claims to cover the whole dispatch (front_share 1: no tile rows are launched).  `edge`: a tile on the frame's
+    last row (and, on the ragged frame, its cut right and bottom edges) that the duplicated statistics leave out."""
+    wl = workloads.prepare(scene, W, H, via_obj=False)
+    want, _, _ = oracle.shadow_mask(wl.packed, wl.constants.as_array(), oracle.light_from_product(wl.light, wl.constants), wl.positions, W, H)
+    ctx.set_bvh(wl.packed)
+    assert ctx.get_option("wide_nodes") > 0
+    d_pos, d_mask = ctx.malloc(wl.positions.nbytes), ctx.malloc(W * H)
+    blocks = ((W + 7) // 8) * ((H + 7) // 8)
+    whole = dict(min_life_us=1e9, piece_us=1e9, front_share=1.0)
+    try:
+        ctx.h2d(d_pos, wl.positions)
+        for kernel in (3, 8):
+            ctx.set_option("kernel", kernel)
+            st, rt = _measured_stats(ctx, wl)
+            assert st.shape[0] == blocks and len(set(st[:, 3].tolist())) == blocks
+            life = (rt[:, 1] - rt[:, 0]).astype(np.float64) * 0.01
+            split = dict(min_life_us=float(np.percentile(life, 80)), piece_us=float(np.percentile(life, 80)) / 3, max_pieces=8, front_share=1.0)
+            assert _plan_from_caller_stats(ctx, wl, want, d_pos, d_mask, (st, rt), "as measured", **whole) == 0
+            assert ctx.get_option("front_tiles") == blocks
+            # record i takes record j's tile word and clocks: tile j twice, tile i (on the edge) nowhere
+            i, j = _record_of(st, *edge), _record_of(st, 5, 3)
+            for extra in (whole, split):
+                s2, r2 = st.copy(), rt.copy()
+                s2[i], r2[i] = st[j], rt[j]
+                _plan_from_caller_stats(ctx, wl, want, d_pos, d_mask, (s2, r2), f"kernel {kernel}: tile {edge} replaced by a copy of (5, 3)",
+                                        omitted=edge, **extra)
+            # ... of the LONGEST tile, its second copy with a quarter of its clocks: one copy split into pieces, one a front record
+            j = int(np.argmax(life))
+            s2, r2 = st.copy(), rt.copy()
+            s2[i], r2[i] = st[j], rt[j]
+            r2[i, 1] = r2[i, 0] + max(1, int(rt[j, 1] - rt[j, 0]) // 4)
+            _plan_from_caller_stats(ctx, wl, want, d_pos, d_mask, (s2, r2), f"kernel {kernel}: the longest tile twice, once short", omitted=edge,
+                                    min_life_us=0.6 * float(life[j]), piece_us=0.2 * float(life[j]), max_pieces=8, front_share=1.0)
+            # unclocked records (end <= start): their tiles have no record in the table and run as tile rows
+            rs = np.random.RandomState(kernel)
+            for extra in (whole, split, dict(split, front_share=0.0)):
+                s2, r2 = st.copy(), rt.copy()
+                pick = rs.choice(blocks, 7, replace=False)
+                r2[pick[:4], 1] = r2[pick[:4], 0]
+                r2[pick[4:], 1] = r2[pick[4:], 0] - np.uint64(1)
+                r2[i, 1] = r2[i, 0]                                          # (the edge tile among them)
+                _plan_from_caller_stats(ctx, wl, want, d_pos, d_mask, (s2, r2), f"kernel {kernel}: unclocked records", **extra)
+            # fewer records than the dispatch has waves
+            for n in (1, blocks // 3, blocks - 1):
+                for extra in (whole, split):
+                    _plan_from_caller_stats(ctx, wl, want, d_pos, d_mask, (st[:n], rt[:n]), f"kernel {kernel}: prev_waves {n} of {blocks}", **extra)
+            # a wider frame's statistics (tiles with bx >= blocksX are not this dispatch's), a taller frame's (refused)
+            wide = workloads.prepare(scene, W + 72, H, via_obj=False, packed=wl.packed)
+            ws, wr = _measured_stats(ctx, wide)
+            assert (_tile_of(ws)[0] >= (W + 7) // 8).any()
+            for extra in (whole, split):
+                _plan_from_caller_stats(ctx, wl, want, d_pos, d_mask, (ws, wr), f"kernel {kernel}: a wider frame's statistics", **extra)
+            tall = workloads.prepare(scene, W, H + 40, via_obj=False, packed=wl.packed)
+            ts, tr = _measured_stats(ctx, tall)
+            for extra in (whole, split):
+                assert _plan_from_caller_stats(ctx, wl, want, d_pos, d_mask, (ts, tr), f"kernel {kernel}: a taller frame's statistics",
+                                               **extra) == 1
+            # one interleaved stripe's statistics planned for another stripe of the same frame
+            stats = [_measured_stats(ctx, wl, stripes=(32, 3, r)) for r in range(3)]
+            for r in range(3):
+                for r2_ in range(3):
+                    if r2_ == r:
+                        continue
+                    for extra in (whole, split):
+                        _plan_from_caller_stats(ctx, wl, want, d_pos, d_mask, stats[r], f"kernel {kernel}: stripe {r}'s statistics for stripe {r2_}",
+                                                stripes=(32, 3, r2_), **extra)
+    finally:
+        ctx.clear_splits()
+        ctx.set_option("wave_stats", 0)
+        ctx.set_option("kernel", -1)
+        ctx.free(d_pos)
+        ctx.free(d_mask)
+
+
+@pytest.mark.parametrize("H", [128, 100])
+def test_ranks_without_a_band_tune_and_trace_nothing(ctx, H):
+    """A frame of 4 bands (32 rows; H = 100 cuts the last one to 4 rows) over 8 ranks: ranks 4..7 own no band.  Each rank
+    tunes (rts_ctx_autotune_stripes), plans a tile order and a split table and traces its stripe into ONE poisoned mask, as
+    `bench.py --gpus 8` does on a short frame.  A rank without a band gets RTS_OK from every call, nothing tuned or planned --
+    no table, no tile order, its launch options as they were -- and not one mask byte changes; the frame is the oracle's.
+    Then the same with four light samples per pixel (the planned tile order of soft shadows)."""
+    wl = workloads.prepare("cornell", 200, H, via_obj=False)
+    W, n = wl.W, 8
+    soft = api.Light.make(api.Light.POINT, wl.scene.light_point, scenes.jitter_offsets(4, 0.5, 1))
+    ctx.set_bvh(wl.packed)
+    d_pos, d_mask = ctx.malloc(wl.positions.nbytes), ctx.malloc(W * H)
+    options = ("kernel", "packet_share", "row_order")
+
+    def mask():
+        ctx.synchronize()
+        out = np.empty((H, W), np.uint8)
+        ctx.d2h(out, d_mask)
+        return out
+
+    try:
+        ctx.h2d(d_pos, wl.positions)
+        for light in (wl.light, soft):
+            want, _, _ = oracle.shadow_mask(wl.packed, wl.constants.as_array(), oracle.light_from_product(light, wl.constants), wl.positions, W, H)
+            ctx.h2d(d_mask, np.full((H, W), 9, np.uint8))
+            for r in range(n):
+                stripes = (32, n, r)
+                owned = partition.stripe_rows(H, n, r, band=32, interleaved=True)
+                assert bool(owned) == (r < 4) and api.stripe_rows(H, 32, n, r) == 32 * len(owned)
+                ctx.set_option("kernel", -1)
+                before, kept = mask(), {k: ctx.get_option(k) for k in options}
+                if light is wl.light:
+                    chosen, ms = ctx.autotune(wl.constants, d_pos, W, H, d_mask, light=light, stripes=stripes)
+                    if not owned:
+                        assert chosen == -1 and ms == 0.0 and {k: ctx.get_option(k) for k in options} == kept
+                        assert ctx.get_option("split_tiles") == 0 and ctx.get_option("front_tiles") == 0 and ctx.split_plan() is None
+                        assert ctx.get_option("tile_order_planned") == 0 and ctx.get_option("tile_order_tiles") == 0
+                ctx.set_option("kernel", 8)
+                ordered = ctx.plan_tile_order(wl.constants, d_pos, W, H, d_mask, light=light, stripes=stripes)
+                assert (ordered > 0) == bool(owned), (r, ordered)
+                if not owned:
+                    assert ctx.get_option("tile_order_planned") == 0 and ctx.get_option("tile_order_tiles") == 0
+                if light is wl.light:
+                    ctx.set_tile_order(None)                                    # (one sample: the stripe is traced with a split table)
+                    tiles, pieces = ctx.plan_splits(wl.constants, d_pos, W, H, d_mask, light=light, min_life_us=2.0, piece_us=1.0,
+                                                    max_pieces=8, front_share=1.0 / 3.0, stripes=stripes)
+                    if not owned:
+                        assert tiles == 0 and pieces == 0 and ctx.get_option("split_tiles") == 0 and ctx.split_plan() is None
+                ctx.trace_shadow_mask_stripes_device(wl.constants, d_pos, W, H, d_mask, *stripes, light=light)
+                after = mask()
+                if not owned:
+                    assert (after == before).all(), (r, int((after != before).sum()))
+                else:
+                    rows = np.zeros(H, bool)
+                    for b, e in owned:
+                        rows[b:e] = True
+                    assert (after[rows] == want[rows]).all() and (after[~rows] == before[~rows]).all(), r
+                ctx.set_tile_order(None)
+                ctx.clear_splits()
+            got = mask()
+            assert (got == want).all(), (H, light.nsamples, int((got != want).sum()))
+    finally:
+        ctx.set_tile_order(None)
+        ctx.clear_splits()
+        ctx.set_option("kernel", -1); ctx.set_option("packet_share", 4); ctx.set_option("row_order", 0)
+        ctx.free(d_pos)
+        ctx.free(d_mask)
+
+
+@pytest.mark.parametrize("nsamples", [3, 5, 17, 31, 33, 63, 64])
+def test_soft_shadows_up_to_64_samples(ctx, nsamples):
+    """rts_light.nsamples up to 64 and an output byte of 0..64: sample counts that are not a multiple of the 4 waves of
+    "soft_split" or of anything else, with the offsets as given (table 0), a per-pixel start inside exactly nsamples entries
+    (table == nsamples) and inside all 64.  Point and directional lights, every kernel, soft_split 0 / 1, on a ragged frame and
+    as two interleaved stripes of another.  Some pixel of every mask sees all its samples: the byte nsamples is produced."""
+    wl = workloads.prepare("cornell", 131, 77, via_obj=False)
+    st = workloads.prepare("cornell", 96, 75, via_obj=False, packed=wl.packed)
+    ctx.set_bvh(wl.packed)
+    sc = wl.scene
+    radius = 0.05 * float(np.linalg.norm(sc.bbox_max - sc.bbox_min))         # (large lights: wide penumbrae, many counts)
+    d_pos, d_mask = ctx.malloc(st.positions.nbytes), ctx.malloc(st.W * st.H)
+    try:
+        ctx.h2d(d_pos, st.positions)
+        for kind, xyz, r in ((api.Light.POINT, sc.light_point, radius), (api.Light.DIRECTIONAL, sc.light_direction, 0.1)):
+            offsets = scenes.jitter_offsets(64, r, nsamples)
+            for table in (0, nsamples, 64):
+                light = api.Light.make(kind, xyz, offsets[:nsamples])
+                if table:
+                    light = api.Light.make(kind, xyz, offsets[:table], nsamples=nsamples)
+                    light.table = table                                     # (table == nsamples: set by hand)
+                assert light.nsamples == nsamples and light.table == table
+                want = {}
+                for f in (wl, st):
+                    want[f.W], _, _ = oracle.shadow_mask(wl.packed, f.constants.as_array(), oracle.light_from_product(light, f.constants),
+                                                         f.positions, f.W, f.H)
+                    assert want[f.W].max() == nsamples and ((want[f.W] > 0) & (want[f.W] < nsamples)).any(), (kind, table)
+                for split in (0, 1):
+                    ctx.set_option("soft_split", split)
+                    for v in _variants(ctx):
+                        ctx.set_option("kernel", v)
+                        got = ctx.trace_shadow_mask(wl.constants, wl.positions, wl.W, wl.H, light=light)
+                        assert (got == want[wl.W]).all(), (kind, table, split, v, int((got != want[wl.W]).sum()))
+                        ctx.h2d(d_mask, np.full((st.H, st.W), 200, np.uint8))
+                        for rank in range(2):
+                            ctx.trace_shadow_mask_stripes_device(st.constants, d_pos, st.W, st.H, d_mask, 32, 2, rank, light=light)
+                        ctx.synchronize()
+                        got = np.empty((st.H, st.W), np.uint8)
+                        ctx.d2h(got, d_mask)
+                        assert (got == want[st.W]).all(), ("stripes", kind, table, split, v, int((got != want[st.W]).sum()))
+    finally:
+        ctx.set_option("soft_split", 1)
+        ctx.set_option("kernel", -1)
+        ctx.free(d_pos)
+        ctx.free(d_mask)

@@ -284,3 +284,122 @@ def test_thirty_frames_and_the_cost_ratio(ctx, small):
     finally:
         ctx.set_option("kernel", -1)
         ctx.free(d_v)
+
+
+# ---- the treelet pass at every size the option allows, on every topology ------------------------------------------------------
+TREELETS = (32, 33, 1022, 1023, 1024, 1261, 2048)      # (1261: the first size whose sparse table needs more than 64 KB of LDS)
+TOPOLOGIES = ("host_sah", "host_median", "lbvh", "ploc", "ploc_sah", "sah", "complete2048", "chain3000")
+
+
+def _complete(lo, hi):
+    return lo if hi - lo == 1 else (_complete(lo, (lo + hi) // 2), _complete((lo + hi) // 2, hi))
+
+
+def _topology(ctx, name):
+    """(packed, vertices, stride, indices, P) of one tree shape, installed on `ctx`.  complete2048: every subtree has 2^k - 1
+    nodes (on the 1023 / 1024 boundary); chain3000: one leaf off every inner node, 3000 heights for the top pass at T = 32."""
+    if name in ("complete2048", "chain3000"):
+        import streams
+        P = 2048 if name == "complete2048" else 3000
+        v, idx = _soup(P, 41)
+        if name == "complete2048":
+            tree = _complete(0, P)
+        else:
+            tree = P - 1
+            for i in range(P - 2, -1, -1):
+                tree = (i, tree)
+        packed = streams.stream_from_tree(tree, v.reshape(P, 3, 3))
+        assert api.bvh_validate(packed) == P
+        ctx.set_bvh(packed)
+        return packed, v, 3, idx, P
+    v, idx = _soup(30011, 5)
+    if name.startswith("host_"):
+        packed = api.BVHBuilder(sah_prim_limit=1 if name == "host_median" else 1000000).build(v, 3, idx, 30011).m_packedNodes
+        ctx.set_bvh(packed)
+    else:
+        packed, _ = api.bvh_build_device(ctx, v, 3, idx, 30011, install=True, algorithm=name)
+    return packed, v, 3, idx, 30011
+
+
+def _zeros_and_denormals(v, seed):
+    """A moved frame in which a tenth of the coordinates are +0.0 / -0.0 and a tenth are denormal (either sign)."""
+    rs = np.random.RandomState(seed)
+    w = _wave(v, 0.3 + seed, amp=0.05 * (float(np.ptp(v[:, 0])) + 1.0))
+    bits = w.view(np.uint32)
+    pick = rs.random_sample(w.shape)
+    sign = (rs.random_sample(w.shape) < 0.5).astype(np.uint32) << np.uint32(31)
+    bits[pick < 0.1] = sign[pick < 0.1]
+    den = (pick >= 0.1) & (pick < 0.2)
+    bits[den] = sign[den] | rs.randint(1, 0x800000, int(den.sum())).astype(np.uint32)
+    assert np.isfinite(w).all() and (bits == 0x80000000).any() and (bits == 0).any()
+    return w
+
+
+@pytest.fixture(scope="module")
+def fresh():
+    c = api.ShadowContext(0)
+    yield c
+    c.close()
+
+
+def _refit_checked(ctx, fresh, w, stride, idx, P, expected, what):
+    """One device refit: its bytes are the numpy restatement's (= the host refit's), and the private copy it refreshed in
+    place is the one a fresh install of those bytes derives."""
+    got, _, _ = api.bvh_refit_device(ctx, w, stride, idx, P, want_packed=True)
+    assert np.array_equal(got, expected), f"{what}: {int((got != expected).any(1).sum())} vec4 differ from the restatement"
+    fresh.set_bvh(got)
+    assert _state(ctx) == _state(fresh), what
+    assert np.array_equal(api.read_private_copy(ctx), api.read_private_copy(fresh)), f"{what}: private copy"
+    return got
+
+
+@pytest.mark.parametrize("topology", TOPOLOGIES)
+def test_device_refit_at_every_treelet_size(ctx, fresh, topology):
+    """Option "refit_treelet" is speed only: at every size from 32 to 2048 -- odd ones, 2^k - 1 / 2^k around the subtrees of a
+    complete tree, above the 64 KB of LDS -- and on trees of every builder and shape, the device refit of MOVED vertices (a
+    child box read before it was updated would show: with the build's own vertices old and new boxes are equal) is the host
+    refit's, byte for byte.  Consecutive refits alternate between two frames, so every refit changes every box."""
+    from test_refit import restate
+    packed, v, stride, idx, P = _topology(ctx, topology)
+    frames = [_wave(v, 1.7, amp=0.05 * (float(np.ptp(v[:, 0])) + 1.0)), _zeros_and_denormals(v, 3)]
+    expected = [restate(packed, w, stride, idx, P) for w in frames]
+    for w, e in zip(frames, expected):
+        assert np.array_equal(api.bvh_refit(packed, w, stride, idx, P), e)
+        assert not np.array_equal(e, packed)
+    try:
+        for T in TREELETS:
+            ctx.set_option("refit_treelet", T)
+            assert ctx.get_option("refit_treelet") == T
+            for f, (w, e) in enumerate(zip(frames, expected)):
+                _refit_checked(ctx, fresh, w, stride, idx, P, e, f"{topology}, treelet {T}, frame {f}")
+    finally:
+        ctx.set_option("refit_treelet", 1024)
+
+
+@pytest.mark.parametrize("topology", ["host_median", "complete2048"])
+def test_treelet_size_changed_between_refits_and_traced(ctx, fresh, topology):
+    """refit_treelet changed between refits on one context (1024 -> 32 -> 2048 -> 1024): the schedule is rebuilt for each,
+    the bytes stay the host refit's, and the refitted stream traces as the oracle does with the default and the wide kernel."""
+    from test_refit import restate
+    packed, v, stride, idx, P = _topology(ctx, topology)
+    lo, hi = v.min(0), v.max(0)
+    eye, target = (hi + (hi - lo) * np.float32(0.6)).astype(np.float32), ((lo + hi) * np.float32(0.5)).astype(np.float32)
+    k = api.RayTracingConstants.make(eye, [0.3, 0.8, 0.5], 96, 72, target - eye)
+    light = api.Light.make(api.Light.POINT, (hi + (hi - lo) * np.float32(0.3)).astype(np.float32))
+    try:
+        for step, T in enumerate((1024, 32, 2048, 1024)):
+            ctx.set_option("refit_treelet", T)
+            w = _wave(v, 0.9 * step + 0.4, amp=0.05 * (float(np.ptp(v[:, 0])) + 1.0)) if step % 2 == 0 else _zeros_and_denormals(v, step)
+            got = _refit_checked(ctx, fresh, w, stride, idx, P, restate(packed, w, stride, idx, P), f"{topology}, step {step}, treelet {T}")
+            pos, hits = api.primary_positions(got, eye, target, 50.0, 96, 72)
+            assert hits > 1000
+            for lt in (None, light):
+                want, _, _ = oracle.shadow_mask(got, k.as_array(), oracle.light_from_product(lt, k), pos, 96, 72)
+                assert 0 < want.sum() < want.size
+                for kernel in (-1, 8):
+                    ctx.set_option("kernel", kernel)
+                    m = ctx.trace_shadow_mask(k, pos, 96, 72, light=lt)
+                    assert (m == want).all(), (topology, T, kernel, int((m != want).sum()))
+    finally:
+        ctx.set_option("refit_treelet", 1024)
+        ctx.set_option("kernel", -1)

@@ -274,6 +274,24 @@ def test_split_front_order_is_a_banded_permutation_in_image_order():
         api.split_front_order(np.ones(2, np.float32), np.array([7, 7], np.uint32))
 
 
+def test_stripe_rows_are_the_owned_bands_and_zero_without_one():
+    """rtsh_stripe_rows, the virtual rows of one interleaved stripe's dispatch that every stripe entry point (trace, autotune,
+    tile order, split table, its wave statistics) sizes its grid by: band_rows x the bands partition.stripe_rows deals to the
+    rank, the cut last band counted whole -- and 0, not a wrapped count, for a rank that owns no band (a frame of fewer bands
+    than ranks).  Bad arguments are refused."""
+    for H in range(1, 301):
+        for band in (8, 16, 32, 40):
+            for n in range(1, 10):
+                for r in range(n):
+                    owned = len(partition.stripe_rows(H, n, r, band=band, interleaved=True))
+                    assert api.stripe_rows(H, band, n, r) == band * owned, (H, band, n, r)
+    assert api.stripe_rows(128, 32, 8, 4) == 0 and api.stripe_rows(100, 32, 8, 3) == 32 and api.stripe_rows(100, 32, 8, 4) == 0
+    assert api.stripe_rows(0xFFFFFFFF, 32, 3, 2) == ((0xFFFFFFFF + 31) // 32 - 3) // 3 * 32 + 32    # (no wrap in the band count)
+    for args in ((100, 0, 8, 0), (100, 32, 0, 0), (100, 32, 8, 8)):
+        with pytest.raises(api.RtsError):
+            api.stripe_rows(*args)
+
+
 def test_split_front_order_deals_image_squares_over_the_xcds():
     """xcd_square S: record first_record + r runs on XCD (first_record + r) mod 8 and is taken from that XCD's S x S-tile squares
     (square (rx, ry) belongs to XCD (rx + 3 ry) mod 8) while it has any left in the band; bands stay where they are and the order
