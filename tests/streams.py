@@ -50,3 +50,49 @@ def stream_from_tree(tree, tris):
         out[2 * i + 1, 3] = nxt
     assert len(seen) == P
     return out
+
+
+def deep_bushy_stream(levels):
+    """A tree whose wide walk keeps three subtrees pending per level: node(l) = ((node(l-1), small), (small, small)), small =
+    two tiny triangles in opposite corners of the unit square (its box covers the middle, where every ray passes; the
+    triangles are hit by nobody).  Level 0 holds two real occluders."""
+    tris, z = [], [0.0]
+
+    def tiny(x, y):
+        tris.append([[x, y, z[0]], [x + 1e-3, y, z[0]], [x, y + 1e-3, z[0]]])
+        return len(tris) - 1
+
+    def small():
+        z[0] += 0.25
+        a = tiny(0.05, 0.05)
+        z[0] += 0.25
+        return (a, tiny(0.95, 0.95))
+
+    def node(l):
+        if l == 0:
+            z[0] += 0.5
+            tris.append([[0.0, 0.0, z[0]], [0.55, 0.0, z[0]], [0.0, 0.9, z[0]]])          # occludes the rays of one corner
+            tris.append([[0.6, 0.6, z[0] + 0.1], [0.9, 0.6, z[0] + 0.1], [0.6, 0.9, z[0] + 0.1]])
+            return (len(tris) - 2, len(tris) - 1)
+        return ((node(l - 1), small()), (small(), small()))
+
+    tree = node(levels)
+    return stream_from_tree(tree, np.array(tris, np.float32))
+
+
+def shrink_boxes(packed, boxes):
+    """A copy of `packed` in which inner nodes whose two children are both leaves get smaller boxes: `boxes` maps a node index
+    to (bboxMin, bboxMax).  Each new box must lie inside the node's old one, so every ancestor still encloses it (the stream
+    stays "enclosed") while the node's triangles stick out of it -- or miss it altogether."""
+    out = np.array(packed, np.uint32).reshape(-1, 4)
+    f = out.view(np.float32)
+    for node, (lo, hi) in boxes.items():
+        assert out[2 * node, 3] == END, f"node {node} is a leaf"
+        left = node + 1
+        right = out[2 * left + 1, 3]
+        assert out[2 * left, 3] != END and out[2 * right, 3] != END, f"node {node}: both children must be leaves"
+        lo, hi = np.asarray(lo, np.float32), np.asarray(hi, np.float32)
+        assert (f[2 * node, :3] <= lo).all() and (hi <= f[2 * node + 1, :3]).all() and (lo <= hi).all(), node
+        f[2 * node, :3] = lo
+        f[2 * node + 1, :3] = hi
+    return out

@@ -387,40 +387,12 @@ def test_degenerate_and_denormal_triangles(ctx):
         assert (got == want).all(), f"kernel {v}: {(got != want).sum()} rays differ"
 
 
-def _deep_bushy_stream(levels):
-    """A tree whose wide walk keeps three subtrees pending per level: node(l) = ((node(l-1), small), (small, small)), small =
-    two tiny triangles in opposite corners of the unit square (its box covers the middle, where every ray passes; the
-    triangles are hit by nobody).  Level 0 holds two real occluders."""
-    tris, z = [], [0.0]
-
-    def tiny(x, y):
-        tris.append([[x, y, z[0]], [x + 1e-3, y, z[0]], [x, y + 1e-3, z[0]]])
-        return len(tris) - 1
-
-    def small():
-        z[0] += 0.25
-        a = tiny(0.05, 0.05)
-        z[0] += 0.25
-        return (a, tiny(0.95, 0.95))
-
-    def node(l):
-        if l == 0:
-            z[0] += 0.5
-            tris.append([[0.0, 0.0, z[0]], [0.55, 0.0, z[0]], [0.0, 0.9, z[0]]])          # occludes the rays of one corner
-            tris.append([[0.6, 0.6, z[0] + 0.1], [0.9, 0.6, z[0] + 0.1], [0.6, 0.9, z[0] + 0.1]])
-            return (len(tris) - 2, len(tris) - 1)
-        return ((node(l - 1), small()), (small(), small()))
-
-    tree = node(levels)
-    return streams.stream_from_tree(tree, np.array(tris, np.float32))
-
-
 def test_wide_stack_limit_dissolves_and_keeps_every_pixel(ctx):
     """the wide packet's stack lives in lanes 0..62 of three VGPRs and lane 63 keeps EXEC of the entry; a walk
     that pushes three subtrees per level for 25 levels must dissolve BEFORE entry 63 is written, and every pixel of the tile
     must still be traversed and stored.  packet_share = 0 switches the coherence rule off, so the stack limit is the only way
     to dissolve -- the wave statistics must show that it did."""
-    packed = _deep_bushy_stream(25)
+    packed = streams.deep_bushy_stream(25)
     assert api.bvh_validate(packed) == (packed.shape[0] + 2) // 5
     W = H = 24
     pos = np.zeros((H, W, 4), np.float32)
@@ -637,7 +609,7 @@ def test_split_tables_on_awkward_streams_and_rays(ctx):
     """Pieces on the hand-made deep tree (their stack limit and the lane-per-ray continuation inside an index range), with an
     axis-parallel light (every wave takes the exact walk: piece 0 walks it whole, the others contribute nothing), on a ragged
     frame, and with soft shadows (no table is planned for them)."""
-    packed = _deep_bushy_stream(25)
+    packed = streams.deep_bushy_stream(25)
     W = H = 24
     pos = np.zeros((H, W, 4), np.float32)
     pos[..., 0] = 0.2 + 0.6 * (np.arange(W, dtype=np.float32)[None, :] + 0.5) / W
