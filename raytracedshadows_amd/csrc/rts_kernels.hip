@@ -683,6 +683,15 @@ __device__ __forceinline__ bool wideRaySetup(const Ray& r, const float* rootLo, 
     return ok;
 }
 
+// Near end of the cheap test.  SEG (a segment ray: d = L - o, tmax = 1, the point light): clamped to [0, 1] instead of
+// max(near, 0) -- the clamp bit of the v_max3 (dx10_clamp), one VALU fewer.  clamp(n) <= max(n, 0) for every n, so the
+// test accepts a superset; the extra boxes have near > 1 and 1 <= far < near: beyond the light.
+template <bool SEG>
+__device__ __forceinline__ float cheapNear(float nx, float ny, float nz) {
+    const float n = __builtin_fmaxf(__builtin_fmaxf(nx, ny), nz);
+    return SEG ? __builtin_amdgcn_fmed3f(n, 0.0f, 1.0f) : __builtin_fmaxf(n, 0.0f);
+}
+
 // OCT 0..7: bit a set <=> 1/d component a is negative in every lane (far plane = bboxMin on that axis); 8: per lane.
 template <int OCT>
 __device__ __forceinline__ bool cheapBox(const float* lo, const float* hi, const F3& inv, const WideRay& w) {
@@ -698,7 +707,7 @@ __device__ __forceinline__ bool cheapBox(const float* lo, const float* hi, const
         fz = __builtin_fmaf(sz ? lo[2] : hi[2], inv.z, -w.cU.z); nz = __builtin_fmaf(sz ? hi[2] : lo[2], inv.z, -w.cD.z);
     }
     const float t1 = __builtin_fminf(__builtin_fminf(fx, fy), fz);
-    const float t0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(nx, ny), nz), 0.0f);
+    const float t0 = cheapNear<false>(nx, ny, nz);
     return t1 >= t0;
 }
 
@@ -717,13 +726,14 @@ __device__ __forceinline__ bool cheapBox(const float* lo, const float* hi, const
 // ------------------------------------------------------------------------------------------------
 static constexpr uint32_t LANE_STACK = 16;
 
+template <bool SEG>
 __device__ __forceinline__ bool cheapBoxLane(const float* lo, const float* hi, const F3& inv, const WideRay& w) {
     const bool sx = inv.x < 0.f, sy = inv.y < 0.f, sz = inv.z < 0.f;
     const float fx = __builtin_fmaf(sx ? lo[0] : hi[0], inv.x, -w.cU.x), nx = __builtin_fmaf(sx ? hi[0] : lo[0], inv.x, -w.cD.x);
     const float fy = __builtin_fmaf(sy ? lo[1] : hi[1], inv.y, -w.cU.y), ny = __builtin_fmaf(sy ? hi[1] : lo[1], inv.y, -w.cD.y);
     const float fz = __builtin_fmaf(sz ? lo[2] : hi[2], inv.z, -w.cU.z), nz = __builtin_fmaf(sz ? hi[2] : lo[2], inv.z, -w.cD.z);
     const float t1 = __builtin_fminf(__builtin_fminf(fx, fy), fz);
-    const float t0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(nx, ny), nz), 0.0f);
+    const float t0 = cheapNear<SEG>(nx, ny, nz);
     return t1 >= t0;
 }
 
@@ -762,6 +772,7 @@ struct LaneWalk {
 // items are on the lane's stack.  One iteration = one item per lane = ONE memory latency: seven 16-byte loads from the
 // item's offset (a node uses all of them, a triangle record the first three), then either four box tests (every slot
 // somebody hit becomes an item: the first is taken up next, the others are pushed) or one triangle test.
+template <bool SEG>
 __device__ __forceinline__ bool laneWideWalk(LaneWalk& lw, const Ray& r, const WideRay& w, uint32_t cur, ShareDiag* diag) {
     bool occluded = false;
     for (;;) {
@@ -798,7 +809,7 @@ __device__ __forceinline__ bool laneWideWalk(LaneWalk& lw, const Ray& r, const W
             const uint32_t ref[4] = { q[6].x, q[6].y, q[6].z, q[6].w };
 #pragma unroll
             for (int k = 3; k >= 0; --k) {                           // last slot first: the first one ends up as `next`
-                const bool hit = isNode && ref[k] != END && cheapBoxLane(&pl[6 * k], &pl[6 * k + 3], r.inv, w);
+                const bool hit = isNode && ref[k] != END && cheapBoxLane<SEG>(&pl[6 * k], &pl[6 * k + 3], r.inv, w);
                 lw.push(next, hit && next != END);
                 next = hit ? ref[k] : next;
             }
@@ -813,6 +824,7 @@ __device__ __forceinline__ bool laneWideWalk(LaneWalk& lw, const Ray& r, const W
 // A dissolved wide packet: every pending (node, members) is on the stack.  A ray continues the reference's stackless walk
 // (lane per ray, work sharing, triangle hits confirmed) from the LOWEST node index among the entries it is a member of:
 // everything it still has to look at lies at or after that node in the stream.
+template <bool SEG>
 __device__ __forceinline__ bool wideDissolve(const TraceParams& p, const NodeStream& bvh, const Ray& r, const WideRay& w, uint64_t occ,
                                              uint32_t sp, uint32_t stRef, uint32_t stLo, uint32_t stHi, uint32_t* lds,
                                              uint32_t* laneStack, ShareDiag* diag) {
@@ -835,7 +847,7 @@ __device__ __forceinline__ bool wideDissolve(const TraceParams& p, const NodeStr
             lw.push(eref, __builtin_amdgcn_inverse_ballot_w64(m));
         }
         const uint32_t first = lw.pop(true);
-        bool h = laneWideWalk(lw, r, w, first, diag);
+        bool h = laneWideWalk<SEG>(lw, r, w, first, diag);
         // rays whose stack overflowed finish with the stackless walk from the lowest node they could not keep
         if (__builtin_amdgcn_ballot_w64((lw.lostNode != END || lw.lostLeaf != END) && !h) != 0) {
             const uint32_t from = h ? END : lw.lostIndex();
@@ -940,10 +952,13 @@ __device__ __forceinline__ bool wideWalk(const TraceParams& p, const NodeStream&
     }
     if (dissolved) *dissolved = dissolve ? -1 : 0;
     if (!dissolve) return __builtin_amdgcn_inverse_ballot_w64(occ);
-    return wideDissolve(p, bvh, r, w, occ, sp, stRef, stLo, stHi, lds, laneStack, diag);
+    return wideDissolve<false>(p, bvh, r, w, occ, sp, stRef, stLo, stHi, lds, laneStack, diag);
 }
 
-template <bool ASM>
+// SEG: the ray is a segment (d = L - o, tmax = 1: a point light, every sample of a soft one) -- the assembly loop and the lane
+// walk then clamp the near end of the cheap test to [0, 1] (cheapNear).  A kernel instantiation for the light kind, so that
+// each carries one set of loop forms.
+template <bool ASM, bool SEG>
 __device__ __forceinline__ bool traverseWide(const TraceParams& p, const NodeStream& bvh, const Ray& r, bool live, uint32_t* lds,
                                              uint32_t* laneStack, int32_t* dissolved, ShareDiag* diag) {
     const uint64_t liveMask = __builtin_amdgcn_ballot_w64(live);
@@ -967,12 +982,14 @@ __device__ __forceinline__ bool traverseWide(const TraceParams& p, const NodeStr
                                (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)liveMask);
         // (tmax is a property of the light, not of the ray: comp:145 / the point-light extension)
         const float tmaxUniform = p.lightType == 0 ? 1e9f : 1.0f;
-        const uint32_t st = wideDescend(form, (const void*)(uintptr_t)uniform64(p.wide), (const void*)(uintptr_t)uniform64(p.tris), r, w,
+        const uint32_t st = wideDescend<SEG>(form, (const void*)(uintptr_t)uniform64(p.wide), (const void*)(uintptr_t)uniform64(p.tris), r, w,
                                         tmaxUniform, liveU, occ, sp, stRef, stLo, stHi, p.packetBudget, p.packetBudget * p.packetShare);
         if (dissolved) *dissolved = st ? -1 : 0;
         if (st == 0) return __builtin_amdgcn_inverse_ballot_w64(occ);
-        return wideDissolve(p, bvh, r, w, occ, sp, stRef, stLo, stHi, lds, laneStack, diag);
+        return wideDissolve<SEG>(p, bvh, r, w, occ, sp, stRef, stLo, stHi, lds, laneStack, diag);
     } else {
+        // (the compiled form, kernel 9, keeps the unclamped test for every light: its segment-ray forms made the compiler spill more)
+        static_assert(!SEG, "kernel 9 has no segment-ray form");
         switch (form) {
         case 0: return wideWalk<0>(p, bvh, r, w, liveMask, lds, laneStack, dissolved, diag);
         case 1: return wideWalk<1>(p, bvh, r, w, liveMask, lds, laneStack, dissolved, diag);
@@ -1350,9 +1367,10 @@ __device__ __forceinline__ void runPiece(const TraceParams& p, uint32_t* lds) {
 // (traversePiece), then FRONT tiles -- long tiles that are not worth splitting, walked by their own wave as ever, only early.
 // The remaining rows are the everyday tile waves, of which those of a tile of the table have nothing to do (one bitmap look-up).
 template <int K, int WPB, bool PREFETCH = false, bool SOFT = false, bool PLAIN = false, int WIDE = 0, int SPLIT = 1, bool BANDS = false,
-          bool TILESPLIT = false, bool PIECES = true>
+          bool TILESPLIT = false, bool PIECES = true, bool SEG = false>
 // PIECES (with TILESPLIT): false = the table holds front tiles only (the whole-dispatch order of the 4K frames): the instantiation
 // without the piece path -- the everyday path then keeps the registers the piece path's state would take.
+// SEG (WIDE 1 and 3): the launch's light is a point light (traverseWide); the split pieces keep the unclamped test in both.
 // (Registers: a SIMD holds 8 waves of a kernel only up to 64 VGPRs AND 80 SGPRs including VCC / FLAT_SCRATCH / XNACK: the
 //  next granule, 96, plus the 16 the trap handler adds per wave fits 800 only 7 times -- measured with the hardware slot ids
 //  of the probe waves, DESIGN.md 4.7.  Every K = 1 instantiation is inside both limits; tools/gen_wide_asm.py budgets for it.)
@@ -1361,6 +1379,7 @@ void shadowMaskPacketKernel(TraceParams p) {
     static_assert(!BANDS || (PLAIN && K == 1 && WPB == 1), "the band form exists for the one-tile everyday launch only");
     static_assert(SPLIT == 1 || (K == 1 && WPB == 1 && SOFT), "samples are split over waves in the one-tile soft-shadow form only");
     static_assert(!TILESPLIT || (PLAIN && K == 1 && WPB == 1 && !SOFT && SPLIT == 1), "split tiles exist for the one-tile everyday launch only");
+    static_assert(!SEG || WIDE == 1 || WIDE == 3, "the segment-ray forms exist in the assembly wide loop and the lane walk only");
     __shared__ uint32_t shareSlots[WPB * SPLIT][64];     // lane numbers exchanged by traverseShare (256 B per wave)
     uint32_t* lds = shareSlots[threadIdx.x >> 6];
     // per-lane stacks of the wide lane walk: 4 KB per wave -- which caps a CU at 28 one-wave workgroups instead of 32, so
@@ -1462,7 +1481,7 @@ void shadowMaskPacketKernel(TraceParams p) {
             asm volatile("" :: "v"(r[0].inv.x), "v"(r[0].inv.y), "v"(r[0].inv.z), "v"(r[0].o.x));
             tReady = __builtin_amdgcn_s_memtime();
         }
-        if constexpr (WIDE != 0) occluded[0] = traverseWide<WIDE != 2>(p, bvh, r[0], live[0], lds, laneStack, &left, &shareDiag);
+        if constexpr (WIDE != 0) occluded[0] = traverseWide<WIDE != 2, SEG>(p, bvh, r[0], live[0], lds, laneStack, &left, &shareDiag);
         else traversePacket<K, PREFETCH>(p, bvh, r, live, occluded, lds, &left, &shareDiag);
 #pragma unroll
         for (int k = 0; k < K; ++k) lit[k] += occluded[k] ? 0u : 1u;                     // comp:148
@@ -1575,35 +1594,43 @@ void tileShape(int variant, int wavesPerBlock, uint32_t* blockW, uint32_t* block
     *blockH = f * (variant == V_PACKET4 ? 16u : 8u);
 }
 
+// The wide packet kernel (variant 8) for one light kind: SEG = a point light (see traverseWide).
+template <bool SEG>
+static void launchWide(int wavesPerBlock, const TraceParams& p, hipStream_t stream, uint32_t ldsPad, dim3 grid, dim3 block) {
+    const bool soft = p.nsamples > 1;
+    if (wavesPerBlock == 4) {                                             // 2 x 2 tiles per workgroup: neighbours share the scalar cache
+        if (soft) hipLaunchKernelGGL((shadowMaskPacketKernel<1, 4, false, true, false, 1, 1, false, false, true, SEG>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((shadowMaskPacketKernel<1, 4, false, false, false, 1, 1, false, false, true, SEG>), grid, block, 0, stream, p);
+        return;
+    }
+    dim3 b1(64);
+    if (soft && p.softSplit) hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, true, false, 1, 4, false, false, true, SEG>), grid, dim3(256), 0, stream, p);
+    else if (soft) hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, true, false, 1, 1, false, false, true, SEG>), grid, b1, ldsPad, stream, p);
+    else if (p.wideLane)                        // lane-per-ray continuation over the wide nodes: the instantiation with LDS stacks
+        hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, false, 3, 1, false, false, true, SEG>), grid, b1, ldsPad, stream, p);
+    else if (p.pieces && p.nStripes > 1 && p.hasPieces)
+        hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, true, true, true, SEG>), grid, b1, ldsPad, stream, p);
+    else if (p.pieces && p.nStripes > 1)
+        hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, true, true, false, SEG>), grid, b1, ldsPad, stream, p);
+    else if (p.pieces && p.hasPieces)
+        hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, false, true, true, SEG>), grid, b1, ldsPad, stream, p);
+    else if (p.pieces)
+        hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, false, true, false, SEG>), grid, b1, ldsPad, stream, p);
+    else if (p.grid2d && p.nStripes > 1 && p.bandShift != 0xFFFFFFFFu && !p.waveStats && p.rowOrder == 0)
+        hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, true, false, true, SEG>), grid, b1, ldsPad, stream, p);
+    else if (p.grid2d && p.nStripes <= 1 && !p.waveStats)
+        hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, false, false, true, SEG>), grid, b1, ldsPad, stream, p);
+    else hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, false, 1, 1, false, false, true, SEG>), grid, b1, ldsPad, stream, p);
+}
+
 hipError_t launchShadowMask(int variant, int wavesPerBlock, const TraceParams& p, hipStream_t stream, uint32_t ldsPad) {
     dim3 grid(p.gridBlocks), block(256);
     // (the records of a split table come first; when every tile has a record there are no tile rows at all)
     if (p.grid2d) grid = dim3(p.blocksX, (p.pieces && p.allInTable ? 0u : p.blocksY) + (p.pieces ? p.pieceRows : 0u));
     const bool soft = p.nsamples > 1;
-    if (variant == V_WIDE && wavesPerBlock == 4) {                       // 2 x 2 tiles per workgroup: neighbours share the scalar cache
-        if (soft) hipLaunchKernelGGL((shadowMaskPacketKernel<1, 4, false, true, false, 1>), grid, block, 0, stream, p);
-        else hipLaunchKernelGGL((shadowMaskPacketKernel<1, 4, false, false, false, 1>), grid, block, 0, stream, p);
-        return hipGetLastError();
-    }
     if (variant == V_WIDE) {
-        dim3 b1(64);
-        if (soft && p.softSplit) hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, true, false, 1, 4>), grid, dim3(256), 0, stream, p);
-        else if (soft) hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, true, false, 1>), grid, b1, ldsPad, stream, p);
-        else if (p.wideLane)                        // lane-per-ray continuation over the wide nodes: the instantiation with LDS stacks
-            hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, false, 3>), grid, b1, ldsPad, stream, p);
-        else if (p.pieces && p.nStripes > 1 && p.hasPieces)
-            hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, true, true>), grid, b1, ldsPad, stream, p);
-        else if (p.pieces && p.nStripes > 1)
-            hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, true, true, false>), grid, b1, ldsPad, stream, p);
-        else if (p.pieces && p.hasPieces)
-            hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, false, true>), grid, b1, ldsPad, stream, p);
-        else if (p.pieces)
-            hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, false, true, false>), grid, b1, ldsPad, stream, p);
-        else if (p.grid2d && p.nStripes > 1 && p.bandShift != 0xFFFFFFFFu && !p.waveStats && p.rowOrder == 0)
-            hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, true>), grid, b1, ldsPad, stream, p);
-        else if (p.grid2d && p.nStripes <= 1 && !p.waveStats)
-            hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1>), grid, b1, ldsPad, stream, p);
-        else hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, false, 1>), grid, b1, ldsPad, stream, p);
+        if (p.lightType != 0) launchWide<true>(wavesPerBlock, p, stream, ldsPad, grid, block);
+        else launchWide<false>(wavesPerBlock, p, stream, ldsPad, grid, block);
         return hipGetLastError();
     }
     if (variant == V_WIDE_C) {

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Generates raytracedshadows_amd/csrc/rts_wide_asm.inc: the hand-written gfx950 loop of the WIDE packet kernel
 (rts_kernels.hip, 'V_WIDE'; data layout: rts_wide.hip), instantiated for the 8 sign octants of the ordered slab test and
-the generic form.  The .inc file is committed; re-run after editing:
+the generic form, once for rays without a usable tmax (directional light) and once for segment rays (point light).  The
+.inc file is committed; re-run after editing:
 
     python tools/gen_wide_asm.py
 
-One iteration = one wide node: two s_load_dwordx16 (128 B), four CHEAP slab tests (10 VALU each, EXEC = the members, so
-the compare results are membership masks as they come), then per slot that somebody hit: a leaf slot runs the triangle
+One iteration = one wide node: two s_load_dwordx16 (128 B), four CHEAP slab tests (10 VALU each, 9 for segment rays;
+EXEC = the members, so the compare results are membership masks as they come), then per slot that somebody hit: a leaf slot runs the triangle
 test for the lanes that hit its box and confirms triangle hits with the EXACT slab test of that box (comp:61-73); the
 first inner slot becomes the next node, further ones are pushed (node, mask) on the stack that lives in three VGPRs
 (entry i in lane i; v_writelane / v_readlane through M0).
@@ -76,8 +77,11 @@ def far_near(k, a, octant):
     return (lo(k, a), hi(k, a)) if neg else (hi(k, a), lo(k, a))
 
 
-def cheap_pair(ka, kb, octant):
-    """cheap slab tests of two slots, interleaved (12 temporaries): 10 VALU each."""
+def cheap_pair(ka, kb, octant, seg=False):
+    """cheap slab tests of two slots, interleaved (12 temporaries): 10 VALU each (generic form: 22).
+    seg: the form of a SEGMENT ray (point light, every sample of a soft light: d = L - o, tmax = 1): near = max3 with the VOP3
+    clamp, i.e. min(max(near, 0), 1) -- one VALU fewer per slot.  clamp(n) <= max(n, 0) for every n, so the test accepts a
+    superset of what the unclamped form accepts; the extra boxes have near > 1 and 1 <= far < near, beyond the light."""
     L = []
     if octant < 8:
         for j, k in enumerate((ka, kb)):
@@ -88,9 +92,12 @@ def cheap_pair(ka, kb, octant):
                 L.append(f"v_fma_f32 %[t{b + 3 + i}], {far_near(k, i, octant)[1]}, %[i{a}], -%[cd{a}]")
         for j, k in enumerate((ka, kb)):
             b = 6 * j
-            L += [f"v_min3_f32 %[t{b}], %[t{b}], %[t{b + 1}], %[t{b + 2}]",
-                  f"v_max_f32 %[t{b + 3}], %[t{b + 3}], %[t{b + 4}]",
-                  f"v_max3_f32 %[t{b + 3}], %[t{b + 3}], %[t{b + 5}], 0"]
+            L.append(f"v_min3_f32 %[t{b}], %[t{b}], %[t{b + 1}], %[t{b + 2}]")
+            if seg:
+                L.append(f"v_max3_f32 %[t{b + 3}], %[t{b + 3}], %[t{b + 4}], %[t{b + 5}] clamp")
+            else:
+                L += [f"v_max_f32 %[t{b + 3}], %[t{b + 3}], %[t{b + 4}]",
+                      f"v_max3_f32 %[t{b + 3}], %[t{b + 3}], %[t{b + 5}], 0"]
         for j, k in enumerate((ka, kb)):
             b = 6 * j
             L.append(f"v_cmp_ge_f32 {H(k)}, %[t{b}], %[t{b + 3}]")
@@ -104,10 +111,13 @@ def cheap_pair(ka, kb, octant):
                       f"v_fma_f32 %[t{6 + i}], {hi(k, i)}, %[i{a}], -%[cd{a}]",
                       f"v_fma_f32 %[t{9 + i}], {lo(k, i)}, %[i{a}], -%[cd{a}]",
                       f"v_min_f32 %[t{6 + i}], %[t{6 + i}], %[t{9 + i}]"]
-            L += ["v_min3_f32 %[t0], %[t0], %[t1], %[t2]",
-                  "v_max_f32 %[t6], %[t6], %[t7]",
-                  "v_max3_f32 %[t6], %[t6], %[t8], 0",
-                  f"v_cmp_ge_f32 {H(k)}, %[t0], %[t6]"]
+            L.append("v_min3_f32 %[t0], %[t0], %[t1], %[t2]")
+            if seg:
+                L.append("v_max3_f32 %[t6], %[t6], %[t7], %[t8] clamp")
+            else:
+                L += ["v_max_f32 %[t6], %[t6], %[t7]",
+                      "v_max3_f32 %[t6], %[t6], %[t8], 0"]
+            L.append(f"v_cmp_ge_f32 {H(k)}, %[t0], %[t6]")
     return L
 
 
@@ -208,7 +218,7 @@ def triangle(dst, tag=0):
         f"19{tag}:"]
 
 
-def loop(octant):
+def loop(octant, seg=False):
     L = [f"s_mov_b64 {R}, exec",
          f"v_writelane_b32 %[vlo], {RLO}, 63",
          f"v_writelane_b32 %[vhi], {RHI}, 63",
@@ -225,8 +235,8 @@ def loop(octant):
          f"s_mov_b32 {NXREF}, -1",
          f"s_mov_b64 exec, {M}",
          "s_waitcnt lgkmcnt(0)"]
-    L += cheap_pair(0, 1, octant)
-    L += cheap_pair(2, 3, octant)
+    L += cheap_pair(0, 1, octant, seg)
+    L += cheap_pair(2, 3, octant, seg)
     for k in range(4):
         L += [f"s_cmp_lg_u64 {H(k)}, 0",
               f"s_cbranch_scc0 2{k}f",
@@ -347,6 +357,8 @@ def loop_range():
          f"s_mov_b32 {NXREF}, -1",
          f"s_mov_b64 exec, {M}",
          "s_waitcnt lgkmcnt(0)"]
+    # (the generic, unclamped test for every light: a second form picked per node by a scalar compare of tmax with 1.0 made
+    #  rts_ctx_autotune drop the atrium's split table, 0.071 -> 0.124 ms; EXPERIMENTS.md, round 5)
     L += cheap_pair(0, 1, octant)
     L += cheap_pair(2, 3, octant)
     L += [f"s_add_u32 {RLO}, {T(0)}, 1"]
@@ -455,8 +467,8 @@ def emit_range(ind):
             f"{ind}    : {', '.join(clob)});\n")
 
 
-def emit(octant, ind):
-    lines = loop(octant)
+def emit(octant, ind, seg):
+    lines = loop(octant, seg)
     body = "\n".join(f'{ind}    "{l}\\n\\t"' for l in lines)
     outs = ['[sp] "+s"(sp)', '[acc] "+s"(acc)', '[budget] "+s"(budget)', '[occ] "+s"(occ)',
             '[vref] "+v"(stRef)', '[vlo] "+v"(stLo)', '[vhi] "+v"(stHi)']
@@ -476,18 +488,26 @@ def main():
          "// the stack in stRef/stLo/stHi (entry i in lane i).  Returns 0 when the packet is finished and 1 when it dissolves",
          "// (too few members per popped node, or the stack nearly full): every pending (node, members) is on the stack then.",
          "// form 0..7: ordered slab tests for the sign octant (bit a set <=> 1/d component a negative in every lane); 8: generic.",
+         "// SEG: the forms of segment rays (d = L - o, tmax = 1: a point light), near clamped to [0, 1] (cheap_pair); a kernel",
+         "// instantiation carries one of the two sets.",
          "",
+         "template <bool SEG>",
          "__device__ __forceinline__ uint32_t wideDescend(uint32_t form, const void* wbase, const void* tbase, const Ray& r,",
          "                                              const WideRay& w, float tmax, uint64_t live, uint64_t& occ, uint32_t& sp,",
          "                                              uint32_t& stRef, uint32_t& stLo, uint32_t& stHi, uint32_t window, uint32_t thr) {",
          "    uint32_t acc = 0;",
          "    int32_t budget = (int32_t)window - 1;",
          "    float t0, t1, t2, t3, t4, t5, t6, t7, t8, t9, t10, t11;",
+         "    if constexpr (SEG) {",
          "    switch (form) {"]
-    for octant in range(9):
-        o.append(f"    case {octant}:" if octant < 8 else "    default:")
-        o.append(emit(octant, "        ").rstrip("\n"))
-        o.append("        break;")
+    for seg in (True, False):
+        if not seg:
+            o += ["    }", "    } else {", "    switch (form) {"]
+        for octant in range(9):
+            o.append(f"    case {octant}:" if octant < 8 else "    default:")
+            o.append(emit(octant, "        ", seg).rstrip("\n"))
+            o.append("        break;")
+    o += ["    }"]
     o += ["    }", "    return acc;", "}", "",
           "// The same walk for a PIECE of a split tile (generic form): pops from the stack the caller prepared, drops the slots whose",
           "// index range lies outside [ra, rb), and returns after `pops` pops (2), on a full stack (1) or when the stack is empty (0);",
