@@ -67,10 +67,26 @@ __device__ __forceinline__ bool rcpInRange(float x) {
     return e - 27u <= 199u;                                               // ... cut at 2^100 exclusive of the last binade: 27 .. 226
 }
 __device__ __forceinline__ float rcpFast(float x) {
+#if defined(__gfx950__)
     const float r = __builtin_amdgcn_rcpf(x);
     const float e = __builtin_fmaf(-x, r, 1.0f);
     return __builtin_fmaf(e, r, r);
+#else
+    return 1.0f / x;                                                     // (the proof above is gfx950's v_rcp_f32)
+#endif
 }
+
+#if defined(__gfx950__)
+// sqrtf(x) for 2^-96 <= x < +inf: the core of the compiler's correctly rounded sequence (v_sqrt_f32, then the neighbour below
+// and above tested with one fma each).  In that range the full sequence takes neither its 2^32 input scaling nor its
+// zero / infinity fix-up, so this is the same result by construction (tests/test_ray_setup.py: the gate boundary).
+__device__ __forceinline__ float sqrtCore(float x) {
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float down = __uint_as_float(__float_as_uint(s) - 1u), up = __uint_as_float(__float_as_uint(s) + 1u);
+    const float r = __builtin_fmaf(-down, s, x) <= 0.0f ? down : s;
+    return __builtin_fmaf(-up, s, x) > 0.0f ? up : r;
+}
+#endif
 
 // comp:41-59
 __device__ __forceinline__ bool triHit(const Ray& r, F3 v0, F3 e0, F3 e1) {
@@ -113,7 +129,73 @@ __device__ __forceinline__ uint32_t sampleIndex(const TraceParams& p, uint32_t s
     return j >= p.lightTable ? j - p.lightTable : j;
 }
 
-__device__ __forceinline__ Ray makeShadowRay(const TraceParams& p, F3 rel, uint32_t sample, uint32_t pixel = 0) {
+// Smallest |d| per axis (float bits) that the fast set-up admits: 2^-100 (rcpInRange) unless a wide kernel raises it so that
+// the root box times 1/d cannot overflow (wideSetupBound).
+struct SetupBound { uint32_t x, y, z; };
+static constexpr uint32_t RCP_LO_BITS = 27u << 23;                       // 2^-100
+
+// comp:128-146.  *fast (when asked for) tells the caller whether the wave took the fast set-up: then every lane's ray has
+// 2^-100 <= |d| < 2^100 (also >= lo per axis), a finite origin and a finite, non-zero 1/d (raySafe holds).
+// FAST = false: the general code alone (the soft-shadow packet kernels: there the fast path's registers cost scratch).
+template <bool FAST = true>
+__device__ __forceinline__ Ray makeShadowRay(const TraceParams& p, F3 rel, uint32_t sample, uint32_t pixel = 0, bool* fast = nullptr,
+                                             SetupBound lo = SetupBound{ RCP_LO_BITS, RCP_LO_BITS, RCP_LO_BITS }) {
+#if defined(__gfx950__)
+    // The fast set-up: one per-lane predicate, one ballot.  It holds for almost every wave of a real frame, and when it holds
+    // for every lane the arithmetic below is today's, instruction for instruction cheaper and bit for bit the same:
+    // - finite origin and rel, max(mo, mr) >= 2^-113: gmax(epsilonFor(mo), epsilonFor(mr)) == epsilonFor(max(mo, mr)), one
+    //   exponent cut (the larger value's exponent is >= 14, so the clamp does not act and epsilonFor is monotone there);
+    // - point light, 2^-96 <= |d0|^2 < inf: sqrtCore is the compiler's sqrt, and len lies in rcpInRange;
+    // - lo <= |d| < 2^100 on every axis: 1/d is rcpFast, finite and non-zero.
+    // The finiteness of origin and rel is implied (a NaN or Inf in them reaches |d0|^2, or the origin, which is tested);
+    // tests/test_ray_setup.py restates both forms and checks every step.  Any other wave runs the general code below.
+    if constexpr (FAST) {
+        F3 L{ p.light[0], p.light[1], p.light[2] };
+        if (p.nsamples > 1) {
+            const uint32_t j = sampleIndex(p, sample, pixel);
+            L.x = L.x + p.offsets[j][0]; L.y = L.y + p.offsets[j][1]; L.z = L.z + p.offsets[j][2];
+        }
+        F3 origin{ p.cam[0] + rel.x, p.cam[1] + rel.y, p.cam[2] + rel.z };
+        // (|rel| as integers: the order of non-negative floats, and no canonicalising of loaded values in front of a float max)
+        const uint32_t mo = __float_as_uint(__builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(origin.x), __builtin_fabsf(origin.y)),
+                                                            __builtin_fabsf(origin.z)));
+        const uint32_t mr = __builtin_elementwise_max(__builtin_elementwise_max(__float_as_uint(rel.x) & 0x7FFFFFFFu,
+                                                                                __float_as_uint(rel.y) & 0x7FFFFFFFu),
+                                                      __float_as_uint(rel.z) & 0x7FFFFFFFu);
+        const uint32_t m = mo > mr ? mo : mr;
+        // (one ballot per compare, ORed on the scalar unit: a ballot of a combined predicate costs a v_cndmask + v_cmp more)
+        uint64_t bad = __builtin_amdgcn_ballot_w64(m < (14u << 23));     // max(mo, mr) >= 2^-113
+        const float bias = __uint_as_float(m - (13u << 23));              // epsilonFor(max(mo, mr), 13)
+        Ray r;
+        if (p.lightType == 0) {
+            origin.x = origin.x + L.x * bias; origin.y = origin.y + L.y * bias; origin.z = origin.z + L.z * bias;
+            r.o = origin; r.tmax = 1e9f; r.d = L;
+            bad |= __builtin_amdgcn_ballot_w64(!__builtin_amdgcn_classf(origin.x, 0x1F8)) |
+                   __builtin_amdgcn_ballot_w64(!__builtin_amdgcn_classf(origin.y, 0x1F8)) |
+                   __builtin_amdgcn_ballot_w64(!__builtin_amdgcn_classf(origin.z, 0x1F8));
+        } else {
+            const F3 d0 = sub3(L, origin);
+            const float dd = dot3(d0, d0);
+            bad |= __builtin_amdgcn_ballot_w64(__float_as_uint(dd) - (31u << 23) >= 0x7F800000u - (31u << 23));   // 2^-96 <= dd < inf
+            const float inv = rcpFast(sqrtCore(dd));
+            origin.x = origin.x + (d0.x * inv) * bias; origin.y = origin.y + (d0.y * inv) * bias;
+            origin.z = origin.z + (d0.z * inv) * bias;
+            r.o = origin; r.tmax = 1.0f; r.d = sub3(L, origin);           // (an origin that overflowed makes |d| infinite)
+        }
+        bad |= __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(r.d.x) >= __uint_as_float(lo.x))) |
+               __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(r.d.y) >= __uint_as_float(lo.y))) |
+               __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(r.d.z) >= __uint_as_float(lo.z))) |
+               __builtin_amdgcn_ballot_w64(!(__builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(r.d.x), __builtin_fabsf(r.d.y)),
+                                                             __builtin_fabsf(r.d.z)) < 0x1p100f));
+        if (bad == 0) {
+            r.inv = F3{ rcpFast(r.d.x), rcpFast(r.d.y), rcpFast(r.d.z) };
+            if (fast) *fast = true;
+            return r;
+        }
+    }
+#endif
+    if (fast) *fast = false;
+    (void)lo;
     F3 origin{ p.cam[0] + rel.x, p.cam[1] + rel.y, p.cam[2] + rel.z };
     float mo = gmax(gmax(__builtin_fabsf(origin.x), __builtin_fabsf(origin.y)), __builtin_fabsf(origin.z));
     float mr = gmax(gmax(__builtin_fabsf(rel.x), __builtin_fabsf(rel.y)), __builtin_fabsf(rel.z));
@@ -683,6 +765,42 @@ __device__ __forceinline__ bool wideRaySetup(const Ray& r, const float* rootLo, 
     return ok;
 }
 
+// The same constants for a ray of the fast set-up made with wideSetupBound's bound (makeShadowRay): there |d| >= that bound
+// keeps max(|rootLo|, |rootHi|) * |1/d| <= 2^122 < 1e37, and with |o/d| < 1e37 the slack is finite too, so |o/d| is the one
+// test left (every lane of such a ray is raySafe as well).
+__device__ __forceinline__ bool wideRaySetupFast(const Ray& r, const float* rootLo, const float* rootHi, WideRay& w) {
+    const float o[3] = { r.o.x, r.o.y, r.o.z }, inv[3] = { r.inv.x, r.inv.y, r.inv.z };
+    float cU[3], cD[3], oi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float E = __builtin_fmaxf(__builtin_fabsf(rootLo[a] - o[a]), __builtin_fabsf(rootHi[a] - o[a]));
+        oi[a] = o[a] * inv[a];
+        const float slack = (E * __builtin_fabsf(inv[a])) * 4.76837158e-7f + __builtin_fabsf(oi[a]) * 2.38418579e-7f + 7.5e-37f;
+        cU[a] = oi[a] - slack; cD[a] = oi[a] + slack;
+    }
+    w.cU = F3{ cU[0], cU[1], cU[2] }; w.cD = F3{ cD[0], cD[1], cD[2] };
+    return __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(oi[0]), __builtin_fabsf(oi[1])), __builtin_fabsf(oi[2])) < 1e37f;
+}
+
+// node 0: the root's box (wave-uniform, one scalar load)
+__device__ __forceinline__ void wideRoot(const TraceParams& p, float* rootLo, float* rootHi) {
+    const u32x8 root = *(ConstNodePtr)(uintptr_t)uniform64(p.bvh);
+    rootLo[0] = __uint_as_float(root.s0); rootLo[1] = __uint_as_float(root.s1); rootLo[2] = __uint_as_float(root.s2);
+    rootHi[0] = __uint_as_float(root.s4); rootHi[1] = __uint_as_float(root.s5); rootHi[2] = __uint_as_float(root.s6);
+}
+
+// The fast set-up's bound on |d| for the wide walk, per axis, from the root box (wave-uniform: scalar integer work): 2^k with
+// 2^k >= max(|rootLo|, |rootHi|) * 2^-122, and at least rcpInRange's 2^-100.  Then |1/d| <= 2^-k and the product with the
+// root's extent is at most 2^122.  A root coordinate that is Inf or NaN gives +Inf: no ray passes.
+__device__ __forceinline__ uint32_t wideAxisBound(float lo, float hi) {
+    const uint32_t a = __float_as_uint(lo) & 0x7FFFFFFFu, b = __float_as_uint(hi) & 0x7FFFFFFFu;
+    const uint32_t e = (a > b ? a : b) >> 23;                            // biased exponent of the larger: R < 2^(e - 126)
+    return e == 255u ? 0x7F800000u : ((e > 148u ? e : 148u) - 121u) << 23;
+}
+__device__ __forceinline__ SetupBound wideSetupBound(const float* rootLo, const float* rootHi) {
+    return SetupBound{ wideAxisBound(rootLo[0], rootHi[0]), wideAxisBound(rootLo[1], rootHi[1]), wideAxisBound(rootLo[2], rootHi[2]) };
+}
+
 // Near end of the cheap test.  SEG (a segment ray: d = L - o, tmax = 1, the point light): clamped to [0, 1] instead of
 // max(near, 0) -- the clamp bit of the v_max3 (dx10_clamp), one VALU fewer.  clamp(n) <= max(n, 0) for every n, so the
 // test accepts a superset; the extra boxes have near > 1 and 1 <= far < near: beyond the light.
@@ -960,15 +1078,15 @@ __device__ __forceinline__ bool wideWalk(const TraceParams& p, const NodeStream&
 // each carries one set of loop forms.
 template <bool ASM, bool SEG>
 __device__ __forceinline__ bool traverseWide(const TraceParams& p, const NodeStream& bvh, const Ray& r, bool live, uint32_t* lds,
-                                             uint32_t* laneStack, int32_t* dissolved, ShareDiag* diag) {
+                                             uint32_t* laneStack, int32_t* dissolved, ShareDiag* diag, bool fast = false) {
     const uint64_t liveMask = __builtin_amdgcn_ballot_w64(live);
     if (dissolved) *dissolved = 0;
     if (liveMask == 0) return false;
-    const u32x8 root = *(ConstNodePtr)(uintptr_t)uniform64(p.bvh);          // node 0: the root's box
-    const float rootLo[3] = { __uint_as_float(root.s0), __uint_as_float(root.s1), __uint_as_float(root.s2) };
-    const float rootHi[3] = { __uint_as_float(root.s4), __uint_as_float(root.s5), __uint_as_float(root.s6) };
+    float rootLo[3], rootHi[3];
+    wideRoot(p, rootLo, rootHi);
     WideRay w;
-    const bool ok = wideRaySetup(r, rootLo, rootHi, w) && raySafe(r);
+    // (fast: the ray came from makeShadowRay's fast set-up with wideSetupBound's bound -- wideRaySetupFast)
+    const bool ok = fast ? wideRaySetupFast(r, rootLo, rootHi, w) : (wideRaySetup(r, rootLo, rootHi, w) && raySafe(r));
     if (__builtin_amdgcn_ballot_w64(live && !ok) != 0)                       // a NaN or an overflow could occur: exact walk
         return traverseShare<false>(bvh, r, live, 0u, lds);
     const uint32_t oct = (__float_as_uint(r.inv.x) >> 31) | ((__float_as_uint(r.inv.y) >> 31) << 1) | ((__float_as_uint(r.inv.z) >> 31) << 2);
@@ -1475,13 +1593,20 @@ void shadowMaskPacketKernel(TraceParams p) {
     for (uint32_t s = SPLIT > 1 ? wave : 0u; s < ns; s += SPLIT) {
         Ray r[K];
         bool occluded[K];
+        [[maybe_unused]] bool fast = false;
+        if constexpr (WIDE != 0) {
+            float rootLo[3], rootHi[3];
+            wideRoot(p, rootLo, rootHi);
+            r[0] = makeShadowRay<!SOFT && WIDE != 3>(p, rel[0], s, (uint32_t)pix[0], &fast, wideSetupBound(rootLo, rootHi));
+        } else {
 #pragma unroll
-        for (int k = 0; k < K; ++k) r[k] = makeShadowRay(p, rel[k], s, (uint32_t)pix[k]);
+            for (int k = 0; k < K; ++k) r[k] = makeShadowRay<!SOFT>(p, rel[k], s, (uint32_t)pix[k]);
+        }
         if (!PLAIN && p.waveStats && s < SPLIT) {    // diagnostics: the G-buffer texel is in and the first ray exists
             asm volatile("" :: "v"(r[0].inv.x), "v"(r[0].inv.y), "v"(r[0].inv.z), "v"(r[0].o.x));
             tReady = __builtin_amdgcn_s_memtime();
         }
-        if constexpr (WIDE != 0) occluded[0] = traverseWide<WIDE != 2, SEG>(p, bvh, r[0], live[0], lds, laneStack, &left, &shareDiag);
+        if constexpr (WIDE != 0) occluded[0] = traverseWide<WIDE != 2, SEG>(p, bvh, r[0], live[0], lds, laneStack, &left, &shareDiag, fast);
         else traversePacket<K, PREFETCH>(p, bvh, r, live, occluded, lds, &left, &shareDiag);
 #pragma unroll
         for (int k = 0; k < K; ++k) lit[k] += occluded[k] ? 0u : 1u;                     // comp:148

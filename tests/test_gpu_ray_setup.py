@@ -1,0 +1,136 @@
+"""Masks byte for byte against the CPU oracle on G-buffers built so that waves fall on both sides of every condition of the
+fast ray set-up's gate (makeShadowRay, tests/test_ray_setup.py): texels at 0, denormal, near 2^-113, huge and non-finite;
+a point light on a texel (len = 0); lights at large coordinates; one bad lane in an otherwise good tile.  Both light
+kinds, kernels 3, 8 and 9, wide_lane, a split table with pieces, and a 16-sample soft light."""
+import numpy as np
+import pytest
+
+import oracle
+from raytracedshadows_amd import api
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    assert api.device_count() >= 1, "no GPU visible: the shadow path has no CPU fallback"
+    c = api.ShadowContext(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def soup():
+    rng = np.random.RandomState(21)
+    c = rng.random_sample((4000, 1, 3))
+    tri = c + (rng.random_sample((4000, 3, 3)) - 0.5) * 0.08
+    floor = np.array([[[-1, 0, -1], [2, 0, -1], [2, 0, 2]], [[-1, 0, -1], [2, 0, 2], [-1, 0, 2]]], np.float64)
+    tri = np.concatenate([tri, floor]).astype(np.float32)
+    verts = np.zeros((tri.shape[0] * 3, 8), np.float32)
+    verts[:, :3] = tri.reshape(-1, 3)
+    idx = np.arange(tri.shape[0] * 3, dtype=np.uint32)
+    return api.BVHBuilder().build(verts, 8, idx, tri.shape[0]).m_packedNodes, tri
+
+
+EDGE = np.array([0.0, -0.0, 1e-45, 3e-39, 2.0 ** -114, 2.0 ** -113, 2.0 ** -112, 1e-30, 1e30, 3e38, np.inf, -np.inf, np.nan],
+                np.float32)
+
+
+def _frame(tri, W=96, H=64, seed=5):
+    """Points on triangles; 8x8 tiles of the first tile row get one edge texel each (one bad lane in a good tile), the
+    second tile row whole tiles of edge values, the rest stays ordinary."""
+    rng = np.random.RandomState(seed)
+    t = tri[rng.randint(0, tri.shape[0], H * W)].astype(np.float64)
+    u, v = rng.random_sample((2, H * W, 1))
+    flip = (u + v) > 1
+    u, v = np.where(flip, 1 - u, u), np.where(flip, 1 - v, v)
+    pos = np.zeros((H, W, 4), np.float32)
+    pos[..., :3] = (t[:, 0] + u * (t[:, 1] - t[:, 0]) + v * (t[:, 2] - t[:, 0])).reshape(H, W, 3)
+    for i in range(W // 8):                                          # one bad lane per tile, one coordinate
+        pos[3, 8 * i + 5, i % 3] = EDGE[i % len(EDGE)]
+    for i in range(W // 8):                                          # whole tiles of edge values
+        vals = rng.choice(EDGE, (8, 8, 3))
+        keep = rng.random_sample((8, 8, 3)) < 0.5
+        pos[8:16, 8 * i:8 * i + 8, :3] = np.where(keep, pos[8:16, 8 * i:8 * i + 8, :3], vals)
+    pos[20, 40, :3] = [0.5, 0.5, 0.5]                                # the point light below sits exactly on this texel
+    return pos
+
+
+def _want(packed, k, pos, light):
+    H, W = pos.shape[:2]
+    want, _, _ = oracle.shadow_mask(packed, k.as_array(), oracle.light_from_product(light, k), pos, W, H)
+    return want
+
+
+LIGHTS = {
+    "on_texel": (api.Light.POINT, [0.5, 0.5, 0.5]),
+    "above": (api.Light.POINT, [0.4, 1.6, 0.3]),
+    "far": (api.Light.POINT, [3e19, 2e19, -1e19]),
+    "huge": (api.Light.POINT, [1e38, 1e37, 1.0]),
+    "directional": (api.Light.DIRECTIONAL, [0.3, 0.8, 0.5]),
+    "directional_axis": (api.Light.DIRECTIONAL, [0.0, 1.0, 0.0]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(LIGHTS))
+def test_gate_edges_equal_the_oracle(ctx, soup, name):
+    packed, tri = soup
+    ctx.set_bvh(packed)
+    pos = _frame(tri)
+    H, W = pos.shape[:2]
+    k = api.RayTracingConstants.make([0, 0, 0], [0.3, 0.8, 0.5], W, H)
+    kind, xyz = LIGHTS[name]
+    light = api.Light.make(kind, np.array(xyz, np.float32))
+    want = _want(packed, k, pos, light)
+    defaults = {key: ctx.get_option(key) for key in ("kernel", "wide_lane")}
+    try:
+        for kernel in (3, 8, 9):
+            for lane in ((0, 1) if kernel == 8 else (0,)):
+                ctx.set_option("kernel", kernel)
+                ctx.set_option("wide_lane", lane)
+                got = ctx.trace_shadow_mask(k, pos, W, H, light=light)
+                assert (got == want).all(), (name, kernel, lane, int((got != want).sum()))
+    finally:
+        for key, val in defaults.items():
+            ctx.set_option(key, val)
+
+
+def test_gate_edges_soft_light_and_split_pieces(ctx, soup):
+    packed, tri = soup
+    ctx.set_bvh(packed)
+    pos = _frame(tri, seed=8)
+    H, W = pos.shape[:2]
+    k = api.RayTracingConstants.make([0, 0, 0], [0.3, 0.8, 0.5], W, H)
+    rng = np.random.RandomState(13)
+    offsets = np.zeros((16, 4), np.float32)
+    offsets[:, :3] = (rng.random_sample((16, 3)) * 2 - 1) * 0.05
+    soft = api.Light.make(api.Light.POINT, np.array([0.5, 0.5, 0.5], np.float32), offsets)
+    point = api.Light.make(api.Light.POINT, np.array([0.5, 0.5, 0.5], np.float32))
+    defaults = {key: ctx.get_option(key) for key in ("kernel", "wide_lane", "block_waves")}
+    d_pos, d_mask = ctx.malloc(pos.nbytes), ctx.malloc(W * H)
+    ctx.h2d(d_pos, pos)
+    try:
+        want = _want(packed, k, pos, soft)
+        for kernel in (3, 8):
+            ctx.set_option("kernel", kernel)
+            got = ctx.trace_shadow_mask(k, pos, W, H, light=soft)
+            assert (got == want).all(), ("soft", kernel, int((got != want).sum()))
+        want = _want(packed, k, pos, point)
+        ctx.set_option("wide_lane", 0)
+        ctx.set_option("block_waves", 1)
+        ctx.set_option("kernel", 8)
+        tiles, _ = ctx.plan_splits(k, d_pos, W, H, d_mask, light=point, min_life_us=0.3, piece_us=0.2, max_pieces=16,
+                                   front_share=0.4)
+        assert tiles > 0 and ctx.get_option("split_pieces") > 0
+        got = np.full((H, W), 9, np.uint8)
+        ctx.h2d(d_mask, got)
+        ctx.trace_shadow_mask_device(k, d_pos, W, H, d_mask, light=point)
+        ctx.synchronize()
+        ctx.d2h(got, d_mask)
+        assert (got == want).all(), ("split table", int((got != want).sum()))
+    finally:
+        for key, val in defaults.items():
+            ctx.set_option(key, val)
+        ctx.clear_splits()
+        ctx.free(d_pos)
+        ctx.free(d_mask)
