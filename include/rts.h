@@ -207,6 +207,12 @@ int rts_ctx_set_bvh(rts_ctx* ctx, const rts_vec4u* packed, size_t count_vec4);
  *   "tune_for_motion" 0 (default): rts_ctx_autotune picks the fastest table for THIS frame; 1: only a table that keeps over a
  *                   camera path -- the whole dispatch in table order sorted by blocks of 16 x 16 tiles (rts_split_plan:
  *                   life_block, xcd_square), no pieces, no front lists
+ *   "follow"        0 (default); 1: FOLLOW MODE -- one-sample traces in a frame loop run the whole dispatch in an order planned on
+ *                   the device from the tile lives of the stream's last trace of the same dispatch (rts_ctx_read_follow below)
+ *   "follow_block"  life_block B of follow mode's order, 1..64 (default 8)
+ *   "follow_square" xcd_square S of follow mode's order, 0..65535 (default 32; 0: no deal over the XCDs)
+ *                   get only: "follow_streams" (streams that hold follow state), "follow_traces" (traces that recorded lives),
+ *                   "follow_ordered" (traces that ran a rolling order)
  *   "piece_stats"   diagnostics, see rts_ctx_read_piece_stats;  get only: "split_tiles", "front_tiles", "split_pieces"
  *   "lds_pad"       experiment: extra dynamic LDS bytes per one-wave packet workgroup (throttles occupancy; default 0)
  *   "wave_stats"    diagnostics, see rts_ctx_read_wave_stats
@@ -384,6 +390,29 @@ int rts_ctx_get_split_plan(rts_ctx* ctx, rts_split_plan* out);
  * lane-per-ray phase, end of the walk}, {wide nodes entered | stack entries at the dissolve << 32}, lanes found occluded.
  * Either pointer may be NULL. */
 int rts_ctx_read_piece_stats(rts_ctx* ctx, uint32_t* records, uint64_t* clocks, size_t pieces);
+/* ---- follow mode (option "follow" 1): a split-table order that follows a moving camera, planned on the device -------------
+ * A table planned on one frame fits that frame; a camera that moves 0.1 % of its view distance per frame makes it stale.  In follow
+ * mode every one-sample trace where an installed split table could apply today (kernel 3 or 8, one tile per workgroup on a 2-D grid,
+ * the private copy, no "wave_stats", no "wide_lane"; stripes with power-of-two bands and "row_order" 0) and none does -- an installed
+ * table or a caller's tile order always wins -- records how long each tile's wave lived, and kernels on the same stream then plan
+ * from those lives the order the NEXT trace of the same dispatch on that stream runs in: the front-only table with every tile in
+ * it (rts_split_plan front_share 1, no pieces) -- half-octave bands of life, longest first, row-major inside a band, a tile as long
+ * as the longest of its follow_block x follow_block block, each band dealt over the XCDs by follow_square squares:
+ *   DEAL.  Inside a band of L records that starts at record R, XCD x's own tiles (those of the squares (sx + 3 sy) mod 8 = x, in
+ *   image order) fill the band's positions q with (R + q) mod 8 = x, in order, until the tiles or the positions run out.  The
+ *   tiles left over, in XCD order and then image order, fill the positions still vacant in increasing order.  (Prefix sums
+ *   compute it -- unlike rts_ctx_plan_splits' greedy deal, which also differs when an XCD runs out.)
+ * Nothing is read back, nothing waits on the host, and a steady frame allocates nothing.  The first trace of a geometry on a stream
+ * runs the everyday launch (and records); later ones the stream's rolling order.  State is per stream, for one dispatch geometry
+ * (W, H, row range, stripe: another one starts the stream over), at most 8 streams (the least recently used is evicted); frames in
+ * flight on two streams never share a buffer.  rts_stream_destroy releases the stream's state; rts_ctx_set_bvh, a GPU build's
+ * install, "follow" 0 and rts_ctx_destroy drop all of it; rts_ctx_refit_bvh_device keeps it (tile coordinates do not change).  A
+ * trace on a stream under graph capture never allocates: without state it runs the everyday launch.  Results never depend on it.
+ *
+ * Diagnostics: synchronises `stream` and returns the life of every tile of its last traced dispatch in 100 MHz ticks (row-major
+ * tile id; either pointer may be NULL) and the order the next trace runs (record i -> bx | by << 16).  RTS_ERR_INVALID_ARG when the
+ * stream holds no state or `tiles` is not the dispatch's tile count.  rtsh_follow_order (rts_scene.h) is the same order on the host. */
+int rts_ctx_read_follow(rts_ctx* ctx, void* stream, uint32_t* lives, uint32_t* order, size_t tiles);
 /* Self-test behind one of the kernels' shortcuts: 1.0f / x (comp:44, comp:77) is computed as v_rcp_f32 + one Newton step in
  * fma arithmetic when 2^-100 <= |x| <= 2^100 in a whole wave.  That this is the correctly rounded quotient is checked HERE for
  * every bit pattern of the range on the context's device: out[0] = patterns checked (3 355 443 200), out[1] = patterns whose

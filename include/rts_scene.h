@@ -70,6 +70,14 @@ float rtsh_obj_parse_float(const char* text, int* consumed);
 int rtsh_split_front_order(const float* life_us, const uint32_t* tiles, size_t n, uint32_t first_record, uint32_t xcd_square,
                            uint32_t life_block, uint32_t* order_out);
 
+/* Follow mode's order (include/rts.h, rts_ctx_read_follow) on the host: the checker of the device planner.  life_ticks[t]: the life of
+ * tile t = bx + by * blocks_x of a blocks_x x blocks_y dispatch in 100 MHz ticks; a tile's band is rts_ctx_plan_splits' half-octave of
+ * ticks * 0.01f us (of the longest tile of its life_block x life_block block, 0 / 1: itself; at most 64); xcd_square S > 0: each band
+ * dealt by the DEAL rule of include/rts.h.  order_out[r] = tile id of record first_record + r.  With S = 0 the order equals
+ * rtsh_split_front_order's for the same lives and life_block. */
+int rtsh_follow_order(const uint32_t* life_ticks, uint32_t blocks_x, uint32_t blocks_y, uint32_t first_record, uint32_t xcd_square,
+                      uint32_t life_block, uint32_t* order_out);
+
 #ifdef __cplusplus
 }
 #endif

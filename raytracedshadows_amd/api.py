@@ -166,6 +166,20 @@ def split_front_order(life_us, tiles, first_record=0, xcd_square=0, life_block=0
     return out
 
 
+_sig("rtsh_follow_order", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rts_ctx_read_follow", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
+
+
+def follow_order(life_ticks, blocks_x, blocks_y, first_record=0, xcd_square=0, life_block=1):
+    """rtsh_follow_order: follow mode's order on the host (no device) -- row-major tile ids in record order."""
+    life = np.ascontiguousarray(life_ticks, np.uint32).ravel()
+    if life.size != blocks_x * blocks_y:
+        raise RtsError(1, "follow_order: life_ticks must hold blocks_x * blocks_y entries")
+    out = np.zeros(life.size, np.uint32)
+    _check(_lib.rtsh_follow_order(_ptr(life), blocks_x, blocks_y, first_record, xcd_square, life_block, _ptr(out)), "rtsh_follow_order")
+    return out
+
+
 def stripe_rows(height, band_rows, n_stripes, stripe):
     """rtsh_stripe_rows: the virtual rows of one interleaved stripe's dispatch (host logic, no device) -- band_rows x the
     bands the stripe owns, 0 for a stripe without a band."""
@@ -498,6 +512,14 @@ class ShadowContext:
             return
         order = np.ascontiguousarray(order, np.uint32)
         _check(_lib.rts_ctx_set_tile_order(self._h, _ptr(order), order.size), "rts_ctx_set_tile_order")
+
+    def read_follow(self, tiles, stream=None):
+        """rts_ctx_read_follow: (lives in 100 MHz ticks per row-major tile of the stream's last traced dispatch, the order its next
+        trace runs as bx | by << 16 per record).  Synchronises the stream."""
+        lives = np.zeros(tiles, np.uint32)
+        order = np.zeros(tiles, np.uint32)
+        _check(_lib.rts_ctx_read_follow(self._h, C.c_void_p(stream or 0), _ptr(lives), _ptr(order), tiles), "rts_ctx_read_follow")
+        return lives, order
 
     def read_wave_stats(self, waves):
         out = np.zeros((waves, 4), dtype=np.uint64)

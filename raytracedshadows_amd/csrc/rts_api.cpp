@@ -97,6 +97,22 @@ struct rts_ctx {
         hipEvent_t ev[2] = { nullptr, nullptr };
     } refit;
     int refitTreelet = 1024;                 // option "refit_treelet": nodes per treelet workgroup (speed only)
+    // follow mode (option "follow", rts_follow.hip): per stream, the lives of the last traced dispatch and the order the next one
+    // runs in -- one dispatch geometry per stream; at most 8 streams, the least recently used evicted
+    struct Follow {
+        void* stream = nullptr;
+        uint32_t W = 0, H = 0, rowBegin = 0, rowEnd = 0, bandRows = 0, nStripes = 0, stripe = 0, blocksX = 0, blocksY = 0;
+        void* d_mem = nullptr;               // one allocation: lives (2 u32 per tile), front map, all-ones skip map, planner scratch
+        uint32_t* d_lives = nullptr; uint32_t* d_frontMap = nullptr; uint32_t* d_skipMap = nullptr; void* d_scratch = nullptr;
+        uint32_t frontStride = 0;
+        bool planned = false;                // the front map holds an order (the planner ran after a trace of this geometry)
+        uint64_t lastUse = 0;
+    };
+    std::vector<Follow> follow;
+    int followOn = 0;                        // option "follow"
+    int followBlock = 8;                     // option "follow_block": life_block B of the rolling order
+    int followSquare = 32;                   // option "follow_square": xcd_square S of the rolling order
+    uint64_t followClock = 0, followTraces = 0, followOrdered = 0;
 };
 
 namespace {
@@ -130,6 +146,14 @@ void clearSplits(rts_ctx* c) {
     if (t.d_frontMap) (void)hipFree(t.d_frontMap);
     for (auto& e : t.state) if (e.second) (void)hipFree(e.second);
     t = rts_ctx::Splits();
+}
+
+void freeFollow(rts_ctx::Follow& f) { if (f.d_mem) (void)hipFree(f.d_mem); f = rts_ctx::Follow(); }
+
+// follow mode: every stream's state (rts_ctx_set_bvh, a GPU build's install, option "follow" 0, rts_ctx_destroy)
+void dropFollow(rts_ctx* c) {
+    for (auto& f : c->follow) freeFollow(f);
+    c->follow.clear();
 }
 
 // the {occluded, done} words of the split tiles for traces on `stream` (zeroed once; every launch leaves them zero)
@@ -371,6 +395,7 @@ int rts_ctx_destroy(rts_ctx* c) {
     if (c->refit.d_status) (void)hipFree(c->refit.d_status);
     for (hipEvent_t e : c->refit.ev) if (e) (void)hipEventDestroy(e);
     clearSplits(c);
+    dropFollow(c);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     for (hipEvent_t e : c->marks) if (e) (void)hipEventDestroy(e);
@@ -394,6 +419,7 @@ int rts_ctx_set_bvh(rts_ctx* c, const rts_vec4u* packed, size_t count) {
     c->d_bvh = d; c->bvhVec4 = count; c->P = P;
     dropRefit(c);
     clearSplits(c);                      // (a split table holds node indices of the stream it was planned on)
+    dropFollow(c);                       // (... a rolling order the lives of the tiles on the old scene)
     if (c->tileOrderPlanned) (void)rts_ctx_set_tile_order(c, nullptr, 0);   // (... a planned tile order the lives of its tiles)
     return finishInstall(c, true);       // finite / ordered / enclosed are decided on the device; private wide copy
 }
@@ -424,6 +450,14 @@ int rts_ctx_set_option(rts_ctx* c, const char* key, int value) {
     if (!strcmp(key, "tile_splits")) { c->useSplits = value ? 1 : 0; return RTS_OK; }     // 0: traces ignore an installed split table
     if (!strcmp(key, "tile_order")) { c->useTileOrder = value ? 1 : 0; return RTS_OK; }            // 0: traces ignore an installed tile order
     if (!strcmp(key, "tune_for_motion")) { c->tuneForMotion = value ? 1 : 0; return RTS_OK; }   // rts_ctx_autotune: only tables that keep over a camera path
+    if (!strcmp(key, "follow")) {                // follow mode: traces record tile lives and run the order planned from the last ones
+        if (value != 0 && value != 1) return RTS_ERR_INVALID_ARG;
+        RTS_HIP(hipSetDevice(c->device));
+        if (!value) dropFollow(c);
+        c->followOn = value; return RTS_OK;
+    }
+    if (!strcmp(key, "follow_block")) { if (value < 1 || value > 64) return RTS_ERR_INVALID_ARG; c->followBlock = value; return RTS_OK; }
+    if (!strcmp(key, "follow_square")) { if (value < 0 || value > 65535) return RTS_ERR_INVALID_ARG; c->followSquare = value; return RTS_OK; }
     if (!strcmp(key, "piece_stats")) {          // diagnostics: value = pieces to stamp (0 = off), see rts_ctx_read_piece_stats
         RTS_HIP(hipSetDevice(c->device));
         if (c->d_pieceClock) { RTS_HIP(hipFree(c->d_pieceClock)); c->d_pieceClock = nullptr; c->pieceClockCount = 0; }
@@ -477,6 +511,12 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "wide_nodes")) { *value = (int)c->wideCount; return RTS_OK; }
     if (!strcmp(key, "tile_splits")) { *value = c->useSplits; return RTS_OK; }
     if (!strcmp(key, "tune_for_motion")) { *value = c->tuneForMotion; return RTS_OK; }
+    if (!strcmp(key, "follow")) { *value = c->followOn; return RTS_OK; }
+    if (!strcmp(key, "follow_block")) { *value = c->followBlock; return RTS_OK; }
+    if (!strcmp(key, "follow_square")) { *value = c->followSquare; return RTS_OK; }
+    if (!strcmp(key, "follow_streams")) { *value = (int)c->follow.size(); return RTS_OK; }
+    if (!strcmp(key, "follow_traces")) { *value = (int)(c->followTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "follow_ordered")) { *value = (int)(c->followOrdered & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
     if (!strcmp(key, "tile_order_planned")) { *value = c->tileOrderPlanned ? 1 : 0; return RTS_OK; }
@@ -507,6 +547,80 @@ extern "C" int rtsh_stripe_rows(uint32_t H, uint32_t band_rows, uint32_t n_strip
     if (!rows || band_rows == 0 || n_stripes == 0 || stripe >= n_stripes) return RTS_ERR_INVALID_ARG;
     *rows = stripeRows(H, band_rows, n_stripes, stripe);
     return RTS_OK;
+}
+
+static int lifeBand(float us);
+
+// follow mode: the per-band lower bounds of the tick count, from the host's own lifeBand (which the device then never evaluates:
+// it compares integers).  Bands grow with the tick count, so each bound is a binary search over the 32-bit counts.
+static const rts::FollowBands& followBands() {
+    static const rts::FollowBands table = [] {
+        rts::FollowBands t{};
+        for (uint32_t i = 0; i < rts::FOLLOW_BANDS; ++i) {
+            const int b = rts::FOLLOW_BAND_LOW + (int)i;
+            uint64_t lo = 0, hi = 0xFFFFFFFFull;                 // the smallest count whose band is b or more
+            while (lo < hi) {
+                const uint64_t mid = (lo + hi) >> 1;
+                if (lifeBand((float)(uint32_t)mid * 0.01f) >= b) hi = mid; else lo = mid + 1;
+            }
+            t.minTicks[i] = (uint32_t)lo;
+        }
+        return t;
+    }();
+    return table;
+}
+
+// follow mode: the state of `stream` for this dispatch geometry.  A stream seen with another geometry starts over; a ninth stream
+// evicts the least recently used.  Created and reset outside graph capture only (nothing is allocated in a captured trace):
+// NULL = run the everyday launch.
+static rts_ctx::Follow* followFor(rts_ctx* c, void* stream, const TraceParams& p, uint32_t bandRows, uint32_t nStripes, uint32_t stripe) {
+    rts_ctx::Follow* f = nullptr;
+    for (auto& e : c->follow) if (e.stream == stream) { f = &e; break; }
+    if (f && f->d_mem && f->W == p.W && f->H == p.H && f->rowBegin == p.rowBegin && f->rowEnd == p.rowEnd && f->bandRows == bandRows &&
+        f->nStripes == nStripes && f->stripe == stripe && f->blocksX == p.blocksX && f->blocksY == p.blocksY) {
+        f->lastUse = ++c->followClock;
+        return f;
+    }
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &capture) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (capture != hipStreamCaptureStatusNone) return nullptr;
+    if (f) freeFollow(*f);
+    else {
+        if (c->follow.size() >= 8) {
+            size_t lru = 0;
+            for (size_t i = 1; i < c->follow.size(); ++i) if (c->follow[i].lastUse < c->follow[lru].lastUse) lru = i;
+            freeFollow(c->follow[lru]);
+            c->follow.erase(c->follow.begin() + (long)lru);
+        }
+        try { c->follow.emplace_back(); } catch (...) { return nullptr; }
+        f = &c->follow.back();
+    }
+    const uint32_t n = p.blocksX * p.blocksY, stride = (n + 7u) / 8u;
+    const auto al = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
+    const size_t livesB = al((size_t)n * 8), mapB = al((size_t)stride * 32), skipB = al(((size_t)n + 31) / 32 * 4 + 4);
+    const size_t scratchB = rts::followScratchBytes(n);
+    void* d = nullptr;
+    hipError_t e = hipMalloc(&d, livesB + mapB + skipB + scratchB);
+    if (e == hipSuccess) e = hipMemsetAsync((char*)d + livesB + mapB, 0xFF, skipB, (hipStream_t)stream);    // (on the stream that uses it)
+    if (e == hipSuccess) e = hipMemsetAsync((char*)d + livesB + mapB + skipB, 0, scratchB, (hipStream_t)stream);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        if (d) (void)hipFree(d);
+        c->follow.erase(c->follow.begin() + (f - c->follow.data()));
+        return nullptr;
+    }
+    f->stream = stream;
+    f->W = p.W; f->H = p.H; f->rowBegin = p.rowBegin; f->rowEnd = p.rowEnd; f->bandRows = bandRows; f->nStripes = nStripes; f->stripe = stripe;
+    f->blocksX = p.blocksX; f->blocksY = p.blocksY;
+    f->d_mem = d;
+    f->d_lives = (uint32_t*)d;
+    f->d_frontMap = (uint32_t*)((char*)d + livesB);
+    f->d_skipMap = (uint32_t*)((char*)d + livesB + mapB);
+    f->d_scratch = (char*)d + livesB + mapB + skipB;
+    f->frontStride = stride;
+    f->planned = false;
+    f->lastUse = ++c->followClock;
+    return f;
 }
 
 static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
@@ -612,9 +726,33 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
             if (c->d_pieceClock && c->pieceClockCount >= sp.nPieces) p.pieceClock = c->d_pieceClock;
         }
     }
-    c->lastKernel = rts::kernelName(variant, true);
+    // follow mode: where a split table could apply but none does, the trace records its tile lives and runs the order the planner
+    // made from the lives of the stream's last trace of this dispatch (the front-only table launch, every tile a record: launch
+    // parameters that depend on the geometry alone); then the planner's kernels make the next one, in the stream
+    rts_ctx::Follow* fol = nullptr;
+    if (c->followOn && !p.pieces && (variant == rts::V_PACKET || variant == rts::V_WIDE) && c->blockWaves == 1 && p.nsamples == 1 &&
+        p.grid2d && !p.waveStats && !c->wideLane && p.wide && (n_stripes <= 1 || (p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0)))
+        fol = followFor(c, stream, p, band_rows, n_stripes, stripe);
+    if (fol) {
+        p.followLives = fol->d_lives;
+        if (fol->planned) {
+            p.skipMap = fol->d_skipMap; p.pieces = fol->d_skipMap;            // (no tile rows and no pieces: neither is read)
+            p.nPieces = p.nBlocks; p.pieceRows = p.blocksY;
+            p.frontMap = fol->d_frontMap; p.frontStride = fol->frontStride;
+            p.allInTable = 1u; p.hasPieces = 0u; p.tileState = nullptr;
+            ++c->followOrdered;
+        }
+        ++c->followTraces;
+    }
+    c->lastKernel = fol ? (variant == rts::V_WIDE ? "shadowMaskFollowKernel<1,wide>" : "shadowMaskFollowKernel<1>") : rts::kernelName(variant, true);
     ++c->launches;
-    return hipStatus(rts::launchShadowMask(variant, c->blockWaves, p, (hipStream_t)stream, (uint32_t)c->ldsPad));
+    hipError_t e = rts::launchShadowMask(variant, c->blockWaves, p, (hipStream_t)stream, (uint32_t)c->ldsPad);
+    if (e == hipSuccess && fol) {
+        e = rts::launchFollowPlan(fol->d_lives, p.blocksX, p.blocksY, (uint32_t)c->followSquare, (uint32_t)c->followBlock, followBands(),
+                                  fol->d_scratch, fol->d_frontMap, fol->frontStride, (hipStream_t)stream);
+        if (e == hipSuccess) fol->planned = true;
+    }
+    return hipStatus(e);
 }
 
 int rts_trace_shadow_mask_device(rts_ctx* c, const rts_constants* k, const rts_light* light,
@@ -734,6 +872,8 @@ int rts_stream_create(rts_ctx* c, void** stream) {
 int rts_stream_destroy(rts_ctx* c, void* stream) {
     if (!c || !stream) return RTS_ERR_INVALID_ARG;
     RTS_HIP(hipSetDevice(c->device));
+    for (size_t i = 0; i < c->follow.size(); ++i)
+        if (c->follow[i].stream == stream) { freeFollow(c->follow[i]); c->follow.erase(c->follow.begin() + (long)i); break; }
     RTS_HIP(hipStreamDestroy((hipStream_t)stream));
     return RTS_OK;
 }
@@ -816,6 +956,7 @@ int rts_ctx_adopt_device_bvh(rts_ctx* c, void* d_packed, size_t count, uint32_t 
     c->bvhVec4 = count; c->P = P;
     dropRefit(c);
     clearSplits(c);
+    dropFollow(c);
     if (c->tileOrderPlanned) (void)rts_ctx_set_tile_order(c, nullptr, 0);
     // the same checks as for an uploaded stream, on the device: layout, finiteness (edges of finite vertices can
     // overflow), box order, enclosure.  A refused stream stays the caller's to free.
@@ -1055,6 +1196,73 @@ extern "C" int rtsh_split_front_order(const float* life_us, const uint32_t* tile
         sortFront(front);
         if (xcd_square) dealOverXcds(front, first_record, xcd_square);
         for (size_t r = 0; r < n; ++r) order_out[r] = index[front[r].tile];
+    } catch (...) { return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+// Follow mode's order on the host (include/rts_scene.h): the checker of the device planner (rts_follow.hip), written plainly --
+// a stable sort by band, then the deal of include/rts.h by filling positions.
+extern "C" int rtsh_follow_order(const uint32_t* life_ticks, uint32_t blocks_x, uint32_t blocks_y, uint32_t first_record, uint32_t xcd_square,
+                                 uint32_t life_block, uint32_t* order_out) {
+    const uint64_t n64 = (uint64_t)blocks_x * blocks_y;
+    if ((n64 && (!life_ticks || !order_out)) || n64 > (1ull << 31) || xcd_square > 65535u || life_block > 64u) return RTS_ERR_INVALID_ARG;
+    try {
+        const uint32_t n = (uint32_t)n64, B = life_block > 1 ? life_block : 1u, S = xcd_square;
+        std::vector<uint32_t> life(life_ticks, life_ticks + n);
+        if (B > 1) {
+            const uint32_t gx = (blocks_x + B - 1) / B;
+            std::vector<uint32_t> m((size_t)gx * ((blocks_y + B - 1) / B), 0u);
+            for (uint32_t t = 0; t < n; ++t) { uint32_t& v = m[(size_t)(t / blocks_x / B) * gx + (t % blocks_x) / B]; if (life[t] > v) v = life[t]; }
+            for (uint32_t t = 0; t < n; ++t) life[t] = m[(size_t)(t / blocks_x / B) * gx + (t % blocks_x) / B];
+        }
+        std::vector<int> band(n);
+        for (uint32_t t = 0; t < n; ++t) band[t] = lifeBand((float)life[t] * 0.01f);
+        std::vector<uint32_t> sorted(n);
+        for (uint32_t t = 0; t < n; ++t) sorted[t] = t;
+        std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return band[a] > band[b]; });
+        if (!S) { std::copy(sorted.begin(), sorted.end(), order_out); return RTS_OK; }
+        for (uint32_t i = 0; i < n;) {
+            uint32_t j = i;
+            while (j < n && band[sorted[j]] == band[sorted[i]]) ++j;
+            const uint32_t R = first_record + i, L = j - i;
+            std::vector<uint32_t> bucket[8];
+            for (uint32_t q = i; q < j; ++q) {
+                const uint32_t t = sorted[q], bx = t % blocks_x, by = t / blocks_x;
+                bucket[((bx / S) + (by / S) * 3u) & 7u].push_back(t);
+            }
+            std::vector<uint32_t> out(L, 0xFFFFFFFFu), left;
+            for (uint32_t y = 0; y < 8; ++y) {
+                const uint32_t off = (y - R) & 7u, slots = L > off ? (L - 1 - off) / 8 + 1 : 0;
+                for (uint32_t k = 0; k < (uint32_t)bucket[y].size(); ++k)
+                    if (k < slots) out[off + 8 * k] = bucket[y][k]; else left.push_back(bucket[y][k]);
+            }
+            size_t next = 0;
+            for (uint32_t q = 0; q < L; ++q) if (out[q] == 0xFFFFFFFFu) out[q] = left[next++];
+            std::copy(out.begin(), out.end(), order_out + i);
+            i = j;
+        }
+    } catch (...) { return RTS_ERR_CAPACITY; }
+    return RTS_OK;
+}
+
+extern "C" int rts_ctx_read_follow(rts_ctx* c, void* stream, uint32_t* lives, uint32_t* order, size_t tiles) {
+    if (!c) return RTS_ERR_INVALID_ARG;
+    const rts_ctx::Follow* f = nullptr;
+    for (const auto& e : c->follow) if (e.stream == stream) { f = &e; break; }
+    if (!f || !f->planned || tiles != (size_t)f->blocksX * f->blocksY) return RTS_ERR_INVALID_ARG;
+    RTS_HIP(hipSetDevice(c->device));
+    RTS_HIP(hipStreamSynchronize((hipStream_t)stream));
+    try {
+        if (lives) {
+            std::vector<uint32_t> buf(tiles * 2);
+            RTS_HIP(hipMemcpy(buf.data(), f->d_lives, tiles * 8, hipMemcpyDeviceToHost));
+            for (size_t t = 0; t < tiles; ++t) lives[t] = buf[2 * t + 1] - buf[2 * t];
+        }
+        if (order) {
+            std::vector<uint32_t> buf((size_t)f->frontStride * 8);
+            RTS_HIP(hipMemcpy(buf.data(), f->d_frontMap, buf.size() * 4, hipMemcpyDeviceToHost));
+            for (size_t i = 0; i < tiles; ++i) order[i] = buf[(i & 7u) * f->frontStride + (i >> 3)];
+        }
     } catch (...) { return RTS_ERR_CAPACITY; }
     return RTS_OK;
 }

@@ -49,7 +49,13 @@ struct TraceParams {
     float light[3];
     // generic rays
     const void* rays;         // rts_ray[n] (device)
-    uint8_t* out;
+    union {
+        uint8_t* out;
+        // follow mode (rts_follow.hip), mask launches only: {s_memrealtime low 32 bits at the wave's start, at its end} per tile of
+        // the dispatch, row-major; non-NULL only in the launches of shadowMaskFollowKernel.  (It shares the slot of the generic rays'
+        // output, which no mask kernel reads: the argument block keeps its size, and every other kernel its code.)
+        uint32_t* followLives;
+    };
     uint64_t nrays;
     const uint32_t* tileOrder; // optional: block i works on tile tileOrder[i] (device array of nBlocks entries)
     uint64_t* waveStats;      // diagnostics (tools/wave_stats.py): 4 u64 per wave, or NULL
@@ -94,6 +100,14 @@ const char* kernelName(int variant, bool mask);
 void tileShape(int variant, int wavesPerBlock, uint32_t* blockW, uint32_t* blockH);   // pixels covered by one block
 hipError_t launchShadowMask(int variant, int wavesPerBlock, const TraceParams& p, hipStream_t stream, uint32_t ldsPad = 0);
 hipError_t launchTraceRays(int variant, const TraceParams& p, hipStream_t stream);
+// follow mode (rts_follow.hip): the per-band lower bounds of the tick counts (band b = lifeBand of the host, bands longest first)
+constexpr uint32_t FOLLOW_BANDS = 55;          // lifeBand -4 (0.25 us and less) .. 50 (2^32 - 1 ticks, 42.9 s, is in band 50)
+constexpr int FOLLOW_BAND_LOW = -4;
+struct FollowBands { uint32_t minTicks[FOLLOW_BANDS]; };   // minTicks[i]: smallest tick count of band FOLLOW_BAND_LOW + i (ascending)
+size_t followScratchBytes(uint32_t tiles);
+// the order the next launch of the dispatch runs: lives (2 u32 per tile) -> frontMap (record i at (i mod 8) * frontStride + i / 8)
+hipError_t launchFollowPlan(const uint32_t* d_lives, uint32_t blocksX, uint32_t blocksY, uint32_t xcdSquare, uint32_t lifeBlock,
+                            const FollowBands& bands, void* d_scratch, uint32_t* d_frontMap, uint32_t frontStride, hipStream_t stream);
 hipError_t launchReciprocalSelfTest(unsigned long long* d_counts, hipStream_t stream);      // 3 counters, zeroed by the caller
 // planning: from the visit logs of `tiles` one-piece walks (p.pieceLog layout) to the piece table: tile t gets cuts[t].pieces
 // records starting at record firstPiece[t], its index ranges cut at the quantiles of its log
