@@ -251,6 +251,41 @@ int rts_trace_shadow_mask_stripes_device(rts_ctx* ctx, const rts_constants* cons
                                          const float* d_positions, uint32_t W, uint32_t H, uint32_t band_rows,
                                          uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, void* stream);
 
+/* ACTIVE MAPS: trace only the pixels the caller marks.  A deferred renderer multiplies the mask by max(0, N.L) and discards the
+ * background, so the byte traced for a surface that faces away from the light, or for a background pixel, never reaches the image;
+ * light range, spot cones, stencilled regions and checkerboard tracing are the same mechanism with another mark.
+ *   active : W x H bytes, row-major like the mask: non-zero = trace this pixel as the call without a map does, zero = send no ray.
+ * The three calls are the three above with that one argument more:
+ *   * for every pixel of the rows the call owns, mask[p] = active[p] ? (the byte the call without a map writes) : 0.  Zero is
+ *     "occluded" in the reference's polarity and "no unoccluded sample" for nsamples > 1; it IS written, so the mask is defined
+ *     wherever the plain call defines it.  Rows outside the range / stripe are not touched.  The positions of an inactive pixel may
+ *     hold anything (NaN included) and change no other pixel's byte.
+ *   * active == NULL is exactly the call without a map (the same launch of the same kernel).
+ *   * results never depend on an option.  An active trace honours "kernel" by FAMILY, one tile (or block) per workgroup: 0, 1, 2, 7
+ *     (and -1 below 256 K pixels) run the lane-per-ray walk with work sharing over 16 x 16 blocks -- an inactive pixel's lane
+ *     works on its neighbours' rays --, 3..6 the stackless packet over 8 x 8 tiles, 8 and 9 the wide packet when the stream has a
+ *     private copy, else the stackless one.  A band of the stripes form is a multiple of 16 rows for the first family, of 8 for the
+ *     others.  "soft_split", "packet_budget", "packet_share", "xcd_swizzle" and "row_order" apply as to the plain trace.
+ *     A packet wave whose tile holds no active pixel stores its zeros and ends before it sets up a ray.
+ *   * this version: an active trace ignores an installed split table, a planned or caller-set tile order, follow mode, "block_waves"
+ *     and "wide_lane" (tables and orders were planned on the lives of full tiles), and records no wave statistics and no clock
+ *     probe.  It never drops or alters any of them: the next plain trace uses them as before.
+ *   * get-only option "active_traces": launches with a map so far; rts_ctx_last_kernel_name then names
+ *     "shadowMaskActiveShareKernel", "shadowMaskActivePacketKernel<1>" or "shadowMaskActivePacketKernel<1,wide>".
+ *   * the device forms are asynchronous, allocate nothing and read nothing back (capturable like the plain trace); the host form
+ *     copies in, traces, copies out, synchronises.
+ * include/rts_scene.h has a mark made from the G-buffer (rtsh_facing_active); INTEGRATION.md shows where a renderer writes it. */
+int rts_trace_shadow_mask_active(rts_ctx* ctx, const rts_constants* constants, const rts_light* light, const float* positions,
+                                 const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                 uint8_t* mask);
+int rts_trace_shadow_mask_active_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light,
+                                        const float* d_positions, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                        uint32_t row_begin, uint32_t row_end, uint8_t* d_mask, void* stream);
+int rts_trace_shadow_mask_active_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light,
+                                                const float* d_positions, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                                uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask,
+                                                void* stream);
+
 /* Generic rays (the shader's `Ray`): out[i] = 1 if ray i is NOT occluded.  Host / device forms. */
 int rts_trace_rays(rts_ctx* ctx, const rts_ray* rays, size_t n, uint8_t* out);
 int rts_trace_rays_device(rts_ctx* ctx, const rts_ray* d_rays, size_t n, uint8_t* d_out, void* stream);

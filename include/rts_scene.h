@@ -52,6 +52,20 @@ int rtsh_combine_device(rts_ctx* ctx, const rts_constants* constants, const rts_
                         const float* d_normals, const uint8_t* d_mask, uint32_t W, uint32_t H, uint8_t* d_rgb,
                         void* stream);
 
+/* The facing mark: an active map (include/rts.h, rts_trace_shadow_mask_active) for one light, made from the G-buffer.
+ * active[p] = 0 where the normal's xyz are all zero (background: the combine pass leaves the pixel 0) or where N.L <= 0 -- N.L being
+ * the very value the combine pass clamps (one shared function: L = the directional light, or normalize(light.xyz - P) for a point
+ * light; a jittered light counts by its centre, as in the combine pass); 1 everywhere else, NaN included (a NaN is traced, never
+ * culled).  For such a pixel direct = 1.25 * 0 * mask whatever the mask holds, so for finite inputs rtsh_combine over a mask traced
+ * with this map equals rtsh_combine over the full mask, byte for byte: culling by this mark never changes the image.
+ * light == NULL: directional light from constants->lightDirection; positions needed for point lights.  active: W*H bytes. */
+int rtsh_facing_active(const rts_constants* constants, const rts_light* light, const float* positions, const float* normals,
+                       uint32_t W, uint32_t H, uint8_t* active);
+
+/* The same on the GPU (shared per-pixel source, the same bytes): DEVICE buffers, asynchronous on `stream`, one pixel per lane. */
+int rtsh_facing_active_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light, const float* d_positions,
+                              const float* d_normals, uint32_t W, uint32_t H, uint8_t* d_active, void* stream);
+
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.
  * Call with vertices == NULL to query *vertex_count (3 per triangle) first.  Returns RTS_OK,

@@ -136,6 +136,12 @@ _sig("rts_trace_shadow_mask_device", C.c_int, C.c_void_p, C.POINTER(RayTracingCo
      C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rts_trace_shadow_mask_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
      C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_shadow_mask_active", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rts_trace_shadow_mask_active_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_shadow_mask_active_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rts_trace_rays", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 _sig("rts_trace_rays_device", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
 _sig("rts_device_malloc", C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t)
@@ -221,6 +227,10 @@ _sig("rtsh_combine_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants),
      C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_combine", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rtsh_facing_active", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+     C.c_void_p)
+_sig("rtsh_facing_active_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_obj_load", C.c_int, C.c_char_p, C.c_void_p, C.c_size_t, _u32p, _f32p, _f32p)
 _sig("rtsh_obj_parse_float", C.c_float, C.c_char_p, C.POINTER(C.c_int))
 
@@ -410,30 +420,51 @@ class ShadowContext:
         return int(v.value)
 
     def trace_shadow_mask(self, constants, positions, width, height, light=None, row_begin=0, row_end=None,
-                          out=None):
-        """Host-pointer dispatch; returns the ``uint8[H, W]`` mask (1 = lit)."""
+                          out=None, active=None):
+        """Host-pointer dispatch; returns the ``uint8[H, W]`` mask (1 = lit).  ``active``: an active map, ``uint8[H, W]``
+        (non-zero = trace the pixel, zero = send no ray and write 0; include/rts.h), or None for every pixel."""
         positions = np.ascontiguousarray(positions, dtype=np.float32)
         if positions.size != width * height * 4:
             raise RtsError(1, "trace_shadow_mask: positions must be W*H*4 floats")
         row_end = height if row_end is None else row_end
         mask = out if out is not None else np.zeros((height, width), dtype=np.uint8)
         lp = C.byref(light) if light is not None else None
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.uint8)
+            if active.size != width * height:
+                raise RtsError(1, "trace_shadow_mask: active must be W*H bytes")
+            _check(_lib.rts_trace_shadow_mask_active(self._h, C.byref(constants), lp, _ptr(positions), _ptr(active), width, height,
+                                                     row_begin, row_end, _ptr(mask)), "rts_trace_shadow_mask_active")
+            return mask
         _check(_lib.rts_trace_shadow_mask(self._h, C.byref(constants), lp, _ptr(positions), width, height,
                                           row_begin, row_end, _ptr(mask)), "rts_trace_shadow_mask")
         return mask
 
     def trace_shadow_mask_device(self, constants, d_positions, width, height, d_mask, light=None, row_begin=0,
-                                 row_end=None, stream=None):
+                                 row_end=None, stream=None, d_active=None):
+        """``d_active``: device pointer of an active map (width * height bytes), or None for every pixel."""
         row_end = height if row_end is None else row_end
         lp = C.byref(light) if light is not None else None
+        if d_active is not None:
+            _check(_lib.rts_trace_shadow_mask_active_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
+                                                            C.c_void_p(d_active), width, height, row_begin, row_end,
+                                                            C.c_void_p(d_mask), C.c_void_p(stream or 0)),
+                   "rts_trace_shadow_mask_active_device")
+            return
         _check(_lib.rts_trace_shadow_mask_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions), width,
                                                  height, row_begin, row_end, C.c_void_p(d_mask),
                                                  C.c_void_p(stream or 0)), "rts_trace_shadow_mask_device")
 
     def trace_shadow_mask_stripes_device(self, constants, d_positions, width, height, d_mask, band_rows, n_stripes,
-                                         stripe, light=None, stream=None):
+                                         stripe, light=None, stream=None, d_active=None):
         """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
         lp = C.byref(light) if light is not None else None
+        if d_active is not None:
+            _check(_lib.rts_trace_shadow_mask_active_stripes_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
+                                                                    C.c_void_p(d_active), width, height, band_rows, n_stripes,
+                                                                    stripe, C.c_void_p(d_mask), C.c_void_p(stream or 0)),
+                   "rts_trace_shadow_mask_active_stripes_device")
+            return
         _check(_lib.rts_trace_shadow_mask_stripes_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
                                                          width, height, band_rows, n_stripes, stripe,
                                                          C.c_void_p(d_mask), C.c_void_p(stream or 0)),
@@ -689,6 +720,27 @@ def combine_device(ctx, constants, light, d_positions, d_normals, d_mask, width,
     _check(_lib.rtsh_combine_device(ctx.handle, C.byref(constants), lp, C.c_void_p(d_positions or 0), C.c_void_p(d_normals),
                                     C.c_void_p(d_mask), width, height, C.c_void_p(d_rgb), C.c_void_p(stream or 0)),
            "rtsh_combine_device")
+
+
+def facing_active(constants, light, positions, normals):
+    """The facing mark on the host (rtsh_facing_active): ``uint8[H, W]``, 0 for the background and where N.L <= 0 -- the pixels whose
+    shadow byte the combine pass cannot show -- and 1 elsewhere.  ``normals``: float32[H, W, 4]."""
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    active = np.zeros((H, W), np.uint8)
+    lp = C.byref(light) if light is not None else None
+    _check(_lib.rtsh_facing_active(C.byref(constants), lp, _ptr(positions) if positions is not None else None, _ptr(normals),
+                                   W, H, _ptr(active)), "rtsh_facing_active")
+    return active
+
+
+def facing_active_device(ctx, constants, light, d_positions, d_normals, width, height, d_active, stream=None):
+    """The facing mark on the GPU: device pointers, d_active = width*height bytes, asynchronous."""
+    lp = C.byref(light) if light is not None else None
+    _check(_lib.rtsh_facing_active_device(ctx.handle, C.byref(constants), lp, C.c_void_p(d_positions or 0), C.c_void_p(d_normals),
+                                          width, height, C.c_void_p(d_active), C.c_void_p(stream or 0)),
+           "rtsh_facing_active_device")
 
 
 def write_ppm(path, rgb):

@@ -32,6 +32,8 @@ struct rts_ctx {
     // staging for the host-pointer entries
     void* d_in = nullptr; size_t inBytes = 0;
     void* d_out = nullptr; size_t outBytes = 0;
+    void* d_act = nullptr; size_t actBytes = 0;      // ... and for the active map of rts_trace_shadow_mask_active
+    uint64_t activeTraces = 0;                        // launches with an active map (get-only option "active_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
     int packetShare = 4;
@@ -383,6 +385,7 @@ int rts_ctx_destroy(rts_ctx* c) {
     if (c->d_bvh) (void)hipFree(c->d_bvh);
     if (c->d_in) (void)hipFree(c->d_in);
     if (c->d_out) (void)hipFree(c->d_out);
+    if (c->d_act) (void)hipFree(c->d_act);
     if (c->d_waveStats) (void)hipFree(c->d_waveStats);
     if (c->d_tileOrder) (void)hipFree(c->d_tileOrder);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
@@ -517,6 +520,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "follow_streams")) { *value = (int)c->follow.size(); return RTS_OK; }
     if (!strcmp(key, "follow_traces")) { *value = (int)(c->followTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "follow_ordered")) { *value = (int)(c->followOrdered & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "active_traces")) { *value = (int)(c->activeTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
     if (!strcmp(key, "tile_order_planned")) { *value = c->tileOrderPlanned ? 1 : 0; return RTS_OK; }
@@ -623,9 +627,56 @@ static rts_ctx::Follow* followFor(rts_ctx* c, void* stream, const TraceParams& p
     return f;
 }
 
+// The light of a mask dispatch (light == NULL: the reference's directional light from the constants).
+static void setLight(TraceParams& p, const rts_constants* k, const rts_light* light) {
+    for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
+    if (light) {
+        p.lightType = light->type;
+        p.nsamples = light->nsamples > 1 ? light->nsamples : 1;
+        for (int i = 0; i < 3; ++i) p.light[i] = light->xyz[i];
+        p.lightTable = p.nsamples > 1 ? light->table : 0u;
+        if (p.nsamples > 1) memcpy(p.offsets, light->offsets, sizeof(float) * 4 * (p.lightTable ? p.lightTable : p.nsamples));
+    } else {
+        p.lightType = RTS_LIGHT_DIRECTIONAL;
+        p.nsamples = 1;
+        for (int i = 0; i < 3; ++i) p.light[i] = k->lightDirection[i];
+    }
+}
+
+// A trace with an active map (include/rts.h): the kernel FAMILY the options ask for, one tile per workgroup, in natural order -- an
+// installed split table, a tile order and follow mode are neither used nor touched, and no statistics are recorded.
+static int traceActive(rts_ctx* c, TraceParams& p, const rts_constants* k, const rts_light* light, const uint8_t* d_active, uint32_t rows,
+                       uint32_t band_rows, uint32_t n_stripes, void* stream) {
+    const uint64_t pixels = (uint64_t)p.W * rows;
+    int variant = c->variant;
+    if (variant == rts::V_AUTO)                      // (the plain trace's rule, traceMaskImpl)
+        variant = pixels < (1u << 18) ? rts::V_SHARE
+                : (c->wideCount && (!light || light->nsamples <= 1) && pixels >= (1u << 22)) ? rts::V_WIDE : rts::V_PACKET;
+    if (variant == rts::V_WIDE || variant == rts::V_WIDE_C) variant = p.wide ? rts::V_WIDE : rts::V_PACKET;
+    else if (variant >= rts::V_PACKET && variant <= rts::V_PACKET_PF) variant = rts::V_PACKET;
+    else variant = rts::V_SHARE;
+    const uint32_t b = variant == rts::V_SHARE ? 16u : 8u;       // pixels per side of a workgroup's block
+    if (n_stripes > 1 && band_rows % b != 0) return RTS_ERR_INVALID_ARG;
+    p.blocksX = (p.W + b - 1) / b;
+    p.blocksY = (rows + b - 1) / b;
+    p.nBlocks = p.blocksX * p.blocksY;
+    p.swizzle = c->swizzle ? 1u : 0u;
+    p.gridBlocks = p.swizzle ? ((p.nBlocks + 7) / 8) * 8 : p.nBlocks;
+    p.grid2d = (!p.swizzle && p.blocksY <= 65535u) ? 1u : 0u;
+    p.rowOrder = (p.grid2d && n_stripes <= 1) ? (uint32_t)c->rowOrder : 0u;
+    p.activeMap = d_active;
+    setLight(p, k, light);
+    ++c->launches;
+    ++c->activeTraces;
+    const char* name = "";
+    const hipError_t e = rts::launchShadowMaskActive(variant, p, (hipStream_t)stream, &name);
+    c->lastKernel = name;
+    return hipStatus(e);
+}
+
 static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
                          uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint32_t band_rows,
-                         uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, void* stream) {
+                         uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, void* stream, const uint8_t* d_active = nullptr) {
     if (!c || !k || !d_positions || !d_mask || W == 0 || H == 0 || row_begin > row_end || row_end > H)
         return RTS_ERR_INVALID_ARG;
     if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 64)) return RTS_ERR_INVALID_ARG;
@@ -653,6 +704,7 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
     uint32_t rows = row_end - row_begin;
     if (n_stripes > 1) rows = stripeRows(H, band_rows, n_stripes, stripe);     // virtual rows = whole owned bands
     if (rows == 0) return RTS_OK;                                                 // (a stripe without a band: no launch)
+    if (d_active) return traceActive(c, p, k, light, d_active, rows, band_rows, n_stripes, stream);
     const uint64_t pixels = (uint64_t)W * rows;
     // Big one-sample dispatches of a stream with a private copy take the WIDE packet (a static rule from what rts_ctx_autotune
     // picks on the 4K frames: city 0.153 against 0.164 ms, courtyard 0.562 against 0.630; at 1080p and for soft shadows the
@@ -684,18 +736,7 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
     p.grid2d = (!p.swizzle && !p.tileOrder && p.blocksY <= 65535u) ? 1u : 0u;
     if (c->d_clockProbe && p.grid2d && p.blocksY <= c->clockProbeRows) p.clockProbe = c->d_clockProbe;
     p.rowOrder = (p.grid2d && n_stripes <= 1) ? (uint32_t)c->rowOrder : 0u;
-    for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
-    if (light) {
-        p.lightType = light->type;
-        p.nsamples = light->nsamples > 1 ? light->nsamples : 1;
-        for (int i = 0; i < 3; ++i) p.light[i] = light->xyz[i];
-        p.lightTable = p.nsamples > 1 ? light->table : 0u;
-        if (p.nsamples > 1) memcpy(p.offsets, light->offsets, sizeof(float) * 4 * (p.lightTable ? p.lightTable : p.nsamples));
-    } else {
-        p.lightType = RTS_LIGHT_DIRECTIONAL;
-        p.nsamples = 1;
-        for (int i = 0; i < 3; ++i) p.light[i] = k->lightDirection[i];
-    }
+    setLight(p, k, light);
     c->lastBlocksX = p.blocksX; c->lastBlocksY = p.blocksY; c->lastVariant = variant; c->lastGrid2d = p.grid2d != 0;
     if (c->planning) {                       // pieces only: the planning walk of the selected tiles, with visit logs
         if (!(variant == rts::V_PACKET || variant == rts::V_WIDE) || c->blockWaves != 1 || p.nsamples != 1 || !p.grid2d || !p.wide ||
@@ -791,6 +832,48 @@ int rts_trace_shadow_mask(rts_ctx* c, const rts_constants* k, const rts_light* l
     RTS_HIP(hipMemcpy(c->d_in, positions + (size_t)row_begin * W * 4, inB, hipMemcpyHostToDevice));
     c->pixelBase = row_begin * W;          // per-pixel jitter hashes the pixel's index in the caller's frame
     s = rts_trace_shadow_mask_device(c, k, light, (const float*)c->d_in, W, rows, 0, rows, (uint8_t*)c->d_out, nullptr);
+    c->pixelBase = 0;
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(mask + (size_t)row_begin * W, c->d_out, outB, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+int rts_trace_shadow_mask_active_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
+                                        const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                        uint8_t* d_mask, void* stream) {
+    return traceMaskImpl(c, k, light, d_positions, W, H, row_begin, row_end, 0, 1, 0, d_mask, stream, d_active);
+}
+
+int rts_trace_shadow_mask_active_stripes_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
+                                                const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes,
+                                                uint32_t stripe, uint8_t* d_mask, void* stream) {
+    if (!d_active) return rts_trace_shadow_mask_stripes_device(c, k, light, d_positions, W, H, band_rows, n_stripes, stripe, d_mask, stream);
+    if (band_rows == 0 || band_rows % 8 != 0 || n_stripes == 0 || stripe >= n_stripes) return RTS_ERR_INVALID_ARG;
+    if (n_stripes == 1) return traceMaskImpl(c, k, light, d_positions, W, H, 0, H, 0, 1, 0, d_mask, stream, d_active);
+    // (a stripe that owns no band launches nothing: traceMaskImpl, after the argument checks)
+    return traceMaskImpl(c, k, light, d_positions, W, H, 0, H, band_rows, n_stripes, stripe, d_mask, stream, d_active);
+}
+
+int rts_trace_shadow_mask_active(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
+                                 uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
+    if (!active) return rts_trace_shadow_mask(c, k, light, positions, W, H, row_begin, row_end, mask);
+    if (!c || !k || !positions || !mask || W == 0 || H == 0 || row_begin > row_end || row_end > H)
+        return RTS_ERR_INVALID_ARG;
+    if (!c->d_bvh) return RTS_ERR_NO_BVH;
+    if (row_begin == row_end) return RTS_OK;
+    RTS_HIP(hipSetDevice(c->device));
+    // Only the stripe travels, as in rts_trace_shadow_mask: positions, map and mask of rows [row_begin,row_end) as a frame of their own.
+    const uint32_t rows = row_end - row_begin;
+    const size_t inB = (size_t)rows * W * 16, outB = (size_t)rows * W;
+    int s = ensure(&c->d_in, &c->inBytes, inB);
+    if (s == RTS_OK) s = ensure(&c->d_out, &c->outBytes, outB);
+    if (s == RTS_OK) s = ensure(&c->d_act, &c->actBytes, outB);
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(c->d_in, positions + (size_t)row_begin * W * 4, inB, hipMemcpyHostToDevice));
+    RTS_HIP(hipMemcpy(c->d_act, active + (size_t)row_begin * W, outB, hipMemcpyHostToDevice));
+    c->pixelBase = row_begin * W;          // per-pixel jitter hashes the pixel's index in the caller's frame
+    s = rts_trace_shadow_mask_active_device(c, k, light, (const float*)c->d_in, (const uint8_t*)c->d_act, W, rows, 0, rows,
+                                            (uint8_t*)c->d_out, nullptr);
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
     RTS_HIP(hipMemcpy(mask + (size_t)row_begin * W, c->d_out, outB, hipMemcpyDeviceToHost));

@@ -117,9 +117,9 @@ RTS_HD void shadePixel(const uint32_t* bvh, const Camera& c, uint32_t x, uint32_
 // L = the light direction for a directional light; for the point-light extension L = normalize(light - P).
 struct CombineParams { V3 cam, viewDir /* normalised */, light; uint32_t pointLight; float samples; };
 
-RTS_HD uint8_t combinePixel(const CombineParams& c, const float* position4, const float* normal4, uint8_t mask) {
-    V3 n{ normal4[0], normal4[1], normal4[2] };
-    if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) return 0;
+// N.L as the combine pass takes it, before the clamp (frag:24-29): the one value both combinePixel and the facing mark
+// (facingPixel) decide on, so that the mark can never cull a pixel the combine pass would have lit.
+RTS_HD float facingNdl(const CombineParams& c, const float* position4, V3 n) {
     V3 L = c.light;
     if (c.pointLight) {
         V3 p{ c.cam.x + position4[0], c.cam.y + position4[1], c.cam.z + position4[2] };
@@ -127,13 +127,28 @@ RTS_HD uint8_t combinePixel(const CombineParams& c, const float* position4, cons
         float ll = __builtin_sqrtf(dot(L, L));
         if (ll > 0) L = mul(L, 1.0f / ll);
     }
-    float ndl = dot(n, L); if (ndl < 0) ndl = 0;
+    return dot(n, L);
+}
+
+RTS_HD uint8_t combinePixel(const CombineParams& c, const float* position4, const float* normal4, uint8_t mask) {
+    V3 n{ normal4[0], normal4[1], normal4[2] };
+    if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) return 0;
+    float ndl = facingNdl(c, position4, n); if (ndl < 0) ndl = 0;
     float ndv = dot(n, mul(c.viewDir, -1.0f)); if (ndv < 0) ndv = 0;
     const float direct = 1.25f * ndl * ((float)mask / c.samples);          // frag:29
     const float ambient = 0.15f + 0.05f * (1.0f - ndv);                     // frag:30
     float v = direct + ambient;                                             // frag:32 (baseColor = 1)
     int q = (int)(v * 255.0f + 0.5f); if (q > 255) q = 255; if (q < 0) q = 0;
     return (uint8_t)q;
+}
+
+// The facing mark (include/rts_scene.h, rtsh_facing_active): 0 where the shadow mask's byte cannot reach the image -- the
+// background (combinePixel leaves the pixel 0) and N.L <= 0 (direct = 1.25 * 0 * mask: either zero) --, 1 everywhere else.
+// `!(ndl > 0)` would cull a NaN; `ndl <= 0` is false for one, so a NaN is traced.
+RTS_HD uint8_t facingPixel(const CombineParams& c, const float* position4, const float* normal4) {
+    V3 n{ normal4[0], normal4[1], normal4[2] };
+    if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) return 0;
+    return facingNdl(c, position4, n) <= 0 ? 0 : 1;
 }
 
 } // namespace rts_harness

@@ -48,7 +48,13 @@ struct TraceParams {
     uint32_t lightTable;        // per-pixel jitter: entries of offsets[] a pixel starts in (0 = off); rts_light.table
     float light[3];
     // generic rays
-    const void* rays;         // rts_ray[n] (device)
+    union {
+        const void* rays;     // rts_ray[n] (device)
+        // active traces (rts_trace_shadow_mask_active*), mask launches only: W x H bytes, non-zero = this pixel sends its ray; non-NULL
+        // only in the launches of the shadowMaskActive* kernels.  (It shares the slot of the generic rays' input, which no mask
+        // kernel reads: the argument block keeps its size, and every other kernel its code.)
+        const uint8_t* activeMap;
+    };
     union {
         uint8_t* out;
         // follow mode (rts_follow.hip), mask launches only: {s_memrealtime low 32 bits at the wave's start, at its end} per tile of
@@ -99,6 +105,9 @@ struct SplitCut {             // planning: one selected tile
 const char* kernelName(int variant, bool mask);
 void tileShape(int variant, int wavesPerBlock, uint32_t* blockW, uint32_t* blockH);   // pixels covered by one block
 hipError_t launchShadowMask(int variant, int wavesPerBlock, const TraceParams& p, hipStream_t stream, uint32_t ldsPad = 0);
+// active traces: the kernel family of `variant` with p.activeMap as the mark (V_SHARE: lane per ray with work sharing, V_PACKET: the
+// stackless packet, V_WIDE: the wide packet); one tile per workgroup.  *name: the kernel's stable name.
+hipError_t launchShadowMaskActive(int variant, const TraceParams& p, hipStream_t stream, const char** name);
 hipError_t launchTraceRays(int variant, const TraceParams& p, hipStream_t stream);
 // follow mode (rts_follow.hip): the per-band lower bounds of the tick counts (band b = lifeBand of the host, bands longest first)
 constexpr uint32_t FOLLOW_BANDS = 55;          // lifeBand -4 (0.25 us and less) .. 50 (2^32 - 1 ticks, 42.9 s, is in band 50)

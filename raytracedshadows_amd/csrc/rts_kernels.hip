@@ -1498,7 +1498,7 @@ template <int K, int WPB, bool PREFETCH = false, bool SOFT = false, bool PLAIN =
           bool TILESPLIT = false, bool PIECES = true, bool SEG = false>
 __global__ __launch_bounds__(64 * WPB * SPLIT) __attribute__((amdgpu_waves_per_eu(K == 1 ? 8 : 4)))
 void shadowMaskPacketKernel(TraceParams p) {
-    constexpr bool LIVES = false;
+    constexpr bool LIVES = false, ACTIVE = false;
 #include "rts_packet_tile.inc"
 }
 
@@ -1509,8 +1509,75 @@ template <int WIDE, bool BANDS, bool TILESPLIT, bool SEG>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8)))
 void shadowMaskFollowKernel(TraceParams p) {
     constexpr int K = 1, WPB = 1, SPLIT = 1;
-    constexpr bool PREFETCH = false, SOFT = false, PLAIN = true, PIECES = false, LIVES = true;
+    constexpr bool PREFETCH = false, SOFT = false, PLAIN = true, PIECES = false, LIVES = true, ACTIVE = false;
 #include "rts_packet_tile.inc"
+}
+
+// Active traces (rts_trace_shadow_mask_active*, include/rts.h): the one-tile forms of kernel 3 (WIDE 0) and kernel 8 (WIDE 1) with
+// an ACTIVE MAP, p.activeMap -- one byte per pixel, requested with the G-buffer texel.  A lane is a member of the walk when it owns
+// a pixel whose byte is set; it stores when it owns a pixel, 0 where the byte is 0; a wave without a member leaves before the
+// stream is opened or a ray is set up.  One sample (PLAIN: a contiguous row range on a 2-D grid, BANDS: one stripe of power-of-two
+// bands, neither: every other geometry), SOFT with SPLIT 4 (4 waves per tile) or 1.  No table, no order, no lives, no statistics.
+// Only this template instantiates ACTIVE: the code objects of the two templates above are those of the body without it.
+template <int WIDE, bool SEG, bool SOFT, int SPLIT, bool PLAIN, bool BANDS>
+__global__ __launch_bounds__(64 * SPLIT) __attribute__((amdgpu_waves_per_eu(8)))
+void shadowMaskActivePacketKernel(TraceParams p) {
+    constexpr int K = 1, WPB = 1;
+    constexpr bool PREFETCH = false, TILESPLIT = false, PIECES = false, LIVES = false, ACTIVE = true;
+#include "rts_packet_tile.inc"
+}
+
+// Active traces, lane per ray (the launches that kernel 7 takes: small dispatches, and the options 0, 1, 2, 7): shadowMaskKernel's
+// 16 x 16 block of four waves around traverseShare.  A pixel whose byte is 0 is simply not live, so the walk's work sharing hands
+// its lane to the neighbours' rays -- which is the point of that walk; a wave without a live ray stores its zeros and leaves (the
+// waves of a workgroup share nothing but the LDS each owns a quarter of, so each decides for itself).
+__global__ __launch_bounds__(256) void shadowMaskActiveShareKernel(TraceParams p) {
+    __shared__ uint32_t shareSlots[4][64];       // lane numbers exchanged by traverseShare (256 B per wave)
+    uint32_t* lds = shareSlots[threadIdx.x >> 6];
+    uint32_t bx, by;
+    if (!blockToXY(p, blockIdx.x, &bx, &by)) return;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t x = bx * 16u + (wave & 1u) * 8u + (lane & 7u);
+    const uint32_t y = ownedRow(p, by * 16u + (wave >> 1) * 8u + (lane >> 3));
+    const bool owns = (x < p.W) && (y < p.rowEnd);
+    const size_t pix = (size_t)y * p.W + x;
+
+    F3 rel{ 0.f, 0.f, 0.f };
+    uint8_t act = 0;
+    if (owns) {
+        f32x4 t = __builtin_nontemporal_load((const f32x4*)p.positions + pix);   // comp:135, read once
+        act = __builtin_nontemporal_load(p.activeMap + pix);                     // (with the texel: one wait for both)
+        rel = F3{ t.x, t.y, t.z };
+    }
+    const bool live = owns && act != 0;
+    const uint64_t walkers = __builtin_amdgcn_ballot_w64(live);
+    if (walkers == 0) {
+        if (owns) __builtin_nontemporal_store((uint8_t)0, &p.mask[pix]);
+        return;
+    }
+    // the stand-in of rts_packet_tile.inc: a lane without a ray sets up the ray of the first lane with one, so that it passes every
+    // wave-wide gate of the set-up that lane passes; exact, since its result is discarded
+    const int firstWalker = __builtin_ctzll(walkers);
+    const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel.x), firstWalker));
+    const float sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel.y), firstWalker));
+    const float sz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel.z), firstWalker));
+    const uint32_t sp = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pix, firstWalker);
+    rel = live ? rel : F3{ sx, sy, sz };
+    const uint32_t rayPix = live ? (uint32_t)pix : sp;
+    const NodeStream bvh = openStream(p);
+    const uint32_t ns = p.nsamples > 1 ? p.nsamples : 1u;
+    uint32_t lit = 0;
+    for (uint32_t s = 0; s < ns; ++s) {
+        Ray r = makeShadowRay(p, rel, s, rayPix);
+        bool unsafe = live && !raySafe(r);
+        bool occluded;
+        if (p.bvhFinite && __builtin_amdgcn_ballot_w64(unsafe) == 0)
+            occluded = traverseShare<true>(bvh, r, live, 0u, lds);
+        else
+            occluded = traverseShare<false>(bvh, r, live, 0u, lds);
+        lit += occluded ? 0u : 1u;                                  // comp:148
+    }
+    if (owns) __builtin_nontemporal_store((uint8_t)(live ? lit : 0u), &p.mask[pix]);   // comp:150; 0 = no ray was sent
 }
 
 template <int VARIANT>
@@ -1664,6 +1731,36 @@ hipError_t launchShadowMask(int variant, int wavesPerBlock, const TraceParams& p
     case V_PACKET_PF: if (soft) hipLaunchKernelGGL((shadowMaskPacketKernel<1, 4, true, true>), grid, block, 0, stream, p); else hipLaunchKernelGGL((shadowMaskPacketKernel<1, 4, true, false>), grid, block, 0, stream, p); break;
     default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// Active traces: one kernel family, one light kind -> the instantiation for the dispatch's geometry and sample count.
+template <int WIDE, bool SEG>
+static void launchActivePacket(const TraceParams& p, hipStream_t stream, dim3 grid) {
+    const dim3 b1(64);
+    if (p.nsamples > 1 && p.softSplit) hipLaunchKernelGGL((shadowMaskActivePacketKernel<WIDE, SEG, true, 4, false, false>), grid, dim3(256), 0, stream, p);
+    else if (p.nsamples > 1) hipLaunchKernelGGL((shadowMaskActivePacketKernel<WIDE, SEG, true, 1, false, false>), grid, b1, 0, stream, p);
+    else if (p.grid2d && p.nStripes > 1 && p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0)
+        hipLaunchKernelGGL((shadowMaskActivePacketKernel<WIDE, SEG, false, 1, true, true>), grid, b1, 0, stream, p);
+    else if (p.grid2d && p.nStripes <= 1) hipLaunchKernelGGL((shadowMaskActivePacketKernel<WIDE, SEG, false, 1, true, false>), grid, b1, 0, stream, p);
+    else hipLaunchKernelGGL((shadowMaskActivePacketKernel<WIDE, SEG, false, 1, false, false>), grid, b1, 0, stream, p);
+}
+
+hipError_t launchShadowMaskActive(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
+    if (!p.activeMap) return hipErrorInvalidValue;
+    dim3 grid(p.gridBlocks);
+    if (p.grid2d) grid = dim3(p.blocksX, p.blocksY);
+    if (variant == V_SHARE) {
+        *name = "shadowMaskActiveShareKernel";
+        hipLaunchKernelGGL(shadowMaskActiveShareKernel, grid, dim3(256), 0, stream, p);
+    } else if (variant == V_WIDE && p.wide) {
+        *name = "shadowMaskActivePacketKernel<1,wide>";
+        if (p.lightType != 0) launchActivePacket<1, true>(p, stream, grid);
+        else launchActivePacket<1, false>(p, stream, grid);
+    } else if (variant == V_PACKET) {
+        *name = "shadowMaskActivePacketKernel<1>";
+        launchActivePacket<0, false>(p, stream, grid);
+    } else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

@@ -1,6 +1,9 @@
-// The body of the one-wave-per-tile packet kernels (rts_kernels.hip): included by shadowMaskPacketKernel (LIVES false) and by
-// shadowMaskFollowKernel (LIVES true), which name the template parameters K ... SEG and LIVES and their kernel argument `p`.
-// One text, two kernel templates: the code objects of shadowMaskPacketKernel are exactly those it had before follow mode.
+// The body of the one-wave-per-tile packet kernels (rts_kernels.hip): included by shadowMaskPacketKernel (LIVES false, ACTIVE false),
+// by shadowMaskFollowKernel (LIVES true) and by shadowMaskActivePacketKernel (ACTIVE true), which name the template parameters
+// K ... SEG, LIVES and ACTIVE and their kernel argument `p`.
+// One text, three kernel templates: the code objects of shadowMaskPacketKernel are exactly those it had before follow mode and
+// before active maps.
+    static_assert(!ACTIVE || (K == 1 && WPB == 1 && !TILESPLIT && !LIVES), "an active map: the one-tile forms without a table only");
     static_assert(!BANDS || (PLAIN && K == 1 && WPB == 1), "the band form exists for the one-tile everyday launch only");
     static_assert(SPLIT == 1 || (K == 1 && WPB == 1 && SOFT), "samples are split over waves in the one-tile soft-shadow form only");
     static_assert(!TILESPLIT || (PLAIN && K == 1 && WPB == 1 && !SOFT && SPLIT == 1), "split tiles exist for the one-tile everyday launch only");
@@ -24,6 +27,10 @@
         const uint32_t a0 = p.W, a1 = p.rowBegin, a2 = p.rowEnd, a3 = p.pieceRows, a4 = p.blocksX, a5 = p.blocksY, a6 = p.rowOrder,
                        a7 = p.bandShift, a8 = p.stripe;
         asm volatile("" :: "s"(posAddr), "s"(mapAddr), "s"(a0), "s"(a1), "s"(a2), "s"(a3), "s"(a4), "s"(a5), "s"(a6), "s"(a7), "s"(a8));
+        if constexpr (ACTIVE) {                                       // ... and the active map's address, in the same batch
+            const uint64_t actAddr = (uint64_t)(uintptr_t)p.activeMap;
+            asm volatile("" :: "s"(actAddr));
+        }
     }
     if constexpr (TILESPLIT) {
         const uint32_t pieceRows = p.pieceRows, blocksX = p.blocksX, blocksY = p.blocksY, rowOrder = p.rowOrder;
@@ -53,6 +60,7 @@
     bool live[K];
     size_t pix[K];
     F3 rel[K];
+    [[maybe_unused]] uint8_t act = 0;                                 // ACTIVE: the pixel's byte of the active map
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const uint32_t x = x0 + (k & 1) * 8u;
@@ -67,13 +75,47 @@
             // (no branch around the request: a lane without a pixel asks for texel 0 and never looks at it -- with the branch
             //  the compiler waits for the texel inside it, before the rest of the prologue's scalar work)
             const f32x4 t = __builtin_nontemporal_load((const f32x4*)p.positions + (live[k] ? pix[k] : (size_t)0));   // comp:135
+            // (ACTIVE: the byte is requested with the texel -- one batch, one wait -- and a lane without a pixel asks for byte 0)
+            if constexpr (ACTIVE) act = __builtin_nontemporal_load(p.activeMap + (live[k] ? pix[k] : (size_t)0));
             rel[k] = F3{ t.x, t.y, t.z };
         } else {
             rel[k] = F3{ 0.f, 0.f, 0.f };
             if (live[k]) {
                 f32x4 t = __builtin_nontemporal_load((const f32x4*)p.positions + pix[k]);   // comp:135
+                if constexpr (ACTIVE) act = __builtin_nontemporal_load(p.activeMap + pix[k]);
                 rel[k] = F3{ t.x, t.y, t.z };
             }
+        }
+    }
+    // ACTIVE: a lane walks when it owns a pixel AND the pixel's byte is set; it stores when it owns a pixel (0 where the byte is 0).
+    [[maybe_unused]] bool owns = false;
+    [[maybe_unused]] uint32_t rayPix = 0;
+    if constexpr (ACTIVE) {
+        owns = live[0];
+        live[0] = owns && act != 0;
+        const uint64_t walkers = __builtin_amdgcn_ballot_w64(live[0]);
+        // A tile without a ray: one ballot, one scalar branch, the zero stores, end -- before the stream is opened or a ray is set
+        // up.  (SPLIT: the four waves of the workgroup look at the same tile, so all of them leave here, in front of the barrier,
+        // or none does.)
+        if (walkers == 0) {
+            if (owns && (SPLIT == 1 || wave == 0)) __builtin_nontemporal_store((uint8_t)0, &p.mask[pix[0]]);
+            return;
+        }
+        // Lanes that do not walk take the texel (and pixel index) of the first lane that does.  The ray set-up decides per WAVE
+        // between forms that give the same bits wherever both apply (makeShadowRay's one-gate fast path, the rcpFast range
+        // tests: ballots over all 64 lanes), so what such a lane holds can never change a walking lane's bits -- but a background
+        // texel (0,0,0,0) or garbage (NaN, Inf, 1e38: allowed in an inactive pixel) would send the whole wave down the general
+        // path.  With the stand-in every lane that does not walk sets up the very ray of a lane that does: it passes every gate
+        // that lane passes.  Exact, because the stand-in only feeds lanes whose result is discarded (they are no members of the
+        // walk, and the store below writes 0 for them).
+        const int firstWalker = __builtin_ctzll(walkers);
+        const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel[0].x), firstWalker));
+        const float sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel[0].y), firstWalker));
+        const float sz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel[0].z), firstWalker));
+        rel[0] = live[0] ? rel[0] : F3{ sx, sy, sz };
+        if constexpr (SOFT) {                                         // (the pixel index picks the light sample: per-pixel jitter)
+            const uint32_t sp = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)pix[0], firstWalker);
+            rayPix = live[0] ? (uint32_t)pix[0] : sp;
         }
     }
     const NodeStream bvh = openStream(p);
@@ -109,10 +151,10 @@
         if constexpr (WIDE != 0) {
             float rootLo[3], rootHi[3];
             wideRoot(p, rootLo, rootHi);
-            r[0] = makeShadowRay<!SOFT && WIDE != 3>(p, rel[0], s, (uint32_t)pix[0], &fast, wideSetupBound(rootLo, rootHi));
+            r[0] = makeShadowRay<!SOFT && WIDE != 3>(p, rel[0], s, ACTIVE ? rayPix : (uint32_t)pix[0], &fast, wideSetupBound(rootLo, rootHi));
         } else {
 #pragma unroll
-            for (int k = 0; k < K; ++k) r[k] = makeShadowRay<!SOFT>(p, rel[k], s, (uint32_t)pix[k]);
+            for (int k = 0; k < K; ++k) r[k] = makeShadowRay<!SOFT>(p, rel[k], s, ACTIVE ? rayPix : (uint32_t)pix[k]);
         }
         if (!PLAIN && p.waveStats && s < SPLIT) {    // diagnostics: the G-buffer texel is in and the first ray exists
             asm volatile("" :: "v"(r[0].inv.x), "v"(r[0].inv.y), "v"(r[0].inv.z), "v"(r[0].o.x));
@@ -132,8 +174,11 @@
             uint32_t sum = 0;
 #pragma unroll
             for (int w = 0; w < SPLIT; ++w) sum += partial[w][lane];
-            if (live[0]) __builtin_nontemporal_store((uint8_t)sum, &p.mask[pix[0]]);     // comp:150
+            if constexpr (ACTIVE) { if (owns) __builtin_nontemporal_store((uint8_t)(live[0] ? sum : 0u), &p.mask[pix[0]]); }
+            else if (live[0]) __builtin_nontemporal_store((uint8_t)sum, &p.mask[pix[0]]);     // comp:150
         }
+    } else if constexpr (ACTIVE) {
+        if (owns) __builtin_nontemporal_store((uint8_t)(live[0] ? lit[0] : 0u), &p.mask[pix[0]]);   // comp:150; 0 = no ray was sent
     } else {
 #pragma unroll
         for (int k = 0; k < K; ++k)

@@ -59,6 +59,15 @@ __global__ __launch_bounds__(256) void combineKernel(CombineParams c, const floa
     const uint8_t q = combinePixel(c, positions ? positions + i * 4 : zero, normals + i * 4, mask[i]);
     rgb[i * 3] = q; rgb[i * 3 + 1] = q; rgb[i * 3 + 2] = q;
 }
+
+// The facing mark (rts_closest_hit.h: facingPixel), one pixel per lane like combineKernel.
+__global__ __launch_bounds__(256) void facingKernel(CombineParams c, const float* positions, const float* normals, uint64_t n,
+                                                    uint8_t* active) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float zero[4] = { 0.f, 0.f, 0.f, 0.f };
+    active[i] = facingPixel(c, positions ? positions + i * 4 : zero, normals + i * 4);
+}
 } // namespace rts_harness
 
 extern "C" const void* rts_ctx_device_bvh(rts_ctx* ctx);   // rts_api.cpp
@@ -76,6 +85,21 @@ extern "C" int rtsh_combine_device(rts_ctx* ctx, const rts_constants* k, const r
     const uint64_t n = (uint64_t)W * H;
     hipLaunchKernelGGL(rts_harness::combineKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c,
                        d_positions, d_normals, d_mask, n, d_rgb);
+    e = hipGetLastError();
+    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+}
+
+extern "C" int rtsh_facing_active_device(rts_ctx* ctx, const rts_constants* k, const rts_light* light, const float* d_positions,
+                                         const float* d_normals, uint32_t W, uint32_t H, uint8_t* d_active, void* stream) {
+    if (!ctx || !k || !d_normals || !d_active || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    rts_harness::CombineParams c;
+    int s = rts_harness::makeCombineParams(k, light, d_positions != nullptr, &c);
+    if (s != RTS_OK) return s;
+    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
+    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
+    const uint64_t n = (uint64_t)W * H;
+    hipLaunchKernelGGL(rts_harness::facingKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c,
+                       d_positions, d_normals, n, d_active);
     e = hipGetLastError();
     return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
 }

@@ -108,3 +108,15 @@ extern "C" int rtsh_combine(const rts_constants* k, const rts_light* light, cons
     }
     return RTS_OK;
 }
+
+// The facing mark on the host (per-pixel rule in rts_closest_hit.h: facingPixel): the checker of rtsh_facing_active_device.
+extern "C" int rtsh_facing_active(const rts_constants* k, const rts_light* light, const float* positions, const float* normals,
+                                  uint32_t W, uint32_t H, uint8_t* active) {
+    if (!k || !normals || !active || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    CombineParams c;
+    int s = makeCombineParams(k, light, positions != nullptr, &c);
+    if (s != RTS_OK) return s;
+    const float zero[4] = { 0, 0, 0, 0 };
+    for (size_t i = 0; i < (size_t)W * H; ++i) active[i] = facingPixel(c, positions ? positions + i * 4 : zero, normals + i * 4);
+    return RTS_OK;
+}
