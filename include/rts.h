@@ -236,7 +236,12 @@ int rts_trace_shadow_mask(rts_ctx* ctx, const rts_constants* constants, const rt
                           const float* positions, uint32_t W, uint32_t H,
                           uint32_t row_begin, uint32_t row_end, uint8_t* mask);
 
-/* Same with DEVICE pointers, asynchronous on `stream` (a hipStream_t, NULL = default stream). */
+/* Same with DEVICE pointers, asynchronous on `stream` (a hipStream_t, NULL = default stream).
+ * GRAPH CAPTURE (tests/test_gpu_graph.py): this call, the stripes form, the active forms, rts_trace_rays_device and the device
+ * passes of rts_scene.h may be issued on a stream under hipStreamBeginCapture.  Each adds kernel nodes only -- one per trace, plus
+ * the planner's four in follow mode (three with "follow_block" 1) -- and no memcpy, memset or allocation node; nothing is allocated, cleared or read back.
+ * constants, light and every option travel in the kernel arguments BY VALUE as they are at the call: a replay traces the captured
+ * light and camera whatever the host structs hold by then, from the positions (and map) the device buffers hold at the replay. */
 int rts_trace_shadow_mask_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light,
                                  const float* d_positions, uint32_t W, uint32_t H,
                                  uint32_t row_begin, uint32_t row_end, uint8_t* d_mask, void* stream);
@@ -380,7 +385,10 @@ int rts_ctx_autotune_stripes(rts_ctx* ctx, const rts_constants* constants, const
  * switches that off; get "split_tiles" / "split_pieces" = the table's size); rts_ctx_set_bvh and rts_ctx_clear_splits drop
  * it.  The table only holds node indices and tile coordinates: a camera or light that moves makes it less well balanced,
  * never wrong.  Needs the private copy of kernel 8 (without one no table is made: *tiles = 0).  Synchronous, default stream;
- * device pointers.  Results never depend on any of it (tests/test_gpu_parity.py). */
+ * device pointers.  Each stream that traces with the table gets a small state buffer at its first such trace (at most 8 streams;
+ * further ones trace without the table).  A trace under graph capture never allocates: a stream whose first trace with the table is
+ * being captured traces -- and replays -- without the table; trace once on the stream before capturing to have the table in the
+ * graph.  Results never depend on any of it (tests/test_gpu_parity.py, tests/test_gpu_graph.py). */
 typedef struct rts_split_plan {
     float    min_life_us;        /* > 0 */
     float    end_after_us;       /* >= 0: ... and only the tiles whose wave ENDED later than this after the dispatch's first wave

@@ -158,11 +158,16 @@ void dropFollow(rts_ctx* c) {
     c->follow.clear();
 }
 
-// the {occluded, done} words of the split tiles for traces on `stream` (zeroed once; every launch leaves them zero)
+// the {occluded, done} words of the split tiles for traces on `stream` (zeroed once; every launch leaves them zero).  Created
+// outside graph capture only, as follow mode's state is (followFor): nothing is allocated or cleared in a captured trace, so a
+// stream whose first trace with the table is being captured traces without the table
 uint64_t* splitState(rts_ctx* c, void* stream) {
     rts_ctx::Splits& t = c->splits;
     for (auto& e : t.state) if (e.first == stream) return e.second;
     if (t.state.size() >= 8) return nullptr;                       // more streams than that trace without the table
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &capture) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (capture != hipStreamCaptureStatusNone) return nullptr;
     uint64_t* d = nullptr;
     if (hipMalloc((void**)&d, (size_t)t.nTiles * 16 + 16) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
     // (cleared ON the stream that is about to use it: a memset on the default stream is not ordered before a launch on a

@@ -358,19 +358,8 @@ def test_generic_rays_including_nan_inf_and_axis_parallel(ctx):
 
 def test_degenerate_and_denormal_triangles(ctx):
     """Zero-area triangles 'hit' through the all-NaN rule (Appendix B-4); denormal edges must not be flushed."""
-    rs = np.random.RandomState(5)
-    P = 400
-    c = rs.random_sample((P, 1, 3)) * 10
-    tri = (c + (rs.random_sample((P, 3, 3)) - 0.5)).astype(np.float32)
-    tri[0:50, 1] = tri[0:50, 0]                                                    # v1 == v0
-    tri[50:100, 2] = tri[50:100, 1]                                                # v2 == v1 (sliver to a line)
-    tri[100:150] = tri[100:150, 0:1]                                               # all three equal (a point)
-    tiny = np.float32(1e-41)
-    tri[150:200, 1] = tri[150:200, 0] + np.array([tiny, 0, 0], np.float32)         # denormal-ish edge lengths
-    base = np.zeros((50, 3, 3), np.float32)
-    base[:, 1, 0] = tiny * 3
-    base[:, 2, 1] = tiny * 5
-    tri[200:250] = base                                                            # denormal triangles at the origin
+    tri, rs = streams.degenerate_triangles()
+    P = tri.shape[0]
     verts = tri.reshape(-1, 3)
     idx = np.arange(3 * P, dtype=np.uint32)
     packed = api.BVHBuilder().build(verts, 3, idx, P).m_packedNodes
@@ -444,28 +433,10 @@ def test_stream_with_orphan_nodes_gets_no_private_copy(ctx):
     """rts_bvh_validate accepts a stream in which a leaf's miss link skips nodes (the skipped nodes are
     orphans no walk ever reaches).  The device-side verdict must then say "not a pre-order tree" so that no wide copy is
     derived from parent entries nobody wrote; every kernel still equals the oracle on that very stream."""
-    tris = np.zeros((3, 3, 3), np.float32)
-    tris[0] = [[0, 0, 5], [4, 0, 5], [0, 4, 5]]
-    tris[1] = [[6, 6, 7], [9, 6, 7], [6, 9, 7]]
-    tris[2] = [[2, 2, 3], [3, 2, 3], [2, 3, 3]]                       # only the stray leaves point at it
-    good = streams.stream_from_tree(((0, 1), 2), tris)                # N = 5: 0 inner, 1 inner, 2 leaf, 3 leaf, 4 leaf
-    N = 5
-    bad = good.copy()
-    # root 0 -> children: leaf 1 (link 4) and leaf 4; nodes 2 and 3 are stray leaves
-    f = bad.view(np.float32)
-    f[2, :3] = tris[0, 1] - tris[0, 0]; bad[2, 3] = 2 * N + 0
-    f[3, :3] = tris[0, 2] - tris[0, 0]; bad[3, 3] = 4
-    for i in (2, 3):
-        f[2 * i, :3] = tris[2, 1] - tris[2, 0]; bad[2 * i, 3] = 2 * N + 2
-        f[2 * i + 1, :3] = tris[2, 2] - tris[2, 0]; bad[2 * i + 1, 3] = i + 1
-    f[8, :3] = tris[1, 1] - tris[1, 0]; bad[8, 3] = 2 * N + 1
-    f[9, :3] = tris[1, 2] - tris[1, 0]; bad[9, 3] = 0xFFFFFFFF
+    good, bad = streams.orphan_streams()
     assert api.bvh_validate(bad) == 3
     W, H = 64, 64
-    pos = np.zeros((H, W, 4), np.float32)
-    pos[..., 0] = 10.0 * (np.arange(W, dtype=np.float32)[None, :] + 0.5) / W
-    pos[..., 1] = 10.0 * (np.arange(H, dtype=np.float32)[:, None] + 0.5) / H
-    k = api.RayTracingConstants.make([0, 0, 0], [0.001, 0.002, 1.0], W, H)
+    pos, k = streams.orphan_frame(W, H)
     for blob, enclosed in ((good, 1), (bad, 0)):
         want, _, _ = oracle.shadow_mask(blob, k.as_array(), oracle.light_from_product(None, k), pos, W, H)
         assert 0 < want.sum() < want.size
@@ -710,10 +681,7 @@ def test_non_finite_bvh_takes_the_exact_path(ctx):
     """A packed buffer from another producer may carry Inf boxes: the fast slab test must not be used."""
     sc = scenes.terrain(9)
     verts, idx = sc.flat()
-    packed = api.BVHBuilder().build(verts, 8, idx, sc.triangle_count).m_packedNodes.copy()
-    f = packed.view(np.float32)
-    f[0, 0:3] = -np.inf                                                            # root box = everything
-    f[1, 0:3] = np.inf
+    packed = streams.infinite_root(api.BVHBuilder().build(verts, 8, idx, sc.triangle_count).m_packedNodes)   # root box = everything
     rays = _random_rays(50000, 9, sc.bbox_min - 1, sc.bbox_max + 3)
     want, _, _ = oracle.trace_rays(packed, rays)
     ctx.set_bvh(packed)
@@ -986,11 +954,7 @@ def test_mixed_sign_and_unordered_boxes_take_the_generic_slab_test(ctx):
     """Light inside the room: ray directions of one tile straddle the sign planes (generic form 8).  A blob whose
     inner boxes have bboxMin > bboxMax on an axis (another producer) must switch the ordered test off."""
     wl = workloads.prepare("cornell", 320, 320, via_obj=False)
-    packed = wl.packed.copy()
-    N = 2 * wl.prim_count - 1
-    inner = np.nonzero(packed[0:2 * N:2, 3] == 0xFFFFFFFF)[0][5:40]
-    for i in inner:                                                      # swap min.x <-> max.x on some inner nodes
-        packed[2 * i, 0], packed[2 * i + 1, 0] = packed[2 * i + 1, 0], packed[2 * i, 0]
+    packed = streams.swapped_boxes(wl.packed)                            # min.x <-> max.x on some inner nodes
     for blob, ordered in ((wl.packed, 1), (packed, 0)):
         want, _, _ = oracle.shadow_mask(blob, wl.constants.as_array(),
                                         oracle.light_from_product(wl.light, wl.constants), wl.positions, wl.W, wl.H)

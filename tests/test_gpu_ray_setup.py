@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import oracle
+import streams
 from raytracedshadows_amd import api
 
 pytestmark = pytest.mark.gpu
@@ -21,15 +22,7 @@ def ctx():
 
 @pytest.fixture(scope="module")
 def soup():
-    rng = np.random.RandomState(21)
-    c = rng.random_sample((4000, 1, 3))
-    tri = c + (rng.random_sample((4000, 3, 3)) - 0.5) * 0.08
-    floor = np.array([[[-1, 0, -1], [2, 0, -1], [2, 0, 2]], [[-1, 0, -1], [2, 0, 2], [-1, 0, 2]]], np.float64)
-    tri = np.concatenate([tri, floor]).astype(np.float32)
-    verts = np.zeros((tri.shape[0] * 3, 8), np.float32)
-    verts[:, :3] = tri.reshape(-1, 3)
-    idx = np.arange(tri.shape[0] * 3, dtype=np.uint32)
-    return api.BVHBuilder().build(verts, 8, idx, tri.shape[0]).m_packedNodes, tri
+    return streams.gate_soup()
 
 
 EDGE = np.array([0.0, -0.0, 1e-45, 3e-39, 2.0 ** -114, 2.0 ** -113, 2.0 ** -112, 1e-30, 1e30, 3e38, np.inf, -np.inf, np.nan],

@@ -46,21 +46,7 @@ def _copy_matches(ctx, packed, what):
     return rs
 
 
-def _triangles_of(packed):
-    """(P, 3, 3) triangles of a stream, in tail order: v0, v0 + e0, v0 + e1."""
-    packed = np.asarray(packed, np.uint32).reshape(-1, 4)
-    P = (packed.shape[0] + 2) // 5
-    N = 2 * P - 1
-    nodes = packed[:2 * N].reshape(N, 8)
-    f = nodes.view(np.float32)
-    leaves = np.flatnonzero(nodes[:, 3] != wc.END)
-    prim = nodes[leaves, 3].astype(np.int64) - 2 * N
-    t = np.zeros((P, 3, 3), np.float32)
-    v0 = packed[2 * N:].view(np.float32)[:, :3]
-    t[prim, 0] = v0[prim]
-    t[prim, 1] = v0[prim] + f[leaves, 0:3]
-    t[prim, 2] = v0[prim] + f[leaves, 4:7]
-    return t
+_triangles_of = streams.triangles_of
 
 
 def _moved(v):
@@ -128,25 +114,7 @@ def test_copy_of_every_device_producer(ctx, algo):
     _copy_matches(ctx, got, algo + ", after a device refit")
 
 
-def _aimed_frame(packed, target, W=32, H=32, seed=0):
-    """Positions and a point light such that every ray passes through the box of node `target` (or, when that box is not a
-    finite ordered one, through the box of the stream's finite vertices)."""
-    packed = np.asarray(packed, np.uint32).reshape(-1, 4)
-    f = packed.view(np.float32)
-    lo, hi = f[2 * target, :3].astype(np.float64), f[2 * target + 1, :3].astype(np.float64)
-    if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (lo <= hi).all()):
-        t = _triangles_of(packed).reshape(-1, 3).astype(np.float64)
-        t = t[np.isfinite(t).all(1)]
-        lo, hi = t.min(0), t.max(0)
-    ext = max(float((hi - lo).max()), 1e-30)
-    c = (lo + hi) / 2
-    light = c + ext * np.array([7.0, 9.0, 11.0])
-    rs = np.random.RandomState(seed)
-    T = lo - 0.05 * ext + rs.random_sample((H * W, 3)) * ((hi - lo) + 0.1 * ext)
-    pos = np.zeros((H, W, 4), np.float32)
-    pos[..., :3] = (T - 0.3 * (light - T)).reshape(H, W, 3)
-    k = api.RayTracingConstants.make([0, 0, 0], [0.3, 0.8, 0.5], W, H)
-    return pos, k, api.Light.make(api.Light.POINT, light.astype(np.float32))
+_aimed_frame = streams.aimed_frame
 
 
 def _every_kernel_equals_oracle(ctx, packed, pos, k, light, what):
