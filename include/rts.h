@@ -436,7 +436,8 @@ int rts_ctx_read_piece_stats(rts_ctx* ctx, uint32_t* records, uint64_t* clocks, 
 /* ---- follow mode (option "follow" 1): a split-table order that follows a moving camera, planned on the device -------------
  * A table planned on one frame fits that frame; a camera that moves 0.1 % of its view distance per frame makes it stale.  In follow
  * mode every one-sample trace where an installed split table could apply today (kernel 3 or 8, one tile per workgroup on a 2-D grid,
- * the private copy, no "wave_stats", no "wide_lane"; stripes with power-of-two bands and "row_order" 0) and none does -- an installed
+ * the private copy, no "wave_stats", no "wide_lane"; stripes with power-of-two bands and -- for follow mode alone: a stripe is always
+ * launched first row to last, and an installed table applies to it whatever the option says -- the option "row_order" 0) and none does -- an installed
  * table or a caller's tile order always wins -- records how long each tile's wave lived, and kernels on the same stream then plan
  * from those lives the order the NEXT trace of the same dispatch on that stream runs in: the front-only table with every tile in
  * it (rts_split_plan front_share 1, no pieces) -- half-octave bands of life, longest first, row-major inside a band, a tile as long

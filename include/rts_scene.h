@@ -92,6 +92,16 @@ int rtsh_split_front_order(const float* life_us, const uint32_t* tiles, size_t n
 int rtsh_follow_order(const uint32_t* life_ticks, uint32_t blocks_x, uint32_t blocks_y, uint32_t first_record, uint32_t xcd_square,
                       uint32_t life_block, uint32_t* order_out);
 
+/* The device planner of follow mode (rts_follow.hip) on lives the caller gives: what a trace in follow mode queues after its mask
+ * kernel, run on tile t's stamps {start_ticks[t], start_ticks[t] + life_ticks[t]} (mod 2^32; start_ticks NULL: 0) in buffers sized
+ * and carved as a stream's follow state is, with "follow_square" xcd_square and "follow_block" life_block.  order_out[i] = the
+ * tile of record i as bx | by << 16 (as rts_ctx_read_follow; first record 0).  Synchronous, on the default stream; refused
+ * (RTS_ERR_INVALID_ARG) while that stream is being captured, for the arguments rtsh_follow_order refuses and for a side of more
+ * than 65 536 tiles; zero tiles: RTS_OK.  Touches no stream's follow state, no counter and no option. */
+int rtsh_follow_plan_device(rts_ctx* ctx, const uint32_t* life_ticks, const uint32_t* start_ticks /* nullable: 0 */,
+                            uint32_t blocks_x, uint32_t blocks_y, uint32_t xcd_square, uint32_t life_block,
+                            uint32_t* order_out /* record i -> bx | by << 16, as rts_ctx_read_follow */);
+
 #ifdef __cplusplus
 }
 #endif

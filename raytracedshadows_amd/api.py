@@ -186,6 +186,26 @@ def follow_order(life_ticks, blocks_x, blocks_y, first_record=0, xcd_square=0, l
     return out
 
 
+_sig("rtsh_follow_plan_device", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
+
+
+def follow_plan_device(ctx, life_ticks, blocks_x, blocks_y, xcd_square=0, life_block=1, start_ticks=None):
+    """rtsh_follow_plan_device: follow mode's device planner run on the given lives (and start stamps) -- row-major tile ids in
+    record order, as follow_order returns them."""
+    life = np.ascontiguousarray(life_ticks, np.uint32).ravel()
+    if life.size != blocks_x * blocks_y:
+        raise RtsError(1, "follow_plan_device: life_ticks must hold blocks_x * blocks_y entries")
+    start = None
+    if start_ticks is not None:
+        start = np.ascontiguousarray(start_ticks, np.uint32).ravel()
+        if start.size != life.size:
+            raise RtsError(1, "follow_plan_device: start_ticks must hold blocks_x * blocks_y entries")
+    out = np.zeros(life.size, np.uint32)
+    _check(_lib.rtsh_follow_plan_device(ctx.handle, _ptr(life), _ptr(start) if start is not None else None, blocks_x, blocks_y,
+                                        xcd_square, life_block, _ptr(out)), "rtsh_follow_plan_device")
+    return (out & 0xFFFF) + (out >> 16) * np.uint32(blocks_x)
+
+
 def stripe_rows(height, band_rows, n_stripes, stripe):
     """rtsh_stripe_rows: the virtual rows of one interleaved stripe's dispatch (host logic, no device) -- band_rows x the
     bands the stripe owns, 0 for a stripe without a band."""

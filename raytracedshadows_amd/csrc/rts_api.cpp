@@ -579,6 +579,22 @@ static const rts::FollowBands& followBands() {
     return table;
 }
 
+// follow mode: one allocation per stream for a dispatch of n tiles -- lives (2 u32 per tile), front map (8 columns of `stride`
+// records), all-ones skip map, planner scratch, each from a 256-byte boundary (followFor; rtsh_follow_plan_device carves the same)
+struct FollowLayout {
+    uint32_t stride;
+    size_t livesB, mapB, skipB, scratchB;
+    explicit FollowLayout(uint32_t n) : stride((n + 7u) / 8u) {
+        const auto al = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
+        livesB = al((size_t)n * 8); mapB = al((size_t)stride * 32); skipB = al(((size_t)n + 31) / 32 * 4 + 4);
+        scratchB = rts::followScratchBytes(n);
+    }
+    size_t mapAt() const { return livesB; }
+    size_t skipAt() const { return livesB + mapB; }
+    size_t scratchAt() const { return livesB + mapB + skipB; }
+    size_t bytes() const { return livesB + mapB + skipB + scratchB; }
+};
+
 // follow mode: the state of `stream` for this dispatch geometry.  A stream seen with another geometry starts over; a ninth stream
 // evicts the least recently used.  Created and reset outside graph capture only (nothing is allocated in a captured trace):
 // NULL = run the everyday launch.
@@ -604,14 +620,11 @@ static rts_ctx::Follow* followFor(rts_ctx* c, void* stream, const TraceParams& p
         try { c->follow.emplace_back(); } catch (...) { return nullptr; }
         f = &c->follow.back();
     }
-    const uint32_t n = p.blocksX * p.blocksY, stride = (n + 7u) / 8u;
-    const auto al = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
-    const size_t livesB = al((size_t)n * 8), mapB = al((size_t)stride * 32), skipB = al(((size_t)n + 31) / 32 * 4 + 4);
-    const size_t scratchB = rts::followScratchBytes(n);
+    const FollowLayout lay(p.blocksX * p.blocksY);
     void* d = nullptr;
-    hipError_t e = hipMalloc(&d, livesB + mapB + skipB + scratchB);
-    if (e == hipSuccess) e = hipMemsetAsync((char*)d + livesB + mapB, 0xFF, skipB, (hipStream_t)stream);    // (on the stream that uses it)
-    if (e == hipSuccess) e = hipMemsetAsync((char*)d + livesB + mapB + skipB, 0, scratchB, (hipStream_t)stream);
+    hipError_t e = hipMalloc(&d, lay.bytes());
+    if (e == hipSuccess) e = hipMemsetAsync((char*)d + lay.skipAt(), 0xFF, lay.skipB, (hipStream_t)stream);    // (on the stream that uses it)
+    if (e == hipSuccess) e = hipMemsetAsync((char*)d + lay.scratchAt(), 0, lay.scratchB, (hipStream_t)stream);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         if (d) (void)hipFree(d);
@@ -623,10 +636,10 @@ static rts_ctx::Follow* followFor(rts_ctx* c, void* stream, const TraceParams& p
     f->blocksX = p.blocksX; f->blocksY = p.blocksY;
     f->d_mem = d;
     f->d_lives = (uint32_t*)d;
-    f->d_frontMap = (uint32_t*)((char*)d + livesB);
-    f->d_skipMap = (uint32_t*)((char*)d + livesB + mapB);
-    f->d_scratch = (char*)d + livesB + mapB + skipB;
-    f->frontStride = stride;
+    f->d_frontMap = (uint32_t*)((char*)d + lay.mapAt());
+    f->d_skipMap = (uint32_t*)((char*)d + lay.skipAt());
+    f->d_scratch = (char*)d + lay.scratchAt();
+    f->frontStride = lay.stride;
     f->planned = false;
     f->lastUse = ++c->followClock;
     return f;
@@ -774,10 +787,11 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
     }
     // follow mode: where a split table could apply but none does, the trace records its tile lives and runs the order the planner
     // made from the lives of the stream's last trace of this dispatch (the front-only table launch, every tile a record: launch
-    // parameters that depend on the geometry alone); then the planner's kernels make the next one, in the stream
+    // parameters that depend on the geometry alone); then the planner's kernels make the next one, in the stream.  (Stripes: the
+    // option "row_order" itself must be 0, as include/rts.h says -- p.rowOrder is 0 for every stripe, whatever the option.)
     rts_ctx::Follow* fol = nullptr;
     if (c->followOn && !p.pieces && (variant == rts::V_PACKET || variant == rts::V_WIDE) && c->blockWaves == 1 && p.nsamples == 1 &&
-        p.grid2d && !p.waveStats && !c->wideLane && p.wide && (n_stripes <= 1 || (p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0)))
+        p.grid2d && !p.waveStats && !c->wideLane && p.wide && (n_stripes <= 1 || (p.bandShift != 0xFFFFFFFFu && c->rowOrder == 0)))
         fol = followFor(c, stream, p, band_rows, n_stripes, stripe);
     if (fol) {
         p.followLives = fol->d_lives;
@@ -1333,6 +1347,14 @@ extern "C" int rtsh_follow_order(const uint32_t* life_ticks, uint32_t blocks_x, 
     return RTS_OK;
 }
 
+// the records of a front map of `tiles` tiles (record i in column i mod 8, row i / 8), read back: order[i] = bx | by << 16
+static int readFollowOrder(const uint32_t* d_frontMap, uint32_t frontStride, size_t tiles, uint32_t* order) {
+    std::vector<uint32_t> buf((size_t)frontStride * 8);
+    RTS_HIP(hipMemcpy(buf.data(), d_frontMap, buf.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < tiles; ++i) order[i] = buf[(i & 7u) * frontStride + (i >> 3)];
+    return RTS_OK;
+}
+
 extern "C" int rts_ctx_read_follow(rts_ctx* c, void* stream, uint32_t* lives, uint32_t* order, size_t tiles) {
     if (!c) return RTS_ERR_INVALID_ARG;
     const rts_ctx::Follow* f = nullptr;
@@ -1346,13 +1368,46 @@ extern "C" int rts_ctx_read_follow(rts_ctx* c, void* stream, uint32_t* lives, ui
             RTS_HIP(hipMemcpy(buf.data(), f->d_lives, tiles * 8, hipMemcpyDeviceToHost));
             for (size_t t = 0; t < tiles; ++t) lives[t] = buf[2 * t + 1] - buf[2 * t];
         }
-        if (order) {
-            std::vector<uint32_t> buf((size_t)f->frontStride * 8);
-            RTS_HIP(hipMemcpy(buf.data(), f->d_frontMap, buf.size() * 4, hipMemcpyDeviceToHost));
-            for (size_t i = 0; i < tiles; ++i) order[i] = buf[(i & 7u) * f->frontStride + (i >> 3)];
-        }
+        if (order) { const int s = readFollowOrder(f->d_frontMap, f->frontStride, tiles, order); if (s != RTS_OK) return s; }
     } catch (...) { return RTS_ERR_CAPACITY; }
     return RTS_OK;
+}
+
+// Harness (include/rts_scene.h): the device planner on the caller's lives, in buffers laid out as a stream's follow state is.
+// No stream's state, no counter and no option is touched.
+extern "C" int rtsh_follow_plan_device(rts_ctx* c, const uint32_t* life_ticks, const uint32_t* start_ticks, uint32_t blocks_x,
+                                       uint32_t blocks_y, uint32_t xcd_square, uint32_t life_block, uint32_t* order_out) {
+    const uint64_t n64 = (uint64_t)blocks_x * blocks_y;
+    if (!c || (n64 && (!life_ticks || !order_out)) || n64 > (1ull << 31) || xcd_square > 65535u || life_block > 64u) return RTS_ERR_INVALID_ARG;
+    if (!n64) return RTS_OK;
+    if (blocks_x > 65536u || blocks_y > 65536u) return RTS_ERR_INVALID_ARG;          // (a record holds bx and by in 16 bits each)
+    RTS_HIP(hipSetDevice(c->device));
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)nullptr, &capture) != hipSuccess) { (void)hipGetLastError(); return RTS_ERR_INVALID_ARG; }
+    if (capture != hipStreamCaptureStatusNone) return RTS_ERR_INVALID_ARG;
+    const uint32_t n = (uint32_t)n64;
+    const FollowLayout lay(n);
+    void* d = nullptr;
+    int status = RTS_OK;
+    try {
+        std::vector<uint32_t> stamps((size_t)n * 2);
+        for (uint32_t t = 0; t < n; ++t) {
+            const uint32_t s = start_ticks ? start_ticks[t] : 0u;
+            stamps[2 * (size_t)t] = s; stamps[2 * (size_t)t + 1] = s + life_ticks[t];      // (mod 2^32, as the clock's low word wraps)
+        }
+        hipError_t e = hipMalloc(&d, lay.bytes());
+        if (e == hipSuccess) e = hipMemcpy(d, stamps.data(), (size_t)n * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemset((char*)d + lay.mapAt(), 0xFF, lay.mapB);
+        if (e == hipSuccess) e = hipMemset((char*)d + lay.scratchAt(), 0, lay.scratchB);
+        if (e == hipSuccess) e = rts::launchFollowPlan((const uint32_t*)d, blocks_x, blocks_y, xcd_square, life_block, followBands(),
+                                                       (char*)d + lay.scratchAt(), (uint32_t*)((char*)d + lay.mapAt()), lay.stride, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        status = hipStatus(e);
+        if (status == RTS_OK) status = readFollowOrder((const uint32_t*)((char*)d + lay.mapAt()), lay.stride, n, order_out);
+    } catch (...) { status = RTS_ERR_CAPACITY; }
+    if (status != RTS_OK) (void)hipGetLastError();
+    if (d) (void)hipFree(d);
+    return status;
 }
 
 // Plans the split table for ONE dispatch geometry (see include/rts.h).  Synchronous, default stream.
