@@ -295,6 +295,52 @@ int rts_trace_shadow_mask_active_stripes_device(rts_ctx* ctx, const rts_constant
 int rts_trace_rays(rts_ctx* ctx, const rts_ray* rays, size_t n, uint8_t* out);
 int rts_trace_rays_device(rts_ctx* ctx, const rts_ray* d_rays, size_t n, uint8_t* d_out, void* stream);
 
+/* OCCLUDER DISTANCE: the nearest blocker's ray parameter beside the shadow byte (hit distance for shadow denoisers, contact-
+ * hardening penumbrae -- (1 - t) / t x light size for a point-light ray, which runs from the surface, t = 0, to the light, t = 1 --,
+ * distance-based fading).
+ * DEFINITION, exact: walk the node stream as intersectAny does (comp:75-111), same box test, same triangle test, but do not
+ * return at a hit -- a leaf that hits goes on through its miss link like one that misses.  (The box test never looks at tmax,
+ * comp:61-73, so the leaves visited do not depend on any hit.)  Every triangle the test accepts contributes c = (t > 0) ? t : +0,
+ * t as intersectRayTri computes it (an accepted NaN or -0 counts as +0); distance = the minimum, +Inf (0x7F800000) if there is
+ * none.  Equivalently: the smallest T >= +0 for which the reference's any-hit with tmax = min(T, the ray's tmax) reports a hit.
+ * No box is culled against the best t so far (boxes and triangles round differently: a cull could change a bit), so an occluded
+ * ray costs what a lit one costs.  Units are the ray parameter's: directional light = world distance along lightDirection as
+ * given (tmax 1e9), point light = fraction of the segment surface -> light (tmax 1).
+ *   rts_trace_rays_distance*: out_t[i] for generic ray i (n floats).
+ *   rts_trace_shadow_distance*: the ray is the one rts_trace_shadow_mask* sets up (same bias, same light model).
+ *     distance : W x H floats, row-major like the mask.  Every pixel of the rows the call owns is written: the ray's distance where
+ *                the pixel is active, +0.0f where it is not.  Rows outside the range / stripe are not touched.
+ *     active   : as in rts_trace_shadow_mask_active*, or NULL = every pixel.  Inactive positions may hold anything and change no
+ *                other pixel.
+ *     mask     : NULL, or W x H bytes that receive exactly what rts_trace_shadow_mask_active* writes -- so
+ *                mask[p] == (distance[p] == +Inf) everywhere, inactive pixels (0, +0) included.
+ *   * light->nsamples > 1 returns RTS_ERR_INVALID_ARG in this version.
+ *   * the stripes form: as for the mask traces, a stripe that owns no band launches nothing, writes nothing and returns RTS_OK.
+ *   * results never depend on an option.  "kernel" picks the FAMILY: 0, 1, 2, 7 (and -1 below 256 K pixels), and every wave that
+ *     must take the exact path, run the lane-per-ray walk with work sharing (16 x 16 blocks; a stripe's band is then a multiple of
+ *     16 rows); 3..6 (and -1 from 256 K pixels) the stackless packet over 8 x 8 tiles.  THIS VERSION: 8 and 9 run the stackless
+ *     packet too -- the wide walk culls with a conservative test and confirms single hits; its distance form is a follow-up.
+ *     Generic rays always run lane per ray.  "packet_budget", "packet_share", "xcd_swizzle" and "row_order" apply (speed only).
+ *   * a distance trace ignores split tables, tile orders, follow mode, "block_waves", "wide_lane", wave statistics and the clock
+ *     probe, and never drops or alters any of them.
+ *   * the device forms are asynchronous, allocate nothing and read nothing back; under graph capture each adds ONE kernel node and
+ *     nothing else, constants, light and options by value as for the mask traces.  The host forms copy in, trace, copy out.
+ *   * get-only option "distance_traces": distance launches so far; rts_ctx_last_kernel_name then names "shadowDistanceShareKernel",
+ *     "traceRaysDistanceKernel", or the packet instantiation launched: "shadowDistancePacketKernel<rows>" (a row range on a 2-D
+ *     grid), "shadowDistancePacketKernel<bands>" (a stripe of power-of-two bands) or "shadowDistancePacketKernel<general>". */
+int rts_trace_rays_distance(rts_ctx* ctx, const rts_ray* rays, size_t n, float* out_t);
+int rts_trace_rays_distance_device(rts_ctx* ctx, const rts_ray* d_rays, size_t n, float* d_out_t, void* stream);
+int rts_trace_shadow_distance(rts_ctx* ctx, const rts_constants* constants, const rts_light* light, const float* positions,
+                              const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                              float* distance, uint8_t* mask);
+int rts_trace_shadow_distance_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light,
+                                     const float* d_positions, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                     uint32_t row_begin, uint32_t row_end, float* d_distance, uint8_t* d_mask, void* stream);
+int rts_trace_shadow_distance_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light,
+                                             const float* d_positions, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                             uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, float* d_distance,
+                                             uint8_t* d_mask, void* stream);
+
 /* ---- device-memory and timing plumbing (so callers need no HIP headers) ------ */
 int rts_device_count(int* count);
 int rts_device_malloc(rts_ctx* ctx, void** d_ptr, size_t bytes);

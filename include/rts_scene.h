@@ -66,6 +66,20 @@ int rtsh_facing_active(const rts_constants* constants, const rts_light* light, c
 int rtsh_facing_active_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light, const float* d_positions,
                               const float* d_normals, uint32_t W, uint32_t H, uint8_t* d_active, void* stream);
 
+/* OCCLUDER DISTANCE on the host: the definition of rts_trace_rays_distance / rts_trace_shadow_distance (include/rts.h) as one
+ * straight loop per ray -- the reference's walk without its return at a hit, its box and triangle tests, and the library's ray
+ * set-up (same bias, same light model) --, multi-threaded (threads: 0 = all host threads).  Runs without a GPU: the checker of the
+ * device forms, bit for bit.  packed / count_vec4: the Appendix-A stream (validated like rts_ctx_set_bvh's input).
+ *   rtsh_rays_distance   : out_t[i] = distance of generic ray i.
+ *   rtsh_shadow_distance : for rows [row_begin, row_end): distance[p] = the ray's distance where active[p] != 0 (active == NULL:
+ *                          everywhere), +0.0f where it is 0; mask (nullable) = 1 exactly where the distance is +Inf, 0 elsewhere
+ *                          and at inactive pixels.  Other rows are not touched.  Inactive positions are never read.
+ *                          light->nsamples > 1 returns RTS_ERR_INVALID_ARG (this version traces one sample). */
+int rtsh_rays_distance(const rts_vec4u* packed, size_t count_vec4, const rts_ray* rays, size_t n, float* out_t, int threads);
+int rtsh_shadow_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_light* light,
+                         const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                         uint32_t row_end, float* distance, uint8_t* mask, int threads);
+
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.
  * Call with vertices == NULL to query *vertex_count (3 per triangle) first.  Returns RTS_OK,

@@ -144,6 +144,17 @@ _sig("rts_trace_shadow_mask_active_stripes_device", C.c_int, C.c_void_p, C.POINT
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rts_trace_rays", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 _sig("rts_trace_rays_device", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
+_sig("rts_trace_rays_distance", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_sig("rts_trace_rays_distance_device", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p)
+_sig("rts_trace_shadow_distance", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_shadow_distance_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rts_trace_shadow_distance_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_rays_distance", C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int)
+_sig("rtsh_shadow_distance", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
 _sig("rts_device_malloc", C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t)
 _sig("rts_device_free", C.c_int, C.c_void_p, C.c_void_p)
 _sig("rts_memcpy_h2d", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -502,6 +513,58 @@ class ShadowContext:
         _check(_lib.rts_trace_rays_device(self._h, C.c_void_p(d_rays), n, C.c_void_p(d_out), C.c_void_p(stream or 0)),
                "rts_trace_rays_device")
 
+    # -- occluder distance (include/rts.h): the nearest accepted triangle's ray parameter, +Inf where the ray is lit ----------
+    def trace_rays_distance(self, rays):
+        """``rays``: float32[n, 8] = {o.xyz, tmax, d.xyz, 0}; returns float32[n]."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        out = np.zeros(rays.shape[0], dtype=np.float32)
+        _check(_lib.rts_trace_rays_distance(self._h, _ptr(rays), rays.shape[0], _ptr(out)), "rts_trace_rays_distance")
+        return out
+
+    def trace_rays_distance_device(self, d_rays, n, d_out_t, stream=None):
+        """Device-pointer form of :meth:`trace_rays_distance` (asynchronous on ``stream``); d_out_t = n floats."""
+        _check(_lib.rts_trace_rays_distance_device(self._h, C.c_void_p(d_rays), n, C.c_void_p(d_out_t), C.c_void_p(stream or 0)),
+               "rts_trace_rays_distance_device")
+
+    def trace_shadow_distance(self, constants, positions, width, height, light=None, row_begin=0, row_end=None, active=None,
+                              out=None, mask=None, want_mask=True):
+        """Host-pointer dispatch; returns ``(float32[H, W] distance, uint8[H, W] mask)`` (mask None with ``want_mask`` False).
+        ``out`` / ``mask``: arrays to write into (rows outside the range keep their contents)."""
+        positions = np.ascontiguousarray(positions, dtype=np.float32)
+        if positions.size != width * height * 4:
+            raise RtsError(1, "trace_shadow_distance: positions must be W*H*4 floats")
+        row_end = height if row_end is None else row_end
+        dist = out if out is not None else np.zeros((height, width), dtype=np.float32)
+        if mask is None and want_mask:
+            mask = np.zeros((height, width), dtype=np.uint8)
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.uint8)
+            if active.size != width * height:
+                raise RtsError(1, "trace_shadow_distance: active must be W*H bytes")
+        lp = C.byref(light) if light is not None else None
+        _check(_lib.rts_trace_shadow_distance(self._h, C.byref(constants), lp, _ptr(positions), _ptr(active) if active is not None else None,
+                                              width, height, row_begin, row_end, _ptr(dist), _ptr(mask) if mask is not None else None),
+               "rts_trace_shadow_distance")
+        return dist, mask
+
+    def trace_shadow_distance_device(self, constants, d_positions, width, height, d_distance, d_mask=None, light=None, row_begin=0,
+                                     row_end=None, stream=None, d_active=None):
+        """Device pointers, asynchronous: d_distance = width * height floats, d_mask / d_active = width * height bytes or None."""
+        row_end = height if row_end is None else row_end
+        lp = C.byref(light) if light is not None else None
+        _check(_lib.rts_trace_shadow_distance_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions), C.c_void_p(d_active or 0),
+                                                     width, height, row_begin, row_end, C.c_void_p(d_distance), C.c_void_p(d_mask or 0),
+                                                     C.c_void_p(stream or 0)), "rts_trace_shadow_distance_device")
+
+    def trace_shadow_distance_stripes_device(self, constants, d_positions, width, height, d_distance, band_rows, n_stripes, stripe,
+                                             d_mask=None, light=None, stream=None, d_active=None):
+        """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        lp = C.byref(light) if light is not None else None
+        _check(_lib.rts_trace_shadow_distance_stripes_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
+                                                             C.c_void_p(d_active or 0), width, height, band_rows, n_stripes, stripe,
+                                                             C.c_void_p(d_distance), C.c_void_p(d_mask or 0), C.c_void_p(stream or 0)),
+               "rts_trace_shadow_distance_stripes_device")
+
     # -- plumbing ---------------------------------------------------------------------------
     def stream_create(self):
         s = C.c_void_p()
@@ -761,6 +824,38 @@ def facing_active_device(ctx, constants, light, d_positions, d_normals, width, h
     _check(_lib.rtsh_facing_active_device(ctx.handle, C.byref(constants), lp, C.c_void_p(d_positions or 0), C.c_void_p(d_normals),
                                           width, height, C.c_void_p(d_active), C.c_void_p(stream or 0)),
            "rtsh_facing_active_device")
+
+
+def rays_distance(packed, rays, threads=0):
+    """Occluder distance of generic rays on the host (rtsh_rays_distance, no GPU): float32[n]."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+    out = np.zeros(rays.shape[0], np.float32)
+    _check(_lib.rtsh_rays_distance(_ptr(packed), packed.shape[0], _ptr(rays), rays.shape[0], _ptr(out), threads), "rtsh_rays_distance")
+    return out
+
+
+def shadow_distance(packed, constants, light, positions, width, height, active=None, row_begin=0, row_end=None, out=None, mask=None,
+                    threads=0, want_mask=True):
+    """Occluder distance of a frame's shadow rays on the host (rtsh_shadow_distance, no GPU): ``(float32[H, W], uint8[H, W])``
+    (mask None with ``want_mask`` False).  ``out`` / ``mask``: arrays to write into (rows outside the range keep their contents)."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    positions = np.ascontiguousarray(positions, np.float32)
+    if positions.size != width * height * 4:
+        raise RtsError(1, "shadow_distance: positions must be W*H*4 floats")
+    if active is not None:
+        active = np.ascontiguousarray(active, np.uint8)
+        if active.size != width * height:
+            raise RtsError(1, "shadow_distance: active must be W*H bytes")
+    row_end = height if row_end is None else row_end
+    dist = out if out is not None else np.zeros((height, width), np.float32)
+    if mask is None and want_mask:
+        mask = np.zeros((height, width), np.uint8)
+    lp = C.byref(light) if light is not None else None
+    _check(_lib.rtsh_shadow_distance(_ptr(packed), packed.shape[0], C.byref(constants), lp, _ptr(positions),
+                                     _ptr(active) if active is not None else None, width, height, row_begin, row_end, _ptr(dist),
+                                     _ptr(mask) if mask is not None else None, threads), "rtsh_shadow_distance")
+    return dist, mask
 
 
 def write_ppm(path, rgb):

@@ -34,6 +34,8 @@ struct rts_ctx {
     void* d_out = nullptr; size_t outBytes = 0;
     void* d_act = nullptr; size_t actBytes = 0;      // ... and for the active map of rts_trace_shadow_mask_active
     uint64_t activeTraces = 0;                        // launches with an active map (get-only option "active_traces")
+    void* d_dist = nullptr; size_t distBytes = 0;     // staging for the distances of the host-pointer distance traces
+    uint64_t distanceTraces = 0;                      // launches of a distance kernel (get-only option "distance_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
     int packetShare = 4;
@@ -391,6 +393,7 @@ int rts_ctx_destroy(rts_ctx* c) {
     if (c->d_in) (void)hipFree(c->d_in);
     if (c->d_out) (void)hipFree(c->d_out);
     if (c->d_act) (void)hipFree(c->d_act);
+    if (c->d_dist) (void)hipFree(c->d_dist);
     if (c->d_waveStats) (void)hipFree(c->d_waveStats);
     if (c->d_tileOrder) (void)hipFree(c->d_tileOrder);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
@@ -526,6 +529,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "follow_traces")) { *value = (int)(c->followTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "follow_ordered")) { *value = (int)(c->followOrdered & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "active_traces")) { *value = (int)(c->activeTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "distance_traces")) { *value = (int)(c->distanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
     if (!strcmp(key, "tile_order_planned")) { *value = c->tileOrderPlanned ? 1 : 0; return RTS_OK; }
@@ -927,6 +931,125 @@ int rts_trace_rays(rts_ctx* c, const rts_ray* rays, size_t n, uint8_t* out) {
     s = rts_trace_rays_device(c, (const rts_ray*)c->d_in, n, (uint8_t*)c->d_out, nullptr);
     if (s != RTS_OK) return s;
     RTS_HIP(hipMemcpy(out, c->d_out, n, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+// ---- occluder distance (include/rts.h): the nearest accepted triangle's t beside the shadow byte ---------------------------------
+// One launch of a distance kernel (rts_distance.inc), one tile (or block) per workgroup in natural order.  The kernel FAMILY follows
+// "kernel" as for an active trace, except that 8 and 9 run the stackless packet too (the wide walk has no distance form yet).  No
+// table, order, follow state or statistic is used or touched.
+static int traceDistanceImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const uint8_t* d_active,
+                             uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint32_t band_rows, uint32_t n_stripes,
+                             uint32_t stripe, float* d_distance, uint8_t* d_mask, void* stream) {
+    if (!c || !k || !d_positions || !d_distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
+    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 1)) return RTS_ERR_INVALID_ARG;     // one sample in this version
+    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;      // tile counts are 32-bit on the device
+    TraceParams p;
+    int s = fillParams(c, p);
+    if (s != RTS_OK) return s;
+    if (row_begin == row_end) return RTS_OK;
+    RTS_HIP(hipSetDevice(c->device));
+    p.positions = (const float4*)d_positions;
+    p.mask = d_mask;
+    p.distance = d_distance;
+    p.activeMap = d_active;
+    p.W = W; p.H = H; p.rowBegin = row_begin; p.rowEnd = row_end;
+    p.bandRows = band_rows; p.nStripes = n_stripes; p.stripe = stripe;
+    p.bandShift = 0xFFFFFFFFu;
+    if (n_stripes > 1 && band_rows % 8 == 0) {
+        const uint32_t tiles = band_rows / 8;
+        if ((tiles & (tiles - 1)) == 0) { uint32_t sh = 0; while ((1u << sh) < tiles) ++sh; p.bandShift = sh; }
+    }
+    uint32_t rows = row_end - row_begin;
+    if (n_stripes > 1) rows = stripeRows(H, band_rows, n_stripes, stripe);     // virtual rows = whole owned bands
+    if (rows == 0) return RTS_OK;                                                 // (a stripe without a band: no launch)
+    const uint64_t pixels = (uint64_t)W * rows;
+    int variant = c->variant;
+    if (variant == rts::V_AUTO) variant = pixels < (1u << 18) ? rts::V_SHARE : rts::V_PACKET;
+    else variant = (variant >= rts::V_PACKET && variant != rts::V_SHARE) ? rts::V_PACKET : rts::V_SHARE;
+    const uint32_t b = variant == rts::V_SHARE ? 16u : 8u;       // pixels per side of a workgroup's block
+    if (n_stripes > 1 && band_rows % b != 0) return RTS_ERR_INVALID_ARG;
+    p.blocksX = (W + b - 1) / b;
+    p.blocksY = (rows + b - 1) / b;
+    p.nBlocks = p.blocksX * p.blocksY;
+    p.swizzle = c->swizzle ? 1u : 0u;
+    p.gridBlocks = p.swizzle ? ((p.nBlocks + 7) / 8) * 8 : p.nBlocks;
+    p.grid2d = (!p.swizzle && p.blocksY <= 65535u) ? 1u : 0u;
+    p.rowOrder = (p.grid2d && n_stripes <= 1) ? (uint32_t)c->rowOrder : 0u;
+    setLight(p, k, light);
+    ++c->launches;
+    ++c->distanceTraces;
+    const char* name = "";
+    const hipError_t e = rts::launchShadowDistance(variant, p, (hipStream_t)stream, &name);
+    c->lastKernel = name;
+    return hipStatus(e);
+}
+
+int rts_trace_shadow_distance_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
+                                     const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                     float* d_distance, uint8_t* d_mask, void* stream) {
+    return traceDistanceImpl(c, k, light, d_positions, d_active, W, H, row_begin, row_end, 0, 1, 0, d_distance, d_mask, stream);
+}
+
+int rts_trace_shadow_distance_stripes_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
+                                             const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes,
+                                             uint32_t stripe, float* d_distance, uint8_t* d_mask, void* stream) {
+    if (band_rows == 0 || band_rows % 8 != 0 || n_stripes == 0 || stripe >= n_stripes) return RTS_ERR_INVALID_ARG;
+    if (n_stripes == 1) return traceDistanceImpl(c, k, light, d_positions, d_active, W, H, 0, H, 0, 1, 0, d_distance, d_mask, stream);
+    return traceDistanceImpl(c, k, light, d_positions, d_active, W, H, 0, H, band_rows, n_stripes, stripe, d_distance, d_mask, stream);
+}
+
+int rts_trace_shadow_distance(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
+                              uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
+    if (!c || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
+    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 1)) return RTS_ERR_INVALID_ARG;
+    if (!c->d_bvh) return RTS_ERR_NO_BVH;
+    if (row_begin == row_end) return RTS_OK;
+    RTS_HIP(hipSetDevice(c->device));
+    // Only the rows travel, as in rts_trace_shadow_mask: positions, map, distances and mask of [row_begin,row_end) as a frame of their own.
+    const uint32_t rows = row_end - row_begin;
+    const size_t inB = (size_t)rows * W * 16, outB = (size_t)rows * W;
+    int s = ensure(&c->d_in, &c->inBytes, inB);
+    if (s == RTS_OK) s = ensure(&c->d_dist, &c->distBytes, outB * 4);
+    if (s == RTS_OK && mask) s = ensure(&c->d_out, &c->outBytes, outB);
+    if (s == RTS_OK && active) s = ensure(&c->d_act, &c->actBytes, outB);
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(c->d_in, positions + (size_t)row_begin * W * 4, inB, hipMemcpyHostToDevice));
+    if (active) RTS_HIP(hipMemcpy(c->d_act, active + (size_t)row_begin * W, outB, hipMemcpyHostToDevice));
+    s = rts_trace_shadow_distance_device(c, k, light, (const float*)c->d_in, active ? (const uint8_t*)c->d_act : nullptr, W, rows, 0, rows,
+                                         (float*)c->d_dist, mask ? (uint8_t*)c->d_out : nullptr, nullptr);
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(distance + (size_t)row_begin * W, c->d_dist, outB * 4, hipMemcpyDeviceToHost));
+    if (mask) RTS_HIP(hipMemcpy(mask + (size_t)row_begin * W, c->d_out, outB, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, float* d_out_t, void* stream) {
+    if (!c || (n && (!d_rays || !d_out_t)) || n > (1ull << 38)) return RTS_ERR_INVALID_ARG;   // grid.x is 31-bit
+    TraceParams p;
+    int s = fillParams(c, p);
+    if (s != RTS_OK) return s;
+    if (n == 0) return RTS_OK;
+    RTS_HIP(hipSetDevice(c->device));
+    p.rays = d_rays; p.distance = d_out_t; p.nrays = n;
+    c->lastKernel = "traceRaysDistanceKernel";
+    ++c->launches;
+    ++c->distanceTraces;
+    return hipStatus(rts::launchTraceRaysDistance(p, (hipStream_t)stream));
+}
+
+int rts_trace_rays_distance(rts_ctx* c, const rts_ray* rays, size_t n, float* out_t) {
+    if (!c || (n && (!rays || !out_t))) return RTS_ERR_INVALID_ARG;
+    if (!c->d_bvh) return RTS_ERR_NO_BVH;
+    if (n == 0) return RTS_OK;
+    RTS_HIP(hipSetDevice(c->device));
+    int s = ensure(&c->d_in, &c->inBytes, n * sizeof(rts_ray));
+    if (s == RTS_OK) s = ensure(&c->d_dist, &c->distBytes, n * 4);
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(c->d_in, rays, n * sizeof(rts_ray), hipMemcpyHostToDevice));
+    s = rts_trace_rays_distance_device(c, (const rts_ray*)c->d_in, n, (float*)c->d_dist, nullptr);
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(out_t, c->d_dist, n * 4, hipMemcpyDeviceToHost));
     return RTS_OK;
 }
 

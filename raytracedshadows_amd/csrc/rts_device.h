@@ -61,6 +61,9 @@ struct TraceParams {
         // the dispatch, row-major; non-NULL only in the launches of shadowMaskFollowKernel.  (It shares the slot of the generic rays'
         // output, which no mask kernel reads: the argument block keeps its size, and every other kernel its code.)
         uint32_t* followLives;
+        // distance traces (rts_trace_shadow_distance*, rts_trace_rays_distance*): W x H floats beside the (then optional) mask, or one
+        // float per generic ray; non-NULL only in the launches of the distance kernels (rts_distance.inc).  The same slot again.
+        float* distance;
     };
     uint64_t nrays;
     const uint32_t* tileOrder; // optional: block i works on tile tileOrder[i] (device array of nBlocks entries)
@@ -109,6 +112,10 @@ hipError_t launchShadowMask(int variant, int wavesPerBlock, const TraceParams& p
 // stackless packet, V_WIDE: the wide packet); one tile per workgroup.  *name: the kernel's stable name.
 hipError_t launchShadowMaskActive(int variant, const TraceParams& p, hipStream_t stream, const char** name);
 hipError_t launchTraceRays(int variant, const TraceParams& p, hipStream_t stream);
+// distance traces (rts_distance.inc): V_SHARE = lane per ray over 16 x 16 blocks, V_PACKET = the stackless packet over 8 x 8 tiles;
+// p.distance is written, p.mask and p.activeMap may be NULL.  *name: the kernel's stable name.
+hipError_t launchShadowDistance(int variant, const TraceParams& p, hipStream_t stream, const char** name);
+hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream);   // p.rays -> p.distance, lane per ray
 // follow mode (rts_follow.hip): the per-band lower bounds of the tick counts (band b = lifeBand of the host, bands longest first)
 constexpr uint32_t FOLLOW_BANDS = 55;          // lifeBand -4 (0.25 us and less) .. 50 (2^32 - 1 ticks, 42.9 s, is in band 50)
 constexpr int FOLLOW_BAND_LOW = -4;

@@ -1894,4 +1894,6 @@ hipError_t launchTraceRays(int variant, const TraceParams& p, hipStream_t stream
     return hipGetLastError();
 }
 
+#include "rts_distance.inc"
+
 } // namespace rts

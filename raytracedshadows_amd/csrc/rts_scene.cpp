@@ -120,3 +120,133 @@ extern "C" int rtsh_facing_active(const rts_constants* k, const rts_light* light
     for (size_t i = 0; i < (size_t)W * H; ++i) active[i] = facingPixel(c, positions ? positions + i * 4 : zero, normals + i * 4);
     return RTS_OK;
 }
+
+// ---- occluder distance on the host (include/rts_scene.h): the checker of rts_trace_shadow_distance* and rts_trace_rays_distance* ----
+// The definition of include/rts.h spelled as one straight loop per ray: the reference's walk (comp:75-111) without its return at a
+// hit, the reference's box test (comp:61-73, GLSL compare-select min / max) and triangle test (comp:41-59), and the library's ray
+// set-up in its general form (comp:128-146 + the point-light extension; rts_kernels.hip: makeShadowRay below its fast path, whose
+// bits are the same wherever it applies).  This file is compiled without contraction, like the kernels.
+namespace rts_harness {
+namespace {
+inline float gmin(float x, float y) { return (y < x) ? y : x; }         // GLSL min
+inline float gmax(float x, float y) { return (x < y) ? y : x; }         // GLSL max
+inline uint32_t asBits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+inline V3 crossG(V3 a, V3 b) { return V3{ a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y }; }   // GLSL cross()
+
+struct DRay { V3 o; float tmax; V3 d; };
+
+inline float epsilonFor(float f, uint32_t diff) {                        // comp:113-120
+    uint32_t u = asBits(f);
+    uint32_t e = (u >> 23) & 0xFFu;
+    e -= (diff < e) ? diff : e;
+    u = (u & ~(0xFFu << 23)) | (e << 23);
+    return asFloat(u);
+}
+inline float max3abs(V3 v) { return gmax(gmax(std::fabs(v.x), std::fabs(v.y)), std::fabs(v.z)); }
+
+inline DRay shadowRay(const float* cam, V3 rel, uint32_t lightType, V3 L) {
+    V3 origin{ cam[0] + rel.x, cam[1] + rel.y, cam[2] + rel.z };                          // comp:136
+    const float bias = gmax(epsilonFor(max3abs(origin), 13), epsilonFor(max3abs(rel), 13));   // comp:138-140
+    DRay r;
+    if (lightType == RTS_LIGHT_DIRECTIONAL) {
+        origin.x = origin.x + L.x * bias; origin.y = origin.y + L.y * bias; origin.z = origin.z + L.z * bias;   // comp:143
+        r.o = origin; r.tmax = 1e9f; r.d = L;                                             // comp:145-146
+    } else {
+        const V3 d0 = sub(L, origin);
+        const float inv = 1.0f / std::sqrt(dot(d0, d0));
+        origin.x = origin.x + (d0.x * inv) * bias; origin.y = origin.y + (d0.y * inv) * bias; origin.z = origin.z + (d0.z * inv) * bias;
+        r.o = origin; r.tmax = 1.0f; r.d = sub(L, origin);
+    }
+    return r;
+}
+
+inline uint32_t rayDistanceBits(const uint32_t* bvh, const DRay& r) {
+    const V3 inv{ 1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z };                             // comp:77
+    uint32_t best = 0x7F800000u, node = 0;
+    while (node != 0xFFFFFFFFu) {
+        const uint32_t* a = bvh + (size_t)node * 8;
+        const uint32_t* b = a + 4;
+        if (a[3] != 0xFFFFFFFFu) {
+            const uint32_t* t = bvh + (size_t)a[3] * 4;
+            const V3 e0{ asFloat(a[0]), asFloat(a[1]), asFloat(a[2]) }, e1{ asFloat(b[0]), asFloat(b[1]), asFloat(b[2]) };
+            const V3 v0{ asFloat(t[0]), asFloat(t[1]), asFloat(t[2]) };
+            const V3 s1 = crossG(r.d, e1);
+            const float invd = 1.0f / dot(s1, e0);
+            const V3 dd = sub(r.o, v0);
+            const float b1 = dot(dd, s1) * invd;
+            const V3 s2 = crossG(dd, e0);
+            const float b2 = dot(r.d, s2) * invd;
+            const float tt = dot(e1, s2) * invd;
+            if (!(b1 < 0.0f || b1 > 1.0f || b2 < 0.0f || b1 + b2 > 1.0f || tt < 0.0f || tt > r.tmax)) {
+                const uint32_t c = tt > 0.0f ? asBits(tt) : 0u;          // an accepted NaN or -0 counts as +0
+                if (c < best) best = c;
+            }
+        } else {
+            const float fx = (asFloat(b[0]) - r.o.x) * inv.x, fy = (asFloat(b[1]) - r.o.y) * inv.y, fz = (asFloat(b[2]) - r.o.z) * inv.z;
+            const float nx = (asFloat(a[0]) - r.o.x) * inv.x, ny = (asFloat(a[1]) - r.o.y) * inv.y, nz = (asFloat(a[2]) - r.o.z) * inv.z;
+            const float t1 = gmin(gmax(fx, nx), gmin(gmax(fy, ny), gmax(fz, nz)));
+            const float t0 = gmax(gmax(gmin(fx, nx), gmax(gmin(fy, ny), gmin(fz, nz))), 0.0f);
+            if (t1 >= t0) { ++node; continue; }
+        }
+        node = b[3];                                                     // hit or miss: on through the miss link
+    }
+    return best;
+}
+
+template <class F>
+void parallelFor(size_t n, size_t chunk, int threads, F&& body) {
+    int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    if (nt < 1) nt = 1;
+    if (nt > 64) nt = 64;
+    std::atomic<size_t> next{ 0 };
+    auto work = [&]() {
+        for (;;) {
+            const size_t b = next.fetch_add(chunk);
+            if (b >= n) break;
+            const size_t e = b + chunk < n ? b + chunk : n;
+            for (size_t i = b; i < e; ++i) body(i);
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt && (size_t)t * chunk < n; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+}
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_rays_distance(const rts_vec4u* packed, size_t count_vec4, const rts_ray* rays, size_t n, float* out_t, int threads) {
+    if (!packed || (n && (!rays || !out_t))) return RTS_ERR_INVALID_ARG;
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const float* f = (const float*)rays;                                 // rts_ray = {o.xyz, tmax, d.xyz, pad}: 8 floats
+    parallelFor(n, 256, threads, [&](size_t i) {
+        const float* q = f + i * 8;
+        const DRay r{ V3{ q[0], q[1], q[2] }, q[3], V3{ q[4], q[5], q[6] } };
+        out_t[i] = asFloat(rayDistanceBits(bvh, r));
+    });
+    return RTS_OK;
+}
+
+extern "C" int rtsh_shadow_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_light* light,
+                                    const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                    uint32_t row_end, float* distance, uint8_t* mask, int threads) {
+    if (!packed || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
+    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 1)) return RTS_ERR_INVALID_ARG;     // one sample in this version
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t lightType = light ? light->type : (uint32_t)RTS_LIGHT_DIRECTIONAL;
+    const V3 L = light ? V3{ light->xyz[0], light->xyz[1], light->xyz[2] } : V3{ k->lightDirection[0], k->lightDirection[1], k->lightDirection[2] };
+    const size_t first = (size_t)row_begin * W;
+    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t j) {
+        const size_t i = first + j;
+        if (active && !active[i]) { distance[i] = 0.0f; if (mask) mask[i] = 0; return; }
+        const float* q = positions + i * 4;
+        const uint32_t best = rayDistanceBits(bvh, shadowRay(k->cameraPosition, V3{ q[0], q[1], q[2] }, lightType, L));
+        distance[i] = asFloat(best);
+        if (mask) mask[i] = best == 0x7F800000u ? 1 : 0;                 // comp:148-150
+    });
+    return RTS_OK;
+}

@@ -23,6 +23,9 @@ def main():
     ap.add_argument("--spp", type=int, default=0)
     ap.add_argument("--save-bvh", default="")
     ap.add_argument("--cull", action="store_true", help="trace through the facing mark (an active map made from the G-buffer)")
+    ap.add_argument("--distance", default="", metavar="FILE.ppm",
+                    help="also write the occluder distance as a grey-scale image: +Inf (lit) white, the rest scaled to the frame's "
+                         "largest finite value (one sample per pixel: the light's first)")
     args = ap.parse_args()
     from raytracedshadows_amd import api, workloads
     scene, W, H, light, spp = workloads.CONFIGS[args.config]
@@ -44,6 +47,20 @@ def main():
             active = np.zeros((H, W), np.uint8)
             ctx.d2h(active, d_active)
             print(f"facing mark: {float((active == 0).mean()) * 100:.1f} % of the pixels send no ray")
+        if args.distance:
+            d_dist = ctx.malloc(W * H * 4)
+            one = wl.light if wl.light is None or wl.light.nsamples <= 1 else api.Light.make(wl.light.type, list(wl.light.xyz))
+            ctx.trace_shadow_distance_device(wl.constants, d_pos, W, H, d_dist, light=one, d_active=d_active)
+            ctx.synchronize()
+            dist = np.zeros((H, W), np.float32)
+            ctx.d2h(dist, d_dist)
+            finite = np.isfinite(dist)
+            top = float(dist[finite].max()) if finite.any() else 0.0
+            grey = np.where(finite, np.clip(dist / top if top > 0 else 0.0, 0.0, 1.0) * 254.0, 255.0).astype(np.uint8)
+            os.makedirs(os.path.dirname(os.path.abspath(args.distance)), exist_ok=True)
+            api.write_ppm(args.distance, np.repeat(grey[..., None], 3, axis=2))
+            print(f"wrote {args.distance}: occluder distance, {ctx.last_kernel_name()}, largest finite value {top:.6g}, "
+                  f"{float((~finite).mean()) * 100:.1f} % lit")
         d_rgb = ctx.malloc(W * H * 3)
         api.combine_device(ctx, wl.constants, wl.light, d_pos, d_nrm, d_mask, W, H, d_rgb)     # the frame stays on the device
         ctx.synchronize()
