@@ -4,6 +4,7 @@
 #include "bvh_builder.h"
 #include "bvh_refit.h"
 #include "rts_device.h"
+#include "rts_dispatch.h"
 #include "rts_refit.h"
 
 #include <algorithm>
@@ -16,6 +17,7 @@
 #include <unordered_map>
 #include <vector>
 
+using rts::Dispatch;
 using rts::TraceParams;
 
 struct rts_ctx {
@@ -65,7 +67,7 @@ struct rts_ctx {
     // split table (rts_ctx_plan_splits): valid for ONE dispatch geometry (the key), used by every trace that matches it
     struct Splits {
         bool valid = false;
-        uint32_t W = 0, H = 0, rowBegin = 0, rowEnd = 0, bandRows = 0, nStripes = 0, stripe = 0, blocksX = 0, blocksY = 0;
+        Dispatch geom{}; uint32_t blocksX = 0, blocksY = 0;     // the dispatch it was planned for and its tiles (madeFor)
         uint32_t* d_skipMap = nullptr;       // one bit per tile of the dispatch
         uint32_t* d_pieces = nullptr;        // 8 dwords per piece
         uint32_t* d_frontMap = nullptr;      // one dword per record, XCD-major (TraceParams::frontMap)
@@ -105,7 +107,7 @@ struct rts_ctx {
     // runs in -- one dispatch geometry per stream; at most 8 streams, the least recently used evicted
     struct Follow {
         void* stream = nullptr;
-        uint32_t W = 0, H = 0, rowBegin = 0, rowEnd = 0, bandRows = 0, nStripes = 0, stripe = 0, blocksX = 0, blocksY = 0;
+        Dispatch geom{}; uint32_t blocksX = 0, blocksY = 0;     // the dispatch the lives belong to and its tiles (madeFor)
         void* d_mem = nullptr;               // one allocation: lives (2 u32 per tile), front map, all-ones skip map, planner scratch
         uint32_t* d_lives = nullptr; uint32_t* d_frontMap = nullptr; uint32_t* d_skipMap = nullptr; void* d_scratch = nullptr;
         uint32_t frontStride = 0;
@@ -245,6 +247,22 @@ int deriveWideCopy(rts_ctx* c) {
 void dropRefit(rts_ctx* c) {
     c->refit.valid = false;
     c->refit.haveBaseline = false;
+}
+
+// "The same dispatch", for a split table and for a stream's follow state alike: the geometry it was made for, cut into the same tiles.
+template <class Kept> bool madeFor(const Kept& kept, const Dispatch& g, const TraceParams& p) {
+    return kept.geom == g && kept.blocksX == p.blocksX && kept.blocksY == p.blocksY;
+}
+
+// A new stream is about to be installed (rts_ctx_set_bvh, the GPU builders' install): the old one is freed, and what was derived from
+// it goes -- a split table holds its node indices, a rolling order and a planned tile order the lives of the tiles on the old scene.
+int forgetInstalled(rts_ctx* c) {
+    if (c->d_bvh) { void* old = c->d_bvh; c->d_bvh = nullptr; c->bvhVec4 = 0; c->P = 0; RTS_HIP(hipFree(old)); }
+    dropRefit(c);
+    clearSplits(c);
+    dropFollow(c);
+    if (c->tileOrderPlanned) (void)rts_ctx_set_tile_order(c, nullptr, 0);
+    return RTS_OK;
 }
 
 // The refit schedule of the installed stream, from its tag and link words (read back once): the topology check of the host
@@ -422,16 +440,13 @@ int rts_ctx_set_bvh(rts_ctx* c, const rts_vec4u* packed, size_t count) {
     if (count * 16 >= 0xFFFFFF00ull) return RTS_ERR_BAD_BVH;           // 32-bit byte offsets on the device (top 256 B = "nothing")
     RTS_HIP(hipSetDevice(c->device));
     // the context only changes once the new copy is complete; a failure leaves it without a BVH, never with a torn one
-    if (c->d_bvh) { void* old = c->d_bvh; c->d_bvh = nullptr; c->bvhVec4 = 0; c->P = 0; RTS_HIP(hipFree(old)); }
+    s = forgetInstalled(c);
+    if (s != RTS_OK) return s;
     void* d = nullptr;
     RTS_HIP(hipMalloc(&d, count * 16 + 64));          // + slack: the prefetching packet loop reads one node ahead
     hipError_t e = hipMemcpy(d, packed, count * 16, hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(d); return hipStatus(e); }
     c->d_bvh = d; c->bvhVec4 = count; c->P = P;
-    dropRefit(c);
-    clearSplits(c);                      // (a split table holds node indices of the stream it was planned on)
-    dropFollow(c);                       // (... a rolling order the lives of the tiles on the old scene)
-    if (c->tileOrderPlanned) (void)rts_ctx_set_tile_order(c, nullptr, 0);   // (... a planned tile order the lives of its tiles)
     return finishInstall(c, true);       // finite / ordered / enclosed are decided on the device; private wide copy
 }
 
@@ -548,17 +563,10 @@ static int planRefused(const char* why) {
     return RTS_ERR_INVALID_ARG;
 }
 
-// Virtual rows of one interleaved stripe's dispatch: band_rows times the number of bands stripe, stripe + n_stripes, ... it
-// owns (the last one may be cut by H: guarded in-kernel).  0 when the stripe owns no band (stripe >= bands): nothing to launch.
-static uint32_t stripeRows(uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe) {
-    const uint32_t bands = (uint32_t)(((uint64_t)H + band_rows - 1) / band_rows);
-    return stripe < bands ? ((bands - stripe - 1) / n_stripes + 1) * band_rows : 0u;
-}
-
-// Test hook (tests/test_host_logic.py): stripeRows, host only.
+// Test hook (tests/test_host_logic.py): rts::stripeRows (rts_dispatch.h), host only.
 extern "C" int rtsh_stripe_rows(uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint32_t* rows) {
     if (!rows || band_rows == 0 || n_stripes == 0 || stripe >= n_stripes) return RTS_ERR_INVALID_ARG;
-    *rows = stripeRows(H, band_rows, n_stripes, stripe);
+    *rows = rts::stripeRows(H, band_rows, n_stripes, stripe);
     return RTS_OK;
 }
 
@@ -602,11 +610,10 @@ struct FollowLayout {
 // follow mode: the state of `stream` for this dispatch geometry.  A stream seen with another geometry starts over; a ninth stream
 // evicts the least recently used.  Created and reset outside graph capture only (nothing is allocated in a captured trace):
 // NULL = run the everyday launch.
-static rts_ctx::Follow* followFor(rts_ctx* c, void* stream, const TraceParams& p, uint32_t bandRows, uint32_t nStripes, uint32_t stripe) {
+static rts_ctx::Follow* followFor(rts_ctx* c, void* stream, const Dispatch& g, const TraceParams& p) {
     rts_ctx::Follow* f = nullptr;
     for (auto& e : c->follow) if (e.stream == stream) { f = &e; break; }
-    if (f && f->d_mem && f->W == p.W && f->H == p.H && f->rowBegin == p.rowBegin && f->rowEnd == p.rowEnd && f->bandRows == bandRows &&
-        f->nStripes == nStripes && f->stripe == stripe && f->blocksX == p.blocksX && f->blocksY == p.blocksY) {
+    if (f && f->d_mem && madeFor(*f, g, p)) {
         f->lastUse = ++c->followClock;
         return f;
     }
@@ -636,8 +643,7 @@ static rts_ctx::Follow* followFor(rts_ctx* c, void* stream, const TraceParams& p
         return nullptr;
     }
     f->stream = stream;
-    f->W = p.W; f->H = p.H; f->rowBegin = p.rowBegin; f->rowEnd = p.rowEnd; f->bandRows = bandRows; f->nStripes = nStripes; f->stripe = stripe;
-    f->blocksX = p.blocksX; f->blocksY = p.blocksY;
+    f->geom = g; f->blocksX = p.blocksX; f->blocksY = p.blocksY;
     f->d_mem = d;
     f->d_lives = (uint32_t*)d;
     f->d_frontMap = (uint32_t*)((char*)d + lay.mapAt());
@@ -665,11 +671,55 @@ static void setLight(TraceParams& p, const rts_constants* k, const rts_light* li
     }
 }
 
+// The launch shape of a dispatch in blocks of bw x bh pixels: its tile counts (Dispatch::grid), then what the options and the tile order
+// decide -- a 2-D grid unless the blocks are swizzled, walked in a tile order, or more than 65535 rows of them; "row_order" on the 2-D
+// grid of an unstriped dispatch.  orderApplies: an installed order of as many tiles is used (never by an active or a distance trace).
+static void setGrid(const rts_ctx* c, TraceParams& p, const Dispatch& g, uint32_t bw, uint32_t bh, bool orderApplies) {
+    const rts::Grid gr = g.grid(bw, bh, c->swizzle != 0);
+    p.blocksX = gr.blocksX; p.blocksY = gr.blocksY; p.nBlocks = gr.nBlocks; p.gridBlocks = gr.gridBlocks;
+    p.swizzle = c->swizzle ? 1u : 0u;
+    if (orderApplies && c->d_tileOrder && c->useTileOrder && c->tileOrderCount == p.nBlocks && !p.swizzle) p.tileOrder = c->d_tileOrder;
+    p.grid2d = (!p.swizzle && !p.tileOrder && p.blocksY <= 65535u) ? 1u : 0u;
+    p.rowOrder = (p.grid2d && g.nStripes <= 1) ? (uint32_t)c->rowOrder : 0u;
+}
+
+// The active and the distance traces: one block per workgroup in natural order, 16 x 16 pixels in the lane-per-ray family and 8 x 8 in
+// the packet families; a band is a whole number of block rows.
+static int setBlockGrid(const rts_ctx* c, TraceParams& p, const Dispatch& g, int variant) {
+    const uint32_t b = variant == rts::V_SHARE ? 16u : 8u;       // pixels per side of a workgroup's block
+    if (g.nStripes > 1 && g.bandRows % b != 0) return RTS_ERR_INVALID_ARG;
+    setGrid(c, p, g, b, b, false);
+    return RTS_OK;
+}
+
+// The prologue of a frame trace, mask or distance: the argument checks both share -- the caller's own (ownArgsOk) in their place
+// among them --, the context's parameters, the geometry.  Return: *status is the call's result.  Nothing: an empty row range or a
+// stripe without a band, no launch; *status is RTS_OK.  Go: p holds the context, the buffers and the geometry; *rows > 0.
+enum class Begin { Return, Nothing, Go };
+static Begin beginFrame(rts_ctx* c, const rts_constants* k, const float* d_positions, uint8_t* d_mask, bool ownArgsOk, const Dispatch& g,
+                        TraceParams& p, uint32_t* rows, int* status) {
+    *status = RTS_ERR_INVALID_ARG;
+    if (!c || !k || !d_positions || !ownArgsOk || g.W == 0 || g.H == 0 || g.rowBegin > g.rowEnd || g.rowEnd > g.H) return Begin::Return;
+    if ((uint64_t)g.W * g.H > (1ull << 31)) return Begin::Return;      // tile counts are 32-bit on the device
+    *status = fillParams(c, p);
+    if (*status != RTS_OK) return Begin::Return;
+    if (g.rowBegin == g.rowEnd) return Begin::Nothing;
+    *status = hipStatus(hipSetDevice(c->device));
+    if (*status != RTS_OK) return Begin::Return;
+    p.positions = (const float4*)d_positions;
+    p.mask = d_mask;
+    p.W = g.W; p.H = g.H; p.rowBegin = g.rowBegin; p.rowEnd = g.rowEnd;
+    p.bandRows = g.bandRows; p.nStripes = g.nStripes; p.stripe = g.stripe;
+    p.bandShift = g.bandShift();
+    *rows = g.rows();                                                  // (stripes: virtual rows = whole owned bands)
+    return *rows ? Begin::Go : Begin::Nothing;                         // (a stripe without a band: no launch)
+}
+
 // A trace with an active map (include/rts.h): the kernel FAMILY the options ask for, one tile per workgroup, in natural order -- an
 // installed split table, a tile order and follow mode are neither used nor touched, and no statistics are recorded.
-static int traceActive(rts_ctx* c, TraceParams& p, const rts_constants* k, const rts_light* light, const uint8_t* d_active, uint32_t rows,
-                       uint32_t band_rows, uint32_t n_stripes, void* stream) {
-    const uint64_t pixels = (uint64_t)p.W * rows;
+static int traceActive(rts_ctx* c, TraceParams& p, const Dispatch& g, uint32_t rows, const rts_constants* k, const rts_light* light,
+                       const uint8_t* d_active, void* stream) {
+    const uint64_t pixels = (uint64_t)g.W * rows;
     int variant = c->variant;
     if (variant == rts::V_AUTO)                      // (the plain trace's rule, traceMaskImpl)
         variant = pixels < (1u << 18) ? rts::V_SHARE
@@ -677,15 +727,8 @@ static int traceActive(rts_ctx* c, TraceParams& p, const rts_constants* k, const
     if (variant == rts::V_WIDE || variant == rts::V_WIDE_C) variant = p.wide ? rts::V_WIDE : rts::V_PACKET;
     else if (variant >= rts::V_PACKET && variant <= rts::V_PACKET_PF) variant = rts::V_PACKET;
     else variant = rts::V_SHARE;
-    const uint32_t b = variant == rts::V_SHARE ? 16u : 8u;       // pixels per side of a workgroup's block
-    if (n_stripes > 1 && band_rows % b != 0) return RTS_ERR_INVALID_ARG;
-    p.blocksX = (p.W + b - 1) / b;
-    p.blocksY = (rows + b - 1) / b;
-    p.nBlocks = p.blocksX * p.blocksY;
-    p.swizzle = c->swizzle ? 1u : 0u;
-    p.gridBlocks = p.swizzle ? ((p.nBlocks + 7) / 8) * 8 : p.nBlocks;
-    p.grid2d = (!p.swizzle && p.blocksY <= 65535u) ? 1u : 0u;
-    p.rowOrder = (p.grid2d && n_stripes <= 1) ? (uint32_t)c->rowOrder : 0u;
+    const int s = setBlockGrid(c, p, g, variant);
+    if (s != RTS_OK) return s;
     p.activeMap = d_active;
     setLight(p, k, light);
     ++c->launches;
@@ -696,38 +739,19 @@ static int traceActive(rts_ctx* c, TraceParams& p, const rts_constants* k, const
     return hipStatus(e);
 }
 
-static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
-                         uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint32_t band_rows,
-                         uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, void* stream, const uint8_t* d_active = nullptr) {
-    if (!c || !k || !d_positions || !d_mask || W == 0 || H == 0 || row_begin > row_end || row_end > H)
-        return RTS_ERR_INVALID_ARG;
-    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 64)) return RTS_ERR_INVALID_ARG;
-    if (light && light->table && (light->table > 64 || light->table < light->nsamples || light->nsamples < 2)) return RTS_ERR_INVALID_ARG;
-    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;      // tile counts are 32-bit on the device
-    TraceParams p;
-    int s = fillParams(c, p);
-    if (s != RTS_OK) return s;
-    if (row_begin == row_end) return RTS_OK;
-    RTS_HIP(hipSetDevice(c->device));
-    p.positions = (const float4*)d_positions;
-    p.mask = d_mask;
-    p.W = W; p.H = H; p.rowBegin = row_begin; p.rowEnd = row_end;
-    p.bandRows = band_rows; p.nStripes = n_stripes; p.stripe = stripe;
-    p.bandShift = 0xFFFFFFFFu;
-    if (n_stripes > 1 && band_rows % 8 == 0) {
-        const uint32_t tiles = band_rows / 8;
-        if ((tiles & (tiles - 1)) == 0) { uint32_t sh = 0; while ((1u << sh) < tiles) ++sh; p.bandShift = sh; }
-    }
+static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const Dispatch& g,
+                         uint8_t* d_mask, void* stream, const uint8_t* d_active = nullptr) {
+    const bool lightOk = !light || (light->type <= RTS_LIGHT_POINT && light->nsamples <= 64 &&
+                                    (!light->table || (light->table <= 64 && light->table >= light->nsamples && light->nsamples >= 2)));
+    TraceParams p; uint32_t rows = 0; int s;
+    if (beginFrame(c, k, d_positions, d_mask, d_mask && lightOk, g, p, &rows, &s) != Begin::Go) return s;
+    if (d_active) return traceActive(c, p, g, rows, k, light, d_active, stream);
     // V_AUTO: a packet's steps are a dependent chain, so it needs several waves per SIMD to overlap them;
     // a launch with fewer than ~4 waves per SIMD is faster lane-per-ray (with in-wave work sharing: measured
     // 5-20 % ahead of the plain loop on every small frame).  (Bigger packets, V_PACKET2/4, were
     // measured slower or equal on every BASELINE config and are kept as selectable variants only.)
     int variant = c->variant;
-    uint32_t rows = row_end - row_begin;
-    if (n_stripes > 1) rows = stripeRows(H, band_rows, n_stripes, stripe);     // virtual rows = whole owned bands
-    if (rows == 0) return RTS_OK;                                                 // (a stripe without a band: no launch)
-    if (d_active) return traceActive(c, p, k, light, d_active, rows, band_rows, n_stripes, stream);
-    const uint64_t pixels = (uint64_t)W * rows;
+    const uint64_t pixels = (uint64_t)g.W * rows;
     // Big one-sample dispatches of a stream with a private copy take the WIDE packet (a static rule from what rts_ctx_autotune
     // picks on the 4K frames: city 0.153 against 0.164 ms, courtyard 0.562 against 0.630; at 1080p and for soft shadows the
     // stackless packet is ahead or level -- profiles/r04/tuning_robustness.log): a caller that never tunes gets the kernel the
@@ -738,31 +762,22 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
     if ((variant == rts::V_WIDE || variant == rts::V_WIDE_C) && !p.wide) variant = rts::V_PACKET;     // no private copy for this stream (see finishInstall)
     uint32_t bw, bh;
     rts::tileShape(variant, c->blockWaves, &bw, &bh);
-    if (n_stripes > 1 && band_rows % bh != 0) return RTS_ERR_INVALID_ARG;   // a band is a whole number of workgroup rows (8, 16 or 32 pixel rows)
-    p.blocksX = (W + bw - 1) / bw;
-    p.blocksY = (rows + bh - 1) / bh;
-    p.nBlocks = p.blocksX * p.blocksY;
-    p.swizzle = c->swizzle ? 1u : 0u;
-    p.gridBlocks = p.swizzle ? ((p.nBlocks + 7) / 8) * 8 : p.nBlocks;
+    if (g.nStripes > 1 && g.bandRows % bh != 0) return RTS_ERR_INVALID_ARG;   // a band is a whole number of workgroup rows (8, 16 or 32 pixel rows)
+    const bool soft = light && light->nsamples > 1;
+    setGrid(c, p, g, bw, bh, !c->tileOrderSoftOnly || soft);
     // (soft shadows in the one-tile packet forms run 4 waves per workgroup: "soft_split")
-    const bool split = light && light->nsamples > 1 && c->softSplit && c->blockWaves == 1 &&
-                       (variant == rts::V_PACKET || variant == rts::V_WIDE);
+    const bool split = soft && c->softSplit && c->blockWaves == 1 && (variant == rts::V_PACKET || variant == rts::V_WIDE);
     const size_t statWaves = split ? 4 : (size_t)c->blockWaves;
     if (c->d_waveStats && (size_t)p.gridBlocks * statWaves * 32 <= c->waveStatsBytes) {
         p.waveStats = c->d_waveStats;
         p.waveRealtime = c->d_waveStats + c->waveStatsBytes / 8;
     }
-    if (c->d_tileOrder && c->useTileOrder && c->tileOrderCount == p.nBlocks && !p.swizzle &&
-        (!c->tileOrderSoftOnly || (light && light->nsamples > 1)))
-        p.tileOrder = c->d_tileOrder;
-    p.grid2d = (!p.swizzle && !p.tileOrder && p.blocksY <= 65535u) ? 1u : 0u;
     if (c->d_clockProbe && p.grid2d && p.blocksY <= c->clockProbeRows) p.clockProbe = c->d_clockProbe;
-    p.rowOrder = (p.grid2d && n_stripes <= 1) ? (uint32_t)c->rowOrder : 0u;
     setLight(p, k, light);
     c->lastBlocksX = p.blocksX; c->lastBlocksY = p.blocksY; c->lastVariant = variant; c->lastGrid2d = p.grid2d != 0;
     if (c->planning) {                       // pieces only: the planning walk of the selected tiles, with visit logs
         if (!(variant == rts::V_PACKET || variant == rts::V_WIDE) || c->blockWaves != 1 || p.nsamples != 1 || !p.grid2d || !p.wide ||
-            (n_stripes > 1 && p.bandShift == 0xFFFFFFFFu))
+            (g.nStripes > 1 && p.bandShift == 0xFFFFFFFFu))
             return planRefused("the planning walk needs a one-tile packet kernel, one sample, a 2-D grid, the private copy");
         p.waveStats = nullptr; p.waveRealtime = nullptr; p.clockProbe = nullptr; p.rowOrder = 0;
         p.skipMap = c->planning->d_pieces;   // (never read: no tile rows in this launch)
@@ -776,10 +791,8 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
     const rts_ctx::Splits& sp = c->splits;
     if (sp.valid && c->useSplits && sp.nPieces && (variant == rts::V_PACKET || variant == rts::V_WIDE) && c->blockWaves == 1 &&
         p.nsamples == 1 && p.grid2d && !p.waveStats && !c->wideLane && p.wide &&
-        (n_stripes <= 1 || (p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0)) &&
-        sp.W == W && sp.H == H && sp.rowBegin == row_begin && sp.rowEnd == row_end && sp.bandRows == band_rows &&
-        sp.nStripes == n_stripes && sp.stripe == stripe && sp.blocksX == p.blocksX && sp.blocksY == p.blocksY &&
-        p.blocksY + sp.pieceRows <= 65535u) {
+        (g.nStripes <= 1 || (p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0)) &&
+        madeFor(sp, g, p) && p.blocksY + sp.pieceRows <= 65535u) {
         if (uint64_t* st = splitState(c, stream)) {
             p.skipMap = sp.d_skipMap; p.pieces = sp.d_pieces; p.nPieces = sp.nPieces; p.pieceRows = sp.pieceRows;
             p.frontMap = sp.d_frontMap; p.frontStride = sp.frontStride;
@@ -795,8 +808,8 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
     // option "row_order" itself must be 0, as include/rts.h says -- p.rowOrder is 0 for every stripe, whatever the option.)
     rts_ctx::Follow* fol = nullptr;
     if (c->followOn && !p.pieces && (variant == rts::V_PACKET || variant == rts::V_WIDE) && c->blockWaves == 1 && p.nsamples == 1 &&
-        p.grid2d && !p.waveStats && !c->wideLane && p.wide && (n_stripes <= 1 || (p.bandShift != 0xFFFFFFFFu && c->rowOrder == 0)))
-        fol = followFor(c, stream, p, band_rows, n_stripes, stripe);
+        p.grid2d && !p.waveStats && !c->wideLane && p.wide && (g.nStripes <= 1 || (p.bandShift != 0xFFFFFFFFu && c->rowOrder == 0)))
+        fol = followFor(c, stream, g, p);
     if (fol) {
         p.followLives = fol->d_lives;
         if (fol->planned) {
@@ -819,88 +832,33 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
     return hipStatus(e);
 }
 
-int rts_trace_shadow_mask_device(rts_ctx* c, const rts_constants* k, const rts_light* light,
-                                 const float* d_positions, uint32_t W, uint32_t H,
+int rts_trace_shadow_mask_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, uint32_t W, uint32_t H,
                                  uint32_t row_begin, uint32_t row_end, uint8_t* d_mask, void* stream) {
-    return traceMaskImpl(c, k, light, d_positions, W, H, row_begin, row_end, 0, 1, 0, d_mask, stream);
+    return traceMaskImpl(c, k, light, d_positions, Dispatch::ofRows(W, H, row_begin, row_end), d_mask, stream);
 }
 
-int rts_trace_shadow_mask_stripes_device(rts_ctx* c, const rts_constants* k, const rts_light* light,
-                                         const float* d_positions, uint32_t W, uint32_t H, uint32_t band_rows,
-                                         uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, void* stream) {
-    if (band_rows == 0 || band_rows % 8 != 0 || n_stripes == 0 || stripe >= n_stripes) return RTS_ERR_INVALID_ARG;
-    if (n_stripes == 1) return traceMaskImpl(c, k, light, d_positions, W, H, 0, H, 0, 1, 0, d_mask, stream);
-    // rows this stripe owns: whole bands stripe, stripe+n, ... (the last one may be cut by H)
-    const uint32_t bands = (H + band_rows - 1) / band_rows;
-    uint32_t owned = 0;
-    for (uint32_t b = stripe; b < bands; b += n_stripes) owned += (b + 1) * band_rows <= H ? band_rows : H - b * band_rows;
-    if (owned == 0) return RTS_OK;
-    // dispatch `owned` virtual rows; the kernel maps them onto the frame (ownedRow) and guards with row < H
-    return traceMaskImpl(c, k, light, d_positions, W, H, 0, H, band_rows, n_stripes, stripe, d_mask, stream);
-}
-
-int rts_trace_shadow_mask(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions,
-                          uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
-    if (!c || !k || !positions || !mask || W == 0 || H == 0 || row_begin > row_end || row_end > H)
-        return RTS_ERR_INVALID_ARG;
-    if (!c->d_bvh) return RTS_ERR_NO_BVH;
-    if (row_begin == row_end) return RTS_OK;
-    RTS_HIP(hipSetDevice(c->device));
-    // Only the stripe travels: the device buffers hold rows [row_begin,row_end) as a frame of their own.
-    const uint32_t rows = row_end - row_begin;
-    const size_t inB = (size_t)rows * W * 16, outB = (size_t)rows * W;
-    int s = ensure(&c->d_in, &c->inBytes, inB);
-    if (s == RTS_OK) s = ensure(&c->d_out, &c->outBytes, outB);
-    if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(c->d_in, positions + (size_t)row_begin * W * 4, inB, hipMemcpyHostToDevice));
-    c->pixelBase = row_begin * W;          // per-pixel jitter hashes the pixel's index in the caller's frame
-    s = rts_trace_shadow_mask_device(c, k, light, (const float*)c->d_in, W, rows, 0, rows, (uint8_t*)c->d_out, nullptr);
-    c->pixelBase = 0;
-    if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(mask + (size_t)row_begin * W, c->d_out, outB, hipMemcpyDeviceToHost));
-    return RTS_OK;
+int rts_trace_shadow_mask_stripes_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, uint32_t W,
+                                         uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    const Dispatch g = Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe);
+    if (n_stripes > 1 && g.rows() == 0) return RTS_OK;     // a stripe that owns no band launches nothing, whatever the other arguments are
+    // dispatch its virtual rows; the kernel maps them onto the frame (ownedRow) and guards with row < H
+    return traceMaskImpl(c, k, light, d_positions, g, d_mask, stream);
 }
 
 int rts_trace_shadow_mask_active_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
                                         const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
                                         uint8_t* d_mask, void* stream) {
-    return traceMaskImpl(c, k, light, d_positions, W, H, row_begin, row_end, 0, 1, 0, d_mask, stream, d_active);
+    return traceMaskImpl(c, k, light, d_positions, Dispatch::ofRows(W, H, row_begin, row_end), d_mask, stream, d_active);
 }
 
 int rts_trace_shadow_mask_active_stripes_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
                                                 const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes,
                                                 uint32_t stripe, uint8_t* d_mask, void* stream) {
     if (!d_active) return rts_trace_shadow_mask_stripes_device(c, k, light, d_positions, W, H, band_rows, n_stripes, stripe, d_mask, stream);
-    if (band_rows == 0 || band_rows % 8 != 0 || n_stripes == 0 || stripe >= n_stripes) return RTS_ERR_INVALID_ARG;
-    if (n_stripes == 1) return traceMaskImpl(c, k, light, d_positions, W, H, 0, H, 0, 1, 0, d_mask, stream, d_active);
-    // (a stripe that owns no band launches nothing: traceMaskImpl, after the argument checks)
-    return traceMaskImpl(c, k, light, d_positions, W, H, 0, H, band_rows, n_stripes, stripe, d_mask, stream, d_active);
-}
-
-int rts_trace_shadow_mask_active(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
-                                 uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
-    if (!active) return rts_trace_shadow_mask(c, k, light, positions, W, H, row_begin, row_end, mask);
-    if (!c || !k || !positions || !mask || W == 0 || H == 0 || row_begin > row_end || row_end > H)
-        return RTS_ERR_INVALID_ARG;
-    if (!c->d_bvh) return RTS_ERR_NO_BVH;
-    if (row_begin == row_end) return RTS_OK;
-    RTS_HIP(hipSetDevice(c->device));
-    // Only the stripe travels, as in rts_trace_shadow_mask: positions, map and mask of rows [row_begin,row_end) as a frame of their own.
-    const uint32_t rows = row_end - row_begin;
-    const size_t inB = (size_t)rows * W * 16, outB = (size_t)rows * W;
-    int s = ensure(&c->d_in, &c->inBytes, inB);
-    if (s == RTS_OK) s = ensure(&c->d_out, &c->outBytes, outB);
-    if (s == RTS_OK) s = ensure(&c->d_act, &c->actBytes, outB);
-    if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(c->d_in, positions + (size_t)row_begin * W * 4, inB, hipMemcpyHostToDevice));
-    RTS_HIP(hipMemcpy(c->d_act, active + (size_t)row_begin * W, outB, hipMemcpyHostToDevice));
-    c->pixelBase = row_begin * W;          // per-pixel jitter hashes the pixel's index in the caller's frame
-    s = rts_trace_shadow_mask_active_device(c, k, light, (const float*)c->d_in, (const uint8_t*)c->d_act, W, rows, 0, rows,
-                                            (uint8_t*)c->d_out, nullptr);
-    c->pixelBase = 0;
-    if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(mask + (size_t)row_begin * W, c->d_out, outB, hipMemcpyDeviceToHost));
-    return RTS_OK;
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    // (a stripe that owns no band launches nothing: beginFrame, after the argument checks)
+    return traceMaskImpl(c, k, light, d_positions, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_mask, stream, d_active);
 }
 
 int rts_trace_rays_device(rts_ctx* c, const rts_ray* d_rays, size_t n, uint8_t* d_out, void* stream) {
@@ -919,63 +877,23 @@ int rts_trace_rays_device(rts_ctx* c, const rts_ray* d_rays, size_t n, uint8_t* 
     return hipStatus(rts::launchTraceRays(variant, p, (hipStream_t)stream));
 }
 
-int rts_trace_rays(rts_ctx* c, const rts_ray* rays, size_t n, uint8_t* out) {
-    if (!c || (n && (!rays || !out))) return RTS_ERR_INVALID_ARG;
-    if (!c->d_bvh) return RTS_ERR_NO_BVH;
-    if (n == 0) return RTS_OK;
-    RTS_HIP(hipSetDevice(c->device));
-    int s = ensure(&c->d_in, &c->inBytes, n * sizeof(rts_ray));
-    if (s == RTS_OK) s = ensure(&c->d_out, &c->outBytes, n);
-    if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(c->d_in, rays, n * sizeof(rts_ray), hipMemcpyHostToDevice));
-    s = rts_trace_rays_device(c, (const rts_ray*)c->d_in, n, (uint8_t*)c->d_out, nullptr);
-    if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(out, c->d_out, n, hipMemcpyDeviceToHost));
-    return RTS_OK;
-}
-
 // ---- occluder distance (include/rts.h): the nearest accepted triangle's t beside the shadow byte ---------------------------------
 // One launch of a distance kernel (rts_distance.inc), one tile (or block) per workgroup in natural order.  The kernel FAMILY follows
 // "kernel" as for an active trace, except that 8 and 9 run the stackless packet too (the wide walk has no distance form yet).  No
 // table, order, follow state or statistic is used or touched.
 static int traceDistanceImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const uint8_t* d_active,
-                             uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint32_t band_rows, uint32_t n_stripes,
-                             uint32_t stripe, float* d_distance, uint8_t* d_mask, void* stream) {
-    if (!c || !k || !d_positions || !d_distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
-    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 1)) return RTS_ERR_INVALID_ARG;     // one sample in this version
-    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;      // tile counts are 32-bit on the device
-    TraceParams p;
-    int s = fillParams(c, p);
-    if (s != RTS_OK) return s;
-    if (row_begin == row_end) return RTS_OK;
-    RTS_HIP(hipSetDevice(c->device));
-    p.positions = (const float4*)d_positions;
-    p.mask = d_mask;
+                             const Dispatch& g, float* d_distance, uint8_t* d_mask, void* stream) {
+    const bool lightOk = !light || (light->type <= RTS_LIGHT_POINT && light->nsamples <= 1);     // one sample in this version
+    TraceParams p; uint32_t rows = 0; int s;
+    if (beginFrame(c, k, d_positions, d_mask, d_distance && lightOk, g, p, &rows, &s) != Begin::Go) return s;
     p.distance = d_distance;
     p.activeMap = d_active;
-    p.W = W; p.H = H; p.rowBegin = row_begin; p.rowEnd = row_end;
-    p.bandRows = band_rows; p.nStripes = n_stripes; p.stripe = stripe;
-    p.bandShift = 0xFFFFFFFFu;
-    if (n_stripes > 1 && band_rows % 8 == 0) {
-        const uint32_t tiles = band_rows / 8;
-        if ((tiles & (tiles - 1)) == 0) { uint32_t sh = 0; while ((1u << sh) < tiles) ++sh; p.bandShift = sh; }
-    }
-    uint32_t rows = row_end - row_begin;
-    if (n_stripes > 1) rows = stripeRows(H, band_rows, n_stripes, stripe);     // virtual rows = whole owned bands
-    if (rows == 0) return RTS_OK;                                                 // (a stripe without a band: no launch)
-    const uint64_t pixels = (uint64_t)W * rows;
+    const uint64_t pixels = (uint64_t)g.W * rows;
     int variant = c->variant;
     if (variant == rts::V_AUTO) variant = pixels < (1u << 18) ? rts::V_SHARE : rts::V_PACKET;
     else variant = (variant >= rts::V_PACKET && variant != rts::V_SHARE) ? rts::V_PACKET : rts::V_SHARE;
-    const uint32_t b = variant == rts::V_SHARE ? 16u : 8u;       // pixels per side of a workgroup's block
-    if (n_stripes > 1 && band_rows % b != 0) return RTS_ERR_INVALID_ARG;
-    p.blocksX = (W + b - 1) / b;
-    p.blocksY = (rows + b - 1) / b;
-    p.nBlocks = p.blocksX * p.blocksY;
-    p.swizzle = c->swizzle ? 1u : 0u;
-    p.gridBlocks = p.swizzle ? ((p.nBlocks + 7) / 8) * 8 : p.nBlocks;
-    p.grid2d = (!p.swizzle && p.blocksY <= 65535u) ? 1u : 0u;
-    p.rowOrder = (p.grid2d && n_stripes <= 1) ? (uint32_t)c->rowOrder : 0u;
+    s = setBlockGrid(c, p, g, variant);
+    if (s != RTS_OK) return s;
     setLight(p, k, light);
     ++c->launches;
     ++c->distanceTraces;
@@ -988,40 +906,14 @@ static int traceDistanceImpl(rts_ctx* c, const rts_constants* k, const rts_light
 int rts_trace_shadow_distance_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
                                      const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
                                      float* d_distance, uint8_t* d_mask, void* stream) {
-    return traceDistanceImpl(c, k, light, d_positions, d_active, W, H, row_begin, row_end, 0, 1, 0, d_distance, d_mask, stream);
+    return traceDistanceImpl(c, k, light, d_positions, d_active, Dispatch::ofRows(W, H, row_begin, row_end), d_distance, d_mask, stream);
 }
 
 int rts_trace_shadow_distance_stripes_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
                                              const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes,
                                              uint32_t stripe, float* d_distance, uint8_t* d_mask, void* stream) {
-    if (band_rows == 0 || band_rows % 8 != 0 || n_stripes == 0 || stripe >= n_stripes) return RTS_ERR_INVALID_ARG;
-    if (n_stripes == 1) return traceDistanceImpl(c, k, light, d_positions, d_active, W, H, 0, H, 0, 1, 0, d_distance, d_mask, stream);
-    return traceDistanceImpl(c, k, light, d_positions, d_active, W, H, 0, H, band_rows, n_stripes, stripe, d_distance, d_mask, stream);
-}
-
-int rts_trace_shadow_distance(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
-                              uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
-    if (!c || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
-    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 1)) return RTS_ERR_INVALID_ARG;
-    if (!c->d_bvh) return RTS_ERR_NO_BVH;
-    if (row_begin == row_end) return RTS_OK;
-    RTS_HIP(hipSetDevice(c->device));
-    // Only the rows travel, as in rts_trace_shadow_mask: positions, map, distances and mask of [row_begin,row_end) as a frame of their own.
-    const uint32_t rows = row_end - row_begin;
-    const size_t inB = (size_t)rows * W * 16, outB = (size_t)rows * W;
-    int s = ensure(&c->d_in, &c->inBytes, inB);
-    if (s == RTS_OK) s = ensure(&c->d_dist, &c->distBytes, outB * 4);
-    if (s == RTS_OK && mask) s = ensure(&c->d_out, &c->outBytes, outB);
-    if (s == RTS_OK && active) s = ensure(&c->d_act, &c->actBytes, outB);
-    if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(c->d_in, positions + (size_t)row_begin * W * 4, inB, hipMemcpyHostToDevice));
-    if (active) RTS_HIP(hipMemcpy(c->d_act, active + (size_t)row_begin * W, outB, hipMemcpyHostToDevice));
-    s = rts_trace_shadow_distance_device(c, k, light, (const float*)c->d_in, active ? (const uint8_t*)c->d_act : nullptr, W, rows, 0, rows,
-                                         (float*)c->d_dist, mask ? (uint8_t*)c->d_out : nullptr, nullptr);
-    if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(distance + (size_t)row_begin * W, c->d_dist, outB * 4, hipMemcpyDeviceToHost));
-    if (mask) RTS_HIP(hipMemcpy(mask + (size_t)row_begin * W, c->d_out, outB, hipMemcpyDeviceToHost));
-    return RTS_OK;
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceDistanceImpl(c, k, light, d_positions, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_distance, d_mask, stream);
 }
 
 int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, float* d_out_t, void* stream) {
@@ -1038,19 +930,80 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
     return hipStatus(rts::launchTraceRaysDistance(p, (hipStream_t)stream));
 }
 
-int rts_trace_rays_distance(rts_ctx* c, const rts_ray* rays, size_t n, float* out_t) {
-    if (!c || (n && (!rays || !out_t))) return RTS_ERR_INVALID_ARG;
+// ---- the host-pointer entries: the same traces through the context's staging buffers ----------------------------------------------
+// Frames (arguments checked by the caller): only rows [row_begin, row_end) travel -- their positions, map, mask and distances, as a
+// frame of their own.  distance != NULL: a distance trace (mask optional), else a mask trace.
+static int traceStagedRows(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
+                           uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
+    if (!c->d_bvh) return RTS_ERR_NO_BVH;
+    if (row_begin == row_end) return RTS_OK;
+    RTS_HIP(hipSetDevice(c->device));
+    const uint32_t rows = row_end - row_begin;
+    const size_t first = (size_t)row_begin * W, pixels = (size_t)rows * W;
+    int s = ensure(&c->d_in, &c->inBytes, pixels * 16);
+    if (s == RTS_OK && distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4);
+    if (s == RTS_OK && mask) s = ensure(&c->d_out, &c->outBytes, pixels);
+    if (s == RTS_OK && active) s = ensure(&c->d_act, &c->actBytes, pixels);
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(c->d_in, positions + first * 4, pixels * 16, hipMemcpyHostToDevice));
+    if (active) RTS_HIP(hipMemcpy(c->d_act, active + first, pixels, hipMemcpyHostToDevice));
+    const uint8_t* d_active = active ? (const uint8_t*)c->d_act : nullptr;
+    uint8_t* d_mask = mask ? (uint8_t*)c->d_out : nullptr;
+    // per-pixel jitter hashes the pixel's index in the caller's frame (sampleIndex, rts_kernels.hip: the one reader, and only of a
+    // light with a table -- several samples, so never in a distance trace)
+    c->pixelBase = row_begin * W;
+    s = distance ? rts_trace_shadow_distance_device(c, k, light, (const float*)c->d_in, d_active, W, rows, 0, rows, (float*)c->d_dist, d_mask, nullptr)
+                 : rts_trace_shadow_mask_active_device(c, k, light, (const float*)c->d_in, d_active, W, rows, 0, rows, d_mask, nullptr);
+    c->pixelBase = 0;
+    if (s != RTS_OK) return s;
+    if (distance) RTS_HIP(hipMemcpy(distance + first, c->d_dist, pixels * 4, hipMemcpyDeviceToHost));
+    if (mask) RTS_HIP(hipMemcpy(mask + first, c->d_out, pixels, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+int rts_trace_shadow_mask_active(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
+                                 uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
+    if (!c || !k || !positions || !mask || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
+    return traceStagedRows(c, k, light, positions, active, W, row_begin, row_end, nullptr, mask);
+}
+
+int rts_trace_shadow_mask(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions,
+                          uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
+    return rts_trace_shadow_mask_active(c, k, light, positions, nullptr, W, H, row_begin, row_end, mask);
+}
+
+int rts_trace_shadow_distance(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
+                              uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
+    if (!c || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
+    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 1)) return RTS_ERR_INVALID_ARG;
+    return traceStagedRows(c, k, light, positions, active, W, row_begin, row_end, distance, mask);
+}
+
+// Rays (the caller's arguments are checked): occlusion bytes to `out`, or distances to `out_t` where out is NULL.
+static int traceStagedRays(rts_ctx* c, const rts_ray* rays, size_t n, uint8_t* out, float* out_t) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
     if (n == 0) return RTS_OK;
     RTS_HIP(hipSetDevice(c->device));
+    const size_t outB = out ? n : n * 4;
     int s = ensure(&c->d_in, &c->inBytes, n * sizeof(rts_ray));
-    if (s == RTS_OK) s = ensure(&c->d_dist, &c->distBytes, n * 4);
+    if (s == RTS_OK) s = out ? ensure(&c->d_out, &c->outBytes, outB) : ensure(&c->d_dist, &c->distBytes, outB);
     if (s != RTS_OK) return s;
     RTS_HIP(hipMemcpy(c->d_in, rays, n * sizeof(rts_ray), hipMemcpyHostToDevice));
-    s = rts_trace_rays_distance_device(c, (const rts_ray*)c->d_in, n, (float*)c->d_dist, nullptr);
+    s = out ? rts_trace_rays_device(c, (const rts_ray*)c->d_in, n, (uint8_t*)c->d_out, nullptr)
+            : rts_trace_rays_distance_device(c, (const rts_ray*)c->d_in, n, (float*)c->d_dist, nullptr);
     if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(out_t, c->d_dist, n * 4, hipMemcpyDeviceToHost));
+    RTS_HIP(hipMemcpy(out ? (void*)out : (void*)out_t, out ? c->d_out : c->d_dist, outB, hipMemcpyDeviceToHost));
     return RTS_OK;
+}
+
+int rts_trace_rays(rts_ctx* c, const rts_ray* rays, size_t n, uint8_t* out) {
+    if (!c || (n && (!rays || !out))) return RTS_ERR_INVALID_ARG;
+    return traceStagedRays(c, rays, n, out, nullptr);
+}
+
+int rts_trace_rays_distance(rts_ctx* c, const rts_ray* rays, size_t n, float* out_t) {
+    if (!c || (n && (!rays || !out_t))) return RTS_ERR_INVALID_ARG;
+    return traceStagedRays(c, rays, n, nullptr, out_t);
 }
 
 int rts_device_malloc(rts_ctx* c, void** p, size_t bytes) {
@@ -1176,13 +1129,10 @@ void* rts_ctx_scratch(rts_ctx* c, size_t bytes) {
 int rts_ctx_adopt_device_bvh(rts_ctx* c, void* d_packed, size_t count, uint32_t P) {
     if (!c || !d_packed || count != (size_t)5 * P - 2 || count * 16 >= 0xFFFFFF00ull) return RTS_ERR_INVALID_ARG;
     RTS_HIP(hipSetDevice(c->device));
-    if (c->d_bvh) { void* old = c->d_bvh; c->d_bvh = nullptr; c->bvhVec4 = 0; c->P = 0; RTS_HIP(hipFree(old)); }
+    const int s = forgetInstalled(c);
+    if (s != RTS_OK) return s;
     c->d_bvh = d_packed;
     c->bvhVec4 = count; c->P = P;
-    dropRefit(c);
-    clearSplits(c);
-    dropFollow(c);
-    if (c->tileOrderPlanned) (void)rts_ctx_set_tile_order(c, nullptr, 0);
     // the same checks as for an uploaded stream, on the device: layout, finiteness (edges of finite vertices can
     // overflow), box order, enclosure.  A refused stream stays the caller's to free.
     return finishInstall(c, false);
@@ -1311,15 +1261,13 @@ int rts_ctx_read_clock_probe(rts_ctx* c, uint64_t* out, size_t rows) {
 
 // Wave statistics of ONE dispatch (what rts_ctx_read_wave_stats / _realtime return): two launches of the diagnostic
 // instantiation without a table, the second one read back.  Used by the planner and, once per tuning call, by the tuner.
-static int measureDispatch(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, uint32_t W, uint32_t H,
-                           uint32_t row_begin, uint32_t row_end, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask,
-                           std::vector<uint64_t>& stats, std::vector<uint64_t>& rt, uint32_t perTile = 1) {
+static int measureDispatch(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const Dispatch& g,
+                           uint8_t* d_mask, std::vector<uint64_t>& stats, std::vector<uint64_t>& rt, uint32_t perTile = 1) {
     int status = RTS_OK;
     uint64_t* keep = c->d_waveStats; const size_t keepBytes = c->waveStatsBytes;
     c->d_waveStats = nullptr; c->waveStatsBytes = 0;
-    uint32_t rows = row_end - row_begin;
-    if (n_stripes > 1) rows = stripeRows(H, band_rows, n_stripes, stripe);
-    const size_t tiles = (size_t)((W + 7) / 8) * ((rows + 7) / 8);
+    const rts::Grid gr = g.grid(8, 8, false);
+    const size_t tiles = (size_t)gr.blocksX * gr.blocksY;
     const size_t waves = tiles * perTile;                             // (soft shadows, "soft_split": 4 waves per tile)
     hipError_t e = hipMalloc((void**)&c->d_waveStats, waves * 64);
     if (e == hipSuccess) e = hipMemset(c->d_waveStats, 0, waves * 64);
@@ -1327,7 +1275,7 @@ static int measureDispatch(rts_ctx* c, const rts_constants* k, const rts_light* 
         c->waveStatsBytes = waves * 32;
         const int use = c->useSplits; c->useSplits = 0;
         for (int i = 0; i < 2 && status == RTS_OK; ++i)                   // (the second launch is the one that counts: warm caches)
-            status = traceMaskImpl(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, nullptr);
+            status = traceMaskImpl(c, k, light, d_positions, g, d_mask, nullptr);
         c->useSplits = use;
         if (status == RTS_OK) e = hipDeviceSynchronize();
         if (status == RTS_OK && e == hipSuccess && (size_t)c->lastBlocksX * c->lastBlocksY != tiles) status = planRefused("not a dispatch of 8x8 tiles");
@@ -1534,9 +1482,8 @@ extern "C" int rtsh_follow_plan_device(rts_ctx* c, const uint32_t* life_ticks, c
 }
 
 // Plans the split table for ONE dispatch geometry (see include/rts.h).  Synchronous, default stream.
-static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, uint32_t W, uint32_t H,
-                          uint32_t row_begin, uint32_t row_end, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask,
-                          const rts_split_plan* plan, uint32_t* tiles_out, uint32_t* pieces_out) {
+static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const Dispatch& g,
+                          uint8_t* d_mask, const rts_split_plan* plan, uint32_t* tiles_out, uint32_t* pieces_out) {
     if (tiles_out) *tiles_out = 0;
     if (pieces_out) *pieces_out = 0;
     if (!c || !k || !d_positions || !d_mask || !plan || !(plan->min_life_us > 0.f) || !(plan->piece_us > 0.f) || !(plan->end_after_us >= 0.f) ||
@@ -1547,7 +1494,7 @@ static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* l
     RTS_HIP(hipSetDevice(c->device));
     clearSplits(c);
     if (!c->wideCount) return RTS_OK;                                            // pieces walk the private copy: none, no table
-    if (n_stripes > 1 && !stripeRows(H, band_rows, n_stripes, stripe)) return RTS_OK;   // a stripe without a band: nothing to launch, no table
+    if (g.nStripes > 1 && !g.rows()) return RTS_OK;                              // a stripe without a band: nothing to launch, no table
     const uint32_t maxPieces = plan->max_pieces < 2 ? 2 : (plan->max_pieces > 64 ? 64 : plan->max_pieces);
     const uint32_t maxTiles = plan->max_tiles ? (plan->max_tiles > 65536u ? 65536u : plan->max_tiles) : 4096u;
     const uint32_t logCap = 16384;
@@ -1560,14 +1507,15 @@ static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* l
             stats.assign(plan->prev_stats, plan->prev_stats + waves * 4);
             rt.assign(plan->prev_realtime, plan->prev_realtime + waves * 4);
         } else {                                                                 // one launch of this dispatch with wave statistics
-            status = measureDispatch(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, stats, rt);
+            status = measureDispatch(c, k, light, d_positions, g, d_mask, stats, rt);
             if (status != RTS_OK) return status;
             waves = stats.size() / 4;
         }
         // the tiles whose wave lived longer than min_life_us, longest first
         using Sel = SplitSel;
         std::vector<Sel> sel, front;                                            // to be split / to be started first, unsplit
-        const uint32_t blocksX = (W + 7) / 8;
+        const rts::Grid key = g.grid(8, 8, false);                              // the dispatch this table belongs to, in 8 x 8 tiles
+        const uint32_t blocksX = key.blocksX, keyBlocksY = key.blocksY;
         uint32_t blocksY = 0;
         uint64_t began = ~0ull;                                                 // the dispatch's first wave
         for (size_t i = 0; i < waves; ++i) if (rt[i * 4 + 1] > rt[i * 4] && rt[i * 4] < began) began = rt[i * 4];
@@ -1606,9 +1554,6 @@ static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* l
             if (us > plan->min_life_us && (float)(r1 - began) * 0.01f > plan->end_after_us) sel.push_back({ us, bx | (by << 16) });
             else if (frontLife > 0.f && us > frontLife) front.push_back({ B > 1 ? blockLife[(bx / B) | ((by / B) << 16)] : us, bx | (by << 16) });
         }
-        // the dispatch this table belongs to (what traceMaskImpl will compute for the same arguments)
-        const uint32_t rows = n_stripes > 1 ? stripeRows(H, band_rows, n_stripes, stripe) : row_end - row_begin;
-        const uint32_t keyBlocksY = (rows + 7) / 8;
         if (blocksY > keyBlocksY) return planRefused("statistics of another dispatch");
         {                                                                       // (the caller's statistics may name a tile twice)
             std::vector<uint32_t> named(((size_t)blocksX * keyBlocksY + 31) / 32, 0u);
@@ -1674,7 +1619,7 @@ static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* l
         if (e == hipSuccess && T) {
             const rts_ctx::Planning pl{ (const uint32_t*)d_prov, T, (T + blocksX - 1) / blocksX, (uint64_t*)d_state, (uint32_t*)d_log, logCap };
             c->planning = &pl;
-            status = traceMaskImpl(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, nullptr);
+            status = traceMaskImpl(c, k, light, d_positions, g, d_mask, nullptr);
             c->planning = nullptr;
             if (status == RTS_OK) e = rts::launchSplitQuantiles((const uint32_t*)d_log, logCap, (const rts::SplitCut*)d_cuts, (const uint32_t*)d_first,
                                                                 T, (uint32_t*)d_pieces, c->d_wide, nullptr);
@@ -1694,8 +1639,7 @@ static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* l
         }
         rts_ctx::Splits& t = c->splits;
         t.valid = true;
-        t.W = W; t.H = H; t.rowBegin = row_begin; t.rowEnd = row_end; t.bandRows = band_rows; t.nStripes = n_stripes; t.stripe = stripe;
-        t.blocksX = blocksX; t.blocksY = keyBlocksY;
+        t.geom = g; t.blocksX = blocksX; t.blocksY = keyBlocksY;
         t.d_skipMap = (uint32_t*)d_map; t.d_pieces = (uint32_t*)d_pieces;
         t.d_frontMap = (uint32_t*)d_front; t.frontStride = frontStride;
         t.nPieces = nPieces + F; t.pieceRows = (nPieces + F + blocksX - 1) / blocksX; t.nTiles = T; t.nFront = F;
@@ -1716,19 +1660,18 @@ static int planSplitsImpl(rts_ctx* c, const rts_constants* k, const rts_light* l
 // soft shadows (several samples per pixel, 4 waves per tile).  Wave statistics of this dispatch, a tile as long as its longest wave,
 // the order of sortFront / dealOverXcds (bands of life, longest first, each band dealt over the XCDs by image squares), installed as
 // the context's tile order (rts_ctx_set_tile_order: workgroup i walks tile order[i]).
-static int planTileOrderImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, uint32_t W, uint32_t H,
-                             uint32_t row_begin, uint32_t row_end, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask,
-                             uint32_t xcd_square, uint32_t life_block, uint32_t* tiles_out) {
+static int planTileOrderImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const Dispatch& g,
+                             uint8_t* d_mask, uint32_t xcd_square, uint32_t life_block, uint32_t* tiles_out) {
     if (tiles_out) *tiles_out = 0;
     if (!c || !k || !d_positions || !d_mask || xcd_square > 65535u || life_block > 65535u) return RTS_ERR_INVALID_ARG;
     RTS_HIP(hipSetDevice(c->device));
     int status = rts_ctx_set_tile_order(c, nullptr, 0);
     if (status != RTS_OK) return status;
     if (c->blockWaves != 1 || c->swizzle) return RTS_OK;                           // (one tile per workgroup only)
-    if (n_stripes > 1 && !stripeRows(H, band_rows, n_stripes, stripe)) return RTS_OK;   // a stripe without a band: nothing to order
+    if (g.nStripes > 1 && !g.rows()) return RTS_OK;                              // a stripe without a band: nothing to order
     const uint32_t perTile = (light && light->nsamples > 1 && c->softSplit) ? 4u : 1u;
     std::vector<uint64_t> stats, rt;
-    status = measureDispatch(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, stats, rt, perTile);
+    status = measureDispatch(c, k, light, d_positions, g, d_mask, stats, rt, perTile);
     if (status == RTS_ERR_INVALID_ARG) return RTS_OK;                               // not a dispatch of 8x8 tiles: no order
     if (status != RTS_OK) return status;
     if (c->lastVariant != rts::V_PACKET && c->lastVariant != rts::V_WIDE) return RTS_OK;
@@ -1773,14 +1716,13 @@ static int planTileOrderImpl(rts_ctx* c, const rts_constants* k, const rts_light
 // few long waves (atrium 1080p: -30 %), and the stripes of a multi-GPU frame; a frame that is throughput-bound to its end
 // (city, courtyard at 4K) keeps the plain launch.  Leaves the options and the table of the winners installed.  Results
 // never depend on any of them.
-static int autotuneImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, uint32_t W, uint32_t H,
-                        uint32_t row_begin, uint32_t row_end, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask,
-                        int* chosen, float* ms_out) {
+static int autotuneImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const Dispatch& g,
+                        uint8_t* d_mask, int* chosen, float* ms_out) {
     if (!c || !k || !d_positions || !d_mask) return RTS_ERR_INVALID_ARG;
     RTS_HIP(hipSetDevice(c->device));
     clearSplits(c);
     int status = RTS_OK;
-    if (n_stripes > 1 && !stripeRows(H, band_rows, n_stripes, stripe)) {        // a stripe without a band: nothing to time, nothing tuned
+    if (g.nStripes > 1 && !g.rows()) {                                          // a stripe without a band: nothing to time, nothing tuned
         if (c->tileOrderPlanned) status = rts_ctx_set_tile_order(c, nullptr, 0);
         if (chosen) *chosen = c->variant;
         if (ms_out) *ms_out = 0.f;
@@ -1792,7 +1734,7 @@ static int autotuneImpl(rts_ctx* c, const rts_constants* k, const rts_light* lig
         for (int i = -2; i < reps; ++i) {
             hipError_t e = hipEventRecord(c->ev0, nullptr);
             if (e != hipSuccess) { status = hipStatus(e); return false; }
-            status = traceMaskImpl(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, nullptr);
+            status = traceMaskImpl(c, k, light, d_positions, g, d_mask, nullptr);
             if (status != RTS_OK) return false;
             float ms = 0;
             e = hipEventRecord(c->ev1, nullptr);
@@ -1818,8 +1760,8 @@ static int autotuneImpl(rts_ctx* c, const rts_constants* k, const rts_light* lig
         status = rts_ctx_set_tile_order(c, nullptr, 0);
         if (status != RTS_OK) return status;
     }
-    uint64_t pixels = (uint64_t)W * (row_end - row_begin);
-    if (n_stripes > 1) pixels /= n_stripes;
+    uint64_t pixels = (uint64_t)g.W * (g.rowEnd - g.rowBegin);
+    if (g.nStripes > 1) pixels /= g.nStripes;
     int best = before;
     float bestMs = 1e30f;
     for (int v : candidates) {
@@ -1839,7 +1781,7 @@ static int autotuneImpl(rts_ctx* c, const rts_constants* k, const rts_light* lig
             if (!median5(&ms)) return giveUp();
             if (ms < bestMs * 0.985f) bestMs = ms; else c->packetShare = shareBefore;
         }
-        if (c->rowOrder == 0 && !c->d_tileOrder && !c->swizzle && n_stripes <= 1) {
+        if (c->rowOrder == 0 && !c->d_tileOrder && !c->swizzle && g.nStripes <= 1) {
             c->rowOrder = 1;
             if (!median5(&ms)) return giveUp();
             if (ms < bestMs * 0.985f) bestMs = ms; else c->rowOrder = orderBefore;
@@ -1858,7 +1800,7 @@ static int autotuneImpl(rts_ctx* c, const rts_constants* k, const rts_light* lig
             int kept = -1, installed = -1;
             rts_split_plan plan{};
             std::vector<uint64_t> tuneStats, tuneRt;
-            status = measureDispatch(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, tuneStats, tuneRt);
+            status = measureDispatch(c, k, light, d_positions, g, d_mask, tuneStats, tuneRt);
             if (status == RTS_ERR_INVALID_ARG) { status = RTS_OK; goto tuned; }    // (not a dispatch of 8x8 tiles: no table)
             if (status != RTS_OK) return giveUp();
             {
@@ -1890,13 +1832,13 @@ static int autotuneImpl(rts_ctx* c, const rts_constants* k, const rts_light* lig
                 if (c->tuneForMotion && i != 5) continue;
                 fill(i);
                 uint32_t tiles = 0;
-                status = planSplitsImpl(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, &plan, &tiles, nullptr);
+                status = planSplitsImpl(c, k, light, d_positions, g, d_mask, &plan, &tiles, nullptr);
                 if (status != RTS_OK) return giveUp();
                 installed = i;
                 if (!tiles) continue;
                 for (const auto t0 = std::chrono::steady_clock::now(); status == RTS_OK && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(20);) {
                     for (int w = 0; w < 8 && status == RTS_OK; ++w)
-                        status = traceMaskImpl(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, nullptr);
+                        status = traceMaskImpl(c, k, light, d_positions, g, d_mask, nullptr);
                     if (hipStreamSynchronize(nullptr) != hipSuccess) status = RTS_ERR_HIP;
                 }
                 if (status != RTS_OK) return giveUp();
@@ -1915,7 +1857,7 @@ static int autotuneImpl(rts_ctx* c, const rts_constants* k, const rts_light* lig
             if (kept < 0) clearSplits(c);
             else if (kept != installed) {
                 fill(kept);
-                status = planSplitsImpl(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, &plan, nullptr, nullptr);
+                status = planSplitsImpl(c, k, light, d_positions, g, d_mask, &plan, nullptr, nullptr);
                 if (status != RTS_OK) return giveUp();
             }
             }
@@ -1927,12 +1869,12 @@ static int autotuneImpl(rts_ctx* c, const rts_constants* k, const rts_light* lig
             // are within 2 % on these frames; in order the stackless packet gains more: city x 16 samples 2.25 against 2.39 ms).
             auto ordered = [&](int variant, float* ms, uint32_t* tiles) {
                 c->variant = variant;
-                status = planTileOrderImpl(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, 32u,
+                status = planTileOrderImpl(c, k, light, d_positions, g, d_mask, 32u,
                                            c->tuneForMotion ? 16u : 0u, tiles);
                 if (status != RTS_OK) return false;
                 if (!*tiles) return true;
                 for (const auto t0 = std::chrono::steady_clock::now(); status == RTS_OK && std::chrono::steady_clock::now() - t0 < std::chrono::milliseconds(20);) {
-                    status = traceMaskImpl(c, k, light, d_positions, W, H, row_begin, row_end, band_rows, n_stripes, stripe, d_mask, nullptr);
+                    status = traceMaskImpl(c, k, light, d_positions, g, d_mask, nullptr);
                     if (hipStreamSynchronize(nullptr) != hipSuccess) status = RTS_ERR_HIP;
                 }
                 return status == RTS_OK && median5(ms);
@@ -1971,21 +1913,19 @@ int rts_ctx_plan_tile_order(rts_ctx* c, const rts_constants* k, const rts_light*
                             uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, uint32_t xcd_square, uint32_t life_block,
                             uint32_t* tiles) {
     if (W == 0 || H == 0 || n_stripes == 0 || stripe >= n_stripes || (n_stripes > 1 && (band_rows == 0 || band_rows % 8 != 0))) return RTS_ERR_INVALID_ARG;
-    if (n_stripes == 1) return planTileOrderImpl(c, k, light, d_positions, W, H, 0, H, 0, 1, 0, d_mask, xcd_square, life_block, tiles);
-    return planTileOrderImpl(c, k, light, d_positions, W, H, 0, H, band_rows, n_stripes, stripe, d_mask, xcd_square, life_block, tiles);
+    return planTileOrderImpl(c, k, light, d_positions, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_mask, xcd_square, life_block, tiles);
 }
 
 int rts_ctx_autotune(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, uint32_t W,
                      uint32_t H, uint8_t* d_mask, int* chosen, float* ms_out) {
     if (W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
-    return autotuneImpl(c, k, light, d_positions, W, H, 0, H, 0, 1, 0, d_mask, chosen, ms_out);
+    return autotuneImpl(c, k, light, d_positions, Dispatch::ofRows(W, H, 0, H), d_mask, chosen, ms_out);
 }
 
 int rts_ctx_autotune_stripes(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, uint32_t W, uint32_t H,
                              uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, int* chosen, float* ms_out) {
-    if (W == 0 || H == 0 || band_rows == 0 || band_rows % 8 != 0 || n_stripes == 0 || stripe >= n_stripes) return RTS_ERR_INVALID_ARG;
-    if (n_stripes == 1) return autotuneImpl(c, k, light, d_positions, W, H, 0, H, 0, 1, 0, d_mask, chosen, ms_out);
-    return autotuneImpl(c, k, light, d_positions, W, H, 0, H, band_rows, n_stripes, stripe, d_mask, chosen, ms_out);
+    if (W == 0 || H == 0 || !rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return autotuneImpl(c, k, light, d_positions, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_mask, chosen, ms_out);
 }
 
 int rts_ctx_get_split_plan(rts_ctx* c, rts_split_plan* out) {
@@ -1997,15 +1937,14 @@ int rts_ctx_get_split_plan(rts_ctx* c, rts_split_plan* out) {
 int rts_ctx_plan_splits(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, uint32_t W, uint32_t H,
                         uint32_t row_begin, uint32_t row_end, uint8_t* d_mask, const rts_split_plan* plan, uint32_t* tiles, uint32_t* pieces) {
     if (W == 0 || H == 0 || row_begin >= row_end || row_end > H) return RTS_ERR_INVALID_ARG;
-    return planSplitsImpl(c, k, light, d_positions, W, H, row_begin, row_end, 0, 1, 0, d_mask, plan, tiles, pieces);
+    return planSplitsImpl(c, k, light, d_positions, Dispatch::ofRows(W, H, row_begin, row_end), d_mask, plan, tiles, pieces);
 }
 
 int rts_ctx_plan_splits_stripes(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, uint32_t W, uint32_t H,
                                 uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, const rts_split_plan* plan,
                                 uint32_t* tiles, uint32_t* pieces) {
-    if (W == 0 || H == 0 || band_rows == 0 || band_rows % 8 != 0 || n_stripes == 0 || stripe >= n_stripes) return RTS_ERR_INVALID_ARG;
-    if (n_stripes == 1) return planSplitsImpl(c, k, light, d_positions, W, H, 0, H, 0, 1, 0, d_mask, plan, tiles, pieces);
-    return planSplitsImpl(c, k, light, d_positions, W, H, 0, H, band_rows, n_stripes, stripe, d_mask, plan, tiles, pieces);
+    if (W == 0 || H == 0 || !rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return planSplitsImpl(c, k, light, d_positions, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_mask, plan, tiles, pieces);
 }
 
 // diagnostics: per piece of the installed table {tile x | y << 16, first node, end node, pieces of its tile} and the 100 MHz

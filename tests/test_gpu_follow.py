@@ -279,3 +279,54 @@ def test_steady_frames_allocate_nothing(ctx):
         ctx.free(d_pos)
         ctx.free(d_mask)
         frames.close()
+
+
+def test_a_stream_starts_over_when_any_field_of_the_geometry_changes(ctx):
+    """A stream's follow state belongs to one dispatch: W, H, the row range, the band, the number of stripes and the stripe.  After two
+    traces of a dispatch (the second runs the planned order), a first trace that differs in ONE of the seven runs no order, resets
+    the stream's state in place, and gives the mask of the same trace with follow off."""
+    wl = workloads.prepare("cornell", 64, 64, via_obj=False)
+    rows = lambda W, H, b, e: lambda **kw: ctx.trace_shadow_mask_device(wl.constants, d_pos, W, H, d_mask, light=wl.light, row_begin=b, row_end=e, **kw)
+    stripes = lambda band, n, r: lambda **kw: ctx.trace_shadow_mask_stripes_device(wl.constants, d_pos, 64, 64, d_mask, band, n, r, light=wl.light, **kw)
+    cases = {"W": (rows(64, 64, 0, 64), rows(56, 64, 0, 64)),
+             "H": (rows(64, 64, 0, 56), rows(64, 56, 0, 56)),
+             "row_begin": (rows(64, 64, 0, 64), rows(64, 64, 8, 64)),
+             "row_end": (rows(64, 64, 0, 64), rows(64, 64, 0, 56)),
+             "band_rows": (stripes(8, 2, 0), stripes(16, 2, 0)),
+             "n_stripes": (stripes(8, 2, 0), stripes(8, 4, 0)),
+             "stripe": (stripes(8, 2, 0), stripes(8, 2, 1))}
+    ctx.set_bvh(wl.packed)
+    ctx.set_option("kernel", 3)
+    d_pos, d_mask = ctx.malloc(wl.positions.nbytes), ctx.malloc(64 * 64)
+
+    def mask_of(trace):
+        ctx.h2d(d_mask, np.full(64 * 64, 7, np.uint8))
+        trace()
+        got = np.empty(64 * 64, np.uint8)
+        ctx.synchronize()
+        ctx.d2h(got, d_mask)
+        return got
+
+    try:
+        ctx.h2d(d_pos, wl.positions)
+        ctx.set_option("follow", 0)
+        plain = {field: mask_of(changed) for field, (_, changed) in cases.items()}
+        assert ctx.last_kernel_name() == "shadowMaskPacketKernel<1>"
+        ctx.set_option("follow", 1)
+        for field, (base, changed) in cases.items():
+            base()
+            ordered = ctx.get_option("follow_ordered")
+            base()
+            assert ctx.get_option("follow_ordered") == ordered + 1, field
+            traces = ctx.get_option("follow_traces")
+            got = mask_of(changed)
+            assert ctx.get_option("follow_ordered") == ordered + 1, f"{field}: the order of another dispatch was run"
+            assert ctx.get_option("follow_traces") == traces + 1 and ctx.last_kernel_name() == "shadowMaskFollowKernel<1>", field
+            assert ctx.get_option("follow_streams") == 1, field
+            assert np.array_equal(got, plain[field]), f"{field}: follow on and off differ"
+            assert (got != 7).any(), field
+    finally:
+        ctx.set_option("follow", 0)
+        ctx.set_option("kernel", -1)
+        ctx.free(d_pos)
+        ctx.free(d_mask)
