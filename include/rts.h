@@ -314,7 +314,7 @@ int rts_trace_rays_device(rts_ctx* ctx, const rts_ray* d_rays, size_t n, uint8_t
  *                other pixel.
  *     mask     : NULL, or W x H bytes that receive exactly what rts_trace_shadow_mask_active* writes -- so
  *                mask[p] == (distance[p] == +Inf) everywhere, inactive pixels (0, +0) included.
- *   * light->nsamples > 1 returns RTS_ERR_INVALID_ARG in this version.
+ *   * light->nsamples > 1 returns RTS_ERR_INVALID_ARG: several samples are rts_trace_soft_distance* (below).
  *   * the stripes form: as for the mask traces, a stripe that owns no band launches nothing, writes nothing and returns RTS_OK.
  *   * results never depend on an option.  "kernel" picks the FAMILY: 0, 1, 2, 7 (and -1 below 256 K pixels), and every wave that
  *     must take the exact path, run the lane-per-ray walk with work sharing (16 x 16 blocks; a stripe's band is then a multiple of
@@ -340,6 +340,43 @@ int rts_trace_shadow_distance_stripes_device(rts_ctx* ctx, const rts_constants* 
                                              const float* d_positions, const uint8_t* d_active, uint32_t W, uint32_t H,
                                              uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, float* d_distance,
                                              uint8_t* d_mask, void* stream);
+
+/* SOFT-SHADOW OCCLUDER DISTANCE: the nearest blocker over ALL of an area light's samples, beside the count of unoccluded ones (what a
+ * shadow denoiser and a contact-hardening penumbra estimate want of a soft shadow).  For pixel p and a light of n = nsamples in [2, 64]:
+ *   sample j's ray is the one rts_trace_shadow_mask* sets up for (p, j): light position xyz + offsets[j], or with `table` != 0
+ *   offsets[(start(p) + j) mod table] -- start(p) hashed from p's index y*W + x in the caller's FULL frame (rts_light.table);
+ *   d_j = that ray's distance as defined above (OCCLUDER DISTANCE);
+ *   distance[p] = min_j d_j -- every d_j is a bit pattern >= +0, so this is an integer minimum that does not depend on the order of
+ *                 the samples; +Inf exactly when every sample is unoccluded;
+ *   mask[p]     = #{ j : d_j == +Inf }: the byte rts_trace_shadow_mask_active* writes for the same light.
+ * Hence mask[p] == n exactly where distance[p] == +Inf, and mask[p] < n exactly where it is finite.  Inactive pixels get +0.0f and 0,
+ * and their positions are never looked at; rows outside the range / stripe are not touched.  active and mask may be NULL.
+ * (The MEAN blocker distance is not offered: a float sum has no order-free definition -- DESIGN.md 4.13.)
+ *   * nsamples 0 or 1 (or light == NULL) IS rts_trace_shadow_distance*: the same launch of the same kernel, the same bytes, counted
+ *     by "distance_traces".  nsamples > 64, type > RTS_LIGHT_POINT, or a table outside nsamples <= table <= 64 with nsamples >= 2:
+ *     RTS_ERR_INVALID_ARG.  (rts_trace_shadow_distance* itself keeps refusing nsamples > 1.)
+ *   * results never depend on an option.  "kernel" picks the FAMILY as for a distance trace: 0, 1, 2, 7 (and -1 below 256 K pixels)
+ *     the lane-per-ray walk over 16 x 16 blocks, the samples one after the other; 3..6, 8, 9 (and -1 from 256 K pixels) the stackless
+ *     packet over 8 x 8 tiles -- with "soft_split" 1 (default) four waves per tile, wave w walking the samples w, w + 4, ..., their
+ *     minima and counts joined in LDS; with 0 one wave walks every sample.  A stripe's band is a multiple of 16 rows for the first
+ *     family, of 8 for the second; a stripe that owns no band launches nothing, writes nothing and returns RTS_OK.
+ *   * like a distance trace it ignores split tables, tile orders, follow mode, "block_waves", "wide_lane", wave statistics and the
+ *     clock probe, and never drops or alters any of them.
+ *   * the device forms are asynchronous, allocate nothing and read nothing back; under graph capture each adds ONE kernel node,
+ *     constants, light and options by value.  The host form copies in its rows only, traces, copies out.
+ *   * get-only option "soft_distance_traces": soft distance launches so far ("distance_traces" does not move for them);
+ *     rts_ctx_last_kernel_name then names "shadowSoftDistanceShareKernel" or "shadowSoftDistancePacketKernel<S,geom>", S = 4 or 1
+ *     waves per tile, geom = rows, bands or general as for "shadowDistancePacketKernel". */
+int rts_trace_soft_distance(rts_ctx* ctx, const rts_constants* constants, const rts_light* light, const float* positions,
+                            const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                            float* distance, uint8_t* mask);
+int rts_trace_soft_distance_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light,
+                                   const float* d_positions, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                   uint32_t row_begin, uint32_t row_end, float* d_distance, uint8_t* d_mask, void* stream);
+int rts_trace_soft_distance_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light,
+                                           const float* d_positions, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                           uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, float* d_distance,
+                                           uint8_t* d_mask, void* stream);
 
 /* ---- device-memory and timing plumbing (so callers need no HIP headers) ------ */
 int rts_device_count(int* count);

@@ -74,11 +74,21 @@ int rtsh_facing_active_device(rts_ctx* ctx, const rts_constants* constants, cons
  *   rtsh_shadow_distance : for rows [row_begin, row_end): distance[p] = the ray's distance where active[p] != 0 (active == NULL:
  *                          everywhere), +0.0f where it is 0; mask (nullable) = 1 exactly where the distance is +Inf, 0 elsewhere
  *                          and at inactive pixels.  Other rows are not touched.  Inactive positions are never read.
- *                          light->nsamples > 1 returns RTS_ERR_INVALID_ARG (this version traces one sample). */
+ *                          light->nsamples > 1 returns RTS_ERR_INVALID_ARG (several samples: rtsh_soft_distance). */
 int rtsh_rays_distance(const rts_vec4u* packed, size_t count_vec4, const rts_ray* rays, size_t n, float* out_t, int threads);
 int rtsh_shadow_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_light* light,
                          const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
                          uint32_t row_end, float* distance, uint8_t* mask, int threads);
+
+/* SOFT-SHADOW OCCLUDER DISTANCE on the host: the definition of rts_trace_soft_distance* (include/rts.h) as one straight loop over
+ * (pixel, sample) -- sample j's light position xyz + offsets[j] (with light->table: the table index hashed from the pixel's index
+ * y*W + x in the frame given here), rtsh_shadow_distance's ray set-up and one-ray distance, distance[p] = the integer minimum over the
+ * samples, mask[p] (nullable) = the number of samples whose distance is +Inf.  Inactive pixels: +0.0f and 0, positions never read;
+ * rows outside [row_begin, row_end) are not touched.  nsamples 0 or 1 gives rtsh_shadow_distance's bytes; nsamples > 64, a bad table or
+ * type > RTS_LIGHT_POINT: RTS_ERR_INVALID_ARG.  Runs without a GPU: the checker of the device forms, bit for bit. */
+int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_light* light,
+                       const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                       uint32_t row_end, float* distance, uint8_t* mask, int threads);
 
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.

@@ -155,6 +155,14 @@ _sig("rts_trace_shadow_distance_stripes_device", C.c_int, C.c_void_p, C.POINTER(
 _sig("rtsh_rays_distance", C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int)
 _sig("rtsh_shadow_distance", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rts_trace_soft_distance", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_soft_distance_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rts_trace_soft_distance_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_soft_distance", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
 _sig("rts_device_malloc", C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t)
 _sig("rts_device_free", C.c_int, C.c_void_p, C.c_void_p)
 _sig("rts_memcpy_h2d", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -565,6 +573,46 @@ class ShadowContext:
                                                              C.c_void_p(d_distance), C.c_void_p(d_mask or 0), C.c_void_p(stream or 0)),
                "rts_trace_shadow_distance_stripes_device")
 
+    # -- soft-shadow occluder distance (include/rts.h): the nearest blocker over all light samples, and the count of unoccluded ones --
+    def trace_soft_distance(self, constants, positions, width, height, light=None, row_begin=0, row_end=None, active=None,
+                            out=None, mask=None, want_mask=True):
+        """Host-pointer dispatch; returns ``(float32[H, W] distance, uint8[H, W] mask)`` (mask None with ``want_mask`` False):
+        the minimum of the samples' distances and the number of unoccluded samples.  ``out`` / ``mask``: arrays to write into."""
+        positions = np.ascontiguousarray(positions, dtype=np.float32)
+        if positions.size != width * height * 4:
+            raise RtsError(1, "trace_soft_distance: positions must be W*H*4 floats")
+        row_end = height if row_end is None else row_end
+        dist = out if out is not None else np.zeros((height, width), dtype=np.float32)
+        if mask is None and want_mask:
+            mask = np.zeros((height, width), dtype=np.uint8)
+        if active is not None:
+            active = np.ascontiguousarray(active, dtype=np.uint8)
+            if active.size != width * height:
+                raise RtsError(1, "trace_soft_distance: active must be W*H bytes")
+        lp = C.byref(light) if light is not None else None
+        _check(_lib.rts_trace_soft_distance(self._h, C.byref(constants), lp, _ptr(positions), _ptr(active) if active is not None else None,
+                                            width, height, row_begin, row_end, _ptr(dist), _ptr(mask) if mask is not None else None),
+               "rts_trace_soft_distance")
+        return dist, mask
+
+    def trace_soft_distance_device(self, constants, d_positions, width, height, d_distance, d_mask=None, light=None, row_begin=0,
+                                   row_end=None, stream=None, d_active=None):
+        """Device pointers, asynchronous: d_distance = width * height floats, d_mask / d_active = width * height bytes or None."""
+        row_end = height if row_end is None else row_end
+        lp = C.byref(light) if light is not None else None
+        _check(_lib.rts_trace_soft_distance_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions), C.c_void_p(d_active or 0),
+                                                   width, height, row_begin, row_end, C.c_void_p(d_distance), C.c_void_p(d_mask or 0),
+                                                   C.c_void_p(stream or 0)), "rts_trace_soft_distance_device")
+
+    def trace_soft_distance_stripes_device(self, constants, d_positions, width, height, d_distance, band_rows, n_stripes, stripe,
+                                           d_mask=None, light=None, stream=None, d_active=None):
+        """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        lp = C.byref(light) if light is not None else None
+        _check(_lib.rts_trace_soft_distance_stripes_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
+                                                           C.c_void_p(d_active or 0), width, height, band_rows, n_stripes, stripe,
+                                                           C.c_void_p(d_distance), C.c_void_p(d_mask or 0), C.c_void_p(stream or 0)),
+               "rts_trace_soft_distance_stripes_device")
+
     # -- plumbing ---------------------------------------------------------------------------
     def stream_create(self):
         s = C.c_void_p()
@@ -855,6 +903,29 @@ def shadow_distance(packed, constants, light, positions, width, height, active=N
     _check(_lib.rtsh_shadow_distance(_ptr(packed), packed.shape[0], C.byref(constants), lp, _ptr(positions),
                                      _ptr(active) if active is not None else None, width, height, row_begin, row_end, _ptr(dist),
                                      _ptr(mask) if mask is not None else None, threads), "rtsh_shadow_distance")
+    return dist, mask
+
+
+def soft_distance(packed, constants, light, positions, width, height, active=None, row_begin=0, row_end=None, out=None, mask=None,
+                  threads=0, want_mask=True):
+    """Soft-shadow occluder distance on the host (rtsh_soft_distance, no GPU): ``(float32[H, W], uint8[H, W])`` -- the minimum of the
+    light samples' distances and the number of unoccluded samples (mask None with ``want_mask`` False)."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    positions = np.ascontiguousarray(positions, np.float32)
+    if positions.size != width * height * 4:
+        raise RtsError(1, "soft_distance: positions must be W*H*4 floats")
+    if active is not None:
+        active = np.ascontiguousarray(active, np.uint8)
+        if active.size != width * height:
+            raise RtsError(1, "soft_distance: active must be W*H bytes")
+    row_end = height if row_end is None else row_end
+    dist = out if out is not None else np.zeros((height, width), np.float32)
+    if mask is None and want_mask:
+        mask = np.zeros((height, width), np.uint8)
+    lp = C.byref(light) if light is not None else None
+    _check(_lib.rtsh_soft_distance(_ptr(packed), packed.shape[0], C.byref(constants), lp, _ptr(positions),
+                                   _ptr(active) if active is not None else None, width, height, row_begin, row_end, _ptr(dist),
+                                   _ptr(mask) if mask is not None else None, threads), "rtsh_soft_distance")
     return dist, mask
 
 

@@ -4,6 +4,7 @@
 #include "bvh_builder.h"
 #include "bvh_refit.h"
 #include "rts_device.h"
+#include "rts_soft_distance.h"
 #include "rts_dispatch.h"
 #include "rts_refit.h"
 
@@ -38,6 +39,7 @@ struct rts_ctx {
     uint64_t activeTraces = 0;                        // launches with an active map (get-only option "active_traces")
     void* d_dist = nullptr; size_t distBytes = 0;     // staging for the distances of the host-pointer distance traces
     uint64_t distanceTraces = 0;                      // launches of a distance kernel (get-only option "distance_traces")
+    uint64_t softDistanceTraces = 0;                  // launches of a soft distance kernel (get-only option "soft_distance_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
     int packetShare = 4;
@@ -545,6 +547,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "follow_ordered")) { *value = (int)(c->followOrdered & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "active_traces")) { *value = (int)(c->activeTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "distance_traces")) { *value = (int)(c->distanceTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "soft_distance_traces")) { *value = (int)(c->softDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
     if (!strcmp(key, "tile_order_planned")) { *value = c->tileOrderPlanned ? 1 : 0; return RTS_OK; }
@@ -916,6 +919,47 @@ int rts_trace_shadow_distance_stripes_device(rts_ctx* c, const rts_constants* k,
     return traceDistanceImpl(c, k, light, d_positions, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_distance, d_mask, stream);
 }
 
+// ---- soft-shadow occluder distance (include/rts.h): the nearest blocker over all light samples, beside the count of unoccluded ones --
+// One launch of a soft distance kernel (rts_soft_distance.inc) with the geometry, the family rule and the launch shape of a distance
+// trace; a light of one sample IS the distance trace.  No table, order, follow state or statistic is used or touched.
+static int traceSoftDistanceImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const uint8_t* d_active,
+                                 const Dispatch& g, float* d_distance, uint8_t* d_mask, void* stream) {
+    const bool lightOk = !light || (light->type <= RTS_LIGHT_POINT && light->nsamples <= 64 &&             // (the mask trace's rule)
+                                    (!light->table || (light->table <= 64 && light->table >= light->nsamples && light->nsamples >= 2)));
+    if (!lightOk) return RTS_ERR_INVALID_ARG;
+    if (!light || light->nsamples <= 1) return traceDistanceImpl(c, k, light, d_positions, d_active, g, d_distance, d_mask, stream);
+    TraceParams p; uint32_t rows = 0; int s;
+    if (beginFrame(c, k, d_positions, d_mask, d_distance != nullptr, g, p, &rows, &s) != Begin::Go) return s;
+    p.distance = d_distance;
+    p.activeMap = d_active;
+    const uint64_t pixels = (uint64_t)g.W * rows;
+    int variant = c->variant;
+    if (variant == rts::V_AUTO) variant = pixels < (1u << 18) ? rts::V_SHARE : rts::V_PACKET;
+    else variant = (variant >= rts::V_PACKET && variant != rts::V_SHARE) ? rts::V_PACKET : rts::V_SHARE;
+    s = setBlockGrid(c, p, g, variant);
+    if (s != RTS_OK) return s;
+    setLight(p, k, light);
+    ++c->launches;
+    ++c->softDistanceTraces;
+    const char* name = "";
+    const hipError_t e = rts::launchShadowSoftDistance(variant, p, (hipStream_t)stream, &name);
+    c->lastKernel = name;
+    return hipStatus(e);
+}
+
+int rts_trace_soft_distance_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
+                                   const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                   float* d_distance, uint8_t* d_mask, void* stream) {
+    return traceSoftDistanceImpl(c, k, light, d_positions, d_active, Dispatch::ofRows(W, H, row_begin, row_end), d_distance, d_mask, stream);
+}
+
+int rts_trace_soft_distance_stripes_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
+                                           const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes,
+                                           uint32_t stripe, float* d_distance, uint8_t* d_mask, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceSoftDistanceImpl(c, k, light, d_positions, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_distance, d_mask, stream);
+}
+
 int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, float* d_out_t, void* stream) {
     if (!c || (n && (!d_rays || !d_out_t)) || n > (1ull << 38)) return RTS_ERR_INVALID_ARG;   // grid.x is 31-bit
     TraceParams p;
@@ -932,9 +976,9 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 
 // ---- the host-pointer entries: the same traces through the context's staging buffers ----------------------------------------------
 // Frames (arguments checked by the caller): only rows [row_begin, row_end) travel -- their positions, map, mask and distances, as a
-// frame of their own.  distance != NULL: a distance trace (mask optional), else a mask trace.
+// frame of their own.  distance != NULL: a distance trace (mask optional; soft: over all light samples), else a mask trace.
 static int traceStagedRows(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
-                           uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
+                           uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask, bool soft = false) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
     if (row_begin == row_end) return RTS_OK;
     RTS_HIP(hipSetDevice(c->device));
@@ -950,9 +994,10 @@ static int traceStagedRows(rts_ctx* c, const rts_constants* k, const rts_light* 
     const uint8_t* d_active = active ? (const uint8_t*)c->d_act : nullptr;
     uint8_t* d_mask = mask ? (uint8_t*)c->d_out : nullptr;
     // per-pixel jitter hashes the pixel's index in the caller's frame (sampleIndex, rts_kernels.hip: the one reader, and only of a
-    // light with a table -- several samples, so never in a distance trace)
+    // light with a table -- several samples, so in a mask trace or a soft distance trace)
     c->pixelBase = row_begin * W;
-    s = distance ? rts_trace_shadow_distance_device(c, k, light, (const float*)c->d_in, d_active, W, rows, 0, rows, (float*)c->d_dist, d_mask, nullptr)
+    s = distance ? (soft ? rts_trace_soft_distance_device(c, k, light, (const float*)c->d_in, d_active, W, rows, 0, rows, (float*)c->d_dist, d_mask, nullptr)
+                         : rts_trace_shadow_distance_device(c, k, light, (const float*)c->d_in, d_active, W, rows, 0, rows, (float*)c->d_dist, d_mask, nullptr))
                  : rts_trace_shadow_mask_active_device(c, k, light, (const float*)c->d_in, d_active, W, rows, 0, rows, d_mask, nullptr);
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
@@ -977,6 +1022,14 @@ int rts_trace_shadow_distance(rts_ctx* c, const rts_constants* k, const rts_ligh
     if (!c || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
     if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 1)) return RTS_ERR_INVALID_ARG;
     return traceStagedRows(c, k, light, positions, active, W, row_begin, row_end, distance, mask);
+}
+
+int rts_trace_soft_distance(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
+                            uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
+    if (!c || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
+    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 64 ||
+                  (light->table && (light->table > 64 || light->table < light->nsamples || light->nsamples < 2)))) return RTS_ERR_INVALID_ARG;
+    return traceStagedRows(c, k, light, positions, active, W, row_begin, row_end, distance, mask, true);
 }
 
 // Rays (the caller's arguments are checked): occlusion bytes to `out`, or distances to `out_t` where out is NULL.

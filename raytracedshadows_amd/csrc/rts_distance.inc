@@ -306,3 +306,6 @@ hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(traceRaysDistanceKernel, grid, block, 0, stream, p);
     return hipGetLastError();
 }
+
+// the soft-shadow forms: the minimum over a light's samples, built on the walks above (its launch is declared in rts_soft_distance.h)
+#include "rts_soft_distance.inc"

@@ -250,3 +250,55 @@ extern "C" int rtsh_shadow_distance(const rts_vec4u* packed, size_t count_vec4, 
     });
     return RTS_OK;
 }
+
+// ---- soft-shadow occluder distance on the host (include/rts_scene.h): the checker of rts_trace_soft_distance* -----------------------
+// The definition of include/rts.h as a straight loop over (pixel, sample): the light position of sample j (rts_light: offsets[j], or
+// the table entry the pixel's hashed start picks), the ray and the one-ray distance of rtsh_shadow_distance above, an integer minimum.
+namespace rts_harness {
+namespace {
+inline uint32_t hash32(uint32_t v) {                                     // rts_light.table (include/rts.h)
+    v ^= v >> 16; v *= 0x7feb352du; v ^= v >> 15; v *= 0x846ca68bu; v ^= v >> 16;
+    return v;
+}
+inline uint32_t sampleIndex(uint32_t table, uint32_t sample, uint32_t pixel) {
+    if (table == 0) return sample;
+    const uint32_t j = (uint32_t)(((uint64_t)hash32(pixel) * table) >> 32) + sample;    // start < table, sample < nsamples <= table
+    return j >= table ? j - table : j;
+}
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_light* light,
+                                  const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                  uint32_t row_end, float* distance, uint8_t* mask, int threads) {
+    if (!packed || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
+    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 64 ||
+                  (light->table && (light->table > 64 || light->table < light->nsamples || light->nsamples < 2)))) return RTS_ERR_INVALID_ARG;
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t lightType = light ? light->type : (uint32_t)RTS_LIGHT_DIRECTIONAL;
+    const V3 L0 = light ? V3{ light->xyz[0], light->xyz[1], light->xyz[2] } : V3{ k->lightDirection[0], k->lightDirection[1], k->lightDirection[2] };
+    const uint32_t ns = (light && light->nsamples > 1) ? light->nsamples : 1u;
+    const uint32_t table = ns > 1 ? light->table : 0u;
+    const size_t first = (size_t)row_begin * W;
+    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t n) {
+        const size_t i = first + n;
+        if (active && !active[i]) { distance[i] = 0.0f; if (mask) mask[i] = 0; return; }
+        const float* q = positions + i * 4;
+        uint32_t best = 0x7F800000u, lit = 0;
+        for (uint32_t j = 0; j < ns; ++j) {
+            V3 L = L0;
+            if (ns > 1) {
+                const float* o = light->offsets[sampleIndex(table, j, (uint32_t)i)];
+                L.x = L.x + o[0]; L.y = L.y + o[1]; L.z = L.z + o[2];
+            }
+            const uint32_t one = rayDistanceBits(bvh, shadowRay(k->cameraPosition, V3{ q[0], q[1], q[2] }, lightType, L));
+            lit += one == 0x7F800000u ? 1u : 0u;                         // comp:148, per sample
+            if (one < best) best = one;
+        }
+        distance[i] = asFloat(best);
+        if (mask) mask[i] = (uint8_t)lit;                                // comp:150
+    });
+    return RTS_OK;
+}
