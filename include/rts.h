@@ -378,6 +378,50 @@ int rts_trace_soft_distance_stripes_device(rts_ctx* ctx, const rts_constants* co
                                            uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, float* d_distance,
                                            uint8_t* d_mask, void* stream);
 
+/* LIGHT LISTS: up to 8 hard lights in ONE dispatch, one bit per light in the mask byte -- one read of the G-buffer texel, one launch and
+ * one mask plane for all of a frame's shadow-casting lights.  For pixel p of the rows the call owns and l < list->count:
+ *   mask[p] bit l = (lights_map == NULL || (lights_map[p] >> l) & 1)
+ *                   ? the byte rts_trace_shadow_mask* writes at p for the hard light { lights[l].type, nsamples 1, lights[l].xyz } alone
+ *                   : 0
+ *   bits l >= count are 0, whatever the map holds.  Directional and point lights may be mixed in one list.
+ * So bit l equals rts_trace_shadow_mask_active* for light l alone with active[p] = bit l of lights_map[p], byte for byte.  Every pixel
+ * of the owned rows is written; a pixel whose map byte has no bit below count gets 0, its position is never looked at (NaN allowed)
+ * and changes no other pixel; rows outside the range / stripe are not touched.  The result does not depend on the order the lights
+ * are walked in nor on which wave walked which: bits are joined by an integer OR.
+ *   * lights_map: NULL, or W x H bytes (rtsh_facing_lights* makes the one a deferred renderer wants: bit l = the surface faces light l).
+ *   * list == NULL, count == 0, count > RTS_MAX_LIST_LIGHTS or a type > RTS_LIGHT_POINT: RTS_ERR_INVALID_ARG, nothing written.
+ *     reserved_ is ignored.  Hard lights only in this version (a soft light in a list is a later one).
+ *   * results never depend on an option.  "kernel" picks the FAMILY as for a distance trace: 0, 1, 2, 7 (and -1 below 256 K pixels) the
+ *     lane-per-ray walk over 16 x 16 blocks, the lights one after the other; 3..6, 8, 9 (and -1 from 256 K pixels) the stackless packet
+ *     over 8 x 8 tiles -- with "soft_split" 1 (default) four waves per tile, wave w walking the lights w and w + 4, their bytes ORed in
+ *     LDS; with 0 one wave walks every light.  8 and 9 run the stackless packet too in this version: the wide walk's segment form is
+ *     chosen at compile time per light type and a list mixes types (the wide form is a follow-up).  A stripe's band is a multiple of 16
+ *     rows for the first family, of 8 for the second; a stripe that owns no band launches nothing, writes nothing and returns RTS_OK.
+ *     "packet_budget", "packet_share", "xcd_swizzle" and "row_order" apply, for speed only.
+ *   * a light no pixel of a wave's tile is marked for costs that wave nothing: it is skipped before any ray is set up.
+ *   * like a distance trace it ignores split tables, tile orders, follow mode, "block_waves", "wide_lane", wave statistics and the
+ *     clock probe, and never drops or alters any of them.
+ *   * the device forms are asynchronous, allocate nothing and read nothing back; under graph capture each adds ONE kernel node,
+ *     constants, list and options by value.  The host form copies in its rows only, traces, copies out and synchronises.
+ *   * get-only option "light_list_traces": list launches so far ("active_traces", "distance_traces" and "soft_distance_traces" do not
+ *     move for them); rts_ctx_last_kernel_name then names "shadowLightListShareKernel" or "shadowLightListPacketKernel<S,geom>",
+ *     S = 4 or 1 waves per tile, geom = rows, bands or general as for "shadowSoftDistancePacketKernel". */
+enum { RTS_MAX_LIST_LIGHTS = 8 };
+typedef struct rts_light_entry { uint32_t type; float xyz[3]; } rts_light_entry;   /* 16 bytes; type, xyz as in rts_light, one sample */
+typedef struct rts_light_list {
+    uint32_t count;
+    uint32_t reserved_[3];
+    rts_light_entry lights[RTS_MAX_LIST_LIGHTS];
+} rts_light_list;                                                                  /* 144 bytes */
+int rts_trace_light_list(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* positions,
+                         const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask);
+int rts_trace_light_list_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* d_positions,
+                                const uint8_t* d_lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                uint8_t* d_mask, void* stream);
+int rts_trace_light_list_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list,
+                                        const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                        uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, void* stream);
+
 /* ---- device-memory and timing plumbing (so callers need no HIP headers) ------ */
 int rts_device_count(int* count);
 int rts_device_malloc(rts_ctx* ctx, void** d_ptr, size_t bytes);

@@ -90,6 +90,24 @@ int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, const rts_con
                        const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
                        uint32_t row_end, float* distance, uint8_t* mask, int threads);
 
+/* LIGHT LISTS on the host: the definition of rts_trace_light_list* (include/rts.h) as one straight loop over (pixel, light) on
+ * rtsh_shadow_distance's walk -- for rows [row_begin, row_end) and l < list->count, bit l of mask[p] = light l's one-ray distance is
+ * +Inf, where lights_map == NULL or bit l of lights_map[p] is set; every other bit is 0.  A pixel whose map byte has no bit below
+ * count gets 0 and its position is never read; other rows are not touched.  list == NULL, count 0 or > RTS_MAX_LIST_LIGHTS, or a
+ * type > RTS_LIGHT_POINT: RTS_ERR_INVALID_ARG.  Runs without a GPU: the checker of the device forms, byte for byte.
+ *
+ * rtsh_facing_lights / rtsh_facing_lights_device: the light map a deferred renderer wants -- bit l of lights_map[p] = the facing mark
+ * of light l (the one function the combine pass shares, so it equals rtsh_facing_active's byte for the light
+ * { lights[l].type, 1 sample, lights[l].xyz }), bits >= count are 0.  positions may be NULL when no light of the list is a point
+ * light.  The device form is asynchronous, one pixel per lane. */
+int rtsh_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_light_list* list,
+                    const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                    uint8_t* mask, int threads);
+int rtsh_facing_lights(const rts_constants* constants, const rts_light_list* list, const float* positions, const float* normals,
+                       uint32_t W, uint32_t H, uint8_t* lights_map);
+int rtsh_facing_lights_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* d_positions,
+                              const float* d_normals, uint32_t W, uint32_t H, uint8_t* d_lights_map, void* stream);
+
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.
  * Call with vertices == NULL to query *vertex_count (3 per triangle) first.  Returns RTS_OK,

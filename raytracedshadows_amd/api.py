@@ -97,6 +97,36 @@ class Light(C.Structure):
         return lt
 
 
+class LightEntry(C.Structure):
+    """``rts_light_entry``: one hard light of a light list (type and xyz as in ``rts_light``, one sample)."""
+    _fields_ = [("type", C.c_uint32), ("xyz", C.c_float * 3)]
+
+
+class LightList(C.Structure):
+    """``rts_light_list``: up to 8 hard lights traced in one dispatch, light ``l`` in bit ``l`` of the mask byte."""
+    _fields_ = [("count", C.c_uint32), ("reserved_", C.c_uint32 * 3), ("lights", LightEntry * 8)]
+    MAX = 8
+
+    @classmethod
+    def make(cls, lights):
+        """lights: a sequence of ``(kind, xyz)`` pairs, ``Light`` structs (type and xyz are taken, one sample) or ``LightEntry``."""
+        lights = list(lights)
+        if len(lights) > cls.MAX:
+            raise RtsError(1, "LightList.make: at most 8 lights")
+        ll = cls()
+        ll.count = len(lights)
+        for l, item in enumerate(lights):
+            kind, xyz = (item.type, item.xyz) if isinstance(item, (Light, LightEntry)) else item
+            ll.lights[l].type = kind
+            for i in range(3):
+                ll.lights[l].xyz[i] = np.float32(xyz[i])
+        return ll
+
+    def light(self, l):
+        """Light ``l`` alone, as the ``Light`` of the one-light entry points."""
+        return Light.make(self.lights[l].type, list(self.lights[l].xyz))
+
+
 #: numpy view of ``struct BVHNode`` (BVHBuilder.h:8-20)
 BVHNode_dtype = np.dtype([("bboxMin", np.float32, 3), ("prim", np.uint32),
                           ("bboxMax", np.float32, 3), ("next", np.uint32)])
@@ -163,6 +193,18 @@ _sig("rts_trace_soft_distance_stripes_device", C.c_int, C.c_void_p, C.POINTER(Ra
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_soft_distance", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rts_trace_light_list", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rts_trace_light_list_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_light_list_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_light_list", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_facing_lights", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+     C.c_void_p)
+_sig("rtsh_facing_lights_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rts_device_malloc", C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t)
 _sig("rts_device_free", C.c_int, C.c_void_p, C.c_void_p)
 _sig("rts_memcpy_h2d", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -613,6 +655,43 @@ class ShadowContext:
                                                            C.c_void_p(d_distance), C.c_void_p(d_mask or 0), C.c_void_p(stream or 0)),
                "rts_trace_soft_distance_stripes_device")
 
+    # -- light lists (include/rts.h): up to 8 hard lights in one dispatch, light l in bit l of the mask byte --
+    def trace_light_list(self, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None):
+        """Host-pointer dispatch; returns ``uint8[H, W]``: bit ``l`` = light ``l``'s shadow byte where ``lights_map`` (uint8[H, W], or
+        None: everywhere) has bit ``l`` set.  ``out``: an array to write the rows into."""
+        positions = np.ascontiguousarray(positions, dtype=np.float32)
+        if positions.size != width * height * 4:
+            raise RtsError(1, "trace_light_list: positions must be W*H*4 floats")
+        if lights_map is not None:
+            lights_map = np.ascontiguousarray(lights_map, dtype=np.uint8)
+            if lights_map.size != width * height:
+                raise RtsError(1, "trace_light_list: lights_map must be W*H bytes")
+        row_end = height if row_end is None else row_end
+        mask = out if out is not None else np.zeros((height, width), dtype=np.uint8)
+        lp = C.byref(lights) if lights is not None else None
+        _check(_lib.rts_trace_light_list(self._h, C.byref(constants), lp, _ptr(positions),
+                                         _ptr(lights_map) if lights_map is not None else None, width, height, row_begin, row_end,
+                                         _ptr(mask)), "rts_trace_light_list")
+        return mask
+
+    def trace_light_list_device(self, constants, lights, d_positions, width, height, d_mask, d_lights_map=None, row_begin=0,
+                                row_end=None, stream=None):
+        """Device pointers, asynchronous: d_mask / d_lights_map = width * height bytes (the map may be None)."""
+        row_end = height if row_end is None else row_end
+        lp = C.byref(lights) if lights is not None else None
+        _check(_lib.rts_trace_light_list_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions), C.c_void_p(d_lights_map or 0),
+                                                width, height, row_begin, row_end, C.c_void_p(d_mask), C.c_void_p(stream or 0)),
+               "rts_trace_light_list_device")
+
+    def trace_light_list_stripes_device(self, constants, lights, d_positions, width, height, d_mask, band_rows, n_stripes, stripe,
+                                        d_lights_map=None, stream=None):
+        """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        lp = C.byref(lights) if lights is not None else None
+        _check(_lib.rts_trace_light_list_stripes_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
+                                                        C.c_void_p(d_lights_map or 0), width, height, band_rows, n_stripes, stripe,
+                                                        C.c_void_p(d_mask), C.c_void_p(stream or 0)),
+               "rts_trace_light_list_stripes_device")
+
     # -- plumbing ---------------------------------------------------------------------------
     def stream_create(self):
         s = C.c_void_p()
@@ -927,6 +1006,46 @@ def soft_distance(packed, constants, light, positions, width, height, active=Non
                                    _ptr(active) if active is not None else None, width, height, row_begin, row_end, _ptr(dist),
                                    _ptr(mask) if mask is not None else None, threads), "rtsh_soft_distance")
     return dist, mask
+
+
+def light_list(packed, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None, threads=0):
+    """A light list trace on the host (rtsh_light_list, no GPU): ``uint8[H, W]``, bit ``l`` = light ``l`` is unoccluded, where
+    ``lights_map`` (None: everywhere) has bit ``l`` set."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    positions = np.ascontiguousarray(positions, np.float32)
+    if positions.size != width * height * 4:
+        raise RtsError(1, "light_list: positions must be W*H*4 floats")
+    if lights_map is not None:
+        lights_map = np.ascontiguousarray(lights_map, np.uint8)
+        if lights_map.size != width * height:
+            raise RtsError(1, "light_list: lights_map must be W*H bytes")
+    row_end = height if row_end is None else row_end
+    mask = out if out is not None else np.zeros((height, width), np.uint8)
+    lp = C.byref(lights) if lights is not None else None
+    _check(_lib.rtsh_light_list(_ptr(packed), packed.shape[0], C.byref(constants), lp, _ptr(positions),
+                                _ptr(lights_map) if lights_map is not None else None, width, height, row_begin, row_end, _ptr(mask),
+                                threads), "rtsh_light_list")
+    return mask
+
+
+def facing_lights(constants, lights, positions, normals):
+    """The light map of a light list on the host (rtsh_facing_lights): ``uint8[H, W]``, bit ``l`` = ``facing_active`` for light ``l``."""
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    lights_map = np.zeros((H, W), np.uint8)
+    lp = C.byref(lights) if lights is not None else None
+    _check(_lib.rtsh_facing_lights(C.byref(constants), lp, _ptr(positions) if positions is not None else None, _ptr(normals),
+                                   W, H, _ptr(lights_map)), "rtsh_facing_lights")
+    return lights_map
+
+
+def facing_lights_device(ctx, constants, lights, d_positions, d_normals, width, height, d_lights_map, stream=None):
+    """The light map on the GPU: device pointers, d_lights_map = width*height bytes, asynchronous."""
+    lp = C.byref(lights) if lights is not None else None
+    _check(_lib.rtsh_facing_lights_device(ctx.handle, C.byref(constants), lp, C.c_void_p(d_positions or 0), C.c_void_p(d_normals),
+                                          width, height, C.c_void_p(d_lights_map), C.c_void_p(stream or 0)),
+           "rtsh_facing_lights_device")
 
 
 def write_ppm(path, rgb):

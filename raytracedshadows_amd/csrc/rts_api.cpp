@@ -5,6 +5,7 @@
 #include "bvh_refit.h"
 #include "rts_device.h"
 #include "rts_soft_distance.h"
+#include "rts_light_list.h"
 #include "rts_dispatch.h"
 #include "rts_refit.h"
 
@@ -40,6 +41,7 @@ struct rts_ctx {
     void* d_dist = nullptr; size_t distBytes = 0;     // staging for the distances of the host-pointer distance traces
     uint64_t distanceTraces = 0;                      // launches of a distance kernel (get-only option "distance_traces")
     uint64_t softDistanceTraces = 0;                  // launches of a soft distance kernel (get-only option "soft_distance_traces")
+    uint64_t lightListTraces = 0;                     // launches of a light list kernel (get-only option "light_list_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
     int packetShare = 4;
@@ -548,6 +550,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "active_traces")) { *value = (int)(c->activeTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "distance_traces")) { *value = (int)(c->distanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_distance_traces")) { *value = (int)(c->softDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "light_list_traces")) { *value = (int)(c->lightListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
     if (!strcmp(key, "tile_order_planned")) { *value = c->tileOrderPlanned ? 1 : 0; return RTS_OK; }
@@ -1030,6 +1033,80 @@ int rts_trace_soft_distance(rts_ctx* c, const rts_constants* k, const rts_light*
     if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 64 ||
                   (light->table && (light->table > 64 || light->table < light->nsamples || light->nsamples < 2)))) return RTS_ERR_INVALID_ARG;
     return traceStagedRows(c, k, light, positions, active, W, row_begin, row_end, distance, mask, true);
+}
+
+// ---- light lists (include/rts.h): up to 8 hard lights in one dispatch, one bit per light in the mask byte ----------------------------
+// One launch of a light list kernel (rts_light_list.inc) with the geometry, the family rule and the launch shape of a distance trace.
+// The list travels in the argument block's 64 sample offsets: light l in offsets[l] = {x, y, z, 0.0f directional / 1.0f point}, the
+// count in nsamples, the map in the active map's slot.  No table, order, follow state or statistic is used or touched.
+static bool lightListOk(const rts_light_list* list) {
+    if (!list || list->count == 0 || list->count > RTS_MAX_LIST_LIGHTS) return false;
+    for (uint32_t l = 0; l < list->count; ++l) if (list->lights[l].type > RTS_LIGHT_POINT) return false;
+    return true;
+}
+
+static int traceLightListImpl(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* d_positions,
+                              const uint8_t* d_lights_map, const Dispatch& g, uint8_t* d_mask, void* stream) {
+    TraceParams p; uint32_t rows = 0; int s;
+    if (beginFrame(c, k, d_positions, d_mask, d_mask && lightListOk(list), g, p, &rows, &s) != Begin::Go) return s;
+    p.activeMap = d_lights_map;
+    const uint64_t pixels = (uint64_t)g.W * rows;
+    int variant = c->variant;
+    if (variant == rts::V_AUTO) variant = pixels < (1u << 18) ? rts::V_SHARE : rts::V_PACKET;
+    else variant = (variant >= rts::V_PACKET && variant != rts::V_SHARE) ? rts::V_PACKET : rts::V_SHARE;
+    s = setBlockGrid(c, p, g, variant);
+    if (s != RTS_OK) return s;
+    for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
+    p.lightType = RTS_LIGHT_DIRECTIONAL;               // (not read: every light carries its own type)
+    p.nsamples = list->count;
+    p.lightTable = 0;
+    for (int i = 0; i < 3; ++i) p.light[i] = 0.0f;
+    for (uint32_t l = 0; l < list->count; ++l) {
+        for (int i = 0; i < 3; ++i) p.offsets[l][i] = list->lights[l].xyz[i];
+        p.offsets[l][3] = list->lights[l].type == RTS_LIGHT_POINT ? 1.0f : 0.0f;
+    }
+    ++c->launches;
+    ++c->lightListTraces;
+    const char* name = "";
+    const hipError_t e = rts::launchShadowLightList(variant, p, (hipStream_t)stream, &name);
+    c->lastKernel = name;
+    return hipStatus(e);
+}
+
+int rts_trace_light_list_device(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* d_positions,
+                                const uint8_t* d_lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                uint8_t* d_mask, void* stream) {
+    return traceLightListImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofRows(W, H, row_begin, row_end), d_mask, stream);
+}
+
+int rts_trace_light_list_stripes_device(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* d_positions,
+                                        const uint8_t* d_lights_map, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes,
+                                        uint32_t stripe, uint8_t* d_mask, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceLightListImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_mask, stream);
+}
+
+// The host form: rows [row_begin, row_end) travel as a frame of their own through the context's staging buffers (the list carries no
+// per-pixel jitter, so the frame index of a pixel plays no part).
+int rts_trace_light_list(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* positions, const uint8_t* lights_map,
+                         uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
+    if (!c || !k || !positions || !mask || W == 0 || H == 0 || row_begin > row_end || row_end > H || !lightListOk(list)) return RTS_ERR_INVALID_ARG;
+    if (!c->d_bvh) return RTS_ERR_NO_BVH;
+    if (row_begin == row_end) return RTS_OK;
+    RTS_HIP(hipSetDevice(c->device));
+    const uint32_t rows = row_end - row_begin;
+    const size_t first = (size_t)row_begin * W, pixels = (size_t)rows * W;
+    int s = ensure(&c->d_in, &c->inBytes, pixels * 16);
+    if (s == RTS_OK) s = ensure(&c->d_out, &c->outBytes, pixels);
+    if (s == RTS_OK && lights_map) s = ensure(&c->d_act, &c->actBytes, pixels);
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(c->d_in, positions + first * 4, pixels * 16, hipMemcpyHostToDevice));
+    if (lights_map) RTS_HIP(hipMemcpy(c->d_act, lights_map + first, pixels, hipMemcpyHostToDevice));
+    s = rts_trace_light_list_device(c, k, list, (const float*)c->d_in, lights_map ? (const uint8_t*)c->d_act : nullptr, W, rows, 0, rows,
+                                    (uint8_t*)c->d_out, nullptr);
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(mask + first, c->d_out, pixels, hipMemcpyDeviceToHost));
+    return RTS_OK;
 }
 
 // Rays (the caller's arguments are checked): occlusion bytes to `out`, or distances to `out_t` where out is NULL.

@@ -151,4 +151,13 @@ RTS_HD uint8_t facingPixel(const CombineParams& c, const float* position4, const
     return facingNdl(c, position4, n) <= 0 ? 0 : 1;
 }
 
+// The light map of a light list (include/rts_scene.h, rtsh_facing_lights): bit l = facingPixel for light l, bits >= count are 0.
+struct FacingLights { uint32_t count; CombineParams light[8]; };
+
+RTS_HD uint8_t facingLightsPixel(const FacingLights& f, const float* position4, const float* normal4) {
+    uint32_t bits = 0;
+    for (uint32_t l = 0; l < f.count; ++l) bits |= (uint32_t)facingPixel(f.light[l], position4, normal4) << l;
+    return (uint8_t)bits;
+}
+
 } // namespace rts_harness

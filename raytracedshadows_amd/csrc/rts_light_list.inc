@@ -1,0 +1,184 @@
+// LIGHT LISTS (rts_trace_light_list*, include/rts.h): included at the end of rts_soft_distance.inc -- so by rts_kernels.hip, inside
+// namespace rts, after every other kernel -- it adds kernels and changes none.
+//
+// Up to 8 hard lights in one dispatch: bit l of mask[p] = the byte the mask trace writes at p for light l alone, where bit l of the
+// pixel's byte of the light map is set (no map: everywhere), else 0.  p.nsamples is the number of lights, light l travels in
+// p.offsets[l] = {x, y, z, 0.0f directional / 1.0f point}, the map in p.activeMap.  A bit is a function of (pixel, light) alone, and
+// bits are joined by an integer OR -- associative, commutative, idempotent --, so the byte does not depend on the order the lights
+// are walked in, nor on which wave walked which: the 4-wave form ORs the waves' bytes in LDS (DESIGN.md 4.14).
+
+// The ray of (pixel, light l), bit for bit the ray makeShadowRay sets up for the hard light {type, 1 sample, xyz} alone: its general
+// set-up restated with the light taken from p.offsets[l] AS GIVEN (a light is not carried as p.light + offsets[j]: 0 + (-0) is +0, and
+// a directional light's d is the light itself).  The general set-up and makeShadowRay's fast path give the same bits wherever both
+// apply (tests/test_ray_setup.py), and so do rcpFast and the division in rcpFast's range; the choices between them are made per wave.
+__device__ __forceinline__ Ray makeListRay(const TraceParams& p, F3 rel, uint32_t l) {
+    const F3 L{ p.offsets[l][0], p.offsets[l][1], p.offsets[l][2] };
+    F3 origin{ p.cam[0] + rel.x, p.cam[1] + rel.y, p.cam[2] + rel.z };
+    float mo = gmax(gmax(__builtin_fabsf(origin.x), __builtin_fabsf(origin.y)), __builtin_fabsf(origin.z));
+    float mr = gmax(gmax(__builtin_fabsf(rel.x), __builtin_fabsf(rel.y)), __builtin_fabsf(rel.z));
+    float bias = gmax(epsilonFor(mo, 13), epsilonFor(mr, 13));
+    Ray r;
+    if (p.offsets[l][3] == 0.0f) {                                       // (wave-uniform: l is)
+        origin.x = origin.x + L.x * bias; origin.y = origin.y + L.y * bias; origin.z = origin.z + L.z * bias;
+        r.o = origin; r.tmax = 1e9f; r.d = L;
+    } else {
+        F3 d0 = sub3(L, origin);
+        const float len = __builtin_sqrtf(dot3(d0, d0));
+        float inv;
+        if (__builtin_amdgcn_ballot_w64(!rcpInRange(len)) == 0) inv = rcpFast(len); else inv = 1.0f / len;
+        origin.x = origin.x + (d0.x * inv) * bias; origin.y = origin.y + (d0.y * inv) * bias;
+        origin.z = origin.z + (d0.z * inv) * bias;
+        r.o = origin; r.tmax = 1.0f; r.d = sub3(L, origin);
+    }
+    if (__builtin_amdgcn_ballot_w64(!(rcpInRange(r.d.x) && rcpInRange(r.d.y) && rcpInRange(r.d.z))) == 0)
+        r.inv = F3{ rcpFast(r.d.x), rcpFast(r.d.y), rcpFast(r.d.z) };
+    else
+        r.inv = F3{ 1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z };   // comp:77
+    return r;
+}
+
+// What a lane knows of its pixel.  bits: the lights that send a ray from it -- the map's byte (0xFF without a map) below bit
+// p.nsamples, 0 where the lane owns no pixel; pix is only looked at where the lane owns one.
+struct ListPixel { bool owns; uint32_t pix; uint32_t bits; F3 rel; };
+
+// The texel and the map's byte are requested in one batch (softDistancePrologue).  -> false: no pixel of the wave's tile has a bit
+// below p.nsamples; the zeros are stored (`stores`: in the 4-wave form every wave looks at the same tile and only wave 0 writes it)
+// and the wave leaves before the stream is opened.  The same answer in the four waves of a tile.
+__device__ __forceinline__ bool lightListPrologue(const TraceParams& p, bool owns, uint32_t pix, bool stores, ListPixel* d) {
+    // (no branch around the requests: a lane without a pixel asks for texel 0 and byte 0 and never looks at them)
+    const f32x4 t = __builtin_nontemporal_load((const f32x4*)p.positions + (owns ? pix : 0u));          // comp:135
+    uint32_t byte = 0xFFu;
+    if (p.activeMap) byte = __builtin_nontemporal_load(p.activeMap + (owns ? pix : 0u));
+    d->owns = owns;
+    d->pix = pix;
+    d->bits = owns ? (byte & ((1u << p.nsamples) - 1u)) : 0u;            // (p.nsamples <= 8; bits >= count are 0 whatever the map holds)
+    d->rel = F3{ t.x, t.y, t.z };
+    if (__builtin_amdgcn_ballot_w64(d->bits != 0u) != 0) return true;
+    if (owns && stores) __builtin_nontemporal_store((uint8_t)0, &p.mask[pix]);
+    return false;
+}
+
+// Lanes that do not walk light l take the texel of the first lane that does (the stand-in of rts_packet_tile.inc): exact, because
+// their result is discarded, and it keeps the wave-wide gates of the ray set-up on real rays -- a background texel or the garbage an
+// unmarked pixel may hold would send the whole wave down the slow forms.
+__device__ __forceinline__ F3 listStandIn(F3 rel, bool walks, uint64_t walkers) {
+    const int firstWalker = __builtin_ctzll(walkers);
+    const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel.x), firstWalker));
+    const float sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel.y), firstWalker));
+    const float sz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel.z), firstWalker));
+    return walks ? rel : F3{ sx, sy, sz };
+}
+
+// Lane per ray: shadowMaskActiveShareKernel's 16 x 16 block, the lights one after the other around traverseShare.  The four waves
+// share nothing but the LDS each owns a quarter of, so each decides for itself.
+__global__ __launch_bounds__(256) void shadowLightListShareKernel(TraceParams p) {
+    __shared__ uint32_t shareSlots[4][64];       // lane numbers exchanged by traverseShare (256 B per wave)
+    uint32_t* lds = shareSlots[threadIdx.x >> 6];
+    uint32_t bx, by;
+    if (!blockToXY(p, blockIdx.x, &bx, &by)) return;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t x = bx * 16u + (wave & 1u) * 8u + (lane & 7u);
+    const uint32_t y = ownedRow(p, by * 16u + (wave >> 1) * 8u + (lane >> 3));
+    ListPixel d;
+    if (!lightListPrologue(p, (x < p.W) && (y < p.rowEnd), y * p.W + x, true, &d)) return;
+    const NodeStream bvh = openStream(p);
+    uint32_t byte = 0;
+    for (uint32_t l = 0; l < p.nsamples; ++l) {
+        const bool walks = ((d.bits >> l) & 1u) != 0u;
+        const uint64_t walkers = __builtin_amdgcn_ballot_w64(walks);
+        if (walkers == 0) continue;                                      // the cull's gain: no ray of this light is set up
+        const Ray r = makeListRay(p, listStandIn(d.rel, walks, walkers), l);
+        const bool unsafe = walks && !raySafe(r);
+        bool occluded;
+        if (p.bvhFinite && __builtin_amdgcn_ballot_w64(unsafe) == 0)
+            occluded = traverseShare<true>(bvh, r, walks, 0u, lds);
+        else
+            occluded = traverseShare<false>(bvh, r, walks, 0u, lds);
+        byte |= (walks && !occluded) ? (1u << l) : 0u;                   // comp:148, as light l's bit
+    }
+    if (d.owns) __builtin_nontemporal_store((uint8_t)byte, &p.mask[d.pix]);   // comp:150
+}
+
+// Stackless packet over 8 x 8 tiles, traversePacket<1, false> once per light (any-hit, the early-out kept).  GEOM as in
+// shadowSoftDistancePacketKernel (1: a row range on a 2-D grid, 2: one stripe of power-of-two bands, 0: every other geometry).
+// SPLIT 1: one wave walks every light.  SPLIT 4: four waves per tile, wave w takes the lights w and w + 4; each wave keeps its byte
+// in an LDS word of its own per lane, and after ONE workgroup barrier wave 0 ORs the four words and stores.  Every wave reaches
+// that barrier or none does: the only exits in front of it (a block outside the dispatch, a tile with no bit below the count in any
+// pixel) depend on the tile alone, which the four waves share; a wave that owns no light, or whose lights have no pixel in the
+// tile, runs no walk and contributes 0.
+template <int SPLIT, int GEOM>
+__global__ __launch_bounds__(64 * SPLIT) __attribute__((amdgpu_waves_per_eu(8)))
+void shadowLightListPacketKernel(TraceParams p) {
+    static_assert(SPLIT == 1 || SPLIT == 4, "one wave per tile, or four that deal its lights");
+    __shared__ uint32_t shareSlots[SPLIT][64];
+    __shared__ uint32_t partial[SPLIT][64];                              // per wave: its lights' bits per lane
+    uint32_t bx = blockIdx.x, by = 0;
+    if constexpr (GEOM == 0) { if (!blockToXY(p, blockIdx.x, &bx, &by)) return; }
+    else by = dispatchRow(p, blockIdx.y);
+    // (the wave's number is wave-uniform: said so, the light counter and the wave's LDS addresses stay on the scalar unit)
+    const uint32_t lane = threadIdx.x & 63u, wave = SPLIT > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
+    const uint32_t x = bx * 8u + (lane & 7u);
+    uint32_t y;
+    if constexpr (GEOM == 2) {
+        const uint32_t band = by >> p.bandShift, within = by - (band << p.bandShift);
+        y = (band * p.nStripes + p.stripe) * p.bandRows + within * 8u + (lane >> 3);
+    } else if constexpr (GEOM == 1) y = p.rowBegin + by * 8u + (lane >> 3);
+    else y = ownedRow(p, by * 8u + (lane >> 3));
+    ListPixel d;
+    if (!lightListPrologue(p, (x < p.W) && (y < p.rowEnd), y * p.W + x, wave == 0, &d)) return;
+    const NodeStream bvh = openStream(p);
+    // (LDS is addressed by laneId(), the number the walks themselves keep; the byte lives there, not in a register across the walk)
+    uint32_t* const mine = &partial[wave][laneId()];
+    *mine = 0;
+    for (uint32_t l = wave; l < p.nsamples; l += SPLIT) {
+        const bool walks[1] = { ((d.bits >> l) & 1u) != 0u };
+        const uint64_t walkers = __builtin_amdgcn_ballot_w64(walks[0]);
+        if (walkers == 0) continue;                                      // the cull's gain, wave-uniform: no ray of this light is set up
+        F3 rel = listStandIn(d.rel, walks[0], walkers);
+        // (made opaque per light: otherwise the compiler hoists the light-independent half of the set-up out of the loop and keeps
+        //  it in registers across the walk -- rts_soft_distance.inc)
+        asm volatile("" : "+v"(rel.x), "+v"(rel.y), "+v"(rel.z));
+        const Ray r[1] = { makeListRay(p, rel, l) };
+        bool occluded[1];
+        traversePacket<1, false>(p, bvh, r, walks, occluded, shareSlots[wave]);
+        *mine |= (walks[0] && !occluded[0]) ? (1u << l) : 0u;            // comp:148, as light l's bit
+    }
+    uint32_t byte;
+    if constexpr (SPLIT > 1) {
+        __syncthreads();
+        if (wave != 0) return;
+        const uint32_t ln = laneId();
+        byte = 0;
+#pragma unroll
+        for (int w = 0; w < SPLIT; ++w) byte |= partial[w][ln];
+    } else byte = *mine;
+    if (d.owns) __builtin_nontemporal_store((uint8_t)byte, &p.mask[d.pix]);   // comp:150
+}
+
+template <int SPLIT>
+static hipError_t launchLightListPacket(const TraceParams& p, dim3 grid, hipStream_t stream, const char** name) {
+    if (p.grid2d && p.nStripes > 1 && p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0) {
+        *name = SPLIT == 4 ? "shadowLightListPacketKernel<4,bands>" : "shadowLightListPacketKernel<1,bands>";
+        hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 2>), grid, dim3(64 * SPLIT), 0, stream, p);
+    } else if (p.grid2d && p.nStripes <= 1) {
+        *name = SPLIT == 4 ? "shadowLightListPacketKernel<4,rows>" : "shadowLightListPacketKernel<1,rows>";
+        hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 1>), grid, dim3(64 * SPLIT), 0, stream, p);
+    } else {
+        *name = SPLIT == 4 ? "shadowLightListPacketKernel<4,general>" : "shadowLightListPacketKernel<1,general>";
+        hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 0>), grid, dim3(64 * SPLIT), 0, stream, p);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launchShadowLightList(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
+    if (!p.mask || p.nsamples < 1 || p.nsamples > 8) return hipErrorInvalidValue;
+    dim3 grid(p.gridBlocks);
+    if (p.grid2d) grid = dim3(p.blocksX, p.blocksY);
+    if (variant == V_SHARE) {
+        *name = "shadowLightListShareKernel";
+        hipLaunchKernelGGL(shadowLightListShareKernel, grid, dim3(256), 0, stream, p);
+        return hipGetLastError();
+    }
+    if (variant != V_PACKET) return hipErrorInvalidValue;
+    return p.softSplit ? launchLightListPacket<4>(p, grid, stream, name) : launchLightListPacket<1>(p, grid, stream, name);
+}

@@ -68,6 +68,17 @@ __global__ __launch_bounds__(256) void facingKernel(CombineParams c, const float
     const float zero[4] = { 0.f, 0.f, 0.f, 0.f };
     active[i] = facingPixel(c, positions ? positions + i * 4 : zero, normals + i * 4);
 }
+
+int makeFacingLights(const rts_constants* k, const rts_light_list* list, bool havePositions, FacingLights* out);
+
+// The light map of a light list (rts_closest_hit.h: facingLightsPixel), one pixel per lane like facingKernel.
+__global__ __launch_bounds__(256) void facingLightsKernel(FacingLights f, const float* positions, const float* normals, uint64_t n,
+                                                          uint8_t* lightsMap) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float zero[4] = { 0.f, 0.f, 0.f, 0.f };
+    lightsMap[i] = facingLightsPixel(f, positions ? positions + i * 4 : zero, normals + i * 4);
+}
 } // namespace rts_harness
 
 extern "C" const void* rts_ctx_device_bvh(rts_ctx* ctx);   // rts_api.cpp
@@ -100,6 +111,21 @@ extern "C" int rtsh_facing_active_device(rts_ctx* ctx, const rts_constants* k, c
     const uint64_t n = (uint64_t)W * H;
     hipLaunchKernelGGL(rts_harness::facingKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c,
                        d_positions, d_normals, n, d_active);
+    e = hipGetLastError();
+    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+}
+
+extern "C" int rtsh_facing_lights_device(rts_ctx* ctx, const rts_constants* k, const rts_light_list* list, const float* d_positions,
+                                         const float* d_normals, uint32_t W, uint32_t H, uint8_t* d_lights_map, void* stream) {
+    if (!ctx || !d_normals || !d_lights_map || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    rts_harness::FacingLights f;
+    int s = rts_harness::makeFacingLights(k, list, d_positions != nullptr, &f);
+    if (s != RTS_OK) return s;
+    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
+    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
+    const uint64_t n = (uint64_t)W * H;
+    hipLaunchKernelGGL(rts_harness::facingLightsKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f,
+                       d_positions, d_normals, n, d_lights_map);
     e = hipGetLastError();
     return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
 }

@@ -302,3 +302,69 @@ extern "C" int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, co
     });
     return RTS_OK;
 }
+
+// ---- light lists on the host (include/rts_scene.h): the checker of rts_trace_light_list*, and the light map of a deferred renderer ----
+// The definition of include/rts.h as a straight loop over (pixel, light): light l's ray and one-ray distance as rtsh_shadow_distance
+// takes them for that light alone, its bit set where the distance is +Inf.
+namespace rts_harness {
+bool lightListOk(const rts_light_list* list) {
+    if (!list || list->count == 0 || list->count > RTS_MAX_LIST_LIGHTS) return false;
+    for (uint32_t l = 0; l < list->count; ++l) if (list->lights[l].type > RTS_LIGHT_POINT) return false;
+    return true;
+}
+
+// Shared by the host and device facing passes: one CombineParams per light, as makeCombineParams condenses that light alone.
+int makeFacingLights(const rts_constants* k, const rts_light_list* list, bool havePositions, FacingLights* out) {
+    if (!k || !out || !lightListOk(list)) return RTS_ERR_INVALID_ARG;
+    out->count = list->count;
+    for (uint32_t l = 0; l < list->count; ++l) {
+        rts_light one;
+        memset(&one, 0, sizeof(one));
+        one.type = list->lights[l].type;
+        one.nsamples = 1;
+        for (int i = 0; i < 3; ++i) one.xyz[i] = list->lights[l].xyz[i];
+        const int s = makeCombineParams(k, &one, havePositions, &out->light[l]);
+        if (s != RTS_OK) return s;
+    }
+    return RTS_OK;
+}
+} // namespace rts_harness
+
+extern "C" int rtsh_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_light_list* list,
+                               const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                               uint32_t row_end, uint8_t* mask, int threads) {
+    if (!packed || !k || !positions || !mask || W == 0 || H == 0 || row_begin > row_end || row_end > H || !lightListOk(list))
+        return RTS_ERR_INVALID_ARG;
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t below = (1u << list->count) - 1u;
+    const size_t first = (size_t)row_begin * W;
+    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t n) {
+        const size_t i = first + n;
+        const uint32_t bits = (lights_map ? lights_map[i] : 0xFFu) & below;
+        uint32_t byte = 0;
+        if (bits) {
+            const float* q = positions + i * 4;
+            for (uint32_t l = 0; l < list->count; ++l) {
+                if (!((bits >> l) & 1u)) continue;
+                const rts_light_entry& e = list->lights[l];
+                const uint32_t one = rayDistanceBits(bvh, shadowRay(k->cameraPosition, V3{ q[0], q[1], q[2] }, e.type, V3{ e.xyz[0], e.xyz[1], e.xyz[2] }));
+                byte |= one == 0x7F800000u ? 1u << l : 0u;                 // comp:148, as light l's bit
+            }
+        }
+        mask[i] = (uint8_t)byte;                                          // comp:150
+    });
+    return RTS_OK;
+}
+
+extern "C" int rtsh_facing_lights(const rts_constants* k, const rts_light_list* list, const float* positions, const float* normals,
+                                  uint32_t W, uint32_t H, uint8_t* lights_map) {
+    if (!normals || !lights_map || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    FacingLights f;
+    const int s = makeFacingLights(k, list, positions != nullptr, &f);
+    if (s != RTS_OK) return s;
+    const float zero[4] = { 0, 0, 0, 0 };
+    for (size_t i = 0; i < (size_t)W * H; ++i) lights_map[i] = facingLightsPixel(f, positions ? positions + i * 4 : zero, normals + i * 4);
+    return RTS_OK;
+}

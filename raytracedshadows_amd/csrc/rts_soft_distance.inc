@@ -163,3 +163,6 @@ hipError_t launchShadowSoftDistance(int variant, const TraceParams& p, hipStream
     if (variant != V_PACKET) return hipErrorInvalidValue;
     return p.softSplit ? launchSoftDistancePacket<4>(p, grid, stream, name) : launchSoftDistancePacket<1>(p, grid, stream, name);
 }
+
+// light lists: up to 8 hard lights in one dispatch, one bit per light (its launch is declared in rts_light_list.h)
+#include "rts_light_list.inc"

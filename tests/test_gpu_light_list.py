@@ -1,0 +1,600 @@
+"""GPU: light list traces (rts_trace_light_list*; include/rts.h) against the host twin (rtsh_light_list, which
+tests/test_light_list_host.py pins to the oracle), byte for byte, on guard-filled buffers: every list in both kernel families and both
+splits, light maps (the facing map made on the device, poisoned unmarked pixels, empty tiles and blocks, a light with no pixel or a
+single one), row ranges and stripes, options that may only change speed, installed state that must stay, the counters and kernel
+names, graph capture, the refusals, and the smallest stream."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import hipgraph
+from light_list_cases import FRAMES, LISTS, list_frame, make_list
+from raytracedshadows_amd import api, workloads
+
+pytestmark = pytest.mark.gpu
+
+GUARD = 0xAB
+SHARE = "shadowLightListShareKernel"
+FORMS = [(7, 1), (3, 1), (3, 0)]                        # ("kernel", "soft_split"); under 7 the split plays no part
+POISON = np.array([np.nan, np.inf, 1e38, -np.inf], np.float32)
+
+
+def _name(kernel, split, geom="rows"):
+    return SHARE if kernel in (0, 1, 2, 7) else "shadowLightListPacketKernel<%d,%s>" % (4 if split else 1, geom)
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = api.ShadowContext(0)
+    yield c
+    c.close()
+
+
+def _reset(ctx):
+    for key, v in (("kernel", -1), ("soft_split", 1), ("xcd_swizzle", 0), ("row_order", 0)):
+        ctx.set_option(key, v)
+
+
+class _Dev:
+    def __init__(self, ctx, positions, W, H):
+        self.ctx, self.W, self.H = ctx, W, H
+        positions = np.ascontiguousarray(positions, np.float32)
+        self.d_pos, self.d_map, self.d_mask = ctx.malloc(positions.nbytes), ctx.malloc(W * H), ctx.malloc(W * H)
+        ctx.h2d(self.d_pos, positions)
+
+    def guard(self):
+        self.ctx.h2d(self.d_mask, np.full(self.W * self.H, GUARD, np.uint8))
+
+    def read(self, stream=None, what=None):
+        m = np.empty((self.H, self.W), np.uint8)
+        self.ctx.synchronize(stream)
+        self.ctx.d2h(m, self.d_mask if what is None else what)
+        return m
+
+    def close(self):
+        for d in (self.d_pos, self.d_map, self.d_mask):
+            self.ctx.free(d)
+
+
+def _expect(want, lights_map=None, rows=None):
+    m = want if lights_map is None else want & lights_map
+    return m if rows is None else np.where(rows[:, None], m, GUARD).astype(np.uint8)
+
+
+def _same(got, want, what):
+    bad = np.argwhere(got != want)
+    assert bad.shape[0] == 0, (what, bad.shape[0], bad[:4].tolist(), [got[tuple(b)] for b in bad[:4]], [want[tuple(b)] for b in bad[:4]])
+
+
+def _trace(ctx, dev, fr, lights, want, what, lights_map=None, rows=None, **kw):
+    if lights_map is not None:
+        ctx.h2d(dev.d_map, np.ascontiguousarray(lights_map, np.uint8))
+    dev.guard()
+    ctx.trace_light_list_device(fr.k, lights, dev.d_pos, fr.W, fr.H, dev.d_mask, d_lights_map=dev.d_map if lights_map is not None else None, **kw)
+    _same(dev.read(), _expect(want, lights_map, rows), what)
+
+
+# ---- 1. parity ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("W,H", FRAMES)
+@pytest.mark.parametrize("name", list(LISTS))
+def test_every_list_family_and_split_equals_the_twin(ctx, name, W, H):
+    fr = list_frame(W, H)
+    lights, want = make_list(name), fr.want(name)
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, W, H)
+    try:
+        for kernel, split in FORMS:
+            ctx.set_option("kernel", kernel)
+            ctx.set_option("soft_split", split)
+            _trace(ctx, dev, fr, lights, want, (name, kernel, split))
+            assert ctx.last_kernel_name() == _name(kernel, split), (kernel, split, ctx.last_kernel_name())
+        # the host form: its rows alone travel
+        out = np.full((H, W), GUARD, np.uint8)
+        ctx.trace_light_list(fr.k, lights, fr.pos, W, H, row_begin=3, row_end=30, out=out)
+        rows = (np.arange(H) >= 3) & (np.arange(H) < 30)
+        _same(out, _expect(want, None, rows), (name, "host rows"))
+    finally:
+        _reset(ctx)
+        dev.close()
+
+
+def test_auto_takes_the_lane_walk_below_256k_pixels(ctx):
+    fr = list_frame(61, 37)
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    try:
+        assert ctx.get_option("kernel") == -1
+        _trace(ctx, dev, fr, make_list("3"), fr.want("3"), "defaults")
+        assert ctx.last_kernel_name() == SHARE
+    finally:
+        dev.close()
+
+
+# ---- 2. the map -----------------------------------------------------------------------------------------------------------------
+def _maps(fr, count):
+    y, x = np.mgrid[0:fr.H, 0:fr.W]
+    below = (1 << count) - 1
+    mixed = ((x * 7 + y * 13 + (x >> 3) * 5) & 0xFF).astype(np.uint8)
+    mixed[(x + y) % 5 == 0] = 0
+    holes = np.full((fr.H, fr.W), 0xFF, np.uint8)
+    holes[8:16, 16:24] = 0                               # an 8 x 8 tile
+    holes[16:32, 32:48] = 0                              # a 16 x 16 block
+    holes[0:8, 0:8] = 0xFF & ~below                      # a tile whose bytes have bits, but none below the count
+    absent = np.full((fr.H, fr.W), 0xFF, np.uint8) & ~np.uint8(1 << (count - 1))     # the last light has no pixel anywhere
+    single = absent.copy()
+    single[21, 34] |= 1 << (count - 1)                   # ... or a single one, in the middle of its tile
+    lone = np.zeros((fr.H, fr.W), np.uint8)
+    lone[21, 34] = 1                                     # one pixel of one light in the whole frame: every other lane stands in
+    return {"mixed": mixed, "holes": holes, "absent": absent, "single": single, "lone": lone, "full": np.full((fr.H, fr.W), 0xFF, np.uint8),
+            "zeros": np.zeros((fr.H, fr.W), np.uint8)}
+
+
+@pytest.mark.parametrize("kernel,split", FORMS)
+@pytest.mark.parametrize("name", ["3", "8"])
+def test_light_maps(ctx, name, kernel, split):
+    fr = list_frame(64, 48)
+    lights, want = make_list(name), fr.want(name)
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    below = (1 << lights.count) - 1
+    try:
+        ctx.set_option("kernel", kernel)
+        ctx.set_option("soft_split", split)
+        for what, m in _maps(fr, lights.count).items():
+            dirty = fr.pos.copy()                        # a pixel no light is marked for may hold anything
+            dirty[(m & below) == 0] = POISON
+            ctx.h2d(dev.d_pos, dirty)
+            _trace(ctx, dev, fr, lights, want, (name, kernel, split, what), lights_map=m)
+            got = dev.read()
+            assert (got >> lights.count == 0).all(), what                   # bits >= count are 0 whatever the map holds
+            if what == "full":                           # NULL equals a map of 0xFF
+                _trace(ctx, dev, fr, lights, want, (name, kernel, split, "NULL"))
+                _same(dev.read(), got, "NULL against 0xFF")
+    finally:
+        _reset(ctx)
+        dev.close()
+
+
+@pytest.mark.parametrize("W,H", FRAMES)
+def test_the_facing_map_made_on_the_device(ctx, W, H):
+    fr = list_frame(W, H)
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, W, H)
+    d_nrm = ctx.malloc(fr.nrm.nbytes)
+    try:
+        ctx.h2d(d_nrm, fr.nrm)
+        for name in ("2", "5", "8"):
+            lights, host_map = make_list(name), fr.facing(name)
+            ctx.h2d(dev.d_map, np.full(W * H, GUARD, np.uint8))
+            api.facing_lights_device(ctx, fr.k, lights, dev.d_pos, d_nrm, W, H, dev.d_map)
+            _same(dev.read(what=dev.d_map), host_map, (name, "device map against host map"))
+            assert 0 < int((host_map != 0).sum()) < host_map.size
+            for kernel, split in FORMS:
+                ctx.set_option("kernel", kernel)
+                ctx.set_option("soft_split", split)
+                dev.guard()
+                ctx.trace_light_list_device(fr.k, lights, dev.d_pos, W, H, dev.d_mask, d_lights_map=dev.d_map)
+                _same(dev.read(), fr.want(name) & host_map, (name, kernel, split, "facing"))
+    finally:
+        _reset(ctx)
+        ctx.free(d_nrm)
+        dev.close()
+
+
+# ---- 3. geometry ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kernel,split", FORMS)
+def test_row_ranges_leave_the_other_rows(ctx, kernel, split):
+    fr = list_frame(64, 48)
+    lights, want = make_list("4"), fr.want("4")
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    m = _maps(fr, 4)["mixed"]
+    try:
+        ctx.set_option("kernel", kernel)
+        ctx.set_option("soft_split", split)
+        for b, e in ((8, 40), (16, 32), (5, 41)):
+            rows = (np.arange(fr.H) >= b) & (np.arange(fr.H) < e)
+            _trace(ctx, dev, fr, lights, want, (kernel, split, b, e), rows=rows, row_begin=b, row_end=e)
+            _trace(ctx, dev, fr, lights, want, (kernel, split, b, e, "map"), lights_map=m, rows=rows, row_begin=b, row_end=e)
+        n0 = ctx.get_option("light_list_traces")
+        _trace(ctx, dev, fr, lights, want, "empty range", rows=np.zeros(fr.H, bool), row_begin=7, row_end=7)
+        assert ctx.get_option("light_list_traces") == n0
+    finally:
+        _reset(ctx)
+        dev.close()
+
+
+@pytest.mark.parametrize("kernel,split,band", [(3, 1, 8), (3, 1, 16), (3, 0, 8), (3, 0, 16), (7, 1, 16)])
+def test_stripes(ctx, kernel, split, band):
+    fr = list_frame(61, 37)
+    lights, want = make_list("5"), fr.want("5")
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    m = _maps(fr, 5)["mixed"]
+    ctx.h2d(dev.d_map, m)
+    try:
+        ctx.set_option("kernel", kernel)
+        ctx.set_option("soft_split", split)
+        for with_map in (False, True):
+            for stripe in range(3):                      # (37 rows in bands of 16: stripe 2 owns band 2, rows 32..36)
+                rows = ((np.arange(fr.H) // band) % 3) == stripe
+                dev.guard()
+                ctx.trace_light_list_stripes_device(fr.k, lights, dev.d_pos, fr.W, fr.H, dev.d_mask, band, 3, stripe,
+                                                    d_lights_map=dev.d_map if with_map else None)
+                _same(dev.read(), _expect(want, m if with_map else None, rows), (kernel, split, band, with_map, stripe))
+                assert ctx.last_kernel_name() == _name(kernel, split, "bands"), ctx.last_kernel_name()
+        # a stripe that owns no band launches nothing, writes nothing and returns OK (37 rows in bands of 16: bands 0..2, stripe 3 of 4)
+        n0 = ctx.get_option("light_list_traces")
+        dev.guard()
+        ctx.trace_light_list_stripes_device(fr.k, lights, dev.d_pos, fr.W, fr.H, dev.d_mask, 16, 4, 3)
+        assert (dev.read() == GUARD).all() and ctx.get_option("light_list_traces") == n0
+        if kernel == 3:                                  # 24 rows: not a power of two -- the general form
+            rows = ((np.arange(fr.H) // 24) % 2) == 1
+            dev.guard()
+            ctx.trace_light_list_stripes_device(fr.k, lights, dev.d_pos, fr.W, fr.H, dev.d_mask, 24, 2, 1)
+            _same(dev.read(), _expect(want, None, rows), (kernel, split, 24))
+            assert ctx.last_kernel_name() == _name(kernel, split, "general")
+    finally:
+        _reset(ctx)
+        dev.close()
+
+
+def test_a_band_of_8_under_the_lane_walk_is_refused_as_the_distance_trace_refuses_it(ctx):
+    fr = list_frame(61, 37)
+    lights = make_list("2")
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    d_dist = ctx.malloc(fr.W * fr.H * 4)
+    try:
+        ctx.set_option("kernel", 7)
+        with pytest.raises(api.RtsError) as dist:
+            ctx.trace_shadow_distance_stripes_device(fr.k, dev.d_pos, fr.W, fr.H, d_dist, 8, 2, 0, light=lights.light(1))
+        dev.guard()
+        n0 = ctx.get_option("light_list_traces")
+        with pytest.raises(api.RtsError) as mine:
+            ctx.trace_light_list_stripes_device(fr.k, lights, dev.d_pos, fr.W, fr.H, dev.d_mask, 8, 2, 0)
+        assert mine.value.status == dist.value.status == 1
+        assert (dev.read() == GUARD).all() and ctx.get_option("light_list_traces") == n0
+    finally:
+        _reset(ctx)
+        ctx.free(d_dist)
+        dev.close()
+
+
+@pytest.mark.parametrize("kernel,split", FORMS)
+def test_the_general_grid_and_the_row_orders(ctx, kernel, split):
+    fr = list_frame(61, 37)
+    lights, want = make_list("8"), fr.want("8")
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    m = _maps(fr, 8)["mixed"]
+    try:
+        ctx.set_option("kernel", kernel)
+        ctx.set_option("soft_split", split)
+        ctx.set_option("xcd_swizzle", 1)
+        _trace(ctx, dev, fr, lights, want, (kernel, split, "swizzle"), lights_map=m)
+        assert ctx.last_kernel_name() == _name(kernel, split, "general")
+        rows = (np.arange(fr.H) >= 5) & (np.arange(fr.H) < 30)
+        _trace(ctx, dev, fr, lights, want, (kernel, split, "swizzle rows"), rows=rows, row_begin=5, row_end=30)
+        ctx.set_option("xcd_swizzle", 0)
+        for order in (1, 2):
+            ctx.set_option("row_order", order)
+            _trace(ctx, dev, fr, lights, want, (kernel, split, "row_order", order), lights_map=m)
+            assert ctx.last_kernel_name() == _name(kernel, split, "rows")
+    finally:
+        _reset(ctx)
+        dev.close()
+
+
+# ---- 4. options change no byte --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("split", [1, 0])
+def test_options_change_no_byte(ctx, split):
+    fr = list_frame(64, 48)
+    lights, want = make_list("8"), fr.want("8")
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    before = (ctx.get_option("packet_budget"), ctx.get_option("packet_share"))
+    m = _maps(fr, 8)["mixed"]
+    try:
+        ctx.set_option("soft_split", split)
+        ctx.set_option("kernel", 3)
+        ctx.set_option("packet_budget", 1)               # every packet dissolves at once
+        ctx.set_option("packet_share", 16)
+        _trace(ctx, dev, fr, lights, want, ("dissolve", split))
+        _trace(ctx, dev, fr, lights, want, ("dissolve", split, "map"), lights_map=m)
+        ctx.set_option("packet_budget", before[0])
+        ctx.set_option("packet_share", before[1])
+        ctx.set_option("kernel", 8)                      # the stream has a private copy; a list trace runs the stackless packet all the same
+        assert ctx.get_option("wide_nodes") > 0
+        _trace(ctx, dev, fr, lights, want, ("kernel 8", split), lights_map=m)
+        assert ctx.last_kernel_name() == _name(3, split)
+        ctx.set_option("kernel", 9)
+        _trace(ctx, dev, fr, lights, want, ("kernel 9", split))
+        assert ctx.last_kernel_name() == _name(3, split)
+    finally:
+        ctx.set_option("packet_budget", before[0])
+        ctx.set_option("packet_share", before[1])
+        _reset(ctx)
+        dev.close()
+
+
+# ---- 5. installed state stays ---------------------------------------------------------------------------------------------------
+def test_installed_state_stays(ctx):
+    wl = workloads.prepare_config("cornell_256")
+    W, H = wl.W, wl.H
+    lights = api.LightList.make([wl.light, (api.Light.DIRECTIONAL, list(wl.scene.light_direction))])
+    want = api.light_list(wl.packed, wl.constants, lights, wl.positions, W, H)
+    plain = want & 1                                     # light 0 is the workload's own: the plain trace's byte
+    assert 0 < int(plain.sum()) < plain.size
+    ctx.set_bvh(wl.packed)
+    dev = _Dev(ctx, wl.positions, W, H)
+
+    def list_trace():
+        n0 = ctx.get_option("light_list_traces")
+        dev.guard()
+        ctx.trace_light_list_device(wl.constants, lights, dev.d_pos, W, H, dev.d_mask)
+        _same(dev.read(), want, "list")
+        assert ctx.get_option("light_list_traces") == n0 + 1 and ctx.last_kernel_name() == _name(3, 1)
+
+    def plain_trace():
+        dev.guard()
+        ctx.trace_shadow_mask_device(wl.constants, dev.d_pos, W, H, dev.d_mask, light=wl.light)
+        _same(dev.read(), plain, "plain")
+        return ctx.last_kernel_name()
+
+    try:
+        ctx.set_option("kernel", 3)
+        # a split table
+        tiles, records = ctx.plan_splits(wl.constants, dev.d_pos, W, H, dev.d_mask, light=wl.light, min_life_us=4.0, piece_us=2.0,
+                                         max_pieces=8, front_share=1.0 / 3.0)
+        assert tiles > 0
+        table = tuple(ctx.get_option(k) for k in ("split_tiles", "front_tiles", "split_pieces"))
+        name_before = plain_trace()
+        list_trace()
+        assert tuple(ctx.get_option(k) for k in ("split_tiles", "front_tiles", "split_pieces")) == table
+        assert plain_trace() == name_before
+        ctx.clear_splits()
+        # a caller's tile order
+        order = np.arange(((W + 7) // 8) * ((H + 7) // 8), dtype=np.uint32)[::-1].copy()
+        ctx.set_tile_order(order)
+        order_state = (ctx.get_option("tile_order_tiles"), ctx.get_option("tile_order"))
+        assert order_state[0] == order.size
+        name_before = plain_trace()
+        list_trace()
+        assert (ctx.get_option("tile_order_tiles"), ctx.get_option("tile_order")) == order_state
+        assert plain_trace() == name_before
+        ctx.set_tile_order(None)
+        # follow mode
+        ctx.set_option("follow", 1)
+        plain_trace()
+        name_follow = plain_trace()
+        assert name_follow.startswith("shadowMaskFollowKernel<")
+        traces, ordered = ctx.get_option("follow_traces"), ctx.get_option("follow_ordered")
+        list_trace()
+        assert (ctx.get_option("follow_traces"), ctx.get_option("follow_ordered"), ctx.get_option("follow")) == (traces, ordered, 1)
+        assert plain_trace() == name_follow
+        assert ctx.get_option("follow_traces") == traces + 1
+    finally:
+        ctx.set_option("follow", 0)
+        ctx.set_tile_order(None)
+        ctx.clear_splits()
+        _reset(ctx)
+        dev.close()
+
+
+# ---- 6. counters and names ------------------------------------------------------------------------------------------------------
+def test_counters_and_names(ctx):
+    fr = list_frame(64, 48)
+    lights, want = make_list("3"), fr.want("3")
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    others = ("active_traces", "distance_traces", "soft_distance_traces")
+    try:
+        before = [ctx.get_option(k) for k in others]
+        n0 = ctx.get_option("light_list_traces")
+        launches = 0
+        for kernel, split in FORMS:
+            ctx.set_option("kernel", kernel)
+            ctx.set_option("soft_split", split)
+            _trace(ctx, dev, fr, lights, want, (kernel, split))
+            assert ctx.last_kernel_name() == _name(kernel, split, "rows")
+            ctx.trace_light_list_stripes_device(fr.k, lights, dev.d_pos, fr.W, fr.H, dev.d_mask, 16, 2, 1)
+            assert ctx.last_kernel_name() == _name(kernel, split, "bands")
+            ctx.set_option("xcd_swizzle", 1)
+            ctx.trace_light_list_device(fr.k, lights, dev.d_pos, fr.W, fr.H, dev.d_mask)
+            assert ctx.last_kernel_name() == _name(kernel, split, "general")
+            ctx.set_option("xcd_swizzle", 0)
+            launches += 3
+        ctx.trace_light_list(fr.k, lights, fr.pos, fr.W, fr.H)
+        ctx.synchronize()
+        assert ctx.get_option("light_list_traces") == n0 + launches + 1
+        assert [ctx.get_option(k) for k in others] == before
+        with pytest.raises(api.RtsError):                # read-only
+            ctx.set_option("light_list_traces", 0)
+        # ... and the one-light traces do not move it
+        n1 = ctx.get_option("light_list_traces")
+        ctx.h2d(dev.d_map, np.full(fr.W * fr.H, 1, np.uint8))
+        ctx.trace_shadow_mask_device(fr.k, dev.d_pos, fr.W, fr.H, dev.d_mask, light=lights.light(0), d_active=dev.d_map)
+        ctx.synchronize()
+        assert ctx.get_option("light_list_traces") == n1 and ctx.get_option("active_traces") == before[0] + 1
+    finally:
+        _reset(ctx)
+        dev.close()
+
+
+def test_bit_l_is_the_active_trace_of_light_l(ctx):
+    """The definition on the device itself: bit l of the list trace = rts_trace_shadow_mask_active for light l with the map's bit l."""
+    fr = list_frame(61, 37)
+    lights = make_list("8")
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    d_one, d_act = ctx.malloc(fr.W * fr.H), ctx.malloc(fr.W * fr.H)
+    m = _maps(fr, 8)["mixed"]
+    try:
+        ctx.set_option("kernel", 3)
+        _trace(ctx, dev, fr, lights, fr.want("8"), "list", lights_map=m)
+        got = dev.read()
+        for l in range(8):
+            ctx.h2d(d_act, np.ascontiguousarray((m >> l) & 1, np.uint8))
+            ctx.trace_shadow_mask_device(fr.k, dev.d_pos, fr.W, fr.H, d_one, light=lights.light(l), d_active=d_act)
+            _same((got >> l) & 1, dev.read(what=d_one), ("light", l))
+    finally:
+        _reset(ctx)
+        ctx.free(d_one)
+        ctx.free(d_act)
+        dev.close()
+
+
+# ---- 7. graph capture -----------------------------------------------------------------------------------------------------------
+def _copy(struct):
+    return type(struct).from_buffer_copy(struct)
+
+
+@pytest.mark.parametrize("form", ["whole", "rows", "stripe"])
+@pytest.mark.parametrize("kernel,split", FORMS)
+def test_device_forms_under_capture(ctx, kernel, split, form):
+    fr = list_frame(64, 48)
+    want = fr.want("5")
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    maps = _maps(fr, 5)
+    stream = ctx.stream_create()
+    k, lights = _copy(fr.k), make_list("5")
+    g = None
+    try:
+        ctx.set_option("kernel", kernel)
+        ctx.set_option("soft_split", split)
+        ctx.h2d(dev.d_map, maps["mixed"])
+        ctx.trace_shadow_mask_device(fr.k, dev.d_pos, fr.W, fr.H, dev.d_mask, light=lights.light(0), stream=stream)   # a stream that has traced
+        ctx.synchronize(stream)
+        rows = None
+        if form == "whole":
+            record = lambda: ctx.trace_light_list_device(k, lights, dev.d_pos, fr.W, fr.H, dev.d_mask, d_lights_map=dev.d_map, stream=stream)
+        elif form == "rows":
+            rows = (np.arange(fr.H) >= 5) & (np.arange(fr.H) < 41)
+            record = lambda: ctx.trace_light_list_device(k, lights, dev.d_pos, fr.W, fr.H, dev.d_mask, d_lights_map=dev.d_map, stream=stream,
+                                                         row_begin=5, row_end=41)
+        else:
+            rows = ((np.arange(fr.H) // 16) % 2) == 1
+            record = lambda: ctx.trace_light_list_stripes_device(k, lights, dev.d_pos, fr.W, fr.H, dev.d_mask, 16, 2, 1,
+                                                                 d_lights_map=dev.d_map, stream=stream)
+        n0 = ctx.get_option("light_list_traces")
+        g = hipgraph.capture(stream, record)
+        assert ctx.get_option("light_list_traces") == n0 + 1
+        types = g.node_types()
+        assert types == [hipgraph.KERNEL], (kernel, split, form, types)   # one kernel node; no memcpy, memset or allocation node
+        for s in (k, lights):                            # what a caller may do to its structs between capture and replay
+            C.memset(C.byref(s), 0x7F, C.sizeof(s))
+        # the replay follows the buffers: the map and the positions the device holds at the replay, not those it held at the capture
+        for replay, m in enumerate((maps["mixed"], (255 - maps["mixed"]).astype(np.uint8))):
+            dirty = fr.pos.copy()
+            dirty[(m & 31) == 0] = POISON
+            ctx.h2d(dev.d_pos, dirty)
+            ctx.h2d(dev.d_map, m)
+            dev.guard()
+            g.launch(stream)
+            _same(dev.read(stream), _expect(want, m, rows), (kernel, split, form, replay))
+    finally:
+        if g:
+            g.close()
+        ctx.synchronize(stream)
+        ctx.stream_destroy(stream)
+        _reset(ctx)
+        dev.close()
+
+
+# ---- 8. refusals ----------------------------------------------------------------------------------------------------------------
+def test_refusals_write_nothing(ctx):
+    fr = list_frame(64, 48)
+    good = make_list("4")
+    ctx.set_bvh(fr.packed)
+    dev = _Dev(ctx, fr.pos, fr.W, fr.H)
+    try:
+        badtype = _copy(good)
+        badtype.lights[1].type = 2
+        zero, nine = _copy(good), _copy(good)
+        zero.count, nine.count = 0, 9
+        n0 = ctx.get_option("light_list_traces")
+        dev.guard()
+        out = np.full((fr.H, fr.W), GUARD, np.uint8)
+        for bad in (None, zero, nine, badtype):
+            with pytest.raises(api.RtsError) as e:
+                ctx.trace_light_list_device(fr.k, bad, dev.d_pos, fr.W, fr.H, dev.d_mask)
+            assert e.value.status == 1
+            with pytest.raises(api.RtsError):
+                ctx.trace_light_list_stripes_device(fr.k, bad, dev.d_pos, fr.W, fr.H, dev.d_mask, 16, 2, 0)
+            with pytest.raises(api.RtsError):
+                ctx.trace_light_list(fr.k, bad, fr.pos, fr.W, fr.H, out=out)
+        with pytest.raises(api.RtsError):
+            ctx.trace_light_list_device(fr.k, good, dev.d_pos, fr.W, fr.H, dev.d_mask, row_begin=9, row_end=8)
+        with pytest.raises(api.RtsError):
+            ctx.trace_light_list_device(fr.k, good, dev.d_pos, fr.W, fr.H, dev.d_mask, row_end=fr.H + 1)
+        with pytest.raises(api.RtsError):
+            ctx.trace_light_list_device(fr.k, good, dev.d_pos, fr.W, fr.H, 0)
+        with pytest.raises(api.RtsError):
+            ctx.trace_light_list_stripes_device(fr.k, good, dev.d_pos, fr.W, fr.H, dev.d_mask, 12, 2, 0)     # no multiple of 8
+        assert (dev.read() == GUARD).all() and (out == GUARD).all()
+        assert ctx.get_option("light_list_traces") == n0
+        good.reserved_[0], good.reserved_[2] = 0xFFFFFFFF, 77   # ignored
+        _trace(ctx, dev, fr, good, fr.want("4"), "reserved_")
+    finally:
+        dev.close()
+
+
+def test_no_bvh_before_a_stream_is_installed():
+    fr = list_frame(64, 48)
+    with api.ShadowContext(0) as fresh:
+        d_pos, d_mask = fresh.malloc(fr.pos.nbytes), fresh.malloc(fr.W * fr.H)
+        try:
+            fresh.h2d(d_mask, np.full(fr.W * fr.H, GUARD, np.uint8))
+            with pytest.raises(api.RtsError) as e:
+                fresh.trace_light_list_device(fr.k, make_list("2"), d_pos, fr.W, fr.H, d_mask)
+            assert e.value.status == 4                   # RTS_ERR_NO_BVH
+            with pytest.raises(api.RtsError) as e:
+                fresh.trace_light_list(fr.k, make_list("2"), fr.pos, fr.W, fr.H)
+            assert e.value.status == 4
+            got = np.empty(fr.W * fr.H, np.uint8)
+            fresh.synchronize()
+            fresh.d2h(got, d_mask)
+            assert (got == GUARD).all() and fresh.get_option("light_list_traces") == 0
+        finally:
+            fresh.free(d_pos)
+            fresh.free(d_mask)
+
+
+# ---- 9. the smallest stream -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kernel,split", FORMS)
+def test_one_triangle_stream(ctx, kernel, split):
+    """The root is the leaf.  A 21 x 13 grid of points on the plane z = 0 under a triangle at z = 1: lights above the triangle see
+    part of the grid shadowed, a light below it sees all of it."""
+    v = np.array([[0, 0, 1], [2, 0, 1], [0, 2, 1]], np.float32)
+    packed = api.BVHBuilder().build(v, 3, np.arange(3, dtype=np.uint32), 1).m_packedNodes
+    W, H = 21, 13
+    pos = np.zeros((H, W, 4), np.float32)
+    y, x = np.mgrid[0:H, 0:W]
+    pos[..., 0], pos[..., 1], pos[..., 3] = x * 0.15 - 0.5, y * 0.2 - 0.5, 1.0
+    k = api.RayTracingConstants.make((0, 0, 0), (0, 0, 1), W, H)
+    lights = api.LightList.make([(api.Light.POINT, (0.5, 0.5, 3.0)), (api.Light.DIRECTIONAL, (0.0, 0.0, 1.0)),
+                                 (api.Light.POINT, (0.5, 0.5, 0.5))])
+    want = api.light_list(packed, k, lights, pos, W, H)
+    for l in (0, 1):
+        assert 0 < int(((want >> l) & 1).sum()) < W * H, l
+    assert ((want >> 2) & 1).all()
+    m = ((x + 2 * y) & 7).astype(np.uint8)
+
+    class F:
+        pass
+    fr = F()
+    fr.k, fr.W, fr.H = k, W, H
+    ctx.set_bvh(packed)
+    dev = _Dev(ctx, pos, W, H)
+    try:
+        ctx.set_option("kernel", kernel)
+        ctx.set_option("soft_split", split)
+        _trace(ctx, dev, fr, lights, want, (kernel, split, "one triangle"))
+        _trace(ctx, dev, fr, lights, want, (kernel, split, "one triangle", "map"), lights_map=m)
+        assert ctx.last_kernel_name() == _name(kernel, split)
+    finally:
+        _reset(ctx)
+        dev.close()

@@ -1,4 +1,4 @@
-"""Kernel resources and instruction text of rts_kernels.hip, parent commit against this one (profiles/r13/kernel_resources.txt).
+"""Kernel resources and instruction text of rts_kernels.hip, parent commit against this one (profiles/r14/kernel_resources.txt).
 
     python tools/kernel_resources_ab.py PARENT_LOG PARENT_S NEW_LOG NEW_S
 
