@@ -325,6 +325,27 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _ptr_or_none(a):
+    return _ptr(a) if a is not None else None
+
+
+def _ref(struct):
+    """``byref(struct)``, or None (a NULL pointer) for None."""
+    return C.byref(struct) if struct is not None else None
+
+
+def _frame_inputs(where, positions, width, height, per_pixel=None, map_name="active"):
+    """The positions of a frame and its optional per-pixel byte map, contiguous and of the frame's size."""
+    positions = np.ascontiguousarray(positions, dtype=np.float32)
+    if positions.size != width * height * 4:
+        raise RtsError(1, f"{where}: positions must be W*H*4 floats")
+    if per_pixel is not None:
+        per_pixel = np.ascontiguousarray(per_pixel, dtype=np.uint8)
+        if per_pixel.size != width * height:
+            raise RtsError(1, f"{where}: {map_name} must be W*H bytes")
+    return positions, per_pixel
+
+
 def packed_count(prim_count):
     """``m_packedNodes.size()`` for ``prim_count`` triangles (= 5P-2)."""
     return int(_lib.rts_bvh_packed_count(prim_count))
@@ -504,20 +525,14 @@ class ShadowContext:
                           out=None, active=None):
         """Host-pointer dispatch; returns the ``uint8[H, W]`` mask (1 = lit).  ``active``: an active map, ``uint8[H, W]``
         (non-zero = trace the pixel, zero = send no ray and write 0; include/rts.h), or None for every pixel."""
-        positions = np.ascontiguousarray(positions, dtype=np.float32)
-        if positions.size != width * height * 4:
-            raise RtsError(1, "trace_shadow_mask: positions must be W*H*4 floats")
+        positions, active = _frame_inputs("trace_shadow_mask", positions, width, height, active)
         row_end = height if row_end is None else row_end
         mask = out if out is not None else np.zeros((height, width), dtype=np.uint8)
-        lp = C.byref(light) if light is not None else None
         if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.uint8)
-            if active.size != width * height:
-                raise RtsError(1, "trace_shadow_mask: active must be W*H bytes")
-            _check(_lib.rts_trace_shadow_mask_active(self._h, C.byref(constants), lp, _ptr(positions), _ptr(active), width, height,
-                                                     row_begin, row_end, _ptr(mask)), "rts_trace_shadow_mask_active")
+            _check(_lib.rts_trace_shadow_mask_active(self._h, C.byref(constants), _ref(light), _ptr(positions), _ptr(active),
+                                                     width, height, row_begin, row_end, _ptr(mask)), "rts_trace_shadow_mask_active")
             return mask
-        _check(_lib.rts_trace_shadow_mask(self._h, C.byref(constants), lp, _ptr(positions), width, height,
+        _check(_lib.rts_trace_shadow_mask(self._h, C.byref(constants), _ref(light), _ptr(positions), width, height,
                                           row_begin, row_end, _ptr(mask)), "rts_trace_shadow_mask")
         return mask
 
@@ -525,28 +540,27 @@ class ShadowContext:
                                  row_end=None, stream=None, d_active=None):
         """``d_active``: device pointer of an active map (width * height bytes), or None for every pixel."""
         row_end = height if row_end is None else row_end
-        lp = C.byref(light) if light is not None else None
         if d_active is not None:
-            _check(_lib.rts_trace_shadow_mask_active_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
+            _check(_lib.rts_trace_shadow_mask_active_device(self._h, C.byref(constants), _ref(light), C.c_void_p(d_positions),
                                                             C.c_void_p(d_active), width, height, row_begin, row_end,
                                                             C.c_void_p(d_mask), C.c_void_p(stream or 0)),
                    "rts_trace_shadow_mask_active_device")
             return
-        _check(_lib.rts_trace_shadow_mask_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions), width,
+        _check(_lib.rts_trace_shadow_mask_device(self._h, C.byref(constants), _ref(light), C.c_void_p(d_positions), width,
                                                  height, row_begin, row_end, C.c_void_p(d_mask),
                                                  C.c_void_p(stream or 0)), "rts_trace_shadow_mask_device")
 
     def trace_shadow_mask_stripes_device(self, constants, d_positions, width, height, d_mask, band_rows, n_stripes,
                                          stripe, light=None, stream=None, d_active=None):
         """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
-        lp = C.byref(light) if light is not None else None
         if d_active is not None:
-            _check(_lib.rts_trace_shadow_mask_active_stripes_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
-                                                                    C.c_void_p(d_active), width, height, band_rows, n_stripes,
-                                                                    stripe, C.c_void_p(d_mask), C.c_void_p(stream or 0)),
+            _check(_lib.rts_trace_shadow_mask_active_stripes_device(self._h, C.byref(constants), _ref(light),
+                                                                    C.c_void_p(d_positions), C.c_void_p(d_active), width, height,
+                                                                    band_rows, n_stripes, stripe, C.c_void_p(d_mask),
+                                                                    C.c_void_p(stream or 0)),
                    "rts_trace_shadow_mask_active_stripes_device")
             return
-        _check(_lib.rts_trace_shadow_mask_stripes_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
+        _check(_lib.rts_trace_shadow_mask_stripes_device(self._h, C.byref(constants), _ref(light), C.c_void_p(d_positions),
                                                          width, height, band_rows, n_stripes, stripe,
                                                          C.c_void_p(d_mask), C.c_void_p(stream or 0)),
                "rts_trace_shadow_mask_stripes_device")
@@ -580,20 +594,13 @@ class ShadowContext:
                               out=None, mask=None, want_mask=True):
         """Host-pointer dispatch; returns ``(float32[H, W] distance, uint8[H, W] mask)`` (mask None with ``want_mask`` False).
         ``out`` / ``mask``: arrays to write into (rows outside the range keep their contents)."""
-        positions = np.ascontiguousarray(positions, dtype=np.float32)
-        if positions.size != width * height * 4:
-            raise RtsError(1, "trace_shadow_distance: positions must be W*H*4 floats")
+        positions, active = _frame_inputs("trace_shadow_distance", positions, width, height, active)
         row_end = height if row_end is None else row_end
         dist = out if out is not None else np.zeros((height, width), dtype=np.float32)
         if mask is None and want_mask:
             mask = np.zeros((height, width), dtype=np.uint8)
-        if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.uint8)
-            if active.size != width * height:
-                raise RtsError(1, "trace_shadow_distance: active must be W*H bytes")
-        lp = C.byref(light) if light is not None else None
-        _check(_lib.rts_trace_shadow_distance(self._h, C.byref(constants), lp, _ptr(positions), _ptr(active) if active is not None else None,
-                                              width, height, row_begin, row_end, _ptr(dist), _ptr(mask) if mask is not None else None),
+        _check(_lib.rts_trace_shadow_distance(self._h, C.byref(constants), _ref(light), _ptr(positions), _ptr_or_none(active),
+                                              width, height, row_begin, row_end, _ptr(dist), _ptr_or_none(mask)),
                "rts_trace_shadow_distance")
         return dist, mask
 
@@ -601,16 +608,15 @@ class ShadowContext:
                                      row_end=None, stream=None, d_active=None):
         """Device pointers, asynchronous: d_distance = width * height floats, d_mask / d_active = width * height bytes or None."""
         row_end = height if row_end is None else row_end
-        lp = C.byref(light) if light is not None else None
-        _check(_lib.rts_trace_shadow_distance_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions), C.c_void_p(d_active or 0),
-                                                     width, height, row_begin, row_end, C.c_void_p(d_distance), C.c_void_p(d_mask or 0),
-                                                     C.c_void_p(stream or 0)), "rts_trace_shadow_distance_device")
+        _check(_lib.rts_trace_shadow_distance_device(self._h, C.byref(constants), _ref(light), C.c_void_p(d_positions),
+                                                     C.c_void_p(d_active or 0), width, height, row_begin, row_end,
+                                                     C.c_void_p(d_distance), C.c_void_p(d_mask or 0), C.c_void_p(stream or 0)),
+               "rts_trace_shadow_distance_device")
 
     def trace_shadow_distance_stripes_device(self, constants, d_positions, width, height, d_distance, band_rows, n_stripes, stripe,
                                              d_mask=None, light=None, stream=None, d_active=None):
         """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
-        lp = C.byref(light) if light is not None else None
-        _check(_lib.rts_trace_shadow_distance_stripes_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
+        _check(_lib.rts_trace_shadow_distance_stripes_device(self._h, C.byref(constants), _ref(light), C.c_void_p(d_positions),
                                                              C.c_void_p(d_active or 0), width, height, band_rows, n_stripes, stripe,
                                                              C.c_void_p(d_distance), C.c_void_p(d_mask or 0), C.c_void_p(stream or 0)),
                "rts_trace_shadow_distance_stripes_device")
@@ -620,20 +626,13 @@ class ShadowContext:
                             out=None, mask=None, want_mask=True):
         """Host-pointer dispatch; returns ``(float32[H, W] distance, uint8[H, W] mask)`` (mask None with ``want_mask`` False):
         the minimum of the samples' distances and the number of unoccluded samples.  ``out`` / ``mask``: arrays to write into."""
-        positions = np.ascontiguousarray(positions, dtype=np.float32)
-        if positions.size != width * height * 4:
-            raise RtsError(1, "trace_soft_distance: positions must be W*H*4 floats")
+        positions, active = _frame_inputs("trace_soft_distance", positions, width, height, active)
         row_end = height if row_end is None else row_end
         dist = out if out is not None else np.zeros((height, width), dtype=np.float32)
         if mask is None and want_mask:
             mask = np.zeros((height, width), dtype=np.uint8)
-        if active is not None:
-            active = np.ascontiguousarray(active, dtype=np.uint8)
-            if active.size != width * height:
-                raise RtsError(1, "trace_soft_distance: active must be W*H bytes")
-        lp = C.byref(light) if light is not None else None
-        _check(_lib.rts_trace_soft_distance(self._h, C.byref(constants), lp, _ptr(positions), _ptr(active) if active is not None else None,
-                                            width, height, row_begin, row_end, _ptr(dist), _ptr(mask) if mask is not None else None),
+        _check(_lib.rts_trace_soft_distance(self._h, C.byref(constants), _ref(light), _ptr(positions), _ptr_or_none(active),
+                                            width, height, row_begin, row_end, _ptr(dist), _ptr_or_none(mask)),
                "rts_trace_soft_distance")
         return dist, mask
 
@@ -641,16 +640,15 @@ class ShadowContext:
                                    row_end=None, stream=None, d_active=None):
         """Device pointers, asynchronous: d_distance = width * height floats, d_mask / d_active = width * height bytes or None."""
         row_end = height if row_end is None else row_end
-        lp = C.byref(light) if light is not None else None
-        _check(_lib.rts_trace_soft_distance_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions), C.c_void_p(d_active or 0),
-                                                   width, height, row_begin, row_end, C.c_void_p(d_distance), C.c_void_p(d_mask or 0),
-                                                   C.c_void_p(stream or 0)), "rts_trace_soft_distance_device")
+        _check(_lib.rts_trace_soft_distance_device(self._h, C.byref(constants), _ref(light), C.c_void_p(d_positions),
+                                                   C.c_void_p(d_active or 0), width, height, row_begin, row_end,
+                                                   C.c_void_p(d_distance), C.c_void_p(d_mask or 0), C.c_void_p(stream or 0)),
+               "rts_trace_soft_distance_device")
 
     def trace_soft_distance_stripes_device(self, constants, d_positions, width, height, d_distance, band_rows, n_stripes, stripe,
                                            d_mask=None, light=None, stream=None, d_active=None):
         """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
-        lp = C.byref(light) if light is not None else None
-        _check(_lib.rts_trace_soft_distance_stripes_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
+        _check(_lib.rts_trace_soft_distance_stripes_device(self._h, C.byref(constants), _ref(light), C.c_void_p(d_positions),
                                                            C.c_void_p(d_active or 0), width, height, band_rows, n_stripes, stripe,
                                                            C.c_void_p(d_distance), C.c_void_p(d_mask or 0), C.c_void_p(stream or 0)),
                "rts_trace_soft_distance_stripes_device")
@@ -659,18 +657,11 @@ class ShadowContext:
     def trace_light_list(self, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None):
         """Host-pointer dispatch; returns ``uint8[H, W]``: bit ``l`` = light ``l``'s shadow byte where ``lights_map`` (uint8[H, W], or
         None: everywhere) has bit ``l`` set.  ``out``: an array to write the rows into."""
-        positions = np.ascontiguousarray(positions, dtype=np.float32)
-        if positions.size != width * height * 4:
-            raise RtsError(1, "trace_light_list: positions must be W*H*4 floats")
-        if lights_map is not None:
-            lights_map = np.ascontiguousarray(lights_map, dtype=np.uint8)
-            if lights_map.size != width * height:
-                raise RtsError(1, "trace_light_list: lights_map must be W*H bytes")
+        positions, lights_map = _frame_inputs("trace_light_list", positions, width, height, lights_map, "lights_map")
         row_end = height if row_end is None else row_end
         mask = out if out is not None else np.zeros((height, width), dtype=np.uint8)
-        lp = C.byref(lights) if lights is not None else None
-        _check(_lib.rts_trace_light_list(self._h, C.byref(constants), lp, _ptr(positions),
-                                         _ptr(lights_map) if lights_map is not None else None, width, height, row_begin, row_end,
+        _check(_lib.rts_trace_light_list(self._h, C.byref(constants), _ref(lights), _ptr(positions),
+                                         _ptr_or_none(lights_map), width, height, row_begin, row_end,
                                          _ptr(mask)), "rts_trace_light_list")
         return mask
 
@@ -678,16 +669,15 @@ class ShadowContext:
                                 row_end=None, stream=None):
         """Device pointers, asynchronous: d_mask / d_lights_map = width * height bytes (the map may be None)."""
         row_end = height if row_end is None else row_end
-        lp = C.byref(lights) if lights is not None else None
-        _check(_lib.rts_trace_light_list_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions), C.c_void_p(d_lights_map or 0),
-                                                width, height, row_begin, row_end, C.c_void_p(d_mask), C.c_void_p(stream or 0)),
+        _check(_lib.rts_trace_light_list_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
+                                                C.c_void_p(d_lights_map or 0), width, height, row_begin, row_end, C.c_void_p(d_mask),
+                                                C.c_void_p(stream or 0)),
                "rts_trace_light_list_device")
 
     def trace_light_list_stripes_device(self, constants, lights, d_positions, width, height, d_mask, band_rows, n_stripes, stripe,
                                         d_lights_map=None, stream=None):
         """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
-        lp = C.byref(lights) if lights is not None else None
-        _check(_lib.rts_trace_light_list_stripes_device(self._h, C.byref(constants), lp, C.c_void_p(d_positions),
+        _check(_lib.rts_trace_light_list_stripes_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
                                                         C.c_void_p(d_lights_map or 0), width, height, band_rows, n_stripes, stripe,
                                                         C.c_void_p(d_mask), C.c_void_p(stream or 0)),
                "rts_trace_light_list_stripes_device")
@@ -967,21 +957,14 @@ def shadow_distance(packed, constants, light, positions, width, height, active=N
     """Occluder distance of a frame's shadow rays on the host (rtsh_shadow_distance, no GPU): ``(float32[H, W], uint8[H, W])``
     (mask None with ``want_mask`` False).  ``out`` / ``mask``: arrays to write into (rows outside the range keep their contents)."""
     packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
-    positions = np.ascontiguousarray(positions, np.float32)
-    if positions.size != width * height * 4:
-        raise RtsError(1, "shadow_distance: positions must be W*H*4 floats")
-    if active is not None:
-        active = np.ascontiguousarray(active, np.uint8)
-        if active.size != width * height:
-            raise RtsError(1, "shadow_distance: active must be W*H bytes")
+    positions, active = _frame_inputs("shadow_distance", positions, width, height, active)
     row_end = height if row_end is None else row_end
     dist = out if out is not None else np.zeros((height, width), np.float32)
     if mask is None and want_mask:
         mask = np.zeros((height, width), np.uint8)
-    lp = C.byref(light) if light is not None else None
-    _check(_lib.rtsh_shadow_distance(_ptr(packed), packed.shape[0], C.byref(constants), lp, _ptr(positions),
-                                     _ptr(active) if active is not None else None, width, height, row_begin, row_end, _ptr(dist),
-                                     _ptr(mask) if mask is not None else None, threads), "rtsh_shadow_distance")
+    _check(_lib.rtsh_shadow_distance(_ptr(packed), packed.shape[0], C.byref(constants), _ref(light), _ptr(positions),
+                                     _ptr_or_none(active), width, height, row_begin, row_end, _ptr(dist),
+                                     _ptr_or_none(mask), threads), "rtsh_shadow_distance")
     return dist, mask
 
 
@@ -990,21 +973,14 @@ def soft_distance(packed, constants, light, positions, width, height, active=Non
     """Soft-shadow occluder distance on the host (rtsh_soft_distance, no GPU): ``(float32[H, W], uint8[H, W])`` -- the minimum of the
     light samples' distances and the number of unoccluded samples (mask None with ``want_mask`` False)."""
     packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
-    positions = np.ascontiguousarray(positions, np.float32)
-    if positions.size != width * height * 4:
-        raise RtsError(1, "soft_distance: positions must be W*H*4 floats")
-    if active is not None:
-        active = np.ascontiguousarray(active, np.uint8)
-        if active.size != width * height:
-            raise RtsError(1, "soft_distance: active must be W*H bytes")
+    positions, active = _frame_inputs("soft_distance", positions, width, height, active)
     row_end = height if row_end is None else row_end
     dist = out if out is not None else np.zeros((height, width), np.float32)
     if mask is None and want_mask:
         mask = np.zeros((height, width), np.uint8)
-    lp = C.byref(light) if light is not None else None
-    _check(_lib.rtsh_soft_distance(_ptr(packed), packed.shape[0], C.byref(constants), lp, _ptr(positions),
-                                   _ptr(active) if active is not None else None, width, height, row_begin, row_end, _ptr(dist),
-                                   _ptr(mask) if mask is not None else None, threads), "rtsh_soft_distance")
+    _check(_lib.rtsh_soft_distance(_ptr(packed), packed.shape[0], C.byref(constants), _ref(light), _ptr(positions),
+                                   _ptr_or_none(active), width, height, row_begin, row_end, _ptr(dist),
+                                   _ptr_or_none(mask), threads), "rtsh_soft_distance")
     return dist, mask
 
 
@@ -1012,18 +988,11 @@ def light_list(packed, constants, lights, positions, width, height, lights_map=N
     """A light list trace on the host (rtsh_light_list, no GPU): ``uint8[H, W]``, bit ``l`` = light ``l`` is unoccluded, where
     ``lights_map`` (None: everywhere) has bit ``l`` set."""
     packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
-    positions = np.ascontiguousarray(positions, np.float32)
-    if positions.size != width * height * 4:
-        raise RtsError(1, "light_list: positions must be W*H*4 floats")
-    if lights_map is not None:
-        lights_map = np.ascontiguousarray(lights_map, np.uint8)
-        if lights_map.size != width * height:
-            raise RtsError(1, "light_list: lights_map must be W*H bytes")
+    positions, lights_map = _frame_inputs("light_list", positions, width, height, lights_map, "lights_map")
     row_end = height if row_end is None else row_end
     mask = out if out is not None else np.zeros((height, width), np.uint8)
-    lp = C.byref(lights) if lights is not None else None
-    _check(_lib.rtsh_light_list(_ptr(packed), packed.shape[0], C.byref(constants), lp, _ptr(positions),
-                                _ptr(lights_map) if lights_map is not None else None, width, height, row_begin, row_end, _ptr(mask),
+    _check(_lib.rtsh_light_list(_ptr(packed), packed.shape[0], C.byref(constants), _ref(lights), _ptr(positions),
+                                _ptr_or_none(lights_map), width, height, row_begin, row_end, _ptr(mask),
                                 threads), "rtsh_light_list")
     return mask
 

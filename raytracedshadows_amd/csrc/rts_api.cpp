@@ -7,6 +7,7 @@
 #include "rts_soft_distance.h"
 #include "rts_light_list.h"
 #include "rts_dispatch.h"
+#include "rts_args.h"
 #include "rts_refit.h"
 
 #include <algorithm>
@@ -705,7 +706,7 @@ enum class Begin { Return, Nothing, Go };
 static Begin beginFrame(rts_ctx* c, const rts_constants* k, const float* d_positions, uint8_t* d_mask, bool ownArgsOk, const Dispatch& g,
                         TraceParams& p, uint32_t* rows, int* status) {
     *status = RTS_ERR_INVALID_ARG;
-    if (!c || !k || !d_positions || !ownArgsOk || g.W == 0 || g.H == 0 || g.rowBegin > g.rowEnd || g.rowEnd > g.H) return Begin::Return;
+    if (!c || !k || !d_positions || !ownArgsOk || !rts::frameRowsOk(g.W, g.H, g.rowBegin, g.rowEnd)) return Begin::Return;
     if ((uint64_t)g.W * g.H > (1ull << 31)) return Begin::Return;      // tile counts are 32-bit on the device
     *status = fillParams(c, p);
     if (*status != RTS_OK) return Begin::Return;
@@ -721,36 +722,48 @@ static Begin beginFrame(rts_ctx* c, const rts_constants* k, const float* d_posit
     return *rows ? Begin::Go : Begin::Nothing;                         // (a stripe without a band: no launch)
 }
 
-// A trace with an active map (include/rts.h): the kernel FAMILY the options ask for, one tile per workgroup, in natural order -- an
-// installed split table, a tile order and follow mode are neither used nor touched, and no statistics are recorded.
+// The tail of a block trace -- active, distance, soft distance, light list: one block per workgroup in natural order, in the kernel
+// FAMILY the caller chose; an installed split table, a tile order and follow mode are neither used nor touched, and no statistics are
+// recorded.  p holds everything but the grid.  A band that is not a whole number of block rows is refused before anything is counted.
+using BlockLaunch = hipError_t (*)(int variant, const TraceParams& p, hipStream_t stream, const char** name);
+static int launchBlocks(rts_ctx* c, TraceParams& p, const Dispatch& g, int family, uint64_t rts_ctx::*counter, BlockLaunch launch, void* stream) {
+    const int s = setBlockGrid(c, p, g, family);
+    if (s != RTS_OK) return s;
+    ++c->launches;
+    ++(c->*counter);
+    const char* name = "";
+    const hipError_t e = launch(family, p, (hipStream_t)stream, &name);
+    c->lastKernel = name;
+    return hipStatus(e);
+}
+
+// The family of a distance, a soft distance and a light list trace: as "kernel" asks, except that 8 and 9 run the stackless packet too
+// (the wide walk has none of these forms yet).
+static int blockFamily(const rts_ctx* c, uint64_t pixels) {
+    if (c->variant == rts::V_AUTO) return pixels < (1u << 18) ? rts::V_SHARE : rts::V_PACKET;
+    return (c->variant >= rts::V_PACKET && c->variant != rts::V_SHARE) ? rts::V_PACKET : rts::V_SHARE;
+}
+
+// A trace with an active map (include/rts.h): the kernel FAMILY the options ask for, which may be the wide packet.
 static int traceActive(rts_ctx* c, TraceParams& p, const Dispatch& g, uint32_t rows, const rts_constants* k, const rts_light* light,
                        const uint8_t* d_active, void* stream) {
     const uint64_t pixels = (uint64_t)g.W * rows;
     int variant = c->variant;
-    if (variant == rts::V_AUTO)                      // (the plain trace's rule, traceMaskImpl)
+    if (variant == rts::V_AUTO)                      // (the plain trace's rule, traceMaskImpl, without its "block_waves" clause)
         variant = pixels < (1u << 18) ? rts::V_SHARE
                 : (c->wideCount && (!light || light->nsamples <= 1) && pixels >= (1u << 22)) ? rts::V_WIDE : rts::V_PACKET;
     if (variant == rts::V_WIDE || variant == rts::V_WIDE_C) variant = p.wide ? rts::V_WIDE : rts::V_PACKET;
     else if (variant >= rts::V_PACKET && variant <= rts::V_PACKET_PF) variant = rts::V_PACKET;
     else variant = rts::V_SHARE;
-    const int s = setBlockGrid(c, p, g, variant);
-    if (s != RTS_OK) return s;
     p.activeMap = d_active;
     setLight(p, k, light);
-    ++c->launches;
-    ++c->activeTraces;
-    const char* name = "";
-    const hipError_t e = rts::launchShadowMaskActive(variant, p, (hipStream_t)stream, &name);
-    c->lastKernel = name;
-    return hipStatus(e);
+    return launchBlocks(c, p, g, variant, &rts_ctx::activeTraces, rts::launchShadowMaskActive, stream);
 }
 
 static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const Dispatch& g,
                          uint8_t* d_mask, void* stream, const uint8_t* d_active = nullptr) {
-    const bool lightOk = !light || (light->type <= RTS_LIGHT_POINT && light->nsamples <= 64 &&
-                                    (!light->table || (light->table <= 64 && light->table >= light->nsamples && light->nsamples >= 2)));
     TraceParams p; uint32_t rows = 0; int s;
-    if (beginFrame(c, k, d_positions, d_mask, d_mask && lightOk, g, p, &rows, &s) != Begin::Go) return s;
+    if (beginFrame(c, k, d_positions, d_mask, d_mask && rts::softLightOk(light), g, p, &rows, &s) != Begin::Go) return s;
     if (d_active) return traceActive(c, p, g, rows, k, light, d_active, stream);
     // V_AUTO: a packet's steps are a dependent chain, so it needs several waves per SIMD to overlap them;
     // a launch with fewer than ~4 waves per SIMD is faster lane-per-ray (with in-wave work sharing: measured
@@ -884,29 +897,15 @@ int rts_trace_rays_device(rts_ctx* c, const rts_ray* d_rays, size_t n, uint8_t* 
 }
 
 // ---- occluder distance (include/rts.h): the nearest accepted triangle's t beside the shadow byte ---------------------------------
-// One launch of a distance kernel (rts_distance.inc), one tile (or block) per workgroup in natural order.  The kernel FAMILY follows
-// "kernel" as for an active trace, except that 8 and 9 run the stackless packet too (the wide walk has no distance form yet).  No
-// table, order, follow state or statistic is used or touched.
+// One launch of a distance kernel (rts_distance.inc) through the block traces' tail (launchBlocks), in the family of blockFamily.
 static int traceDistanceImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const uint8_t* d_active,
                              const Dispatch& g, float* d_distance, uint8_t* d_mask, void* stream) {
-    const bool lightOk = !light || (light->type <= RTS_LIGHT_POINT && light->nsamples <= 1);     // one sample in this version
     TraceParams p; uint32_t rows = 0; int s;
-    if (beginFrame(c, k, d_positions, d_mask, d_distance && lightOk, g, p, &rows, &s) != Begin::Go) return s;
+    if (beginFrame(c, k, d_positions, d_mask, d_distance && rts::hardLightOk(light), g, p, &rows, &s) != Begin::Go) return s;   // one sample in this version
     p.distance = d_distance;
     p.activeMap = d_active;
-    const uint64_t pixels = (uint64_t)g.W * rows;
-    int variant = c->variant;
-    if (variant == rts::V_AUTO) variant = pixels < (1u << 18) ? rts::V_SHARE : rts::V_PACKET;
-    else variant = (variant >= rts::V_PACKET && variant != rts::V_SHARE) ? rts::V_PACKET : rts::V_SHARE;
-    s = setBlockGrid(c, p, g, variant);
-    if (s != RTS_OK) return s;
     setLight(p, k, light);
-    ++c->launches;
-    ++c->distanceTraces;
-    const char* name = "";
-    const hipError_t e = rts::launchShadowDistance(variant, p, (hipStream_t)stream, &name);
-    c->lastKernel = name;
-    return hipStatus(e);
+    return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::distanceTraces, rts::launchShadowDistance, stream);
 }
 
 int rts_trace_shadow_distance_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
@@ -923,31 +922,18 @@ int rts_trace_shadow_distance_stripes_device(rts_ctx* c, const rts_constants* k,
 }
 
 // ---- soft-shadow occluder distance (include/rts.h): the nearest blocker over all light samples, beside the count of unoccluded ones --
-// One launch of a soft distance kernel (rts_soft_distance.inc) with the geometry, the family rule and the launch shape of a distance
-// trace; a light of one sample IS the distance trace.  No table, order, follow state or statistic is used or touched.
+// One launch of a soft distance kernel (rts_soft_distance.inc) with the geometry, the family rule and the tail of a distance trace; a
+// light of one sample IS the distance trace.
 static int traceSoftDistanceImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const uint8_t* d_active,
                                  const Dispatch& g, float* d_distance, uint8_t* d_mask, void* stream) {
-    const bool lightOk = !light || (light->type <= RTS_LIGHT_POINT && light->nsamples <= 64 &&             // (the mask trace's rule)
-                                    (!light->table || (light->table <= 64 && light->table >= light->nsamples && light->nsamples >= 2)));
-    if (!lightOk) return RTS_ERR_INVALID_ARG;
+    if (!rts::softLightOk(light)) return RTS_ERR_INVALID_ARG;                                              // (the mask trace's rule)
     if (!light || light->nsamples <= 1) return traceDistanceImpl(c, k, light, d_positions, d_active, g, d_distance, d_mask, stream);
     TraceParams p; uint32_t rows = 0; int s;
     if (beginFrame(c, k, d_positions, d_mask, d_distance != nullptr, g, p, &rows, &s) != Begin::Go) return s;
     p.distance = d_distance;
     p.activeMap = d_active;
-    const uint64_t pixels = (uint64_t)g.W * rows;
-    int variant = c->variant;
-    if (variant == rts::V_AUTO) variant = pixels < (1u << 18) ? rts::V_SHARE : rts::V_PACKET;
-    else variant = (variant >= rts::V_PACKET && variant != rts::V_SHARE) ? rts::V_PACKET : rts::V_SHARE;
-    s = setBlockGrid(c, p, g, variant);
-    if (s != RTS_OK) return s;
     setLight(p, k, light);
-    ++c->launches;
-    ++c->softDistanceTraces;
-    const char* name = "";
-    const hipError_t e = rts::launchShadowSoftDistance(variant, p, (hipStream_t)stream, &name);
-    c->lastKernel = name;
-    return hipStatus(e);
+    return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::softDistanceTraces, rts::launchShadowSoftDistance, stream);
 }
 
 int rts_trace_soft_distance_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
@@ -979,9 +965,11 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 
 // ---- the host-pointer entries: the same traces through the context's staging buffers ----------------------------------------------
 // Frames (arguments checked by the caller): only rows [row_begin, row_end) travel -- their positions, map, mask and distances, as a
-// frame of their own.  distance != NULL: a distance trace (mask optional; soft: over all light samples), else a mask trace.
-static int traceStagedRows(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
-                           uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask, bool soft = false) {
+// frame of their own, to the device entry of what is being traced.  lights: the rts_light, or for Staged::LightList the rts_light_list;
+// each case below names the type it reads, and nothing else does.  distance: of the distance traces alone, whose mask is optional.
+enum class Staged { Mask, Distance, SoftDistance, LightList };
+static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, const void* lights, const float* positions, const uint8_t* active,
+                           uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
     if (row_begin == row_end) return RTS_OK;
     RTS_HIP(hipSetDevice(c->device));
@@ -996,12 +984,21 @@ static int traceStagedRows(rts_ctx* c, const rts_constants* k, const rts_light* 
     if (active) RTS_HIP(hipMemcpy(c->d_act, active + first, pixels, hipMemcpyHostToDevice));
     const uint8_t* d_active = active ? (const uint8_t*)c->d_act : nullptr;
     uint8_t* d_mask = mask ? (uint8_t*)c->d_out : nullptr;
+    const float* d_in = (const float*)c->d_in;
+    float* d_dist = (float*)c->d_dist;
     // per-pixel jitter hashes the pixel's index in the caller's frame (sampleIndex, rts_kernels.hip: the one reader, and only of a
-    // light with a table -- several samples, so in a mask trace or a soft distance trace)
+    // light with a table -- several samples, so in a mask trace or a soft distance trace; a light list never reads it)
     c->pixelBase = row_begin * W;
-    s = distance ? (soft ? rts_trace_soft_distance_device(c, k, light, (const float*)c->d_in, d_active, W, rows, 0, rows, (float*)c->d_dist, d_mask, nullptr)
-                         : rts_trace_shadow_distance_device(c, k, light, (const float*)c->d_in, d_active, W, rows, 0, rows, (float*)c->d_dist, d_mask, nullptr))
-                 : rts_trace_shadow_mask_active_device(c, k, light, (const float*)c->d_in, d_active, W, rows, 0, rows, d_mask, nullptr);
+    switch (what) {
+    case Staged::Mask:
+        s = rts_trace_shadow_mask_active_device(c, k, (const rts_light*)lights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
+    case Staged::Distance:
+        s = rts_trace_shadow_distance_device(c, k, (const rts_light*)lights, d_in, d_active, W, rows, 0, rows, d_dist, d_mask, nullptr); break;
+    case Staged::SoftDistance:
+        s = rts_trace_soft_distance_device(c, k, (const rts_light*)lights, d_in, d_active, W, rows, 0, rows, d_dist, d_mask, nullptr); break;
+    case Staged::LightList:
+        s = rts_trace_light_list_device(c, k, (const rts_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
+    }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
     if (distance) RTS_HIP(hipMemcpy(distance + first, c->d_dist, pixels * 4, hipMemcpyDeviceToHost));
@@ -1011,8 +1008,8 @@ static int traceStagedRows(rts_ctx* c, const rts_constants* k, const rts_light* 
 
 int rts_trace_shadow_mask_active(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
                                  uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
-    if (!c || !k || !positions || !mask || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
-    return traceStagedRows(c, k, light, positions, active, W, row_begin, row_end, nullptr, mask);
+    if (!c || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    return traceStagedRows(c, Staged::Mask, k, light, positions, active, W, row_begin, row_end, nullptr, mask);
 }
 
 int rts_trace_shadow_mask(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions,
@@ -1022,40 +1019,27 @@ int rts_trace_shadow_mask(rts_ctx* c, const rts_constants* k, const rts_light* l
 
 int rts_trace_shadow_distance(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
                               uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
-    if (!c || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
-    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 1)) return RTS_ERR_INVALID_ARG;
-    return traceStagedRows(c, k, light, positions, active, W, row_begin, row_end, distance, mask);
+    if (!c || !k || !positions || !distance || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::hardLightOk(light)) return RTS_ERR_INVALID_ARG;
+    return traceStagedRows(c, Staged::Distance, k, light, positions, active, W, row_begin, row_end, distance, mask);
 }
 
 int rts_trace_soft_distance(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
                             uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
-    if (!c || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
-    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 64 ||
-                  (light->table && (light->table > 64 || light->table < light->nsamples || light->nsamples < 2)))) return RTS_ERR_INVALID_ARG;
-    return traceStagedRows(c, k, light, positions, active, W, row_begin, row_end, distance, mask, true);
+    if (!c || !k || !positions || !distance || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::softLightOk(light)) return RTS_ERR_INVALID_ARG;
+    return traceStagedRows(c, Staged::SoftDistance, k, light, positions, active, W, row_begin, row_end, distance, mask);
 }
 
 // ---- light lists (include/rts.h): up to 8 hard lights in one dispatch, one bit per light in the mask byte ----------------------------
-// One launch of a light list kernel (rts_light_list.inc) with the geometry, the family rule and the launch shape of a distance trace.
-// The list travels in the argument block's 64 sample offsets: light l in offsets[l] = {x, y, z, 0.0f directional / 1.0f point}, the
-// count in nsamples, the map in the active map's slot.  No table, order, follow state or statistic is used or touched.
-static bool lightListOk(const rts_light_list* list) {
-    if (!list || list->count == 0 || list->count > RTS_MAX_LIST_LIGHTS) return false;
-    for (uint32_t l = 0; l < list->count; ++l) if (list->lights[l].type > RTS_LIGHT_POINT) return false;
-    return true;
-}
-
+// One launch of a light list kernel (rts_light_list.inc) with the geometry, the family rule and the tail of a distance trace.  The
+// list travels in the argument block's 64 sample offsets: light l in offsets[l] = {x, y, z, 0.0f directional / 1.0f point}, the
+// count in nsamples, the map in the active map's slot.
 static int traceLightListImpl(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* d_positions,
                               const uint8_t* d_lights_map, const Dispatch& g, uint8_t* d_mask, void* stream) {
     TraceParams p; uint32_t rows = 0; int s;
-    if (beginFrame(c, k, d_positions, d_mask, d_mask && lightListOk(list), g, p, &rows, &s) != Begin::Go) return s;
+    if (beginFrame(c, k, d_positions, d_mask, d_mask && rts::lightListOk(list), g, p, &rows, &s) != Begin::Go) return s;
     p.activeMap = d_lights_map;
-    const uint64_t pixels = (uint64_t)g.W * rows;
-    int variant = c->variant;
-    if (variant == rts::V_AUTO) variant = pixels < (1u << 18) ? rts::V_SHARE : rts::V_PACKET;
-    else variant = (variant >= rts::V_PACKET && variant != rts::V_SHARE) ? rts::V_PACKET : rts::V_SHARE;
-    s = setBlockGrid(c, p, g, variant);
-    if (s != RTS_OK) return s;
     for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
     p.lightType = RTS_LIGHT_DIRECTIONAL;               // (not read: every light carries its own type)
     p.nsamples = list->count;
@@ -1065,12 +1049,7 @@ static int traceLightListImpl(rts_ctx* c, const rts_constants* k, const rts_ligh
         for (int i = 0; i < 3; ++i) p.offsets[l][i] = list->lights[l].xyz[i];
         p.offsets[l][3] = list->lights[l].type == RTS_LIGHT_POINT ? 1.0f : 0.0f;
     }
-    ++c->launches;
-    ++c->lightListTraces;
-    const char* name = "";
-    const hipError_t e = rts::launchShadowLightList(variant, p, (hipStream_t)stream, &name);
-    c->lastKernel = name;
-    return hipStatus(e);
+    return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::lightListTraces, rts::launchShadowLightList, stream);
 }
 
 int rts_trace_light_list_device(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* d_positions,
@@ -1086,27 +1065,12 @@ int rts_trace_light_list_stripes_device(rts_ctx* c, const rts_constants* k, cons
     return traceLightListImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_mask, stream);
 }
 
-// The host form: rows [row_begin, row_end) travel as a frame of their own through the context's staging buffers (the list carries no
-// per-pixel jitter, so the frame index of a pixel plays no part).
+// The host form goes through traceStagedRows like the other host entries, the list in the light's place and the map in the active
+// map's.  traceStagedRows sets pixelBase around the call all the same; a list carries no per-pixel jitter, so no list trace reads it.
 int rts_trace_light_list(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* positions, const uint8_t* lights_map,
                          uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
-    if (!c || !k || !positions || !mask || W == 0 || H == 0 || row_begin > row_end || row_end > H || !lightListOk(list)) return RTS_ERR_INVALID_ARG;
-    if (!c->d_bvh) return RTS_ERR_NO_BVH;
-    if (row_begin == row_end) return RTS_OK;
-    RTS_HIP(hipSetDevice(c->device));
-    const uint32_t rows = row_end - row_begin;
-    const size_t first = (size_t)row_begin * W, pixels = (size_t)rows * W;
-    int s = ensure(&c->d_in, &c->inBytes, pixels * 16);
-    if (s == RTS_OK) s = ensure(&c->d_out, &c->outBytes, pixels);
-    if (s == RTS_OK && lights_map) s = ensure(&c->d_act, &c->actBytes, pixels);
-    if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(c->d_in, positions + first * 4, pixels * 16, hipMemcpyHostToDevice));
-    if (lights_map) RTS_HIP(hipMemcpy(c->d_act, lights_map + first, pixels, hipMemcpyHostToDevice));
-    s = rts_trace_light_list_device(c, k, list, (const float*)c->d_in, lights_map ? (const uint8_t*)c->d_act : nullptr, W, rows, 0, rows,
-                                    (uint8_t*)c->d_out, nullptr);
-    if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(mask + first, c->d_out, pixels, hipMemcpyDeviceToHost));
-    return RTS_OK;
+    if (!c || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
+    return traceStagedRows(c, Staged::LightList, k, list, positions, lights_map, W, row_begin, row_end, nullptr, mask);
 }
 
 // Rays (the caller's arguments are checked): occlusion bytes to `out`, or distances to `out_t` where out is NULL.

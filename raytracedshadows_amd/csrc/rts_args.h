@@ -1,0 +1,31 @@
+// The argument rules of include/rts.h that the library (rts_api.cpp) and its host twins (rts_scene.cpp) both apply, written once.
+// Host only: nothing of HIP (tests/cpp/args_host.cpp checks them against slow restatements).
+#pragma once
+#include "../../include/rts.h"
+
+namespace rts {
+
+// a hard light: NULL (the constants' directional light), or a known type with one sample
+inline bool hardLightOk(const rts_light* light) {
+    return !light || (light->type <= RTS_LIGHT_POINT && light->nsamples <= 1);
+}
+
+// a light of up to 64 samples; a table (per-pixel jitter) holds nsamples..64 entries and needs at least 2 samples
+inline bool softLightOk(const rts_light* light) {
+    return !light || (light->type <= RTS_LIGHT_POINT && light->nsamples <= 64 &&
+                      (!light->table || (light->table <= 64 && light->table >= light->nsamples && light->nsamples >= 2)));
+}
+
+// a light list: 1..RTS_MAX_LIST_LIGHTS lights of known types
+inline bool lightListOk(const rts_light_list* list) {
+    if (!list || list->count == 0 || list->count > RTS_MAX_LIST_LIGHTS) return false;
+    for (uint32_t l = 0; l < list->count; ++l) if (list->lights[l].type > RTS_LIGHT_POINT) return false;
+    return true;
+}
+
+// a frame and its row range [row_begin, row_end), which may be empty
+inline bool frameRowsOk(uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end) {
+    return W != 0 && H != 0 && row_begin <= row_end && row_end <= H;
+}
+
+} // namespace rts

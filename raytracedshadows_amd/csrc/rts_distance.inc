@@ -279,24 +279,28 @@ __global__ __launch_bounds__(256) void traceRaysDistanceKernel(TraceParams p) {
     if (live) p.distance[i] = __uint_as_float(best);
 }
 
+// The host side of a block launch, here and in rts_soft_distance.inc and rts_light_list.inc: the GEOM of the packet kernels (2: bands on a
+// 2-D grid, 1: rows on a 2-D grid, 0: general) and the grid.  (launchShadowMaskActive and launchActivePacket keep their own copy of the
+// geometry choice: they live in rts_kernels.hip, whose text is part of the kernel-build hash that the committed counter profiles carry.)
+static int packetGeom(const TraceParams& p) {
+    if (p.grid2d && p.nStripes > 1 && p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0) return 2;
+    return (p.grid2d && p.nStripes <= 1) ? 1 : 0;
+}
+static dim3 blockGrid(const TraceParams& p) { return p.grid2d ? dim3(p.blocksX, p.blocksY) : dim3(p.gridBlocks); }
+
 hipError_t launchShadowDistance(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
+    static const char* const names[3] = { "shadowDistancePacketKernel<general>", "shadowDistancePacketKernel<rows>", "shadowDistancePacketKernel<bands>" };
     if (!p.distance) return hipErrorInvalidValue;
-    dim3 grid(p.gridBlocks);
-    if (p.grid2d) grid = dim3(p.blocksX, p.blocksY);
+    const dim3 grid = blockGrid(p);
     if (variant == V_SHARE) {
         *name = "shadowDistanceShareKernel";
         hipLaunchKernelGGL(shadowDistanceShareKernel, grid, dim3(256), 0, stream, p);
     } else if (variant == V_PACKET) {
-        if (p.grid2d && p.nStripes > 1 && p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0) {
-            *name = "shadowDistancePacketKernel<bands>";
-            hipLaunchKernelGGL(shadowDistancePacketKernel<2>, grid, dim3(64), 0, stream, p);
-        } else if (p.grid2d && p.nStripes <= 1) {
-            *name = "shadowDistancePacketKernel<rows>";
-            hipLaunchKernelGGL(shadowDistancePacketKernel<1>, grid, dim3(64), 0, stream, p);
-        } else {
-            *name = "shadowDistancePacketKernel<general>";
-            hipLaunchKernelGGL(shadowDistancePacketKernel<0>, grid, dim3(64), 0, stream, p);
-        }
+        const int geom = packetGeom(p);
+        *name = names[geom];
+        if (geom == 2) hipLaunchKernelGGL(shadowDistancePacketKernel<2>, grid, dim3(64), 0, stream, p);
+        else if (geom == 1) hipLaunchKernelGGL(shadowDistancePacketKernel<1>, grid, dim3(64), 0, stream, p);
+        else hipLaunchKernelGGL(shadowDistancePacketKernel<0>, grid, dim3(64), 0, stream, p);
     } else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -157,23 +157,20 @@ void shadowLightListPacketKernel(TraceParams p) {
 
 template <int SPLIT>
 static hipError_t launchLightListPacket(const TraceParams& p, dim3 grid, hipStream_t stream, const char** name) {
-    if (p.grid2d && p.nStripes > 1 && p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0) {
-        *name = SPLIT == 4 ? "shadowLightListPacketKernel<4,bands>" : "shadowLightListPacketKernel<1,bands>";
-        hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 2>), grid, dim3(64 * SPLIT), 0, stream, p);
-    } else if (p.grid2d && p.nStripes <= 1) {
-        *name = SPLIT == 4 ? "shadowLightListPacketKernel<4,rows>" : "shadowLightListPacketKernel<1,rows>";
-        hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 1>), grid, dim3(64 * SPLIT), 0, stream, p);
-    } else {
-        *name = SPLIT == 4 ? "shadowLightListPacketKernel<4,general>" : "shadowLightListPacketKernel<1,general>";
-        hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 0>), grid, dim3(64 * SPLIT), 0, stream, p);
-    }
+    static const char* const names[2][3] = {
+        { "shadowLightListPacketKernel<1,general>", "shadowLightListPacketKernel<1,rows>", "shadowLightListPacketKernel<1,bands>" },
+        { "shadowLightListPacketKernel<4,general>", "shadowLightListPacketKernel<4,rows>", "shadowLightListPacketKernel<4,bands>" } };
+    const int geom = packetGeom(p);                                      // (rts_distance.inc)
+    *name = names[SPLIT == 4][geom];
+    if (geom == 2) hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 2>), grid, dim3(64 * SPLIT), 0, stream, p);
+    else if (geom == 1) hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 1>), grid, dim3(64 * SPLIT), 0, stream, p);
+    else hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 0>), grid, dim3(64 * SPLIT), 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t launchShadowLightList(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
     if (!p.mask || p.nsamples < 1 || p.nsamples > 8) return hipErrorInvalidValue;
-    dim3 grid(p.gridBlocks);
-    if (p.grid2d) grid = dim3(p.blocksX, p.blocksY);
+    const dim3 grid = blockGrid(p);
     if (variant == V_SHARE) {
         *name = "shadowLightListShareKernel";
         hipLaunchKernelGGL(shadowLightListShareKernel, grid, dim3(256), 0, stream, p);

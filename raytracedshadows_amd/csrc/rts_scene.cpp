@@ -6,6 +6,7 @@
 // the buffers this file produces.
 #include "../../include/rts_scene.h"
 #include "rts_closest_hit.h"
+#include "rts_args.h"
 
 #include <atomic>
 #include <cmath>
@@ -121,7 +122,7 @@ extern "C" int rtsh_facing_active(const rts_constants* k, const rts_light* light
     return RTS_OK;
 }
 
-// ---- occluder distance on the host (include/rts_scene.h): the checker of rts_trace_shadow_distance* and rts_trace_rays_distance* ----
+// ---- one ray's occluder distance on the host (include/rts_scene.h): the checker of rts_trace_rays_distance*, and of the frames below ----
 // The definition of include/rts.h spelled as one straight loop per ray: the reference's walk (comp:75-111) without its return at a
 // hit, the reference's box test (comp:61-73, GLSL compare-select min / max) and triangle test (comp:41-59), and the library's ray
 // set-up in its general form (comp:128-146 + the point-light extension; rts_kernels.hip: makeShadowRay below its fast path, whose
@@ -229,31 +230,10 @@ extern "C" int rtsh_rays_distance(const rts_vec4u* packed, size_t count_vec4, co
     return RTS_OK;
 }
 
-extern "C" int rtsh_shadow_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_light* light,
-                                    const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
-                                    uint32_t row_end, float* distance, uint8_t* mask, int threads) {
-    if (!packed || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
-    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 1)) return RTS_ERR_INVALID_ARG;     // one sample in this version
-    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
-    if (s != RTS_OK) return s;
-    const uint32_t* bvh = (const uint32_t*)packed;
-    const uint32_t lightType = light ? light->type : (uint32_t)RTS_LIGHT_DIRECTIONAL;
-    const V3 L = light ? V3{ light->xyz[0], light->xyz[1], light->xyz[2] } : V3{ k->lightDirection[0], k->lightDirection[1], k->lightDirection[2] };
-    const size_t first = (size_t)row_begin * W;
-    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t j) {
-        const size_t i = first + j;
-        if (active && !active[i]) { distance[i] = 0.0f; if (mask) mask[i] = 0; return; }
-        const float* q = positions + i * 4;
-        const uint32_t best = rayDistanceBits(bvh, shadowRay(k->cameraPosition, V3{ q[0], q[1], q[2] }, lightType, L));
-        distance[i] = asFloat(best);
-        if (mask) mask[i] = best == 0x7F800000u ? 1 : 0;                 // comp:148-150
-    });
-    return RTS_OK;
-}
-
-// ---- soft-shadow occluder distance on the host (include/rts_scene.h): the checker of rts_trace_soft_distance* -----------------------
+// ---- occluder distance of a frame on the host (include/rts_scene.h): the checker of rts_trace_shadow_distance* and rts_trace_soft_distance* ----
 // The definition of include/rts.h as a straight loop over (pixel, sample): the light position of sample j (rts_light: offsets[j], or
-// the table entry the pixel's hashed start picks), the ray and the one-ray distance of rtsh_shadow_distance above, an integer minimum.
+// the table entry the pixel's hashed start picks), the ray and the one-ray distance above, an integer minimum.  One sample: the hard
+// light itself, and the count of unoccluded samples is the 0/1 shadow byte.
 namespace rts_harness {
 namespace {
 inline uint32_t hash32(uint32_t v) {                                     // rts_light.table (include/rts.h)
@@ -268,19 +248,15 @@ inline uint32_t sampleIndex(uint32_t table, uint32_t sample, uint32_t pixel) {
 } // namespace
 } // namespace rts_harness
 
-extern "C" int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_light* light,
-                                  const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
-                                  uint32_t row_end, float* distance, uint8_t* mask, int threads) {
-    if (!packed || !k || !positions || !distance || W == 0 || H == 0 || row_begin > row_end || row_end > H) return RTS_ERR_INVALID_ARG;
-    if (light && (light->type > RTS_LIGHT_POINT || light->nsamples > 64 ||
-                  (light->table && (light->table > 64 || light->table < light->nsamples || light->nsamples < 2)))) return RTS_ERR_INVALID_ARG;
+// rows [row_begin, row_end) of a frame, ns samples per pixel (the light's rule checked by the caller; ns > 1 only with a light)
+static int frameDistance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_light* light, uint32_t ns, uint32_t table,
+                         const float* positions, const uint8_t* active, uint32_t W, uint32_t row_begin, uint32_t row_end,
+                         float* distance, uint8_t* mask, int threads) {
     const int s = rts_bvh_validate(packed, count_vec4, nullptr);
     if (s != RTS_OK) return s;
     const uint32_t* bvh = (const uint32_t*)packed;
     const uint32_t lightType = light ? light->type : (uint32_t)RTS_LIGHT_DIRECTIONAL;
     const V3 L0 = light ? V3{ light->xyz[0], light->xyz[1], light->xyz[2] } : V3{ k->lightDirection[0], k->lightDirection[1], k->lightDirection[2] };
-    const uint32_t ns = (light && light->nsamples > 1) ? light->nsamples : 1u;
-    const uint32_t table = ns > 1 ? light->table : 0u;
     const size_t first = (size_t)row_begin * W;
     parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t n) {
         const size_t i = first + n;
@@ -303,19 +279,30 @@ extern "C" int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, co
     return RTS_OK;
 }
 
+extern "C" int rtsh_shadow_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_light* light,
+                                    const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                    uint32_t row_end, float* distance, uint8_t* mask, int threads) {
+    if (!packed || !k || !positions || !distance || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::hardLightOk(light)) return RTS_ERR_INVALID_ARG;            // one sample in this version
+    return frameDistance(packed, count_vec4, k, light, 1u, 0u, positions, active, W, row_begin, row_end, distance, mask, threads);
+}
+
+extern "C" int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_light* light,
+                                  const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                  uint32_t row_end, float* distance, uint8_t* mask, int threads) {
+    if (!packed || !k || !positions || !distance || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::softLightOk(light)) return RTS_ERR_INVALID_ARG;
+    const uint32_t ns = (light && light->nsamples > 1) ? light->nsamples : 1u;
+    return frameDistance(packed, count_vec4, k, light, ns, ns > 1 ? light->table : 0u, positions, active, W, row_begin, row_end, distance, mask, threads);
+}
+
 // ---- light lists on the host (include/rts_scene.h): the checker of rts_trace_light_list*, and the light map of a deferred renderer ----
 // The definition of include/rts.h as a straight loop over (pixel, light): light l's ray and one-ray distance as rtsh_shadow_distance
 // takes them for that light alone, its bit set where the distance is +Inf.
 namespace rts_harness {
-bool lightListOk(const rts_light_list* list) {
-    if (!list || list->count == 0 || list->count > RTS_MAX_LIST_LIGHTS) return false;
-    for (uint32_t l = 0; l < list->count; ++l) if (list->lights[l].type > RTS_LIGHT_POINT) return false;
-    return true;
-}
-
 // Shared by the host and device facing passes: one CombineParams per light, as makeCombineParams condenses that light alone.
 int makeFacingLights(const rts_constants* k, const rts_light_list* list, bool havePositions, FacingLights* out) {
-    if (!k || !out || !lightListOk(list)) return RTS_ERR_INVALID_ARG;
+    if (!k || !out || !rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
     out->count = list->count;
     for (uint32_t l = 0; l < list->count; ++l) {
         rts_light one;
@@ -333,8 +320,7 @@ int makeFacingLights(const rts_constants* k, const rts_light_list* list, bool ha
 extern "C" int rtsh_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_light_list* list,
                                const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
                                uint32_t row_end, uint8_t* mask, int threads) {
-    if (!packed || !k || !positions || !mask || W == 0 || H == 0 || row_begin > row_end || row_end > H || !lightListOk(list))
-        return RTS_ERR_INVALID_ARG;
+    if (!packed || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
     const int s = rts_bvh_validate(packed, count_vec4, nullptr);
     if (s != RTS_OK) return s;
     const uint32_t* bvh = (const uint32_t*)packed;

@@ -138,23 +138,20 @@ void shadowSoftDistancePacketKernel(TraceParams p) {
 
 template <int SPLIT>
 static hipError_t launchSoftDistancePacket(const TraceParams& p, dim3 grid, hipStream_t stream, const char** name) {
-    if (p.grid2d && p.nStripes > 1 && p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0) {
-        *name = SPLIT == 4 ? "shadowSoftDistancePacketKernel<4,bands>" : "shadowSoftDistancePacketKernel<1,bands>";
-        hipLaunchKernelGGL((shadowSoftDistancePacketKernel<SPLIT, 2>), grid, dim3(64 * SPLIT), 0, stream, p);
-    } else if (p.grid2d && p.nStripes <= 1) {
-        *name = SPLIT == 4 ? "shadowSoftDistancePacketKernel<4,rows>" : "shadowSoftDistancePacketKernel<1,rows>";
-        hipLaunchKernelGGL((shadowSoftDistancePacketKernel<SPLIT, 1>), grid, dim3(64 * SPLIT), 0, stream, p);
-    } else {
-        *name = SPLIT == 4 ? "shadowSoftDistancePacketKernel<4,general>" : "shadowSoftDistancePacketKernel<1,general>";
-        hipLaunchKernelGGL((shadowSoftDistancePacketKernel<SPLIT, 0>), grid, dim3(64 * SPLIT), 0, stream, p);
-    }
+    static const char* const names[2][3] = {
+        { "shadowSoftDistancePacketKernel<1,general>", "shadowSoftDistancePacketKernel<1,rows>", "shadowSoftDistancePacketKernel<1,bands>" },
+        { "shadowSoftDistancePacketKernel<4,general>", "shadowSoftDistancePacketKernel<4,rows>", "shadowSoftDistancePacketKernel<4,bands>" } };
+    const int geom = packetGeom(p);                                      // (rts_distance.inc)
+    *name = names[SPLIT == 4][geom];
+    if (geom == 2) hipLaunchKernelGGL((shadowSoftDistancePacketKernel<SPLIT, 2>), grid, dim3(64 * SPLIT), 0, stream, p);
+    else if (geom == 1) hipLaunchKernelGGL((shadowSoftDistancePacketKernel<SPLIT, 1>), grid, dim3(64 * SPLIT), 0, stream, p);
+    else hipLaunchKernelGGL((shadowSoftDistancePacketKernel<SPLIT, 0>), grid, dim3(64 * SPLIT), 0, stream, p);
     return hipGetLastError();
 }
 
 hipError_t launchShadowSoftDistance(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
     if (!p.distance || p.nsamples < 2 || p.nsamples > 64) return hipErrorInvalidValue;
-    dim3 grid(p.gridBlocks);
-    if (p.grid2d) grid = dim3(p.blocksX, p.blocksY);
+    const dim3 grid = blockGrid(p);
     if (variant == V_SHARE) {
         *name = "shadowSoftDistanceShareKernel";
         hipLaunchKernelGGL(shadowSoftDistanceShareKernel, grid, dim3(256), 0, stream, p);

@@ -187,6 +187,44 @@ def test_active_maps(ctx, kernel, key):
         dev.close()
 
 
+_HOST_ROWS = {}
+
+
+def _host_rows_case():
+    """Frame 61 x 37, the checker map (zero bytes and set bytes), and the twin's values under that map: computed once."""
+    if not _HOST_ROWS:
+        fr = frame(61, 37)
+        active = _maps(fr, "point")["checker"]
+        assert 0 < np.count_nonzero(active[3:30]) < active[3:30].size
+        want = api.shadow_distance(fr.packed, fr.k, fr.lights["point"], fr.pos, fr.W, fr.H, active=active)
+        for a in (active,) + want:
+            a.setflags(write=False)
+        _HOST_ROWS.update(fr=fr, active=active, want=want)
+    return _HOST_ROWS["fr"], _HOST_ROWS["active"], _HOST_ROWS["want"]
+
+
+@pytest.mark.parametrize("kernel", [7, 3])
+def test_host_form_with_an_active_map_and_a_row_range(ctx, kernel):
+    """The host-pointer form with a per-pixel map AND a row range: rows [3, 30) of the positions and of the map travel through the
+    staging buffers as a frame of their own.  Inside the rows the twin's bits, outside them the guard the arrays were filled with."""
+    fr, active, want = _host_rows_case()
+    rows = (np.arange(fr.H) >= 3) & (np.arange(fr.H) < 30)
+    ctx.set_bvh(fr.packed)
+    try:
+        ctx.set_option("kernel", kernel)
+        out, om = np.full((fr.H, fr.W), GUARD_F, np.float32), np.full((fr.H, fr.W), GUARD_B, np.uint8)
+        ctx.trace_shadow_distance(fr.k, fr.pos, fr.W, fr.H, light=fr.lights["point"], row_begin=3, row_end=30, active=active, out=out, mask=om)
+        assert ctx.last_kernel_name() == _name(kernel, fr.W * 27), ctx.last_kernel_name()
+        _same((out, om), _expect(want, None, rows), (kernel, "host rows with a map"))
+        out = np.full((fr.H, fr.W), GUARD_F, np.float32)
+        d, m = ctx.trace_shadow_distance(fr.k, fr.pos, fr.W, fr.H, light=fr.lights["point"], row_begin=3, row_end=30, active=active, out=out,
+                                         want_mask=False)
+        assert d is out and m is None
+        assert np.array_equal(bits(out), bits(_expect(want, None, rows)[0])), (kernel, "distances alone")
+    finally:
+        ctx.set_option("kernel", -1)
+
+
 @pytest.mark.parametrize("band", [8, 16, 24, 32])
 def test_stripes(ctx, band):
     fr = frame(61, 37)

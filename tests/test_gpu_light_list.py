@@ -205,6 +205,44 @@ def test_row_ranges_leave_the_other_rows(ctx, kernel, split):
         dev.close()
 
 
+_HOST_ROWS = {}
+
+
+def _host_rows_case():
+    """Frame 61 x 37, a 3-light list, the mixed map (zero bytes, set bytes, bits at and above the count), and the twin's bytes under
+    that map: computed once."""
+    if not _HOST_ROWS:
+        fr = list_frame(61, 37)
+        lights = make_list("3")
+        m = _maps(fr, lights.count)["mixed"]
+        inside = m[3:30]
+        assert (inside == 0).any() and ((inside & 7) != 0).any() and ((inside >> 3) != 0).any()
+        want = api.light_list(fr.packed, fr.k, lights, fr.pos, fr.W, fr.H, lights_map=m)
+        m.setflags(write=False)
+        want.setflags(write=False)
+        _HOST_ROWS.update(fr=fr, lights=lights, map=m, want=want)
+    return _HOST_ROWS["fr"], _HOST_ROWS["lights"], _HOST_ROWS["map"], _HOST_ROWS["want"]
+
+
+@pytest.mark.parametrize("kernel,split", FORMS)
+def test_host_form_with_a_light_map_and_a_row_range(ctx, kernel, split):
+    """The host-pointer form with a per-pixel map AND a row range: rows [3, 30) of the positions and of the map travel through the
+    staging buffers as a frame of their own.  Inside the rows the twin's bytes, outside them the guard the array was filled with."""
+    fr, lights, m, want = _host_rows_case()
+    rows = (np.arange(fr.H) >= 3) & (np.arange(fr.H) < 30)
+    ctx.set_bvh(fr.packed)
+    try:
+        ctx.set_option("kernel", kernel)
+        ctx.set_option("soft_split", split)
+        out = np.full((fr.H, fr.W), GUARD, np.uint8)
+        got = ctx.trace_light_list(fr.k, lights, fr.pos, fr.W, fr.H, lights_map=m, row_begin=3, row_end=30, out=out)
+        assert got is out
+        assert ctx.last_kernel_name() == _name(kernel, split), ctx.last_kernel_name()
+        _same(out, _expect(want, None, rows), (kernel, split, "host rows with a map"))
+    finally:
+        _reset(ctx)
+
+
 @pytest.mark.parametrize("kernel,split,band", [(3, 1, 8), (3, 1, 16), (3, 0, 8), (3, 0, 16), (7, 1, 16)])
 def test_stripes(ctx, kernel, split, band):
     fr = list_frame(61, 37)

@@ -155,6 +155,49 @@ def test_table_jitter_whole_rows_and_host_form(ctx, kernel, split):
         dev.close()
 
 
+_HOST_ROWS = {}
+
+
+def _host_rows_case():
+    """Frame 61 x 37 under 5 of 16 jittered samples, the checker map (zero bytes and set bytes), and the twin's values under that
+    map: computed once."""
+    if not _HOST_ROWS:
+        fr = soft_frame(61, 37)
+        light = fr.light(("point", 5, 16, RADIUS))
+        assert light.nsamples == 5 and light.table == 16
+        active = _maps(fr)["checker"]
+        assert 0 < np.count_nonzero(active[3:30]) < active[3:30].size
+        want = api.soft_distance(fr.packed, fr.k, light, fr.pos, fr.W, fr.H, active=active)
+        for a in (active,) + want:
+            a.setflags(write=False)
+        _HOST_ROWS.update(fr=fr, light=light, active=active, want=want)
+    return _HOST_ROWS["fr"], _HOST_ROWS["light"], _HOST_ROWS["active"], _HOST_ROWS["want"]
+
+
+@pytest.mark.parametrize("kernel,split", [(7, 1), (3, 1), (3, 0)])
+def test_host_form_with_an_active_map_and_a_row_range(ctx, kernel, split):
+    """The host-pointer form with a per-pixel map AND a row range, under per-pixel jitter: rows [3, 30) of the positions and of the
+    map travel through the staging buffers as a frame of their own, and every pixel's samples still start where its index in the
+    caller's frame says ("pixelBase").  Inside the rows the twin's bits, outside them the guard the arrays were filled with."""
+    fr, light, active, want = _host_rows_case()
+    rows = (np.arange(fr.H) >= 3) & (np.arange(fr.H) < 30)
+    ctx.set_bvh(fr.packed)
+    try:
+        ctx.set_option("kernel", kernel)
+        ctx.set_option("soft_split", split)
+        out, om = np.full((fr.H, fr.W), GUARD_F, np.float32), np.full((fr.H, fr.W), GUARD_B, np.uint8)
+        ctx.trace_soft_distance(fr.k, fr.pos, fr.W, fr.H, light=light, row_begin=3, row_end=30, active=active, out=out, mask=om)
+        assert ctx.last_kernel_name() == _name(kernel, split), ctx.last_kernel_name()
+        _same((out, om), _expect(want, None, rows), (kernel, split, "host rows with a map"))
+        out = np.full((fr.H, fr.W), GUARD_F, np.float32)
+        d, m = ctx.trace_soft_distance(fr.k, fr.pos, fr.W, fr.H, light=light, row_begin=3, row_end=30, active=active, out=out, want_mask=False)
+        assert d is out and m is None
+        assert np.array_equal(bits(out), bits(_expect(want, None, rows)[0])), (kernel, split, "distances alone")
+    finally:
+        ctx.set_option("kernel", -1)
+        ctx.set_option("soft_split", 1)
+
+
 def _maps(fr):
     y, x = np.mgrid[0:fr.H, 0:fr.W]
     tile = np.ones((fr.H, fr.W), np.uint8)

@@ -306,6 +306,21 @@ def test_dispatch_geometry_under_address_and_ub_sanitizers(tmp_path):
     assert run.stdout.startswith("ok ") and int(run.stdout.split()[1]) > 2000, run.stdout[-2000:]
 
 
+def test_argument_rules_under_address_and_ub_sanitizers(tmp_path):
+    """rts_args.h alone in a host program of its own (tests/cpp/args_host.cpp, -fsanitize=address,undefined): the hard and the soft
+    light's rule over every (type 0..2, nsamples 0..66, table 0..66), lightListOk over every count 0..9 with one bad type at each
+    position, and the frame check at the row-range corners, against restatements of include/rts.h written the slow way."""
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "args_host")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    os.path.join(root, "tests", "cpp", "args_host.cpp"), "-o", exe], check=True)
+    run = subprocess.run([exe], capture_output=True, text=True)
+    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-2000:])
+    assert run.stdout.startswith("ok ") and int(run.stdout.split()[1]) > 2 * 3 * 67 * 67, run.stdout[-2000:]
+
+
 def test_split_front_order_deals_image_squares_over_the_xcds():
     """xcd_square S: record first_record + r runs on XCD (first_record + r) mod 8 and is taken from that XCD's S x S-tile squares
     (square (rx, ry) belongs to XCD (rx + 3 ry) mod 8) while it has any left in the band; bands stay where they are and the order
