@@ -34,14 +34,20 @@ int rtsh_primary_gbuffer(const rts_vec4u* packed, size_t count_vec4, const float
                          uint64_t* hit_count, int threads);
 
 /* The same pass on the GPU: traces through the BVH already uploaded to `ctx`, writes DEVICE
- * buffers (W*H*4 floats each, d_normals may be NULL), asynchronous on `stream`.  Produces the same bits as the host
- * version (shared code, same FP rules). */
+ * buffers (W*H*4 floats each, d_normals may be NULL), asynchronous on `stream`, on the context's device.  Produces the
+ * same bits as the host version (shared code, same FP rules).  One block per 8x8 tile in a two-dimensional grid, so the
+ * frame may be at most RTSH_GBUFFER_MAX_HEIGHT rows tall: a taller one is RTS_ERR_INVALID_ARG, with nothing launched or
+ * written (the host version has no such limit).  RTS_ERR_NO_BVH before rts_ctx_set_bvh. */
+#define RTSH_GBUFFER_MAX_HEIGHT (8u * 65535u)
 int rtsh_primary_gbuffer_device(rts_ctx* ctx, const float eye[3], const float target[3], float fovy,
                                 uint32_t W, uint32_t H, float* d_positions, float* d_normals, void* stream);
 
 /* Combine pass (Source/Shaders/Combine.frag:18-37 with the default white material):
  * rgb[W*H*3] = 255 * (1.25*max(0,N.L)*mask/samples + 0.15 + 0.05*(1 - max(0, N.-cameraDirection))), 0 where the
- * normal is 0.  light == NULL: directional light from constants->lightDirection; positions needed for point lights. */
+ * normal is 0.  max(0, x) is GLSL's (x > 0 ? x : 0: a NaN N.L or N.V contributes 0); the byte is 255 where
+ * value*255 + 0.5 >= 255, its integer part where it lies in (0, 255), 0 otherwise, NaN included -- saturated before the
+ * conversion, so huge, infinite and NaN normals give defined bytes, the same on the host and the device.
+ * light == NULL: directional light from constants->lightDirection; positions needed for point lights. */
 int rtsh_combine(const rts_constants* constants, const rts_light* light, const float* positions, const float* normals,
                  const uint8_t* mask, uint32_t W, uint32_t H, uint8_t* rgb);
 

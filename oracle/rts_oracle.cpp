@@ -686,7 +686,7 @@ extern "C" void orc_combine(const float* constants, const void* light_v, const f
             const float ambientLight = 0.15f + 0.05f * (1.0f - (nDotV > 0.0f ? nDotV : 0.0f));
             const float result = directLight + ambientLight;
             const float scaled = result * 255.0f + 0.5f;
-            out = scaled >= 255.0f ? 255 : (scaled <= 0.0f ? 0 : (uint8_t)(int)scaled);
+            out = scaled >= 255.0f ? 255 : (scaled > 0.0f ? (uint8_t)(int)scaled : 0);     // a NaN (Inf * 0, Inf - Inf) is 0: never converted
         }
         rgb[i * 3] = rgb[i * 3 + 1] = rgb[i * 3 + 2] = out;
     }

@@ -114,6 +114,8 @@ RTS_HD void shadePixel(const uint32_t* bvh, const Camera& c, uint32_t x, uint32_
 //   direct  = 1.25 * max(0, N.L) * shadowMask            shadowMask = mask / samples
 //   ambient = 0.15 + 0.05 * (1 - max(0, N.(-cameraDirection)))
 //   pixel discarded (left 0) where the normal is 0 (background)
+//   max(0, x) = x > 0 ? x : 0, as GLSL defines it: a NaN N.L or N.V contributes 0 (the ambient term stays)
+//   byte = 255 where scaled >= 255, int(scaled) where 0 < scaled < 255, 0 otherwise (NaN included); scaled = value * 255 + 0.5
 // L = the light direction for a directional light; for the point-light extension L = normalize(light - P).
 struct CombineParams { V3 cam, viewDir /* normalised */, light; uint32_t pointLight; float samples; };
 
@@ -133,13 +135,15 @@ RTS_HD float facingNdl(const CombineParams& c, const float* position4, V3 n) {
 RTS_HD uint8_t combinePixel(const CombineParams& c, const float* position4, const float* normal4, uint8_t mask) {
     V3 n{ normal4[0], normal4[1], normal4[2] };
     if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) return 0;
-    float ndl = facingNdl(c, position4, n); if (ndl < 0) ndl = 0;
-    float ndv = dot(n, mul(c.viewDir, -1.0f)); if (ndv < 0) ndv = 0;
+    float ndl = facingNdl(c, position4, n); ndl = ndl > 0 ? ndl : 0.0f;    // GLSL's max(0.0, x): 0 for a NaN
+    float ndv = dot(n, mul(c.viewDir, -1.0f)); ndv = ndv > 0 ? ndv : 0.0f;
     const float direct = 1.25f * ndl * ((float)mask / c.samples);          // frag:29
     const float ambient = 0.15f + 0.05f * (1.0f - ndv);                     // frag:30
-    float v = direct + ambient;                                             // frag:32 (baseColor = 1)
-    int q = (int)(v * 255.0f + 0.5f); if (q > 255) q = 255; if (q < 0) q = 0;
-    return (uint8_t)q;
+    const float v = direct + ambient;                                       // frag:32 (baseColor = 1)
+    // UNORM8, saturated in float BEFORE the conversion: converting a float outside int's range (a normal of 1e7, +Inf, a NaN from
+    // Inf * 0) is undefined on the host, and the host and the device then disagree.  A NaN is 0.
+    const float scaled = v * 255.0f + 0.5f;
+    return scaled >= 255.0f ? (uint8_t)255 : (scaled > 0.0f ? (uint8_t)(int)scaled : (uint8_t)0);
 }
 
 // The facing mark (include/rts_scene.h, rtsh_facing_active): 0 where the shadow mask's byte cannot reach the image -- the

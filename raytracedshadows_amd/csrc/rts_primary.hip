@@ -133,12 +133,15 @@ extern "C" int rtsh_facing_lights_device(rts_ctx* ctx, const rts_constants* k, c
 extern "C" int rtsh_primary_gbuffer_device(rts_ctx* ctx, const float eye[3], const float target[3], float fovy,
                                            uint32_t W, uint32_t H, float* d_positions, float* d_normals, void* stream) {
     if (!ctx || !eye || !target || !d_positions || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    if (H > RTSH_GBUFFER_MAX_HEIGHT) return RTS_ERR_INVALID_ARG;        // the grid's y extent: refused here, not by the launch
     const void* bvh = rts_ctx_device_bvh(ctx);
     if (!bvh) return RTS_ERR_NO_BVH;
+    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
+    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
     const rts_harness::Camera cam = rts_harness::makeCamera(eye, target, fovy, W, H);
     dim3 grid((W + 7) / 8, (H + 7) / 8), block(64);
     hipLaunchKernelGGL(rts_harness::gbufferKernel, grid, block, 0, (hipStream_t)stream, (const uint32_t*)bvh, cam, W, H,
                        d_positions, d_normals);
-    hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
 }
