@@ -422,6 +422,52 @@ int rts_trace_light_list_stripes_device(rts_ctx* ctx, const rts_constants* const
                                         const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
                                         uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_mask, void* stream);
 
+/* ADAPTIVE SOFT SHADOWS: a probe of a few samples per pixel, the remaining samples only where the probe disagrees -- inside ONE
+ * dispatch, so the rays of the umbra and of the fully lit area beyond the probe are never sent.  For a light of n = nsamples in
+ * [2, 64], a probe count k in [1, n - 1] and pixel p of the rows the call owns:
+ *   sample j's ray is the one rts_trace_shadow_mask* sets up for (p, j) of THIS light: light position xyz + offsets[j], or with
+ *   `table` != 0 offsets[(start(p) + j) mod table] -- start(p) hashed from p's index y*W + x in the caller's FULL frame;
+ *   u_j in {0, 1} = that sample's any-hit byte (1: unoccluded);  c_k = u_0 + ... + u_(k-1),  c_n = u_0 + ... + u_(n-1) -- c_n is
+ *   the byte the soft mask trace writes;
+ *   mask[p]    = 0    where active[p] == 0 (the position is never looked at: NaN allowed),
+ *                0    where c_k == 0,
+ *                n    where c_k == k,
+ *                c_n  otherwise;
+ *   refined[p] = 1 exactly where the c_n case applied, else 0 (inactive pixels included).
+ * Hence mask[p] == c_n wherever refined[p] == 1, and elsewhere mask[p] is 0 or n: a value the full trace could have written for a
+ * unanimous pixel.  A pixel whose probe is unanimous although its full count is not keeps the probe's verdict: that is the quality
+ * cost, and what the per-pixel table is for (neighbouring pixels probe different points of the light).  All of it is integer counting
+ * of bytes that depend on (pixel, sample) alone, so the result does not depend on the order of the samples, on which wave walked which,
+ * or on any option.  Rows outside the range / stripe are not touched.  active and refined may be NULL.
+ *   * light == NULL, nsamples < 2 or > 64, type > RTS_LIGHT_POINT, a table outside nsamples <= table <= 64, probe == 0 or
+ *     probe >= nsamples: RTS_ERR_INVALID_ARG, nothing written.
+ *   * "kernel" picks the FAMILY as for a distance trace: 0, 1, 2, 7 (and -1 below 256 K pixels) the lane-per-ray walk over 16 x 16
+ *     blocks, each wave deciding for its own 8 x 8 quarter; 3..6, 8, 9 (and -1 from 256 K pixels) the stackless packet over 8 x 8
+ *     tiles -- with "soft_split" 1 (default) four waves per tile that deal the probe samples, join their counts in LDS, decide alike,
+ *     and deal the remaining samples over the penumbra pixels; with 0 one wave does both.  A stripe's band is a multiple of 16 rows for
+ *     the first family, of 8 for the second; a stripe that owns no band launches nothing, writes nothing and returns RTS_OK.
+ *     "packet_budget", "packet_share", "xcd_swizzle" and "row_order" apply, for speed only.
+ *   * a tile without an active pixel ends before a ray is set up; a tile without a penumbra pixel ends after its probe.
+ *   * like a distance trace it ignores split tables, tile orders, follow mode, "block_waves", "wide_lane", wave statistics and the
+ *     clock probe, and never drops or alters any of them.
+ *   * the device forms are asynchronous, allocate nothing and read nothing back; under graph capture each adds ONE kernel node,
+ *     constants, light, probe and options by value.  The host form copies in its rows only, traces, copies out and synchronises.
+ *   * get-only option "adaptive_traces": adaptive launches so far ("active_traces", "distance_traces", "soft_distance_traces" and
+ *     "light_list_traces" do not move for them); rts_ctx_last_kernel_name then names "shadowMaskAdaptiveShareKernel" or
+ *     "shadowMaskAdaptivePacketKernel<S,geom>", S = 4 or 1 waves per tile, geom = rows, bands or general as for
+ *     "shadowSoftDistancePacketKernel". */
+int rts_trace_shadow_mask_adaptive(rts_ctx* ctx, const rts_constants* constants, const rts_light* light, const float* positions,
+                                   const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                   uint32_t probe, uint8_t* mask, uint8_t* refined);
+int rts_trace_shadow_mask_adaptive_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light,
+                                          const float* d_positions, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                          uint32_t row_begin, uint32_t row_end, uint32_t probe, uint8_t* d_mask, uint8_t* d_refined,
+                                          void* stream);
+int rts_trace_shadow_mask_adaptive_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_light* light,
+                                                  const float* d_positions, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                                  uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint32_t probe,
+                                                  uint8_t* d_mask, uint8_t* d_refined, void* stream);
+
 /* ---- device-memory and timing plumbing (so callers need no HIP headers) ------ */
 int rts_device_count(int* count);
 int rts_device_malloc(rts_ctx* ctx, void** d_ptr, size_t bytes);

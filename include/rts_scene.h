@@ -96,6 +96,16 @@ int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, const rts_con
                        const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
                        uint32_t row_end, float* distance, uint8_t* mask, int threads);
 
+/* ADAPTIVE SOFT SHADOWS on the host: the definition of rts_trace_shadow_mask_adaptive* (include/rts.h) applied literally, one straight
+ * loop over (pixel, sample) on rtsh_soft_distance's walk and ray set-up -- the first `probe` samples; where they agree, 0 or nsamples;
+ * where they disagree, the remaining samples and the full count.  mask[p] as defined there, refined[p] (nullable) = 1 exactly where the
+ * full count was taken.  Inactive pixels: 0 and 0, positions never read; rows outside [row_begin, row_end) are not touched.
+ * light == NULL, nsamples < 2 or > 64, a bad table, type > RTS_LIGHT_POINT, probe == 0 or probe >= nsamples: RTS_ERR_INVALID_ARG.
+ * Runs without a GPU: the checker of the device forms, byte for byte. */
+int rtsh_shadow_mask_adaptive(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_light* light,
+                              const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                              uint32_t row_end, uint32_t probe, uint8_t* mask, uint8_t* refined, int threads);
+
 /* LIGHT LISTS on the host: the definition of rts_trace_light_list* (include/rts.h) as one straight loop over (pixel, light) on
  * rtsh_shadow_distance's walk -- for rows [row_begin, row_end) and l < list->count, bit l of mask[p] = light l's one-ray distance is
  * +Inf, where lights_map == NULL or bit l of lights_map[p] is set; every other bit is 0.  A pixel whose map byte has no bit below

@@ -201,6 +201,14 @@ _sig("rts_trace_light_list_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTr
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_light_list", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rts_trace_shadow_mask_adaptive", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_shadow_mask_adaptive_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rts_trace_shadow_mask_adaptive_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_shadow_mask_adaptive", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
 _sig("rtsh_facing_lights", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
      C.c_void_p)
 _sig("rtsh_facing_lights_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
@@ -682,6 +690,40 @@ class ShadowContext:
                                                         C.c_void_p(d_mask), C.c_void_p(stream or 0)),
                "rts_trace_light_list_stripes_device")
 
+    # -- adaptive soft shadows (include/rts.h): `probe` samples per pixel, the remaining ones only where the probe disagrees --
+    def trace_shadow_mask_adaptive(self, constants, positions, width, height, light, probe, row_begin=0, row_end=None, active=None,
+                                   out=None, refined=None, want_refined=True):
+        """Host-pointer dispatch; returns ``(uint8[H, W] mask, uint8[H, W] refined)`` (refined None with ``want_refined`` False):
+        the count of unoccluded samples where ``refined`` is 1, else 0 or ``nsamples`` by the probe's verdict.  ``out`` / ``refined``:
+        arrays to write into (rows outside the range keep their contents)."""
+        positions, active = _frame_inputs("trace_shadow_mask_adaptive", positions, width, height, active)
+        row_end = height if row_end is None else row_end
+        mask = out if out is not None else np.zeros((height, width), dtype=np.uint8)
+        if refined is None and want_refined:
+            refined = np.zeros((height, width), dtype=np.uint8)
+        _check(_lib.rts_trace_shadow_mask_adaptive(self._h, C.byref(constants), _ref(light), _ptr(positions), _ptr_or_none(active),
+                                                   width, height, row_begin, row_end, probe, _ptr(mask), _ptr_or_none(refined)),
+               "rts_trace_shadow_mask_adaptive")
+        return mask, refined
+
+    def trace_shadow_mask_adaptive_device(self, constants, d_positions, width, height, d_mask, light, probe, d_refined=None,
+                                          row_begin=0, row_end=None, stream=None, d_active=None):
+        """Device pointers, asynchronous: d_mask = width * height bytes, d_refined / d_active = the same or None."""
+        row_end = height if row_end is None else row_end
+        _check(_lib.rts_trace_shadow_mask_adaptive_device(self._h, C.byref(constants), _ref(light), C.c_void_p(d_positions),
+                                                          C.c_void_p(d_active or 0), width, height, row_begin, row_end, probe,
+                                                          C.c_void_p(d_mask), C.c_void_p(d_refined or 0), C.c_void_p(stream or 0)),
+               "rts_trace_shadow_mask_adaptive_device")
+
+    def trace_shadow_mask_adaptive_stripes_device(self, constants, d_positions, width, height, d_mask, band_rows, n_stripes, stripe,
+                                                  light, probe, d_refined=None, stream=None, d_active=None):
+        """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        _check(_lib.rts_trace_shadow_mask_adaptive_stripes_device(self._h, C.byref(constants), _ref(light), C.c_void_p(d_positions),
+                                                                  C.c_void_p(d_active or 0), width, height, band_rows, n_stripes,
+                                                                  stripe, probe, C.c_void_p(d_mask), C.c_void_p(d_refined or 0),
+                                                                  C.c_void_p(stream or 0)),
+               "rts_trace_shadow_mask_adaptive_stripes_device")
+
     # -- plumbing ---------------------------------------------------------------------------
     def stream_create(self):
         s = C.c_void_p()
@@ -982,6 +1024,23 @@ def soft_distance(packed, constants, light, positions, width, height, active=Non
                                    _ptr_or_none(active), width, height, row_begin, row_end, _ptr(dist),
                                    _ptr_or_none(mask), threads), "rtsh_soft_distance")
     return dist, mask
+
+
+def shadow_mask_adaptive(packed, constants, light, positions, width, height, probe, active=None, row_begin=0, row_end=None, out=None,
+                         refined=None, threads=0, want_refined=True):
+    """The adaptive soft mask on the host (rtsh_shadow_mask_adaptive, no GPU): ``(uint8[H, W] mask, uint8[H, W] refined)`` -- the
+    first ``probe`` samples of every active pixel, the remaining ones only where they disagree (refined None with ``want_refined``
+    False)."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    positions, active = _frame_inputs("shadow_mask_adaptive", positions, width, height, active)
+    row_end = height if row_end is None else row_end
+    mask = out if out is not None else np.zeros((height, width), np.uint8)
+    if refined is None and want_refined:
+        refined = np.zeros((height, width), np.uint8)
+    _check(_lib.rtsh_shadow_mask_adaptive(_ptr(packed), packed.shape[0], C.byref(constants), _ref(light), _ptr(positions),
+                                          _ptr_or_none(active), width, height, row_begin, row_end, probe, _ptr(mask),
+                                          _ptr_or_none(refined), threads), "rtsh_shadow_mask_adaptive")
+    return mask, refined
 
 
 def light_list(packed, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None, threads=0):

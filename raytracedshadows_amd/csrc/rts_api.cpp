@@ -6,6 +6,7 @@
 #include "rts_device.h"
 #include "rts_soft_distance.h"
 #include "rts_light_list.h"
+#include "rts_adaptive.h"
 #include "rts_dispatch.h"
 #include "rts_args.h"
 #include "rts_refit.h"
@@ -43,6 +44,7 @@ struct rts_ctx {
     uint64_t distanceTraces = 0;                      // launches of a distance kernel (get-only option "distance_traces")
     uint64_t softDistanceTraces = 0;                  // launches of a soft distance kernel (get-only option "soft_distance_traces")
     uint64_t lightListTraces = 0;                     // launches of a light list kernel (get-only option "light_list_traces")
+    uint64_t adaptiveTraces = 0;                      // launches of an adaptive soft mask kernel (get-only option "adaptive_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
     int packetShare = 4;
@@ -552,6 +554,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "distance_traces")) { *value = (int)(c->distanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_distance_traces")) { *value = (int)(c->softDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "light_list_traces")) { *value = (int)(c->lightListTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "adaptive_traces")) { *value = (int)(c->adaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
     if (!strcmp(key, "tile_order_planned")) { *value = c->tileOrderPlanned ? 1 : 0; return RTS_OK; }
@@ -949,6 +952,34 @@ int rts_trace_soft_distance_stripes_device(rts_ctx* c, const rts_constants* k, c
     return traceSoftDistanceImpl(c, k, light, d_positions, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_distance, d_mask, stream);
 }
 
+// ---- adaptive soft shadows (include/rts.h): a probe of a few samples per pixel, the others only where the probe disagrees ------------
+// One launch of an adaptive kernel (rts_adaptive.inc) with the geometry, the family rule and the tail of a distance trace.  The probe
+// count and the refined plane travel in the generic rays' slots of the argument block (rts_adaptive.h).
+static int traceAdaptiveImpl(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions, const uint8_t* d_active,
+                             const Dispatch& g, uint32_t probe, uint8_t* d_mask, uint8_t* d_refined, void* stream) {
+    TraceParams p; uint32_t rows = 0; int s;
+    if (beginFrame(c, k, d_positions, d_mask, d_mask && rts::adaptiveLightOk(light, probe), g, p, &rows, &s) != Begin::Go) return s;
+    p.activeMap = d_active;
+    p.out = d_refined;
+    p.nrays = probe;
+    setLight(p, k, light);
+    return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::adaptiveTraces, rts::launchShadowMaskAdaptive, stream);
+}
+
+int rts_trace_shadow_mask_adaptive_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
+                                          const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                          uint32_t probe, uint8_t* d_mask, uint8_t* d_refined, void* stream) {
+    return traceAdaptiveImpl(c, k, light, d_positions, d_active, Dispatch::ofRows(W, H, row_begin, row_end), probe, d_mask, d_refined, stream);
+}
+
+int rts_trace_shadow_mask_adaptive_stripes_device(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* d_positions,
+                                                  const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes,
+                                                  uint32_t stripe, uint32_t probe, uint8_t* d_mask, uint8_t* d_refined, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceAdaptiveImpl(c, k, light, d_positions, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), probe, d_mask, d_refined,
+                             stream);
+}
+
 int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, float* d_out_t, void* stream) {
     if (!c || (n && (!d_rays || !d_out_t)) || n > (1ull << 38)) return RTS_ERR_INVALID_ARG;   // grid.x is 31-bit
     TraceParams p;
@@ -967,9 +998,11 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 // Frames (arguments checked by the caller): only rows [row_begin, row_end) travel -- their positions, map, mask and distances, as a
 // frame of their own, to the device entry of what is being traced.  lights: the rts_light, or for Staged::LightList the rts_light_list;
 // each case below names the type it reads, and nothing else does.  distance: of the distance traces alone, whose mask is optional.
-enum class Staged { Mask, Distance, SoftDistance, LightList };
+// probe, refined: of Staged::Adaptive alone; its refined plane (optional) is staged in the distances' buffer, which it does not use.
+enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive };
 static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, const void* lights, const float* positions, const uint8_t* active,
-                           uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
+                           uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask, uint32_t probe = 0,
+                           uint8_t* refined = nullptr) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
     if (row_begin == row_end) return RTS_OK;
     RTS_HIP(hipSetDevice(c->device));
@@ -977,6 +1010,7 @@ static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, cons
     const size_t first = (size_t)row_begin * W, pixels = (size_t)rows * W;
     int s = ensure(&c->d_in, &c->inBytes, pixels * 16);
     if (s == RTS_OK && distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4);
+    if (s == RTS_OK && refined) s = ensure(&c->d_dist, &c->distBytes, pixels);
     if (s == RTS_OK && mask) s = ensure(&c->d_out, &c->outBytes, pixels);
     if (s == RTS_OK && active) s = ensure(&c->d_act, &c->actBytes, pixels);
     if (s != RTS_OK) return s;
@@ -998,10 +1032,14 @@ static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, cons
         s = rts_trace_soft_distance_device(c, k, (const rts_light*)lights, d_in, d_active, W, rows, 0, rows, d_dist, d_mask, nullptr); break;
     case Staged::LightList:
         s = rts_trace_light_list_device(c, k, (const rts_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
+    case Staged::Adaptive:
+        s = rts_trace_shadow_mask_adaptive_device(c, k, (const rts_light*)lights, d_in, d_active, W, rows, 0, rows, probe, d_mask,
+                                                  refined ? (uint8_t*)c->d_dist : nullptr, nullptr); break;
     }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
     if (distance) RTS_HIP(hipMemcpy(distance + first, c->d_dist, pixels * 4, hipMemcpyDeviceToHost));
+    if (refined) RTS_HIP(hipMemcpy(refined + first, c->d_dist, pixels, hipMemcpyDeviceToHost));
     if (mask) RTS_HIP(hipMemcpy(mask + first, c->d_out, pixels, hipMemcpyDeviceToHost));
     return RTS_OK;
 }
@@ -1071,6 +1109,13 @@ int rts_trace_light_list(rts_ctx* c, const rts_constants* k, const rts_light_lis
                          uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
     if (!c || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
     return traceStagedRows(c, Staged::LightList, k, list, positions, lights_map, W, row_begin, row_end, nullptr, mask);
+}
+
+int rts_trace_shadow_mask_adaptive(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
+                                   uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint32_t probe, uint8_t* mask, uint8_t* refined) {
+    if (!c || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::adaptiveLightOk(light, probe)) return RTS_ERR_INVALID_ARG;
+    return traceStagedRows(c, Staged::Adaptive, k, light, positions, active, W, row_begin, row_end, nullptr, mask, probe, refined);
 }
 
 // Rays (the caller's arguments are checked): occlusion bytes to `out`, or distances to `out_t` where out is NULL.

@@ -16,6 +16,11 @@ inline bool softLightOk(const rts_light* light) {
                       (!light->table || (light->table <= 64 && light->table >= light->nsamples && light->nsamples >= 2)));
 }
 
+// an adaptive trace: a light that MUST be there, of 2..64 samples (softLightOk's type and table rules), and a probe of 1..nsamples - 1
+inline bool adaptiveLightOk(const rts_light* light, uint32_t probe) {
+    return light && light->nsamples >= 2 && softLightOk(light) && probe >= 1 && probe < light->nsamples;
+}
+
 // a light list: 1..RTS_MAX_LIST_LIGHTS lights of known types
 inline bool lightListOk(const rts_light_list* list) {
     if (!list || list->count == 0 || list->count > RTS_MAX_LIST_LIGHTS) return false;

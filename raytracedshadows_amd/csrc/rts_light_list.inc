@@ -179,3 +179,6 @@ hipError_t launchShadowLightList(int variant, const TraceParams& p, hipStream_t 
     if (variant != V_PACKET) return hipErrorInvalidValue;
     return p.softSplit ? launchLightListPacket<4>(p, grid, stream, name) : launchLightListPacket<1>(p, grid, stream, name);
 }
+
+// adaptive soft shadows: a probe of a few samples, the others only in the penumbra (its launch is declared in rts_adaptive.h)
+#include "rts_adaptive.inc"

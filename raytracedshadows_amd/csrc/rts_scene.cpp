@@ -296,6 +296,42 @@ extern "C" int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, co
     return frameDistance(packed, count_vec4, k, light, ns, ns > 1 ? light->table : 0u, positions, active, W, row_begin, row_end, distance, mask, threads);
 }
 
+// ---- adaptive soft shadows on the host (include/rts_scene.h): the checker of rts_trace_shadow_mask_adaptive* ----
+// The definition of include/rts.h applied literally, one straight loop over (pixel, sample) on frameDistance's walk: the probe's
+// samples, then the others only where the probe disagrees.
+extern "C" int rtsh_shadow_mask_adaptive(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_light* light,
+                                         const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                         uint32_t row_end, uint32_t probe, uint8_t* mask, uint8_t* refined, int threads) {
+    if (!packed || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::adaptiveLightOk(light, probe)) return RTS_ERR_INVALID_ARG;
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t n = light->nsamples, table = light->table;
+    const V3 L0{ light->xyz[0], light->xyz[1], light->xyz[2] };
+    const size_t first = (size_t)row_begin * W;
+    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t at) {
+        const size_t i = first + at;
+        if (refined) refined[i] = 0;
+        if (active && !active[i]) { mask[i] = 0; return; }
+        const float* q = positions + i * 4;
+        uint32_t lit = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            if (j == probe && (lit == 0 || lit == probe)) {              // the probe agrees: its verdict, no further ray
+                mask[i] = (uint8_t)(lit ? n : 0u);
+                return;
+            }
+            const float* o = light->offsets[sampleIndex(table, j, (uint32_t)i)];
+            const V3 L{ L0.x + o[0], L0.y + o[1], L0.z + o[2] };
+            const uint32_t one = rayDistanceBits(bvh, shadowRay(k->cameraPosition, V3{ q[0], q[1], q[2] }, light->type, L));
+            lit += one == 0x7F800000u ? 1u : 0u;                         // comp:148, per sample
+        }
+        mask[i] = (uint8_t)lit;                                          // comp:150
+        if (refined) refined[i] = 1;
+    });
+    return RTS_OK;
+}
+
 // ---- light lists on the host (include/rts_scene.h): the checker of rts_trace_light_list*, and the light map of a deferred renderer ----
 // The definition of include/rts.h as a straight loop over (pixel, light): light l's ray and one-ray distance as rtsh_shadow_distance
 // takes them for that light alone, its bit set where the distance is +Inf.

@@ -1,9 +1,11 @@
 """Human-checkable output: OBJ scene -> BVH -> G-buffer (GPU) -> shadow mask (GPU) -> combine -> PPM.
 
-    python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull]
+    python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
 
 --cull: the shadow pass traces only the pixels of the facing mark (rtsh_facing_active_device: not the background, not the surfaces
 that face away from the light) -- the same image, byte for byte.
+--adaptive K: the soft light (--spp, or a soft config) is traced by rts_trace_shadow_mask_adaptive* with a probe of K samples: the
+remaining samples only where the probe disagrees; --refined writes the plane of refined pixels (white = the full count was taken).
 """
 import argparse
 import os
@@ -26,6 +28,9 @@ def main():
     ap.add_argument("--distance", default="", metavar="FILE.ppm",
                     help="also write the occluder distance as a grey-scale image: +Inf (lit) white, the rest scaled to the frame's "
                          "largest finite value (with several samples per pixel, --spp: the nearest blocker over all of them)")
+    ap.add_argument("--adaptive", type=int, default=0, metavar="K",
+                    help="trace the soft light adaptively: K probe samples per pixel, the others only in the penumbra (1 <= K < spp)")
+    ap.add_argument("--refined", default="", metavar="FILE.ppm", help="with --adaptive: also write the refined plane as an image")
     args = ap.parse_args()
     from raytracedshadows_amd import api, workloads
     scene, W, H, light, spp = workloads.CONFIGS[args.config]
@@ -40,13 +45,24 @@ def main():
         d_active = ctx.malloc(W * H) if args.cull else None
         if args.cull:
             api.facing_active_device(ctx, wl.constants, wl.light, d_pos, d_nrm, W, H, d_active)
-        ctx.trace_shadow_mask_device(wl.constants, d_pos, W, H, d_mask, light=wl.light, d_active=d_active)
+        d_refined = ctx.malloc(W * H) if args.adaptive and args.refined else None
+        if args.adaptive:
+            ctx.trace_shadow_mask_adaptive_device(wl.constants, d_pos, W, H, d_mask, wl.light, args.adaptive, d_refined=d_refined,
+                                                  d_active=d_active)
+        else:
+            ctx.trace_shadow_mask_device(wl.constants, d_pos, W, H, d_mask, light=wl.light, d_active=d_active)
         ctx.synchronize()
         print(f"G-buffer + shadow mask on the GPU: {(time.time() - t0) * 1e3:.2f} ms (first call, incl. launch); {ctx.last_kernel_name()}")
         if args.cull:
             active = np.zeros((H, W), np.uint8)
             ctx.d2h(active, d_active)
             print(f"facing mark: {float((active == 0).mean()) * 100:.1f} % of the pixels send no ray")
+        if d_refined:
+            refined = np.zeros((H, W), np.uint8)
+            ctx.d2h(refined, d_refined)
+            os.makedirs(os.path.dirname(os.path.abspath(args.refined)), exist_ok=True)
+            api.write_ppm(args.refined, np.repeat((refined * 255)[..., None], 3, axis=2))
+            print(f"wrote {args.refined}: {float(refined.mean()) * 100:.1f} % of the pixels took the full count of {wl.light.nsamples} samples")
         if args.distance:
             d_dist = ctx.malloc(W * H * 4)
             ctx.trace_soft_distance_device(wl.constants, d_pos, W, H, d_dist, light=wl.light, d_active=d_active)   # (one sample: the distance trace)
