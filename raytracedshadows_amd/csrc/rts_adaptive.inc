@@ -1,5 +1,6 @@
-// ADAPTIVE SOFT SHADOWS (rts_trace_shadow_mask_adaptive*, include/rts.h): included at the end of rts_light_list.inc -- so by
-// rts_kernels.hip, inside namespace rts, after every other kernel -- it adds kernels and changes none.
+// ADAPTIVE SOFT SHADOWS (rts_trace_shadow_mask_adaptive*, include/rts.h): included by rts_distance.inc after the light-list kernels.
+// From the common part (rts_block_common.inc): SoftPixel, softPrologue<false>, tileBlock, tilePixel, blockPixel, tileWave, freshLaneId,
+// launchLoopFamily.
 //
 // For a light of n = p.nsamples samples and a probe count k = p.nrays (rts_adaptive.h: the slots), with u_j the any-hit byte of
 // sample j (1 = unoccluded), c_k = u_0 + ... + u_(k-1) and c_n = u_0 + ... + u_(n-1):
@@ -7,43 +8,17 @@
 // Everything is integer counting of bytes that are functions of (pixel, sample) alone, so the result does not depend on the order
 // the samples are walked in, nor on which wave walked which (DESIGN.md 4.16).
 
-// What every adaptive kernel does in front of its probe: softDistancePrologue's requests and stand-in with this trace's zeros.
-// - the texel and the active byte are requested in one batch;
-// - a pixel that owns no ray gets its zeros HERE, in mask and in refined; from then on a lane is `live` or has nothing to store;
-// - lanes that do not walk take the texel AND the pixel index of the first lane that does (per-pixel jitter hashes the index).
-// -> false: no lane of the wave sends a ray; the same answer in the four waves of a tile.
-__device__ __forceinline__ bool adaptivePrologue(const TraceParams& p, bool owns, uint32_t pix, bool stores, SoftPixel* d) {
-    // (no branch around the requests: a lane without a pixel asks for texel 0 and byte 0 and never looks at them)
-    const f32x4 t = __builtin_nontemporal_load((const f32x4*)p.positions + (owns ? pix : 0u));          // comp:135
-    uint8_t act = 1;
-    if (p.activeMap) act = __builtin_nontemporal_load(p.activeMap + (owns ? pix : 0u));
-    d->live = owns && act != 0;
-    if (owns && !d->live && stores) {
-        __builtin_nontemporal_store((uint8_t)0, &p.mask[pix]);
-        if (p.out) __builtin_nontemporal_store((uint8_t)0, &p.out[pix]);
-    }
-    const uint64_t walkers = __builtin_amdgcn_ballot_w64(d->live);
-    if (walkers == 0) return false;
-    const int firstWalker = __builtin_ctzll(walkers);
-    const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t.x), firstWalker));
-    const float sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t.y), firstWalker));
-    const float sz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, t.z), firstWalker));
-    const uint32_t sp = (uint32_t)__builtin_amdgcn_readlane((int)pix, firstWalker);
-    d->rel = d->live ? F3{ t.x, t.y, t.z } : F3{ sx, sy, sz };
-    d->pix = d->live ? pix : sp;
-    return true;
-}
-
 // Between the phases: a live pixel whose probe was unanimous gets its verdict NOW (0 or n, refined 0) -- the bytes the definition
 // gives it, stored in front of the second walk like the prologue's zeros, so that nothing of such a pixel stays in registers across
 // it.  Then the lanes that do not refine take the texel and pixel index of the first lane that does (d->live becomes `pen`): from
-// here on the wave is in the state adaptivePrologue leaves, with the penumbra as its live set.
+// here on the wave is in the state softPrologue leaves, with the penumbra as its live set.
 // pens != 0.  `stores`: as in the prologue.
 __device__ __forceinline__ void adaptiveRefineSetup(const TraceParams& p, SoftPixel* d, uint32_t ck, bool pen, uint64_t pens, bool stores) {
     if (d->live && !pen && stores) {
         __builtin_nontemporal_store((uint8_t)(ck != 0u ? p.nsamples : 0u), &p.mask[d->pix]);    // (unanimous: c_k is 0 or k)
         if (p.out) __builtin_nontemporal_store((uint8_t)0, &p.out[d->pix]);
     }
+    // (standInTexel with the pixel index, written out: through the helper the lane-per-ray kernel's text changes)
     const int first = __builtin_ctzll(pens);
     const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d->rel.x), first));
     const float sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d->rel.y), first));
@@ -70,13 +45,10 @@ __device__ __forceinline__ void adaptiveStoreRefined(const TraceParams& p, const
 __global__ __launch_bounds__(256) void shadowMaskAdaptiveShareKernel(TraceParams p) {
     __shared__ uint32_t shareSlots[4][64];       // lane numbers exchanged by traverseShare (256 B per wave)
     uint32_t* lds = shareSlots[threadIdx.x >> 6];
-    uint32_t bx, by;
-    if (!blockToXY(p, blockIdx.x, &bx, &by)) return;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t x = bx * 16u + (wave & 1u) * 8u + (lane & 7u);
-    const uint32_t y = ownedRow(p, by * 16u + (wave >> 1) * 8u + (lane >> 3));
+    uint32_t x, y;
+    if (!blockPixel(p, &x, &y)) return;
     SoftPixel d;
-    if (!adaptivePrologue(p, (x < p.W) && (y < p.rowEnd), y * p.W + x, true, &d)) return;
+    if (!softPrologue<false>(p, (x < p.W) && (y < p.rowEnd), y * p.W + x, true, &d)) return;
     const NodeStream bvh = openStream(p);
     const uint32_t probe = (uint32_t)p.nrays;
     uint32_t count = 0;
@@ -94,6 +66,8 @@ __global__ __launch_bounds__(256) void shadowMaskAdaptiveShareKernel(TraceParams
     const uint64_t pens = __builtin_amdgcn_ballot_w64(pen);
     if (pens == 0) { adaptiveStoreUnanimous(p, d, count); return; }
     adaptiveRefineSetup(p, &d, count, pen, pens, true);
+    // (the probe's loop again, shareAnyHit's gate written out in both: as one helper over [from, to) the loop is optimised on its
+    //  own before it is inlined, hoists differently, and this kernel's text moves)
     for (uint32_t s = probe; s < p.nsamples; ++s) {
         const Ray r = makeShadowRay(p, d.rel, s, d.pix);
         const bool unsafe = d.live && !raySafe(r);
@@ -120,14 +94,6 @@ __device__ __forceinline__ uint32_t adaptiveSample(const TraceParams& p, const N
     return (walks[0] && !occluded[0]) ? 1u : 0u;                         // comp:148
 }
 
-// The lane's number from an operand the compiler cannot see through: asked for wherever a count is touched, so that no LDS address is
-// carried in a register across a walk (rts_soft_distance.inc: in the 4-wave form that is the one register too many).
-__device__ __forceinline__ uint32_t freshLaneId() {
-    uint32_t zero = 0;
-    asm volatile("" : "+v"(zero));
-    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
-}
-
 // Stackless packet over 8 x 8 tiles.  GEOM as in shadowSoftDistancePacketKernel (1: a row range on a 2-D grid, 2: one stripe of
 // power-of-two bands, 0: every other geometry).  SPLIT 1: one wave walks the probe, decides, walks the rest.  SPLIT 4: four waves
 // per tile, which map lane -> pixel identically:
@@ -148,20 +114,12 @@ void shadowMaskAdaptivePacketKernel(TraceParams p) {
     static_assert(SPLIT == 1 || SPLIT == 4, "one wave per tile, or four that deal its samples");
     __shared__ uint32_t shareSlots[SPLIT][64];
     __shared__ uint32_t partial[2][SPLIT][64];                           // per phase and wave: unoccluded samples per lane
-    uint32_t bx = blockIdx.x, by = 0;
-    if constexpr (GEOM == 0) { if (!blockToXY(p, blockIdx.x, &bx, &by)) return; }
-    else by = dispatchRow(p, blockIdx.y);
-    // (the wave's number is wave-uniform: said so, the sample counter and the wave's LDS addresses stay on the scalar unit)
-    const uint32_t lane = threadIdx.x & 63u, wave = SPLIT > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
-    const uint32_t x = bx * 8u + (lane & 7u);
-    uint32_t y;
-    if constexpr (GEOM == 2) {
-        const uint32_t band = by >> p.bandShift, within = by - (band << p.bandShift);
-        y = (band * p.nStripes + p.stripe) * p.bandRows + within * 8u + (lane >> 3);
-    } else if constexpr (GEOM == 1) y = p.rowBegin + by * 8u + (lane >> 3);
-    else y = ownedRow(p, by * 8u + (lane >> 3));
+    uint32_t bx, by, x, y;
+    if (!tileBlock<GEOM>(p, &bx, &by)) return;
+    const uint32_t wave = tileWave<SPLIT>();
+    tilePixel<GEOM>(p, bx, by, &x, &y);
     SoftPixel d;
-    if (!adaptivePrologue(p, (x < p.W) && (y < p.rowEnd), y * p.W + x, wave == 0, &d)) return;
+    if (!softPrologue<false>(p, (x < p.W) && (y < p.rowEnd), y * p.W + x, wave == 0, &d)) return;
     const NodeStream bvh = openStream(p);
     const uint32_t probe = (uint32_t)p.nrays;
     partial[0][wave][freshLaneId()] = 0;
@@ -199,27 +157,13 @@ void shadowMaskAdaptivePacketKernel(TraceParams p) {
     adaptiveStoreRefined(p, d, cn);
 }
 
-template <int SPLIT>
-static hipError_t launchAdaptivePacket(const TraceParams& p, dim3 grid, hipStream_t stream, const char** name) {
+hipError_t launchShadowMaskAdaptive(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
+    if (!p.mask || p.nsamples < 2 || p.nsamples > 64 || p.nrays == 0 || p.nrays >= p.nsamples) return hipErrorInvalidValue;
     static const char* const names[2][3] = {
         { "shadowMaskAdaptivePacketKernel<1,general>", "shadowMaskAdaptivePacketKernel<1,rows>", "shadowMaskAdaptivePacketKernel<1,bands>" },
         { "shadowMaskAdaptivePacketKernel<4,general>", "shadowMaskAdaptivePacketKernel<4,rows>", "shadowMaskAdaptivePacketKernel<4,bands>" } };
-    const int geom = packetGeom(p);                                      // (rts_distance.inc)
-    *name = names[SPLIT == 4][geom];
-    if (geom == 2) hipLaunchKernelGGL((shadowMaskAdaptivePacketKernel<SPLIT, 2>), grid, dim3(64 * SPLIT), 0, stream, p);
-    else if (geom == 1) hipLaunchKernelGGL((shadowMaskAdaptivePacketKernel<SPLIT, 1>), grid, dim3(64 * SPLIT), 0, stream, p);
-    else hipLaunchKernelGGL((shadowMaskAdaptivePacketKernel<SPLIT, 0>), grid, dim3(64 * SPLIT), 0, stream, p);
-    return hipGetLastError();
-}
-
-hipError_t launchShadowMaskAdaptive(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
-    if (!p.mask || p.nsamples < 2 || p.nsamples > 64 || p.nrays == 0 || p.nrays >= p.nsamples) return hipErrorInvalidValue;
-    const dim3 grid = blockGrid(p);
-    if (variant == V_SHARE) {
-        *name = "shadowMaskAdaptiveShareKernel";
-        hipLaunchKernelGGL(shadowMaskAdaptiveShareKernel, grid, dim3(256), 0, stream, p);
-        return hipGetLastError();
-    }
-    if (variant != V_PACKET) return hipErrorInvalidValue;
-    return p.softSplit ? launchAdaptivePacket<4>(p, grid, stream, name) : launchAdaptivePacket<1>(p, grid, stream, name);
+    return launchLoopFamily(variant, p, stream, name, shadowMaskAdaptiveShareKernel, "shadowMaskAdaptiveShareKernel", names,
+                            [&](dim3 grid, auto split, auto geom) {
+        constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;
+        hipLaunchKernelGGL((shadowMaskAdaptivePacketKernel<SPLIT, GEOM>), grid, dim3(64 * SPLIT), 0, stream, p); });
 }

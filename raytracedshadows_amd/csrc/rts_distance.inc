@@ -1,5 +1,9 @@
-// OCCLUDER DISTANCE (rts_trace_shadow_distance*, rts_trace_rays_distance*, include/rts.h): included by rts_kernels.hip, inside
-// namespace rts, after every kernel of the mask traces -- it adds kernels and changes none.
+// THE BLOCK TRACES: included by rts_kernels.hip, inside namespace rts, after every kernel of the mask traces -- they add kernels and
+// change none.  The common part first, then this file's family and the three built beside it, each in a file of its own below.
+#include "rts_block_common.inc"
+
+// OCCLUDER DISTANCE (rts_trace_shadow_distance*, rts_trace_rays_distance*, include/rts.h).  From the common part: DIST_NONE,
+// tileBlock, tilePixel, blockPixel, launchPacketGeom, blockGrid.
 //
 // distance = min over every triangle the reference's test accepts on the reference's walk WITHOUT its return at a hit
 // (comp:75-111: a leaf that hits goes on through its miss link, like a leaf that misses) of  c = (t > 0) ? t : +0,  t as
@@ -7,7 +11,6 @@
 // leaves visited do not depend on any hit, and nothing is culled against the best t so far: the boxes and the triangles round
 // differently, and a cull could change a bit.  Every contribution is >= +0, so the float order is the order of the bits as
 // unsigned integers and the minimum is an integer minimum that does not depend on the order of the tests.
-static constexpr uint32_t DIST_NONE = 0x7F800000u;                       // +Inf: no triangle accepted
 
 // comp:41-59, handing the contribution back: triHit's arithmetic, operation for operation (rcpFast behind the same wave-wide gate).
 __device__ __forceinline__ bool triHitT(const Ray& r, F3 v0, F3 e0, F3 e1, uint32_t* c) {
@@ -109,6 +112,12 @@ __device__ __forceinline__ uint32_t traverseShareDistance(const NodeStream& bvh,
     __builtin_amdgcn_wave_barrier();
     return ldsMin[laneId()];
 }
+// shareAnyHit's gate around that walk, every minimum starting at +Inf.
+__device__ __forceinline__ uint32_t shareDistance(const TraceParams& p, const NodeStream& bvh, const Ray& r, bool live, bool unsafe,
+                                                  uint32_t* lds, uint32_t* ldsMin) {
+    if (p.bvhFinite && __builtin_amdgcn_ballot_w64(unsafe) == 0) return traverseShareDistance<true>(bvh, r, live, 0u, lds, ldsMin, DIST_NONE);
+    return traverseShareDistance<false>(bvh, r, live, 0u, lds, ldsMin, DIST_NONE);
+}
 
 // traversePacket's one-ray form for the distance, on packetDescend -- the assembly descent that comes back at leaves.  The leaf is
 // tested here: the members that hit fold t into their minimum and STAY members through the miss link with those that miss, so a
@@ -192,13 +201,12 @@ __device__ __forceinline__ bool distancePrologue(const TraceParams& p, bool owns
         }
         return false;
     }
-    // the stand-in of rts_packet_tile.inc: a lane without a ray sets up the ray of the first lane with one, so that it passes every
-    // wave-wide gate of the set-up that lane passes; exact, since its result is discarded
+    // (standInTexel, written out: through the helper the three packet kernels' text changes)
     const int firstWalker = __builtin_ctzll(walkers);
     const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d->rel.x), firstWalker));
     const float sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d->rel.y), firstWalker));
     const float sz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, d->rel.z), firstWalker));
-    d->rel = d->live ? d->rel : F3{ sx, sy, sz };
+    d->rel = d->live ? d->rel : F3{ sx, sy, sz };                        // (no pixel stand-in: a hard light has no per-pixel jitter)
     return true;
 }
 __device__ __forceinline__ void distanceStore(const TraceParams& p, const DistancePixel& d, uint32_t best) {
@@ -212,41 +220,23 @@ __global__ __launch_bounds__(256) void shadowDistanceShareKernel(TraceParams p) 
     __shared__ uint32_t shareSlots[4][2][64];    // per wave: lane numbers exchanged by the walk, and the owners' minima
     uint32_t* lds = shareSlots[threadIdx.x >> 6][0];
     uint32_t* ldsMin = shareSlots[threadIdx.x >> 6][1];
-    uint32_t bx, by;
-    if (!blockToXY(p, blockIdx.x, &bx, &by)) return;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t x = bx * 16u + (wave & 1u) * 8u + (lane & 7u);
-    const uint32_t y = ownedRow(p, by * 16u + (wave >> 1) * 8u + (lane >> 3));
+    uint32_t x, y;
+    if (!blockPixel(p, &x, &y)) return;
     DistancePixel d;
     if (!distancePrologue(p, (x < p.W) && (y < p.rowEnd), (size_t)y * p.W + x, &d)) return;
     const NodeStream bvh = openStream(p);
     const Ray r = makeShadowRay(p, d.rel, 0u, 0u);
-    const bool unsafe = d.live && !raySafe(r);
-    uint32_t best;
-    if (p.bvhFinite && __builtin_amdgcn_ballot_w64(unsafe) == 0)
-        best = traverseShareDistance<true>(bvh, r, d.live, 0u, lds, ldsMin, DIST_NONE);
-    else
-        best = traverseShareDistance<false>(bvh, r, d.live, 0u, lds, ldsMin, DIST_NONE);
-    distanceStore(p, d, best);
+    distanceStore(p, d, shareDistance(p, bvh, r, d.live, d.live && !raySafe(r), lds, ldsMin));
 }
 
-// Stackless packet, one wave per 8 x 8 tile.  GEOM 1: a contiguous row range on a 2-D grid; 2: one stripe of power-of-two bands on a
-// 2-D grid (the frame row of a tile row is two shifts and a multiply); 0: every other geometry (blockToXY, ownedRow).
+// Stackless packet, one wave per 8 x 8 tile.  GEOM: tilePixel.
 template <int GEOM>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8)))
 void shadowDistancePacketKernel(TraceParams p) {
     __shared__ uint32_t shareSlots[2][64];
-    uint32_t bx = blockIdx.x, by = 0;
-    if constexpr (GEOM == 0) { if (!blockToXY(p, blockIdx.x, &bx, &by)) return; }
-    else by = dispatchRow(p, blockIdx.y);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t x = bx * 8u + (lane & 7u);
-    uint32_t y;
-    if constexpr (GEOM == 2) {
-        const uint32_t band = by >> p.bandShift, within = by - (band << p.bandShift);
-        y = (band * p.nStripes + p.stripe) * p.bandRows + within * 8u + (lane >> 3);
-    } else if constexpr (GEOM == 1) y = p.rowBegin + by * 8u + (lane >> 3);
-    else y = ownedRow(p, by * 8u + (lane >> 3));
+    uint32_t bx, by, x, y;
+    if (!tileBlock<GEOM>(p, &bx, &by)) return;
+    tilePixel<GEOM>(p, bx, by, &x, &y);
     DistancePixel d;
     if (!distancePrologue(p, (x < p.W) && (y < p.rowEnd), (size_t)y * p.W + x, &d)) return;
     const NodeStream bvh = openStream(p);
@@ -270,23 +260,9 @@ __global__ __launch_bounds__(256) void traceRaysDistanceKernel(TraceParams p) {
     }
     r.inv = F3{ 1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z };
     const NodeStream bvh = openStream(p);
-    const bool unsafe = live && !raySafe(r);
-    uint32_t best;
-    if (p.bvhFinite && __builtin_amdgcn_ballot_w64(unsafe) == 0)
-        best = traverseShareDistance<true>(bvh, r, live, 0u, lds, ldsMin, DIST_NONE);
-    else
-        best = traverseShareDistance<false>(bvh, r, live, 0u, lds, ldsMin, DIST_NONE);
+    const uint32_t best = shareDistance(p, bvh, r, live, live && !raySafe(r), lds, ldsMin);
     if (live) p.distance[i] = __uint_as_float(best);
 }
-
-// The host side of a block launch, here and in rts_soft_distance.inc and rts_light_list.inc: the GEOM of the packet kernels (2: bands on a
-// 2-D grid, 1: rows on a 2-D grid, 0: general) and the grid.  (launchShadowMaskActive and launchActivePacket keep their own copy of the
-// geometry choice: they live in rts_kernels.hip, whose text is part of the kernel-build hash that the committed counter profiles carry.)
-static int packetGeom(const TraceParams& p) {
-    if (p.grid2d && p.nStripes > 1 && p.bandShift != 0xFFFFFFFFu && p.rowOrder == 0) return 2;
-    return (p.grid2d && p.nStripes <= 1) ? 1 : 0;
-}
-static dim3 blockGrid(const TraceParams& p) { return p.grid2d ? dim3(p.blocksX, p.blocksY) : dim3(p.gridBlocks); }
 
 hipError_t launchShadowDistance(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
     static const char* const names[3] = { "shadowDistancePacketKernel<general>", "shadowDistancePacketKernel<rows>", "shadowDistancePacketKernel<bands>" };
@@ -295,14 +271,11 @@ hipError_t launchShadowDistance(int variant, const TraceParams& p, hipStream_t s
     if (variant == V_SHARE) {
         *name = "shadowDistanceShareKernel";
         hipLaunchKernelGGL(shadowDistanceShareKernel, grid, dim3(256), 0, stream, p);
-    } else if (variant == V_PACKET) {
-        const int geom = packetGeom(p);
-        *name = names[geom];
-        if (geom == 2) hipLaunchKernelGGL(shadowDistancePacketKernel<2>, grid, dim3(64), 0, stream, p);
-        else if (geom == 1) hipLaunchKernelGGL(shadowDistancePacketKernel<1>, grid, dim3(64), 0, stream, p);
-        else hipLaunchKernelGGL(shadowDistancePacketKernel<0>, grid, dim3(64), 0, stream, p);
-    } else return hipErrorInvalidValue;
-    return hipGetLastError();
+        return hipGetLastError();
+    }
+    if (variant != V_PACKET) return hipErrorInvalidValue;
+    return launchPacketGeom(p, names, name, [&](auto geom) {
+        hipLaunchKernelGGL(shadowDistancePacketKernel<decltype(geom)::value>, grid, dim3(64), 0, stream, p); });
 }
 
 hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
@@ -313,3 +286,7 @@ hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
 
 // the soft-shadow forms: the minimum over a light's samples, built on the walks above (its launch is declared in rts_soft_distance.h)
 #include "rts_soft_distance.inc"
+// light lists: up to 8 hard lights in one dispatch, one bit per light (its launch is declared in rts_light_list.h)
+#include "rts_light_list.inc"
+// adaptive soft shadows: a probe of a few samples, the others only in the penumbra (its launch is declared in rts_adaptive.h)
+#include "rts_adaptive.inc"

@@ -1,5 +1,5 @@
-// LIGHT LISTS (rts_trace_light_list*, include/rts.h): included at the end of rts_soft_distance.inc -- so by rts_kernels.hip, inside
-// namespace rts, after every other kernel -- it adds kernels and changes none.
+// LIGHT LISTS (rts_trace_light_list*, include/rts.h): included by rts_distance.inc after the soft-distance kernels.  From the common
+// part (rts_block_common.inc): tileBlock, tilePixel, blockPixel, tileWave, standInTexel, shareAnyHit, launchLoopFamily.
 //
 // Up to 8 hard lights in one dispatch: bit l of mask[p] = the byte the mask trace writes at p for light l alone, where bit l of the
 // pixel's byte of the light map is set (no map: everywhere), else 0.  p.nsamples is the number of lights, light l travels in
@@ -41,7 +41,7 @@ __device__ __forceinline__ Ray makeListRay(const TraceParams& p, F3 rel, uint32_
 // p.nsamples, 0 where the lane owns no pixel; pix is only looked at where the lane owns one.
 struct ListPixel { bool owns; uint32_t pix; uint32_t bits; F3 rel; };
 
-// The texel and the map's byte are requested in one batch (softDistancePrologue).  -> false: no pixel of the wave's tile has a bit
+// The texel and the map's byte are requested in one batch (softPrologue).  -> false: no pixel of the wave's tile has a bit
 // below p.nsamples; the zeros are stored (`stores`: in the 4-wave form every wave looks at the same tile and only wave 0 writes it)
 // and the wave leaves before the stream is opened.  The same answer in the four waves of a tile.
 __device__ __forceinline__ bool lightListPrologue(const TraceParams& p, bool owns, uint32_t pix, bool stores, ListPixel* d) {
@@ -58,27 +58,13 @@ __device__ __forceinline__ bool lightListPrologue(const TraceParams& p, bool own
     return false;
 }
 
-// Lanes that do not walk light l take the texel of the first lane that does (the stand-in of rts_packet_tile.inc): exact, because
-// their result is discarded, and it keeps the wave-wide gates of the ray set-up on real rays -- a background texel or the garbage an
-// unmarked pixel may hold would send the whole wave down the slow forms.
-__device__ __forceinline__ F3 listStandIn(F3 rel, bool walks, uint64_t walkers) {
-    const int firstWalker = __builtin_ctzll(walkers);
-    const float sx = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel.x), firstWalker));
-    const float sy = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel.y), firstWalker));
-    const float sz = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rel.z), firstWalker));
-    return walks ? rel : F3{ sx, sy, sz };
-}
-
 // Lane per ray: shadowMaskActiveShareKernel's 16 x 16 block, the lights one after the other around traverseShare.  The four waves
 // share nothing but the LDS each owns a quarter of, so each decides for itself.
 __global__ __launch_bounds__(256) void shadowLightListShareKernel(TraceParams p) {
     __shared__ uint32_t shareSlots[4][64];       // lane numbers exchanged by traverseShare (256 B per wave)
     uint32_t* lds = shareSlots[threadIdx.x >> 6];
-    uint32_t bx, by;
-    if (!blockToXY(p, blockIdx.x, &bx, &by)) return;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t x = bx * 16u + (wave & 1u) * 8u + (lane & 7u);
-    const uint32_t y = ownedRow(p, by * 16u + (wave >> 1) * 8u + (lane >> 3));
+    uint32_t x, y;
+    if (!blockPixel(p, &x, &y)) return;
     ListPixel d;
     if (!lightListPrologue(p, (x < p.W) && (y < p.rowEnd), y * p.W + x, true, &d)) return;
     const NodeStream bvh = openStream(p);
@@ -87,13 +73,8 @@ __global__ __launch_bounds__(256) void shadowLightListShareKernel(TraceParams p)
         const bool walks = ((d.bits >> l) & 1u) != 0u;
         const uint64_t walkers = __builtin_amdgcn_ballot_w64(walks);
         if (walkers == 0) continue;                                      // the cull's gain: no ray of this light is set up
-        const Ray r = makeListRay(p, listStandIn(d.rel, walks, walkers), l);
-        const bool unsafe = walks && !raySafe(r);
-        bool occluded;
-        if (p.bvhFinite && __builtin_amdgcn_ballot_w64(unsafe) == 0)
-            occluded = traverseShare<true>(bvh, r, walks, 0u, lds);
-        else
-            occluded = traverseShare<false>(bvh, r, walks, 0u, lds);
+        const Ray r = makeListRay(p, standInTexel(d.rel, walks, walkers), l);   // (lanes that do not walk light l stand in)
+        const bool occluded = shareAnyHit(p, bvh, r, walks, walks && !raySafe(r), lds);
         byte |= (walks && !occluded) ? (1u << l) : 0u;                   // comp:148, as light l's bit
     }
     if (d.owns) __builtin_nontemporal_store((uint8_t)byte, &p.mask[d.pix]);   // comp:150
@@ -112,18 +93,10 @@ void shadowLightListPacketKernel(TraceParams p) {
     static_assert(SPLIT == 1 || SPLIT == 4, "one wave per tile, or four that deal its lights");
     __shared__ uint32_t shareSlots[SPLIT][64];
     __shared__ uint32_t partial[SPLIT][64];                              // per wave: its lights' bits per lane
-    uint32_t bx = blockIdx.x, by = 0;
-    if constexpr (GEOM == 0) { if (!blockToXY(p, blockIdx.x, &bx, &by)) return; }
-    else by = dispatchRow(p, blockIdx.y);
-    // (the wave's number is wave-uniform: said so, the light counter and the wave's LDS addresses stay on the scalar unit)
-    const uint32_t lane = threadIdx.x & 63u, wave = SPLIT > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0u;
-    const uint32_t x = bx * 8u + (lane & 7u);
-    uint32_t y;
-    if constexpr (GEOM == 2) {
-        const uint32_t band = by >> p.bandShift, within = by - (band << p.bandShift);
-        y = (band * p.nStripes + p.stripe) * p.bandRows + within * 8u + (lane >> 3);
-    } else if constexpr (GEOM == 1) y = p.rowBegin + by * 8u + (lane >> 3);
-    else y = ownedRow(p, by * 8u + (lane >> 3));
+    uint32_t bx, by, x, y;
+    if (!tileBlock<GEOM>(p, &bx, &by)) return;
+    const uint32_t wave = tileWave<SPLIT>();
+    tilePixel<GEOM>(p, bx, by, &x, &y);
     ListPixel d;
     if (!lightListPrologue(p, (x < p.W) && (y < p.rowEnd), y * p.W + x, wave == 0, &d)) return;
     const NodeStream bvh = openStream(p);
@@ -134,7 +107,7 @@ void shadowLightListPacketKernel(TraceParams p) {
         const bool walks[1] = { ((d.bits >> l) & 1u) != 0u };
         const uint64_t walkers = __builtin_amdgcn_ballot_w64(walks[0]);
         if (walkers == 0) continue;                                      // the cull's gain, wave-uniform: no ray of this light is set up
-        F3 rel = listStandIn(d.rel, walks[0], walkers);
+        F3 rel = standInTexel(d.rel, walks[0], walkers);
         // (made opaque per light: otherwise the compiler hoists the light-independent half of the set-up out of the loop and keeps
         //  it in registers across the walk -- rts_soft_distance.inc)
         asm volatile("" : "+v"(rel.x), "+v"(rel.y), "+v"(rel.z));
@@ -155,30 +128,13 @@ void shadowLightListPacketKernel(TraceParams p) {
     if (d.owns) __builtin_nontemporal_store((uint8_t)byte, &p.mask[d.pix]);   // comp:150
 }
 
-template <int SPLIT>
-static hipError_t launchLightListPacket(const TraceParams& p, dim3 grid, hipStream_t stream, const char** name) {
+hipError_t launchShadowLightList(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
+    if (!p.mask || p.nsamples < 1 || p.nsamples > 8) return hipErrorInvalidValue;
     static const char* const names[2][3] = {
         { "shadowLightListPacketKernel<1,general>", "shadowLightListPacketKernel<1,rows>", "shadowLightListPacketKernel<1,bands>" },
         { "shadowLightListPacketKernel<4,general>", "shadowLightListPacketKernel<4,rows>", "shadowLightListPacketKernel<4,bands>" } };
-    const int geom = packetGeom(p);                                      // (rts_distance.inc)
-    *name = names[SPLIT == 4][geom];
-    if (geom == 2) hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 2>), grid, dim3(64 * SPLIT), 0, stream, p);
-    else if (geom == 1) hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 1>), grid, dim3(64 * SPLIT), 0, stream, p);
-    else hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, 0>), grid, dim3(64 * SPLIT), 0, stream, p);
-    return hipGetLastError();
+    return launchLoopFamily(variant, p, stream, name, shadowLightListShareKernel, "shadowLightListShareKernel", names,
+                            [&](dim3 grid, auto split, auto geom) {
+        constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;
+        hipLaunchKernelGGL((shadowLightListPacketKernel<SPLIT, GEOM>), grid, dim3(64 * SPLIT), 0, stream, p); });
 }
-
-hipError_t launchShadowLightList(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
-    if (!p.mask || p.nsamples < 1 || p.nsamples > 8) return hipErrorInvalidValue;
-    const dim3 grid = blockGrid(p);
-    if (variant == V_SHARE) {
-        *name = "shadowLightListShareKernel";
-        hipLaunchKernelGGL(shadowLightListShareKernel, grid, dim3(256), 0, stream, p);
-        return hipGetLastError();
-    }
-    if (variant != V_PACKET) return hipErrorInvalidValue;
-    return p.softSplit ? launchLightListPacket<4>(p, grid, stream, name) : launchLightListPacket<1>(p, grid, stream, name);
-}
-
-// adaptive soft shadows: a probe of a few samples, the others only in the penumbra (its launch is declared in rts_adaptive.h)
-#include "rts_adaptive.inc"
