@@ -390,7 +390,7 @@ int rts_trace_soft_distance_stripes_device(rts_ctx* ctx, const rts_constants* co
  * are walked in nor on which wave walked which: bits are joined by an integer OR.
  *   * lights_map: NULL, or W x H bytes (rtsh_facing_lights* makes the one a deferred renderer wants: bit l = the surface faces light l).
  *   * list == NULL, count == 0, count > RTS_MAX_LIST_LIGHTS or a type > RTS_LIGHT_POINT: RTS_ERR_INVALID_ARG, nothing written.
- *     reserved_ is ignored.  Hard lights only in this version (a soft light in a list is a later one).
+ *     reserved_ is ignored.  Hard lights only (soft lights in a list: rts_trace_soft_light_list* below).
  *   * results never depend on an option.  "kernel" picks the FAMILY as for a distance trace: 0, 1, 2, 7 (and -1 below 256 K pixels) the
  *     lane-per-ray walk over 16 x 16 blocks, the lights one after the other; 3..6, 8, 9 (and -1 from 256 K pixels) the stackless packet
  *     over 8 x 8 tiles -- with "soft_split" 1 (default) four waves per tile, wave w walking the lights w and w + 4, their bytes ORed in
@@ -467,6 +467,67 @@ int rts_trace_shadow_mask_adaptive_stripes_device(rts_ctx* ctx, const rts_consta
                                                   const float* d_positions, const uint8_t* d_active, uint32_t W, uint32_t H,
                                                   uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint32_t probe,
                                                   uint8_t* d_mask, uint8_t* d_refined, void* stream);
+
+/* SOFT LIGHT LISTS: up to 8 lights, each hard or soft, in ONE dispatch, one COUNT PLANE per light -- one read of the G-buffer texel,
+ * one launch and one light map for all of a frame's area lights.  The lights share one table of RTS_SOFT_LIST_OFFSETS sample offsets;
+ * light l uses the nsamples entries from `first` on, scaled by its radius (ranges may overlap or coincide).  For pixel p of the rows
+ * the call owns and l < list->count, light l stands for the derived rts_light
+ *   { type, nsamples, xyz, table 0, offsets'[j][c] = radius * offsets[first + j][c] }       (j < nsamples, c < 3)
+ * -- the product ONE rounded float multiply per component, which the set-up then adds to xyz as for any rts_light (the library is
+ * built without FMA contraction, so the product is never fused into that add; radius 1.0f gives the table's entries themselves) -- and
+ *   counts[l * W * H + p] = (lights_map == NULL || (lights_map[p] >> l) & 1)
+ *                           ? the byte rts_trace_shadow_mask_active* writes at p for that derived light alone
+ *                           : 0
+ * So plane l lies in 0 .. max(1, nsamples_l): the number of unoccluded samples.  A hard entry (nsamples 0 or 1) ignores first, radius
+ * and the table in what it computes: its plane is bit l of rts_trace_light_list* for { type, xyz }, as 0 or 1.  Planes l >= count are
+ * never touched; rows outside the range / stripe are not touched in any plane.  A pixel whose map byte has no bit below count gets 0
+ * in every plane, its position is never looked at (NaN allowed) and changes no other pixel.  The per-pixel jitter table
+ * (rts_light.table) is not offered in a list in this version.  A count is a sum of bytes that depend on (pixel, light, sample) alone:
+ * no order of the pairs, no deal over waves and no option can change a byte.
+ *   * counts: count * W * H bytes, plane l at counts + l * W * H.  lights_map: NULL, or W x H bytes (rtsh_facing_lights* makes it from
+ *     the rts_light_list of the same types and positions).
+ *   * RTS_ERR_INVALID_ARG, nothing written, no counter moved: list == NULL, count == 0 or > RTS_MAX_LIST_LIGHTS, a type >
+ *     RTS_LIGHT_POINT, nsamples > RTS_SOFT_LIST_OFFSETS, nsamples >= 2 with first + nsamples > RTS_SOFT_LIST_OFFSETS, a radius that is
+ *     not finite (in any entry, also a hard one), counts == NULL, a bad row range or a bad band as rts_trace_light_list* refuses them.
+ *     reserved_ is ignored.
+ *   * results never depend on an option.  "kernel" picks the FAMILY as for a light list: 0, 1, 2, 7 (and -1 below 256 K pixels) the
+ *     lane-per-ray walk over 16 x 16 blocks, lights in order and samples in order; 3..6, 8, 9 (and -1 from 256 K pixels) the stackless
+ *     packet over 8 x 8 tiles -- with "soft_split" 1 (default) four waves per tile: the (light, sample) PAIRS of the list, flattened in
+ *     list order, are dealt r = w, w + 4, ... over the waves, so a list of many small lights and a list of one large light both keep
+ *     four waves busy; the waves' counts are joined in LDS.  With 0 one wave walks every pair.  8 and 9 run the stackless packet too.
+ *     A stripe's band is a multiple of 16 rows for the first family, of 8 for the second; a stripe that owns no band launches nothing,
+ *     writes nothing and returns RTS_OK.  "packet_budget", "packet_share", "xcd_swizzle" and "row_order" apply, for speed only.
+ *   * a light no pixel of a wave's tile is marked for costs that wave nothing: it is skipped before any ray is set up.
+ *   * like the other block traces it ignores split tables, tile orders, follow mode, "block_waves", "wide_lane", wave statistics and
+ *     the clock probe, and never drops or alters any of them.
+ *   * the device forms are asynchronous, allocate nothing and read nothing back; under graph capture each adds ONE kernel node,
+ *     constants, list and options by value.  The host form copies in its rows only, traces, copies out and synchronises.
+ *   * get-only option "soft_light_list_traces": soft list launches so far (no other counter moves for them); rts_ctx_last_kernel_name
+ *     then names "shadowSoftLightListShareKernel" or "shadowSoftLightListPacketKernel<S,geom>", S = 4 or 1 waves per tile, geom =
+ *     rows, bands or general as for "shadowSoftDistancePacketKernel". */
+enum { RTS_SOFT_LIST_OFFSETS = 48 };
+typedef struct rts_soft_light_entry {      /* 32 bytes */
+    uint32_t type;       /* RTS_LIGHT_DIRECTIONAL / RTS_LIGHT_POINT */
+    uint32_t nsamples;   /* 0 or 1 = hard; 2..48 = soft */
+    uint32_t first;      /* first entry of offsets[] this light uses; first + nsamples <= 48 when nsamples >= 2 */
+    float    radius;     /* scales the shared offsets for this light */
+    float    xyz[3];
+    uint32_t reserved_;  /* ignored */
+} rts_soft_light_entry;
+typedef struct rts_soft_light_list {
+    uint32_t count;                       /* 1..RTS_MAX_LIST_LIGHTS */
+    uint32_t reserved_[3];                /* ignored */
+    rts_soft_light_entry lights[RTS_MAX_LIST_LIGHTS];
+    float offsets[RTS_SOFT_LIST_OFFSETS][4];   /* one sample table shared by all lights; ranges may overlap */
+} rts_soft_light_list;                                                             /* 1040 bytes */
+int rts_trace_soft_light_list(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list, const float* positions,
+                              const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* counts);
+int rts_trace_soft_light_list_device(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                     const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                     uint32_t row_end, uint8_t* d_counts, void* stream);
+int rts_trace_soft_light_list_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                             const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                             uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts, void* stream);
 
 /* ---- device-memory and timing plumbing (so callers need no HIP headers) ------ */
 int rts_device_count(int* count);

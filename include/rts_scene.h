@@ -119,6 +119,15 @@ int rtsh_shadow_mask_adaptive(const rts_vec4u* packed, size_t count_vec4, const 
 int rtsh_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_light_list* list,
                     const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
                     uint8_t* mask, int threads);
+/* SOFT LIGHT LISTS on the host: the definition of rts_trace_soft_light_list* (include/rts.h) as one straight loop over (pixel, light,
+ * sample) on rtsh_soft_distance's walk and ray set-up -- for rows [row_begin, row_end) and l < list->count, counts[l * W * H + p] = the
+ * number of samples j of light l whose one-ray distance from p to xyz + radius * offsets[first + j] (a hard entry: to xyz as given) is
+ * +Inf, where lights_map == NULL or bit l of lights_map[p] is set, else 0.  A pixel whose map byte has no bit below count gets 0 in
+ * every plane and its position is never read; other rows and the planes l >= count are not touched.  The refusals of include/rts.h:
+ * RTS_ERR_INVALID_ARG.  Runs without a GPU: the checker of the device forms, byte for byte. */
+int rtsh_soft_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_soft_light_list* list,
+                         const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                         uint8_t* counts, int threads);
 int rtsh_facing_lights(const rts_constants* constants, const rts_light_list* list, const float* positions, const float* normals,
                        uint32_t W, uint32_t H, uint8_t* lights_map);
 int rtsh_facing_lights_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* d_positions,

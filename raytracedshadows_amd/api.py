@@ -127,6 +127,59 @@ class LightList(C.Structure):
         return Light.make(self.lights[l].type, list(self.lights[l].xyz))
 
 
+class SoftLightEntry(C.Structure):
+    """``rts_soft_light_entry``: one light of a soft light list -- hard (``nsamples`` 0 or 1) or soft (2..48 samples: the entries
+    ``first`` .. ``first + nsamples - 1`` of the list's shared offset table, scaled by ``radius``)."""
+    _fields_ = [("type", C.c_uint32), ("nsamples", C.c_uint32), ("first", C.c_uint32), ("radius", C.c_float), ("xyz", C.c_float * 3),
+                ("reserved_", C.c_uint32)]
+
+
+class SoftLightList(C.Structure):
+    """``rts_soft_light_list``: up to 8 lights, hard or soft, traced in one dispatch, a count plane per light."""
+    _fields_ = [("count", C.c_uint32), ("reserved_", C.c_uint32 * 3), ("lights", SoftLightEntry * 8), ("offsets", (C.c_float * 4) * 48)]
+    MAX = 8
+    OFFSETS = 48
+
+    @classmethod
+    def make(cls, lights, offsets=None):
+        """lights: a sequence of ``(kind, xyz)`` (a hard light), ``(kind, xyz, nsamples, first, radius)`` or ``SoftLightEntry``.
+        offsets: the shared table, at most 48 rows of 3 (or 4) floats; the rows not given are 0."""
+        lights = list(lights)
+        if len(lights) > cls.MAX:
+            raise RtsError(1, "SoftLightList.make: at most 8 lights")
+        sl = cls()
+        sl.count = len(lights)
+        for l, item in enumerate(lights):
+            if isinstance(item, SoftLightEntry):
+                item = (item.type, list(item.xyz), item.nsamples, item.first, item.radius)
+            kind, xyz, nsamples, first, radius = tuple(item) + ((1, 0, 1.0) if len(item) == 2 else ())
+            e = sl.lights[l]
+            e.type, e.nsamples, e.first, e.radius = kind, nsamples, first, np.float32(radius)
+            for i in range(3):
+                e.xyz[i] = np.float32(xyz[i])
+        if offsets is not None:
+            offsets = np.asarray(offsets, dtype=np.float32)
+            if offsets.ndim != 2 or offsets.shape[0] > cls.OFFSETS or offsets.shape[1] < 3:
+                raise RtsError(1, "SoftLightList.make: offsets is at most 48 rows of 3 floats")
+            for j in range(offsets.shape[0]):
+                for i in range(3):
+                    sl.offsets[j][i] = offsets[j, i]
+        return sl
+
+    def light(self, l):
+        """Light ``l`` alone, as the derived ``Light`` of include/rts.h: offsets'[j] = radius * offsets[first + j], the product
+        rounded to float32 on its own; a hard entry gives the hard ``Light``."""
+        e = self.lights[l]
+        if e.nsamples < 2:
+            return Light.make(e.type, list(e.xyz))
+        table = np.array([[self.offsets[e.first + j][i] for i in range(3)] for j in range(e.nsamples)], dtype=np.float32)
+        return Light.make(e.type, list(e.xyz), np.float32(e.radius) * table)
+
+    def hard_list(self):
+        """The ``LightList`` of the same types and positions: what ``facing_lights`` makes this list's light map from."""
+        return LightList.make([(self.lights[l].type, list(self.lights[l].xyz)) for l in range(self.count)])
+
+
 #: numpy view of ``struct BVHNode`` (BVHBuilder.h:8-20)
 BVHNode_dtype = np.dtype([("bboxMin", np.float32, 3), ("prim", np.uint32),
                           ("bboxMax", np.float32, 3), ("next", np.uint32)])
@@ -201,6 +254,14 @@ _sig("rts_trace_light_list_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTr
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_light_list", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rts_trace_soft_light_list", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rts_trace_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_soft_light_list_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_soft_light_list", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
 _sig("rts_trace_shadow_mask_adaptive", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rts_trace_shadow_mask_adaptive_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
@@ -690,6 +751,35 @@ class ShadowContext:
                                                         C.c_void_p(d_mask), C.c_void_p(stream or 0)),
                "rts_trace_light_list_stripes_device")
 
+    # -- soft light lists (include/rts.h): up to 8 lights, hard or soft, in one dispatch, a count plane per light --
+    def trace_soft_light_list(self, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None):
+        """Host-pointer dispatch; returns ``uint8[count, H, W]``: plane ``l`` = light ``l``'s unoccluded samples where ``lights_map``
+        (uint8[H, W], or None: everywhere) has bit ``l`` set.  ``out``: an array of at least ``count`` planes to write the rows into."""
+        positions, lights_map = _frame_inputs("trace_soft_light_list", positions, width, height, lights_map, "lights_map")
+        row_end = height if row_end is None else row_end
+        counts = out if out is not None else np.zeros((lights.count if lights is not None else 1, height, width), dtype=np.uint8)
+        _check(_lib.rts_trace_soft_light_list(self._h, C.byref(constants), _ref(lights), _ptr(positions),
+                                              _ptr_or_none(lights_map), width, height, row_begin, row_end,
+                                              _ptr(counts)), "rts_trace_soft_light_list")
+        return counts
+
+    def trace_soft_light_list_device(self, constants, lights, d_positions, width, height, d_counts, d_lights_map=None, row_begin=0,
+                                     row_end=None, stream=None):
+        """Device pointers, asynchronous: d_counts = count * width * height bytes, d_lights_map = width * height bytes or None."""
+        row_end = height if row_end is None else row_end
+        _check(_lib.rts_trace_soft_light_list_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
+                                                     C.c_void_p(d_lights_map or 0), width, height, row_begin, row_end,
+                                                     C.c_void_p(d_counts), C.c_void_p(stream or 0)),
+               "rts_trace_soft_light_list_device")
+
+    def trace_soft_light_list_stripes_device(self, constants, lights, d_positions, width, height, d_counts, band_rows, n_stripes, stripe,
+                                             d_lights_map=None, stream=None):
+        """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        _check(_lib.rts_trace_soft_light_list_stripes_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
+                                                             C.c_void_p(d_lights_map or 0), width, height, band_rows, n_stripes, stripe,
+                                                             C.c_void_p(d_counts), C.c_void_p(stream or 0)),
+               "rts_trace_soft_light_list_stripes_device")
+
     # -- adaptive soft shadows (include/rts.h): `probe` samples per pixel, the remaining ones only where the probe disagrees --
     def trace_shadow_mask_adaptive(self, constants, positions, width, height, light, probe, row_begin=0, row_end=None, active=None,
                                    out=None, refined=None, want_refined=True):
@@ -1054,6 +1144,19 @@ def light_list(packed, constants, lights, positions, width, height, lights_map=N
                                 _ptr_or_none(lights_map), width, height, row_begin, row_end, _ptr(mask),
                                 threads), "rtsh_light_list")
     return mask
+
+
+def soft_light_list(packed, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None, threads=0):
+    """A soft light list trace on the host (rtsh_soft_light_list, no GPU): ``uint8[count, H, W]``, plane ``l`` = the unoccluded
+    samples of light ``l`` where ``lights_map`` (None: everywhere) has bit ``l`` set.  ``out``: at least ``count`` planes to write into."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    positions, lights_map = _frame_inputs("soft_light_list", positions, width, height, lights_map, "lights_map")
+    row_end = height if row_end is None else row_end
+    counts = out if out is not None else np.zeros((lights.count if lights is not None else 1, height, width), np.uint8)
+    _check(_lib.rtsh_soft_light_list(_ptr(packed), packed.shape[0], C.byref(constants), _ref(lights), _ptr(positions),
+                                     _ptr_or_none(lights_map), width, height, row_begin, row_end, _ptr(counts),
+                                     threads), "rtsh_soft_light_list")
+    return counts
 
 
 def facing_lights(constants, lights, positions, normals):

@@ -7,6 +7,7 @@
 #include "rts_soft_distance.h"
 #include "rts_light_list.h"
 #include "rts_adaptive.h"
+#include "rts_soft_light_list.h"
 #include "rts_dispatch.h"
 #include "rts_args.h"
 #include "rts_refit.h"
@@ -45,6 +46,7 @@ struct rts_ctx {
     uint64_t softDistanceTraces = 0;                  // launches of a soft distance kernel (get-only option "soft_distance_traces")
     uint64_t lightListTraces = 0;                     // launches of a light list kernel (get-only option "light_list_traces")
     uint64_t adaptiveTraces = 0;                      // launches of an adaptive soft mask kernel (get-only option "adaptive_traces")
+    uint64_t softLightListTraces = 0;                 // launches of a soft light list kernel (get-only option "soft_light_list_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
     int packetShare = 4;
@@ -555,6 +557,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "soft_distance_traces")) { *value = (int)(c->softDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "light_list_traces")) { *value = (int)(c->lightListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "adaptive_traces")) { *value = (int)(c->adaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "soft_light_list_traces")) { *value = (int)(c->softLightListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
     if (!strcmp(key, "tile_order_planned")) { *value = c->tileOrderPlanned ? 1 : 0; return RTS_OK; }
@@ -999,10 +1002,12 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 // frame of their own, to the device entry of what is being traced.  lights: the rts_light, or for Staged::LightList the rts_light_list;
 // each case below names the type it reads, and nothing else does.  distance: of the distance traces alone, whose mask is optional.
 // probe, refined: of Staged::Adaptive alone; its refined plane (optional) is staged in the distances' buffer, which it does not use.
-enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive };
+// Staged::SoftLightList: lights is the rts_soft_light_list, mask its count planes -- `count` planes of frameH rows in the caller's
+// buffer, of the staged rows alone on the device.
+enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList };
 static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, const void* lights, const float* positions, const uint8_t* active,
                            uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask, uint32_t probe = 0,
-                           uint8_t* refined = nullptr) {
+                           uint8_t* refined = nullptr, uint32_t frameH = 0) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
     if (row_begin == row_end) return RTS_OK;
     RTS_HIP(hipSetDevice(c->device));
@@ -1011,7 +1016,8 @@ static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, cons
     int s = ensure(&c->d_in, &c->inBytes, pixels * 16);
     if (s == RTS_OK && distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4);
     if (s == RTS_OK && refined) s = ensure(&c->d_dist, &c->distBytes, pixels);
-    if (s == RTS_OK && mask) s = ensure(&c->d_out, &c->outBytes, pixels);
+    const size_t planes = what == Staged::SoftLightList ? ((const rts_soft_light_list*)lights)->count : 1u;
+    if (s == RTS_OK && mask) s = ensure(&c->d_out, &c->outBytes, pixels * planes);
     if (s == RTS_OK && active) s = ensure(&c->d_act, &c->actBytes, pixels);
     if (s != RTS_OK) return s;
     RTS_HIP(hipMemcpy(c->d_in, positions + first * 4, pixels * 16, hipMemcpyHostToDevice));
@@ -1035,12 +1041,15 @@ static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, cons
     case Staged::Adaptive:
         s = rts_trace_shadow_mask_adaptive_device(c, k, (const rts_light*)lights, d_in, d_active, W, rows, 0, rows, probe, d_mask,
                                                   refined ? (uint8_t*)c->d_dist : nullptr, nullptr); break;
+    case Staged::SoftLightList:
+        s = rts_trace_soft_light_list_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
     }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
     if (distance) RTS_HIP(hipMemcpy(distance + first, c->d_dist, pixels * 4, hipMemcpyDeviceToHost));
     if (refined) RTS_HIP(hipMemcpy(refined + first, c->d_dist, pixels, hipMemcpyDeviceToHost));
-    if (mask) RTS_HIP(hipMemcpy(mask + first, c->d_out, pixels, hipMemcpyDeviceToHost));
+    for (size_t l = 0; mask && l < planes; ++l)
+        RTS_HIP(hipMemcpy(mask + l * ((size_t)W * frameH) + first, (const uint8_t*)c->d_out + l * pixels, pixels, hipMemcpyDeviceToHost));
     return RTS_OK;
 }
 
@@ -1109,6 +1118,53 @@ int rts_trace_light_list(rts_ctx* c, const rts_constants* k, const rts_light_lis
                          uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
     if (!c || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
     return traceStagedRows(c, Staged::LightList, k, list, positions, lights_map, W, row_begin, row_end, nullptr, mask);
+}
+
+// ---- soft light lists (include/rts.h): up to 8 lights, hard or soft, in one dispatch, one count plane per light -----------------------
+// One launch of a soft light list kernel (rts_soft_light_list.inc) with the geometry, the family rule and the tail of a distance trace.
+// The list travels in the argument block's 64 sample offsets (rts_soft_light_list.h): the shared table in the first 48, two slots per
+// light behind them, the count in nsamples, the map in the active map's slot, the planes in the mask's.
+static int traceSoftLightListImpl(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
+                                  const uint8_t* d_lights_map, const Dispatch& g, uint8_t* d_counts, void* stream) {
+    TraceParams p; uint32_t rows = 0; int s;
+    if (beginFrame(c, k, d_positions, d_counts, d_counts && rts::softListOk(list), g, p, &rows, &s) != Begin::Go) return s;
+    p.activeMap = d_lights_map;
+    for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
+    p.lightType = RTS_LIGHT_DIRECTIONAL;               // (not read: every light carries its own type)
+    p.nsamples = list->count;
+    p.lightTable = 0;
+    for (int i = 0; i < 3; ++i) p.light[i] = 0.0f;
+    static_assert(sizeof(list->offsets) == sizeof(float) * 4 * RTS_SOFT_LIST_OFFSETS && RTS_SOFT_LIST_OFFSETS + 2 * RTS_MAX_LIST_LIGHTS == 64,
+                  "48 sample slots and two slots per light fill TraceParams::offsets");
+    memcpy(p.offsets, list->offsets, sizeof(list->offsets));
+    for (uint32_t l = 0; l < list->count; ++l) {
+        const rts_soft_light_entry& e = list->lights[l];
+        const bool soft = e.nsamples >= 2;
+        rts::setSoftListEntry(p, l, e.type, soft ? e.nsamples : 1u, soft ? e.first : 0u, e.radius, e.xyz);
+    }
+    return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::softLightListTraces, rts::launchShadowSoftLightList, stream);
+}
+
+int rts_trace_soft_light_list_device(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
+                                     const uint8_t* d_lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                     uint8_t* d_counts, void* stream) {
+    return traceSoftLightListImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofRows(W, H, row_begin, row_end), d_counts, stream);
+}
+
+int rts_trace_soft_light_list_stripes_device(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
+                                             const uint8_t* d_lights_map, uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes,
+                                             uint32_t stripe, uint8_t* d_counts, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceSoftLightListImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_counts, stream);
+}
+
+// The host form goes through traceStagedRows like the other host entries: its rows travel as a frame of their own, whose `count`
+// planes come back to the caller's planes of H rows.
+int rts_trace_soft_light_list(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* positions,
+                              const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* counts) {
+    if (!c || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
+    return traceStagedRows(c, Staged::SoftLightList, k, list, positions, lights_map, W, row_begin, row_end, nullptr, counts, 0, nullptr, H);
 }
 
 int rts_trace_shadow_mask_adaptive(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,

@@ -1,6 +1,7 @@
 // The argument rules of include/rts.h that the library (rts_api.cpp) and its host twins (rts_scene.cpp) both apply, written once.
 // Host only: nothing of HIP (tests/cpp/args_host.cpp checks them against slow restatements).
 #pragma once
+#include <string.h>
 #include "../../include/rts.h"
 
 namespace rts {
@@ -25,6 +26,21 @@ inline bool adaptiveLightOk(const rts_light* light, uint32_t probe) {
 inline bool lightListOk(const rts_light_list* list) {
     if (!list || list->count == 0 || list->count > RTS_MAX_LIST_LIGHTS) return false;
     for (uint32_t l = 0; l < list->count; ++l) if (list->lights[l].type > RTS_LIGHT_POINT) return false;
+    return true;
+}
+
+// a soft light list: 1..RTS_MAX_LIST_LIGHTS entries of known types, each of at most RTS_SOFT_LIST_OFFSETS samples with a finite radius;
+// a soft entry's range [first, first + nsamples) lies inside the shared table (a hard entry's `first` is not looked at)
+inline bool softListOk(const rts_soft_light_list* list) {
+    if (!list || list->count == 0 || list->count > RTS_MAX_LIST_LIGHTS) return false;
+    for (uint32_t l = 0; l < list->count; ++l) {
+        const rts_soft_light_entry& e = list->lights[l];
+        if (e.type > RTS_LIGHT_POINT || e.nsamples > RTS_SOFT_LIST_OFFSETS) return false;
+        if (e.nsamples >= 2 && (uint64_t)e.first + e.nsamples > RTS_SOFT_LIST_OFFSETS) return false;
+        uint32_t bits;
+        memcpy(&bits, &e.radius, sizeof(bits));
+        if ((bits & 0x7F800000u) == 0x7F800000u) return false;           // Inf or NaN: every exponent bit set
+    }
     return true;
 }
 

@@ -290,3 +290,5 @@ hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
 #include "rts_light_list.inc"
 // adaptive soft shadows: a probe of a few samples, the others only in the penumbra (its launch is declared in rts_adaptive.h)
 #include "rts_adaptive.inc"
+// soft light lists: up to 8 lights, hard or soft, in one dispatch, a count plane per light (its launch is declared in rts_soft_light_list.h)
+#include "rts_soft_light_list.inc"

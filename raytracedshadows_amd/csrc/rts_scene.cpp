@@ -380,6 +380,45 @@ extern "C" int rtsh_light_list(const rts_vec4u* packed, size_t count_vec4, const
     return RTS_OK;
 }
 
+// ---- soft light lists on the host (include/rts_scene.h): the checker of rts_trace_soft_light_list* ----
+// The definition of include/rts.h as a straight loop over (pixel, light, sample): sample j of light l aims at xyz + radius *
+// offsets[first + j] -- the product rounded on its own (this file is built without FMA contraction), then frameDistance's add -- and a
+// hard entry at xyz as given; the plane's byte counts the samples whose one-ray distance is +Inf.
+extern "C" int rtsh_soft_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
+                                    const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                    uint32_t row_end, uint8_t* counts, int threads) {
+    if (!packed || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t below = (1u << list->count) - 1u;
+    const size_t first = (size_t)row_begin * W, plane = (size_t)W * H;
+    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t n) {
+        const size_t i = first + n;
+        const uint32_t bits = (lights_map ? lights_map[i] : 0xFFu) & below;
+        const float* q = positions + i * 4;                              // (not read where bits == 0)
+        for (uint32_t l = 0; l < list->count; ++l) {
+            uint32_t lit = 0;
+            if ((bits >> l) & 1u) {
+                const rts_soft_light_entry& e = list->lights[l];
+                const uint32_t ns = e.nsamples > 1 ? e.nsamples : 1u;
+                for (uint32_t j = 0; j < ns; ++j) {
+                    V3 L{ e.xyz[0], e.xyz[1], e.xyz[2] };
+                    if (ns > 1) {
+                        const float* o = list->offsets[e.first + j];
+                        const float ox = e.radius * o[0], oy = e.radius * o[1], oz = e.radius * o[2];
+                        L.x = L.x + ox; L.y = L.y + oy; L.z = L.z + oz;
+                    }
+                    const uint32_t one = rayDistanceBits(bvh, shadowRay(k->cameraPosition, V3{ q[0], q[1], q[2] }, e.type, L));
+                    lit += one == 0x7F800000u ? 1u : 0u;                 // comp:148, per sample
+                }
+            }
+            counts[l * plane + i] = (uint8_t)lit;                        // comp:150
+        }
+    });
+    return RTS_OK;
+}
+
 extern "C" int rtsh_facing_lights(const rts_constants* k, const rts_light_list* list, const float* positions, const float* normals,
                                   uint32_t W, uint32_t H, uint8_t* lights_map) {
     if (!normals || !lights_map || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;

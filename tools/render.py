@@ -1,11 +1,15 @@
 """Human-checkable output: OBJ scene -> BVH -> G-buffer (GPU) -> shadow mask (GPU) -> combine -> PPM.
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
+                           [--soft-list N]
 
 --cull: the shadow pass traces only the pixels of the facing mark (rtsh_facing_active_device: not the background, not the surfaces
 that face away from the light) -- the same image, byte for byte.
 --adaptive K: the soft light (--spp, or a soft config) is traced by rts_trace_shadow_mask_adaptive* with a probe of K samples: the
 remaining samples only where the probe disagrees; --refined writes the plane of refined pixels (white = the full count was taken).
+--soft-list N: the frame is lit by N (1..8) area lights on a ring around the scene's light, each of --spp samples (default 4; N * spp
+<= 48), traced in ONE rts_trace_soft_light_list_device dispatch through the facing map; the image is the mean of the lights' own
+combine passes, each over its count plane.
 """
 import argparse
 import os
@@ -16,6 +20,36 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def soft_list(ctx, wl, W, H, count, spp, out):
+    """A frame lit by `count` area lights of `spp` samples: one list dispatch, then one combine pass per light over its plane."""
+    from raytracedshadows_amd import api, scenes
+    from soft_list_ab import entries
+    if not 1 <= count <= 8 or count * max(spp, 1) > 48:
+        sys.exit("render: --soft-list takes 1..8 lights of at most 48 samples in all")
+    lights = api.SoftLightList.make(entries(wl.scene, count, spp), scenes.jitter_offsets(48, 1.0, 19))
+    d_pos, d_nrm, d_map = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
+    d_counts, d_rgb = ctx.malloc(count * W * H), ctx.malloc(W * H * 3)
+    t0 = time.time()
+    api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
+    api.facing_lights_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, W, H, d_map)
+    ctx.trace_soft_light_list_device(wl.constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
+    ctx.synchronize()
+    print(f"G-buffer + facing map + {count} lights x {spp} samples in one dispatch: {(time.time() - t0) * 1e3:.2f} ms (first call, incl. "
+          f"launch); {ctx.last_kernel_name()}")
+    total, rgb = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.uint8)
+    for l in range(count):
+        api.combine_device(ctx, wl.constants, lights.light(l), d_pos, d_nrm, d_counts + l * W * H, W, H, d_rgb)
+        ctx.synchronize()
+        ctx.d2h(rgb, d_rgb)
+        total += rgb
+    planes = np.zeros((count, H, W), np.uint8)
+    ctx.d2h(planes, d_counts)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    api.write_ppm(out, np.clip(total / count + 0.5, 0, 255).astype(np.uint8))
+    print(f"wrote {out}: {W}x{H}, lit fraction per light {[round(float((planes[l] > 0).mean()), 3) for l in range(count)]}")
 
 
 def main():
@@ -31,6 +65,8 @@ def main():
     ap.add_argument("--adaptive", type=int, default=0, metavar="K",
                     help="trace the soft light adaptively: K probe samples per pixel, the others only in the penumbra (1 <= K < spp)")
     ap.add_argument("--refined", default="", metavar="FILE.ppm", help="with --adaptive: also write the refined plane as an image")
+    ap.add_argument("--soft-list", type=int, default=0, metavar="N",
+                    help="light the frame by N area lights of --spp samples each, traced in one soft light list dispatch")
     args = ap.parse_args()
     from raytracedshadows_amd import api, workloads
     scene, W, H, light, spp = workloads.CONFIGS[args.config]
@@ -39,6 +75,8 @@ def main():
         api.save_bvh(args.save_bvh, wl.packed)
     with api.ShadowContext(0) as ctx:
         ctx.set_bvh(wl.packed)
+        if args.soft_list:
+            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
         t0 = time.time()
         api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
