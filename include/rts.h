@@ -529,6 +529,51 @@ int rts_trace_soft_light_list_stripes_device(rts_ctx* ctx, const rts_constants* 
                                              const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
                                              uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts, void* stream);
 
+/* ADAPTIVE SOFT LIGHT LISTS: a soft light list with a probe count per light -- the two traces above joined inside ONE dispatch: every
+ * light's probe is walked first, and a light's remaining samples only over the pixels whose probe of THAT light disagrees.  The
+ * arguments are those of rts_trace_soft_light_list*, plus `probes` (list->count entries on the host, read by value at the call, under
+ * graph capture too) and the optional plane `refined`.  With n_l = max(1, nsamples_l) and k_l = probes[l], for pixel p of the rows
+ * the call owns and l < list->count:
+ *   k_l == 0            light l is traced in full: counts[l * W * H + p] is byte for byte what rts_trace_soft_light_list* writes, and
+ *                       bit l of refined[p] is 0.
+ *   1 <= k_l <= n_l - 1 (only a soft entry has such a k) counts[l * W * H + p] is the byte rts_trace_shadow_mask_adaptive* writes at p
+ *                       for the derived light of entry l (above: xyz + radius * offsets[first + j], table 0) with probe k_l and the
+ *                       active byte (lights_map == NULL ? 1 : (lights_map[p] >> l) & 1); bit l of refined[p] is that call's refined
+ *                       byte.
+ * refined is ONE plane of W * H bytes for the whole list (NULL: not wanted): bit l set exactly where light l took its full count; bits
+ * at and above count are 0.  A pixel whose map byte has no bit below count gets 0 in refined and in every plane; its position is never
+ * looked at (NaN allowed).  Planes at and above count, and rows outside the range / stripe, are not touched in counts or in refined.
+ * Every byte is integer counting of bytes that depend on (pixel, light, sample) alone: no order of the pairs, no deal over waves and no
+ * option can change one.  The per-pixel jitter table is not offered in a list in this version.
+ *   * RTS_ERR_INVALID_ARG, nothing written, no counter moved: everything rts_trace_soft_light_list* refuses; probes == NULL;
+ *     probes[l] >= n_l for any l < count -- a hard entry therefore accepts 0 alone.  probes[] from count up is not read.
+ *   * "kernel" picks the FAMILY as for a soft light list: 0, 1, 2, 7 (and -1 below 256 K pixels) the lane-per-ray walk over 16 x 16
+ *     blocks, the lights in order, each wave deciding per light for its own 8 x 8 quarter; 3..6, 8, 9 (and -1 from 256 K pixels) the
+ *     stackless packet over 8 x 8 tiles -- with "soft_split" 1 (default) four waves per tile that deal the probe pairs (l, j < k_l) --
+ *     all n_l samples where k_l == 0 --, join their counts in LDS, decide alike, and deal the remaining pairs over each light's own
+ *     penumbra pixels; with 0 one wave does both.  Bands, "packet_budget", "packet_share", "xcd_swizzle" and "row_order" as for a soft
+ *     light list, for speed only.
+ *   * a tile with no bit below count ends before a ray is set up; a tile without a penumbra pixel of any light ends after its probes;
+ *     a light without a penumbra pixel in a tile costs that tile nothing beyond its probe.
+ *   * like the other block traces it ignores split tables, tile orders, follow mode, "block_waves", "wide_lane", wave statistics and
+ *     the clock probe, and never drops or alters any of them.
+ *   * the device forms are asynchronous, allocate nothing and read nothing back; under graph capture each adds ONE kernel node,
+ *     constants, list, probes and options by value.  The host form copies in its rows only, traces, copies out and synchronises.
+ *   * get-only option "soft_list_adaptive_traces": launches so far (no other counter moves for them); rts_ctx_last_kernel_name then
+ *     names "shadowSoftLightListAdaptiveShareKernel" or "shadowSoftLightListAdaptivePacketKernel<S,geom>", S = 4 or 1 waves per tile,
+ *     geom = rows, bands or general as for "shadowSoftDistancePacketKernel". */
+int rts_trace_soft_light_list_adaptive(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                       const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                       uint32_t row_end, uint8_t* counts, const uint32_t* probes, uint8_t* refined);
+int rts_trace_soft_light_list_adaptive_device(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                              const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                              uint32_t row_begin, uint32_t row_end, uint8_t* d_counts, const uint32_t* probes,
+                                              uint8_t* d_refined, void* stream);
+int rts_trace_soft_light_list_adaptive_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                                      const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                                      uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts,
+                                                      const uint32_t* probes, uint8_t* d_refined, void* stream);
+
 /* ---- device-memory and timing plumbing (so callers need no HIP headers) ------ */
 int rts_device_count(int* count);
 int rts_device_malloc(rts_ctx* ctx, void** d_ptr, size_t bytes);

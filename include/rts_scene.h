@@ -128,6 +128,14 @@ int rtsh_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_consta
 int rtsh_soft_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_soft_light_list* list,
                          const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
                          uint8_t* counts, int threads);
+/* ADAPTIVE SOFT LIGHT LISTS on the host: the definition of rts_trace_soft_light_list_adaptive* (include/rts.h) as one straight loop
+ * over (pixel, light, sample) on rtsh_soft_light_list's walk and ray set-up -- light l's samples in order, and after its first
+ * probes[l] != 0 of them the verdict 0 or max(1, nsamples_l) where they agree, no further ray; else the full count, and bit l of
+ * refined[p] (optional; one plane for the list).  The refusals of include/rts.h: RTS_ERR_INVALID_ARG.  Runs without a GPU: the
+ * checker of the device forms, byte for byte. */
+int rtsh_soft_light_list_adaptive(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_soft_light_list* list,
+                                  const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                  uint32_t row_end, uint8_t* counts, const uint32_t* probes, uint8_t* refined, int threads);
 int rtsh_facing_lights(const rts_constants* constants, const rts_light_list* list, const float* positions, const float* normals,
                        uint32_t W, uint32_t H, uint8_t* lights_map);
 int rtsh_facing_lights_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* d_positions,

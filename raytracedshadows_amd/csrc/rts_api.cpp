@@ -8,6 +8,7 @@
 #include "rts_light_list.h"
 #include "rts_adaptive.h"
 #include "rts_soft_light_list.h"
+#include "rts_soft_light_list_adaptive.h"
 #include "rts_dispatch.h"
 #include "rts_args.h"
 #include "rts_refit.h"
@@ -46,6 +47,7 @@ struct rts_ctx {
     uint64_t softDistanceTraces = 0;                  // launches of a soft distance kernel (get-only option "soft_distance_traces")
     uint64_t lightListTraces = 0;                     // launches of a light list kernel (get-only option "light_list_traces")
     uint64_t adaptiveTraces = 0;                      // launches of an adaptive soft mask kernel (get-only option "adaptive_traces")
+    uint64_t softListAdaptiveTraces = 0;              // launches of an adaptive soft light list kernel (get-only option "soft_list_adaptive_traces")
     uint64_t softLightListTraces = 0;                 // launches of a soft light list kernel (get-only option "soft_light_list_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
@@ -557,6 +559,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "soft_distance_traces")) { *value = (int)(c->softDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "light_list_traces")) { *value = (int)(c->lightListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "adaptive_traces")) { *value = (int)(c->adaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "soft_list_adaptive_traces")) { *value = (int)(c->softListAdaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_light_list_traces")) { *value = (int)(c->softLightListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
@@ -1003,11 +1006,11 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 // each case below names the type it reads, and nothing else does.  distance: of the distance traces alone, whose mask is optional.
 // probe, refined: of Staged::Adaptive alone; its refined plane (optional) is staged in the distances' buffer, which it does not use.
 // Staged::SoftLightList: lights is the rts_soft_light_list, mask its count planes -- `count` planes of frameH rows in the caller's
-// buffer, of the staged rows alone on the device.
-enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList };
+// buffer, of the staged rows alone on the device.  Staged::SoftListAdaptive: the same, with `probes` (one per light) and the refined plane.
+enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive };
 static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, const void* lights, const float* positions, const uint8_t* active,
                            uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask, uint32_t probe = 0,
-                           uint8_t* refined = nullptr, uint32_t frameH = 0) {
+                           uint8_t* refined = nullptr, uint32_t frameH = 0, const uint32_t* probes = nullptr) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
     if (row_begin == row_end) return RTS_OK;
     RTS_HIP(hipSetDevice(c->device));
@@ -1016,7 +1019,7 @@ static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, cons
     int s = ensure(&c->d_in, &c->inBytes, pixels * 16);
     if (s == RTS_OK && distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4);
     if (s == RTS_OK && refined) s = ensure(&c->d_dist, &c->distBytes, pixels);
-    const size_t planes = what == Staged::SoftLightList ? ((const rts_soft_light_list*)lights)->count : 1u;
+    const size_t planes = (what == Staged::SoftLightList || what == Staged::SoftListAdaptive) ? ((const rts_soft_light_list*)lights)->count : 1u;
     if (s == RTS_OK && mask) s = ensure(&c->d_out, &c->outBytes, pixels * planes);
     if (s == RTS_OK && active) s = ensure(&c->d_act, &c->actBytes, pixels);
     if (s != RTS_OK) return s;
@@ -1043,6 +1046,9 @@ static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, cons
                                                   refined ? (uint8_t*)c->d_dist : nullptr, nullptr); break;
     case Staged::SoftLightList:
         s = rts_trace_soft_light_list_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
+    case Staged::SoftListAdaptive:
+        s = rts_trace_soft_light_list_adaptive_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, probes,
+                                                      refined ? (uint8_t*)c->d_dist : nullptr, nullptr); break;
     }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
@@ -1121,13 +1127,10 @@ int rts_trace_light_list(rts_ctx* c, const rts_constants* k, const rts_light_lis
 }
 
 // ---- soft light lists (include/rts.h): up to 8 lights, hard or soft, in one dispatch, one count plane per light -----------------------
-// One launch of a soft light list kernel (rts_soft_light_list.inc) with the geometry, the family rule and the tail of a distance trace.
-// The list travels in the argument block's 64 sample offsets (rts_soft_light_list.h): the shared table in the first 48, two slots per
-// light behind them, the count in nsamples, the map in the active map's slot, the planes in the mask's.
-static int traceSoftLightListImpl(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
-                                  const uint8_t* d_lights_map, const Dispatch& g, uint8_t* d_counts, void* stream) {
-    TraceParams p; uint32_t rows = 0; int s;
-    if (beginFrame(c, k, d_positions, d_counts, d_counts && rts::softListOk(list), g, p, &rows, &s) != Begin::Go) return s;
+// The list in the argument block, what the soft list trace and its adaptive form both launch with: it travels in the 64 sample offsets
+// (rts_soft_light_list.h) -- the shared table in the first 48, two slots per light behind them --, the count in nsamples, the map in the
+// active map's slot.
+static void setSoftList(TraceParams& p, const rts_constants* k, const rts_soft_light_list* list, const uint8_t* d_lights_map) {
     p.activeMap = d_lights_map;
     for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
     p.lightType = RTS_LIGHT_DIRECTIONAL;               // (not read: every light carries its own type)
@@ -1142,6 +1145,15 @@ static int traceSoftLightListImpl(rts_ctx* c, const rts_constants* k, const rts_
         const bool soft = e.nsamples >= 2;
         rts::setSoftListEntry(p, l, e.type, soft ? e.nsamples : 1u, soft ? e.first : 0u, e.radius, e.xyz);
     }
+}
+
+// One launch of a soft light list kernel (rts_soft_light_list.inc) with the geometry, the family rule and the tail of a distance trace.
+// The planes travel in the mask's slot.
+static int traceSoftLightListImpl(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
+                                  const uint8_t* d_lights_map, const Dispatch& g, uint8_t* d_counts, void* stream) {
+    TraceParams p; uint32_t rows = 0; int s;
+    if (beginFrame(c, k, d_positions, d_counts, d_counts && rts::softListOk(list), g, p, &rows, &s) != Begin::Go) return s;
+    setSoftList(p, k, list, d_lights_map);
     return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::softLightListTraces, rts::launchShadowSoftLightList, stream);
 }
 
@@ -1165,6 +1177,49 @@ int rts_trace_soft_light_list(rts_ctx* c, const rts_constants* k, const rts_soft
     if (!c || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
     if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
     return traceStagedRows(c, Staged::SoftLightList, k, list, positions, lights_map, W, row_begin, row_end, nullptr, counts, 0, nullptr, H);
+}
+
+// ---- adaptive soft light lists (include/rts.h): a soft light list with a probe count per light, its penumbra alone refined ---------
+// One launch of an adaptive soft light list kernel (rts_soft_light_list_adaptive.inc): the soft list's argument block, the probe
+// counts in the fourth word of each light's second slot and the refined plane in the generic rays' output slot
+// (rts_soft_light_list_adaptive.h).  probes is read here, by value: the caller may change it as soon as the call returns.
+static int traceSoftListAdaptiveImpl(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
+                                     const uint8_t* d_lights_map, const Dispatch& g, uint8_t* d_counts, const uint32_t* probes,
+                                     uint8_t* d_refined, void* stream) {
+    TraceParams p; uint32_t rows = 0; int s;
+    if (beginFrame(c, k, d_positions, d_counts, d_counts && rts::softListProbesOk(list, probes), g, p, &rows, &s) != Begin::Go) return s;
+    setSoftList(p, k, list, d_lights_map);
+    for (uint32_t l = 0; l < list->count; ++l) rts::setSoftListProbe(p, l, probes[l]);
+    p.out = d_refined;
+    return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::softListAdaptiveTraces, rts::launchShadowSoftLightListAdaptive,
+                        stream);
+}
+
+int rts_trace_soft_light_list_adaptive_device(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
+                                              const uint8_t* d_lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                              uint8_t* d_counts, const uint32_t* probes, uint8_t* d_refined, void* stream) {
+    return traceSoftListAdaptiveImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofRows(W, H, row_begin, row_end), d_counts, probes,
+                                     d_refined, stream);
+}
+
+int rts_trace_soft_light_list_adaptive_stripes_device(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list,
+                                                      const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                                      uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts,
+                                                      const uint32_t* probes, uint8_t* d_refined, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceSoftListAdaptiveImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_counts,
+                                     probes, d_refined, stream);
+}
+
+// The host form: the soft list's staging, with the refined rows staged as Staged::Adaptive stages its own.
+int rts_trace_soft_light_list_adaptive(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* positions,
+                                       const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                       uint8_t* counts, const uint32_t* probes, uint8_t* refined) {
+    if (!c || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListProbesOk(list, probes))
+        return RTS_ERR_INVALID_ARG;
+    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
+    return traceStagedRows(c, Staged::SoftListAdaptive, k, list, positions, lights_map, W, row_begin, row_end, nullptr, counts, 0, refined, H,
+                           probes);
 }
 
 int rts_trace_shadow_mask_adaptive(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,

@@ -44,6 +44,17 @@ inline bool softListOk(const rts_soft_light_list* list) {
     return true;
 }
 
+// the probe counts of an adaptive soft light list trace, one per entry below the count of a list softListOk accepts: 0 (the light is
+// traced in full) or 1 .. max(1, nsamples) - 1 -- so a hard entry accepts 0 alone.  Entries of probes[] from the count up are not read.
+inline bool softListProbesOk(const rts_soft_light_list* list, const uint32_t* probes) {
+    if (!probes || !softListOk(list)) return false;
+    for (uint32_t l = 0; l < list->count; ++l) {
+        const uint32_t n = list->lights[l].nsamples > 1u ? list->lights[l].nsamples : 1u;
+        if (probes[l] >= n) return false;
+    }
+    return true;
+}
+
 // a frame and its row range [row_begin, row_end), which may be empty
 inline bool frameRowsOk(uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end) {
     return W != 0 && H != 0 && row_begin <= row_end && row_end <= H;

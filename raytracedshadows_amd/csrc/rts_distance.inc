@@ -292,3 +292,5 @@ hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
 #include "rts_adaptive.inc"
 // soft light lists: up to 8 lights, hard or soft, in one dispatch, a count plane per light (its launch is declared in rts_soft_light_list.h)
 #include "rts_soft_light_list.inc"
+// adaptive soft light lists: a probe per light, its penumbra alone refined (its launch is declared in rts_soft_light_list_adaptive.h)
+#include "rts_soft_light_list_adaptive.inc"

@@ -1,0 +1,20 @@
+// Internal interface between the C-ABI layer (rts_api.cpp) and the adaptive soft light list kernels (rts_soft_light_list_adaptive.inc,
+// compiled with rts_kernels.hip): beside rts_device.h, whose text is part of the kernel-build hash that the committed counter profiles carry.
+#pragma once
+#include "rts_soft_light_list.h"
+
+namespace rts {
+
+// adaptive soft light list traces (include/rts.h).  TraceParams keeps its size and layout; the list travels as in
+// rts_soft_light_list.h, and the two values this trace adds in slots that trace leaves alone:
+//   p.offsets[48 + 2 l + 1][3] = the bit pattern of k_l, the probe count of light l: 0 (every sample, no decision) or 1 .. samples - 1
+//                                (setSoftListEntry writes 0 there and the soft list kernels never read it; setSoftListProbe writes k_l
+//                                 AFTER setSoftListEntry)
+//   p.out                      = the refined plane, W x H bytes, bit l = light l took its full count here, or NULL (the generic rays'
+//                                output, as in rts_adaptive.h)
+// p.mask = the count planes, p.activeMap = the light map or NULL.  The launcher re-checks every entry and every k_l against the 64
+// slots before it launches.  V_SHARE, or V_PACKET with 4 waves per tile (p.softSplit) or one.  *name: the kernel's stable name.
+void setSoftListProbe(TraceParams& p, uint32_t l, uint32_t probe);
+hipError_t launchShadowSoftLightListAdaptive(int variant, const TraceParams& p, hipStream_t stream, const char** name);
+
+} // namespace rts

@@ -1,7 +1,7 @@
 """Human-checkable output: OBJ scene -> BVH -> G-buffer (GPU) -> shadow mask (GPU) -> combine -> PPM.
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
-                           [--soft-list N]
+                           [--soft-list N [--adaptive K [--refined FILE.ppm]]]
 
 --cull: the shadow pass traces only the pixels of the facing mark (rtsh_facing_active_device: not the background, not the surfaces
 that face away from the light) -- the same image, byte for byte.
@@ -9,7 +9,9 @@ that face away from the light) -- the same image, byte for byte.
 remaining samples only where the probe disagrees; --refined writes the plane of refined pixels (white = the full count was taken).
 --soft-list N: the frame is lit by N (1..8) area lights on a ring around the scene's light, each of --spp samples (default 4; N * spp
 <= 48), traced in ONE rts_trace_soft_light_list_device dispatch through the facing map; the image is the mean of the lights' own
-combine passes, each over its count plane.
+combine passes, each over its count plane.  With --adaptive K the list is traced by rts_trace_soft_light_list_adaptive_device with a
+probe of K samples for every light (1 <= K < spp); --refined then writes the list's refined plane as a grey-scale image, a pixel's
+value the share of the lights that took their full count there.
 """
 import argparse
 import os
@@ -23,21 +25,29 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def soft_list(ctx, wl, W, H, count, spp, out):
-    """A frame lit by `count` area lights of `spp` samples: one list dispatch, then one combine pass per light over its plane."""
+def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out=""):
+    """A frame lit by `count` area lights of `spp` samples: one list dispatch (adaptive with `probe` != 0), then one combine pass per
+    light over its plane."""
     from raytracedshadows_amd import api, scenes
     from soft_list_ab import entries
     if not 1 <= count <= 8 or count * max(spp, 1) > 48:
         sys.exit("render: --soft-list takes 1..8 lights of at most 48 samples in all")
+    if probe and not 1 <= probe < spp:
+        sys.exit("render: --soft-list N --adaptive K takes 1 <= K < spp")
     lights = api.SoftLightList.make(entries(wl.scene, count, spp), scenes.jitter_offsets(48, 1.0, 19))
     d_pos, d_nrm, d_map = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
     d_counts, d_rgb = ctx.malloc(count * W * H), ctx.malloc(W * H * 3)
+    d_refined = ctx.malloc(W * H) if probe and refined_out else None
     t0 = time.time()
     api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
     api.facing_lights_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, W, H, d_map)
-    ctx.trace_soft_light_list_device(wl.constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
+    if probe:
+        ctx.trace_soft_light_list_adaptive_device(wl.constants, lights, (probe,) * count, d_pos, W, H, d_counts, d_refined=d_refined,
+                                                  d_lights_map=d_map)
+    else:
+        ctx.trace_soft_light_list_device(wl.constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
     ctx.synchronize()
-    print(f"G-buffer + facing map + {count} lights x {spp} samples in one dispatch: {(time.time() - t0) * 1e3:.2f} ms (first call, incl. "
+    print(f"G-buffer + facing map + {count} lights x {spp} samples{f', probe {probe},' if probe else ''} in one dispatch: {(time.time() - t0) * 1e3:.2f} ms (first call, incl. "
           f"launch); {ctx.last_kernel_name()}")
     total, rgb = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.uint8)
     for l in range(count):
@@ -50,6 +60,14 @@ def soft_list(ctx, wl, W, H, count, spp, out):
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     api.write_ppm(out, np.clip(total / count + 0.5, 0, 255).astype(np.uint8))
     print(f"wrote {out}: {W}x{H}, lit fraction per light {[round(float((planes[l] > 0).mean()), 3) for l in range(count)]}")
+    if d_refined:
+        refined = np.zeros((H, W), np.uint8)
+        ctx.d2h(refined, d_refined)
+        took = np.stack([(refined >> l) & 1 for l in range(count)])
+        os.makedirs(os.path.dirname(os.path.abspath(refined_out)), exist_ok=True)
+        api.write_ppm(refined_out, np.repeat((took.sum(axis=0) * 255 // count).astype(np.uint8)[..., None], 3, axis=2))
+        print(f"wrote {refined_out}: share of the pixels that took the full count, per light "
+              f"{[round(float(took[l].mean()), 3) for l in range(count)]}")
 
 
 def main():
@@ -76,7 +94,7 @@ def main():
     with api.ShadowContext(0) as ctx:
         ctx.set_bvh(wl.packed)
         if args.soft_list:
-            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out)
+            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
         t0 = time.time()
         api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
