@@ -482,7 +482,7 @@ int rts_trace_shadow_mask_adaptive_stripes_device(rts_ctx* ctx, const rts_consta
  * and the table in what it computes: its plane is bit l of rts_trace_light_list* for { type, xyz }, as 0 or 1.  Planes l >= count are
  * never touched; rows outside the range / stripe are not touched in any plane.  A pixel whose map byte has no bit below count gets 0
  * in every plane, its position is never looked at (NaN allowed) and changes no other pixel.  The per-pixel jitter table
- * (rts_light.table) is not offered in a list in this version.  A count is a sum of bytes that depend on (pixel, light, sample) alone:
+ * (rts_light.table) is offered by rts_trace_soft_light_list_jittered* below, not by these calls.  A count is a sum of bytes that depend on (pixel, light, sample) alone:
  * no order of the pairs, no deal over waves and no option can change a byte.
  *   * counts: count * W * H bytes, plane l at counts + l * W * H.  lights_map: NULL, or W x H bytes (rtsh_facing_lights* makes it from
  *     the rts_light_list of the same types and positions).
@@ -544,7 +544,7 @@ int rts_trace_soft_light_list_stripes_device(rts_ctx* ctx, const rts_constants* 
  * at and above count are 0.  A pixel whose map byte has no bit below count gets 0 in refined and in every plane; its position is never
  * looked at (NaN allowed).  Planes at and above count, and rows outside the range / stripe, are not touched in counts or in refined.
  * Every byte is integer counting of bytes that depend on (pixel, light, sample) alone: no order of the pairs, no deal over waves and no
- * option can change one.  The per-pixel jitter table is not offered in a list in this version.
+ * option can change one.  The per-pixel jitter table: rts_trace_soft_light_list_jittered* below.
  *   * RTS_ERR_INVALID_ARG, nothing written, no counter moved: everything rts_trace_soft_light_list* refuses; probes == NULL;
  *     probes[l] >= n_l for any l < count -- a hard entry therefore accepts 0 alone.  probes[] from count up is not read.
  *   * "kernel" picks the FAMILY as for a soft light list: 0, 1, 2, 7 (and -1 below 256 K pixels) the lane-per-ray walk over 16 x 16
@@ -573,6 +573,46 @@ int rts_trace_soft_light_list_adaptive_stripes_device(rts_ctx* ctx, const rts_co
                                                       const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
                                                       uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts,
                                                       const uint32_t* probes, uint8_t* d_refined, void* stream);
+
+/* JITTERED SOFT LIGHT LISTS: the adaptive soft light list with a PER-PIXEL JITTER TABLE per light (rts_light.table, in a list).  The
+ * arguments are those of rts_trace_soft_light_list_adaptive*, plus `tables` after `probes`: list->count entries on the host, read by
+ * value at the call, under graph capture too.  With n_l = max(1, nsamples_l), k_l = probes[l] and T_l = tables[l]:
+ *   T_l == 0   light l is exactly what rts_trace_soft_light_list_adaptive* makes of it.
+ *   T_l != 0   (a soft entry only) light l stands for the derived rts_light
+ *                { type, nsamples_l, xyz, table T_l, offsets'[i][c] = radius * offsets[first + i][c] }      (i < T_l, c < 3)
+ *              -- the product one rounded multiply, as above.  So pixel p aims sample j at offsets'[(start(p) + j) mod T_l], start(p) =
+ *              (hash32(p) * T_l) >> 32, p = y * W + x in the caller's FULL frame: the rule of rts_light.table, unchanged, in a row
+ *              range, in a stripe and in the host form alike.  Plane l is byte for byte what the one-light trace writes for that
+ *              derived light under bit l of the light map: rts_trace_shadow_mask_adaptive* with probe k_l where k_l >= 1, bit l of
+ *              refined that call's refined byte; rts_trace_shadow_mask_active* where k_l == 0, the refined bit 0.
+ * Neighbouring pixels then probe different points of the light, so a thin penumbra that one fixed probe pattern misses everywhere is
+ * caught in some pixels.  Everything else is the adaptive list's contract: planes at and above count and rows outside the range /
+ * stripe are untouched; a pixel whose map byte has no bit below count gets zeros and its position is never read; every byte is integer
+ * counting of bytes that depend on (pixel, light, sample) alone, so no order, deal or option can change one.
+ *   * tables == NULL or all zeros below count IS rts_trace_soft_light_list_adaptive*: the same launch of the same kernel, counted by
+ *     "soft_list_adaptive_traces".
+ *   * RTS_ERR_INVALID_ARG, nothing written, no counter moved: everything rts_trace_soft_light_list_adaptive* refuses; tables[l] != 0 on
+ *     a hard entry; tables[l] < nsamples_l; first + tables[l] > RTS_SOFT_LIST_OFFSETS.  tables[] from count up is not read.
+ *   * families, "soft_split", bands and the speed-only options as for the adaptive list; split tables, tile orders, follow mode and
+ *     the wide packet are ignored as by every block trace.  The device forms are asynchronous, allocate nothing and read nothing
+ *     back; under graph capture each adds ONE kernel node, constants, list, probes, tables and options by value.  The host form
+ *     stages its rows as the adaptive list's host form does.
+ *   * get-only option "soft_list_jitter_traces": launches with some table so far (no other counter moves for them);
+ *     rts_ctx_last_kernel_name then names "shadowSoftLightListAdaptiveShareKernel<jitter>" or
+ *     "shadowSoftLightListAdaptivePacketKernel<S,geom,jitter>".
+ *   * a list with every probe 0 and some table is the full jittered list trace; it runs this family, first phase only. */
+int rts_trace_soft_light_list_jittered(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                       const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                       uint32_t row_end, uint8_t* counts, const uint32_t* probes, const uint32_t* tables,
+                                       uint8_t* refined);
+int rts_trace_soft_light_list_jittered_device(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                              const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                              uint32_t row_begin, uint32_t row_end, uint8_t* d_counts, const uint32_t* probes,
+                                              const uint32_t* tables, uint8_t* d_refined, void* stream);
+int rts_trace_soft_light_list_jittered_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                                      const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                                      uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts,
+                                                      const uint32_t* probes, const uint32_t* tables, uint8_t* d_refined, void* stream);
 
 /* ---- device-memory and timing plumbing (so callers need no HIP headers) ------ */
 int rts_device_count(int* count);

@@ -136,6 +136,14 @@ int rtsh_soft_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_c
 int rtsh_soft_light_list_adaptive(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_soft_light_list* list,
                                   const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
                                   uint32_t row_end, uint8_t* counts, const uint32_t* probes, uint8_t* refined, int threads);
+/* JITTERED SOFT LIGHT LISTS on the host: the definition of rts_trace_soft_light_list_jittered* (include/rts.h) --
+ * rtsh_soft_light_list_adaptive's loop, sample j of a light with a table tables[l] != 0 aimed at offsets[first + (start(p) + j) mod
+ * tables[l]], p the pixel's index in the full frame.  tables == NULL: all zeros.  The refusals of include/rts.h: RTS_ERR_INVALID_ARG.
+ * Runs without a GPU: the checker of the device forms, byte for byte. */
+int rtsh_soft_light_list_jittered(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_soft_light_list* list,
+                                  const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                  uint32_t row_end, uint8_t* counts, const uint32_t* probes, const uint32_t* tables, uint8_t* refined,
+                                  int threads);
 int rtsh_facing_lights(const rts_constants* constants, const rts_light_list* list, const float* positions, const float* normals,
                        uint32_t W, uint32_t H, uint8_t* lights_map);
 int rtsh_facing_lights_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* d_positions,

@@ -166,14 +166,22 @@ class SoftLightList(C.Structure):
                     sl.offsets[j][i] = offsets[j, i]
         return sl
 
-    def light(self, l):
+    def light(self, l, table=0):
         """Light ``l`` alone, as the derived ``Light`` of include/rts.h: offsets'[j] = radius * offsets[first + j], the product
-        rounded to float32 on its own; a hard entry gives the hard ``Light``."""
+        rounded to float32 on its own; a hard entry gives the hard ``Light``.  ``table`` != 0 (a soft entry, ``nsamples <= table <=
+        48 - first``): the derived light of a jittered list -- ``table`` scaled offsets and ``Light.table`` set, also where it
+        equals ``nsamples``."""
         e = self.lights[l]
         if e.nsamples < 2:
+            if table:
+                raise RtsError(1, "SoftLightList.light: a hard entry has no table")
             return Light.make(e.type, list(e.xyz))
-        table = np.array([[self.offsets[e.first + j][i] for i in range(3)] for j in range(e.nsamples)], dtype=np.float32)
-        return Light.make(e.type, list(e.xyz), np.float32(e.radius) * table)
+        if table and (table < e.nsamples or e.first + table > self.OFFSETS):
+            raise RtsError(1, "SoftLightList.light: table is 0 or nsamples .. 48 - first")
+        rows = np.array([[self.offsets[e.first + j][i] for i in range(3)] for j in range(table or e.nsamples)], dtype=np.float32)
+        lt = Light.make(e.type, list(e.xyz), np.float32(e.radius) * rows, nsamples=e.nsamples)
+        lt.table = table
+        return lt
 
     def hard_list(self):
         """The ``LightList`` of the same types and positions: what ``facing_lights`` makes this list's light map from."""
@@ -270,6 +278,14 @@ _sig("rts_trace_soft_light_list_adaptive_stripes_device", C.c_int, C.c_void_p, C
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _u32p, C.c_void_p, C.c_void_p)
 _sig("rtsh_soft_light_list_adaptive", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
      C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _u32p, C.c_void_p, C.c_int)
+_sig("rts_trace_soft_light_list_jittered", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _u32p, _u32p, C.c_void_p)
+_sig("rts_trace_soft_light_list_jittered_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _u32p, _u32p, C.c_void_p, C.c_void_p)
+_sig("rts_trace_soft_light_list_jittered_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _u32p, _u32p, C.c_void_p, C.c_void_p)
+_sig("rtsh_soft_light_list_jittered", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _u32p, _u32p, C.c_void_p, C.c_int)
 _sig("rts_trace_shadow_mask_adaptive", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rts_trace_shadow_mask_adaptive_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light),
@@ -790,15 +806,23 @@ class ShadowContext:
 
     # -- adaptive soft light lists (include/rts.h): a soft light list with a probe count per light, its penumbra alone refined --
     def trace_soft_light_list_adaptive(self, constants, lights, probes, positions, width, height, lights_map=None, row_begin=0,
-                                       row_end=None, out=None, refined=None, want_refined=True):
+                                       row_end=None, out=None, refined=None, want_refined=True, tables=None):
         """Host-pointer dispatch; returns ``(uint8[count, H, W] counts, uint8[H, W] refined)`` (refined None with ``want_refined``
         False).  ``probes``: ``count`` integers, 0 = light ``l`` in full, else its probe; bit ``l`` of ``refined`` = light ``l`` took
-        its full count there.  ``out`` / ``refined``: arrays to write the rows into."""
+        its full count there.  ``out`` / ``refined``: arrays to write the rows into.  ``tables``: None, or ``count`` integers, the
+        per-pixel jitter table of each light (0: none) -- rts_trace_soft_light_list_jittered."""
         positions, lights_map = _frame_inputs("trace_soft_light_list_adaptive", positions, width, height, lights_map, "lights_map")
         row_end = height if row_end is None else row_end
         counts = out if out is not None else np.zeros((lights.count if lights is not None else 1, height, width), dtype=np.uint8)
         if refined is None and want_refined:
             refined = np.zeros((height, width), dtype=np.uint8)
+        if tables is not None:
+            _check(_lib.rts_trace_soft_light_list_jittered(self._h, C.byref(constants), _ref(lights), _ptr(positions),
+                                                           _ptr_or_none(lights_map), width, height, row_begin, row_end, _ptr(counts),
+                                                           _probes(lights, probes), _probes(lights, tables, "tables"),
+                                                           _ptr_or_none(refined)),
+                   "rts_trace_soft_light_list_jittered")
+            return counts, refined
         _check(_lib.rts_trace_soft_light_list_adaptive(self._h, C.byref(constants), _ref(lights), _ptr(positions),
                                                        _ptr_or_none(lights_map), width, height, row_begin, row_end, _ptr(counts),
                                                        _probes(lights, probes), _ptr_or_none(refined)),
@@ -806,10 +830,18 @@ class ShadowContext:
         return counts, refined
 
     def trace_soft_light_list_adaptive_device(self, constants, lights, probes, d_positions, width, height, d_counts, d_refined=None,
-                                              d_lights_map=None, row_begin=0, row_end=None, stream=None):
+                                              d_lights_map=None, row_begin=0, row_end=None, stream=None, tables=None):
         """Device pointers, asynchronous: d_counts = count * width * height bytes, d_refined / d_lights_map = width * height bytes or
-        None.  ``probes`` is read at the call."""
+        None.  ``probes`` and ``tables`` (None: today's call) are read at the call."""
         row_end = height if row_end is None else row_end
+        if tables is not None:
+            _check(_lib.rts_trace_soft_light_list_jittered_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
+                                                                  C.c_void_p(d_lights_map or 0), width, height, row_begin, row_end,
+                                                                  C.c_void_p(d_counts), _probes(lights, probes),
+                                                                  _probes(lights, tables, "tables"), C.c_void_p(d_refined or 0),
+                                                                  C.c_void_p(stream or 0)),
+                   "rts_trace_soft_light_list_jittered_device")
+            return
         _check(_lib.rts_trace_soft_light_list_adaptive_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
                                                               C.c_void_p(d_lights_map or 0), width, height, row_begin, row_end,
                                                               C.c_void_p(d_counts), _probes(lights, probes), C.c_void_p(d_refined or 0),
@@ -817,8 +849,16 @@ class ShadowContext:
                "rts_trace_soft_light_list_adaptive_device")
 
     def trace_soft_light_list_adaptive_stripes_device(self, constants, lights, probes, d_positions, width, height, d_counts, band_rows,
-                                                      n_stripes, stripe, d_refined=None, d_lights_map=None, stream=None):
+                                                      n_stripes, stripe, d_refined=None, d_lights_map=None, stream=None, tables=None):
         """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        if tables is not None:
+            _check(_lib.rts_trace_soft_light_list_jittered_stripes_device(self._h, C.byref(constants), _ref(lights),
+                                                                          C.c_void_p(d_positions), C.c_void_p(d_lights_map or 0), width,
+                                                                          height, band_rows, n_stripes, stripe, C.c_void_p(d_counts),
+                                                                          _probes(lights, probes), _probes(lights, tables, "tables"),
+                                                                          C.c_void_p(d_refined or 0), C.c_void_p(stream or 0)),
+                   "rts_trace_soft_light_list_jittered_stripes_device")
+            return
         _check(_lib.rts_trace_soft_light_list_adaptive_stripes_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
                                                                       C.c_void_p(d_lights_map or 0), width, height, band_rows,
                                                                       n_stripes, stripe, C.c_void_p(d_counts), _probes(lights, probes),
@@ -1204,29 +1244,37 @@ def soft_light_list(packed, constants, lights, positions, width, height, lights_
     return counts
 
 
-def _probes(lights, probes):
-    """``probes`` (None, or any sequence of ``lights.count`` integers) as the ``uint32`` array the C entry points read by value."""
+def _probes(lights, probes, what="probes"):
+    """``probes`` (None, or any sequence of ``lights.count`` integers) as the ``uint32`` array the C entry points read by value;
+    ``tables`` travels the same way."""
     if probes is None:
         return None
     probes = [int(v) for v in probes]
     if lights is not None and len(probes) != lights.count:
-        raise RtsError(1, "probes: one integer per light of the list")
+        raise RtsError(1, what + ": one integer per light of the list")
     if any(v < 0 or v > 0xFFFFFFFF for v in probes):
-        raise RtsError(1, "probes: unsigned 32-bit integers")
+        raise RtsError(1, what + ": unsigned 32-bit integers")
     return (C.c_uint32 * max(1, len(probes)))(*probes)
 
 
 def soft_light_list_adaptive(packed, constants, lights, probes, positions, width, height, lights_map=None, row_begin=0, row_end=None,
-                             out=None, refined=None, threads=0, want_refined=True):
+                             out=None, refined=None, threads=0, want_refined=True, tables=None):
     """An adaptive soft light list trace on the host (rtsh_soft_light_list_adaptive, no GPU): ``(uint8[count, H, W] counts,
     uint8[H, W] refined)`` -- per light its first ``probes[l]`` samples, the remaining ones only where they disagree (``probes[l]`` 0:
-    all of them); bit ``l`` of ``refined`` = light ``l`` took its full count there (None with ``want_refined`` False)."""
+    all of them); bit ``l`` of ``refined`` = light ``l`` took its full count there (None with ``want_refined`` False).  ``tables``:
+    None, or per light the size of its per-pixel jitter table (0: none) -- rtsh_soft_light_list_jittered."""
     packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
     positions, lights_map = _frame_inputs("soft_light_list_adaptive", positions, width, height, lights_map, "lights_map")
     row_end = height if row_end is None else row_end
     counts = out if out is not None else np.zeros((lights.count if lights is not None else 1, height, width), np.uint8)
     if refined is None and want_refined:
         refined = np.zeros((height, width), np.uint8)
+    if tables is not None:
+        _check(_lib.rtsh_soft_light_list_jittered(_ptr(packed), packed.shape[0], C.byref(constants), _ref(lights), _ptr(positions),
+                                                  _ptr_or_none(lights_map), width, height, row_begin, row_end, _ptr(counts),
+                                                  _probes(lights, probes), _probes(lights, tables, "tables"), _ptr_or_none(refined),
+                                                  threads), "rtsh_soft_light_list_jittered")
+        return counts, refined
     _check(_lib.rtsh_soft_light_list_adaptive(_ptr(packed), packed.shape[0], C.byref(constants), _ref(lights), _ptr(positions),
                                               _ptr_or_none(lights_map), width, height, row_begin, row_end, _ptr(counts),
                                               _probes(lights, probes), _ptr_or_none(refined), threads), "rtsh_soft_light_list_adaptive")

@@ -48,6 +48,7 @@ struct rts_ctx {
     uint64_t lightListTraces = 0;                     // launches of a light list kernel (get-only option "light_list_traces")
     uint64_t adaptiveTraces = 0;                      // launches of an adaptive soft mask kernel (get-only option "adaptive_traces")
     uint64_t softListAdaptiveTraces = 0;              // launches of an adaptive soft light list kernel (get-only option "soft_list_adaptive_traces")
+    uint64_t softListJitterTraces = 0;                // launches of a jittered adaptive soft light list kernel (get-only option "soft_list_jitter_traces")
     uint64_t softLightListTraces = 0;                 // launches of a soft light list kernel (get-only option "soft_light_list_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
@@ -560,6 +561,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "light_list_traces")) { *value = (int)(c->lightListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "adaptive_traces")) { *value = (int)(c->adaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_list_adaptive_traces")) { *value = (int)(c->softListAdaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "soft_list_jitter_traces")) { *value = (int)(c->softListJitterTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_light_list_traces")) { *value = (int)(c->softLightListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
@@ -1006,11 +1008,13 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 // each case below names the type it reads, and nothing else does.  distance: of the distance traces alone, whose mask is optional.
 // probe, refined: of Staged::Adaptive alone; its refined plane (optional) is staged in the distances' buffer, which it does not use.
 // Staged::SoftLightList: lights is the rts_soft_light_list, mask its count planes -- `count` planes of frameH rows in the caller's
-// buffer, of the staged rows alone on the device.  Staged::SoftListAdaptive: the same, with `probes` (one per light) and the refined plane.
+// buffer, of the staged rows alone on the device.  Staged::SoftListAdaptive: the same, with `probes` (one per light) and the refined plane;
+// with `tables` the jittered form, whose hash pixelBase makes that of the caller's frame.
 enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive };
 static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, const void* lights, const float* positions, const uint8_t* active,
                            uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask, uint32_t probe = 0,
-                           uint8_t* refined = nullptr, uint32_t frameH = 0, const uint32_t* probes = nullptr) {
+                           uint8_t* refined = nullptr, uint32_t frameH = 0, const uint32_t* probes = nullptr,
+                           const uint32_t* tables = nullptr) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
     if (row_begin == row_end) return RTS_OK;
     RTS_HIP(hipSetDevice(c->device));
@@ -1030,7 +1034,7 @@ static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, cons
     const float* d_in = (const float*)c->d_in;
     float* d_dist = (float*)c->d_dist;
     // per-pixel jitter hashes the pixel's index in the caller's frame (sampleIndex, rts_kernels.hip: the one reader, and only of a
-    // light with a table -- several samples, so in a mask trace or a soft distance trace; a light list never reads it)
+    // light with a table -- several samples, so in a mask trace or a soft distance trace; of the lists the jittered one alone reads it)
     c->pixelBase = row_begin * W;
     switch (what) {
     case Staged::Mask:
@@ -1047,8 +1051,8 @@ static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, cons
     case Staged::SoftLightList:
         s = rts_trace_soft_light_list_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
     case Staged::SoftListAdaptive:
-        s = rts_trace_soft_light_list_adaptive_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, probes,
-                                                      refined ? (uint8_t*)c->d_dist : nullptr, nullptr); break;
+        s = rts_trace_soft_light_list_jittered_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, probes,
+                                                      tables, refined ? (uint8_t*)c->d_dist : nullptr, nullptr); break;
     }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
@@ -1119,7 +1123,7 @@ int rts_trace_light_list_stripes_device(rts_ctx* c, const rts_constants* k, cons
 }
 
 // The host form goes through traceStagedRows like the other host entries, the list in the light's place and the map in the active
-// map's.  traceStagedRows sets pixelBase around the call all the same; a list carries no per-pixel jitter, so no list trace reads it.
+// map's.  traceStagedRows sets pixelBase around the call all the same; of the list traces only the jittered soft list reads it.
 int rts_trace_light_list(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* positions, const uint8_t* lights_map,
                          uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
     if (!c || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
@@ -1183,15 +1187,21 @@ int rts_trace_soft_light_list(rts_ctx* c, const rts_constants* k, const rts_soft
 // One launch of an adaptive soft light list kernel (rts_soft_light_list_adaptive.inc): the soft list's argument block, the probe
 // counts in the fourth word of each light's second slot and the refined plane in the generic rays' output slot
 // (rts_soft_light_list_adaptive.h).  probes is read here, by value: the caller may change it as soon as the call returns.
+// tables (rts_trace_soft_light_list_jittered*): NULL or all zeros is the call without them -- the same launch of the same kernel under
+// the same counter; else the table sizes travel in the .w of the shared table's first entries and the JITTER instantiations run.
 static int traceSoftListAdaptiveImpl(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
                                      const uint8_t* d_lights_map, const Dispatch& g, uint8_t* d_counts, const uint32_t* probes,
-                                     uint8_t* d_refined, void* stream) {
+                                     uint8_t* d_refined, void* stream, const uint32_t* tables = nullptr) {
     TraceParams p; uint32_t rows = 0; int s;
-    if (beginFrame(c, k, d_positions, d_counts, d_counts && rts::softListProbesOk(list, probes), g, p, &rows, &s) != Begin::Go) return s;
+    if (beginFrame(c, k, d_positions, d_counts, d_counts && rts::softListTablesOk(list, probes, tables), g, p, &rows, &s) != Begin::Go) return s;
     setSoftList(p, k, list, d_lights_map);
     for (uint32_t l = 0; l < list->count; ++l) rts::setSoftListProbe(p, l, probes[l]);
     p.out = d_refined;
-    return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::softListAdaptiveTraces, rts::launchShadowSoftLightListAdaptive,
+    if (!rts::softListHasTable(list, tables))
+        return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::softListAdaptiveTraces,
+                            rts::launchShadowSoftLightListAdaptive, stream);
+    for (uint32_t l = 0; l < list->count; ++l) rts::setSoftListTable(p, l, tables[l]);
+    return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::softListJitterTraces, rts::launchShadowSoftLightListJittered,
                         stream);
 }
 
@@ -1220,6 +1230,36 @@ int rts_trace_soft_light_list_adaptive(rts_ctx* c, const rts_constants* k, const
     if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
     return traceStagedRows(c, Staged::SoftListAdaptive, k, list, positions, lights_map, W, row_begin, row_end, nullptr, counts, 0, refined, H,
                            probes);
+}
+
+// ---- jittered soft light lists (include/rts.h): the adaptive list with a per-pixel jitter table per light ----------------------------
+int rts_trace_soft_light_list_jittered_device(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
+                                              const uint8_t* d_lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                              uint8_t* d_counts, const uint32_t* probes, const uint32_t* tables, uint8_t* d_refined,
+                                              void* stream) {
+    return traceSoftListAdaptiveImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofRows(W, H, row_begin, row_end), d_counts, probes,
+                                     d_refined, stream, tables);
+}
+
+int rts_trace_soft_light_list_jittered_stripes_device(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list,
+                                                      const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                                      uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts,
+                                                      const uint32_t* probes, const uint32_t* tables, uint8_t* d_refined, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceSoftListAdaptiveImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_counts,
+                                     probes, d_refined, stream, tables);
+}
+
+// The host form: the adaptive list's staging; pixelBase, which traceStagedRows sets around the device call, makes the hash that of
+// the caller's frame although the rows travel as a frame of their own.
+int rts_trace_soft_light_list_jittered(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* positions,
+                                       const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                       uint8_t* counts, const uint32_t* probes, const uint32_t* tables, uint8_t* refined) {
+    if (!c || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListTablesOk(list, probes, tables))
+        return RTS_ERR_INVALID_ARG;
+    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
+    return traceStagedRows(c, Staged::SoftListAdaptive, k, list, positions, lights_map, W, row_begin, row_end, nullptr, counts, 0, refined, H,
+                           probes, tables);
 }
 
 int rts_trace_shadow_mask_adaptive(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,

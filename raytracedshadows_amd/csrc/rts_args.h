@@ -55,6 +55,26 @@ inline bool softListProbesOk(const rts_soft_light_list* list, const uint32_t* pr
     return true;
 }
 
+// the probe counts and the per-pixel table sizes of a jittered soft light list trace: softListProbesOk, and per entry below the count
+// a table of 0 (none), or on a SOFT entry one of nsamples .. RTS_SOFT_LIST_OFFSETS - first entries -- the table starts at the light's
+// `first` and must hold every sample and end inside the shared table.  tables == NULL stands for all zeros.  Entries of tables[] from
+// the count up are not read.
+inline bool softListTablesOk(const rts_soft_light_list* list, const uint32_t* probes, const uint32_t* tables) {
+    if (!softListProbesOk(list, probes)) return false;
+    for (uint32_t l = 0; tables && l < list->count; ++l) {
+        const rts_soft_light_entry& e = list->lights[l];
+        if (tables[l] == 0u) continue;
+        if (e.nsamples < 2u || tables[l] < e.nsamples || (uint64_t)e.first + tables[l] > RTS_SOFT_LIST_OFFSETS) return false;
+    }
+    return true;
+}
+
+// whether any entry below the count has a table (a list softListTablesOk accepts)
+inline bool softListHasTable(const rts_soft_light_list* list, const uint32_t* tables) {
+    for (uint32_t l = 0; tables && l < list->count; ++l) if (tables[l] != 0u) return true;
+    return false;
+}
+
 // a frame and its row range [row_begin, row_end), which may be empty
 inline bool frameRowsOk(uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end) {
     return W != 0 && H != 0 && row_begin <= row_end && row_end <= H;

@@ -422,10 +422,14 @@ extern "C" int rtsh_soft_light_list(const rts_vec4u* packed, size_t count_vec4, 
 // ---- adaptive soft light lists on the host (include/rts_scene.h): the checker of rts_trace_soft_light_list_adaptive* ----
 // The definition of include/rts.h applied literally: rtsh_soft_light_list's loop, and per light rtsh_shadow_mask_adaptive's decision
 // after the probe's samples.
-extern "C" int rtsh_soft_light_list_adaptive(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
+// The jittered form (rts_trace_soft_light_list_jittered*) is the same loop with sampleIndex(T_l, j, pixel) in front of the offset;
+// without tables sampleIndex(0, j, .) is j.
+extern "C" int rtsh_soft_light_list_jittered(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
                                              const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
-                                             uint32_t row_end, uint8_t* counts, const uint32_t* probes, uint8_t* refined, int threads) {
-    if (!packed || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListProbesOk(list, probes))
+                                             uint32_t row_end, uint8_t* counts, const uint32_t* probes, const uint32_t* tables, uint8_t* refined,
+                                             int threads) {
+    using rts_harness::sampleIndex;
+    if (!packed || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListTablesOk(list, probes, tables))
         return RTS_ERR_INVALID_ARG;
     const int s = rts_bvh_validate(packed, count_vec4, nullptr);
     if (s != RTS_OK) return s;
@@ -441,13 +445,13 @@ extern "C" int rtsh_soft_light_list_adaptive(const rts_vec4u* packed, size_t cou
             uint32_t lit = 0;
             if ((bits >> l) & 1u) {
                 const rts_soft_light_entry& e = list->lights[l];
-                const uint32_t ns = e.nsamples > 1 ? e.nsamples : 1u, probe = probes[l];
+                const uint32_t ns = e.nsamples > 1 ? e.nsamples : 1u, probe = probes[l], table = tables ? tables[l] : 0u;
                 uint32_t j = 0;
                 for (; j < ns; ++j) {
                     if (probe != 0 && j == probe && (lit == 0 || lit == probe)) break;      // the probe agrees: its verdict, no further ray
                     V3 L{ e.xyz[0], e.xyz[1], e.xyz[2] };
                     if (ns > 1) {
-                        const float* o = list->offsets[e.first + j];
+                        const float* o = list->offsets[e.first + sampleIndex(table, j, (uint32_t)i)];
                         const float ox = e.radius * o[0], oy = e.radius * o[1], oz = e.radius * o[2];
                         L.x = L.x + ox; L.y = L.y + oy; L.z = L.z + oz;
                     }
@@ -462,6 +466,13 @@ extern "C" int rtsh_soft_light_list_adaptive(const rts_vec4u* packed, size_t cou
         if (refined) refined[i] = (uint8_t)took;
     });
     return RTS_OK;
+}
+
+extern "C" int rtsh_soft_light_list_adaptive(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
+                                             const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                             uint32_t row_end, uint8_t* counts, const uint32_t* probes, uint8_t* refined, int threads) {
+    return rtsh_soft_light_list_jittered(packed, count_vec4, k, list, positions, lights_map, W, H, row_begin, row_end, counts, probes, nullptr,
+                                         refined, threads);
 }
 
 extern "C" int rtsh_facing_lights(const rts_constants* k, const rts_light_list* list, const float* positions, const float* normals,

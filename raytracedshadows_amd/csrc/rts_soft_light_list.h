@@ -12,8 +12,8 @@ namespace rts {
 //   p.offsets[48 + 2 l + 1]             = the bit patterns of { type, samples = max(1, nsamples), first (0 for a hard entry), 0 }
 // (setSoftListEntry writes the two slots of light l: the kernels' file owns that part of the layout.)
 // p.activeMap = the per-pixel light map (bit l: light l sends its rays here) or NULL (every light everywhere); p.mask = the count
-// planes, plane l at p.mask + l * W * H: the number of unoccluded samples of light l.  p.lightTable is 0: a list carries no per-pixel
-// jitter.  V_SHARE, or V_PACKET with 4 waves per tile (p.softSplit) or one.  *name: the kernel's stable name.
+// planes, plane l at p.mask + l * W * H: the number of unoccluded samples of light l.  p.lightTable is 0: a list's per-pixel jitter
+// tables, where it has any, travel per light (rts_soft_light_list_adaptive.h).  V_SHARE, or V_PACKET with 4 waves per tile (p.softSplit) or one.  *name: the kernel's stable name.
 void setSoftListEntry(TraceParams& p, uint32_t l, uint32_t type, uint32_t samples, uint32_t first, float radius, const float* xyz);
 hipError_t launchShadowSoftLightList(int variant, const TraceParams& p, hipStream_t stream, const char** name);
 

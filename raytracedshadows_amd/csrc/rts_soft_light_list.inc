@@ -29,13 +29,16 @@ __device__ __forceinline__ uint32_t softListSamples(const TraceParams& p, uint32
 //                                           without FMA contraction), then makeShadowRay's own add;
 //   L = xyz AS GIVEN                        for a hard entry (makeShadowRay adds no offset to a light of one sample: 0 + (-0) is +0).
 // The choices between rcpFast and the division are made per wave, as there.
+// AT (the jittered lists, rts_soft_light_list_adaptive.inc): j is the entry of the shared table itself, first + sampleIndexOf(...),
+// and may differ from lane to lane; the launcher has checked that the light's whole table lies below SOFT_LIST_SLOT.
+template <bool AT = false>
 __device__ __forceinline__ Ray makeSoftListRay(const TraceParams& p, F3 rel, uint32_t l, uint32_t j) {
     const float* const e = p.offsets[SOFT_LIST_SLOT + 2u * l];         // { x, y, z, radius }
     const float* const u = p.offsets[SOFT_LIST_SLOT + 2u * l + 1u];    // bit patterns of { type, samples, first, 0 }
     F3 L{ e[0], e[1], e[2] };
     if (__float_as_uint(u[1]) > 1u) {                                    // (wave-uniform: l is)
         const float radius = e[3];
-        const float* const o = p.offsets[__float_as_uint(u[2]) + j];
+        const float* const o = p.offsets[AT ? j : __float_as_uint(u[2]) + j];
         L.x = L.x + radius * o[0]; L.y = L.y + radius * o[1]; L.z = L.z + radius * o[2];
     }
     F3 origin{ p.cam[0] + rel.x, p.cam[1] + rel.y, p.cam[2] + rel.z };

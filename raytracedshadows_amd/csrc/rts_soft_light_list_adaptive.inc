@@ -20,6 +20,35 @@ __device__ __forceinline__ uint32_t softListProbe(const TraceParams& p, uint32_t
     return __float_as_uint(p.offsets[SOFT_LIST_SLOT + 2u * l + 1u][3]);
 }
 
+// JITTERED LISTS (rts_trace_soft_light_list_jittered*): a table size T_l per light (rts_soft_light_list_adaptive.h: the slot).
+// T_l == 0: sample j of light l is entry first + j of the shared table for every pixel, as above.  T_l != 0: pixel p takes entry
+// first + (start(p) + j) mod T_l, start(p) = (hash32(p) * T_l) >> 32, p the pixel's index in the caller's full frame -- sampleIndex
+// (rts_kernels.hip) with T_l in p.lightTable's place, so the ray is the one the mask kernels set up for the derived light with that
+// table.  Which pairs are walked over which lanes is decided by k_l, the map and the tile, never by an offset: the counting above
+// and the barriers' argument below hold as they stand (DESIGN.md 4.19).
+void setSoftListTable(TraceParams& p, uint32_t l, uint32_t table) {
+    __builtin_memcpy(&p.offsets[l][3], &table, sizeof(table));
+}
+
+// T_l.  Wave-uniform like l: a scalar load from the argument block.
+__device__ __forceinline__ uint32_t softListTable(const TraceParams& p, uint32_t l) {
+    return __float_as_uint(p.offsets[l][3]);
+}
+
+// The shared table's entry of (light l, sample j) at the pixel `pixel` of this dispatch.  j < n_l <= T_l, so one subtraction wraps.
+__device__ __forceinline__ uint32_t softListSampleAt(const TraceParams& p, uint32_t l, uint32_t j, uint32_t pixel) {
+    const uint32_t first = __float_as_uint(p.offsets[SOFT_LIST_SLOT + 2u * l + 1u][2]), table = softListTable(p, l);
+    if (table == 0u) return first + j;                                   // (wave-uniform: l is)
+    const uint32_t at = __umulhi(hash32(pixel + p.pixelBase), table) + j;
+    return first + (at >= table ? at - table : at);
+}
+
+// standInTexel for the pixel index: a lane that stands in sets up the walker's very ray only if it hashes the walker's pixel.
+__device__ __forceinline__ uint32_t standInPixel(uint32_t pix, bool keeps, uint64_t walkers) {
+    const uint32_t sp = (uint32_t)__builtin_amdgcn_readlane((int)pix, __builtin_ctzll(walkers));
+    return keeps ? pix : sp;
+}
+
 // softListPrologue with the refined plane: a tile that has no bit below the count gets its zeros there too.
 __device__ __forceinline__ bool softListAdaptivePrologue(const TraceParams& p, bool owns, uint32_t pix, bool stores, ListPixel* d) {
     if (softListPrologue(p, owns, pix, stores, d)) return true;
@@ -30,6 +59,8 @@ __device__ __forceinline__ bool softListAdaptivePrologue(const TraceParams& p, b
 // Lane per ray: shadowSoftLightListShareKernel's 16 x 16 block, the lights in order: the probe's samples, the decision of the wave's
 // own 8 x 8 quarter (the four waves share nothing but the LDS each owns a quarter of), then the remaining samples over the penumbra
 // lanes.  A light's plane is stored as soon as the light is done, the refined byte at the end.
+// JITTER: the tables are honoured; a stand-in takes the pixel index with the texel, per light and again per penumbra.
+template <bool JITTER>
 __global__ __launch_bounds__(256) void shadowSoftLightListAdaptiveShareKernel(TraceParams p) {
     __shared__ uint32_t shareSlots[4][64];       // lane numbers exchanged by traverseShare (256 B per wave)
     uint32_t* lds = shareSlots[threadIdx.x >> 6];
@@ -48,8 +79,12 @@ __global__ __launch_bounds__(256) void shadowSoftLightListAdaptiveShareKernel(Tr
             const uint32_t first = k != 0u ? k : n;                      // samples of the first phase
             {
                 const F3 rel = standInTexel(d.rel, walks, walkers);      // (lanes that do not walk light l stand in)
+                uint32_t px = 0;
+                if constexpr (JITTER) px = standInPixel(d.pix, walks, walkers);
                 for (uint32_t j = 0; j < first; ++j) {
-                    const Ray r = makeSoftListRay(p, rel, l, j);
+                    Ray r;
+                    if constexpr (JITTER) r = makeSoftListRay<true>(p, rel, l, softListSampleAt(p, l, j, px));
+                    else r = makeSoftListRay(p, rel, l, j);
                     const bool occluded = shareAnyHit(p, bvh, r, walks, walks && !raySafe(r), lds);
                     count += (walks && !occluded) ? 1u : 0u;             // comp:148, per sample
                 }
@@ -59,8 +94,12 @@ __global__ __launch_bounds__(256) void shadowSoftLightListAdaptiveShareKernel(Tr
                 const uint64_t pens = __builtin_amdgcn_ballot_w64(pen);
                 if (pens != 0) {                                         // else the quarter's probe was unanimous: no further ray
                     const F3 rel = standInTexel(d.rel, pen, pens);       // (lanes that do not refine light l stand in)
+                    uint32_t px = 0;
+                    if constexpr (JITTER) px = standInPixel(d.pix, pen, pens);
                     for (uint32_t j = k; j < n; ++j) {
-                        const Ray r = makeSoftListRay(p, rel, l, j);
+                        Ray r;
+                        if constexpr (JITTER) r = makeSoftListRay<true>(p, rel, l, softListSampleAt(p, l, j, px));
+                        else r = makeSoftListRay(p, rel, l, j);
                         const bool occluded = shareAnyHit(p, bvh, r, pen, pen && !raySafe(r), lds);
                         count += (pen && !occluded) ? 1u : 0u;
                     }
@@ -79,9 +118,11 @@ __global__ __launch_bounds__(256) void shadowSoftLightListAdaptiveShareKernel(Tr
 //   REFINE true  (phase 2): light l has the samples k_l .. n_l - 1, none where k_l == 0.
 // bits: per lane, the lights it walks in this phase (the map's byte; the penumbra mask).  A light no lane of the tile walks is
 // stepped over before any ray is set up, as the cull does.  The counts go to mine[l >> 2][lane], byte l & 3 (rts_soft_light_list.inc).
-template <int SPLIT, bool REFINE>
+// JITTER: pix is the lane's pixel index where it has a bit in `bits` (the kernel keeps it across the walks anyway); a stand-in takes
+// the walker's, and the index is made opaque per pair with the texel.
+template <int SPLIT, bool REFINE, bool JITTER>
 __device__ __forceinline__ void softListAdaptivePhase(const TraceParams& p, const NodeStream& bvh, const F3& texel, uint32_t bits,
-                                                      uint32_t wave, uint32_t* share, uint32_t (*mine)[64]) {
+                                                      uint32_t wave, uint32_t* share, uint32_t (*mine)[64], uint32_t pix) {
     uint32_t l = 0, j = wave;
     for (;;) {
         uint32_t n = 0, from = 0;
@@ -103,7 +144,12 @@ __device__ __forceinline__ void softListAdaptivePhase(const TraceParams& p, cons
         // (made opaque per pair: otherwise the compiler hoists the pair-independent half of the set-up out of the loop and keeps it
         //  in registers across the walk -- rts_soft_distance.inc)
         asm volatile("" : "+v"(rel.x), "+v"(rel.y), "+v"(rel.z));
-        const Ray r[1] = { makeSoftListRay(p, rel, l, from + j) };
+        Ray r[1];
+        if constexpr (JITTER) {
+            uint32_t px = standInPixel(pix, walks[0], walkers);
+            asm volatile("" : "+v"(px));
+            r[0] = makeSoftListRay<true>(p, rel, l, softListSampleAt(p, l, from + j, px));
+        } else r[0] = makeSoftListRay(p, rel, l, from + j);
         bool occluded[1];
         traversePacket<1, false>(p, bvh, r, walks, occluded, share);
         mine[l >> 2][freshLaneId()] += (walks[0] && !occluded[0]) ? (1u << ((l & 3u) * 8u)) : 0u;   // comp:148, per sample
@@ -159,7 +205,8 @@ __device__ __forceinline__ void softListAdaptiveStore(const TraceParams& p, uint
 // phase, or whose pairs' lights have no lane in the tile, runs no walk in it, contributes 0 and still reaches both barriers.
 // A byte holds at most 48 summed over BOTH sets and all four waves -- c_k + rest <= n_l <= 48 --, so a packed add never carries into
 // the next byte.  SPLIT 1: one wave, the same two loops, no barrier.
-template <int SPLIT, int GEOM>
+// JITTER: the tables are honoured.  They change the offsets alone, so nothing above changes: no barrier is added or moved.
+template <int SPLIT, int GEOM, bool JITTER>
 __global__ __launch_bounds__(64 * SPLIT) __attribute__((amdgpu_waves_per_eu(8)))
 void shadowSoftLightListAdaptivePacketKernel(TraceParams p) {
     static_assert(SPLIT == 1 || SPLIT == 4, "one wave per tile, or four that deal its pairs");
@@ -178,7 +225,7 @@ void shadowSoftLightListAdaptivePacketKernel(TraceParams p) {
         partial[0][wave][0][ln] = 0; partial[0][wave][1][ln] = 0;
         partial[1][wave][0][ln] = 0; partial[1][wave][1][ln] = 0;
     }
-    softListAdaptivePhase<SPLIT, false>(p, bvh, d.rel, d.bits, wave, shareSlots[wave], partial[0][wave]);
+    softListAdaptivePhase<SPLIT, false, JITTER>(p, bvh, d.rel, d.bits, wave, shareSlots[wave], partial[0][wave], pix);
     if constexpr (SPLIT > 1) __syncthreads();                            // BARRIER 1
     uint32_t pen;
     {
@@ -192,7 +239,7 @@ void shadowSoftLightListAdaptivePacketKernel(TraceParams p) {
             return;
         }
     }
-    softListAdaptivePhase<SPLIT, true>(p, bvh, d.rel, pen, wave, shareSlots[wave], partial[1][wave]);
+    softListAdaptivePhase<SPLIT, true, JITTER>(p, bvh, d.rel, pen, wave, shareSlots[wave], partial[1][wave], pix);
     if constexpr (SPLIT > 1) {
         __syncthreads();                                                 // BARRIER 2
         if (wave != 0) return;
@@ -207,22 +254,46 @@ void shadowSoftLightListAdaptivePacketKernel(TraceParams p) {
     softListAdaptiveStore(p, pix, lo0, hi0, lo1, hi1);
 }
 
-hipError_t launchShadowSoftLightListAdaptive(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
-    if (!p.mask || p.nsamples < 1 || p.nsamples > 8) return hipErrorInvalidValue;
-    for (uint32_t l = 0; l < p.nsamples; ++l) {                          // (what keeps every index inside p.offsets, and k_l below the samples)
+// What keeps every index inside p.offsets, and k_l below the samples.  tables: T_l is looked at too -- 0, or samples .. 48 - first on
+// a soft entry, so that first + sampleIndexOf(...) < SOFT_LIST_SLOT for every pixel.
+static bool softListAdaptiveParamsOk(const TraceParams& p, bool tables) {
+    if (!p.mask || p.nsamples < 1 || p.nsamples > 8) return false;
+    for (uint32_t l = 0; l < p.nsamples; ++l) {
         uint32_t bits[4];
         __builtin_memcpy(bits, p.offsets[SOFT_LIST_SLOT + 2u * l + 1u], sizeof(bits));
         if (bits[0] > 1u || bits[1] < 1u || bits[1] > SOFT_LIST_SLOT || (bits[1] > 1u && (uint64_t)bits[2] + bits[1] > SOFT_LIST_SLOT))
-            return hipErrorInvalidValue;
-        if (bits[3] >= bits[1]) return hipErrorInvalidValue;
+            return false;
+        if (bits[3] >= bits[1]) return false;
+        if (!tables) continue;
+        uint32_t table;
+        __builtin_memcpy(&table, &p.offsets[l][3], sizeof(table));
+        if (table != 0u && (bits[1] < 2u || table < bits[1] || (uint64_t)bits[2] + table > SOFT_LIST_SLOT)) return false;
     }
+    return true;
+}
+
+hipError_t launchShadowSoftLightListAdaptive(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
+    if (!softListAdaptiveParamsOk(p, false)) return hipErrorInvalidValue;
     static const char* const names[2][3] = {
         { "shadowSoftLightListAdaptivePacketKernel<1,general>", "shadowSoftLightListAdaptivePacketKernel<1,rows>",
           "shadowSoftLightListAdaptivePacketKernel<1,bands>" },
         { "shadowSoftLightListAdaptivePacketKernel<4,general>", "shadowSoftLightListAdaptivePacketKernel<4,rows>",
           "shadowSoftLightListAdaptivePacketKernel<4,bands>" } };
-    return launchLoopFamily(variant, p, stream, name, shadowSoftLightListAdaptiveShareKernel, "shadowSoftLightListAdaptiveShareKernel", names,
-                            [&](dim3 grid, auto split, auto geom) {
+    return launchLoopFamily(variant, p, stream, name, shadowSoftLightListAdaptiveShareKernel<false>, "shadowSoftLightListAdaptiveShareKernel",
+                            names, [&](dim3 grid, auto split, auto geom) {
         constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;
-        hipLaunchKernelGGL((shadowSoftLightListAdaptivePacketKernel<SPLIT, GEOM>), grid, dim3(64 * SPLIT), 0, stream, p); });
+        hipLaunchKernelGGL((shadowSoftLightListAdaptivePacketKernel<SPLIT, GEOM, false>), grid, dim3(64 * SPLIT), 0, stream, p); });
+}
+
+hipError_t launchShadowSoftLightListJittered(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
+    if (!softListAdaptiveParamsOk(p, true)) return hipErrorInvalidValue;
+    static const char* const names[2][3] = {
+        { "shadowSoftLightListAdaptivePacketKernel<1,general,jitter>", "shadowSoftLightListAdaptivePacketKernel<1,rows,jitter>",
+          "shadowSoftLightListAdaptivePacketKernel<1,bands,jitter>" },
+        { "shadowSoftLightListAdaptivePacketKernel<4,general,jitter>", "shadowSoftLightListAdaptivePacketKernel<4,rows,jitter>",
+          "shadowSoftLightListAdaptivePacketKernel<4,bands,jitter>" } };
+    return launchLoopFamily(variant, p, stream, name, shadowSoftLightListAdaptiveShareKernel<true>,
+                            "shadowSoftLightListAdaptiveShareKernel<jitter>", names, [&](dim3 grid, auto split, auto geom) {
+        constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;
+        hipLaunchKernelGGL((shadowSoftLightListAdaptivePacketKernel<SPLIT, GEOM, true>), grid, dim3(64 * SPLIT), 0, stream, p); });
 }

@@ -1,7 +1,8 @@
 """Kernel resources and instruction text of rts_kernels.hip, parent commit against this one (profiles/r14/kernel_resources.txt).
 
-    python tools/kernel_resources_ab.py PARENT_LOG PARENT_S NEW_LOG NEW_S
+    python tools/kernel_resources_ab.py PARENT_LOG PARENT_S NEW_LOG NEW_S [PARENT_NAME=NEW_NAME ...]
 
+PARENT_NAME=NEW_NAME: a kernel that only changed its mangled name (it gained a template parameter, say) is compared under the parent's.
 LOG = the output of `make -C raytracedshadows_amd/csrc asm` in that tree, S = the build/rts_kernels.s it writes.  A kernel counts as
 the same when every figure of its resource remark and the hash of its instructions and labels agree."""
 import hashlib
@@ -31,6 +32,9 @@ def bodies(path):
 pr, nr = remarks(sys.argv[1]), remarks(sys.argv[3])
 pb = bodies(sys.argv[2])
 nb = bodies(sys.argv[4])
+for old, new in (a.split("=") for a in sys.argv[5:]):
+    nr[old] = nr.pop(new); nb[old] = nb.pop(new)
+    print("# renamed:", old, "is this commit's", new)
 keys = ["VGPRs", "TotalSGPRs", "ScratchSize", "Occupancy", "LDS Size"]
 def row(r): return " ".join(f"{k.split()[0]}={r.get(k, r.get(k+' [bytes/lane]', '?'))}" for k in keys)
 print("# hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (`make asm`) of rts_kernels.hip, parent commit and this commit.")

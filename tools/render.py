@@ -25,15 +25,17 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out=""):
-    """A frame lit by `count` area lights of `spp` samples: one list dispatch (adaptive with `probe` != 0), then one combine pass per
-    light over its plane."""
+def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0):
+    """A frame lit by `count` area lights of `spp` samples: one list dispatch (adaptive with `probe` != 0; with `table` every light
+    takes its samples from a per-pixel jitter table of `table` entries), then one combine pass per light over its plane."""
     from raytracedshadows_amd import api, scenes
     from soft_list_ab import entries
     if not 1 <= count <= 8 or count * max(spp, 1) > 48:
         sys.exit("render: --soft-list takes 1..8 lights of at most 48 samples in all")
     if probe and not 1 <= probe < spp:
         sys.exit("render: --soft-list N --adaptive K takes 1 <= K < spp")
+    if table and (not probe or table < spp or (count - 1) * spp + table > 48):
+        sys.exit("render: --table T goes with --soft-list N --adaptive K and takes spp <= T <= 48 - (N - 1) * spp")
     lights = api.SoftLightList.make(entries(wl.scene, count, spp), scenes.jitter_offsets(48, 1.0, 19))
     d_pos, d_nrm, d_map = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
     d_counts, d_rgb = ctx.malloc(count * W * H), ctx.malloc(W * H * 3)
@@ -43,7 +45,7 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out=""):
     api.facing_lights_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, W, H, d_map)
     if probe:
         ctx.trace_soft_light_list_adaptive_device(wl.constants, lights, (probe,) * count, d_pos, W, H, d_counts, d_refined=d_refined,
-                                                  d_lights_map=d_map)
+                                                  d_lights_map=d_map, tables=(table,) * count if table else None)
     else:
         ctx.trace_soft_light_list_device(wl.constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
     ctx.synchronize()
@@ -83,6 +85,8 @@ def main():
     ap.add_argument("--adaptive", type=int, default=0, metavar="K",
                     help="trace the soft light adaptively: K probe samples per pixel, the others only in the penumbra (1 <= K < spp)")
     ap.add_argument("--refined", default="", metavar="FILE.ppm", help="with --adaptive: also write the refined plane as an image")
+    ap.add_argument("--table", type=int, default=0, metavar="T",
+                    help="with --soft-list N --adaptive K: a per-pixel jitter table of T entries per light (spp <= T), its start hashed per pixel")
     ap.add_argument("--soft-list", type=int, default=0, metavar="N",
                     help="light the frame by N area lights of --spp samples each, traced in one soft light list dispatch")
     args = ap.parse_args()
@@ -94,7 +98,7 @@ def main():
     with api.ShadowContext(0) as ctx:
         ctx.set_bvh(wl.packed)
         if args.soft_list:
-            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined)
+            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
         t0 = time.time()
         api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
