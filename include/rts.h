@@ -529,6 +529,52 @@ int rts_trace_soft_light_list_stripes_device(rts_ctx* ctx, const rts_constants* 
                                              const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
                                              uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts, void* stream);
 
+/* SOFT LIGHT LIST DISTANCE: a soft light list with the NEAREST BLOCKER per light beside its count -- one DISTANCE PLANE per light, what
+ * contact-hardening penumbrae, a distance-guided denoiser or a distance fade want of several area lights, without one
+ * rts_trace_soft_distance* dispatch per light.  The arguments are those of rts_trace_soft_light_list*, with `distances` in front of
+ * `counts`.  For pixel p of the rows the call owns and l < list->count, with the derived rts_light of entry l as defined above
+ * (SOFT LIGHT LISTS) and on = (lights_map == NULL || (lights_map[p] >> l) & 1):
+ *   distances[l * W * H + p] = on ? the float rts_trace_soft_distance* writes at p for that derived light alone -- the minimum over the
+ *                                   light's samples of the one-ray distance (SOFT-SHADOW OCCLUDER DISTANCE), +Inf exactly when every
+ *                                   sample is unoccluded; a hard entry (nsamples 0 or 1) gives the one-ray distance of
+ *                                   rts_trace_shadow_distance*, its ray aimed at xyz as given
+ *                                 : +0.0f
+ *   counts[l * W * H + p]    = byte for byte what rts_trace_soft_light_list* writes.
+ * Hence, where on, counts == max(1, nsamples_l) exactly where the distance is +Inf.  Planes l >= count are never touched in either
+ * output; rows outside the range / stripe are not touched in any plane.  A pixel whose map byte has no bit below count gets +0.0f and 0
+ * in every plane, its position is never looked at (NaN allowed) and changes no other pixel.  Every one-ray distance is a bit pattern
+ * >= +0 whose unsigned order is the float order, so a light's minimum is an integer minimum per (pixel, light) and its count an integer
+ * sum: no order of the pairs, no deal over waves and no option can change a bit.  The per-pixel jitter table and
+ * probes are not offered here, nor is the MEAN blocker distance.
+ *   * distances: count * W * H floats, plane l at distances + l * W * H.  counts: NULL, or count * W * H bytes.  lights_map as above.
+ *   * RTS_ERR_INVALID_ARG, nothing written, no counter moved: everything rts_trace_soft_light_list* refuses of the list, the row range,
+ *     the band and the stripe; distances == NULL.
+ *   * results never depend on an option.  "kernel" picks the FAMILY as for a soft light list: 0, 1, 2, 7 (and -1 below 256 K pixels)
+ *     the lane-per-ray walk over 16 x 16 blocks, lights in order and samples in order; 3..6, 8, 9 (and -1 from 256 K pixels) the
+ *     stackless packet over 8 x 8 tiles -- with "soft_split" 1 (default) four waves per tile that deal the (light, sample) pairs as the
+ *     soft light list does and join their minima and counts in LDS, with 0 one wave walks every pair.  A stripe's band is a multiple of
+ *     16 rows for the first family, of 8 for the second; a stripe that owns no band launches nothing, writes nothing and returns
+ *     RTS_OK.  "packet_budget", "packet_share", "xcd_swizzle" and "row_order" apply, for speed only.
+ *   * a light no pixel of a wave's tile is marked for costs that wave nothing: it is skipped before any ray is set up.  Unlike the
+ *     counts alone, a distance needs every accepted triangle of every sample: no walk ends at its first hit.
+ *   * like the other block traces it ignores split tables, tile orders, follow mode, "block_waves", "wide_lane", wave statistics and
+ *     the clock probe, and never drops or alters any of them.
+ *   * the device forms are asynchronous, allocate nothing and read nothing back; under graph capture each adds ONE kernel node,
+ *     constants, list and options by value.  The host form copies in its rows only, traces, copies out both outputs and synchronises.
+ *   * get-only option "soft_list_distance_traces": launches so far (no other counter moves for them); rts_ctx_last_kernel_name then
+ *     names "shadowSoftLightListDistanceShareKernel" or "shadowSoftLightListDistancePacketKernel<S,geom>", S = 4 or 1 waves per tile,
+ *     geom = rows, bands or general as for "shadowSoftDistancePacketKernel". */
+int rts_trace_soft_light_list_distance(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                       const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                       uint32_t row_end, float* distances, uint8_t* counts);
+int rts_trace_soft_light_list_distance_device(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                              const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                              uint32_t row_begin, uint32_t row_end, float* d_distances, uint8_t* d_counts, void* stream);
+int rts_trace_soft_light_list_distance_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                                      const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                                      uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, float* d_distances,
+                                                      uint8_t* d_counts, void* stream);
+
 /* ADAPTIVE SOFT LIGHT LISTS: a soft light list with a probe count per light -- the two traces above joined inside ONE dispatch: every
  * light's probe is walked first, and a light's remaining samples only over the pixels whose probe of THAT light disagrees.  The
  * arguments are those of rts_trace_soft_light_list*, plus `probes` (list->count entries on the host, read by value at the call, under

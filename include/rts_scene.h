@@ -128,6 +128,15 @@ int rtsh_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_consta
 int rtsh_soft_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_soft_light_list* list,
                          const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
                          uint8_t* counts, int threads);
+/* SOFT LIGHT LIST DISTANCE on the host: the definition of rts_trace_soft_light_list_distance* (include/rts.h) as one straight loop over
+ * (pixel, light, sample) on rtsh_soft_distance's walk and rtsh_soft_light_list's ray set-up -- distances[l * W * H + p] = the integer
+ * minimum over light l's samples of the one-ray distance, counts[l * W * H + p] (counts nullable) = the number of them that are +Inf,
+ * where lights_map == NULL or bit l of lights_map[p] is set, else +0.0f and 0.  A pixel whose map byte has no bit below count gets +0.0f
+ * and 0 in every plane and its position is never read; other rows and the planes l >= count are not touched.  The refusals of
+ * include/rts.h: RTS_ERR_INVALID_ARG.  Runs without a GPU: the checker of the device forms, bit for bit. */
+int rtsh_soft_light_list_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_soft_light_list* list,
+                                  const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                  uint32_t row_end, float* distances, uint8_t* counts, int threads);
 /* ADAPTIVE SOFT LIGHT LISTS on the host: the definition of rts_trace_soft_light_list_adaptive* (include/rts.h) as one straight loop
  * over (pixel, light, sample) on rtsh_soft_light_list's walk and ray set-up -- light l's samples in order, and after its first
  * probes[l] != 0 of them the verdict 0 or max(1, nsamples_l) where they agree, no further ray; else the full count, and bit l of

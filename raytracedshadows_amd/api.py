@@ -270,6 +270,14 @@ _sig("rts_trace_soft_light_list_stripes_device", C.c_int, C.c_void_p, C.POINTER(
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_soft_light_list", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
      C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rts_trace_soft_light_list_distance", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_soft_light_list_distance_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rts_trace_soft_light_list_distance_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList),
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_soft_light_list_distance", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
 _sig("rts_trace_soft_light_list_adaptive", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
      C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, _u32p, C.c_void_p)
 _sig("rts_trace_soft_light_list_adaptive_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList),
@@ -804,6 +812,44 @@ class ShadowContext:
                                                              C.c_void_p(d_counts), C.c_void_p(stream or 0)),
                "rts_trace_soft_light_list_stripes_device")
 
+    # -- soft light list distance (include/rts.h): a soft light list with the nearest blocker per light beside its count --
+    def trace_soft_light_list_distance(self, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None,
+                                       out=None, counts=None, want_counts=True):
+        """Host-pointer dispatch; returns ``(float32[count, H, W] distances, uint8[count, H, W] counts)`` (counts None with
+        ``want_counts`` False): plane ``l`` = the minimum of light ``l``'s samples' distances and the number of unoccluded ones where
+        ``lights_map`` (uint8[H, W], or None: everywhere) has bit ``l`` set, else +0 and 0.  ``out`` / ``counts``: arrays of at least
+        ``count`` planes to write the rows into."""
+        positions, lights_map = _frame_inputs("trace_soft_light_list_distance", positions, width, height, lights_map, "lights_map")
+        row_end = height if row_end is None else row_end
+        planes = lights.count if lights is not None else 1
+        dist = out if out is not None else np.zeros((planes, height, width), dtype=np.float32)
+        if counts is None and want_counts:
+            counts = np.zeros((planes, height, width), dtype=np.uint8)
+        _check(_lib.rts_trace_soft_light_list_distance(self._h, C.byref(constants), _ref(lights), _ptr(positions),
+                                                       _ptr_or_none(lights_map), width, height, row_begin, row_end,
+                                                       _ptr_or_none(dist), _ptr_or_none(counts)), "rts_trace_soft_light_list_distance")
+        return dist, counts
+
+    def trace_soft_light_list_distance_device(self, constants, lights, d_positions, width, height, d_distances, d_counts=None,
+                                              d_lights_map=None, row_begin=0, row_end=None, stream=None):
+        """Device pointers, asynchronous: d_distances = count * width * height floats, d_counts = count * width * height bytes or None,
+        d_lights_map = width * height bytes or None."""
+        row_end = height if row_end is None else row_end
+        _check(_lib.rts_trace_soft_light_list_distance_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
+                                                              C.c_void_p(d_lights_map or 0), width, height, row_begin, row_end,
+                                                              C.c_void_p(d_distances or 0), C.c_void_p(d_counts or 0),
+                                                              C.c_void_p(stream or 0)),
+               "rts_trace_soft_light_list_distance_device")
+
+    def trace_soft_light_list_distance_stripes_device(self, constants, lights, d_positions, width, height, d_distances, band_rows,
+                                                      n_stripes, stripe, d_counts=None, d_lights_map=None, stream=None):
+        """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        _check(_lib.rts_trace_soft_light_list_distance_stripes_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
+                                                                      C.c_void_p(d_lights_map or 0), width, height, band_rows, n_stripes,
+                                                                      stripe, C.c_void_p(d_distances or 0), C.c_void_p(d_counts or 0),
+                                                                      C.c_void_p(stream or 0)),
+               "rts_trace_soft_light_list_distance_stripes_device")
+
     # -- adaptive soft light lists (include/rts.h): a soft light list with a probe count per light, its penumbra alone refined --
     def trace_soft_light_list_adaptive(self, constants, lights, probes, positions, width, height, lights_map=None, row_begin=0,
                                        row_end=None, out=None, refined=None, want_refined=True, tables=None):
@@ -1242,6 +1288,24 @@ def soft_light_list(packed, constants, lights, positions, width, height, lights_
                                      _ptr_or_none(lights_map), width, height, row_begin, row_end, _ptr(counts),
                                      threads), "rtsh_soft_light_list")
     return counts
+
+
+def soft_light_list_distance(packed, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None,
+                             counts=None, threads=0, want_counts=True):
+    """A soft light list distance trace on the host (rtsh_soft_light_list_distance, no GPU): ``(float32[count, H, W], uint8[count, H,
+    W])`` -- per light the minimum of its samples' distances and the number of unoccluded ones where ``lights_map`` (None: everywhere)
+    has bit ``l`` set, else +0 and 0 (counts None with ``want_counts`` False).  ``out`` / ``counts``: at least ``count`` planes."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    positions, lights_map = _frame_inputs("soft_light_list_distance", positions, width, height, lights_map, "lights_map")
+    row_end = height if row_end is None else row_end
+    planes = lights.count if lights is not None else 1
+    dist = out if out is not None else np.zeros((planes, height, width), np.float32)
+    if counts is None and want_counts:
+        counts = np.zeros((planes, height, width), np.uint8)
+    _check(_lib.rtsh_soft_light_list_distance(_ptr(packed), packed.shape[0], C.byref(constants), _ref(lights), _ptr(positions),
+                                              _ptr_or_none(lights_map), width, height, row_begin, row_end, _ptr_or_none(dist),
+                                              _ptr_or_none(counts), threads), "rtsh_soft_light_list_distance")
+    return dist, counts
 
 
 def _probes(lights, probes, what="probes"):

@@ -9,6 +9,7 @@
 #include "rts_adaptive.h"
 #include "rts_soft_light_list.h"
 #include "rts_soft_light_list_adaptive.h"
+#include "rts_soft_light_list_distance.h"
 #include "rts_dispatch.h"
 #include "rts_args.h"
 #include "rts_refit.h"
@@ -50,6 +51,7 @@ struct rts_ctx {
     uint64_t softListAdaptiveTraces = 0;              // launches of an adaptive soft light list kernel (get-only option "soft_list_adaptive_traces")
     uint64_t softListJitterTraces = 0;                // launches of a jittered adaptive soft light list kernel (get-only option "soft_list_jitter_traces")
     uint64_t softLightListTraces = 0;                 // launches of a soft light list kernel (get-only option "soft_light_list_traces")
+    uint64_t softListDistanceTraces = 0;              // launches of a soft light list distance kernel (get-only option "soft_list_distance_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
     int packetShare = 4;
@@ -563,6 +565,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "soft_list_adaptive_traces")) { *value = (int)(c->softListAdaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_list_jitter_traces")) { *value = (int)(c->softListJitterTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_light_list_traces")) { *value = (int)(c->softLightListTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "soft_list_distance_traces")) { *value = (int)(c->softListDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
     if (!strcmp(key, "tile_order_planned")) { *value = c->tileOrderPlanned ? 1 : 0; return RTS_OK; }
@@ -1009,8 +1012,9 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 // probe, refined: of Staged::Adaptive alone; its refined plane (optional) is staged in the distances' buffer, which it does not use.
 // Staged::SoftLightList: lights is the rts_soft_light_list, mask its count planes -- `count` planes of frameH rows in the caller's
 // buffer, of the staged rows alone on the device.  Staged::SoftListAdaptive: the same, with `probes` (one per light) and the refined plane;
-// with `tables` the jittered form, whose hash pixelBase makes that of the caller's frame.
-enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive };
+// with `tables` the jittered form, whose hash pixelBase makes that of the caller's frame.  Staged::SoftListDistance: the soft light
+// list's staging with `distance` its distance planes, staged and copied back plane by plane like the counts (mask, optional here).
+enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive, SoftListDistance };
 static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, const void* lights, const float* positions, const uint8_t* active,
                            uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask, uint32_t probe = 0,
                            uint8_t* refined = nullptr, uint32_t frameH = 0, const uint32_t* probes = nullptr,
@@ -1021,9 +1025,11 @@ static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, cons
     const uint32_t rows = row_end - row_begin;
     const size_t first = (size_t)row_begin * W, pixels = (size_t)rows * W;
     int s = ensure(&c->d_in, &c->inBytes, pixels * 16);
-    if (s == RTS_OK && distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4);
+    const size_t planes = (what == Staged::SoftLightList || what == Staged::SoftListAdaptive || what == Staged::SoftListDistance)
+                              ? ((const rts_soft_light_list*)lights)->count : 1u;
+    const size_t distPlanes = what == Staged::SoftListDistance ? planes : 1u;
+    if (s == RTS_OK && distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4 * distPlanes);
     if (s == RTS_OK && refined) s = ensure(&c->d_dist, &c->distBytes, pixels);
-    const size_t planes = (what == Staged::SoftLightList || what == Staged::SoftListAdaptive) ? ((const rts_soft_light_list*)lights)->count : 1u;
     if (s == RTS_OK && mask) s = ensure(&c->d_out, &c->outBytes, pixels * planes);
     if (s == RTS_OK && active) s = ensure(&c->d_act, &c->actBytes, pixels);
     if (s != RTS_OK) return s;
@@ -1053,10 +1059,14 @@ static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, cons
     case Staged::SoftListAdaptive:
         s = rts_trace_soft_light_list_jittered_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, probes,
                                                       tables, refined ? (uint8_t*)c->d_dist : nullptr, nullptr); break;
+    case Staged::SoftListDistance:
+        s = rts_trace_soft_light_list_distance_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_dist, d_mask,
+                                                      nullptr); break;
     }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
-    if (distance) RTS_HIP(hipMemcpy(distance + first, c->d_dist, pixels * 4, hipMemcpyDeviceToHost));
+    for (size_t l = 0; distance && l < distPlanes; ++l)
+        RTS_HIP(hipMemcpy(distance + l * ((size_t)W * frameH) + first, (const float*)c->d_dist + l * pixels, pixels * 4, hipMemcpyDeviceToHost));
     if (refined) RTS_HIP(hipMemcpy(refined + first, c->d_dist, pixels, hipMemcpyDeviceToHost));
     for (size_t l = 0; mask && l < planes; ++l)
         RTS_HIP(hipMemcpy(mask + l * ((size_t)W * frameH) + first, (const uint8_t*)c->d_out + l * pixels, pixels, hipMemcpyDeviceToHost));
@@ -1181,6 +1191,44 @@ int rts_trace_soft_light_list(rts_ctx* c, const rts_constants* k, const rts_soft
     if (!c || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
     if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
     return traceStagedRows(c, Staged::SoftLightList, k, list, positions, lights_map, W, row_begin, row_end, nullptr, counts, 0, nullptr, H);
+}
+
+// ---- soft light list distance (include/rts.h): a soft light list with the nearest blocker per light beside its count --------------
+// One launch of a soft light list distance kernel (rts_soft_light_list_distance.inc): the soft list's argument block, the distance
+// planes in the distance's slot, the count planes (optional) in the mask's.
+static int traceSoftListDistanceImpl(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
+                                     const uint8_t* d_lights_map, const Dispatch& g, float* d_distances, uint8_t* d_counts, void* stream) {
+    TraceParams p; uint32_t rows = 0; int s;
+    if (beginFrame(c, k, d_positions, d_counts, d_distances && rts::softListOk(list), g, p, &rows, &s) != Begin::Go) return s;
+    setSoftList(p, k, list, d_lights_map);
+    p.distance = d_distances;
+    return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::softListDistanceTraces, rts::launchShadowSoftLightListDistance,
+                        stream);
+}
+
+int rts_trace_soft_light_list_distance_device(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
+                                              const uint8_t* d_lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                              float* d_distances, uint8_t* d_counts, void* stream) {
+    return traceSoftListDistanceImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofRows(W, H, row_begin, row_end), d_distances, d_counts,
+                                     stream);
+}
+
+int rts_trace_soft_light_list_distance_stripes_device(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list,
+                                                      const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                                      uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, float* d_distances,
+                                                      uint8_t* d_counts, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceSoftListDistanceImpl(c, k, list, d_positions, d_lights_map, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_distances,
+                                     d_counts, stream);
+}
+
+// The host form: the soft list's staging, both outputs coming back plane by plane to the caller's planes of H rows.
+int rts_trace_soft_light_list_distance(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* positions,
+                                       const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                       float* distances, uint8_t* counts) {
+    if (!c || !k || !positions || !distances || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
+    return traceStagedRows(c, Staged::SoftListDistance, k, list, positions, lights_map, W, row_begin, row_end, distances, counts, 0, nullptr, H);
 }
 
 // ---- adaptive soft light lists (include/rts.h): a soft light list with a probe count per light, its penumbra alone refined ---------

@@ -294,3 +294,5 @@ hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
 #include "rts_soft_light_list.inc"
 // adaptive soft light lists: a probe per light, its penumbra alone refined (its launch is declared in rts_soft_light_list_adaptive.h)
 #include "rts_soft_light_list_adaptive.inc"
+// soft light list distance: a distance plane per light beside its count plane (its launch is declared in rts_soft_light_list_distance.h)
+#include "rts_soft_light_list_distance.inc"

@@ -419,6 +419,47 @@ extern "C" int rtsh_soft_light_list(const rts_vec4u* packed, size_t count_vec4, 
     return RTS_OK;
 }
 
+// ---- soft light list distance on the host (include/rts_scene.h): the checker of rts_trace_soft_light_list_distance* ----
+// The definition of include/rts.h as a straight loop over (pixel, light, sample): rtsh_soft_light_list's aim and ray, frameDistance's
+// integer minimum and count per light.
+extern "C" int rtsh_soft_light_list_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
+                                             const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                             uint32_t row_end, float* distances, uint8_t* counts, int threads) {
+    if (!packed || !k || !positions || !distances || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t below = (1u << list->count) - 1u;
+    const size_t first = (size_t)row_begin * W, plane = (size_t)W * H;
+    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t n) {
+        const size_t i = first + n;
+        const uint32_t bits = (lights_map ? lights_map[i] : 0xFFu) & below;
+        const float* q = positions + i * 4;                              // (not read where bits == 0)
+        for (uint32_t l = 0; l < list->count; ++l) {
+            uint32_t best = 0u, lit = 0;                                 // (+0.0f and 0 where the map's bit is clear)
+            if ((bits >> l) & 1u) {
+                const rts_soft_light_entry& e = list->lights[l];
+                const uint32_t ns = e.nsamples > 1 ? e.nsamples : 1u;
+                best = 0x7F800000u;
+                for (uint32_t j = 0; j < ns; ++j) {
+                    V3 L{ e.xyz[0], e.xyz[1], e.xyz[2] };
+                    if (ns > 1) {
+                        const float* o = list->offsets[e.first + j];
+                        const float ox = e.radius * o[0], oy = e.radius * o[1], oz = e.radius * o[2];
+                        L.x = L.x + ox; L.y = L.y + oy; L.z = L.z + oz;
+                    }
+                    const uint32_t one = rayDistanceBits(bvh, shadowRay(k->cameraPosition, V3{ q[0], q[1], q[2] }, e.type, L));
+                    lit += one == 0x7F800000u ? 1u : 0u;                 // comp:148, per sample
+                    if (one < best) best = one;
+                }
+            }
+            distances[l * plane + i] = asFloat(best);
+            if (counts) counts[l * plane + i] = (uint8_t)lit;            // comp:150
+        }
+    });
+    return RTS_OK;
+}
+
 // ---- adaptive soft light lists on the host (include/rts_scene.h): the checker of rts_trace_soft_light_list_adaptive* ----
 // The definition of include/rts.h applied literally: rtsh_soft_light_list's loop, and per light rtsh_shadow_mask_adaptive's decision
 // after the probe's samples.

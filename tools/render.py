@@ -1,7 +1,7 @@
 """Human-checkable output: OBJ scene -> BVH -> G-buffer (GPU) -> shadow mask (GPU) -> combine -> PPM.
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
-                           [--soft-list N [--adaptive K [--refined FILE.ppm]]]
+                           [--soft-list N [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]]
 
 --cull: the shadow pass traces only the pixels of the facing mark (rtsh_facing_active_device: not the background, not the surfaces
 that face away from the light) -- the same image, byte for byte.
@@ -11,7 +11,10 @@ remaining samples only where the probe disagrees; --refined writes the plane of 
 <= 48), traced in ONE rts_trace_soft_light_list_device dispatch through the facing map; the image is the mean of the lights' own
 combine passes, each over its count plane.  With --adaptive K the list is traced by rts_trace_soft_light_list_adaptive_device with a
 probe of K samples for every light (1 <= K < spp); --refined then writes the list's refined plane as a grey-scale image, a pixel's
-value the share of the lights that took their full count there.
+value the share of the lights that took their full count there.  With --distance FILE.ppm (and no --adaptive) the list is traced by
+rts_trace_soft_light_list_distance_device, which gives every light's nearest blocker over its samples beside its count plane; the file
+shows, per pixel, the nearest blocker over the lights that reach it as a grey-scale image: lit by all of them white, the rest scaled to
+the frame's largest finite value.
 """
 import argparse
 import os
@@ -25,7 +28,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0):
+def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, distance_out=""):
     """A frame lit by `count` area lights of `spp` samples: one list dispatch (adaptive with `probe` != 0; with `table` every light
     takes its samples from a per-pixel jitter table of `table` entries), then one combine pass per light over its plane."""
     from raytracedshadows_amd import api, scenes
@@ -34,18 +37,23 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0):
         sys.exit("render: --soft-list takes 1..8 lights of at most 48 samples in all")
     if probe and not 1 <= probe < spp:
         sys.exit("render: --soft-list N --adaptive K takes 1 <= K < spp")
+    if distance_out and probe:
+        sys.exit("render: --soft-list N --distance FILE.ppm does not go with --adaptive (the distance list has no probes)")
     if table and (not probe or table < spp or (count - 1) * spp + table > 48):
         sys.exit("render: --table T goes with --soft-list N --adaptive K and takes spp <= T <= 48 - (N - 1) * spp")
     lights = api.SoftLightList.make(entries(wl.scene, count, spp), scenes.jitter_offsets(48, 1.0, 19))
     d_pos, d_nrm, d_map = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
     d_counts, d_rgb = ctx.malloc(count * W * H), ctx.malloc(W * H * 3)
     d_refined = ctx.malloc(W * H) if probe and refined_out else None
+    d_dist = ctx.malloc(count * W * H * 4) if distance_out else None
     t0 = time.time()
     api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
     api.facing_lights_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, W, H, d_map)
     if probe:
         ctx.trace_soft_light_list_adaptive_device(wl.constants, lights, (probe,) * count, d_pos, W, H, d_counts, d_refined=d_refined,
                                                   d_lights_map=d_map, tables=(table,) * count if table else None)
+    elif d_dist:
+        ctx.trace_soft_light_list_distance_device(wl.constants, lights, d_pos, W, H, d_dist, d_counts, d_lights_map=d_map)
     else:
         ctx.trace_soft_light_list_device(wl.constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
     ctx.synchronize()
@@ -62,6 +70,19 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0):
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     api.write_ppm(out, np.clip(total / count + 0.5, 0, 255).astype(np.uint8))
     print(f"wrote {out}: {W}x{H}, lit fraction per light {[round(float((planes[l] > 0).mean()), 3) for l in range(count)]}")
+    if d_dist:
+        dist, marks = np.zeros((count, H, W), np.float32), np.zeros((H, W), np.uint8)
+        ctx.d2h(dist, d_dist)
+        ctx.d2h(marks, d_map)
+        reached = np.stack([((marks >> l) & 1) != 0 for l in range(count)])          # (+0 where the map's bit is clear: no blocker)
+        nearest = np.where(reached, dist, np.inf).min(axis=0)
+        finite = np.isfinite(nearest)
+        top = float(nearest[finite].max()) if finite.any() else 0.0
+        grey = np.where(finite, np.clip(nearest / top if top > 0 else 0.0, 0.0, 1.0) * 254.0, 255.0).astype(np.uint8)
+        os.makedirs(os.path.dirname(os.path.abspath(distance_out)), exist_ok=True)
+        api.write_ppm(distance_out, np.repeat(grey[..., None], 3, axis=2))
+        print(f"wrote {distance_out}: nearest blocker over {count} lights, largest finite value {top:.6g}; share of the pixels with a "
+              f"blocker, per light {[round(float((reached[l] & np.isfinite(dist[l])).mean()), 3) for l in range(count)]}")
     if d_refined:
         refined = np.zeros((H, W), np.uint8)
         ctx.d2h(refined, d_refined)
@@ -98,7 +119,7 @@ def main():
     with api.ShadowContext(0) as ctx:
         ctx.set_bvh(wl.packed)
         if args.soft_list:
-            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table)
+            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
         t0 = time.time()
         api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
