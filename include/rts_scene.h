@@ -158,6 +158,42 @@ int rtsh_facing_lights(const rts_constants* constants, const rts_light_list* lis
 int rtsh_facing_lights_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* d_positions,
                               const float* d_normals, uint32_t W, uint32_t H, uint8_t* d_lights_map, void* stream);
 
+/* THE COMBINE PASS OF A LIGHT LIST: the image of a frame lit by all of a list's lights, from the list's own output, in ONE pass -- one
+ * read of the normal (and, for point lights, the position) per pixel, one launch, one RGB frame.  For pixel p, n = normals[p].xyz:
+ *   n all zero (background): rgb[p] = 0, 0, 0; nothing else of p is looked at (position, map byte and plane bytes may hold anything);
+ *   ambient = 0.15f + 0.05f * (1 - max0(N.(-cameraDirection)))                                  -- rtsh_combine's, once per pixel;
+ *   sum[c] = +0.0f;  for l = 0 .. count - 1, in this order, where lights_map == NULL or bit l of lights_map[p] is set:
+ *       direct = 1.25f * max0(N.L_l) * ((float)byte_l / samples_l)    -- rtsh_combine's expression for light l alone (an area light
+ *                                                                        counts by its centre), samples_l = (float)max(1, nsamples_l)
+ *       sum[c] = sum[c] + direct * color_l[c]                         -- two rounded operations: the library is built without contraction
+ *     (a light whose bit is clear adds nothing, and its plane byte at p is not looked at);
+ *   rgb[p][c] = rtsh_combine's byte of sum[c] + ambient (saturated in float before the conversion, a NaN gives 0).
+ * byte_l = counts[l * W * H + p] for a soft list (rts_trace_soft_light_list*'s planes); bit l of mask[p] as 0 or 1 with samples_l = 1
+ * for a hard list (rts_trace_light_list*'s mask).  max0(x) = x > 0 ? x : 0.  The order of the sum is part of the definition: float
+ * addition is not associative, and a fixed order is what lets the host form check the device form byte for byte.
+ * ANCHOR: a list of one light, white or colors == NULL, no map, gives rtsh_combine's bytes for that light over that plane
+ * (0 + direct * 1 + ambient is direct + ambient).  With the map of rtsh_facing_lights* and finite inputs the image equals the one
+ * without a map (a culled light's direct term is 1.25 * 0 * byte).
+ *   * colors: HOST memory in every form, count * 4 floats (light l at colors + 4 * l, .w ignored), passed to the kernel by value;
+ *     NULL: every light (1, 1, 1).  Any float is allowed; the rule above defines the result.
+ *   * positions may be NULL exactly when no light of the list is a point light; lights_map may be NULL; planes l >= count are never read.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: what rts_trace_light_list* / rts_trace_soft_light_list* refuse of a
+ *     list; NULL constants, normals, mask / counts or rgb; a point light without positions; W == 0 or H == 0; a NULL ctx.
+ *   * the device forms take DEVICE buffers (colors excepted), are asynchronous on `stream`, allocate nothing and read nothing back;
+ *     under graph capture each adds ONE kernel node, list, colours and constants by value.  They need no BVH and no alignment of any
+ *     buffer beyond its element type's.  One pixel per lane. */
+int rtsh_combine_light_list(const rts_constants* constants, const rts_light_list* list, const float* colors, const float* positions,
+                            const float* normals, const uint8_t* lights_map, const uint8_t* mask, uint32_t W, uint32_t H, uint8_t* rgb);
+int rtsh_combine_soft_light_list(const rts_constants* constants, const rts_soft_light_list* list, const float* colors,
+                                 const float* positions, const float* normals, const uint8_t* lights_map, const uint8_t* counts,
+                                 uint32_t W, uint32_t H, uint8_t* rgb);
+int rtsh_combine_light_list_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* colors,
+                                   const float* d_positions, const float* d_normals, const uint8_t* d_lights_map, const uint8_t* d_mask,
+                                   uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream);
+int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list, const float* colors,
+                                        const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                        const uint8_t* d_counts, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream);
+
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.
  * Call with vertices == NULL to query *vertex_count (3 per triangle) first.  Returns RTS_OK,

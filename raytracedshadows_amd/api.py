@@ -409,6 +409,14 @@ _sig("rtsh_combine_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants),
      C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_combine", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rtsh_combine_light_list", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rtsh_combine_soft_light_list", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rtsh_combine_light_list_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_combine_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_facing_active", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
      C.c_void_p)
 _sig("rtsh_facing_active_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
@@ -1363,6 +1371,72 @@ def facing_lights_device(ctx, constants, lights, d_positions, d_normals, width, 
     _check(_lib.rtsh_facing_lights_device(ctx.handle, C.byref(constants), lp, C.c_void_p(d_positions or 0), C.c_void_p(d_normals),
                                           width, height, C.c_void_p(d_lights_map), C.c_void_p(stream or 0)),
            "rtsh_facing_lights_device")
+
+
+def _colors(lights, colors):
+    """``colors`` (None: every light white, or ``count`` rows of 3 or 4 floats) as the host array of ``count * 4`` float32 the C
+    entry points read by value."""
+    if colors is None:
+        return None
+    colors = np.asarray(colors, np.float32)
+    if colors.ndim != 2 or colors.shape[1] not in (3, 4) or (lights is not None and colors.shape[0] != lights.count):
+        raise RtsError(1, "colors: one row of 3 (or 4) floats per light of the list")
+    out = np.zeros((max(1, colors.shape[0]), 4), np.float32)
+    out[:colors.shape[0], :colors.shape[1]] = colors
+    return out
+
+
+def _combine_list(fn, name, constants, lights, positions, normals, planes, lights_map, colors):
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    planes = np.ascontiguousarray(planes, np.uint8)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    if planes.size < (lights.count if name.startswith("rtsh_combine_soft") and lights is not None else 1) * H * W or \
+            (lights_map is not None and lights_map.size != H * W) or (positions is not None and positions.size != H * W * 4):
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    colors = _colors(lights, colors)
+    rgb = np.zeros((H, W, 3), np.uint8)
+    _check(fn(C.byref(constants), _ref(lights), _ptr_or_none(colors), _ptr_or_none(positions), _ptr(normals), _ptr_or_none(lights_map),
+              _ptr(planes), W, H, _ptr(rgb)), name)
+    return rgb
+
+
+def combine_light_list(constants, light_list, positions, normals, mask, lights_map=None, colors=None):
+    """The combine pass of a hard light list on the host (rtsh_combine_light_list): ``uint8[H, W, 3]`` -- every light's direct term
+    over its bit of ``mask`` (rts_trace_light_list*'s), times its colour, summed in list order, plus one ambient term.  ``colors``:
+    None (white), or one row of 3 floats per light; ``lights_map``: None, or ``uint8[H, W]`` (a light whose bit is clear adds nothing)."""
+    return _combine_list(_lib.rtsh_combine_light_list, "rtsh_combine_light_list", constants, light_list, positions, normals, mask,
+                         lights_map, colors)
+
+
+def combine_soft_light_list(constants, lights, positions, normals, counts, lights_map=None, colors=None):
+    """The combine pass of a soft light list on the host (rtsh_combine_soft_light_list): ``uint8[H, W, 3]`` -- light ``l``'s direct
+    term over plane ``l`` of ``counts`` (``uint8[>= count, H, W]``, rts_trace_soft_light_list*'s) divided by its sample count."""
+    return _combine_list(_lib.rtsh_combine_soft_light_list, "rtsh_combine_soft_light_list", constants, lights, positions, normals, counts,
+                         lights_map, colors)
+
+
+def combine_light_list_device(ctx, constants, light_list, d_positions, d_normals, d_mask, width, height, d_rgb, d_lights_map=None,
+                              colors=None, stream=None):
+    """The combine pass of a hard light list on the GPU: device pointers (``colors`` stays a host array), d_rgb = width*height*3
+    bytes, one kernel, asynchronous."""
+    colors = _colors(light_list, colors)
+    _check(_lib.rtsh_combine_light_list_device(ctx.handle, C.byref(constants), _ref(light_list), _ptr_or_none(colors),
+                                               C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
+                                               C.c_void_p(d_mask), width, height, C.c_void_p(d_rgb), C.c_void_p(stream or 0)),
+           "rtsh_combine_light_list_device")
+
+
+def combine_soft_light_list_device(ctx, constants, lights, d_positions, d_normals, d_counts, width, height, d_rgb, d_lights_map=None,
+                                   colors=None, stream=None):
+    """The combine pass of a soft light list on the GPU: device pointers (``colors`` stays a host array), d_counts = count planes of
+    width*height bytes, d_rgb = width*height*3 bytes, one kernel, asynchronous."""
+    colors = _colors(lights, colors)
+    _check(_lib.rtsh_combine_soft_light_list_device(ctx.handle, C.byref(constants), _ref(lights), _ptr_or_none(colors),
+                                                    C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
+                                                    C.c_void_p(d_counts), width, height, C.c_void_p(d_rgb), C.c_void_p(stream or 0)),
+           "rtsh_combine_soft_light_list_device")
 
 
 def write_ppm(path, rgb):

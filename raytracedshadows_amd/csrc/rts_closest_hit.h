@@ -132,18 +132,53 @@ RTS_HD float facingNdl(const CombineParams& c, const float* position4, V3 n) {
     return dot(n, L);
 }
 
+// combinePixel's pieces, shared with the light list rule below (combineListPixel).
+RTS_HD float clamp0(float x) { return x > 0 ? x : 0.0f; }                                        // GLSL's max(0.0, x): 0 for a NaN
+RTS_HD float viewNdv(const CombineParams& c, V3 n) { return dot(n, mul(c.viewDir, -1.0f)); }
+RTS_HD float combineDirect(float ndl, uint8_t mask, float samples) { return 1.25f * ndl * ((float)mask / samples); }   // frag:29
+RTS_HD float combineAmbient(float ndv) { return 0.15f + 0.05f * (1.0f - ndv); }                 // frag:30
+// UNORM8, saturated in float BEFORE the conversion: converting a float outside int's range (a normal of 1e7, +Inf, a NaN from
+// Inf * 0) is undefined on the host, and the host and the device then disagree.  A NaN is 0.
+RTS_HD uint8_t combineByte(float v) {
+    const float scaled = v * 255.0f + 0.5f;
+    return scaled >= 255.0f ? (uint8_t)255 : (scaled > 0.0f ? (uint8_t)(int)scaled : (uint8_t)0);
+}
+
 RTS_HD uint8_t combinePixel(const CombineParams& c, const float* position4, const float* normal4, uint8_t mask) {
     V3 n{ normal4[0], normal4[1], normal4[2] };
     if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) return 0;
-    float ndl = facingNdl(c, position4, n); ndl = ndl > 0 ? ndl : 0.0f;    // GLSL's max(0.0, x): 0 for a NaN
-    float ndv = dot(n, mul(c.viewDir, -1.0f)); ndv = ndv > 0 ? ndv : 0.0f;
-    const float direct = 1.25f * ndl * ((float)mask / c.samples);          // frag:29
-    const float ambient = 0.15f + 0.05f * (1.0f - ndv);                     // frag:30
-    const float v = direct + ambient;                                       // frag:32 (baseColor = 1)
-    // UNORM8, saturated in float BEFORE the conversion: converting a float outside int's range (a normal of 1e7, +Inf, a NaN from
-    // Inf * 0) is undefined on the host, and the host and the device then disagree.  A NaN is 0.
-    const float scaled = v * 255.0f + 0.5f;
-    return scaled >= 255.0f ? (uint8_t)255 : (scaled > 0.0f ? (uint8_t)(int)scaled : (uint8_t)0);
+    const float ndl = clamp0(facingNdl(c, position4, n));
+    const float ndv = clamp0(viewNdv(c, n));
+    const float direct = combineDirect(ndl, mask, c.samples);
+    const float ambient = combineAmbient(ndv);
+    return combineByte(direct + ambient);                                   // frag:32 (baseColor = 1)
+}
+
+// The combine pass of a LIGHT LIST (include/rts_scene.h, rtsh_combine_light_list / rtsh_combine_soft_light_list), one pixel: the
+// lights' direct terms, each times its colour, summed in list order from +0, plus ONE ambient term --
+//   rgb[c] = byte(((0 + direct_0 * color_0[c]) + direct_1 * color_1[c] + ...) + ambient),   direct_l = combinePixel's for light l alone
+// over its own byte (byteOf(l): the count plane's byte, or the mask's bit as 0 / 1).  A light whose bit of `bits` (the light map's byte)
+// is clear adds nothing and byteOf is not asked for it; a background pixel is 0 and nothing but the normal is looked at.  Every product
+// and every sum is rounded on its own (no contraction), in this order, on the host and on the device.
+struct CombineList { uint32_t count; CombineParams light[8]; float color[8][3]; };
+
+template <class ByteOf>
+RTS_HD void combineListPixel(const CombineList& f, const float* position4, const float* normal4, uint32_t bits, ByteOf byteOf,
+                             uint8_t* rgb3) {
+    V3 n{ normal4[0], normal4[1], normal4[2] };
+    if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) { rgb3[0] = rgb3[1] = rgb3[2] = 0; return; }
+    const float ambient = combineAmbient(clamp0(viewNdv(f.light[0], n)));     // (camera and view direction: the same in every entry)
+    float sum[3] = { 0.0f, 0.0f, 0.0f };
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        if (!((bits >> l) & 1u)) continue;
+        const float direct = combineDirect(clamp0(facingNdl(f.light[l], position4, n)), byteOf(l), f.light[l].samples);
+        for (int c = 0; c < 3; ++c) sum[c] = sum[c] + direct * f.color[l][c];
+    }
+    for (int c = 0; c < 3; ++c) rgb3[c] = combineByte(sum[c] + ambient);
 }
 
 // The facing mark (include/rts_scene.h, rtsh_facing_active): 0 where the shadow mask's byte cannot reach the image -- the

@@ -6,6 +6,9 @@
 #include "../../include/rts_scene.h"
 #include "rts_closest_hit.h"
 
+extern "C" const void* rts_ctx_device_bvh(rts_ctx* ctx);   // rts_api.cpp
+extern "C" int rts_ctx_device_ordinal(rts_ctx* ctx);
+
 namespace rts_harness {
 Camera makeCamera(const float eye[3], const float target[3], float fovy, uint32_t W, uint32_t H);
 
@@ -79,10 +82,43 @@ __global__ __launch_bounds__(256) void facingLightsKernel(FacingLights f, const 
     const float zero[4] = { 0.f, 0.f, 0.f, 0.f };
     lightsMap[i] = facingLightsPixel(f, positions ? positions + i * 4 : zero, normals + i * 4);
 }
-} // namespace rts_harness
 
-extern "C" const void* rts_ctx_device_bvh(rts_ctx* ctx);   // rts_api.cpp
-extern "C" int rts_ctx_device_ordinal(rts_ctx* ctx);
+int makeCombineList(const rts_constants* k, const rts_light_list* list, const float* colors, bool havePositions, CombineList* out);
+int makeCombineSoftList(const rts_constants* k, const rts_soft_light_list* list, const float* colors, bool havePositions, CombineList* out);
+
+// The combine pass of a light list (rts_closest_hit.h: combineListPixel), one pixel per lane like combineKernel, for every frame size
+// and every pointer.  (A form of four pixels per lane -- dword loads of the planes and the map, 16-byte loads of the normals, three
+// dword stores -- was measured 1.3 to 1.7 times slower at 4K and removed: EXPERIMENTS.md)  HARD: `planes` is the one mask plane of rts_trace_light_list*, light l in bit l; else the count
+// planes of rts_trace_soft_light_list*, plane l at planes + l * n.
+template <bool HARD>
+__global__ __launch_bounds__(256) void combineListKernel(CombineList f, const float* positions, const float* normals,
+                                                         const uint8_t* lightsMap, const uint8_t* planes, uint64_t n, uint8_t* rgb) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float zero[4] = { 0.f, 0.f, 0.f, 0.f };
+    const float* n4 = normals + i * 4;
+    const float nx = n4[0], ny = n4[1], nz = n4[2];
+    const float nrm[4] = { nx, ny, nz, 0.f };
+    const bool background = nx == 0.0f && ny == 0.0f && nz == 0.0f;        // (its map byte is not read)
+    const uint32_t bits = (lightsMap && !background) ? lightsMap[i] : 0xFFu;
+    uint8_t q[3];
+    combineListPixel(f, positions ? positions + i * 4 : zero, nrm, bits,
+                     [&](uint32_t l) { return HARD ? (uint8_t)((planes[i] >> l) & 1u) : planes[(uint64_t)l * n + i]; }, q);
+    rgb[i * 3] = q[0]; rgb[i * 3 + 1] = q[1]; rgb[i * 3 + 2] = q[2];
+}
+
+template <bool HARD>
+static int launchCombineList(rts_ctx* ctx, const CombineList& f, const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                             const uint8_t* d_planes, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream) {
+    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
+    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
+    const uint64_t n = (uint64_t)W * H;
+    hipLaunchKernelGGL(combineListKernel<HARD>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, d_positions,
+                       d_normals, d_lights_map, d_planes, n, d_rgb);
+    e = hipGetLastError();
+    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+}
+} // namespace rts_harness
 
 extern "C" int rtsh_combine_device(rts_ctx* ctx, const rts_constants* k, const rts_light* light, const float* d_positions,
                                    const float* d_normals, const uint8_t* d_mask, uint32_t W, uint32_t H, uint8_t* d_rgb,
@@ -144,4 +180,25 @@ extern "C" int rtsh_primary_gbuffer_device(rts_ctx* ctx, const float eye[3], con
                        d_positions, d_normals);
     e = hipGetLastError();
     return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+}
+
+// The combine pass of a light list on the GPU (include/rts_scene.h): one kernel, the list, the colours and the constants by value.
+extern "C" int rtsh_combine_light_list_device(rts_ctx* ctx, const rts_constants* k, const rts_light_list* list, const float* colors,
+                                              const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                              const uint8_t* d_mask, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream) {
+    if (!ctx || !k || !d_normals || !d_mask || !d_rgb || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    rts_harness::CombineList f;
+    const int s = rts_harness::makeCombineList(k, list, colors, d_positions != nullptr, &f);
+    if (s != RTS_OK) return s;
+    return rts_harness::launchCombineList<true>(ctx, f, d_positions, d_normals, d_lights_map, d_mask, W, H, d_rgb, stream);
+}
+
+extern "C" int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_constants* k, const rts_soft_light_list* list, const float* colors,
+                                                   const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                   const uint8_t* d_counts, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream) {
+    if (!ctx || !k || !d_normals || !d_counts || !d_rgb || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    rts_harness::CombineList f;
+    const int s = rts_harness::makeCombineSoftList(k, list, colors, d_positions != nullptr, &f);
+    if (s != RTS_OK) return s;
+    return rts_harness::launchCombineList<false>(ctx, f, d_positions, d_normals, d_lights_map, d_counts, W, H, d_rgb, stream);
 }

@@ -526,3 +526,89 @@ extern "C" int rtsh_facing_lights(const rts_constants* k, const rts_light_list* 
     for (size_t i = 0; i < (size_t)W * H; ++i) lights_map[i] = facingLightsPixel(f, positions ? positions + i * 4 : zero, normals + i * 4);
     return RTS_OK;
 }
+
+// ---- the combine pass of a light list (include/rts_scene.h; per-pixel rule in rts_closest_hit.h: combineListPixel) ----
+namespace rts_harness {
+// Shared by the host and device list combine passes: one CombineParams per light, as makeCombineParams condenses that light alone
+// (type, xyz and its sample count; an area light counts by its centre), and the colours -- count * 4 floats, .w ignored, NULL = white.
+static int makeCombineListOf(const rts_constants* k, uint32_t count, const uint32_t* types, const uint32_t* nsamples, const float (*xyz)[3],
+                             const float* colors, bool havePositions, CombineList* out) {
+    out->count = count;
+    for (uint32_t l = 0; l < count; ++l) {
+        rts_light one;
+        memset(&one, 0, sizeof(one));
+        one.type = types[l];
+        one.nsamples = nsamples[l];
+        for (int i = 0; i < 3; ++i) one.xyz[i] = xyz[l][i];
+        const int s = makeCombineParams(k, &one, havePositions, &out->light[l]);
+        if (s != RTS_OK) return s;
+        for (int c = 0; c < 3; ++c) out->color[l][c] = colors ? colors[l * 4 + c] : 1.0f;
+    }
+    for (uint32_t l = count; l < 8; ++l) {                               // (never looked at: defined bytes for the by-value copy)
+        out->light[l] = out->light[0];
+        for (int c = 0; c < 3; ++c) out->color[l][c] = 0.0f;
+    }
+    return RTS_OK;
+}
+
+int makeCombineList(const rts_constants* k, const rts_light_list* list, const float* colors, bool havePositions, CombineList* out) {
+    if (!k || !out || !rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
+    uint32_t types[8], ns[8];
+    float xyz[8][3];
+    for (uint32_t l = 0; l < list->count; ++l) {
+        types[l] = list->lights[l].type;
+        ns[l] = 1u;
+        for (int i = 0; i < 3; ++i) xyz[l][i] = list->lights[l].xyz[i];
+    }
+    return makeCombineListOf(k, list->count, types, ns, xyz, colors, havePositions, out);
+}
+
+int makeCombineSoftList(const rts_constants* k, const rts_soft_light_list* list, const float* colors, bool havePositions, CombineList* out) {
+    if (!k || !out || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    uint32_t types[8], ns[8];
+    float xyz[8][3];
+    for (uint32_t l = 0; l < list->count; ++l) {
+        types[l] = list->lights[l].type;
+        ns[l] = list->lights[l].nsamples;
+        for (int i = 0; i < 3; ++i) xyz[l][i] = list->lights[l].xyz[i];
+    }
+    return makeCombineListOf(k, list->count, types, ns, xyz, colors, havePositions, out);
+}
+
+namespace {
+template <bool HARD>
+void combineListFrame(const CombineList& f, const float* positions, const float* normals, const uint8_t* lights_map, const uint8_t* planes,
+                      size_t n, uint8_t* rgb) {
+    const float zero[4] = { 0, 0, 0, 0 };
+    for (size_t i = 0; i < n; ++i) {
+        const float* n4 = normals + i * 4;
+        const bool background = n4[0] == 0.0f && n4[1] == 0.0f && n4[2] == 0.0f;      // (its map byte is not read)
+        const uint32_t bits = (lights_map && !background) ? lights_map[i] : 0xFFu;
+        combineListPixel(f, positions ? positions + i * 4 : zero, n4, bits,
+                         [&](uint32_t l) { return HARD ? (uint8_t)((planes[i] >> l) & 1u) : planes[(size_t)l * n + i]; }, rgb + i * 3);
+    }
+}
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_combine_light_list(const rts_constants* k, const rts_light_list* list, const float* colors, const float* positions,
+                                       const float* normals, const uint8_t* lights_map, const uint8_t* mask, uint32_t W, uint32_t H,
+                                       uint8_t* rgb) {
+    if (!k || !normals || !mask || !rgb || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    CombineList f;
+    const int s = makeCombineList(k, list, colors, positions != nullptr, &f);
+    if (s != RTS_OK) return s;
+    combineListFrame<true>(f, positions, normals, lights_map, mask, (size_t)W * H, rgb);
+    return RTS_OK;
+}
+
+extern "C" int rtsh_combine_soft_light_list(const rts_constants* k, const rts_soft_light_list* list, const float* colors, const float* positions,
+                                            const float* normals, const uint8_t* lights_map, const uint8_t* counts, uint32_t W, uint32_t H,
+                                            uint8_t* rgb) {
+    if (!k || !normals || !counts || !rgb || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    CombineList f;
+    const int s = makeCombineSoftList(k, list, colors, positions != nullptr, &f);
+    if (s != RTS_OK) return s;
+    combineListFrame<false>(f, positions, normals, lights_map, counts, (size_t)W * H, rgb);
+    return RTS_OK;
+}

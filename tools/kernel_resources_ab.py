@@ -19,7 +19,7 @@ def remarks(path):
 def bodies(path):
     out = {}; cur = None; buf = []
     for line in open(path):
-        m = re.match(r"^(_ZN3rts\w+):\s", line)
+        m = re.match(r"^(_ZN\d+rts\w+):\s", line)
         if m and not line.startswith("."):
             cur = m.group(1); buf = []; continue
         if cur is not None:

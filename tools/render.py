@@ -1,15 +1,16 @@
 """Human-checkable output: OBJ scene -> BVH -> G-buffer (GPU) -> shadow mask (GPU) -> combine -> PPM.
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
-                           [--soft-list N [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]]
+                           [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]]
 
 --cull: the shadow pass traces only the pixels of the facing mark (rtsh_facing_active_device: not the background, not the surfaces
 that face away from the light) -- the same image, byte for byte.
 --adaptive K: the soft light (--spp, or a soft config) is traced by rts_trace_shadow_mask_adaptive* with a probe of K samples: the
 remaining samples only where the probe disagrees; --refined writes the plane of refined pixels (white = the full count was taken).
 --soft-list N: the frame is lit by N (1..8) area lights on a ring around the scene's light, each of --spp samples (default 4; N * spp
-<= 48), traced in ONE rts_trace_soft_light_list_device dispatch through the facing map; the image is the mean of the lights' own
-combine passes, each over its count plane.  With --adaptive K the list is traced by rts_trace_soft_light_list_adaptive_device with a
+<= 48), traced in ONE rts_trace_soft_light_list_device dispatch through the facing map and lit in ONE
+rtsh_combine_soft_light_list_device pass over the count planes, every light of colour 1/N (--colors r,g,b[;r,g,b...] gives each light its
+own: one triple for all of them, or N); the RGB frame is read back once.  With --adaptive K the list is traced by rts_trace_soft_light_list_adaptive_device with a
 probe of K samples for every light (1 <= K < spp); --refined then writes the list's refined plane as a grey-scale image, a pixel's
 value the share of the lights that took their full count there.  With --distance FILE.ppm (and no --adaptive) the list is traced by
 rts_trace_soft_light_list_distance_device, which gives every light's nearest blocker over its samples beside its count plane; the file
@@ -28,9 +29,25 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, distance_out=""):
+def parse_colors(text, count):
+    """--colors: `count` rows of r,g,b (one triple stands for every light); empty: 1/count each, the mean of the lights."""
+    if not text:
+        return np.full((count, 3), 1.0 / count, np.float32)
+    try:
+        rows = [[float(v) for v in triple.split(",")] for triple in text.split(";")]
+    except ValueError:
+        rows = []
+    if len(rows) == 1:
+        rows = rows * count
+    if len(rows) != count or any(len(r) != 3 for r in rows):
+        sys.exit(f"render: --colors takes one r,g,b triple, or {count} of them separated by ';'")
+    return np.asarray(rows, np.float32)
+
+
+def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, distance_out="", colors=""):
     """A frame lit by `count` area lights of `spp` samples: one list dispatch (adaptive with `probe` != 0; with `table` every light
-    takes its samples from a per-pixel jitter table of `table` entries), then one combine pass per light over its plane."""
+    takes its samples from a per-pixel jitter table of `table` entries), then ONE combine pass over all the count planes and one
+    read-back of the RGB frame."""
     from raytracedshadows_amd import api, scenes
     from soft_list_ab import entries
     if not 1 <= count <= 8 or count * max(spp, 1) > 48:
@@ -41,6 +58,7 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
         sys.exit("render: --soft-list N --distance FILE.ppm does not go with --adaptive (the distance list has no probes)")
     if table and (not probe or table < spp or (count - 1) * spp + table > 48):
         sys.exit("render: --table T goes with --soft-list N --adaptive K and takes spp <= T <= 48 - (N - 1) * spp")
+    colors = parse_colors(colors, count)
     lights = api.SoftLightList.make(entries(wl.scene, count, spp), scenes.jitter_offsets(48, 1.0, 19))
     d_pos, d_nrm, d_map = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
     d_counts, d_rgb = ctx.malloc(count * W * H), ctx.malloc(W * H * 3)
@@ -59,16 +77,14 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
     ctx.synchronize()
     print(f"G-buffer + facing map + {count} lights x {spp} samples{f', probe {probe},' if probe else ''} in one dispatch: {(time.time() - t0) * 1e3:.2f} ms (first call, incl. "
           f"launch); {ctx.last_kernel_name()}")
-    total, rgb = np.zeros((H, W, 3), np.float32), np.zeros((H, W, 3), np.uint8)
-    for l in range(count):
-        api.combine_device(ctx, wl.constants, lights.light(l), d_pos, d_nrm, d_counts + l * W * H, W, H, d_rgb)
-        ctx.synchronize()
-        ctx.d2h(rgb, d_rgb)
-        total += rgb
+    rgb = np.zeros((H, W, 3), np.uint8)
+    api.combine_soft_light_list_device(ctx, wl.constants, lights, d_pos, d_nrm, d_counts, W, H, d_rgb, d_lights_map=d_map, colors=colors)
+    ctx.synchronize()
+    ctx.d2h(rgb, d_rgb)                                  # the one read-back of the image
     planes = np.zeros((count, H, W), np.uint8)
-    ctx.d2h(planes, d_counts)
+    ctx.d2h(planes, d_counts)                            # (for the statistics printed below only)
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    api.write_ppm(out, np.clip(total / count + 0.5, 0, 255).astype(np.uint8))
+    api.write_ppm(out, rgb)
     print(f"wrote {out}: {W}x{H}, lit fraction per light {[round(float((planes[l] > 0).mean()), 3) for l in range(count)]}")
     if d_dist:
         dist, marks = np.zeros((count, H, W), np.float32), np.zeros((H, W), np.uint8)
@@ -110,6 +126,8 @@ def main():
                     help="with --soft-list N --adaptive K: a per-pixel jitter table of T entries per light (spp <= T), its start hashed per pixel")
     ap.add_argument("--soft-list", type=int, default=0, metavar="N",
                     help="light the frame by N area lights of --spp samples each, traced in one soft light list dispatch")
+    ap.add_argument("--colors", default="", metavar="r,g,b[;r,g,b...]",
+                    help="with --soft-list N: the lights' colours, one triple for all of them or N separated by ';' (default 1/N each)")
     args = ap.parse_args()
     from raytracedshadows_amd import api, workloads
     scene, W, H, light, spp = workloads.CONFIGS[args.config]
@@ -119,7 +137,7 @@ def main():
     with api.ShadowContext(0) as ctx:
         ctx.set_bvh(wl.packed)
         if args.soft_list:
-            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance)
+            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance, args.colors)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
         t0 = time.time()
         api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
