@@ -194,6 +194,80 @@ int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_constants* const
                                         const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
                                         const uint8_t* d_counts, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream);
 
+/* THE FILTER OF A LIGHT LIST'S PLANES: from the count planes of a soft light list (or the mask of a hard one) to one FLOAT VISIBILITY
+ * plane per light -- a spatial, edge-aware, optionally distance-guided filter: the stage between a trace of few samples (five grey
+ * levels for four samples; the noise of a jitter table) and the image.  The result is a function of the inputs alone: every sum
+ * across pixels is an INTEGER sum, floats appear in per-tap comparisons and in one division per light, and the library is built
+ * without contraction -- so no order of the taps, no tiling and no option can change a bit, and the host form checks the device form
+ * bit for bit.  All buffers are whole frames of W x H.
+ *   typedef struct rtsh_filter_params: radius R (0 .. RTSH_FILTER_MAX_RADIUS: the window is (2R+1) x (2R+1) pixels), normal_cos_min,
+ *   plane_eps (world units), spread[l] (per light, used with distances only), reserved_ (ignored).
+ * For pixel p = (x, y) and light l < count:  n_l = max(1, nsamples_l) (1 for a hard list);  c_l(q) = the byte of plane l at q
+ * (counts[l * W * H + q]; bit l of mask[q] as 0 or 1 for a hard list), unclamped, as the combine pass reads it;  on(q, l) = lights_map
+ * == NULL or bit l of lights_map[q] is set;  bg(q) = normals[q].xyz all zero;  N_q = normals[q].xyz, P_q = positions[q].xyz.
+ *   INACTIVE: where bg(p) or not on(p, l), visibility[l * W * H + p] = +0.0f and nothing else of p is looked at for that light.
+ *   TAPS: otherwise, over the taps q = (x + dx, y + dy) INSIDE THE FRAME with |dx|, |dy| <= R, each of the integer tent weight
+ *     w = (R + 1 - |dx|) * (R + 1 - |dy|):  the centre tap q == p is always accepted; another tap is accepted when geom(p, q) and
+ *     lit(p, q, l) both hold; every comparison is written so that a NaN rejects the tap --
+ *       geom(p, q): not bg(q), and (Np.x*Nq.x + Np.y*Nq.y) + Np.z*Nq.z >= normal_cos_min, and fabsf(h) <= plane_eps, where
+ *                   D = P_q - P_p (three subtractions) and h = (Np.x*D.x + Np.y*D.y) + Np.z*D.z.  It does not depend on the light;
+ *                   the position of a background tap is never looked at.
+ *       lit(p, q, l), distances == NULL: on(q, l).
+ *       lit(p, q, l), with distances:    on(q, l), and either m is +Inf (0x7F800000) or (D.x*D.x + D.y*D.y) + D.z*D.z <=
+ *                   (spread_l * m) * (spread_l * m), m = the smaller of the BIT PATTERNS of distances[l][p] and distances[l][q] taken
+ *                   as unsigned 32-bit integers (for the traces' planes, which hold +0 .. +Inf: the smaller distance), read as a float.
+ *                   This is the contact-hardening guide: two pixels share their counts only across less than the penumbra width at
+ *                   the nearer blocker, spread_l times the ray parameter -- world distance for a directional light, a fraction of
+ *                   the segment for a point light.  The CALLER folds the light's size and range into spread_l.
+ *   QUOTIENT: num = sum of w * c_l(q), den = sum of w * n_l over the accepted taps, both unsigned 32-bit integers below 2^24
+ *     (255 * 81 * 289);  visibility[l * W * H + p] = (float)num / (float)den, one rounded division.
+ * ANCHORS: (1) R = 0, or thresholds that accept no neighbour: (float)c / (float)n_l, the very quotient the list combine pass forms
+ * (the fraction reduces: the weight cancels exactly).  (2) Where every accepted tap of a pixel carries the same byte c, the result is
+ * (float)c / (float)n_l: the device form skips the walk for a light whose bytes are all equal over a block's window.
+ *   * distances: NULL, or the planes of rts_trace_soft_light_list_distance* (soft form only).  lights_map may be NULL.  positions is
+ *     always required.  visibility: count * W * H floats; planes of any buffer from `count` up are never touched.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: what rtsh_combine_*_light_list* refuse of a list; NULL params, positions,
+ *     normals, mask / counts or visibility; radius > RTSH_FILTER_MAX_RADIUS; a normal_cos_min or plane_eps that is not finite; with
+ *     distances, a spread_l (l < count) that is negative or not finite; W == 0 or H == 0; a NULL ctx.
+ *   * host forms: multi-threaded (threads: 0 = all host threads).  Device forms: DEVICE buffers, asynchronous on `stream`, allocate
+ *     nothing and read nothing back; under graph capture each adds ONE kernel node, list and parameters by value (params is read
+ *     during the call).  They need no BVH and no alignment of any buffer beyond its element type's.
+ *   * OUT OF SCOPE: row ranges and stripes (a stripe would need a halo of R rows from its neighbours), a temporal filter, variance
+ *     guidance. */
+enum { RTSH_FILTER_MAX_RADIUS = 8 };
+typedef struct rtsh_filter_params {
+    uint32_t radius;          /* R, 0 .. RTSH_FILTER_MAX_RADIUS (8): the window is (2R+1) x (2R+1) pixels */
+    float    normal_cos_min;  /* a tap needs N_p . N_q >= this */
+    float    plane_eps;       /* ... and |N_p . (P_q - P_p)| <= this (world units) */
+    float    spread[RTS_MAX_LIST_LIGHTS]; /* per light, used with distances only: finite, >= 0 */
+    uint32_t reserved_[5];    /* ignored */
+} rtsh_filter_params;                                                              /* 64 bytes */
+int rtsh_filter_light_list(const rts_light_list* list, const rtsh_filter_params* params, const float* positions, const float* normals,
+                           const uint8_t* lights_map, const uint8_t* mask, uint32_t W, uint32_t H, float* visibility, int threads);
+int rtsh_filter_soft_light_list(const rts_soft_light_list* list, const rtsh_filter_params* params, const float* positions,
+                                const float* normals, const uint8_t* lights_map, const uint8_t* counts, const float* distances,
+                                uint32_t W, uint32_t H, float* visibility, int threads);
+int rtsh_filter_light_list_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_filter_params* params, const float* d_positions,
+                                  const float* d_normals, const uint8_t* d_lights_map, const uint8_t* d_mask, uint32_t W, uint32_t H,
+                                  float* d_visibility, void* stream);
+int rtsh_filter_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list, const rtsh_filter_params* params,
+                                       const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                       const uint8_t* d_counts, const float* d_distances, uint32_t W, uint32_t H, float* d_visibility,
+                                       void* stream);
+
+/* THE VISIBILITY COMBINE: the combine pass of a light list (above) with visibility[l * W * H + p] -- a filter's plane -- in place of
+ * (float)byte_l / samples_l:  direct = 1.25f * max0(N.L_l) * visibility_l;  everything else, the order of the sum and every refusal
+ * included, is rtsh_combine_light_list's (`visibility` in the place of `mask`).  Any float is allowed in a plane; a light whose map
+ * bit is clear and a background pixel do not look at theirs.  ANCHOR: over the planes of an R = 0 filter it gives
+ * rtsh_combine_soft_light_list's bytes (rtsh_combine_light_list's for a hard list), byte for byte.  `list` gives types and positions;
+ * for a soft list pass the rts_light_list of the same types and positions. */
+int rtsh_combine_visibility_list(const rts_constants* constants, const rts_light_list* list, const float* colors, const float* positions,
+                                 const float* normals, const uint8_t* lights_map, const float* visibility, uint32_t W, uint32_t H,
+                                 uint8_t* rgb);
+int rtsh_combine_visibility_list_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* colors,
+                                        const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                        const float* d_visibility, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream);
+
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.
  * Call with vertices == NULL to query *vertex_count (3 per triangle) first.  Returns RTS_OK,

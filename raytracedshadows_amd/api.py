@@ -188,6 +188,26 @@ class SoftLightList(C.Structure):
         return LightList.make([(self.lights[l].type, list(self.lights[l].xyz)) for l in range(self.count)])
 
 
+class FilterParams(C.Structure):
+    """``rtsh_filter_params``: the window radius (0..8), the two geometry thresholds and, for the distance guide, one spread per light."""
+    _fields_ = [("radius", C.c_uint32), ("normal_cos_min", C.c_float), ("plane_eps", C.c_float), ("spread", C.c_float * 8),
+                ("reserved_", C.c_uint32 * 5)]
+    MAX_RADIUS = 8
+
+    @classmethod
+    def make(cls, radius, normal_cos_min=0.9, plane_eps=0.05, spread=None):
+        """spread: None (0 for every light), one float for all lights, or up to 8 floats."""
+        p = cls()
+        p.radius, p.normal_cos_min, p.plane_eps = radius, np.float32(normal_cos_min), np.float32(plane_eps)
+        if spread is not None:
+            values = np.broadcast_to(np.asarray(spread, np.float32), (8,)) if np.ndim(spread) == 0 else np.asarray(spread, np.float32)
+            if values.ndim != 1 or values.shape[0] > 8:
+                raise RtsError(1, "FilterParams.make: spread is one float or at most 8")
+            for l in range(values.shape[0]):
+                p.spread[l] = values[l]
+        return p
+
+
 #: numpy view of ``struct BVHNode`` (BVHBuilder.h:8-20)
 BVHNode_dtype = np.dtype([("bboxMin", np.float32, 3), ("prim", np.uint32),
                           ("bboxMax", np.float32, 3), ("next", np.uint32)])
@@ -416,6 +436,18 @@ _sig("rtsh_combine_soft_light_list", C.c_int, C.POINTER(RayTracingConstants), C.
 _sig("rtsh_combine_light_list_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_combine_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_filter_light_list", C.c_int, C.POINTER(LightList), C.POINTER(FilterParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_filter_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(FilterParams), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_filter_light_list_device", C.c_int, C.c_void_p, C.POINTER(LightList), C.POINTER(FilterParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_filter_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(FilterParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_combine_visibility_list", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rtsh_combine_visibility_list_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_facing_active", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
      C.c_void_p)
@@ -1437,6 +1469,92 @@ def combine_soft_light_list_device(ctx, constants, lights, d_positions, d_normal
                                                     C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
                                                     C.c_void_p(d_counts), width, height, C.c_void_p(d_rgb), C.c_void_p(stream or 0)),
            "rtsh_combine_soft_light_list_device")
+
+
+def _filter_list(soft, lights, params, positions, normals, planes, lights_map, distances, threads):
+    name = "rtsh_filter_soft_light_list" if soft else "rtsh_filter_light_list"
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    planes = np.ascontiguousarray(planes, np.uint8)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    distances = np.ascontiguousarray(distances, np.float32) if distances is not None else None
+    if planes.size < (count if soft else 1) * H * W or (lights_map is not None and lights_map.size != H * W) or \
+            (positions is not None and positions.size != H * W * 4) or (distances is not None and distances.size < count * H * W):
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    visibility = np.zeros((count, H, W), np.float32)
+    if soft:
+        status = _lib.rtsh_filter_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals), _ptr_or_none(lights_map),
+                                                  _ptr(planes), _ptr_or_none(distances), W, H, _ptr(visibility), threads)
+    else:
+        status = _lib.rtsh_filter_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals), _ptr_or_none(lights_map),
+                                             _ptr(planes), W, H, _ptr(visibility), threads)
+    _check(status, name)
+    return visibility
+
+
+def filter_light_list(light_list, params, positions, normals, mask, lights_map=None, threads=0):
+    """The filter of a hard light list's mask on the host (rtsh_filter_light_list): ``float32[count, H, W]``, plane ``l`` the
+    edge-aware tent average of bit ``l`` of ``mask`` over the window of ``params`` (a ``FilterParams``)."""
+    return _filter_list(False, light_list, params, positions, normals, mask, lights_map, None, threads)
+
+
+def filter_soft_light_list(lights, params, positions, normals, counts, lights_map=None, distances=None, threads=0):
+    """The filter of a soft light list's count planes on the host (rtsh_filter_soft_light_list): ``float32[count, H, W]`` visibility.
+    ``distances``: None, or the ``float32[>= count, H, W]`` planes of a soft light list distance trace (the contact-hardening guide,
+    with ``params.spread``)."""
+    return _filter_list(True, lights, params, positions, normals, counts, lights_map, distances, threads)
+
+
+def filter_light_list_device(ctx, light_list, params, d_positions, d_normals, d_mask, width, height, d_visibility, d_lights_map=None,
+                             stream=None):
+    """The filter of a hard light list's mask on the GPU: device pointers, d_visibility = count planes of width*height floats, one
+    kernel, asynchronous."""
+    _check(_lib.rtsh_filter_light_list_device(ctx.handle, _ref(light_list), _ref(params), C.c_void_p(d_positions or 0), C.c_void_p(d_normals),
+                                              C.c_void_p(d_lights_map or 0), C.c_void_p(d_mask), width, height, C.c_void_p(d_visibility),
+                                              C.c_void_p(stream or 0)), "rtsh_filter_light_list_device")
+
+
+def filter_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_counts, width, height, d_visibility, d_lights_map=None,
+                                  d_distances=None, stream=None):
+    """The filter of a soft light list's count planes on the GPU: device pointers (d_distances: None, or the distance planes), one
+    kernel, asynchronous."""
+    _check(_lib.rtsh_filter_soft_light_list_device(ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions or 0), C.c_void_p(d_normals),
+                                                   C.c_void_p(d_lights_map or 0), C.c_void_p(d_counts), C.c_void_p(d_distances or 0), width,
+                                                   height, C.c_void_p(d_visibility), C.c_void_p(stream or 0)),
+           "rtsh_filter_soft_light_list_device")
+
+
+def combine_visibility_list(constants, light_list, positions, normals, visibility, lights_map=None, colors=None):
+    """The visibility combine on the host (rtsh_combine_visibility_list): ``uint8[H, W, 3]`` -- the list combine pass with plane ``l``
+    of ``visibility`` (``float32[>= count, H, W]``, a filter's output) as light ``l``'s shadow factor.  ``light_list``: a ``LightList``
+    (for a soft list: its ``hard_list()``)."""
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    visibility = np.ascontiguousarray(visibility, np.float32)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    if visibility.size < (light_list.count if light_list is not None and light_list.count <= 8 else 1) * H * W or \
+            (lights_map is not None and lights_map.size != H * W) or (positions is not None and positions.size != H * W * 4):
+        raise RtsError(1, "rtsh_combine_visibility_list: a buffer does not fit the frame of the normals")
+    colors = _colors(light_list, colors)
+    rgb = np.zeros((H, W, 3), np.uint8)
+    _check(_lib.rtsh_combine_visibility_list(C.byref(constants), _ref(light_list), _ptr_or_none(colors), _ptr_or_none(positions),
+                                             _ptr(normals), _ptr_or_none(lights_map), _ptr(visibility), W, H, _ptr(rgb)),
+           "rtsh_combine_visibility_list")
+    return rgb
+
+
+def combine_visibility_list_device(ctx, constants, light_list, d_positions, d_normals, d_visibility, width, height, d_rgb,
+                                   d_lights_map=None, colors=None, stream=None):
+    """The visibility combine on the GPU: device pointers (``colors`` stays a host array), d_visibility = count planes of width*height
+    floats, d_rgb = width*height*3 bytes, one kernel, asynchronous."""
+    colors = _colors(light_list, colors)
+    _check(_lib.rtsh_combine_visibility_list_device(ctx.handle, C.byref(constants), _ref(light_list), _ptr_or_none(colors),
+                                                    C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
+                                                    C.c_void_p(d_visibility), width, height, C.c_void_p(d_rgb), C.c_void_p(stream or 0)),
+           "rtsh_combine_visibility_list_device")
 
 
 def write_ppm(path, rgb):

@@ -181,6 +181,108 @@ RTS_HD void combineListPixel(const CombineList& f, const float* position4, const
     for (int c = 0; c < 3; ++c) rgb3[c] = combineByte(sum[c] + ambient);
 }
 
+// The VISIBILITY combine (include/rts_scene.h, rtsh_combine_visibility_list): combineListPixel with a float visibility per light --
+// what the filter below writes -- in place of (float)byte / samples; everything else, the order of the sum included, is the same, so
+// over the quotients of an R = 0 filter it gives combineListPixel's bytes.
+template <class VisibilityOf>
+RTS_HD void combineVisibilityPixel(const CombineList& f, const float* position4, const float* normal4, uint32_t bits,
+                                   VisibilityOf visibilityOf, uint8_t* rgb3) {
+    V3 n{ normal4[0], normal4[1], normal4[2] };
+    if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) { rgb3[0] = rgb3[1] = rgb3[2] = 0; return; }
+    const float ambient = combineAmbient(clamp0(viewNdv(f.light[0], n)));
+    float sum[3] = { 0.0f, 0.0f, 0.0f };
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        if (!((bits >> l) & 1u)) continue;
+        const float direct = 1.25f * clamp0(facingNdl(f.light[l], position4, n)) * visibilityOf(l);
+        for (int c = 0; c < 3; ++c) sum[c] = sum[c] + direct * f.color[l][c];
+    }
+    for (int c = 0; c < 3; ++c) rgb3[c] = combineByte(sum[c] + ambient);
+}
+
+// The FILTER of a light list's planes (include/rts_scene.h, rtsh_filter_light_list / rtsh_filter_soft_light_list), one pixel: a
+// (2R+1) x (2R+1) window of integer tent weights over the taps that pass the geometry test (normal and plane distance, once per
+// tap) and, per light, the map bit and -- with distances -- the spread test.  num and den are integer sums (< 2^24), so no order of
+// the taps can change them; the floats are per-tap comparisons, each written so that a NaN rejects, and one division per light.
+// `Texels` gives the frame by pixel coordinates (the host twin reads the buffers, the kernel its LDS tile):
+//   V3 normal(x, y), V3 position(x, y); uint32_t bits(x, y) (the map byte, 0xFF without a map); uint32_t byte(x, y, l) (the count
+//   byte, or the mask's bit as 0 / 1); uint32_t distance(x, y, l) (the bit pattern; DIST only).
+// `walk`: the lights whose taps are walked.  A light outside it takes the centre tap alone -- (float)c / (float)n, which is also what
+// the walk gives wherever every accepted tap carries the centre's byte (the weights cancel, the quotient is rounded once): the kernel
+// clears a light's bit for a block whose staged window holds one byte for that light.  The host twin walks every light.
+struct FilterList { uint32_t count, radius; float normalCosMin, planeEps; uint32_t samples[8]; float spread[8]; };
+
+RTS_HD bool isBackground(V3 n) { return n.x == 0.0f && n.y == 0.0f && n.z == 0.0f; }
+
+template <bool DIST, class Texels>
+RTS_HD void filterListPixel(const FilterList& f, const Texels& t, int x, int y, int W, int H, uint32_t walk, float* visibility8) {
+    const V3 np = t.normal(x, y);
+    const uint32_t onp = isBackground(np) ? 0u : (t.bits(x, y) & ((1u << f.count) - 1u));
+    const int R = (int)f.radius;
+    const uint32_t w0 = (uint32_t)((R + 1) * (R + 1));
+    uint32_t num[8], den[8], dp[8];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        num[l] = den[l] = dp[l] = 0u;
+        if (l >= f.count || !((onp >> l) & 1u)) continue;
+        num[l] = w0 * t.byte(x, y, l);                                            // the centre tap: always accepted
+        den[l] = w0 * f.samples[l];
+        if (DIST) dp[l] = t.distance(x, y, l);
+    }
+    const uint32_t todo = onp & walk;
+    if (todo != 0u && R > 0) {
+        const V3 pp = t.position(x, y);
+        for (int dy = -R; dy <= R; ++dy) {
+            const int qy = y + dy;
+            if (qy < 0 || qy >= H) continue;
+            const uint32_t wy = (uint32_t)(R + 1 - (dy < 0 ? -dy : dy));
+            for (int dx = -R; dx <= R; ++dx) {
+                const int qx = x + dx;
+                if (qx < 0 || qx >= W || (dx == 0 && dy == 0)) continue;
+                const V3 nq = t.normal(qx, qy);
+                if (isBackground(nq)) continue;
+                if (!((np.x * nq.x + np.y * nq.y) + np.z * nq.z >= f.normalCosMin)) continue;
+                const V3 d = sub(t.position(qx, qy), pp);
+                const float h = (np.x * d.x + np.y * d.y) + np.z * d.z;
+                if (!(__builtin_fabsf(h) <= f.planeEps)) continue;
+                const uint32_t acc = t.bits(qx, qy) & todo;
+                if (acc == 0u) continue;
+                const float d2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
+                const uint32_t w = wy * (uint32_t)(R + 1 - (dx < 0 ? -dx : dx));
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+                for (uint32_t l = 0; l < 8; ++l) {
+                    if (l >= f.count) break;
+                    if (!((acc >> l) & 1u)) continue;
+                    if (DIST) {
+                        const uint32_t dq = t.distance(qx, qy, l);
+                        const uint32_t m = dq < dp[l] ? dq : dp[l];
+                        if (m != 0x7F800000u) {
+                            const float sm = f.spread[l] * asFloat(m);
+                            if (!(d2 <= sm * sm)) continue;
+                        }
+                    }
+                    num[l] += w * t.byte(qx, qy, l);
+                    den[l] += w * f.samples[l];
+                }
+            }
+        }
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        visibility8[l] = ((onp >> l) & 1u) ? (float)num[l] / (float)den[l] : 0.0f;
+    }
+}
+
 // The facing mark (include/rts_scene.h, rtsh_facing_active): 0 where the shadow mask's byte cannot reach the image -- the
 // background (combinePixel leaves the pixel 0) and N.L <= 0 (direct = 1.25 * 0 * mask: either zero) --, 1 everywhere else.
 // `!(ndl > 0)` would cull a NaN; `ndl <= 0` is false for one, so a NaN is traced.

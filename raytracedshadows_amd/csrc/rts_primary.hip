@@ -202,3 +202,5 @@ extern "C" int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_const
     if (s != RTS_OK) return s;
     return rts_harness::launchCombineList<false>(ctx, f, d_positions, d_normals, d_lights_map, d_counts, W, H, d_rgb, stream);
 }
+
+#include "rts_filter.inc"   // the filter of a light list's planes and the visibility combine

@@ -612,3 +612,107 @@ extern "C" int rtsh_combine_soft_light_list(const rts_constants* k, const rts_so
     combineListFrame<false>(f, positions, normals, lights_map, counts, (size_t)W * H, rgb);
     return RTS_OK;
 }
+
+// ---- the filter of a light list's planes and the visibility combine (include/rts_scene.h; per-pixel rules in rts_closest_hit.h:
+// filterListPixel, combineVisibilityPixel) ----
+namespace rts_harness {
+// Shared by the host and device filters: the refusals of the parameters and the condensed form the per-pixel rule reads.
+int makeFilterList(uint32_t count, const uint32_t* nsamples, const rtsh_filter_params* p, bool withDistances, FilterList* out) {
+    if (!p || !out || p->radius > (uint32_t)RTSH_FILTER_MAX_RADIUS || !std::isfinite(p->normal_cos_min) || !std::isfinite(p->plane_eps))
+        return RTS_ERR_INVALID_ARG;
+    out->count = count;
+    out->radius = p->radius;
+    out->normalCosMin = p->normal_cos_min;
+    out->planeEps = p->plane_eps;
+    for (uint32_t l = 0; l < 8; ++l) {
+        const bool used = l < count;
+        if (used && withDistances && !(std::isfinite(p->spread[l]) && p->spread[l] >= 0.0f)) return RTS_ERR_INVALID_ARG;
+        out->samples[l] = used && nsamples && nsamples[l] > 1u ? nsamples[l] : 1u;
+        out->spread[l] = used && withDistances ? p->spread[l] : 0.0f;              // (defined bytes for the by-value copy)
+    }
+    return RTS_OK;
+}
+
+int makeFilterHardList(const rts_light_list* list, const rtsh_filter_params* p, FilterList* out) {
+    if (!rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
+    return makeFilterList(list->count, nullptr, p, false, out);
+}
+
+int makeFilterSoftList(const rts_soft_light_list* list, const rtsh_filter_params* p, bool withDistances, FilterList* out) {
+    if (!rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    uint32_t ns[8];
+    for (uint32_t l = 0; l < list->count; ++l) ns[l] = list->lights[l].nsamples;
+    return makeFilterList(list->count, ns, p, withDistances, out);
+}
+
+namespace {
+// The frame as filterListPixel reads it on the host: straight from the buffers.
+template <bool HARD>
+struct FrameTexels {
+    const float *positions, *normals, *distances;
+    const uint8_t *map, *planes;
+    size_t W, n;
+    size_t at(int x, int y) const { return (size_t)y * W + (size_t)x; }
+    V3 normal(int x, int y) const { const float* v = normals + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
+    V3 position(int x, int y) const { const float* v = positions + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
+    uint32_t bits(int x, int y) const { return map ? map[at(x, y)] : 0xFFu; }
+    uint32_t byte(int x, int y, uint32_t l) const { return HARD ? (planes[at(x, y)] >> l) & 1u : planes[(size_t)l * n + at(x, y)]; }
+    uint32_t distance(int x, int y, uint32_t l) const { uint32_t u; memcpy(&u, distances + (size_t)l * n + at(x, y), 4); return u; }
+};
+
+template <bool HARD>
+void filterListFrame(const FilterList& f, const float* positions, const float* normals, const uint8_t* lights_map, const uint8_t* planes,
+                     const float* distances, uint32_t W, uint32_t H, float* visibility, int threads) {
+    const size_t n = (size_t)W * H;
+    const FrameTexels<HARD> t{ positions, normals, distances, lights_map, planes, W, n };
+    parallelFor(n, 256, threads, [&](size_t i) {
+        float v[8];
+        const int x = (int)(i % W), y = (int)(i / W);
+        if (distances) filterListPixel<true>(f, t, x, y, (int)W, (int)H, 0xFFu, v);
+        else filterListPixel<false>(f, t, x, y, (int)W, (int)H, 0xFFu, v);
+        for (uint32_t l = 0; l < f.count; ++l) visibility[(size_t)l * n + i] = v[l];
+    });
+}
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_filter_light_list(const rts_light_list* list, const rtsh_filter_params* params, const float* positions,
+                                      const float* normals, const uint8_t* lights_map, const uint8_t* mask, uint32_t W, uint32_t H,
+                                      float* visibility, int threads) {
+    if (!positions || !normals || !mask || !visibility || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    FilterList f;
+    const int s = makeFilterHardList(list, params, &f);
+    if (s != RTS_OK) return s;
+    filterListFrame<true>(f, positions, normals, lights_map, mask, nullptr, W, H, visibility, threads);
+    return RTS_OK;
+}
+
+extern "C" int rtsh_filter_soft_light_list(const rts_soft_light_list* list, const rtsh_filter_params* params, const float* positions,
+                                           const float* normals, const uint8_t* lights_map, const uint8_t* counts, const float* distances,
+                                           uint32_t W, uint32_t H, float* visibility, int threads) {
+    if (!positions || !normals || !counts || !visibility || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    FilterList f;
+    const int s = makeFilterSoftList(list, params, distances != nullptr, &f);
+    if (s != RTS_OK) return s;
+    filterListFrame<false>(f, positions, normals, lights_map, counts, distances, W, H, visibility, threads);
+    return RTS_OK;
+}
+
+extern "C" int rtsh_combine_visibility_list(const rts_constants* k, const rts_light_list* list, const float* colors, const float* positions,
+                                            const float* normals, const uint8_t* lights_map, const float* visibility, uint32_t W, uint32_t H,
+                                            uint8_t* rgb) {
+    if (!k || !normals || !visibility || !rgb || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    CombineList f;
+    const int s = makeCombineList(k, list, colors, positions != nullptr, &f);
+    if (s != RTS_OK) return s;
+    const float zero[4] = { 0, 0, 0, 0 };
+    const size_t n = (size_t)W * H;
+    for (size_t i = 0; i < n; ++i) {
+        const float* n4 = normals + i * 4;
+        const bool background = n4[0] == 0.0f && n4[1] == 0.0f && n4[2] == 0.0f;          // (its map byte is not read)
+        const uint32_t bits = (lights_map && !background) ? lights_map[i] : 0xFFu;
+        combineVisibilityPixel(f, positions ? positions + i * 4 : zero, n4, bits, [&](uint32_t l) { return visibility[(size_t)l * n + i]; },
+                               rgb + i * 3);
+    }
+    return RTS_OK;
+}

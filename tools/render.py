@@ -1,8 +1,12 @@
 """Human-checkable output: OBJ scene -> BVH -> G-buffer (GPU) -> shadow mask (GPU) -> combine -> PPM.
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
-                           [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]]
+                           [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]
+                                          [--filter R [--spread S] [--plane-eps E] [--normal-cos C]]]
 
+--filter R (with --soft-list N): between trace and image the count planes go through rtsh_filter_soft_light_list_device -- an edge-aware
+tent window of (2R+1)^2 pixels that stops at normal and depth edges (--normal-cos, --plane-eps) -- and the frame is lit from the float
+visibility planes by rtsh_combine_visibility_list_device; with --distance the distance planes guide the filter (--spread).
 --cull: the shadow pass traces only the pixels of the facing mark (rtsh_facing_active_device: not the background, not the surfaces
 that face away from the light) -- the same image, byte for byte.
 --adaptive K: the soft light (--spp, or a soft config) is traced by rts_trace_shadow_mask_adaptive* with a probe of K samples: the
@@ -44,7 +48,7 @@ def parse_colors(text, count):
     return np.asarray(rows, np.float32)
 
 
-def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, distance_out="", colors=""):
+def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, distance_out="", colors="", filt=None):
     """A frame lit by `count` area lights of `spp` samples: one list dispatch (adaptive with `probe` != 0; with `table` every light
     takes its samples from a per-pixel jitter table of `table` entries), then ONE combine pass over all the count planes and one
     read-back of the RGB frame."""
@@ -78,7 +82,15 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
     print(f"G-buffer + facing map + {count} lights x {spp} samples{f', probe {probe},' if probe else ''} in one dispatch: {(time.time() - t0) * 1e3:.2f} ms (first call, incl. "
           f"launch); {ctx.last_kernel_name()}")
     rgb = np.zeros((H, W, 3), np.uint8)
-    api.combine_soft_light_list_device(ctx, wl.constants, lights, d_pos, d_nrm, d_counts, W, H, d_rgb, d_lights_map=d_map, colors=colors)
+    if filt is not None:                                 # trace -> filter -> visibility combine, all on the device
+        d_vis = ctx.malloc(count * W * H * 4)
+        api.filter_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_lights_map=d_map, d_distances=d_dist)
+        api.combine_visibility_list_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, d_vis, W, H, d_rgb, d_lights_map=d_map,
+                                           colors=colors)
+        print(f"filtered: radius {filt.radius}, N.N' >= {filt.normal_cos_min:g}, plane distance <= {filt.plane_eps:g}"
+              + (f", distance-guided with spread {filt.spread[0]:g}" if d_dist else ""))
+    else:
+        api.combine_soft_light_list_device(ctx, wl.constants, lights, d_pos, d_nrm, d_counts, W, H, d_rgb, d_lights_map=d_map, colors=colors)
     ctx.synchronize()
     ctx.d2h(rgb, d_rgb)                                  # the one read-back of the image
     planes = np.zeros((count, H, W), np.uint8)
@@ -126,6 +138,12 @@ def main():
                     help="with --soft-list N --adaptive K: a per-pixel jitter table of T entries per light (spp <= T), its start hashed per pixel")
     ap.add_argument("--soft-list", type=int, default=0, metavar="N",
                     help="light the frame by N area lights of --spp samples each, traced in one soft light list dispatch")
+    ap.add_argument("--filter", type=int, default=-1, metavar="R",
+                    help="with --soft-list N: filter the count planes (rtsh_filter_soft_light_list_device, a window of (2R+1)^2 pixels, "
+                         "R = 0..8) and light the frame from the visibility planes; with --distance the distance planes guide the filter")
+    ap.add_argument("--spread", type=float, default=0.25, help="with --filter and --distance: the penumbra width per unit of blocker distance")
+    ap.add_argument("--plane-eps", type=float, default=0.05, help="with --filter: the largest plane distance of an accepted tap (world units)")
+    ap.add_argument("--normal-cos", type=float, default=0.9, help="with --filter: the smallest N.N' of an accepted tap")
     ap.add_argument("--colors", default="", metavar="r,g,b[;r,g,b...]",
                     help="with --soft-list N: the lights' colours, one triple for all of them or N separated by ';' (default 1/N each)")
     args = ap.parse_args()
@@ -137,7 +155,11 @@ def main():
     with api.ShadowContext(0) as ctx:
         ctx.set_bvh(wl.packed)
         if args.soft_list:
-            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance, args.colors)
+            if not -1 <= args.filter <= api.FilterParams.MAX_RADIUS:
+                sys.exit("render: --filter R takes 0 <= R <= 8")
+            filt = api.FilterParams.make(args.filter, args.normal_cos, args.plane_eps, args.spread) if args.filter >= 0 else None
+            return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance,
+                             args.colors, filt)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
         t0 = time.time()
         api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
