@@ -232,8 +232,8 @@ int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_constants* const
  *   * host forms: multi-threaded (threads: 0 = all host threads).  Device forms: DEVICE buffers, asynchronous on `stream`, allocate
  *     nothing and read nothing back; under graph capture each adds ONE kernel node, list and parameters by value (params is read
  *     during the call).  They need no BVH and no alignment of any buffer beyond its element type's.
- *   * OUT OF SCOPE: row ranges and stripes (a stripe would need a halo of R rows from its neighbours), a temporal filter, variance
- *     guidance. */
+ *   * OUT OF SCOPE: row ranges and stripes (a stripe would need a halo of R rows from its neighbours), variance guidance.  (The
+ *     temporal stage is rtsh_accumulate_visibility_list below.) */
 enum { RTSH_FILTER_MAX_RADIUS = 8 };
 typedef struct rtsh_filter_params {
     uint32_t radius;          /* R, 0 .. RTSH_FILTER_MAX_RADIUS (8): the window is (2R+1) x (2R+1) pixels */
@@ -267,6 +267,89 @@ int rtsh_combine_visibility_list(const rts_constants* constants, const rts_light
 int rtsh_combine_visibility_list_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* colors,
                                         const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
                                         const float* d_visibility, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream);
+
+/* THE TEMPORAL ACCUMULATION OF A LIGHT LIST'S VISIBILITY: this frame's float visibility planes (a filter's output; the R = 0 filter is
+ * the conversion from counts) blended with LAST frame's result, which is fetched through the camera motion -- reprojected -- and
+ * rejected where the surface seen last frame is another one (a disocclusion).  It is the stage that turns 4 samples per frame into 16
+ * or 48 over frames: the jitter hash takes no frame term, the CALLER rotates its shared offsets table per frame.  The result is a
+ * function of the inputs alone: bilinear weights are INTEGERS on a 1/32-pixel grid, every float step below is one rounded float32
+ * operation (the library is built without contraction), and the order of the four taps is part of the definition -- so the host form
+ * checks the device form bit for bit.  All buffers are whole frames of W x H.
+ *   CURRENT frame: positions, normals, lights_map (may be NULL), visibility (count float planes).
+ *   PREVIOUS frame: prev_positions, prev_normals, prev_visibility (the history, count float planes), prev_lengths (count byte planes:
+ *     how many frames a pixel's history holds, 0 = none).  All four NULL: the FIRST FRAME (no history); all four or none.
+ *   Outputs: visibility_out (count float planes), lengths_out (count byte planes).
+ *   typedef struct rtsh_temporal_params: eye_delta (current eye minus previous eye; positions are camera-relative), prev_right, prev_up,
+ *   prev_fwd (the previous camera's basis), prev_scale_x = tanHalf * aspect and prev_scale_y = tanHalf of the previous camera,
+ *   normal_cos_min, plane_eps, max_length (1 .. 255), reset_lights (bit l set: light l takes no history this frame -- it moved),
+ *   reserved_ (ignored).  rtsh_camera_basis gives the numbers the G-buffer pass itself used.
+ * dot3(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.  For pixel p = (x, y) and light l < count, N_p = normals[p].xyz, P_p = positions[p].xyz:
+ *   INACTIVE: where N_p is all zero, or lights_map != NULL and bit l of lights_map[p] is clear: visibility_out[l][p] = +0.0f,
+ *     lengths_out[l][p] = 0, and nothing else of p is looked at for that light.
+ *   REPROJECT (once per pixel): Q = P_p + eye_delta (three additions); z = dot3(Q, prev_fwd); a = dot3(Q, prev_right) / z;
+ *     b = dot3(Q, prev_up) / z;  fx = (a / prev_scale_x + 1.0f) * (0.5f * (float)W) - 0.5f;
+ *     fy = (1.0f - b / prev_scale_y) * (0.5f * (float)H) - 0.5f  (the inverse of the primary pass's pixel-to-direction map);
+ *     gx = fx * 32.0f + 0.5f, gy = fy * 32.0f + 0.5f.  p is ON SCREEN when z > 0, gx >= -32.0f, gx < (float)W * 32.0f, gy >= -32.0f and
+ *     gy < (float)H * 32.0f all hold (a NaN fails).  Then ix = (int32_t)floorf(gx), x0 = ix >> 5 (floor), ax = ix & 31, and the same
+ *     for y.  The four taps IN THIS ORDER: (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), of the INTEGER weights
+ *     (32-ax)*(32-ay), ax*(32-ay), (32-ax)*ay, ax*ay, which sum to 1024.
+ *   A tap q is ACCEPTED for light l when: its weight is not 0; q is inside the frame; prev_normals[q].xyz is not all zero;
+ *     dot3(N_p, N'_q) >= normal_cos_min; fabsf(dot3(N_p, P'_q - Q)) <= plane_eps (three subtractions; P'_q and Q are both relative to
+ *     the previous eye, so for static geometry this is the disocclusion test); prev_lengths[l][q] != 0; bit l of reset_lights is clear.
+ *     The first five do not depend on the light.  Every comparison is written so that a NaN rejects.  The position and the history of a
+ *     rejected tap are not looked at.
+ *   BLEND: sw = the integer sum of the accepted weights; sv = +0.0f, then for the accepted taps in the order above
+ *     sv = sv + (float)w * prev_visibility[l][q]; m = the smallest prev_lengths[l][q] over the accepted taps.  With no accepted tap, or p
+ *     not on screen, or on the first frame: visibility_out[l][p] = visibility[l][p] (its bits), lengths_out[l][p] = 1.  Otherwise
+ *     n = min(m + 1, max_length), lengths_out[l][p] = n, and visibility_out[l][p] = visibility[l][p] if n == 1, else
+ *     v = prev + (cur - prev) * (1.0f / (float)n) with prev = sv / (float)sw and cur = visibility[l][p]; where v is a NaN (v != v),
+ *     the word stored is the canonical quiet NaN 0x7FC00000, whatever NaN the machine's arithmetic produced -- which NaN an operation
+ *     returns is the one thing hosts and the GPU disagree on.  Only a BLENDED value is treated so: a value passed through
+ *     (visibility_out = visibility[l][p]: no accepted tap, off screen, first frame, n == 1) keeps its bits, a NaN's payload included.
+ *   Any float is allowed in any plane; the rule, with the NaN step, defines every bit of the result.
+ * ANCHORS: (1) max_length == 1, or all-ones reset_lights, or the first frame: visibility_out is visibility, bit for bit, at active
+ * pixels, and lengths_out is 1 there.  (2) A still camera -- params from rtsh_camera_basis of the very camera both G-buffers were made
+ * with, eye_delta 0: every non-background pixel lands on itself (ax == ay == 0: one tap of weight 1024; the float32 inverse misses a
+ * pixel centre by up to 0.0023 pixel at 7680 wide for frames of ordinary aspect, well inside the 1/64 pixel that rounds to ax == 0;
+ * the miss grows with W / H -- 0.0084 pixel for a strip of 1920 x 8 -- and from an aspect of a few hundred on some pixels of a still
+ * camera take two taps: the rule still defines them, the anchor no longer covers them), 1024 * h / 1024 is exact for
+ * a history value in the normal range, and frame k holds h_k = h_(k-1) + (c_k - h_(k-1)) * (1 / min(k, max_length)): a running mean,
+ * then an exponential one.  (3) A light whose bit is set in reset_lights gets anchor 1 whatever the other lights do.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: what rtsh_filter_*_light_list* refuse of a list; NULL params, positions,
+ *     normals, visibility, visibility_out or lengths_out; some but not all of the four prev_* NULL; max_length 0 or above 255; a
+ *     normal_cos_min, plane_eps, eye_delta, basis or scale component that is not finite; a scale that is not > 0; W or H equal to 0 or
+ *     above 65536 (so that (float)W * 32 and ix stay exact); visibility_out == prev_visibility or lengths_out == prev_lengths (the pass
+ *     gathers from neighbours: history must ping-pong); a NULL ctx.
+ *   * visibility_out == visibility IS allowed: a pixel reads only its own current value, and reads it before it writes.
+ *   * planes of any buffer from `count` up are never touched.  Only `count` of the list matters; it is the list the visibility combine
+ *     takes.
+ *   * host form: multi-threaded (threads: 0 = all host threads).  Device form: DEVICE buffers, asynchronous on `stream`, allocates
+ *     nothing and reads nothing back; under graph capture ONE kernel node, list and params by value (params is read during the call).
+ *     No BVH, no alignment of any buffer beyond its element type's.
+ *   * OUT OF SCOPE: moving geometry (no motion vectors: the plane test takes it for a disocclusion and resets), neighbourhood or variance
+ *     clamping of the history, accumulating count or distance planes, row ranges and stripes, a frame term in the jitter hash. */
+typedef struct rtsh_temporal_params {
+    float    eye_delta[3];                             /* current eye - previous eye */
+    float    prev_right[3], prev_up[3], prev_fwd[3];   /* the previous camera's basis */
+    float    prev_scale_x, prev_scale_y;               /* its tanHalf * aspect and tanHalf: finite, > 0 */
+    float    normal_cos_min;                           /* a tap needs N_p . N'_q >= this */
+    float    plane_eps;                                /* ... and |N_p . (P'_q - Q)| <= this (world units) */
+    uint32_t max_length;                               /* 1 .. 255 */
+    uint32_t reset_lights;                             /* bit l: light l takes no history this frame */
+    uint32_t reserved_[2];                             /* ignored */
+} rtsh_temporal_params;                                                            /* 80 bytes */
+/* The camera the primary pass (rtsh_primary_gbuffer*) builds from (eye, target, fovy, W, H), exactly: out = eye[3], fwd[3], right[3],
+ * up[3], tanHalf, aspect.  RTS_ERR_INVALID_ARG for a NULL pointer or W == 0 or H == 0. */
+int rtsh_camera_basis(const float eye[3], const float target[3], float fovy, uint32_t W, uint32_t H, float out[14]);
+int rtsh_accumulate_visibility_list(const rts_light_list* list, const rtsh_temporal_params* params, const float* positions,
+                                    const float* normals, const uint8_t* lights_map, const float* visibility, const float* prev_positions,
+                                    const float* prev_normals, const float* prev_visibility, const uint8_t* prev_lengths, uint32_t W,
+                                    uint32_t H, float* visibility_out, uint8_t* lengths_out, int threads);
+int rtsh_accumulate_visibility_list_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_temporal_params* params,
+                                           const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                           const float* d_visibility, const float* d_prev_positions, const float* d_prev_normals,
+                                           const float* d_prev_visibility, const uint8_t* d_prev_lengths, uint32_t W, uint32_t H,
+                                           float* d_visibility_out, uint8_t* d_lengths_out, void* stream);
 
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.

@@ -208,6 +208,33 @@ class FilterParams(C.Structure):
         return p
 
 
+class TemporalParams(C.Structure):
+    """``rtsh_temporal_params``: the camera motion (current eye minus previous eye, the previous camera's basis and scales), the two
+    geometry thresholds, the longest history (1..255) and the lights that take no history this frame (a bit per light)."""
+    _fields_ = [("eye_delta", C.c_float * 3), ("prev_right", C.c_float * 3), ("prev_up", C.c_float * 3), ("prev_fwd", C.c_float * 3),
+                ("prev_scale_x", C.c_float), ("prev_scale_y", C.c_float), ("normal_cos_min", C.c_float), ("plane_eps", C.c_float),
+                ("max_length", C.c_uint32), ("reset_lights", C.c_uint32), ("reserved_", C.c_uint32 * 2)]
+
+    @classmethod
+    def make(cls, eye_delta, prev_right, prev_up, prev_fwd, prev_scale_x, prev_scale_y, normal_cos_min=0.9, plane_eps=0.05, max_length=32,
+             reset_lights=0):
+        p = cls()
+        for field, value in (("eye_delta", eye_delta), ("prev_right", prev_right), ("prev_up", prev_up), ("prev_fwd", prev_fwd)):
+            getattr(p, field)[:] = [np.float32(v) for v in value]
+        p.prev_scale_x, p.prev_scale_y = np.float32(prev_scale_x), np.float32(prev_scale_y)
+        p.normal_cos_min, p.plane_eps, p.max_length, p.reset_lights = np.float32(normal_cos_min), np.float32(plane_eps), max_length, reset_lights
+        return p
+
+    @classmethod
+    def from_cameras(cls, cur, prev, width, height, normal_cos_min=0.9, plane_eps=0.05, max_length=32, reset_lights=0):
+        """``cur`` and ``prev``: ``(eye, target, fovy)`` of this frame's and the previous frame's camera.  The numbers are
+        ``camera_basis``'s: the ones the G-buffer pass itself used; eye_delta is the float32 difference of the two eyes."""
+        c, q = camera_basis(*cur, width, height), camera_basis(*prev, width, height)
+        tan_half, aspect = q["tan_half"], q["aspect"]
+        return cls.make(c["eye"] - q["eye"], q["right"], q["up"], q["fwd"], np.float32(tan_half * aspect), tan_half, normal_cos_min, plane_eps,
+                        max_length, reset_lights)
+
+
 #: numpy view of ``struct BVHNode`` (BVHBuilder.h:8-20)
 BVHNode_dtype = np.dtype([("bboxMin", np.float32, 3), ("prim", np.uint32),
                           ("bboxMax", np.float32, 3), ("next", np.uint32)])
@@ -449,6 +476,11 @@ _sig("rtsh_combine_visibility_list", C.c_int, C.POINTER(RayTracingConstants), C.
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
 _sig("rtsh_combine_visibility_list_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_camera_basis", C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rtsh_accumulate_visibility_list", C.c_int, C.POINTER(LightList), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rtsh_accumulate_visibility_list_device", C.c_int, C.c_void_p, C.POINTER(LightList), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_facing_active", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
      C.c_void_p)
 _sig("rtsh_facing_active_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
@@ -1555,6 +1587,58 @@ def combine_visibility_list_device(ctx, constants, light_list, d_positions, d_no
                                                     C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
                                                     C.c_void_p(d_visibility), width, height, C.c_void_p(d_rgb), C.c_void_p(stream or 0)),
            "rtsh_combine_visibility_list_device")
+
+
+def camera_basis(eye, target, fovy, width, height):
+    """The camera the primary pass builds from (eye, target, fovy, width, height) (rtsh_camera_basis): a dict of float32 ``eye``,
+    ``fwd``, ``right``, ``up`` (3 each), ``tan_half`` and ``aspect``."""
+    e, t, out = np.asarray(eye, np.float32).copy(), np.asarray(target, np.float32).copy(), np.zeros(14, np.float32)
+    if e.shape != (3,) or t.shape != (3,):
+        raise RtsError(1, "rtsh_camera_basis: eye and target are 3 floats")
+    _check(_lib.rtsh_camera_basis(_ptr(e), _ptr(t), C.c_float(fovy), width, height, _ptr(out)), "rtsh_camera_basis")
+    return {"eye": out[0:3].copy(), "fwd": out[3:6].copy(), "right": out[6:9].copy(), "up": out[9:12].copy(), "tan_half": out[12],
+            "aspect": out[13]}
+
+
+def accumulate_visibility_list(light_list, params, positions, normals, visibility, prev=None, lights_map=None, threads=0):
+    """The temporal accumulation of a light list's visibility on the host (rtsh_accumulate_visibility_list): ``(float32[count, H, W]
+    visibility, uint8[count, H, W] lengths)``.  ``visibility``: this frame's ``float32[>= count, H, W]`` (a filter's output);
+    ``prev``: None on the first frame, else ``(prev_positions, prev_normals, prev_visibility, prev_lengths)`` of the previous frame
+    (its G-buffer and what this call returned for it); ``params`` a ``TemporalParams``."""
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    count = light_list.count if light_list is not None and 1 <= light_list.count <= 8 else 1
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    visibility = np.ascontiguousarray(visibility, np.float32)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    fits = visibility.size >= count * H * W and (lights_map is None or lights_map.size == H * W) and \
+        (positions is None or positions.size == H * W * 4)
+    if prev is not None:
+        prev = (np.ascontiguousarray(prev[0], np.float32), np.ascontiguousarray(prev[1], np.float32), np.ascontiguousarray(prev[2], np.float32),
+                np.ascontiguousarray(prev[3], np.uint8))
+        fits = fits and prev[0].size == H * W * 4 and prev[1].size == H * W * 4 and prev[2].size >= count * H * W and prev[3].size >= count * H * W
+    if not fits:
+        raise RtsError(1, "rtsh_accumulate_visibility_list: a buffer does not fit the frame of the normals")
+    out, lengths = np.zeros((count, H, W), np.float32), np.zeros((count, H, W), np.uint8)
+    pp = [_ptr(a) for a in prev] if prev is not None else [None] * 4
+    _check(_lib.rtsh_accumulate_visibility_list(_ref(light_list), _ref(params), _ptr_or_none(positions), _ptr(normals), _ptr_or_none(lights_map),
+                                                _ptr(visibility), pp[0], pp[1], pp[2], pp[3], W, H, _ptr(out), _ptr(lengths), threads),
+           "rtsh_accumulate_visibility_list")
+    return out, lengths
+
+
+def accumulate_visibility_list_device(ctx, light_list, params, d_positions, d_normals, d_visibility, width, height, d_visibility_out,
+                                      d_lengths_out, d_prev=None, d_lights_map=None, stream=None):
+    """The temporal accumulation on the GPU: device pointers; ``d_prev``: None on the first frame, else the device pointers
+    ``(prev_positions, prev_normals, prev_visibility, prev_lengths)``.  d_visibility_out = count planes of width*height floats,
+    d_lengths_out = count planes of width*height bytes; neither may be the history it reads.  One kernel, asynchronous."""
+    pp = tuple(d_prev) if d_prev is not None else (0, 0, 0, 0)
+    _check(_lib.rtsh_accumulate_visibility_list_device(ctx.handle, _ref(light_list), _ref(params), C.c_void_p(d_positions or 0),
+                                                       C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0), C.c_void_p(d_visibility),
+                                                       C.c_void_p(pp[0] or 0), C.c_void_p(pp[1] or 0), C.c_void_p(pp[2] or 0),
+                                                       C.c_void_p(pp[3] or 0), width, height, C.c_void_p(d_visibility_out),
+                                                       C.c_void_p(d_lengths_out), C.c_void_p(stream or 0)),
+           "rtsh_accumulate_visibility_list_device")
 
 
 def write_ppm(path, rgb):

@@ -283,6 +283,93 @@ RTS_HD void filterListPixel(const FilterList& f, const Texels& t, int x, int y, 
     }
 }
 
+// The TEMPORAL ACCUMULATION of a light list's visibility (include/rts_scene.h, rtsh_accumulate_visibility_list), one pixel: reproject
+// through the previous camera onto a 1/32-pixel grid, four bilinear taps of INTEGER weights (they sum to 1024), each accepted by the
+// geometry (inside the frame, not background, normal, plane distance: once per tap, a 4-bit mask) and per light by its history length;
+// then one division, one reciprocal and one lerp per light.  Every float step is one rounded operation in the order the header states;
+// every comparison is written so that a NaN rejects.  A tap of weight 0 or a rejected tap is never loaded: a still camera costs one
+// gather per light.  `Frames` gives both frames by pixel coordinates (the host twin reads the buffers, the kernel reads them with its
+// own cache policy):
+//   V3 normal(x, y), position(x, y); uint32_t bits(x, y) (the map byte, 0xFF without a map); uint32_t current(l, x, y) (the BITS of
+//   visibility[l][p]); V3 prevNormal(x, y), prevPosition(x, y); uint32_t prevLength(l, x, y); float prevVisibility(l, x, y);
+//   void store(l, x, y, uint32_t visibilityBits, uint32_t length).
+// A blended value that is a NaN is stored as 0x7FC00000: which NaN an operation returns is the one thing the machines disagree on.
+struct TemporalList {
+    uint32_t count, maxLength, resetLights, history;      // history: 0 on the first frame (no prev_* buffers)
+    V3 eyeDelta, right, up, fwd;
+    float scaleX, scaleY, normalCosMin, planeEps;
+};
+
+RTS_HD float dotGrouped(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+RTS_HD uint32_t floatBits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+
+template <class Frames>
+RTS_HD void accumulatePixel(const TemporalList& f, const Frames& t, int x, int y, int W, int H) {
+    const V3 np = t.normal(x, y);
+    const uint32_t all = (1u << f.count) - 1u;
+    const uint32_t onp = isBackground(np) ? 0u : (t.bits(x, y) & all);
+    int qx[4] = { 0, 0, 0, 0 }, qy[4] = { 0, 0, 0, 0 };
+    uint32_t w[4] = { 0, 0, 0, 0 }, taps = 0;                                                      // taps: bit k = tap k passes the geometry
+    if (onp != 0u && f.history != 0u && (all & ~f.resetLights) != 0u) {
+        const V3 q = add(t.position(x, y), f.eyeDelta);
+        const float z = dotGrouped(q, f.fwd);
+        const float a = dotGrouped(q, f.right) / z, b = dotGrouped(q, f.up) / z;
+        const float fx = (a / f.scaleX + 1.0f) * (0.5f * (float)W) - 0.5f;
+        const float fy = (1.0f - b / f.scaleY) * (0.5f * (float)H) - 0.5f;
+        const float gx = fx * 32.0f + 0.5f, gy = fy * 32.0f + 0.5f;
+        if (z > 0.0f && gx >= -32.0f && gx < (float)W * 32.0f && gy >= -32.0f && gy < (float)H * 32.0f) {
+            const int32_t ix = (int32_t)__builtin_floorf(gx), iy = (int32_t)__builtin_floorf(gy);
+            const int x0 = ix >> 5, y0 = iy >> 5;
+            const uint32_t ax = (uint32_t)(ix & 31), ay = (uint32_t)(iy & 31);
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int k = 0; k < 4; ++k) {
+                qx[k] = x0 + (k & 1); qy[k] = y0 + (k >> 1);
+                w[k] = ((k & 1) ? ax : 32u - ax) * ((k >> 1) ? ay : 32u - ay);
+                if (w[k] == 0u || qx[k] < 0 || qx[k] >= W || qy[k] < 0 || qy[k] >= H) continue;
+                const V3 nq = t.prevNormal(qx[k], qy[k]);
+                if (isBackground(nq)) continue;
+                if (!(dotGrouped(np, nq) >= f.normalCosMin)) continue;
+                const float h = dotGrouped(np, sub(t.prevPosition(qx[k], qy[k]), q));
+                if (!(__builtin_fabsf(h) <= f.planeEps)) continue;
+                taps |= 1u << k;
+            }
+        }
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        if (!((onp >> l) & 1u)) { t.store(l, x, y, 0u, 0u); continue; }
+        const uint32_t cur = t.current(l, x, y);
+        uint32_t sw = 0, m = 255u;
+        float sv = 0.0f;
+        if (taps != 0u && !((f.resetLights >> l) & 1u)) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int k = 0; k < 4; ++k) {
+                if (!((taps >> k) & 1u)) continue;
+                const uint32_t len = t.prevLength(l, qx[k], qy[k]);
+                if (len == 0u) continue;
+                sw += w[k];
+                sv = sv + (float)w[k] * t.prevVisibility(l, qx[k], qy[k]);
+                if (len < m) m = len;
+            }
+        }
+        const uint32_t n = sw == 0u ? 1u : (m + 1u < f.maxLength ? m + 1u : f.maxLength);
+        uint32_t out = cur;
+        if (n != 1u) {
+            const float prev = sv / (float)sw, c = asFloat(cur);
+            const float v = prev + (c - prev) * (1.0f / (float)n);
+            out = v != v ? 0x7FC00000u : floatBits(v);
+        }
+        t.store(l, x, y, out, n);
+    }
+}
+
 // The facing mark (include/rts_scene.h, rtsh_facing_active): 0 where the shadow mask's byte cannot reach the image -- the
 // background (combinePixel leaves the pixel 0) and N.L <= 0 (direct = 1.25 * 0 * mask: either zero) --, 1 everywhere else.
 // `!(ndl > 0)` would cull a NaN; `ndl <= 0` is false for one, so a NaN is traced.

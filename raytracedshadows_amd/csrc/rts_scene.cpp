@@ -716,3 +716,88 @@ extern "C" int rtsh_combine_visibility_list(const rts_constants* k, const rts_li
     }
     return RTS_OK;
 }
+
+// ---- the temporal accumulation of a light list's visibility (include/rts_scene.h; per-pixel rule in rts_closest_hit.h: accumulatePixel) ----
+extern "C" int rtsh_camera_basis(const float eye[3], const float target[3], float fovy, uint32_t W, uint32_t H, float out[14]) {
+    if (!eye || !target || !out || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    const Camera c = makeCamera(eye, target, fovy, W, H);
+    const V3 v[4] = { c.eye, c.fwd, c.right, c.up };
+    for (int i = 0; i < 4; ++i) { out[i * 3] = v[i].x; out[i * 3 + 1] = v[i].y; out[i * 3 + 2] = v[i].z; }
+    out[12] = c.tanHalf;
+    out[13] = c.aspect;
+    return RTS_OK;
+}
+
+namespace rts_harness {
+// Shared by the host and device forms: every refusal that needs no context, and the condensed form the per-pixel rule reads.
+int makeTemporalList(const rts_light_list* list, const rtsh_temporal_params* p, const void* positions, const void* normals,
+                     const void* visibility, const void* prevPositions, const void* prevNormals, const void* prevVisibility,
+                     const void* prevLengths, uint32_t W, uint32_t H, const void* visibilityOut, const void* lengthsOut, TemporalList* out) {
+    if (!rts::lightListOk(list) || !p || !positions || !normals || !visibility || !visibilityOut || !lengthsOut) return RTS_ERR_INVALID_ARG;
+    const int prevs = (prevPositions != nullptr) + (prevNormals != nullptr) + (prevVisibility != nullptr) + (prevLengths != nullptr);
+    if (prevs != 0 && prevs != 4) return RTS_ERR_INVALID_ARG;
+    if (W == 0 || H == 0 || W > 65536u || H > 65536u || p->max_length == 0 || p->max_length > 255u) return RTS_ERR_INVALID_ARG;
+    const float* numbers[] = { p->eye_delta, p->prev_right, p->prev_up, p->prev_fwd };
+    for (const float* v : numbers)
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(v[i])) return RTS_ERR_INVALID_ARG;
+    if (!std::isfinite(p->normal_cos_min) || !std::isfinite(p->plane_eps) || !std::isfinite(p->prev_scale_x) ||
+        !std::isfinite(p->prev_scale_y) || !(p->prev_scale_x > 0.0f) || !(p->prev_scale_y > 0.0f))
+        return RTS_ERR_INVALID_ARG;
+    if (prevs == 4 && (visibilityOut == prevVisibility || lengthsOut == prevLengths)) return RTS_ERR_INVALID_ARG;   // history must ping-pong
+    out->count = list->count;
+    out->maxLength = p->max_length;
+    out->resetLights = p->reset_lights & 0xFFu;
+    out->history = prevs == 4 ? 1u : 0u;
+    out->eyeDelta = V3{ p->eye_delta[0], p->eye_delta[1], p->eye_delta[2] };
+    out->right = V3{ p->prev_right[0], p->prev_right[1], p->prev_right[2] };
+    out->up = V3{ p->prev_up[0], p->prev_up[1], p->prev_up[2] };
+    out->fwd = V3{ p->prev_fwd[0], p->prev_fwd[1], p->prev_fwd[2] };
+    out->scaleX = p->prev_scale_x;
+    out->scaleY = p->prev_scale_y;
+    out->normalCosMin = p->normal_cos_min;
+    out->planeEps = p->plane_eps;
+    return RTS_OK;
+}
+
+namespace {
+// Both frames as accumulatePixel reads them on the host: straight from the buffers.
+struct TemporalFrames {
+    const float *positions, *normals, *visibility, *prevPositions, *prevNormals, *history;
+    const uint8_t *map, *prevLengths;
+    float* visibilityOut;
+    uint8_t* lengthsOut;
+    size_t W, n;
+    size_t at(int x, int y) const { return (size_t)y * W + (size_t)x; }
+    static V3 xyz(const float* base, size_t i) { const float* v = base + i * 4; return V3{ v[0], v[1], v[2] }; }
+    V3 normal(int x, int y) const { return xyz(normals, at(x, y)); }
+    V3 position(int x, int y) const { return xyz(positions, at(x, y)); }
+    uint32_t bits(int x, int y) const { return map ? map[at(x, y)] : 0xFFu; }
+    uint32_t current(uint32_t l, int x, int y) const { uint32_t u; memcpy(&u, visibility + (size_t)l * n + at(x, y), 4); return u; }
+    V3 prevNormal(int x, int y) const { return xyz(prevNormals, at(x, y)); }
+    V3 prevPosition(int x, int y) const { return xyz(prevPositions, at(x, y)); }
+    uint32_t prevLength(uint32_t l, int x, int y) const { return prevLengths[(size_t)l * n + at(x, y)]; }
+    float prevVisibility(uint32_t l, int x, int y) const { return history[(size_t)l * n + at(x, y)]; }
+    void store(uint32_t l, int x, int y, uint32_t bits, uint32_t length) const {
+        memcpy(visibilityOut + (size_t)l * n + at(x, y), &bits, 4);
+        lengthsOut[(size_t)l * n + at(x, y)] = (uint8_t)length;
+    }
+};
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_accumulate_visibility_list(const rts_light_list* list, const rtsh_temporal_params* params, const float* positions,
+                                               const float* normals, const uint8_t* lights_map, const float* visibility,
+                                               const float* prev_positions, const float* prev_normals, const float* prev_visibility,
+                                               const uint8_t* prev_lengths, uint32_t W, uint32_t H, float* visibility_out,
+                                               uint8_t* lengths_out, int threads) {
+    TemporalList f;
+    const int s = makeTemporalList(list, params, positions, normals, visibility, prev_positions, prev_normals, prev_visibility, prev_lengths,
+                                   W, H, visibility_out, lengths_out, &f);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const TemporalFrames t{ positions, normals, visibility, prev_positions, prev_normals, prev_visibility, lights_map, prev_lengths,
+                            visibility_out, lengths_out, W, n };
+    parallelFor(n, 256, threads, [&](size_t i) { accumulatePixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H); });
+    return RTS_OK;
+}

@@ -2,7 +2,13 @@
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
                            [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]
-                                          [--filter R [--spread S] [--plane-eps E] [--normal-cos C]]]
+                                          [--filter R [--spread S] [--plane-eps E] [--normal-cos C]
+                                                      [--temporal F [--orbit DEG] [--max-length L]]]]
+
+--temporal F (with --soft-list N --filter R): F frames are rendered -- trace, filter, rtsh_accumulate_visibility_list_device with
+ping-pong history -- and the LAST frame is lit from the accumulated visibility.  Frame k traces with the shared offsets table rotated
+by k entries; --orbit DEG turns the eye around the target by DEG per frame (default 0: a still camera); --max-length L (default 32) is
+the longest history.
 
 --filter R (with --soft-list N): between trace and image the count planes go through rtsh_filter_soft_light_list_device -- an edge-aware
 tent window of (2R+1)^2 pixels that stops at normal and depth edges (--normal-cos, --plane-eps) -- and the frame is lit from the float
@@ -121,6 +127,58 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
               f"{[round(float(took[l].mean()), 3) for l in range(count)]}")
 
 
+def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, max_length, probe=0, table=0, colors=""):
+    """`frames` frames of a light list: per frame G-buffer, facing map, trace (the offsets table rotated by one entry per frame), filter
+    and accumulation with ping-pong history; the last frame is lit from the accumulated visibility."""
+    from raytracedshadows_amd import api, scenes
+    from list_temporal_ab import orbit
+    from soft_list_ab import entries
+    if not 1 <= count <= 8 or count * max(spp, 1) > 48 or frames < 1 or not 1 <= max_length <= 255:
+        sys.exit("render: --temporal F takes F >= 1, 1..8 lights of at most 48 samples in all and 1 <= --max-length <= 255")
+    colors = parse_colors(colors, count)
+    offsets = scenes.jitter_offsets(48, 1.0, 19)
+    sc, n = wl.scene, W * H
+    gbuf = [(ctx.malloc(n * 16), ctx.malloc(n * 16)) for _ in range(2)]
+    hist = [(ctx.malloc(count * n * 4), ctx.malloc(count * n)) for _ in range(2)]
+    d_map, d_counts, d_vis, d_rgb = ctx.malloc(n), ctx.malloc(count * n), ctx.malloc(count * n * 4), ctx.malloc(n * 3)
+    eyes = [orbit(sc.eye, sc.target, orbit_deg * (k - (frames - 1))) for k in range(frames)]      # the last frame is the scene's own camera
+    t0 = time.time()
+    for k in range(frames):
+        d_pos, d_nrm = gbuf[k % 2]
+        lights = api.SoftLightList.make(entries(sc, count, spp), np.ascontiguousarray(np.roll(offsets, -k, axis=0)))
+        hard = lights.hard_list()
+        constants = api.RayTracingConstants.make(eyes[k], sc.light_direction, W, H)
+        api.primary_gbuffer_device(ctx, eyes[k], sc.target, sc.fovy, W, H, d_pos, d_nrm)
+        api.facing_lights_device(ctx, constants, hard, d_pos, d_nrm, W, H, d_map)
+        if probe:
+            ctx.trace_soft_light_list_adaptive_device(constants, lights, (probe,) * count, d_pos, W, H, d_counts, d_lights_map=d_map,
+                                                      tables=(table,) * count if table else None)
+        else:
+            ctx.trace_soft_light_list_device(constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
+        api.filter_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_lights_map=d_map)
+        tp = api.TemporalParams.from_cameras((eyes[k], sc.target, sc.fovy), (eyes[max(k - 1, 0)], sc.target, sc.fovy), W, H,
+                                             filt.normal_cos_min, filt.plane_eps, max_length)
+        d_prev = None if k == 0 else gbuf[(k - 1) % 2] + hist[(k - 1) % 2]
+        api.accumulate_visibility_list_device(ctx, hard, tp, d_pos, d_nrm, d_vis, W, H, hist[k % 2][0], hist[k % 2][1], d_prev=d_prev,
+                                              d_lights_map=d_map)
+    last = (frames - 1) % 2
+    api.combine_visibility_list_device(ctx, constants, hard, gbuf[last][0], gbuf[last][1], hist[last][0], W, H, d_rgb, d_lights_map=d_map,
+                                       colors=colors)
+    ctx.synchronize()
+    print(f"{frames} frames of {count} lights x {spp} samples, filter radius {filt.radius}, orbit {orbit_deg:g} degree per frame, "
+          f"max_length {max_length}: {(time.time() - t0) * 1e3:.2f} ms (incl. first launches)")
+    rgb, lengths, marks = np.zeros((H, W, 3), np.uint8), np.zeros((count, H, W), np.uint8), np.zeros((H, W), np.uint8)
+    ctx.d2h(rgb, d_rgb)
+    ctx.d2h(lengths, hist[last][1])
+    ctx.d2h(marks, d_map)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    api.write_ppm(out, rgb)
+    reached = np.stack([((marks >> l) & 1) != 0 for l in range(count)])
+    print(f"wrote {out}: {W}x{H}, mean history length per light over the pixels it reaches "
+          f"{[round(float(lengths[l][reached[l]].mean()), 2) if reached[l].any() else 0.0 for l in range(count)]}, share of them without "
+          f"history {[round(float((lengths[l][reached[l]] == 1).mean()), 3) if reached[l].any() else 0.0 for l in range(count)]}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="atrium_1080p")
@@ -144,6 +202,11 @@ def main():
     ap.add_argument("--spread", type=float, default=0.25, help="with --filter and --distance: the penumbra width per unit of blocker distance")
     ap.add_argument("--plane-eps", type=float, default=0.05, help="with --filter: the largest plane distance of an accepted tap (world units)")
     ap.add_argument("--normal-cos", type=float, default=0.9, help="with --filter: the smallest N.N' of an accepted tap")
+    ap.add_argument("--temporal", type=int, default=0, metavar="F",
+                    help="with --soft-list N --filter R: render F frames, accumulate the visibility over them (ping-pong history, the "
+                         "offsets table rotated by one entry per frame) and light the last one from it")
+    ap.add_argument("--orbit", type=float, default=0.0, metavar="DEG", help="with --temporal: turn the eye around the target by DEG per frame")
+    ap.add_argument("--max-length", type=int, default=32, metavar="L", help="with --temporal: the longest history, 1..255")
     ap.add_argument("--colors", default="", metavar="r,g,b[;r,g,b...]",
                     help="with --soft-list N: the lights' colours, one triple for all of them or N separated by ';' (default 1/N each)")
     args = ap.parse_args()
@@ -158,6 +221,11 @@ def main():
             if not -1 <= args.filter <= api.FilterParams.MAX_RADIUS:
                 sys.exit("render: --filter R takes 0 <= R <= 8")
             filt = api.FilterParams.make(args.filter, args.normal_cos, args.plane_eps, args.spread) if args.filter >= 0 else None
+            if args.temporal:
+                if filt is None or args.distance or args.refined:
+                    sys.exit("render: --temporal F goes with --soft-list N --filter R, without --distance and --refined")
+                return soft_list_temporal(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, filt, args.temporal, args.orbit,
+                                          args.max_length, args.adaptive, args.table, args.colors)
             return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance,
                              args.colors, filt)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
