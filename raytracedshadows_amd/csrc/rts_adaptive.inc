@@ -159,9 +159,7 @@ void shadowMaskAdaptivePacketKernel(TraceParams p) {
 
 hipError_t launchShadowMaskAdaptive(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
     if (!p.mask || p.nsamples < 2 || p.nsamples > 64 || p.nrays == 0 || p.nrays >= p.nsamples) return hipErrorInvalidValue;
-    static const char* const names[2][3] = {
-        { "shadowMaskAdaptivePacketKernel<1,general>", "shadowMaskAdaptivePacketKernel<1,rows>", "shadowMaskAdaptivePacketKernel<1,bands>" },
-        { "shadowMaskAdaptivePacketKernel<4,general>", "shadowMaskAdaptivePacketKernel<4,rows>", "shadowMaskAdaptivePacketKernel<4,bands>" } };
+    static const char* const names[2][3] = RTS_PACKET_NAMES("shadowMaskAdaptivePacketKernel", "");
     return launchLoopFamily(variant, p, stream, name, shadowMaskAdaptiveShareKernel, "shadowMaskAdaptiveShareKernel", names,
                             [&](dim3 grid, auto split, auto geom) {
         constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;

@@ -1006,77 +1006,93 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 }
 
 // ---- the host-pointer entries: the same traces through the context's staging buffers ----------------------------------------------
-// Frames (arguments checked by the caller): only rows [row_begin, row_end) travel -- their positions, map, mask and distances, as a
-// frame of their own, to the device entry of what is being traced.  lights: the rts_light, or for Staged::LightList the rts_light_list;
-// each case below names the type it reads, and nothing else does.  distance: of the distance traces alone, whose mask is optional.
-// probe, refined: of Staged::Adaptive alone; its refined plane (optional) is staged in the distances' buffer, which it does not use.
-// Staged::SoftLightList: lights is the rts_soft_light_list, mask its count planes -- `count` planes of frameH rows in the caller's
-// buffer, of the staged rows alone on the device.  Staged::SoftListAdaptive: the same, with `probes` (one per light) and the refined plane;
-// with `tables` the jittered form, whose hash pixelBase makes that of the caller's frame.  Staged::SoftListDistance: the soft light
-// list's staging with `distance` its distance planes, staged and copied back plane by plane like the counts (mask, optional here).
+// Frames (arguments checked by the caller): only rows [rowBegin, rowEnd) travel -- their positions, map, mask and distances, as a
+// frame of their own, to the device entry of what is being traced.  StagedRows names what a host entry hands over: the first nine
+// members every entry gives, in this order; the others it sets by name, and what it leaves alone is NULL.
 enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive, SoftListDistance };
-static int traceStagedRows(rts_ctx* c, Staged what, const rts_constants* k, const void* lights, const float* positions, const uint8_t* active,
-                           uint32_t W, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask, uint32_t probe = 0,
-                           uint8_t* refined = nullptr, uint32_t frameH = 0, const uint32_t* probes = nullptr,
-                           const uint32_t* tables = nullptr) {
+struct StagedRows {
+    Staged what;
+    const rts_constants* k;
+    const void* lights;                  // the rts_light; Staged::LightList: the rts_light_list; the soft lists: the rts_soft_light_list --
+                                         // each case below names the type it reads, and nothing else does
+    const float* positions;
+    const uint8_t* active;               // the active map, or a list's light map
+    uint32_t W, H, rowBegin, rowEnd;     // the caller's frame: its planes are W * H apart, of the staged rows alone on the device
+    uint8_t* mask = nullptr;             // the mask; a soft list's count planes, `count` of them (optional beside distances)
+    float* distance = nullptr;           // of the distance traces alone; Staged::SoftListDistance: a plane per light, like the counts
+    uint32_t probe = 0;                  // Staged::Adaptive
+    uint8_t* refined = nullptr;          // Staged::Adaptive, Staged::SoftListAdaptive (optional): staged in the distances' buffer
+    const uint32_t* probes = nullptr;    // Staged::SoftListAdaptive: one per light
+    const uint32_t* tables = nullptr;    // ... its jittered form, whose hash pixelBase makes that of the caller's frame
+};
+static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
-    if (row_begin == row_end) return RTS_OK;
+    if (r.rowBegin == r.rowEnd) return RTS_OK;
     RTS_HIP(hipSetDevice(c->device));
-    const uint32_t rows = row_end - row_begin;
-    const size_t first = (size_t)row_begin * W, pixels = (size_t)rows * W;
+    const uint32_t W = r.W, rows = r.rowEnd - r.rowBegin;
+    const size_t first = (size_t)r.rowBegin * W, pixels = (size_t)rows * W, frame = (size_t)W * r.H;
     int s = ensure(&c->d_in, &c->inBytes, pixels * 16);
-    const size_t planes = (what == Staged::SoftLightList || what == Staged::SoftListAdaptive || what == Staged::SoftListDistance)
-                              ? ((const rts_soft_light_list*)lights)->count : 1u;
-    const size_t distPlanes = what == Staged::SoftListDistance ? planes : 1u;
-    if (s == RTS_OK && distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4 * distPlanes);
-    if (s == RTS_OK && refined) s = ensure(&c->d_dist, &c->distBytes, pixels);
-    if (s == RTS_OK && mask) s = ensure(&c->d_out, &c->outBytes, pixels * planes);
-    if (s == RTS_OK && active) s = ensure(&c->d_act, &c->actBytes, pixels);
+    const bool softList = r.what == Staged::SoftLightList || r.what == Staged::SoftListAdaptive || r.what == Staged::SoftListDistance;
+    const size_t planes = softList ? ((const rts_soft_light_list*)r.lights)->count : 1u;
+    const size_t distPlanes = r.what == Staged::SoftListDistance ? planes : 1u;
+    if (s == RTS_OK && r.distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4 * distPlanes);
+    if (s == RTS_OK && r.refined) s = ensure(&c->d_dist, &c->distBytes, pixels);
+    if (s == RTS_OK && r.mask) s = ensure(&c->d_out, &c->outBytes, pixels * planes);
+    if (s == RTS_OK && r.active) s = ensure(&c->d_act, &c->actBytes, pixels);
     if (s != RTS_OK) return s;
-    RTS_HIP(hipMemcpy(c->d_in, positions + first * 4, pixels * 16, hipMemcpyHostToDevice));
-    if (active) RTS_HIP(hipMemcpy(c->d_act, active + first, pixels, hipMemcpyHostToDevice));
-    const uint8_t* d_active = active ? (const uint8_t*)c->d_act : nullptr;
-    uint8_t* d_mask = mask ? (uint8_t*)c->d_out : nullptr;
+    RTS_HIP(hipMemcpy(c->d_in, r.positions + first * 4, pixels * 16, hipMemcpyHostToDevice));
+    if (r.active) RTS_HIP(hipMemcpy(c->d_act, r.active + first, pixels, hipMemcpyHostToDevice));
+    const rts_constants* const k = r.k;
+    const rts_light* const light = (const rts_light*)r.lights;
+    const rts_soft_light_list* const softLights = (const rts_soft_light_list*)r.lights;
+    const uint8_t* d_active = r.active ? (const uint8_t*)c->d_act : nullptr;
+    uint8_t* d_mask = r.mask ? (uint8_t*)c->d_out : nullptr;
+    uint8_t* d_refined = r.refined ? (uint8_t*)c->d_dist : nullptr;
     const float* d_in = (const float*)c->d_in;
     float* d_dist = (float*)c->d_dist;
     // per-pixel jitter hashes the pixel's index in the caller's frame (sampleIndex, rts_kernels.hip: the one reader, and only of a
     // light with a table -- several samples, so in a mask trace or a soft distance trace; of the lists the jittered one alone reads it)
-    c->pixelBase = row_begin * W;
-    switch (what) {
+    c->pixelBase = r.rowBegin * W;
+    switch (r.what) {
     case Staged::Mask:
-        s = rts_trace_shadow_mask_active_device(c, k, (const rts_light*)lights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
+        s = rts_trace_shadow_mask_active_device(c, k, light, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
     case Staged::Distance:
-        s = rts_trace_shadow_distance_device(c, k, (const rts_light*)lights, d_in, d_active, W, rows, 0, rows, d_dist, d_mask, nullptr); break;
+        s = rts_trace_shadow_distance_device(c, k, light, d_in, d_active, W, rows, 0, rows, d_dist, d_mask, nullptr); break;
     case Staged::SoftDistance:
-        s = rts_trace_soft_distance_device(c, k, (const rts_light*)lights, d_in, d_active, W, rows, 0, rows, d_dist, d_mask, nullptr); break;
+        s = rts_trace_soft_distance_device(c, k, light, d_in, d_active, W, rows, 0, rows, d_dist, d_mask, nullptr); break;
     case Staged::LightList:
-        s = rts_trace_light_list_device(c, k, (const rts_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
+        s = rts_trace_light_list_device(c, k, (const rts_light_list*)r.lights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
     case Staged::Adaptive:
-        s = rts_trace_shadow_mask_adaptive_device(c, k, (const rts_light*)lights, d_in, d_active, W, rows, 0, rows, probe, d_mask,
-                                                  refined ? (uint8_t*)c->d_dist : nullptr, nullptr); break;
+        s = rts_trace_shadow_mask_adaptive_device(c, k, light, d_in, d_active, W, rows, 0, rows, r.probe, d_mask, d_refined, nullptr); break;
     case Staged::SoftLightList:
-        s = rts_trace_soft_light_list_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
+        s = rts_trace_soft_light_list_device(c, k, softLights, d_in, d_active, W, rows, 0, rows, d_mask, nullptr); break;
     case Staged::SoftListAdaptive:
-        s = rts_trace_soft_light_list_jittered_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_mask, probes,
-                                                      tables, refined ? (uint8_t*)c->d_dist : nullptr, nullptr); break;
-    case Staged::SoftListDistance:
-        s = rts_trace_soft_light_list_distance_device(c, k, (const rts_soft_light_list*)lights, d_in, d_active, W, rows, 0, rows, d_dist, d_mask,
+        s = rts_trace_soft_light_list_jittered_device(c, k, softLights, d_in, d_active, W, rows, 0, rows, d_mask, r.probes, r.tables, d_refined,
                                                       nullptr); break;
+    case Staged::SoftListDistance:
+        s = rts_trace_soft_light_list_distance_device(c, k, softLights, d_in, d_active, W, rows, 0, rows, d_dist, d_mask, nullptr); break;
     }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
-    for (size_t l = 0; distance && l < distPlanes; ++l)
-        RTS_HIP(hipMemcpy(distance + l * ((size_t)W * frameH) + first, (const float*)c->d_dist + l * pixels, pixels * 4, hipMemcpyDeviceToHost));
-    if (refined) RTS_HIP(hipMemcpy(refined + first, c->d_dist, pixels, hipMemcpyDeviceToHost));
-    for (size_t l = 0; mask && l < planes; ++l)
-        RTS_HIP(hipMemcpy(mask + l * ((size_t)W * frameH) + first, (const uint8_t*)c->d_out + l * pixels, pixels, hipMemcpyDeviceToHost));
+    for (size_t l = 0; r.distance && l < distPlanes; ++l)
+        RTS_HIP(hipMemcpy(r.distance + l * frame + first, (const float*)c->d_dist + l * pixels, pixels * 4, hipMemcpyDeviceToHost));
+    if (r.refined) RTS_HIP(hipMemcpy(r.refined + first, c->d_dist, pixels, hipMemcpyDeviceToHost));
+    for (size_t l = 0; r.mask && l < planes; ++l)
+        RTS_HIP(hipMemcpy(r.mask + l * frame + first, (const uint8_t*)c->d_out + l * pixels, pixels, hipMemcpyDeviceToHost));
     return RTS_OK;
+}
+
+// The frame of a soft list's host entry: its rows, and the device forms' limit of 2^31 pixels, said before anything is staged.
+static bool stagedListFrameOk(uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end) {
+    return rts::frameRowsOk(W, H, row_begin, row_end) && (uint64_t)W * H <= (1ull << 31);
 }
 
 int rts_trace_shadow_mask_active(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
                                  uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
     if (!c || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
-    return traceStagedRows(c, Staged::Mask, k, light, positions, active, W, row_begin, row_end, nullptr, mask);
+    StagedRows r{ Staged::Mask, k, light, positions, active, W, H, row_begin, row_end };
+    r.mask = mask;
+    return traceStagedRows(c, r);
 }
 
 int rts_trace_shadow_mask(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions,
@@ -1088,30 +1104,38 @@ int rts_trace_shadow_distance(rts_ctx* c, const rts_constants* k, const rts_ligh
                               uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
     if (!c || !k || !positions || !distance || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
     if (!rts::hardLightOk(light)) return RTS_ERR_INVALID_ARG;
-    return traceStagedRows(c, Staged::Distance, k, light, positions, active, W, row_begin, row_end, distance, mask);
+    StagedRows r{ Staged::Distance, k, light, positions, active, W, H, row_begin, row_end };
+    r.distance = distance; r.mask = mask;
+    return traceStagedRows(c, r);
 }
 
 int rts_trace_soft_distance(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
                             uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, float* distance, uint8_t* mask) {
     if (!c || !k || !positions || !distance || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
     if (!rts::softLightOk(light)) return RTS_ERR_INVALID_ARG;
-    return traceStagedRows(c, Staged::SoftDistance, k, light, positions, active, W, row_begin, row_end, distance, mask);
+    StagedRows r{ Staged::SoftDistance, k, light, positions, active, W, H, row_begin, row_end };
+    r.distance = distance; r.mask = mask;
+    return traceStagedRows(c, r);
 }
 
 // ---- light lists (include/rts.h): up to 8 hard lights in one dispatch, one bit per light in the mask byte ----------------------------
+// What the hard and the soft list both say in front of their lights: the count in nsamples, the map in the active map's slot.
+static void setListHeader(TraceParams& p, const rts_constants* k, uint32_t count, const uint8_t* d_lights_map) {
+    p.activeMap = d_lights_map;
+    for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
+    p.lightType = RTS_LIGHT_DIRECTIONAL;               // (not read: every light carries its own type)
+    p.nsamples = count;
+    p.lightTable = 0;
+    for (int i = 0; i < 3; ++i) p.light[i] = 0.0f;
+}
+
 // One launch of a light list kernel (rts_light_list.inc) with the geometry, the family rule and the tail of a distance trace.  The
-// list travels in the argument block's 64 sample offsets: light l in offsets[l] = {x, y, z, 0.0f directional / 1.0f point}, the
-// count in nsamples, the map in the active map's slot.
+// list travels in the argument block's 64 sample offsets: light l in offsets[l] = {x, y, z, 0.0f directional / 1.0f point}.
 static int traceLightListImpl(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* d_positions,
                               const uint8_t* d_lights_map, const Dispatch& g, uint8_t* d_mask, void* stream) {
     TraceParams p; uint32_t rows = 0; int s;
     if (beginFrame(c, k, d_positions, d_mask, d_mask && rts::lightListOk(list), g, p, &rows, &s) != Begin::Go) return s;
-    p.activeMap = d_lights_map;
-    for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
-    p.lightType = RTS_LIGHT_DIRECTIONAL;               // (not read: every light carries its own type)
-    p.nsamples = list->count;
-    p.lightTable = 0;
-    for (int i = 0; i < 3; ++i) p.light[i] = 0.0f;
+    setListHeader(p, k, list->count, d_lights_map);
     for (uint32_t l = 0; l < list->count; ++l) {
         for (int i = 0; i < 3; ++i) p.offsets[l][i] = list->lights[l].xyz[i];
         p.offsets[l][3] = list->lights[l].type == RTS_LIGHT_POINT ? 1.0f : 0.0f;
@@ -1137,28 +1161,17 @@ int rts_trace_light_list_stripes_device(rts_ctx* c, const rts_constants* k, cons
 int rts_trace_light_list(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* positions, const uint8_t* lights_map,
                          uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* mask) {
     if (!c || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
-    return traceStagedRows(c, Staged::LightList, k, list, positions, lights_map, W, row_begin, row_end, nullptr, mask);
+    StagedRows r{ Staged::LightList, k, list, positions, lights_map, W, H, row_begin, row_end };
+    r.mask = mask;
+    return traceStagedRows(c, r);
 }
 
 // ---- soft light lists (include/rts.h): up to 8 lights, hard or soft, in one dispatch, one count plane per light -----------------------
 // The list in the argument block, what the soft list trace and its adaptive form both launch with: it travels in the 64 sample offsets
-// (rts_soft_light_list.h) -- the shared table in the first 48, two slots per light behind them --, the count in nsamples, the map in the
-// active map's slot.
+// (rts_soft_light_list.h) -- the shared table in the first 48, two slots per light behind them -- behind the lists' header.
 static void setSoftList(TraceParams& p, const rts_constants* k, const rts_soft_light_list* list, const uint8_t* d_lights_map) {
-    p.activeMap = d_lights_map;
-    for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
-    p.lightType = RTS_LIGHT_DIRECTIONAL;               // (not read: every light carries its own type)
-    p.nsamples = list->count;
-    p.lightTable = 0;
-    for (int i = 0; i < 3; ++i) p.light[i] = 0.0f;
-    static_assert(sizeof(list->offsets) == sizeof(float) * 4 * RTS_SOFT_LIST_OFFSETS && RTS_SOFT_LIST_OFFSETS + 2 * RTS_MAX_LIST_LIGHTS == 64,
-                  "48 sample slots and two slots per light fill TraceParams::offsets");
-    memcpy(p.offsets, list->offsets, sizeof(list->offsets));
-    for (uint32_t l = 0; l < list->count; ++l) {
-        const rts_soft_light_entry& e = list->lights[l];
-        const bool soft = e.nsamples >= 2;
-        rts::setSoftListEntry(p, l, e.type, soft ? e.nsamples : 1u, soft ? e.first : 0u, e.radius, e.xyz);
-    }
+    setListHeader(p, k, list->count, d_lights_map);
+    rts::setSoftList(p.offsets, list);
 }
 
 // One launch of a soft light list kernel (rts_soft_light_list.inc) with the geometry, the family rule and the tail of a distance trace.
@@ -1188,9 +1201,10 @@ int rts_trace_soft_light_list_stripes_device(rts_ctx* c, const rts_constants* k,
 // planes come back to the caller's planes of H rows.
 int rts_trace_soft_light_list(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* positions,
                               const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* counts) {
-    if (!c || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
-    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
-    return traceStagedRows(c, Staged::SoftLightList, k, list, positions, lights_map, W, row_begin, row_end, nullptr, counts, 0, nullptr, H);
+    if (!c || !k || !positions || !counts || !stagedListFrameOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    StagedRows r{ Staged::SoftLightList, k, list, positions, lights_map, W, H, row_begin, row_end };
+    r.mask = counts;
+    return traceStagedRows(c, r);
 }
 
 // ---- soft light list distance (include/rts.h): a soft light list with the nearest blocker per light beside its count --------------
@@ -1226,9 +1240,10 @@ int rts_trace_soft_light_list_distance_stripes_device(rts_ctx* c, const rts_cons
 int rts_trace_soft_light_list_distance(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* positions,
                                        const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
                                        float* distances, uint8_t* counts) {
-    if (!c || !k || !positions || !distances || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
-    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
-    return traceStagedRows(c, Staged::SoftListDistance, k, list, positions, lights_map, W, row_begin, row_end, distances, counts, 0, nullptr, H);
+    if (!c || !k || !positions || !distances || !stagedListFrameOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    StagedRows r{ Staged::SoftListDistance, k, list, positions, lights_map, W, H, row_begin, row_end };
+    r.distance = distances; r.mask = counts;
+    return traceStagedRows(c, r);
 }
 
 // ---- adaptive soft light lists (include/rts.h): a soft light list with a probe count per light, its penumbra alone refined ---------
@@ -1243,12 +1258,12 @@ static int traceSoftListAdaptiveImpl(rts_ctx* c, const rts_constants* k, const r
     TraceParams p; uint32_t rows = 0; int s;
     if (beginFrame(c, k, d_positions, d_counts, d_counts && rts::softListTablesOk(list, probes, tables), g, p, &rows, &s) != Begin::Go) return s;
     setSoftList(p, k, list, d_lights_map);
-    for (uint32_t l = 0; l < list->count; ++l) rts::setSoftListProbe(p, l, probes[l]);
+    for (uint32_t l = 0; l < list->count; ++l) rts::setSoftListProbe(p.offsets, l, probes[l]);
     p.out = d_refined;
     if (!rts::softListHasTable(list, tables))
         return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::softListAdaptiveTraces,
                             rts::launchShadowSoftLightListAdaptive, stream);
-    for (uint32_t l = 0; l < list->count; ++l) rts::setSoftListTable(p, l, tables[l]);
+    for (uint32_t l = 0; l < list->count; ++l) rts::setSoftListTable(p.offsets, l, tables[l]);
     return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::softListJitterTraces, rts::launchShadowSoftLightListJittered,
                         stream);
 }
@@ -1269,15 +1284,11 @@ int rts_trace_soft_light_list_adaptive_stripes_device(rts_ctx* c, const rts_cons
                                      probes, d_refined, stream);
 }
 
-// The host form: the soft list's staging, with the refined rows staged as Staged::Adaptive stages its own.
+// The host form: the jittered list's without tables.
 int rts_trace_soft_light_list_adaptive(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* positions,
                                        const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
                                        uint8_t* counts, const uint32_t* probes, uint8_t* refined) {
-    if (!c || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListProbesOk(list, probes))
-        return RTS_ERR_INVALID_ARG;
-    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
-    return traceStagedRows(c, Staged::SoftListAdaptive, k, list, positions, lights_map, W, row_begin, row_end, nullptr, counts, 0, refined, H,
-                           probes);
+    return rts_trace_soft_light_list_jittered(c, k, list, positions, lights_map, W, H, row_begin, row_end, counts, probes, nullptr, refined);
 }
 
 // ---- jittered soft light lists (include/rts.h): the adaptive list with a per-pixel jitter table per light ----------------------------
@@ -1298,23 +1309,25 @@ int rts_trace_soft_light_list_jittered_stripes_device(rts_ctx* c, const rts_cons
                                      probes, d_refined, stream, tables);
 }
 
-// The host form: the adaptive list's staging; pixelBase, which traceStagedRows sets around the device call, makes the hash that of
-// the caller's frame although the rows travel as a frame of their own.
+// The host form: the soft list's staging, with the refined rows staged as Staged::Adaptive stages its own; pixelBase, which
+// traceStagedRows sets around the device call, makes the hash that of the caller's frame although the rows travel as a frame of their own.
 int rts_trace_soft_light_list_jittered(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* positions,
                                        const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
                                        uint8_t* counts, const uint32_t* probes, const uint32_t* tables, uint8_t* refined) {
-    if (!c || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListTablesOk(list, probes, tables))
+    if (!c || !k || !positions || !counts || !stagedListFrameOk(W, H, row_begin, row_end) || !rts::softListTablesOk(list, probes, tables))
         return RTS_ERR_INVALID_ARG;
-    if ((uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;    // (the device forms' limit, said before anything is staged)
-    return traceStagedRows(c, Staged::SoftListAdaptive, k, list, positions, lights_map, W, row_begin, row_end, nullptr, counts, 0, refined, H,
-                           probes, tables);
+    StagedRows r{ Staged::SoftListAdaptive, k, list, positions, lights_map, W, H, row_begin, row_end };
+    r.mask = counts; r.refined = refined; r.probes = probes; r.tables = tables;
+    return traceStagedRows(c, r);
 }
 
 int rts_trace_shadow_mask_adaptive(rts_ctx* c, const rts_constants* k, const rts_light* light, const float* positions, const uint8_t* active,
                                    uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint32_t probe, uint8_t* mask, uint8_t* refined) {
     if (!c || !k || !positions || !mask || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
     if (!rts::adaptiveLightOk(light, probe)) return RTS_ERR_INVALID_ARG;
-    return traceStagedRows(c, Staged::Adaptive, k, light, positions, active, W, row_begin, row_end, nullptr, mask, probe, refined);
+    StagedRows r{ Staged::Adaptive, k, light, positions, active, W, H, row_begin, row_end };
+    r.mask = mask; r.probe = probe; r.refined = refined;
+    return traceStagedRows(c, r);
 }
 
 // Rays (the caller's arguments are checked): occlusion bytes to `out`, or distances to `out_t` where out is NULL.

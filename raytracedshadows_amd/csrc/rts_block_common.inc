@@ -127,6 +127,10 @@ static hipError_t launchPacketGeom(const TraceParams& p, const char* const (&nam
     else launch(std::integral_constant<int, 0>{});
     return hipGetLastError();
 }
+// The names of a family's packet kernels as launchLoopFamily takes them, [SPLIT == 4][GEOM], from the kernel's stem and what follows the
+// geometry ("" or ",jitter"): "stem<1,general>" .. "stem<4,bands>".
+#define RTS_PACKET_NAMES(stem, more) { { stem "<1,general" more ">", stem "<1,rows" more ">", stem "<1,bands" more ">" }, \
+                                       { stem "<4,general" more ">", stem "<4,rows" more ">", stem "<4,bands" more ">" } }
 // The families with a sample or light loop, after their argument guards: the lane-per-ray kernel, or the packet kernel with one
 // wave or four per tile.  packet(grid, integral_constant SPLIT, integral_constant GEOM) launches that instantiation; names[SPLIT == 4][GEOM].
 template <class Packet>

@@ -161,12 +161,8 @@ static int launchFilter(rts_ctx* ctx, const FilterList& f, const float* d_positi
     const FilterGeometry g = filterGeometry(f, HARD, DIST);
     const dim3 grid((W + 15) / 16, (H + (uint32_t)g.rows - 1) / (uint32_t)g.rows);
     if (grid.y > 65535u) return RTS_ERR_INVALID_ARG;
-    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
-    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
-    hipLaunchKernelGGL((filterListKernel<HARD, DIST>), grid, dim3(16, (unsigned)g.rows), g.bytes, (hipStream_t)stream, f, d_positions,
-                       d_normals, d_lights_map, d_planes, (const uint32_t*)d_distances, (int)W, (int)H, g.pitch, d_visibility);
-    e = hipGetLastError();
-    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+    return launchPass(ctx, stream, grid, dim3(16, (unsigned)g.rows), g.bytes, filterListKernel<HARD, DIST>, f, d_positions, d_normals,
+                      d_lights_map, d_planes, (const uint32_t*)d_distances, (int)W, (int)H, g.pitch, d_visibility);
 }
 
 // The visibility combine: combineListKernel's frame (one pixel per lane) over float planes.
@@ -217,11 +213,7 @@ extern "C" int rtsh_combine_visibility_list_device(rts_ctx* ctx, const rts_const
     rts_harness::CombineList f;
     const int s = rts_harness::makeCombineList(k, list, colors, d_positions != nullptr, &f);
     if (s != RTS_OK) return s;
-    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
-    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
     const uint64_t n = (uint64_t)W * H;
-    hipLaunchKernelGGL(rts_harness::combineVisibilityKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f,
-                       d_positions, d_normals, d_lights_map, d_visibility, n, d_rgb);
-    e = hipGetLastError();
-    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+    return rts_harness::launchPerPixel(ctx, stream, n, rts_harness::combineVisibilityKernel, f, d_positions, d_normals, d_lights_map,
+                                       d_visibility, n, d_rgb);
 }

@@ -130,9 +130,7 @@ void shadowLightListPacketKernel(TraceParams p) {
 
 hipError_t launchShadowLightList(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
     if (!p.mask || p.nsamples < 1 || p.nsamples > 8) return hipErrorInvalidValue;
-    static const char* const names[2][3] = {
-        { "shadowLightListPacketKernel<1,general>", "shadowLightListPacketKernel<1,rows>", "shadowLightListPacketKernel<1,bands>" },
-        { "shadowLightListPacketKernel<4,general>", "shadowLightListPacketKernel<4,rows>", "shadowLightListPacketKernel<4,bands>" } };
+    static const char* const names[2][3] = RTS_PACKET_NAMES("shadowLightListPacketKernel", "");
     return launchLoopFamily(variant, p, stream, name, shadowLightListShareKernel, "shadowLightListShareKernel", names,
                             [&](dim3 grid, auto split, auto geom) {
         constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;

@@ -12,6 +12,21 @@ extern "C" int rts_ctx_device_ordinal(rts_ctx* ctx);
 namespace rts_harness {
 Camera makeCamera(const float eye[3], const float target[3], float fovy, uint32_t W, uint32_t H);
 
+// The launch of every scene pass, after the entry's own argument checks: the context's device, the kernel, the RTS_* status.
+template <class... Params, class... Args>
+static int launchPass(rts_ctx* ctx, void* stream, dim3 grid, dim3 block, size_t ldsBytes, void (*kernel)(Params...), Args... args) {
+    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
+    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
+    hipLaunchKernelGGL(kernel, grid, block, ldsBytes, (hipStream_t)stream, args...);
+    e = hipGetLastError();
+    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+}
+// ... of a pass of one pixel per lane: 256 lanes per workgroup over n pixels (n travels among the kernel's own arguments too).
+template <class... Params, class... Args>
+static int launchPerPixel(rts_ctx* ctx, void* stream, uint64_t n, void (*kernel)(Params...), Args... args) {
+    return launchPass(ctx, stream, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, kernel, args...);
+}
+
 // One wave = one 8x8 tile of primary rays, walked as a PACKET: the rays of a tile are coherent, every index only grows, and
 // every way out of a subtree leads to its root's miss link -- so the smallest index any ray stands on is wave-uniform
 // (the argument of the shadow kernel): the node comes through the scalar cache once per wave, and each ray
@@ -110,13 +125,8 @@ __global__ __launch_bounds__(256) void combineListKernel(CombineList f, const fl
 template <bool HARD>
 static int launchCombineList(rts_ctx* ctx, const CombineList& f, const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
                              const uint8_t* d_planes, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream) {
-    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
-    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
     const uint64_t n = (uint64_t)W * H;
-    hipLaunchKernelGGL(combineListKernel<HARD>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f, d_positions,
-                       d_normals, d_lights_map, d_planes, n, d_rgb);
-    e = hipGetLastError();
-    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+    return launchPerPixel(ctx, stream, n, combineListKernel<HARD>, f, d_positions, d_normals, d_lights_map, d_planes, n, d_rgb);
 }
 } // namespace rts_harness
 
@@ -127,13 +137,8 @@ extern "C" int rtsh_combine_device(rts_ctx* ctx, const rts_constants* k, const r
     rts_harness::CombineParams c;
     int s = rts_harness::makeCombineParams(k, light, d_positions != nullptr, &c);
     if (s != RTS_OK) return s;
-    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
-    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
     const uint64_t n = (uint64_t)W * H;
-    hipLaunchKernelGGL(rts_harness::combineKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c,
-                       d_positions, d_normals, d_mask, n, d_rgb);
-    e = hipGetLastError();
-    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+    return rts_harness::launchPerPixel(ctx, stream, n, rts_harness::combineKernel, c, d_positions, d_normals, d_mask, n, d_rgb);
 }
 
 extern "C" int rtsh_facing_active_device(rts_ctx* ctx, const rts_constants* k, const rts_light* light, const float* d_positions,
@@ -142,13 +147,8 @@ extern "C" int rtsh_facing_active_device(rts_ctx* ctx, const rts_constants* k, c
     rts_harness::CombineParams c;
     int s = rts_harness::makeCombineParams(k, light, d_positions != nullptr, &c);
     if (s != RTS_OK) return s;
-    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
-    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
     const uint64_t n = (uint64_t)W * H;
-    hipLaunchKernelGGL(rts_harness::facingKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, c,
-                       d_positions, d_normals, n, d_active);
-    e = hipGetLastError();
-    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+    return rts_harness::launchPerPixel(ctx, stream, n, rts_harness::facingKernel, c, d_positions, d_normals, n, d_active);
 }
 
 extern "C" int rtsh_facing_lights_device(rts_ctx* ctx, const rts_constants* k, const rts_light_list* list, const float* d_positions,
@@ -157,13 +157,8 @@ extern "C" int rtsh_facing_lights_device(rts_ctx* ctx, const rts_constants* k, c
     rts_harness::FacingLights f;
     int s = rts_harness::makeFacingLights(k, list, d_positions != nullptr, &f);
     if (s != RTS_OK) return s;
-    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
-    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
     const uint64_t n = (uint64_t)W * H;
-    hipLaunchKernelGGL(rts_harness::facingLightsKernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f,
-                       d_positions, d_normals, n, d_lights_map);
-    e = hipGetLastError();
-    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+    return rts_harness::launchPerPixel(ctx, stream, n, rts_harness::facingLightsKernel, f, d_positions, d_normals, n, d_lights_map);
 }
 
 extern "C" int rtsh_primary_gbuffer_device(rts_ctx* ctx, const float eye[3], const float target[3], float fovy,
@@ -172,14 +167,9 @@ extern "C" int rtsh_primary_gbuffer_device(rts_ctx* ctx, const float eye[3], con
     if (H > RTSH_GBUFFER_MAX_HEIGHT) return RTS_ERR_INVALID_ARG;        // the grid's y extent: refused here, not by the launch
     const void* bvh = rts_ctx_device_bvh(ctx);
     if (!bvh) return RTS_ERR_NO_BVH;
-    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
-    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
     const rts_harness::Camera cam = rts_harness::makeCamera(eye, target, fovy, W, H);
-    dim3 grid((W + 7) / 8, (H + 7) / 8), block(64);
-    hipLaunchKernelGGL(rts_harness::gbufferKernel, grid, block, 0, (hipStream_t)stream, (const uint32_t*)bvh, cam, W, H,
-                       d_positions, d_normals);
-    e = hipGetLastError();
-    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+    return rts_harness::launchPass(ctx, stream, dim3((W + 7) / 8, (H + 7) / 8), dim3(64), 0, rts_harness::gbufferKernel, (const uint32_t*)bvh,
+                                   cam, W, H, d_positions, d_normals);
 }
 
 // The combine pass of a light list on the GPU (include/rts_scene.h): one kernel, the list, the colours and the constants by value.

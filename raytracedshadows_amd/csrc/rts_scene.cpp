@@ -32,6 +32,29 @@ Camera makeCamera(const float eye[3], const float target[3], float fovy, uint32_
     c.aspect = (float)W / (float)H;
     return c;
 }
+
+namespace {
+// body(i) for every i < n, in chunks of `chunk` dealt over `threads` threads (0: the machine's), 64 at the most
+template <class F>
+void parallelFor(size_t n, size_t chunk, int threads, F&& body) {
+    int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
+    if (nt < 1) nt = 1;
+    if (nt > 64) nt = 64;
+    std::atomic<size_t> next{ 0 };
+    auto work = [&]() {
+        for (;;) {
+            const size_t b = next.fetch_add(chunk);
+            if (b >= n) break;
+            const size_t e = b + chunk < n ? b + chunk : n;
+            for (size_t i = b; i < e; ++i) body(i);
+        }
+    };
+    std::vector<std::thread> pool;
+    for (int t = 1; t < nt && (size_t)t * chunk < n; ++t) pool.emplace_back(work);
+    work();
+    for (auto& t : pool) t.join();
+}
+} // namespace
 } // namespace rts_harness
 
 extern "C" int rtsh_primary_gbuffer(const rts_vec4u* packed, size_t count, const float eye[3], const float target[3],
@@ -43,28 +66,16 @@ extern "C" int rtsh_primary_gbuffer(const rts_vec4u* packed, size_t count, const
     if (s != RTS_OK) return s;
     const Camera cam = makeCamera(eye, target, fovy, W, H);
     const uint32_t* bvh = (const uint32_t*)packed;
-    int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if (nt > 64) nt = 64;
-    std::atomic<uint32_t> nextRow{ 0 };
-    std::atomic<uint64_t> hits{ 0 };
-    auto work = [&]() {
+    std::atomic<uint64_t> hits{ 0 };                                    // (integer adds: exact, whichever thread took which row)
+    parallelFor(H, 1, threads, [&](size_t y) {
         uint64_t local = 0;
-        for (;;) {
-            uint32_t y = nextRow.fetch_add(1);
-            if (y >= H) break;
-            for (uint32_t x = 0; x < W; ++x) {
-                size_t i = ((size_t)y * W + x) * 4;
-                shadePixel(bvh, cam, x, y, W, H, positions + i, normals ? normals + i : nullptr);
-                local += positions[i + 3] != 0.0f;
-            }
+        for (uint32_t x = 0; x < W; ++x) {
+            const size_t i = (y * W + x) * 4;
+            shadePixel(bvh, cam, x, (uint32_t)y, W, H, positions + i, normals ? normals + i : nullptr);
+            local += positions[i + 3] != 0.0f;
         }
         hits.fetch_add(local);
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nt; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
+    });
     if (hit_count) *hit_count = hits.load();
     return RTS_OK;
 }
@@ -193,26 +204,6 @@ inline uint32_t rayDistanceBits(const uint32_t* bvh, const DRay& r) {
     }
     return best;
 }
-
-template <class F>
-void parallelFor(size_t n, size_t chunk, int threads, F&& body) {
-    int nt = threads > 0 ? threads : (int)std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if (nt > 64) nt = 64;
-    std::atomic<size_t> next{ 0 };
-    auto work = [&]() {
-        for (;;) {
-            const size_t b = next.fetch_add(chunk);
-            if (b >= n) break;
-            const size_t e = b + chunk < n ? b + chunk : n;
-            for (size_t i = b; i < e; ++i) body(i);
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < nt && (size_t)t * chunk < n; ++t) pool.emplace_back(work);
-    work();
-    for (auto& t : pool) t.join();
-}
 } // namespace
 } // namespace rts_harness
 
@@ -336,16 +327,24 @@ extern "C" int rtsh_shadow_mask_adaptive(const rts_vec4u* packed, size_t count_v
 // The definition of include/rts.h as a straight loop over (pixel, light): light l's ray and one-ray distance as rtsh_shadow_distance
 // takes them for that light alone, its bit set where the distance is +Inf.
 namespace rts_harness {
+namespace {
+// One light of a list as makeCombineParams reads it: its type, its sample count and its position or direction.
+rts_light lightOf(uint32_t type, uint32_t nsamples, const float* xyz) {
+    rts_light one;
+    memset(&one, 0, sizeof(one));
+    one.type = type;
+    one.nsamples = nsamples;
+    for (int i = 0; i < 3; ++i) one.xyz[i] = xyz[i];
+    return one;
+}
+} // namespace
+
 // Shared by the host and device facing passes: one CombineParams per light, as makeCombineParams condenses that light alone.
 int makeFacingLights(const rts_constants* k, const rts_light_list* list, bool havePositions, FacingLights* out) {
     if (!k || !out || !rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
     out->count = list->count;
     for (uint32_t l = 0; l < list->count; ++l) {
-        rts_light one;
-        memset(&one, 0, sizeof(one));
-        one.type = list->lights[l].type;
-        one.nsamples = 1;
-        for (int i = 0; i < 3; ++i) one.xyz[i] = list->lights[l].xyz[i];
+        const rts_light one = lightOf(list->lights[l].type, 1u, list->lights[l].xyz);
         const int s = makeCombineParams(k, &one, havePositions, &out->light[l]);
         if (s != RTS_OK) return s;
     }
@@ -380,98 +379,28 @@ extern "C" int rtsh_light_list(const rts_vec4u* packed, size_t count_vec4, const
     return RTS_OK;
 }
 
-// ---- soft light lists on the host (include/rts_scene.h): the checker of rts_trace_soft_light_list* ----
-// The definition of include/rts.h as a straight loop over (pixel, light, sample): sample j of light l aims at xyz + radius *
-// offsets[first + j] -- the product rounded on its own (this file is built without FMA contraction), then frameDistance's add -- and a
-// hard entry at xyz as given; the plane's byte counts the samples whose one-ray distance is +Inf.
-extern "C" int rtsh_soft_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
-                                    const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
-                                    uint32_t row_end, uint8_t* counts, int threads) {
-    if (!packed || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
-    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
-    if (s != RTS_OK) return s;
-    const uint32_t* bvh = (const uint32_t*)packed;
-    const uint32_t below = (1u << list->count) - 1u;
-    const size_t first = (size_t)row_begin * W, plane = (size_t)W * H;
-    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t n) {
-        const size_t i = first + n;
-        const uint32_t bits = (lights_map ? lights_map[i] : 0xFFu) & below;
-        const float* q = positions + i * 4;                              // (not read where bits == 0)
-        for (uint32_t l = 0; l < list->count; ++l) {
-            uint32_t lit = 0;
-            if ((bits >> l) & 1u) {
-                const rts_soft_light_entry& e = list->lights[l];
-                const uint32_t ns = e.nsamples > 1 ? e.nsamples : 1u;
-                for (uint32_t j = 0; j < ns; ++j) {
-                    V3 L{ e.xyz[0], e.xyz[1], e.xyz[2] };
-                    if (ns > 1) {
-                        const float* o = list->offsets[e.first + j];
-                        const float ox = e.radius * o[0], oy = e.radius * o[1], oz = e.radius * o[2];
-                        L.x = L.x + ox; L.y = L.y + oy; L.z = L.z + oz;
-                    }
-                    const uint32_t one = rayDistanceBits(bvh, shadowRay(k->cameraPosition, V3{ q[0], q[1], q[2] }, e.type, L));
-                    lit += one == 0x7F800000u ? 1u : 0u;                 // comp:148, per sample
-                }
-            }
-            counts[l * plane + i] = (uint8_t)lit;                        // comp:150
-        }
-    });
-    return RTS_OK;
+// ---- soft light lists on the host (include/rts_scene.h): the checker of rts_trace_soft_light_list*, their distance, adaptive and
+// jittered forms ----
+// The definition of include/rts.h as ONE straight loop over (pixel, light, sample), every form a thin caller of it:
+//   the aim      a sample of a soft entry aims at xyz + radius * offsets[at] -- the product rounded on its own (this file is built
+//                without FMA contraction), then frameDistance's add --, a hard entry at xyz as given;
+//   counts       the plane's byte counts the samples whose one-ray distance is +Inf;
+//   distances    frameDistance's integer minimum per light, +0 where the map's bit is clear;
+//   probes       per light rtsh_shadow_mask_adaptive's decision after the probe's samples, `refined` the lights that walked them all;
+//   tables       sampleIndex(T_l, j, pixel) in front of the offset; without tables sampleIndex(0, j, .) is j.
+// NULL for distances, counts, probes, tables or refined is the trace without them.
+namespace rts_harness {
+namespace {
+inline V3 softListAim(const rts_soft_light_entry& e, const float (*offsets)[4], uint32_t at) {
+    const float* o = offsets[at];
+    const float ox = e.radius * o[0], oy = e.radius * o[1], oz = e.radius * o[2];
+    return V3{ e.xyz[0] + ox, e.xyz[1] + oy, e.xyz[2] + oz };
 }
 
-// ---- soft light list distance on the host (include/rts_scene.h): the checker of rts_trace_soft_light_list_distance* ----
-// The definition of include/rts.h as a straight loop over (pixel, light, sample): rtsh_soft_light_list's aim and ray, frameDistance's
-// integer minimum and count per light.
-extern "C" int rtsh_soft_light_list_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
-                                             const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
-                                             uint32_t row_end, float* distances, uint8_t* counts, int threads) {
-    if (!packed || !k || !positions || !distances || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
-    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
-    if (s != RTS_OK) return s;
-    const uint32_t* bvh = (const uint32_t*)packed;
-    const uint32_t below = (1u << list->count) - 1u;
-    const size_t first = (size_t)row_begin * W, plane = (size_t)W * H;
-    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t n) {
-        const size_t i = first + n;
-        const uint32_t bits = (lights_map ? lights_map[i] : 0xFFu) & below;
-        const float* q = positions + i * 4;                              // (not read where bits == 0)
-        for (uint32_t l = 0; l < list->count; ++l) {
-            uint32_t best = 0u, lit = 0;                                 // (+0.0f and 0 where the map's bit is clear)
-            if ((bits >> l) & 1u) {
-                const rts_soft_light_entry& e = list->lights[l];
-                const uint32_t ns = e.nsamples > 1 ? e.nsamples : 1u;
-                best = 0x7F800000u;
-                for (uint32_t j = 0; j < ns; ++j) {
-                    V3 L{ e.xyz[0], e.xyz[1], e.xyz[2] };
-                    if (ns > 1) {
-                        const float* o = list->offsets[e.first + j];
-                        const float ox = e.radius * o[0], oy = e.radius * o[1], oz = e.radius * o[2];
-                        L.x = L.x + ox; L.y = L.y + oy; L.z = L.z + oz;
-                    }
-                    const uint32_t one = rayDistanceBits(bvh, shadowRay(k->cameraPosition, V3{ q[0], q[1], q[2] }, e.type, L));
-                    lit += one == 0x7F800000u ? 1u : 0u;                 // comp:148, per sample
-                    if (one < best) best = one;
-                }
-            }
-            distances[l * plane + i] = asFloat(best);
-            if (counts) counts[l * plane + i] = (uint8_t)lit;            // comp:150
-        }
-    });
-    return RTS_OK;
-}
-
-// ---- adaptive soft light lists on the host (include/rts_scene.h): the checker of rts_trace_soft_light_list_adaptive* ----
-// The definition of include/rts.h applied literally: rtsh_soft_light_list's loop, and per light rtsh_shadow_mask_adaptive's decision
-// after the probe's samples.
-// The jittered form (rts_trace_soft_light_list_jittered*) is the same loop with sampleIndex(T_l, j, pixel) in front of the offset;
-// without tables sampleIndex(0, j, .) is j.
-extern "C" int rtsh_soft_light_list_jittered(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
-                                             const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
-                                             uint32_t row_end, uint8_t* counts, const uint32_t* probes, const uint32_t* tables, uint8_t* refined,
-                                             int threads) {
-    using rts_harness::sampleIndex;
-    if (!packed || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListTablesOk(list, probes, tables))
-        return RTS_ERR_INVALID_ARG;
+// rows [row_begin, row_end) of a frame (the arguments checked by the caller, each form by its own rule)
+int softListFrame(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list, const float* positions,
+                  const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, float* distances, uint8_t* counts,
+                  const uint32_t* probes, const uint32_t* tables, uint8_t* refined, int threads) {
     const int s = rts_bvh_validate(packed, count_vec4, nullptr);
     if (s != RTS_OK) return s;
     const uint32_t* bvh = (const uint32_t*)packed;
@@ -483,30 +412,57 @@ extern "C" int rtsh_soft_light_list_jittered(const rts_vec4u* packed, size_t cou
         const float* q = positions + i * 4;                              // (not read where bits == 0)
         uint32_t took = 0;
         for (uint32_t l = 0; l < list->count; ++l) {
-            uint32_t lit = 0;
+            uint32_t best = 0u, lit = 0;                                 // (+0.0f and 0 where the map's bit is clear)
             if ((bits >> l) & 1u) {
                 const rts_soft_light_entry& e = list->lights[l];
-                const uint32_t ns = e.nsamples > 1 ? e.nsamples : 1u, probe = probes[l], table = tables ? tables[l] : 0u;
+                const uint32_t ns = e.nsamples > 1 ? e.nsamples : 1u, probe = probes ? probes[l] : 0u, table = tables ? tables[l] : 0u;
+                best = 0x7F800000u;
                 uint32_t j = 0;
                 for (; j < ns; ++j) {
                     if (probe != 0 && j == probe && (lit == 0 || lit == probe)) break;      // the probe agrees: its verdict, no further ray
-                    V3 L{ e.xyz[0], e.xyz[1], e.xyz[2] };
-                    if (ns > 1) {
-                        const float* o = list->offsets[e.first + sampleIndex(table, j, (uint32_t)i)];
-                        const float ox = e.radius * o[0], oy = e.radius * o[1], oz = e.radius * o[2];
-                        L.x = L.x + ox; L.y = L.y + oy; L.z = L.z + oz;
-                    }
+                    const V3 L = ns > 1 ? softListAim(e, list->offsets, e.first + sampleIndex(table, j, (uint32_t)i))
+                                        : V3{ e.xyz[0], e.xyz[1], e.xyz[2] };
                     const uint32_t one = rayDistanceBits(bvh, shadowRay(k->cameraPosition, V3{ q[0], q[1], q[2] }, e.type, L));
                     lit += one == 0x7F800000u ? 1u : 0u;                 // comp:148, per sample
+                    if (one < best) best = one;
                 }
                 if (j < ns) lit = lit ? ns : 0u;                         // (left at the probe)
                 else if (probe != 0) took |= 1u << l;                    // every sample walked because the probe disagreed
             }
-            counts[l * plane + i] = (uint8_t)lit;                        // comp:150
+            if (distances) distances[l * plane + i] = asFloat(best);
+            if (counts) counts[l * plane + i] = (uint8_t)lit;            // comp:150
         }
         if (refined) refined[i] = (uint8_t)took;
     });
     return RTS_OK;
+}
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_soft_light_list(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
+                                    const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                    uint32_t row_end, uint8_t* counts, int threads) {
+    if (!packed || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    return softListFrame(packed, count_vec4, k, list, positions, lights_map, W, H, row_begin, row_end, nullptr, counts, nullptr, nullptr, nullptr,
+                         threads);
+}
+
+extern "C" int rtsh_soft_light_list_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
+                                             const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                             uint32_t row_end, float* distances, uint8_t* counts, int threads) {
+    if (!packed || !k || !positions || !distances || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    return softListFrame(packed, count_vec4, k, list, positions, lights_map, W, H, row_begin, row_end, distances, counts, nullptr, nullptr, nullptr,
+                         threads);
+}
+
+extern "C" int rtsh_soft_light_list_jittered(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
+                                             const float* positions, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t row_begin,
+                                             uint32_t row_end, uint8_t* counts, const uint32_t* probes, const uint32_t* tables, uint8_t* refined,
+                                             int threads) {
+    if (!packed || !k || !positions || !counts || !rts::frameRowsOk(W, H, row_begin, row_end) || !rts::softListTablesOk(list, probes, tables))
+        return RTS_ERR_INVALID_ARG;
+    return softListFrame(packed, count_vec4, k, list, positions, lights_map, W, H, row_begin, row_end, nullptr, counts, probes, tables, refined,
+                         threads);
 }
 
 extern "C" int rtsh_soft_light_list_adaptive(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_soft_light_list* list,
@@ -535,11 +491,7 @@ static int makeCombineListOf(const rts_constants* k, uint32_t count, const uint3
                              const float* colors, bool havePositions, CombineList* out) {
     out->count = count;
     for (uint32_t l = 0; l < count; ++l) {
-        rts_light one;
-        memset(&one, 0, sizeof(one));
-        one.type = types[l];
-        one.nsamples = nsamples[l];
-        for (int i = 0; i < 3; ++i) one.xyz[i] = xyz[l][i];
+        const rts_light one = lightOf(types[l], nsamples[l], xyz[l]);
         const int s = makeCombineParams(k, &one, havePositions, &out->light[l]);
         if (s != RTS_OK) return s;
         for (int c = 0; c < 3; ++c) out->color[l][c] = colors ? colors[l * 4 + c] : 1.0f;
@@ -576,16 +528,15 @@ int makeCombineSoftList(const rts_constants* k, const rts_soft_light_list* list,
 }
 
 namespace {
-template <bool HARD>
-void combineListFrame(const CombineList& f, const float* positions, const float* normals, const uint8_t* lights_map, const uint8_t* planes,
-                      size_t n, uint8_t* rgb) {
+// The frame walk of the three list combines: pixel(i, position, normal, bits) for every pixel, bits its byte of the light map -- every
+// light where there is no map, and on the background, whose map byte is not read.
+template <class Pixel>
+void combineFrame(const float* positions, const float* normals, const uint8_t* lights_map, size_t n, Pixel&& pixel) {
     const float zero[4] = { 0, 0, 0, 0 };
     for (size_t i = 0; i < n; ++i) {
         const float* n4 = normals + i * 4;
-        const bool background = n4[0] == 0.0f && n4[1] == 0.0f && n4[2] == 0.0f;      // (its map byte is not read)
-        const uint32_t bits = (lights_map && !background) ? lights_map[i] : 0xFFu;
-        combineListPixel(f, positions ? positions + i * 4 : zero, n4, bits,
-                         [&](uint32_t l) { return HARD ? (uint8_t)((planes[i] >> l) & 1u) : planes[(size_t)l * n + i]; }, rgb + i * 3);
+        const bool background = n4[0] == 0.0f && n4[1] == 0.0f && n4[2] == 0.0f;
+        pixel(i, positions ? positions + i * 4 : zero, n4, (lights_map && !background) ? lights_map[i] : 0xFFu);
     }
 }
 } // namespace
@@ -598,7 +549,9 @@ extern "C" int rtsh_combine_light_list(const rts_constants* k, const rts_light_l
     CombineList f;
     const int s = makeCombineList(k, list, colors, positions != nullptr, &f);
     if (s != RTS_OK) return s;
-    combineListFrame<true>(f, positions, normals, lights_map, mask, (size_t)W * H, rgb);
+    combineFrame(positions, normals, lights_map, (size_t)W * H, [&](size_t i, const float* p4, const float* n4, uint32_t bits) {
+        combineListPixel(f, p4, n4, bits, [&](uint32_t l) { return (uint8_t)((mask[i] >> l) & 1u); }, rgb + i * 3);
+    });
     return RTS_OK;
 }
 
@@ -609,7 +562,10 @@ extern "C" int rtsh_combine_soft_light_list(const rts_constants* k, const rts_so
     CombineList f;
     const int s = makeCombineSoftList(k, list, colors, positions != nullptr, &f);
     if (s != RTS_OK) return s;
-    combineListFrame<false>(f, positions, normals, lights_map, counts, (size_t)W * H, rgb);
+    const size_t n = (size_t)W * H;
+    combineFrame(positions, normals, lights_map, n, [&](size_t i, const float* p4, const float* n4, uint32_t bits) {
+        combineListPixel(f, p4, n4, bits, [&](uint32_t l) { return counts[(size_t)l * n + i]; }, rgb + i * 3);
+    });
     return RTS_OK;
 }
 
@@ -705,15 +661,10 @@ extern "C" int rtsh_combine_visibility_list(const rts_constants* k, const rts_li
     CombineList f;
     const int s = makeCombineList(k, list, colors, positions != nullptr, &f);
     if (s != RTS_OK) return s;
-    const float zero[4] = { 0, 0, 0, 0 };
     const size_t n = (size_t)W * H;
-    for (size_t i = 0; i < n; ++i) {
-        const float* n4 = normals + i * 4;
-        const bool background = n4[0] == 0.0f && n4[1] == 0.0f && n4[2] == 0.0f;          // (its map byte is not read)
-        const uint32_t bits = (lights_map && !background) ? lights_map[i] : 0xFFu;
-        combineVisibilityPixel(f, positions ? positions + i * 4 : zero, n4, bits, [&](uint32_t l) { return visibility[(size_t)l * n + i]; },
-                               rgb + i * 3);
-    }
+    combineFrame(positions, normals, lights_map, n, [&](size_t i, const float* p4, const float* n4, uint32_t bits) {
+        combineVisibilityPixel(f, p4, n4, bits, [&](uint32_t l) { return visibility[(size_t)l * n + i]; }, rgb + i * 3);
+    });
     return RTS_OK;
 }
 

@@ -89,9 +89,7 @@ void shadowSoftDistancePacketKernel(TraceParams p) {
 
 hipError_t launchShadowSoftDistance(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
     if (!p.distance || p.nsamples < 2 || p.nsamples > 64) return hipErrorInvalidValue;
-    static const char* const names[2][3] = {
-        { "shadowSoftDistancePacketKernel<1,general>", "shadowSoftDistancePacketKernel<1,rows>", "shadowSoftDistancePacketKernel<1,bands>" },
-        { "shadowSoftDistancePacketKernel<4,general>", "shadowSoftDistancePacketKernel<4,rows>", "shadowSoftDistancePacketKernel<4,bands>" } };
+    static const char* const names[2][3] = RTS_PACKET_NAMES("shadowSoftDistancePacketKernel", "");
     return launchLoopFamily(variant, p, stream, name, shadowSoftDistanceShareKernel, "shadowSoftDistanceShareKernel", names,
                             [&](dim3 grid, auto split, auto geom) {
         constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;

@@ -2,6 +2,7 @@
 // rts_kernels.hip): beside rts_device.h, whose text is part of the kernel-build hash that the committed counter profiles carry.
 #pragma once
 #include "rts_device.h"
+#include "rts_soft_list_slots.h"
 
 namespace rts {
 
@@ -10,11 +11,10 @@ namespace rts {
 //   p.offsets[j], j < 48                = the list's shared sample table (RTS_SOFT_LIST_OFFSETS entries; .w is not read)
 //   p.offsets[48 + 2 l]                 = { x, y, z, radius } of light l
 //   p.offsets[48 + 2 l + 1]             = the bit patterns of { type, samples = max(1, nsamples), first (0 for a hard entry), 0 }
-// (setSoftListEntry writes the two slots of light l: the kernels' file owns that part of the layout.)
+// (rts_soft_list_slots.h writes the two slots of light l, setSoftListEntry, and has the launchers' guard of them, softListSlotsOk.)
 // p.activeMap = the per-pixel light map (bit l: light l sends its rays here) or NULL (every light everywhere); p.mask = the count
 // planes, plane l at p.mask + l * W * H: the number of unoccluded samples of light l.  p.lightTable is 0: a list's per-pixel jitter
 // tables, where it has any, travel per light (rts_soft_light_list_adaptive.h).  V_SHARE, or V_PACKET with 4 waves per tile (p.softSplit) or one.  *name: the kernel's stable name.
-void setSoftListEntry(TraceParams& p, uint32_t l, uint32_t type, uint32_t samples, uint32_t first, float radius, const float* xyz);
 hipError_t launchShadowSoftLightList(int variant, const TraceParams& p, hipStream_t stream, const char** name);
 
 } // namespace rts

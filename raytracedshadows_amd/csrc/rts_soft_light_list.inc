@@ -9,14 +9,11 @@
 // (pixel, light, sample) alone, and integer addition is associative and commutative, so a plane does not depend on the order the
 // pairs are walked in, nor on which wave walked which: the 4-wave form adds the waves' counts in LDS (DESIGN.md 4.17).
 
-static constexpr uint32_t SOFT_LIST_SLOT = 48;                           // p.offsets[48 + 2 l], [48 + 2 l + 1]: light l (rts_soft_light_list.h)
-
-void setSoftListEntry(TraceParams& p, uint32_t l, uint32_t type, uint32_t samples, uint32_t first, float radius, const float* xyz) {
-    float* a = p.offsets[SOFT_LIST_SLOT + 2u * l];
-    a[0] = xyz[0]; a[1] = xyz[1]; a[2] = xyz[2]; a[3] = radius;
-    const uint32_t bits[4] = { type, samples, first, 0u };
-    __builtin_memcpy(p.offsets[SOFT_LIST_SLOT + 2u * l + 1u], bits, sizeof(bits));
-}
+// SOFT_LIST_SLOT, the slots' writers and the guard of every launcher below, softListSlotsOk: a header of its own with its own
+// namespace, so rts_kernels.hip's is closed around it.
+} // namespace rts
+#include "rts_soft_list_slots.h"
+namespace rts {
 
 // samples of light l: 1 (a hard entry) .. 48.  Wave-uniform like l: a scalar load from the argument block.
 __device__ __forceinline__ uint32_t softListSamples(const TraceParams& p, uint32_t l) {
@@ -173,16 +170,8 @@ void shadowSoftLightListPacketKernel(TraceParams p) {
 }
 
 hipError_t launchShadowSoftLightList(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
-    if (!p.mask || p.nsamples < 1 || p.nsamples > 8) return hipErrorInvalidValue;
-    for (uint32_t l = 0; l < p.nsamples; ++l) {                          // (what keeps every index inside p.offsets)
-        uint32_t bits[4];
-        __builtin_memcpy(bits, p.offsets[SOFT_LIST_SLOT + 2u * l + 1u], sizeof(bits));
-        if (bits[0] > 1u || bits[1] < 1u || bits[1] > SOFT_LIST_SLOT || (bits[1] > 1u && (uint64_t)bits[2] + bits[1] > SOFT_LIST_SLOT))
-            return hipErrorInvalidValue;
-    }
-    static const char* const names[2][3] = {
-        { "shadowSoftLightListPacketKernel<1,general>", "shadowSoftLightListPacketKernel<1,rows>", "shadowSoftLightListPacketKernel<1,bands>" },
-        { "shadowSoftLightListPacketKernel<4,general>", "shadowSoftLightListPacketKernel<4,rows>", "shadowSoftLightListPacketKernel<4,bands>" } };
+    if (!p.mask || !softListSlotsOk(p.offsets, p.nsamples, false, false)) return hipErrorInvalidValue;
+    static const char* const names[2][3] = RTS_PACKET_NAMES("shadowSoftLightListPacketKernel", "");
     return launchLoopFamily(variant, p, stream, name, shadowSoftLightListShareKernel, "shadowSoftLightListShareKernel", names,
                             [&](dim3 grid, auto split, auto geom) {
         constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;

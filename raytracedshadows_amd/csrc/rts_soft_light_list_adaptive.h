@@ -20,9 +20,7 @@ namespace rts {
 // below 64), would have changed what the existing kernels load for k_l and with it their text.
 // p.pixelBase = the index in the caller's frame of the dispatch's pixel 0: the hash is the full frame's (rts_light.table).
 // p.mask = the count planes, p.activeMap = the light map or NULL.  The launcher re-checks every entry and every k_l against the 64
-// slots before it launches.  V_SHARE, or V_PACKET with 4 waves per tile (p.softSplit) or one.  *name: the kernel's stable name.
-void setSoftListProbe(TraceParams& p, uint32_t l, uint32_t probe);
-void setSoftListTable(TraceParams& p, uint32_t l, uint32_t table);
+// slots before it launches (softListSlotsOk).  V_SHARE, or V_PACKET with 4 waves per tile (p.softSplit) or one.  *name: the kernel's stable name.
 hipError_t launchShadowSoftLightListAdaptive(int variant, const TraceParams& p, hipStream_t stream, const char** name);
 // the same with the tables honoured: the JITTER instantiations, named "...ShareKernel<jitter>" and "...PacketKernel<S,geom,jitter>";
 // the launcher checks first + T_l <= 48 as well.

@@ -11,10 +11,6 @@
 // Everything is integer counting of bytes that are functions of (pixel, light, sample) alone, so no byte depends on the order the
 // pairs are walked in, nor on which wave walked which (DESIGN.md 4.18).
 
-void setSoftListProbe(TraceParams& p, uint32_t l, uint32_t probe) {
-    __builtin_memcpy(&p.offsets[SOFT_LIST_SLOT + 2u * l + 1u][3], &probe, sizeof(probe));
-}
-
 // k_l: 0 (every sample in the first phase) .. samples - 1.  Wave-uniform like l: a scalar load from the argument block.
 __device__ __forceinline__ uint32_t softListProbe(const TraceParams& p, uint32_t l) {
     return __float_as_uint(p.offsets[SOFT_LIST_SLOT + 2u * l + 1u][3]);
@@ -26,10 +22,6 @@ __device__ __forceinline__ uint32_t softListProbe(const TraceParams& p, uint32_t
 // (rts_kernels.hip) with T_l in p.lightTable's place, so the ray is the one the mask kernels set up for the derived light with that
 // table.  Which pairs are walked over which lanes is decided by k_l, the map and the tile, never by an offset: the counting above
 // and the barriers' argument below hold as they stand (DESIGN.md 4.19).
-void setSoftListTable(TraceParams& p, uint32_t l, uint32_t table) {
-    __builtin_memcpy(&p.offsets[l][3], &table, sizeof(table));
-}
-
 // T_l.  Wave-uniform like l: a scalar load from the argument block.
 __device__ __forceinline__ uint32_t softListTable(const TraceParams& p, uint32_t l) {
     return __float_as_uint(p.offsets[l][3]);
@@ -254,31 +246,9 @@ void shadowSoftLightListAdaptivePacketKernel(TraceParams p) {
     softListAdaptiveStore(p, pix, lo0, hi0, lo1, hi1);
 }
 
-// What keeps every index inside p.offsets, and k_l below the samples.  tables: T_l is looked at too -- 0, or samples .. 48 - first on
-// a soft entry, so that first + sampleIndexOf(...) < SOFT_LIST_SLOT for every pixel.
-static bool softListAdaptiveParamsOk(const TraceParams& p, bool tables) {
-    if (!p.mask || p.nsamples < 1 || p.nsamples > 8) return false;
-    for (uint32_t l = 0; l < p.nsamples; ++l) {
-        uint32_t bits[4];
-        __builtin_memcpy(bits, p.offsets[SOFT_LIST_SLOT + 2u * l + 1u], sizeof(bits));
-        if (bits[0] > 1u || bits[1] < 1u || bits[1] > SOFT_LIST_SLOT || (bits[1] > 1u && (uint64_t)bits[2] + bits[1] > SOFT_LIST_SLOT))
-            return false;
-        if (bits[3] >= bits[1]) return false;
-        if (!tables) continue;
-        uint32_t table;
-        __builtin_memcpy(&table, &p.offsets[l][3], sizeof(table));
-        if (table != 0u && (bits[1] < 2u || table < bits[1] || (uint64_t)bits[2] + table > SOFT_LIST_SLOT)) return false;
-    }
-    return true;
-}
-
 hipError_t launchShadowSoftLightListAdaptive(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
-    if (!softListAdaptiveParamsOk(p, false)) return hipErrorInvalidValue;
-    static const char* const names[2][3] = {
-        { "shadowSoftLightListAdaptivePacketKernel<1,general>", "shadowSoftLightListAdaptivePacketKernel<1,rows>",
-          "shadowSoftLightListAdaptivePacketKernel<1,bands>" },
-        { "shadowSoftLightListAdaptivePacketKernel<4,general>", "shadowSoftLightListAdaptivePacketKernel<4,rows>",
-          "shadowSoftLightListAdaptivePacketKernel<4,bands>" } };
+    if (!p.mask || !softListSlotsOk(p.offsets, p.nsamples, true, false)) return hipErrorInvalidValue;
+    static const char* const names[2][3] = RTS_PACKET_NAMES("shadowSoftLightListAdaptivePacketKernel", "");
     return launchLoopFamily(variant, p, stream, name, shadowSoftLightListAdaptiveShareKernel<false>, "shadowSoftLightListAdaptiveShareKernel",
                             names, [&](dim3 grid, auto split, auto geom) {
         constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;
@@ -286,12 +256,8 @@ hipError_t launchShadowSoftLightListAdaptive(int variant, const TraceParams& p, 
 }
 
 hipError_t launchShadowSoftLightListJittered(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
-    if (!softListAdaptiveParamsOk(p, true)) return hipErrorInvalidValue;
-    static const char* const names[2][3] = {
-        { "shadowSoftLightListAdaptivePacketKernel<1,general,jitter>", "shadowSoftLightListAdaptivePacketKernel<1,rows,jitter>",
-          "shadowSoftLightListAdaptivePacketKernel<1,bands,jitter>" },
-        { "shadowSoftLightListAdaptivePacketKernel<4,general,jitter>", "shadowSoftLightListAdaptivePacketKernel<4,rows,jitter>",
-          "shadowSoftLightListAdaptivePacketKernel<4,bands,jitter>" } };
+    if (!p.mask || !softListSlotsOk(p.offsets, p.nsamples, true, true)) return hipErrorInvalidValue;
+    static const char* const names[2][3] = RTS_PACKET_NAMES("shadowSoftLightListAdaptivePacketKernel", ",jitter");
     return launchLoopFamily(variant, p, stream, name, shadowSoftLightListAdaptiveShareKernel<true>,
                             "shadowSoftLightListAdaptiveShareKernel<jitter>", names, [&](dim3 grid, auto split, auto geom) {
         constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;

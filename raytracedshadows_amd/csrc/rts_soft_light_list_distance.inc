@@ -145,18 +145,8 @@ void shadowSoftLightListDistancePacketKernel(TraceParams p) {
 }
 
 hipError_t launchShadowSoftLightListDistance(int variant, const TraceParams& p, hipStream_t stream, const char** name) {
-    if (!p.distance || p.nsamples < 1 || p.nsamples > 8) return hipErrorInvalidValue;
-    for (uint32_t l = 0; l < p.nsamples; ++l) {                          // (what keeps every index inside p.offsets)
-        uint32_t bits[4];
-        __builtin_memcpy(bits, p.offsets[SOFT_LIST_SLOT + 2u * l + 1u], sizeof(bits));
-        if (bits[0] > 1u || bits[1] < 1u || bits[1] > SOFT_LIST_SLOT || (bits[1] > 1u && (uint64_t)bits[2] + bits[1] > SOFT_LIST_SLOT))
-            return hipErrorInvalidValue;
-    }
-    static const char* const names[2][3] = {
-        { "shadowSoftLightListDistancePacketKernel<1,general>", "shadowSoftLightListDistancePacketKernel<1,rows>",
-          "shadowSoftLightListDistancePacketKernel<1,bands>" },
-        { "shadowSoftLightListDistancePacketKernel<4,general>", "shadowSoftLightListDistancePacketKernel<4,rows>",
-          "shadowSoftLightListDistancePacketKernel<4,bands>" } };
+    if (!p.distance || !softListSlotsOk(p.offsets, p.nsamples, false, false)) return hipErrorInvalidValue;
+    static const char* const names[2][3] = RTS_PACKET_NAMES("shadowSoftLightListDistancePacketKernel", "");
     return launchLoopFamily(variant, p, stream, name, shadowSoftLightListDistanceShareKernel, "shadowSoftLightListDistanceShareKernel", names,
                             [&](dim3 grid, auto split, auto geom) {
         constexpr int SPLIT = decltype(split)::value, GEOM = decltype(geom)::value;

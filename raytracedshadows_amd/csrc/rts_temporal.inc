@@ -67,10 +67,6 @@ extern "C" int rtsh_accumulate_visibility_list_device(rts_ctx* ctx, const rts_li
     // W, H <= 65536 (makeTemporalList): at most 4096 x 4096 blocks, inside every grid limit
     const rts_harness::TemporalDeviceFrames t{ d_positions, d_normals, d_visibility, d_prev_positions, d_prev_normals, d_prev_visibility,
                                                d_lights_map, d_prev_lengths, d_visibility_out, d_lengths_out, W, (uint64_t)W * H };
-    hipError_t e = hipSetDevice(rts_ctx_device_ordinal(ctx));
-    if (e != hipSuccess) return RTS_ERR_HIP + (int)e;
-    hipLaunchKernelGGL(rts_harness::accumulateListKernel, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0, (hipStream_t)stream, f, t,
-                       (int)W, (int)H);
-    e = hipGetLastError();
-    return e == hipSuccess ? RTS_OK : RTS_ERR_HIP + (int)e;
+    return rts_harness::launchPass(ctx, stream, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0, rts_harness::accumulateListKernel, f, t,
+                                   (int)W, (int)H);
 }
