@@ -326,8 +326,9 @@ int rtsh_combine_visibility_list_device(rts_ctx* ctx, const rts_constants* const
  *   * host form: multi-threaded (threads: 0 = all host threads).  Device form: DEVICE buffers, asynchronous on `stream`, allocates
  *     nothing and reads nothing back; under graph capture ONE kernel node, list and params by value (params is read during the call).
  *     No BVH, no alignment of any buffer beyond its element type's.
- *   * OUT OF SCOPE: moving geometry (no motion vectors: the plane test takes it for a disocclusion and resets), neighbourhood or variance
- *     clamping of the history, accumulating count or distance planes, row ranges and stripes, a frame term in the jitter hash. */
+ *   * OUT OF SCOPE: moving geometry (no motion vectors: the plane test takes it for a disocclusion and resets), variance clamping of
+ *     the history (a mean +- k sigma box needs a square root; the min/max box is rtsh_accumulate_visibility_list_clamped below),
+ *     accumulating count or distance planes, row ranges and stripes, a frame term in the jitter hash. */
 typedef struct rtsh_temporal_params {
     float    eye_delta[3];                             /* current eye - previous eye */
     float    prev_right[3], prev_up[3], prev_fwd[3];   /* the previous camera's basis */
@@ -350,6 +351,59 @@ int rtsh_accumulate_visibility_list_device(rts_ctx* ctx, const rts_light_list* l
                                            const float* d_visibility, const float* d_prev_positions, const float* d_prev_normals,
                                            const float* d_prev_visibility, const uint8_t* d_prev_lengths, uint32_t W, uint32_t H,
                                            float* d_visibility_out, uint8_t* d_lengths_out, void* stream);
+
+/* THE CLAMPED FORM OF THE TEMPORAL ACCUMULATION: the pass above rejects history by the RECEIVER's geometry alone, so when an occluder or
+ * a light moves it keeps blending a shadow that is no longer there (max_length 32: a pixel that has just become lit still shows 97 % of
+ * it), and reset_lights throws a light's whole history away, noise reduction included.  Here a pixel's reprojected history is first
+ * CLAMPED into the range its light's CURRENT visibility spans over a (2r+1) x (2r+1) window around the pixel.  The range is a minimum
+ * and a maximum, so it does not depend on any order, and the host form checks the device form bit for bit as above.
+ * Everything of rtsh_accumulate_visibility_list holds unchanged -- INACTIVE, REPROJECT, tap acceptance, sw, sv, m, n, the pass-through
+ * cases, the canonical NaN --; ONE step is added between prev = sv / (float)sw and the lerp, so only where a value is blended (n != 1).
+ *   ORDER: for a float of bits u, key(u) = u ^ ((u >> 31) ? 0xFFFFFFFF : 0x80000000), compared as unsigned integers: a total order on
+ *     the non-NaN floats in which -0 < +0.  The minimum and maximum below are integer min/max of keys: no order of taps, no tiling, no
+ *     staging scheme can change a bit.
+ *   BOX of pixel p = (x, y) for light l: of the taps q = (x+dx, y+dy), |dx| <= r and |dy| <= r, those CONTRIBUTE for which q lies
+ *     inside the frame, normals[q].xyz is not all zero, lights_map is NULL or bit l of lights_map[q] is set, and visibility[l][q] is
+ *     not a NaN (v != v).  (The middle two exclude the +0.0f that inactive pixels hold.)  The centre is a tap like any other: active
+ *     by the INACTIVE rule, it contributes unless it is a NaN.  lo and hi are the contributing values of the smallest and the largest
+ *     key; where in the window they lie is never looked at.
+ *   CLAMP: with no contributing tap, prev is used as it is.  Otherwise lo_m = lo - margin and hi_m = hi + margin (one rounded
+ *     operation each) and prev' = prev < lo_m ? lo_m : (prev > hi_m ? hi_m : prev); a NaN prev fails both comparisons and stays.  The
+ *     lerp reads v = prev' + (cur - prev') * (1.0f / (float)n).  lengths_out is what the unclamped rule gives: the clamp does not
+ *     shorten a history.
+ * ANCHORS: (1) Over finite planes, a margin so large that lo_m <= prev <= hi_m everywhere (3.0e38f over planes in [0, 1]) gives the
+ * unclamped pass's bits, wherever every blended pixel has a contributing tap -- true when the current planes hold no NaN, the centre
+ * being one.  (With a plane value or a history beyond +-(FLT_MAX - margin) the sums overflow or round and the anchor ends.)
+ * (2) radius 0 with margin 0: lo_m = hi_m = cur, so prev' = cur and visibility_out == visibility, bit for bit, at every blended pixel
+ * whose current value is finite and not -0 and whose prev is not a NaN: cur + (cur - cur) * k is cur.  -0 is excepted because
+ * hi_m = -0 + 0 is +0 (and a prev above it then gives +0 + (-0 - +0) * k = +0, not -0); the infinities because Inf - Inf is a NaN,
+ * stored as the canonical one; a NaN prev because it stays.  (3) The pass-through cases -- the first frame, max_length 1, a light in
+ * reset_lights, a pixel with no accepted tap -- keep the current bits exactly as above: the clamp never touches them.  (4) THE STEP:
+ * history 1.0f of length >= 1 everywhere, current 0.0f everywhere, a still camera, margin 0: the result is exactly +0.0f at any radius
+ * and any max_length, where the unclamped pass gives 1 - 1/n.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the unclamped form refuses; a NULL clamp; radius above
+ *     RTSH_CLAMP_MAX_RADIUS; a margin that is negative or not finite; visibility_out == visibility -- the unclamped form allows it,
+ *     this one reads its neighbours' current values and cannot (overlap other than equality is the caller's error, as everywhere).
+ *   * reserved_ is ignored.  Planes from `count` up are never touched.  Host form: multi-threaded.  Device form: DEVICE buffers,
+ *     asynchronous on `stream`, allocates nothing, reads nothing back; under graph capture ONE kernel node, list, params and clamp by
+ *     value.  No BVH, no alignment of any buffer beyond its element type's. */
+enum { RTSH_CLAMP_MAX_RADIUS = 4 };
+typedef struct rtsh_history_clamp {
+    uint32_t radius;                                   /* r, 0 .. RTSH_CLAMP_MAX_RADIUS: the window is (2r+1) x (2r+1) pixels */
+    float    margin;                                   /* finite, >= 0: the box is widened by this on both sides */
+    uint32_t reserved_[2];                             /* ignored */
+} rtsh_history_clamp;                                                              /* 16 bytes */
+int rtsh_accumulate_visibility_list_clamped(const rts_light_list* list, const rtsh_temporal_params* params, const float* positions,
+                                            const float* normals, const uint8_t* lights_map, const float* visibility,
+                                            const float* prev_positions, const float* prev_normals, const float* prev_visibility,
+                                            const uint8_t* prev_lengths, uint32_t W, uint32_t H, float* visibility_out,
+                                            uint8_t* lengths_out, const rtsh_history_clamp* clamp, int threads);
+int rtsh_accumulate_visibility_list_clamped_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_temporal_params* params,
+                                                   const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                   const float* d_visibility, const float* d_prev_positions, const float* d_prev_normals,
+                                                   const float* d_prev_visibility, const uint8_t* d_prev_lengths, uint32_t W, uint32_t H,
+                                                   float* d_visibility_out, uint8_t* d_lengths_out, const rtsh_history_clamp* clamp,
+                                                   void* stream);
 
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.

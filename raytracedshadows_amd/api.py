@@ -235,6 +235,18 @@ class TemporalParams(C.Structure):
                         max_length, reset_lights)
 
 
+class HistoryClamp(C.Structure):
+    """``rtsh_history_clamp``: the neighbourhood clamp of the temporal accumulation -- a window of (2 * radius + 1)^2 pixels
+    (radius 0..4) whose current minimum and maximum, widened by ``margin`` (finite, >= 0), bound the reprojected history."""
+    _fields_ = [("radius", C.c_uint32), ("margin", C.c_float), ("reserved_", C.c_uint32 * 2)]
+
+    @classmethod
+    def make(cls, radius, margin=0.0):
+        c = cls()
+        c.radius, c.margin = radius, np.float32(margin)
+        return c
+
+
 #: numpy view of ``struct BVHNode`` (BVHBuilder.h:8-20)
 BVHNode_dtype = np.dtype([("bboxMin", np.float32, 3), ("prim", np.uint32),
                           ("bboxMax", np.float32, 3), ("next", np.uint32)])
@@ -481,6 +493,12 @@ _sig("rtsh_accumulate_visibility_list", C.c_int, C.POINTER(LightList), C.POINTER
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
 _sig("rtsh_accumulate_visibility_list_device", C.c_int, C.c_void_p, C.POINTER(LightList), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_accumulate_visibility_list_clamped", C.c_int, C.POINTER(LightList), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(HistoryClamp),
+     C.c_int)
+_sig("rtsh_accumulate_visibility_list_clamped_device", C.c_int, C.c_void_p, C.POINTER(LightList), C.POINTER(TemporalParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+     C.POINTER(HistoryClamp), C.c_void_p)
 _sig("rtsh_facing_active", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
      C.c_void_p)
 _sig("rtsh_facing_active_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
@@ -1600,11 +1618,12 @@ def camera_basis(eye, target, fovy, width, height):
             "aspect": out[13]}
 
 
-def accumulate_visibility_list(light_list, params, positions, normals, visibility, prev=None, lights_map=None, threads=0):
+def accumulate_visibility_list(light_list, params, positions, normals, visibility, prev=None, lights_map=None, threads=0, clamp=None):
     """The temporal accumulation of a light list's visibility on the host (rtsh_accumulate_visibility_list): ``(float32[count, H, W]
     visibility, uint8[count, H, W] lengths)``.  ``visibility``: this frame's ``float32[>= count, H, W]`` (a filter's output);
     ``prev``: None on the first frame, else ``(prev_positions, prev_normals, prev_visibility, prev_lengths)`` of the previous frame
-    (its G-buffer and what this call returned for it); ``params`` a ``TemporalParams``."""
+    (its G-buffer and what this call returned for it); ``params`` a ``TemporalParams``.  ``clamp``: None, or a ``HistoryClamp`` for
+    the clamped form (rtsh_accumulate_visibility_list_clamped)."""
     normals = np.ascontiguousarray(normals, np.float32)
     H, W = normals.shape[:2]
     count = light_list.count if light_list is not None and 1 <= light_list.count <= 8 else 1
@@ -1621,6 +1640,12 @@ def accumulate_visibility_list(light_list, params, positions, normals, visibilit
         raise RtsError(1, "rtsh_accumulate_visibility_list: a buffer does not fit the frame of the normals")
     out, lengths = np.zeros((count, H, W), np.float32), np.zeros((count, H, W), np.uint8)
     pp = [_ptr(a) for a in prev] if prev is not None else [None] * 4
+    if clamp is not None:
+        _check(_lib.rtsh_accumulate_visibility_list_clamped(_ref(light_list), _ref(params), _ptr_or_none(positions), _ptr(normals),
+                                                            _ptr_or_none(lights_map), _ptr(visibility), pp[0], pp[1], pp[2], pp[3], W, H,
+                                                            _ptr(out), _ptr(lengths), _ref(clamp), threads),
+               "rtsh_accumulate_visibility_list_clamped")
+        return out, lengths
     _check(_lib.rtsh_accumulate_visibility_list(_ref(light_list), _ref(params), _ptr_or_none(positions), _ptr(normals), _ptr_or_none(lights_map),
                                                 _ptr(visibility), pp[0], pp[1], pp[2], pp[3], W, H, _ptr(out), _ptr(lengths), threads),
            "rtsh_accumulate_visibility_list")
@@ -1628,11 +1653,21 @@ def accumulate_visibility_list(light_list, params, positions, normals, visibilit
 
 
 def accumulate_visibility_list_device(ctx, light_list, params, d_positions, d_normals, d_visibility, width, height, d_visibility_out,
-                                      d_lengths_out, d_prev=None, d_lights_map=None, stream=None):
+                                      d_lengths_out, d_prev=None, d_lights_map=None, stream=None, clamp=None):
     """The temporal accumulation on the GPU: device pointers; ``d_prev``: None on the first frame, else the device pointers
     ``(prev_positions, prev_normals, prev_visibility, prev_lengths)``.  d_visibility_out = count planes of width*height floats,
-    d_lengths_out = count planes of width*height bytes; neither may be the history it reads.  One kernel, asynchronous."""
+    d_lengths_out = count planes of width*height bytes; neither may be the history it reads.  One kernel, asynchronous.  ``clamp``: None,
+    or a ``HistoryClamp`` for the clamped form (then d_visibility_out may not be d_visibility either)."""
     pp = tuple(d_prev) if d_prev is not None else (0, 0, 0, 0)
+    if clamp is not None:
+        _check(_lib.rtsh_accumulate_visibility_list_clamped_device(ctx.handle, _ref(light_list), _ref(params), C.c_void_p(d_positions or 0),
+                                                                   C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
+                                                                   C.c_void_p(d_visibility), C.c_void_p(pp[0] or 0), C.c_void_p(pp[1] or 0),
+                                                                   C.c_void_p(pp[2] or 0), C.c_void_p(pp[3] or 0), width, height,
+                                                                   C.c_void_p(d_visibility_out), C.c_void_p(d_lengths_out), _ref(clamp),
+                                                                   C.c_void_p(stream or 0)),
+               "rtsh_accumulate_visibility_list_clamped_device")
+        return
     _check(_lib.rtsh_accumulate_visibility_list_device(ctx.handle, _ref(light_list), _ref(params), C.c_void_p(d_positions or 0),
                                                        C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0), C.c_void_p(d_visibility),
                                                        C.c_void_p(pp[0] or 0), C.c_void_p(pp[1] or 0), C.c_void_p(pp[2] or 0),

@@ -294,6 +294,11 @@ RTS_HD void filterListPixel(const FilterList& f, const Texels& t, int x, int y, 
 //   visibility[l][p]); V3 prevNormal(x, y), prevPosition(x, y); uint32_t prevLength(l, x, y); float prevVisibility(l, x, y);
 //   void store(l, x, y, uint32_t visibilityBits, uint32_t length).
 // A blended value that is a NaN is stored as 0x7FC00000: which NaN an operation returns is the one thing the machines disagree on.
+// CLAMPED (rtsh_accumulate_visibility_list_clamped): one step between `prev` and the lerp, compiled in by the switch alone -- the
+// unclamped instantiation is the text it was.  `Frames` then also gives
+//   bool box(l, x, y, uint32_t* loKey, uint32_t* hiKey): the smallest and largest clampKey over the contributing taps of the pixel's
+//   window for light l; false when no tap contributes.  The host twin loops over the window, the kernel reduces it in LDS: a minimum
+//   and a maximum of integers, so no order of taps can change a bit.
 struct TemporalList {
     uint32_t count, maxLength, resetLights, history;      // history: 0 on the first frame (no prev_* buffers)
     V3 eyeDelta, right, up, fwd;
@@ -303,8 +308,15 @@ struct TemporalList {
 RTS_HD float dotGrouped(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 RTS_HD uint32_t floatBits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
 
-template <class Frames>
-RTS_HD void accumulatePixel(const TemporalList& f, const Frames& t, int x, int y, int W, int H) {
+// ORDER of the clamp's box: a total order on the non-NaN floats as unsigned integers, -0 < +0.  No non-NaN float has the key
+// kClampNoKey (keys of the non-NaN floats lie in 0x007FFFFF .. 0xFF800000): it marks a tap that does not contribute.
+enum : uint32_t { kClampNoKey = 0xFFFFFFFFu };
+RTS_HD uint32_t clampKey(uint32_t u) { return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u); }
+RTS_HD uint32_t clampUnkey(uint32_t k) { return k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
+RTS_HD bool bitsAreNaN(uint32_t u) { return (u & 0x7FFFFFFFu) > 0x7F800000u; }
+
+template <bool Clamped = false, class Frames>
+RTS_HD void accumulatePixel(const TemporalList& f, const Frames& t, int x, int y, int W, int H, float margin = 0.0f) {
     const V3 np = t.normal(x, y);
     const uint32_t all = (1u << f.count) - 1u;
     const uint32_t onp = isBackground(np) ? 0u : (t.bits(x, y) & all);
@@ -362,7 +374,15 @@ RTS_HD void accumulatePixel(const TemporalList& f, const Frames& t, int x, int y
         const uint32_t n = sw == 0u ? 1u : (m + 1u < f.maxLength ? m + 1u : f.maxLength);
         uint32_t out = cur;
         if (n != 1u) {
-            const float prev = sv / (float)sw, c = asFloat(cur);
+            float prev = sv / (float)sw;
+            const float c = asFloat(cur);
+            if constexpr (Clamped) {
+                uint32_t loKey, hiKey;
+                if (t.box(l, x, y, &loKey, &hiKey)) {
+                    const float lo = asFloat(clampUnkey(loKey)) - margin, hi = asFloat(clampUnkey(hiKey)) + margin;
+                    prev = prev < lo ? lo : (prev > hi ? hi : prev);                              // a NaN fails both and stays
+                }
+            }
             const float v = prev + (c - prev) * (1.0f / (float)n);
             out = v != v ? 0x7FC00000u : floatBits(v);
         }

@@ -711,6 +711,14 @@ int makeTemporalList(const rts_light_list* list, const rtsh_temporal_params* p, 
     return RTS_OK;
 }
 
+// The clamp's own refusals, beside makeTemporalList's: also shared by the host and device forms.
+int checkHistoryClamp(const rtsh_history_clamp* clamp, const void* visibility, const void* visibilityOut) {
+    if (!clamp || clamp->radius > (uint32_t)RTSH_CLAMP_MAX_RADIUS || !std::isfinite(clamp->margin) || !(clamp->margin >= 0.0f))
+        return RTS_ERR_INVALID_ARG;
+    if (visibilityOut == visibility) return RTS_ERR_INVALID_ARG;                      // the pass reads its neighbours' current values
+    return RTS_OK;
+}
+
 namespace {
 // Both frames as accumulatePixel reads them on the host: straight from the buffers.
 struct TemporalFrames {
@@ -734,6 +742,29 @@ struct TemporalFrames {
         lengthsOut[(size_t)l * n + at(x, y)] = (uint8_t)length;
     }
 };
+
+// ... and with the clamp's box: a straight loop over the window.
+struct ClampedTemporalFrames : TemporalFrames {
+    int W_, H_, radius;
+    bool box(uint32_t l, int x, int y, uint32_t* loKey, uint32_t* hiKey) const {
+        uint32_t lo = kClampNoKey, hi = 0u;
+        bool any = false;
+        for (int qy = y - radius; qy <= y + radius; ++qy)
+            for (int qx = x - radius; qx <= x + radius; ++qx) {
+                if (qx < 0 || qx >= W_ || qy < 0 || qy >= H_) continue;
+                if (isBackground(normal(qx, qy)) || !((bits(qx, qy) >> l) & 1u)) continue;
+                const uint32_t u = current(l, qx, qy);
+                if (bitsAreNaN(u)) continue;
+                const uint32_t k = clampKey(u);
+                lo = k < lo ? k : lo;
+                hi = k > hi ? k : hi;
+                any = true;
+            }
+        *loKey = lo;
+        *hiKey = hi;
+        return any;
+    }
+};
 } // namespace
 } // namespace rts_harness
 
@@ -750,5 +781,24 @@ extern "C" int rtsh_accumulate_visibility_list(const rts_light_list* list, const
     const TemporalFrames t{ positions, normals, visibility, prev_positions, prev_normals, prev_visibility, lights_map, prev_lengths,
                             visibility_out, lengths_out, W, n };
     parallelFor(n, 256, threads, [&](size_t i) { accumulatePixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H); });
+    return RTS_OK;
+}
+
+extern "C" int rtsh_accumulate_visibility_list_clamped(const rts_light_list* list, const rtsh_temporal_params* params, const float* positions,
+                                                       const float* normals, const uint8_t* lights_map, const float* visibility,
+                                                       const float* prev_positions, const float* prev_normals,
+                                                       const float* prev_visibility, const uint8_t* prev_lengths, uint32_t W, uint32_t H,
+                                                       float* visibility_out, uint8_t* lengths_out, const rtsh_history_clamp* clamp,
+                                                       int threads) {
+    TemporalList f;
+    int s = makeTemporalList(list, params, positions, normals, visibility, prev_positions, prev_normals, prev_visibility, prev_lengths, W, H,
+                             visibility_out, lengths_out, &f);
+    if (s == RTS_OK) s = checkHistoryClamp(clamp, visibility, visibility_out);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const float margin = clamp->margin;
+    const ClampedTemporalFrames t{ { positions, normals, visibility, prev_positions, prev_normals, prev_visibility, lights_map, prev_lengths,
+                                     visibility_out, lengths_out, W, n }, (int)W, (int)H, (int)clamp->radius };
+    parallelFor(n, 256, threads, [&](size_t i) { accumulatePixel<true>(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H, margin); });
     return RTS_OK;
 }

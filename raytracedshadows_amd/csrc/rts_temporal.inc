@@ -8,6 +8,7 @@ int makeTemporalList(const rts_light_list* list, const rtsh_temporal_params* p, 
                      const void* visibility, const void* prevPositions, const void* prevNormals, const void* prevVisibility,
                      const void* prevLengths, uint32_t W, uint32_t H, const void* visibilityOut, const void* lengthsOut,
                      TemporalList* out);                                                                                 // rts_scene.cpp
+int checkHistoryClamp(const rtsh_history_clamp* clamp, const void* visibility, const void* visibilityOut);              // rts_scene.cpp
 
 // ACCUMULATE KERNEL.  One pixel per lane, one workgroup of 256 lanes per block of 16 x 16 pixels, each of its four waves 16 x 4 of
 // them.  Most of the pass's bytes are streamed -- this frame's texel, its visibility, both outputs -- and a wave's row of 16 pixels is
@@ -51,6 +52,105 @@ __global__ __launch_bounds__(256) void accumulateListKernel(TemporalList f, Temp
     if (x >= W || y >= H) return;
     accumulatePixel(f, t, x, y, W, H);
 }
+
+// CLAMPED ACCUMULATE KERNEL (rtsh_accumulate_visibility_list_clamped_device).  The parent's shape -- 256 lanes per block of 16 x 16
+// pixels, four waves of 16 x 4, one pixel per lane, the pixel's own streams non-temporal -- in front of which the block builds every
+// pixel's box in LDS.  S = 16 + 2r <= 24 is the side of the block's window.
+//   ACTIVITY, once per block: one byte per window pixel, (not background) AND the map byte AND the list's bits; 0 outside the frame.
+//   Per light that can blend (below), one at a time through the same LDS:
+//     KEYS: the window's S x S keys, kClampNoKey where the pixel is inactive for the light or its value a NaN;          barrier A
+//     ROWS: for each of the S window rows and 16 pixel columns the min and max over 2r + 1 keys (kClampNoKey never wins a minimum
+//           and counts as 0 in a maximum: no key of a float is 0);                                                     barrier B
+//     COLUMNS: each lane reduces 2r + 1 row results to its pixel's box, kept in two registers per light.
+//   Then the lanes inside the frame run accumulatePixel<true>, whose box() reads those registers.
+// Window values are read with plain loads (neighbouring blocks share them); the normals and map bytes the pixel rule streams again
+// come from the cache the staging just filled.
+// BARRIERS: every condition around a barrier is a function of kernel arguments alone (f.count, f.history, f.maxLength, f.resetLights,
+// radius), so all four waves of a block reach each barrier or none does; lanes outside the frame stage, reduce and wait like the
+// others and only skip the pixel rule, which has no barrier.  A light's KEYS may be written while a slow wave still reduces the
+// previous light's COLUMNS: those read the row arrays only, and nobody writes the row arrays before barrier A of the next light, which
+// that wave must reach first.  Boxes are needed only where a value is blended: the first frame and max_length 1 skip all of them, a
+// reset light skips its own (DESIGN.md 4.24).
+struct ClampedDeviceFrames : TemporalDeviceFrames {
+    uint32_t lo[8], hi[8];
+    __device__ bool box(uint32_t l, int, int, uint32_t* loKey, uint32_t* hiKey) const {
+        *loKey = lo[l];
+        *hiKey = hi[l];
+        return lo[l] != kClampNoKey;
+    }
+};
+
+__global__ __launch_bounds__(256) void accumulateListClampedKernel(TemporalList f, TemporalDeviceFrames t, int W, int H, int radius,
+                                                                   float margin) {
+    enum { S_MAX = 16 + 2 * RTSH_CLAMP_MAX_RADIUS };
+    __shared__ uint8_t activity[S_MAX * S_MAX];
+    __shared__ uint32_t keys[S_MAX * S_MAX], rowLo[S_MAX * 16], rowHi[S_MAX * 16];
+    const int tx = (int)threadIdx.x, ty = (int)threadIdx.y, lane = ty * 16 + tx;
+    const int x = (int)blockIdx.x * 16 + tx, y = (int)blockIdx.y * 16 + ty;
+    const int S = 16 + 2 * radius, taps = 2 * radius + 1;
+    const int x0 = (int)blockIdx.x * 16 - radius, y0 = (int)blockIdx.y * 16 - radius;
+    ClampedDeviceFrames c{ t, {}, {} };
+#pragma unroll
+    for (int l = 0; l < 8; ++l) { c.lo[l] = kClampNoKey; c.hi[l] = 0u; }
+    const uint32_t all = (1u << f.count) - 1u;
+    const uint32_t boxed = (f.history != 0u && f.maxLength > 1u) ? (all & ~f.resetLights) : 0u;      // lights that can blend: block-uniform
+    if (boxed != 0u) {
+        int wx[3], wy[3];                                              // the lane's window pixels, lane + 256 k: divided once
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { wx[k] = x0 + (lane + 256 * k) % S; wy[k] = y0 + (lane + 256 * k) / S; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int i = lane + 256 * k;
+            if (i >= S * S) break;
+            uint32_t a = 0u;
+            if (wx[k] >= 0 && wx[k] < W && wy[k] >= 0 && wy[k] < H) {
+                const uint64_t q = t.at(wx[k], wy[k]);
+                if (!isBackground(TemporalDeviceFrames::shared(t.normals, q))) a = (t.map ? (uint32_t)t.map[q] : 0xFFu) & all;
+            }
+            activity[i] = (uint8_t)a;
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t l = 0; l < 8; ++l) {
+            if (l >= f.count) break;
+            if (!((boxed >> l) & 1u)) continue;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int i = lane + 256 * k;
+                if (i >= S * S) break;
+                uint32_t key = kClampNoKey;
+                if ((activity[i] >> l) & 1u) {                           // (set only inside the frame)
+                    const uint32_t u = __float_as_uint(t.visibility[(uint64_t)l * t.n + t.at(wx[k], wy[k])]);
+                    if (!bitsAreNaN(u)) key = clampKey(u);
+                }
+                keys[i] = key;
+            }
+            __syncthreads();                                                                                             // barrier A
+            for (int i = lane; i < S * 16; i += 256) {
+                const uint32_t* row = keys + (i >> 4) * S + (i & 15);
+                uint32_t lo = kClampNoKey, hi = 0u;
+                for (int d = 0; d < taps; ++d) {
+                    const uint32_t k = row[d];
+                    lo = k < lo ? k : lo;
+                    hi = (k != kClampNoKey && k > hi) ? k : hi;
+                }
+                rowLo[i] = lo;
+                rowHi[i] = hi;
+            }
+            __syncthreads();                                                                                             // barrier B
+            uint32_t lo = kClampNoKey, hi = 0u;
+            for (int d = 0; d < taps; ++d) {
+                const uint32_t a = rowLo[(ty + d) * 16 + tx], b = rowHi[(ty + d) * 16 + tx];
+                lo = a < lo ? a : lo;
+                hi = b > hi ? b : hi;
+            }
+            c.lo[l] = lo;
+            c.hi[l] = hi;
+        }
+    }
+    if (x >= W || y >= H) return;                                                                     // (after the last barrier)
+    accumulatePixel<true>(f, c, x, y, W, H, margin);
+}
 } // namespace rts_harness
 
 extern "C" int rtsh_accumulate_visibility_list_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_temporal_params* params,
@@ -69,4 +169,23 @@ extern "C" int rtsh_accumulate_visibility_list_device(rts_ctx* ctx, const rts_li
                                                d_lights_map, d_prev_lengths, d_visibility_out, d_lengths_out, W, (uint64_t)W * H };
     return rts_harness::launchPass(ctx, stream, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0, rts_harness::accumulateListKernel, f, t,
                                    (int)W, (int)H);
+}
+
+extern "C" int rtsh_accumulate_visibility_list_clamped_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_temporal_params* params,
+                                                              const float* d_positions, const float* d_normals,
+                                                              const uint8_t* d_lights_map, const float* d_visibility,
+                                                              const float* d_prev_positions, const float* d_prev_normals,
+                                                              const float* d_prev_visibility, const uint8_t* d_prev_lengths, uint32_t W,
+                                                              uint32_t H, float* d_visibility_out, uint8_t* d_lengths_out,
+                                                              const rtsh_history_clamp* clamp, void* stream) {
+    if (!ctx) return RTS_ERR_INVALID_ARG;
+    rts_harness::TemporalList f;
+    int s = rts_harness::makeTemporalList(list, params, d_positions, d_normals, d_visibility, d_prev_positions, d_prev_normals,
+                                          d_prev_visibility, d_prev_lengths, W, H, d_visibility_out, d_lengths_out, &f);
+    if (s == RTS_OK) s = rts_harness::checkHistoryClamp(clamp, d_visibility, d_visibility_out);
+    if (s != RTS_OK) return s;
+    const rts_harness::TemporalDeviceFrames t{ d_positions, d_normals, d_visibility, d_prev_positions, d_prev_normals, d_prev_visibility,
+                                               d_lights_map, d_prev_lengths, d_visibility_out, d_lengths_out, W, (uint64_t)W * H };
+    return rts_harness::launchPass(ctx, stream, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0, rts_harness::accumulateListClampedKernel,
+                                   f, t, (int)W, (int)H, (int)clamp->radius, clamp->margin);
 }

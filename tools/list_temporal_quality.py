@@ -12,7 +12,18 @@ yardstick over the active pixels of
     accumulated  rtsh_accumulate_visibility_list over 2, 4, 8 and 12 frames of a still camera (max_length 32: a running mean) of the raw
                  visibility, and of the filtered one
     single_16    count / 16 of ONE frame of 16 jittered samples: what four accumulated frames of 4 samples are to be compared with
-A record, not a test: every row is written as it comes out."""
+A record, not a test: every row is written as it comes out.
+
+    python tools/list_temporal_quality.py --jump [--out profiles/r28/list_clamp_quality.jsonl]
+
+The neighbourhood clamp (rtsh_accumulate_visibility_list_clamped, DESIGN.md 4.24): the same scenes and light of 3 % of the diagonal;
+the light stands for JUMP_AT frames, then JUMPS sideways by 15 % of the diagonal and stands for AFTER more.  Per frame after the jump,
+the mean absolute difference to the 48-sample trace of the NEW light over its active pixels, of the raw (R = 0) and the filtered
+(R = 2) planes accumulated
+    unclamped    as before: the history of the old light is blended in
+    clamp_r      clamped at r = 1, 2 and 4, margin 0
+    reset        unclamped, with the light in reset_lights on the frame of the jump: its history thrown away
+and a STILL row: the same light standing for all JUMP_AT + AFTER frames, where the clamp can only cost noise reduction."""
 import argparse
 import json
 import os
@@ -25,12 +36,74 @@ sys.path.insert(0, ROOT)
 FRAMES = (2, 4, 8, 12)
 
 
+JUMP_AT, AFTER, JUMP = 8, 4, 0.15
+MODES = ("unclamped", "clamp_1", "clamp_2", "clamp_4", "reset")
+
+
+def jump_rows():
+    from raytracedshadows_amd import api, scenes
+    rows = []
+    for name, sc, W, H in (("cornell_128", scenes.cornell(), 128, 128), ("terrain_96", scenes.terrain(23), 96, 96)):
+        verts, idx = sc.flat()
+        packed = api.BVHBuilder().build(verts, 8, idx, sc.triangle_count).m_packedNodes
+        pos, nrm, _ = api.primary_gbuffer(packed, sc.eye, sc.target, sc.fovy, W, H)
+        k = api.RayTracingConstants.make(sc.eye, sc.light_direction, W, H)
+        diag = float(np.linalg.norm(np.asarray(sc.bbox_max, np.float64) - np.asarray(sc.bbox_min, np.float64)))
+        table = scenes.jitter_offsets(48, 1.0, 19)
+        cam = (sc.eye, sc.target, sc.fovy)
+        moved = tuple(float(v) for v in np.asarray(sc.light_point, np.float64) + np.array([JUMP * diag, 0.0, 0.0]))
+        light = lambda at, n, t=table: api.SoftLightList.make([(api.Light.POINT, at, n, 0, 0.03 * diag)], t)
+        jittered = lambda lst, facing: api.soft_light_list_adaptive(packed, k, lst, (2,), pos, W, H, facing, want_refined=False, tables=(48,))[0]
+        filters = {"raw": api.FilterParams.make(0, 0.9, 0.005 * diag), "filtered": api.FilterParams.make(2, 0.9, 0.005 * diag)}
+        for scenario in ("jump", "still"):
+            frames, planes, truth = JUMP_AT + AFTER, {"raw": [], "filtered": []}, {}
+            for frame in range(frames):
+                at = moved if scenario == "jump" and frame >= JUMP_AT else tuple(sc.light_point)
+                lst = light(at, 4, np.ascontiguousarray(np.roll(table, -frame, axis=0)))
+                facing = api.facing_lights(k, lst.hard_list(), pos, nrm)
+                if at not in truth:
+                    truth[at] = ((facing & 1) != 0, api.soft_light_list(packed, k, light(at, 48), pos, W, H, facing)[0].astype(np.float32)
+                                 / np.float32(48))
+                counts = jittered(lst, facing)
+                for key, fp in filters.items():
+                    planes[key].append((at, lst.hard_list(), facing, api.filter_soft_light_list(lst, fp, pos, nrm, counts, facing)))
+            for key in filters:
+                row = {"scene": name, "scenario": scenario, "planes": key, "jump_at": JUMP_AT, "max_length": 32, "error": {}}
+                for mode in MODES:
+                    if scenario == "still" and mode == "reset":
+                        continue
+                    hist, errors = None, []
+                    for frame, (at, hard, facing, vis) in enumerate(planes[key]):
+                        reset = 1 if mode == "reset" and scenario == "jump" and frame == JUMP_AT else 0
+                        tp = api.TemporalParams.from_cameras(cam, cam, W, H, 0.9, 0.005 * diag, 32, reset)
+                        clamp = api.HistoryClamp.make(int(mode[-1])) if mode.startswith("clamp") else None
+                        hist = api.accumulate_visibility_list(hard, tp, pos, nrm, vis, None if hist is None else (pos, nrm) + hist, facing,
+                                                              clamp=clamp)
+                        if frame >= JUMP_AT:
+                            active, want = truth[at]
+                            errors.append(round(float(np.abs(hist[0][0][active] - want[active]).mean()), 5))
+                    row["error"][mode] = errors
+                active, want = truth[planes[key][-1][0]]
+                row["single_frame"] = round(float(np.abs(planes[key][-1][3][0][active] - want[active]).mean()), 5)
+                rows.append(row)
+                print(json.dumps(row))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
+    ap.add_argument("--jump", action="store_true", help="the light-jump scenario of the neighbourhood clamp instead of the still-camera table")
     args = ap.parse_args()
     from raytracedshadows_amd import api, scenes
-    rows = []
+    rows = jump_rows() if args.jump else []
+    if args.jump:
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                for row in rows:
+                    f.write(json.dumps(row) + "\n")
+        return
     for name, sc, W, H in (("cornell_128", scenes.cornell(), 128, 128), ("terrain_96", scenes.terrain(23), 96, 96)):
         verts, idx = sc.flat()
         packed = api.BVHBuilder().build(verts, 8, idx, sc.triangle_count).m_packedNodes

@@ -3,7 +3,7 @@
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
                            [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]
                                           [--filter R [--spread S] [--plane-eps E] [--normal-cos C]
-                                                      [--temporal F [--orbit DEG] [--max-length L]]]]
+                                                      [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]]]]]
 
 --temporal F (with --soft-list N --filter R): F frames are rendered -- trace, filter, rtsh_accumulate_visibility_list_device with
 ping-pong history -- and the LAST frame is lit from the accumulated visibility.  Frame k traces with the shared offsets table rotated
@@ -127,7 +127,7 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
               f"{[round(float(took[l].mean()), 3) for l in range(count)]}")
 
 
-def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, max_length, probe=0, table=0, colors=""):
+def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, max_length, probe=0, table=0, colors="", clamp=None):
     """`frames` frames of a light list: per frame G-buffer, facing map, trace (the offsets table rotated by one entry per frame), filter
     and accumulation with ping-pong history; the last frame is lit from the accumulated visibility."""
     from raytracedshadows_amd import api, scenes
@@ -160,13 +160,14 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
                                              filt.normal_cos_min, filt.plane_eps, max_length)
         d_prev = None if k == 0 else gbuf[(k - 1) % 2] + hist[(k - 1) % 2]
         api.accumulate_visibility_list_device(ctx, hard, tp, d_pos, d_nrm, d_vis, W, H, hist[k % 2][0], hist[k % 2][1], d_prev=d_prev,
-                                              d_lights_map=d_map)
+                                              d_lights_map=d_map, clamp=clamp)
     last = (frames - 1) % 2
     api.combine_visibility_list_device(ctx, constants, hard, gbuf[last][0], gbuf[last][1], hist[last][0], W, H, d_rgb, d_lights_map=d_map,
                                        colors=colors)
     ctx.synchronize()
     print(f"{frames} frames of {count} lights x {spp} samples, filter radius {filt.radius}, orbit {orbit_deg:g} degree per frame, "
-          f"max_length {max_length}: {(time.time() - t0) * 1e3:.2f} ms (incl. first launches)")
+          f"max_length {max_length}{'' if clamp is None else f', history clamped at r = {clamp.radius}, margin {clamp.margin:g}'}: "
+          f"{(time.time() - t0) * 1e3:.2f} ms (incl. first launches)")
     rgb, lengths, marks = np.zeros((H, W, 3), np.uint8), np.zeros((count, H, W), np.uint8), np.zeros((H, W), np.uint8)
     ctx.d2h(rgb, d_rgb)
     ctx.d2h(lengths, hist[last][1])
@@ -207,6 +208,10 @@ def main():
                          "offsets table rotated by one entry per frame) and light the last one from it")
     ap.add_argument("--orbit", type=float, default=0.0, metavar="DEG", help="with --temporal: turn the eye around the target by DEG per frame")
     ap.add_argument("--max-length", type=int, default=32, metavar="L", help="with --temporal: the longest history, 1..255")
+    ap.add_argument("--clamp", type=int, default=-1, metavar="R",
+                    help="with --temporal: clamp the history into the current visibility's range over a window of (2R+1)^2 pixels, "
+                         "R = 0..4 (rtsh_accumulate_visibility_list_clamped_device)")
+    ap.add_argument("--clamp-margin", type=float, default=0.0, metavar="M", help="with --clamp: widen the range by M on both sides")
     ap.add_argument("--colors", default="", metavar="r,g,b[;r,g,b...]",
                     help="with --soft-list N: the lights' colours, one triple for all of them or N separated by ';' (default 1/N each)")
     args = ap.parse_args()
@@ -224,8 +229,11 @@ def main():
             if args.temporal:
                 if filt is None or args.distance or args.refined:
                     sys.exit("render: --temporal F goes with --soft-list N --filter R, without --distance and --refined")
+                if args.clamp > 4 or not 0.0 <= args.clamp_margin < float("inf"):
+                    sys.exit("render: --clamp R takes 0 <= R <= 4 and a finite --clamp-margin M >= 0")
+                clamp = api.HistoryClamp.make(args.clamp, args.clamp_margin) if args.clamp >= 0 else None
                 return soft_list_temporal(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, filt, args.temporal, args.orbit,
-                                          args.max_length, args.adaptive, args.table, args.colors)
+                                          args.max_length, args.adaptive, args.table, args.colors, clamp)
             return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance,
                              args.colors, filt)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
