@@ -233,7 +233,8 @@ int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_constants* const
  *     nothing and read nothing back; under graph capture each adds ONE kernel node, list and parameters by value (params is read
  *     during the call).  They need no BVH and no alignment of any buffer beyond its element type's.
  *   * OUT OF SCOPE: row ranges and stripes (a stripe would need a halo of R rows from its neighbours), variance guidance.  (The
- *     temporal stage is rtsh_accumulate_visibility_list below.) */
+ *     temporal stage is rtsh_accumulate_visibility_list below; the form for a reach beyond 8 pixels is rtsh_wide_filter_*_light_list*
+ *     further below: another filter, an a-trous one.) */
 enum { RTSH_FILTER_MAX_RADIUS = 8 };
 typedef struct rtsh_filter_params {
     uint32_t radius;          /* R, 0 .. RTSH_FILTER_MAX_RADIUS (8): the window is (2R+1) x (2R+1) pixels */
@@ -404,6 +405,70 @@ int rtsh_accumulate_visibility_list_clamped_device(rts_ctx* ctx, const rts_light
                                                    const float* d_prev_visibility, const uint8_t* d_prev_lengths, uint32_t W, uint32_t H,
                                                    float* d_visibility_out, uint8_t* d_lengths_out, const rtsh_history_clamp* clamp,
                                                    void* stream);
+
+/* THE WIDE FILTER OF A LIGHT LIST'S PLANES: an a-trous filter -- up to five passes of one 5 x 5 kernel whose taps lie 1, 2, 4, 8 and 16
+ * pixels apart -- from the count planes of a soft light list (or the mask of a hard one) to one float visibility plane per light.  Its
+ * cost grows with the logarithm of its reach (2 * (2^passes - 1) pixels: 2, 6, 14, 30, 62), where rtsh_filter_*_light_list* above walk
+ * every tap of a (2R+1)^2 window.  It is ANOTHER filter, not a faster form of that one: the two agree only where the anchors below say
+ * so.  The result is a function of the inputs alone: the planes between passes are 16-BIT FIXED POINT and every sum across pixels is an
+ * INTEGER sum -- a float intermediate would make the result depend on the order of a float sum over taps --, floats appear in per-tap
+ * comparisons and in one division per light at the end; so no order of taps, no tiling and no staging form can change a bit, and the
+ * host form checks the device form bit for bit.  All buffers are whole frames of W x H.
+ *   typedef struct rtsh_wide_filter_params: passes (0 .. RTSH_WIDE_FILTER_MAX_PASSES), normal_cos_min, plane_eps, reserved_ (ignored).
+ * For light l < count:  n_l = max(1, nsamples_l) (1 for a hard list);  S_l = 65535 / n_l by integer division (65535 for a hard light,
+ * 16383 for 4 samples, 1365 for 48);  on(q, l), bg(q), N_q, P_q and c_l(q) are the filter's above.
+ *   INPUT: V_0(q, l) = min(c_l(q), n_l) * S_l.  The CLAMP to n_l is this filter's own (the filter above reads the byte unclamped): it
+ *     makes V fit 16 bits at full precision for every n_l, and the traces never write more than n_l.
+ *   PASS k (k = 0 .. passes - 1, step s = 1 << k), for an ACTIVE pixel p = (x, y) -- not bg(p), and on(p, l) --: over the taps
+ *     q = (x + dx * s, y + dy * s), dx, dy in -2 .. 2, INSIDE THE FRAME, each of the integer weight w = b[|dx|] * b[|dy|],
+ *     b = {6, 4, 1} (the 25 weights sum to 256):  the centre tap is always accepted; another tap is accepted when geom(p, q) -- the
+ *     filter's expression above: not bg(q), the normal test against normal_cos_min, the plane test against plane_eps, a NaN rejects;
+ *     evaluated once per tap for all lights -- and on(q, l) hold.  num = sum of w * V_k(q, l), den = sum of w over the accepted taps
+ *     (num <= 65535 * 256 < 2^24: everything fits 32 bits), and V_(k+1)(p, l) = (2 * num + den) / (2 * den) by integer division: the
+ *     ROUNDED MEAN.  An INACTIVE pixel carries V = 0 in every pass and is never accepted.
+ *   OUTPUT: visibility[l * W * H + p] = (float)V_passes / (float)(n_l * S_l), one correctly rounded division of two integers below
+ *     2^16, formed by the last pass itself; +0.0f at an inactive pixel.
+ * ANCHORS: (1) passes == 0, or thresholds that accept no neighbour at any pass: (float)(c * S_l) / (float)(n_l * S_l), which is
+ * (float)c / (float)n_l bit for bit (c the clamped byte) -- the R = 0 filter's plane wherever c <= n_l, so the visibility combine over
+ * it gives the list combine's bytes.  (2) Where every accepted tap of every pass carries the same value, the rounded mean of equal
+ * values is that value and the result is the centre's quotient.  (3) RANGE: every V_(k+1)(p) lies between the smallest and the largest
+ * accepted V_k; visibility never leaves [0, 1].
+ *   * lights_map may be NULL; positions is always required.  visibility: count * W * H floats; planes of any buffer from `count` up are
+ *     never touched.
+ *   * host forms: multi-threaded (threads: 0 = all host threads); they allocate their own intermediates.
+ *   * device forms: DEVICE buffers, asynchronous on `stream`, allocate nothing and read nothing back.  d_scratch: 2 * count * W * H
+ *     uint16_t (rtsh_wide_filter_scratch_bytes), aligned to 2 bytes and no more, used as two ping-pong sets of count planes (the second
+ *     begins count * W * H elements in); it may be NULL when passes <= 1, and nothing of it is touched then.  Under graph capture a
+ *     call adds exactly max(1, passes) KERNEL nodes on one chain, list and parameters by value (params is read during the call).  No
+ *     BVH, no alignment of any other buffer beyond its element type's.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: what rtsh_filter_*_light_list* refuse of a list; NULL params, positions,
+ *     normals, mask / counts or visibility; passes > RTSH_WIDE_FILTER_MAX_PASSES; a normal_cos_min or plane_eps that is not finite;
+ *     W == 0 or H == 0, W or H above 0x7FFFFFF0; in the device forms a NULL ctx, H above 16 * 65535 (the grid), a NULL d_scratch with
+ *     passes >= 2, and d_visibility equal to d_scratch or to its second half (overlap other than equality is the caller's error).
+ *   * OUT OF SCOPE: distance planes as a guide (the spread guide of the filter above degenerated at these resolutions, and no useful
+ *     spread is known), variance guidance, row ranges and stripes. */
+enum { RTSH_WIDE_FILTER_MAX_PASSES = 5 };
+typedef struct rtsh_wide_filter_params {
+    uint32_t passes;          /* 0 .. RTSH_WIDE_FILTER_MAX_PASSES (5): pass k has its taps 1 << k pixels apart */
+    float    normal_cos_min;  /* a tap needs N_p . N_q >= this */
+    float    plane_eps;       /* ... and |N_p . (P_q - P_p)| <= this (world units) */
+    uint32_t reserved_[5];    /* ignored */
+} rtsh_wide_filter_params;                                                         /* 32 bytes */
+/* 2 * count * W * H * sizeof(uint16_t): the bytes of d_scratch; 0 where count is outside 1 .. 8 or W or H is 0. */
+size_t rtsh_wide_filter_scratch_bytes(uint32_t count, uint32_t W, uint32_t H);
+int rtsh_wide_filter_light_list(const rts_light_list* list, const rtsh_wide_filter_params* params, const float* positions,
+                                const float* normals, const uint8_t* lights_map, const uint8_t* mask, uint32_t W, uint32_t H,
+                                float* visibility, int threads);
+int rtsh_wide_filter_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_filter_params* params, const float* positions,
+                                     const float* normals, const uint8_t* lights_map, const uint8_t* counts, uint32_t W, uint32_t H,
+                                     float* visibility, int threads);
+int rtsh_wide_filter_light_list_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_wide_filter_params* params,
+                                       const float* d_positions, const float* d_normals, const uint8_t* d_lights_map, const uint8_t* d_mask,
+                                       uint32_t W, uint32_t H, float* d_visibility, uint16_t* d_scratch, void* stream);
+int rtsh_wide_filter_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list, const rtsh_wide_filter_params* params,
+                                            const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                            const uint8_t* d_counts, uint32_t W, uint32_t H, float* d_visibility, uint16_t* d_scratch,
+                                            void* stream);
 
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.

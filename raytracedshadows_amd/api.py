@@ -208,6 +208,19 @@ class FilterParams(C.Structure):
         return p
 
 
+class WideFilterParams(C.Structure):
+    """``rtsh_wide_filter_params``: the number of a-trous passes (0..5; the reach is 2 * (2**passes - 1) pixels) and the two geometry
+    thresholds."""
+    _fields_ = [("passes", C.c_uint32), ("normal_cos_min", C.c_float), ("plane_eps", C.c_float), ("reserved_", C.c_uint32 * 5)]
+    MAX_PASSES = 5
+
+    @classmethod
+    def make(cls, passes, normal_cos_min=0.9, plane_eps=0.05):
+        p = cls()
+        p.passes, p.normal_cos_min, p.plane_eps = passes, np.float32(normal_cos_min), np.float32(plane_eps)
+        return p
+
+
 class TemporalParams(C.Structure):
     """``rtsh_temporal_params``: the camera motion (current eye minus previous eye, the previous camera's basis and scales), the two
     geometry thresholds, the longest history (1..255) and the lights that take no history this frame (a bit per light)."""
@@ -484,6 +497,15 @@ _sig("rtsh_filter_light_list_device", C.c_int, C.c_void_p, C.POINTER(LightList),
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_filter_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(FilterParams), C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_wide_filter_scratch_bytes", C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32)
+_sig("rtsh_wide_filter_light_list", C.c_int, C.POINTER(LightList), C.POINTER(WideFilterParams), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_wide_filter_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(WideFilterParams), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_wide_filter_light_list_device", C.c_int, C.c_void_p, C.POINTER(LightList), C.POINTER(WideFilterParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_wide_filter_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(WideFilterParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_combine_visibility_list", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
 _sig("rtsh_combine_visibility_list_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p,
@@ -1574,6 +1596,63 @@ def filter_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d
                                                    C.c_void_p(d_lights_map or 0), C.c_void_p(d_counts), C.c_void_p(d_distances or 0), width,
                                                    height, C.c_void_p(d_visibility), C.c_void_p(stream or 0)),
            "rtsh_filter_soft_light_list_device")
+
+
+def wide_filter_scratch_bytes(count, width, height):
+    """The bytes of ``d_scratch`` of the wide filter's device forms (rtsh_wide_filter_scratch_bytes): 2 * count * width * height
+    uint16."""
+    return int(_lib.rtsh_wide_filter_scratch_bytes(count, width, height))
+
+
+def _wide_filter_list(soft, lights, params, positions, normals, planes, lights_map, threads):
+    name = "rtsh_wide_filter_soft_light_list" if soft else "rtsh_wide_filter_light_list"
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    planes = np.ascontiguousarray(planes, np.uint8)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    if planes.size < (count if soft else 1) * H * W or (lights_map is not None and lights_map.size != H * W) or \
+            (positions is not None and positions.size != H * W * 4):
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    visibility = np.zeros((count, H, W), np.float32)
+    fn = _lib.rtsh_wide_filter_soft_light_list if soft else _lib.rtsh_wide_filter_light_list
+    _check(fn(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals), _ptr_or_none(lights_map), _ptr(planes), W, H,
+              _ptr(visibility), threads), name)
+    return visibility
+
+
+def wide_filter_light_list(light_list, params, positions, normals, mask, lights_map=None, threads=0):
+    """The wide (a-trous) filter of a hard light list's mask on the host (rtsh_wide_filter_light_list): ``float32[count, H, W]``,
+    plane ``l`` the edge-aware average of bit ``l`` of ``mask`` after ``params.passes`` passes (a ``WideFilterParams``)."""
+    return _wide_filter_list(False, light_list, params, positions, normals, mask, lights_map, threads)
+
+
+def wide_filter_soft_light_list(lights, params, positions, normals, counts, lights_map=None, threads=0):
+    """The wide (a-trous) filter of a soft light list's count planes on the host (rtsh_wide_filter_soft_light_list):
+    ``float32[count, H, W]`` visibility."""
+    return _wide_filter_list(True, lights, params, positions, normals, counts, lights_map, threads)
+
+
+def wide_filter_light_list_device(ctx, light_list, params, d_positions, d_normals, d_mask, width, height, d_visibility, d_scratch=None,
+                                  d_lights_map=None, stream=None):
+    """The wide filter of a hard light list's mask on the GPU: device pointers, d_visibility = count planes of width*height floats,
+    d_scratch = ``wide_filter_scratch_bytes(count, width, height)`` bytes (None allowed for passes <= 1); max(1, passes) kernels,
+    asynchronous."""
+    _check(_lib.rtsh_wide_filter_light_list_device(ctx.handle, _ref(light_list), _ref(params), C.c_void_p(d_positions or 0),
+                                                   C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0), C.c_void_p(d_mask), width, height,
+                                                   C.c_void_p(d_visibility), C.c_void_p(d_scratch or 0), C.c_void_p(stream or 0)),
+           "rtsh_wide_filter_light_list_device")
+
+
+def wide_filter_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_counts, width, height, d_visibility, d_scratch=None,
+                                       d_lights_map=None, stream=None):
+    """The wide filter of a soft light list's count planes on the GPU: as ``wide_filter_light_list_device``, over the count planes."""
+    _check(_lib.rtsh_wide_filter_soft_light_list_device(ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions or 0),
+                                                        C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0), C.c_void_p(d_counts), width,
+                                                        height, C.c_void_p(d_visibility), C.c_void_p(d_scratch or 0),
+                                                        C.c_void_p(stream or 0)),
+           "rtsh_wide_filter_soft_light_list_device")
 
 
 def combine_visibility_list(constants, light_list, positions, normals, visibility, lights_map=None, colors=None):

@@ -283,6 +283,82 @@ RTS_HD void filterListPixel(const FilterList& f, const Texels& t, int x, int y, 
     }
 }
 
+// The WIDE FILTER of a light list's planes (include/rts_scene.h, rtsh_wide_filter_light_list / rtsh_wide_filter_soft_light_list), ONE
+// PASS at one pixel: the 5 x 5 taps `step` pixels apart, integer weights b[|dx|] * b[|dy|] with b = {6, 4, 1}, over the taps that pass
+// wideFilterGeom (once per tap) and, per light, the map bit; num and den are integer sums (num <= 65535 * 256), the result is the rounded
+// mean (2 * num + den) / (2 * den) as a 16-bit value, 0 at an inactive pixel.  step == 0 walks no tap: the centre's own value (the
+// passes == 0 form).  `Texels` gives the frame by pixel coordinates (the host twin reads the buffers, the kernel its LDS tile or the
+// buffers): V3 normal(x, y), V3 position(x, y); uint32_t bits(x, y) (the map byte, 0xFF without a map); uint32_t value(x, y, l): V_k --
+// for the first pass wideFilterInput of the count byte (or of the mask's bit), later the previous pass's plane.
+// geom(p, q) of the header for a tap q inside the frame: not background, the normal test, the plane test, each comparison written so that
+// a NaN rejects; the position of a background tap or of one the normal test rejects is never looked at.  A COPY of filterListPixel's
+// expression, operation for operation: calling this from filterListPixel changed the instruction text of filterListKernel<false, true>
+// (the spread test reads D again), and that kernel keeps its text.
+template <class Texels>
+RTS_HD bool wideFilterGeom(const Texels& t, V3 np, V3 pp, int qx, int qy, float normalCosMin, float planeEps) {
+    const V3 nq = t.normal(qx, qy);
+    if (isBackground(nq)) return false;
+    if (!((np.x * nq.x + np.y * nq.y) + np.z * nq.z >= normalCosMin)) return false;
+    const V3 d = sub(t.position(qx, qy), pp);
+    const float h = (np.x * d.x + np.y * d.y) + np.z * d.z;
+    return __builtin_fabsf(h) <= planeEps;
+}
+
+struct WideFilterList { uint32_t count, passes; float normalCosMin, planeEps; uint32_t samples[8], scale[8]; };   // n_l, S_l
+
+RTS_HD uint32_t wideFilterScale(uint32_t samples) { return 65535u / samples; }                            // S_l
+RTS_HD uint32_t wideFilterInput(uint32_t byte, uint32_t samples, uint32_t scale) { return (byte < samples ? byte : samples) * scale; }   // V_0
+// visibility = (float)V / (float)(n_l * S_l): one rounded division
+RTS_HD float wideFilterOutput(uint32_t v, uint32_t samples, uint32_t scale) { return (float)v / (float)(samples * scale); }
+
+template <class Texels>
+RTS_HD void wideFilterPassPixel(const WideFilterList& f, const Texels& t, int x, int y, int W, int H, int step, uint32_t* value8) {
+    const V3 np = t.normal(x, y);
+    const uint32_t onp = isBackground(np) ? 0u : (t.bits(x, y) & ((1u << f.count) - 1u));
+    uint32_t num[8], den[8];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        num[l] = 0u; den[l] = 1u;
+        if (l >= f.count || !((onp >> l) & 1u)) continue;
+        num[l] = 36u * t.value(x, y, l);                                          // the centre tap: always accepted
+        den[l] = 36u;
+    }
+    if (onp != 0u && step > 0) {
+        const V3 pp = t.position(x, y);
+        for (int dy = -2; dy <= 2; ++dy) {
+            const int qy = y + dy * step;
+            if (qy < 0 || qy >= H) continue;
+            const uint32_t wy = dy == 0 ? 6u : ((dy == 1 || dy == -1) ? 4u : 1u);
+            for (int dx = -2; dx <= 2; ++dx) {
+                const int qx = x + dx * step;
+                if (qx < 0 || qx >= W || (dx == 0 && dy == 0)) continue;
+                if (!wideFilterGeom(t, np, pp, qx, qy, f.normalCosMin, f.planeEps)) continue;
+                const uint32_t acc = t.bits(qx, qy) & onp;
+                if (acc == 0u) continue;
+                const uint32_t w = wy * (dx == 0 ? 6u : ((dx == 1 || dx == -1) ? 4u : 1u));
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+                for (uint32_t l = 0; l < 8; ++l) {
+                    if (l >= f.count) break;
+                    if (!((acc >> l) & 1u)) continue;
+                    num[l] += w * t.value(qx, qy, l);
+                    den[l] += w;
+                }
+            }
+        }
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        value8[l] = ((onp >> l) & 1u) ? (2u * num[l] + den[l]) / (2u * den[l]) : 0u;
+    }
+}
+
 // The TEMPORAL ACCUMULATION of a light list's visibility (include/rts_scene.h, rtsh_accumulate_visibility_list), one pixel: reproject
 // through the previous camera onto a 1/32-pixel grid, four bilinear taps of INTEGER weights (they sum to 1024), each accepted by the
 // geometry (inside the frame, not background, normal, plane distance: once per tap, a 4-bit mask) and per light by its history length;

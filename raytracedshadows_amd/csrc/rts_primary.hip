@@ -195,3 +195,4 @@ extern "C" int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_const
 
 #include "rts_filter.inc"   // the filter of a light list's planes and the visibility combine
 #include "rts_temporal.inc" // the temporal accumulation of a light list's visibility
+#include "rts_wide_filter.inc" // the wide (a-trous) filter of a light list's planes

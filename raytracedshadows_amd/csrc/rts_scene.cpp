@@ -11,6 +11,7 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <new>
 #include <thread>
 #include <vector>
 
@@ -666,6 +667,113 @@ extern "C" int rtsh_combine_visibility_list(const rts_constants* k, const rts_li
         combineVisibilityPixel(f, p4, n4, bits, [&](uint32_t l) { return visibility[(size_t)l * n + i]; }, rgb + i * 3);
     });
     return RTS_OK;
+}
+
+// ---- the wide filter of a light list's planes (include/rts_scene.h; per-pixel rule in rts_closest_hit.h: wideFilterPassPixel) ----
+namespace rts_harness {
+// Shared by the host and device forms: the refusals of the parameters and of the frame, and the condensed form the per-pixel rule reads.
+int makeWideFilterList(uint32_t count, const uint32_t* nsamples, const rtsh_wide_filter_params* p, uint32_t W, uint32_t H,
+                       WideFilterList* out) {
+    if (!p || !out || p->passes > (uint32_t)RTSH_WIDE_FILTER_MAX_PASSES || !std::isfinite(p->normal_cos_min) || !std::isfinite(p->plane_eps))
+        return RTS_ERR_INVALID_ARG;
+    if (W == 0 || H == 0 || W > 0x7FFFFFF0u || H > 0x7FFFFFF0u) return RTS_ERR_INVALID_ARG;
+    out->count = count;
+    out->passes = p->passes;
+    out->normalCosMin = p->normal_cos_min;
+    out->planeEps = p->plane_eps;
+    for (uint32_t l = 0; l < 8; ++l) {
+        out->samples[l] = l < count && nsamples && nsamples[l] > 1u ? nsamples[l] : 1u;
+        out->scale[l] = wideFilterScale(out->samples[l]);
+    }
+    return RTS_OK;
+}
+
+int makeWideFilterHardList(const rts_light_list* list, const rtsh_wide_filter_params* p, uint32_t W, uint32_t H, WideFilterList* out) {
+    if (!rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
+    return makeWideFilterList(list->count, nullptr, p, W, H, out);
+}
+
+int makeWideFilterSoftList(const rts_soft_light_list* list, const rtsh_wide_filter_params* p, uint32_t W, uint32_t H, WideFilterList* out) {
+    if (!rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    uint32_t ns[8];
+    for (uint32_t l = 0; l < list->count; ++l) ns[l] = list->lights[l].nsamples;
+    return makeWideFilterList(list->count, ns, p, W, H, out);
+}
+
+namespace {
+// The frame as wideFilterPassPixel reads it on the host: the G-buffer and the map straight from the buffers, V_k from the bytes (the
+// first pass) or from the previous pass's 16-bit planes.
+template <bool HARD>
+struct WideFrameTexels {
+    const float *positions, *normals;
+    const uint8_t *map, *bytes;                  // bytes: the first pass's input, else NULL
+    const uint16_t* values;                      // the previous pass's planes
+    const uint32_t *samples, *scale;
+    size_t W, n;
+    size_t at(int x, int y) const { return (size_t)y * W + (size_t)x; }
+    V3 normal(int x, int y) const { const float* v = normals + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
+    V3 position(int x, int y) const { const float* v = positions + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
+    uint32_t bits(int x, int y) const { return map ? map[at(x, y)] : 0xFFu; }
+    uint32_t value(int x, int y, uint32_t l) const {
+        if (!bytes) return values[(size_t)l * n + at(x, y)];
+        return wideFilterInput(HARD ? (bytes[at(x, y)] >> l) & 1u : bytes[(size_t)l * n + at(x, y)], samples[l], scale[l]);
+    }
+};
+
+template <bool HARD>
+int wideFilterFrames(const WideFilterList& f, const float* positions, const float* normals, const uint8_t* lights_map, const uint8_t* planes,
+                     uint32_t W, uint32_t H, float* visibility, int threads) {
+    const size_t n = (size_t)W * H;
+    std::vector<uint16_t> scratch;
+    try {
+        if (f.passes >= 2u) scratch.resize(2 * (size_t)f.count * n);
+    } catch (const std::bad_alloc&) {
+        return RTS_ERR_CAPACITY;
+    }
+    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
+    for (uint32_t k = 0; k < launches; ++k) {
+        const bool first = k == 0u, last = k + 1u == launches;
+        const int step = f.passes == 0u ? 0 : 1 << k;
+        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * (size_t)f.count * n;
+        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * (size_t)f.count * n;
+        const WideFrameTexels<HARD> t{ positions, normals, lights_map, first ? planes : nullptr, in, f.samples, f.scale, W, n };
+        parallelFor(n, 256, threads, [&](size_t i) {
+            uint32_t v[8];
+            wideFilterPassPixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H, step, v);
+            for (uint32_t l = 0; l < f.count; ++l) {
+                if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
+                else out[(size_t)l * n + i] = (uint16_t)v[l];
+            }
+        });
+    }
+    return RTS_OK;
+}
+} // namespace
+} // namespace rts_harness
+
+extern "C" size_t rtsh_wide_filter_scratch_bytes(uint32_t count, uint32_t W, uint32_t H) {
+    if (count == 0 || count > 8u || W == 0 || H == 0) return 0;
+    return 2 * (size_t)count * (size_t)W * (size_t)H * sizeof(uint16_t);
+}
+
+extern "C" int rtsh_wide_filter_light_list(const rts_light_list* list, const rtsh_wide_filter_params* params, const float* positions,
+                                           const float* normals, const uint8_t* lights_map, const uint8_t* mask, uint32_t W, uint32_t H,
+                                           float* visibility, int threads) {
+    if (!positions || !normals || !mask || !visibility) return RTS_ERR_INVALID_ARG;
+    WideFilterList f;
+    const int s = makeWideFilterHardList(list, params, W, H, &f);
+    if (s != RTS_OK) return s;
+    return wideFilterFrames<true>(f, positions, normals, lights_map, mask, W, H, visibility, threads);
+}
+
+extern "C" int rtsh_wide_filter_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_filter_params* params, const float* positions,
+                                                const float* normals, const uint8_t* lights_map, const uint8_t* counts, uint32_t W,
+                                                uint32_t H, float* visibility, int threads) {
+    if (!positions || !normals || !counts || !visibility) return RTS_ERR_INVALID_ARG;
+    WideFilterList f;
+    const int s = makeWideFilterSoftList(list, params, W, H, &f);
+    if (s != RTS_OK) return s;
+    return wideFilterFrames<false>(f, positions, normals, lights_map, counts, W, H, visibility, threads);
 }
 
 // ---- the temporal accumulation of a light list's visibility (include/rts_scene.h; per-pixel rule in rts_closest_hit.h: accumulatePixel) ----

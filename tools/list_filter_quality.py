@@ -1,6 +1,7 @@
 """What the list filter buys in image quality, measured on the CPU with the host twins alone (no GPU): DESIGN.md 4.22.
 
     python tools/list_filter_quality.py [--radius 4] [--out profiles/r25/list_filter_quality.jsonl]
+    python tools/list_filter_quality.py --wide [--light 0.1] [--out profiles/r29/list_wide_filter_quality.jsonl]      
 
 Scenes: the cornell box at 128 x 128 and the terrain at 96 x 96 (the scenes of tests/golden/cornell_128.npz and terrain_96.npz), one
 area light at the scene's point light, its radius --light (default 3 %) of the scene's diagonal, through the facing map.  The yardstick is the UNFILTERED
@@ -9,6 +10,8 @@ visibility of 48 samples (count / 48).  Per scene and per trace of 4 samples -- 
     raw       count / 4, unfiltered        (the number the filter has to beat)
     filtered  rtsh_filter_soft_light_list at --radius, N.N' >= 0.9, plane distance <= 0.5 % of the diagonal
     guided    the same with the distance planes of a 4-sample distance trace and spread 0.05 (plain trace only)
+--wide: instead, per scene and trace, one row per tent radius R = 1, 2, 4, 8 ("filter": "tent") and one per number of passes 1 .. 4 of the
+wide (a-trous) filter rtsh_wide_filter_soft_light_list ("filter": "wide", its reach 2, 6, 14, 30 pixels), same thresholds, same measure.
 A record, not a test: every row is written as it comes out."""
 import argparse
 import json
@@ -25,6 +28,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--radius", type=int, default=4)
     ap.add_argument("--light", type=float, default=0.03, help="the light's radius as a share of the scene's diagonal")
+    ap.add_argument("--wide", action="store_true", help="rows for R = 1, 2, 4, 8 and for 1 .. 4 passes of the wide filter")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from raytracedshadows_amd import api, scenes
@@ -48,6 +52,21 @@ def main():
         dist, _ = api.soft_light_list_distance(packed, k, four, pos, W, H, facing)
         mad = lambda v: float(np.abs(v[active] - truth[active]).mean())
         for trace, counts in traces.items():
+            if args.wide:
+                base = {"scene": name, "trace": trace, "light": args.light, "active_pixels": int(active.sum()),
+                        "penumbra_pixels": int(((truth > 0) & (truth < 1) & active).sum()),
+                        "raw": mad(counts[0].astype(np.float32) / np.float32(4))}
+                for radius in (1, 2, 4, 8):
+                    q = api.FilterParams.make(radius, 0.9, 0.005 * diag)
+                    rows.append(dict(base, filter="tent", radius=radius, reach=radius,
+                                     filtered=mad(api.filter_soft_light_list(four, q, pos, nrm, counts, facing)[0])))
+                    print(json.dumps(rows[-1]))
+                for passes in (1, 2, 3, 4):
+                    q = api.WideFilterParams.make(passes, 0.9, 0.005 * diag)
+                    rows.append(dict(base, filter="wide", passes=passes, reach=2 * (2 ** passes - 1),
+                                     filtered=mad(api.wide_filter_soft_light_list(four, q, pos, nrm, counts, facing)[0])))
+                    print(json.dumps(rows[-1]))
+                continue
             row = {"scene": name, "trace": trace, "radius": args.radius, "light": args.light, "active_pixels": int(active.sum()),
                    "penumbra_pixels": int(((truth > 0) & (truth < 1) & active).sum()),
                    "raw": mad(counts[0].astype(np.float32) / np.float32(4)),

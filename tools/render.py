@@ -2,7 +2,7 @@
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
                            [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]
-                                          [--filter R [--spread S] [--plane-eps E] [--normal-cos C]
+                                          [--filter R [--spread S] | --filter-passes K] [--plane-eps E] [--normal-cos C]
                                                       [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]]]]]
 
 --temporal F (with --soft-list N --filter R): F frames are rendered -- trace, filter, rtsh_accumulate_visibility_list_device with
@@ -13,6 +13,9 @@ the longest history.
 --filter R (with --soft-list N): between trace and image the count planes go through rtsh_filter_soft_light_list_device -- an edge-aware
 tent window of (2R+1)^2 pixels that stops at normal and depth edges (--normal-cos, --plane-eps) -- and the frame is lit from the float
 visibility planes by rtsh_combine_visibility_list_device; with --distance the distance planes guide the filter (--spread).
+--filter-passes K (in place of --filter R; the two exclude each other): the wide a-trous filter rtsh_wide_filter_soft_light_list_device,
+K = 0..5 passes of 5 x 5 taps 1, 2, 4, 8 and 16 pixels apart -- a reach of 2, 6, 14, 30, 62 pixels --, same thresholds, no distance
+guide; it feeds --temporal and --clamp exactly as --filter does.
 --cull: the shadow pass traces only the pixels of the facing mark (rtsh_facing_active_device: not the background, not the surfaces
 that face away from the light) -- the same image, byte for byte.
 --adaptive K: the soft light (--spp, or a soft config) is traced by rts_trace_shadow_mask_adaptive* with a probe of K samples: the
@@ -90,11 +93,13 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
     rgb = np.zeros((H, W, 3), np.uint8)
     if filt is not None:                                 # trace -> filter -> visibility combine, all on the device
         d_vis = ctx.malloc(count * W * H * 4)
-        api.filter_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_lights_map=d_map, d_distances=d_dist)
+        wide = isinstance(filt, api.WideFilterParams)
+        d_scratch = ctx.malloc(api.wide_filter_scratch_bytes(count, W, H)) if wide and filt.passes >= 2 else None
+        list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, d_dist, d_scratch)
         api.combine_visibility_list_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, d_vis, W, H, d_rgb, d_lights_map=d_map,
                                            colors=colors)
-        print(f"filtered: radius {filt.radius}, N.N' >= {filt.normal_cos_min:g}, plane distance <= {filt.plane_eps:g}"
-              + (f", distance-guided with spread {filt.spread[0]:g}" if d_dist else ""))
+        print(f"filtered: {filter_words(api, filt)}, N.N' >= {filt.normal_cos_min:g}, plane distance <= {filt.plane_eps:g}"
+              + (f", distance-guided with spread {filt.spread[0]:g}" if d_dist and not wide else ""))
     else:
         api.combine_soft_light_list_device(ctx, wl.constants, lights, d_pos, d_nrm, d_counts, W, H, d_rgb, d_lights_map=d_map, colors=colors)
     ctx.synchronize()
@@ -127,6 +132,21 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
               f"{[round(float(took[l].mean()), 3) for l in range(count)]}")
 
 
+def list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, d_dist=None, d_scratch=None):
+    """The filter stage of a soft light list: the tent filter of a ``FilterParams`` (--filter R) or the wide a-trous filter of a
+    ``WideFilterParams`` (--filter-passes K, which takes a scratch and no distances)."""
+    if isinstance(filt, api.WideFilterParams):
+        api.wide_filter_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_scratch=d_scratch, d_lights_map=d_map)
+    else:
+        api.filter_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_lights_map=d_map, d_distances=d_dist)
+
+
+def filter_words(api, filt):
+    if isinstance(filt, api.WideFilterParams):
+        return f"{filt.passes} a-trous passes (reach {2 * (2 ** filt.passes - 1)} pixels)"
+    return f"radius {filt.radius}"
+
+
 def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, max_length, probe=0, table=0, colors="", clamp=None):
     """`frames` frames of a light list: per frame G-buffer, facing map, trace (the offsets table rotated by one entry per frame), filter
     and accumulation with ping-pong history; the last frame is lit from the accumulated visibility."""
@@ -141,6 +161,7 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
     gbuf = [(ctx.malloc(n * 16), ctx.malloc(n * 16)) for _ in range(2)]
     hist = [(ctx.malloc(count * n * 4), ctx.malloc(count * n)) for _ in range(2)]
     d_map, d_counts, d_vis, d_rgb = ctx.malloc(n), ctx.malloc(count * n), ctx.malloc(count * n * 4), ctx.malloc(n * 3)
+    d_scratch = ctx.malloc(api.wide_filter_scratch_bytes(count, W, H)) if isinstance(filt, api.WideFilterParams) and filt.passes >= 2 else None
     eyes = [orbit(sc.eye, sc.target, orbit_deg * (k - (frames - 1))) for k in range(frames)]      # the last frame is the scene's own camera
     t0 = time.time()
     for k in range(frames):
@@ -155,7 +176,7 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
                                                       tables=(table,) * count if table else None)
         else:
             ctx.trace_soft_light_list_device(constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
-        api.filter_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_lights_map=d_map)
+        list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, None, d_scratch)
         tp = api.TemporalParams.from_cameras((eyes[k], sc.target, sc.fovy), (eyes[max(k - 1, 0)], sc.target, sc.fovy), W, H,
                                              filt.normal_cos_min, filt.plane_eps, max_length)
         d_prev = None if k == 0 else gbuf[(k - 1) % 2] + hist[(k - 1) % 2]
@@ -165,7 +186,7 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
     api.combine_visibility_list_device(ctx, constants, hard, gbuf[last][0], gbuf[last][1], hist[last][0], W, H, d_rgb, d_lights_map=d_map,
                                        colors=colors)
     ctx.synchronize()
-    print(f"{frames} frames of {count} lights x {spp} samples, filter radius {filt.radius}, orbit {orbit_deg:g} degree per frame, "
+    print(f"{frames} frames of {count} lights x {spp} samples, filter {filter_words(api, filt)}, orbit {orbit_deg:g} degree per frame, "
           f"max_length {max_length}{'' if clamp is None else f', history clamped at r = {clamp.radius}, margin {clamp.margin:g}'}: "
           f"{(time.time() - t0) * 1e3:.2f} ms (incl. first launches)")
     rgb, lengths, marks = np.zeros((H, W, 3), np.uint8), np.zeros((count, H, W), np.uint8), np.zeros((H, W), np.uint8)
@@ -200,6 +221,9 @@ def main():
     ap.add_argument("--filter", type=int, default=-1, metavar="R",
                     help="with --soft-list N: filter the count planes (rtsh_filter_soft_light_list_device, a window of (2R+1)^2 pixels, "
                          "R = 0..8) and light the frame from the visibility planes; with --distance the distance planes guide the filter")
+    ap.add_argument("--filter-passes", type=int, default=-1, metavar="K",
+                    help="with --soft-list N, in place of --filter R: the wide a-trous filter (rtsh_wide_filter_soft_light_list_device), "
+                         "K = 0..5 passes of 5 x 5 taps 1, 2, 4, 8, 16 pixels apart (reach 2, 6, 14, 30, 62 pixels); without --distance")
     ap.add_argument("--spread", type=float, default=0.25, help="with --filter and --distance: the penumbra width per unit of blocker distance")
     ap.add_argument("--plane-eps", type=float, default=0.05, help="with --filter: the largest plane distance of an accepted tap (world units)")
     ap.add_argument("--normal-cos", type=float, default=0.9, help="with --filter: the smallest N.N' of an accepted tap")
@@ -225,10 +249,18 @@ def main():
         if args.soft_list:
             if not -1 <= args.filter <= api.FilterParams.MAX_RADIUS:
                 sys.exit("render: --filter R takes 0 <= R <= 8")
+            if not -1 <= args.filter_passes <= api.WideFilterParams.MAX_PASSES:
+                sys.exit("render: --filter-passes K takes 0 <= K <= 5")
+            if args.filter >= 0 and args.filter_passes >= 0:
+                sys.exit("render: --filter R and --filter-passes K exclude each other")
+            if args.filter_passes >= 0 and args.distance:
+                sys.exit("render: --filter-passes K takes no distance guide: leave --distance out")
             filt = api.FilterParams.make(args.filter, args.normal_cos, args.plane_eps, args.spread) if args.filter >= 0 else None
+            if args.filter_passes >= 0:
+                filt = api.WideFilterParams.make(args.filter_passes, args.normal_cos, args.plane_eps)
             if args.temporal:
                 if filt is None or args.distance or args.refined:
-                    sys.exit("render: --temporal F goes with --soft-list N --filter R, without --distance and --refined")
+                    sys.exit("render: --temporal F goes with --soft-list N and --filter R or --filter-passes K, without --distance and --refined")
                 if args.clamp > 4 or not 0.0 <= args.clamp_margin < float("inf"):
                     sys.exit("render: --clamp R takes 0 <= R <= 4 and a finite --clamp-margin M >= 0")
                 clamp = api.HistoryClamp.make(args.clamp, args.clamp_margin) if args.clamp >= 0 else None
