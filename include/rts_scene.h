@@ -446,7 +446,7 @@ int rtsh_accumulate_visibility_list_clamped_device(rts_ctx* ctx, const rts_light
  *     W == 0 or H == 0, W or H above 0x7FFFFFF0; in the device forms a NULL ctx, H above 16 * 65535 (the grid), a NULL d_scratch with
  *     passes >= 2, and d_visibility equal to d_scratch or to its second half (overlap other than equality is the caller's error).
  *   * OUT OF SCOPE: distance planes as a guide (the spread guide of the filter above degenerated at these resolutions, and no useful
- *     spread is known), variance guidance, row ranges and stripes. */
+ *     spread is known), row ranges and stripes.  (Variance guidance is rtsh_wide_filter_guided_soft_light_list below.) */
 enum { RTSH_WIDE_FILTER_MAX_PASSES = 5 };
 typedef struct rtsh_wide_filter_params {
     uint32_t passes;          /* 0 .. RTSH_WIDE_FILTER_MAX_PASSES (5): pass k has its taps 1 << k pixels apart */
@@ -469,6 +469,62 @@ int rtsh_wide_filter_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_l
                                             const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
                                             const uint8_t* d_counts, uint32_t W, uint32_t H, float* d_visibility, uint16_t* d_scratch,
                                             void* stream);
+
+/* THE VARIANCE-GUIDED WIDE FILTER OF A SOFT LIGHT LIST'S PLANES: rtsh_wide_filter_soft_light_list above with SVGF's luminance stop, so
+ * that the passes blur noise and stop at a sharp shadow edge.  A tap is accepted for a light only if its value lies within a tolerance
+ * T of the centre's, and T comes from the count plane itself: a pixel with c of n samples unoccluded has a Bernoulli variance
+ * proportional to c * (n - c) -- an integer, a function of the inputs alone, no history.  Where the samples of a neighbourhood are
+ * unanimous T is 0 and the edge stays; where they disagree the filter blurs.  Everything of the unguided filter holds (16-bit planes,
+ * integer sums, bit-for-bit host and device forms); the notation -- n_l, S_l, V_0, geom, on, bg, b = {6, 4, 1} -- is its own.
+ *   typedef struct rtsh_wide_guide_params: passes, normal_cos_min, plane_eps as in rtsh_wide_filter_params; guide_k4: the tolerance k
+ *     in QUARTER units, 0 .. 255 (k = 3 standard deviations is 12); reserved_ (ignored).
+ *   ENERGY: E(q, l) = V_0(q, l) * (n_l * S_l - V_0(q, l)) = c (n - c) S^2, at most about 2^30.
+ *   NEIGHBOURHOOD SUM, for an active pixel p and a light with n_l >= 2: over the 3 x 3 pixels q around p that are INSIDE THE FRAME, not
+ *     bg(q), and have on(q, l), weights w = {1, 2, 1} x {1, 2, 1}:  G = sum of w * E(q, l),  D = sum of w (the centre always counts:
+ *     D >= 4).  There is NO geom TEST here: the worst a pixel of a foreign surface can do is RAISE the tolerance; it never makes the
+ *     filter cross a geometry edge -- the pass below still applies geom to every tap --, and leaving the test out keeps the sum to
+ *     nine integer loads.
+ *   THRESHOLD: T(p, l) = min(65535, isqrt((guide_k4^2 * G) / (16 * D * n_l))), the division an integer division, isqrt the exact
+ *     integer square root; everything fits unsigned 64 bits (guide_k4^2 < 2^16, G < 2^35).  It is k * S_l * sqrt(mean of c (n - c) / n)
+ *     rounded down.  For n_l <= 1 (a hard light inside a soft list) the estimate carries no information: T = 65535, and that light is
+ *     filtered exactly as the unguided filter does.
+ *   PASS k: the unguided filter's pass with one change: a tap other than the centre is accepted for light l when geom(p, q) and
+ *     on(q, l) hold AND |V_k(q, l) - V_k(p, l)| <= T(p, l).  Acceptance, num and den are per light; the rounded mean
+ *     (2 * num + den) / (2 * den) and the final quotient are unchanged.  T comes from V_0 and is THE SAME AT EVERY PASS.
+ * There is NO guided form for a hard list: its c (1 - c) is 0 everywhere.
+ * ANCHORS: (1) guide_k4 == 0 gives the passes == 0 plane bit for bit whatever passes is: with T = 0 only equal values are accepted, and
+ * the rounded mean of equal values is that value.  (2) Plane l of a light with n_l <= 1 is bit for bit the plane of
+ * rtsh_wide_filter_soft_light_list for the same inputs.  (3) A pixel whose 3 x 3 neighbourhood is unanimous for light l -- every
+ * counted c is 0 or n_l -- keeps its own quotient through every pass.  (4) RANGE: every V_(k+1)(p) lies between the smallest and the
+ * largest accepted V_k.  (5) passes == 0 is the unguided conversion, (float)min(c, n_l) / (float)n_l.
+ *   * buffers, lights_map, threads, stream and graph capture as for rtsh_wide_filter_soft_light_list*: a device call adds exactly
+ *     max(1, passes) KERNEL nodes on one chain, list and parameters by value.  The FIRST pass computes T; for passes >= 2 it writes T to
+ *     a THIRD set of count planes of d_scratch, of which later passes read one uint16_t per pixel and light.
+ *   * d_scratch: 3 * count * W * H uint16_t (rtsh_wide_filter_guided_scratch_bytes): the two ping-pong sets, then the planes of T; it
+ *     may be NULL when passes <= 1, and nothing of it is touched then.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything rtsh_wide_filter_soft_light_list* refuse (d_visibility equal
+ *     to the start of any of the three sets of d_scratch included); guide_k4 > 255; a NULL d_scratch with passes >= 2.
+ *   * OUT OF SCOPE: variance propagated through the passes (T is the first pass's at every pass), a temporal variance from the
+ *     accumulation stage, a guide for the tent filter rtsh_filter_*_light_list*. */
+enum { RTSH_WIDE_GUIDE_MAX_K4 = 255 };
+typedef struct rtsh_wide_guide_params {
+    uint32_t passes;          /* 0 .. RTSH_WIDE_FILTER_MAX_PASSES (5) */
+    float    normal_cos_min;  /* a tap needs N_p . N_q >= this */
+    float    plane_eps;       /* ... and |N_p . (P_q - P_p)| <= this (world units) */
+    uint32_t guide_k4;        /* the tolerance in quarter standard deviations, 0 .. RTSH_WIDE_GUIDE_MAX_K4 (255) */
+    uint32_t reserved_[4];    /* ignored */
+} rtsh_wide_guide_params;                                                          /* 32 bytes */
+/* 3 * count * W * H * sizeof(uint16_t): the bytes of d_scratch; 0 where count is outside 1 .. 8 or W or H is 0. */
+size_t rtsh_wide_filter_guided_scratch_bytes(uint32_t count, uint32_t W, uint32_t H);
+/* T of the rule above from its parts (G < 2^35, 4 <= D <= 16, 2 <= n <= 48, guide_k4 <= 255): what host twin and kernels evaluate. */
+uint32_t rtsh_wide_guide_threshold(uint64_t G, uint32_t D, uint32_t n, uint32_t guide_k4);
+int rtsh_wide_filter_guided_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_guide_params* params, const float* positions,
+                                            const float* normals, const uint8_t* lights_map, const uint8_t* counts, uint32_t W,
+                                            uint32_t H, float* visibility, int threads);
+int rtsh_wide_filter_guided_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list, const rtsh_wide_guide_params* params,
+                                                   const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                   const uint8_t* d_counts, uint32_t W, uint32_t H, float* d_visibility,
+                                                   uint16_t* d_scratch, void* stream);
 
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.

@@ -221,6 +221,21 @@ class WideFilterParams(C.Structure):
         return p
 
 
+class WideGuideParams(C.Structure):
+    """``rtsh_wide_guide_params``: ``WideFilterParams`` plus ``guide_k4``, the variance guide's tolerance in quarter standard deviations
+    (0..255; 12 is k = 3, 0 accepts equal values only)."""
+    _fields_ = [("passes", C.c_uint32), ("normal_cos_min", C.c_float), ("plane_eps", C.c_float), ("guide_k4", C.c_uint32),
+                ("reserved_", C.c_uint32 * 4)]
+    MAX_PASSES = 5
+    MAX_K4 = 255
+
+    @classmethod
+    def make(cls, passes, guide_k4=12, normal_cos_min=0.9, plane_eps=0.05):
+        p = cls()
+        p.passes, p.guide_k4, p.normal_cos_min, p.plane_eps = passes, guide_k4, np.float32(normal_cos_min), np.float32(plane_eps)
+        return p
+
+
 class TemporalParams(C.Structure):
     """``rtsh_temporal_params``: the camera motion (current eye minus previous eye, the previous camera's basis and scales), the two
     geometry thresholds, the longest history (1..255) and the lights that take no history this frame (a bit per light)."""
@@ -505,6 +520,12 @@ _sig("rtsh_wide_filter_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.PO
 _sig("rtsh_wide_filter_light_list_device", C.c_int, C.c_void_p, C.POINTER(LightList), C.POINTER(WideFilterParams), C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_wide_filter_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(WideFilterParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_wide_filter_guided_scratch_bytes", C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32)
+_sig("rtsh_wide_guide_threshold", C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32)
+_sig("rtsh_wide_filter_guided_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(WideGuideParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_wide_filter_guided_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(WideGuideParams), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_combine_visibility_list", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
@@ -1653,6 +1674,48 @@ def wide_filter_soft_light_list_device(ctx, lights, params, d_positions, d_norma
                                                         height, C.c_void_p(d_visibility), C.c_void_p(d_scratch or 0),
                                                         C.c_void_p(stream or 0)),
            "rtsh_wide_filter_soft_light_list_device")
+
+
+def wide_filter_guided_scratch_bytes(count, width, height):
+    """The bytes of ``d_scratch`` of the guided wide filter's device form (rtsh_wide_filter_guided_scratch_bytes): 3 * count * width *
+    height uint16 -- two ping-pong sets and the planes of the threshold."""
+    return int(_lib.rtsh_wide_filter_guided_scratch_bytes(count, width, height))
+
+
+def wide_guide_threshold(G, D, n, guide_k4):
+    """``T`` of the guided wide filter from its parts (rtsh_wide_guide_threshold): min(65535, isqrt(guide_k4**2 * G // (16 * D * n)))."""
+    return int(_lib.rtsh_wide_guide_threshold(G, D, n, guide_k4))
+
+
+def wide_filter_guided_soft_light_list(lights, params, positions, normals, counts, lights_map=None, threads=0):
+    """The variance-guided wide (a-trous) filter of a soft light list's count planes on the host
+    (rtsh_wide_filter_guided_soft_light_list): ``float32[count, H, W]`` visibility; ``params`` a ``WideGuideParams``."""
+    name = "rtsh_wide_filter_guided_soft_light_list"
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    counts = np.ascontiguousarray(counts, np.uint8)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    if counts.size < count * H * W or (lights_map is not None and lights_map.size != H * W) or \
+            (positions is not None and positions.size != H * W * 4):
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    visibility = np.zeros((count, H, W), np.float32)
+    _check(_lib.rtsh_wide_filter_guided_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
+                                                        _ptr_or_none(lights_map), _ptr(counts), W, H, _ptr(visibility), threads), name)
+    return visibility
+
+
+def wide_filter_guided_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_counts, width, height, d_visibility,
+                                              d_scratch=None, d_lights_map=None, stream=None):
+    """The variance-guided wide filter of a soft light list's count planes on the GPU: device pointers, d_visibility = count planes of
+    width*height floats, d_scratch = ``wide_filter_guided_scratch_bytes(count, width, height)`` bytes (None allowed for passes <= 1);
+    max(1, passes) kernels, asynchronous."""
+    _check(_lib.rtsh_wide_filter_guided_soft_light_list_device(ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions or 0),
+                                                               C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0), C.c_void_p(d_counts),
+                                                               width, height, C.c_void_p(d_visibility), C.c_void_p(d_scratch or 0),
+                                                               C.c_void_p(stream or 0)),
+           "rtsh_wide_filter_guided_soft_light_list_device")
 
 
 def combine_visibility_list(constants, light_list, positions, normals, visibility, lights_map=None, colors=None):

@@ -359,6 +359,118 @@ RTS_HD void wideFilterPassPixel(const WideFilterList& f, const Texels& t, int x,
     }
 }
 
+// The VARIANCE-GUIDED wide filter of a soft light list's planes (include/rts_scene.h, rtsh_wide_filter_guided_soft_light_list): the
+// threshold T(p, l) of the header from the 3 x 3 neighbourhood of V_0, and one pass that accepts a tap for light l only where
+// |V_k(q, l) - V_k(p, l)| <= T(p, l).  Integers throughout, so header, host twin, numpy rule and kernels agree bit for bit.
+//
+// T = min(65535, isqrt((k4^2 * G) / (16 * D * n))) WITHOUT the 64-bit division: for integers r, N and d > 0, r * r <= N / d (the
+// integer quotient) exactly when r * r * d <= N, so T is the largest r <= 65535 with r * r * d <= N -- a float estimate, then an integer
+// fix-up in 64 bits (r * r * d < 2^49) that makes it exact whatever the estimate's rounding: the same source on host and device.
+RTS_HD uint32_t wideGuideThreshold(uint64_t G, uint32_t D, uint32_t samples, uint32_t k4) {
+    const uint64_t N = (uint64_t)(k4 * k4) * G;                                  // < 2^16 * 2^35
+    const uint64_t d = (uint64_t)(16u * D * samples);                            // 128 .. 16 * 16 * 48
+    const float est = __builtin_sqrtf((float)N / (float)d);
+    uint32_t r = est < 65535.0f ? (uint32_t)est : 65535u;
+    while ((uint64_t)r * r * d > N) --r;
+    while (r < 65535u && (uint64_t)(r + 1u) * (r + 1u) * d <= N) ++r;
+    return r;
+}
+
+// T(p, l) for every light of the list at pixel (x, y); `t` gives V_0.  The 3 x 3 pixels inside the frame, not background, with the
+// light's map bit -- NO geom test (the header says why) --, weights {1, 2, 1} x {1, 2, 1}; a light of one sample gets 65535 (every tap
+// passes: the unguided filter), a light that is not on at p gets 0 (its value is 0 whatever the taps).
+template <class Texels>
+RTS_HD void wideGuideThresholdPixel(const WideFilterList& f, uint32_t k4, const Texels& t, int x, int y, int W, int H, uint32_t* T8) {
+    const uint32_t onp = isBackground(t.normal(x, y)) ? 0u : (t.bits(x, y) & ((1u << f.count) - 1u));
+    uint32_t nb[9];                                                              // the map bits of the nine pixels that count
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 9; ++j) {
+        const int qx = x + j % 3 - 1, qy = y + j / 3 - 1;
+        nb[j] = 0u;
+        if (onp == 0u || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+        nb[j] = j == 4 ? onp : (isBackground(t.normal(qx, qy)) ? 0u : t.bits(qx, qy));
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        T8[l] = 0u;
+        if (!((onp >> l) & 1u)) continue;
+        T8[l] = 65535u;
+        if (f.samples[l] < 2u) continue;
+        const uint32_t full = f.samples[l] * f.scale[l];                         // n_l * S_l
+        uint64_t G = 0;
+        uint32_t D = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < 9; ++j) {
+            if (!((nb[j] >> l) & 1u)) continue;
+            const uint32_t w = (j % 3 == 1 ? 2u : 1u) * (j / 3 == 1 ? 2u : 1u);
+            const uint32_t v = t.value(x + j % 3 - 1, y + j / 3 - 1, l);
+            G += (uint64_t)w * (uint64_t)(v * (full - v));                       // E = V_0 * (n S - V_0) < 2^30
+            D += w;
+        }
+        T8[l] = wideGuideThreshold(G, D, f.samples[l], k4);
+    }
+}
+
+// One guided pass at one pixel: wideFilterPassPixel with the per-light test of the tap's value against the centre's (T8: T(p, l)).
+template <class Texels>
+RTS_HD void wideGuidedPassPixel(const WideFilterList& f, const Texels& t, int x, int y, int W, int H, int step, const uint32_t* T8,
+                                uint32_t* value8) {
+    const V3 np = t.normal(x, y);
+    const uint32_t onp = isBackground(np) ? 0u : (t.bits(x, y) & ((1u << f.count) - 1u));
+    uint32_t num[8], den[8], ctr[8];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        num[l] = 0u; den[l] = 1u; ctr[l] = 0u;
+        if (l >= f.count || !((onp >> l) & 1u)) continue;
+        ctr[l] = t.value(x, y, l);
+        num[l] = 36u * ctr[l];                                                    // the centre tap: always accepted
+        den[l] = 36u;
+    }
+    if (onp != 0u && step > 0) {
+        const V3 pp = t.position(x, y);
+        for (int dy = -2; dy <= 2; ++dy) {
+            const int qy = y + dy * step;
+            if (qy < 0 || qy >= H) continue;
+            const uint32_t wy = dy == 0 ? 6u : ((dy == 1 || dy == -1) ? 4u : 1u);
+            for (int dx = -2; dx <= 2; ++dx) {
+                const int qx = x + dx * step;
+                if (qx < 0 || qx >= W || (dx == 0 && dy == 0)) continue;
+                if (!wideFilterGeom(t, np, pp, qx, qy, f.normalCosMin, f.planeEps)) continue;
+                const uint32_t acc = t.bits(qx, qy) & onp;
+                if (acc == 0u) continue;
+                const uint32_t w = wy * (dx == 0 ? 6u : ((dx == 1 || dx == -1) ? 4u : 1u));
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+                for (uint32_t l = 0; l < 8; ++l) {
+                    if (l >= f.count) break;
+                    if (!((acc >> l) & 1u)) continue;
+                    const uint32_t v = t.value(qx, qy, l);
+                    if ((v > ctr[l] ? v - ctr[l] : ctr[l] - v) > T8[l]) continue;  // the guide
+                    num[l] += w * v;
+                    den[l] += w;
+                }
+            }
+        }
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        value8[l] = ((onp >> l) & 1u) ? (2u * num[l] + den[l]) / (2u * den[l]) : 0u;
+    }
+}
+
 // The TEMPORAL ACCUMULATION of a light list's visibility (include/rts_scene.h, rtsh_accumulate_visibility_list), one pixel: reproject
 // through the previous camera onto a 1/32-pixel grid, four bilinear taps of INTEGER weights (they sum to 1024), each accepted by the
 // geometry (inside the frame, not background, normal, plane distance: once per tap, a 4-bit mask) and per light by its history length;

@@ -196,3 +196,4 @@ extern "C" int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_const
 #include "rts_filter.inc"   // the filter of a light list's planes and the visibility combine
 #include "rts_temporal.inc" // the temporal accumulation of a light list's visibility
 #include "rts_wide_filter.inc" // the wide (a-trous) filter of a light list's planes
+#include "rts_wide_guided.inc" // the variance-guided wide filter of a soft light list's planes

@@ -776,6 +776,71 @@ extern "C" int rtsh_wide_filter_soft_light_list(const rts_soft_light_list* list,
     return wideFilterFrames<false>(f, positions, normals, lights_map, counts, W, H, visibility, threads);
 }
 
+// ---- the variance-guided wide filter of a soft light list's planes (include/rts_scene.h; per-pixel rule in rts_closest_hit.h:
+// wideGuideThresholdPixel, wideGuidedPassPixel) ----
+namespace rts_harness {
+// Shared by the host and device forms: the refusals, and the unguided filter's condensed list.
+int makeWideGuidedList(const rts_soft_light_list* list, const rtsh_wide_guide_params* p, uint32_t W, uint32_t H, WideFilterList* out) {
+    if (!p || p->guide_k4 > (uint32_t)RTSH_WIDE_GUIDE_MAX_K4) return RTS_ERR_INVALID_ARG;
+    rtsh_wide_filter_params q;
+    std::memset(&q, 0, sizeof(q));
+    q.passes = p->passes; q.normal_cos_min = p->normal_cos_min; q.plane_eps = p->plane_eps;
+    return makeWideFilterSoftList(list, &q, W, H, out);
+}
+} // namespace rts_harness
+
+extern "C" size_t rtsh_wide_filter_guided_scratch_bytes(uint32_t count, uint32_t W, uint32_t H) {
+    if (count == 0 || count > 8u || W == 0 || H == 0) return 0;
+    return 3 * (size_t)count * (size_t)W * (size_t)H * sizeof(uint16_t);
+}
+
+extern "C" uint32_t rtsh_wide_guide_threshold(uint64_t G, uint32_t D, uint32_t n, uint32_t guide_k4) {
+    if (D == 0 || n == 0) return 65535u;
+    return wideGuideThreshold(G, D, n, guide_k4);
+}
+
+extern "C" int rtsh_wide_filter_guided_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_guide_params* params,
+                                                       const float* positions, const float* normals, const uint8_t* lights_map,
+                                                       const uint8_t* counts, uint32_t W, uint32_t H, float* visibility, int threads) {
+    if (!positions || !normals || !counts || !visibility) return RTS_ERR_INVALID_ARG;
+    WideFilterList f;
+    const int s = makeWideGuidedList(list, params, W, H, &f);
+    if (s != RTS_OK) return s;
+    const uint32_t k4 = params->guide_k4;
+    const size_t n = (size_t)W * H, set = (size_t)f.count * n;
+    std::vector<uint16_t> scratch;                                       // two ping-pong sets, then the planes of T: the device form's
+    try {
+        if (f.passes >= 2u) scratch.resize(3 * set);
+    } catch (const std::bad_alloc&) {
+        return RTS_ERR_CAPACITY;
+    }
+    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
+    for (uint32_t k = 0; k < launches; ++k) {
+        const bool first = k == 0u, last = k + 1u == launches;
+        const int step = f.passes == 0u ? 0 : 1 << k;
+        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * set;
+        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * set;
+        uint16_t* guide = f.passes >= 2u ? scratch.data() + 2 * set : nullptr;
+        const WideFrameTexels<false> t{ positions, normals, lights_map, first ? counts : nullptr, in, f.samples, f.scale, W, n };
+        parallelFor(n, 256, threads, [&](size_t i) {
+            const int x = (int)(i % W), y = (int)(i / W);
+            uint32_t T[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, v[8];
+            if (first) {
+                if (step > 0) wideGuideThresholdPixel(f, k4, t, x, y, (int)W, (int)H, T);
+                if (!last) for (uint32_t l = 0; l < f.count; ++l) guide[(size_t)l * n + i] = (uint16_t)T[l];
+            } else {
+                for (uint32_t l = 0; l < f.count; ++l) T[l] = guide[(size_t)l * n + i];
+            }
+            wideGuidedPassPixel(f, t, x, y, (int)W, (int)H, step, T, v);
+            for (uint32_t l = 0; l < f.count; ++l) {
+                if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
+                else out[(size_t)l * n + i] = (uint16_t)v[l];
+            }
+        });
+    }
+    return RTS_OK;
+}
+
 // ---- the temporal accumulation of a light list's visibility (include/rts_scene.h; per-pixel rule in rts_closest_hit.h: accumulatePixel) ----
 extern "C" int rtsh_camera_basis(const float eye[3], const float target[3], float fovy, uint32_t W, uint32_t H, float out[14]) {
     if (!eye || !target || !out || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;

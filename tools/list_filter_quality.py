@@ -2,6 +2,7 @@
 
     python tools/list_filter_quality.py [--radius 4] [--out profiles/r25/list_filter_quality.jsonl]
     python tools/list_filter_quality.py --wide [--light 0.1] [--out profiles/r29/list_wide_filter_quality.jsonl]      
+    python tools/list_filter_quality.py --wide --guide 8,12,16 [--light 0.1] [--out profiles/r30/list_wide_guided_quality.jsonl]   (4.26)
 
 Scenes: the cornell box at 128 x 128 and the terrain at 96 x 96 (the scenes of tests/golden/cornell_128.npz and terrain_96.npz), one
 area light at the scene's point light, its radius --light (default 3 %) of the scene's diagonal, through the facing map.  The yardstick is the UNFILTERED
@@ -12,6 +13,8 @@ visibility of 48 samples (count / 48).  Per scene and per trace of 4 samples -- 
     guided    the same with the distance planes of a 4-sample distance trace and spread 0.05 (plain trace only)
 --wide: instead, per scene and trace, one row per tent radius R = 1, 2, 4, 8 ("filter": "tent") and one per number of passes 1 .. 4 of the
 wide (a-trous) filter rtsh_wide_filter_soft_light_list ("filter": "wide", its reach 2, 6, 14, 30 pixels), same thresholds, same measure.
+--wide --guide K4[,K4...]: only the wide rows, each with one more figure per K4 -- "guided_k4_<K4>", the variance-guided filter
+rtsh_wide_filter_guided_soft_light_list at that tolerance (K4 / 4 standard deviations), same thresholds, same measure.
 A record, not a test: every row is written as it comes out."""
 import argparse
 import json
@@ -29,6 +32,7 @@ def main():
     ap.add_argument("--radius", type=int, default=4)
     ap.add_argument("--light", type=float, default=0.03, help="the light's radius as a share of the scene's diagonal")
     ap.add_argument("--wide", action="store_true", help="rows for R = 1, 2, 4, 8 and for 1 .. 4 passes of the wide filter")
+    ap.add_argument("--guide", default="", metavar="K4[,K4...]", help="with --wide: guided figures at these tolerances (quarter deviations)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from raytracedshadows_amd import api, scenes
@@ -56,7 +60,8 @@ def main():
                 base = {"scene": name, "trace": trace, "light": args.light, "active_pixels": int(active.sum()),
                         "penumbra_pixels": int(((truth > 0) & (truth < 1) & active).sum()),
                         "raw": mad(counts[0].astype(np.float32) / np.float32(4))}
-                for radius in (1, 2, 4, 8):
+                guides = [int(v) for v in args.guide.split(",") if v]
+                for radius in () if guides else (1, 2, 4, 8):
                     q = api.FilterParams.make(radius, 0.9, 0.005 * diag)
                     rows.append(dict(base, filter="tent", radius=radius, reach=radius,
                                      filtered=mad(api.filter_soft_light_list(four, q, pos, nrm, counts, facing)[0])))
@@ -65,6 +70,9 @@ def main():
                     q = api.WideFilterParams.make(passes, 0.9, 0.005 * diag)
                     rows.append(dict(base, filter="wide", passes=passes, reach=2 * (2 ** passes - 1),
                                      filtered=mad(api.wide_filter_soft_light_list(four, q, pos, nrm, counts, facing)[0])))
+                    for k4 in guides:
+                        g = api.WideGuideParams.make(passes, k4, 0.9, 0.005 * diag)
+                        rows[-1][f"guided_k4_{k4}"] = mad(api.wide_filter_guided_soft_light_list(four, g, pos, nrm, counts, facing)[0])
                     print(json.dumps(rows[-1]))
                 continue
             row = {"scene": name, "trace": trace, "radius": args.radius, "light": args.light, "active_pixels": int(active.sum()),

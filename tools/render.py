@@ -2,7 +2,7 @@
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
                            [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]
-                                          [--filter R [--spread S] | --filter-passes K] [--plane-eps E] [--normal-cos C]
+                                          [--filter R [--spread S] | --filter-passes K [--filter-guide K4]] [--plane-eps E] [--normal-cos C]
                                                       [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]]]]]
 
 --temporal F (with --soft-list N --filter R): F frames are rendered -- trace, filter, rtsh_accumulate_visibility_list_device with
@@ -16,6 +16,9 @@ visibility planes by rtsh_combine_visibility_list_device; with --distance the di
 --filter-passes K (in place of --filter R; the two exclude each other): the wide a-trous filter rtsh_wide_filter_soft_light_list_device,
 K = 0..5 passes of 5 x 5 taps 1, 2, 4, 8 and 16 pixels apart -- a reach of 2, 6, 14, 30, 62 pixels --, same thresholds, no distance
 guide; it feeds --temporal and --clamp exactly as --filter does.
+--filter-guide K4 (with --filter-passes K): the variance-guided form rtsh_wide_filter_guided_soft_light_list_device -- a tap is accepted
+for a light only where its value lies within K4 / 4 standard deviations of the centre's, the deviation estimated from the count planes
+themselves (c (n - c) over the 3 x 3 neighbourhood) --, K4 = 0..255; the passes then blur noise and stop at sharp shadow edges.
 --cull: the shadow pass traces only the pixels of the facing mark (rtsh_facing_active_device: not the background, not the surfaces
 that face away from the light) -- the same image, byte for byte.
 --adaptive K: the soft light (--spp, or a soft config) is traced by rts_trace_shadow_mask_adaptive* with a probe of K samples: the
@@ -93,8 +96,8 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
     rgb = np.zeros((H, W, 3), np.uint8)
     if filt is not None:                                 # trace -> filter -> visibility combine, all on the device
         d_vis = ctx.malloc(count * W * H * 4)
-        wide = isinstance(filt, api.WideFilterParams)
-        d_scratch = ctx.malloc(api.wide_filter_scratch_bytes(count, W, H)) if wide and filt.passes >= 2 else None
+        wide = isinstance(filt, (api.WideFilterParams, api.WideGuideParams))
+        d_scratch = ctx.malloc(wide_scratch_bytes(api, filt, count, W, H)) if wide and filt.passes >= 2 else None
         list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, d_dist, d_scratch)
         api.combine_visibility_list_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, d_vis, W, H, d_rgb, d_lights_map=d_map,
                                            colors=colors)
@@ -134,14 +137,26 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
 
 def list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, d_dist=None, d_scratch=None):
     """The filter stage of a soft light list: the tent filter of a ``FilterParams`` (--filter R) or the wide a-trous filter of a
-    ``WideFilterParams`` (--filter-passes K, which takes a scratch and no distances)."""
-    if isinstance(filt, api.WideFilterParams):
+    ``WideFilterParams`` (--filter-passes K, which takes a scratch and no distances) or its variance-guided form of a ``WideGuideParams``
+    (--filter-guide K4)."""
+    if isinstance(filt, api.WideGuideParams):
+        api.wide_filter_guided_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_scratch=d_scratch,
+                                                      d_lights_map=d_map)
+    elif isinstance(filt, api.WideFilterParams):
         api.wide_filter_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_scratch=d_scratch, d_lights_map=d_map)
     else:
         api.filter_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_lights_map=d_map, d_distances=d_dist)
 
 
+def wide_scratch_bytes(api, filt, count, W, H):
+    if isinstance(filt, api.WideGuideParams):
+        return api.wide_filter_guided_scratch_bytes(count, W, H)
+    return api.wide_filter_scratch_bytes(count, W, H)
+
+
 def filter_words(api, filt):
+    if isinstance(filt, api.WideGuideParams):
+        return f"{filt.passes} a-trous passes (reach {2 * (2 ** filt.passes - 1)} pixels), variance-guided at {filt.guide_k4 / 4:g} deviations"
     if isinstance(filt, api.WideFilterParams):
         return f"{filt.passes} a-trous passes (reach {2 * (2 ** filt.passes - 1)} pixels)"
     return f"radius {filt.radius}"
@@ -161,7 +176,8 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
     gbuf = [(ctx.malloc(n * 16), ctx.malloc(n * 16)) for _ in range(2)]
     hist = [(ctx.malloc(count * n * 4), ctx.malloc(count * n)) for _ in range(2)]
     d_map, d_counts, d_vis, d_rgb = ctx.malloc(n), ctx.malloc(count * n), ctx.malloc(count * n * 4), ctx.malloc(n * 3)
-    d_scratch = ctx.malloc(api.wide_filter_scratch_bytes(count, W, H)) if isinstance(filt, api.WideFilterParams) and filt.passes >= 2 else None
+    wide = isinstance(filt, (api.WideFilterParams, api.WideGuideParams))
+    d_scratch = ctx.malloc(wide_scratch_bytes(api, filt, count, W, H)) if wide and filt.passes >= 2 else None
     eyes = [orbit(sc.eye, sc.target, orbit_deg * (k - (frames - 1))) for k in range(frames)]      # the last frame is the scene's own camera
     t0 = time.time()
     for k in range(frames):
@@ -224,6 +240,9 @@ def main():
     ap.add_argument("--filter-passes", type=int, default=-1, metavar="K",
                     help="with --soft-list N, in place of --filter R: the wide a-trous filter (rtsh_wide_filter_soft_light_list_device), "
                          "K = 0..5 passes of 5 x 5 taps 1, 2, 4, 8, 16 pixels apart (reach 2, 6, 14, 30, 62 pixels); without --distance")
+    ap.add_argument("--filter-guide", type=int, default=-1, metavar="K4",
+                    help="with --filter-passes K: the variance-guided wide filter (rtsh_wide_filter_guided_soft_light_list_device), a tap's "
+                         "value within K4 / 4 standard deviations of the centre's, K4 = 0..255")
     ap.add_argument("--spread", type=float, default=0.25, help="with --filter and --distance: the penumbra width per unit of blocker distance")
     ap.add_argument("--plane-eps", type=float, default=0.05, help="with --filter: the largest plane distance of an accepted tap (world units)")
     ap.add_argument("--normal-cos", type=float, default=0.9, help="with --filter: the smallest N.N' of an accepted tap")
@@ -256,8 +275,14 @@ def main():
             if args.filter_passes >= 0 and args.distance:
                 sys.exit("render: --filter-passes K takes no distance guide: leave --distance out")
             filt = api.FilterParams.make(args.filter, args.normal_cos, args.plane_eps, args.spread) if args.filter >= 0 else None
+            if args.filter_guide >= 0 and args.filter_passes < 0:
+                sys.exit("render: --filter-guide K4 goes with --filter-passes K")
+            if not -1 <= args.filter_guide <= api.WideGuideParams.MAX_K4:
+                sys.exit("render: --filter-guide K4 takes 0 <= K4 <= 255")
             if args.filter_passes >= 0:
                 filt = api.WideFilterParams.make(args.filter_passes, args.normal_cos, args.plane_eps)
+            if args.filter_guide >= 0:
+                filt = api.WideGuideParams.make(args.filter_passes, args.filter_guide, args.normal_cos, args.plane_eps)
             if args.temporal:
                 if filt is None or args.distance or args.refined:
                     sys.exit("render: --temporal F goes with --soft-list N and --filter R or --filter-passes K, without --distance and --refined")
