@@ -329,7 +329,8 @@ int rtsh_combine_visibility_list_device(rts_ctx* ctx, const rts_constants* const
  *     No BVH, no alignment of any buffer beyond its element type's.
  *   * OUT OF SCOPE: moving geometry (no motion vectors: the plane test takes it for a disocclusion and resets), variance clamping of
  *     the history (a mean +- k sigma box needs a square root; the min/max box is rtsh_accumulate_visibility_list_clamped below),
- *     accumulating count or distance planes, row ranges and stripes, a frame term in the jitter hash. */
+ *     accumulating distance planes (the count planes' moments: rtsh_accumulate_moments_soft_light_list below), row ranges and
+ *     stripes, a frame term in the jitter hash. */
 typedef struct rtsh_temporal_params {
     float    eye_delta[3];                             /* current eye - previous eye */
     float    prev_right[3], prev_up[3], prev_fwd[3];   /* the previous camera's basis */
@@ -504,8 +505,9 @@ int rtsh_wide_filter_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_l
  *     may be NULL when passes <= 1, and nothing of it is touched then.
  *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything rtsh_wide_filter_soft_light_list* refuse (d_visibility equal
  *     to the start of any of the three sets of d_scratch included); guide_k4 > 255; a NULL d_scratch with passes >= 2.
- *   * OUT OF SCOPE: variance propagated through the passes (T is the first pass's at every pass), a temporal variance from the
- *     accumulation stage, a guide for the tent filter rtsh_filter_*_light_list*. */
+ *   * OUT OF SCOPE: variance propagated through the passes (T is the first pass's at every pass), a guide for the tent filter
+ *     rtsh_filter_*_light_list*.  (A temporal variance from accumulated moments: rtsh_wide_filter_guided_temporal_soft_light_list
+ *     below.) */
 enum { RTSH_WIDE_GUIDE_MAX_K4 = 255 };
 typedef struct rtsh_wide_guide_params {
     uint32_t passes;          /* 0 .. RTSH_WIDE_FILTER_MAX_PASSES (5) */
@@ -525,6 +527,90 @@ int rtsh_wide_filter_guided_soft_light_list_device(rts_ctx* ctx, const rts_soft_
                                                    const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
                                                    const uint8_t* d_counts, uint32_t W, uint32_t H, float* d_visibility,
                                                    uint16_t* d_scratch, void* stream);
+
+/* THE TEMPORAL ACCUMULATION OF A SOFT LIGHT LIST'S COUNT MOMENTS: the first and second moment of V_0 = min(c, n_l) * S_l -- the wide
+ * filter's own 16-bit input, its notation -- over reprojected frames, in FIXED POINT.  It is what SVGF drives its luminance stop with:
+ * rtsh_wide_filter_guided_temporal_soft_light_list below takes its tolerance from these planes where a pixel's history is long enough.
+ * Counts are integers and the bilinear weights of rtsh_accumulate_visibility_list are integers, so every sum here is an integer sum:
+ * THE RESULT DOES NOT DEPEND ON THE ORDER OF THE TAPS, and the host form checks the device form bit for bit.
+ *   CURRENT frame: positions, normals, lights_map (may be NULL), counts (count uint8_t planes).
+ *   PREVIOUS frame: prev_positions, prev_normals, prev_mean (count uint16_t planes), prev_square (count uint32_t planes), prev_lengths
+ *     (count uint8_t planes).  All five NULL: the FIRST FRAME; all five or none.
+ *   Outputs: mean_out (uint16_t), square_out (uint32_t), lengths_out (uint8_t), count planes each.
+ *   params: rtsh_temporal_params, the struct and the meaning of rtsh_accumulate_visibility_list, max_length and reset_lights included.
+ * For pixel p and light l < count:  cur1 = V_0(p, l) (at most 65535), cur2 = cur1 * cur1 (below 2^32).
+ *   GEOMETRY: INACTIVE, REPROJECT, the four taps, their integer weights and the acceptance of a tap are rtsh_accumulate_visibility_list's,
+ *     word for word (prev_lengths in the place of its prev_lengths).  An inactive (pixel, light) holds 0, 0 and length 0.
+ *   PASS-THROUGH: on the first frame, off screen, with no accepted tap, or with n == 1: cur1, cur2 and length 1.
+ *   BLEND: sw = the sum of the accepted weights, m = the smallest accepted length, n = min(m + 1, max_length), lengths_out = n; for X in
+ *     {mean, square}: s = the integer sum of w * prev_X[l][q] over the accepted taps, num = (n - 1) * s + sw * cur_X, den = n * sw,
+ *     out_X = (2 * num + den) / (2 * den) by integer division: ONE rounded mean in place of the float pass's two steps.
+ *   WIDTH: s < 2^42, 2 * num + den < 2^52, 2 * den < 2^19: everything fits unsigned 64 bits (and a double, exactly).
+ * ANCHORS: (1) lengths_out is byte for byte what rtsh_accumulate_visibility_list writes for the same G-buffers, params, map and
+ * prev_lengths.  (2) A still camera (anchor 2 there: one tap of weight 1024) gives h_k = (2 * ((n - 1) * h_(k-1) + cur) + n) / (2 * n),
+ * n = min(k, max_length), per pixel and moment.  (3) Where every accepted history value and the current one are the same value, the
+ * output is that value, for any weights; so a pixel whose count never changed has square == mean * mean exactly.  (4) max_length == 1,
+ * an all-ones reset_lights and the first frame give cur1, cur2 and 1 at active pixels.  (5) RANGE: every output lies between the
+ * smallest and the largest of its accepted history values and the current one.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: what rtsh_accumulate_visibility_list refuses (of params, the frame and the
+ *     buffers, counts in the place of visibility); what rtsh_wide_filter_soft_light_list refuses of a soft list; some but not all of the
+ *     five prev_*; mean_out == prev_mean, square_out == prev_square or lengths_out == prev_lengths (history must ping-pong); a NULL ctx.
+ *   * planes of any buffer from `count` up are never touched.  No buffer needs alignment beyond its element type's.
+ *   * host form: multi-threaded.  Device form: DEVICE buffers, asynchronous on `stream`, allocates nothing, reads nothing back; under
+ *     graph capture ONE kernel node, list and params by value.  No BVH.
+ *   * OUT OF SCOPE: moving geometry, a clamp of the moments' history, hard lists (their variance is 0), row ranges and stripes. */
+int rtsh_accumulate_moments_soft_light_list(const rts_soft_light_list* list, const rtsh_temporal_params* params, const float* positions,
+                                            const float* normals, const uint8_t* lights_map, const uint8_t* counts,
+                                            const float* prev_positions, const float* prev_normals, const uint16_t* prev_mean,
+                                            const uint32_t* prev_square, const uint8_t* prev_lengths, uint32_t W, uint32_t H,
+                                            uint16_t* mean_out, uint32_t* square_out, uint8_t* lengths_out, int threads);
+int rtsh_accumulate_moments_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list, const rtsh_temporal_params* params,
+                                                   const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                   const uint8_t* d_counts, const float* d_prev_positions, const float* d_prev_normals,
+                                                   const uint16_t* d_prev_mean, const uint32_t* d_prev_square,
+                                                   const uint8_t* d_prev_lengths, uint32_t W, uint32_t H, uint16_t* d_mean_out,
+                                                   uint32_t* d_square_out, uint8_t* d_lengths_out, void* stream);
+
+/* THE GUIDED WIDE FILTER WITH A TEMPORAL THRESHOLD: rtsh_wide_filter_guided_soft_light_list with ONE change, in ENERGY -- where a pixel's
+ * moments (the planes above, for THIS frame) have a history of at least min_history frames, its energy is the variance seen over those
+ * frames, not the one frame's Bernoulli estimate.  Under a jittered trace of few samples whole 3 x 3 neighbourhoods hold only 0 or n_l:
+ * the spatial estimate is 0 there and the guided filter keeps the noise; the temporal one sees the pixel change from frame to frame.
+ *   typedef struct rtsh_wide_guide_temporal_params: passes, normal_cos_min, plane_eps, guide_k4 as in rtsh_wide_guide_params;
+ *     min_history 1 .. 255; reserved_ (ignored).
+ *   ENERGY: E*(q, l) = n_l * max(0, square[l][q] - mean[l][q]^2) where lengths[l][q] >= min_history, else E(q, l) of the guided filter.
+ *     (n_l times the variance of V is in the units of E: E / n_l is the binomial variance of V.)  Arbitrary plane contents are allowed:
+ *     E* < 48 * 2^32, so G < 2^42 and guide_k4^2 * G < 2^58, inside 64 bits; rtsh_wide_guide_threshold is exact for such G too (its
+ *     integer fix-up multiplies r * r * d < 2^46).
+ *   G, D and the 3 x 3 weights, T = min(65535, isqrt((guide_k4^2 * G) / (16 * D * n_l))), T = 65535 for n_l <= 1, the pass, the rounded
+ *     mean and the output are the guided filter's, unchanged.
+ * ANCHORS: (1) where every counted lengths value is below min_history the result is bit for bit the guided filter's for the same inputs.
+ * (2) From first-frame moments (square == mean^2, length 1) with min_history == 1 every T is 0: the passes == 0 plane for every light
+ * with n_l >= 2.  (3) guide_k4 == 0 gives the passes == 0 plane.  (4) A light with n_l <= 1 gives rtsh_wide_filter_soft_light_list's
+ * plane.  (5) RANGE as in the guided filter.
+ *   * buffers, scratch (rtsh_wide_filter_guided_scratch_bytes), threads, stream and graph capture as for the guided filter: max(1, passes)
+ *     KERNEL nodes on one chain; only the first differs from the guided filter's.  mean, square, lengths: count planes each, read at
+ *     counted pixels only, each on its element type's alignment.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the guided filter refuses; a NULL mean, square or lengths;
+ *     min_history 0 or above 255.
+ *   * OUT OF SCOPE: filtering the accumulated mean plane in place of this frame's counts (it has V_0's format), variance propagated
+ *     through the passes, motion vectors, a guide for the tent filter, row ranges and stripes, hard lists. */
+typedef struct rtsh_wide_guide_temporal_params {
+    uint32_t passes;          /* 0 .. RTSH_WIDE_FILTER_MAX_PASSES (5) */
+    float    normal_cos_min;  /* a tap needs N_p . N_q >= this */
+    float    plane_eps;       /* ... and |N_p . (P_q - P_p)| <= this (world units) */
+    uint32_t guide_k4;        /* the tolerance in quarter standard deviations, 0 .. RTSH_WIDE_GUIDE_MAX_K4 (255) */
+    uint32_t min_history;     /* 1 .. 255: a pixel of at least this many frames of history gives its temporal variance */
+    uint32_t reserved_[3];    /* ignored */
+} rtsh_wide_guide_temporal_params;                                                 /* 32 bytes */
+int rtsh_wide_filter_guided_temporal_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_guide_temporal_params* params,
+                                                     const float* positions, const float* normals, const uint8_t* lights_map,
+                                                     const uint8_t* counts, const uint16_t* mean, const uint32_t* square,
+                                                     const uint8_t* lengths, uint32_t W, uint32_t H, float* visibility, int threads);
+int rtsh_wide_filter_guided_temporal_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list,
+                                                            const rtsh_wide_guide_temporal_params* params, const float* d_positions,
+                                                            const float* d_normals, const uint8_t* d_lights_map, const uint8_t* d_counts,
+                                                            const uint16_t* d_mean, const uint32_t* d_square, const uint8_t* d_lengths,
+                                                            uint32_t W, uint32_t H, float* d_visibility, uint16_t* d_scratch, void* stream);
 
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.

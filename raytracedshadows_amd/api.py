@@ -236,6 +236,22 @@ class WideGuideParams(C.Structure):
         return p
 
 
+class WideGuideTemporalParams(C.Structure):
+    """``rtsh_wide_guide_temporal_params``: ``WideGuideParams`` plus ``min_history`` (1..255): a pixel whose count moments hold at
+    least that many frames gives the guide its temporal variance, every other pixel this frame's Bernoulli estimate."""
+    _fields_ = [("passes", C.c_uint32), ("normal_cos_min", C.c_float), ("plane_eps", C.c_float), ("guide_k4", C.c_uint32),
+                ("min_history", C.c_uint32), ("reserved_", C.c_uint32 * 3)]
+    MAX_PASSES = 5
+    MAX_K4 = 255
+
+    @classmethod
+    def make(cls, passes, guide_k4=12, min_history=4, normal_cos_min=0.9, plane_eps=0.05):
+        p = cls()
+        p.passes, p.guide_k4, p.min_history = passes, guide_k4, min_history
+        p.normal_cos_min, p.plane_eps = np.float32(normal_cos_min), np.float32(plane_eps)
+        return p
+
+
 class TemporalParams(C.Structure):
     """``rtsh_temporal_params``: the camera motion (current eye minus previous eye, the previous camera's basis and scales), the two
     geometry thresholds, the longest history (1..255) and the lights that take no history this frame (a bit per light)."""
@@ -542,6 +558,17 @@ _sig("rtsh_accumulate_visibility_list_clamped", C.c_int, C.POINTER(LightList), C
 _sig("rtsh_accumulate_visibility_list_clamped_device", C.c_int, C.c_void_p, C.POINTER(LightList), C.POINTER(TemporalParams), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
      C.POINTER(HistoryClamp), C.c_void_p)
+_sig("rtsh_accumulate_moments_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_int)
+_sig("rtsh_accumulate_moments_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(TemporalParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_wide_filter_guided_temporal_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(WideGuideTemporalParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_wide_filter_guided_temporal_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList),
+     C.POINTER(WideGuideTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_facing_active", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
      C.c_void_p)
 _sig("rtsh_facing_active_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
@@ -1816,6 +1843,85 @@ def accumulate_visibility_list_device(ctx, light_list, params, d_positions, d_no
                                                        C.c_void_p(pp[3] or 0), width, height, C.c_void_p(d_visibility_out),
                                                        C.c_void_p(d_lengths_out), C.c_void_p(stream or 0)),
            "rtsh_accumulate_visibility_list_device")
+
+
+def accumulate_moments_soft_light_list(lights, params, positions, normals, counts, prev=None, lights_map=None, threads=0):
+    """The temporal accumulation of a soft light list's count moments on the host (rtsh_accumulate_moments_soft_light_list):
+    ``(uint16[count, H, W] mean, uint32[count, H, W] square, uint8[count, H, W] lengths)``.  ``counts``: this frame's
+    ``uint8[>= count, H, W]``; ``prev``: None on the first frame, else ``(prev_positions, prev_normals, prev_mean, prev_square,
+    prev_lengths)`` of the previous frame (its G-buffer and what this call returned for it); ``params`` a ``TemporalParams``."""
+    name = "rtsh_accumulate_moments_soft_light_list"
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    counts = np.ascontiguousarray(counts, np.uint8)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    fits = counts.size >= count * H * W and (lights_map is None or lights_map.size == H * W) and \
+        (positions is None or positions.size == H * W * 4)
+    if prev is not None:
+        prev = tuple(np.ascontiguousarray(a, t) for a, t in zip(prev, (np.float32, np.float32, np.uint16, np.uint32, np.uint8)))
+        fits = fits and len(prev) == 5 and prev[0].size == H * W * 4 and prev[1].size == H * W * 4 and \
+            all(a.size >= count * H * W for a in prev[2:])
+    if not fits:
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    mean, square, lengths = np.zeros((count, H, W), np.uint16), np.zeros((count, H, W), np.uint32), np.zeros((count, H, W), np.uint8)
+    pp = [_ptr(a) for a in prev] if prev is not None else [None] * 5
+    _check(_lib.rtsh_accumulate_moments_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
+                                                        _ptr_or_none(lights_map), _ptr(counts), pp[0], pp[1], pp[2], pp[3], pp[4], W, H,
+                                                        _ptr(mean), _ptr(square), _ptr(lengths), threads), name)
+    return mean, square, lengths
+
+
+def accumulate_moments_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_counts, width, height, d_mean_out,
+                                              d_square_out, d_lengths_out, d_prev=None, d_lights_map=None, stream=None):
+    """The moments pass on the GPU: device pointers; ``d_prev``: None on the first frame, else the device pointers ``(prev_positions,
+    prev_normals, prev_mean, prev_square, prev_lengths)``.  d_mean_out = count planes of width*height uint16, d_square_out of uint32,
+    d_lengths_out of bytes; none may be the history it reads.  One kernel, asynchronous."""
+    pp = tuple(d_prev) if d_prev is not None else (0, 0, 0, 0, 0)
+    _check(_lib.rtsh_accumulate_moments_soft_light_list_device(ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions or 0),
+                                                               C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0), C.c_void_p(d_counts),
+                                                               C.c_void_p(pp[0] or 0), C.c_void_p(pp[1] or 0), C.c_void_p(pp[2] or 0),
+                                                               C.c_void_p(pp[3] or 0), C.c_void_p(pp[4] or 0), width, height,
+                                                               C.c_void_p(d_mean_out), C.c_void_p(d_square_out), C.c_void_p(d_lengths_out),
+                                                               C.c_void_p(stream or 0)),
+           "rtsh_accumulate_moments_soft_light_list_device")
+
+
+def wide_filter_guided_temporal_soft_light_list(lights, params, positions, normals, counts, moments, lights_map=None, threads=0):
+    """The guided wide filter with a temporal threshold on the host (rtsh_wide_filter_guided_temporal_soft_light_list):
+    ``float32[count, H, W]`` visibility.  ``params`` a ``WideGuideTemporalParams``; ``moments`` = ``(mean, square, lengths)`` of
+    ``accumulate_moments_soft_light_list`` for this frame."""
+    name = "rtsh_wide_filter_guided_temporal_soft_light_list"
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    counts = np.ascontiguousarray(counts, np.uint8)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    mean, square, lengths = (np.ascontiguousarray(a, t) for a, t in zip(moments, (np.uint16, np.uint32, np.uint8)))
+    if counts.size < count * H * W or (lights_map is not None and lights_map.size != H * W) or \
+            (positions is not None and positions.size != H * W * 4) or any(a.size < count * H * W for a in (mean, square, lengths)):
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    visibility = np.zeros((count, H, W), np.float32)
+    _check(_lib.rtsh_wide_filter_guided_temporal_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
+                                                                 _ptr_or_none(lights_map), _ptr(counts), _ptr(mean), _ptr(square),
+                                                                 _ptr(lengths), W, H, _ptr(visibility), threads), name)
+    return visibility
+
+
+def wide_filter_guided_temporal_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_counts, d_moments, width, height,
+                                                       d_visibility, d_scratch=None, d_lights_map=None, stream=None):
+    """The guided wide filter with a temporal threshold on the GPU: device pointers, ``d_moments`` = ``(d_mean, d_square, d_lengths)``,
+    d_scratch = ``wide_filter_guided_scratch_bytes(count, width, height)`` bytes (None allowed for passes <= 1); max(1, passes)
+    kernels, asynchronous."""
+    m = tuple(d_moments)
+    _check(_lib.rtsh_wide_filter_guided_temporal_soft_light_list_device(ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions or 0),
+                                                                        C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
+                                                                        C.c_void_p(d_counts), C.c_void_p(m[0] or 0), C.c_void_p(m[1] or 0),
+                                                                        C.c_void_p(m[2] or 0), width, height, C.c_void_p(d_visibility),
+                                                                        C.c_void_p(d_scratch or 0), C.c_void_p(stream or 0)),
+           "rtsh_wide_filter_guided_temporal_soft_light_list_device")
 
 
 def write_ppm(path, rgb):

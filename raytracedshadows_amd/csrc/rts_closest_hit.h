@@ -578,6 +578,159 @@ RTS_HD void accumulatePixel(const TemporalList& f, const Frames& t, int x, int y
     }
 }
 
+// The TEMPORAL ACCUMULATION OF A SOFT LIGHT LIST'S COUNT MOMENTS (include/rts_scene.h, rtsh_accumulate_moments_soft_light_list), one
+// pixel: accumulatePixel's geometry -- INACTIVE, REPROJECT, the four taps, their integer weights and their acceptance, a COPY of its
+// statements (accumulateListKernel keeps its instruction text) -- in front of an INTEGER blend of the first and second moment of
+// V_0 = min(c, n_l) * S_l.  s = the sum of w * prev over the accepted taps (< 2^26 for the mean, < 2^42 for the square),
+// num = (n - 1) * s + sw * cur, den = n * sw < 2^18, out = (2 * num + den) / (2 * den): 2 * num + den < 2^52, so everything is exact in
+// unsigned 64 bits and no order of taps can change a bit.  `Frames`: V3 normal(x, y), position(x, y); uint32_t bits(x, y);
+// uint32_t count(l, x, y) (the byte); V3 prevNormal(x, y), prevPosition(x, y); uint32_t prevLength(l, x, y), prevMean(l, x, y),
+// prevSquare(l, x, y); void store(l, x, y, uint32_t mean, uint32_t square, uint32_t length).
+struct MomentsList { TemporalList t; uint32_t samples[8], scale[8]; };                            // n_l, S_l as in WideFilterList
+
+// a / b by integer division for a < 2^53 and 0 < b < 2^20 WITHOUT the 64-bit division (on the GPU a loop of some 90 instructions): both
+// are exact as doubles, their correctly rounded quotient misses a / b by less than 2^-18, so its integer part is the quotient or one
+// above it (where a / b lies just below an integer and rounds onto it; never below: rounding is monotonic and integers are
+// representable).  Two integer comparisons make the result exact whatever the estimate: the same source on host and device.
+RTS_HD uint64_t momentsQuotient(uint64_t a, uint32_t b) {
+    uint64_t q = (uint64_t)((double)a / (double)b);
+    if (q * b > a) --q;
+    if ((q + 1u) * b <= a) ++q;
+    return q;
+}
+
+template <class Frames>
+RTS_HD void accumulateMomentsPixel(const MomentsList& g, const Frames& t, int x, int y, int W, int H) {
+    const TemporalList& f = g.t;
+    const V3 np = t.normal(x, y);
+    const uint32_t all = (1u << f.count) - 1u;
+    const uint32_t onp = isBackground(np) ? 0u : (t.bits(x, y) & all);
+    int qx[4] = { 0, 0, 0, 0 }, qy[4] = { 0, 0, 0, 0 };
+    uint32_t w[4] = { 0, 0, 0, 0 }, taps = 0;                                                      // taps: bit k = tap k passes the geometry
+    if (onp != 0u && f.history != 0u && (all & ~f.resetLights) != 0u) {
+        const V3 q = add(t.position(x, y), f.eyeDelta);
+        const float z = dotGrouped(q, f.fwd);
+        const float a = dotGrouped(q, f.right) / z, b = dotGrouped(q, f.up) / z;
+        const float fx = (a / f.scaleX + 1.0f) * (0.5f * (float)W) - 0.5f;
+        const float fy = (1.0f - b / f.scaleY) * (0.5f * (float)H) - 0.5f;
+        const float gx = fx * 32.0f + 0.5f, gy = fy * 32.0f + 0.5f;
+        if (z > 0.0f && gx >= -32.0f && gx < (float)W * 32.0f && gy >= -32.0f && gy < (float)H * 32.0f) {
+            const int32_t ix = (int32_t)__builtin_floorf(gx), iy = (int32_t)__builtin_floorf(gy);
+            const int x0 = ix >> 5, y0 = iy >> 5;
+            const uint32_t ax = (uint32_t)(ix & 31), ay = (uint32_t)(iy & 31);
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int k = 0; k < 4; ++k) {
+                qx[k] = x0 + (k & 1); qy[k] = y0 + (k >> 1);
+                w[k] = ((k & 1) ? ax : 32u - ax) * ((k >> 1) ? ay : 32u - ay);
+                if (w[k] == 0u || qx[k] < 0 || qx[k] >= W || qy[k] < 0 || qy[k] >= H) continue;
+                const V3 nq = t.prevNormal(qx[k], qy[k]);
+                if (isBackground(nq)) continue;
+                if (!(dotGrouped(np, nq) >= f.normalCosMin)) continue;
+                const float h = dotGrouped(np, sub(t.prevPosition(qx[k], qy[k]), q));
+                if (!(__builtin_fabsf(h) <= f.planeEps)) continue;
+                taps |= 1u << k;
+            }
+        }
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        if (!((onp >> l) & 1u)) { t.store(l, x, y, 0u, 0u, 0u); continue; }
+        const uint32_t cur1 = wideFilterInput(t.count(l, x, y), g.samples[l], g.scale[l]);         // V_0 <= 65535
+        const uint32_t cur2 = cur1 * cur1;                                                        // < 2^32
+        uint32_t sw = 0, m = 255u;
+        uint64_t s1 = 0, s2 = 0;
+        if (taps != 0u && !((f.resetLights >> l) & 1u)) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int k = 0; k < 4; ++k) {
+                if (!((taps >> k) & 1u)) continue;
+                const uint32_t len = t.prevLength(l, qx[k], qy[k]);
+                if (len == 0u) continue;
+                sw += w[k];
+                s1 += (uint64_t)(w[k] * t.prevMean(l, qx[k], qy[k]));                              // 1024 * 65535 < 2^26
+                s2 += (uint64_t)w[k] * (uint64_t)t.prevSquare(l, qx[k], qy[k]);
+                if (len < m) m = len;
+            }
+        }
+        const uint32_t n = sw == 0u ? 1u : (m + 1u < f.maxLength ? m + 1u : f.maxLength);
+        uint32_t out1 = cur1, out2 = cur2;
+        if (n != 1u) {
+            const uint32_t den = n * sw;                                                           // <= 255 * 1024
+            out1 = (uint32_t)momentsQuotient(2u * ((uint64_t)(n - 1u) * s1 + (uint64_t)sw * cur1) + den, 2u * den);
+            out2 = (uint32_t)momentsQuotient(2u * ((uint64_t)(n - 1u) * s2 + (uint64_t)sw * cur2) + den, 2u * den);
+        }
+        t.store(l, x, y, out1, out2, n);
+    }
+}
+
+// The TEMPORAL THRESHOLD of the guided wide filter (include/rts_scene.h, rtsh_wide_filter_guided_temporal_soft_light_list):
+// wideGuideThresholdPixel with one change, in the energy of a counted pixel q: n_l * max(0, square - mean^2) where the moments'
+// history at q is at least minHistory frames long, else the Bernoulli energy V_0 * (n S - V_0) as there.  The planes are read where
+// they are (the host twin and the kernel alike): `length` first, then either the two moments or V_0.  E* < 48 * 2^32, G < 2^42,
+// k4^2 * G < 2^58: wideGuideThreshold's fix-up multiplies r * r * d < 2^46 and is exact whatever G is.
+struct GuideMoments {
+    const uint16_t* mean;
+    const uint32_t* square;
+    const uint8_t* lengths;
+    uint64_t W, n;
+    RTS_HD uint64_t at(int x, int y, uint32_t l) const { return (uint64_t)l * n + (uint64_t)y * W + (uint64_t)x; }
+};
+
+template <class Texels>
+RTS_HD void wideGuideTemporalThresholdPixel(const WideFilterList& f, uint32_t k4, uint32_t minHistory, const Texels& t, const GuideMoments& h,
+                                            int x, int y, int W, int H, uint32_t* T8) {
+    const uint32_t onp = isBackground(t.normal(x, y)) ? 0u : (t.bits(x, y) & ((1u << f.count) - 1u));
+    uint32_t nb[9];                                                              // the map bits of the nine pixels that count
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 9; ++j) {
+        const int qx = x + j % 3 - 1, qy = y + j / 3 - 1;
+        nb[j] = 0u;
+        if (onp == 0u || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+        nb[j] = j == 4 ? onp : (isBackground(t.normal(qx, qy)) ? 0u : t.bits(qx, qy));
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        T8[l] = 0u;
+        if (!((onp >> l) & 1u)) continue;
+        T8[l] = 65535u;
+        if (f.samples[l] < 2u) continue;
+        const uint32_t full = f.samples[l] * f.scale[l];                         // n_l * S_l
+        uint64_t G = 0;
+        uint32_t D = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < 9; ++j) {
+            if (!((nb[j] >> l) & 1u)) continue;
+            const int qx = x + j % 3 - 1, qy = y + j / 3 - 1;
+            const uint32_t w = (j % 3 == 1 ? 2u : 1u) * (j / 3 == 1 ? 2u : 1u);
+            const uint64_t i = h.at(qx, qy, l);
+            uint64_t E;
+            if ((uint32_t)h.lengths[i] >= minHistory) {
+                const uint64_t mean = h.mean[i], square = h.square[i];
+                E = square > mean * mean ? (uint64_t)f.samples[l] * (square - mean * mean) : 0u;   // n_l * max(0, square - mean^2)
+            } else {
+                const uint32_t v = t.value(qx, qy, l);
+                E = (uint64_t)(v * (full - v));                                  // E = V_0 * (n S - V_0) < 2^30
+            }
+            G += (uint64_t)w * E;
+            D += w;
+        }
+        T8[l] = wideGuideThreshold(G, D, f.samples[l], k4);
+    }
+}
+
 // The facing mark (include/rts_scene.h, rtsh_facing_active): 0 where the shadow mask's byte cannot reach the image -- the
 // background (combinePixel leaves the pixel 0) and N.L <= 0 (direct = 1.25 * 0 * mask: either zero) --, 1 everywhere else.
 // `!(ndl > 0)` would cull a NaN; `ndl <= 0` is false for one, so a NaN is traced.

@@ -1,0 +1,203 @@
+// The temporal accumulation of a soft light list's count moments, and the guided wide filter whose threshold reads them, on the GPU
+// (include/rts_scene.h: rtsh_accumulate_moments_soft_light_list_device, rtsh_wide_filter_guided_temporal_soft_light_list_device).  The
+// per-pixel rules are the host twin's own source (rts_closest_hit.h: accumulateMomentsPixel, wideGuideTemporalThresholdPixel,
+// wideGuidedPassPixel), compiled with the same flags.  Included at the end of rts_primary.hip after rts_wide_guided.inc; every kernel
+// in front of it keeps its instruction text: both kernels here are SIBLINGS, nothing above is touched.
+
+namespace rts_harness {
+int makeMomentsList(const rts_soft_light_list* list, const rtsh_temporal_params* p, const void* positions, const void* normals,
+                    const void* counts, const void* prevPositions, const void* prevNormals, const void* prevMean, const void* prevSquare,
+                    const void* prevLengths, uint32_t W, uint32_t H, const void* meanOut, const void* squareOut, const void* lengthsOut,
+                    MomentsList* out);                                                                                  // rts_scene.cpp
+int makeWideGuidedTemporalList(const rts_soft_light_list* list, const rtsh_wide_guide_temporal_params* p, uint32_t W, uint32_t H,
+                               WideFilterList* out);                                                                    // rts_scene.cpp
+
+// MOMENTS KERNEL.  accumulateListKernel's shape, for its reasons (rts_temporal.inc): one pixel per lane, 256 lanes per block of 16 x 16
+// pixels, four waves of 16 x 4, no LDS -- where the gathered patch lies depends on the data.  The geometry of the four taps is decided
+// once per pixel; the light loop sits behind the wave-uniform l < count; a tap of weight 0 or a rejected tap is never loaded.  What is
+// streamed once -- this frame's texel, map byte and count bytes, the three outputs -- goes non-temporal; the previous frame's texels
+// and history (1 + 2 + 4 bytes per tap and light), which neighbours share, plain.  Every load is of its element type's size.
+struct MomentsDeviceFrames {
+    const float *positions, *normals, *prevPositions, *prevNormals;
+    const uint8_t *map, *counts, *prevLengths;
+    const uint16_t* prevMeans;
+    const uint32_t* prevSquares;
+    uint16_t* meanOut;
+    uint32_t* squareOut;
+    uint8_t* lengthsOut;
+    uint64_t W, n;
+    __device__ uint64_t at(int x, int y) const { return (uint64_t)y * W + (uint64_t)x; }
+    __device__ V3 normal(int x, int y) const { return TemporalDeviceFrames::streamed(normals, at(x, y)); }
+    __device__ V3 position(int x, int y) const { return TemporalDeviceFrames::streamed(positions, at(x, y)); }
+    __device__ uint32_t bits(int x, int y) const { return map ? __builtin_nontemporal_load(map + at(x, y)) : 0xFFu; }
+    __device__ uint32_t count(uint32_t l, int x, int y) const { return __builtin_nontemporal_load(counts + (uint64_t)l * n + at(x, y)); }
+    __device__ V3 prevNormal(int x, int y) const { return TemporalDeviceFrames::shared(prevNormals, at(x, y)); }
+    __device__ V3 prevPosition(int x, int y) const { return TemporalDeviceFrames::shared(prevPositions, at(x, y)); }
+    __device__ uint32_t prevLength(uint32_t l, int x, int y) const { return prevLengths[(uint64_t)l * n + at(x, y)]; }
+    __device__ uint32_t prevMean(uint32_t l, int x, int y) const { return prevMeans[(uint64_t)l * n + at(x, y)]; }
+    __device__ uint32_t prevSquare(uint32_t l, int x, int y) const { return prevSquares[(uint64_t)l * n + at(x, y)]; }
+    __device__ void store(uint32_t l, int x, int y, uint32_t mean, uint32_t square, uint32_t length) const {
+        __builtin_nontemporal_store((uint16_t)mean, meanOut + (uint64_t)l * n + at(x, y));
+        __builtin_nontemporal_store(square, squareOut + (uint64_t)l * n + at(x, y));
+        __builtin_nontemporal_store((uint8_t)length, lengthsOut + (uint64_t)l * n + at(x, y));
+    }
+};
+
+__global__ __launch_bounds__(256) void accumulateMomentsKernel(MomentsList f, MomentsDeviceFrames t, int W, int H) {
+    const int x = (int)blockIdx.x * 16 + (int)threadIdx.x, y = (int)blockIdx.y * 16 + (int)threadIdx.y;
+    if (x >= W || y >= H) return;
+    accumulateMomentsPixel(f, t, x, y, W, H);
+}
+
+// THE FIRST PASS OF THE TEMPORAL GUIDE: wideGuidedKernel<true, LAST, DENSE> with wideGuideTemporalThresholdPixel in the place of
+// wideGuideThresholdPixel -- a sibling, so that every instantiation of wideGuidedKernel keeps its text; later passes ARE
+// wideGuidedKernel<false, ...>, which read T from the third set of the scratch.  The staging loop is wideFilterKernel's, statement for
+// statement.  The nine (length, mean, square) triples per light are loaded from GLOBAL memory, not staged: 7 bytes per texel and light
+// beside the window's 25 + 2 * count would take the step-1 window of eight lights (pitch 48 x 20 rows) from 39 KiB to 92 KiB, beyond
+// the 64 KiB a workgroup gets without opting in, and a compact 18 x 18 side array (18 KiB more) would still cut the workgroups per CU
+// from four to two (160 KiB of LDS) for a read that neighbouring lanes share through the vector cache anyway: a wave's row of 16
+// pixels reads 18 consecutive elements of a plane's row.  `length` is read first; the moments only where it reaches minHistory.
+template <bool LAST, bool DENSE>
+__global__ __launch_bounds__(256) void wideGuidedTemporalKernel(WideFilterList f, uint32_t k4, uint32_t minHistory, GuideMoments h,
+                                                                const float* positions, const float* normals, const uint8_t* lightsMap,
+                                                                const void* in, int W, int H, int step, int pitch, void* out,
+                                                                uint16_t* guide) {
+    const uint32_t count = f.count;
+    const uint64_t n = (uint64_t)W * (uint64_t)H;
+    const int x = (int)blockIdx.x * 16 + (int)threadIdx.x, y = (int)blockIdx.y * 16 + (int)threadIdx.y;
+    const uint64_t p = (uint64_t)y * (uint64_t)W + (uint64_t)x;
+    uint32_t v[8], T[8];
+    auto storeGuide = [&]() {
+#pragma unroll
+        for (uint32_t l = 0; l < 8; ++l) {
+            if (l >= count) break;
+            guide[(uint64_t)l * n + p] = (uint16_t)T[l];
+        }
+    };
+#pragma unroll
+    for (uint32_t l = 0; l < 8; ++l) T[l] = 0u;
+    if constexpr (DENSE) {
+        extern __shared__ __align__(16) unsigned char lds[];
+        const int reach = 2 * step, TW = 16 + 2 * reach, cells = pitch * TW;
+        float2* sa = (float2*)lds;
+        float2* sb = sa + cells;
+        float2* sc = sb + cells;
+        uint16_t* svalues = (uint16_t*)(sc + cells);
+        uint8_t* smap = (uint8_t*)(svalues + count * cells);
+        const int x0 = (int)blockIdx.x * 16 - reach, y0 = (int)blockIdx.y * 16 - reach;
+        const int tid = (int)(threadIdx.y * 16 + threadIdx.x);
+        for (int i = tid; i < TW * TW; i += 256) {
+            const int ty = i / TW, tx = i - ty * TW, gx = x0 + tx, gy = y0 + ty, s = ty * pitch + tx;
+            float nx = 0.f, ny = 0.f, nz = 0.f, px = 0.f, py = 0.f, pz = 0.f;
+            uint32_t bits = 0;
+            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+                const uint64_t g = (uint64_t)gy * (uint64_t)W + (uint64_t)gx;
+                nx = normals[g * 4]; ny = normals[g * 4 + 1]; nz = normals[g * 4 + 2];
+                if (!(nx == 0.0f && ny == 0.0f && nz == 0.0f)) {       // (a background texel: only its normal is read)
+                    px = positions[g * 4]; py = positions[g * 4 + 1]; pz = positions[g * 4 + 2];
+                    bits = (lightsMap ? lightsMap[g] : 0xFFu) & ((1u << count) - 1u);
+#pragma unroll
+                    for (uint32_t l = 0; l < 8; ++l) {
+                        if (l >= count) break;
+                        if (!((bits >> l) & 1u)) continue;             // (a value whose map bit is clear is neither read nor staged)
+                        svalues[l * cells + s] = (uint16_t)wideLoadValue<true, false>(f, in, n, g, l);
+                    }
+                }
+            }
+            sa[s] = make_float2(nx, ny); sb[s] = make_float2(nz, px); sc[s] = make_float2(py, pz);
+            smap[s] = (uint8_t)bits;
+        }
+        __syncthreads();
+        if (x >= W || y >= H) return;
+        const WideTile t{ sa, sb, sc, svalues, smap, x0, y0, pitch, cells };
+        wideGuideTemporalThresholdPixel(f, k4, minHistory, t, h, x, y, W, H, T);   // (a DENSE pass has step >= 1)
+        if (!LAST) storeGuide();
+        wideGuidedPassPixel(f, t, x, y, W, H, step, T, v);
+    } else {
+        if (x >= W || y >= H) return;
+        const WideGlobal<true, false> t{ f, positions, normals, lightsMap, in, (uint64_t)W, n };
+        if (step > 0) wideGuideTemporalThresholdPixel(f, k4, minHistory, t, h, x, y, W, H, T);   // (step 0: the conversion needs no T)
+        if (!LAST) storeGuide();
+        wideGuidedPassPixel(f, t, x, y, W, H, step, T, v);
+    }
+#pragma unroll
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= count) break;
+        if (LAST) ((float*)out)[(uint64_t)l * n + p] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
+        else ((uint16_t*)out)[(uint64_t)l * n + p] = (uint16_t)v[l];
+    }
+}
+
+template <bool LAST>
+static int launchWideGuidedTemporalFirst(rts_ctx* ctx, void* stream, dim3 grid, const WideFilterList& f, uint32_t k4, uint32_t minHistory,
+                                         const GuideMoments& h, const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                         const void* in, uint32_t W, uint32_t H, int step, void* out, uint16_t* guide) {
+    if (step >= 1 && step <= kWideDenseMaxStep) {
+        const WideGeometry g = wideGeometry(f.count, step);
+        return launchPass(ctx, stream, grid, dim3(16, 16), g.bytes, wideGuidedTemporalKernel<LAST, true>, f, k4, minHistory, h, d_positions,
+                          d_normals, d_lights_map, in, (int)W, (int)H, step, g.pitch, out, guide);
+    }
+    return launchPass(ctx, stream, grid, dim3(16, 16), 0, wideGuidedTemporalKernel<LAST, false>, f, k4, minHistory, h, d_positions, d_normals,
+                      d_lights_map, in, (int)W, (int)H, step, 0, out, guide);
+}
+} // namespace rts_harness
+
+extern "C" int rtsh_accumulate_moments_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list, const rtsh_temporal_params* params,
+                                                              const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                              const uint8_t* d_counts, const float* d_prev_positions,
+                                                              const float* d_prev_normals, const uint16_t* d_prev_mean,
+                                                              const uint32_t* d_prev_square, const uint8_t* d_prev_lengths, uint32_t W,
+                                                              uint32_t H, uint16_t* d_mean_out, uint32_t* d_square_out,
+                                                              uint8_t* d_lengths_out, void* stream) {
+    if (!ctx) return RTS_ERR_INVALID_ARG;
+    rts_harness::MomentsList f;
+    const int s = rts_harness::makeMomentsList(list, params, d_positions, d_normals, d_counts, d_prev_positions, d_prev_normals, d_prev_mean,
+                                               d_prev_square, d_prev_lengths, W, H, d_mean_out, d_square_out, d_lengths_out, &f);
+    if (s != RTS_OK) return s;
+    // W, H <= 65536 (makeTemporalList): at most 4096 x 4096 blocks, inside every grid limit
+    const rts_harness::MomentsDeviceFrames t{ d_positions, d_normals, d_prev_positions, d_prev_normals, d_lights_map, d_counts, d_prev_lengths,
+                                              d_prev_mean, d_prev_square, d_mean_out, d_square_out, d_lengths_out, W, (uint64_t)W * H };
+    return rts_harness::launchPass(ctx, stream, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0, rts_harness::accumulateMomentsKernel, f,
+                                   t, (int)W, (int)H);
+}
+
+// The chain of a call: rtsh_wide_filter_guided_soft_light_list_device's, with the sibling kernel as its first pass.
+extern "C" int rtsh_wide_filter_guided_temporal_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list,
+                                                                       const rtsh_wide_guide_temporal_params* params, const float* d_positions,
+                                                                       const float* d_normals, const uint8_t* d_lights_map,
+                                                                       const uint8_t* d_counts, const uint16_t* d_mean, const uint32_t* d_square,
+                                                                       const uint8_t* d_lengths, uint32_t W, uint32_t H, float* d_visibility,
+                                                                       uint16_t* d_scratch, void* stream) {
+    using namespace rts_harness;
+    if (!ctx || !d_positions || !d_normals || !d_counts || !d_mean || !d_square || !d_lengths || !d_visibility) return RTS_ERR_INVALID_ARG;
+    WideFilterList f;
+    const int made = makeWideGuidedTemporalList(list, params, W, H, &f);
+    if (made != RTS_OK) return made;
+    const uint32_t k4 = params->guide_k4, minHistory = params->min_history;
+    const dim3 grid((W + 15) / 16, (H + 15) / 16);
+    if (grid.y > 65535u) return RTS_ERR_INVALID_ARG;
+    const size_t set = (size_t)f.count * (size_t)W * (size_t)H;
+    if (f.passes >= 2u && !d_scratch) return RTS_ERR_INVALID_ARG;
+    if (d_scratch)
+        for (size_t i = 0; i < 3; ++i)
+            if ((const void*)d_visibility == (const void*)(d_scratch + i * set)) return RTS_ERR_INVALID_ARG;
+    const GuideMoments h{ d_mean, d_square, d_lengths, W, (uint64_t)W * H };
+    if (f.passes <= 1u)
+        return launchWideGuidedTemporalFirst<true>(ctx, stream, grid, f, k4, minHistory, h, d_positions, d_normals, d_lights_map, d_counts, W, H,
+                                                   (int)f.passes, d_visibility, nullptr);
+    uint16_t* guide = d_scratch + 2 * set;
+    for (uint32_t k = 0; k < f.passes; ++k) {
+        const int step = 1 << k;
+        const void* in = k == 0 ? (const void*)d_counts : (const void*)(d_scratch + ((k - 1u) & 1u) * set);
+        uint16_t* mid = d_scratch + (k & 1u) * set;
+        int s;
+        if (k == 0)
+            s = launchWideGuidedTemporalFirst<false>(ctx, stream, grid, f, k4, minHistory, h, d_positions, d_normals, d_lights_map, in, W, H, step,
+                                                     mid, guide);
+        else if (k + 1u < f.passes)
+            s = launchWideGuidedPass<false, false>(ctx, stream, grid, f, k4, d_positions, d_normals, d_lights_map, in, W, H, step, mid, guide);
+        else s = launchWideGuidedPass<false, true>(ctx, stream, grid, f, k4, d_positions, d_normals, d_lights_map, in, W, H, step, d_visibility, guide);
+        if (s != RTS_OK) return s;
+    }
+    return RTS_OK;
+}

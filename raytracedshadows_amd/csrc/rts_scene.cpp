@@ -975,3 +975,137 @@ extern "C" int rtsh_accumulate_visibility_list_clamped(const rts_light_list* lis
     parallelFor(n, 256, threads, [&](size_t i) { accumulatePixel<true>(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H, margin); });
     return RTS_OK;
 }
+
+// ---- the temporal accumulation of a soft light list's count moments (include/rts_scene.h; per-pixel rule in rts_closest_hit.h:
+// accumulateMomentsPixel) ----
+namespace rts_harness {
+// Shared by the host and device forms: every refusal that needs no context -- makeTemporalList's own over a stand-in list of the same
+// count (counts in the place of visibility, the mean planes in the place of the float history), then the square planes' -- and the
+// condensed form the per-pixel rule reads.
+int makeMomentsList(const rts_soft_light_list* list, const rtsh_temporal_params* p, const void* positions, const void* normals,
+                    const void* counts, const void* prevPositions, const void* prevNormals, const void* prevMean, const void* prevSquare,
+                    const void* prevLengths, uint32_t W, uint32_t H, const void* meanOut, const void* squareOut, const void* lengthsOut,
+                    MomentsList* out) {
+    if (!rts::softListOk(list) || !squareOut) return RTS_ERR_INVALID_ARG;
+    rts_light_list hard;
+    std::memset(&hard, 0, sizeof(hard));
+    hard.count = list->count;
+    for (uint32_t l = 0; l < list->count; ++l) hard.lights[l].type = list->lights[l].type;
+    if ((prevSquare != nullptr) != (prevMean != nullptr)) return RTS_ERR_INVALID_ARG;               // all five prev_* or none
+    const int s = makeTemporalList(&hard, p, positions, normals, counts, prevPositions, prevNormals, prevMean, prevLengths, W, H, meanOut,
+                                   lengthsOut, &out->t);
+    if (s != RTS_OK) return s;
+    if (prevSquare && squareOut == prevSquare) return RTS_ERR_INVALID_ARG;                          // history must ping-pong
+    for (uint32_t l = 0; l < 8; ++l) {
+        out->samples[l] = l < list->count && list->lights[l].nsamples > 1u ? list->lights[l].nsamples : 1u;
+        out->scale[l] = wideFilterScale(out->samples[l]);
+    }
+    return RTS_OK;
+}
+
+namespace {
+// Both frames as accumulateMomentsPixel reads them on the host: straight from the buffers.
+struct MomentsFrames {
+    const float *positions, *normals, *prevPositions, *prevNormals;
+    const uint8_t *map, *counts, *prevLengths;
+    const uint16_t* prevMeans;
+    const uint32_t* prevSquares;
+    uint16_t* meanOut;
+    uint32_t* squareOut;
+    uint8_t* lengthsOut;
+    size_t W, n;
+    size_t at(int x, int y) const { return (size_t)y * W + (size_t)x; }
+    static V3 xyz(const float* base, size_t i) { const float* v = base + i * 4; return V3{ v[0], v[1], v[2] }; }
+    V3 normal(int x, int y) const { return xyz(normals, at(x, y)); }
+    V3 position(int x, int y) const { return xyz(positions, at(x, y)); }
+    uint32_t bits(int x, int y) const { return map ? map[at(x, y)] : 0xFFu; }
+    uint32_t count(uint32_t l, int x, int y) const { return counts[(size_t)l * n + at(x, y)]; }
+    V3 prevNormal(int x, int y) const { return xyz(prevNormals, at(x, y)); }
+    V3 prevPosition(int x, int y) const { return xyz(prevPositions, at(x, y)); }
+    uint32_t prevLength(uint32_t l, int x, int y) const { return prevLengths[(size_t)l * n + at(x, y)]; }
+    uint32_t prevMean(uint32_t l, int x, int y) const { return prevMeans[(size_t)l * n + at(x, y)]; }
+    uint32_t prevSquare(uint32_t l, int x, int y) const { return prevSquares[(size_t)l * n + at(x, y)]; }
+    void store(uint32_t l, int x, int y, uint32_t mean, uint32_t square, uint32_t length) const {
+        meanOut[(size_t)l * n + at(x, y)] = (uint16_t)mean;
+        squareOut[(size_t)l * n + at(x, y)] = square;
+        lengthsOut[(size_t)l * n + at(x, y)] = (uint8_t)length;
+    }
+};
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_accumulate_moments_soft_light_list(const rts_soft_light_list* list, const rtsh_temporal_params* params,
+                                                       const float* positions, const float* normals, const uint8_t* lights_map,
+                                                       const uint8_t* counts, const float* prev_positions, const float* prev_normals,
+                                                       const uint16_t* prev_mean, const uint32_t* prev_square, const uint8_t* prev_lengths,
+                                                       uint32_t W, uint32_t H, uint16_t* mean_out, uint32_t* square_out,
+                                                       uint8_t* lengths_out, int threads) {
+    MomentsList f;
+    const int s = makeMomentsList(list, params, positions, normals, counts, prev_positions, prev_normals, prev_mean, prev_square,
+                                  prev_lengths, W, H, mean_out, square_out, lengths_out, &f);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const MomentsFrames t{ positions, normals, prev_positions, prev_normals, lights_map, counts, prev_lengths, prev_mean, prev_square,
+                           mean_out, square_out, lengths_out, W, n };
+    parallelFor(n, 256, threads, [&](size_t i) { accumulateMomentsPixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H); });
+    return RTS_OK;
+}
+
+// ---- the guided wide filter with a temporal threshold (include/rts_scene.h; per-pixel rule in rts_closest_hit.h:
+// wideGuideTemporalThresholdPixel, wideGuidedPassPixel) ----
+namespace rts_harness {
+// Shared by the host and device forms: the refusals, and the unguided filter's condensed list.
+int makeWideGuidedTemporalList(const rts_soft_light_list* list, const rtsh_wide_guide_temporal_params* p, uint32_t W, uint32_t H,
+                               WideFilterList* out) {
+    if (!p || p->min_history == 0u || p->min_history > 255u) return RTS_ERR_INVALID_ARG;
+    rtsh_wide_guide_params q;
+    std::memset(&q, 0, sizeof(q));
+    q.passes = p->passes; q.normal_cos_min = p->normal_cos_min; q.plane_eps = p->plane_eps; q.guide_k4 = p->guide_k4;
+    return makeWideGuidedList(list, &q, W, H, out);
+}
+} // namespace rts_harness
+
+extern "C" int rtsh_wide_filter_guided_temporal_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_guide_temporal_params* params,
+                                                                const float* positions, const float* normals, const uint8_t* lights_map,
+                                                                const uint8_t* counts, const uint16_t* mean, const uint32_t* square,
+                                                                const uint8_t* lengths, uint32_t W, uint32_t H, float* visibility,
+                                                                int threads) {
+    if (!positions || !normals || !counts || !mean || !square || !lengths || !visibility) return RTS_ERR_INVALID_ARG;
+    WideFilterList f;
+    const int s = makeWideGuidedTemporalList(list, params, W, H, &f);
+    if (s != RTS_OK) return s;
+    const uint32_t k4 = params->guide_k4, minHistory = params->min_history;
+    const size_t n = (size_t)W * H, set = (size_t)f.count * n;
+    const GuideMoments h{ mean, square, lengths, W, n };
+    std::vector<uint16_t> scratch;                                       // two ping-pong sets, then the planes of T: the device form's
+    try {
+        if (f.passes >= 2u) scratch.resize(3 * set);
+    } catch (const std::bad_alloc&) {
+        return RTS_ERR_CAPACITY;
+    }
+    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
+    for (uint32_t k = 0; k < launches; ++k) {
+        const bool first = k == 0u, last = k + 1u == launches;
+        const int step = f.passes == 0u ? 0 : 1 << k;
+        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * set;
+        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * set;
+        uint16_t* guide = f.passes >= 2u ? scratch.data() + 2 * set : nullptr;
+        const WideFrameTexels<false> t{ positions, normals, lights_map, first ? counts : nullptr, in, f.samples, f.scale, W, n };
+        parallelFor(n, 256, threads, [&](size_t i) {
+            const int x = (int)(i % W), y = (int)(i / W);
+            uint32_t T[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, v[8];
+            if (first) {
+                if (step > 0) wideGuideTemporalThresholdPixel(f, k4, minHistory, t, h, x, y, (int)W, (int)H, T);
+                if (!last) for (uint32_t l = 0; l < f.count; ++l) guide[(size_t)l * n + i] = (uint16_t)T[l];
+            } else {
+                for (uint32_t l = 0; l < f.count; ++l) T[l] = guide[(size_t)l * n + i];
+            }
+            wideGuidedPassPixel(f, t, x, y, (int)W, (int)H, step, T, v);
+            for (uint32_t l = 0; l < f.count; ++l) {
+                if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
+                else out[(size_t)l * n + i] = (uint16_t)v[l];
+            }
+        });
+    }
+    return RTS_OK;
+}

@@ -23,7 +23,15 @@ the mean absolute difference to the 48-sample trace of the NEW light over its ac
     unclamped    as before: the history of the old light is blended in
     clamp_r      clamped at r = 1, 2 and 4, margin 0
     reset        unclamped, with the light in reset_lights on the frame of the jump: its history thrown away
-and a STILL row: the same light standing for all JUMP_AT + AFTER frames, where the clamp can only cost noise reduction."""
+and a STILL row: the same light standing for all JUMP_AT + AFTER frames, where the clamp can only cost noise reduction.
+
+    python tools/list_temporal_quality.py --guide-history [--out profiles/r31/list_moments_quality.jsonl]
+
+The temporal guide of the wide filter (rtsh_accumulate_moments_soft_light_list, rtsh_wide_filter_guided_temporal_soft_light_list,
+DESIGN.md 4.27): the still-camera scenes and lights of the first table; the count moments are accumulated per frame (max_length 32),
+and after 4, 8 and 12 frames THAT frame's jittered counts are filtered, two passes, by the unguided wide filter, by 4.26's guide and
+by the temporal guide (min_history 4) at guide_k4 8, 12 and 16; "raw" is count / 4 of that frame.  Every row twice: the shared table
+rotated by one entry per frame, and by the sample count per frame (4)."""
 import argparse
 import json
 import os
@@ -90,14 +98,61 @@ def jump_rows():
     return rows
 
 
+GUIDE_FRAMES, GUIDE_K4, GUIDE_PASSES, GUIDE_MIN_HISTORY = (4, 8, 12), (8, 12, 16), 2, 4
+
+
+def guide_rows():
+    from raytracedshadows_amd import api, scenes
+    rows = []
+    for name, sc, W, H in (("cornell_128", scenes.cornell(), 128, 128), ("terrain_96", scenes.terrain(23), 96, 96)):
+        verts, idx = sc.flat()
+        packed = api.BVHBuilder().build(verts, 8, idx, sc.triangle_count).m_packedNodes
+        pos, nrm, _ = api.primary_gbuffer(packed, sc.eye, sc.target, sc.fovy, W, H)
+        k = api.RayTracingConstants.make(sc.eye, sc.light_direction, W, H)
+        diag = float(np.linalg.norm(np.asarray(sc.bbox_max, np.float64) - np.asarray(sc.bbox_min, np.float64)))
+        table = scenes.jitter_offsets(48, 1.0, 19)
+        cam = (sc.eye, sc.target, sc.fovy)
+        eps = 0.005 * diag
+        tp = api.TemporalParams.from_cameras(cam, cam, W, H, 0.9, eps, 32)
+        for radius in (0.03, 0.1):
+            light = lambda n, t=table: api.SoftLightList.make([(api.Light.POINT, sc.light_point, n, 0, radius * diag)], t)
+            facing = api.facing_lights(k, light(4).hard_list(), pos, nrm)
+            active = (facing & 1) != 0
+            truth = api.soft_light_list(packed, k, light(48), pos, W, H, facing)[0].astype(np.float32) / np.float32(48)
+            mad = lambda v: round(float(np.abs(v[active] - truth[active]).mean()), 5)
+            for rotate in (1, 4):
+                moments = None
+                for frame in range(max(GUIDE_FRAMES)):
+                    lst = light(4, np.ascontiguousarray(np.roll(table, -frame * rotate, axis=0)))
+                    counts = api.soft_light_list_adaptive(packed, k, lst, (2,), pos, W, H, facing, want_refined=False, tables=(48,))[0]
+                    moments = api.accumulate_moments_soft_light_list(lst, tp, pos, nrm, counts, None if moments is None else (pos, nrm) + moments,
+                                                                     facing)
+                    if frame + 1 not in GUIDE_FRAMES:
+                        continue
+                    assert int(moments[2][0][active].min()) == frame + 1          # a still camera: every pixel keeps its history
+                    row = {"scene": name, "light": radius, "rotate": rotate, "history": frame + 1, "passes": GUIDE_PASSES,
+                           "min_history": GUIDE_MIN_HISTORY, "raw": mad(counts[0].astype(np.float32) / np.float32(4)),
+                           "unguided": mad(api.wide_filter_soft_light_list(lst, api.WideFilterParams.make(GUIDE_PASSES, 0.9, eps), pos, nrm, counts,
+                                                                           facing)[0]), "guided": {}, "temporal": {}}
+                    for k4 in GUIDE_K4:
+                        row["guided"][str(k4)] = mad(api.wide_filter_guided_soft_light_list(
+                            lst, api.WideGuideParams.make(GUIDE_PASSES, k4, 0.9, eps), pos, nrm, counts, facing)[0])
+                        row["temporal"][str(k4)] = mad(api.wide_filter_guided_temporal_soft_light_list(
+                            lst, api.WideGuideTemporalParams.make(GUIDE_PASSES, k4, GUIDE_MIN_HISTORY, 0.9, eps), pos, nrm, counts, moments, facing)[0])
+                    rows.append(row)
+                    print(json.dumps(row))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--jump", action="store_true", help="the light-jump scenario of the neighbourhood clamp instead of the still-camera table")
+    ap.add_argument("--guide-history", action="store_true", help="the temporal guide of the wide filter against the unguided filter and 4.26's guide")
     args = ap.parse_args()
     from raytracedshadows_amd import api, scenes
-    rows = jump_rows() if args.jump else []
-    if args.jump:
+    rows = jump_rows() if args.jump else (guide_rows() if args.guide_history else [])
+    if args.jump or args.guide_history:
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:

@@ -2,7 +2,7 @@
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
                            [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]
-                                          [--filter R [--spread S] | --filter-passes K [--filter-guide K4]] [--plane-eps E] [--normal-cos C]
+                                          [--filter R [--spread S] | --filter-passes K [--filter-guide K4 [--guide-history M]]] [--plane-eps E] [--normal-cos C]
                                                       [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]]]]]
 
 --temporal F (with --soft-list N --filter R): F frames are rendered -- trace, filter, rtsh_accumulate_visibility_list_device with
@@ -16,6 +16,9 @@ visibility planes by rtsh_combine_visibility_list_device; with --distance the di
 --filter-passes K (in place of --filter R; the two exclude each other): the wide a-trous filter rtsh_wide_filter_soft_light_list_device,
 K = 0..5 passes of 5 x 5 taps 1, 2, 4, 8 and 16 pixels apart -- a reach of 2, 6, 14, 30, 62 pixels --, same thresholds, no distance
 guide; it feeds --temporal and --clamp exactly as --filter does.
+--guide-history M (with --filter-guide K4 and --temporal F): per frame the count moments are accumulated
+(rtsh_accumulate_moments_soft_light_list_device) and the guide takes its variance from them where a pixel has at least M frames of
+history (rtsh_wide_filter_guided_temporal_soft_light_list_device); without --temporal it has no meaning and is refused.
 --filter-guide K4 (with --filter-passes K): the variance-guided form rtsh_wide_filter_guided_soft_light_list_device -- a tap is accepted
 for a light only where its value lies within K4 / 4 standard deviations of the centre's, the deviation estimated from the count planes
 themselves (c (n - c) over the 3 x 3 neighbourhood) --, K4 = 0..255; the passes then blur noise and stop at sharp shadow edges.
@@ -135,11 +138,14 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
               f"{[round(float(took[l].mean()), 3) for l in range(count)]}")
 
 
-def list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, d_dist=None, d_scratch=None):
+def list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, d_dist=None, d_scratch=None, d_moments=None):
     """The filter stage of a soft light list: the tent filter of a ``FilterParams`` (--filter R) or the wide a-trous filter of a
     ``WideFilterParams`` (--filter-passes K, which takes a scratch and no distances) or its variance-guided form of a ``WideGuideParams``
-    (--filter-guide K4)."""
-    if isinstance(filt, api.WideGuideParams):
+    (--filter-guide K4), or of a ``WideGuideTemporalParams`` with this frame's count moments (--guide-history M)."""
+    if isinstance(filt, api.WideGuideTemporalParams):
+        api.wide_filter_guided_temporal_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, d_moments, W, H, d_vis,
+                                                               d_scratch=d_scratch, d_lights_map=d_map)
+    elif isinstance(filt, api.WideGuideParams):
         api.wide_filter_guided_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_scratch=d_scratch,
                                                       d_lights_map=d_map)
     elif isinstance(filt, api.WideFilterParams):
@@ -149,12 +155,15 @@ def list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_m
 
 
 def wide_scratch_bytes(api, filt, count, W, H):
-    if isinstance(filt, api.WideGuideParams):
+    if isinstance(filt, (api.WideGuideParams, api.WideGuideTemporalParams)):
         return api.wide_filter_guided_scratch_bytes(count, W, H)
     return api.wide_filter_scratch_bytes(count, W, H)
 
 
 def filter_words(api, filt):
+    if isinstance(filt, api.WideGuideTemporalParams):
+        return (f"{filt.passes} a-trous passes (reach {2 * (2 ** filt.passes - 1)} pixels), guided at {filt.guide_k4 / 4:g} deviations by the "
+                f"temporal variance from {filt.min_history} frames of history on")
     if isinstance(filt, api.WideGuideParams):
         return f"{filt.passes} a-trous passes (reach {2 * (2 ** filt.passes - 1)} pixels), variance-guided at {filt.guide_k4 / 4:g} deviations"
     if isinstance(filt, api.WideFilterParams):
@@ -176,7 +185,9 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
     gbuf = [(ctx.malloc(n * 16), ctx.malloc(n * 16)) for _ in range(2)]
     hist = [(ctx.malloc(count * n * 4), ctx.malloc(count * n)) for _ in range(2)]
     d_map, d_counts, d_vis, d_rgb = ctx.malloc(n), ctx.malloc(count * n), ctx.malloc(count * n * 4), ctx.malloc(n * 3)
-    wide = isinstance(filt, (api.WideFilterParams, api.WideGuideParams))
+    wide = isinstance(filt, (api.WideFilterParams, api.WideGuideParams, api.WideGuideTemporalParams))
+    temporal_guide = isinstance(filt, api.WideGuideTemporalParams)
+    moments = [(ctx.malloc(count * n * 2), ctx.malloc(count * n * 4), ctx.malloc(count * n)) for _ in range(2)] if temporal_guide else None
     d_scratch = ctx.malloc(wide_scratch_bytes(api, filt, count, W, H)) if wide and filt.passes >= 2 else None
     eyes = [orbit(sc.eye, sc.target, orbit_deg * (k - (frames - 1))) for k in range(frames)]      # the last frame is the scene's own camera
     t0 = time.time()
@@ -192,9 +203,12 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
                                                       tables=(table,) * count if table else None)
         else:
             ctx.trace_soft_light_list_device(constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
-        list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, None, d_scratch)
         tp = api.TemporalParams.from_cameras((eyes[k], sc.target, sc.fovy), (eyes[max(k - 1, 0)], sc.target, sc.fovy), W, H,
                                              filt.normal_cos_min, filt.plane_eps, max_length)
+        if temporal_guide:                                               # this frame's count moments, then the filter they guide
+            api.accumulate_moments_soft_light_list_device(ctx, lights, tp, d_pos, d_nrm, d_counts, W, H, *moments[k % 2],
+                                                          d_prev=None if k == 0 else gbuf[(k - 1) % 2] + moments[(k - 1) % 2], d_lights_map=d_map)
+        list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, None, d_scratch, moments[k % 2] if temporal_guide else None)
         d_prev = None if k == 0 else gbuf[(k - 1) % 2] + hist[(k - 1) % 2]
         api.accumulate_visibility_list_device(ctx, hard, tp, d_pos, d_nrm, d_vis, W, H, hist[k % 2][0], hist[k % 2][1], d_prev=d_prev,
                                               d_lights_map=d_map, clamp=clamp)
@@ -246,6 +260,10 @@ def main():
     ap.add_argument("--spread", type=float, default=0.25, help="with --filter and --distance: the penumbra width per unit of blocker distance")
     ap.add_argument("--plane-eps", type=float, default=0.05, help="with --filter: the largest plane distance of an accepted tap (world units)")
     ap.add_argument("--normal-cos", type=float, default=0.9, help="with --filter: the smallest N.N' of an accepted tap")
+    ap.add_argument("--guide-history", type=int, default=0, metavar="M",
+                    help="with --filter-guide K4 and --temporal F: accumulate the count moments per frame "
+                         "(rtsh_accumulate_moments_soft_light_list_device) and take the guide's variance from them where a pixel has at "
+                         "least M frames of history (rtsh_wide_filter_guided_temporal_soft_light_list_device), 1 <= M <= 255")
     ap.add_argument("--temporal", type=int, default=0, metavar="F",
                     help="with --soft-list N --filter R: render F frames, accumulate the visibility over them (ping-pong history, the "
                          "offsets table rotated by one entry per frame) and light the last one from it")
@@ -283,6 +301,10 @@ def main():
                 filt = api.WideFilterParams.make(args.filter_passes, args.normal_cos, args.plane_eps)
             if args.filter_guide >= 0:
                 filt = api.WideGuideParams.make(args.filter_passes, args.filter_guide, args.normal_cos, args.plane_eps)
+            if args.guide_history:
+                if args.filter_guide < 0 or not args.temporal or not 1 <= args.guide_history <= 255:
+                    sys.exit("render: --guide-history M goes with --filter-guide K4 and --temporal F, 1 <= M <= 255")
+                filt = api.WideGuideTemporalParams.make(args.filter_passes, args.filter_guide, args.guide_history, args.normal_cos, args.plane_eps)
             if args.temporal:
                 if filt is None or args.distance or args.refined:
                     sys.exit("render: --temporal F goes with --soft-list N and --filter R or --filter-passes K, without --distance and --refined")
