@@ -592,8 +592,9 @@ int rtsh_accumulate_moments_soft_light_list_device(rts_ctx* ctx, const rts_soft_
  *     counted pixels only, each on its element type's alignment.
  *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the guided filter refuses; a NULL mean, square or lengths;
  *     min_history 0 or above 255.
- *   * OUT OF SCOPE: filtering the accumulated mean plane in place of this frame's counts (it has V_0's format), variance propagated
- *     through the passes, motion vectors, a guide for the tent filter, row ranges and stripes, hard lists. */
+ *   * OUT OF SCOPE: variance propagated through the passes, motion vectors, a guide for the tent filter, row ranges and stripes, hard
+ *     lists.  (Filtering the accumulated mean plane in place of this frame's counts: rtsh_wide_filter_mean_soft_light_list and
+ *     rtsh_wide_filter_guided_temporal_mean_soft_light_list below.) */
 typedef struct rtsh_wide_guide_temporal_params {
     uint32_t passes;          /* 0 .. RTSH_WIDE_FILTER_MAX_PASSES (5) */
     float    normal_cos_min;  /* a tap needs N_p . N_q >= this */
@@ -611,6 +612,69 @@ int rtsh_wide_filter_guided_temporal_soft_light_list_device(rts_ctx* ctx, const 
                                                             const float* d_normals, const uint8_t* d_lights_map, const uint8_t* d_counts,
                                                             const uint16_t* d_mean, const uint32_t* d_square, const uint8_t* d_lengths,
                                                             uint32_t W, uint32_t H, float* d_visibility, uint16_t* d_scratch, void* stream);
+
+/* THE WIDE FILTERS FED FROM THE ACCUMULATED MEAN: SVGF's order -- integrate over time first, then run the a-trous passes over the
+ * integrated signal.  rtsh_accumulate_moments_soft_light_list* above writes, per light, a uint16_t `mean` plane in the wide filter's own
+ * fixed point; the two families here run the wide filter and the temporally guided wide filter over THAT plane in the place of this
+ * frame's count bytes.  Everything of those filters holds (16-bit planes, integer sums, bit-for-bit host and device forms); the notation
+ * -- n_l, S_l, on, bg, geom, b = {6, 4, 1}, V_0 -- is the wide filter's.
+ *   INPUT: V_0'(q, l) = min(mean[l][q], n_l * S_l) at an active (pixel, light), 0 elsewhere.  mean: count planes of uint16_t, the
+ *     moments pass's output for THIS frame.  The CLAMP is this family's own: the moments pass never writes more than n_l * S_l (its
+ *     RANGE anchor), but arbitrary plane contents are allowed and visibility must stay in [0, 1] (65535 > n_l * S_l for n_l = 48: 65520).
+ *     mean is read only where on(q, l) holds and q is not background.
+ * rtsh_wide_filter_mean_soft_light_list*: THE UNGUIDED FILTER.  rtsh_wide_filter_soft_light_list's rule word for word with V_0' in the
+ *   place of V_0: PASS k over the 5 x 5 taps 1 << k apart, integer weights b[|dx|] * b[|dy|], the centre always accepted, another tap
+ *   where geom(p, q) and on(q, l) hold, V_(k+1) = (2 * num + den) / (2 * den), the ROUNDED MEAN; OUTPUT
+ *   visibility[l * W * H + p] = (float)V_passes / (float)(n_l * S_l), +0.0f at an inactive pixel.  The argument list is that
+ *   function's with `const uint16_t* mean` in the place of counts; rtsh_wide_filter_params, the scratch
+ *   (rtsh_wide_filter_scratch_bytes: two ping-pong sets) and the refusals are unchanged.
+ * rtsh_wide_filter_guided_temporal_mean_soft_light_list*: THE GUIDED FILTER.  rtsh_wide_filter_guided_temporal_soft_light_list's rule
+ *   with the same ONE change of input; its argument list, rtsh_wide_guide_temporal_params and the three scratch sets
+ *   (rtsh_wide_filter_guided_scratch_bytes).  ENERGY E*, G, D and T are exactly that filter's:
+ *     E*(q, l) = n_l * max(0, square[l][q] - mean[l][q]^2), from the UNCLAMPED planes, where lengths[l][q] >= min_history;
+ *     E*(q, l) = V_0(q, l) * (n_l * S_l - V_0(q, l)) = c (n - c) S^2 from THIS frame's count byte elsewhere -- which is why counts stays
+ *     in the argument list; a count byte is read only at a counted pixel whose length is below min_history;
+ *     G, D over the 3 x 3 with weights {1, 2, 1} x {1, 2, 1}, no geom test; T = min(65535, isqrt((guide_k4^2 * G) / (16 * D * n_l))),
+ *     65535 for n_l <= 1.  Only the values that the passes AVERAGE and COMPARE against T are V_0' (and the planes that follow from it):
+ *     a tap other than the centre is accepted for light l when geom(p, q) and on(q, l) hold and |V_k(q, l) - V_k(p, l)| <= T(p, l).
+ *     T DOES NOT SHRINK WITH THE HISTORY'S LENGTH: it is the spread of one frame's V_0 about the mean, while the mean of m frames
+ *     scatters by about 1 / sqrt(m) of that -- so at equal guide_k4 this form accepts more than the count-input form.  Dividing the
+ *     variance by the length is out of scope (below).
+ * ANCHORS: (1) Where mean[l][q] == min(c_l(q), n_l) * S_l at every active (pixel, light), both functions give bit for bit the planes of
+ * their count-input counterparts (rtsh_wide_filter_soft_light_list*, rtsh_wide_filter_guided_temporal_soft_light_list*) for the same
+ * inputs: first-frame moments are such a case, so is max_length 1.  (2) passes == 0 gives (float)min(mean, n S) / (float)(n S).
+ * (3) Where every accepted tap of every pass carries one value, the result is that value's quotient.  (4) RANGE: every V_(k+1)(p) lies
+ * between the smallest and the largest accepted V_k, and visibility stays in [0, 1] whatever the mean plane holds.  (5) The guided
+ * form: guide_k4 == 0 gives the passes == 0 plane of every light with n_l >= 2; a light with n_l <= 1 gives rtsh_wide_filter_mean_soft_light_list's plane; every
+ * counted length below min_history together with anchor 1's condition gives rtsh_wide_filter_guided_soft_light_list's bits.
+ *   * lights_map may be NULL.  mean needs 2-byte alignment and no more, square 4, every byte plane none.  Planes of any buffer from
+ *     `count` up are never touched.  Host forms: multi-threaded, they allocate their own intermediates.
+ *   * device forms: DEVICE buffers, asynchronous on `stream`, allocate nothing, read nothing back.  Under graph capture a call adds
+ *     exactly max(1, passes) KERNEL nodes on one chain, list and parameters by value; only the FIRST differs from the counterpart's.
+ *     d_scratch may be NULL when passes <= 1, and nothing of it is touched then; in the guided form the first pass writes T to the
+ *     third set for passes >= 2.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the counterpart refuses, with mean in the place of counts;
+ *     a NULL mean; d_visibility equal to the start of any scratch set (two for the unguided form, three for the guided one).
+ *   * OUT OF SCOPE: variance divided by the history's length or propagated through the passes, a clamp of the moments' history, motion
+ *     vectors, the tent filter, hard lists, row ranges and stripes, an LDS-staged form of the moments, and feeding the float visibility
+ *     history of rtsh_accumulate_visibility_list to the a-trous passes (it is not fixed point). */
+int rtsh_wide_filter_mean_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_filter_params* params, const float* positions,
+                                          const float* normals, const uint8_t* lights_map, const uint16_t* mean, uint32_t W, uint32_t H,
+                                          float* visibility, int threads);
+int rtsh_wide_filter_mean_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list, const rtsh_wide_filter_params* params,
+                                                 const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                 const uint16_t* d_mean, uint32_t W, uint32_t H, float* d_visibility, uint16_t* d_scratch,
+                                                 void* stream);
+int rtsh_wide_filter_guided_temporal_mean_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_guide_temporal_params* params,
+                                                          const float* positions, const float* normals, const uint8_t* lights_map,
+                                                          const uint8_t* counts, const uint16_t* mean, const uint32_t* square,
+                                                          const uint8_t* lengths, uint32_t W, uint32_t H, float* visibility, int threads);
+int rtsh_wide_filter_guided_temporal_mean_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list,
+                                                                 const rtsh_wide_guide_temporal_params* params, const float* d_positions,
+                                                                 const float* d_normals, const uint8_t* d_lights_map,
+                                                                 const uint8_t* d_counts, const uint16_t* d_mean, const uint32_t* d_square,
+                                                                 const uint8_t* d_lengths, uint32_t W, uint32_t H, float* d_visibility,
+                                                                 uint16_t* d_scratch, void* stream);
 
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.

@@ -569,6 +569,15 @@ _sig("rtsh_wide_filter_guided_temporal_soft_light_list", C.c_int, C.POINTER(Soft
 _sig("rtsh_wide_filter_guided_temporal_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList),
      C.POINTER(WideGuideTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
      C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_wide_filter_mean_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(WideFilterParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_wide_filter_mean_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(WideFilterParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_wide_filter_guided_temporal_mean_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(WideGuideTemporalParams),
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_wide_filter_guided_temporal_mean_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList),
+     C.POINTER(WideGuideTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_facing_active", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
      C.c_void_p)
 _sig("rtsh_facing_active_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
@@ -1922,6 +1931,73 @@ def wide_filter_guided_temporal_soft_light_list_device(ctx, lights, params, d_po
                                                                         C.c_void_p(m[2] or 0), width, height, C.c_void_p(d_visibility),
                                                                         C.c_void_p(d_scratch or 0), C.c_void_p(stream or 0)),
            "rtsh_wide_filter_guided_temporal_soft_light_list_device")
+
+
+def wide_filter_mean_soft_light_list(lights, params, positions, normals, mean, lights_map=None, threads=0):
+    """The wide (a-trous) filter of a soft light list's ACCUMULATED MEAN on the host (rtsh_wide_filter_mean_soft_light_list):
+    ``float32[count, H, W]`` visibility.  ``params`` a ``WideFilterParams``; ``mean`` = the ``uint16[count, H, W]`` mean planes of
+    ``accumulate_moments_soft_light_list`` for this frame."""
+    name = "rtsh_wide_filter_mean_soft_light_list"
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    mean = np.ascontiguousarray(mean, np.uint16)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    if mean.size < count * H * W or (lights_map is not None and lights_map.size != H * W) or \
+            (positions is not None and positions.size != H * W * 4):
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    visibility = np.zeros((count, H, W), np.float32)
+    _check(_lib.rtsh_wide_filter_mean_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
+                                                      _ptr_or_none(lights_map), _ptr(mean), W, H, _ptr(visibility), threads), name)
+    return visibility
+
+
+def wide_filter_mean_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_mean, width, height, d_visibility, d_scratch=None,
+                                            d_lights_map=None, stream=None):
+    """The wide filter of a soft light list's accumulated mean on the GPU: as ``wide_filter_soft_light_list_device``, over the uint16
+    mean planes of the moments pass in the place of the count planes."""
+    _check(_lib.rtsh_wide_filter_mean_soft_light_list_device(ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions or 0),
+                                                             C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0), C.c_void_p(d_mean or 0),
+                                                             width, height, C.c_void_p(d_visibility), C.c_void_p(d_scratch or 0),
+                                                             C.c_void_p(stream or 0)),
+           "rtsh_wide_filter_mean_soft_light_list_device")
+
+
+def wide_filter_guided_temporal_mean_soft_light_list(lights, params, positions, normals, counts, moments, lights_map=None, threads=0):
+    """The guided wide filter with a temporal threshold over the ACCUMULATED MEAN on the host
+    (rtsh_wide_filter_guided_temporal_mean_soft_light_list): ``float32[count, H, W]`` visibility.  Arguments as for
+    ``wide_filter_guided_temporal_soft_light_list``; the passes average ``moments[0]``, ``counts`` feeds the threshold's fallback."""
+    name = "rtsh_wide_filter_guided_temporal_mean_soft_light_list"
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    counts = np.ascontiguousarray(counts, np.uint8)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    mean, square, lengths = (np.ascontiguousarray(a, t) for a, t in zip(moments, (np.uint16, np.uint32, np.uint8)))
+    if counts.size < count * H * W or (lights_map is not None and lights_map.size != H * W) or \
+            (positions is not None and positions.size != H * W * 4) or any(a.size < count * H * W for a in (mean, square, lengths)):
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    visibility = np.zeros((count, H, W), np.float32)
+    _check(_lib.rtsh_wide_filter_guided_temporal_mean_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
+                                                                      _ptr_or_none(lights_map), _ptr(counts), _ptr(mean), _ptr(square),
+                                                                      _ptr(lengths), W, H, _ptr(visibility), threads), name)
+    return visibility
+
+
+def wide_filter_guided_temporal_mean_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_counts, d_moments, width, height,
+                                                            d_visibility, d_scratch=None, d_lights_map=None, stream=None):
+    """The guided mean filter on the GPU: arguments as for ``wide_filter_guided_temporal_soft_light_list_device``; max(1, passes)
+    kernels, asynchronous."""
+    m = tuple(d_moments)
+    _check(_lib.rtsh_wide_filter_guided_temporal_mean_soft_light_list_device(ctx.handle, _ref(lights), _ref(params),
+                                                                             C.c_void_p(d_positions or 0), C.c_void_p(d_normals),
+                                                                             C.c_void_p(d_lights_map or 0), C.c_void_p(d_counts or 0),
+                                                                             C.c_void_p(m[0] or 0), C.c_void_p(m[1] or 0), C.c_void_p(m[2] or 0),
+                                                                             width, height, C.c_void_p(d_visibility),
+                                                                             C.c_void_p(d_scratch or 0), C.c_void_p(stream or 0)),
+           "rtsh_wide_filter_guided_temporal_mean_soft_light_list_device")
 
 
 def write_ppm(path, rgb):

@@ -731,6 +731,72 @@ RTS_HD void wideGuideTemporalThresholdPixel(const WideFilterList& f, uint32_t k4
     }
 }
 
+// The WIDE FILTERS FED FROM THE ACCUMULATED MEAN (include/rts_scene.h, rtsh_wide_filter_mean_soft_light_list and
+// rtsh_wide_filter_guided_temporal_mean_soft_light_list): the passes above over V_0' = min(mean, n_l * S_l) in the place of V_0.  The
+// passes are wideFilterPassPixel and wideGuidedPassPixel as they are -- a `Texels` whose value(x, y, l) is wideMeanInput of the mean
+// plane is the whole change.  The threshold of the guided form is a SIBLING of wideGuideTemporalThresholdPixel (which keeps its text, and
+// with it every kernel that calls it): E* is that function's, from the UNCLAMPED moments where the history is long enough, but its
+// Bernoulli fallback cannot come from t.value -- the window now holds the mean --, so the count byte is read where it is, and only
+// where lengths < minHistory.
+RTS_HD uint32_t wideMeanInput(uint32_t mean, uint32_t samples, uint32_t scale) {                          // V_0'
+    const uint32_t full = samples * scale;
+    return mean < full ? mean : full;
+}
+
+struct GuideMomentsCounts {
+    GuideMoments m;
+    const uint8_t* counts;
+};
+
+template <class Texels>
+RTS_HD void wideGuideTemporalMeanThresholdPixel(const WideFilterList& f, uint32_t k4, uint32_t minHistory, const Texels& t,
+                                                const GuideMomentsCounts& h, int x, int y, int W, int H, uint32_t* T8) {
+    const uint32_t onp = isBackground(t.normal(x, y)) ? 0u : (t.bits(x, y) & ((1u << f.count) - 1u));
+    uint32_t nb[9];                                                              // the map bits of the nine pixels that count
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 9; ++j) {
+        const int qx = x + j % 3 - 1, qy = y + j / 3 - 1;
+        nb[j] = 0u;
+        if (onp == 0u || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+        nb[j] = j == 4 ? onp : (isBackground(t.normal(qx, qy)) ? 0u : t.bits(qx, qy));
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        T8[l] = 0u;
+        if (!((onp >> l) & 1u)) continue;
+        T8[l] = 65535u;
+        if (f.samples[l] < 2u) continue;
+        const uint32_t full = f.samples[l] * f.scale[l];                         // n_l * S_l
+        uint64_t G = 0;
+        uint32_t D = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < 9; ++j) {
+            if (!((nb[j] >> l) & 1u)) continue;
+            const int qx = x + j % 3 - 1, qy = y + j / 3 - 1;
+            const uint32_t w = (j % 3 == 1 ? 2u : 1u) * (j / 3 == 1 ? 2u : 1u);
+            const uint64_t i = h.m.at(qx, qy, l);
+            uint64_t E;
+            if ((uint32_t)h.m.lengths[i] >= minHistory) {
+                const uint64_t mean = h.m.mean[i], square = h.m.square[i];
+                E = square > mean * mean ? (uint64_t)f.samples[l] * (square - mean * mean) : 0u;   // n_l * max(0, square - mean^2)
+            } else {
+                const uint32_t v = wideFilterInput(h.counts[i], f.samples[l], f.scale[l]);         // V_0 of THIS frame's count
+                E = (uint64_t)(v * (full - v));                                  // E = c (n - c) S^2 < 2^30
+            }
+            G += (uint64_t)w * E;
+            D += w;
+        }
+        T8[l] = wideGuideThreshold(G, D, f.samples[l], k4);
+    }
+}
+
 // The facing mark (include/rts_scene.h, rtsh_facing_active): 0 where the shadow mask's byte cannot reach the image -- the
 // background (combinePixel leaves the pixel 0) and N.L <= 0 (direct = 1.25 * 0 * mask: either zero) --, 1 everywhere else.
 // `!(ndl > 0)` would cull a NaN; `ndl <= 0` is false for one, so a NaN is traced.

@@ -1109,3 +1109,105 @@ extern "C" int rtsh_wide_filter_guided_temporal_soft_light_list(const rts_soft_l
     }
     return RTS_OK;
 }
+
+// ---- the wide filters fed from the accumulated mean (include/rts_scene.h; per-pixel rule in rts_closest_hit.h: wideMeanInput,
+// wideFilterPassPixel, wideGuideTemporalMeanThresholdPixel, wideGuidedPassPixel) ----
+namespace rts_harness {
+namespace {
+// The frame as the passes read it on the host: WideFrameTexels with V_0' = min(mean, n S) as the first pass's input.
+struct WideMeanFrameTexels {
+    const float *positions, *normals;
+    const uint8_t* map;
+    const uint16_t* mean;                        // the first pass's input, else NULL
+    const uint16_t* values;                      // the previous pass's planes
+    const uint32_t *samples, *scale;
+    size_t W, n;
+    size_t at(int x, int y) const { return (size_t)y * W + (size_t)x; }
+    V3 normal(int x, int y) const { const float* v = normals + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
+    V3 position(int x, int y) const { const float* v = positions + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
+    uint32_t bits(int x, int y) const { return map ? map[at(x, y)] : 0xFFu; }
+    uint32_t value(int x, int y, uint32_t l) const {
+        if (!mean) return values[(size_t)l * n + at(x, y)];
+        return wideMeanInput(mean[(size_t)l * n + at(x, y)], samples[l], scale[l]);
+    }
+};
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_wide_filter_mean_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_filter_params* params,
+                                                     const float* positions, const float* normals, const uint8_t* lights_map,
+                                                     const uint16_t* mean, uint32_t W, uint32_t H, float* visibility, int threads) {
+    if (!positions || !normals || !mean || !visibility) return RTS_ERR_INVALID_ARG;
+    WideFilterList f;
+    const int s = makeWideFilterSoftList(list, params, W, H, &f);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H, set = (size_t)f.count * n;
+    std::vector<uint16_t> scratch;
+    try {
+        if (f.passes >= 2u) scratch.resize(2 * set);
+    } catch (const std::bad_alloc&) {
+        return RTS_ERR_CAPACITY;
+    }
+    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
+    for (uint32_t k = 0; k < launches; ++k) {
+        const bool first = k == 0u, last = k + 1u == launches;
+        const int step = f.passes == 0u ? 0 : 1 << k;
+        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * set;
+        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * set;
+        const WideMeanFrameTexels t{ positions, normals, lights_map, first ? mean : nullptr, in, f.samples, f.scale, W, n };
+        parallelFor(n, 256, threads, [&](size_t i) {
+            uint32_t v[8];
+            wideFilterPassPixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H, step, v);
+            for (uint32_t l = 0; l < f.count; ++l) {
+                if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
+                else out[(size_t)l * n + i] = (uint16_t)v[l];
+            }
+        });
+    }
+    return RTS_OK;
+}
+
+extern "C" int rtsh_wide_filter_guided_temporal_mean_soft_light_list(const rts_soft_light_list* list,
+                                                                     const rtsh_wide_guide_temporal_params* params, const float* positions,
+                                                                     const float* normals, const uint8_t* lights_map, const uint8_t* counts,
+                                                                     const uint16_t* mean, const uint32_t* square, const uint8_t* lengths,
+                                                                     uint32_t W, uint32_t H, float* visibility, int threads) {
+    if (!positions || !normals || !counts || !mean || !square || !lengths || !visibility) return RTS_ERR_INVALID_ARG;
+    WideFilterList f;
+    const int s = makeWideGuidedTemporalList(list, params, W, H, &f);
+    if (s != RTS_OK) return s;
+    const uint32_t k4 = params->guide_k4, minHistory = params->min_history;
+    const size_t n = (size_t)W * H, set = (size_t)f.count * n;
+    const GuideMomentsCounts h{ GuideMoments{ mean, square, lengths, W, n }, counts };
+    std::vector<uint16_t> scratch;                                       // two ping-pong sets, then the planes of T: the device form's
+    try {
+        if (f.passes >= 2u) scratch.resize(3 * set);
+    } catch (const std::bad_alloc&) {
+        return RTS_ERR_CAPACITY;
+    }
+    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
+    for (uint32_t k = 0; k < launches; ++k) {
+        const bool first = k == 0u, last = k + 1u == launches;
+        const int step = f.passes == 0u ? 0 : 1 << k;
+        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * set;
+        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * set;
+        uint16_t* guide = f.passes >= 2u ? scratch.data() + 2 * set : nullptr;
+        const WideMeanFrameTexels t{ positions, normals, lights_map, first ? mean : nullptr, in, f.samples, f.scale, W, n };
+        parallelFor(n, 256, threads, [&](size_t i) {
+            const int x = (int)(i % W), y = (int)(i / W);
+            uint32_t T[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, v[8];
+            if (first) {
+                if (step > 0) wideGuideTemporalMeanThresholdPixel(f, k4, minHistory, t, h, x, y, (int)W, (int)H, T);
+                if (!last) for (uint32_t l = 0; l < f.count; ++l) guide[(size_t)l * n + i] = (uint16_t)T[l];
+            } else {
+                for (uint32_t l = 0; l < f.count; ++l) T[l] = guide[(size_t)l * n + i];
+            }
+            wideGuidedPassPixel(f, t, x, y, (int)W, (int)H, step, T, v);
+            for (uint32_t l = 0; l < f.count; ++l) {
+                if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
+                else out[(size_t)l * n + i] = (uint16_t)v[l];
+            }
+        });
+    }
+    return RTS_OK;
+}

@@ -31,7 +31,14 @@ The temporal guide of the wide filter (rtsh_accumulate_moments_soft_light_list, 
 DESIGN.md 4.27): the still-camera scenes and lights of the first table; the count moments are accumulated per frame (max_length 32),
 and after 4, 8 and 12 frames THAT frame's jittered counts are filtered, two passes, by the unguided wide filter, by 4.26's guide and
 by the temporal guide (min_history 4) at guide_k4 8, 12 and 16; "raw" is count / 4 of that frame.  Every row twice: the shared table
-rotated by one entry per frame, and by the sample count per frame (4)."""
+rotated by one entry per frame, and by the sample count per frame (4).
+
+    python tools/list_temporal_quality.py --mean-input [--out profiles/r32/list_mean_filter_quality.jsonl]
+
+The wide filters fed from the accumulated mean (rtsh_wide_filter_mean_soft_light_list,
+rtsh_wide_filter_guided_temporal_mean_soft_light_list): the protocol of --guide-history unchanged, and three more
+columns per row: "mean_raw" the unfiltered mean plane (passes 0), "mean_unguided" the unguided filter over it, "mean_temporal" the
+guided one at guide_k4 8, 12 and 16."""
 import argparse
 import json
 import os
@@ -101,7 +108,7 @@ def jump_rows():
 GUIDE_FRAMES, GUIDE_K4, GUIDE_PASSES, GUIDE_MIN_HISTORY = (4, 8, 12), (8, 12, 16), 2, 4
 
 
-def guide_rows():
+def guide_rows(mean_input=False):
     from raytracedshadows_amd import api, scenes
     rows = []
     for name, sc, W, H in (("cornell_128", scenes.cornell(), 128, 128), ("terrain_96", scenes.terrain(23), 96, 96)):
@@ -139,6 +146,14 @@ def guide_rows():
                             lst, api.WideGuideParams.make(GUIDE_PASSES, k4, 0.9, eps), pos, nrm, counts, facing)[0])
                         row["temporal"][str(k4)] = mad(api.wide_filter_guided_temporal_soft_light_list(
                             lst, api.WideGuideTemporalParams.make(GUIDE_PASSES, k4, GUIDE_MIN_HISTORY, 0.9, eps), pos, nrm, counts, moments, facing)[0])
+                    if mean_input:
+                        row["mean_raw"] = mad(api.wide_filter_mean_soft_light_list(lst, api.WideFilterParams.make(0, 0.9, eps), pos, nrm,
+                                                                                   moments[0], facing)[0])
+                        row["mean_unguided"] = mad(api.wide_filter_mean_soft_light_list(lst, api.WideFilterParams.make(GUIDE_PASSES, 0.9, eps),
+                                                                                        pos, nrm, moments[0], facing)[0])
+                        row["mean_temporal"] = {str(k4): mad(api.wide_filter_guided_temporal_mean_soft_light_list(
+                            lst, api.WideGuideTemporalParams.make(GUIDE_PASSES, k4, GUIDE_MIN_HISTORY, 0.9, eps), pos, nrm, counts, moments,
+                            facing)[0]) for k4 in GUIDE_K4}
                     rows.append(row)
                     print(json.dumps(row))
     return rows
@@ -149,10 +164,11 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--jump", action="store_true", help="the light-jump scenario of the neighbourhood clamp instead of the still-camera table")
     ap.add_argument("--guide-history", action="store_true", help="the temporal guide of the wide filter against the unguided filter and 4.26's guide")
+    ap.add_argument("--mean-input", action="store_true", help="--guide-history's table with the mean-input filters' three columns beside it")
     args = ap.parse_args()
     from raytracedshadows_amd import api, scenes
-    rows = jump_rows() if args.jump else (guide_rows() if args.guide_history else [])
-    if args.jump or args.guide_history:
+    rows = jump_rows() if args.jump else (guide_rows(args.mean_input) if args.guide_history or args.mean_input else [])
+    if args.jump or args.guide_history or args.mean_input:
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:

@@ -171,7 +171,8 @@ def filter_words(api, filt):
     return f"radius {filt.radius}"
 
 
-def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, max_length, probe=0, table=0, colors="", clamp=None):
+def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, max_length, probe=0, table=0, colors="", clamp=None,
+                       filter_mean=False):
     """`frames` frames of a light list: per frame G-buffer, facing map, trace (the offsets table rotated by one entry per frame), filter
     and accumulation with ping-pong history; the last frame is lit from the accumulated visibility."""
     from raytracedshadows_amd import api, scenes
@@ -187,7 +188,8 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
     d_map, d_counts, d_vis, d_rgb = ctx.malloc(n), ctx.malloc(count * n), ctx.malloc(count * n * 4), ctx.malloc(n * 3)
     wide = isinstance(filt, (api.WideFilterParams, api.WideGuideParams, api.WideGuideTemporalParams))
     temporal_guide = isinstance(filt, api.WideGuideTemporalParams)
-    moments = [(ctx.malloc(count * n * 2), ctx.malloc(count * n * 4), ctx.malloc(count * n)) for _ in range(2)] if temporal_guide else None
+    with_moments = temporal_guide or filter_mean                         # (--filter-mean without a guide accumulates the moments itself)
+    moments = [(ctx.malloc(count * n * 2), ctx.malloc(count * n * 4), ctx.malloc(count * n)) for _ in range(2)] if with_moments else None
     d_scratch = ctx.malloc(wide_scratch_bytes(api, filt, count, W, H)) if wide and filt.passes >= 2 else None
     eyes = [orbit(sc.eye, sc.target, orbit_deg * (k - (frames - 1))) for k in range(frames)]      # the last frame is the scene's own camera
     t0 = time.time()
@@ -205,10 +207,18 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
             ctx.trace_soft_light_list_device(constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
         tp = api.TemporalParams.from_cameras((eyes[k], sc.target, sc.fovy), (eyes[max(k - 1, 0)], sc.target, sc.fovy), W, H,
                                              filt.normal_cos_min, filt.plane_eps, max_length)
-        if temporal_guide:                                               # this frame's count moments, then the filter they guide
+        if with_moments:                                                 # this frame's count moments, then the filter they guide or feed
             api.accumulate_moments_soft_light_list_device(ctx, lights, tp, d_pos, d_nrm, d_counts, W, H, *moments[k % 2],
                                                           d_prev=None if k == 0 else gbuf[(k - 1) % 2] + moments[(k - 1) % 2], d_lights_map=d_map)
-        list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, None, d_scratch, moments[k % 2] if temporal_guide else None)
+        if filter_mean and temporal_guide:
+            api.wide_filter_guided_temporal_mean_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, moments[k % 2], W, H, d_vis,
+                                                                        d_scratch=d_scratch, d_lights_map=d_map)
+        elif filter_mean:
+            api.wide_filter_mean_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, moments[k % 2][0], W, H, d_vis, d_scratch=d_scratch,
+                                                        d_lights_map=d_map)
+        else:
+            list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, None, d_scratch,
+                        moments[k % 2] if temporal_guide else None)
         d_prev = None if k == 0 else gbuf[(k - 1) % 2] + hist[(k - 1) % 2]
         api.accumulate_visibility_list_device(ctx, hard, tp, d_pos, d_nrm, d_vis, W, H, hist[k % 2][0], hist[k % 2][1], d_prev=d_prev,
                                               d_lights_map=d_map, clamp=clamp)
@@ -216,7 +226,7 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
     api.combine_visibility_list_device(ctx, constants, hard, gbuf[last][0], gbuf[last][1], hist[last][0], W, H, d_rgb, d_lights_map=d_map,
                                        colors=colors)
     ctx.synchronize()
-    print(f"{frames} frames of {count} lights x {spp} samples, filter {filter_words(api, filt)}, orbit {orbit_deg:g} degree per frame, "
+    print(f"{frames} frames of {count} lights x {spp} samples, filter {filter_words(api, filt)}{' over the accumulated mean' if filter_mean else ''}, orbit {orbit_deg:g} degree per frame, "
           f"max_length {max_length}{'' if clamp is None else f', history clamped at r = {clamp.radius}, margin {clamp.margin:g}'}: "
           f"{(time.time() - t0) * 1e3:.2f} ms (incl. first launches)")
     rgb, lengths, marks = np.zeros((H, W, 3), np.uint8), np.zeros((count, H, W), np.uint8), np.zeros((H, W), np.uint8)
@@ -264,6 +274,10 @@ def main():
                     help="with --filter-guide K4 and --temporal F: accumulate the count moments per frame "
                          "(rtsh_accumulate_moments_soft_light_list_device) and take the guide's variance from them where a pixel has at "
                          "least M frames of history (rtsh_wide_filter_guided_temporal_soft_light_list_device), 1 <= M <= 255")
+    ap.add_argument("--filter-mean", action="store_true",
+                    help="with --filter-passes K and --temporal F: run the passes over the accumulated mean of the count moments in place "
+                         "of this frame's counts (rtsh_wide_filter_mean_soft_light_list_device); with --filter-guide K4 --guide-history M "
+                         "the guided form (rtsh_wide_filter_guided_temporal_mean_soft_light_list_device)")
     ap.add_argument("--temporal", type=int, default=0, metavar="F",
                     help="with --soft-list N --filter R: render F frames, accumulate the visibility over them (ping-pong history, the "
                          "offsets table rotated by one entry per frame) and light the last one from it")
@@ -305,6 +319,9 @@ def main():
                 if args.filter_guide < 0 or not args.temporal or not 1 <= args.guide_history <= 255:
                     sys.exit("render: --guide-history M goes with --filter-guide K4 and --temporal F, 1 <= M <= 255")
                 filt = api.WideGuideTemporalParams.make(args.filter_passes, args.filter_guide, args.guide_history, args.normal_cos, args.plane_eps)
+            if args.filter_mean and (args.filter_passes < 0 or not args.temporal or (args.filter_guide >= 0) != bool(args.guide_history)):
+                sys.exit("render: --filter-mean goes with --filter-passes K and --temporal F, alone or with both --filter-guide K4 and "
+                         "--guide-history M")
             if args.temporal:
                 if filt is None or args.distance or args.refined:
                     sys.exit("render: --temporal F goes with --soft-list N and --filter R or --filter-passes K, without --distance and --refined")
@@ -312,7 +329,7 @@ def main():
                     sys.exit("render: --clamp R takes 0 <= R <= 4 and a finite --clamp-margin M >= 0")
                 clamp = api.HistoryClamp.make(args.clamp, args.clamp_margin) if args.clamp >= 0 else None
                 return soft_list_temporal(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, filt, args.temporal, args.orbit,
-                                          args.max_length, args.adaptive, args.table, args.colors, clamp)
+                                          args.max_length, args.adaptive, args.table, args.colors, clamp, args.filter_mean)
             return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance,
                              args.colors, filt)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
