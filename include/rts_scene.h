@@ -327,7 +327,7 @@ int rtsh_combine_visibility_list_device(rts_ctx* ctx, const rts_constants* const
  *   * host form: multi-threaded (threads: 0 = all host threads).  Device form: DEVICE buffers, asynchronous on `stream`, allocates
  *     nothing and reads nothing back; under graph capture ONE kernel node, list and params by value (params is read during the call).
  *     No BVH, no alignment of any buffer beyond its element type's.
- *   * OUT OF SCOPE: moving geometry (no motion vectors: the plane test takes it for a disocclusion and resets), variance clamping of
+ *   * OUT OF SCOPE: (moving geometry is followed by the motion forms at the end of this header, DESIGN.md 4.29;) variance clamping of
  *     the history (a mean +- k sigma box needs a square root; the min/max box is rtsh_accumulate_visibility_list_clamped below),
  *     accumulating distance planes (the count planes' moments: rtsh_accumulate_moments_soft_light_list below), row ranges and
  *     stripes, a frame term in the jitter hash. */
@@ -558,7 +558,7 @@ int rtsh_wide_filter_guided_soft_light_list_device(rts_ctx* ctx, const rts_soft_
  *   * planes of any buffer from `count` up are never touched.  No buffer needs alignment beyond its element type's.
  *   * host form: multi-threaded.  Device form: DEVICE buffers, asynchronous on `stream`, allocates nothing, reads nothing back; under
  *     graph capture ONE kernel node, list and params by value.  No BVH.
- *   * OUT OF SCOPE: moving geometry, a clamp of the moments' history, hard lists (their variance is 0), row ranges and stripes. */
+ *   * OUT OF SCOPE: (moving geometry: the motion form at the end of this header;) a clamp of the moments' history, hard lists (their variance is 0), row ranges and stripes. */
 int rtsh_accumulate_moments_soft_light_list(const rts_soft_light_list* list, const rtsh_temporal_params* params, const float* positions,
                                             const float* normals, const uint8_t* lights_map, const uint8_t* counts,
                                             const float* prev_positions, const float* prev_normals, const uint16_t* prev_mean,
@@ -592,7 +592,7 @@ int rtsh_accumulate_moments_soft_light_list_device(rts_ctx* ctx, const rts_soft_
  *     counted pixels only, each on its element type's alignment.
  *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the guided filter refuses; a NULL mean, square or lengths;
  *     min_history 0 or above 255.
- *   * OUT OF SCOPE: variance propagated through the passes, motion vectors, a guide for the tent filter, row ranges and stripes, hard
+ *   * OUT OF SCOPE: variance propagated through the passes, a guide for the tent filter, row ranges and stripes, hard
  *     lists.  (Filtering the accumulated mean plane in place of this frame's counts: rtsh_wide_filter_mean_soft_light_list and
  *     rtsh_wide_filter_guided_temporal_mean_soft_light_list below.) */
 typedef struct rtsh_wide_guide_temporal_params {
@@ -711,6 +711,107 @@ int rtsh_follow_order(const uint32_t* life_ticks, uint32_t blocks_x, uint32_t bl
 int rtsh_follow_plan_device(rts_ctx* ctx, const uint32_t* life_ticks, const uint32_t* start_ticks /* nullable: 0 */,
                             uint32_t blocks_x, uint32_t blocks_y, uint32_t xcd_square, uint32_t life_block,
                             uint32_t* order_out /* record i -> bx | by << 16, as rts_ctx_read_follow */);
+
+/* MOTION VECTORS: TEMPORAL ACCUMULATION THAT FOLLOWS REFITTED GEOMETRY.  The temporal passes above reproject through
+ * the CAMERA's motion alone; a pixel on geometry that a refit moved fails their plane test and restarts every frame, and a face that
+ * slides in its own plane blends the history of another surface point.  A refit keeps every node index (include/rts.h), and the
+ * closest hit knows its leaf, so the surface point a pixel sees can be looked up in the PREVIOUS frame's stream at the same leaf index:
+ * two streams of one topology are all that is needed.
+ *
+ * THE MOTION G-BUFFER PASS: rtsh_primary_gbuffer* plus prev_packed (the previous frame's stream: prev_count_vec4 == count_vec4, a refit
+ * sibling of `packed`) and prev_eye.  positions, normals (nullable) and hit_count are rtsh_primary_gbuffer*'s, bit for bit.  New planes:
+ *   prev_points         W*H*4 floats: the seen surface point where it was last frame, relative to the PREVIOUS eye; .w = 1 STATIC,
+ *                       2 MOVED, 0 background.
+ *   prev_point_normals  W*H*4 floats: that surface's normal last frame, .w = 0.
+ *   leaves              W*H uint32_t, nullable: the hit leaf's node index, 0xFFFFFFFF for background.
+ * Per pixel, with d and hit = the closest hit as in rtsh_primary_gbuffer*:
+ *   BACKGROUND: all four floats of both new texels are +0, leaves = 0xFFFFFFFF.
+ *   HIT of leaf L: e0, e1, v0 = its nine words in the current stream -- words 0..2 and 4..6 of node L and words 0..2 of the tail at
+ *     index a[3] --, e0', e1', v0' = the words at the SAME indices of prev_packed.  The tail index is always the CURRENT stream's, so a
+ *     prev_packed of the right size is never read out of bounds, whatever it holds.
+ *   STATIC (the nine words are bit-identical): prev_point.xyz = position.xyz + eye_delta, eye_delta[k] = eye[k] - prev_eye[k] formed
+ *     once on the host; prev_point.w = 1; prev_point_normal = normal, bit for bit.  This is REPROJECT's Q above.
+ *   MOVED (any word differs): with o = eye, s1 = cross(d, e1), det = dot(s1, e0), invd = 1 / det, dd = o - v0, b1 = dot(dd, s1) * invd,
+ *     s2 = cross(dd, e0), b2 = dot(d, s2) * invd (the closest hit's own expressions), per component
+ *       prev_point = (v0' + (e0' * b1 + e1' * b2)) - prev_eye,   every operation rounded once, in this grouping, no contraction;
+ *     prev_point.w = 2.  n' = cross(e0', e1'), s' = dot(n', n') > 0 ? 1 / sqrtf(dot(n', n')) : 0, negated exactly where the current
+ *     normal was (dot(cross(e0, e1), d) > 0: the same side of the triangle, not a new decision); prev_point_normal = n' * s', .w = 0.
+ *     A triangle that was degenerate last frame gives a zero normal: "no history" to the passes below.
+ *   * RTS_ERR_INVALID_ARG, nothing written, nothing launched: everything rtsh_primary_gbuffer* refuses; a NULL prev_packed, prev_eye,
+ *     prev_points or prev_point_normals; a prev_eye that is not finite; prev_count_vec4 != count_vec4 (device form: != the installed
+ *     stream's).  Host form: a prev_packed whose tag and link words differ from packed's is RTS_ERR_BAD_BVH.  Device form: equal
+ *     topology is the caller's contract; the index rule keeps a violation memory-safe.
+ *   * device form: the same 8 x 8 tile grid and RTSH_GBUFFER_MAX_HEIGHT; ONE kernel node under capture; allocates nothing, reads
+ *     nothing back; every buffer on its element type's alignment. */
+int rtsh_primary_gbuffer_motion(const rts_vec4u* packed, size_t count_vec4, const rts_vec4u* prev_packed, size_t prev_count_vec4,
+                                const float eye[3], const float prev_eye[3], const float target[3], float fovy, uint32_t W, uint32_t H,
+                                float* positions, float* normals, float* prev_points, float* prev_point_normals, uint32_t* leaves,
+                                uint64_t* hit_count, int threads);
+int rtsh_primary_gbuffer_motion_device(rts_ctx* ctx, const rts_vec4u* d_prev_packed, size_t prev_count_vec4, const float eye[3],
+                                       const float prev_eye[3], const float target[3], float fovy, uint32_t W, uint32_t H,
+                                       float* d_positions, float* d_normals, float* d_prev_points, float* d_prev_point_normals,
+                                       uint32_t* d_leaves, void* stream);
+
+/* The installed stream, copied into a caller's DEVICE buffer of capacity_vec4 vec4: one asynchronous device-to-device copy on `stream`
+ * (ONE memcpy node under capture), so that a frame loop is snapshot -> rts_ctx_refit_bvh_device -> motion G-buffer with no host round
+ * trip.  RTS_ERR_NO_BVH before rts_ctx_set_bvh; RTS_ERR_INVALID_ARG for a
+ * NULL ctx or buffer or too small a capacity, with nothing copied. */
+int rtsh_ctx_snapshot_bvh_device(rts_ctx* ctx, rts_vec4u* d_out, size_t capacity_vec4, void* stream);
+/* The installed stream's size in vec4, 0 before rts_ctx_set_bvh. */
+size_t rtsh_ctx_bvh_count(rts_ctx* ctx);
+
+/* THE MOTION FORMS OF THE THREE TEMPORAL PASSES: each is its parent's signature plus prev_points and prev_point_normals, THIS frame's
+ * planes from the motion G-buffer pass.  Everything of the parent rule holds word for word except:
+ *   REPROJECT: Q = prev_points[p].xyz in place of P_p + eye_delta.  params->eye_delta is not used but must still be finite.
+ *   TAP ACCEPTANCE: M_p = prev_point_normals[p].xyz stands in place of N_p in both geometric tests -- dot3(M_p, N'_q) >= normal_cos_min
+ *     and fabsf(dot3(M_p, P'_q - Q)) <= plane_eps: the surface is compared with what the previous frame saw, in the previous frame's
+ *     orientation, so a rotating object keeps its history.  Where M_p is all zero at an active pixel no tap is accepted and the pixel
+ *     restarts.  INACTIVE is still decided by the CURRENT normal and map.  A NaN anywhere in Q or M_p rejects, as every comparison does.
+ * ANCHOR: over the planes of a motion G-buffer pass with prev_packed == packed (every hit STATIC) and eye_delta = eye - prev_eye, each
+ * motion form gives its parent's bits.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: the parents' refusals; prev_points or prev_point_normals NULL while the
+ *     prev_* history is given (on the first frame both may be NULL and are not read).
+ *   * device forms: the parents' shape, ONE kernel node under capture; the two texels are read once, by their own pixel. */
+int rtsh_accumulate_visibility_list_motion(const rts_light_list* list, const rtsh_temporal_params* params, const float* positions,
+                                           const float* normals, const uint8_t* lights_map, const float* visibility,
+                                           const float* prev_positions, const float* prev_normals, const float* prev_visibility,
+                                           const uint8_t* prev_lengths, const float* prev_points, const float* prev_point_normals,
+                                           uint32_t W, uint32_t H, float* visibility_out, uint8_t* lengths_out, int threads);
+int rtsh_accumulate_visibility_list_motion_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_temporal_params* params,
+                                                  const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                  const float* d_visibility, const float* d_prev_positions, const float* d_prev_normals,
+                                                  const float* d_prev_visibility, const uint8_t* d_prev_lengths,
+                                                  const float* d_prev_points, const float* d_prev_point_normals, uint32_t W, uint32_t H,
+                                                  float* d_visibility_out, uint8_t* d_lengths_out, void* stream);
+int rtsh_accumulate_visibility_list_clamped_motion(const rts_light_list* list, const rtsh_temporal_params* params, const float* positions,
+                                                   const float* normals, const uint8_t* lights_map, const float* visibility,
+                                                   const float* prev_positions, const float* prev_normals, const float* prev_visibility,
+                                                   const uint8_t* prev_lengths, const float* prev_points,
+                                                   const float* prev_point_normals, uint32_t W, uint32_t H, float* visibility_out,
+                                                   uint8_t* lengths_out, const rtsh_history_clamp* clamp, int threads);
+int rtsh_accumulate_visibility_list_clamped_motion_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_temporal_params* params,
+                                                          const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                          const float* d_visibility, const float* d_prev_positions,
+                                                          const float* d_prev_normals, const float* d_prev_visibility,
+                                                          const uint8_t* d_prev_lengths, const float* d_prev_points,
+                                                          const float* d_prev_point_normals, uint32_t W, uint32_t H,
+                                                          float* d_visibility_out, uint8_t* d_lengths_out,
+                                                          const rtsh_history_clamp* clamp, void* stream);
+int rtsh_accumulate_moments_soft_light_list_motion(const rts_soft_light_list* list, const rtsh_temporal_params* params,
+                                                   const float* positions, const float* normals, const uint8_t* lights_map,
+                                                   const uint8_t* counts, const float* prev_positions, const float* prev_normals,
+                                                   const uint16_t* prev_mean, const uint32_t* prev_square, const uint8_t* prev_lengths,
+                                                   const float* prev_points, const float* prev_point_normals, uint32_t W, uint32_t H,
+                                                   uint16_t* mean_out, uint32_t* square_out, uint8_t* lengths_out, int threads);
+int rtsh_accumulate_moments_soft_light_list_motion_device(rts_ctx* ctx, const rts_soft_light_list* list,
+                                                          const rtsh_temporal_params* params, const float* d_positions,
+                                                          const float* d_normals, const uint8_t* d_lights_map, const uint8_t* d_counts,
+                                                          const float* d_prev_positions, const float* d_prev_normals,
+                                                          const uint16_t* d_prev_mean, const uint32_t* d_prev_square,
+                                                          const uint8_t* d_prev_lengths, const float* d_prev_points,
+                                                          const float* d_prev_point_normals, uint32_t W, uint32_t H,
+                                                          uint16_t* d_mean_out, uint32_t* d_square_out, uint8_t* d_lengths_out,
+                                                          void* stream);
 
 #ifdef __cplusplus
 }

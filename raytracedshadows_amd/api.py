@@ -564,6 +564,30 @@ _sig("rtsh_accumulate_moments_soft_light_list", C.c_int, C.POINTER(SoftLightList
 _sig("rtsh_accumulate_moments_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(TemporalParams), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_primary_gbuffer_motion", C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, _f32p, _f32p, _f32p, C.c_float, C.c_uint32,
+     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.c_int)
+_sig("rtsh_primary_gbuffer_motion_device", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, _f32p, _f32p, _f32p, C.c_float, C.c_uint32,
+     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_ctx_snapshot_bvh_device", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_sig("rtsh_ctx_bvh_count", C.c_size_t, C.c_void_p)
+_sig("rtsh_accumulate_visibility_list_motion", C.c_int, C.POINTER(LightList), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+     C.c_int)
+_sig("rtsh_accumulate_visibility_list_motion_device", C.c_int, C.c_void_p, C.POINTER(LightList), C.POINTER(TemporalParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+     C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_accumulate_visibility_list_clamped_motion", C.c_int, C.POINTER(LightList), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+     C.c_void_p, C.POINTER(HistoryClamp), C.c_int)
+_sig("rtsh_accumulate_visibility_list_clamped_motion_device", C.c_int, C.c_void_p, C.POINTER(LightList), C.POINTER(TemporalParams),
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+     C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(HistoryClamp), C.c_void_p)
+_sig("rtsh_accumulate_moments_soft_light_list_motion", C.c_int, C.POINTER(SoftLightList), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rtsh_accumulate_moments_soft_light_list_motion_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(TemporalParams),
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_wide_filter_guided_temporal_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(WideGuideTemporalParams), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
 _sig("rtsh_wide_filter_guided_temporal_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList),
@@ -1333,6 +1357,49 @@ def primary_gbuffer_device(ctx, eye, target, fovy, width, height, d_positions, d
            "rtsh_primary_gbuffer_device")
 
 
+def _f3(v):
+    return (C.c_float * 3)(*[float(x) for x in v]) if v is not None else None
+
+
+def primary_gbuffer_motion(packed, prev_packed, eye, prev_eye, target, fovy, width, height, threads=0, want_leaves=True):
+    """The motion G-buffer pass on the host (rtsh_primary_gbuffer_motion): ``(positions, normals, prev_points, prev_point_normals,
+    leaves or None, hits)``.  ``prev_packed``: the previous frame's stream, a refit sibling of ``packed``; ``prev_points[..., 3]`` is 1
+    where the hit triangle did not move, 2 where it did, 0 on the background."""
+    packed = np.ascontiguousarray(packed, dtype=np.uint32).reshape(-1, 4) if packed is not None else None
+    prev_packed = np.ascontiguousarray(prev_packed, dtype=np.uint32).reshape(-1, 4) if prev_packed is not None else None
+    pos, nrm, pts, pnr = (np.zeros((height, width, 4), dtype=np.float32) for _ in range(4))
+    leaves = np.zeros((height, width), np.uint32) if want_leaves else None
+    hits = C.c_uint64(0)
+    _check(_lib.rtsh_primary_gbuffer_motion(_ptr_or_none(packed), packed.shape[0] if packed is not None else 0, _ptr_or_none(prev_packed),
+                                            prev_packed.shape[0] if prev_packed is not None else 0, _f3(eye), _f3(prev_eye), _f3(target), fovy,
+                                            width, height, _ptr(pos), _ptr(nrm), _ptr(pts), _ptr(pnr), _ptr_or_none(leaves), C.byref(hits),
+                                            threads), "rtsh_primary_gbuffer_motion")
+    return pos, nrm, pts, pnr, leaves, int(hits.value)
+
+
+def primary_gbuffer_motion_device(ctx, d_prev_packed, prev_count, eye, prev_eye, target, fovy, width, height, d_positions, d_normals,
+                                  d_prev_points, d_prev_point_normals, d_leaves=None, stream=None):
+    """The motion G-buffer pass on the GPU, through the stream installed in ``ctx`` and the previous stream at ``d_prev_packed``
+    (``prev_count`` vec4, e.g. from :func:`snapshot_bvh_device`).  Device pointers, one kernel, asynchronous."""
+    _check(_lib.rtsh_primary_gbuffer_motion_device(ctx.handle, C.c_void_p(d_prev_packed or 0), prev_count, _f3(eye), _f3(prev_eye), _f3(target),
+                                                   fovy, width, height, C.c_void_p(d_positions or 0), C.c_void_p(d_normals or 0),
+                                                   C.c_void_p(d_prev_points or 0), C.c_void_p(d_prev_point_normals or 0),
+                                                   C.c_void_p(d_leaves or 0), C.c_void_p(stream or 0)), "rtsh_primary_gbuffer_motion_device")
+
+
+def bvh_count_device(ctx):
+    """The size in vec4 of the stream installed in ``ctx`` (0 before ``set_bvh``)."""
+    return int(_lib.rtsh_ctx_bvh_count(ctx.handle))
+
+
+def snapshot_bvh_device(ctx, d_out, capacity_vec4, stream=None):
+    """rtsh_ctx_snapshot_bvh_device: the installed stream copied into the device buffer ``d_out`` (one asynchronous device-to-device
+    copy).  Returns the stream's size in vec4."""
+    _check(_lib.rtsh_ctx_snapshot_bvh_device(ctx.handle, C.c_void_p(d_out or 0), capacity_vec4, C.c_void_p(stream or 0)),
+           "rtsh_ctx_snapshot_bvh_device")
+    return bvh_count_device(ctx)
+
+
 def combine(constants, light, positions, normals, mask):
     """Combine.frag on the host: uint8[H, W, 3]."""
     H, W = mask.shape
@@ -1796,12 +1863,15 @@ def camera_basis(eye, target, fovy, width, height):
             "aspect": out[13]}
 
 
-def accumulate_visibility_list(light_list, params, positions, normals, visibility, prev=None, lights_map=None, threads=0, clamp=None):
+def accumulate_visibility_list(light_list, params, positions, normals, visibility, prev=None, lights_map=None, threads=0, clamp=None,
+                               motion=None):
     """The temporal accumulation of a light list's visibility on the host (rtsh_accumulate_visibility_list): ``(float32[count, H, W]
     visibility, uint8[count, H, W] lengths)``.  ``visibility``: this frame's ``float32[>= count, H, W]`` (a filter's output);
     ``prev``: None on the first frame, else ``(prev_positions, prev_normals, prev_visibility, prev_lengths)`` of the previous frame
     (its G-buffer and what this call returned for it); ``params`` a ``TemporalParams``.  ``clamp``: None, or a ``HistoryClamp`` for
-    the clamped form (rtsh_accumulate_visibility_list_clamped)."""
+    the clamped form (rtsh_accumulate_visibility_list_clamped).  ``motion``: None, or ``(prev_points, prev_point_normals)`` -- this frame's
+    planes from :func:`primary_gbuffer_motion`, either of which may be None -- for the motion forms (rtsh_accumulate_visibility_list_motion,
+    ..._clamped_motion)."""
     normals = np.ascontiguousarray(normals, np.float32)
     H, W = normals.shape[:2]
     count = light_list.count if light_list is not None and 1 <= light_list.count <= 8 else 1
@@ -1818,6 +1888,13 @@ def accumulate_visibility_list(light_list, params, positions, normals, visibilit
         raise RtsError(1, "rtsh_accumulate_visibility_list: a buffer does not fit the frame of the normals")
     out, lengths = np.zeros((count, H, W), np.float32), np.zeros((count, H, W), np.uint8)
     pp = [_ptr(a) for a in prev] if prev is not None else [None] * 4
+    if motion is not None:
+        name = "rtsh_accumulate_visibility_list_clamped_motion" if clamp is not None else "rtsh_accumulate_visibility_list_motion"
+        mp = _motion_planes(motion, H, W, name)
+        args = (_ref(light_list), _ref(params), _ptr_or_none(positions), _ptr(normals), _ptr_or_none(lights_map), _ptr(visibility), pp[0], pp[1],
+                pp[2], pp[3], _ptr_or_none(mp[0]), _ptr_or_none(mp[1]), W, H, _ptr(out), _ptr(lengths))
+        _check(getattr(_lib, name)(*args, *((_ref(clamp),) if clamp is not None else ()), threads), name)
+        return out, lengths
     if clamp is not None:
         _check(_lib.rtsh_accumulate_visibility_list_clamped(_ref(light_list), _ref(params), _ptr_or_none(positions), _ptr(normals),
                                                             _ptr_or_none(lights_map), _ptr(visibility), pp[0], pp[1], pp[2], pp[3], W, H,
@@ -1830,13 +1907,33 @@ def accumulate_visibility_list(light_list, params, positions, normals, visibilit
     return out, lengths
 
 
+def _motion_planes(motion, H, W, name):
+    planes = tuple(np.ascontiguousarray(a, np.float32) if a is not None else None for a in motion)
+    if len(planes) != 2 or any(a is not None and a.size != H * W * 4 for a in planes):
+        raise RtsError(1, name + ": motion is (prev_points, prev_point_normals), W*H*4 floats each")
+    return planes
+
+
 def accumulate_visibility_list_device(ctx, light_list, params, d_positions, d_normals, d_visibility, width, height, d_visibility_out,
-                                      d_lengths_out, d_prev=None, d_lights_map=None, stream=None, clamp=None):
+                                      d_lengths_out, d_prev=None, d_lights_map=None, stream=None, clamp=None, d_motion=None):
     """The temporal accumulation on the GPU: device pointers; ``d_prev``: None on the first frame, else the device pointers
     ``(prev_positions, prev_normals, prev_visibility, prev_lengths)``.  d_visibility_out = count planes of width*height floats,
     d_lengths_out = count planes of width*height bytes; neither may be the history it reads.  One kernel, asynchronous.  ``clamp``: None,
-    or a ``HistoryClamp`` for the clamped form (then d_visibility_out may not be d_visibility either)."""
+    or a ``HistoryClamp`` for the clamped form (then d_visibility_out may not be d_visibility either).  ``d_motion``: None, or the device
+    pointers ``(prev_points, prev_point_normals)`` of this frame's motion G-buffer pass for the motion forms."""
     pp = tuple(d_prev) if d_prev is not None else (0, 0, 0, 0)
+    if d_motion is not None:
+        args = (ctx.handle, _ref(light_list), _ref(params), C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
+                C.c_void_p(d_visibility), C.c_void_p(pp[0] or 0), C.c_void_p(pp[1] or 0), C.c_void_p(pp[2] or 0), C.c_void_p(pp[3] or 0),
+                C.c_void_p(d_motion[0] or 0), C.c_void_p(d_motion[1] or 0), width, height, C.c_void_p(d_visibility_out),
+                C.c_void_p(d_lengths_out))
+        if clamp is not None:
+            _check(_lib.rtsh_accumulate_visibility_list_clamped_motion_device(*args, _ref(clamp), C.c_void_p(stream or 0)),
+                   "rtsh_accumulate_visibility_list_clamped_motion_device")
+        else:
+            _check(_lib.rtsh_accumulate_visibility_list_motion_device(*args, C.c_void_p(stream or 0)),
+                   "rtsh_accumulate_visibility_list_motion_device")
+        return
     if clamp is not None:
         _check(_lib.rtsh_accumulate_visibility_list_clamped_device(ctx.handle, _ref(light_list), _ref(params), C.c_void_p(d_positions or 0),
                                                                    C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
@@ -1854,12 +1951,13 @@ def accumulate_visibility_list_device(ctx, light_list, params, d_positions, d_no
            "rtsh_accumulate_visibility_list_device")
 
 
-def accumulate_moments_soft_light_list(lights, params, positions, normals, counts, prev=None, lights_map=None, threads=0):
+def accumulate_moments_soft_light_list(lights, params, positions, normals, counts, prev=None, lights_map=None, threads=0, motion=None):
     """The temporal accumulation of a soft light list's count moments on the host (rtsh_accumulate_moments_soft_light_list):
     ``(uint16[count, H, W] mean, uint32[count, H, W] square, uint8[count, H, W] lengths)``.  ``counts``: this frame's
     ``uint8[>= count, H, W]``; ``prev``: None on the first frame, else ``(prev_positions, prev_normals, prev_mean, prev_square,
-    prev_lengths)`` of the previous frame (its G-buffer and what this call returned for it); ``params`` a ``TemporalParams``."""
-    name = "rtsh_accumulate_moments_soft_light_list"
+    prev_lengths)`` of the previous frame (its G-buffer and what this call returned for it); ``params`` a ``TemporalParams``.  ``motion``:
+    None, or ``(prev_points, prev_point_normals)`` of this frame's motion G-buffer pass for the motion form."""
+    name = "rtsh_accumulate_moments_soft_light_list" + ("_motion" if motion is not None else "")
     normals = np.ascontiguousarray(normals, np.float32)
     H, W = normals.shape[:2]
     count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
@@ -1876,6 +1974,13 @@ def accumulate_moments_soft_light_list(lights, params, positions, normals, count
         raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
     mean, square, lengths = np.zeros((count, H, W), np.uint16), np.zeros((count, H, W), np.uint32), np.zeros((count, H, W), np.uint8)
     pp = [_ptr(a) for a in prev] if prev is not None else [None] * 5
+    if motion is not None:
+        mp = _motion_planes(motion, H, W, name)
+        _check(_lib.rtsh_accumulate_moments_soft_light_list_motion(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
+                                                                   _ptr_or_none(lights_map), _ptr(counts), pp[0], pp[1], pp[2], pp[3], pp[4],
+                                                                   _ptr_or_none(mp[0]), _ptr_or_none(mp[1]), W, H, _ptr(mean), _ptr(square),
+                                                                   _ptr(lengths), threads), name)
+        return mean, square, lengths
     _check(_lib.rtsh_accumulate_moments_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
                                                         _ptr_or_none(lights_map), _ptr(counts), pp[0], pp[1], pp[2], pp[3], pp[4], W, H,
                                                         _ptr(mean), _ptr(square), _ptr(lengths), threads), name)
@@ -1883,11 +1988,20 @@ def accumulate_moments_soft_light_list(lights, params, positions, normals, count
 
 
 def accumulate_moments_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_counts, width, height, d_mean_out,
-                                              d_square_out, d_lengths_out, d_prev=None, d_lights_map=None, stream=None):
+                                              d_square_out, d_lengths_out, d_prev=None, d_lights_map=None, stream=None, d_motion=None):
     """The moments pass on the GPU: device pointers; ``d_prev``: None on the first frame, else the device pointers ``(prev_positions,
     prev_normals, prev_mean, prev_square, prev_lengths)``.  d_mean_out = count planes of width*height uint16, d_square_out of uint32,
-    d_lengths_out of bytes; none may be the history it reads.  One kernel, asynchronous."""
+    d_lengths_out of bytes; none may be the history it reads.  One kernel, asynchronous.  ``d_motion``: None, or the device pointers
+    ``(prev_points, prev_point_normals)`` of this frame's motion G-buffer pass for the motion form."""
     pp = tuple(d_prev) if d_prev is not None else (0, 0, 0, 0, 0)
+    if d_motion is not None:
+        _check(_lib.rtsh_accumulate_moments_soft_light_list_motion_device(
+            ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
+            C.c_void_p(d_counts), C.c_void_p(pp[0] or 0), C.c_void_p(pp[1] or 0), C.c_void_p(pp[2] or 0), C.c_void_p(pp[3] or 0),
+            C.c_void_p(pp[4] or 0), C.c_void_p(d_motion[0] or 0), C.c_void_p(d_motion[1] or 0), width, height, C.c_void_p(d_mean_out),
+            C.c_void_p(d_square_out), C.c_void_p(d_lengths_out), C.c_void_p(stream or 0)),
+            "rtsh_accumulate_moments_soft_light_list_motion_device")
+        return
     _check(_lib.rtsh_accumulate_moments_soft_light_list_device(ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions or 0),
                                                                C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0), C.c_void_p(d_counts),
                                                                C.c_void_p(pp[0] or 0), C.c_void_p(pp[1] or 0), C.c_void_p(pp[2] or 0),

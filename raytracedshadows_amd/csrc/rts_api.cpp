@@ -1576,6 +1576,19 @@ const void* rts_ctx_device_bvh(rts_ctx* c) {
     return c->d_bvh;
 }
 
+// the installed stream's size in vec4, 0 before rts_ctx_set_bvh (include/rts_scene.h)
+size_t rtsh_ctx_bvh_count(rts_ctx* c) { return (c && c->d_bvh) ? c->bvhVec4 : 0; }
+
+// The installed stream into a caller's device buffer (include/rts_scene.h): one asynchronous device-to-device copy.
+int rtsh_ctx_snapshot_bvh_device(rts_ctx* c, rts_vec4u* d_out, size_t capacity_vec4, void* stream) {
+    if (!c || !d_out) return RTS_ERR_INVALID_ARG;
+    if (!c->d_bvh) return RTS_ERR_NO_BVH;
+    if (capacity_vec4 < c->bvhVec4) return RTS_ERR_INVALID_ARG;
+    RTS_HIP(hipSetDevice(c->device));
+    RTS_HIP(hipMemcpyAsync(d_out, c->d_bvh, c->bvhVec4 * 16, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return RTS_OK;
+}
+
 // Dispatch order for the next traces whose block count equals `count` (NULL/0 = natural order).  Every tile index
 // must appear exactly once (checked).  Speed only: results never depend on it.
 int rts_ctx_set_tile_order(rts_ctx* c, const uint32_t* order, size_t count) {

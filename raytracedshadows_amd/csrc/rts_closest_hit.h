@@ -110,6 +110,74 @@ RTS_HD void shadePixel(const uint32_t* bvh, const Camera& c, uint32_t x, uint32_
     writeTexel(bvh, d, closestHit(bvh, c.eye, d), position4, normal4);
 }
 
+// The MOTION G-buffer texels (include/rts_scene.h, rtsh_primary_gbuffer_motion): beside writeTexel's two, where the seen surface point
+// was in the previous frame -- relative to the previous eye -- and that surface's normal then.  `prev` is the previous frame's stream, a
+// refit sibling of `bvh`: the same node indices.  The nine words of the hit leaf (e0, e1 and the tail's v0) are read at the SAME word
+// indices of both streams, the tail index from the CURRENT stream alone, so a `prev` of the right size is never read out of bounds.
+//   STATIC (the nine words are bit-identical): position + eyeDelta, .w = 1, and the current normal's bits -- 4.23's Q.
+//   MOVED: b1, b2 by leafTest's own expressions on the current leaf, then (v0' + (e0' * b1 + e1' * b2)) - prevEye per component, .w = 2;
+//          the normal of (e0', e1') turned to the side writeTexel chose for the CURRENT normal.
+// position4 / normal4: what writeTexel wrote for this pixel (the normal always, whether or not the caller keeps it).
+RTS_HD void writeMotionTexel(const uint32_t* bvh, const uint32_t* prev, V3 o, V3 prevEye, V3 eyeDelta, V3 d, Hit h, const float* position4,
+                             const float* normal4, float* prevPoint4, float* prevNormal4) {
+    if (h.leaf == 0xFFFFFFFFu) {
+        prevPoint4[0] = prevPoint4[1] = prevPoint4[2] = prevPoint4[3] = 0.0f;
+        prevNormal4[0] = prevNormal4[1] = prevNormal4[2] = prevNormal4[3] = 0.0f;
+        return;
+    }
+    const size_t leafWord = (size_t)h.leaf * 8;
+    const size_t tailWord = (size_t)bvh[leafWord + 3] * 4;                   // (the CURRENT stream's index)
+    uint32_t cw[9], pw[9];
+    bool moved = false;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 9; ++k) {
+        const size_t i = k < 3 ? leafWord + (size_t)k : (k < 6 ? leafWord + 4 + (size_t)(k - 3) : tailWord + (size_t)(k - 6));
+        cw[k] = bvh[i];
+        pw[k] = prev[i];
+        moved |= cw[k] != pw[k];
+    }
+    if (!moved) {
+        prevPoint4[0] = position4[0] + eyeDelta.x; prevPoint4[1] = position4[1] + eyeDelta.y; prevPoint4[2] = position4[2] + eyeDelta.z;
+        prevPoint4[3] = 1.0f;
+        prevNormal4[0] = normal4[0]; prevNormal4[1] = normal4[1]; prevNormal4[2] = normal4[2]; prevNormal4[3] = normal4[3];
+        return;
+    }
+    const V3 e0{ asFloat(cw[0]), asFloat(cw[1]), asFloat(cw[2]) }, e1{ asFloat(cw[3]), asFloat(cw[4]), asFloat(cw[5]) };
+    const V3 v0{ asFloat(cw[6]), asFloat(cw[7]), asFloat(cw[8]) };
+    const V3 pe0{ asFloat(pw[0]), asFloat(pw[1]), asFloat(pw[2]) }, pe1{ asFloat(pw[3]), asFloat(pw[4]), asFloat(pw[5]) };
+    const V3 pv0{ asFloat(pw[6]), asFloat(pw[7]), asFloat(pw[8]) };
+    const V3 s1 = cross(d, e1);                                              // leafTest's expressions, in its order
+    const float det = dot(s1, e0);
+    const float invd = 1.0f / det;
+    const V3 dd = sub(o, v0);
+    const float b1 = dot(dd, s1) * invd;
+    const V3 s2 = cross(dd, e0);
+    const float b2 = dot(d, s2) * invd;
+    prevPoint4[0] = (pv0.x + (pe0.x * b1 + pe1.x * b2)) - prevEye.x;
+    prevPoint4[1] = (pv0.y + (pe0.y * b1 + pe1.y * b2)) - prevEye.y;
+    prevPoint4[2] = (pv0.z + (pe0.z * b1 + pe1.z * b2)) - prevEye.z;
+    prevPoint4[3] = 2.0f;
+    const V3 n = cross(e0, e1), pn = cross(pe0, pe1);
+    const float len2 = dot(pn, pn);
+    float s = len2 > 0.0f ? 1.0f / __builtin_sqrtf(len2) : 0.0f;
+    if (dot(n, d) > 0.0f) s = -s;                                            // writeTexel's side of the CURRENT triangle
+    prevNormal4[0] = pn.x * s; prevNormal4[1] = pn.y * s; prevNormal4[2] = pn.z * s; prevNormal4[3] = 0.0f;
+}
+
+RTS_HD void shadeMotionPixel(const uint32_t* bvh, const uint32_t* prev, const Camera& c, V3 prevEye, V3 eyeDelta, uint32_t x, uint32_t y,
+                             uint32_t W, uint32_t H, float* position4, float* normal4, float* prevPoint4, float* prevNormal4,
+                             uint32_t* leaf) {
+    const V3 d = primaryDirection(c, x, y, W, H);
+    const Hit h = closestHit(bvh, c.eye, d);
+    float n4[4];
+    writeTexel(bvh, d, h, position4, n4);
+    if (normal4) { normal4[0] = n4[0]; normal4[1] = n4[1]; normal4[2] = n4[2]; normal4[3] = n4[3]; }
+    writeMotionTexel(bvh, prev, c.eye, prevEye, eyeDelta, d, h, position4, n4, prevPoint4, prevNormal4);
+    if (leaf) *leaf = h.leaf;
+}
+
 // Combine.frag:18-37 with baseColor = 1 (the default white material, RayTracedShadows.cpp:1013-1018), one pixel:
 //   direct  = 1.25 * max(0, N.L) * shadowMask            shadowMask = mask / samples
 //   ambient = 0.15 + 0.05 * (1 - max(0, N.(-cameraDirection)))
@@ -487,6 +555,9 @@ RTS_HD void wideGuidedPassPixel(const WideFilterList& f, const Texels& t, int x,
 //   bool box(l, x, y, uint32_t* loKey, uint32_t* hiKey): the smallest and largest clampKey over the contributing taps of the pixel's
 //   window for light l; false when no tap contributes.  The host twin loops over the window, the kernel reduces it in LDS: a minimum
 //   and a maximum of integers, so no order of taps can change a bit.
+// MOTION (rtsh_accumulate_visibility_list_motion and its clamped form; accumulateMomentsPixel alike): Q and the normal the taps are
+// tested with come from this frame's motion G-buffer planes, compiled in by the switch alone -- the non-motion instantiations are the
+// text they were.  `Frames` then also gives V3 prevPoint(x, y) (Q) and V3 prevPointNormal(x, y) (M_p; all zero: no tap is accepted).
 struct TemporalList {
     uint32_t count, maxLength, resetLights, history;      // history: 0 on the first frame (no prev_* buffers)
     V3 eyeDelta, right, up, fwd;
@@ -503,7 +574,7 @@ RTS_HD uint32_t clampKey(uint32_t u) { return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x8
 RTS_HD uint32_t clampUnkey(uint32_t k) { return k ^ ((k >> 31) ? 0x80000000u : 0xFFFFFFFFu); }
 RTS_HD bool bitsAreNaN(uint32_t u) { return (u & 0x7FFFFFFFu) > 0x7F800000u; }
 
-template <bool Clamped = false, class Frames>
+template <bool Clamped = false, bool Motion = false, class Frames>
 RTS_HD void accumulatePixel(const TemporalList& f, const Frames& t, int x, int y, int W, int H, float margin = 0.0f) {
     const V3 np = t.normal(x, y);
     const uint32_t all = (1u << f.count) - 1u;
@@ -511,13 +582,15 @@ RTS_HD void accumulatePixel(const TemporalList& f, const Frames& t, int x, int y
     int qx[4] = { 0, 0, 0, 0 }, qy[4] = { 0, 0, 0, 0 };
     uint32_t w[4] = { 0, 0, 0, 0 }, taps = 0;                                                      // taps: bit k = tap k passes the geometry
     if (onp != 0u && f.history != 0u && (all & ~f.resetLights) != 0u) {
-        const V3 q = add(t.position(x, y), f.eyeDelta);
+        V3 q, mp;                                                                                  // Q, and the normal the taps are tested with
+        if constexpr (Motion) { q = t.prevPoint(x, y); mp = t.prevPointNormal(x, y); }
+        else { q = add(t.position(x, y), f.eyeDelta); mp = np; }
         const float z = dotGrouped(q, f.fwd);
         const float a = dotGrouped(q, f.right) / z, b = dotGrouped(q, f.up) / z;
         const float fx = (a / f.scaleX + 1.0f) * (0.5f * (float)W) - 0.5f;
         const float fy = (1.0f - b / f.scaleY) * (0.5f * (float)H) - 0.5f;
         const float gx = fx * 32.0f + 0.5f, gy = fy * 32.0f + 0.5f;
-        if (z > 0.0f && gx >= -32.0f && gx < (float)W * 32.0f && gy >= -32.0f && gy < (float)H * 32.0f) {
+        if (z > 0.0f && gx >= -32.0f && gx < (float)W * 32.0f && gy >= -32.0f && gy < (float)H * 32.0f && !(Motion && isBackground(mp))) {
             const int32_t ix = (int32_t)__builtin_floorf(gx), iy = (int32_t)__builtin_floorf(gy);
             const int x0 = ix >> 5, y0 = iy >> 5;
             const uint32_t ax = (uint32_t)(ix & 31), ay = (uint32_t)(iy & 31);
@@ -530,8 +603,8 @@ RTS_HD void accumulatePixel(const TemporalList& f, const Frames& t, int x, int y
                 if (w[k] == 0u || qx[k] < 0 || qx[k] >= W || qy[k] < 0 || qy[k] >= H) continue;
                 const V3 nq = t.prevNormal(qx[k], qy[k]);
                 if (isBackground(nq)) continue;
-                if (!(dotGrouped(np, nq) >= f.normalCosMin)) continue;
-                const float h = dotGrouped(np, sub(t.prevPosition(qx[k], qy[k]), q));
+                if (!(dotGrouped(mp, nq) >= f.normalCosMin)) continue;
+                const float h = dotGrouped(mp, sub(t.prevPosition(qx[k], qy[k]), q));
                 if (!(__builtin_fabsf(h) <= f.planeEps)) continue;
                 taps |= 1u << k;
             }
@@ -599,7 +672,7 @@ RTS_HD uint64_t momentsQuotient(uint64_t a, uint32_t b) {
     return q;
 }
 
-template <class Frames>
+template <bool Motion = false, class Frames>
 RTS_HD void accumulateMomentsPixel(const MomentsList& g, const Frames& t, int x, int y, int W, int H) {
     const TemporalList& f = g.t;
     const V3 np = t.normal(x, y);
@@ -608,13 +681,15 @@ RTS_HD void accumulateMomentsPixel(const MomentsList& g, const Frames& t, int x,
     int qx[4] = { 0, 0, 0, 0 }, qy[4] = { 0, 0, 0, 0 };
     uint32_t w[4] = { 0, 0, 0, 0 }, taps = 0;                                                      // taps: bit k = tap k passes the geometry
     if (onp != 0u && f.history != 0u && (all & ~f.resetLights) != 0u) {
-        const V3 q = add(t.position(x, y), f.eyeDelta);
+        V3 q, mp;                                                                                  // Q, and the normal the taps are tested with
+        if constexpr (Motion) { q = t.prevPoint(x, y); mp = t.prevPointNormal(x, y); }
+        else { q = add(t.position(x, y), f.eyeDelta); mp = np; }
         const float z = dotGrouped(q, f.fwd);
         const float a = dotGrouped(q, f.right) / z, b = dotGrouped(q, f.up) / z;
         const float fx = (a / f.scaleX + 1.0f) * (0.5f * (float)W) - 0.5f;
         const float fy = (1.0f - b / f.scaleY) * (0.5f * (float)H) - 0.5f;
         const float gx = fx * 32.0f + 0.5f, gy = fy * 32.0f + 0.5f;
-        if (z > 0.0f && gx >= -32.0f && gx < (float)W * 32.0f && gy >= -32.0f && gy < (float)H * 32.0f) {
+        if (z > 0.0f && gx >= -32.0f && gx < (float)W * 32.0f && gy >= -32.0f && gy < (float)H * 32.0f && !(Motion && isBackground(mp))) {
             const int32_t ix = (int32_t)__builtin_floorf(gx), iy = (int32_t)__builtin_floorf(gy);
             const int x0 = ix >> 5, y0 = iy >> 5;
             const uint32_t ax = (uint32_t)(ix & 31), ay = (uint32_t)(iy & 31);
@@ -627,8 +702,8 @@ RTS_HD void accumulateMomentsPixel(const MomentsList& g, const Frames& t, int x,
                 if (w[k] == 0u || qx[k] < 0 || qx[k] >= W || qy[k] < 0 || qy[k] >= H) continue;
                 const V3 nq = t.prevNormal(qx[k], qy[k]);
                 if (isBackground(nq)) continue;
-                if (!(dotGrouped(np, nq) >= f.normalCosMin)) continue;
-                const float h = dotGrouped(np, sub(t.prevPosition(qx[k], qy[k]), q));
+                if (!(dotGrouped(mp, nq) >= f.normalCosMin)) continue;
+                const float h = dotGrouped(mp, sub(t.prevPosition(qx[k], qy[k]), q));
                 if (!(__builtin_fabsf(h) <= f.planeEps)) continue;
                 taps |= 1u << k;
             }

@@ -49,6 +49,22 @@ __global__ __launch_bounds__(256) void accumulateMomentsKernel(MomentsList f, Mo
     accumulateMomentsPixel(f, t, x, y, W, H);
 }
 
+// MOTION FORM (rtsh_accumulate_moments_soft_light_list_motion_device; DESIGN.md 4.29): a SIBLING of the kernel above in its shape;
+// accumulateMomentsPixel<true> takes Q and M_p from this frame's two motion texels, each read once by its own pixel: non-temporal.
+struct MotionMomentsDeviceFrames : MomentsDeviceFrames {
+    const float *prevPoints, *prevPointNormals;
+    __device__ V3 prevPoint(int x, int y) const { return TemporalDeviceFrames::streamed(prevPoints, at(x, y)); }
+    __device__ V3 prevPointNormal(int x, int y) const { return TemporalDeviceFrames::streamed(prevPointNormals, at(x, y)); }
+};
+
+__global__ __launch_bounds__(256) void accumulateMomentsMotionKernel(MomentsList f, MomentsDeviceFrames t, const float* prevPoints,
+                                                                     const float* prevPointNormals, int W, int H) {
+    const int x = (int)blockIdx.x * 16 + (int)threadIdx.x, y = (int)blockIdx.y * 16 + (int)threadIdx.y;
+    if (x >= W || y >= H) return;
+    const MotionMomentsDeviceFrames m{ t, prevPoints, prevPointNormals };
+    accumulateMomentsPixel<true>(f, m, x, y, W, H);
+}
+
 // THE FIRST PASS OF THE TEMPORAL GUIDE: wideGuidedKernel<true, LAST, DENSE> with wideGuideTemporalThresholdPixel in the place of
 // wideGuideThresholdPixel -- a sibling, so that every instantiation of wideGuidedKernel keeps its text; later passes ARE
 // wideGuidedKernel<false, ...>, which read T from the third set of the scratch.  The staging loop is wideFilterKernel's, statement for
@@ -159,6 +175,27 @@ extern "C" int rtsh_accumulate_moments_soft_light_list_device(rts_ctx* ctx, cons
                                               d_prev_mean, d_prev_square, d_mean_out, d_square_out, d_lengths_out, W, (uint64_t)W * H };
     return rts_harness::launchPass(ctx, stream, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0, rts_harness::accumulateMomentsKernel, f,
                                    t, (int)W, (int)H);
+}
+
+extern "C" int rtsh_accumulate_moments_soft_light_list_motion_device(rts_ctx* ctx, const rts_soft_light_list* list,
+                                                                     const rtsh_temporal_params* params, const float* d_positions,
+                                                                     const float* d_normals, const uint8_t* d_lights_map,
+                                                                     const uint8_t* d_counts, const float* d_prev_positions,
+                                                                     const float* d_prev_normals, const uint16_t* d_prev_mean,
+                                                                     const uint32_t* d_prev_square, const uint8_t* d_prev_lengths,
+                                                                     const float* d_prev_points, const float* d_prev_point_normals,
+                                                                     uint32_t W, uint32_t H, uint16_t* d_mean_out, uint32_t* d_square_out,
+                                                                     uint8_t* d_lengths_out, void* stream) {
+    if (!ctx) return RTS_ERR_INVALID_ARG;
+    rts_harness::MomentsList f;
+    int s = rts_harness::makeMomentsList(list, params, d_positions, d_normals, d_counts, d_prev_positions, d_prev_normals, d_prev_mean,
+                                         d_prev_square, d_prev_lengths, W, H, d_mean_out, d_square_out, d_lengths_out, &f);
+    if (s == RTS_OK) s = rts_harness::checkMotionPlanes(f.t.history, d_prev_points, d_prev_point_normals);
+    if (s != RTS_OK) return s;
+    const rts_harness::MomentsDeviceFrames t{ d_positions, d_normals, d_prev_positions, d_prev_normals, d_lights_map, d_counts, d_prev_lengths,
+                                              d_prev_mean, d_prev_square, d_mean_out, d_square_out, d_lengths_out, W, (uint64_t)W * H };
+    return rts_harness::launchPass(ctx, stream, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0,
+                                   rts_harness::accumulateMomentsMotionKernel, f, t, d_prev_points, d_prev_point_normals, (int)W, (int)H);
 }
 
 // The chain of a call: rtsh_wide_filter_guided_soft_light_list_device's, with the sibling kernel as its first pass.

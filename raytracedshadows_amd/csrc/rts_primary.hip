@@ -199,3 +199,4 @@ extern "C" int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_const
 #include "rts_wide_guided.inc" // the variance-guided wide filter of a soft light list's planes
 #include "rts_moments.inc" // the temporal accumulation of a soft light list's count moments and the filter they guide
 #include "rts_wide_mean.inc" // the wide filters fed from the accumulated mean of the count moments
+#include "rts_motion.inc" // the motion G-buffer pass: where the seen surface was in the previous frame's stream

@@ -87,6 +87,52 @@ extern "C" int rtsh_primary_positions(const rts_vec4u* packed, size_t count, con
     return rtsh_primary_gbuffer(packed, count, eye, target, fovy, W, H, positions, nullptr, hit_count, threads);
 }
 
+// ---- the motion G-buffer pass (include/rts_scene.h; per-pixel rule in rts_closest_hit.h: shadeMotionPixel) ----
+namespace rts_harness {
+// Shared by the host and device forms: the refusals that need neither stream, and eye - prev_eye, formed once.
+int makeMotionEyes(const float eye[3], const float prev_eye[3], const float target[3], const void* positions, const void* prevPoints,
+                   const void* prevPointNormals, uint32_t W, uint32_t H, V3* prevEye, V3* eyeDelta) {
+    if (!eye || !prev_eye || !target || !positions || !prevPoints || !prevPointNormals || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    for (int i = 0; i < 3; ++i)
+        if (!std::isfinite(prev_eye[i])) return RTS_ERR_INVALID_ARG;
+    *prevEye = V3{ prev_eye[0], prev_eye[1], prev_eye[2] };
+    *eyeDelta = V3{ eye[0] - prev_eye[0], eye[1] - prev_eye[1], eye[2] - prev_eye[2] };
+    return RTS_OK;
+}
+} // namespace rts_harness
+
+extern "C" int rtsh_primary_gbuffer_motion(const rts_vec4u* packed, size_t count, const rts_vec4u* prev_packed, size_t prev_count,
+                                           const float eye[3], const float prev_eye[3], const float target[3], float fovy, uint32_t W,
+                                           uint32_t H, float* positions, float* normals, float* prev_points, float* prev_point_normals,
+                                           uint32_t* leaves, uint64_t* hit_count, int threads) {
+    V3 prevEye, eyeDelta;
+    if (!packed || !prev_packed) return RTS_ERR_INVALID_ARG;
+    int s = makeMotionEyes(eye, prev_eye, target, positions, prev_points, prev_point_normals, W, H, &prevEye, &eyeDelta);
+    if (s != RTS_OK) return s;
+    uint32_t P = 0;
+    s = rts_bvh_validate(packed, count, &P);
+    if (s != RTS_OK) return s;
+    if (prev_count != count) return RTS_ERR_INVALID_ARG;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t* prev = (const uint32_t*)prev_packed;
+    for (size_t node = 0; node + 1 < (size_t)2 * P; ++node)                // the 2P - 1 nodes: the tag and the link word of each
+        if (bvh[node * 8 + 3] != prev[node * 8 + 3] || bvh[node * 8 + 7] != prev[node * 8 + 7]) return RTS_ERR_BAD_BVH;
+    const Camera cam = makeCamera(eye, target, fovy, W, H);
+    std::atomic<uint64_t> hits{ 0 };
+    parallelFor(H, 1, threads, [&](size_t y) {
+        uint64_t local = 0;
+        for (uint32_t x = 0; x < W; ++x) {
+            const size_t p = y * W + x, i = p * 4;
+            shadeMotionPixel(bvh, prev, cam, prevEye, eyeDelta, x, (uint32_t)y, W, H, positions + i, normals ? normals + i : nullptr,
+                             prev_points + i, prev_point_normals + i, leaves ? leaves + p : nullptr);
+            local += positions[i + 3] != 0.0f;
+        }
+        hits.fetch_add(local);
+    });
+    if (hit_count) *hit_count = hits.load();
+    return RTS_OK;
+}
+
 namespace rts_harness {
 // Shared by the host and device combine passes: validates and condenses the arguments.
 int makeCombineParams(const rts_constants* k, const rts_light* light, bool havePositions, CombineParams* out) {
@@ -938,7 +984,20 @@ struct ClampedTemporalFrames : TemporalFrames {
         return any;
     }
 };
+
+// ... and with this frame's motion planes (the motion forms): Q and M_p of the pixel itself.
+template <class Base>
+struct MotionOf : Base {
+    const float *prevPoints, *prevPointNormals;
+    V3 prevPoint(int x, int y) const { return Base::xyz(prevPoints, Base::at(x, y)); }
+    V3 prevPointNormal(int x, int y) const { return Base::xyz(prevPointNormals, Base::at(x, y)); }
+};
 } // namespace
+
+// The motion forms' own refusal, beside their parents': with a history, both of this frame's motion planes.
+int checkMotionPlanes(uint32_t history, const void* prevPoints, const void* prevPointNormals) {
+    return (history != 0u && (!prevPoints || !prevPointNormals)) ? RTS_ERR_INVALID_ARG : RTS_OK;
+}
 } // namespace rts_harness
 
 extern "C" int rtsh_accumulate_visibility_list(const rts_light_list* list, const rtsh_temporal_params* params, const float* positions,
@@ -973,6 +1032,48 @@ extern "C" int rtsh_accumulate_visibility_list_clamped(const rts_light_list* lis
     const ClampedTemporalFrames t{ { positions, normals, visibility, prev_positions, prev_normals, prev_visibility, lights_map, prev_lengths,
                                      visibility_out, lengths_out, W, n }, (int)W, (int)H, (int)clamp->radius };
     parallelFor(n, 256, threads, [&](size_t i) { accumulatePixel<true>(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H, margin); });
+    return RTS_OK;
+}
+
+// ---- the motion forms of the two passes above (include/rts_scene.h): accumulatePixel<Clamped, true> ----
+extern "C" int rtsh_accumulate_visibility_list_motion(const rts_light_list* list, const rtsh_temporal_params* params, const float* positions,
+                                                      const float* normals, const uint8_t* lights_map, const float* visibility,
+                                                      const float* prev_positions, const float* prev_normals, const float* prev_visibility,
+                                                      const uint8_t* prev_lengths, const float* prev_points,
+                                                      const float* prev_point_normals, uint32_t W, uint32_t H, float* visibility_out,
+                                                      uint8_t* lengths_out, int threads) {
+    TemporalList f;
+    int s = makeTemporalList(list, params, positions, normals, visibility, prev_positions, prev_normals, prev_visibility, prev_lengths, W, H,
+                             visibility_out, lengths_out, &f);
+    if (s == RTS_OK) s = checkMotionPlanes(f.history, prev_points, prev_point_normals);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const MotionOf<TemporalFrames> t{ { positions, normals, visibility, prev_positions, prev_normals, prev_visibility, lights_map, prev_lengths,
+                                        visibility_out, lengths_out, W, n }, prev_points, prev_point_normals };
+    parallelFor(n, 256, threads, [&](size_t i) { accumulatePixel<false, true>(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H); });
+    return RTS_OK;
+}
+
+extern "C" int rtsh_accumulate_visibility_list_clamped_motion(const rts_light_list* list, const rtsh_temporal_params* params,
+                                                              const float* positions, const float* normals, const uint8_t* lights_map,
+                                                              const float* visibility, const float* prev_positions,
+                                                              const float* prev_normals, const float* prev_visibility,
+                                                              const uint8_t* prev_lengths, const float* prev_points,
+                                                              const float* prev_point_normals, uint32_t W, uint32_t H,
+                                                              float* visibility_out, uint8_t* lengths_out, const rtsh_history_clamp* clamp,
+                                                              int threads) {
+    TemporalList f;
+    int s = makeTemporalList(list, params, positions, normals, visibility, prev_positions, prev_normals, prev_visibility, prev_lengths, W, H,
+                             visibility_out, lengths_out, &f);
+    if (s == RTS_OK) s = checkHistoryClamp(clamp, visibility, visibility_out);
+    if (s == RTS_OK) s = checkMotionPlanes(f.history, prev_points, prev_point_normals);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const float margin = clamp->margin;
+    const MotionOf<ClampedTemporalFrames> t{ { { positions, normals, visibility, prev_positions, prev_normals, prev_visibility, lights_map,
+                                                 prev_lengths, visibility_out, lengths_out, W, n }, (int)W, (int)H, (int)clamp->radius },
+                                             prev_points, prev_point_normals };
+    parallelFor(n, 256, threads, [&](size_t i) { accumulatePixel<true, true>(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H, margin); });
     return RTS_OK;
 }
 
@@ -1048,6 +1149,36 @@ extern "C" int rtsh_accumulate_moments_soft_light_list(const rts_soft_light_list
     const MomentsFrames t{ positions, normals, prev_positions, prev_normals, lights_map, counts, prev_lengths, prev_mean, prev_square,
                            mean_out, square_out, lengths_out, W, n };
     parallelFor(n, 256, threads, [&](size_t i) { accumulateMomentsPixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H); });
+    return RTS_OK;
+}
+
+namespace rts_harness {
+namespace {
+struct MotionMomentsFrames : MomentsFrames {
+    const float *prevPoints, *prevPointNormals;
+    V3 prevPoint(int x, int y) const { return xyz(prevPoints, at(x, y)); }
+    V3 prevPointNormal(int x, int y) const { return xyz(prevPointNormals, at(x, y)); }
+};
+} // namespace
+} // namespace rts_harness
+
+// ---- the motion form of the moments pass (include/rts_scene.h): accumulateMomentsPixel<true> ----
+extern "C" int rtsh_accumulate_moments_soft_light_list_motion(const rts_soft_light_list* list, const rtsh_temporal_params* params,
+                                                              const float* positions, const float* normals, const uint8_t* lights_map,
+                                                              const uint8_t* counts, const float* prev_positions, const float* prev_normals,
+                                                              const uint16_t* prev_mean, const uint32_t* prev_square,
+                                                              const uint8_t* prev_lengths, const float* prev_points,
+                                                              const float* prev_point_normals, uint32_t W, uint32_t H, uint16_t* mean_out,
+                                                              uint32_t* square_out, uint8_t* lengths_out, int threads) {
+    MomentsList f;
+    int s = makeMomentsList(list, params, positions, normals, counts, prev_positions, prev_normals, prev_mean, prev_square, prev_lengths, W, H,
+                            mean_out, square_out, lengths_out, &f);
+    if (s == RTS_OK) s = checkMotionPlanes(f.t.history, prev_points, prev_point_normals);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const MotionMomentsFrames t{ { positions, normals, prev_positions, prev_normals, lights_map, counts, prev_lengths, prev_mean, prev_square,
+                                   mean_out, square_out, lengths_out, W, n }, prev_points, prev_point_normals };
+    parallelFor(n, 256, threads, [&](size_t i) { accumulateMomentsPixel<true>(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H); });
     return RTS_OK;
 }
 

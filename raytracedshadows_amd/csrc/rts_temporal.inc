@@ -151,6 +151,99 @@ __global__ __launch_bounds__(256) void accumulateListClampedKernel(TemporalList 
     if (x >= W || y >= H) return;                                                                     // (after the last barrier)
     accumulatePixel<true>(f, c, x, y, W, H, margin);
 }
+
+// MOTION FORMS (rtsh_accumulate_visibility_list_motion_device, ..._clamped_motion_device; DESIGN.md 4.29).  SIBLINGS of the two kernels
+// above in their shape; accumulatePixel<Clamped, true> takes Q and M_p from this frame's two motion texels, each read once by its own
+// pixel: non-temporal, like the pixel's other streams.  The current position is not read at all.  The clamped sibling repeats the
+// parent's staging statement for statement (the barriers' conditions are the same functions of kernel arguments alone).
+template <class Base>
+struct MotionDeviceFrames : Base {
+    const float *prevPoints, *prevPointNormals;
+    __device__ V3 prevPoint(int x, int y) const { return TemporalDeviceFrames::streamed(prevPoints, this->at(x, y)); }
+    __device__ V3 prevPointNormal(int x, int y) const { return TemporalDeviceFrames::streamed(prevPointNormals, this->at(x, y)); }
+};
+
+__global__ __launch_bounds__(256) void accumulateListMotionKernel(TemporalList f, TemporalDeviceFrames t, const float* prevPoints,
+                                                                  const float* prevPointNormals, int W, int H) {
+    const int x = (int)blockIdx.x * 16 + (int)threadIdx.x, y = (int)blockIdx.y * 16 + (int)threadIdx.y;
+    if (x >= W || y >= H) return;
+    const MotionDeviceFrames<TemporalDeviceFrames> m{ t, prevPoints, prevPointNormals };
+    accumulatePixel<false, true>(f, m, x, y, W, H);
+}
+
+__global__ __launch_bounds__(256) void accumulateListClampedMotionKernel(TemporalList f, TemporalDeviceFrames t, const float* prevPoints,
+                                                                         const float* prevPointNormals, int W, int H, int radius,
+                                                                         float margin) {
+    enum { S_MAX = 16 + 2 * RTSH_CLAMP_MAX_RADIUS };
+    __shared__ uint8_t activity[S_MAX * S_MAX];
+    __shared__ uint32_t keys[S_MAX * S_MAX], rowLo[S_MAX * 16], rowHi[S_MAX * 16];
+    const int tx = (int)threadIdx.x, ty = (int)threadIdx.y, lane = ty * 16 + tx;
+    const int x = (int)blockIdx.x * 16 + tx, y = (int)blockIdx.y * 16 + ty;
+    const int S = 16 + 2 * radius, taps = 2 * radius + 1;
+    const int x0 = (int)blockIdx.x * 16 - radius, y0 = (int)blockIdx.y * 16 - radius;
+    MotionDeviceFrames<ClampedDeviceFrames> c{ { t, {}, {} }, prevPoints, prevPointNormals };
+#pragma unroll
+    for (int l = 0; l < 8; ++l) { c.lo[l] = kClampNoKey; c.hi[l] = 0u; }
+    const uint32_t all = (1u << f.count) - 1u;
+    const uint32_t boxed = (f.history != 0u && f.maxLength > 1u) ? (all & ~f.resetLights) : 0u;      // lights that can blend: block-uniform
+    if (boxed != 0u) {
+        int wx[3], wy[3];                                              // the lane's window pixels, lane + 256 k: divided once
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { wx[k] = x0 + (lane + 256 * k) % S; wy[k] = y0 + (lane + 256 * k) / S; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int i = lane + 256 * k;
+            if (i >= S * S) break;
+            uint32_t a = 0u;
+            if (wx[k] >= 0 && wx[k] < W && wy[k] >= 0 && wy[k] < H) {
+                const uint64_t q = t.at(wx[k], wy[k]);
+                if (!isBackground(TemporalDeviceFrames::shared(t.normals, q))) a = (t.map ? (uint32_t)t.map[q] : 0xFFu) & all;
+            }
+            activity[i] = (uint8_t)a;
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t l = 0; l < 8; ++l) {
+            if (l >= f.count) break;
+            if (!((boxed >> l) & 1u)) continue;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int i = lane + 256 * k;
+                if (i >= S * S) break;
+                uint32_t key = kClampNoKey;
+                if ((activity[i] >> l) & 1u) {                           // (set only inside the frame)
+                    const uint32_t u = __float_as_uint(t.visibility[(uint64_t)l * t.n + t.at(wx[k], wy[k])]);
+                    if (!bitsAreNaN(u)) key = clampKey(u);
+                }
+                keys[i] = key;
+            }
+            __syncthreads();                                                                                             // barrier A
+            for (int i = lane; i < S * 16; i += 256) {
+                const uint32_t* row = keys + (i >> 4) * S + (i & 15);
+                uint32_t lo = kClampNoKey, hi = 0u;
+                for (int d = 0; d < taps; ++d) {
+                    const uint32_t k = row[d];
+                    lo = k < lo ? k : lo;
+                    hi = (k != kClampNoKey && k > hi) ? k : hi;
+                }
+                rowLo[i] = lo;
+                rowHi[i] = hi;
+            }
+            __syncthreads();                                                                                             // barrier B
+            uint32_t lo = kClampNoKey, hi = 0u;
+            for (int d = 0; d < taps; ++d) {
+                const uint32_t a = rowLo[(ty + d) * 16 + tx], b = rowHi[(ty + d) * 16 + tx];
+                lo = a < lo ? a : lo;
+                hi = b > hi ? b : hi;
+            }
+            c.lo[l] = lo;
+            c.hi[l] = hi;
+        }
+    }
+    if (x >= W || y >= H) return;                                                                     // (after the last barrier)
+    accumulatePixel<true, true>(f, c, x, y, W, H, margin);
+}
+int checkMotionPlanes(uint32_t history, const void* prevPoints, const void* prevPointNormals);                          // rts_scene.cpp
 } // namespace rts_harness
 
 extern "C" int rtsh_accumulate_visibility_list_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_temporal_params* params,
@@ -188,4 +281,46 @@ extern "C" int rtsh_accumulate_visibility_list_clamped_device(rts_ctx* ctx, cons
                                                d_lights_map, d_prev_lengths, d_visibility_out, d_lengths_out, W, (uint64_t)W * H };
     return rts_harness::launchPass(ctx, stream, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0, rts_harness::accumulateListClampedKernel,
                                    f, t, (int)W, (int)H, (int)clamp->radius, clamp->margin);
+}
+
+extern "C" int rtsh_accumulate_visibility_list_motion_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_temporal_params* params,
+                                                             const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                             const float* d_visibility, const float* d_prev_positions,
+                                                             const float* d_prev_normals, const float* d_prev_visibility,
+                                                             const uint8_t* d_prev_lengths, const float* d_prev_points,
+                                                             const float* d_prev_point_normals, uint32_t W, uint32_t H,
+                                                             float* d_visibility_out, uint8_t* d_lengths_out, void* stream) {
+    if (!ctx) return RTS_ERR_INVALID_ARG;
+    rts_harness::TemporalList f;
+    int s = rts_harness::makeTemporalList(list, params, d_positions, d_normals, d_visibility, d_prev_positions, d_prev_normals,
+                                          d_prev_visibility, d_prev_lengths, W, H, d_visibility_out, d_lengths_out, &f);
+    if (s == RTS_OK) s = rts_harness::checkMotionPlanes(f.history, d_prev_points, d_prev_point_normals);
+    if (s != RTS_OK) return s;
+    const rts_harness::TemporalDeviceFrames t{ d_positions, d_normals, d_visibility, d_prev_positions, d_prev_normals, d_prev_visibility,
+                                               d_lights_map, d_prev_lengths, d_visibility_out, d_lengths_out, W, (uint64_t)W * H };
+    return rts_harness::launchPass(ctx, stream, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0, rts_harness::accumulateListMotionKernel,
+                                   f, t, d_prev_points, d_prev_point_normals, (int)W, (int)H);
+}
+
+extern "C" int rtsh_accumulate_visibility_list_clamped_motion_device(rts_ctx* ctx, const rts_light_list* list,
+                                                                     const rtsh_temporal_params* params, const float* d_positions,
+                                                                     const float* d_normals, const uint8_t* d_lights_map,
+                                                                     const float* d_visibility, const float* d_prev_positions,
+                                                                     const float* d_prev_normals, const float* d_prev_visibility,
+                                                                     const uint8_t* d_prev_lengths, const float* d_prev_points,
+                                                                     const float* d_prev_point_normals, uint32_t W, uint32_t H,
+                                                                     float* d_visibility_out, uint8_t* d_lengths_out,
+                                                                     const rtsh_history_clamp* clamp, void* stream) {
+    if (!ctx) return RTS_ERR_INVALID_ARG;
+    rts_harness::TemporalList f;
+    int s = rts_harness::makeTemporalList(list, params, d_positions, d_normals, d_visibility, d_prev_positions, d_prev_normals,
+                                          d_prev_visibility, d_prev_lengths, W, H, d_visibility_out, d_lengths_out, &f);
+    if (s == RTS_OK) s = rts_harness::checkHistoryClamp(clamp, d_visibility, d_visibility_out);
+    if (s == RTS_OK) s = rts_harness::checkMotionPlanes(f.history, d_prev_points, d_prev_point_normals);
+    if (s != RTS_OK) return s;
+    const rts_harness::TemporalDeviceFrames t{ d_positions, d_normals, d_visibility, d_prev_positions, d_prev_normals, d_prev_visibility,
+                                               d_lights_map, d_prev_lengths, d_visibility_out, d_lengths_out, W, (uint64_t)W * H };
+    return rts_harness::launchPass(ctx, stream, dim3((W + 15) / 16, (H + 15) / 16), dim3(16, 16), 0,
+                                   rts_harness::accumulateListClampedMotionKernel, f, t, d_prev_points, d_prev_point_normals, (int)W, (int)H,
+                                   (int)clamp->radius, clamp->margin);
 }

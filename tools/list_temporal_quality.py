@@ -38,7 +38,16 @@ rotated by one entry per frame, and by the sample count per frame (4).
 The wide filters fed from the accumulated mean (rtsh_wide_filter_mean_soft_light_list,
 rtsh_wide_filter_guided_temporal_mean_soft_light_list): the protocol of --guide-history unchanged, and three more
 columns per row: "mean_raw" the unfiltered mean plane (passes 0), "mean_unguided" the unguided filter over it, "mean_temporal" the
-guided one at guide_k4 8, 12 and 16."""
+guided one at guide_k4 8, 12 and 16.
+
+    python tools/list_temporal_quality.py --move [--out profiles/r33/list_motion_quality.jsonl]
+
+Motion vectors (rtsh_primary_gbuffer_motion, rtsh_accumulate_visibility_list_motion): cornell_128, a still camera in the
+room's open front (MOVE_EYE, MOVE_TARGET), the
+light of 3 % and 10 % of the diagonal; the tall box is translated by MOVE_STEP per frame and the stream refitted (api.bvh_refit of one
+build).  Every frame traces 4 jittered samples; the raw (R = 0) visibility is accumulated (max_length 32) by the plain pass and by the
+motion pass.  After 4, 8 and 12 frames: the mean absolute difference to the 48-sample trace of THAT frame's geometry, and the mean
+history length, over the active pixels of the MOVED object (prev_points.w == 2) and over the rest; "raw" is that frame's count / 4."""
 import argparse
 import json
 import os
@@ -159,16 +168,74 @@ def guide_rows(mean_input=False):
     return rows
 
 
+MOVE_FRAMES, MOVE_STEP = (4, 8, 12), (-0.12, 0.0, 0.04)      # (away from under the light: the box's seen faces stay lit for 12 frames)
+#: a camera in the room's open front (the scene's own stands outside and sees a sliver of the box)
+MOVE_EYE, MOVE_TARGET = (5.0, 5.0, 14.0), (4.0, 3.5, 3.0)
+
+
+def move_rows():
+    from raytracedshadows_amd import api, scenes
+    rows = []
+    sc, W, H = scenes.cornell(), 128, 128
+    faces = np.ascontiguousarray(sc.faces, np.uint32)
+    idx, P = np.ascontiguousarray(faces.reshape(-1)), faces.shape[0]
+    box = np.unique(faces[640:832])                                     # the tall box: its own vertices
+    base = np.ascontiguousarray(sc.verts, np.float64)
+    built = api.BVHBuilder().build(np.ascontiguousarray(base, np.float32), 3, idx, P).m_packedNodes
+    sc.eye, sc.target, sc.fovy = np.array(MOVE_EYE, np.float32), np.array(MOVE_TARGET, np.float32), 0.9
+    k = api.RayTracingConstants.make(sc.eye, sc.light_direction, W, H)
+    diag = float(np.linalg.norm(np.asarray(sc.bbox_max, np.float64) - np.asarray(sc.bbox_min, np.float64)))
+    table = scenes.jitter_offsets(48, 1.0, 19)
+    cam = (sc.eye, sc.target, sc.fovy)
+    eps = 0.005 * diag
+    tp = api.TemporalParams.from_cameras(cam, cam, W, H, 0.9, eps, 32)
+    raw = api.FilterParams.make(0, 0.9, eps)
+    for radius in (0.03, 0.1):
+        light = lambda n, t=table: api.SoftLightList.make([(api.Light.POINT, sc.light_point, n, 0, radius * diag)], t)
+        hard = light(4).hard_list()
+        hist = {"plain": None, "motion": None}
+        prev_stream = prev_g = None
+        for frame in range(max(MOVE_FRAMES)):
+            verts = base.copy()
+            verts[box] += np.asarray(MOVE_STEP) * frame
+            packed = api.bvh_refit(built, np.ascontiguousarray(verts, np.float32), 3, idx, P)
+            pos, nrm, pts, pnr, _, _ = api.primary_gbuffer_motion(packed, packed if prev_stream is None else prev_stream, sc.eye, sc.eye, sc.target,
+                                                                  sc.fovy, W, H, want_leaves=False)
+            facing = api.facing_lights(k, hard, pos, nrm)
+            lst = light(4, np.ascontiguousarray(np.roll(table, -frame, axis=0)))
+            counts = api.soft_light_list_adaptive(packed, k, lst, (2,), pos, W, H, facing, want_refined=False, tables=(48,))[0]
+            vis = api.filter_soft_light_list(lst, raw, pos, nrm, counts, facing)
+            for key in hist:
+                prev = None if hist[key] is None else prev_g + hist[key]
+                hist[key] = api.accumulate_visibility_list(hard, tp, pos, nrm, vis, prev, facing, motion=(pts, pnr) if key == "motion" else None)
+            prev_stream, prev_g = packed, (pos, nrm)
+            if frame + 1 not in MOVE_FRAMES:
+                continue
+            active = (facing & 1) != 0
+            truth = api.soft_light_list(packed, k, light(48), pos, W, H, facing)[0].astype(np.float32) / np.float32(48)
+            regions = {"moved": active & (pts[..., 3] == 2), "rest": active & (pts[..., 3] != 2)}
+            row = {"scene": "cornell_128", "light": radius, "frames": frame + 1, "step": list(MOVE_STEP), "max_length": 32}
+            for name, where in regions.items():
+                mad = lambda v: round(float(np.abs(v[where] - truth[where]).mean()), 5)
+                row[name] = {"pixels": int(where.sum()), "raw": mad(vis[0]), "plain": mad(hist["plain"][0][0]), "motion": mad(hist["motion"][0][0]),
+                             "plain_length": round(float(hist["plain"][1][0][where].mean()), 2),
+                             "motion_length": round(float(hist["motion"][1][0][where].mean()), 2)}
+            rows.append(row)
+            print(json.dumps(row))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
     ap.add_argument("--jump", action="store_true", help="the light-jump scenario of the neighbourhood clamp instead of the still-camera table")
     ap.add_argument("--guide-history", action="store_true", help="the temporal guide of the wide filter against the unguided filter and 4.26's guide")
     ap.add_argument("--mean-input", action="store_true", help="--guide-history's table with the mean-input filters' three columns beside it")
+    ap.add_argument("--move", action="store_true", help="the plain and the motion accumulate over a box translated and refitted every frame")
     args = ap.parse_args()
     from raytracedshadows_amd import api, scenes
-    rows = jump_rows() if args.jump else (guide_rows(args.mean_input) if args.guide_history or args.mean_input else [])
-    if args.jump or args.guide_history or args.mean_input:
+    rows = move_rows() if args.move else jump_rows() if args.jump else (guide_rows(args.mean_input) if args.guide_history or args.mean_input else [])
+    if args.move or args.jump or args.guide_history or args.mean_input:
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:

@@ -3,7 +3,7 @@
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
                            [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]
                                           [--filter R [--spread S] | --filter-passes K [--filter-guide K4 [--guide-history M]]] [--plane-eps E] [--normal-cos C]
-                                                      [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]]]]]
+                                                      [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]] [--move SPEC]]]]
 
 --temporal F (with --soft-list N --filter R): F frames are rendered -- trace, filter, rtsh_accumulate_visibility_list_device with
 ping-pong history -- and the LAST frame is lit from the accumulated visibility.  Frame k traces with the shared offsets table rotated
@@ -171,8 +171,25 @@ def filter_words(api, filt):
     return f"radius {filt.radius}"
 
 
+def parse_move(text, wl):
+    """--move SPEC = AXIS:LO:HI:DX,DY,DZ -- the part of the scene is the slab of vertices whose AXIS coordinate (x, y or z) lies between the
+    fractions LO and HI of the scene's extent; it is displaced by (DX, DY, DZ) world units per frame.  Returns (vertices [nv, 8], the
+    slab's mask, the step)."""
+    try:
+        axis, lo, hi, step = text.split(":")
+        a, lo, hi = "xyz".index(axis), float(lo), float(hi)
+        step = np.array([float(v) for v in step.split(",")], np.float32)
+        assert step.shape == (3,) and np.isfinite(step).all() and 0.0 <= lo < hi <= 1.0
+    except (ValueError, AssertionError):
+        sys.exit("render: --move SPEC is AXIS:LO:HI:DX,DY,DZ, e.g. x:0.33:0.67:0,0.5,0")
+    verts = np.array(wl.vertices, np.float32).reshape(-1, 8)
+    b0, b1 = float(wl.scene.bbox_min[a]), float(wl.scene.bbox_max[a])
+    mask = (verts[:, a] >= b0 + lo * (b1 - b0)) & (verts[:, a] <= b0 + hi * (b1 - b0))
+    return verts, mask, step
+
+
 def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, max_length, probe=0, table=0, colors="", clamp=None,
-                       filter_mean=False):
+                       filter_mean=False, move=""):
     """`frames` frames of a light list: per frame G-buffer, facing map, trace (the offsets table rotated by one entry per frame), filter
     and accumulation with ping-pong history; the last frame is lit from the accumulated visibility."""
     from raytracedshadows_amd import api, scenes
@@ -192,13 +209,30 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
     moments = [(ctx.malloc(count * n * 2), ctx.malloc(count * n * 4), ctx.malloc(count * n)) for _ in range(2)] if with_moments else None
     d_scratch = ctx.malloc(wide_scratch_bytes(api, filt, count, W, H)) if wide and filt.passes >= 2 else None
     eyes = [orbit(sc.eye, sc.target, orbit_deg * (k - (frames - 1))) for k in range(frames)]      # the last frame is the scene's own camera
+    moving = parse_move(move, wl) if move else None
+    if moving:                                                           # the previous stream and this frame's two motion planes
+        stream_vec4 = api.bvh_count_device(ctx)
+        d_snap, d_motion = ctx.malloc(stream_vec4 * 16), (ctx.malloc(n * 16), ctx.malloc(n * 16))
+    else:
+        d_motion = None
     t0 = time.time()
     for k in range(frames):
         d_pos, d_nrm = gbuf[k % 2]
         lights = api.SoftLightList.make(entries(sc, count, spp), np.ascontiguousarray(np.roll(offsets, -k, axis=0)))
         hard = lights.hard_list()
         constants = api.RayTracingConstants.make(eyes[k], sc.light_direction, W, H)
-        api.primary_gbuffer_device(ctx, eyes[k], sc.target, sc.fovy, W, H, d_pos, d_nrm)
+        if moving:                                                       # snapshot -> refit -> motion G-buffer, all on the device
+            verts, mask, step = moving
+            now = verts.copy()
+            now[mask, :3] += step * np.float32(k)
+            api.snapshot_bvh_device(ctx, d_snap, stream_vec4)
+            api.bvh_refit_device(ctx, now.reshape(-1), 8, wl.indices, wl.prim_count)
+            if k == 0:
+                api.snapshot_bvh_device(ctx, d_snap, stream_vec4)      # (the first frame has no previous stream: its own)
+            api.primary_gbuffer_motion_device(ctx, d_snap, stream_vec4, eyes[k], eyes[max(k - 1, 0)], sc.target, sc.fovy, W, H, d_pos, d_nrm,
+                                              d_motion[0], d_motion[1])
+        else:
+            api.primary_gbuffer_device(ctx, eyes[k], sc.target, sc.fovy, W, H, d_pos, d_nrm)
         api.facing_lights_device(ctx, constants, hard, d_pos, d_nrm, W, H, d_map)
         if probe:
             ctx.trace_soft_light_list_adaptive_device(constants, lights, (probe,) * count, d_pos, W, H, d_counts, d_lights_map=d_map,
@@ -209,7 +243,8 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
                                              filt.normal_cos_min, filt.plane_eps, max_length)
         if with_moments:                                                 # this frame's count moments, then the filter they guide or feed
             api.accumulate_moments_soft_light_list_device(ctx, lights, tp, d_pos, d_nrm, d_counts, W, H, *moments[k % 2],
-                                                          d_prev=None if k == 0 else gbuf[(k - 1) % 2] + moments[(k - 1) % 2], d_lights_map=d_map)
+                                                          d_prev=None if k == 0 else gbuf[(k - 1) % 2] + moments[(k - 1) % 2], d_lights_map=d_map,
+                                                          d_motion=d_motion)
         if filter_mean and temporal_guide:
             api.wide_filter_guided_temporal_mean_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, moments[k % 2], W, H, d_vis,
                                                                         d_scratch=d_scratch, d_lights_map=d_map)
@@ -221,7 +256,7 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
                         moments[k % 2] if temporal_guide else None)
         d_prev = None if k == 0 else gbuf[(k - 1) % 2] + hist[(k - 1) % 2]
         api.accumulate_visibility_list_device(ctx, hard, tp, d_pos, d_nrm, d_vis, W, H, hist[k % 2][0], hist[k % 2][1], d_prev=d_prev,
-                                              d_lights_map=d_map, clamp=clamp)
+                                              d_lights_map=d_map, clamp=clamp, d_motion=d_motion)
     last = (frames - 1) % 2
     api.combine_visibility_list_device(ctx, constants, hard, gbuf[last][0], gbuf[last][1], hist[last][0], W, H, d_rgb, d_lights_map=d_map,
                                        colors=colors)
@@ -229,6 +264,14 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
     print(f"{frames} frames of {count} lights x {spp} samples, filter {filter_words(api, filt)}{' over the accumulated mean' if filter_mean else ''}, orbit {orbit_deg:g} degree per frame, "
           f"max_length {max_length}{'' if clamp is None else f', history clamped at r = {clamp.radius}, margin {clamp.margin:g}'}: "
           f"{(time.time() - t0) * 1e3:.2f} ms (incl. first launches)")
+    if moving:
+        pts = np.zeros((H, W, 4), np.float32)
+        ctx.d2h(pts, d_motion[0])
+        lengths = np.zeros((count, H, W), np.uint8)
+        ctx.d2h(lengths, hist[(frames - 1) % 2][1])
+        part = pts[..., 3] == 2
+        print(f"--move {move}: {int(moving[1].sum())} vertices refitted per frame, {int(part.sum())} pixels on the moved part in the last frame, "
+              f"their mean history length for light 0 {round(float(lengths[0][part & (lengths[0] > 0)].mean()), 2) if (part & (lengths[0] > 0)).any() else 0.0}")
     rgb, lengths, marks = np.zeros((H, W, 3), np.uint8), np.zeros((count, H, W), np.uint8), np.zeros((H, W), np.uint8)
     ctx.d2h(rgb, d_rgb)
     ctx.d2h(lengths, hist[last][1])
@@ -287,6 +330,9 @@ def main():
                     help="with --temporal: clamp the history into the current visibility's range over a window of (2R+1)^2 pixels, "
                          "R = 0..4 (rtsh_accumulate_visibility_list_clamped_device)")
     ap.add_argument("--clamp-margin", type=float, default=0.0, metavar="M", help="with --clamp: widen the range by M on both sides")
+    ap.add_argument("--move", default="", metavar="AXIS:LO:HI:DX,DY,DZ",
+                    help="with --temporal: displace the slab of the scene between the fractions LO and HI of its AXIS extent by (DX, DY, DZ) "
+                         "per frame, refit, and drive the motion G-buffer pass and the motion forms of the accumulates (DESIGN.md 4.29)")
     ap.add_argument("--colors", default="", metavar="r,g,b[;r,g,b...]",
                     help="with --soft-list N: the lights' colours, one triple for all of them or N separated by ';' (default 1/N each)")
     args = ap.parse_args()
@@ -322,6 +368,8 @@ def main():
             if args.filter_mean and (args.filter_passes < 0 or not args.temporal or (args.filter_guide >= 0) != bool(args.guide_history)):
                 sys.exit("render: --filter-mean goes with --filter-passes K and --temporal F, alone or with both --filter-guide K4 and "
                          "--guide-history M")
+            if args.move and not args.temporal:
+                sys.exit("render: --move SPEC goes with --temporal F")
             if args.temporal:
                 if filt is None or args.distance or args.refined:
                     sys.exit("render: --temporal F goes with --soft-list N and --filter R or --filter-passes K, without --distance and --refined")
@@ -329,7 +377,7 @@ def main():
                     sys.exit("render: --clamp R takes 0 <= R <= 4 and a finite --clamp-margin M >= 0")
                 clamp = api.HistoryClamp.make(args.clamp, args.clamp_margin) if args.clamp >= 0 else None
                 return soft_list_temporal(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, filt, args.temporal, args.orbit,
-                                          args.max_length, args.adaptive, args.table, args.colors, clamp, args.filter_mean)
+                                          args.max_length, args.adaptive, args.table, args.colors, clamp, args.filter_mean, args.move)
             return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance,
                              args.colors, filt)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
