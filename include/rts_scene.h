@@ -737,6 +737,10 @@ int rtsh_follow_plan_device(rts_ctx* ctx, const uint32_t* life_ticks, const uint
  *     prev_point.w = 2.  n' = cross(e0', e1'), s' = dot(n', n') > 0 ? 1 / sqrtf(dot(n', n')) : 0, negated exactly where the current
  *     normal was (dot(cross(e0, e1), d) > 0: the same side of the triangle, not a new decision); prev_point_normal = n' * s', .w = 0.
  *     A triangle that was degenerate last frame gives a zero normal: "no history" to the passes below.
+ *     The host and the device form agree bit for bit on every component that is not a NaN.  A component of a MOVED texel can be a
+ *     NaN only where the nine words of prev_packed hold a NaN or an Inf; it is then a NaN in both forms, but WHICH NaN is not defined
+ *     (which NaN Inf * 0 or Inf - Inf returns is the one thing hosts and the GPU disagree on; measured on poisoned streams, a third
+ *     of the NaN components differ in their bits, all of them in prev_point_normals).  The passes below reject every NaN alike.
  *   * RTS_ERR_INVALID_ARG, nothing written, nothing launched: everything rtsh_primary_gbuffer* refuses; a NULL prev_packed, prev_eye,
  *     prev_points or prev_point_normals; a prev_eye that is not finite; prev_count_vec4 != count_vec4 (device form: != the installed
  *     stream's).  Host form: a prev_packed whose tag and link words differ from packed's is RTS_ERR_BAD_BVH.  Device form: equal
