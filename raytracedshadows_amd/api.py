@@ -1728,18 +1728,34 @@ def wide_filter_scratch_bytes(count, width, height):
     return int(_lib.rtsh_wide_filter_scratch_bytes(count, width, height))
 
 
-def _wide_filter_list(soft, lights, params, positions, normals, planes, lights_map, threads):
-    name = "rtsh_wide_filter_soft_light_list" if soft else "rtsh_wide_filter_light_list"
+_NO_MOMENTS = object()
+
+
+def _wide_filter_frame(name, lights, positions, normals, planes, plane_type, lights_map, per_light=True, moments=_NO_MOMENTS):
+    """What the host forms of the wide filters share before their call: the buffers made contiguous in their types, checked against
+    the frame of the normals, and the zeroed visibility.  ``planes``: the first pass's input, one plane per light unless ``per_light``
+    is false (the one mask plane of a hard list).  Returns (positions, normals, planes, lights_map, moments, W, H, visibility)."""
     normals = np.ascontiguousarray(normals, np.float32)
     H, W = normals.shape[:2]
     count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
     positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
-    planes = np.ascontiguousarray(planes, np.uint8)
+    planes = np.ascontiguousarray(planes, plane_type)
     lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
-    if planes.size < (count if soft else 1) * H * W or (lights_map is not None and lights_map.size != H * W) or \
-            (positions is not None and positions.size != H * W * 4):
+    if moments is not _NO_MOMENTS:
+        mean, square, lengths = (np.ascontiguousarray(a, t) for a, t in zip(moments, (np.uint16, np.uint32, np.uint8)))
+        moments = (mean, square, lengths)
+    else:
+        moments = ()
+    if planes.size < (count if per_light else 1) * H * W or (lights_map is not None and lights_map.size != H * W) or \
+            (positions is not None and positions.size != H * W * 4) or any(a.size < count * H * W for a in moments):
         raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
-    visibility = np.zeros((count, H, W), np.float32)
+    return positions, normals, planes, lights_map, moments, W, H, np.zeros((count, H, W), np.float32)
+
+
+def _wide_filter_list(soft, lights, params, positions, normals, planes, lights_map, threads):
+    name = "rtsh_wide_filter_soft_light_list" if soft else "rtsh_wide_filter_light_list"
+    positions, normals, planes, lights_map, _, W, H, visibility = _wide_filter_frame(name, lights, positions, normals, planes, np.uint8,
+                                                                                     lights_map, per_light=soft)
     fn = _lib.rtsh_wide_filter_soft_light_list if soft else _lib.rtsh_wide_filter_light_list
     _check(fn(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals), _ptr_or_none(lights_map), _ptr(planes), W, H,
               _ptr(visibility), threads), name)
@@ -1794,16 +1810,8 @@ def wide_filter_guided_soft_light_list(lights, params, positions, normals, count
     """The variance-guided wide (a-trous) filter of a soft light list's count planes on the host
     (rtsh_wide_filter_guided_soft_light_list): ``float32[count, H, W]`` visibility; ``params`` a ``WideGuideParams``."""
     name = "rtsh_wide_filter_guided_soft_light_list"
-    normals = np.ascontiguousarray(normals, np.float32)
-    H, W = normals.shape[:2]
-    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
-    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
-    counts = np.ascontiguousarray(counts, np.uint8)
-    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
-    if counts.size < count * H * W or (lights_map is not None and lights_map.size != H * W) or \
-            (positions is not None and positions.size != H * W * 4):
-        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
-    visibility = np.zeros((count, H, W), np.float32)
+    positions, normals, counts, lights_map, _, W, H, visibility = _wide_filter_frame(name, lights, positions, normals, counts, np.uint8,
+                                                                                     lights_map)
     _check(_lib.rtsh_wide_filter_guided_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
                                                         _ptr_or_none(lights_map), _ptr(counts), W, H, _ptr(visibility), threads), name)
     return visibility
@@ -2016,17 +2024,8 @@ def wide_filter_guided_temporal_soft_light_list(lights, params, positions, norma
     ``float32[count, H, W]`` visibility.  ``params`` a ``WideGuideTemporalParams``; ``moments`` = ``(mean, square, lengths)`` of
     ``accumulate_moments_soft_light_list`` for this frame."""
     name = "rtsh_wide_filter_guided_temporal_soft_light_list"
-    normals = np.ascontiguousarray(normals, np.float32)
-    H, W = normals.shape[:2]
-    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
-    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
-    counts = np.ascontiguousarray(counts, np.uint8)
-    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
-    mean, square, lengths = (np.ascontiguousarray(a, t) for a, t in zip(moments, (np.uint16, np.uint32, np.uint8)))
-    if counts.size < count * H * W or (lights_map is not None and lights_map.size != H * W) or \
-            (positions is not None and positions.size != H * W * 4) or any(a.size < count * H * W for a in (mean, square, lengths)):
-        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
-    visibility = np.zeros((count, H, W), np.float32)
+    positions, normals, counts, lights_map, (mean, square, lengths), W, H, visibility = _wide_filter_frame(
+        name, lights, positions, normals, counts, np.uint8, lights_map, moments=moments)
     _check(_lib.rtsh_wide_filter_guided_temporal_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
                                                                  _ptr_or_none(lights_map), _ptr(counts), _ptr(mean), _ptr(square),
                                                                  _ptr(lengths), W, H, _ptr(visibility), threads), name)
@@ -2052,16 +2051,8 @@ def wide_filter_mean_soft_light_list(lights, params, positions, normals, mean, l
     ``float32[count, H, W]`` visibility.  ``params`` a ``WideFilterParams``; ``mean`` = the ``uint16[count, H, W]`` mean planes of
     ``accumulate_moments_soft_light_list`` for this frame."""
     name = "rtsh_wide_filter_mean_soft_light_list"
-    normals = np.ascontiguousarray(normals, np.float32)
-    H, W = normals.shape[:2]
-    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
-    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
-    mean = np.ascontiguousarray(mean, np.uint16)
-    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
-    if mean.size < count * H * W or (lights_map is not None and lights_map.size != H * W) or \
-            (positions is not None and positions.size != H * W * 4):
-        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
-    visibility = np.zeros((count, H, W), np.float32)
+    positions, normals, mean, lights_map, _, W, H, visibility = _wide_filter_frame(name, lights, positions, normals, mean, np.uint16,
+                                                                                   lights_map)
     _check(_lib.rtsh_wide_filter_mean_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
                                                       _ptr_or_none(lights_map), _ptr(mean), W, H, _ptr(visibility), threads), name)
     return visibility
@@ -2083,17 +2074,8 @@ def wide_filter_guided_temporal_mean_soft_light_list(lights, params, positions, 
     (rtsh_wide_filter_guided_temporal_mean_soft_light_list): ``float32[count, H, W]`` visibility.  Arguments as for
     ``wide_filter_guided_temporal_soft_light_list``; the passes average ``moments[0]``, ``counts`` feeds the threshold's fallback."""
     name = "rtsh_wide_filter_guided_temporal_mean_soft_light_list"
-    normals = np.ascontiguousarray(normals, np.float32)
-    H, W = normals.shape[:2]
-    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
-    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
-    counts = np.ascontiguousarray(counts, np.uint8)
-    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
-    mean, square, lengths = (np.ascontiguousarray(a, t) for a, t in zip(moments, (np.uint16, np.uint32, np.uint8)))
-    if counts.size < count * H * W or (lights_map is not None and lights_map.size != H * W) or \
-            (positions is not None and positions.size != H * W * 4) or any(a.size < count * H * W for a in (mean, square, lengths)):
-        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
-    visibility = np.zeros((count, H, W), np.float32)
+    positions, normals, counts, lights_map, (mean, square, lengths), W, H, visibility = _wide_filter_frame(
+        name, lights, positions, normals, counts, np.uint8, lights_map, moments=moments)
     _check(_lib.rtsh_wide_filter_guided_temporal_mean_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
                                                                       _ptr_or_none(lights_map), _ptr(counts), _ptr(mean), _ptr(square),
                                                                       _ptr(lengths), W, H, _ptr(visibility), threads), name)

@@ -143,19 +143,6 @@ __global__ __launch_bounds__(256) void wideGuidedTemporalKernel(WideFilterList f
         else ((uint16_t*)out)[(uint64_t)l * n + p] = (uint16_t)v[l];
     }
 }
-
-template <bool LAST>
-static int launchWideGuidedTemporalFirst(rts_ctx* ctx, void* stream, dim3 grid, const WideFilterList& f, uint32_t k4, uint32_t minHistory,
-                                         const GuideMoments& h, const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
-                                         const void* in, uint32_t W, uint32_t H, int step, void* out, uint16_t* guide) {
-    if (step >= 1 && step <= kWideDenseMaxStep) {
-        const WideGeometry g = wideGeometry(f.count, step);
-        return launchPass(ctx, stream, grid, dim3(16, 16), g.bytes, wideGuidedTemporalKernel<LAST, true>, f, k4, minHistory, h, d_positions,
-                          d_normals, d_lights_map, in, (int)W, (int)H, step, g.pitch, out, guide);
-    }
-    return launchPass(ctx, stream, grid, dim3(16, 16), 0, wideGuidedTemporalKernel<LAST, false>, f, k4, minHistory, h, d_positions, d_normals,
-                      d_lights_map, in, (int)W, (int)H, step, 0, out, guide);
-}
 } // namespace rts_harness
 
 extern "C" int rtsh_accumulate_moments_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list, const rtsh_temporal_params* params,
@@ -198,7 +185,7 @@ extern "C" int rtsh_accumulate_moments_soft_light_list_motion_device(rts_ctx* ct
                                    rts_harness::accumulateMomentsMotionKernel, f, t, d_prev_points, d_prev_point_normals, (int)W, (int)H);
 }
 
-// The chain of a call: rtsh_wide_filter_guided_soft_light_list_device's, with the sibling kernel as its first pass.
+// The chain of a call is launchWideChain (rts_wide_filter.inc), with three sets and the sibling kernel as its first pass.
 extern "C" int rtsh_wide_filter_guided_temporal_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list,
                                                                        const rtsh_wide_guide_temporal_params* params, const float* d_positions,
                                                                        const float* d_normals, const uint8_t* d_lights_map,
@@ -211,30 +198,12 @@ extern "C" int rtsh_wide_filter_guided_temporal_soft_light_list_device(rts_ctx* 
     const int made = makeWideGuidedTemporalList(list, params, W, H, &f);
     if (made != RTS_OK) return made;
     const uint32_t k4 = params->guide_k4, minHistory = params->min_history;
-    const dim3 grid((W + 15) / 16, (H + 15) / 16);
-    if (grid.y > 65535u) return RTS_ERR_INVALID_ARG;
-    const size_t set = (size_t)f.count * (size_t)W * (size_t)H;
-    if (f.passes >= 2u && !d_scratch) return RTS_ERR_INVALID_ARG;
-    if (d_scratch)
-        for (size_t i = 0; i < 3; ++i)
-            if ((const void*)d_visibility == (const void*)(d_scratch + i * set)) return RTS_ERR_INVALID_ARG;
     const GuideMoments h{ d_mean, d_square, d_lengths, W, (uint64_t)W * H };
-    if (f.passes <= 1u)
-        return launchWideGuidedTemporalFirst<true>(ctx, stream, grid, f, k4, minHistory, h, d_positions, d_normals, d_lights_map, d_counts, W, H,
-                                                   (int)f.passes, d_visibility, nullptr);
-    uint16_t* guide = d_scratch + 2 * set;
-    for (uint32_t k = 0; k < f.passes; ++k) {
-        const int step = 1 << k;
-        const void* in = k == 0 ? (const void*)d_counts : (const void*)(d_scratch + ((k - 1u) & 1u) * set);
-        uint16_t* mid = d_scratch + (k & 1u) * set;
-        int s;
-        if (k == 0)
-            s = launchWideGuidedTemporalFirst<false>(ctx, stream, grid, f, k4, minHistory, h, d_positions, d_normals, d_lights_map, in, W, H, step,
-                                                     mid, guide);
-        else if (k + 1u < f.passes)
-            s = launchWideGuidedPass<false, false>(ctx, stream, grid, f, k4, d_positions, d_normals, d_lights_map, in, W, H, step, mid, guide);
-        else s = launchWideGuidedPass<false, true>(ctx, stream, grid, f, k4, d_positions, d_normals, d_lights_map, in, W, H, step, d_visibility, guide);
-        if (s != RTS_OK) return s;
-    }
-    return RTS_OK;
+    auto firstPass = [&](dim3 grid, auto last, int step, void* out, uint16_t* guide) {
+        constexpr bool LAST = decltype(last)::value;
+        return launchWideKernel(ctx, stream, grid, f, W, H, step, wideGuidedTemporalKernel<LAST, true>, wideGuidedTemporalKernel<LAST, false>,
+                                std::make_tuple(k4, minHistory, h, d_positions, d_normals, d_lights_map, (const void*)d_counts), out, guide);
+    };
+    return launchWideChain(ctx, f, W, H, d_visibility, d_scratch, 3, firstPass,
+                           wideGuidedLaterPass(ctx, stream, f, k4, d_positions, d_normals, d_lights_map, W, H));
 }

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <new>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 using namespace rts_harness;
@@ -747,13 +748,35 @@ int makeWideFilterSoftList(const rts_soft_light_list* list, const rtsh_wide_filt
 }
 
 namespace {
-// The frame as wideFilterPassPixel reads it on the host: the G-buffer and the map straight from the buffers, V_k from the bytes (the
-// first pass) or from the previous pass's 16-bit planes.
-template <bool HARD>
+// The first pass's input rule: V_0 of light l at texel `at` from the mask byte of a hard list, from the count bytes of a soft list, or
+// V_0' from the accumulated mean (plane l at + l * n).
+struct WideHardInput {
+    const uint8_t* mask;
+    uint32_t operator()(size_t at, uint32_t l, size_t, uint32_t samples, uint32_t scale) const {
+        return wideFilterInput((mask[at] >> l) & 1u, samples, scale);
+    }
+};
+struct WideSoftInput {
+    const uint8_t* counts;
+    uint32_t operator()(size_t at, uint32_t l, size_t n, uint32_t samples, uint32_t scale) const {
+        return wideFilterInput(counts[(size_t)l * n + at], samples, scale);
+    }
+};
+struct WideMeanInput {
+    const uint16_t* mean;
+    uint32_t operator()(size_t at, uint32_t l, size_t n, uint32_t samples, uint32_t scale) const {
+        return wideMeanInput(mean[(size_t)l * n + at], samples, scale);
+    }
+};
+
+// The frame as a pass reads it on the host: the G-buffer and the map straight from the buffers, V_k from the input rule (the first pass)
+// or from the previous pass's 16-bit planes.
+template <class Input>
 struct WideFrameTexels {
     const float *positions, *normals;
-    const uint8_t *map, *bytes;                  // bytes: the first pass's input, else NULL
-    const uint16_t* values;                      // the previous pass's planes
+    const uint8_t* map;
+    Input input;
+    const uint16_t* values;                      // the previous pass's planes; NULL: the first pass
     const uint32_t *samples, *scale;
     size_t W, n;
     size_t at(int x, int y) const { return (size_t)y * W + (size_t)x; }
@@ -761,18 +784,23 @@ struct WideFrameTexels {
     V3 position(int x, int y) const { const float* v = positions + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
     uint32_t bits(int x, int y) const { return map ? map[at(x, y)] : 0xFFu; }
     uint32_t value(int x, int y, uint32_t l) const {
-        if (!bytes) return values[(size_t)l * n + at(x, y)];
-        return wideFilterInput(HARD ? (bytes[at(x, y)] >> l) & 1u : bytes[(size_t)l * n + at(x, y)], samples[l], scale[l]);
+        if (values) return values[(size_t)l * n + at(x, y)];
+        return input(at(x, y), l, n, samples[l], scale[l]);
     }
 };
 
-template <bool HARD>
-int wideFilterFrames(const WideFilterList& f, const float* positions, const float* normals, const uint8_t* lights_map, const uint8_t* planes,
-                     uint32_t W, uint32_t H, float* visibility, int threads) {
-    const size_t n = (size_t)W * H;
+// THE ONE CHAIN OF A CALL, for the five host twins: max(1, passes) passes, pass k from the input rule (k == 0) or from set (k - 1) & 1
+// of the scratch into set k & 1, the last one into visibility.  threshold(texels, x, y, T) is the first pass's rule of a guided chain:
+// T goes to a third set of planes behind the two ping-pong sets, as in the device form, and later passes read it there.  nullptr: the
+// unguided chain, two sets.
+template <class Input, class Threshold>
+int widePassChain(const WideFilterList& f, const float* positions, const float* normals, const uint8_t* lights_map, const Input& input,
+                  uint32_t W, uint32_t H, float* visibility, int threads, const Threshold& threshold) {
+    constexpr bool GUIDED = !std::is_same<Threshold, std::nullptr_t>::value;
+    const size_t n = (size_t)W * H, set = (size_t)f.count * n;
     std::vector<uint16_t> scratch;
     try {
-        if (f.passes >= 2u) scratch.resize(2 * (size_t)f.count * n);
+        if (f.passes >= 2u) scratch.resize((GUIDED ? 3 : 2) * set);
     } catch (const std::bad_alloc&) {
         return RTS_ERR_CAPACITY;
     }
@@ -780,12 +808,25 @@ int wideFilterFrames(const WideFilterList& f, const float* positions, const floa
     for (uint32_t k = 0; k < launches; ++k) {
         const bool first = k == 0u, last = k + 1u == launches;
         const int step = f.passes == 0u ? 0 : 1 << k;
-        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * (size_t)f.count * n;
-        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * (size_t)f.count * n;
-        const WideFrameTexels<HARD> t{ positions, normals, lights_map, first ? planes : nullptr, in, f.samples, f.scale, W, n };
+        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * set;
+        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * set;
+        uint16_t* guide = GUIDED && f.passes >= 2u ? scratch.data() + 2 * set : nullptr;
+        const WideFrameTexels<Input> t{ positions, normals, lights_map, input, in, f.samples, f.scale, W, n };
         parallelFor(n, 256, threads, [&](size_t i) {
+            const int x = (int)(i % W), y = (int)(i / W);
             uint32_t v[8];
-            wideFilterPassPixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H, step, v);
+            if constexpr (GUIDED) {
+                uint32_t T[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+                if (first) {
+                    if (step > 0) threshold(t, x, y, T);
+                    if (!last) for (uint32_t l = 0; l < f.count; ++l) guide[(size_t)l * n + i] = (uint16_t)T[l];
+                } else {
+                    for (uint32_t l = 0; l < f.count; ++l) T[l] = guide[(size_t)l * n + i];
+                }
+                wideGuidedPassPixel(f, t, x, y, (int)W, (int)H, step, T, v);
+            } else {
+                wideFilterPassPixel(f, t, x, y, (int)W, (int)H, step, v);
+            }
             for (uint32_t l = 0; l < f.count; ++l) {
                 if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
                 else out[(size_t)l * n + i] = (uint16_t)v[l];
@@ -794,13 +835,15 @@ int wideFilterFrames(const WideFilterList& f, const float* positions, const floa
     }
     return RTS_OK;
 }
+
+size_t wideScratchBytes(size_t sets, uint32_t count, uint32_t W, uint32_t H) {
+    if (count == 0 || count > 8u || W == 0 || H == 0) return 0;
+    return sets * (size_t)count * (size_t)W * (size_t)H * sizeof(uint16_t);
+}
 } // namespace
 } // namespace rts_harness
 
-extern "C" size_t rtsh_wide_filter_scratch_bytes(uint32_t count, uint32_t W, uint32_t H) {
-    if (count == 0 || count > 8u || W == 0 || H == 0) return 0;
-    return 2 * (size_t)count * (size_t)W * (size_t)H * sizeof(uint16_t);
-}
+extern "C" size_t rtsh_wide_filter_scratch_bytes(uint32_t count, uint32_t W, uint32_t H) { return wideScratchBytes(2, count, W, H); }
 
 extern "C" int rtsh_wide_filter_light_list(const rts_light_list* list, const rtsh_wide_filter_params* params, const float* positions,
                                            const float* normals, const uint8_t* lights_map, const uint8_t* mask, uint32_t W, uint32_t H,
@@ -809,7 +852,7 @@ extern "C" int rtsh_wide_filter_light_list(const rts_light_list* list, const rts
     WideFilterList f;
     const int s = makeWideFilterHardList(list, params, W, H, &f);
     if (s != RTS_OK) return s;
-    return wideFilterFrames<true>(f, positions, normals, lights_map, mask, W, H, visibility, threads);
+    return widePassChain(f, positions, normals, lights_map, WideHardInput{ mask }, W, H, visibility, threads, nullptr);
 }
 
 extern "C" int rtsh_wide_filter_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_filter_params* params, const float* positions,
@@ -819,7 +862,7 @@ extern "C" int rtsh_wide_filter_soft_light_list(const rts_soft_light_list* list,
     WideFilterList f;
     const int s = makeWideFilterSoftList(list, params, W, H, &f);
     if (s != RTS_OK) return s;
-    return wideFilterFrames<false>(f, positions, normals, lights_map, counts, W, H, visibility, threads);
+    return widePassChain(f, positions, normals, lights_map, WideSoftInput{ counts }, W, H, visibility, threads, nullptr);
 }
 
 // ---- the variance-guided wide filter of a soft light list's planes (include/rts_scene.h; per-pixel rule in rts_closest_hit.h:
@@ -835,10 +878,7 @@ int makeWideGuidedList(const rts_soft_light_list* list, const rtsh_wide_guide_pa
 }
 } // namespace rts_harness
 
-extern "C" size_t rtsh_wide_filter_guided_scratch_bytes(uint32_t count, uint32_t W, uint32_t H) {
-    if (count == 0 || count > 8u || W == 0 || H == 0) return 0;
-    return 3 * (size_t)count * (size_t)W * (size_t)H * sizeof(uint16_t);
-}
+extern "C" size_t rtsh_wide_filter_guided_scratch_bytes(uint32_t count, uint32_t W, uint32_t H) { return wideScratchBytes(3, count, W, H); }
 
 extern "C" uint32_t rtsh_wide_guide_threshold(uint64_t G, uint32_t D, uint32_t n, uint32_t guide_k4) {
     if (D == 0 || n == 0) return 65535u;
@@ -853,38 +893,8 @@ extern "C" int rtsh_wide_filter_guided_soft_light_list(const rts_soft_light_list
     const int s = makeWideGuidedList(list, params, W, H, &f);
     if (s != RTS_OK) return s;
     const uint32_t k4 = params->guide_k4;
-    const size_t n = (size_t)W * H, set = (size_t)f.count * n;
-    std::vector<uint16_t> scratch;                                       // two ping-pong sets, then the planes of T: the device form's
-    try {
-        if (f.passes >= 2u) scratch.resize(3 * set);
-    } catch (const std::bad_alloc&) {
-        return RTS_ERR_CAPACITY;
-    }
-    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
-    for (uint32_t k = 0; k < launches; ++k) {
-        const bool first = k == 0u, last = k + 1u == launches;
-        const int step = f.passes == 0u ? 0 : 1 << k;
-        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * set;
-        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * set;
-        uint16_t* guide = f.passes >= 2u ? scratch.data() + 2 * set : nullptr;
-        const WideFrameTexels<false> t{ positions, normals, lights_map, first ? counts : nullptr, in, f.samples, f.scale, W, n };
-        parallelFor(n, 256, threads, [&](size_t i) {
-            const int x = (int)(i % W), y = (int)(i / W);
-            uint32_t T[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, v[8];
-            if (first) {
-                if (step > 0) wideGuideThresholdPixel(f, k4, t, x, y, (int)W, (int)H, T);
-                if (!last) for (uint32_t l = 0; l < f.count; ++l) guide[(size_t)l * n + i] = (uint16_t)T[l];
-            } else {
-                for (uint32_t l = 0; l < f.count; ++l) T[l] = guide[(size_t)l * n + i];
-            }
-            wideGuidedPassPixel(f, t, x, y, (int)W, (int)H, step, T, v);
-            for (uint32_t l = 0; l < f.count; ++l) {
-                if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
-                else out[(size_t)l * n + i] = (uint16_t)v[l];
-            }
-        });
-    }
-    return RTS_OK;
+    return widePassChain(f, positions, normals, lights_map, WideSoftInput{ counts }, W, H, visibility, threads,
+                         [&](const auto& t, int x, int y, uint32_t* T) { wideGuideThresholdPixel(f, k4, t, x, y, (int)W, (int)H, T); });
 }
 
 // ---- the temporal accumulation of a light list's visibility (include/rts_scene.h; per-pixel rule in rts_closest_hit.h: accumulatePixel) ----
@@ -1206,65 +1216,15 @@ extern "C" int rtsh_wide_filter_guided_temporal_soft_light_list(const rts_soft_l
     const int s = makeWideGuidedTemporalList(list, params, W, H, &f);
     if (s != RTS_OK) return s;
     const uint32_t k4 = params->guide_k4, minHistory = params->min_history;
-    const size_t n = (size_t)W * H, set = (size_t)f.count * n;
-    const GuideMoments h{ mean, square, lengths, W, n };
-    std::vector<uint16_t> scratch;                                       // two ping-pong sets, then the planes of T: the device form's
-    try {
-        if (f.passes >= 2u) scratch.resize(3 * set);
-    } catch (const std::bad_alloc&) {
-        return RTS_ERR_CAPACITY;
-    }
-    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
-    for (uint32_t k = 0; k < launches; ++k) {
-        const bool first = k == 0u, last = k + 1u == launches;
-        const int step = f.passes == 0u ? 0 : 1 << k;
-        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * set;
-        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * set;
-        uint16_t* guide = f.passes >= 2u ? scratch.data() + 2 * set : nullptr;
-        const WideFrameTexels<false> t{ positions, normals, lights_map, first ? counts : nullptr, in, f.samples, f.scale, W, n };
-        parallelFor(n, 256, threads, [&](size_t i) {
-            const int x = (int)(i % W), y = (int)(i / W);
-            uint32_t T[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, v[8];
-            if (first) {
-                if (step > 0) wideGuideTemporalThresholdPixel(f, k4, minHistory, t, h, x, y, (int)W, (int)H, T);
-                if (!last) for (uint32_t l = 0; l < f.count; ++l) guide[(size_t)l * n + i] = (uint16_t)T[l];
-            } else {
-                for (uint32_t l = 0; l < f.count; ++l) T[l] = guide[(size_t)l * n + i];
-            }
-            wideGuidedPassPixel(f, t, x, y, (int)W, (int)H, step, T, v);
-            for (uint32_t l = 0; l < f.count; ++l) {
-                if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
-                else out[(size_t)l * n + i] = (uint16_t)v[l];
-            }
-        });
-    }
-    return RTS_OK;
+    const GuideMoments h{ mean, square, lengths, W, (size_t)W * H };
+    return widePassChain(f, positions, normals, lights_map, WideSoftInput{ counts }, W, H, visibility, threads,
+                         [&](const auto& t, int x, int y, uint32_t* T) {
+                             wideGuideTemporalThresholdPixel(f, k4, minHistory, t, h, x, y, (int)W, (int)H, T);
+                         });
 }
 
 // ---- the wide filters fed from the accumulated mean (include/rts_scene.h; per-pixel rule in rts_closest_hit.h: wideMeanInput,
 // wideFilterPassPixel, wideGuideTemporalMeanThresholdPixel, wideGuidedPassPixel) ----
-namespace rts_harness {
-namespace {
-// The frame as the passes read it on the host: WideFrameTexels with V_0' = min(mean, n S) as the first pass's input.
-struct WideMeanFrameTexels {
-    const float *positions, *normals;
-    const uint8_t* map;
-    const uint16_t* mean;                        // the first pass's input, else NULL
-    const uint16_t* values;                      // the previous pass's planes
-    const uint32_t *samples, *scale;
-    size_t W, n;
-    size_t at(int x, int y) const { return (size_t)y * W + (size_t)x; }
-    V3 normal(int x, int y) const { const float* v = normals + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
-    V3 position(int x, int y) const { const float* v = positions + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
-    uint32_t bits(int x, int y) const { return map ? map[at(x, y)] : 0xFFu; }
-    uint32_t value(int x, int y, uint32_t l) const {
-        if (!mean) return values[(size_t)l * n + at(x, y)];
-        return wideMeanInput(mean[(size_t)l * n + at(x, y)], samples[l], scale[l]);
-    }
-};
-} // namespace
-} // namespace rts_harness
-
 extern "C" int rtsh_wide_filter_mean_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_filter_params* params,
                                                      const float* positions, const float* normals, const uint8_t* lights_map,
                                                      const uint16_t* mean, uint32_t W, uint32_t H, float* visibility, int threads) {
@@ -1272,30 +1232,7 @@ extern "C" int rtsh_wide_filter_mean_soft_light_list(const rts_soft_light_list* 
     WideFilterList f;
     const int s = makeWideFilterSoftList(list, params, W, H, &f);
     if (s != RTS_OK) return s;
-    const size_t n = (size_t)W * H, set = (size_t)f.count * n;
-    std::vector<uint16_t> scratch;
-    try {
-        if (f.passes >= 2u) scratch.resize(2 * set);
-    } catch (const std::bad_alloc&) {
-        return RTS_ERR_CAPACITY;
-    }
-    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
-    for (uint32_t k = 0; k < launches; ++k) {
-        const bool first = k == 0u, last = k + 1u == launches;
-        const int step = f.passes == 0u ? 0 : 1 << k;
-        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * set;
-        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * set;
-        const WideMeanFrameTexels t{ positions, normals, lights_map, first ? mean : nullptr, in, f.samples, f.scale, W, n };
-        parallelFor(n, 256, threads, [&](size_t i) {
-            uint32_t v[8];
-            wideFilterPassPixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H, step, v);
-            for (uint32_t l = 0; l < f.count; ++l) {
-                if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
-                else out[(size_t)l * n + i] = (uint16_t)v[l];
-            }
-        });
-    }
-    return RTS_OK;
+    return widePassChain(f, positions, normals, lights_map, WideMeanInput{ mean }, W, H, visibility, threads, nullptr);
 }
 
 extern "C" int rtsh_wide_filter_guided_temporal_mean_soft_light_list(const rts_soft_light_list* list,
@@ -1308,37 +1245,9 @@ extern "C" int rtsh_wide_filter_guided_temporal_mean_soft_light_list(const rts_s
     const int s = makeWideGuidedTemporalList(list, params, W, H, &f);
     if (s != RTS_OK) return s;
     const uint32_t k4 = params->guide_k4, minHistory = params->min_history;
-    const size_t n = (size_t)W * H, set = (size_t)f.count * n;
-    const GuideMomentsCounts h{ GuideMoments{ mean, square, lengths, W, n }, counts };
-    std::vector<uint16_t> scratch;                                       // two ping-pong sets, then the planes of T: the device form's
-    try {
-        if (f.passes >= 2u) scratch.resize(3 * set);
-    } catch (const std::bad_alloc&) {
-        return RTS_ERR_CAPACITY;
-    }
-    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
-    for (uint32_t k = 0; k < launches; ++k) {
-        const bool first = k == 0u, last = k + 1u == launches;
-        const int step = f.passes == 0u ? 0 : 1 << k;
-        const uint16_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * set;
-        uint16_t* out = last ? nullptr : scratch.data() + (k & 1u) * set;
-        uint16_t* guide = f.passes >= 2u ? scratch.data() + 2 * set : nullptr;
-        const WideMeanFrameTexels t{ positions, normals, lights_map, first ? mean : nullptr, in, f.samples, f.scale, W, n };
-        parallelFor(n, 256, threads, [&](size_t i) {
-            const int x = (int)(i % W), y = (int)(i / W);
-            uint32_t T[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, v[8];
-            if (first) {
-                if (step > 0) wideGuideTemporalMeanThresholdPixel(f, k4, minHistory, t, h, x, y, (int)W, (int)H, T);
-                if (!last) for (uint32_t l = 0; l < f.count; ++l) guide[(size_t)l * n + i] = (uint16_t)T[l];
-            } else {
-                for (uint32_t l = 0; l < f.count; ++l) T[l] = guide[(size_t)l * n + i];
-            }
-            wideGuidedPassPixel(f, t, x, y, (int)W, (int)H, step, T, v);
-            for (uint32_t l = 0; l < f.count; ++l) {
-                if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
-                else out[(size_t)l * n + i] = (uint16_t)v[l];
-            }
-        });
-    }
-    return RTS_OK;
+    const GuideMomentsCounts h{ GuideMoments{ mean, square, lengths, W, (size_t)W * H }, counts };
+    return widePassChain(f, positions, normals, lights_map, WideMeanInput{ mean }, W, H, visibility, threads,
+                         [&](const auto& t, int x, int y, uint32_t* T) {
+                             wideGuideTemporalMeanThresholdPixel(f, k4, minHistory, t, h, x, y, (int)W, (int)H, T);
+                         });
 }

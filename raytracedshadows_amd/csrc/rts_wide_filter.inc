@@ -18,6 +18,8 @@
 //           do not fit; and for the passes == 0 conversion (step 0: no tap is walked).
 // kWideDenseMaxStep: the largest step that takes the DENSE form (tools/list_wide_filter_ab.py builds a second library with
 // -DRTS_WIDE_FILTER_DENSE_MAX_STEP=0, every pass DIRECT, to measure the choice per step).
+#include <tuple>
+#include <type_traits>
 
 namespace rts_harness {
 int makeWideFilterHardList(const rts_light_list* list, const rtsh_wide_filter_params* p, uint32_t W, uint32_t H, WideFilterList* out); // rts_scene.cpp
@@ -128,44 +130,74 @@ static WideGeometry wideGeometry(uint32_t count, int step) {
     return WideGeometry{ pitch, (size_t)pitch * (size_t)TW * (24 + 2 * (size_t)count + 1) };
 }
 
-template <bool FIRST, bool LAST, bool HARD>
-static int launchWidePass(rts_ctx* ctx, void* stream, dim3 grid, const WideFilterList& f, const float* d_positions, const float* d_normals,
-                          const uint8_t* d_lights_map, const void* in, uint32_t W, uint32_t H, int step, void* out) {
-    if (step >= 1 && step <= kWideDenseMaxStep) {
-        const WideGeometry g = wideGeometry(f.count, step);
-        return launchPass(ctx, stream, grid, dim3(16, 16), g.bytes, wideFilterKernel<FIRST, LAST, HARD, true>, f, d_positions, d_normals,
-                          d_lights_map, in, (int)W, (int)H, step, g.pitch, out);
-    }
-    return launchPass(ctx, stream, grid, dim3(16, 16), 0, wideFilterKernel<FIRST, LAST, HARD, false>, f, d_positions, d_normals, d_lights_map,
-                      in, (int)W, (int)H, step, 0, out);
+// THE ONE LAUNCH OF A PASS, for the five kernels of the wide filters (wideFilterKernel here; wideGuidedKernel, wideGuidedTemporalKernel,
+// wideMeanKernel, wideGuidedTemporalMeanKernel in the files included after this one): the DENSE instantiation with its window's pitch
+// and LDS bytes for steps 1 .. kWideDenseMaxStep, else the DIRECT one with pitch 0.  Every one of the kernels takes
+// (f, head..., int W, int H, int step, int pitch, tail...): `head` is what stands between the list and the frame size, in the kernel's order.
+template <class... Params, class... Head, class... Tail>
+static int launchWideKernel(rts_ctx* ctx, void* stream, dim3 grid, const WideFilterList& f, uint32_t W, uint32_t H, int step,
+                            void (*denseKernel)(Params...), void (*directKernel)(Params...), const std::tuple<Head...>& head, Tail... tail) {
+    const bool dense = step >= 1 && step <= kWideDenseMaxStep;
+    const WideGeometry g = dense ? wideGeometry(f.count, step) : WideGeometry{ 0, 0 };
+    auto launch = [&](Head... h) {
+        return launchPass(ctx, stream, grid, dim3(16, 16), g.bytes, dense ? denseKernel : directKernel, f, h..., (int)W, (int)H, step, g.pitch,
+                          tail...);
+    };
+    return std::apply(launch, head);
 }
 
-// The chain of a call: max(1, passes) launches on `stream`, pass k from the bytes (k == 0) or from half (k - 1) & 1 of the scratch into
-// half k & 1, the last one into visibility.
-template <bool HARD>
-static int launchWideFilter(rts_ctx* ctx, const WideFilterList& f, const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
-                            const uint8_t* d_planes, uint32_t W, uint32_t H, float* d_visibility, uint16_t* d_scratch, void* stream) {
+// THE ONE CHAIN OF A CALL, for the five device entries: max(1, passes) launches on `stream`, pass k from the entry's own input (k == 0) or
+// from set (k - 1) & 1 of the scratch into set k & 1, the last one into visibility.  `sets`: 2, or 3 for the guided forms, whose planes
+// of T lie behind the two ping-pong sets (`guide`; NULL for the one launch of passes <= 1, which is FIRST and LAST and stores no T).
+// firstPass(grid, last, step, out, guide) and laterPass(grid, last, in, step, out, guide) launch the entry's instantiations; `last` is a
+// std::bool_constant, so that LAST stays a template argument.
+template <class First, class Later>
+static int launchWideChain(rts_ctx* ctx, const WideFilterList& f, uint32_t W, uint32_t H, float* d_visibility, uint16_t* d_scratch, size_t sets,
+                           First firstPass, Later laterPass) {
     const dim3 grid((W + 15) / 16, (H + 15) / 16);
     if (grid.y > 65535u) return RTS_ERR_INVALID_ARG;
-    const size_t half = (size_t)f.count * (size_t)W * (size_t)H;
+    const size_t set = (size_t)f.count * (size_t)W * (size_t)H;
     if (f.passes >= 2u && !d_scratch) return RTS_ERR_INVALID_ARG;
-    if (d_scratch && ((const void*)d_visibility == (const void*)d_scratch || (const void*)d_visibility == (const void*)(d_scratch + half)))
-        return RTS_ERR_INVALID_ARG;
-    if (f.passes <= 1u)
-        return launchWidePass<true, true, HARD>(ctx, stream, grid, f, d_positions, d_normals, d_lights_map, d_planes, W, H, (int)f.passes,
-                                                d_visibility);
+    if (d_scratch)
+        for (size_t i = 0; i < sets; ++i)
+            if ((const void*)d_visibility == (const void*)(d_scratch + i * set)) return RTS_ERR_INVALID_ARG;
+    if (f.passes <= 1u) return firstPass(grid, std::true_type{}, (int)f.passes, (void*)d_visibility, (uint16_t*)nullptr);
+    uint16_t* guide = sets > 2 ? d_scratch + 2 * set : nullptr;
     for (uint32_t k = 0; k < f.passes; ++k) {
         const int step = 1 << k;
-        const void* in = k == 0 ? (const void*)d_planes : (const void*)(d_scratch + ((k - 1u) & 1u) * half);
-        uint16_t* mid = d_scratch + (k & 1u) * half;
+        const void* in = k == 0 ? nullptr : (const void*)(d_scratch + ((k - 1u) & 1u) * set);
+        void* mid = d_scratch + (k & 1u) * set;
         int s;
-        if (k == 0) s = launchWidePass<true, false, HARD>(ctx, stream, grid, f, d_positions, d_normals, d_lights_map, in, W, H, step, mid);
-        else if (k + 1u < f.passes)
-            s = launchWidePass<false, false, HARD>(ctx, stream, grid, f, d_positions, d_normals, d_lights_map, in, W, H, step, mid);
-        else s = launchWidePass<false, true, HARD>(ctx, stream, grid, f, d_positions, d_normals, d_lights_map, in, W, H, step, d_visibility);
+        if (k == 0) s = firstPass(grid, std::false_type{}, step, mid, guide);
+        else if (k + 1u < f.passes) s = laterPass(grid, std::false_type{}, in, step, mid, guide);
+        else s = laterPass(grid, std::true_type{}, in, step, (void*)d_visibility, guide);
         if (s != RTS_OK) return s;
     }
     return RTS_OK;
+}
+
+// The later passes of the unguided chains (this file's and rts_wide_mean.inc's): wideFilterKernel<false, LAST, HARD>.
+template <bool HARD>
+static auto wideLaterPass(rts_ctx* ctx, void* stream, const WideFilterList& f, const float* d_positions, const float* d_normals,
+                          const uint8_t* d_lights_map, uint32_t W, uint32_t H) {
+    return [=, &f](dim3 grid, auto last, const void* in, int step, void* out, uint16_t*) {
+        constexpr bool LAST = decltype(last)::value;
+        return launchWideKernel(ctx, stream, grid, f, W, H, step, wideFilterKernel<false, LAST, HARD, true>,
+                                wideFilterKernel<false, LAST, HARD, false>, std::make_tuple(d_positions, d_normals, d_lights_map, in), out);
+    };
+}
+
+template <bool HARD>
+static int launchWideFilter(rts_ctx* ctx, const WideFilterList& f, const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                            const uint8_t* d_planes, uint32_t W, uint32_t H, float* d_visibility, uint16_t* d_scratch, void* stream) {
+    auto firstPass = [&](dim3 grid, auto last, int step, void* out, uint16_t*) {
+        constexpr bool LAST = decltype(last)::value;
+        return launchWideKernel(ctx, stream, grid, f, W, H, step, wideFilterKernel<true, LAST, HARD, true>,
+                                wideFilterKernel<true, LAST, HARD, false>,
+                                std::make_tuple(d_positions, d_normals, d_lights_map, (const void*)d_planes), out);
+    };
+    return launchWideChain(ctx, f, W, H, d_visibility, d_scratch, 2, firstPass,
+                           wideLaterPass<HARD>(ctx, stream, f, d_positions, d_normals, d_lights_map, W, H));
 }
 } // namespace rts_harness
 

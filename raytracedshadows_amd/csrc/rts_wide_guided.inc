@@ -1,8 +1,8 @@
 // The variance-guided wide filter of a soft light list's planes on the GPU (include/rts_scene.h:
 // rtsh_wide_filter_guided_soft_light_list_device).  The per-pixel rule is the host twin's own source (rts_closest_hit.h:
 // wideGuideThresholdPixel, wideGuidedPassPixel).  Included by rts_primary.hip after rts_wide_filter.inc, whose tile, global texels,
-// window geometry and staging layout this file uses as they are; wideFilterKernel is not touched: a SIBLING kernel, so that every
-// instantiation of the unguided kernel keeps its instruction text.
+// window geometry, staging layout, launch of a pass (launchWideKernel) and chain of a call (launchWideChain) this file uses as they
+// are; wideFilterKernel is not touched: a SIBLING kernel, so that every instantiation of the unguided kernel keeps its instruction text.
 //
 // ONE KERNEL PER PASS as there: one pixel per lane, 16 x 16 pixels per workgroup, templated on FIRST, LAST and the staging form (DENSE
 // for steps 1, 2, 4; DIRECT for steps 8, 16 and the passes == 0 conversion).  The FIRST pass forms T(p, l) for its own pixel: its
@@ -95,21 +95,18 @@ __global__ __launch_bounds__(256) void wideGuidedKernel(WideFilterList f, uint32
     }
 }
 
-template <bool FIRST, bool LAST>
-static int launchWideGuidedPass(rts_ctx* ctx, void* stream, dim3 grid, const WideFilterList& f, uint32_t k4, const float* d_positions,
-                                const float* d_normals, const uint8_t* d_lights_map, const void* in, uint32_t W, uint32_t H, int step,
-                                void* out, uint16_t* guide) {
-    if (step >= 1 && step <= kWideDenseMaxStep) {
-        const WideGeometry g = wideGeometry(f.count, step);
-        return launchPass(ctx, stream, grid, dim3(16, 16), g.bytes, wideGuidedKernel<FIRST, LAST, true>, f, k4, d_positions, d_normals,
-                          d_lights_map, in, (int)W, (int)H, step, g.pitch, out, guide);
-    }
-    return launchPass(ctx, stream, grid, dim3(16, 16), 0, wideGuidedKernel<FIRST, LAST, false>, f, k4, d_positions, d_normals, d_lights_map,
-                      in, (int)W, (int)H, step, 0, out, guide);
+// The later passes of the guided chains (this file's, rts_moments.inc's and rts_wide_mean.inc's): wideGuidedKernel<false, LAST>.
+static auto wideGuidedLaterPass(rts_ctx* ctx, void* stream, const WideFilterList& f, uint32_t k4, const float* d_positions,
+                                const float* d_normals, const uint8_t* d_lights_map, uint32_t W, uint32_t H) {
+    return [=, &f](dim3 grid, auto last, const void* in, int step, void* out, uint16_t* guide) {
+        constexpr bool LAST = decltype(last)::value;
+        return launchWideKernel(ctx, stream, grid, f, W, H, step, wideGuidedKernel<false, LAST, true>, wideGuidedKernel<false, LAST, false>,
+                                std::make_tuple(k4, d_positions, d_normals, d_lights_map, in), out, guide);
+    };
 }
 } // namespace rts_harness
 
-// The chain of a call: launchWideFilter's, with the planes of T behind the two ping-pong sets.
+// The chain of a call is launchWideChain (rts_wide_filter.inc), with three sets.
 extern "C" int rtsh_wide_filter_guided_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list,
                                                               const rtsh_wide_guide_params* params, const float* d_positions,
                                                               const float* d_normals, const uint8_t* d_lights_map, const uint8_t* d_counts,
@@ -120,27 +117,11 @@ extern "C" int rtsh_wide_filter_guided_soft_light_list_device(rts_ctx* ctx, cons
     const int made = makeWideGuidedList(list, params, W, H, &f);
     if (made != RTS_OK) return made;
     const uint32_t k4 = params->guide_k4;
-    const dim3 grid((W + 15) / 16, (H + 15) / 16);
-    if (grid.y > 65535u) return RTS_ERR_INVALID_ARG;
-    const size_t set = (size_t)f.count * (size_t)W * (size_t)H;
-    if (f.passes >= 2u && !d_scratch) return RTS_ERR_INVALID_ARG;
-    if (d_scratch)
-        for (size_t i = 0; i < 3; ++i)
-            if ((const void*)d_visibility == (const void*)(d_scratch + i * set)) return RTS_ERR_INVALID_ARG;
-    if (f.passes <= 1u)
-        return launchWideGuidedPass<true, true>(ctx, stream, grid, f, k4, d_positions, d_normals, d_lights_map, d_counts, W, H, (int)f.passes,
-                                                d_visibility, nullptr);
-    uint16_t* guide = d_scratch + 2 * set;
-    for (uint32_t k = 0; k < f.passes; ++k) {
-        const int step = 1 << k;
-        const void* in = k == 0 ? (const void*)d_counts : (const void*)(d_scratch + ((k - 1u) & 1u) * set);
-        uint16_t* mid = d_scratch + (k & 1u) * set;
-        int s;
-        if (k == 0) s = launchWideGuidedPass<true, false>(ctx, stream, grid, f, k4, d_positions, d_normals, d_lights_map, in, W, H, step, mid, guide);
-        else if (k + 1u < f.passes)
-            s = launchWideGuidedPass<false, false>(ctx, stream, grid, f, k4, d_positions, d_normals, d_lights_map, in, W, H, step, mid, guide);
-        else s = launchWideGuidedPass<false, true>(ctx, stream, grid, f, k4, d_positions, d_normals, d_lights_map, in, W, H, step, d_visibility, guide);
-        if (s != RTS_OK) return s;
-    }
-    return RTS_OK;
+    auto firstPass = [&](dim3 grid, auto last, int step, void* out, uint16_t* guide) {
+        constexpr bool LAST = decltype(last)::value;
+        return launchWideKernel(ctx, stream, grid, f, W, H, step, wideGuidedKernel<true, LAST, true>, wideGuidedKernel<true, LAST, false>,
+                                std::make_tuple(k4, d_positions, d_normals, d_lights_map, (const void*)d_counts), out, guide);
+    };
+    return launchWideChain(ctx, f, W, H, d_visibility, d_scratch, 3, firstPass,
+                           wideGuidedLaterPass(ctx, stream, f, k4, d_positions, d_normals, d_lights_map, W, H));
 }

@@ -159,34 +159,9 @@ __global__ __launch_bounds__(256) void wideGuidedTemporalMeanKernel(WideFilterLi
         else ((uint16_t*)out)[(uint64_t)l * n + p] = (uint16_t)v[l];
     }
 }
-
-template <bool LAST>
-static int launchWideMeanFirst(rts_ctx* ctx, void* stream, dim3 grid, const WideFilterList& f, const float* d_positions, const float* d_normals,
-                               const uint8_t* d_lights_map, const uint16_t* d_mean, uint32_t W, uint32_t H, int step, void* out) {
-    if (step >= 1 && step <= kWideDenseMaxStep) {
-        const WideGeometry g = wideGeometry(f.count, step);
-        return launchPass(ctx, stream, grid, dim3(16, 16), g.bytes, wideMeanKernel<LAST, true>, f, d_positions, d_normals, d_lights_map, d_mean,
-                          (int)W, (int)H, step, g.pitch, out);
-    }
-    return launchPass(ctx, stream, grid, dim3(16, 16), 0, wideMeanKernel<LAST, false>, f, d_positions, d_normals, d_lights_map, d_mean, (int)W,
-                      (int)H, step, 0, out);
-}
-
-template <bool LAST>
-static int launchWideGuidedTemporalMeanFirst(rts_ctx* ctx, void* stream, dim3 grid, const WideFilterList& f, uint32_t k4, uint32_t minHistory,
-                                             const GuideMomentsCounts& h, const float* d_positions, const float* d_normals,
-                                             const uint8_t* d_lights_map, uint32_t W, uint32_t H, int step, void* out, uint16_t* guide) {
-    if (step >= 1 && step <= kWideDenseMaxStep) {
-        const WideGeometry g = wideGeometry(f.count, step);
-        return launchPass(ctx, stream, grid, dim3(16, 16), g.bytes, wideGuidedTemporalMeanKernel<LAST, true>, f, k4, minHistory, h, d_positions,
-                          d_normals, d_lights_map, (int)W, (int)H, step, g.pitch, out, guide);
-    }
-    return launchPass(ctx, stream, grid, dim3(16, 16), 0, wideGuidedTemporalMeanKernel<LAST, false>, f, k4, minHistory, h, d_positions,
-                      d_normals, d_lights_map, (int)W, (int)H, step, 0, out, guide);
-}
 } // namespace rts_harness
 
-// The chain of a call: launchWideFilter's, with the sibling kernel as its first pass.
+// The chain of both calls is launchWideChain (rts_wide_filter.inc), with two and three sets and the sibling kernel as its first pass.
 extern "C" int rtsh_wide_filter_mean_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list, const rtsh_wide_filter_params* params,
                                                             const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
                                                             const uint16_t* d_mean, uint32_t W, uint32_t H, float* d_visibility,
@@ -196,29 +171,15 @@ extern "C" int rtsh_wide_filter_mean_soft_light_list_device(rts_ctx* ctx, const 
     WideFilterList f;
     const int made = makeWideFilterSoftList(list, params, W, H, &f);
     if (made != RTS_OK) return made;
-    const dim3 grid((W + 15) / 16, (H + 15) / 16);
-    if (grid.y > 65535u) return RTS_ERR_INVALID_ARG;
-    const size_t half = (size_t)f.count * (size_t)W * (size_t)H;
-    if (f.passes >= 2u && !d_scratch) return RTS_ERR_INVALID_ARG;
-    if (d_scratch && ((const void*)d_visibility == (const void*)d_scratch || (const void*)d_visibility == (const void*)(d_scratch + half)))
-        return RTS_ERR_INVALID_ARG;
-    if (f.passes <= 1u)
-        return launchWideMeanFirst<true>(ctx, stream, grid, f, d_positions, d_normals, d_lights_map, d_mean, W, H, (int)f.passes, d_visibility);
-    for (uint32_t k = 0; k < f.passes; ++k) {
-        const int step = 1 << k;
-        const void* in = k == 0 ? nullptr : (const void*)(d_scratch + ((k - 1u) & 1u) * half);
-        uint16_t* mid = d_scratch + (k & 1u) * half;
-        int s;
-        if (k == 0) s = launchWideMeanFirst<false>(ctx, stream, grid, f, d_positions, d_normals, d_lights_map, d_mean, W, H, step, mid);
-        else if (k + 1u < f.passes)
-            s = launchWidePass<false, false, false>(ctx, stream, grid, f, d_positions, d_normals, d_lights_map, in, W, H, step, mid);
-        else s = launchWidePass<false, true, false>(ctx, stream, grid, f, d_positions, d_normals, d_lights_map, in, W, H, step, d_visibility);
-        if (s != RTS_OK) return s;
-    }
-    return RTS_OK;
+    auto firstPass = [&](dim3 grid, auto last, int step, void* out, uint16_t*) {
+        constexpr bool LAST = decltype(last)::value;
+        return launchWideKernel(ctx, stream, grid, f, W, H, step, wideMeanKernel<LAST, true>, wideMeanKernel<LAST, false>,
+                                std::make_tuple(d_positions, d_normals, d_lights_map, d_mean), out);
+    };
+    return launchWideChain(ctx, f, W, H, d_visibility, d_scratch, 2, firstPass,
+                           wideLaterPass<false>(ctx, stream, f, d_positions, d_normals, d_lights_map, W, H));
 }
 
-// The chain of a call: rtsh_wide_filter_guided_temporal_soft_light_list_device's, with the sibling kernel as its first pass.
 extern "C" int rtsh_wide_filter_guided_temporal_mean_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list,
                                                                             const rtsh_wide_guide_temporal_params* params,
                                                                             const float* d_positions, const float* d_normals,
@@ -232,30 +193,13 @@ extern "C" int rtsh_wide_filter_guided_temporal_mean_soft_light_list_device(rts_
     const int made = makeWideGuidedTemporalList(list, params, W, H, &f);
     if (made != RTS_OK) return made;
     const uint32_t k4 = params->guide_k4, minHistory = params->min_history;
-    const dim3 grid((W + 15) / 16, (H + 15) / 16);
-    if (grid.y > 65535u) return RTS_ERR_INVALID_ARG;
-    const size_t set = (size_t)f.count * (size_t)W * (size_t)H;
-    if (f.passes >= 2u && !d_scratch) return RTS_ERR_INVALID_ARG;
-    if (d_scratch)
-        for (size_t i = 0; i < 3; ++i)
-            if ((const void*)d_visibility == (const void*)(d_scratch + i * set)) return RTS_ERR_INVALID_ARG;
     const GuideMomentsCounts h{ GuideMoments{ d_mean, d_square, d_lengths, W, (uint64_t)W * H }, d_counts };
-    if (f.passes <= 1u)
-        return launchWideGuidedTemporalMeanFirst<true>(ctx, stream, grid, f, k4, minHistory, h, d_positions, d_normals, d_lights_map, W, H,
-                                                       (int)f.passes, d_visibility, nullptr);
-    uint16_t* guide = d_scratch + 2 * set;
-    for (uint32_t k = 0; k < f.passes; ++k) {
-        const int step = 1 << k;
-        const void* in = k == 0 ? nullptr : (const void*)(d_scratch + ((k - 1u) & 1u) * set);
-        uint16_t* mid = d_scratch + (k & 1u) * set;
-        int s;
-        if (k == 0)
-            s = launchWideGuidedTemporalMeanFirst<false>(ctx, stream, grid, f, k4, minHistory, h, d_positions, d_normals, d_lights_map, W, H, step,
-                                                         mid, guide);
-        else if (k + 1u < f.passes)
-            s = launchWideGuidedPass<false, false>(ctx, stream, grid, f, k4, d_positions, d_normals, d_lights_map, in, W, H, step, mid, guide);
-        else s = launchWideGuidedPass<false, true>(ctx, stream, grid, f, k4, d_positions, d_normals, d_lights_map, in, W, H, step, d_visibility, guide);
-        if (s != RTS_OK) return s;
-    }
-    return RTS_OK;
+    auto firstPass = [&](dim3 grid, auto last, int step, void* out, uint16_t* guide) {
+        constexpr bool LAST = decltype(last)::value;
+        return launchWideKernel(ctx, stream, grid, f, W, H, step, wideGuidedTemporalMeanKernel<LAST, true>,
+                                wideGuidedTemporalMeanKernel<LAST, false>,
+                                std::make_tuple(k4, minHistory, h, d_positions, d_normals, d_lights_map), out, guide);
+    };
+    return launchWideChain(ctx, f, W, H, d_visibility, d_scratch, 3, firstPass,
+                           wideGuidedLaterPass(ctx, stream, f, k4, d_positions, d_normals, d_lights_map, W, H));
 }
