@@ -558,7 +558,8 @@ int rtsh_wide_filter_guided_soft_light_list_device(rts_ctx* ctx, const rts_soft_
  *   * planes of any buffer from `count` up are never touched.  No buffer needs alignment beyond its element type's.
  *   * host form: multi-threaded.  Device form: DEVICE buffers, asynchronous on `stream`, allocates nothing, reads nothing back; under
  *     graph capture ONE kernel node, list and params by value.  No BVH.
- *   * OUT OF SCOPE: (moving geometry: the motion form at the end of this header;) a clamp of the moments' history, hard lists (their variance is 0), row ranges and stripes. */
+ *   * OUT OF SCOPE: (moving geometry: the motion form at the end of this header;) (a clamp of the moments' history: the clamped forms at
+ *     the end of this header, DESIGN.md 4.30;) hard lists (their variance is 0), row ranges and stripes. */
 int rtsh_accumulate_moments_soft_light_list(const rts_soft_light_list* list, const rtsh_temporal_params* params, const float* positions,
                                             const float* normals, const uint8_t* lights_map, const uint8_t* counts,
                                             const float* prev_positions, const float* prev_normals, const uint16_t* prev_mean,
@@ -655,8 +656,8 @@ int rtsh_wide_filter_guided_temporal_soft_light_list_device(rts_ctx* ctx, const 
  *     third set for passes >= 2.
  *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the counterpart refuses, with mean in the place of counts;
  *     a NULL mean; d_visibility equal to the start of any scratch set (two for the unguided form, three for the guided one).
- *   * OUT OF SCOPE: variance divided by the history's length or propagated through the passes, a clamp of the moments' history, motion
- *     vectors, the tent filter, hard lists, row ranges and stripes, an LDS-staged form of the moments, and feeding the float visibility
+ *   * OUT OF SCOPE: variance divided by the history's length or propagated through the passes, (a clamp of the moments' history: the
+ *     clamped forms at the end of this header,) motion vectors, the tent filter, hard lists, row ranges and stripes, an LDS-staged form of the moments, and feeding the float visibility
  *     history of rtsh_accumulate_visibility_list to the a-trous passes (it is not fixed point). */
 int rtsh_wide_filter_mean_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_filter_params* params, const float* positions,
                                           const float* normals, const uint8_t* lights_map, const uint16_t* mean, uint32_t W, uint32_t H,
@@ -816,6 +817,88 @@ int rtsh_accumulate_moments_soft_light_list_motion_device(rts_ctx* ctx, const rt
                                                           const float* d_prev_point_normals, uint32_t W, uint32_t H,
                                                           uint16_t* d_mean_out, uint32_t* d_square_out, uint8_t* d_lengths_out,
                                                           void* stream);
+
+/* THE CLAMPED FORMS OF THE MOMENTS PASS: rtsh_accumulate_moments_soft_light_list and its motion form reject history by the RECEIVER's
+ * geometry alone, so a shadow that changes on a receiver that does not -- a moving occluder's cast shadow, a drifting light -- lags
+ * (max_length 32: 97 % of the stale mean), and reset_lights throws a light's whole history away.  Here a pair's reprojected tap sums are
+ * first CLAMPED into a box built from THIS frame's counts over a (2r+1) x (2r+1) window: the window's [min, max] INTERSECTED with its
+ * mean +- sigma_k4/4 standard deviations.  V_0 is a 16-bit integer, so the window's sums are integer sums and the square root is an
+ * exact integer one: no order of taps, no tiling and no staging scheme can change a bit, and the host forms check the device forms bit
+ * for bit.  Everything of the parent rule holds unchanged -- INACTIVE, REPROJECT (or the motion forms' Q and M_p), tap acceptance, sw,
+ * s, m, n, PASS-THROUGH, lengths_out --; ONE step is added between the tap sums and the quotient, so only at a BLENDED (pixel, light).
+ *   WINDOW of pixel p = (x, y) for light l: of the taps q = (x+dx, y+dy), |dx| <= r and |dy| <= r, those CONTRIBUTE that lie inside the
+ *     frame, whose normals[q].xyz is not all zero, and for which lights_map is NULL or bit l of lights_map[q] is set (the activity
+ *     conditions of rtsh_accumulate_visibility_list_clamped; no NaN case: the values are integers).  A tap's value is v_q = V_0(q, l)
+ *     of THIS frame's counts; the window lies on THIS frame's pixel grid in the motion form too.  The centre of a blended pair always
+ *     contributes.  Over the contributing taps: m = their number (at most 81), S1 = sum v (< 2^23), S2 = sum v^2 (< 2^39), lo = min v,
+ *     hi = max v.
+ *   BOX (unsigned 64-bit integers throughout): D = m * S2 - S1^2 (never negative, < 2^43); x = sigma_k4^2 * D (< 2^59);
+ *     R = ceil(sqrt(x)) = isqrt(x), plus one where isqrt(x)^2 < x; Rc = (R + 3) / 4; A = S1 - Rc saturating at 0, B = S1 + Rc;
+ *     L_m = max(m * lo, A), H_m = min(m * hi, B); Lv = L_m / m (floor), Hv = (H_m + m - 1) / m (ceiling): rounded OUTWARD to whole
+ *     units of V_0; Lv' = Lv - margin saturating at 0, Hv' = min(65535, Hv + margin).  (m * mean = S1 and m * sigma = sqrt(D): the
+ *     box is mean +- (sigma_k4 / 4) sigma in units of 1/m, cut to the range.)  rtsh_moments_clamp_bounds evaluates exactly this from
+ *     its parts: the host twin, the kernels and the tests share that one source.  Outside the widths above (m == 0 or above 81,
+ *     sigma_k4 above 255, hi above 65535, lo above hi, S1 >= 2^23, S2 >= 2^39, m * S2 < S1^2) it gives Lv' = 0 and Hv' = 65535.
+ *   CLAMP: s1' = min(max(s1, sw * Lv'), sw * Hv'), s2' = min(max(s2, sw * Lv'^2), sw * Hv'^2) (at most 2^42); then num, den and the
+ *     single rounded quotient of the parent rule on s1' and s2'.  Every width of the parent rule still holds.
+ * ANCHORS: (1) margin 65535 gives the unclamped pass's three planes bit for bit, for any radius and sigma_k4, over a history whose
+ * squares are at most 65535^2 -- every plane this pass or its parent wrote is, by RANGE; a foreign prev_square above it is cut to
+ * sw * 65535^2 like any other value above the box.  (2) radius 0 with
+ * margin 0 gives mean_out = cur1 and square_out = cur2 at every blended pair, and the unclamped lengths.  (3) Pass-through and inactive
+ * pairs are the unclamped rule's bits: the first frame, max_length 1 and a light in reset_lights are all pass-through.  (4) THE STEP:
+ * history mean 65535 and square 65535^2 of any length, current counts all 0, a still camera, margin 0: mean 0 and square 0 exactly, at
+ * any radius, sigma_k4 and max_length, where the unclamped pass gives round(65535 * (n - 1) / n).  (5) sigma_k4 >= 36 is the range box
+ * alone: by Samuelson's inequality no value lies further than sqrt(m - 1) < 9 deviations from its window's mean; so sigma_k4 36 and
+ * 255 agree bit for bit.  At sigma_k4 0 the box is the window's mean rounded outward: Hv - Lv <= 1.  Always lo <= Lv <= Hv <= hi.
+ * (6) RANGE: every mean_out lies between min(Lv', cur1) and max(Hv', cur1), every square_out between min(Lv'^2, cur2) and
+ * max(Hv'^2, cur2).
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the unclamped form (and, for the motion forms, the motion form)
+ *     refuses; a NULL clamp; radius above RTSH_MOMENTS_CLAMP_MAX_RADIUS; sigma_k4 above 255; margin above 65535.  `counts` is only read
+ *     and no output has its type: there is no counterpart of the float clamp's visibility_out == visibility refusal.
+ *   * reserved_ is ignored.  Planes from `count` up are never touched.  Host forms: multi-threaded.  Device forms: DEVICE buffers,
+ *     asynchronous on `stream`, allocate nothing, read nothing back; under graph capture ONE kernel node, list, params and clamp by
+ *     value.  No BVH, no alignment of any buffer beyond its element type's.
+ *   * OUT OF SCOPE: a sigma box for the float pass (rtsh_accumulate_visibility_list_clamped keeps its min/max box), a data-dependent
+ *     skip per block, row ranges and stripes. */
+enum { RTSH_MOMENTS_CLAMP_MAX_RADIUS = 4 };
+typedef struct rtsh_moments_clamp {
+    uint32_t radius;                                   /* r, 0 .. RTSH_MOMENTS_CLAMP_MAX_RADIUS: the window is (2r+1) x (2r+1) pixels */
+    uint32_t sigma_k4;                                 /* 0 .. 255: the box is mean +- sigma_k4/4 deviations, cut to [min, max] */
+    uint32_t margin;                                   /* 0 .. 65535, in units of V_0: widens the box on both sides */
+    uint32_t reserved_;                                /* ignored */
+} rtsh_moments_clamp;                                                              /* 16 bytes */
+void rtsh_moments_clamp_bounds(uint32_t m, uint64_t S1, uint64_t S2, uint32_t lo, uint32_t hi, uint32_t sigma_k4, uint32_t margin,
+                               uint32_t* Lv, uint32_t* Hv);
+int rtsh_accumulate_moments_soft_light_list_clamped(const rts_soft_light_list* list, const rtsh_temporal_params* params,
+                                                    const float* positions, const float* normals, const uint8_t* lights_map,
+                                                    const uint8_t* counts, const float* prev_positions, const float* prev_normals,
+                                                    const uint16_t* prev_mean, const uint32_t* prev_square, const uint8_t* prev_lengths,
+                                                    uint32_t W, uint32_t H, uint16_t* mean_out, uint32_t* square_out, uint8_t* lengths_out,
+                                                    const rtsh_moments_clamp* clamp, int threads);
+int rtsh_accumulate_moments_soft_light_list_clamped_device(rts_ctx* ctx, const rts_soft_light_list* list, const rtsh_temporal_params* params,
+                                                           const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                           const uint8_t* d_counts, const float* d_prev_positions,
+                                                           const float* d_prev_normals, const uint16_t* d_prev_mean,
+                                                           const uint32_t* d_prev_square, const uint8_t* d_prev_lengths, uint32_t W,
+                                                           uint32_t H, uint16_t* d_mean_out, uint32_t* d_square_out, uint8_t* d_lengths_out,
+                                                           const rtsh_moments_clamp* clamp, void* stream);
+int rtsh_accumulate_moments_soft_light_list_clamped_motion(const rts_soft_light_list* list, const rtsh_temporal_params* params,
+                                                           const float* positions, const float* normals, const uint8_t* lights_map,
+                                                           const uint8_t* counts, const float* prev_positions, const float* prev_normals,
+                                                           const uint16_t* prev_mean, const uint32_t* prev_square,
+                                                           const uint8_t* prev_lengths, const float* prev_points,
+                                                           const float* prev_point_normals, uint32_t W, uint32_t H, uint16_t* mean_out,
+                                                           uint32_t* square_out, uint8_t* lengths_out, const rtsh_moments_clamp* clamp,
+                                                           int threads);
+int rtsh_accumulate_moments_soft_light_list_clamped_motion_device(rts_ctx* ctx, const rts_soft_light_list* list,
+                                                                  const rtsh_temporal_params* params, const float* d_positions,
+                                                                  const float* d_normals, const uint8_t* d_lights_map,
+                                                                  const uint8_t* d_counts, const float* d_prev_positions,
+                                                                  const float* d_prev_normals, const uint16_t* d_prev_mean,
+                                                                  const uint32_t* d_prev_square, const uint8_t* d_prev_lengths,
+                                                                  const float* d_prev_points, const float* d_prev_point_normals,
+                                                                  uint32_t W, uint32_t H, uint16_t* d_mean_out, uint32_t* d_square_out,
+                                                                  uint8_t* d_lengths_out, const rtsh_moments_clamp* clamp, void* stream);
 
 #ifdef __cplusplus
 }

@@ -291,6 +291,19 @@ class HistoryClamp(C.Structure):
         return c
 
 
+class MomentsClamp(C.Structure):
+    """``rtsh_moments_clamp``: the neighbourhood clamp of the moments pass -- a window of (2 * radius + 1)^2 pixels (radius 0..4) of
+    this frame's V_0 whose [min, max], intersected with mean +- ``sigma_k4``/4 standard deviations (0..255; 36 and above: the range
+    alone) and widened by ``margin`` units of V_0 (0..65535), bounds the reprojected tap sums."""
+    _fields_ = [("radius", C.c_uint32), ("sigma_k4", C.c_uint32), ("margin", C.c_uint32), ("reserved_", C.c_uint32)]
+
+    @classmethod
+    def make(cls, radius, sigma_k4=8, margin=0):
+        c = cls()
+        c.radius, c.sigma_k4, c.margin = radius, sigma_k4, margin
+        return c
+
+
 #: numpy view of ``struct BVHNode`` (BVHBuilder.h:8-20)
 BVHNode_dtype = np.dtype([("bboxMin", np.float32, 3), ("prim", np.uint32),
                           ("bboxMax", np.float32, 3), ("next", np.uint32)])
@@ -588,6 +601,20 @@ _sig("rtsh_accumulate_moments_soft_light_list_motion", C.c_int, C.POINTER(SoftLi
 _sig("rtsh_accumulate_moments_soft_light_list_motion_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(TemporalParams),
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_moments_clamp_bounds", None, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
+_sig("rtsh_accumulate_moments_soft_light_list_clamped", C.c_int, C.POINTER(SoftLightList), C.POINTER(TemporalParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.POINTER(MomentsClamp), C.c_int)
+_sig("rtsh_accumulate_moments_soft_light_list_clamped_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(TemporalParams),
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MomentsClamp), C.c_void_p)
+_sig("rtsh_accumulate_moments_soft_light_list_clamped_motion", C.c_int, C.POINTER(SoftLightList), C.POINTER(TemporalParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MomentsClamp), C.c_int)
+_sig("rtsh_accumulate_moments_soft_light_list_clamped_motion_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList),
+     C.POINTER(TemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(MomentsClamp), C.c_void_p)
 _sig("rtsh_wide_filter_guided_temporal_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(WideGuideTemporalParams), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
 _sig("rtsh_wide_filter_guided_temporal_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList),
@@ -1959,13 +1986,23 @@ def accumulate_visibility_list_device(ctx, light_list, params, d_positions, d_no
            "rtsh_accumulate_visibility_list_device")
 
 
-def accumulate_moments_soft_light_list(lights, params, positions, normals, counts, prev=None, lights_map=None, threads=0, motion=None):
+def moments_clamp_bounds(m, S1, S2, lo, hi, sigma_k4, margin=0):
+    """``(Lv', Hv')`` of the clamped moments pass from a window's parts (rtsh_moments_clamp_bounds): ``m`` contributing taps, ``S1`` the
+    sum of their V_0, ``S2`` the sum of the squares, ``lo`` and ``hi`` their minimum and maximum."""
+    lv, hv = C.c_uint32(0), C.c_uint32(0)
+    _lib.rtsh_moments_clamp_bounds(m, S1, S2, lo, hi, sigma_k4, margin, C.byref(lv), C.byref(hv))
+    return int(lv.value), int(hv.value)
+
+
+def accumulate_moments_soft_light_list(lights, params, positions, normals, counts, prev=None, lights_map=None, threads=0, motion=None,
+                                       clamp=None):
     """The temporal accumulation of a soft light list's count moments on the host (rtsh_accumulate_moments_soft_light_list):
     ``(uint16[count, H, W] mean, uint32[count, H, W] square, uint8[count, H, W] lengths)``.  ``counts``: this frame's
     ``uint8[>= count, H, W]``; ``prev``: None on the first frame, else ``(prev_positions, prev_normals, prev_mean, prev_square,
     prev_lengths)`` of the previous frame (its G-buffer and what this call returned for it); ``params`` a ``TemporalParams``.  ``motion``:
-    None, or ``(prev_points, prev_point_normals)`` of this frame's motion G-buffer pass for the motion form."""
-    name = "rtsh_accumulate_moments_soft_light_list" + ("_motion" if motion is not None else "")
+    None, or ``(prev_points, prev_point_normals)`` of this frame's motion G-buffer pass for the motion form.  ``clamp``: None, or a
+    ``MomentsClamp`` for the clamped form (rtsh_accumulate_moments_soft_light_list_clamped, ..._clamped_motion)."""
+    name = "rtsh_accumulate_moments_soft_light_list" + ("_clamped" if clamp is not None else "") + ("_motion" if motion is not None else "")
     normals = np.ascontiguousarray(normals, np.float32)
     H, W = normals.shape[:2]
     count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
@@ -1984,10 +2021,17 @@ def accumulate_moments_soft_light_list(lights, params, positions, normals, count
     pp = [_ptr(a) for a in prev] if prev is not None else [None] * 5
     if motion is not None:
         mp = _motion_planes(motion, H, W, name)
-        _check(_lib.rtsh_accumulate_moments_soft_light_list_motion(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
-                                                                   _ptr_or_none(lights_map), _ptr(counts), pp[0], pp[1], pp[2], pp[3], pp[4],
-                                                                   _ptr_or_none(mp[0]), _ptr_or_none(mp[1]), W, H, _ptr(mean), _ptr(square),
-                                                                   _ptr(lengths), threads), name)
+        args = (_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals), _ptr_or_none(lights_map), _ptr(counts), pp[0], pp[1], pp[2],
+                pp[3], pp[4], _ptr_or_none(mp[0]), _ptr_or_none(mp[1]), W, H, _ptr(mean), _ptr(square), _ptr(lengths))
+        if clamp is not None:
+            _check(_lib.rtsh_accumulate_moments_soft_light_list_clamped_motion(*args, _ref(clamp), threads), name)
+            return mean, square, lengths
+        _check(_lib.rtsh_accumulate_moments_soft_light_list_motion(*args, threads), name)
+        return mean, square, lengths
+    if clamp is not None:
+        _check(_lib.rtsh_accumulate_moments_soft_light_list_clamped(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
+                                                                    _ptr_or_none(lights_map), _ptr(counts), pp[0], pp[1], pp[2], pp[3], pp[4],
+                                                                    W, H, _ptr(mean), _ptr(square), _ptr(lengths), _ref(clamp), threads), name)
         return mean, square, lengths
     _check(_lib.rtsh_accumulate_moments_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
                                                         _ptr_or_none(lights_map), _ptr(counts), pp[0], pp[1], pp[2], pp[3], pp[4], W, H,
@@ -1996,12 +2040,23 @@ def accumulate_moments_soft_light_list(lights, params, positions, normals, count
 
 
 def accumulate_moments_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_counts, width, height, d_mean_out,
-                                              d_square_out, d_lengths_out, d_prev=None, d_lights_map=None, stream=None, d_motion=None):
+                                              d_square_out, d_lengths_out, d_prev=None, d_lights_map=None, stream=None, d_motion=None,
+                                              clamp=None):
     """The moments pass on the GPU: device pointers; ``d_prev``: None on the first frame, else the device pointers ``(prev_positions,
     prev_normals, prev_mean, prev_square, prev_lengths)``.  d_mean_out = count planes of width*height uint16, d_square_out of uint32,
     d_lengths_out of bytes; none may be the history it reads.  One kernel, asynchronous.  ``d_motion``: None, or the device pointers
-    ``(prev_points, prev_point_normals)`` of this frame's motion G-buffer pass for the motion form."""
+    ``(prev_points, prev_point_normals)`` of this frame's motion G-buffer pass for the motion form.  ``clamp``: None, or a
+    ``MomentsClamp`` for the clamped forms (one kernel as well)."""
     pp = tuple(d_prev) if d_prev is not None else (0, 0, 0, 0, 0)
+    if clamp is not None:
+        name = "rtsh_accumulate_moments_soft_light_list_clamped" + ("_motion" if d_motion is not None else "") + "_device"
+        motion = (C.c_void_p(d_motion[0] or 0), C.c_void_p(d_motion[1] or 0)) if d_motion is not None else ()
+        _check(getattr(_lib, name)(
+            ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
+            C.c_void_p(d_counts), C.c_void_p(pp[0] or 0), C.c_void_p(pp[1] or 0), C.c_void_p(pp[2] or 0), C.c_void_p(pp[3] or 0),
+            C.c_void_p(pp[4] or 0), *motion, width, height, C.c_void_p(d_mean_out), C.c_void_p(d_square_out), C.c_void_p(d_lengths_out),
+            _ref(clamp), C.c_void_p(stream or 0)), name)
+        return
     if d_motion is not None:
         _check(_lib.rtsh_accumulate_moments_soft_light_list_motion_device(
             ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),

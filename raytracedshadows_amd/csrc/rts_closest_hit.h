@@ -672,7 +672,36 @@ RTS_HD uint64_t momentsQuotient(uint64_t a, uint32_t b) {
     return q;
 }
 
-template <bool Motion = false, class Frames>
+// CLAMPED (rtsh_accumulate_moments_soft_light_list_clamped and its motion form): the box of the header from the window's
+// five integers -- m contributing taps, S1 = the sum of their V_0, S2 = the sum of the squares, lo and hi --, everything in unsigned
+// 64 bits: D = m S2 - S1^2 < 2^43, x = k4^2 D < 2^59, R = ceil(sqrt(x)) by a double estimate and an integer fix-up that makes it exact
+// (R < 2^30, so (R + 1)^2 < 2^61); the quotients by m are of numbers below 2^23.  The same source
+// on host and device; rtsh_moments_clamp_bounds exports it.
+RTS_HD void momentsClampBounds(uint32_t m, uint64_t S1, uint64_t S2, uint32_t lo, uint32_t hi, uint32_t k4, uint32_t margin, uint32_t* Lv,
+                               uint32_t* Hv) {
+    const uint64_t D = (uint64_t)m * S2 - S1 * S1;
+    const uint64_t xx = (uint64_t)(k4 * k4) * D;
+    // (double)x misses x by at most 2^-53 of it and the root of that by less than 2^-22 for x < 2^62, so the estimate's integer part is
+    // isqrt(x) or one beside it: one step down and one step up make it exact, as in momentsQuotient.  NO LOOP: a loop here would
+    // not end for an x near 2^64, which only parts that no window gives (m * S2 < S1^2) can produce -- a kernel must end anyway.
+    uint64_t R = (uint64_t)__builtin_sqrt((double)xx);
+    if (R * R > xx) --R;
+    if ((R + 1u) * (R + 1u) <= xx) ++R;                                                            // R = isqrt(x)
+    if (R * R < xx) ++R;                                                                           // ... its ceiling
+    const uint64_t Rc = (R + 3u) / 4u;
+    const uint64_t A = S1 > Rc ? S1 - Rc : 0u, B = S1 + Rc;
+    const uint64_t mlo = (uint64_t)m * lo, mhi = (uint64_t)m * hi;
+    const uint32_t Lm = (uint32_t)(mlo > A ? mlo : A), Hm = (uint32_t)(mhi < B ? mhi : B);         // both at most m * hi < 2^23
+    const uint32_t lv = Lm / m, hv = (Hm + m - 1u) / m;                                            // rounded OUTWARD
+    const uint64_t top = (uint64_t)hv + margin;
+    *Lv = lv > margin ? lv - margin : 0u;
+    *Hv = top < 65535u ? (uint32_t)top : 65535u;
+}
+
+// `Frames` of the clamped instantiation also gives  void box(l, x, y, uint32_t* Lv, uint32_t* Hv): Lv' and Hv' of the pixel's window for
+// light l (the host twin loops over the window and calls momentsClampBounds; the kernel reads what it staged).  It is asked only at a
+// blended pair, whose centre contributes: m >= 1.  Compiled in by the switch alone -- the other instantiations are the text they were.
+template <bool Motion = false, bool Clamped = false, class Frames>
 RTS_HD void accumulateMomentsPixel(const MomentsList& g, const Frames& t, int x, int y, int W, int H) {
     const TemporalList& f = g.t;
     const V3 np = t.normal(x, y);
@@ -737,6 +766,14 @@ RTS_HD void accumulateMomentsPixel(const MomentsList& g, const Frames& t, int x,
         uint32_t out1 = cur1, out2 = cur2;
         if (n != 1u) {
             const uint32_t den = n * sw;                                                           // <= 255 * 1024
+            if constexpr (Clamped) {
+                uint32_t lv, hv;
+                t.box(l, x, y, &lv, &hv);
+                const uint64_t lo1 = (uint64_t)sw * lv, hi1 = (uint64_t)sw * hv;                   // sw * Hv'^2 <= 2^10 * 2^32
+                const uint64_t lo2 = (uint64_t)sw * (uint64_t)(lv * lv), hi2 = (uint64_t)sw * (uint64_t)(hv * hv);
+                s1 = s1 < lo1 ? lo1 : (s1 > hi1 ? hi1 : s1);
+                s2 = s2 < lo2 ? lo2 : (s2 > hi2 ? hi2 : s2);
+            }
             out1 = (uint32_t)momentsQuotient(2u * ((uint64_t)(n - 1u) * s1 + (uint64_t)sw * cur1) + den, 2u * den);
             out2 = (uint32_t)momentsQuotient(2u * ((uint64_t)(n - 1u) * s2 + (uint64_t)sw * cur2) + den, 2u * den);
         }

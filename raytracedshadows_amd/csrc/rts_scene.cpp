@@ -1192,6 +1192,96 @@ extern "C" int rtsh_accumulate_moments_soft_light_list_motion(const rts_soft_lig
     return RTS_OK;
 }
 
+// ---- the clamped forms of the moments pass (include/rts_scene.h): accumulateMomentsPixel<Motion, true> ----
+namespace rts_harness {
+// The clamp's own refusals, beside makeMomentsList's: shared by the host and device forms.
+int checkMomentsClamp(const rtsh_moments_clamp* clamp) {
+    return (!clamp || clamp->radius > (uint32_t)RTSH_MOMENTS_CLAMP_MAX_RADIUS || clamp->sigma_k4 > 255u || clamp->margin > 65535u)
+               ? RTS_ERR_INVALID_ARG : RTS_OK;
+}
+
+namespace {
+// The frames with the clamp's box: a straight loop over the window, then the bounds from its five integers.
+template <class Base>
+struct ClampedMomentsOf : Base {
+    const uint32_t *samples, *scale;
+    int W_, H_, radius;
+    uint32_t k4, margin;
+    void box(uint32_t l, int x, int y, uint32_t* Lv, uint32_t* Hv) const {
+        uint32_t m = 0, lo = 65535u, hi = 0u;
+        uint64_t S1 = 0, S2 = 0;
+        for (int qy = y - radius; qy <= y + radius; ++qy)
+            for (int qx = x - radius; qx <= x + radius; ++qx) {
+                if (qx < 0 || qx >= W_ || qy < 0 || qy >= H_) continue;
+                if (isBackground(Base::normal(qx, qy)) || !((Base::bits(qx, qy) >> l) & 1u)) continue;
+                const uint32_t v = wideFilterInput(Base::count(l, qx, qy), samples[l], scale[l]);
+                ++m;
+                S1 += v;
+                S2 += (uint64_t)(v * v);
+                lo = v < lo ? v : lo;
+                hi = v > hi ? v : hi;
+            }
+        momentsClampBounds(m, S1, S2, lo, hi, k4, margin, Lv, Hv);                    // (m >= 1: asked at blended pairs only)
+    }
+};
+} // namespace
+} // namespace rts_harness
+
+extern "C" void rtsh_moments_clamp_bounds(uint32_t m, uint64_t S1, uint64_t S2, uint32_t lo, uint32_t hi, uint32_t sigma_k4, uint32_t margin,
+                                          uint32_t* Lv, uint32_t* Hv) {
+    if (!Lv || !Hv) return;
+    *Lv = 0u;
+    *Hv = 65535u;
+    // outside the widths of the rule (no window gives such parts): no box.  Inside them x < 2^62 and every step stays in 64 bits.
+    if (m == 0u || m > 81u || sigma_k4 > 255u || hi > 65535u || lo > hi || S1 >= (1ull << 23) || S2 >= (1ull << 39)) return;
+    if ((uint64_t)m * S2 < S1 * S1) return;
+    momentsClampBounds(m, S1, S2, lo, hi, sigma_k4, margin, Lv, Hv);
+}
+
+extern "C" int rtsh_accumulate_moments_soft_light_list_clamped(const rts_soft_light_list* list, const rtsh_temporal_params* params,
+                                                               const float* positions, const float* normals, const uint8_t* lights_map,
+                                                               const uint8_t* counts, const float* prev_positions, const float* prev_normals,
+                                                               const uint16_t* prev_mean, const uint32_t* prev_square,
+                                                               const uint8_t* prev_lengths, uint32_t W, uint32_t H, uint16_t* mean_out,
+                                                               uint32_t* square_out, uint8_t* lengths_out, const rtsh_moments_clamp* clamp,
+                                                               int threads) {
+    MomentsList f;
+    int s = makeMomentsList(list, params, positions, normals, counts, prev_positions, prev_normals, prev_mean, prev_square, prev_lengths, W, H,
+                            mean_out, square_out, lengths_out, &f);
+    if (s == RTS_OK) s = checkMomentsClamp(clamp);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const ClampedMomentsOf<MomentsFrames> t{ { positions, normals, prev_positions, prev_normals, lights_map, counts, prev_lengths, prev_mean,
+                                               prev_square, mean_out, square_out, lengths_out, W, n },
+                                             f.samples, f.scale, (int)W, (int)H, (int)clamp->radius, clamp->sigma_k4, clamp->margin };
+    parallelFor(n, 256, threads, [&](size_t i) { accumulateMomentsPixel<false, true>(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H); });
+    return RTS_OK;
+}
+
+extern "C" int rtsh_accumulate_moments_soft_light_list_clamped_motion(const rts_soft_light_list* list, const rtsh_temporal_params* params,
+                                                                      const float* positions, const float* normals,
+                                                                      const uint8_t* lights_map, const uint8_t* counts,
+                                                                      const float* prev_positions, const float* prev_normals,
+                                                                      const uint16_t* prev_mean, const uint32_t* prev_square,
+                                                                      const uint8_t* prev_lengths, const float* prev_points,
+                                                                      const float* prev_point_normals, uint32_t W, uint32_t H,
+                                                                      uint16_t* mean_out, uint32_t* square_out, uint8_t* lengths_out,
+                                                                      const rtsh_moments_clamp* clamp, int threads) {
+    MomentsList f;
+    int s = makeMomentsList(list, params, positions, normals, counts, prev_positions, prev_normals, prev_mean, prev_square, prev_lengths, W, H,
+                            mean_out, square_out, lengths_out, &f);
+    if (s == RTS_OK) s = checkMomentsClamp(clamp);
+    if (s == RTS_OK) s = checkMotionPlanes(f.t.history, prev_points, prev_point_normals);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const ClampedMomentsOf<MotionMomentsFrames> t{ { { positions, normals, prev_positions, prev_normals, lights_map, counts, prev_lengths,
+                                                       prev_mean, prev_square, mean_out, square_out, lengths_out, W, n },
+                                                     prev_points, prev_point_normals },
+                                                   f.samples, f.scale, (int)W, (int)H, (int)clamp->radius, clamp->sigma_k4, clamp->margin };
+    parallelFor(n, 256, threads, [&](size_t i) { accumulateMomentsPixel<true, true>(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H); });
+    return RTS_OK;
+}
+
 // ---- the guided wide filter with a temporal threshold (include/rts_scene.h; per-pixel rule in rts_closest_hit.h:
 // wideGuideTemporalThresholdPixel, wideGuidedPassPixel) ----
 namespace rts_harness {

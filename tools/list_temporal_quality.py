@@ -47,7 +47,20 @@ room's open front (MOVE_EYE, MOVE_TARGET), the
 light of 3 % and 10 % of the diagonal; the tall box is translated by MOVE_STEP per frame and the stream refitted (api.bvh_refit of one
 build).  Every frame traces 4 jittered samples; the raw (R = 0) visibility is accumulated (max_length 32) by the plain pass and by the
 motion pass.  After 4, 8 and 12 frames: the mean absolute difference to the 48-sample trace of THAT frame's geometry, and the mean
-history length, over the active pixels of the MOVED object (prev_points.w == 2) and over the rest; "raw" is that frame's count / 4."""
+history length, over the active pixels of the MOVED object (prev_points.w == 2) and over the rest; "raw" is that frame's count / 4.
+
+    python tools/list_temporal_quality.py --jump --moments [--out profiles/r35/list_moments_clamp_quality.jsonl]
+    python tools/list_temporal_quality.py --move --moments [--out ...]
+
+The clamp of the moments' history (rtsh_accumulate_moments_soft_light_list_clamped*): the moments column set of the two
+protocols above, cornell_128, lights of 3 % and 10 % of the diagonal.  --jump: the light stands for JUMP_AT frames, jumps and stands for
+AFTER more; --move: the box moves every frame for JUMP_AT + AFTER frames and the error is taken over the REST pixels (the static
+receivers, prev_points.w != 2) of the last AFTER frames.  Each also as a STILL scene (no jump, no move), where a clamp can only cost.
+Per frame the mean absolute difference to the 48-sample trace of three quantities: "mean" the accumulated mean plane unfiltered,
+"unguided" and "k4_12" the mean-input filters of 4.28 at two passes.  Columns: "unclamped"; "clamp_R_K4" for R in 1, 2, 4 and sigma_k4 in
+4, 8, 36, margin 0; "reset" (reset_lights on the frame of the jump; --jump only); "single" one frame alone (max_length 1); and as
+bases "float_clamp_1", 4.24's clamp at r = 1 over the raw float visibility.  "scatter" is the largest minus the smallest unclamped
+error of the STILL scene over its last AFTER frames: the frame-to-frame noise a difference has to exceed."""
 import argparse
 import json
 import os
@@ -225,6 +238,87 @@ def move_rows():
     return rows
 
 
+MOMENTS_CLAMPS = [(r, k4) for r in (1, 2, 4) for k4 in (4, 8, 36)]
+
+
+def moments_rows(protocol):
+    """The moments column set of --jump and --move; see the module text."""
+    from raytracedshadows_amd import api, scenes
+    rows = []
+    sc, W, H = scenes.cornell(), 128, 128
+    faces = np.ascontiguousarray(sc.faces, np.uint32)
+    idx, P = np.ascontiguousarray(faces.reshape(-1)), faces.shape[0]
+    box = np.unique(faces[640:832])
+    base = np.ascontiguousarray(sc.verts, np.float64)
+    built = api.BVHBuilder().build(np.ascontiguousarray(base, np.float32), 3, idx, P).m_packedNodes
+    if protocol == "move":
+        sc.eye, sc.target, sc.fovy = np.array(MOVE_EYE, np.float32), np.array(MOVE_TARGET, np.float32), 0.9
+    k = api.RayTracingConstants.make(sc.eye, sc.light_direction, W, H)
+    diag = float(np.linalg.norm(np.asarray(sc.bbox_max, np.float64) - np.asarray(sc.bbox_min, np.float64)))
+    table = scenes.jitter_offsets(48, 1.0, 19)
+    cam = (sc.eye, sc.target, sc.fovy)
+    eps = 0.005 * diag
+    total = JUMP_AT + AFTER
+    jumped = tuple(float(v) for v in np.asarray(sc.light_point, np.float64) + np.array([JUMP * diag, 0.0, 0.0]))
+    modes = ["unclamped"] + [f"clamp_{r}_{k4}" for r, k4 in MOMENTS_CLAMPS] + (["reset"] if protocol == "jump" else []) + ["single", "float_clamp_1"]
+    for radius in (0.03, 0.1):
+        light = lambda at, n, t=table: api.SoftLightList.make([(api.Light.POINT, at, n, 0, radius * diag)], t)
+        still_unclamped = None
+        for scenario in ("still", protocol):
+            frames, prev_stream = [], None
+            for frame in range(total):
+                at = jumped if scenario == "jump" and frame >= JUMP_AT else tuple(sc.light_point)
+                verts = base.copy()
+                if scenario == "move":
+                    verts[box] += np.asarray(MOVE_STEP) * frame
+                packed = api.bvh_refit(built, np.ascontiguousarray(verts, np.float32), 3, idx, P)
+                pos, nrm, pts, pnr, _, _ = api.primary_gbuffer_motion(packed, packed if prev_stream is None else prev_stream, sc.eye, sc.eye,
+                                                                      sc.target, sc.fovy, W, H, want_leaves=False)
+                lst = light(at, 4, np.ascontiguousarray(np.roll(table, -frame, axis=0)))
+                facing = api.facing_lights(k, lst.hard_list(), pos, nrm)
+                counts = api.soft_light_list_adaptive(packed, k, lst, (2,), pos, W, H, facing, want_refined=False, tables=(48,))[0]
+                where = truth = None
+                if frame >= JUMP_AT:
+                    where = ((facing & 1) != 0) & ((pts[..., 3] != 2) if protocol == "move" else True)
+                    truth = api.soft_light_list(packed, k, light(at, 48), pos, W, H, facing)[0].astype(np.float32) / np.float32(48)
+                frames.append((lst, facing, counts, pos, nrm, pts, pnr, where, truth))
+                prev_stream = packed
+            row = {"protocol": protocol, "scenario": scenario, "scene": "cornell_128", "light": radius, "jump_at": JUMP_AT, "max_length": 32,
+                   "error": {}}
+            for mode in modes:
+                hist, prev_g, errors = None, None, {"mean": [], "unguided": [], "k4_12": []}
+                for frame, (lst, facing, counts, pos, nrm, pts, pnr, where, truth) in enumerate(frames):
+                    reset = 1 if mode == "reset" and scenario == "jump" and frame == JUMP_AT else 0
+                    tp = api.TemporalParams.from_cameras(cam, cam, W, H, 0.9, eps, 1 if mode == "single" else 32, reset)
+                    prev = None if hist is None else prev_g + hist
+                    motion = (pts, pnr) if protocol == "move" else None
+                    mad = lambda v: round(float(np.abs(v[where] - truth[where]).mean()), 5)
+                    if mode == "float_clamp_1":
+                        vis = api.filter_soft_light_list(lst, api.FilterParams.make(0, 0.9, eps), pos, nrm, counts, facing)
+                        hist = api.accumulate_visibility_list(lst.hard_list(), tp, pos, nrm, vis, prev, facing, clamp=api.HistoryClamp.make(1),
+                                                              motion=motion)
+                        if frame >= JUMP_AT:
+                            errors["mean"].append(mad(hist[0][0]))
+                    else:
+                        clamp = api.MomentsClamp.make(int(mode.split("_")[1]), int(mode.split("_")[2]), 0) if mode.startswith("clamp") else None
+                        hist = api.accumulate_moments_soft_light_list(lst, tp, pos, nrm, counts, prev, facing, motion=motion, clamp=clamp)
+                        if frame >= JUMP_AT:
+                            errors["mean"].append(mad(api.wide_filter_mean_soft_light_list(lst, api.WideFilterParams.make(0, 0.9, eps), pos, nrm,
+                                                                                           hist[0], facing)[0]))
+                            errors["unguided"].append(mad(api.wide_filter_mean_soft_light_list(
+                                lst, api.WideFilterParams.make(GUIDE_PASSES, 0.9, eps), pos, nrm, hist[0], facing)[0]))
+                            errors["k4_12"].append(mad(api.wide_filter_guided_temporal_mean_soft_light_list(
+                                lst, api.WideGuideTemporalParams.make(GUIDE_PASSES, 12, GUIDE_MIN_HISTORY, 0.9, eps), pos, nrm, counts, hist, facing)[0]))
+                    prev_g = (pos, nrm)
+                row["error"][mode] = {q: v for q, v in errors.items() if v}
+            if scenario == "still":
+                still_unclamped = row["error"]["unclamped"]
+            row["scatter"] = {q: round(max(v) - min(v), 5) for q, v in still_unclamped.items()}
+            rows.append(row)
+            print(json.dumps(row))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
@@ -232,8 +326,17 @@ def main():
     ap.add_argument("--guide-history", action="store_true", help="the temporal guide of the wide filter against the unguided filter and 4.26's guide")
     ap.add_argument("--mean-input", action="store_true", help="--guide-history's table with the mean-input filters' three columns beside it")
     ap.add_argument("--move", action="store_true", help="the plain and the motion accumulate over a box translated and refitted every frame")
+    ap.add_argument("--moments", action="store_true", help="with --jump or --move: the moments column set of the clamped moments pass")
     args = ap.parse_args()
     from raytracedshadows_amd import api, scenes
+    if args.moments and (args.jump or args.move):
+        rows = (moments_rows("jump") if args.jump else []) + (moments_rows("move") if args.move else [])
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                for row in rows:
+                    f.write(json.dumps(row) + "\n")
+        return
     rows = move_rows() if args.move else jump_rows() if args.jump else (guide_rows(args.mean_input) if args.guide_history or args.mean_input else [])
     if args.move or args.jump or args.guide_history or args.mean_input:
         if args.out:

@@ -3,7 +3,7 @@
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
                            [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]
                                           [--filter R [--spread S] | --filter-passes K [--filter-guide K4 [--guide-history M]]] [--plane-eps E] [--normal-cos C]
-                                                      [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]] [--move SPEC]]]]
+                                                      [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]] [--moments-clamp R[:K4[:MARGIN]]] [--move SPEC]]]]
 
 --temporal F (with --soft-list N --filter R): F frames are rendered -- trace, filter, rtsh_accumulate_visibility_list_device with
 ping-pong history -- and the LAST frame is lit from the accumulated visibility.  Frame k traces with the shared offsets table rotated
@@ -16,6 +16,9 @@ visibility planes by rtsh_combine_visibility_list_device; with --distance the di
 --filter-passes K (in place of --filter R; the two exclude each other): the wide a-trous filter rtsh_wide_filter_soft_light_list_device,
 K = 0..5 passes of 5 x 5 taps 1, 2, 4, 8 and 16 pixels apart -- a reach of 2, 6, 14, 30, 62 pixels --, same thresholds, no distance
 guide; it feeds --temporal and --clamp exactly as --filter does.
+--moments-clamp R[:K4[:MARGIN]] (with --guide-history M or --filter-mean, also with --move): the count moments are accumulated by the
+clamped form (rtsh_accumulate_moments_soft_light_list_clamped_device or ..._clamped_motion_device): the history is
+clamped into this frame's (2R+1)^2 window, its [min, max] cut to mean +- K4/4 deviations (default 8), widened by MARGIN units of V_0.
 --guide-history M (with --filter-guide K4 and --temporal F): per frame the count moments are accumulated
 (rtsh_accumulate_moments_soft_light_list_device) and the guide takes its variance from them where a pixel has at least M frames of
 history (rtsh_wide_filter_guided_temporal_soft_light_list_device); without --temporal it has no meaning and is refused.
@@ -189,7 +192,7 @@ def parse_move(text, wl):
 
 
 def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, max_length, probe=0, table=0, colors="", clamp=None,
-                       filter_mean=False, move=""):
+                       filter_mean=False, move="", moments_clamp=None):
     """`frames` frames of a light list: per frame G-buffer, facing map, trace (the offsets table rotated by one entry per frame), filter
     and accumulation with ping-pong history; the last frame is lit from the accumulated visibility."""
     from raytracedshadows_amd import api, scenes
@@ -244,7 +247,7 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
         if with_moments:                                                 # this frame's count moments, then the filter they guide or feed
             api.accumulate_moments_soft_light_list_device(ctx, lights, tp, d_pos, d_nrm, d_counts, W, H, *moments[k % 2],
                                                           d_prev=None if k == 0 else gbuf[(k - 1) % 2] + moments[(k - 1) % 2], d_lights_map=d_map,
-                                                          d_motion=d_motion)
+                                                          d_motion=d_motion, clamp=moments_clamp)
         if filter_mean and temporal_guide:
             api.wide_filter_guided_temporal_mean_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, moments[k % 2], W, H, d_vis,
                                                                         d_scratch=d_scratch, d_lights_map=d_map)
@@ -262,7 +265,8 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
                                        colors=colors)
     ctx.synchronize()
     print(f"{frames} frames of {count} lights x {spp} samples, filter {filter_words(api, filt)}{' over the accumulated mean' if filter_mean else ''}, orbit {orbit_deg:g} degree per frame, "
-          f"max_length {max_length}{'' if clamp is None else f', history clamped at r = {clamp.radius}, margin {clamp.margin:g}'}: "
+          f"max_length {max_length}{'' if clamp is None else f', history clamped at r = {clamp.radius}, margin {clamp.margin:g}'}"
+          f"{'' if moments_clamp is None else f', moments clamped at r = {moments_clamp.radius}, sigma_k4 {moments_clamp.sigma_k4}, margin {moments_clamp.margin}'}: "
           f"{(time.time() - t0) * 1e3:.2f} ms (incl. first launches)")
     if moving:
         pts = np.zeros((H, W, 4), np.float32)
@@ -330,6 +334,10 @@ def main():
                     help="with --temporal: clamp the history into the current visibility's range over a window of (2R+1)^2 pixels, "
                          "R = 0..4 (rtsh_accumulate_visibility_list_clamped_device)")
     ap.add_argument("--clamp-margin", type=float, default=0.0, metavar="M", help="with --clamp: widen the range by M on both sides")
+    ap.add_argument("--moments-clamp", default="", metavar="R[:K4[:MARGIN]]",
+                    help="with --guide-history M or --filter-mean: accumulate the count moments by the clamped form "
+                         "(rtsh_accumulate_moments_soft_light_list_clamped*_device): window radius R = 0..4, sigma_k4 K4 = 0..255 (default 8), "
+                         "margin in units of V_0 (default 0)")
     ap.add_argument("--move", default="", metavar="AXIS:LO:HI:DX,DY,DZ",
                     help="with --temporal: displace the slab of the scene between the fractions LO and HI of its AXIS extent by (DX, DY, DZ) "
                          "per frame, refit, and drive the motion G-buffer pass and the motion forms of the accumulates (DESIGN.md 4.29)")
@@ -376,8 +384,20 @@ def main():
                 if args.clamp > 4 or not 0.0 <= args.clamp_margin < float("inf"):
                     sys.exit("render: --clamp R takes 0 <= R <= 4 and a finite --clamp-margin M >= 0")
                 clamp = api.HistoryClamp.make(args.clamp, args.clamp_margin) if args.clamp >= 0 else None
+                moments_clamp = None
+                if args.moments_clamp:
+                    try:
+                        parts = [int(v) for v in args.moments_clamp.split(":")]
+                    except ValueError:
+                        parts = []
+                    parts += [8, 0][len(parts) - 1:] if 1 <= len(parts) <= 3 else []
+                    if len(parts) != 3 or not (0 <= parts[0] <= 4 and 0 <= parts[1] <= 255 and 0 <= parts[2] <= 65535):
+                        sys.exit("render: --moments-clamp R[:K4[:MARGIN]] takes 0 <= R <= 4, 0 <= K4 <= 255 and 0 <= MARGIN <= 65535")
+                    if not (args.guide_history or args.filter_mean):
+                        sys.exit("render: --moments-clamp goes with --guide-history M or --filter-mean (where the moments pass runs)")
+                    moments_clamp = api.MomentsClamp.make(*parts)
                 return soft_list_temporal(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, filt, args.temporal, args.orbit,
-                                          args.max_length, args.adaptive, args.table, args.colors, clamp, args.filter_mean, args.move)
+                                          args.max_length, args.adaptive, args.table, args.colors, clamp, args.filter_mean, args.move, moments_clamp)
             return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance,
                              args.colors, filt)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
