@@ -505,7 +505,8 @@ int rtsh_wide_filter_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_l
  *     may be NULL when passes <= 1, and nothing of it is touched then.
  *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything rtsh_wide_filter_soft_light_list* refuse (d_visibility equal
  *     to the start of any of the three sets of d_scratch included); guide_k4 > 255; a NULL d_scratch with passes >= 2.
- *   * OUT OF SCOPE: variance propagated through the passes (T is the first pass's at every pass), a guide for the tent filter
+ *   * OUT OF SCOPE: ~~variance propagated through the passes~~ (T is the first pass's at every pass HERE; propagated:
+ *     rtsh_wide_filter_propagated_mean_soft_light_list below), a guide for the tent filter
  *     rtsh_filter_*_light_list*.  (A temporal variance from accumulated moments: rtsh_wide_filter_guided_temporal_soft_light_list
  *     below.) */
 enum { RTSH_WIDE_GUIDE_MAX_K4 = 255 };
@@ -593,7 +594,8 @@ int rtsh_accumulate_moments_soft_light_list_device(rts_ctx* ctx, const rts_soft_
  *     counted pixels only, each on its element type's alignment.
  *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the guided filter refuses; a NULL mean, square or lengths;
  *     min_history 0 or above 255.
- *   * OUT OF SCOPE: variance propagated through the passes, a guide for the tent filter, row ranges and stripes, hard
+ *   * OUT OF SCOPE: ~~variance propagated through the passes~~ (rtsh_wide_filter_propagated_mean_soft_light_list below, DESIGN.md
+ *     4.31), a guide for the tent filter, row ranges and stripes, hard
  *     lists.  (Filtering the accumulated mean plane in place of this frame's counts: rtsh_wide_filter_mean_soft_light_list and
  *     rtsh_wide_filter_guided_temporal_mean_soft_light_list below.) */
 typedef struct rtsh_wide_guide_temporal_params {
@@ -640,7 +642,7 @@ int rtsh_wide_filter_guided_temporal_soft_light_list_device(rts_ctx* ctx, const 
  *     a tap other than the centre is accepted for light l when geom(p, q) and on(q, l) hold and |V_k(q, l) - V_k(p, l)| <= T(p, l).
  *     T DOES NOT SHRINK WITH THE HISTORY'S LENGTH: it is the spread of one frame's V_0 about the mean, while the mean of m frames
  *     scatters by about 1 / sqrt(m) of that -- so at equal guide_k4 this form accepts more than the count-input form.  Dividing the
- *     variance by the length is out of scope (below).
+ *     variance by the length is out of scope HERE (below): by_length of rtsh_wide_filter_propagated_mean_soft_light_list does it.
  * ANCHORS: (1) Where mean[l][q] == min(c_l(q), n_l) * S_l at every active (pixel, light), both functions give bit for bit the planes of
  * their count-input counterparts (rtsh_wide_filter_soft_light_list*, rtsh_wide_filter_guided_temporal_soft_light_list*) for the same
  * inputs: first-frame moments are such a case, so is max_length 1.  (2) passes == 0 gives (float)min(mean, n S) / (float)(n S).
@@ -656,7 +658,8 @@ int rtsh_wide_filter_guided_temporal_soft_light_list_device(rts_ctx* ctx, const 
  *     third set for passes >= 2.
  *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the counterpart refuses, with mean in the place of counts;
  *     a NULL mean; d_visibility equal to the start of any scratch set (two for the unguided form, three for the guided one).
- *   * OUT OF SCOPE: variance divided by the history's length or propagated through the passes, (a clamp of the moments' history: the
+ *   * OUT OF SCOPE: ~~variance divided by the history's length or propagated through the passes~~ (both:
+ *     rtsh_wide_filter_propagated_mean_soft_light_list below), (a clamp of the moments' history: the
  *     clamped forms at the end of this header,) motion vectors, the tent filter, hard lists, row ranges and stripes, an LDS-staged form of the moments, and feeding the float visibility
  *     history of rtsh_accumulate_visibility_list to the a-trous passes (it is not fixed point). */
 int rtsh_wide_filter_mean_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_filter_params* params, const float* positions,
@@ -676,6 +679,76 @@ int rtsh_wide_filter_guided_temporal_mean_soft_light_list_device(rts_ctx* ctx, c
                                                                  const uint8_t* d_counts, const uint16_t* d_mean, const uint32_t* d_square,
                                                                  const uint8_t* d_lengths, uint32_t W, uint32_t H, float* d_visibility,
                                                                  uint16_t* d_scratch, void* stream);
+
+/* THE GUIDED MEAN FILTER WITH A PROPAGATED VARIANCE: rtsh_wide_filter_guided_temporal_mean_soft_light_list above with
+ * SVGF's second half -- a per-pixel VARIANCE plane is filtered along with the signal, Var' = sum w^2 Var / (sum w)^2, and the edge stop
+ * is re-derived from it at every pass, so the tolerance tightens as the signal gets cleaner.  Moments and tap weights are integers, so
+ * this is exact: host and device forms agree bit for bit.  Notation as above: n_l, S_l, V_0' = min(mean, n_l * S_l), geom, on, bg,
+ * b = {6, 4, 1}; "active pair" = a (pixel, light) with not bg(q) and on(q, l).
+ *   typedef struct rtsh_wide_guide_propagated_params: passes, normal_cos_min, plane_eps, guide_k4, min_history as in
+ *     rtsh_wide_guide_temporal_params; by_length 0 or 1; reserved_ (ignored).
+ *   R: at an active pair with lengths[l][q] >= min_history, R(q, l) = max(0, square[l][q] - mean[l][q]^2), from the UNCLAMPED planes.
+ *   Q_0(q, l), a uint32_t in V^2 units: R(q, l) where the history suffices -- R(q, l) / lengths[l][q] by integer division there if
+ *     by_length is set --; (V_0 * (n_l * S_l - V_0)) / n_l by integer division elsewhere, V_0 = min(c, n_l) * S_l from THIS frame's
+ *     count byte: the Bernoulli energy in the same units; 0 at an inactive pair.
+ *   T_0(p, l): with by_length == 0 the guided mean filter's T word for word -- E* = n_l * R in the temporal branch, V_0 * (n_l * S_l - V_0)
+ *     elsewhere, G and D over the 3 x 3 with weights {1, 2, 1} x {1, 2, 1}, no geom test,
+ *     T = min(65535, isqrt((guide_k4^2 * G) / (16 * D * n_l))).  With by_length == 1 the same expression with E* = n_l * Q_0 in the
+ *     temporal branch (the other branch keeps its E: n_l * Q_0 would round there).
+ *   PASS k, k = 0 .. passes - 1, VALUES: the guided filter's pass with T_k: taps 1 << k apart, the centre always accepted, another tap
+ *     where geom(p, q) and on(q, l) hold and |V_k(q, l) - V_k(p, l)| <= T_k(p, l); V_(k+1) = (2 * num + den) / (2 * den).
+ *   PASS k, VARIANCE: over EXACTLY the taps accepted for light l, the centre included, w = b[|dx|] * b[|dy|]:
+ *     numQ = sum of w^2 * Q_k(q, l), den = sum of w (the values' den), Q_(k+1)(p, l) = (2 * numQ + den^2) / (2 * den^2) by integer
+ *     division; 0 at an inactive pair.  sum of w^2 <= 70^2, so numQ < 2^45; den^2 <= 2^16: rtsh_wide_variance_step evaluates it, the
+ *     same source on host and device, without a 64-bit division.  The last pass writes no Q.
+ *   T_k(p, l) for k >= 1, formed by pass k before its taps: over the 3 x 3 ADJACENT pixels q (one pixel apart whatever k is) that are
+ *     inside the frame, not bg(q) and have on(q, l), weights {1, 2, 1} x {1, 2, 1}, no geom test, the centre always counts:
+ *     G_k = sum of w * Q_k(q, l) < 2^36, D_k = sum of w, T_k = rtsh_wide_guide_threshold(G_k, D_k, 1, guide_k4) =
+ *     min(65535, isqrt((guide_k4^2 * G_k) / (16 * D_k))): Q is the variance of V itself, so n_l leaves the divisor.  0 where l is not
+ *     on at p.
+ *   ONE-SAMPLE LIGHTS: n_l <= 1 gives T = 65535 at every pass; that light's Q is never read and is written as 0.
+ *   OUTPUT: visibility[l * W * H + p] = (float)V_passes / (float)(n_l * S_l), formed by the last pass; passes == 0 converts V_0'.
+ * ANCHORS: (1) passes <= 1 with by_length == 0 gives rtsh_wide_filter_guided_temporal_mean_soft_light_list's plane bit for bit.
+ * (2) guide_k4 == 0 gives the passes == 0 plane of every light with n_l >= 2.  (3) A light with n_l <= 1 gives
+ * rtsh_wide_filter_mean_soft_light_list's plane.  (4) RANGE: every V_(k+1)(p) lies between the smallest and the largest accepted V_k,
+ * and visibility stays in [0, 1] whatever the planes hold.  (5) Q_(k+1)(p) is at most the largest accepted Q_k (sum w^2 <= (sum w)^2),
+ * and a pixel that accepts only its centre keeps its Q exactly (1296 Q / 36^2).  (6) Where lengths >= min_history and
+ * square == mean^2 hold at every active pair, every Q and every T is 0 and every pixel keeps its own quotient through every pass.
+ * (7) by_length == 1 with every counted length equal to 1 gives the by_length == 0 bits.
+ *   * argument lists: rtsh_wide_filter_guided_temporal_mean_soft_light_list*'s, with `void* d_scratch` in the device form.  Buffers,
+ *     lights_map, alignment, threads, stream as there; planes from `count` up are never touched.
+ *   * d_scratch: rtsh_wide_filter_propagated_scratch_bytes(count, W, H) = 12 * count * W * H bytes, aligned to 4: two ping-pong sets of
+ *     count uint16_t planes, then -- 4 * count * W * H bytes in, a multiple of 4 -- two ping-pong sets of count uint32_t planes of Q.
+ *     There is no plane of T: each pass recomputes T_k.  Pass k < passes - 1 writes V_(k+1) and Q_(k+1) to sets k & 1.  It may be NULL
+ *     when passes <= 1, and nothing of it is touched then.
+ *   * under graph capture a device call adds exactly max(1, passes) KERNEL nodes on one chain, list and parameters by value.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the guided mean filter refuses; by_length > 1; a d_scratch that
+ *     is not a multiple of 4; d_visibility equal to the start of any of the four sets of d_scratch.
+ *   * OUT OF SCOPE: the count-input form (a caller without history passes first-frame moments: anchor 1 of the mean family), the tent
+ *     filter, hard lists, row ranges and stripes, the effective sample count of an exponential history (lengths is capped at
+ *     max_length, and by_length divides by that). */
+typedef struct rtsh_wide_guide_propagated_params {
+    uint32_t passes;          /* 0 .. RTSH_WIDE_FILTER_MAX_PASSES (5) */
+    float    normal_cos_min;  /* a tap needs N_p . N_q >= this */
+    float    plane_eps;       /* ... and |N_p . (P_q - P_p)| <= this (world units) */
+    uint32_t guide_k4;        /* the tolerance in quarter standard deviations, 0 .. RTSH_WIDE_GUIDE_MAX_K4 (255) */
+    uint32_t min_history;     /* 1 .. 255: a pixel of at least this many frames of history gives its temporal variance */
+    uint32_t by_length;       /* 0, or 1: the temporal variance is divided by the history's length (the variance OF THE MEAN) */
+    uint32_t reserved_[2];    /* ignored */
+} rtsh_wide_guide_propagated_params;                                               /* 32 bytes */
+/* 12 * count * W * H: the bytes of d_scratch; 0 where count is outside 1 .. 8 or W or H is 0. */
+size_t rtsh_wide_filter_propagated_scratch_bytes(uint32_t count, uint32_t W, uint32_t H);
+/* Q_(k+1) of the rule above from its parts (1 <= den <= 256, numQ <= den^2 * (2^32 - 1)); 0xFFFFFFFF outside that domain. */
+uint32_t rtsh_wide_variance_step(uint64_t numQ, uint32_t den);
+int rtsh_wide_filter_propagated_mean_soft_light_list(const rts_soft_light_list* list, const rtsh_wide_guide_propagated_params* params,
+                                                     const float* positions, const float* normals, const uint8_t* lights_map,
+                                                     const uint8_t* counts, const uint16_t* mean, const uint32_t* square,
+                                                     const uint8_t* lengths, uint32_t W, uint32_t H, float* visibility, int threads);
+int rtsh_wide_filter_propagated_mean_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list,
+                                                            const rtsh_wide_guide_propagated_params* params, const float* d_positions,
+                                                            const float* d_normals, const uint8_t* d_lights_map, const uint8_t* d_counts,
+                                                            const uint16_t* d_mean, const uint32_t* d_square, const uint8_t* d_lengths,
+                                                            uint32_t W, uint32_t H, float* d_visibility, void* d_scratch, void* stream);
 
 /* OBJ ingest.  rtsh_obj_load parses `path` and expands it to the reference's flat
  * Vertex stream: 8 floats per vertex (position.xyz, normal.xyz, texcoord.uv), indices[i] = i.

@@ -252,6 +252,22 @@ class WideGuideTemporalParams(C.Structure):
         return p
 
 
+class WideGuidePropagatedParams(C.Structure):
+    """``rtsh_wide_guide_propagated_params``: ``WideGuideTemporalParams`` plus ``by_length`` (0 or 1): the temporal variance is divided
+    by the history's length before it is carried through the passes."""
+    _fields_ = [("passes", C.c_uint32), ("normal_cos_min", C.c_float), ("plane_eps", C.c_float), ("guide_k4", C.c_uint32),
+                ("min_history", C.c_uint32), ("by_length", C.c_uint32), ("reserved_", C.c_uint32 * 2)]
+    MAX_PASSES = 5
+    MAX_K4 = 255
+
+    @classmethod
+    def make(cls, passes, guide_k4=12, min_history=4, by_length=0, normal_cos_min=0.9, plane_eps=0.05):
+        p = cls()
+        p.passes, p.guide_k4, p.min_history, p.by_length = passes, guide_k4, min_history, by_length
+        p.normal_cos_min, p.plane_eps = np.float32(normal_cos_min), np.float32(plane_eps)
+        return p
+
+
 class TemporalParams(C.Structure):
     """``rtsh_temporal_params``: the camera motion (current eye minus previous eye, the previous camera's basis and scales), the two
     geometry thresholds, the longest history (1..255) and the lights that take no history this frame (a bit per light)."""
@@ -628,6 +644,13 @@ _sig("rtsh_wide_filter_guided_temporal_mean_soft_light_list", C.c_int, C.POINTER
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
 _sig("rtsh_wide_filter_guided_temporal_mean_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList),
      C.POINTER(WideGuideTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_wide_filter_propagated_scratch_bytes", C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32)
+_sig("rtsh_wide_variance_step", C.c_uint32, C.c_uint64, C.c_uint32)
+_sig("rtsh_wide_filter_propagated_mean_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(WideGuidePropagatedParams),
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_wide_filter_propagated_mean_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList),
+     C.POINTER(WideGuidePropagatedParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
      C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_facing_active", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
      C.c_void_p)
@@ -2149,6 +2172,45 @@ def wide_filter_guided_temporal_mean_soft_light_list_device(ctx, lights, params,
                                                                              width, height, C.c_void_p(d_visibility),
                                                                              C.c_void_p(d_scratch or 0), C.c_void_p(stream or 0)),
            "rtsh_wide_filter_guided_temporal_mean_soft_light_list_device")
+
+
+def wide_filter_propagated_scratch_bytes(count, width, height):
+    """The bytes of ``d_scratch`` of the propagated filter's device form (rtsh_wide_filter_propagated_scratch_bytes): 12 * count * width *
+    height -- two ping-pong sets of uint16 values, then two of uint32 variance."""
+    return int(_lib.rtsh_wide_filter_propagated_scratch_bytes(count, width, height))
+
+
+def wide_variance_step(num_q, den):
+    """``Q_(k+1) = (2 * num_q + den^2) // (2 * den^2)`` as host twin and kernels evaluate it (rtsh_wide_variance_step)."""
+    return int(_lib.rtsh_wide_variance_step(int(num_q), int(den)))
+
+
+def wide_filter_propagated_mean_soft_light_list(lights, params, positions, normals, counts, moments, lights_map=None, threads=0):
+    """The guided mean filter with a variance plane carried through the passes, on the host
+    (rtsh_wide_filter_propagated_mean_soft_light_list): ``float32[count, H, W]`` visibility.  ``params`` a
+    ``WideGuidePropagatedParams``; the other arguments as for ``wide_filter_guided_temporal_mean_soft_light_list``."""
+    name = "rtsh_wide_filter_propagated_mean_soft_light_list"
+    positions, normals, counts, lights_map, (mean, square, lengths), W, H, visibility = _wide_filter_frame(
+        name, lights, positions, normals, counts, np.uint8, lights_map, moments=moments)
+    _check(_lib.rtsh_wide_filter_propagated_mean_soft_light_list(_ref(lights), _ref(params), _ptr_or_none(positions), _ptr(normals),
+                                                                 _ptr_or_none(lights_map), _ptr(counts), _ptr(mean), _ptr(square),
+                                                                 _ptr(lengths), W, H, _ptr(visibility), threads), name)
+    return visibility
+
+
+def wide_filter_propagated_mean_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_counts, d_moments, width, height,
+                                                       d_visibility, d_scratch=None, d_lights_map=None, stream=None):
+    """The propagated filter on the GPU: arguments as for ``wide_filter_guided_temporal_mean_soft_light_list_device``; d_scratch =
+    ``wide_filter_propagated_scratch_bytes(count, width, height)`` bytes on a 4-byte boundary (None allowed for passes <= 1);
+    max(1, passes) kernels, asynchronous."""
+    m = tuple(d_moments)
+    _check(_lib.rtsh_wide_filter_propagated_mean_soft_light_list_device(ctx.handle, _ref(lights), _ref(params),
+                                                                        C.c_void_p(d_positions or 0), C.c_void_p(d_normals),
+                                                                        C.c_void_p(d_lights_map or 0), C.c_void_p(d_counts or 0),
+                                                                        C.c_void_p(m[0] or 0), C.c_void_p(m[1] or 0), C.c_void_p(m[2] or 0),
+                                                                        width, height, C.c_void_p(d_visibility),
+                                                                        C.c_void_p(d_scratch or 0), C.c_void_p(stream or 0)),
+           "rtsh_wide_filter_propagated_mean_soft_light_list_device")
 
 
 def write_ppm(path, rgb):

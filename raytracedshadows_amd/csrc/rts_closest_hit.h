@@ -909,6 +909,197 @@ RTS_HD void wideGuideTemporalMeanThresholdPixel(const WideFilterList& f, uint32_
     }
 }
 
+// The GUIDED MEAN FILTER WITH A PROPAGATED VARIANCE (include/rts_scene.h, rtsh_wide_filter_propagated_mean_soft_light_list; DESIGN.md
+// 4.31): the guided mean filter above with a per-pixel variance plane Q_k (uint32_t, V^2 units) carried from pass to pass, and the
+// threshold re-derived from it at every pass.  Everything here is NEW TEXT -- no function above is edited, so every kernel that calls
+// one keeps its instruction text.  `Variance` gives Q_k by pixel coordinates: uint32_t variance(x, y, l), asked only at a pair that is
+// inside the frame, not background and on, of a light with n_l >= 2.
+struct WidePropagatedRule { uint32_t k4, minHistory, byLength; };
+
+// Q_(k+1) = (2 * numQ + den^2) / (2 * den^2) for numQ < 2^45 and 1 <= den <= 256: 2 * numQ + den^2 < 2^46, 2 * den^2 <= 2^17.
+RTS_HD uint32_t wideVarianceStep(uint64_t numQ, uint32_t den) {
+    const uint32_t d2 = den * den;
+    return (uint32_t)momentsQuotient(2u * numQ + d2, 2u * d2);
+}
+
+// Q_0 of an active pair (i: its index into the planes): R, R / lengths, or this frame's Bernoulli energy over n_l.
+RTS_HD uint32_t wideVarianceInput(const WideFilterList& f, const WidePropagatedRule& r, const GuideMomentsCounts& h, uint64_t i, uint32_t l) {
+    const uint32_t len = h.m.lengths[i];
+    if (len >= r.minHistory) {                                                   // (minHistory >= 1: len != 0)
+        const uint64_t mean = h.m.mean[i], square = h.m.square[i];
+        const uint32_t R = square > mean * mean ? (uint32_t)(square - mean * mean) : 0u;
+        return r.byLength ? R / len : R;
+    }
+    const uint32_t v = wideFilterInput(h.counts[i], f.samples[l], f.scale[l]);
+    return (v * (f.samples[l] * f.scale[l] - v)) / f.samples[l];                 // c (n - c) S^2 / n
+}
+
+// Q_k where a pass reads it: Q_0 formed from the moments (planes == NULL: the first pass), else the previous pass's planes.
+struct WideVarianceGlobal {
+    const WideFilterList& f;
+    WidePropagatedRule r;
+    GuideMomentsCounts h;
+    const uint32_t* planes;
+    RTS_HD uint32_t variance(int x, int y, uint32_t l) const {
+        const uint64_t i = h.m.at(x, y, l);
+        return planes ? planes[i] : wideVarianceInput(f, r, h, i, l);
+    }
+};
+
+// T_0: wideGuideTemporalMeanThresholdPixel's statements with E* = n_l * (R / lengths) in the temporal branch where byLength is set;
+// with byLength == 0 it is that function's expression value for value.
+template <class Texels>
+RTS_HD void widePropagatedFirstThresholdPixel(const WideFilterList& f, const WidePropagatedRule& r, const Texels& t, const GuideMomentsCounts& h,
+                                              int x, int y, int W, int H, uint32_t* T8) {
+    const uint32_t onp = isBackground(t.normal(x, y)) ? 0u : (t.bits(x, y) & ((1u << f.count) - 1u));
+    uint32_t nb[9];                                                              // the map bits of the nine pixels that count
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 9; ++j) {
+        const int qx = x + j % 3 - 1, qy = y + j / 3 - 1;
+        nb[j] = 0u;
+        if (onp == 0u || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+        nb[j] = j == 4 ? onp : (isBackground(t.normal(qx, qy)) ? 0u : t.bits(qx, qy));
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        T8[l] = 0u;
+        if (!((onp >> l) & 1u)) continue;
+        T8[l] = 65535u;
+        if (f.samples[l] < 2u) continue;
+        const uint32_t full = f.samples[l] * f.scale[l];                         // n_l * S_l
+        uint64_t G = 0;
+        uint32_t D = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < 9; ++j) {
+            if (!((nb[j] >> l) & 1u)) continue;
+            const int qx = x + j % 3 - 1, qy = y + j / 3 - 1;
+            const uint32_t w = (j % 3 == 1 ? 2u : 1u) * (j / 3 == 1 ? 2u : 1u);
+            const uint64_t i = h.m.at(qx, qy, l);
+            const uint32_t len = h.m.lengths[i];
+            uint64_t E;
+            if (len >= r.minHistory) {
+                const uint64_t mean = h.m.mean[i], square = h.m.square[i];
+                const uint32_t R = square > mean * mean ? (uint32_t)(square - mean * mean) : 0u;
+                E = (uint64_t)f.samples[l] * (uint64_t)(r.byLength ? R / len : R);                 // n_l * Q_0
+            } else {
+                const uint32_t v = wideFilterInput(h.counts[i], f.samples[l], f.scale[l]);         // V_0 of THIS frame's count
+                E = (uint64_t)(v * (full - v));                                  // E = c (n - c) S^2 < 2^30
+            }
+            G += (uint64_t)w * E;
+            D += w;
+        }
+        T8[l] = wideGuideThreshold(G, D, f.samples[l], r.k4);
+    }
+}
+
+// T_k for k >= 1, formed by pass k before its taps: G_k = sum of w * Q_k(q) < 2^36 over the 3 x 3 ADJACENT pixels that count (inside the
+// frame, not background, on; no geom test; weights {1, 2, 1} x {1, 2, 1}), T_k = wideGuideThreshold(G_k, D_k, 1, k4): Q is a variance
+// of V already, so n_l leaves the divisor.  The shipped function is exact there: its fix-up multiplies r * r * d < 2^40.
+template <class Texels, class Variance>
+RTS_HD void widePropagatedThresholdPixel(const WideFilterList& f, uint32_t k4, const Texels& t, const Variance& q, int x, int y, int W, int H,
+                                         uint32_t* T8) {
+    const uint32_t onp = isBackground(t.normal(x, y)) ? 0u : (t.bits(x, y) & ((1u << f.count) - 1u));
+    uint32_t nb[9];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 9; ++j) {
+        const int qx = x + j % 3 - 1, qy = y + j / 3 - 1;
+        nb[j] = 0u;
+        if (onp == 0u || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+        nb[j] = j == 4 ? onp : (isBackground(t.normal(qx, qy)) ? 0u : t.bits(qx, qy));
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        T8[l] = 0u;
+        if (!((onp >> l) & 1u)) continue;
+        T8[l] = 65535u;
+        if (f.samples[l] < 2u) continue;
+        uint64_t G = 0;
+        uint32_t D = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int j = 0; j < 9; ++j) {
+            if (!((nb[j] >> l) & 1u)) continue;
+            const uint32_t w = (j % 3 == 1 ? 2u : 1u) * (j / 3 == 1 ? 2u : 1u);
+            G += (uint64_t)w * (uint64_t)q.variance(x + j % 3 - 1, y + j / 3 - 1, l);
+            D += w;
+        }
+        T8[l] = wideGuideThreshold(G, D, 1u, k4);
+    }
+}
+
+// One pass at one pixel: wideGuidedPassPixel's statements for the values, and with VARIANCE (every pass but the last) numQ = the sum of
+// w^2 * Q_k(q) over exactly the taps accepted for the light, the centre included; variance8[l] = Q_(k+1), 0 at an inactive pair and for
+// a light with n_l <= 1, whose Q is never read.
+template <bool VARIANCE, class Texels, class Variance>
+RTS_HD void widePropagatedPassPixel(const WideFilterList& f, const Texels& t, const Variance& q, int x, int y, int W, int H, int step,
+                                    const uint32_t* T8, uint32_t* value8, uint32_t* variance8) {
+    const V3 np = t.normal(x, y);
+    const uint32_t onp = isBackground(np) ? 0u : (t.bits(x, y) & ((1u << f.count) - 1u));
+    uint32_t num[8], den[8], ctr[8];
+    uint64_t numQ[8];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        num[l] = 0u; den[l] = 1u; ctr[l] = 0u; numQ[l] = 0u;
+        if (l >= f.count || !((onp >> l) & 1u)) continue;
+        ctr[l] = t.value(x, y, l);
+        num[l] = 36u * ctr[l];                                                    // the centre tap: always accepted
+        den[l] = 36u;
+        if (VARIANCE && f.samples[l] >= 2u) numQ[l] = 1296u * (uint64_t)q.variance(x, y, l);
+    }
+    if (onp != 0u && step > 0) {
+        const V3 pp = t.position(x, y);
+        for (int dy = -2; dy <= 2; ++dy) {
+            const int qy = y + dy * step;
+            if (qy < 0 || qy >= H) continue;
+            const uint32_t wy = dy == 0 ? 6u : ((dy == 1 || dy == -1) ? 4u : 1u);
+            for (int dx = -2; dx <= 2; ++dx) {
+                const int qx = x + dx * step;
+                if (qx < 0 || qx >= W || (dx == 0 && dy == 0)) continue;
+                if (!wideFilterGeom(t, np, pp, qx, qy, f.normalCosMin, f.planeEps)) continue;
+                const uint32_t acc = t.bits(qx, qy) & onp;
+                if (acc == 0u) continue;
+                const uint32_t w = wy * (dx == 0 ? 6u : ((dx == 1 || dx == -1) ? 4u : 1u));
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+                for (uint32_t l = 0; l < 8; ++l) {
+                    if (l >= f.count) break;
+                    if (!((acc >> l) & 1u)) continue;
+                    const uint32_t v = t.value(qx, qy, l);
+                    if ((v > ctr[l] ? v - ctr[l] : ctr[l] - v) > T8[l]) continue;  // the guide
+                    num[l] += w * v;
+                    den[l] += w;
+                    if (VARIANCE && f.samples[l] >= 2u) numQ[l] += (uint64_t)(w * w) * (uint64_t)q.variance(qx, qy, l);
+                }
+            }
+        }
+    }
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        const bool on = ((onp >> l) & 1u) != 0u;
+        value8[l] = on ? (2u * num[l] + den[l]) / (2u * den[l]) : 0u;
+        if (VARIANCE) variance8[l] = on && f.samples[l] >= 2u ? wideVarianceStep(numQ[l], den[l]) : 0u;
+    }
+}
+
 // The facing mark (include/rts_scene.h, rtsh_facing_active): 0 where the shadow mask's byte cannot reach the image -- the
 // background (combinePixel leaves the pixel 0) and N.L <= 0 (direct = 1.25 * 0 * mask: either zero) --, 1 everywhere else.
 // `!(ndl > 0)` would cull a NaN; `ndl <= 0` is false for one, so a NaN is traced.

@@ -1341,3 +1341,85 @@ extern "C" int rtsh_wide_filter_guided_temporal_mean_soft_light_list(const rts_s
                              wideGuideTemporalMeanThresholdPixel(f, k4, minHistory, t, h, x, y, (int)W, (int)H, T);
                          });
 }
+
+// ---- the guided mean filter with a propagated variance (include/rts_scene.h; per-pixel rule in rts_closest_hit.h:
+// wideVarianceInput, widePropagatedFirstThresholdPixel, widePropagatedThresholdPixel, widePropagatedPassPixel) ----
+namespace rts_harness {
+// Shared by the host and device forms: the refusals, and the unguided filter's condensed list.
+int makeWidePropagatedList(const rts_soft_light_list* list, const rtsh_wide_guide_propagated_params* p, uint32_t W, uint32_t H,
+                           WideFilterList* out) {
+    if (!p || p->by_length > 1u) return RTS_ERR_INVALID_ARG;
+    rtsh_wide_guide_temporal_params q;
+    std::memset(&q, 0, sizeof(q));
+    q.passes = p->passes; q.normal_cos_min = p->normal_cos_min; q.plane_eps = p->plane_eps; q.guide_k4 = p->guide_k4;
+    q.min_history = p->min_history;
+    return makeWideGuidedTemporalList(list, &q, W, H, out);
+}
+
+namespace {
+// A SIBLING of widePassChain, which keeps its text and with it the five shipped twins: this chain carries two kinds of planes (uint16_t
+// values and uint32_t variance, each ping-pong), has no plane of T, and its later passes form T_k themselves from the variance plane they
+// read -- three differences that would each be a branch in the shared chain.
+int widePropagatedChain(const WideFilterList& f, const WidePropagatedRule& r, const GuideMomentsCounts& h, const float* positions,
+                        const float* normals, const uint8_t* lights_map, uint32_t W, uint32_t H, float* visibility, int threads) {
+    const size_t n = (size_t)W * H, set = (size_t)f.count * n;
+    std::vector<uint16_t> values;
+    std::vector<uint32_t> variance;
+    try {
+        if (f.passes >= 2u) { values.resize(2 * set); variance.resize(2 * set); }
+    } catch (const std::bad_alloc&) {
+        return RTS_ERR_CAPACITY;
+    }
+    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
+    for (uint32_t k = 0; k < launches; ++k) {
+        const bool first = k == 0u, last = k + 1u == launches;
+        const int step = f.passes == 0u ? 0 : 1 << k;
+        const uint16_t* in = first ? nullptr : values.data() + ((k - 1u) & 1u) * set;
+        const uint32_t* qin = first ? nullptr : variance.data() + ((k - 1u) & 1u) * set;
+        uint16_t* out = last ? nullptr : values.data() + (k & 1u) * set;
+        uint32_t* qout = last ? nullptr : variance.data() + (k & 1u) * set;
+        const WideFrameTexels<WideMeanInput> t{ positions, normals, lights_map, WideMeanInput{ h.m.mean }, in, f.samples, f.scale, W, n };
+        const WideVarianceGlobal q{ f, r, h, qin };
+        parallelFor(n, 256, threads, [&](size_t i) {
+            const int x = (int)(i % W), y = (int)(i / W);
+            uint32_t v[8], Q[8], T[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+            if (first) {
+                if (step > 0) widePropagatedFirstThresholdPixel(f, r, t, h, x, y, (int)W, (int)H, T);
+            } else {
+                widePropagatedThresholdPixel(f, r.k4, t, q, x, y, (int)W, (int)H, T);
+            }
+            if (last) widePropagatedPassPixel<false>(f, t, q, x, y, (int)W, (int)H, step, T, v, Q);
+            else widePropagatedPassPixel<true>(f, t, q, x, y, (int)W, (int)H, step, T, v, Q);
+            for (uint32_t l = 0; l < f.count; ++l) {
+                if (last) visibility[(size_t)l * n + i] = wideFilterOutput(v[l], f.samples[l], f.scale[l]);
+                else { out[(size_t)l * n + i] = (uint16_t)v[l]; qout[(size_t)l * n + i] = Q[l]; }
+            }
+        });
+    }
+    return RTS_OK;
+}
+} // namespace
+} // namespace rts_harness
+
+extern "C" size_t rtsh_wide_filter_propagated_scratch_bytes(uint32_t count, uint32_t W, uint32_t H) {
+    return wideScratchBytes(2, count, W, H) * 3;                                 // 2 * 2 bytes of values, then 2 * 4 bytes of variance
+}
+
+extern "C" uint32_t rtsh_wide_variance_step(uint64_t numQ, uint32_t den) {
+    if (den == 0 || den > 256u || numQ > (uint64_t)(den * den) * 0xFFFFFFFFull) return 0xFFFFFFFFu;
+    return wideVarianceStep(numQ, den);
+}
+
+extern "C" int rtsh_wide_filter_propagated_mean_soft_light_list(const rts_soft_light_list* list,
+                                                                const rtsh_wide_guide_propagated_params* params, const float* positions,
+                                                                const float* normals, const uint8_t* lights_map, const uint8_t* counts,
+                                                                const uint16_t* mean, const uint32_t* square, const uint8_t* lengths,
+                                                                uint32_t W, uint32_t H, float* visibility, int threads) {
+    if (!positions || !normals || !counts || !mean || !square || !lengths || !visibility) return RTS_ERR_INVALID_ARG;
+    WideFilterList f;
+    const int s = makeWidePropagatedList(list, params, W, H, &f);
+    if (s != RTS_OK) return s;
+    const WidePropagatedRule r{ params->guide_k4, params->min_history, params->by_length };
+    const GuideMomentsCounts h{ GuideMoments{ mean, square, lengths, W, (size_t)W * H }, counts };
+    return widePropagatedChain(f, r, h, positions, normals, lights_map, W, H, visibility, threads);
+}

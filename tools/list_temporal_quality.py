@@ -40,6 +40,12 @@ rtsh_wide_filter_guided_temporal_mean_soft_light_list): the prot
 columns per row: "mean_raw" the unfiltered mean plane (passes 0), "mean_unguided" the unguided filter over it, "mean_temporal" the
 guided one at guide_k4 8, 12 and 16.
 
+    python tools/list_temporal_quality.py --propagate [--out profiles/r36/list_propagated_quality.jsonl]
+
+The guided mean filter with a propagated variance (rtsh_wide_filter_propagated_mean_soft_light_list): --mean-input's rows,
+and per row "passes_2" and "passes_4": at that many passes the unguided mean filter, 4.27's guide ("temporal"), 4.28's guided mean filter
+("mean_temporal") and the propagated filter without and with by_length, each guided one at guide_k4 8, 12 and 16.
+
     python tools/list_temporal_quality.py --move [--out profiles/r33/list_motion_quality.jsonl]
 
 Motion vectors (rtsh_primary_gbuffer_motion, rtsh_accumulate_visibility_list_motion): cornell_128, a still camera in the
@@ -130,7 +136,10 @@ def jump_rows():
 GUIDE_FRAMES, GUIDE_K4, GUIDE_PASSES, GUIDE_MIN_HISTORY = (4, 8, 12), (8, 12, 16), 2, 4
 
 
-def guide_rows(mean_input=False):
+PROPAGATE_PASSES = (2, 4)
+
+
+def guide_rows(mean_input=False, propagate=False):
     from raytracedshadows_amd import api, scenes
     rows = []
     for name, sc, W, H in (("cornell_128", scenes.cornell(), 128, 128), ("terrain_96", scenes.terrain(23), 96, 96)):
@@ -176,6 +185,22 @@ def guide_rows(mean_input=False):
                         row["mean_temporal"] = {str(k4): mad(api.wide_filter_guided_temporal_mean_soft_light_list(
                             lst, api.WideGuideTemporalParams.make(GUIDE_PASSES, k4, GUIDE_MIN_HISTORY, 0.9, eps), pos, nrm, counts, moments,
                             facing)[0]) for k4 in GUIDE_K4}
+                    if propagate:
+                        for passes in PROPAGATE_PASSES:
+                            cell = {"unguided": mad(api.wide_filter_mean_soft_light_list(lst, api.WideFilterParams.make(passes, 0.9, eps), pos, nrm,
+                                                                                         moments[0], facing)[0]),
+                                    "temporal": {}, "mean_temporal": {}, "propagated": {}, "propagated_by_length": {}}
+                            for k4 in GUIDE_K4:
+                                gp = api.WideGuideTemporalParams.make(passes, k4, GUIDE_MIN_HISTORY, 0.9, eps)
+                                cell["temporal"][str(k4)] = mad(api.wide_filter_guided_temporal_soft_light_list(lst, gp, pos, nrm, counts, moments,
+                                                                                                                facing)[0])
+                                cell["mean_temporal"][str(k4)] = mad(api.wide_filter_guided_temporal_mean_soft_light_list(lst, gp, pos, nrm, counts,
+                                                                                                                          moments, facing)[0])
+                                for by_length, key in ((0, "propagated"), (1, "propagated_by_length")):
+                                    pp = api.WideGuidePropagatedParams.make(passes, k4, GUIDE_MIN_HISTORY, by_length, 0.9, eps)
+                                    cell[key][str(k4)] = mad(api.wide_filter_propagated_mean_soft_light_list(lst, pp, pos, nrm, counts, moments,
+                                                                                                             facing)[0])
+                            row["passes_" + str(passes)] = cell
                     rows.append(row)
                     print(json.dumps(row))
     return rows
@@ -325,6 +350,7 @@ def main():
     ap.add_argument("--jump", action="store_true", help="the light-jump scenario of the neighbourhood clamp instead of the still-camera table")
     ap.add_argument("--guide-history", action="store_true", help="the temporal guide of the wide filter against the unguided filter and 4.26's guide")
     ap.add_argument("--mean-input", action="store_true", help="--guide-history's table with the mean-input filters' three columns beside it")
+    ap.add_argument("--propagate", action="store_true", help="--mean-input's table with the propagated filter's columns at 2 and 4 passes")
     ap.add_argument("--move", action="store_true", help="the plain and the motion accumulate over a box translated and refitted every frame")
     ap.add_argument("--moments", action="store_true", help="with --jump or --move: the moments column set of the clamped moments pass")
     args = ap.parse_args()
@@ -337,8 +363,9 @@ def main():
                 for row in rows:
                     f.write(json.dumps(row) + "\n")
         return
-    rows = move_rows() if args.move else jump_rows() if args.jump else (guide_rows(args.mean_input) if args.guide_history or args.mean_input else [])
-    if args.move or args.jump or args.guide_history or args.mean_input:
+    rows = move_rows() if args.move else jump_rows() if args.jump else (
+        guide_rows(args.mean_input or args.propagate, args.propagate) if args.guide_history or args.mean_input or args.propagate else [])
+    if args.move or args.jump or args.guide_history or args.mean_input or args.propagate:
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as f:

@@ -192,7 +192,7 @@ def parse_move(text, wl):
 
 
 def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, max_length, probe=0, table=0, colors="", clamp=None,
-                       filter_mean=False, move="", moments_clamp=None):
+                       filter_mean=False, move="", moments_clamp=None, propagate=None):
     """`frames` frames of a light list: per frame G-buffer, facing map, trace (the offsets table rotated by one entry per frame), filter
     and accumulation with ping-pong history; the last frame is lit from the accumulated visibility."""
     from raytracedshadows_amd import api, scenes
@@ -211,6 +211,11 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
     with_moments = temporal_guide or filter_mean                         # (--filter-mean without a guide accumulates the moments itself)
     moments = [(ctx.malloc(count * n * 2), ctx.malloc(count * n * 4), ctx.malloc(count * n)) for _ in range(2)] if with_moments else None
     d_scratch = ctx.malloc(wide_scratch_bytes(api, filt, count, W, H)) if wide and filt.passes >= 2 else None
+    if propagate is not None:                                            # --filter-propagate: the variance plane carried through the passes
+        prop = api.WideGuidePropagatedParams.make(filt.passes, filt.guide_k4, filt.min_history, propagate, filt.normal_cos_min, filt.plane_eps)
+        if filt.passes >= 2:
+            ctx.free(d_scratch)
+            d_scratch = ctx.malloc(api.wide_filter_propagated_scratch_bytes(count, W, H))
     eyes = [orbit(sc.eye, sc.target, orbit_deg * (k - (frames - 1))) for k in range(frames)]      # the last frame is the scene's own camera
     moving = parse_move(move, wl) if move else None
     if moving:                                                           # the previous stream and this frame's two motion planes
@@ -248,7 +253,10 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
             api.accumulate_moments_soft_light_list_device(ctx, lights, tp, d_pos, d_nrm, d_counts, W, H, *moments[k % 2],
                                                           d_prev=None if k == 0 else gbuf[(k - 1) % 2] + moments[(k - 1) % 2], d_lights_map=d_map,
                                                           d_motion=d_motion, clamp=moments_clamp)
-        if filter_mean and temporal_guide:
+        if propagate is not None:
+            api.wide_filter_propagated_mean_soft_light_list_device(ctx, lights, prop, d_pos, d_nrm, d_counts, moments[k % 2], W, H, d_vis,
+                                                                   d_scratch=d_scratch, d_lights_map=d_map)
+        elif filter_mean and temporal_guide:
             api.wide_filter_guided_temporal_mean_soft_light_list_device(ctx, lights, filt, d_pos, d_nrm, d_counts, moments[k % 2], W, H, d_vis,
                                                                         d_scratch=d_scratch, d_lights_map=d_map)
         elif filter_mean:
@@ -264,7 +272,7 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
     api.combine_visibility_list_device(ctx, constants, hard, gbuf[last][0], gbuf[last][1], hist[last][0], W, H, d_rgb, d_lights_map=d_map,
                                        colors=colors)
     ctx.synchronize()
-    print(f"{frames} frames of {count} lights x {spp} samples, filter {filter_words(api, filt)}{' over the accumulated mean' if filter_mean else ''}, orbit {orbit_deg:g} degree per frame, "
+    print(f"{frames} frames of {count} lights x {spp} samples, filter {filter_words(api, filt)}{' over the accumulated mean' if filter_mean else ''}{'' if propagate is None else ', variance propagated' + (' and divided by the length' if propagate else '')}, orbit {orbit_deg:g} degree per frame, "
           f"max_length {max_length}{'' if clamp is None else f', history clamped at r = {clamp.radius}, margin {clamp.margin:g}'}"
           f"{'' if moments_clamp is None else f', moments clamped at r = {moments_clamp.radius}, sigma_k4 {moments_clamp.sigma_k4}, margin {moments_clamp.margin}'}: "
           f"{(time.time() - t0) * 1e3:.2f} ms (incl. first launches)")
@@ -321,6 +329,11 @@ def main():
                     help="with --filter-guide K4 and --temporal F: accumulate the count moments per frame "
                          "(rtsh_accumulate_moments_soft_light_list_device) and take the guide's variance from them where a pixel has at "
                          "least M frames of history (rtsh_wide_filter_guided_temporal_soft_light_list_device), 1 <= M <= 255")
+    ap.add_argument("--filter-propagate", action="store_true",
+                    help="with --filter-mean --filter-guide K4 --guide-history M: carry a variance plane through the passes and re-derive "
+                         "the tolerance from it at every pass (rtsh_wide_filter_propagated_mean_soft_light_list_device)")
+    ap.add_argument("--variance-by-length", action="store_true",
+                    help="with --filter-propagate: divide the temporal variance by the history's length (by_length = 1)")
     ap.add_argument("--filter-mean", action="store_true",
                     help="with --filter-passes K and --temporal F: run the passes over the accumulated mean of the count moments in place "
                          "of this frame's counts (rtsh_wide_filter_mean_soft_light_list_device); with --filter-guide K4 --guide-history M "
@@ -384,6 +397,11 @@ def main():
                 if args.clamp > 4 or not 0.0 <= args.clamp_margin < float("inf"):
                     sys.exit("render: --clamp R takes 0 <= R <= 4 and a finite --clamp-margin M >= 0")
                 clamp = api.HistoryClamp.make(args.clamp, args.clamp_margin) if args.clamp >= 0 else None
+                if args.variance_by_length and not args.filter_propagate:
+                    sys.exit("render: --variance-by-length goes with --filter-propagate")
+                if args.filter_propagate and not (args.filter_mean and args.guide_history):
+                    sys.exit("render: --filter-propagate goes with --filter-mean --filter-guide K4 --guide-history M")
+                propagate = (1 if args.variance_by_length else 0) if args.filter_propagate else None
                 moments_clamp = None
                 if args.moments_clamp:
                     try:
@@ -397,7 +415,7 @@ def main():
                         sys.exit("render: --moments-clamp goes with --guide-history M or --filter-mean (where the moments pass runs)")
                     moments_clamp = api.MomentsClamp.make(*parts)
                 return soft_list_temporal(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, filt, args.temporal, args.orbit,
-                                          args.max_length, args.adaptive, args.table, args.colors, clamp, args.filter_mean, args.move, moments_clamp)
+                                          args.max_length, args.adaptive, args.table, args.colors, clamp, args.filter_mean, args.move, moments_clamp, propagate)
             return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance,
                              args.colors, filt)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
