@@ -973,6 +973,97 @@ int rtsh_accumulate_moments_soft_light_list_clamped_motion_device(rts_ctx* ctx, 
                                                                   uint32_t W, uint32_t H, uint16_t* d_mean_out, uint32_t* d_square_out,
                                                                   uint8_t* d_lengths_out, const rtsh_moments_clamp* clamp, void* stream);
 
+/* HALF-RESOLUTION LIGHT LISTS: trace a quarter of the pixels and reconstruct the rest from the G-buffer.  Three passes around the
+ * EXISTING traces -- subsample the G-buffer, (trace it at w x h with rts_trace_soft_light_list* / rts_trace_light_list*,) mark the pixels
+ * no traced neighbour can stand for, (trace those at full resolution with the mark as lights_map,) upsample the rest -- whose result is
+ * COUNT PLANES again, uint8_t per light at W x H (one mask byte for a hard list), which every later stage takes unchanged.  A dense
+ * half-resolution frame keeps the 8 x 8 packets of the trace full, where a checkerboard map would idle half of each.  The result is
+ * a function of the inputs alone: integer weights, integer sums, one integer quotient per light; floats appear in per-tap comparisons
+ * only; so the host forms check the device forms byte for byte.
+ *   typedef struct rtsh_upsample_params: phase_x, phase_y (0 or 1), normal_cos_min, plane_eps (world units), reserved_ (ignored).
+ * THE LATTICE: low-resolution pixel (X, Y) IS full-resolution pixel s(X, Y) = (2X + phase_x, 2Y + phase_y); the low-resolution frame
+ *   is w x h with w = (W + 1 - phase_x) >> 1 and h = (H + 1 - phase_y) >> 1 (rtsh_subsampled_size): exactly the sampled pixels inside
+ *   the frame, nothing is ever clamped.  A caller may rotate the phase per frame so that a temporal stage sees all four pixels of a quad.
+ * on(p, l), bg(p), N_p, P_p and geom(p, q) are the filter's above (rtsh_filter_*_light_list); c_l(q) = the byte of LOW-RESOLUTION
+ *   plane l at q (lo_counts[l * w * h + q]; bit l of lo_mask[q] as 0 or 1), unclamped.
+ * rtsh_subsample_gbuffer: lo_positions[q], lo_normals[q] (four floats each, copied as they are) and, where lights_map is not NULL,
+ *   lo_lights_map[q] = those of s(q).  lights_map == NULL: lo_lights_map is not touched (and may be NULL).
+ * TAPS of p = (x, y): u = x - phase_x, X0 = u >> 1 (arithmetic: -1 for u = -1), ax = u & 1; v = y - phase_y, Y0 = v >> 1, ay = v & 1.
+ *   Four taps IN THIS ORDER: (X0, Y0), (X0+1, Y0), (X0, Y0+1), (X0+1, Y0+1), of the INTEGER weights (2-ax)*(2-ay), ax*(2-ay), (2-ax)*ay,
+ *   ax*ay, which sum to 4.  A tap of weight 0, or outside w x h, DOES NOT EXIST.  A tap whose sampled pixel is p itself (ax == ay == 0:
+ *   the one tap, of weight 4) is always accepted for every light; its map bit is not looked at.  Any other tap q is ACCEPTED for light
+ *   l when geom(p, q) holds -- the one shared function of the wide filters: not bg(q), the normal test against normal_cos_min, the plane
+ *   test against plane_eps, in that order, a NaN rejects; p's data from the full-resolution G-buffer, q's from the low-resolution one
+ *   -- and on(q, l) holds in lo_lights_map (NULL: every light).
+ * rtsh_upsample_retrace_map: bit l < count of retrace[p] is set exactly where p is not background, on(p, l) holds, p is not a sampled
+ *   pixel and no tap of p is accepted for light l; every other bit is 0.  Given to a full-resolution trace as lights_map, that trace
+ *   writes the planes: the traced byte where the bit is set, 0 where it is clear.
+ * rtsh_upsample_soft_light_list / rtsh_upsample_light_list, for p and l < count, in this order:
+ *   KEEP: where keep != NULL and bit l of keep[p] is set, plane l at p is NOT TOUCHED (a hard list: bit l of mask[p] stays, the byte is
+ *     read and rewritten) and nothing else of p is looked at for that light.  With keep = the retrace map the pass merges in place
+ *     behind the masked trace: no temporary, no merge pass.
+ *   INACTIVE: where bg(p) or not on(p, l), the byte is 0 and nothing else is read.
+ *   QUOTIENT: num = sum of w * c_l(q), den = sum of w over the accepted taps; byte = (2 * num + den) / (2 * den) in unsigned integers:
+ *     the mean rounded half up.  A hard list uses the same formula on bits.
+ *   FALLBACK: with no accepted tap, the byte c_l(q) of the existing tap with on(q, l) of the LARGEST weight, the FIRST such in tap
+ *     order; 0 if there is none.  (Its geometry is not looked at: every existing tap failed it.)
+ *   Bits of a hard list's mask from `count` up are written 0 wherever the byte is written (it is not where every light below count
+ *   is kept); planes of a soft list from `count` up are never touched.
+ * ANCHORS: (1) a sampled pixel active for light l gets its low-resolution byte exactly ((8c + 4) / 8 = c).  (2) Where every accepted
+ * tap carries the same byte c the result is c ((2 * c * den + den) / (2 * den) = c).  (3) With keep = the retrace map of the same
+ * params and maps, no written (pixel, light) takes the fallback.  (4) With a list without jitter tables and plane_eps = -1.0f (no
+ * neighbour is accepted): subsample, trace at w x h, retrace map, trace at W x H under it, upsample with keep -- equals the plain trace
+ * at W x H byte for byte, in every phase: a pixel's count depends on its position and the list alone, and a pixel is either sampled
+ * or retraced.  (At background pixels this needs a map that clears them, as rtsh_facing_lights' does: WITHOUT a map the plain trace
+ * traces a background pixel's cleared texel like any other, and the INACTIVE rule gives it 0.)
+ *   * lights_map, lo_lights_map and keep may each be NULL.  All other buffers are required.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: what rtsh_filter_*_light_list* refuse of a list (the retrace map takes
+ *     `count` alone: 0 or above RTS_MAX_LIST_LIGHTS); NULL params, G-buffers (full or low) or planes (full or low); a phase above 1; a
+ *     normal_cos_min or plane_eps that is not finite; W, H, w or h equal to 0 (phase 1 on a frame one pixel wide); W or H above
+ *     0x7FFFFFF0; output planes equal to the low-resolution planes; in rtsh_subsample_gbuffer a lights_map without lo_lights_map; in
+ *     the device forms a NULL ctx and, in the two full-resolution passes, H above 8 * 65535 (the grid).
+ *   * host forms: multi-threaded (threads: 0 = all host threads).  Device forms: DEVICE buffers, asynchronous on `stream`, allocate
+ *     nothing and read nothing back, need no BVH and no alignment of any buffer beyond its element type's; under graph capture each
+ *     adds ONE kernel node, parameters by value (params is read during the call).  One low-resolution pixel per lane in the
+ *     subsample, one full-resolution pixel per lane in the other two.
+ *   * OUT OF SCOPE: distance planes; the adaptive and jittered list forms (a jitter hash takes the index in the frame traced); factors
+ *     other than 2; row ranges and stripes. */
+typedef struct rtsh_upsample_params {
+    uint32_t phase_x, phase_y;  /* 0 or 1: low-resolution (X, Y) is full-resolution (2X + phase_x, 2Y + phase_y) */
+    float    normal_cos_min;    /* a tap needs N_p . N_q >= this */
+    float    plane_eps;         /* ... and |N_p . (P_q - P_p)| <= this (world units) */
+    uint32_t reserved_[4];      /* ignored */
+} rtsh_upsample_params;                                                            /* 32 bytes */
+int rtsh_subsampled_size(uint32_t W, uint32_t H, uint32_t phase_x, uint32_t phase_y, uint32_t* w, uint32_t* h);
+int rtsh_subsample_gbuffer(const rtsh_upsample_params* params, const float* positions, const float* normals, const uint8_t* lights_map,
+                           uint32_t W, uint32_t H, float* lo_positions, float* lo_normals, uint8_t* lo_lights_map);
+int rtsh_subsample_gbuffer_device(rts_ctx* ctx, const rtsh_upsample_params* params, const float* d_positions, const float* d_normals,
+                                  const uint8_t* d_lights_map, uint32_t W, uint32_t H, float* d_lo_positions, float* d_lo_normals,
+                                  uint8_t* d_lo_lights_map, void* stream);
+int rtsh_upsample_retrace_map(uint32_t count, const rtsh_upsample_params* params, const float* positions, const float* normals,
+                              const uint8_t* lights_map, const float* lo_positions, const float* lo_normals, const uint8_t* lo_lights_map,
+                              uint32_t W, uint32_t H, uint8_t* retrace, int threads);
+int rtsh_upsample_retrace_map_device(rts_ctx* ctx, uint32_t count, const rtsh_upsample_params* params, const float* d_positions,
+                                     const float* d_normals, const uint8_t* d_lights_map, const float* d_lo_positions,
+                                     const float* d_lo_normals, const uint8_t* d_lo_lights_map, uint32_t W, uint32_t H, uint8_t* d_retrace,
+                                     void* stream);
+int rtsh_upsample_light_list(const rts_light_list* list, const rtsh_upsample_params* params, const float* positions, const float* normals,
+                             const uint8_t* lights_map, const float* lo_positions, const float* lo_normals, const uint8_t* lo_lights_map,
+                             const uint8_t* lo_mask, const uint8_t* keep, uint32_t W, uint32_t H, uint8_t* mask, int threads);
+int rtsh_upsample_soft_light_list(const rts_soft_light_list* list, const rtsh_upsample_params* params, const float* positions,
+                                  const float* normals, const uint8_t* lights_map, const float* lo_positions, const float* lo_normals,
+                                  const uint8_t* lo_lights_map, const uint8_t* lo_counts, const uint8_t* keep, uint32_t W, uint32_t H,
+                                  uint8_t* counts, int threads);
+int rtsh_upsample_light_list_device(rts_ctx* ctx, const rts_light_list* list, const rtsh_upsample_params* params, const float* d_positions,
+                                    const float* d_normals, const uint8_t* d_lights_map, const float* d_lo_positions,
+                                    const float* d_lo_normals, const uint8_t* d_lo_lights_map, const uint8_t* d_lo_mask,
+                                    const uint8_t* d_keep, uint32_t W, uint32_t H, uint8_t* d_mask, void* stream);
+int rtsh_upsample_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list* list, const rtsh_upsample_params* params,
+                                         const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                         const float* d_lo_positions, const float* d_lo_normals, const uint8_t* d_lo_lights_map,
+                                         const uint8_t* d_lo_counts, const uint8_t* d_keep, uint32_t W, uint32_t H, uint8_t* d_counts,
+                                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

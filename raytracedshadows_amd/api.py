@@ -221,6 +221,19 @@ class WideFilterParams(C.Structure):
         return p
 
 
+class UpsampleParams(C.Structure):
+    """``rtsh_upsample_params``: the phase of the half-resolution lattice (low-resolution pixel (X, Y) is full-resolution pixel
+    (2X + phase_x, 2Y + phase_y)) and the two geometry thresholds of a tap."""
+    _fields_ = [("phase_x", C.c_uint32), ("phase_y", C.c_uint32), ("normal_cos_min", C.c_float), ("plane_eps", C.c_float),
+                ("reserved_", C.c_uint32 * 4)]
+
+    @classmethod
+    def make(cls, phase_x=0, phase_y=0, normal_cos_min=0.9, plane_eps=0.05):
+        p = cls()
+        p.phase_x, p.phase_y, p.normal_cos_min, p.plane_eps = phase_x, phase_y, np.float32(normal_cos_min), np.float32(plane_eps)
+        return p
+
+
 class WideGuideParams(C.Structure):
     """``rtsh_wide_guide_params``: ``WideFilterParams`` plus ``guide_k4``, the variance guide's tolerance in quarter standard deviations
     (0..255; 12 is k = 3, 0 accepts equal values only)."""
@@ -557,6 +570,23 @@ _sig("rtsh_filter_light_list_device", C.c_int, C.c_void_p, C.POINTER(LightList),
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_filter_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(FilterParams), C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_subsampled_size", C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
+_sig("rtsh_subsample_gbuffer", C.c_int, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+     C.c_void_p, C.c_void_p)
+_sig("rtsh_subsample_gbuffer_device", C.c_int, C.c_void_p, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+     C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_upsample_retrace_map", C.c_int, C.c_uint32, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_upsample_retrace_map_device", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_upsample_light_list", C.c_int, C.POINTER(LightList), C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_upsample_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_upsample_light_list_device", C.c_int, C.c_void_p, C.POINTER(LightList), C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_upsample_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(UpsampleParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_wide_filter_scratch_bytes", C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32)
 _sig("rtsh_wide_filter_light_list", C.c_int, C.POINTER(LightList), C.POINTER(WideFilterParams), C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
@@ -1770,6 +1800,139 @@ def filter_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d
                                                    C.c_void_p(d_lights_map or 0), C.c_void_p(d_counts), C.c_void_p(d_distances or 0), width,
                                                    height, C.c_void_p(d_visibility), C.c_void_p(stream or 0)),
            "rtsh_filter_soft_light_list_device")
+
+
+def subsampled_size(width, height, phase_x=0, phase_y=0):
+    """``(w, h)`` of the half-resolution frame of a ``width`` x ``height`` one in the given phase (rtsh_subsampled_size): the sampled
+    pixels ``(2X + phase_x, 2Y + phase_y)`` inside the frame.  Refused (RtsError) where there is none."""
+    w, h = C.c_uint32(0), C.c_uint32(0)
+    _check(_lib.rtsh_subsampled_size(width, height, phase_x, phase_y, C.byref(w), C.byref(h)), "rtsh_subsampled_size")
+    return int(w.value), int(h.value)
+
+
+def _upsample_frame(name, params, positions, normals, lights_map):
+    """The full-resolution G-buffer of the half-resolution passes, contiguous and checked: (positions, normals, lights_map, W, H, w, h)."""
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    positions = np.ascontiguousarray(positions, np.float32)
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    if normals.size != H * W * 4 or positions.size != H * W * 4 or (lights_map is not None and lights_map.size != H * W):
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    w, h = subsampled_size(W, H, params.phase_x, params.phase_y) if params is not None else (1, 1)
+    return positions, normals, lights_map, W, H, w, h
+
+
+def _upsample_low(name, w, h, lo_positions, lo_normals, lo_lights_map):
+    lo_positions, lo_normals = np.ascontiguousarray(lo_positions, np.float32), np.ascontiguousarray(lo_normals, np.float32)
+    lo_lights_map = np.ascontiguousarray(lo_lights_map, np.uint8) if lo_lights_map is not None else None
+    if lo_positions.size != w * h * 4 or lo_normals.size != w * h * 4 or (lo_lights_map is not None and lo_lights_map.size != w * h):
+        raise RtsError(1, name + ": a low-resolution buffer does not fit the subsampled frame")
+    return lo_positions, lo_normals, lo_lights_map
+
+
+def subsample_gbuffer(params, positions, normals, lights_map=None):
+    """The half-resolution G-buffer of a frame on the host (rtsh_subsample_gbuffer): ``(float32[h, w, 4] positions, float32[h, w, 4]
+    normals, uint8[h, w] lights_map or None)``, the texels of the pixels ``(2X + phase_x, 2Y + phase_y)`` of ``params`` (an
+    ``UpsampleParams``)."""
+    positions, normals, lights_map, W, H, w, h = _upsample_frame("rtsh_subsample_gbuffer", params, positions, normals, lights_map)
+    lo_pos, lo_nrm = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+    lo_map = np.zeros((h, w), np.uint8) if lights_map is not None else None
+    _check(_lib.rtsh_subsample_gbuffer(_ref(params), _ptr(positions), _ptr(normals), _ptr_or_none(lights_map), W, H, _ptr(lo_pos), _ptr(lo_nrm),
+                                       _ptr_or_none(lo_map)), "rtsh_subsample_gbuffer")
+    return lo_pos, lo_nrm, lo_map
+
+
+def subsample_gbuffer_device(ctx, params, d_positions, d_normals, width, height, d_lo_positions, d_lo_normals, d_lights_map=None,
+                             d_lo_lights_map=None, stream=None):
+    """The half-resolution G-buffer on the GPU: device pointers, the low-resolution buffers of ``subsampled_size`` texels, one kernel,
+    asynchronous."""
+    _check(_lib.rtsh_subsample_gbuffer_device(ctx.handle, _ref(params), C.c_void_p(d_positions), C.c_void_p(d_normals),
+                                              C.c_void_p(d_lights_map or 0), width, height, C.c_void_p(d_lo_positions),
+                                              C.c_void_p(d_lo_normals), C.c_void_p(d_lo_lights_map or 0), C.c_void_p(stream or 0)),
+           "rtsh_subsample_gbuffer_device")
+
+
+def upsample_retrace_map(count, params, positions, normals, lo_positions, lo_normals, lights_map=None, lo_lights_map=None, threads=0):
+    """The retrace map of a half-resolution light list on the host (rtsh_upsample_retrace_map): ``uint8[H, W]``, bit ``l`` set where
+    the pixel is active for light ``l``, not sampled, and no low-resolution tap is accepted for it -- the ``lights_map`` of the
+    full-resolution trace that fills those pixels."""
+    name = "rtsh_upsample_retrace_map"
+    positions, normals, lights_map, W, H, w, h = _upsample_frame(name, params, positions, normals, lights_map)
+    lo_positions, lo_normals, lo_lights_map = _upsample_low(name, w, h, lo_positions, lo_normals, lo_lights_map)
+    retrace = np.zeros((H, W), np.uint8)
+    _check(_lib.rtsh_upsample_retrace_map(count, _ref(params), _ptr(positions), _ptr(normals), _ptr_or_none(lights_map), _ptr(lo_positions),
+                                          _ptr(lo_normals), _ptr_or_none(lo_lights_map), W, H, _ptr(retrace), threads), name)
+    return retrace
+
+
+def upsample_retrace_map_device(ctx, count, params, d_positions, d_normals, d_lo_positions, d_lo_normals, width, height, d_retrace,
+                                d_lights_map=None, d_lo_lights_map=None, stream=None):
+    """The retrace map on the GPU: device pointers, d_retrace = width*height bytes, one kernel, asynchronous."""
+    _check(_lib.rtsh_upsample_retrace_map_device(ctx.handle, count, _ref(params), C.c_void_p(d_positions), C.c_void_p(d_normals),
+                                                 C.c_void_p(d_lights_map or 0), C.c_void_p(d_lo_positions), C.c_void_p(d_lo_normals),
+                                                 C.c_void_p(d_lo_lights_map or 0), width, height, C.c_void_p(d_retrace),
+                                                 C.c_void_p(stream or 0)), "rtsh_upsample_retrace_map_device")
+
+
+def _upsample_list(soft, lights, params, positions, normals, lo_positions, lo_normals, lo_planes, lights_map, lo_lights_map, keep, out,
+                   threads):
+    name = "rtsh_upsample_soft_light_list" if soft else "rtsh_upsample_light_list"
+    positions, normals, lights_map, W, H, w, h = _upsample_frame(name, params, positions, normals, lights_map)
+    lo_positions, lo_normals, lo_lights_map = _upsample_low(name, w, h, lo_positions, lo_normals, lo_lights_map)
+    count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
+    lo_planes = np.ascontiguousarray(lo_planes, np.uint8)
+    keep = np.ascontiguousarray(keep, np.uint8) if keep is not None else None
+    shape = (count, H, W) if soft else (H, W)
+    if out is None:
+        out = np.zeros(shape, np.uint8)
+    if lo_planes.size < (count if soft else 1) * w * h or (keep is not None and keep.size != H * W) or out.dtype != np.uint8 or \
+            not out.flags.c_contiguous or out.size < int(np.prod(shape)):
+        raise RtsError(1, name + ": a buffer does not fit the frame")
+    fn = _lib.rtsh_upsample_soft_light_list if soft else _lib.rtsh_upsample_light_list
+    _check(fn(_ref(lights), _ref(params), _ptr(positions), _ptr(normals), _ptr_or_none(lights_map), _ptr(lo_positions), _ptr(lo_normals),
+              _ptr_or_none(lo_lights_map), _ptr(lo_planes), _ptr_or_none(keep), W, H, _ptr(out), threads), name)
+    return out
+
+
+def upsample_soft_light_list(lights, params, positions, normals, lo_positions, lo_normals, lo_counts, lights_map=None, lo_lights_map=None,
+                             keep=None, out=None, threads=0):
+    """The full-resolution count planes of a soft light list traced at half resolution, on the host (rtsh_upsample_soft_light_list):
+    ``uint8[count, H, W]`` from ``lo_counts`` (``uint8[count, h, w]``) by four geometry-tested integer-weighted taps.  ``keep``
+    (``uint8[H, W]``, the retrace map) and ``out`` (the planes a masked full-resolution trace wrote): a (pixel, light) whose keep bit
+    is set is left as ``out`` holds it."""
+    return _upsample_list(True, lights, params, positions, normals, lo_positions, lo_normals, lo_counts, lights_map, lo_lights_map, keep, out,
+                          threads)
+
+
+def upsample_light_list(light_list, params, positions, normals, lo_positions, lo_normals, lo_mask, lights_map=None, lo_lights_map=None,
+                        keep=None, out=None, threads=0):
+    """The same for a hard light list (rtsh_upsample_light_list): ``uint8[H, W]``, bit ``l`` from bit ``l`` of ``lo_mask``."""
+    return _upsample_list(False, light_list, params, positions, normals, lo_positions, lo_normals, lo_mask, lights_map, lo_lights_map, keep,
+                          out, threads)
+
+
+def _upsample_list_device(fn, name, ctx, lights, params, d_positions, d_normals, d_lo_positions, d_lo_normals, d_lo_planes, width, height,
+                          d_planes, d_lights_map, d_lo_lights_map, d_keep, stream):
+    _check(fn(ctx.handle, _ref(lights), _ref(params), C.c_void_p(d_positions), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
+              C.c_void_p(d_lo_positions), C.c_void_p(d_lo_normals), C.c_void_p(d_lo_lights_map or 0), C.c_void_p(d_lo_planes),
+              C.c_void_p(d_keep or 0), width, height, C.c_void_p(d_planes), C.c_void_p(stream or 0)), name)
+
+
+def upsample_soft_light_list_device(ctx, lights, params, d_positions, d_normals, d_lo_positions, d_lo_normals, d_lo_counts, width, height,
+                                    d_counts, d_lights_map=None, d_lo_lights_map=None, d_keep=None, stream=None):
+    """The upsample of a soft light list's count planes on the GPU: device pointers, d_counts = count planes of width*height bytes,
+    written except where ``d_keep`` has the light's bit, one kernel, asynchronous."""
+    _upsample_list_device(_lib.rtsh_upsample_soft_light_list_device, "rtsh_upsample_soft_light_list_device", ctx, lights, params, d_positions,
+                          d_normals, d_lo_positions, d_lo_normals, d_lo_counts, width, height, d_counts, d_lights_map, d_lo_lights_map, d_keep,
+                          stream)
+
+
+def upsample_light_list_device(ctx, light_list, params, d_positions, d_normals, d_lo_positions, d_lo_normals, d_lo_mask, width, height,
+                               d_mask, d_lights_map=None, d_lo_lights_map=None, d_keep=None, stream=None):
+    """The upsample of a hard light list's mask on the GPU: device pointers, d_mask = width*height bytes, one kernel, asynchronous."""
+    _upsample_list_device(_lib.rtsh_upsample_light_list_device, "rtsh_upsample_light_list_device", ctx, light_list, params, d_positions,
+                          d_normals, d_lo_positions, d_lo_normals, d_lo_mask, width, height, d_mask, d_lights_map, d_lo_lights_map, d_keep,
+                          stream)
 
 
 def wide_filter_scratch_bytes(count, width, height):

@@ -1118,4 +1118,95 @@ RTS_HD uint8_t facingLightsPixel(const FacingLights& f, const float* position4, 
     return (uint8_t)bits;
 }
 
+// HALF-RESOLUTION LIGHT LISTS (include/rts_scene.h, rtsh_upsample_*): the four taps of a full-resolution pixel in the low-resolution
+// frame, and the two per-pixel rules read from them.  `Full` gives the full-resolution frame by pixel coordinates: V3 normal(x, y),
+// V3 position(x, y), uint32_t bits(x, y) (the map byte, 0xFF without a map).  `Low` gives the low-resolution one the same way, plus
+// uint32_t byte(X, Y, l) (the count byte, or the mask's bit as 0 / 1): the host twin reads the buffers, the kernel its LDS window.
+struct UpsampleList { uint32_t count, phaseX, phaseY; float normalCosMin, planeEps; int w, h; };
+
+// weight[t] == 0: the tap does not exist (weight 0 by the tent, or outside w x h).  bits[t]: on(q, .) of an existing tap, below count;
+// all of them for the tap that IS the pixel (its map bit is not looked at).  geom: bit t set where tap t passed the geometry test (the
+// pixel itself always does).
+struct UpsampleTaps { int X[4], Y[4]; uint32_t weight[4], bits[4], geom; };
+
+template <class Low>
+RTS_HD UpsampleTaps upsampleTaps(const UpsampleList& f, const Low& lo, V3 np, V3 pp, int x, int y) {
+    const int ux = x - (int)f.phaseX, uy = y - (int)f.phaseY;
+    const int X0 = ux >> 1, Y0 = uy >> 1;
+    const uint32_t ax = (uint32_t)(ux & 1), ay = (uint32_t)(uy & 1), all = (1u << f.count) - 1u;
+    const bool self = ax == 0u && ay == 0u;
+    UpsampleTaps t;
+    t.geom = 0u;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 4; ++k) {
+        const int X = X0 + (k & 1), Y = Y0 + (k >> 1);
+        const uint32_t wx = (k & 1) ? ax : 2u - ax, wy = (k >> 1) ? ay : 2u - ay;
+        const bool exists = wx * wy != 0u && X >= 0 && X < f.w && Y >= 0 && Y < f.h;
+        t.X[k] = X; t.Y[k] = Y;
+        t.weight[k] = exists ? wx * wy : 0u;
+        t.bits[k] = 0u;
+        if (!exists) continue;
+        if (self) { t.bits[k] = all; t.geom |= 1u << k; continue; }
+        t.bits[k] = lo.bits(X, Y) & all;
+        if (wideFilterGeom(lo, np, pp, X, Y, f.normalCosMin, f.planeEps)) t.geom |= 1u << k;
+    }
+    return t;
+}
+
+// The retrace map's byte: the lights of an active, unsampled pixel for which no tap is accepted.
+template <class Full, class Low>
+RTS_HD uint8_t upsampleRetracePixel(const UpsampleList& f, const Full& full, const Low& lo, int x, int y) {
+    const V3 np = full.normal(x, y);
+    if (isBackground(np)) return 0;
+    const uint32_t onp = full.bits(x, y) & ((1u << f.count) - 1u);
+    if (onp == 0u) return 0;
+    if ((((uint32_t)x ^ f.phaseX) & 1u) == 0u && (((uint32_t)y ^ f.phaseY) & 1u) == 0u) return 0;       // a sampled pixel
+    const UpsampleTaps t = upsampleTaps(f, lo, np, full.position(x, y), x, y);
+    uint32_t accepted = 0u;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 4; ++k)
+        if ((t.geom >> k) & 1u) accepted |= t.bits[k];
+    return (uint8_t)(onp & ~accepted);
+}
+
+// The upsampled bytes of the lights in `todo` (the lights below count whose keep bit is clear; not 0) at one pixel: byte8[l] for every
+// l in todo.  Returns the lights of todo that took the fallback (the tests' census; the kernels drop it).
+template <class Full, class Low>
+RTS_HD uint32_t upsamplePixel(const UpsampleList& f, const Full& full, const Low& lo, int x, int y, uint32_t todo, uint32_t* byte8) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) byte8[l] = 0u;
+    const V3 np = full.normal(x, y);
+    if (isBackground(np)) return 0u;
+    const uint32_t active = full.bits(x, y) & todo;
+    if (active == 0u) return 0u;
+    const UpsampleTaps t = upsampleTaps(f, lo, np, full.position(x, y), x, y);
+    uint32_t fell = 0u;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (uint32_t l = 0; l < 8; ++l) {
+        if (l >= f.count) break;
+        if (!((active >> l) & 1u)) continue;
+        uint32_t num = 0u, den = 0u, best = 0u, bestByte = 0u;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+        for (int k = 0; k < 4; ++k) {
+            if (!((t.bits[k] >> l) & 1u)) continue;                               // (0 for a tap that does not exist)
+            const uint32_t c = lo.byte(t.X[k], t.Y[k], l);
+            if ((t.geom >> k) & 1u) { num += t.weight[k] * c; den += t.weight[k]; }
+            if (t.weight[k] > best) { best = t.weight[k]; bestByte = c; }         // the fallback: largest weight, the first of equals
+        }
+        if (den != 0u) byte8[l] = (2u * num + den) / (2u * den);
+        else { byte8[l] = bestByte; fell |= 1u << l; }
+    }
+    return fell;
+}
+
 } // namespace rts_harness

@@ -201,3 +201,4 @@ extern "C" int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_const
 #include "rts_wide_mean.inc" // the wide filters fed from the accumulated mean of the count moments
 #include "rts_motion.inc" // the motion G-buffer pass: where the seen surface was in the previous frame's stream
 #include "rts_wide_propagated.inc" // the guided mean filter with a variance plane carried through the passes
+#include "rts_upsample.inc" // half-resolution light lists: subsample, retrace map, upsample

@@ -1423,3 +1423,108 @@ extern "C" int rtsh_wide_filter_propagated_mean_soft_light_list(const rts_soft_l
     const GuideMomentsCounts h{ GuideMoments{ mean, square, lengths, W, (size_t)W * H }, counts };
     return widePropagatedChain(f, r, h, positions, normals, lights_map, W, H, visibility, threads);
 }
+
+// ---- half-resolution light lists: subsample, retrace map, upsample (include/rts_scene.h; per-pixel rules in rts_closest_hit.h:
+// upsampleTaps, upsampleRetracePixel, upsamplePixel) ----
+namespace rts_harness {
+// Shared by the host and device forms: the refusals of the parameters and the frame, and the condensed form the per-pixel rules read.
+int makeUpsampleList(uint32_t count, const rtsh_upsample_params* p, uint32_t W, uint32_t H, UpsampleList* out) {
+    if (!p || !out || count == 0 || count > (uint32_t)RTS_MAX_LIST_LIGHTS || p->phase_x > 1u || p->phase_y > 1u ||
+        !std::isfinite(p->normal_cos_min) || !std::isfinite(p->plane_eps) || W == 0 || H == 0 || W > 0x7FFFFFF0u || H > 0x7FFFFFF0u)
+        return RTS_ERR_INVALID_ARG;
+    const uint32_t w = (W + 1u - p->phase_x) >> 1, h = (H + 1u - p->phase_y) >> 1;
+    if (w == 0 || h == 0) return RTS_ERR_INVALID_ARG;
+    *out = UpsampleList{ count, p->phase_x, p->phase_y, p->normal_cos_min, p->plane_eps, (int)w, (int)h };
+    return RTS_OK;
+}
+
+namespace {
+template <bool HARD>
+int upsampleListFrame(uint32_t count, const rtsh_upsample_params* params, const float* positions, const float* normals,
+                      const uint8_t* lights_map, const float* lo_positions, const float* lo_normals, const uint8_t* lo_lights_map,
+                      const uint8_t* lo_planes, const uint8_t* keep, uint32_t W, uint32_t H, uint8_t* planes, int threads) {
+    if (!positions || !normals || !lo_positions || !lo_normals || !lo_planes || !planes || planes == lo_planes) return RTS_ERR_INVALID_ARG;
+    UpsampleList f;
+    const int s = makeUpsampleList(count, params, W, H, &f);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const FrameTexels<false> full{ positions, normals, nullptr, lights_map, nullptr, W, n };
+    const FrameTexels<HARD> lo{ lo_positions, lo_normals, nullptr, lo_lights_map, lo_planes, (size_t)f.w, (size_t)f.w * (size_t)f.h };
+    const uint32_t all = (1u << count) - 1u;
+    parallelFor(n, 256, threads, [&](size_t i) {
+        const uint32_t kept = keep ? keep[i] & all : 0u, todo = all & ~kept;
+        if (todo == 0u) return;
+        uint32_t b[8];
+        upsamplePixel(f, full, lo, (int)(i % W), (int)(i / W), todo, b);
+        if (HARD) {
+            uint32_t bits = kept ? planes[i] & kept : 0u;
+            for (uint32_t l = 0; l < count; ++l)
+                if ((todo >> l) & 1u) bits |= (b[l] & 1u) << l;
+            planes[i] = (uint8_t)bits;
+        } else {
+            for (uint32_t l = 0; l < count; ++l)
+                if ((todo >> l) & 1u) planes[(size_t)l * n + i] = (uint8_t)b[l];
+        }
+    });
+    return RTS_OK;
+}
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_subsampled_size(uint32_t W, uint32_t H, uint32_t phase_x, uint32_t phase_y, uint32_t* w, uint32_t* h) {
+    const rtsh_upsample_params p{ phase_x, phase_y, 0.0f, 0.0f, { 0, 0, 0, 0 } };
+    UpsampleList f;
+    if (!w || !h || makeUpsampleList(1, &p, W, H, &f) != RTS_OK) return RTS_ERR_INVALID_ARG;
+    *w = (uint32_t)f.w;
+    *h = (uint32_t)f.h;
+    return RTS_OK;
+}
+
+extern "C" int rtsh_subsample_gbuffer(const rtsh_upsample_params* params, const float* positions, const float* normals,
+                                      const uint8_t* lights_map, uint32_t W, uint32_t H, float* lo_positions, float* lo_normals,
+                                      uint8_t* lo_lights_map) {
+    if (!positions || !normals || !lo_positions || !lo_normals || (lights_map && !lo_lights_map)) return RTS_ERR_INVALID_ARG;
+    UpsampleList f;
+    const int s = makeUpsampleList(1, params, W, H, &f);
+    if (s != RTS_OK) return s;
+    for (size_t Y = 0; Y < (size_t)f.h; ++Y)
+        for (size_t X = 0; X < (size_t)f.w; ++X) {
+            const size_t q = Y * (size_t)f.w + X, p = (2 * Y + f.phaseY) * W + (2 * X + f.phaseX);
+            memcpy(lo_positions + q * 4, positions + p * 4, 16);
+            memcpy(lo_normals + q * 4, normals + p * 4, 16);
+            if (lights_map) lo_lights_map[q] = lights_map[p];
+        }
+    return RTS_OK;
+}
+
+extern "C" int rtsh_upsample_retrace_map(uint32_t count, const rtsh_upsample_params* params, const float* positions, const float* normals,
+                                         const uint8_t* lights_map, const float* lo_positions, const float* lo_normals,
+                                         const uint8_t* lo_lights_map, uint32_t W, uint32_t H, uint8_t* retrace, int threads) {
+    if (!positions || !normals || !lo_positions || !lo_normals || !retrace) return RTS_ERR_INVALID_ARG;
+    UpsampleList f;
+    const int s = makeUpsampleList(count, params, W, H, &f);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const FrameTexels<false> full{ positions, normals, nullptr, lights_map, nullptr, W, n };
+    const FrameTexels<false> lo{ lo_positions, lo_normals, nullptr, lo_lights_map, nullptr, (size_t)f.w, (size_t)f.w * (size_t)f.h };
+    parallelFor(n, 256, threads, [&](size_t i) { retrace[i] = upsampleRetracePixel(f, full, lo, (int)(i % W), (int)(i / W)); });
+    return RTS_OK;
+}
+
+extern "C" int rtsh_upsample_light_list(const rts_light_list* list, const rtsh_upsample_params* params, const float* positions,
+                                        const float* normals, const uint8_t* lights_map, const float* lo_positions, const float* lo_normals,
+                                        const uint8_t* lo_lights_map, const uint8_t* lo_mask, const uint8_t* keep, uint32_t W, uint32_t H,
+                                        uint8_t* mask, int threads) {
+    if (!rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
+    return upsampleListFrame<true>(list->count, params, positions, normals, lights_map, lo_positions, lo_normals, lo_lights_map, lo_mask, keep,
+                                   W, H, mask, threads);
+}
+
+extern "C" int rtsh_upsample_soft_light_list(const rts_soft_light_list* list, const rtsh_upsample_params* params, const float* positions,
+                                             const float* normals, const uint8_t* lights_map, const float* lo_positions,
+                                             const float* lo_normals, const uint8_t* lo_lights_map, const uint8_t* lo_counts,
+                                             const uint8_t* keep, uint32_t W, uint32_t H, uint8_t* counts, int threads) {
+    if (!rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    return upsampleListFrame<false>(list->count, params, positions, normals, lights_map, lo_positions, lo_normals, lo_lights_map, lo_counts,
+                                    keep, W, H, counts, threads);
+}

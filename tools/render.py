@@ -2,6 +2,7 @@
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
                            [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]
+                                          [--half-res [--retrace] [--phase PX,PY]]
                                           [--filter R [--spread S] | --filter-passes K [--filter-guide K4 [--guide-history M]]] [--plane-eps E] [--normal-cos C]
                                                       [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]] [--moments-clamp R[:K4[:MARGIN]]] [--move SPEC]]]]
 
@@ -9,6 +10,12 @@
 ping-pong history -- and the LAST frame is lit from the accumulated visibility.  Frame k traces with the shared offsets table rotated
 by k entries; --orbit DEG turns the eye around the target by DEG per frame (default 0: a still camera); --max-length L (default 32) is
 the longest history.
+
+--half-res (with --soft-list N, the plain trace): the list is traced at HALF resolution and upsampled into the full-resolution count
+planes, all on the device: rtsh_subsample_gbuffer_device, rts_trace_soft_light_list_device at w x h,
+rtsh_upsample_soft_light_list_device; with --retrace also rtsh_upsample_retrace_map_device and a full-resolution trace under that map
+for the pixels no low-resolution tap stands for.  --phase PX,PY picks the sampled pixel of each quad (default 0,0; under --temporal the
+phase rotates per frame unless given).  The planes feed --filter*, --temporal and the combine exactly as the full-resolution trace's.
 
 --filter R (with --soft-list N): between trace and image the count planes go through rtsh_filter_soft_light_list_device -- an edge-aware
 tent window of (2R+1)^2 pixels that stops at normal and depth edges (--normal-cos, --plane-eps) -- and the frame is lit from the float
@@ -66,7 +73,38 @@ def parse_colors(text, count):
     return np.asarray(rows, np.float32)
 
 
-def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, distance_out="", colors="", filt=None):
+class HalfRes:
+    """--half-res: the list is traced at half resolution and upsampled into the full-resolution count planes, all on the device:
+    subsample -> trace at w x h -> (--retrace: retrace map -> full-resolution trace under it ->) upsample.  `phase`: (px, py), or None
+    to rotate it per frame so that --temporal sees all four pixels of a quad."""
+    ROTATION = ((0, 0), (1, 1), (1, 0), (0, 1))
+
+    def __init__(self, ctx, W, H, count, retrace, phase, normal_cos, plane_eps):
+        self.ctx, self.retrace, self.phase, self.thresholds = ctx, retrace, phase, (normal_cos, plane_eps)
+        m = ((W + 1) // 2) * ((H + 1) // 2)                              # the largest of the four phases' frames
+        self.d_lpos, self.d_lnrm, self.d_lmap, self.d_lo = ctx.malloc(m * 16), ctx.malloc(m * 16), ctx.malloc(m), ctx.malloc(count * m)
+        self.d_keep = ctx.malloc(W * H) if retrace else None
+
+    def trace(self, api, constants, lights, d_pos, d_nrm, d_map, W, H, d_counts, frame=0):
+        ctx = self.ctx
+        px, py = self.phase if self.phase is not None else self.ROTATION[frame % 4]
+        p = api.UpsampleParams.make(px, py, *self.thresholds)
+        w, h = api.subsampled_size(W, H, px, py)
+        api.subsample_gbuffer_device(ctx, p, d_pos, d_nrm, W, H, self.d_lpos, self.d_lnrm, d_lights_map=d_map, d_lo_lights_map=self.d_lmap)
+        ctx.trace_soft_light_list_device(constants, lights, self.d_lpos, w, h, self.d_lo, d_lights_map=self.d_lmap)
+        if self.retrace:
+            api.upsample_retrace_map_device(ctx, lights.count, p, d_pos, d_nrm, self.d_lpos, self.d_lnrm, W, H, self.d_keep, d_lights_map=d_map,
+                                            d_lo_lights_map=self.d_lmap)
+            ctx.trace_soft_light_list_device(constants, lights, d_pos, W, H, d_counts, d_lights_map=self.d_keep)
+        api.upsample_soft_light_list_device(ctx, lights, p, d_pos, d_nrm, self.d_lpos, self.d_lnrm, self.d_lo, W, H, d_counts, d_lights_map=d_map,
+                                            d_lo_lights_map=self.d_lmap, d_keep=self.d_keep)
+
+    def words(self):
+        return (f"half resolution, phase {'rotated per frame' if self.phase is None else self.phase}"
+                + (", edges retraced at full resolution" if self.retrace else ", edges from the nearest traced pixel"))
+
+
+def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, distance_out="", colors="", filt=None, half=None):
     """A frame lit by `count` area lights of `spp` samples: one list dispatch (adaptive with `probe` != 0; with `table` every light
     takes its samples from a per-pixel jitter table of `table` entries), then ONE combine pass over all the count planes and one
     read-back of the RGB frame."""
@@ -94,6 +132,9 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
                                                   d_lights_map=d_map, tables=(table,) * count if table else None)
     elif d_dist:
         ctx.trace_soft_light_list_distance_device(wl.constants, lights, d_pos, W, H, d_dist, d_counts, d_lights_map=d_map)
+    elif half is not None:
+        half.trace(api, wl.constants, lights, d_pos, d_nrm, d_map, W, H, d_counts)
+        print(half.words())
     else:
         ctx.trace_soft_light_list_device(wl.constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
     ctx.synchronize()
@@ -192,7 +233,7 @@ def parse_move(text, wl):
 
 
 def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, max_length, probe=0, table=0, colors="", clamp=None,
-                       filter_mean=False, move="", moments_clamp=None, propagate=None):
+                       filter_mean=False, move="", moments_clamp=None, propagate=None, half=None):
     """`frames` frames of a light list: per frame G-buffer, facing map, trace (the offsets table rotated by one entry per frame), filter
     and accumulation with ping-pong history; the last frame is lit from the accumulated visibility."""
     from raytracedshadows_amd import api, scenes
@@ -245,6 +286,8 @@ def soft_list_temporal(ctx, wl, W, H, count, spp, out, filt, frames, orbit_deg, 
         if probe:
             ctx.trace_soft_light_list_adaptive_device(constants, lights, (probe,) * count, d_pos, W, H, d_counts, d_lights_map=d_map,
                                                       tables=(table,) * count if table else None)
+        elif half is not None:
+            half.trace(api, constants, lights, d_pos, d_nrm, d_map, W, H, d_counts, frame=k)
         else:
             ctx.trace_soft_light_list_device(constants, lights, d_pos, W, H, d_counts, d_lights_map=d_map)
         tp = api.TemporalParams.from_cameras((eyes[k], sc.target, sc.fovy), (eyes[max(k - 1, 0)], sc.target, sc.fovy), W, H,
@@ -354,6 +397,13 @@ def main():
     ap.add_argument("--move", default="", metavar="AXIS:LO:HI:DX,DY,DZ",
                     help="with --temporal: displace the slab of the scene between the fractions LO and HI of its AXIS extent by (DX, DY, DZ) "
                          "per frame, refit, and drive the motion G-buffer pass and the motion forms of the accumulates (DESIGN.md 4.29)")
+    ap.add_argument("--half-res", action="store_true",
+                    help="with --soft-list N: trace at half resolution and upsample (rtsh_subsample_gbuffer_device, "
+                         "rtsh_upsample_soft_light_list_device); --normal-cos and --plane-eps are the taps' thresholds")
+    ap.add_argument("--retrace", action="store_true",
+                    help="with --half-res: trace the pixels no low-resolution tap stands for at full resolution (rtsh_upsample_retrace_map_device)")
+    ap.add_argument("--phase", default="", metavar="PX,PY",
+                    help="with --half-res: the sampled pixel of each quad (default 0,0; with --temporal: rotated per frame)")
     ap.add_argument("--colors", default="", metavar="r,g,b[;r,g,b...]",
                     help="with --soft-list N: the lights' colours, one triple for all of them or N separated by ';' (default 1/N each)")
     args = ap.parse_args()
@@ -391,6 +441,21 @@ def main():
                          "--guide-history M")
             if args.move and not args.temporal:
                 sys.exit("render: --move SPEC goes with --temporal F")
+            half = None
+            if args.half_res:
+                if args.adaptive or args.distance or args.table:
+                    sys.exit("render: --half-res goes with the plain --soft-list N trace: no --adaptive, --table or --distance")
+                try:
+                    phase = tuple(int(v) for v in args.phase.split(",")) if args.phase else None
+                except ValueError:
+                    phase = (2, 2)
+                if phase is not None and (len(phase) != 2 or not all(v in (0, 1) for v in phase)):
+                    sys.exit("render: --phase PX,PY takes 0 or 1 twice")
+                if phase is None and not args.temporal:
+                    phase = (0, 0)
+                half = HalfRes(ctx, W, H, args.soft_list, args.retrace, phase, args.normal_cos, args.plane_eps)
+            elif args.retrace or args.phase:
+                sys.exit("render: --retrace and --phase PX,PY go with --half-res")
             if args.temporal:
                 if filt is None or args.distance or args.refined:
                     sys.exit("render: --temporal F goes with --soft-list N and --filter R or --filter-passes K, without --distance and --refined")
@@ -415,9 +480,9 @@ def main():
                         sys.exit("render: --moments-clamp goes with --guide-history M or --filter-mean (where the moments pass runs)")
                     moments_clamp = api.MomentsClamp.make(*parts)
                 return soft_list_temporal(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, filt, args.temporal, args.orbit,
-                                          args.max_length, args.adaptive, args.table, args.colors, clamp, args.filter_mean, args.move, moments_clamp, propagate)
+                                          args.max_length, args.adaptive, args.table, args.colors, clamp, args.filter_mean, args.move, moments_clamp, propagate, half)
             return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance,
-                             args.colors, filt)
+                             args.colors, filt, half)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
         t0 = time.time()
         api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
