@@ -832,7 +832,11 @@ int rtsh_primary_gbuffer_motion_device(rts_ctx* ctx, const rts_vec4u* d_prev_pac
 
 /* The installed stream, copied into a caller's DEVICE buffer of capacity_vec4 vec4: one asynchronous device-to-device copy on `stream`
  * (ONE memcpy node under capture), so that a frame loop is snapshot -> rts_ctx_refit_bvh_device -> motion G-buffer with no host round
- * trip.  RTS_ERR_NO_BVH before rts_ctx_set_bvh; RTS_ERR_INVALID_ARG for a
+ * trip.  ORDER: rts_ctx_refit_bvh_device runs on the DEFAULT stream and waits for no stream of rts_stream_create (those do not
+ * synchronise with the default one): the copy is ordered before the refit when `stream` is the default stream (NULL), as the frame
+ * loop of tools/render.py issues it, or when the caller has synchronised `stream` before it calls the refit.  The refit returns when
+ * its kernels are done, so whatever is issued after it, on any stream, sees the refitted stream and a finished default-stream copy.
+ * RTS_ERR_NO_BVH before rts_ctx_set_bvh; RTS_ERR_INVALID_ARG for a
  * NULL ctx or buffer or too small a capacity, with nothing copied. */
 int rtsh_ctx_snapshot_bvh_device(rts_ctx* ctx, rts_vec4u* d_out, size_t capacity_vec4, void* stream);
 /* The installed stream's size in vec4, 0 before rts_ctx_set_bvh. */
