@@ -529,6 +529,54 @@ int rts_trace_soft_light_list_stripes_device(rts_ctx* ctx, const rts_constants* 
                                              const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
                                              uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts, void* stream);
 
+/* SPARSE LIGHT LISTS: the two list traces over a LIST of pixels instead of a row range -- for a mark that sets few bits (the retrace
+ * map of a half-resolution list, rts_scene.h; spot cones, light range, stencilled regions).  The block traces give a wave one 8 x 8
+ * tile, so a tile that holds ONE marked pixel costs a wave; here lane i of the launch owns entry i of the list (rtsh_compact_light_map*
+ * makes it from a map), 64 marked pixels per wave.  The arguments are those of rts_trace_soft_light_list_device and
+ * rts_trace_light_list_device without row range and stripes; in their place d_pixels (32-bit pixel indices y * W + x), d_n (ONE
+ * 32-bit word: the list's length) -- both ON THE DEVICE, read by the kernel, never read back -- and capacity (the entries d_pixels
+ * has room for).  The host forms take pixels and n from host memory.
+ *   Take every entry p = pixels[i] with i < min(*d_n, capacity) and p < W * H, and every l < count with on(p, l): lights_map == NULL
+ *   or bit l of lights_map[p] set.
+ *     soft list: counts[l * W * H + p] is the byte rts_trace_soft_light_list* writes there under the same map;
+ *     hard list: bit l of mask[p] is the bit rts_trace_light_list* writes; the other bits of that byte keep what they held (the byte is
+ *                read, changed and stored by the one lane that owns the entry).
+ *   EVERY OTHER BYTE of the planes is NOT TOUCHED: pixels not listed, pairs whose bit is clear, planes from count up.  That is what
+ *   rtsh_upsample_*_light_list* with `keep` expects in front of it.  An entry of W * H or above is skipped: nothing is read or written
+ *   for it.  A list that names a pixel twice gives the same bytes.  A listed pixel's position is read; an unlisted one's never is (NaN
+ *   allowed).  The result depends on no option and not on the order of the list: each byte is a function of (pixel, light, sample)
+ *   alone.
+ *   * RTS_ERR_INVALID_ARG, nothing written, no counter moved: what rts_trace_soft_light_list* / rts_trace_light_list* refuse of the
+ *     list, the planes and the frame; NULL pixels or n; capacity 0.  Behind those, without a BVH: RTS_ERR_NO_BVH.
+ *   * ONE kernel, the lane-per-ray walk with work sharing of "shadowSoftLightListShareKernel" / "shadowLightListShareKernel" -- lights in
+ *     order, samples in order, the same ray set-up, so every ray has the same bits -- launched as ceil(capacity / 256) workgroups of
+ *     four waves; a wave whose first entry lies at or beyond min(*d_n, capacity) leaves at once.  Every exit is wave-uniform, there is
+ *     no workgroup barrier.  "kernel", "soft_split" and every other option choose nothing here.
+ *   * FROM WHAT SHARE OF MARKED PIXELS the masked block trace is the better call: AT EVERY SHARE MEASURED, 0.06 % to 66 % of the frame
+ *     (DESIGN.md 4.33's tables, MI355X, one run): compaction plus the sparse trace took 1.5-5.3 times the masked trace on retrace maps
+ *     of 0.06-0.54 % and 1.9-2.7 times on dense maps.  The list's few waves each walk lights x samples rays one after the other with the
+ *     lane-per-ray walk; the masked packet trace opens more tiles but its waves are short and many.  These calls are exact and kept for
+ *     marks and walks to come; today rts_trace_*_light_list* under the map is the faster call.
+ *   * the device forms are asynchronous, allocate nothing and read nothing back; under graph capture each adds ONE kernel node --
+ *     constants, list, options and capacity by value, the POINTERS d_pixels and d_n captured: a replay traces whatever list the buffers
+ *     hold then.  The host forms copy in the frame, the caller's planes and the list, trace, copy out the planes and synchronise; n == 0
+ *     is RTS_OK and nothing is copied.
+ *   * get-only option "sparse_list_traces": launches of either kernel so far (no other counter moves for them);
+ *     rts_ctx_last_kernel_name then names "shadowSoftLightListSparseKernel" or "shadowLightListSparseKernel".
+ *   * OUT OF SCOPE: the distance, adaptive and jittered forms; row ranges and stripes. */
+int rts_trace_light_list_sparse(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* positions,
+                                const uint8_t* lights_map, uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint8_t* mask);
+int rts_trace_light_list_sparse_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* d_positions,
+                                       const uint8_t* d_lights_map, uint32_t W, uint32_t H, const uint32_t* d_pixels, const uint32_t* d_n,
+                                       uint32_t capacity, uint8_t* d_mask, void* stream);
+int rts_trace_soft_light_list_sparse(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list, const float* positions,
+                                     const uint8_t* lights_map, uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n,
+                                     uint8_t* counts);
+int rts_trace_soft_light_list_sparse_device(rts_ctx* ctx, const rts_constants* constants, const rts_soft_light_list* list,
+                                            const float* d_positions, const uint8_t* d_lights_map, uint32_t W, uint32_t H,
+                                            const uint32_t* d_pixels, const uint32_t* d_n, uint32_t capacity, uint8_t* d_counts,
+                                            void* stream);
+
 /* SOFT LIGHT LIST DISTANCE: a soft light list with the NEAREST BLOCKER per light beside its count -- one DISTANCE PLANE per light, what
  * contact-hardening penumbrae, a distance-guided denoiser or a distance fade want of several area lights, without one
  * rts_trace_soft_distance* dispatch per light.  The arguments are those of rts_trace_soft_light_list*, with `distances` in front of

@@ -1068,6 +1068,37 @@ int rtsh_upsample_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_list
                                          const uint8_t* d_lo_counts, const uint8_t* d_keep, uint32_t W, uint32_t H, uint8_t* d_counts,
                                          void* stream);
 
+/* COMPACTED LIGHT MAPS: a light map -> the dense LIST of its marked pixels, for the sparse list traces (rts.h, SPARSE LIGHT LISTS).  A
+ * masked block trace opens every 8 x 8 tile that holds one marked pixel; a mark that sets 1 % of the bits along every silhouette costs
+ * a fifth to a third of a whole trace.  The list lets a trace put 64 marked pixels into every wave.  Integers only, no float anywhere.
+ * THE RULE, for a map of W x H bytes and count = 1..8 lights:
+ *   MARKED: pixel p = y * W + x is marked when lights_map[p] & ((1 << count) - 1) is not 0.
+ *   TILE ORDER: the frame is cut into tiles of 8 x 8 pixels, tile (tx, ty) = the pixels x in [8 tx, 8 tx + 8), y in [8 ty, 8 ty + 8)
+ *     that lie inside the frame; there are ceil(W / 8) x ceil(H / 8) tiles.  The tiles are taken in row-major order (ty ascending, then
+ *     tx ascending), the pixels of a tile in row-major order (y ascending, then x ascending).  The list holds the marked pixels in that
+ *     order, as 32-bit indices p.  So 64 consecutive entries come from one tile or from neighbouring tiles of a tile row (and, at a
+ *     row's end, the next row's first tiles): a wave's rays stay near each other.
+ *   *n receives the number of marked pixels of the WHOLE frame; it may exceed capacity.  pixels[0 .. min(n, capacity)) receive the first
+ *   entries of the list.  No entry from min(n, capacity) on is touched.  The order is fixed by the rule: the host form, the device form
+ *   and a restatement from this text agree word for word.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: count 0 or above 8; a NULL map, list or n; W or H equal to 0; W * H above
+ *     2^31; capacity 0; in the device form a NULL ctx or scratch.
+ *   * rtsh_compact_scratch_bytes(W, H): the bytes of d_scratch, 4 * (tiles + ceil(tiles / 1024)); 0 for a frame that is refused.
+ *   * device form: DEVICE buffers, asynchronous on `stream`, allocates nothing and reads nothing back, needs no BVH; d_scratch and d_n
+ *     need 4-byte alignment.  FOUR kernels (rtsh_compact_nodes()): a count per tile (one wave per tile: ballot and popcount), an
+ *     exclusive sum inside groups of 1024 tiles, an exclusive sum of the groups' totals by ONE workgroup (which also writes *d_n), the
+ *     write pass (one wave per tile again).  No workgroup waits for another one: each kernel reads what the kernel in front of it has
+ *     finished.  Under graph capture it adds those four kernel nodes and no other node; the pointers are captured, so a replay compacts
+ *     whatever map the buffer holds then.
+ *   * SIZING capacity: W * H always suffices.  A renderer that knows its mark sizes it from the mark; a frame whose
+ *     list does not fit is seen from *n > capacity, and the first `capacity` entries are still valid. */
+size_t rtsh_compact_scratch_bytes(uint32_t W, uint32_t H);
+int rtsh_compact_nodes(void);
+int rtsh_compact_light_map(uint32_t count, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t* pixels, uint32_t capacity,
+                           uint32_t* n_out);
+int rtsh_compact_light_map_device(rts_ctx* ctx, uint32_t count, const uint8_t* d_lights_map, uint32_t W, uint32_t H, uint32_t* d_pixels,
+                                  uint32_t capacity, uint32_t* d_n, void* d_scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -451,6 +451,20 @@ _sig("rtsh_facing_lights", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(Li
      C.c_void_p)
 _sig("rtsh_facing_lights_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_light_list_sparse", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p)
+_sig("rts_trace_light_list_sparse_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_soft_light_list_sparse", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p)
+_sig("rts_trace_soft_light_list_sparse_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(SoftLightList), C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_compact_scratch_bytes", C.c_size_t, C.c_uint32, C.c_uint32)
+_sig("rtsh_compact_nodes", C.c_int)
+_sig("rtsh_compact_light_map", C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, _u32p)
+_sig("rtsh_compact_light_map_device", C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+     C.c_void_p, C.c_void_p)
+COMPACT_NODES = int(_lib.rtsh_compact_nodes())      # kernel nodes of compact_light_map_device under graph capture (rts_scene.h)
 _sig("rts_device_malloc", C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t)
 _sig("rts_device_free", C.c_int, C.c_void_p, C.c_void_p)
 _sig("rts_memcpy_h2d", C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -1084,6 +1098,52 @@ class ShadowContext:
                                                              C.c_void_p(d_lights_map or 0), width, height, band_rows, n_stripes, stripe,
                                                              C.c_void_p(d_counts), C.c_void_p(stream or 0)),
                "rts_trace_soft_light_list_stripes_device")
+
+    # -- sparse light lists (include/rts.h): the two list traces over a list of pixels, the marked pairs alone written --
+    def _sparse_host(self, fn, name, constants, lights, positions, width, height, pixels, planes, planes_shape, lights_map):
+        positions, lights_map = _frame_inputs(name, positions, width, height, lights_map, "lights_map")
+        pixels = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        if planes is None or planes.dtype != np.uint8 or not planes.flags.c_contiguous or planes.size < int(np.prod(planes_shape)):
+            raise RtsError(1, f"{name}: the planes must be contiguous uint8 of the list's planes (they are merged into, in place)")
+        if pixels.size == 0:
+            pixels = np.zeros(1, np.uint32)
+            n = 0
+        else:
+            n = pixels.size
+        _check(fn(self._h, C.byref(constants), _ref(lights), _ptr(positions), _ptr_or_none(lights_map), width, height, _ptr(pixels), n,
+                  _ptr(planes)), name)
+        return planes
+
+    def trace_light_list_sparse(self, constants, lights, positions, width, height, pixels, mask, lights_map=None):
+        """Host-pointer sparse trace of a hard light list: ``mask`` (``uint8[H, W]``) is MERGED INTO, in place: bit ``l`` of
+        ``mask[p]`` for every ``p`` in ``pixels`` (uint32 indices ``y * W + x``) and ``l`` with bit ``l`` of ``lights_map[p]`` set
+        (None: every ``l < count``); nothing else is touched.  Returns ``mask``."""
+        return self._sparse_host(_lib.rts_trace_light_list_sparse, "rts_trace_light_list_sparse", constants, lights, positions, width, height,
+                                 pixels, mask, (height, width), lights_map)
+
+    def trace_light_list_sparse_device(self, constants, lights, d_positions, width, height, d_pixels, d_n, capacity, d_mask,
+                                       d_lights_map=None, stream=None):
+        """Device pointers, asynchronous, one kernel: d_pixels = ``capacity`` uint32 entries, d_n = one uint32 (the list's length), both
+        read on the device; the first ``min(*d_n, capacity)`` entries are traced."""
+        _check(_lib.rts_trace_light_list_sparse_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
+                                                       C.c_void_p(d_lights_map or 0), width, height, C.c_void_p(d_pixels or 0),
+                                                       C.c_void_p(d_n or 0), capacity, C.c_void_p(d_mask), C.c_void_p(stream or 0)),
+               "rts_trace_light_list_sparse_device")
+
+    def trace_soft_light_list_sparse(self, constants, lights, positions, width, height, pixels, counts, lights_map=None):
+        """Host-pointer sparse trace of a soft light list: ``counts`` (``uint8[count, H, W]``) is MERGED INTO, in place: plane ``l`` at
+        every ``p`` in ``pixels`` with bit ``l`` of ``lights_map[p]`` set (None: every ``l < count``).  Returns ``counts``."""
+        count = lights.count if lights is not None and 1 <= lights.count <= 8 else 1
+        return self._sparse_host(_lib.rts_trace_soft_light_list_sparse, "rts_trace_soft_light_list_sparse", constants, lights, positions, width,
+                                 height, pixels, counts, (count, height, width), lights_map)
+
+    def trace_soft_light_list_sparse_device(self, constants, lights, d_positions, width, height, d_pixels, d_n, capacity, d_counts,
+                                            d_lights_map=None, stream=None):
+        """Device pointers, asynchronous, one kernel: as trace_light_list_sparse_device, d_counts = count planes of width * height bytes."""
+        _check(_lib.rts_trace_soft_light_list_sparse_device(self._h, C.byref(constants), _ref(lights), C.c_void_p(d_positions),
+                                                            C.c_void_p(d_lights_map or 0), width, height, C.c_void_p(d_pixels or 0),
+                                                            C.c_void_p(d_n or 0), capacity, C.c_void_p(d_counts), C.c_void_p(stream or 0)),
+               "rts_trace_soft_light_list_sparse_device")
 
     # -- soft light list distance (include/rts.h): a soft light list with the nearest blocker per light beside its count --
     def trace_soft_light_list_distance(self, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None,
@@ -1933,6 +1993,78 @@ def upsample_light_list_device(ctx, light_list, params, d_positions, d_normals, 
     _upsample_list_device(_lib.rtsh_upsample_light_list_device, "rtsh_upsample_light_list_device", ctx, light_list, params, d_positions,
                           d_normals, d_lo_positions, d_lo_normals, d_lo_mask, width, height, d_mask, d_lights_map, d_lo_lights_map, d_keep,
                           stream)
+
+
+def compact_scratch_bytes(width, height):
+    """The bytes of ``d_scratch`` of ``compact_light_map_device`` (rtsh_compact_scratch_bytes); 0 for a frame it refuses."""
+    return int(_lib.rtsh_compact_scratch_bytes(width, height))
+
+
+def compact_light_map(count, lights_map, capacity=None, out=None):
+    """The list of a light map's marked pixels on the host (rtsh_compact_light_map): ``(pixels, n)``.  ``lights_map``: ``uint8[H, W]``;
+    a pixel is marked when its byte has a bit below ``count``.  ``pixels``: uint32 indices ``y * W + x`` in TILE ORDER (8 x 8 tiles
+    row-major over the frame, pixels row-major inside a tile), the first ``min(n, capacity)`` of them written into ``out`` (an array
+    of ``capacity`` uint32; made here, of ``capacity`` = W * H entries by default, and then returned cut to the entries written);
+    ``n``: the marked pixels of the whole frame."""
+    lights_map = np.ascontiguousarray(lights_map, np.uint8)
+    if lights_map.ndim != 2:
+        raise RtsError(1, "rtsh_compact_light_map: the map must be uint8[H, W]")
+    H, W = lights_map.shape
+    made = out is None
+    if made:
+        capacity = W * H if capacity is None else capacity
+        out = np.zeros(max(int(capacity), 1), np.uint32)
+    elif capacity is None:
+        capacity = out.size
+    if out.dtype != np.uint32 or not out.flags.c_contiguous or out.size < capacity:
+        raise RtsError(1, "rtsh_compact_light_map: out must be contiguous uint32 of at least capacity entries")
+    n = C.c_uint32(0)
+    _check(_lib.rtsh_compact_light_map(count, _ptr(lights_map), W, H, _ptr(out), capacity, C.byref(n)), "rtsh_compact_light_map")
+    n = int(n.value)
+    return (out[:min(n, capacity)] if made else out), n
+
+
+def compact_light_map_device(ctx, count, d_lights_map, width, height, d_pixels, capacity, d_n, d_scratch, stream=None):
+    """The same on the GPU: device pointers, d_pixels = ``capacity`` uint32, d_n = one uint32, d_scratch = ``compact_scratch_bytes``
+    bytes; ``COMPACT_NODES`` kernels, asynchronous, nothing read back."""
+    _check(_lib.rtsh_compact_light_map_device(ctx.handle, count, C.c_void_p(d_lights_map or 0), width, height, C.c_void_p(d_pixels or 0),
+                                              capacity, C.c_void_p(d_n or 0), C.c_void_p(d_scratch or 0), C.c_void_p(stream or 0)),
+           "rtsh_compact_light_map_device")
+
+
+def _sparse_twin(trace, count, hard, packed, constants, lights, positions, width, height, pixels, planes, lights_map, threads):
+    """The host twin of a sparse trace: the block trace's twin under the map cut down to the listed pixels, merged into ``planes`` at
+    the listed pairs alone."""
+    n = width * height
+    pixels = np.asarray(pixels, np.uint32).reshape(-1)
+    listed = np.zeros(n, bool)
+    listed[pixels[pixels < n]] = True
+    below = (1 << count) - 1
+    on = np.full(n, below, np.uint8) if lights_map is None else (np.ascontiguousarray(lights_map, np.uint8).reshape(-1) & below)
+    on = np.where(listed, on, 0).astype(np.uint8)                       # an unlisted pixel sends no ray: its position is never read
+    traced = trace(packed, constants, lights, positions, width, height, lights_map=on.reshape(height, width), threads=threads)
+    if hard:
+        flat, got = planes.reshape(-1), traced.reshape(-1)
+        flat[:] = (flat & ~on) | (got & on)
+    else:
+        flat, got = planes.reshape(-1)[:count * n].reshape(count, n), traced.reshape(count, n)
+        for l in range(count):
+            sel = ((on >> l) & 1).astype(bool)
+            flat[l][sel] = got[l][sel]
+    return planes
+
+
+def light_list_sparse(packed, constants, lights, positions, width, height, pixels, mask, lights_map=None, threads=0):
+    """The sparse hard light list trace on the host (no GPU): ``api.light_list`` under the map, merged into ``mask`` (``uint8[H, W]``,
+    contiguous, changed in place and returned) at bit ``l`` of the listed pixels with bit ``l`` of the map set; nothing else changes."""
+    return _sparse_twin(light_list, lights.count, True, packed, constants, lights, positions, width, height, pixels, mask, lights_map, threads)
+
+
+def soft_light_list_sparse(packed, constants, lights, positions, width, height, pixels, counts, lights_map=None, threads=0):
+    """The sparse soft light list trace on the host (no GPU): ``api.soft_light_list`` under the map, merged into ``counts``
+    (``uint8[count, H, W]``, contiguous, changed in place and returned) at the listed pairs alone."""
+    return _sparse_twin(soft_light_list, lights.count, False, packed, constants, lights, positions, width, height, pixels, counts, lights_map,
+                        threads)
 
 
 def wide_filter_scratch_bytes(count, width, height):

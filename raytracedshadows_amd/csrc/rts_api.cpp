@@ -10,6 +10,7 @@
 #include "rts_soft_light_list.h"
 #include "rts_soft_light_list_adaptive.h"
 #include "rts_soft_light_list_distance.h"
+#include "rts_light_list_sparse.h"
 #include "rts_dispatch.h"
 #include "rts_args.h"
 #include "rts_refit.h"
@@ -52,6 +53,7 @@ struct rts_ctx {
     uint64_t softListJitterTraces = 0;                // launches of a jittered adaptive soft light list kernel (get-only option "soft_list_jitter_traces")
     uint64_t softLightListTraces = 0;                 // launches of a soft light list kernel (get-only option "soft_light_list_traces")
     uint64_t softListDistanceTraces = 0;              // launches of a soft light list distance kernel (get-only option "soft_list_distance_traces")
+    uint64_t sparseListTraces = 0;                    // launches of a sparse light list kernel, hard or soft (get-only option "sparse_list_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
     int packetShare = 4;
@@ -565,6 +567,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "soft_list_adaptive_traces")) { *value = (int)(c->softListAdaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_list_jitter_traces")) { *value = (int)(c->softListJitterTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_light_list_traces")) { *value = (int)(c->softLightListTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "sparse_list_traces")) { *value = (int)(c->sparseListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_list_distance_traces")) { *value = (int)(c->softListDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
     if (!strcmp(key, "tile_order_tiles")) { *value = (int)c->tileOrderCount; return RTS_OK; }
@@ -1205,6 +1208,86 @@ int rts_trace_soft_light_list(rts_ctx* c, const rts_constants* k, const rts_soft
     StagedRows r{ Staged::SoftLightList, k, list, positions, lights_map, W, H, row_begin, row_end };
     r.mask = counts;
     return traceStagedRows(c, r);
+}
+
+// ---- sparse light lists (include/rts.h): the two list traces over a LIST of pixels, the marked pairs alone written -----------------
+// One launch of a sparse kernel (rts_light_list_sparse.inc): the list trace's own argument block for the whole frame -- beginFrame's
+// checks with the list's among them, so what the list traces refuse is refused here in the same order, a missing BVH behind the
+// arguments -- and the pixel list beside it.  No grid of tiles: "kernel", "soft_split" and the other options choose nothing.
+static int launchSparse(rts_ctx* c, const TraceParams& p, bool soft, const uint32_t* d_pixels, const uint32_t* d_n, uint32_t capacity,
+                        void* stream) {
+    ++c->launches;
+    ++c->sparseListTraces;
+    const char* name = "";
+    const hipError_t e = soft ? rts::launchShadowSoftLightListSparse(p, d_pixels, d_n, capacity, (hipStream_t)stream, &name)
+                              : rts::launchShadowLightListSparse(p, d_pixels, d_n, capacity, (hipStream_t)stream, &name);
+    c->lastKernel = name;
+    return hipStatus(e);
+}
+
+int rts_trace_light_list_sparse_device(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* d_positions,
+                                       const uint8_t* d_lights_map, uint32_t W, uint32_t H, const uint32_t* d_pixels, const uint32_t* d_n,
+                                       uint32_t capacity, uint8_t* d_mask, void* stream) {
+    TraceParams p; uint32_t rows = 0; int s;
+    const bool ok = d_mask && rts::lightListOk(list) && rts::sparseListOk(d_pixels, d_n, capacity);
+    if (beginFrame(c, k, d_positions, d_mask, ok, Dispatch::ofRows(W, H, 0, H), p, &rows, &s) != Begin::Go) return s;
+    setListHeader(p, k, list->count, d_lights_map);
+    for (uint32_t l = 0; l < list->count; ++l) {
+        for (int i = 0; i < 3; ++i) p.offsets[l][i] = list->lights[l].xyz[i];
+        p.offsets[l][3] = list->lights[l].type == RTS_LIGHT_POINT ? 1.0f : 0.0f;
+    }
+    return launchSparse(c, p, false, d_pixels, d_n, capacity, stream);
+}
+
+int rts_trace_soft_light_list_sparse_device(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* d_positions,
+                                            const uint8_t* d_lights_map, uint32_t W, uint32_t H, const uint32_t* d_pixels,
+                                            const uint32_t* d_n, uint32_t capacity, uint8_t* d_counts, void* stream) {
+    TraceParams p; uint32_t rows = 0; int s;
+    const bool ok = d_counts && rts::softListOk(list) && rts::sparseListOk(d_pixels, d_n, capacity);
+    if (beginFrame(c, k, d_positions, d_counts, ok, Dispatch::ofRows(W, H, 0, H), p, &rows, &s) != Begin::Go) return s;
+    setSoftList(p, k, list, d_lights_map);
+    return launchSparse(c, p, true, d_pixels, d_n, capacity, stream);
+}
+
+// The host forms: the whole frame travels -- positions, map and the caller's PLANES, which the trace merges into --, the list and its
+// length behind them in the distances' staging buffer; the planes come back.  An empty list is RTS_OK with nothing copied.
+static int traceSparseStaged(rts_ctx* c, const rts_constants* k, const void* list, bool soft, const float* positions, const uint8_t* lights_map,
+                             uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint8_t* planes) {
+    if (!c->d_bvh) return RTS_ERR_NO_BVH;
+    if (n == 0) return RTS_OK;
+    RTS_HIP(hipSetDevice(c->device));
+    const size_t frame = (size_t)W * H, count = soft ? ((const rts_soft_light_list*)list)->count : 1u;
+    int s = ensure(&c->d_in, &c->inBytes, frame * 16);
+    if (s == RTS_OK) s = ensure(&c->d_out, &c->outBytes, frame * count);
+    if (s == RTS_OK && lights_map) s = ensure(&c->d_act, &c->actBytes, frame);
+    if (s == RTS_OK) s = ensure(&c->d_dist, &c->distBytes, ((size_t)n + 1u) * 4u);
+    if (s != RTS_OK) return s;
+    uint32_t* const d_n = (uint32_t*)c->d_dist;
+    RTS_HIP(hipMemcpy(c->d_in, positions, frame * 16, hipMemcpyHostToDevice));
+    RTS_HIP(hipMemcpy(c->d_out, planes, frame * count, hipMemcpyHostToDevice));
+    if (lights_map) RTS_HIP(hipMemcpy(c->d_act, lights_map, frame, hipMemcpyHostToDevice));
+    RTS_HIP(hipMemcpy(d_n, &n, 4, hipMemcpyHostToDevice));
+    RTS_HIP(hipMemcpy(d_n + 1, pixels, (size_t)n * 4u, hipMemcpyHostToDevice));
+    const uint8_t* const d_map = lights_map ? (const uint8_t*)c->d_act : nullptr;
+    s = soft ? rts_trace_soft_light_list_sparse_device(c, k, (const rts_soft_light_list*)list, (const float*)c->d_in, d_map, W, H, d_n + 1, d_n,
+                                                       n, (uint8_t*)c->d_out, nullptr)
+             : rts_trace_light_list_sparse_device(c, k, (const rts_light_list*)list, (const float*)c->d_in, d_map, W, H, d_n + 1, d_n, n,
+                                                  (uint8_t*)c->d_out, nullptr);
+    if (s != RTS_OK) return s;
+    RTS_HIP(hipMemcpy(planes, c->d_out, frame * count, hipMemcpyDeviceToHost));
+    return RTS_OK;
+}
+
+int rts_trace_light_list_sparse(rts_ctx* c, const rts_constants* k, const rts_light_list* list, const float* positions, const uint8_t* lights_map,
+                                uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint8_t* mask) {
+    if (!c || !k || !positions || !mask || !pixels || !stagedListFrameOk(W, H, 0, H) || !rts::lightListOk(list)) return RTS_ERR_INVALID_ARG;
+    return traceSparseStaged(c, k, list, false, positions, lights_map, W, H, pixels, n, mask);
+}
+
+int rts_trace_soft_light_list_sparse(rts_ctx* c, const rts_constants* k, const rts_soft_light_list* list, const float* positions,
+                                     const uint8_t* lights_map, uint32_t W, uint32_t H, const uint32_t* pixels, uint32_t n, uint8_t* counts) {
+    if (!c || !k || !positions || !counts || !pixels || !stagedListFrameOk(W, H, 0, H) || !rts::softListOk(list)) return RTS_ERR_INVALID_ARG;
+    return traceSparseStaged(c, k, list, true, positions, lights_map, W, H, pixels, n, counts);
 }
 
 // ---- soft light list distance (include/rts.h): a soft light list with the nearest blocker per light beside its count --------------

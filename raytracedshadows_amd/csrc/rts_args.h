@@ -75,6 +75,11 @@ inline bool softListHasTable(const rts_soft_light_list* list, const uint32_t* ta
     return false;
 }
 
+// the pixel list of a sparse list trace: the list and its length (on the device in the device forms) and room for at least one entry
+inline bool sparseListOk(const uint32_t* pixels, const uint32_t* n, uint32_t capacity) {
+    return pixels && n && capacity != 0;
+}
+
 // a frame and its row range [row_begin, row_end), which may be empty
 inline bool frameRowsOk(uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end) {
     return W != 0 && H != 0 && row_begin <= row_end && row_end <= H;

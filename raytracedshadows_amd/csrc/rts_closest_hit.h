@@ -1209,4 +1209,27 @@ RTS_HD uint32_t upsamplePixel(const UpsampleList& f, const Full& full, const Low
     return fell;
 }
 
+// COMPACTED LIGHT MAPS (include/rts_scene.h, rtsh_compact_light_map*): the tile order of the list and the mark.  Integers only.
+// Tiles of 8 x 8 pixels, row-major over the frame; slot k = 0..63 of a tile is its pixel (k & 7, k >> 3), so the slots in order are the
+// tile's pixels row-major.  The host twin walks the tiles and slots in order; the kernels give a tile to a wave and slot k to lane k.
+constexpr int kCompactNodes = 4;                                                   // kernels of the device form (rts_compact.inc)
+constexpr uint32_t kCompactScanLanes = 256, kCompactScanPerLane = 4;
+constexpr uint32_t kCompactScanTiles = kCompactScanLanes * kCompactScanPerLane;    // tiles one scan workgroup handles
+struct CompactFrame { uint32_t W, H, tilesX, tiles, allBelowCount; };
+
+RTS_HD bool makeCompactFrame(uint32_t count, uint32_t W, uint32_t H, CompactFrame* out) {
+    if (count == 0u || count > 8u || W == 0u || H == 0u || (uint64_t)W * H > (1ull << 31)) return false;
+    const uint64_t tilesX = ((uint64_t)W + 7u) / 8u, tilesY = ((uint64_t)H + 7u) / 8u;          // (tilesX * tilesY <= 2^28 + ...: 32 bits hold it)
+    *out = CompactFrame{ W, H, (uint32_t)tilesX, (uint32_t)(tilesX * tilesY), (1u << count) - 1u };
+    return true;
+}
+// -> whether slot k of tile t lies in the frame; *p: its pixel index y * W + x
+RTS_HD bool compactSlotPixel(const CompactFrame& f, uint32_t t, uint32_t k, uint32_t* p) {
+    const uint32_t ty = t / f.tilesX, tx = t - ty * f.tilesX;
+    const uint32_t x = tx * 8u + (k & 7u), y = ty * 8u + (k >> 3);
+    *p = y * f.W + x;                                                                           // (read only where the slot is in the frame)
+    return x < f.W && y < f.H;
+}
+RTS_HD bool compactMarked(const CompactFrame& f, uint8_t mapByte) { return (mapByte & f.allBelowCount) != 0u; }
+
 } // namespace rts_harness

@@ -296,3 +296,5 @@ hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
 #include "rts_soft_light_list_adaptive.inc"
 // soft light list distance: a distance plane per light beside its count plane (its launch is declared in rts_soft_light_list_distance.h)
 #include "rts_soft_light_list_distance.inc"
+// sparse light lists: the two lane-per-ray list kernels fed from a list of pixels (their launches are declared in rts_light_list_sparse.h)
+#include "rts_light_list_sparse.inc"

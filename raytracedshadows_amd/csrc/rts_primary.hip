@@ -202,3 +202,4 @@ extern "C" int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_const
 #include "rts_motion.inc" // the motion G-buffer pass: where the seen surface was in the previous frame's stream
 #include "rts_wide_propagated.inc" // the guided mean filter with a variance plane carried through the passes
 #include "rts_upsample.inc" // half-resolution light lists: subsample, retrace map, upsample
+#include "rts_compact.inc" // a light map compacted into the list of its marked pixels, for the sparse list traces

@@ -1528,3 +1528,30 @@ extern "C" int rtsh_upsample_soft_light_list(const rts_soft_light_list* list, co
     return upsampleListFrame<false>(list->count, params, positions, normals, lights_map, lo_positions, lo_normals, lo_lights_map, lo_counts,
                                     keep, W, H, counts, threads);
 }
+
+// ---- compacted light maps (include/rts_scene.h; the tile order and the mark in rts_closest_hit.h: makeCompactFrame, compactSlotPixel,
+// compactMarked) ----
+extern "C" int rtsh_compact_light_map(uint32_t count, const uint8_t* lights_map, uint32_t W, uint32_t H, uint32_t* pixels, uint32_t capacity,
+                                      uint32_t* n_out) {
+    CompactFrame f;
+    if (!lights_map || !pixels || !n_out || capacity == 0 || !makeCompactFrame(count, W, H, &f)) return RTS_ERR_INVALID_ARG;
+    uint32_t n = 0;
+    for (uint32_t t = 0; t < f.tiles; ++t)
+        for (uint32_t k = 0; k < 64u; ++k) {
+            uint32_t p;
+            if (!compactSlotPixel(f, t, k, &p) || !compactMarked(f, lights_map[p])) continue;
+            if (n < capacity) pixels[n] = p;
+            ++n;
+        }
+    *n_out = n;
+    return RTS_OK;
+}
+
+extern "C" size_t rtsh_compact_scratch_bytes(uint32_t W, uint32_t H) {
+    CompactFrame f;
+    if (!makeCompactFrame(1, W, H, &f)) return 0;
+    const size_t groups = ((size_t)f.tiles + kCompactScanTiles - 1u) / kCompactScanTiles;
+    return ((size_t)f.tiles + groups) * sizeof(uint32_t);
+}
+
+extern "C" int rtsh_compact_nodes(void) { return kCompactNodes; }

@@ -2,7 +2,7 @@
 
     python tools/render.py --config atrium_1080p --out atrium.ppm [--spp 16] [--save-bvh x.bvh] [--cull] [--adaptive K [--refined FILE.ppm]]
                            [--soft-list N [--colors r,g,b[;r,g,b...]] [--adaptive K [--refined FILE.ppm]] [--distance FILE.ppm]
-                                          [--half-res [--retrace] [--phase PX,PY]]
+                                          [--half-res [--retrace [--retrace-sparse]] [--phase PX,PY]]
                                           [--filter R [--spread S] | --filter-passes K [--filter-guide K4 [--guide-history M]]] [--plane-eps E] [--normal-cos C]
                                                       [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]] [--moments-clamp R[:K4[:MARGIN]]] [--move SPEC]]]]
 
@@ -15,7 +15,9 @@ the longest history.
 planes, all on the device: rtsh_subsample_gbuffer_device, rts_trace_soft_light_list_device at w x h,
 rtsh_upsample_soft_light_list_device; with --retrace also rtsh_upsample_retrace_map_device and a full-resolution trace under that map
 for the pixels no low-resolution tap stands for.  --phase PX,PY picks the sampled pixel of each quad (default 0,0; under --temporal the
-phase rotates per frame unless given).  The planes feed --filter*, --temporal and the combine exactly as the full-resolution trace's.
+phase rotates per frame unless given).  --retrace-sparse (with --retrace): the retrace map is compacted into the list of its marked
+pixels (rtsh_compact_light_map_device) and those are traced by rts_trace_soft_light_list_sparse_device, 64 marked pixels per wave, where
+--retrace alone opens every 8 x 8 tile that holds one; the same planes, byte for byte.  The planes feed --filter*, --temporal and the combine exactly as the full-resolution trace's.
 
 --filter R (with --soft-list N): between trace and image the count planes go through rtsh_filter_soft_light_list_device -- an edge-aware
 tent window of (2R+1)^2 pixels that stops at normal and depth edges (--normal-cos, --plane-eps) -- and the frame is lit from the float
@@ -76,14 +78,18 @@ def parse_colors(text, count):
 class HalfRes:
     """--half-res: the list is traced at half resolution and upsampled into the full-resolution count planes, all on the device:
     subsample -> trace at w x h -> (--retrace: retrace map -> full-resolution trace under it ->) upsample.  `phase`: (px, py), or None
-    to rotate it per frame so that --temporal sees all four pixels of a quad."""
+    to rotate it per frame so that --temporal sees all four pixels of a quad.  `sparse` (--retrace-sparse): the trace under the retrace
+    map is compact -> sparse trace of the listed pixels; the list has room for every pixel of the frame."""
     ROTATION = ((0, 0), (1, 1), (1, 0), (0, 1))
 
-    def __init__(self, ctx, W, H, count, retrace, phase, normal_cos, plane_eps):
-        self.ctx, self.retrace, self.phase, self.thresholds = ctx, retrace, phase, (normal_cos, plane_eps)
+    def __init__(self, ctx, W, H, count, retrace, phase, normal_cos, plane_eps, sparse=False):
+        self.ctx, self.retrace, self.phase, self.thresholds, self.sparse = ctx, retrace, phase, (normal_cos, plane_eps), sparse
         m = ((W + 1) // 2) * ((H + 1) // 2)                              # the largest of the four phases' frames
         self.d_lpos, self.d_lnrm, self.d_lmap, self.d_lo = ctx.malloc(m * 16), ctx.malloc(m * 16), ctx.malloc(m), ctx.malloc(count * m)
         self.d_keep = ctx.malloc(W * H) if retrace else None
+        if sparse:
+            from raytracedshadows_amd import api
+            self.d_list, self.d_n, self.d_scratch = ctx.malloc(W * H * 4), ctx.malloc(4), ctx.malloc(api.compact_scratch_bytes(W, H))
 
     def trace(self, api, constants, lights, d_pos, d_nrm, d_map, W, H, d_counts, frame=0):
         ctx = self.ctx
@@ -95,13 +101,19 @@ class HalfRes:
         if self.retrace:
             api.upsample_retrace_map_device(ctx, lights.count, p, d_pos, d_nrm, self.d_lpos, self.d_lnrm, W, H, self.d_keep, d_lights_map=d_map,
                                             d_lo_lights_map=self.d_lmap)
-            ctx.trace_soft_light_list_device(constants, lights, d_pos, W, H, d_counts, d_lights_map=self.d_keep)
+            if self.sparse:
+                api.compact_light_map_device(ctx, lights.count, self.d_keep, W, H, self.d_list, W * H, self.d_n, self.d_scratch)
+                ctx.trace_soft_light_list_sparse_device(constants, lights, d_pos, W, H, self.d_list, self.d_n, W * H, d_counts,
+                                                        d_lights_map=self.d_keep)
+            else:
+                ctx.trace_soft_light_list_device(constants, lights, d_pos, W, H, d_counts, d_lights_map=self.d_keep)
         api.upsample_soft_light_list_device(ctx, lights, p, d_pos, d_nrm, self.d_lpos, self.d_lnrm, self.d_lo, W, H, d_counts, d_lights_map=d_map,
                                             d_lo_lights_map=self.d_lmap, d_keep=self.d_keep)
 
     def words(self):
         return (f"half resolution, phase {'rotated per frame' if self.phase is None else self.phase}"
-                + (", edges retraced at full resolution" if self.retrace else ", edges from the nearest traced pixel"))
+                + (", edges retraced at full resolution" if self.retrace else ", edges from the nearest traced pixel")
+                + (" from the compacted list of their pixels" if self.sparse else ""))
 
 
 def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, distance_out="", colors="", filt=None, half=None):
@@ -402,6 +414,9 @@ def main():
                          "rtsh_upsample_soft_light_list_device); --normal-cos and --plane-eps are the taps' thresholds")
     ap.add_argument("--retrace", action="store_true",
                     help="with --half-res: trace the pixels no low-resolution tap stands for at full resolution (rtsh_upsample_retrace_map_device)")
+    ap.add_argument("--retrace-sparse", action="store_true",
+                    help="with --half-res --retrace: compact the retrace map (rtsh_compact_light_map_device) and trace the listed pixels alone "
+                         "(rts_trace_soft_light_list_sparse_device); the same planes")
     ap.add_argument("--phase", default="", metavar="PX,PY",
                     help="with --half-res: the sampled pixel of each quad (default 0,0; with --temporal: rotated per frame)")
     ap.add_argument("--colors", default="", metavar="r,g,b[;r,g,b...]",
@@ -453,9 +468,11 @@ def main():
                     sys.exit("render: --phase PX,PY takes 0 or 1 twice")
                 if phase is None and not args.temporal:
                     phase = (0, 0)
-                half = HalfRes(ctx, W, H, args.soft_list, args.retrace, phase, args.normal_cos, args.plane_eps)
-            elif args.retrace or args.phase:
-                sys.exit("render: --retrace and --phase PX,PY go with --half-res")
+                if args.retrace_sparse and not args.retrace:
+                    sys.exit("render: --retrace-sparse goes with --half-res --retrace")
+                half = HalfRes(ctx, W, H, args.soft_list, args.retrace, phase, args.normal_cos, args.plane_eps, sparse=args.retrace_sparse)
+            elif args.retrace or args.phase or args.retrace_sparse:
+                sys.exit("render: --retrace, --retrace-sparse and --phase PX,PY go with --half-res")
             if args.temporal:
                 if filt is None or args.distance or args.refined:
                     sys.exit("render: --temporal F goes with --soft-list N and --filter R or --filter-passes K, without --distance and --refined")
