@@ -378,6 +378,56 @@ int rts_trace_soft_distance_stripes_device(rts_ctx* ctx, const rts_constants* co
                                            uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, float* d_distance,
                                            uint8_t* d_mask, void* stream);
 
+/* AMBIENT OCCLUSION: short segment rays from the surface over the hemisphere around the normal, the unoccluded ones counted -- the
+ * any-hit walk of the shadow traces aimed by the G-buffer's normal instead of a light.  For pixel p of the rows the
+ * call owns, N = normals[p].xyz, rel = positions[p].xyz, n = max(1, ao->nsamples):
+ *   INACTIVE: N all zero (background), or active != NULL && active[p] == 0: counts[p] = 0, and the position is never read (NaN allowed).
+ *   FRAME (Duff et al.'s branchless basis; every operation ONE rounded float operation, parenthesised as written, no contraction):
+ *     sg = -1.0f if the sign bit of N.z is set, else 1.0f;   a = -1.0f / (sg + N.z);   b = (N.x * N.y) * a;
+ *     T = (1.0f + (sg * (N.x * N.x)) * a,  sg * b,  -(sg * N.x));      B = (b,  sg + (N.y * N.y) * a,  -N.y)
+ *   SAMPLE j < n: s = dirs[idx], idx = j with table == 0, else (start(p) + j) mod table -- start(p) hashed from p's index y*W + x in
+ *     the caller's FULL frame exactly as for rts_light.table;  per component c:
+ *     dir.c = ((T.c * s.x) + (B.c * s.y)) + (N.c * s.z);   o0.c = cam.c + rel.c;   L.c = o0.c + (radius * dir.c)
+ *     the ray is the one rts_trace_shadow_mask* sets up at p for the hard point light { RTS_LIGHT_POINT, 1 sample, xyz = L }: the same
+ *     bias, d = L - o, tmax = 1 -- a segment of about `radius` world units.  u_j = its any-hit byte (1: unoccluded).
+ *   counts[p] = u_0 + ... + u_(n-1): a sum of bytes that are functions of (pixel, sample) alone, so no order of the samples, no deal
+ *   over waves and no option can change it.  Any float is allowed in dirs (z <= 0 is legal: the rule defines the result).
+ *   * RTS_ERR_INVALID_ARG, nothing written, no counter moved: NULL ao, normals, positions, counts or constants; nsamples >
+ *     RTS_AO_MAX_SAMPLES; a table that is neither 0 nor in nsamples..RTS_AO_MAX_DIRS with nsamples >= 2; a radius that is Inf or NaN; a
+ *     bad row range or band, as rts_trace_soft_distance* refuses them.
+ *   * "kernel" picks the FAMILY as for a soft distance trace: the lane-per-ray walk over 16 x 16 blocks, samples in order, or the
+ *     stackless packet over 8 x 8 tiles -- "soft_split" 1 (default): four waves per tile, wave w walking the samples w, w + 4, ...,
+ *     their counts added in LDS; 0: one wave walks every sample.  A tile without an active non-background pixel stores its zeros and
+ *     sets up no ray.  Bands: a multiple of 16 rows for the first family, of 8 for the second; a stripe that owns no band launches
+ *     nothing, writes nothing and returns RTS_OK.
+ *   * like the other block traces it ignores split tables, tile orders, follow mode, "block_waves", "wide_lane", wave statistics and
+ *     the clock probe, and never drops or alters any of them.
+ *   * the device forms are asynchronous, allocate nothing and read nothing back; under graph capture each adds ONE kernel node, `ao`,
+ *     constants and options by value.  The host form copies in its rows only, traces, copies out.
+ *   * get-only option "ao_traces": AO launches so far (no other trace counter moves); rts_ctx_last_kernel_name then names
+ *     "ambientOcclusionShareKernel" or "ambientOcclusionPacketKernel<S,geom>", S = 4 or 1 waves per tile, geom = rows, bands or general.
+ * The count plane is a soft list's plane of n samples to everything downstream: the filters, the moments pass and the upsample read it
+ * under a one-entry rts_soft_light_list of the same nsamples (they read nothing else of a light when `distances` is NULL).
+ * rtsh_ambient_occlusion (rts_scene.h) is the host twin, rtsh_ao_rays the same rays as rts_ray records for rts_trace_rays*. */
+enum { RTS_AO_MAX_SAMPLES = 48, RTS_AO_MAX_DIRS = 64 };
+typedef struct rts_ao_params {
+    uint32_t nsamples;   /* 1..48 (0 counts as 1) */
+    uint32_t table;      /* 0, or nsamples..64 with nsamples >= 2: per-pixel start as rts_light.table */
+    float    radius;     /* finite; world units: the length of every AO segment */
+    uint32_t reserved_;  /* ignored */
+    float    dirs[64][4];/* tangent-space directions (x, y: tangent plane, z: along the normal); .w ignored */
+} rts_ao_params;         /* 1040 bytes */
+int rts_trace_ambient_occlusion(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao, const float* positions,
+                                const float* normals, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                uint32_t row_end, uint8_t* counts);
+int rts_trace_ambient_occlusion_device(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao, const float* d_positions,
+                                       const float* d_normals, const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                       uint32_t row_end, uint8_t* d_counts, void* stream);
+int rts_trace_ambient_occlusion_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao,
+                                               const float* d_positions, const float* d_normals, const uint8_t* d_active, uint32_t W,
+                                               uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts,
+                                               void* stream);
+
 /* LIGHT LISTS: up to 8 hard lights in ONE dispatch, one bit per light in the mask byte -- one read of the G-buffer texel, one launch and
  * one mask plane for all of a frame's shadow-casting lights.  For pixel p of the rows the call owns and l < list->count:
  *   mask[p] bit l = (lights_map == NULL || (lights_map[p] >> l) & 1)

@@ -96,6 +96,26 @@ int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, const rts_con
                        const float* positions, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
                        uint32_t row_end, float* distance, uint8_t* mask, int threads);
 
+/* AMBIENT OCCLUSION on the host: the definition of rts_trace_ambient_occlusion* (include/rts.h) as one straight loop over (pixel,
+ * sample) on rtsh_soft_distance's walk -- the frame around the normal, L of sample j (with ao->table: the index hashed from the pixel's
+ * index y*W + x in the frame given here), rtsh_shadow_distance's point-light ray set-up, u_j = 1 where the one-ray distance is +Inf;
+ * counts[p] = their sum.  Background and inactive pixels: 0, positions never read; rows outside [row_begin, row_end) are not touched.
+ * The refusals are rts_trace_ambient_occlusion's.  Runs without a GPU: the checker of the device forms, byte for byte.
+ *
+ * rtsh_ao_rays: the same rays as records for rts_trace_rays* / rtsh_rays_distance -- the n = max(1, nsamples) rays of pixel p at
+ * rays[p * n + j] = { o.xyz, tmax = 1, d.xyz, 0 } as defined there; the 32 bytes of every ray of a background or inactive pixel are
+ * zero (what the walk answers for such a record is no part of any count: sum the bytes of the other pixels only).  Whole frames only,
+ * on all host threads.
+ * rays: W * H * n records.  The refusals are rts_trace_ambient_occlusion's, without the row range.
+ * BEWARE of tracing the zero records: a generic ray with d = 0 is never occluded but is no cheap ray -- its slab tests are NaN or
+ * infinite, and from the world's origin it walks every box that contains the origin (all 2 M nodes of a 1 M-triangle city).  A frame
+ * with sky should drop or compact them before rts_trace_rays* (DESIGN.md 4.34). */
+int rtsh_ambient_occlusion(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_ao_params* ao,
+                           const float* positions, const float* normals, const uint8_t* active, uint32_t W, uint32_t H,
+                           uint32_t row_begin, uint32_t row_end, uint8_t* counts, int threads);
+int rtsh_ao_rays(const rts_constants* constants, const rts_ao_params* ao, const float* positions, const float* normals,
+                 const uint8_t* active, uint32_t W, uint32_t H, rts_ray* rays);
+
 /* ADAPTIVE SOFT SHADOWS on the host: the definition of rts_trace_shadow_mask_adaptive* (include/rts.h) applied literally, one straight
  * loop over (pixel, sample) on rtsh_soft_distance's walk and ray set-up -- the first `probe` samples; where they agree, 0 or nsamples;
  * where they disagree, the remaining samples and the full count.  mask[p] as defined there, refined[p] (nullable) = 1 exactly where the
@@ -268,6 +288,19 @@ int rtsh_combine_visibility_list(const rts_constants* constants, const rts_light
 int rtsh_combine_visibility_list_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* colors,
                                         const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
                                         const float* d_visibility, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream);
+
+/* THE VISIBILITY COMBINE WITH AMBIENT OCCLUSION: rtsh_combine_visibility_list* with the ambient term scaled per pixel --
+ * ambient' = ambient * ao[p], ONE rounded multiply; nothing else changes, every refusal included.  `ao`: W x H floats, any float
+ * allowed (the filtered plane of an AO count plane: (float)c / (float)n after the R = 0 filter); not looked at on background pixels.
+ * ao == NULL: RTS_ERR_INVALID_ARG (the call above is the form without AO).  ANCHOR: with a plane of 1.0f it gives
+ * rtsh_combine_visibility_list's bytes.  The device form adds one kernel node; the per-pixel source is shared, byte for byte. */
+int rtsh_combine_visibility_list_ao(const rts_constants* constants, const rts_light_list* list, const float* colors, const float* positions,
+                                    const float* normals, const uint8_t* lights_map, const float* visibility, const float* ao, uint32_t W,
+                                    uint32_t H, uint8_t* rgb);
+int rtsh_combine_visibility_list_ao_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* colors,
+                                           const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                           const float* d_visibility, const float* d_ao, uint32_t W, uint32_t H, uint8_t* d_rgb,
+                                           void* stream);
 
 /* THE TEMPORAL ACCUMULATION OF A LIGHT LIST'S VISIBILITY: this frame's float visibility planes (a filter's output; the R = 0 filter is
  * the conversion from counts) blended with LAST frame's result, which is fetched through the camera motion -- reprojected -- and

@@ -188,6 +188,51 @@ class SoftLightList(C.Structure):
         return LightList.make([(self.lights[l].type, list(self.lights[l].xyz)) for l in range(self.count)])
 
 
+class AoParams(C.Structure):
+    """``rts_ao_params``: an ambient occlusion trace -- ``nsamples`` segment rays of length ``radius`` per pixel, aimed by the
+    tangent-space directions ``dirs`` (x, y in the tangent plane, z along the normal) through the frame around the G-buffer's normal."""
+    _fields_ = [("nsamples", C.c_uint32), ("table", C.c_uint32), ("radius", C.c_float), ("reserved_", C.c_uint32),
+                ("dirs", (C.c_float * 4) * 64)]
+    MAX_SAMPLES = 48
+    MAX_DIRS = 64
+
+    @classmethod
+    def make(cls, nsamples, radius, table=0, seed=0, dirs=None):
+        """``table or nsamples`` cosine-weighted directions with z > 0, stratified (a Latin square over radius and azimuth, one sample
+        per row and per column, jittered inside its cell by ``numpy.random.RandomState(seed)``): deterministic, numpy only.
+        ``dirs``: the directions to use instead, at most 64 rows of 3 (or 4) floats, any float allowed."""
+        ao = cls()
+        ao.nsamples, ao.table, ao.radius = int(nsamples), int(table), np.float32(radius)
+        if dirs is None:
+            m = max(1, min(int(table) if table else int(nsamples), cls.MAX_DIRS))
+            rng = np.random.RandomState(seed)
+            u = (np.arange(m) + rng.random_sample(m)) / m                 # the fraction of the disc's area inside the sample
+            v = (rng.permutation(m) + rng.random_sample(m)) / m           # its azimuth, in turns
+            r = np.sqrt(u)
+            dirs = np.stack([r * np.cos(2.0 * np.pi * v), r * np.sin(2.0 * np.pi * v), np.sqrt(1.0 - u)], axis=1)
+        dirs = np.asarray(dirs, dtype=np.float32)
+        if dirs.ndim != 2 or dirs.shape[0] > cls.MAX_DIRS or dirs.shape[1] < 3:
+            raise RtsError(1, "AoParams.make: dirs is at most 64 rows of 3 floats")
+        for j in range(dirs.shape[0]):
+            for i in range(3):
+                ao.dirs[j][i] = dirs[j, i]
+        return ao
+
+    @property
+    def samples(self):
+        """The rays per pixel: ``max(1, nsamples)``."""
+        return max(1, int(self.nsamples))
+
+    def dirs_array(self):
+        """``float32[64, 4]``, a copy."""
+        return np.ctypeslib.as_array(self.dirs).reshape(64, 4).astype(np.float32).copy()
+
+    def stand_in_list(self):
+        """The one-entry ``SoftLightList`` of the same ``nsamples``: what the filters, the moments pass and the upsample take an AO
+        count plane under (they read a count plane and its sample count, and nothing else of a light without ``distances``)."""
+        return SoftLightList.make([(Light.POINT, (0.0, 0.0, 0.0), self.samples, 0, 0.0)])
+
+
 class FilterParams(C.Structure):
     """``rtsh_filter_params``: the window radius (0..8), the two geometry thresholds and, for the distance guide, one spread per light."""
     _fields_ = [("radius", C.c_uint32), ("normal_cos_min", C.c_float), ("plane_eps", C.c_float), ("spread", C.c_float * 8),
@@ -399,6 +444,20 @@ _sig("rts_trace_soft_distance_stripes_device", C.c_int, C.c_void_p, C.POINTER(Ra
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_soft_distance", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(Light), C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rts_trace_ambient_occlusion", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rts_trace_ambient_occlusion_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_ambient_occlusion_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rtsh_ambient_occlusion", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rtsh_ao_rays", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+     C.c_uint32, C.c_void_p)
+_sig("rtsh_combine_visibility_list_ao", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rtsh_combine_visibility_list_ao_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rts_trace_light_list", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p)
 _sig("rts_trace_light_list_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList),
@@ -1041,6 +1100,36 @@ class ShadowContext:
                                                            C.c_void_p(d_distance), C.c_void_p(d_mask or 0), C.c_void_p(stream or 0)),
                "rts_trace_soft_distance_stripes_device")
 
+    # -- ambient occlusion (include/rts.h): hemisphere segments around the normal, the unoccluded ones counted --
+    def trace_ambient_occlusion(self, constants, ao, positions, normals, width, height, row_begin=0, row_end=None, active=None, out=None):
+        """Host-pointer dispatch; returns ``uint8[H, W]`` counts of unoccluded samples (0 on the background and where ``active`` is 0).
+        ``out``: an array to write into (rows outside the range keep their contents)."""
+        positions, active = _frame_inputs("trace_ambient_occlusion", positions, width, height, active)
+        normals, _ = _frame_inputs("trace_ambient_occlusion (normals)", normals, width, height)
+        row_end = height if row_end is None else row_end
+        counts = out if out is not None else np.zeros((height, width), dtype=np.uint8)
+        _check(_lib.rts_trace_ambient_occlusion(self._h, C.byref(constants), _ref(ao), _ptr(positions), _ptr(normals), _ptr_or_none(active),
+                                                width, height, row_begin, row_end, _ptr(counts)), "rts_trace_ambient_occlusion")
+        return counts
+
+    def trace_ambient_occlusion_device(self, constants, ao, d_positions, d_normals, width, height, d_counts, row_begin=0, row_end=None,
+                                       stream=None, d_active=None):
+        """Device pointers, asynchronous: d_positions / d_normals = width * height RGBA32F, d_counts / d_active = width * height bytes."""
+        row_end = height if row_end is None else row_end
+        _check(_lib.rts_trace_ambient_occlusion_device(self._h, C.byref(constants), _ref(ao), C.c_void_p(d_positions or 0),
+                                                       C.c_void_p(d_normals or 0), C.c_void_p(d_active or 0), width, height, row_begin,
+                                                       row_end, C.c_void_p(d_counts or 0), C.c_void_p(stream or 0)),
+               "rts_trace_ambient_occlusion_device")
+
+    def trace_ambient_occlusion_stripes_device(self, constants, ao, d_positions, d_normals, width, height, d_counts, band_rows, n_stripes,
+                                               stripe, stream=None, d_active=None):
+        """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        _check(_lib.rts_trace_ambient_occlusion_stripes_device(self._h, C.byref(constants), _ref(ao), C.c_void_p(d_positions or 0),
+                                                               C.c_void_p(d_normals or 0), C.c_void_p(d_active or 0), width, height,
+                                                               band_rows, n_stripes, stripe, C.c_void_p(d_counts or 0),
+                                                               C.c_void_p(stream or 0)),
+               "rts_trace_ambient_occlusion_stripes_device")
+
     # -- light lists (include/rts.h): up to 8 hard lights in one dispatch, light l in bit l of the mask byte --
     def trace_light_list(self, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None):
         """Host-pointer dispatch; returns ``uint8[H, W]``: bit ``l`` = light ``l``'s shadow byte where ``lights_map`` (uint8[H, W], or
@@ -1623,6 +1712,32 @@ def soft_distance(packed, constants, light, positions, width, height, active=Non
     return dist, mask
 
 
+def ambient_occlusion(packed, constants, ao, positions, normals, width, height, active=None, row_begin=0, row_end=None, out=None, threads=0):
+    """Ambient occlusion on the host (rtsh_ambient_occlusion, no GPU): ``uint8[H, W]`` -- per pixel the number of the ``ao`` samples
+    whose segment meets no triangle; 0 on the background and where ``active`` is 0.  ``out``: an array to write into."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    positions, active = _frame_inputs("ambient_occlusion", positions, width, height, active)
+    normals, _ = _frame_inputs("ambient_occlusion (normals)", normals, width, height)
+    row_end = height if row_end is None else row_end
+    counts = out if out is not None else np.zeros((height, width), np.uint8)
+    _check(_lib.rtsh_ambient_occlusion(_ptr(packed), packed.shape[0], C.byref(constants), _ref(ao), _ptr(positions), _ptr(normals),
+                                       _ptr_or_none(active), width, height, row_begin, row_end, _ptr(counts), threads),
+           "rtsh_ambient_occlusion")
+    return counts
+
+
+def ao_rays(constants, ao, positions, normals, width, height, active=None):
+    """The rays of an ambient occlusion trace as ``rts_ray`` records (rtsh_ao_rays): ``float32[H * W * n, 8]``, the ``n = ao.samples``
+    rays of pixel ``p`` at rows ``p * n .. p * n + n - 1``; all zero for a background or inactive pixel.  What ``trace_rays`` takes."""
+    positions, active = _frame_inputs("ao_rays", positions, width, height, active)
+    normals, _ = _frame_inputs("ao_rays (normals)", normals, width, height)
+    n = ao.samples if ao is not None else 1
+    rays = np.zeros((width * height * n, 8), np.float32)
+    _check(_lib.rtsh_ao_rays(C.byref(constants), _ref(ao), _ptr(positions), _ptr(normals), _ptr_or_none(active), width, height, _ptr(rays)),
+           "rtsh_ao_rays")
+    return rays
+
+
 def shadow_mask_adaptive(packed, constants, light, positions, width, height, probe, active=None, row_begin=0, row_end=None, out=None,
                          refined=None, threads=0, want_refined=True):
     """The adaptive soft mask on the host (rtsh_shadow_mask_adaptive, no GPU): ``(uint8[H, W] mask, uint8[H, W] refined)`` -- the
@@ -2203,6 +2318,38 @@ def combine_visibility_list_device(ctx, constants, light_list, d_positions, d_no
                                                     C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
                                                     C.c_void_p(d_visibility), width, height, C.c_void_p(d_rgb), C.c_void_p(stream or 0)),
            "rtsh_combine_visibility_list_device")
+
+
+def combine_visibility_list_ao(constants, light_list, positions, normals, visibility, ao, lights_map=None, colors=None):
+    """The visibility combine with ambient occlusion on the host (rtsh_combine_visibility_list_ao): ``combine_visibility_list`` with the
+    ambient term of pixel ``p`` times ``ao[p]`` (``float32[H, W]``: a filtered AO count plane)."""
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    visibility = np.ascontiguousarray(visibility, np.float32)
+    ao = np.ascontiguousarray(ao, np.float32) if ao is not None else None
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    if visibility.size < (light_list.count if light_list is not None and light_list.count <= 8 else 1) * H * W or \
+            (lights_map is not None and lights_map.size != H * W) or (positions is not None and positions.size != H * W * 4) or \
+            (ao is not None and ao.size != H * W):
+        raise RtsError(1, "rtsh_combine_visibility_list_ao: a buffer does not fit the frame of the normals")
+    colors = _colors(light_list, colors)
+    rgb = np.zeros((H, W, 3), np.uint8)
+    _check(_lib.rtsh_combine_visibility_list_ao(C.byref(constants), _ref(light_list), _ptr_or_none(colors), _ptr_or_none(positions),
+                                                _ptr(normals), _ptr_or_none(lights_map), _ptr(visibility), _ptr_or_none(ao), W, H,
+                                                _ptr(rgb)), "rtsh_combine_visibility_list_ao")
+    return rgb
+
+
+def combine_visibility_list_ao_device(ctx, constants, light_list, d_positions, d_normals, d_visibility, d_ao, width, height, d_rgb,
+                                      d_lights_map=None, colors=None, stream=None):
+    """The visibility combine with ambient occlusion on the GPU: ``combine_visibility_list_device`` plus d_ao = width*height floats; one
+    kernel, asynchronous."""
+    colors = _colors(light_list, colors)
+    _check(_lib.rtsh_combine_visibility_list_ao_device(ctx.handle, C.byref(constants), _ref(light_list), _ptr_or_none(colors),
+                                                       C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
+                                                       C.c_void_p(d_visibility), C.c_void_p(d_ao or 0), width, height, C.c_void_p(d_rgb),
+                                                       C.c_void_p(stream or 0)), "rtsh_combine_visibility_list_ao_device")
 
 
 def camera_basis(eye, target, fovy, width, height):

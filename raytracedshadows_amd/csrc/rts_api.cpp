@@ -5,6 +5,7 @@
 #include "bvh_refit.h"
 #include "rts_device.h"
 #include "rts_soft_distance.h"
+#include "rts_ao.h"
 #include "rts_light_list.h"
 #include "rts_adaptive.h"
 #include "rts_soft_light_list.h"
@@ -53,6 +54,7 @@ struct rts_ctx {
     uint64_t softListJitterTraces = 0;                // launches of a jittered adaptive soft light list kernel (get-only option "soft_list_jitter_traces")
     uint64_t softLightListTraces = 0;                 // launches of a soft light list kernel (get-only option "soft_light_list_traces")
     uint64_t softListDistanceTraces = 0;              // launches of a soft light list distance kernel (get-only option "soft_list_distance_traces")
+    uint64_t aoTraces = 0;                            // launches of an ambient occlusion kernel (get-only option "ao_traces")
     uint64_t sparseListTraces = 0;                    // launches of a sparse light list kernel, hard or soft (get-only option "sparse_list_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
@@ -567,6 +569,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "soft_list_adaptive_traces")) { *value = (int)(c->softListAdaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_list_jitter_traces")) { *value = (int)(c->softListJitterTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_light_list_traces")) { *value = (int)(c->softLightListTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "ao_traces")) { *value = (int)(c->aoTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "sparse_list_traces")) { *value = (int)(c->sparseListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_list_distance_traces")) { *value = (int)(c->softListDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
@@ -966,6 +969,39 @@ int rts_trace_soft_distance_stripes_device(rts_ctx* c, const rts_constants* k, c
     return traceSoftDistanceImpl(c, k, light, d_positions, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe), d_distance, d_mask, stream);
 }
 
+// ---- ambient occlusion (include/rts.h): hemisphere segments around the G-buffer's normal, the unoccluded ones counted ----------------
+// One launch of an AO kernel (rts_ao.inc) with the geometry, the family rule and the tail of a distance trace.  The normals travel in
+// the distances' slot of the argument block, the radius in the light's x, the directions in the sample offsets and their table size
+// in the light's table (rts_ao.h), so sampleIndex and pixelBase are the mask traces' own.
+static int traceAmbientOcclusionImpl(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* d_positions,
+                                     const float* d_normals, const uint8_t* d_active, const Dispatch& g, uint8_t* d_counts, void* stream) {
+    TraceParams p; uint32_t rows = 0; int s;
+    if (beginFrame(c, k, d_positions, d_counts, d_counts && d_normals && rts::aoParamsOk(ao), g, p, &rows, &s) != Begin::Go) return s;
+    rts::setAoNormals(p, d_normals);
+    p.activeMap = d_active;
+    for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
+    p.lightType = RTS_LIGHT_POINT;
+    p.nsamples = ao->nsamples > 1 ? ao->nsamples : 1u;
+    p.lightTable = ao->table;
+    p.light[0] = ao->radius; p.light[1] = 0.0f; p.light[2] = 0.0f;
+    memcpy(p.offsets, ao->dirs, sizeof(float) * 4 * (p.lightTable ? p.lightTable : p.nsamples));
+    return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::aoTraces, rts::launchAmbientOcclusion, stream);
+}
+
+int rts_trace_ambient_occlusion_device(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* d_positions,
+                                       const float* d_normals, const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                       uint32_t row_end, uint8_t* d_counts, void* stream) {
+    return traceAmbientOcclusionImpl(c, k, ao, d_positions, d_normals, d_active, Dispatch::ofRows(W, H, row_begin, row_end), d_counts, stream);
+}
+
+int rts_trace_ambient_occlusion_stripes_device(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* d_positions,
+                                               const float* d_normals, const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t band_rows,
+                                               uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceAmbientOcclusionImpl(c, k, ao, d_positions, d_normals, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe),
+                                     d_counts, stream);
+}
+
 // ---- adaptive soft shadows (include/rts.h): a probe of a few samples per pixel, the others only where the probe disagrees ------------
 // One launch of an adaptive kernel (rts_adaptive.inc) with the geometry, the family rule and the tail of a distance trace.  The probe
 // count and the refined plane travel in the generic rays' slots of the argument block (rts_adaptive.h).
@@ -1012,11 +1048,12 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 // Frames (arguments checked by the caller): only rows [rowBegin, rowEnd) travel -- their positions, map, mask and distances, as a
 // frame of their own, to the device entry of what is being traced.  StagedRows names what a host entry hands over: the first nine
 // members every entry gives, in this order; the others it sets by name, and what it leaves alone is NULL.
-enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive, SoftListDistance };
+enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive, SoftListDistance, AmbientOcclusion };
 struct StagedRows {
     Staged what;
     const rts_constants* k;
-    const void* lights;                  // the rts_light; Staged::LightList: the rts_light_list; the soft lists: the rts_soft_light_list --
+    const void* lights;                  // the rts_light; Staged::LightList: the rts_light_list; the soft lists: the rts_soft_light_list;
+                                         // Staged::AmbientOcclusion: the rts_ao_params --
                                          // each case below names the type it reads, and nothing else does
     const float* positions;
     const uint8_t* active;               // the active map, or a list's light map
@@ -1027,6 +1064,7 @@ struct StagedRows {
     uint8_t* refined = nullptr;          // Staged::Adaptive, Staged::SoftListAdaptive (optional): staged in the distances' buffer
     const uint32_t* probes = nullptr;    // Staged::SoftListAdaptive: one per light
     const uint32_t* tables = nullptr;    // ... its jittered form, whose hash pixelBase makes that of the caller's frame
+    const float* normals = nullptr;      // Staged::AmbientOcclusion: staged in the distances' buffer
 };
 static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
@@ -1040,11 +1078,13 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     const size_t distPlanes = r.what == Staged::SoftListDistance ? planes : 1u;
     if (s == RTS_OK && r.distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4 * distPlanes);
     if (s == RTS_OK && r.refined) s = ensure(&c->d_dist, &c->distBytes, pixels);
+    if (s == RTS_OK && r.normals) s = ensure(&c->d_dist, &c->distBytes, pixels * 16);
     if (s == RTS_OK && r.mask) s = ensure(&c->d_out, &c->outBytes, pixels * planes);
     if (s == RTS_OK && r.active) s = ensure(&c->d_act, &c->actBytes, pixels);
     if (s != RTS_OK) return s;
     RTS_HIP(hipMemcpy(c->d_in, r.positions + first * 4, pixels * 16, hipMemcpyHostToDevice));
     if (r.active) RTS_HIP(hipMemcpy(c->d_act, r.active + first, pixels, hipMemcpyHostToDevice));
+    if (r.normals) RTS_HIP(hipMemcpy(c->d_dist, r.normals + first * 4, pixels * 16, hipMemcpyHostToDevice));
     const rts_constants* const k = r.k;
     const rts_light* const light = (const rts_light*)r.lights;
     const rts_soft_light_list* const softLights = (const rts_soft_light_list*)r.lights;
@@ -1074,6 +1114,9 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
                                                       nullptr); break;
     case Staged::SoftListDistance:
         s = rts_trace_soft_light_list_distance_device(c, k, softLights, d_in, d_active, W, rows, 0, rows, d_dist, d_mask, nullptr); break;
+    case Staged::AmbientOcclusion:
+        s = rts_trace_ambient_occlusion_device(c, k, (const rts_ao_params*)r.lights, d_in, d_dist, d_active, W, rows, 0, rows, d_mask,
+                                               nullptr); break;
     }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
@@ -1118,6 +1161,15 @@ int rts_trace_soft_distance(rts_ctx* c, const rts_constants* k, const rts_light*
     if (!rts::softLightOk(light)) return RTS_ERR_INVALID_ARG;
     StagedRows r{ Staged::SoftDistance, k, light, positions, active, W, H, row_begin, row_end };
     r.distance = distance; r.mask = mask;
+    return traceStagedRows(c, r);
+}
+
+int rts_trace_ambient_occlusion(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* positions, const float* normals,
+                                const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* counts) {
+    if (!c || !k || !positions || !normals || !counts || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::aoParamsOk(ao) || (uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;
+    StagedRows r{ Staged::AmbientOcclusion, k, ao, positions, active, W, H, row_begin, row_end };
+    r.mask = counts; r.normals = normals;
     return traceStagedRows(c, r);
 }
 

@@ -75,6 +75,15 @@ inline bool softListHasTable(const rts_soft_light_list* list, const uint32_t* ta
     return false;
 }
 
+// an ambient occlusion trace: at most RTS_AO_MAX_SAMPLES samples, a finite radius, and softLightOk's table rule over RTS_AO_MAX_DIRS
+inline bool aoParamsOk(const rts_ao_params* ao) {
+    if (!ao || ao->nsamples > RTS_AO_MAX_SAMPLES) return false;
+    if (ao->table && (ao->table > RTS_AO_MAX_DIRS || ao->table < ao->nsamples || ao->nsamples < 2)) return false;
+    uint32_t bits;
+    memcpy(&bits, &ao->radius, sizeof(bits));
+    return (bits & 0x7F800000u) != 0x7F800000u;                          // Inf or NaN: every exponent bit set
+}
+
 // the pixel list of a sparse list trace: the list and its length (on the device in the device forms) and room for at least one entry
 inline bool sparseListOk(const uint32_t* pixels, const uint32_t* n, uint32_t capacity) {
     return pixels && n && capacity != 0;

@@ -252,12 +252,14 @@ RTS_HD void combineListPixel(const CombineList& f, const float* position4, const
 // The VISIBILITY combine (include/rts_scene.h, rtsh_combine_visibility_list): combineListPixel with a float visibility per light --
 // what the filter below writes -- in place of (float)byte / samples; everything else, the order of the sum included, is the same, so
 // over the quotients of an R = 0 filter it gives combineListPixel's bytes.
-template <class VisibilityOf>
+// ambientOf(ambient): the ambient term as it enters the sum -- itself, or times the pixel's ambient occlusion (rtsh_combine_visibility_
+// list_ao: ONE rounded multiply, asked for on non-background pixels only).
+template <class VisibilityOf, class AmbientOf>
 RTS_HD void combineVisibilityPixel(const CombineList& f, const float* position4, const float* normal4, uint32_t bits,
-                                   VisibilityOf visibilityOf, uint8_t* rgb3) {
+                                   VisibilityOf visibilityOf, AmbientOf ambientOf, uint8_t* rgb3) {
     V3 n{ normal4[0], normal4[1], normal4[2] };
     if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) { rgb3[0] = rgb3[1] = rgb3[2] = 0; return; }
-    const float ambient = combineAmbient(clamp0(viewNdv(f.light[0], n)));
+    const float ambient = ambientOf(combineAmbient(clamp0(viewNdv(f.light[0], n))));
     float sum[3] = { 0.0f, 0.0f, 0.0f };
 #if defined(__HIPCC__)
 #pragma unroll
@@ -269,6 +271,11 @@ RTS_HD void combineVisibilityPixel(const CombineList& f, const float* position4,
         for (int c = 0; c < 3; ++c) sum[c] = sum[c] + direct * f.color[l][c];
     }
     for (int c = 0; c < 3; ++c) rgb3[c] = combineByte(sum[c] + ambient);
+}
+template <class VisibilityOf>
+RTS_HD void combineVisibilityPixel(const CombineList& f, const float* position4, const float* normal4, uint32_t bits,
+                                   VisibilityOf visibilityOf, uint8_t* rgb3) {
+    combineVisibilityPixel(f, position4, normal4, bits, visibilityOf, [](float ambient) { return ambient; }, rgb3);
 }
 
 // The FILTER of a light list's planes (include/rts_scene.h, rtsh_filter_light_list / rtsh_filter_soft_light_list), one pixel: a
@@ -1231,5 +1238,24 @@ RTS_HD bool compactSlotPixel(const CompactFrame& f, uint32_t t, uint32_t k, uint
     return x < f.W && y < f.H;
 }
 RTS_HD bool compactMarked(const CompactFrame& f, uint8_t mapByte) { return (mapByte & f.allBelowCount) != 0u; }
+
+// AMBIENT OCCLUSION (include/rts.h, rts_trace_ambient_occlusion*): the frame around the normal and the point a sample's segment ends at
+// -- the light position of the hard point light whose shadow ray the sample IS.  Shared by the host twin (rts_scene.cpp), rtsh_ao_rays
+// and the kernels (rts_ao.inc); every operation is one rounded float operation, parenthesised as in the header (no contraction, the
+// division correctly rounded).  sg + N.z is never 0 (sg carries N.z's sign), so a is finite for a finite normal.
+struct AoFrame { V3 T, B; };
+RTS_HD AoFrame aoFrame(V3 N) {
+    const float sg = (floatBits(N.z) >> 31) ? -1.0f : 1.0f;
+    const float a = -1.0f / (sg + N.z);
+    const float b = (N.x * N.y) * a;
+    return AoFrame{ V3{ 1.0f + (sg * (N.x * N.x)) * a, sg * b, -(sg * N.x) }, V3{ b, sg + (N.y * N.y) * a, -N.y } };
+}
+// L of sample direction s = dirs[idx] (x, y, z read): o0 + radius * dir, dir = ((T * s.x) + (B * s.y)) + (N * s.z) per component
+RTS_HD V3 aoAim(V3 cam, V3 rel, V3 N, const AoFrame& f, const float* s, float radius) {
+    const V3 dir{ ((f.T.x * s[0]) + (f.B.x * s[1])) + (N.x * s[2]), ((f.T.y * s[0]) + (f.B.y * s[1])) + (N.y * s[2]),
+                  ((f.T.z * s[0]) + (f.B.z * s[1])) + (N.z * s[2]) };
+    const V3 o0{ cam.x + rel.x, cam.y + rel.y, cam.z + rel.z };
+    return V3{ o0.x + (radius * dir.x), o0.y + (radius * dir.y), o0.z + (radius * dir.z) };
+}
 
 } // namespace rts_harness

@@ -298,3 +298,5 @@ hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
 #include "rts_soft_light_list_distance.inc"
 // sparse light lists: the two lane-per-ray list kernels fed from a list of pixels (their launches are declared in rts_light_list_sparse.h)
 #include "rts_light_list_sparse.inc"
+// ambient occlusion: hemisphere segments around the G-buffer's normal, counted (its launch is declared in rts_ao.h)
+#include "rts_ao.inc"

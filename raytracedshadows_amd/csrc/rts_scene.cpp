@@ -335,6 +335,65 @@ extern "C" int rtsh_soft_distance(const rts_vec4u* packed, size_t count_vec4, co
     return frameDistance(packed, count_vec4, k, light, ns, ns > 1 ? light->table : 0u, positions, active, W, row_begin, row_end, distance, mask, threads);
 }
 
+// ---- ambient occlusion on the host (include/rts_scene.h): the checker of rts_trace_ambient_occlusion*, and its rays as records ----
+// The definition of include/rts.h as a straight loop over (pixel, sample): the frame and L from rts_closest_hit.h (aoFrame, aoAim: the
+// kernels' own source), the point-light ray set-up and the one-ray distance of frameDistance.  aoPixelRays calls ray(j, r) for the n
+// rays of an active, non-background pixel in sample order; -> false, and no position read, for any other pixel.
+namespace rts_harness {
+namespace {
+template <class EachRay>
+inline bool aoPixelRays(const rts_constants* k, const rts_ao_params* ao, uint32_t n, const float* positions, const float* normals,
+                        const uint8_t* active, size_t i, EachRay&& ray) {
+    const float* n4 = normals + i * 4;
+    const V3 N{ n4[0], n4[1], n4[2] };
+    if (isBackground(N) || (active && !active[i])) return false;
+    const float* q = positions + i * 4;
+    const V3 cam{ k->cameraPosition[0], k->cameraPosition[1], k->cameraPosition[2] }, rel{ q[0], q[1], q[2] };
+    const AoFrame f = aoFrame(N);
+    for (uint32_t j = 0; j < n; ++j) {
+        const V3 L = aoAim(cam, rel, N, f, ao->dirs[sampleIndex(ao->table, j, (uint32_t)i)], ao->radius);
+        ray(j, shadowRay(k->cameraPosition, rel, RTS_LIGHT_POINT, L));
+    }
+    return true;
+}
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_ambient_occlusion(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_ao_params* ao,
+                                      const float* positions, const float* normals, const uint8_t* active, uint32_t W, uint32_t H,
+                                      uint32_t row_begin, uint32_t row_end, uint8_t* counts, int threads) {
+    if (!packed || !k || !positions || !normals || !counts || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::aoParamsOk(ao)) return RTS_ERR_INVALID_ARG;
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t n = ao->nsamples > 1 ? ao->nsamples : 1u;
+    const size_t first = (size_t)row_begin * W;
+    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t at) {
+        const size_t i = first + at;
+        uint32_t lit = 0;
+        aoPixelRays(k, ao, n, positions, normals, active, i, [&](uint32_t, const DRay& r) {
+            lit += rayDistanceBits(bvh, r) == 0x7F800000u ? 1u : 0u;    // u_j: comp:148, per sample
+        });
+        counts[i] = (uint8_t)lit;
+    });
+    return RTS_OK;
+}
+
+extern "C" int rtsh_ao_rays(const rts_constants* k, const rts_ao_params* ao, const float* positions, const float* normals,
+                            const uint8_t* active, uint32_t W, uint32_t H, rts_ray* rays) {
+    if (!k || !positions || !normals || !rays || W == 0 || H == 0 || !rts::aoParamsOk(ao)) return RTS_ERR_INVALID_ARG;
+    const uint32_t n = ao->nsamples > 1 ? ao->nsamples : 1u;
+    parallelFor((size_t)W * H, 256, 0, [&](size_t i) {                    // (every pixel writes its own n records)
+        rts_ray* out = rays + i * n;
+        memset(out, 0, sizeof(rts_ray) * n);
+        aoPixelRays(k, ao, n, positions, normals, active, i, [&](uint32_t j, const DRay& r) {
+            out[j] = rts_ray{ { r.o.x, r.o.y, r.o.z, r.tmax }, { r.d.x, r.d.y, r.d.z, 0.0f } };
+        });
+    });
+    return RTS_OK;
+}
+
 // ---- adaptive soft shadows on the host (include/rts_scene.h): the checker of rts_trace_shadow_mask_adaptive* ----
 // The definition of include/rts.h applied literally, one straight loop over (pixel, sample) on frameDistance's walk: the probe's
 // samples, then the others only where the probe disagrees.
@@ -712,6 +771,21 @@ extern "C" int rtsh_combine_visibility_list(const rts_constants* k, const rts_li
     const size_t n = (size_t)W * H;
     combineFrame(positions, normals, lights_map, n, [&](size_t i, const float* p4, const float* n4, uint32_t bits) {
         combineVisibilityPixel(f, p4, n4, bits, [&](uint32_t l) { return visibility[(size_t)l * n + i]; }, rgb + i * 3);
+    });
+    return RTS_OK;
+}
+
+extern "C" int rtsh_combine_visibility_list_ao(const rts_constants* k, const rts_light_list* list, const float* colors, const float* positions,
+                                               const float* normals, const uint8_t* lights_map, const float* visibility, const float* ao,
+                                               uint32_t W, uint32_t H, uint8_t* rgb) {
+    if (!k || !normals || !visibility || !ao || !rgb || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    CombineList f;
+    const int s = makeCombineList(k, list, colors, positions != nullptr, &f);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    combineFrame(positions, normals, lights_map, n, [&](size_t i, const float* p4, const float* n4, uint32_t bits) {
+        combineVisibilityPixel(f, p4, n4, bits, [&](uint32_t l) { return visibility[(size_t)l * n + i]; },
+                               [&](float ambient) { return ambient * ao[i]; }, rgb + i * 3);
     });
     return RTS_OK;
 }

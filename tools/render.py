@@ -116,7 +116,54 @@ class HalfRes:
                 + (" from the compacted list of their pixels" if self.sparse else ""))
 
 
-def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, distance_out="", colors="", filt=None, half=None):
+def parse_ao(text, wl):
+    """--ao N[:RADIUS[:TABLE]] -> AoParams: N samples of RADIUS world units (default 5 % of the scene's diagonal), a per-pixel table of
+    TABLE directions (default none)."""
+    from raytracedshadows_amd import api
+    try:
+        parts = text.split(":")
+        n = int(parts[0])
+        radius = float(parts[1]) if len(parts) > 1 and parts[1] else None
+        table = int(parts[2]) if len(parts) > 2 else 0
+    except (ValueError, IndexError):
+        sys.exit("render: --ao takes N[:RADIUS[:TABLE]]")
+    if radius is None:
+        radius = 0.05 * float(np.linalg.norm(wl.scene.bbox_max - wl.scene.bbox_min))
+    if not 1 <= n <= api.AoParams.MAX_SAMPLES or (table and not (n >= 2 and n <= table <= api.AoParams.MAX_DIRS)) or not np.isfinite(radius):
+        sys.exit("render: --ao N[:RADIUS[:TABLE]] takes 1 <= N <= 48, a finite RADIUS and TABLE 0 or N..64 with N >= 2")
+    return api.AoParams.make(n, radius, table=table, seed=5)
+
+
+def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
+    """Traces ambient occlusion on the device and turns the counts into a float plane under the stand-in list: through `filt` (--filter /
+    --filter-passes) when given, else the R = 0 tent filter -- (float)c / (float)n.  -> the plane (device)."""
+    d_counts, d_ao = ctx.malloc(W * H), ctx.malloc(W * H * 4)
+    t0 = time.time()
+    ctx.trace_ambient_occlusion_device(wl.constants, ao, d_pos, d_nrm, W, H, d_counts)
+    ctx.synchronize()
+    print(f"ambient occlusion: {ao.samples} segments of {ao.radius:g} per pixel{f', table {ao.table}' if ao.table else ''}: "
+          f"{(time.time() - t0) * 1e3:.2f} ms (first call, incl. launch); {ctx.last_kernel_name()}")
+    stand_in = ao.stand_in_list()
+    if isinstance(filt, api.WideFilterParams):
+        d_scratch = ctx.malloc(api.wide_filter_scratch_bytes(1, W, H)) if filt.passes >= 2 else None
+        api.wide_filter_soft_light_list_device(ctx, stand_in, filt, d_pos, d_nrm, d_counts, W, H, d_ao, d_scratch=d_scratch)
+    else:
+        if not isinstance(filt, api.FilterParams):
+            filt = api.FilterParams.make(0, 0.9, 0.05)
+        api.filter_soft_light_list_device(ctx, stand_in, filt, d_pos, d_nrm, d_counts, W, H, d_ao)
+    ctx.synchronize()
+    plane = np.zeros((H, W), np.float32)
+    ctx.d2h(plane, d_ao)
+    print(f"ambient occlusion: mean openness {float(plane.mean()):.3f}, fully open {float((plane >= 1).mean()) * 100:.1f} % of the pixels")
+    if ao_out:
+        os.makedirs(os.path.dirname(os.path.abspath(ao_out)), exist_ok=True)
+        api.write_ppm(ao_out, np.repeat((np.clip(plane, 0, 1) * 255).astype(np.uint8)[..., None], 3, axis=2))
+        print(f"wrote {ao_out}")
+    return d_ao
+
+
+def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, distance_out="", colors="", filt=None, half=None, ao=None,
+              ao_out=""):
     """A frame lit by `count` area lights of `spp` samples: one list dispatch (adaptive with `probe` != 0; with `table` every light
     takes its samples from a per-pixel jitter table of `table` entries), then ONE combine pass over all the count planes and one
     read-back of the RGB frame."""
@@ -153,13 +200,20 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
     print(f"G-buffer + facing map + {count} lights x {spp} samples{f', probe {probe},' if probe else ''} in one dispatch: {(time.time() - t0) * 1e3:.2f} ms (first call, incl. "
           f"launch); {ctx.last_kernel_name()}")
     rgb = np.zeros((H, W, 3), np.uint8)
+    d_ao = ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out) if ao is not None else None
+    if d_ao and filt is None:
+        filt = api.FilterParams.make(0, 0.9, 0.05)       # (the AO combine takes float planes: the R = 0 filter is the conversion)
     if filt is not None:                                 # trace -> filter -> visibility combine, all on the device
         d_vis = ctx.malloc(count * W * H * 4)
         wide = isinstance(filt, (api.WideFilterParams, api.WideGuideParams))
         d_scratch = ctx.malloc(wide_scratch_bytes(api, filt, count, W, H)) if wide and filt.passes >= 2 else None
         list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, d_dist, d_scratch)
-        api.combine_visibility_list_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, d_vis, W, H, d_rgb, d_lights_map=d_map,
-                                           colors=colors)
+        if d_ao:
+            api.combine_visibility_list_ao_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, d_vis, d_ao, W, H, d_rgb,
+                                                  d_lights_map=d_map, colors=colors)
+        else:
+            api.combine_visibility_list_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, d_vis, W, H, d_rgb, d_lights_map=d_map,
+                                               colors=colors)
         print(f"filtered: {filter_words(api, filt)}, N.N' >= {filt.normal_cos_min:g}, plane distance <= {filt.plane_eps:g}"
               + (f", distance-guided with spread {filt.spread[0]:g}" if d_dist and not wide else ""))
     else:
@@ -421,6 +475,12 @@ def main():
                     help="with --half-res: the sampled pixel of each quad (default 0,0; with --temporal: rotated per frame)")
     ap.add_argument("--colors", default="", metavar="r,g,b[;r,g,b...]",
                     help="with --soft-list N: the lights' colours, one triple for all of them or N separated by ';' (default 1/N each)")
+    ap.add_argument("--ao", default="", metavar="N[:RADIUS[:TABLE]]",
+                    help="trace ambient occlusion beside the lights (rts_trace_ambient_occlusion_device): N segments of RADIUS world units "
+                         "(default 5 %% of the scene's diagonal) per pixel, TABLE directions dealt per pixel; the counts become a float plane "
+                         "through --filter R / --filter-passes K (default: the R = 0 filter) and scale the ambient term "
+                         "(rtsh_combine_visibility_list_ao_device)")
+    ap.add_argument("--ao-out", default="", metavar="FILE.ppm", help="with --ao: also write the ambient occlusion plane as an image")
     args = ap.parse_args()
     from raytracedshadows_amd import api, workloads
     scene, W, H, light, spp = workloads.CONFIGS[args.config]
@@ -429,6 +489,11 @@ def main():
         api.save_bvh(args.save_bvh, wl.packed)
     with api.ShadowContext(0) as ctx:
         ctx.set_bvh(wl.packed)
+        if args.ao_out and not args.ao:
+            sys.exit("render: --ao-out goes with --ao")
+        ao = parse_ao(args.ao, wl) if args.ao else None
+        if ao is not None and args.temporal:
+            sys.exit("render: --ao does not go with --temporal")
         if args.soft_list:
             if not -1 <= args.filter <= api.FilterParams.MAX_RADIUS:
                 sys.exit("render: --filter R takes 0 <= R <= 8")
@@ -499,7 +564,7 @@ def main():
                 return soft_list_temporal(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, filt, args.temporal, args.orbit,
                                           args.max_length, args.adaptive, args.table, args.colors, clamp, args.filter_mean, args.move, moments_clamp, propagate, half)
             return soft_list(ctx, wl, W, H, args.soft_list, args.spp or 4, args.out, args.adaptive, args.refined, args.table, args.distance,
-                             args.colors, filt, half)
+                             args.colors, filt, half, ao, args.ao_out)
         d_pos, d_nrm, d_mask = ctx.malloc(W * H * 16), ctx.malloc(W * H * 16), ctx.malloc(W * H)
         t0 = time.time()
         api.primary_gbuffer_device(ctx, wl.scene.eye, wl.scene.target, wl.scene.fovy, W, H, d_pos, d_nrm)
@@ -538,7 +603,23 @@ def main():
             print(f"wrote {args.distance}: occluder distance, {ctx.last_kernel_name()}, largest finite value {top:.6g}, "
                   f"{float((~finite).mean()) * 100:.1f} % lit")
         d_rgb = ctx.malloc(W * H * 3)
-        api.combine_device(ctx, wl.constants, wl.light, d_pos, d_nrm, d_mask, W, H, d_rgb)     # the frame stays on the device
+        if ao is not None:                               # mask -> R = 0 filter -> the combine with ambient occlusion, all on the device
+            if not -1 <= args.filter <= api.FilterParams.MAX_RADIUS or not -1 <= args.filter_passes <= api.WideFilterParams.MAX_PASSES or \
+                    (args.filter >= 0 and args.filter_passes >= 0):
+                sys.exit("render: --ao takes --filter R (0..8) or --filter-passes K (0..5), not both")
+            filt = api.FilterParams.make(args.filter, args.normal_cos, args.plane_eps) if args.filter >= 0 else None
+            if args.filter_passes >= 0:
+                filt = api.WideFilterParams.make(args.filter_passes, args.normal_cos, args.plane_eps)
+            d_ao = ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, args.ao_out)
+            one = wl.light if wl.light is not None else api.Light.make(api.Light.DIRECTIONAL, list(wl.constants.lightDirection)[:3])
+            n = max(1, one.nsamples)
+            as_list = api.SoftLightList.make([(one.type, list(one.xyz), n, 0, 0.0)])
+            d_vis = ctx.malloc(W * H * 4)
+            api.filter_soft_light_list_device(ctx, as_list, api.FilterParams.make(0, 0.9, 0.05), d_pos, d_nrm, d_mask, W, H, d_vis)
+            api.combine_visibility_list_ao_device(ctx, wl.constants, as_list.hard_list(), d_pos, d_nrm, d_vis, d_ao, W, H, d_rgb,
+                                                  colors=None)
+        else:
+            api.combine_device(ctx, wl.constants, wl.light, d_pos, d_nrm, d_mask, W, H, d_rgb)     # the frame stays on the device
         ctx.synchronize()
         rgb, mask = np.zeros((H, W, 3), np.uint8), np.zeros((H, W), np.uint8)
         ctx.d2h(rgb, d_rgb); ctx.d2h(mask, d_mask)
