@@ -76,6 +76,10 @@ struct rts_ctx {
     void* d_parents = nullptr;
     uint32_t* d_word = nullptr;              // 4 bytes for the validation kernel's verdict
     uint32_t wideCount = 0, wideLevels = 0;
+    // the root box of the installed stream and the fast set-up's bounds from it (TraceParams::sceneBounds, rts_alltable.h): 64 bytes,
+    // allocated once, rewritten on the device after every install and refit that leaves a private copy
+    uint32_t* d_sceneBounds = nullptr;
+    uint64_t allTableTraces = 0;             // traces that ran the ALLTABLE instantiation (option "alltable_traces", read-only)
     bool bvhEnclosed = false;                // pre-order binary tree whose boxes enclose their children's (validateKernel)
     int wideCopy = 1;                        // option "wide_copy": build the private copy at upload
     int wideLane = 0;                        // option "wide_lane": dissolved wide packets walk the wide nodes lane per ray (LDS stacks: 28 waves per CU)
@@ -244,6 +248,15 @@ bool wideAllowed(const rts_ctx* c) {
     return c->bvhFinite && c->bvhOrdered && c->bvhEnclosed && c->P >= 2 && c->P <= (1u << 24);
 }
 
+// The per-scene constants of the ALLTABLE launch, in the default stream behind whatever just wrote the stream's boxes (the kernels
+// of an install or of a refit).  Without them (no memory, a failed launch) that launch is simply not selected.
+void refreshSceneBounds(rts_ctx* c) {
+    if (!c->d_sceneBounds && hipMalloc((void**)&c->d_sceneBounds, 64) != hipSuccess) { c->d_sceneBounds = nullptr; (void)hipGetLastError(); return; }
+    if (rts::launchSceneBounds(c->d_bvh, c->d_sceneBounds, nullptr) != hipSuccess) {
+        (void)hipGetLastError(); (void)hipFree(c->d_sceneBounds); c->d_sceneBounds = nullptr;
+    }
+}
+
 // the private copy of kernel 8, derived in full from the installed stream (when the option and the flags allow one)
 int deriveWideCopy(rts_ctx* c) {
     c->wideCount = 0; c->wideLevels = 0;
@@ -258,6 +271,7 @@ int deriveWideCopy(rts_ctx* c) {
     // a failure here only costs the private copy: the stream itself is installed and valid, the stackless kernels need
     // nothing else.  (Returning the error would leave the caller of the adopt path freeing a stream the context still holds.)
     if (e != hipSuccess) { c->wideCount = 0; c->wideLevels = 0; (void)hipGetLastError(); }
+    if (c->wideCount) refreshSceneBounds(c);
     return RTS_OK;
 }
 
@@ -434,6 +448,7 @@ int rts_ctx_destroy(rts_ctx* c) {
     if (c->d_tileOrder) (void)hipFree(c->d_tileOrder);
     if (c->d_scratch) (void)hipFree(c->d_scratch);
     if (c->d_wide) (void)hipFree(c->d_wide);
+    if (c->d_sceneBounds) (void)hipFree(c->d_sceneBounds);
     if (c->d_word) (void)hipFree(c->d_word);
     if (c->d_clockProbe) (void)hipFree(c->d_clockProbe);
     if (c->d_pieceClock) (void)hipFree(c->d_pieceClock);
@@ -559,6 +574,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "follow_block")) { *value = c->followBlock; return RTS_OK; }
     if (!strcmp(key, "follow_square")) { *value = c->followSquare; return RTS_OK; }
     if (!strcmp(key, "follow_streams")) { *value = (int)c->follow.size(); return RTS_OK; }
+    if (!strcmp(key, "alltable_traces")) { *value = (int)(c->allTableTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "follow_traces")) { *value = (int)(c->followTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "follow_ordered")) { *value = (int)(c->followOrdered & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "active_traces")) { *value = (int)(c->activeTraces & 0x7FFFFFFF); return RTS_OK; }
@@ -839,6 +855,8 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
             p.allInTable = sp.allTiles ? 1u : 0u;
             p.hasPieces = sp.nTiles ? 1u : 0u;
             if (c->d_pieceClock && c->pieceClockCount >= sp.nPieces) p.pieceClock = c->d_pieceClock;
+            // (a whole-dispatch table without pieces: kernel 8 may take its ALLTABLE instantiation -- rts::allTableLaunch)
+            if (variant == rts::V_WIDE && sp.allTiles && !sp.nTiles) p.sceneBounds = c->d_sceneBounds;
         }
     }
     // follow mode: where a split table could apply but none does, the trace records its tile lives and runs the order the planner
@@ -860,7 +878,10 @@ static int traceMaskImpl(rts_ctx* c, const rts_constants* k, const rts_light* li
         }
         ++c->followTraces;
     }
+    // (the ALLTABLE instantiation is an instantiation of kernel 8 like the other table forms and keeps its name -- the committed counter
+    //  summaries are keyed by it; the option "alltable_traces" counts its launches)
     c->lastKernel = fol ? (variant == rts::V_WIDE ? "shadowMaskFollowKernel<1,wide>" : "shadowMaskFollowKernel<1>") : rts::kernelName(variant, true);
+    if (!fol && variant == rts::V_WIDE && rts::allTableLaunch(p, c->blockWaves)) ++c->allTableTraces;
     ++c->launches;
     hipError_t e = rts::launchShadowMask(variant, c->blockWaves, p, (hipStream_t)stream, (uint32_t)c->ldsPad);
     if (e == hipSuccess && fol) {
@@ -1660,6 +1681,7 @@ int rts_ctx_refit_bvh_device(rts_ctx* c, const float* vertices, size_t vertex_fl
     L.baseline = !R.haveBaseline;
     RTS_HIP(hipEventRecord(R.ev[0], nullptr));
     RTS_HIP(rts::refitLaunch(L));
+    if (c->wideCount) refreshSceneBounds(c);              // (the root box may have moved: in stream order, before the read-back below)
     RTS_HIP(hipEventRecord(R.ev[1], nullptr));
     rts::RefitStatus st{};
     RTS_HIP(hipMemcpy(&st, R.d_status, sizeof(st), hipMemcpyDeviceToHost));      // (the one read-back of a steady refit)

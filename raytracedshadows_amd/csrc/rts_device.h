@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "rts_alltable.h"
 
 namespace rts {
 
@@ -85,7 +86,16 @@ struct TraceParams {
     const uint32_t* pieces;   // 8 dwords per piece: {bx | by << 16, first node, end node, state slot | pieces of the tile << 24,
                               //  byte offset of the wide node the piece starts at, 0, 0, 0}
     uint64_t* tileState;      // 2 u64 per split tile {lanes found occluded by any piece, pieces done}; zero between launches
-    uint32_t* pieceLog;       // split planning only: per piece 1 + pieceLogCap dwords {count, node indices visited ...}
+    union {
+        uint32_t* pieceLog;   // split planning only: per piece 1 + pieceLogCap dwords {count, node indices visited ...}
+        // the ALLTABLE launch only (allTableLaunch below): the context's block of per-scene constants, 9 dwords of device memory
+        // {rootLo.xyz, bound.x, rootHi.xyz, bound.y, bound.z} -- the root box of the installed stream and wideSetupBound of it,
+        // written by sceneBoundsKernel in stream order whenever the stream's boxes change (install, adopt, refit).  In memory and
+        // not by value: a captured trace replayed after an in-place refit must see the refitted root, as it does through p.bvh.
+        // (It shares the slot of the planning log, which only the piece path of a planning launch reads: the argument block
+        // keeps its size, and every other kernel its code.)
+        const uint32_t* sceneBounds;
+    };
     uint64_t* pieceClock;     // diagnostics ("piece_stats"): per piece {100 MHz clock at its start, at its end}, or NULL
     uint32_t nPieces, pieceLogCap;
     uint32_t allInTable;      // every tile of the dispatch has a record: the grid is the records alone (no tile rows at all)
@@ -104,6 +114,18 @@ struct SplitCut {             // planning: one selected tile
     uint32_t tile;            // bx | by << 16 (tile coordinates of the dispatch)
     uint32_t pieces;          // S
 };
+
+// Kernel 8's launch of `p` runs the ALLTABLE instantiation (rts_alltable.h: the rule itself, checked on the CPU).
+inline bool allTableLaunch(const TraceParams& p, int wavesPerBlock) {
+    AllTableFacts f{};
+    f.wavesPerBlock = (uint32_t)wavesPerBlock; f.nsamples = p.nsamples; f.wideLane = p.wideLane != 0; f.follow = p.followLives != nullptr;
+    f.table = p.pieces != nullptr; f.hasPieces = p.hasPieces != 0; f.allInTable = p.allInTable != 0; f.frontMap = p.frontMap != nullptr;
+    f.stripes = p.nStripes > 1; f.waveStats = p.waveStats != nullptr; f.sceneBounds = p.sceneBounds != nullptr;
+    f.nPieces = p.nPieces; f.blocksX = p.blocksX; f.pieceRows = p.pieceRows;
+    return allTableRule(f);
+}
+// the context's per-scene constants (TraceParams::sceneBounds, SCENE_BOUNDS_DWORDS dwords) from node 0 of the stream: one thread
+hipError_t launchSceneBounds(const void* d_packed, uint32_t* d_sceneBounds, hipStream_t stream);
 
 const char* kernelName(int variant, bool mask);
 void tileShape(int variant, int wavesPerBlock, uint32_t* blockW, uint32_t* blockH);   // pixels covered by one block

@@ -1122,6 +1122,34 @@ __device__ __forceinline__ bool traverseWide(const TraceParams& p, const NodeStr
     }
 }
 
+// traverseWide<true, SEG> for the ALLTABLE instantiation: the root box comes from the caller (the context's per-scene constants,
+// TraceParams::sceneBounds) instead of the stream's node 0, and the stream's buffer resource is made where it is used -- the
+// inexact-ray exit and the dissolve -- so that nothing of it is held across the assembly loop.  A function of its own, so that
+// the other instantiations keep their code to the register.
+template <bool SEG>
+__device__ __forceinline__ bool traverseWideScene(const TraceParams& p, const float* rootLo, const float* rootHi, const Ray& r, bool live,
+                                                  uint32_t* lds, uint32_t* laneStack, int32_t* dissolved, ShareDiag* diag, bool fast) {
+    const uint64_t liveMask = __builtin_amdgcn_ballot_w64(live);
+    if (dissolved) *dissolved = 0;
+    if (liveMask == 0) return false;
+    WideRay w;
+    const bool ok = fast ? wideRaySetupFast(r, rootLo, rootHi, w) : (wideRaySetup(r, rootLo, rootHi, w) && raySafe(r));
+    if (__builtin_amdgcn_ballot_w64(live && !ok) != 0)                       // a NaN or an overflow could occur: exact walk
+        return traverseShare<false>(openStream(p), r, live, 0u, lds);
+    const uint32_t oct = (__float_as_uint(r.inv.x) >> 31) | ((__float_as_uint(r.inv.y) >> 31) << 1) | ((__float_as_uint(r.inv.z) >> 31) << 2);
+    const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)oct, __builtin_ctzll(liveMask));
+    const uint32_t form = (uint32_t)__builtin_amdgcn_readfirstlane((__builtin_amdgcn_ballot_w64(live && oct != first) == 0) ? (int)first : 8);
+    uint32_t stRef = 0, stLo = 0, stHi = 0, sp = 0;
+    uint64_t occ = 0;
+    const float tmaxUniform = p.lightType == 0 ? 1e9f : 1.0f;
+    // (a ballot is wave-uniform, and so are kernel arguments: no v_readfirstlane around them)
+    const uint32_t st = wideDescend<SEG>(form, p.wide, p.tris, r, w, tmaxUniform, liveMask, occ, sp, stRef, stLo, stHi, p.packetBudget,
+                                    p.packetBudget * p.packetShare);
+    if (dissolved) *dissolved = st ? -1 : 0;
+    if (st == 0) return __builtin_amdgcn_inverse_ballot_w64(occ);
+    return wideDissolve<SEG>(p, openStream(p), r, w, occ, sp, stRef, stLo, stHi, lds, laneStack, diag);
+}
+
 // ------------------------------------------------------------------------------------------------
 // SPLIT TILES: a tile that was measured to be long (rts_ctx_plan_splits) is walked by S one-wave workgroups, the PIECES.
 // Every piece sets up all 64 rays of the tile and walks ONE index range [a, b) of the node stream; the ranges partition
@@ -1495,7 +1523,7 @@ __device__ __forceinline__ void runPiece(const TraceParams& p, uint32_t* lds) {
 //  of the probe waves, DESIGN.md 4.7.  Every K = 1 instantiation is inside both limits; tools/gen_wide_asm.py budgets for it.)
 
 template <int K, int WPB, bool PREFETCH = false, bool SOFT = false, bool PLAIN = false, int WIDE = 0, int SPLIT = 1, bool BANDS = false,
-          bool TILESPLIT = false, bool PIECES = true, bool SEG = false>
+          bool TILESPLIT = false, bool PIECES = true, bool SEG = false, bool ALLTABLE = false>
 __global__ __launch_bounds__(64 * WPB * SPLIT) __attribute__((amdgpu_waves_per_eu(K == 1 ? 8 : 4)))
 void shadowMaskPacketKernel(TraceParams p) {
     constexpr bool LIVES = false, ACTIVE = false;
@@ -1509,7 +1537,7 @@ template <int WIDE, bool BANDS, bool TILESPLIT, bool SEG>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8)))
 void shadowMaskFollowKernel(TraceParams p) {
     constexpr int K = 1, WPB = 1, SPLIT = 1;
-    constexpr bool PREFETCH = false, SOFT = false, PLAIN = true, PIECES = false, LIVES = true, ACTIVE = false;
+    constexpr bool PREFETCH = false, SOFT = false, PLAIN = true, PIECES = false, LIVES = true, ACTIVE = false, ALLTABLE = false;
 #include "rts_packet_tile.inc"
 }
 
@@ -1523,7 +1551,7 @@ template <int WIDE, bool SEG, bool SOFT, int SPLIT, bool PLAIN, bool BANDS>
 __global__ __launch_bounds__(64 * SPLIT) __attribute__((amdgpu_waves_per_eu(8)))
 void shadowMaskActivePacketKernel(TraceParams p) {
     constexpr int K = 1, WPB = 1;
-    constexpr bool PREFETCH = false, TILESPLIT = false, PIECES = false, LIVES = false, ACTIVE = true;
+    constexpr bool PREFETCH = false, TILESPLIT = false, PIECES = false, LIVES = false, ACTIVE = true, ALLTABLE = false;
 #include "rts_packet_tile.inc"
 }
 
@@ -1640,6 +1668,19 @@ void tileShape(int variant, int wavesPerBlock, uint32_t* blockW, uint32_t* block
     *blockH = f * (variant == V_PACKET4 ? 16u : 8u);
 }
 
+// The per-scene constants of the ALLTABLE instantiation (TraceParams::sceneBounds): one thread reads node 0 of the stream.
+__global__ __launch_bounds__(64) void sceneBoundsKernel(const uint32_t* packed, uint32_t* out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    uint32_t root[8], c[SCENE_BOUNDS_DWORDS];
+    for (int i = 0; i < 8; ++i) root[i] = packed[i];
+    sceneBoundsOf(root, c);
+    for (uint32_t i = 0; i < SCENE_BOUNDS_DWORDS; ++i) out[i] = c[i];
+}
+hipError_t launchSceneBounds(const void* d_packed, uint32_t* d_sceneBounds, hipStream_t stream) {
+    hipLaunchKernelGGL(sceneBoundsKernel, dim3(1), dim3(64), 0, stream, (const uint32_t*)d_packed, d_sceneBounds);
+    return hipGetLastError();
+}
+
 // The wide packet kernel (variant 8) for one light kind: SEG = a point light (see traverseWide).
 template <bool SEG>
 static void launchWide(int wavesPerBlock, const TraceParams& p, hipStream_t stream, uint32_t ldsPad, dim3 grid, dim3 block) {
@@ -1658,6 +1699,8 @@ static void launchWide(int wavesPerBlock, const TraceParams& p, hipStream_t stre
     else if (p.followLives && p.pieces) hipLaunchKernelGGL((shadowMaskFollowKernel<1, false, true, SEG>), grid, b1, ldsPad, stream, p);
     else if (p.followLives && p.nStripes > 1) hipLaunchKernelGGL((shadowMaskFollowKernel<1, true, false, SEG>), grid, b1, ldsPad, stream, p);
     else if (p.followLives) hipLaunchKernelGGL((shadowMaskFollowKernel<1, false, false, SEG>), grid, b1, ldsPad, stream, p);
+    else if (allTableLaunch(p, wavesPerBlock))  // every tile a record and nothing else: the wave is its record
+        hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, false, true, false, SEG, true>), grid, b1, ldsPad, stream, p);
     else if (p.pieces && p.nStripes > 1 && p.hasPieces)
         hipLaunchKernelGGL((shadowMaskPacketKernel<1, 1, false, false, true, 1, 1, true, true, true, SEG>), grid, b1, ldsPad, stream, p);
     else if (p.pieces && p.nStripes > 1)

@@ -8,6 +8,7 @@
     static_assert(SPLIT == 1 || (K == 1 && WPB == 1 && SOFT), "samples are split over waves in the one-tile soft-shadow form only");
     static_assert(!TILESPLIT || (PLAIN && K == 1 && WPB == 1 && !SOFT && SPLIT == 1), "split tiles exist for the one-tile everyday launch only");
     static_assert(!SEG || WIDE == 1 || WIDE == 3, "the segment-ray forms exist in the assembly wide loop and the lane walk only");
+    static_assert(!ALLTABLE || (TILESPLIT && !PIECES && !BANDS && WIDE == 1 && !LIVES), "ALLTABLE: a whole-dispatch table of the wide kernel, whole frames");
     __shared__ uint32_t shareSlots[WPB * SPLIT][64];     // lane numbers exchanged by traverseShare (256 B per wave)
     uint32_t* lds = shareSlots[threadIdx.x >> 6];
     // per-lane stacks of the wide lane walk: 4 KB per wave -- which caps a CU at 28 one-wave workgroups instead of 32, so
@@ -19,7 +20,19 @@
     constexpr uint32_t TW = K >= 2 ? 16u : 8u, TH = K >= 4 ? 16u : 8u;
     uint32_t bx = blockIdx.x, by = 0;
     bool mine = true;
-    if constexpr (PLAIN) {
+    if constexpr (ALLTABLE) {
+        // The table holds every tile and nothing else (rts_alltable.h: allTableRule), so the wave is its record: no tile rows, no
+        // bitmap, no piece path, no test against the record count.  What the record's address and the texel's need -- and the
+        // address of the per-scene constants -- is asked for in ONE batch; then the record and the constants in a second.
+        const uint64_t posAddr = (uint64_t)(uintptr_t)p.positions, frontAddr = (uint64_t)(uintptr_t)p.frontMap,
+                       sceneAddr = (uint64_t)(uintptr_t)p.sceneBounds;
+        const uint32_t a0 = p.W, a1 = p.rowBegin, a2 = p.rowEnd, a3 = p.blocksX, a4 = p.frontStride;
+        asm volatile("" :: "s"(posAddr), "s"(frontAddr), "s"(sceneAddr), "s"(a0), "s"(a1), "s"(a2), "s"(a3), "s"(a4));
+        const uint32_t id = blockIdx.y * a3 + blockIdx.x;             // (the grid is blocksX wide)
+        const uint32_t slot = (id & 7u) * a4 + (id >> 3);             // (this XCD's run of the map: TraceParams::frontMap)
+        const uint32_t tile = *(ConstU32Ptr)(uintptr_t)(frontAddr + (uint64_t)slot * 4u);
+        bx = tile & 0xFFFFu; by = tile >> 16;
+    } else if constexpr (PLAIN) {
         // Everything a tile wave needs before it can ask for its texel is the first 64 bytes of the argument block: asked for
         // here in one batch (the compiler would fetch each field where it is first used: three or four dependent round
         // trips to the scalar cache in front of the texel request).
@@ -32,7 +45,8 @@
             asm volatile("" :: "s"(actAddr));
         }
     }
-    if constexpr (TILESPLIT) {
+    if constexpr (ALLTABLE) {
+    } else if constexpr (TILESPLIT) {
         const uint32_t pieceRows = p.pieceRows, blocksX = p.blocksX, blocksY = p.blocksY, rowOrder = p.rowOrder;
         const uint64_t mapAddr = uniform64(p.skipMap);
         if (blockIdx.y < pieceRows) {                                 // the head of the grid: records of the split table
@@ -123,9 +137,9 @@
     // clock probe (every instantiation, so that the clock is measured on the launches that are timed): one wave per tile row
     // (the stamps go straight to memory: nothing of the probe stays in registers across the walk)
     // (with a table: the tile rows stamp; when the table holds every tile there are none, and the front-tile rows stamp instead)
-    const uint32_t probeRow = TILESPLIT ? (p.allInTable ? blockIdx.y : blockIdx.y - p.pieceRows) : (p.grid2d ? blockIdx.y : 0u);
+    const uint32_t probeRow = ALLTABLE ? blockIdx.y : TILESPLIT ? (p.allInTable ? blockIdx.y : blockIdx.y - p.pieceRows) : (p.grid2d ? blockIdx.y : 0u);
     const bool probed = p.clockProbe != nullptr && blockIdx.x == 0 && threadIdx.x == 0 &&
-                        (!TILESPLIT || (p.allInTable ? blockIdx.y < p.blocksY : blockIdx.y >= p.pieceRows));
+                        (ALLTABLE ? blockIdx.y < p.blocksY : (!TILESPLIT || (p.allInTable ? blockIdx.y < p.blocksY : blockIdx.y >= p.pieceRows)));
     if (probed) {
         uint64_t* o = p.clockProbe + (size_t)probeRow * 4;
         o[0] = __builtin_amdgcn_s_memtime(); o[2] = __builtin_amdgcn_s_memrealtime();
@@ -148,7 +162,16 @@
         Ray r[K];
         bool occluded[K];
         [[maybe_unused]] bool fast = false;
-        if constexpr (WIDE != 0) {
+        [[maybe_unused]] float sceneRoot[6];
+        if constexpr (ALLTABLE) {
+            // the root box and wideSetupBound of it: computed when the stream's boxes change (sceneBoundsKernel), not per wave
+            const uint64_t sceneAddr = (uint64_t)(uintptr_t)p.sceneBounds;
+            const u32x8 c = *(ConstNodePtr)(uintptr_t)sceneAddr;
+            const uint32_t bz = *(ConstU32Ptr)(uintptr_t)(sceneAddr + 32u);
+            sceneRoot[0] = __uint_as_float(c.s0); sceneRoot[1] = __uint_as_float(c.s1); sceneRoot[2] = __uint_as_float(c.s2);
+            sceneRoot[3] = __uint_as_float(c.s4); sceneRoot[4] = __uint_as_float(c.s5); sceneRoot[5] = __uint_as_float(c.s6);
+            r[0] = makeShadowRay<true>(p, rel[0], s, (uint32_t)pix[0], &fast, SetupBound{ c.s3, c.s7, bz });
+        } else if constexpr (WIDE != 0) {
             float rootLo[3], rootHi[3];
             wideRoot(p, rootLo, rootHi);
             r[0] = makeShadowRay<!SOFT && WIDE != 3>(p, rel[0], s, ACTIVE ? rayPix : (uint32_t)pix[0], &fast, wideSetupBound(rootLo, rootHi));
@@ -160,7 +183,8 @@
             asm volatile("" :: "v"(r[0].inv.x), "v"(r[0].inv.y), "v"(r[0].inv.z), "v"(r[0].o.x));
             tReady = __builtin_amdgcn_s_memtime();
         }
-        if constexpr (WIDE != 0) occluded[0] = traverseWide<WIDE != 2, SEG>(p, bvh, r[0], live[0], lds, laneStack, &left, &shareDiag, fast);
+        if constexpr (ALLTABLE) occluded[0] = traverseWideScene<SEG>(p, sceneRoot, sceneRoot + 3, r[0], live[0], lds, laneStack, &left, &shareDiag, fast);
+        else if constexpr (WIDE != 0) occluded[0] = traverseWide<WIDE != 2, SEG>(p, bvh, r[0], live[0], lds, laneStack, &left, &shareDiag, fast);
         else traversePacket<K, PREFETCH>(p, bvh, r, live, occluded, lds, &left, &shareDiag);
 #pragma unroll
         for (int k = 0; k < K; ++k) lit[k] += occluded[k] ? 0u : 1u;                     // comp:148
