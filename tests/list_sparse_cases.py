@@ -5,7 +5,8 @@ compaction cases; the golden frames, lists and pixel lists of the sparse traces.
 Compaction cases.  Frames: 1 x 1, 7 x 9, 8 x 8, 9 x 8, 17 x 5, 70 x 33 (partial tiles right and below), and 8192 x 8 / 8200 x 8 -- 1024
 tiles, exactly what one scan workgroup of the device form handles (SCAN_TILES), and the same frame with one tile more.  Maps: all zero,
 all set, bits from `count` up only (an empty list), one marked pixel in the frame's last (partial) tile, random maps of about 1 % and
-about 50 % marked pixels.  Capacities: n - 1, n, n + 1 and 1 (those that are positive).
+about 50 % marked pixels.  Capacities: n - 1, n, n + 1 and 1 (those that are positive).  And three frames of many groups of tiles
+(MANY_FRAMES: 3, 257 and 1027 groups) with two arithmetic maps each, for the kernel that sums the groups' totals.
 
 Sparse traces.  The bottom-right 48 x 40 of cornell_128 and 40 x 36 of terrain_96 (tests/golden/), lists of 1 and 8 lights -- soft
 entries of 2 and 16 samples and hard entries mixed, point and directional --, a map that mixes every bit pattern with whole zero
@@ -84,6 +85,75 @@ def compaction_cases():
 
 def capacities(n):
     return sorted({c for c in (n - 1, n, n + 1, 1) if c >= 1})
+
+
+# ---------------------------------------------------------------------------------------------- compaction over many groups of tiles
+# The third kernel of the device form sums the groups' totals in ONE workgroup: four totals per lane, 256 lanes, strips of 1024 totals
+# with a carry.  On FRAMES (at most two groups) only lane 0 of it ever holds a non-zero value.  These frames give it 3 groups (one
+# lane, more than one total in it), 257 groups (512 x 513 tiles: 65 lanes, so two waves of the block scan) and 1027 groups (1025 x 1025
+# = 1026 * 1024 + 1 tiles: a second strip, so the carry, and a last group of one tile).  Kept out of compaction_cases(): each frame
+# meets its two maps only, at 8 lights.
+MANY_FRAMES = [(1024, 136), (4096, 4104), (8200, 8200)]
+MANY_GROUPS = {(1024, 136): 3, (4096, 4104): 257, (8200, 8200): 1027}
+MANY_MAPS = ["sparse", "full_group"]
+MANY_STRIDE = 4099                                   # a prime just above 4096: about one marked pixel per 4096, drifting over the columns
+
+
+def full_group_of(wh):
+    """The group that "full_group" marks whole: a middle one, all of whose tiles lie inside the frame (every MANY_FRAMES side is a
+    multiple of 8, so no tile is partial), with a group on either side."""
+    return max(1, MANY_GROUPS[wh] // 2)
+
+
+def _tile_pixel(W, tile, slot):
+    """Flat index of slot `slot` (row-major in the tile) of tile `tile` (row-major over the frame)."""
+    bx = (W + 7) // 8
+    return ((tile // bx) * 8 + (slot >> 3)) * W + (tile % bx) * 8 + (slot & 7)
+
+
+def many_groups_pinned(wh):
+    """Flat indices both maps mark whatever the stride does: the frame's first and last pixel, one pixel in the last tile of group 0,
+    one in the first tile of the last group, and -- where the frame has it -- one in the first tile of group 1024 (the second strip)."""
+    W, H = wh
+    groups = MANY_GROUPS[wh]
+    pins = [0, W * H - 1, _tile_pixel(W, SCAN_TILES - 1, 37), _tile_pixel(W, (groups - 1) * SCAN_TILES, 0)]
+    if groups > SCAN_TILES:
+        pins.append(_tile_pixel(W, SCAN_TILES * SCAN_TILES, 9))
+    return pins
+
+
+def many_groups_map(kind, wh):
+    """uint8[H, W], read-only, made by arithmetic alone.  "sparse": every MANY_STRIDE-th pixel and the pinned ones, bytes 1 .. 255.
+    "full_group": the same, except that group full_group_of(wh) is marked whole (65 536 entries) and its two neighbours not at all
+    (but for a pinned pixel, which only the frame of 3 groups has there)."""
+    key = ("many", kind, wh)
+    if key not in _MAPS:
+        W, H = wh
+        assert ((W + 7) // 8) * ((H + 7) // 8) > (MANY_GROUPS[wh] - 1) * SCAN_TILES and W % 8 == 0 and H % 8 == 0
+        idx = np.concatenate([np.arange(0, W * H, MANY_STRIDE, dtype=np.int64), np.array(many_groups_pinned(wh), np.int64)])
+        flat = np.zeros(W * H, np.uint8)
+        flat[idx] = (1 + idx % 255).astype(np.uint8)
+        m = flat.reshape(H, W)
+        if kind == "full_group":
+            bx, g = W // 8, full_group_of(wh)
+            group = (((idx // W) >> 3) * bx + ((idx % W) >> 3)) // SCAN_TILES
+            pinned = np.isin(idx, many_groups_pinned(wh))                # (3 groups: the pinned pixels stay in the neighbours, all else goes)
+            flat[idx[((group == g - 1) | (group == g + 1)) & ~pinned]] = 0
+            tiles = np.arange(g * SCAN_TILES, (g + 1) * SCAN_TILES)
+            for ty in np.unique(tiles // bx):                            # (a group is a few runs of tiles along tile rows)
+                tx = tiles[tiles // bx == ty] % bx
+                m[ty * 8:ty * 8 + 8, tx.min() * 8:tx.max() * 8 + 8] = 0x80 | (ty & 0x7F)
+        m.setflags(write=False)
+        _MAPS[key] = m
+    return _MAPS[key]
+
+
+def group_totals(wh, pixels):
+    """Marked pixels per group of SCAN_TILES tiles, from a list of flat indices (what the third kernel sums)."""
+    W, H = wh
+    p = np.asarray(pixels, np.int64)
+    tile = ((p // W) >> 3) * ((W + 7) // 8) + ((p % W) >> 3)
+    return np.bincount(tile // SCAN_TILES, minlength=MANY_GROUPS[wh])
 
 
 # ------------------------------------------------------------------------------------------------------------ the sparse traces' cases

@@ -105,6 +105,42 @@ def test_compaction_equals_the_host_twin(ctx, other_stream, wh):
             b.free()
 
 
+@pytest.mark.parametrize("kind", sc.MANY_MAPS)
+@pytest.mark.parametrize("wh", sc.MANY_FRAMES, ids=lambda wh: f"{wh[0]}x{wh[1]}")
+def test_compaction_over_many_groups_equals_the_rule(ctx, wh, kind):
+    """3, 257 and 1027 groups of tiles: the kernel that sums the groups' totals with data in more than one total of a lane, in more than
+    one wave of its block scan, and in a second strip (the carry).  Against the numpy rule; capacities n and n - 1, a guard behind the
+    list."""
+    W, H = wh
+    m = sc.many_groups_map(kind, wh)
+    want = sc.compact_rule_fast(8, m)
+    n = want.size
+    scratch_bytes = api.compact_scratch_bytes(W, H)
+    assert scratch_bytes >= 4 * ((W // 8) * (H // 8) + sc.MANY_GROUPS[wh])
+    d_map = _Guarded(ctx, W * H, 1, m)
+    d_list = _Guarded(ctx, 4 * n, 4)
+    d_n = _Guarded(ctx, 4, 4)
+    d_scratch = _Guarded(ctx, scratch_bytes, 4)
+    try:
+        for capacity in (n, n - 1):
+            d_list.reset()
+            d_n.reset()
+            api.compact_light_map_device(ctx, 8, d_map.ptr, W, H, d_list.ptr, capacity, d_n.ptr, d_scratch.ptr)
+            ctx.synchronize()
+            what = (kind, wh, capacity)
+            got_n = int(d_n.read((1,), np.uint32)[0])
+            assert got_n == n, (what, got_n, n)
+            got = d_list.read((n,), np.uint32)                            # (read() checks the guard words behind the list)
+            bad = np.flatnonzero(got[:capacity] != want[:capacity])
+            assert bad.size == 0, (what, bad.size, bad[:4].tolist(), sc.group_totals(wh, want)[:8].tolist())
+            assert (got[capacity:] == FILL32).all(), what
+            d_scratch.read((scratch_bytes,))                              # (its guards)
+        d_map.read((W * H,))                                              # (the map's guards: nothing wrote around it)
+    finally:
+        for b in (d_map, d_list, d_n, d_scratch):
+            b.free()
+
+
 def test_compaction_under_capture(ctx, other_stream):
     """COMPACT_NODES kernel nodes and no other node; nothing runs during the capture; a replay after the map was changed on the device
     gives the new map's list."""

@@ -51,6 +51,44 @@ def test_compaction_equals_the_rule(case):
     assert n2 == n and np.array_equal(pixels, want)
 
 
+@pytest.mark.parametrize("wh", sc.MANY_FRAMES, ids=lambda wh: f"{wh[0]}x{wh[1]}")
+def test_the_many_group_maps_hold_what_their_cases_are_for(wh):
+    """No library: the arithmetic maps of the many-group frames against the numpy rule."""
+    W, H = wh
+    tiles, groups = (W // 8) * (H // 8), sc.MANY_GROUPS[wh]
+    assert (tiles + sc.SCAN_TILES - 1) // sc.SCAN_TILES == groups
+    g = sc.full_group_of(wh)
+    for kind in sc.MANY_MAPS:
+        m = sc.many_groups_map(kind, wh)
+        want = sc.compact_rule_fast(8, m)
+        flat = m.reshape(-1)
+        assert all(flat[p] != 0 for p in sc.many_groups_pinned(wh)), kind        # first and last pixel, group edges
+        totals = sc.group_totals(wh, want)
+        assert totals.sum() == want.size and totals[0] > 0 and totals[-1] > 0
+        if kind == "sparse":
+            assert abs(want.size - W * H / 4096) < W * H / 4096 * 0.01 + 8
+            assert (totals > 0).sum() >= groups - 1                                # (data in every lane of the sum)
+        else:
+            assert totals[g] == 64 * sc.SCAN_TILES
+            assert totals[g - 1] <= 3 and totals[g + 1] <= 3
+            if groups > 3:
+                assert totals[g - 1] == 0 and totals[g + 1] == 0
+
+
+@pytest.mark.parametrize("kind", sc.MANY_MAPS)
+def test_compaction_of_three_groups_equals_the_rule(kind):
+    wh = sc.MANY_FRAMES[0]
+    m = sc.many_groups_map(kind, wh)
+    want = sc.compact_rule_fast(8, m)
+    n = want.size
+    for capacity in (n - 1, n):
+        raw = np.full(capacity + 1 + GUARD, FILL32, np.uint32)                    # the list, then a guard
+        got = C.c_uint32(0xABABABAB)
+        assert api._lib.rtsh_compact_light_map(8, api._ptr(m), wh[0], wh[1], api._ptr(raw), capacity, C.byref(got)) == 0
+        assert got.value == n, (kind, capacity, got.value, n)
+        assert np.array_equal(raw[:capacity], want[:capacity]) and (raw[capacity:] == FILL32).all(), (kind, capacity)
+
+
 def test_compaction_refusals_write_nothing():
     m = sc.light_map("half", (17, 5), 8)
     out = np.full(100, FILL32, np.uint32)
