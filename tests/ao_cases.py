@@ -128,6 +128,25 @@ def aim_rule(k, ao, positions, normals, y, x, j):
 _FRAMES = {}
 
 
+def empty_texels(q):
+    """A frame's background: a zero texel (or one that is not finite)."""
+    return (q == 0).all(-1) | ~np.isfinite(q).all(-1)
+
+
+def geometric_normals(positions):
+    """float64[H, W, 3] of positions[H, W, 3 or 4]: the normalised cross product of the position differences to the right and below,
+    turned towards the camera; all-zero (background) where that is not finite, where one of the three texels is background, and in
+    the last row and column."""
+    p3 = np.asarray(positions)[..., :3].astype(np.float64)
+    cross = np.cross(p3[:-1, 1:] - p3[:-1, :-1], p3[1:, :-1] - p3[:-1, :-1])
+    with np.errstate(all="ignore"):
+        N = cross / np.linalg.norm(cross, axis=-1, keepdims=True)
+    N = np.where((np.einsum("ijk,ijk->ij", N, p3[:-1, :-1]) > 0)[..., None], -N, N)      # towards the camera
+    bad = ~np.isfinite(N).all(-1) | empty_texels(p3[:-1, :-1]) | empty_texels(p3[:-1, 1:]) | empty_texels(p3[1:, :-1])
+    N[bad] = 0
+    return np.pad(N, ((0, 1), (0, 1), (0, 0)))                           # (the last row and column: background)
+
+
 class AoFrame:
     """A golden crop (read-only arrays): positions (background NaN), normals, the mixed active map, `dirty` (inactive NaN too)."""
 
@@ -136,14 +155,7 @@ class AoFrame:
         self.packed, self.k, _, pos = golden_frame(name)                 # (the whole frame: the differences need a texel more)
         pos = np.ascontiguousarray(pos, f32)
         p3 = pos[..., :3].astype(np.float64)
-        cross = np.cross(p3[:-1, 1:] - p3[:-1, :-1], p3[1:, :-1] - p3[:-1, :-1])
-        with np.errstate(all="ignore"):
-            N = cross / np.linalg.norm(cross, axis=-1, keepdims=True)
-        N = np.where((np.einsum("ijk,ijk->ij", N, p3[:-1, :-1]) > 0)[..., None], -N, N)      # towards the camera
-        empty = lambda q: (q == 0).all(-1) | ~np.isfinite(q).all(-1)     # (the golden frames' background: a zero texel)
-        bad = ~np.isfinite(N).all(-1) | empty(p3[:-1, :-1]) | empty(p3[:-1, 1:]) | empty(p3[1:, :-1])
-        N[bad] = 0
-        N = np.pad(N, ((0, 1), (0, 1), (0, 0)))                          # (the last row and column: background)
+        N = geometric_normals(pos)
         y1, x1 = pos.shape[0] - inset, pos.shape[1] - inset
         sl = (slice(y1 - H, y1), slice(x1 - W, x1))
         nrm = np.zeros((H, W, 4), f32)
@@ -168,7 +180,7 @@ class AoFrame:
             self.active[:] = 1
         self.dirty = pos.copy()
         self.dirty[self.active == 0] = np.nan                            # (nor an inactive one)
-        seen = p3[~empty(p3)]
+        seen = p3[~empty_texels(p3)]
         self.diagonal = float(np.linalg.norm(seen.max(0) - seen.min(0)))  # of the scene as the whole golden frame sees it
         assert self.diagonal > 0 and (~self.background).any()
         self.pos, self.nrm = pos, nrm
