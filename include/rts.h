@@ -428,6 +428,52 @@ int rts_trace_ambient_occlusion_stripes_device(rts_ctx* ctx, const rts_constants
                                                uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts,
                                                void* stream);
 
+/* ADAPTIVE AMBIENT OCCLUSION: a probe of a few AO samples per pixel, the remaining samples only where the probe disagrees -- inside
+ * ONE dispatch, so the rays of open surface and of closed corners beyond the probe are never sent.  This is
+ * rts_trace_ambient_occlusion*'s definition with rts_trace_shadow_mask_adaptive*'s decision on top.  For n = ao->nsamples in [2, 48],
+ * a probe count k in [1, n - 1] and pixel p of the rows the call owns:
+ *   u_j = sample j's any-hit byte exactly as AMBIENT OCCLUSION above defines it: the same frame, the same idx with or without a table,
+ *   the same point light's ray at L;   c_k = u_0 + ... + u_(k-1),   c_n = u_0 + ... + u_(n-1);
+ *   counts[p]  = 0    where p is inactive (N all zero, or active != NULL && active[p] == 0; the position is never read, NaN allowed),
+ *                0    where c_k == 0,
+ *                n    where c_k == k,
+ *                c_n  otherwise;
+ *   refined[p] = 1 exactly where the c_n case applied, else 0 (inactive pixels included).  refined may be NULL.
+ * Hence counts[p] == rts_trace_ambient_occlusion's byte wherever refined[p] == 1, and elsewhere it is 0 or n.  A pixel whose probe is
+ * unanimous although its full count is not keeps the probe's verdict: that is the quality cost of the call (a pixel with one or two
+ * occluded samples of 16 often passes a probe of 4 as fully open), which is why it is a call of its own; a table makes neighbouring
+ * pixels probe different directions.  All of it is integer counting of bytes that depend on (pixel, sample) alone, so no byte depends
+ * on the kernel family, on "soft_split", on the order the samples are walked in or on any other option.  Rows outside the range /
+ * stripe are not touched.
+ *   * RTS_ERR_INVALID_ARG, nothing written, no counter moved: everything rts_trace_ambient_occlusion* refuses; nsamples < 2;
+ *     probe == 0 or probe >= nsamples.
+ *   * "kernel" picks the FAMILY as for an AO trace: the lane-per-ray walk over 16 x 16 blocks, each wave deciding for its own 8 x 8
+ *     quarter, or the stackless packet over 8 x 8 tiles -- "soft_split" 1 (default): four waves per tile that deal the probe samples,
+ *     join their counts in LDS, decide alike, and deal the remaining samples over the refining pixels; 0: one wave does both.  A tile
+ *     without an active non-background pixel ends before a ray is set up; a tile without a refining pixel ends after its probe.  Bands:
+ *     a multiple of 16 rows for the first family, of 8 for the second; a stripe that owns no band launches nothing, writes nothing
+ *     and returns RTS_OK.
+ *   * like the other block traces it ignores split tables, tile orders, follow mode, "block_waves", "wide_lane", wave statistics and
+ *     the clock probe, and never drops or alters any of them.
+ *   * the device forms are asynchronous, allocate nothing and read nothing back; under graph capture each adds ONE kernel node, `ao`,
+ *     probe, constants and options by value.  The host form copies in its rows only, traces, copies out.
+ *   * get-only option "ao_adaptive_traces": launches so far ("ao_traces" and "adaptive_traces" do not move for them);
+ *     rts_ctx_last_kernel_name then names "ambientOcclusionAdaptiveShareKernel" or "ambientOcclusionAdaptivePacketKernel<S,geom>",
+ *     S and geom as for "ambientOcclusionPacketKernel".
+ * The plane is a count plane of n samples like rts_trace_ambient_occlusion's to everything downstream.
+ * rtsh_ambient_occlusion_adaptive (rts_scene.h) is the host twin. */
+int rts_trace_ambient_occlusion_adaptive(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao, const float* positions,
+                                         const float* normals, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                         uint32_t row_end, uint32_t probe, uint8_t* counts, uint8_t* refined);
+int rts_trace_ambient_occlusion_adaptive_device(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao,
+                                                const float* d_positions, const float* d_normals, const uint8_t* d_active, uint32_t W,
+                                                uint32_t H, uint32_t row_begin, uint32_t row_end, uint32_t probe, uint8_t* d_counts,
+                                                uint8_t* d_refined, void* stream);
+int rts_trace_ambient_occlusion_adaptive_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao,
+                                                        const float* d_positions, const float* d_normals, const uint8_t* d_active,
+                                                        uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe,
+                                                        uint32_t probe, uint8_t* d_counts, uint8_t* d_refined, void* stream);
+
 /* LIGHT LISTS: up to 8 hard lights in ONE dispatch, one bit per light in the mask byte -- one read of the G-buffer texel, one launch and
  * one mask plane for all of a frame's shadow-casting lights.  For pixel p of the rows the call owns and l < list->count:
  *   mask[p] bit l = (lights_map == NULL || (lights_map[p] >> l) & 1)

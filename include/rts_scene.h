@@ -116,6 +116,17 @@ int rtsh_ambient_occlusion(const rts_vec4u* packed, size_t count_vec4, const rts
 int rtsh_ao_rays(const rts_constants* constants, const rts_ao_params* ao, const float* positions, const float* normals,
                  const uint8_t* active, uint32_t W, uint32_t H, rts_ray* rays);
 
+/* ADAPTIVE AMBIENT OCCLUSION on the host: the definition of rts_trace_ambient_occlusion_adaptive* (include/rts.h) applied literally,
+ * one straight loop over (pixel, sample) on rtsh_ambient_occlusion's walk and set-up (the same frame, the same idx, the same point
+ * light's ray at L) -- the first `probe` samples; where they agree, 0 or nsamples; where they disagree, the remaining samples and the
+ * full count.  counts[p] as defined there, refined[p] (nullable) = 1 exactly where the full count was taken.  Background and inactive
+ * pixels: 0 and 0, positions never read; rows outside [row_begin, row_end) are not touched.  The refusals are
+ * rts_trace_ambient_occlusion_adaptive's.  Runs without a GPU: the checker of the device forms, byte for byte. */
+int rtsh_ambient_occlusion_adaptive(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_ao_params* ao,
+                                    const float* positions, const float* normals, const uint8_t* active, uint32_t W, uint32_t H,
+                                    uint32_t row_begin, uint32_t row_end, uint32_t probe, uint8_t* counts, uint8_t* refined,
+                                    int threads);
+
 /* ADAPTIVE SOFT SHADOWS on the host: the definition of rts_trace_shadow_mask_adaptive* (include/rts.h) applied literally, one straight
  * loop over (pixel, sample) on rtsh_soft_distance's walk and ray set-up -- the first `probe` samples; where they agree, 0 or nsamples;
  * where they disagree, the remaining samples and the full count.  mask[p] as defined there, refined[p] (nullable) = 1 exactly where the

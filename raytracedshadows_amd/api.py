@@ -452,6 +452,15 @@ _sig("rts_trace_ambient_occlusion_stripes_device", C.c_int, C.c_void_p, C.POINTE
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
 _sig("rtsh_ambient_occlusion", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int)
+_sig("rts_trace_ambient_occlusion_adaptive", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_ambient_occlusion_adaptive_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rts_trace_ambient_occlusion_adaptive_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams),
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+     C.c_void_p)
+_sig("rtsh_ambient_occlusion_adaptive", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
 _sig("rtsh_ao_rays", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
      C.c_uint32, C.c_void_p)
 _sig("rtsh_combine_visibility_list_ao", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1130,6 +1139,44 @@ class ShadowContext:
                                                                C.c_void_p(stream or 0)),
                "rts_trace_ambient_occlusion_stripes_device")
 
+    # -- adaptive ambient occlusion (include/rts.h): `probe` AO samples per pixel, the remaining ones only where the probe disagrees --
+    def trace_ambient_occlusion_adaptive(self, constants, ao, positions, normals, width, height, probe, row_begin=0, row_end=None,
+                                         active=None, out=None, refined=None, want_refined=True):
+        """Host-pointer dispatch; returns ``(uint8[H, W] counts, uint8[H, W] refined)`` (refined None with ``want_refined`` False):
+        the count of unoccluded samples where ``refined`` is 1, else 0 or ``ao.samples`` by the probe's verdict.  ``out`` / ``refined``:
+        arrays to write into (rows outside the range keep their contents)."""
+        positions, active = _frame_inputs("trace_ambient_occlusion_adaptive", positions, width, height, active)
+        normals, _ = _frame_inputs("trace_ambient_occlusion_adaptive (normals)", normals, width, height)
+        row_end = height if row_end is None else row_end
+        counts = out if out is not None else np.zeros((height, width), dtype=np.uint8)
+        if refined is None and want_refined:
+            refined = np.zeros((height, width), dtype=np.uint8)
+        _check(_lib.rts_trace_ambient_occlusion_adaptive(self._h, C.byref(constants), _ref(ao), _ptr(positions), _ptr(normals),
+                                                         _ptr_or_none(active), width, height, row_begin, row_end, probe, _ptr(counts),
+                                                         _ptr_or_none(refined)), "rts_trace_ambient_occlusion_adaptive")
+        return counts, refined
+
+    def trace_ambient_occlusion_adaptive_device(self, constants, ao, d_positions, d_normals, width, height, d_counts, probe,
+                                                d_refined=None, row_begin=0, row_end=None, stream=None, d_active=None):
+        """Device pointers, asynchronous: d_positions / d_normals = width * height RGBA32F, d_counts = width * height bytes,
+        d_refined / d_active = the same or None."""
+        row_end = height if row_end is None else row_end
+        _check(_lib.rts_trace_ambient_occlusion_adaptive_device(self._h, C.byref(constants), _ref(ao), C.c_void_p(d_positions or 0),
+                                                                C.c_void_p(d_normals or 0), C.c_void_p(d_active or 0), width, height,
+                                                                row_begin, row_end, probe, C.c_void_p(d_counts or 0),
+                                                                C.c_void_p(d_refined or 0), C.c_void_p(stream or 0)),
+               "rts_trace_ambient_occlusion_adaptive_device")
+
+    def trace_ambient_occlusion_adaptive_stripes_device(self, constants, ao, d_positions, d_normals, width, height, d_counts, band_rows,
+                                                        n_stripes, stripe, probe, d_refined=None, stream=None, d_active=None):
+        """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        _check(_lib.rts_trace_ambient_occlusion_adaptive_stripes_device(self._h, C.byref(constants), _ref(ao), C.c_void_p(d_positions or 0),
+                                                                        C.c_void_p(d_normals or 0), C.c_void_p(d_active or 0), width,
+                                                                        height, band_rows, n_stripes, stripe, probe,
+                                                                        C.c_void_p(d_counts or 0), C.c_void_p(d_refined or 0),
+                                                                        C.c_void_p(stream or 0)),
+               "rts_trace_ambient_occlusion_adaptive_stripes_device")
+
     # -- light lists (include/rts.h): up to 8 hard lights in one dispatch, light l in bit l of the mask byte --
     def trace_light_list(self, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None):
         """Host-pointer dispatch; returns ``uint8[H, W]``: bit ``l`` = light ``l``'s shadow byte where ``lights_map`` (uint8[H, W], or
@@ -1724,6 +1771,24 @@ def ambient_occlusion(packed, constants, ao, positions, normals, width, height, 
                                        _ptr_or_none(active), width, height, row_begin, row_end, _ptr(counts), threads),
            "rtsh_ambient_occlusion")
     return counts
+
+
+def ambient_occlusion_adaptive(packed, constants, ao, positions, normals, width, height, probe, active=None, row_begin=0, row_end=None,
+                               out=None, refined=None, threads=0, want_refined=True):
+    """Adaptive ambient occlusion on the host (rtsh_ambient_occlusion_adaptive, no GPU): ``(uint8[H, W] counts, uint8[H, W] refined)``
+    -- the first ``probe`` samples of every active, non-background pixel, the remaining ones only where they disagree (refined None
+    with ``want_refined`` False)."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    positions, active = _frame_inputs("ambient_occlusion_adaptive", positions, width, height, active)
+    normals, _ = _frame_inputs("ambient_occlusion_adaptive (normals)", normals, width, height)
+    row_end = height if row_end is None else row_end
+    counts = out if out is not None else np.zeros((height, width), np.uint8)
+    if refined is None and want_refined:
+        refined = np.zeros((height, width), np.uint8)
+    _check(_lib.rtsh_ambient_occlusion_adaptive(_ptr(packed), packed.shape[0], C.byref(constants), _ref(ao), _ptr(positions),
+                                                _ptr(normals), _ptr_or_none(active), width, height, row_begin, row_end, probe,
+                                                _ptr(counts), _ptr_or_none(refined), threads), "rtsh_ambient_occlusion_adaptive")
+    return counts, refined
 
 
 def ao_rays(constants, ao, positions, normals, width, height, active=None):

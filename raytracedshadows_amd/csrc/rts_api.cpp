@@ -6,6 +6,7 @@
 #include "rts_device.h"
 #include "rts_soft_distance.h"
 #include "rts_ao.h"
+#include "rts_ao_adaptive.h"
 #include "rts_light_list.h"
 #include "rts_adaptive.h"
 #include "rts_soft_light_list.h"
@@ -55,6 +56,7 @@ struct rts_ctx {
     uint64_t softLightListTraces = 0;                 // launches of a soft light list kernel (get-only option "soft_light_list_traces")
     uint64_t softListDistanceTraces = 0;              // launches of a soft light list distance kernel (get-only option "soft_list_distance_traces")
     uint64_t aoTraces = 0;                            // launches of an ambient occlusion kernel (get-only option "ao_traces")
+    uint64_t aoAdaptiveTraces = 0;                    // launches of an adaptive ambient occlusion kernel (get-only option "ao_adaptive_traces")
     uint64_t sparseListTraces = 0;                    // launches of a sparse light list kernel, hard or soft (get-only option "sparse_list_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
@@ -586,6 +588,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "soft_list_jitter_traces")) { *value = (int)(c->softListJitterTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_light_list_traces")) { *value = (int)(c->softLightListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "ao_traces")) { *value = (int)(c->aoTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "ao_adaptive_traces")) { *value = (int)(c->aoAdaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "sparse_list_traces")) { *value = (int)(c->sparseListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_list_distance_traces")) { *value = (int)(c->softListDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
@@ -994,10 +997,14 @@ int rts_trace_soft_distance_stripes_device(rts_ctx* c, const rts_constants* k, c
 // One launch of an AO kernel (rts_ao.inc) with the geometry, the family rule and the tail of a distance trace.  The normals travel in
 // the distances' slot of the argument block, the radius in the light's x, the directions in the sample offsets and their table size
 // in the light's table (rts_ao.h), so sampleIndex and pixelBase are the mask traces' own.
+// probe == 0: the AO trace itself.  probe != 0: its adaptive form (rts_ao_adaptive.inc), the probe count and the refined plane in the
+// slots rts_ao_adaptive.h names, counted by "ao_adaptive_traces" alone.
 static int traceAmbientOcclusionImpl(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* d_positions,
-                                     const float* d_normals, const uint8_t* d_active, const Dispatch& g, uint8_t* d_counts, void* stream) {
+                                     const float* d_normals, const uint8_t* d_active, const Dispatch& g, uint8_t* d_counts, void* stream,
+                                     bool adaptive = false, uint32_t probe = 0, uint8_t* d_refined = nullptr) {
     TraceParams p; uint32_t rows = 0; int s;
-    if (beginFrame(c, k, d_positions, d_counts, d_counts && d_normals && rts::aoParamsOk(ao), g, p, &rows, &s) != Begin::Go) return s;
+    const bool ownOk = d_counts && d_normals && (adaptive ? rts::aoAdaptiveOk(ao, probe) : rts::aoParamsOk(ao));
+    if (beginFrame(c, k, d_positions, d_counts, ownOk, g, p, &rows, &s) != Begin::Go) return s;
     rts::setAoNormals(p, d_normals);
     p.activeMap = d_active;
     for (int i = 0; i < 3; ++i) p.cam[i] = k->cameraPosition[i];
@@ -1006,6 +1013,11 @@ static int traceAmbientOcclusionImpl(rts_ctx* c, const rts_constants* k, const r
     p.lightTable = ao->table;
     p.light[0] = ao->radius; p.light[1] = 0.0f; p.light[2] = 0.0f;
     memcpy(p.offsets, ao->dirs, sizeof(float) * 4 * (p.lightTable ? p.lightTable : p.nsamples));
+    if (adaptive) {
+        p.nrays = probe;
+        rts::setAoRefined(p, d_refined);
+        return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::aoAdaptiveTraces, rts::launchAmbientOcclusionAdaptive, stream);
+    }
     return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::aoTraces, rts::launchAmbientOcclusion, stream);
 }
 
@@ -1021,6 +1033,22 @@ int rts_trace_ambient_occlusion_stripes_device(rts_ctx* c, const rts_constants* 
     if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
     return traceAmbientOcclusionImpl(c, k, ao, d_positions, d_normals, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe),
                                      d_counts, stream);
+}
+
+int rts_trace_ambient_occlusion_adaptive_device(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* d_positions,
+                                                const float* d_normals, const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                                uint32_t row_end, uint32_t probe, uint8_t* d_counts, uint8_t* d_refined, void* stream) {
+    return traceAmbientOcclusionImpl(c, k, ao, d_positions, d_normals, d_active, Dispatch::ofRows(W, H, row_begin, row_end), d_counts, stream,
+                                     true, probe, d_refined);
+}
+
+int rts_trace_ambient_occlusion_adaptive_stripes_device(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* d_positions,
+                                                        const float* d_normals, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                                        uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint32_t probe,
+                                                        uint8_t* d_counts, uint8_t* d_refined, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceAmbientOcclusionImpl(c, k, ao, d_positions, d_normals, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe),
+                                     d_counts, stream, true, probe, d_refined);
 }
 
 // ---- adaptive soft shadows (include/rts.h): a probe of a few samples per pixel, the others only where the probe disagrees ------------
@@ -1069,7 +1097,8 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 // Frames (arguments checked by the caller): only rows [rowBegin, rowEnd) travel -- their positions, map, mask and distances, as a
 // frame of their own, to the device entry of what is being traced.  StagedRows names what a host entry hands over: the first nine
 // members every entry gives, in this order; the others it sets by name, and what it leaves alone is NULL.
-enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive, SoftListDistance, AmbientOcclusion };
+enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive, SoftListDistance, AmbientOcclusion,
+                    AoAdaptive };
 struct StagedRows {
     Staged what;
     const rts_constants* k;
@@ -1081,11 +1110,12 @@ struct StagedRows {
     uint32_t W, H, rowBegin, rowEnd;     // the caller's frame: its planes are W * H apart, of the staged rows alone on the device
     uint8_t* mask = nullptr;             // the mask; a soft list's count planes, `count` of them (optional beside distances)
     float* distance = nullptr;           // of the distance traces alone; Staged::SoftListDistance: a plane per light, like the counts
-    uint32_t probe = 0;                  // Staged::Adaptive
-    uint8_t* refined = nullptr;          // Staged::Adaptive, Staged::SoftListAdaptive (optional): staged in the distances' buffer
+    uint32_t probe = 0;                  // Staged::Adaptive, Staged::AoAdaptive
+    uint8_t* refined = nullptr;          // Staged::Adaptive, Staged::SoftListAdaptive (optional): staged in the distances' buffer;
+                                         // Staged::AoAdaptive (optional): behind the normals there
     const uint32_t* probes = nullptr;    // Staged::SoftListAdaptive: one per light
     const uint32_t* tables = nullptr;    // ... its jittered form, whose hash pixelBase makes that of the caller's frame
-    const float* normals = nullptr;      // Staged::AmbientOcclusion: staged in the distances' buffer
+    const float* normals = nullptr;      // Staged::AmbientOcclusion, Staged::AoAdaptive: staged in the distances' buffer
 };
 static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
@@ -1099,7 +1129,7 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     const size_t distPlanes = r.what == Staged::SoftListDistance ? planes : 1u;
     if (s == RTS_OK && r.distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4 * distPlanes);
     if (s == RTS_OK && r.refined) s = ensure(&c->d_dist, &c->distBytes, pixels);
-    if (s == RTS_OK && r.normals) s = ensure(&c->d_dist, &c->distBytes, pixels * 16);
+    if (s == RTS_OK && r.normals) s = ensure(&c->d_dist, &c->distBytes, pixels * 16 + (r.refined ? pixels : 0u));
     if (s == RTS_OK && r.mask) s = ensure(&c->d_out, &c->outBytes, pixels * planes);
     if (s == RTS_OK && r.active) s = ensure(&c->d_act, &c->actBytes, pixels);
     if (s != RTS_OK) return s;
@@ -1111,7 +1141,7 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     const rts_soft_light_list* const softLights = (const rts_soft_light_list*)r.lights;
     const uint8_t* d_active = r.active ? (const uint8_t*)c->d_act : nullptr;
     uint8_t* d_mask = r.mask ? (uint8_t*)c->d_out : nullptr;
-    uint8_t* d_refined = r.refined ? (uint8_t*)c->d_dist : nullptr;
+    uint8_t* d_refined = r.refined ? (uint8_t*)c->d_dist + (r.normals ? pixels * 16 : 0u) : nullptr;
     const float* d_in = (const float*)c->d_in;
     float* d_dist = (float*)c->d_dist;
     // per-pixel jitter hashes the pixel's index in the caller's frame (sampleIndex, rts_kernels.hip: the one reader, and only of a
@@ -1138,12 +1168,15 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     case Staged::AmbientOcclusion:
         s = rts_trace_ambient_occlusion_device(c, k, (const rts_ao_params*)r.lights, d_in, d_dist, d_active, W, rows, 0, rows, d_mask,
                                                nullptr); break;
+    case Staged::AoAdaptive:
+        s = rts_trace_ambient_occlusion_adaptive_device(c, k, (const rts_ao_params*)r.lights, d_in, d_dist, d_active, W, rows, 0, rows,
+                                                        r.probe, d_mask, d_refined, nullptr); break;
     }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
     for (size_t l = 0; r.distance && l < distPlanes; ++l)
         RTS_HIP(hipMemcpy(r.distance + l * frame + first, (const float*)c->d_dist + l * pixels, pixels * 4, hipMemcpyDeviceToHost));
-    if (r.refined) RTS_HIP(hipMemcpy(r.refined + first, c->d_dist, pixels, hipMemcpyDeviceToHost));
+    if (r.refined) RTS_HIP(hipMemcpy(r.refined + first, d_refined, pixels, hipMemcpyDeviceToHost));
     for (size_t l = 0; r.mask && l < planes; ++l)
         RTS_HIP(hipMemcpy(r.mask + l * frame + first, (const uint8_t*)c->d_out + l * pixels, pixels, hipMemcpyDeviceToHost));
     return RTS_OK;
@@ -1191,6 +1224,16 @@ int rts_trace_ambient_occlusion(rts_ctx* c, const rts_constants* k, const rts_ao
     if (!rts::aoParamsOk(ao) || (uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;
     StagedRows r{ Staged::AmbientOcclusion, k, ao, positions, active, W, H, row_begin, row_end };
     r.mask = counts; r.normals = normals;
+    return traceStagedRows(c, r);
+}
+
+int rts_trace_ambient_occlusion_adaptive(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* positions,
+                                         const float* normals, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                         uint32_t row_end, uint32_t probe, uint8_t* counts, uint8_t* refined) {
+    if (!c || !k || !positions || !normals || !counts || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::aoAdaptiveOk(ao, probe) || (uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;
+    StagedRows r{ Staged::AoAdaptive, k, ao, positions, active, W, H, row_begin, row_end };
+    r.mask = counts; r.normals = normals; r.probe = probe; r.refined = refined;
     return traceStagedRows(c, r);
 }
 

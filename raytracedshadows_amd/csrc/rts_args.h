@@ -84,6 +84,11 @@ inline bool aoParamsOk(const rts_ao_params* ao) {
     return (bits & 0x7F800000u) != 0x7F800000u;                          // Inf or NaN: every exponent bit set
 }
 
+// an adaptive ambient occlusion trace: aoParamsOk's rules, at least 2 samples, and a probe of 1..nsamples - 1
+inline bool aoAdaptiveOk(const rts_ao_params* ao, uint32_t probe) {
+    return aoParamsOk(ao) && ao->nsamples >= 2 && probe >= 1 && probe < ao->nsamples;
+}
+
 // the pixel list of a sparse list trace: the list and its length (on the device in the device forms) and room for at least one entry
 inline bool sparseListOk(const uint32_t* pixels, const uint32_t* n, uint32_t capacity) {
     return pixels && n && capacity != 0;

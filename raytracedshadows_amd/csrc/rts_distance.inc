@@ -300,3 +300,5 @@ hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
 #include "rts_light_list_sparse.inc"
 // ambient occlusion: hemisphere segments around the G-buffer's normal, counted (its launch is declared in rts_ao.h)
 #include "rts_ao.inc"
+// adaptive ambient occlusion: a probe of a few AO samples, the others only where it disagrees (its launch is declared in rts_ao_adaptive.h)
+#include "rts_ao_adaptive.inc"

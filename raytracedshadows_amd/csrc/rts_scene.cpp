@@ -394,6 +394,44 @@ extern "C" int rtsh_ao_rays(const rts_constants* k, const rts_ao_params* ao, con
     return RTS_OK;
 }
 
+// ---- adaptive ambient occlusion on the host (include/rts_scene.h): the checker of rts_trace_ambient_occlusion_adaptive* ----
+// The definition of include/rts.h applied literally on rtsh_ambient_occlusion's walk and set-up (aoFrame, aoAim, the point light's ray
+// at L): the probe's samples, then the others only where the probe disagrees.
+extern "C" int rtsh_ambient_occlusion_adaptive(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_ao_params* ao,
+                                               const float* positions, const float* normals, const uint8_t* active, uint32_t W, uint32_t H,
+                                               uint32_t row_begin, uint32_t row_end, uint32_t probe, uint8_t* counts, uint8_t* refined,
+                                               int threads) {
+    if (!packed || !k || !positions || !normals || !counts || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::aoAdaptiveOk(ao, probe)) return RTS_ERR_INVALID_ARG;
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t n = ao->nsamples;
+    const size_t first = (size_t)row_begin * W;
+    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t at) {
+        const size_t i = first + at;
+        if (refined) refined[i] = 0;
+        const float* n4 = normals + i * 4;
+        const V3 N{ n4[0], n4[1], n4[2] };
+        if (isBackground(N) || (active && !active[i])) { counts[i] = 0; return; }
+        const float* q = positions + i * 4;
+        const V3 cam{ k->cameraPosition[0], k->cameraPosition[1], k->cameraPosition[2] }, rel{ q[0], q[1], q[2] };
+        const AoFrame f = aoFrame(N);
+        uint32_t lit = 0;
+        for (uint32_t j = 0; j < n; ++j) {
+            if (j == probe && (lit == 0 || lit == probe)) {              // the probe agrees: its verdict, no further ray
+                counts[i] = (uint8_t)(lit ? n : 0u);
+                return;
+            }
+            const V3 L = aoAim(cam, rel, N, f, ao->dirs[sampleIndex(ao->table, j, (uint32_t)i)], ao->radius);
+            lit += rayDistanceBits(bvh, shadowRay(k->cameraPosition, rel, RTS_LIGHT_POINT, L)) == 0x7F800000u ? 1u : 0u;   // u_j
+        }
+        counts[i] = (uint8_t)lit;
+        if (refined) refined[i] = 1;
+    });
+    return RTS_OK;
+}
+
 // ---- adaptive soft shadows on the host (include/rts_scene.h): the checker of rts_trace_shadow_mask_adaptive* ----
 // The definition of include/rts.h applied literally, one straight loop over (pixel, sample) on frameDistance's walk: the probe's
 // samples, then the others only where the probe disagrees.

@@ -134,13 +134,31 @@ def parse_ao(text, wl):
     return api.AoParams.make(n, radius, table=table, seed=5)
 
 
+AO_ADAPTIVE = {"probe": 0, "refined_out": ""}           # --ao-adaptive K [--ao-refined FILE.ppm], set by main()
+
+
 def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
     """Traces ambient occlusion on the device and turns the counts into a float plane under the stand-in list: through `filt` (--filter /
-    --filter-passes) when given, else the R = 0 tent filter -- (float)c / (float)n.  -> the plane (device)."""
+    --filter-passes) when given, else the R = 0 tent filter -- (float)c / (float)n.  -> the plane (device).
+    With --ao-adaptive K the counts come from rts_trace_ambient_occlusion_adaptive_device: the same kind of plane, nothing behind it changes."""
     d_counts, d_ao = ctx.malloc(W * H), ctx.malloc(W * H * 4)
+    probe = AO_ADAPTIVE["probe"]
     t0 = time.time()
-    ctx.trace_ambient_occlusion_device(wl.constants, ao, d_pos, d_nrm, W, H, d_counts)
-    ctx.synchronize()
+    if probe:
+        d_refined = ctx.malloc(W * H)
+        ctx.trace_ambient_occlusion_adaptive_device(wl.constants, ao, d_pos, d_nrm, W, H, d_counts, probe, d_refined=d_refined)
+        ctx.synchronize()
+        refined = np.zeros((H, W), np.uint8)
+        ctx.d2h(refined, d_refined)
+        ctx.free(d_refined)
+        print(f"adaptive ambient occlusion: probe {probe} of {ao.samples}, {float(refined.mean()) * 100:.1f} % of the pixels refined")
+        if AO_ADAPTIVE["refined_out"]:
+            os.makedirs(os.path.dirname(os.path.abspath(AO_ADAPTIVE["refined_out"])), exist_ok=True)
+            api.write_ppm(AO_ADAPTIVE["refined_out"], np.repeat((refined * 255).astype(np.uint8)[..., None], 3, axis=2))
+            print(f"wrote {AO_ADAPTIVE['refined_out']}")
+    else:
+        ctx.trace_ambient_occlusion_device(wl.constants, ao, d_pos, d_nrm, W, H, d_counts)
+        ctx.synchronize()
     print(f"ambient occlusion: {ao.samples} segments of {ao.radius:g} per pixel{f', table {ao.table}' if ao.table else ''}: "
           f"{(time.time() - t0) * 1e3:.2f} ms (first call, incl. launch); {ctx.last_kernel_name()}")
     stand_in = ao.stand_in_list()
@@ -481,6 +499,10 @@ def main():
                          "through --filter R / --filter-passes K (default: the R = 0 filter) and scale the ambient term "
                          "(rtsh_combine_visibility_list_ao_device)")
     ap.add_argument("--ao-out", default="", metavar="FILE.ppm", help="with --ao: also write the ambient occlusion plane as an image")
+    ap.add_argument("--ao-adaptive", type=int, default=0, metavar="K",
+                    help="with --ao N: trace K probe segments per pixel and the other N - K only where the probe disagrees "
+                         "(rts_trace_ambient_occlusion_adaptive_device), 1 <= K < N; the plane goes the same way")
+    ap.add_argument("--ao-refined", default="", metavar="FILE.ppm", help="with --ao-adaptive: also write the refined plane as an image")
     args = ap.parse_args()
     from raytracedshadows_amd import api, workloads
     scene, W, H, light, spp = workloads.CONFIGS[args.config]
@@ -492,6 +514,13 @@ def main():
         if args.ao_out and not args.ao:
             sys.exit("render: --ao-out goes with --ao")
         ao = parse_ao(args.ao, wl) if args.ao else None
+        if (args.ao_adaptive or args.ao_refined) and ao is None:
+            sys.exit("render: --ao-adaptive and --ao-refined go with --ao")
+        if args.ao_refined and not args.ao_adaptive:
+            sys.exit("render: --ao-refined goes with --ao-adaptive")
+        if args.ao_adaptive and not 1 <= args.ao_adaptive < ao.samples:
+            sys.exit("render: --ao-adaptive K takes 1 <= K < N")
+        AO_ADAPTIVE.update(probe=args.ao_adaptive, refined_out=args.ao_refined)
         if ao is not None and args.temporal:
             sys.exit("render: --ao does not go with --temporal")
         if args.soft_list:
