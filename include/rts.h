@@ -474,6 +474,47 @@ int rts_trace_ambient_occlusion_adaptive_stripes_device(rts_ctx* ctx, const rts_
                                                         uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe,
                                                         uint32_t probe, uint8_t* d_counts, uint8_t* d_refined, void* stream);
 
+/* BENT NORMALS: the AO trace with the DIRECTION the hemisphere is open in beside the count -- per pixel the frame applied to the sum of
+ * the unoccluded samples' directions, what an ambient term lit from a sky or an environment is aimed by.  The rays
+ * are rts_trace_ambient_occlusion*'s own.  For pixel p of the rows the call owns, u_j, idx(p, j), N, T and B are exactly those of
+ * AMBIENT OCCLUSION above, n = max(1, ao->nsamples):
+ *   Q(v)  = 0 if v is NaN, else (int32) rint(min(max(v, -1.0f), 1.0f) * 16384.0f): the product is exact, ties round to even,
+ *           infinities clamp to +-16384;
+ *   q_j   = (Q(s.x), Q(s.y), Q(s.z)) for s = dirs[idx(p, j)]: a function of the table entry alone;
+ *   S     = sum over j of u_j * q_j, an INTEGER vector;  c = sum u_j, the AO trace's byte;  |S.c| <= 48 * 16384 < 2^24;
+ *   f     = ((float)S.x * 0x1p-14f, (float)S.y * 0x1p-14f, (float)S.z * 0x1p-14f): both steps exact;
+ *   bent[p].c = ((T.c * f.x) + (B.c * f.y)) + (N.c * f.z) per component c of xyz, each operation ONE rounded float operation, no
+ *           contraction;   bent[p].w = (float)c.
+ *   INACTIVE (N all zero, or active != NULL && active[p] == 0): counts[p] = 0, bent[p] = (+0, +0, +0, +0); the position is never read.
+ * WHY THE SUM IS TAKEN IN TANGENT SPACE: the frame is linear, so the sum of the samples' world directions IS the frame applied to the
+ * sum of their tangent-space directions -- but only the latter can be added over integers.  Summing per-sample world directions in
+ * float would make the result depend on the order the samples are walked in and on which wave walked which; integer addition is
+ * associative, so S is as order-free as the count is, and the frame meets it ONCE, in the written order.  Hence no byte of `bent` or
+ * `counts` depends on the kernel family, on "soft_split" or on any other option.  (An active pixel with c == 0 gets the frame applied
+ * to the zero vector: every component is a zero, whose sign is the written operations' -- -0 where all three products are -0.)
+ * The vector is NOT normalised: its length over c says how narrow the open cone is; rtsh_combine_visibility_list_ao_bent normalises.
+ * `bent`: W x H RGBA32F, required.  `counts`: W x H bytes or NULL; where given it is byte for byte the plane
+ * rts_trace_ambient_occlusion* writes.  Rows outside the range / stripe are not touched in either plane.
+ *   * RTS_ERR_INVALID_ARG, nothing written, no counter moved: everything rts_trace_ambient_occlusion* refuses except NULL counts; NULL
+ *     bent.
+ *   * families, "soft_split", bands, the ignored options and the behaviour under capture are rts_trace_ambient_occlusion*'s: ONE
+ *     kernel node per call, `ao`, constants and options by value; the four waves of a tile add their integer words in LDS.
+ *   * get-only option "ao_bent_traces": launches so far ("ao_traces" and "ao_adaptive_traces" do not move for them);
+ *     rts_ctx_last_kernel_name then names "ambientOcclusionBentShareKernel" or "ambientOcclusionBentPacketKernel<S,geom>", S and
+ *     geom as for "ambientOcclusionPacketKernel".
+ * rtsh_ambient_occlusion_bent (rts_scene.h) is the host twin. */
+int rts_trace_ambient_occlusion_bent(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao, const float* positions,
+                                     const float* normals, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                     uint32_t row_end, uint8_t* counts, float* bent);
+int rts_trace_ambient_occlusion_bent_device(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao,
+                                            const float* d_positions, const float* d_normals, const uint8_t* d_active, uint32_t W,
+                                            uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* d_counts, float* d_bent,
+                                            void* stream);
+int rts_trace_ambient_occlusion_bent_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao,
+                                                    const float* d_positions, const float* d_normals, const uint8_t* d_active,
+                                                    uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe,
+                                                    uint8_t* d_counts, float* d_bent, void* stream);
+
 /* LIGHT LISTS: up to 8 hard lights in ONE dispatch, one bit per light in the mask byte -- one read of the G-buffer texel, one launch and
  * one mask plane for all of a frame's shadow-casting lights.  For pixel p of the rows the call owns and l < list->count:
  *   mask[p] bit l = (lights_map == NULL || (lights_map[p] >> l) & 1)

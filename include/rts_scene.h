@@ -127,6 +127,15 @@ int rtsh_ambient_occlusion_adaptive(const rts_vec4u* packed, size_t count_vec4, 
                                     uint32_t row_begin, uint32_t row_end, uint32_t probe, uint8_t* counts, uint8_t* refined,
                                     int threads);
 
+/* BENT NORMALS on the host: the definition of rts_trace_ambient_occlusion_bent* (include/rts.h) applied literally, one straight loop
+ * over (pixel, sample) on rtsh_ambient_occlusion's walk and set-up -- the integer sum of Q(dirs[idx]) over the unoccluded samples, the
+ * frame applied to it once; the quantisation and the final transform are the kernels' own source.  counts (nullable) and bent as
+ * defined there.  Background and inactive pixels: 0 and (+0, +0, +0, +0), positions never read; rows outside [row_begin, row_end) are
+ * not touched.  The refusals are rts_trace_ambient_occlusion_bent's.  Runs without a GPU: the checker of the device forms, bit for bit. */
+int rtsh_ambient_occlusion_bent(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_ao_params* ao,
+                                const float* positions, const float* normals, const uint8_t* active, uint32_t W, uint32_t H,
+                                uint32_t row_begin, uint32_t row_end, uint8_t* counts, float* bent, int threads);
+
 /* ADAPTIVE SOFT SHADOWS on the host: the definition of rts_trace_shadow_mask_adaptive* (include/rts.h) applied literally, one straight
  * loop over (pixel, sample) on rtsh_soft_distance's walk and ray set-up -- the first `probe` samples; where they agree, 0 or nsamples;
  * where they disagree, the remaining samples and the full count.  mask[p] as defined there, refined[p] (nullable) = 1 exactly where the
@@ -312,6 +321,33 @@ int rtsh_combine_visibility_list_ao_device(rts_ctx* ctx, const rts_constants* co
                                            const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
                                            const float* d_visibility, const float* d_ao, uint32_t W, uint32_t H, uint8_t* d_rgb,
                                            void* stream);
+
+/* THE VISIBILITY COMBINE WITH AMBIENT OCCLUSION AND A SKY: rtsh_combine_visibility_list_ao* with a hemispheric tint on the ambient
+ * term, aimed by the pixel's bent vector (rts_trace_ambient_occlusion_bent*'s plane, W x H RGBA32F; .w is not read): where the open
+ * part of the hemisphere looks along `up` the ambient light takes the sky's colour, against it the ground's.  Per non-background pixel
+ * p, b = bent[p].xyz, every operation ONE rounded float operation, parenthesised as written, no contraction:
+ *   l2 = ((b.x * b.x) + (b.y * b.y)) + (b.z * b.z);   len = sqrtf(l2);
+ *   u  = (((b.x * up.x) + (b.y * up.y)) + (b.z * up.z)) / len  if len > 0 and len is finite, else 0;
+ *   h  = 0.5f + 0.5f * u;   h = (h > 0) ? ((h < 1) ? h : 1) : 0   (a NaN becomes 0);
+ *   tint_c = ground_c + (sky_c - ground_c) * h;   channel c's ambient term = (ambient * ao[p]) * tint_c.
+ * Everything else is rtsh_combine_visibility_list_ao's: the direct terms, the order of the sum, the rounding to bytes and every refusal;
+ * NULL bent or NULL sky: RTS_ERR_INVALID_ARG as well.  Any float is allowed in `bent` and in the sky.  ANCHORS: sky == ground ==
+ * (1, 1, 1) gives rtsh_combine_visibility_list_ao's bytes (1 + 0 * h == 1); an all-zero bent texel gives h = 0.5.  The device form adds
+ * one kernel node, the sky by value; the per-pixel source is shared, byte for byte. */
+typedef struct rtsh_sky_ambient {
+    float up[3];        /* the direction of the sky; normalise it (it is used as given) */
+    float sky[3];       /* the ambient light's colour where the bent vector points along up */
+    float ground[3];    /* ... and where it points against it */
+    float reserved_[3]; /* ignored */
+} rtsh_sky_ambient;     /* 48 bytes */
+int rtsh_combine_visibility_list_ao_bent(const rts_constants* constants, const rts_light_list* list, const float* colors,
+                                         const float* positions, const float* normals, const uint8_t* lights_map, const float* visibility,
+                                         const float* ao, const float* bent, const rtsh_sky_ambient* sky, uint32_t W, uint32_t H,
+                                         uint8_t* rgb);
+int rtsh_combine_visibility_list_ao_bent_device(rts_ctx* ctx, const rts_constants* constants, const rts_light_list* list, const float* colors,
+                                                const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                const float* d_visibility, const float* d_ao, const float* d_bent,
+                                                const rtsh_sky_ambient* sky, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream);
 
 /* THE TEMPORAL ACCUMULATION OF A LIGHT LIST'S VISIBILITY: this frame's float visibility planes (a filter's output; the R = 0 filter is
  * the conversion from counts) blended with LAST frame's result, which is fetched through the camera motion -- reprojected -- and

@@ -233,6 +233,20 @@ class AoParams(C.Structure):
         return SoftLightList.make([(Light.POINT, (0.0, 0.0, 0.0), self.samples, 0, 0.0)])
 
 
+class SkyAmbient(C.Structure):
+    """``rtsh_sky_ambient``: the hemispheric sky of ``combine_visibility_list_ao_bent`` -- the ambient light's colour where a pixel's
+    bent vector points along ``up`` (``sky``) and against it (``ground``)."""
+    _fields_ = [("up", C.c_float * 3), ("sky", C.c_float * 3), ("ground", C.c_float * 3), ("reserved_", C.c_float * 3)]
+
+    @classmethod
+    def make(cls, up=(0.0, 1.0, 0.0), sky=(1.0, 1.0, 1.0), ground=(1.0, 1.0, 1.0)):
+        """``up`` is used as given: normalise it."""
+        s = cls()
+        for i in range(3):
+            s.up[i], s.sky[i], s.ground[i] = np.float32(up[i]), np.float32(sky[i]), np.float32(ground[i])
+        return s
+
+
 class FilterParams(C.Structure):
     """``rtsh_filter_params``: the window radius (0..8), the two geometry thresholds and, for the distance guide, one spread per light."""
     _fields_ = [("radius", C.c_uint32), ("normal_cos_min", C.c_float), ("plane_eps", C.c_float), ("spread", C.c_float * 8),
@@ -461,6 +475,19 @@ _sig("rts_trace_ambient_occlusion_adaptive_stripes_device", C.c_int, C.c_void_p,
      C.c_void_p)
 _sig("rtsh_ambient_occlusion_adaptive", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rts_trace_ambient_occlusion_bent", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)
+_sig("rts_trace_ambient_occlusion_bent_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rts_trace_ambient_occlusion_bent_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams),
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_ambient_occlusion_bent", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rtsh_combine_visibility_list_ao_bent", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SkyAmbient), C.c_uint32, C.c_uint32, C.c_void_p)
+_sig("rtsh_combine_visibility_list_ao_bent_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SkyAmbient), C.c_uint32, C.c_uint32, C.c_void_p,
+     C.c_void_p)
 _sig("rtsh_ao_rays", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
      C.c_uint32, C.c_void_p)
 _sig("rtsh_combine_visibility_list_ao", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -1177,6 +1204,43 @@ class ShadowContext:
                                                                         C.c_void_p(stream or 0)),
                "rts_trace_ambient_occlusion_adaptive_stripes_device")
 
+    # -- bent normals (include/rts.h): the AO trace with the frame applied to the integer sum of its unoccluded directions --
+    def trace_ambient_occlusion_bent(self, constants, ao, positions, normals, width, height, row_begin=0, row_end=None, active=None,
+                                     out=None, bent=None, want_counts=True):
+        """Host-pointer dispatch; returns ``(uint8[H, W] counts, float32[H, W, 4] bent)`` (counts None with ``want_counts`` False):
+        ``bent[..., :3]`` the unnormalised mean free direction times the count, ``bent[..., 3]`` the count.  ``out`` / ``bent``: arrays
+        to write into (rows outside the range keep their contents)."""
+        positions, active = _frame_inputs("trace_ambient_occlusion_bent", positions, width, height, active)
+        normals, _ = _frame_inputs("trace_ambient_occlusion_bent (normals)", normals, width, height)
+        row_end = height if row_end is None else row_end
+        counts = out if out is not None else (np.zeros((height, width), dtype=np.uint8) if want_counts else None)
+        if bent is None:
+            bent = np.zeros((height, width, 4), dtype=np.float32)
+        _check(_lib.rts_trace_ambient_occlusion_bent(self._h, C.byref(constants), _ref(ao), _ptr(positions), _ptr(normals),
+                                                     _ptr_or_none(active), width, height, row_begin, row_end, _ptr_or_none(counts),
+                                                     _ptr(bent)), "rts_trace_ambient_occlusion_bent")
+        return counts, bent
+
+    def trace_ambient_occlusion_bent_device(self, constants, ao, d_positions, d_normals, width, height, d_counts, d_bent, row_begin=0,
+                                            row_end=None, stream=None, d_active=None):
+        """Device pointers, asynchronous: d_positions / d_normals / d_bent = width * height RGBA32F, d_counts (or None) / d_active (or
+        None) = width * height bytes."""
+        row_end = height if row_end is None else row_end
+        _check(_lib.rts_trace_ambient_occlusion_bent_device(self._h, C.byref(constants), _ref(ao), C.c_void_p(d_positions or 0),
+                                                            C.c_void_p(d_normals or 0), C.c_void_p(d_active or 0), width, height,
+                                                            row_begin, row_end, C.c_void_p(d_counts or 0), C.c_void_p(d_bent or 0),
+                                                            C.c_void_p(stream or 0)),
+               "rts_trace_ambient_occlusion_bent_device")
+
+    def trace_ambient_occlusion_bent_stripes_device(self, constants, ao, d_positions, d_normals, width, height, d_counts, d_bent,
+                                                    band_rows, n_stripes, stripe, stream=None, d_active=None):
+        """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        _check(_lib.rts_trace_ambient_occlusion_bent_stripes_device(self._h, C.byref(constants), _ref(ao), C.c_void_p(d_positions or 0),
+                                                                    C.c_void_p(d_normals or 0), C.c_void_p(d_active or 0), width, height,
+                                                                    band_rows, n_stripes, stripe, C.c_void_p(d_counts or 0),
+                                                                    C.c_void_p(d_bent or 0), C.c_void_p(stream or 0)),
+               "rts_trace_ambient_occlusion_bent_stripes_device")
+
     # -- light lists (include/rts.h): up to 8 hard lights in one dispatch, light l in bit l of the mask byte --
     def trace_light_list(self, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None):
         """Host-pointer dispatch; returns ``uint8[H, W]``: bit ``l`` = light ``l``'s shadow byte where ``lights_map`` (uint8[H, W], or
@@ -1789,6 +1853,24 @@ def ambient_occlusion_adaptive(packed, constants, ao, positions, normals, width,
                                                 _ptr(normals), _ptr_or_none(active), width, height, row_begin, row_end, probe,
                                                 _ptr(counts), _ptr_or_none(refined), threads), "rtsh_ambient_occlusion_adaptive")
     return counts, refined
+
+
+def ambient_occlusion_bent(packed, constants, ao, positions, normals, width, height, active=None, row_begin=0, row_end=None, out=None,
+                           bent=None, threads=0, want_counts=True):
+    """Bent normals on the host (rtsh_ambient_occlusion_bent, no GPU): ``(uint8[H, W] counts, float32[H, W, 4] bent)`` -- the AO count
+    and, per pixel, the frame applied to the integer sum of the unoccluded samples' quantised directions, with the count in ``.w``
+    (counts None with ``want_counts`` False)."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    positions, active = _frame_inputs("ambient_occlusion_bent", positions, width, height, active)
+    normals, _ = _frame_inputs("ambient_occlusion_bent (normals)", normals, width, height)
+    row_end = height if row_end is None else row_end
+    counts = out if out is not None else (np.zeros((height, width), np.uint8) if want_counts else None)
+    if bent is None:
+        bent = np.zeros((height, width, 4), np.float32)
+    _check(_lib.rtsh_ambient_occlusion_bent(_ptr(packed), packed.shape[0], C.byref(constants), _ref(ao), _ptr(positions), _ptr(normals),
+                                            _ptr_or_none(active), width, height, row_begin, row_end, _ptr_or_none(counts), _ptr(bent),
+                                            threads), "rtsh_ambient_occlusion_bent")
+    return counts, bent
 
 
 def ao_rays(constants, ao, positions, normals, width, height, active=None):
@@ -2415,6 +2497,42 @@ def combine_visibility_list_ao_device(ctx, constants, light_list, d_positions, d
                                                        C.c_void_p(d_positions or 0), C.c_void_p(d_normals), C.c_void_p(d_lights_map or 0),
                                                        C.c_void_p(d_visibility), C.c_void_p(d_ao or 0), width, height, C.c_void_p(d_rgb),
                                                        C.c_void_p(stream or 0)), "rtsh_combine_visibility_list_ao_device")
+
+
+def combine_visibility_list_ao_bent(constants, light_list, positions, normals, visibility, ao, bent, sky, lights_map=None, colors=None):
+    """The visibility combine with ambient occlusion and a sky on the host (rtsh_combine_visibility_list_ao_bent):
+    ``combine_visibility_list_ao`` with the ambient term of pixel ``p`` tinted between ``sky.ground`` and ``sky.sky`` by where
+    ``bent[p]`` (``float32[H, W, 4]``, a bent trace's plane) points relative to ``sky.up``."""
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    visibility = np.ascontiguousarray(visibility, np.float32)
+    ao = np.ascontiguousarray(ao, np.float32) if ao is not None else None
+    bent = np.ascontiguousarray(bent, np.float32) if bent is not None else None
+    lights_map = np.ascontiguousarray(lights_map, np.uint8) if lights_map is not None else None
+    if visibility.size < (light_list.count if light_list is not None and light_list.count <= 8 else 1) * H * W or \
+            (lights_map is not None and lights_map.size != H * W) or (positions is not None and positions.size != H * W * 4) or \
+            (ao is not None and ao.size != H * W) or (bent is not None and bent.size != H * W * 4):
+        raise RtsError(1, "rtsh_combine_visibility_list_ao_bent: a buffer does not fit the frame of the normals")
+    colors = _colors(light_list, colors)
+    rgb = np.zeros((H, W, 3), np.uint8)
+    _check(_lib.rtsh_combine_visibility_list_ao_bent(C.byref(constants), _ref(light_list), _ptr_or_none(colors), _ptr_or_none(positions),
+                                                     _ptr(normals), _ptr_or_none(lights_map), _ptr(visibility), _ptr_or_none(ao),
+                                                     _ptr_or_none(bent), _ref(sky), W, H, _ptr(rgb)),
+           "rtsh_combine_visibility_list_ao_bent")
+    return rgb
+
+
+def combine_visibility_list_ao_bent_device(ctx, constants, light_list, d_positions, d_normals, d_visibility, d_ao, d_bent, sky, width,
+                                           height, d_rgb, d_lights_map=None, colors=None, stream=None):
+    """The visibility combine with ambient occlusion and a sky on the GPU: ``combine_visibility_list_ao_device`` plus d_bent =
+    width*height RGBA32F and ``sky`` (a ``SkyAmbient``, by value); one kernel, asynchronous."""
+    colors = _colors(light_list, colors)
+    _check(_lib.rtsh_combine_visibility_list_ao_bent_device(ctx.handle, C.byref(constants), _ref(light_list), _ptr_or_none(colors),
+                                                            C.c_void_p(d_positions or 0), C.c_void_p(d_normals),
+                                                            C.c_void_p(d_lights_map or 0), C.c_void_p(d_visibility), C.c_void_p(d_ao or 0),
+                                                            C.c_void_p(d_bent or 0), _ref(sky), width, height, C.c_void_p(d_rgb),
+                                                            C.c_void_p(stream or 0)), "rtsh_combine_visibility_list_ao_bent_device")
 
 
 def camera_basis(eye, target, fovy, width, height):

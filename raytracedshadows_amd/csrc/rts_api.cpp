@@ -7,6 +7,7 @@
 #include "rts_soft_distance.h"
 #include "rts_ao.h"
 #include "rts_ao_adaptive.h"
+#include "rts_ao_bent.h"
 #include "rts_light_list.h"
 #include "rts_adaptive.h"
 #include "rts_soft_light_list.h"
@@ -57,6 +58,7 @@ struct rts_ctx {
     uint64_t softListDistanceTraces = 0;              // launches of a soft light list distance kernel (get-only option "soft_list_distance_traces")
     uint64_t aoTraces = 0;                            // launches of an ambient occlusion kernel (get-only option "ao_traces")
     uint64_t aoAdaptiveTraces = 0;                    // launches of an adaptive ambient occlusion kernel (get-only option "ao_adaptive_traces")
+    uint64_t aoBentTraces = 0;                        // launches of a bent-normal ambient occlusion kernel (get-only option "ao_bent_traces")
     uint64_t sparseListTraces = 0;                    // launches of a sparse light list kernel, hard or soft (get-only option "sparse_list_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
@@ -589,6 +591,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "soft_light_list_traces")) { *value = (int)(c->softLightListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "ao_traces")) { *value = (int)(c->aoTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "ao_adaptive_traces")) { *value = (int)(c->aoAdaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "ao_bent_traces")) { *value = (int)(c->aoBentTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "sparse_list_traces")) { *value = (int)(c->sparseListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_list_distance_traces")) { *value = (int)(c->softListDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
@@ -999,11 +1002,15 @@ int rts_trace_soft_distance_stripes_device(rts_ctx* c, const rts_constants* k, c
 // in the light's table (rts_ao.h), so sampleIndex and pixelBase are the mask traces' own.
 // probe == 0: the AO trace itself.  probe != 0: its adaptive form (rts_ao_adaptive.inc), the probe count and the refined plane in the
 // slots rts_ao_adaptive.h names, counted by "ao_adaptive_traces" alone.
+// bent: the bent-normal form (rts_ao_bent.inc): the bent plane in the slot rts_ao_bent.h names, required, the counts optional; counted by
+// "ao_bent_traces" alone.
 static int traceAmbientOcclusionImpl(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* d_positions,
                                      const float* d_normals, const uint8_t* d_active, const Dispatch& g, uint8_t* d_counts, void* stream,
-                                     bool adaptive = false, uint32_t probe = 0, uint8_t* d_refined = nullptr) {
+                                     bool adaptive = false, uint32_t probe = 0, uint8_t* d_refined = nullptr, bool bent = false,
+                                     float* d_bent = nullptr) {
     TraceParams p; uint32_t rows = 0; int s;
-    const bool ownOk = d_counts && d_normals && (adaptive ? rts::aoAdaptiveOk(ao, probe) : rts::aoParamsOk(ao));
+    const bool ownOk = (bent ? d_bent != nullptr : d_counts != nullptr) && d_normals &&
+                       (adaptive ? rts::aoAdaptiveOk(ao, probe) : rts::aoParamsOk(ao));
     if (beginFrame(c, k, d_positions, d_counts, ownOk, g, p, &rows, &s) != Begin::Go) return s;
     rts::setAoNormals(p, d_normals);
     p.activeMap = d_active;
@@ -1017,6 +1024,10 @@ static int traceAmbientOcclusionImpl(rts_ctx* c, const rts_constants* k, const r
         p.nrays = probe;
         rts::setAoRefined(p, d_refined);
         return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::aoAdaptiveTraces, rts::launchAmbientOcclusionAdaptive, stream);
+    }
+    if (bent) {
+        rts::setAoBent(p, d_bent);
+        return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::aoBentTraces, rts::launchAmbientOcclusionBent, stream);
     }
     return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::aoTraces, rts::launchAmbientOcclusion, stream);
 }
@@ -1049,6 +1060,22 @@ int rts_trace_ambient_occlusion_adaptive_stripes_device(rts_ctx* c, const rts_co
     if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
     return traceAmbientOcclusionImpl(c, k, ao, d_positions, d_normals, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe),
                                      d_counts, stream, true, probe, d_refined);
+}
+
+int rts_trace_ambient_occlusion_bent_device(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* d_positions,
+                                            const float* d_normals, const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                            uint32_t row_end, uint8_t* d_counts, float* d_bent, void* stream) {
+    return traceAmbientOcclusionImpl(c, k, ao, d_positions, d_normals, d_active, Dispatch::ofRows(W, H, row_begin, row_end), d_counts, stream,
+                                     false, 0, nullptr, true, d_bent);
+}
+
+int rts_trace_ambient_occlusion_bent_stripes_device(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* d_positions,
+                                                    const float* d_normals, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                                    uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts,
+                                                    float* d_bent, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    return traceAmbientOcclusionImpl(c, k, ao, d_positions, d_normals, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe),
+                                     d_counts, stream, false, 0, nullptr, true, d_bent);
 }
 
 // ---- adaptive soft shadows (include/rts.h): a probe of a few samples per pixel, the others only where the probe disagrees ------------
@@ -1098,7 +1125,7 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 // frame of their own, to the device entry of what is being traced.  StagedRows names what a host entry hands over: the first nine
 // members every entry gives, in this order; the others it sets by name, and what it leaves alone is NULL.
 enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive, SoftListDistance, AmbientOcclusion,
-                    AoAdaptive };
+                    AoAdaptive, AoBent };
 struct StagedRows {
     Staged what;
     const rts_constants* k;
@@ -1115,7 +1142,8 @@ struct StagedRows {
                                          // Staged::AoAdaptive (optional): behind the normals there
     const uint32_t* probes = nullptr;    // Staged::SoftListAdaptive: one per light
     const uint32_t* tables = nullptr;    // ... its jittered form, whose hash pixelBase makes that of the caller's frame
-    const float* normals = nullptr;      // Staged::AmbientOcclusion, Staged::AoAdaptive: staged in the distances' buffer
+    const float* normals = nullptr;      // Staged::AmbientOcclusion, Staged::AoAdaptive, Staged::AoBent: staged in the distances' buffer
+    float* bent = nullptr;               // Staged::AoBent: W x H RGBA32F, behind the normals there (its counts, `mask`, are optional)
 };
 static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
@@ -1129,7 +1157,7 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     const size_t distPlanes = r.what == Staged::SoftListDistance ? planes : 1u;
     if (s == RTS_OK && r.distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4 * distPlanes);
     if (s == RTS_OK && r.refined) s = ensure(&c->d_dist, &c->distBytes, pixels);
-    if (s == RTS_OK && r.normals) s = ensure(&c->d_dist, &c->distBytes, pixels * 16 + (r.refined ? pixels : 0u));
+    if (s == RTS_OK && r.normals) s = ensure(&c->d_dist, &c->distBytes, pixels * 16 + (r.refined ? pixels : 0u) + (r.bent ? pixels * 16 : 0u));
     if (s == RTS_OK && r.mask) s = ensure(&c->d_out, &c->outBytes, pixels * planes);
     if (s == RTS_OK && r.active) s = ensure(&c->d_act, &c->actBytes, pixels);
     if (s != RTS_OK) return s;
@@ -1144,6 +1172,7 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     uint8_t* d_refined = r.refined ? (uint8_t*)c->d_dist + (r.normals ? pixels * 16 : 0u) : nullptr;
     const float* d_in = (const float*)c->d_in;
     float* d_dist = (float*)c->d_dist;
+    float* d_bent = r.bent ? d_dist + pixels * 4 : nullptr;
     // per-pixel jitter hashes the pixel's index in the caller's frame (sampleIndex, rts_kernels.hip: the one reader, and only of a
     // light with a table -- several samples, so in a mask trace or a soft distance trace; of the lists the jittered one alone reads it)
     c->pixelBase = r.rowBegin * W;
@@ -1171,12 +1200,16 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     case Staged::AoAdaptive:
         s = rts_trace_ambient_occlusion_adaptive_device(c, k, (const rts_ao_params*)r.lights, d_in, d_dist, d_active, W, rows, 0, rows,
                                                         r.probe, d_mask, d_refined, nullptr); break;
+    case Staged::AoBent:
+        s = rts_trace_ambient_occlusion_bent_device(c, k, (const rts_ao_params*)r.lights, d_in, d_dist, d_active, W, rows, 0, rows, d_mask,
+                                                    d_bent, nullptr); break;
     }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
     for (size_t l = 0; r.distance && l < distPlanes; ++l)
         RTS_HIP(hipMemcpy(r.distance + l * frame + first, (const float*)c->d_dist + l * pixels, pixels * 4, hipMemcpyDeviceToHost));
     if (r.refined) RTS_HIP(hipMemcpy(r.refined + first, d_refined, pixels, hipMemcpyDeviceToHost));
+    if (r.bent) RTS_HIP(hipMemcpy(r.bent + first * 4, d_bent, pixels * 16, hipMemcpyDeviceToHost));
     for (size_t l = 0; r.mask && l < planes; ++l)
         RTS_HIP(hipMemcpy(r.mask + l * frame + first, (const uint8_t*)c->d_out + l * pixels, pixels, hipMemcpyDeviceToHost));
     return RTS_OK;
@@ -1234,6 +1267,16 @@ int rts_trace_ambient_occlusion_adaptive(rts_ctx* c, const rts_constants* k, con
     if (!rts::aoAdaptiveOk(ao, probe) || (uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;
     StagedRows r{ Staged::AoAdaptive, k, ao, positions, active, W, H, row_begin, row_end };
     r.mask = counts; r.normals = normals; r.probe = probe; r.refined = refined;
+    return traceStagedRows(c, r);
+}
+
+int rts_trace_ambient_occlusion_bent(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* positions,
+                                     const float* normals, const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin,
+                                     uint32_t row_end, uint8_t* counts, float* bent) {
+    if (!c || !k || !positions || !normals || !bent || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::aoParamsOk(ao) || (uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;
+    StagedRows r{ Staged::AoBent, k, ao, positions, active, W, H, row_begin, row_end };
+    r.mask = counts; r.normals = normals; r.bent = bent;
     return traceStagedRows(c, r);
 }
 

@@ -254,12 +254,15 @@ RTS_HD void combineListPixel(const CombineList& f, const float* position4, const
 // over the quotients of an R = 0 filter it gives combineListPixel's bytes.
 // ambientOf(ambient): the ambient term as it enters the sum -- itself, or times the pixel's ambient occlusion (rtsh_combine_visibility_
 // list_ao: ONE rounded multiply, asked for on non-background pixels only).
-template <class VisibilityOf, class AmbientOf>
-RTS_HD void combineVisibilityPixel(const CombineList& f, const float* position4, const float* normal4, uint32_t bits,
-                                   VisibilityOf visibilityOf, AmbientOf ambientOf, uint8_t* rgb3) {
+// ambient3Of(ambient, out3): the PER-CHANNEL form of the same -- the ambient term of each channel as it enters that channel's sum
+// (rtsh_combine_visibility_list_ao_bent: the sky tint); the one-value forms hand every channel the same float.
+template <class VisibilityOf, class Ambient3Of>
+RTS_HD void combineVisibilityPixelRgb(const CombineList& f, const float* position4, const float* normal4, uint32_t bits,
+                                      VisibilityOf visibilityOf, Ambient3Of ambient3Of, uint8_t* rgb3) {
     V3 n{ normal4[0], normal4[1], normal4[2] };
     if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) { rgb3[0] = rgb3[1] = rgb3[2] = 0; return; }
-    const float ambient = ambientOf(combineAmbient(clamp0(viewNdv(f.light[0], n))));
+    float ambient[3];
+    ambient3Of(combineAmbient(clamp0(viewNdv(f.light[0], n))), ambient);
     float sum[3] = { 0.0f, 0.0f, 0.0f };
 #if defined(__HIPCC__)
 #pragma unroll
@@ -270,7 +273,13 @@ RTS_HD void combineVisibilityPixel(const CombineList& f, const float* position4,
         const float direct = 1.25f * clamp0(facingNdl(f.light[l], position4, n)) * visibilityOf(l);
         for (int c = 0; c < 3; ++c) sum[c] = sum[c] + direct * f.color[l][c];
     }
-    for (int c = 0; c < 3; ++c) rgb3[c] = combineByte(sum[c] + ambient);
+    for (int c = 0; c < 3; ++c) rgb3[c] = combineByte(sum[c] + ambient[c]);
+}
+template <class VisibilityOf, class AmbientOf>
+RTS_HD void combineVisibilityPixel(const CombineList& f, const float* position4, const float* normal4, uint32_t bits,
+                                   VisibilityOf visibilityOf, AmbientOf ambientOf, uint8_t* rgb3) {
+    combineVisibilityPixelRgb(f, position4, normal4, bits, visibilityOf,
+                              [&](float ambient, float* out3) { out3[0] = out3[1] = out3[2] = ambientOf(ambient); }, rgb3);
 }
 template <class VisibilityOf>
 RTS_HD void combineVisibilityPixel(const CombineList& f, const float* position4, const float* normal4, uint32_t bits,
@@ -1256,6 +1265,48 @@ RTS_HD V3 aoAim(V3 cam, V3 rel, V3 N, const AoFrame& f, const float* s, float ra
                   ((f.T.z * s[0]) + (f.B.z * s[1])) + (N.z * s[2]) };
     const V3 o0{ cam.x + rel.x, cam.y + rel.y, cam.z + rel.z };
     return V3{ o0.x + (radius * dir.x), o0.y + (radius * dir.y), o0.z + (radius * dir.z) };
+}
+
+// BENT NORMALS (include/rts.h, rts_trace_ambient_occlusion_bent*): the sum of the unoccluded samples' directions, taken over INTEGERS.
+// aoQuantise is Q of the header -- a tangent-space component in 1/16384ths, a function of the table entry alone --; the kernels and the
+// host twin add these integers per pixel (associative: no deal over waves and no order changes the sum) and aoBent applies the pixel's
+// frame to the finished sum ONCE, in float, parenthesised as in the header.  |S.c| <= 48 * 16384 < 2^24, so both (float)S.c and the
+// scale by 2^-14 are exact.  Shared by the host twin (rts_scene.cpp) and the kernels (rts_ao_bent.inc).
+RTS_HD int32_t aoQuantise(float v) {
+    if (v != v) return 0;
+    const float c = v < -1.0f ? -1.0f : (v > 1.0f ? 1.0f : v);
+    return (int32_t)__builtin_rintf(c * 16384.0f);                       // (exact product; ties to even)
+}
+// bent4 = (frame * (S * 2^-14), (float)count) for the normal N of an active, non-background pixel
+RTS_HD void aoBent(V3 N, int32_t sx, int32_t sy, int32_t sz, uint32_t count, float* bent4) {
+    const AoFrame f = aoFrame(N);
+    const float fx = (float)sx * 0x1p-14f, fy = (float)sy * 0x1p-14f, fz = (float)sz * 0x1p-14f;
+    bent4[0] = ((f.T.x * fx) + (f.B.x * fy)) + (N.x * fz);
+    bent4[1] = ((f.T.y * fx) + (f.B.y * fy)) + (N.y * fz);
+    bent4[2] = ((f.T.z * fx) + (f.B.z * fy)) + (N.z * fz);
+    bent4[3] = (float)count;
+}
+
+// THE HEMISPHERIC SKY TINT of the bent combine (include/rts_scene.h, rtsh_combine_visibility_list_ao_bent): where the bent vector
+// points along `up` the ambient term takes the sky's colour, against it the ground's.  up3, sky3, ground3: rtsh_sky_ambient's members.
+// Every operation is one rounded float operation in the written order; the clamp sends a NaN to 0.
+RTS_HD void skyTint(const float* up3, const float* sky3, const float* ground3, const float* bent4, float* tint3) {
+    const float bx = bent4[0], by = bent4[1], bz = bent4[2];
+    const float l2 = ((bx * bx) + (by * by)) + (bz * bz);
+    const float len = __builtin_sqrtf(l2);
+    float u = 0.0f;
+    if (len > 0.0f && len < __builtin_inff()) u = (((bx * up3[0]) + (by * up3[1])) + (bz * up3[2])) / len;
+    float h = 0.5f + 0.5f * u;
+    h = (h > 0.0f) ? ((h < 1.0f) ? h : 1.0f) : 0.0f;
+    for (int c = 0; c < 3; ++c) tint3[c] = ground3[c] + (sky3[c] - ground3[c]) * h;
+}
+// The ambient terms of the bent combine, per channel: (ambient * ao) * tint_c -- what combineVisibilityPixelRgb's ambient3Of hands back,
+// on the host and in the kernel.  sky9 = { up, sky, ground }, rtsh_sky_ambient's first nine floats.
+RTS_HD void skyAmbient3(float ambient, float ao, const float* sky9, const float* bent4, float* out3) {
+    float tint[3];
+    skyTint(sky9, sky9 + 3, sky9 + 6, bent4, tint);
+    const float scaled = ambient * ao;
+    for (int c = 0; c < 3; ++c) out3[c] = scaled * tint[c];
 }
 
 } // namespace rts_harness

@@ -302,3 +302,5 @@ hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
 #include "rts_ao.inc"
 // adaptive ambient occlusion: a probe of a few AO samples, the others only where it disagrees (its launch is declared in rts_ao_adaptive.h)
 #include "rts_ao_adaptive.inc"
+// bent normals: the AO trace with the integer sum of its unoccluded directions beside the count (its launch is declared in rts_ao_bent.h)
+#include "rts_ao_bent.inc"

@@ -199,7 +199,46 @@ __global__ __launch_bounds__(256) void combineVisibilityAoKernel(CombineList f, 
                            [&](float ambient) { return ambient * ao[i]; }, q);
     rgb[i * 3] = q[0]; rgb[i * 3 + 1] = q[1]; rgb[i * 3 + 2] = q[2];
 }
+
+// The same again with the hemispheric sky tint on the ambient term, aimed by the pixel's bent vector (rtsh_combine_visibility_list_ao_
+// bent_device): a third kernel, so that the two above keep their text.  The sky's nine floats travel by value.
+struct SkyAmbient9 { float v[9]; };
+__global__ __launch_bounds__(256) void combineVisibilityAoBentKernel(CombineList f, SkyAmbient9 sky, const float* positions,
+                                                                     const float* normals, const uint8_t* lightsMap, const float* visibility,
+                                                                     const float* ao, const float* bent, uint64_t n, uint8_t* rgb) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float zero[4] = { 0.f, 0.f, 0.f, 0.f };
+    const float* n4 = normals + i * 4;
+    const float nx = n4[0], ny = n4[1], nz = n4[2];
+    const float nrm[4] = { nx, ny, nz, 0.f };
+    const bool background = nx == 0.0f && ny == 0.0f && nz == 0.0f;        // (neither its map byte, its ao nor its bent texel is read)
+    const uint32_t bits = (lightsMap && !background) ? lightsMap[i] : 0xFFu;
+    uint8_t q[3];
+    combineVisibilityPixelRgb(f, positions ? positions + i * 4 : zero, nrm, bits, [&](uint32_t l) { return visibility[(uint64_t)l * n + i]; },
+                              [&](float ambient, float* out3) {
+                                  const float* b4 = bent + i * 4;
+                                  const float b[4] = { b4[0], b4[1], b4[2], 0.f };
+                                  skyAmbient3(ambient, ao[i], sky.v, b, out3);
+                              }, q);
+    rgb[i * 3] = q[0]; rgb[i * 3 + 1] = q[1]; rgb[i * 3 + 2] = q[2];
+}
 } // namespace rts_harness
+
+extern "C" int rtsh_combine_visibility_list_ao_bent_device(rts_ctx* ctx, const rts_constants* k, const rts_light_list* list, const float* colors,
+                                                           const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,
+                                                           const float* d_visibility, const float* d_ao, const float* d_bent,
+                                                           const rtsh_sky_ambient* sky, uint32_t W, uint32_t H, uint8_t* d_rgb, void* stream) {
+    if (!ctx || !k || !d_normals || !d_visibility || !d_ao || !d_bent || !sky || !d_rgb || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    rts_harness::CombineList f;
+    const int s = rts_harness::makeCombineList(k, list, colors, d_positions != nullptr, &f);
+    if (s != RTS_OK) return s;
+    rts_harness::SkyAmbient9 sky9;
+    memcpy(sky9.v, sky, sizeof(sky9.v));                                   // { up, sky, ground }
+    const uint64_t n = (uint64_t)W * H;
+    return rts_harness::launchPerPixel(ctx, stream, n, rts_harness::combineVisibilityAoBentKernel, f, sky9, d_positions, d_normals, d_lights_map,
+                                       d_visibility, d_ao, d_bent, n, d_rgb);
+}
 
 extern "C" int rtsh_combine_visibility_list_ao_device(rts_ctx* ctx, const rts_constants* k, const rts_light_list* list, const float* colors,
                                                       const float* d_positions, const float* d_normals, const uint8_t* d_lights_map,

@@ -432,6 +432,37 @@ extern "C" int rtsh_ambient_occlusion_adaptive(const rts_vec4u* packed, size_t c
     return RTS_OK;
 }
 
+// ---- bent normals on the host (include/rts_scene.h): the checker of rts_trace_ambient_occlusion_bent* ----
+// rtsh_ambient_occlusion's loop with the integer sum beside the count: aoQuantise of the sample's table entry where its ray is free,
+// aoBent on the finished sum (rts_closest_hit.h: the kernels' own source).
+extern "C" int rtsh_ambient_occlusion_bent(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_ao_params* ao,
+                                           const float* positions, const float* normals, const uint8_t* active, uint32_t W, uint32_t H,
+                                           uint32_t row_begin, uint32_t row_end, uint8_t* counts, float* bent, int threads) {
+    if (!packed || !k || !positions || !normals || !bent || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::aoParamsOk(ao)) return RTS_ERR_INVALID_ARG;
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t n = ao->nsamples > 1 ? ao->nsamples : 1u;
+    const size_t first = (size_t)row_begin * W;
+    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t at) {
+        const size_t i = first + at;
+        int32_t S[3] = { 0, 0, 0 };
+        uint32_t lit = 0;
+        const bool live = aoPixelRays(k, ao, n, positions, normals, active, i, [&](uint32_t j, const DRay& r) {
+            if (rayDistanceBits(bvh, r) != 0x7F800000u) return;         // u_j == 0
+            const float* d = ao->dirs[sampleIndex(ao->table, j, (uint32_t)i)];
+            for (int c = 0; c < 3; ++c) S[c] += aoQuantise(d[c]);
+            ++lit;
+        });
+        float* b = bent + i * 4;
+        if (live) aoBent(V3{ normals[i * 4], normals[i * 4 + 1], normals[i * 4 + 2] }, S[0], S[1], S[2], lit, b);
+        else b[0] = b[1] = b[2] = b[3] = 0.0f;
+        if (counts) counts[i] = (uint8_t)lit;
+    });
+    return RTS_OK;
+}
+
 // ---- adaptive soft shadows on the host (include/rts_scene.h): the checker of rts_trace_shadow_mask_adaptive* ----
 // The definition of include/rts.h applied literally, one straight loop over (pixel, sample) on frameDistance's walk: the probe's
 // samples, then the others only where the probe disagrees.
@@ -824,6 +855,24 @@ extern "C" int rtsh_combine_visibility_list_ao(const rts_constants* k, const rts
     combineFrame(positions, normals, lights_map, n, [&](size_t i, const float* p4, const float* n4, uint32_t bits) {
         combineVisibilityPixel(f, p4, n4, bits, [&](uint32_t l) { return visibility[(size_t)l * n + i]; },
                                [&](float ambient) { return ambient * ao[i]; }, rgb + i * 3);
+    });
+    return RTS_OK;
+}
+
+extern "C" int rtsh_combine_visibility_list_ao_bent(const rts_constants* k, const rts_light_list* list, const float* colors,
+                                                    const float* positions, const float* normals, const uint8_t* lights_map,
+                                                    const float* visibility, const float* ao, const float* bent, const rtsh_sky_ambient* sky,
+                                                    uint32_t W, uint32_t H, uint8_t* rgb) {
+    if (!k || !normals || !visibility || !ao || !bent || !sky || !rgb || W == 0 || H == 0) return RTS_ERR_INVALID_ARG;
+    CombineList f;
+    const int s = makeCombineList(k, list, colors, positions != nullptr, &f);
+    if (s != RTS_OK) return s;
+    float sky9[9];
+    memcpy(sky9, sky, sizeof(sky9));                                       // { up, sky, ground }
+    const size_t n = (size_t)W * H;
+    combineFrame(positions, normals, lights_map, n, [&](size_t i, const float* p4, const float* n4, uint32_t bits) {
+        combineVisibilityPixelRgb(f, p4, n4, bits, [&](uint32_t l) { return visibility[(size_t)l * n + i]; },
+                                  [&](float ambient, float* out3) { skyAmbient3(ambient, ao[i], sky9, bent + i * 4, out3); }, rgb + i * 3);
     });
     return RTS_OK;
 }

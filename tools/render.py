@@ -135,6 +135,15 @@ def parse_ao(text, wl):
 
 
 AO_ADAPTIVE = {"probe": 0, "refined_out": ""}           # --ao-adaptive K [--ao-refined FILE.ppm], set by main()
+AO_BENT = {"on": False, "sky": None, "out": "", "d_bent": None}   # --ao-bent [--sky --ground --up --bent-out], set by main()
+
+
+def ao_combine(ctx, api, constants, hard_list, d_pos, d_nrm, d_vis, d_ao, W, H, d_rgb, **kw):
+    """The combine with ambient occlusion; with --ao-bent the one that tints the ambient term by the bent plane ambient_plane traced."""
+    if AO_BENT["on"]:
+        return api.combine_visibility_list_ao_bent_device(ctx, constants, hard_list, d_pos, d_nrm, d_vis, d_ao, AO_BENT["d_bent"],
+                                                          AO_BENT["sky"], W, H, d_rgb, **kw)
+    return api.combine_visibility_list_ao_device(ctx, constants, hard_list, d_pos, d_nrm, d_vis, d_ao, W, H, d_rgb, **kw)
 
 
 def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
@@ -156,6 +165,18 @@ def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
             os.makedirs(os.path.dirname(os.path.abspath(AO_ADAPTIVE["refined_out"])), exist_ok=True)
             api.write_ppm(AO_ADAPTIVE["refined_out"], np.repeat((refined * 255).astype(np.uint8)[..., None], 3, axis=2))
             print(f"wrote {AO_ADAPTIVE['refined_out']}")
+    elif AO_BENT["on"]:                                  # the same counts, and the bent plane beside them
+        AO_BENT["d_bent"] = ctx.malloc(W * H * 16)
+        ctx.trace_ambient_occlusion_bent_device(wl.constants, ao, d_pos, d_nrm, W, H, d_counts, AO_BENT["d_bent"])
+        ctx.synchronize()
+        if AO_BENT["out"]:
+            bent = np.zeros((H, W, 4), np.float32)
+            ctx.d2h(bent, AO_BENT["d_bent"])
+            length = np.linalg.norm(bent[..., :3], axis=-1, keepdims=True)
+            unit = np.divide(bent[..., :3], length, out=np.zeros((H, W, 3), np.float32), where=length > 0)
+            os.makedirs(os.path.dirname(os.path.abspath(AO_BENT["out"])), exist_ok=True)
+            api.write_ppm(AO_BENT["out"], (np.clip(0.5 + 0.5 * unit, 0, 1) * 255).astype(np.uint8))
+            print(f"wrote {AO_BENT['out']}: 0.5 + 0.5 * unit(bent)")
     else:
         ctx.trace_ambient_occlusion_device(wl.constants, ao, d_pos, d_nrm, W, H, d_counts)
         ctx.synchronize()
@@ -227,7 +248,7 @@ def soft_list(ctx, wl, W, H, count, spp, out, probe=0, refined_out="", table=0, 
         d_scratch = ctx.malloc(wide_scratch_bytes(api, filt, count, W, H)) if wide and filt.passes >= 2 else None
         list_filter(ctx, api, lights, filt, d_pos, d_nrm, d_counts, W, H, d_vis, d_map, d_dist, d_scratch)
         if d_ao:
-            api.combine_visibility_list_ao_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, d_vis, d_ao, W, H, d_rgb,
+            ao_combine(ctx, api, wl.constants, lights.hard_list(), d_pos, d_nrm, d_vis, d_ao, W, H, d_rgb,
                                                   d_lights_map=d_map, colors=colors)
         else:
             api.combine_visibility_list_device(ctx, wl.constants, lights.hard_list(), d_pos, d_nrm, d_vis, W, H, d_rgb, d_lights_map=d_map,
@@ -503,6 +524,13 @@ def main():
                     help="with --ao N: trace K probe segments per pixel and the other N - K only where the probe disagrees "
                          "(rts_trace_ambient_occlusion_adaptive_device), 1 <= K < N; the plane goes the same way")
     ap.add_argument("--ao-refined", default="", metavar="FILE.ppm", help="with --ao-adaptive: also write the refined plane as an image")
+    ap.add_argument("--ao-bent", action="store_true",
+                    help="with --ao N: trace the bent normals beside the counts (rts_trace_ambient_occlusion_bent_device) and tint the "
+                         "ambient term between --ground and --sky by where they point (rtsh_combine_visibility_list_ao_bent_device)")
+    ap.add_argument("--sky", default="0.55,0.7,1.0", metavar="r,g,b", help="with --ao-bent: the ambient colour towards --up")
+    ap.add_argument("--ground", default="0.45,0.35,0.25", metavar="r,g,b", help="with --ao-bent: the ambient colour against --up")
+    ap.add_argument("--up", default="0,1,0", metavar="x,y,z", help="with --ao-bent: the direction of the sky (normalised here)")
+    ap.add_argument("--bent-out", default="", metavar="FILE.ppm", help="with --ao-bent: also write 0.5 + 0.5 * unit(bent) as an image")
     args = ap.parse_args()
     from raytracedshadows_amd import api, workloads
     scene, W, H, light, spp = workloads.CONFIGS[args.config]
@@ -521,6 +549,19 @@ def main():
         if args.ao_adaptive and not 1 <= args.ao_adaptive < ao.samples:
             sys.exit("render: --ao-adaptive K takes 1 <= K < N")
         AO_ADAPTIVE.update(probe=args.ao_adaptive, refined_out=args.ao_refined)
+        if (args.ao_bent or args.bent_out) and ao is None:
+            sys.exit("render: --ao-bent and --bent-out go with --ao")
+        if args.bent_out and not args.ao_bent:
+            sys.exit("render: --bent-out goes with --ao-bent")
+        if args.ao_bent and args.ao_adaptive:
+            sys.exit("render: --ao-bent does not go with --ao-adaptive (a unanimous pixel has no traced sum)")
+        if args.ao_bent:
+            try:
+                sky, ground, up = ([float(v) for v in t.split(",")] for t in (args.sky, args.ground, args.up))
+                assert len(sky) == len(ground) == len(up) == 3 and np.linalg.norm(up) > 0
+            except (ValueError, AssertionError):
+                sys.exit("render: --sky, --ground and --up take three numbers r,g,b / x,y,z (up not zero)")
+            AO_BENT.update(on=True, out=args.bent_out, sky=api.SkyAmbient.make(up=np.asarray(up) / np.linalg.norm(up), sky=sky, ground=ground))
         if ao is not None and args.temporal:
             sys.exit("render: --ao does not go with --temporal")
         if args.soft_list:
@@ -645,7 +686,7 @@ def main():
             as_list = api.SoftLightList.make([(one.type, list(one.xyz), n, 0, 0.0)])
             d_vis = ctx.malloc(W * H * 4)
             api.filter_soft_light_list_device(ctx, as_list, api.FilterParams.make(0, 0.9, 0.05), d_pos, d_nrm, d_mask, W, H, d_vis)
-            api.combine_visibility_list_ao_device(ctx, wl.constants, as_list.hard_list(), d_pos, d_nrm, d_vis, d_ao, W, H, d_rgb,
+            ao_combine(ctx, api, wl.constants, as_list.hard_list(), d_pos, d_nrm, d_vis, d_ao, W, H, d_rgb,
                                                   colors=None)
         else:
             api.combine_device(ctx, wl.constants, wl.light, d_pos, d_nrm, d_mask, W, H, d_rgb)     # the frame stays on the device
