@@ -515,6 +515,59 @@ int rts_trace_ambient_occlusion_bent_stripes_device(rts_ctx* ctx, const rts_cons
                                                     uint32_t W, uint32_t H, uint32_t band_rows, uint32_t n_stripes, uint32_t stripe,
                                                     uint8_t* d_counts, float* d_bent, void* stream);
 
+/* AO DISTANCE AND FALLOFF: the AO trace with the NEAREST BLOCKER over the hemisphere and a WEIGHTED obscurance beside the count -- a
+ * blocker at 99 % of the radius no longer darkens a pixel as much as one at 1 %, and the hit distance is there for the denoiser and
+ * for contact darkening.  The rays, the frame, idx(p, j) and INACTIVE are word for word those of AMBIENT OCCLUSION
+ * above.  For pixel p of the rows the call owns, n = max(1, ao->nsamples):
+ *   d_j   = the OCCLUDER DISTANCE of sample j's ray as defined above: the walk does not return at a hit; the smallest accepted t as a
+ *           bit pattern >= +0, +Inf if there is none.  The ray is the point light's segment, so t is the fraction of the segment from
+ *           the surface (0) to L (1);
+ *   u_j   = (d_j == +Inf);   c = sum u_j;   counts[p] = c, byte for byte the plane of rts_trace_ambient_occlusion*;
+ *   distance[p] = min_j d_j, an integer minimum of bit patterns as in SOFT-SHADOW OCCLUDER DISTANCE; +Inf exactly where c == n;
+ *   b_j   = min(63u, (uint32_t)(min(d_j, 1.0f) * 64.0f)) for a blocked sample: the product is exact, the conversion truncates;
+ *   a_j   = 255 where u_j, else falloff->weight[b_j]: weight[b] says how OPEN a sample counts whose nearest blocker lies in the b-th
+ *           64th of the segment -- 0 a full occluder, 255 no occlusion.  A falloff rises with b, but any bytes are legal;
+ *   A     = sum a_j, an integer <= 48 * 255;   S = 65535 / n by integer division (the wide filter's S_l, rts_scene.h);
+ *   obscurance[p] = (2 * A * S + 255) / 510, an integer quotient: the intermediate stays below 2^26, the value never exceeds n * S.
+ *   INACTIVE: counts[p] = 0, distance[p] = +0.0f, obscurance[p] = 0, and the position is never read.  Rows outside the range / stripe
+ *   are not touched in any plane.
+ * Every quantity that crosses samples is an integer sum or an integer minimum of functions of (pixel, sample) alone -- a weighted sum of
+ * float distances would have no order-free definition; a sum of integer weights looked up from a QUANTISED distance
+ * has one --, so no byte depends on the kernel family, on "soft_split", on the order of the samples or on any option.
+ * ANCHORS: (1) counts is the AO trace's plane, and distance is finite exactly where counts < n.  (2) weight all 0: obscurance ==
+ * counts * S, the wide filter's V_0 of the count plane.  (3) weight all 255: obscurance == n * S at every active pixel.
+ * (4) obscurance >= counts * S always, and raising any weight[b] never lowers any pixel.  (5) n == 1: distance is bit for bit what
+ * rts_trace_shadow_distance* gives at that pixel for the hard point light at L.
+ * DOWNSTREAM: obscurance IS a plane in the wide filter's fixed point: it goes into rtsh_wide_filter_mean_soft_light_list* as `mean`
+ * under a one-entry rts_soft_light_list of n samples without a conversion pass; passes == 0 gives the float plane V / (n S) that
+ * rtsh_combine_visibility_list_ao* and rtsh_accumulate_visibility_list* take.  Nothing downstream changes.
+ * counts, distance (W x H floats) and obscurance (W x H uint16_t) may each be NULL, but at least one of distance and obscurance is
+ * given; falloff may be NULL only when obscurance is (it is not read then).
+ *   * RTS_ERR_INVALID_ARG, nothing written, no counter moved: everything rts_trace_ambient_occlusion* refuses except NULL counts; both
+ *     outputs NULL; obscurance without falloff; an obscurance pointer that is not 2-byte aligned; a distance pointer that is not
+ *     4-byte aligned.
+ *   * families, "soft_split", bands, stripes and the ignored options are rts_trace_ambient_occlusion*'s; under graph capture a call is
+ *     ONE kernel node, `ao`, `falloff`, constants and options by value; the four waves of a tile join their integer words in LDS.
+ *   * get-only option "ao_distance_traces": launches so far (no other counter moves); rts_ctx_last_kernel_name then names
+ *     "ambientOcclusionDistanceShareKernel" or "ambientOcclusionDistancePacketKernel<S,geom>", S and geom as for
+ *     "ambientOcclusionPacketKernel".
+ * A distance walk never stops at its first hit: where neither plane is wanted, stay with rts_trace_ambient_occlusion*.
+ * rtsh_ambient_occlusion_distance (rts_scene.h) is the host twin. */
+typedef struct rts_ao_falloff { uint8_t weight[64]; } rts_ao_falloff;   /* 64 bytes */
+int rts_trace_ambient_occlusion_distance(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao,
+                                         const rts_ao_falloff* falloff, const float* positions, const float* normals,
+                                         const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                         uint8_t* counts, float* distance, uint16_t* obscurance);
+int rts_trace_ambient_occlusion_distance_device(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao,
+                                                const rts_ao_falloff* falloff, const float* d_positions, const float* d_normals,
+                                                const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                                uint8_t* d_counts, float* d_distance, uint16_t* d_obscurance, void* stream);
+int rts_trace_ambient_occlusion_distance_stripes_device(rts_ctx* ctx, const rts_constants* constants, const rts_ao_params* ao,
+                                                        const rts_ao_falloff* falloff, const float* d_positions,
+                                                        const float* d_normals, const uint8_t* d_active, uint32_t W, uint32_t H,
+                                                        uint32_t band_rows, uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts,
+                                                        float* d_distance, uint16_t* d_obscurance, void* stream);
+
 /* LIGHT LISTS: up to 8 hard lights in ONE dispatch, one bit per light in the mask byte -- one read of the G-buffer texel, one launch and
  * one mask plane for all of a frame's shadow-casting lights.  For pixel p of the rows the call owns and l < list->count:
  *   mask[p] bit l = (lights_map == NULL || (lights_map[p] >> l) & 1)

@@ -136,6 +136,17 @@ int rtsh_ambient_occlusion_bent(const rts_vec4u* packed, size_t count_vec4, cons
                                 const float* positions, const float* normals, const uint8_t* active, uint32_t W, uint32_t H,
                                 uint32_t row_begin, uint32_t row_end, uint8_t* counts, float* bent, int threads);
 
+/* AO DISTANCE AND FALLOFF on the host: the definition of rts_trace_ambient_occlusion_distance* (include/rts.h) applied literally, one
+ * straight loop over (pixel, sample) on rtsh_ambient_occlusion's walk and set-up -- the one-ray distance of every sample, their integer
+ * minimum, the count of the free ones and the integer sum of the falloff's weights; bin, weight and quotient are the kernels' own
+ * source.  counts, distance and obscurance (each nullable, distance or obscurance given) as defined there.  Background and inactive
+ * pixels: 0, +0.0f and 0, positions never read; rows outside [row_begin, row_end) are not touched.  The refusals are
+ * rts_trace_ambient_occlusion_distance's.  Runs without a GPU, multi-threaded: the checker of the device forms, bit for bit. */
+int rtsh_ambient_occlusion_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* constants, const rts_ao_params* ao,
+                                    const rts_ao_falloff* falloff, const float* positions, const float* normals, const uint8_t* active,
+                                    uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* counts, float* distance,
+                                    uint16_t* obscurance, int threads);
+
 /* ADAPTIVE SOFT SHADOWS on the host: the definition of rts_trace_shadow_mask_adaptive* (include/rts.h) applied literally, one straight
  * loop over (pixel, sample) on rtsh_soft_distance's walk and ray set-up -- the first `probe` samples; where they agree, 0 or nsamples;
  * where they disagree, the remaining samples and the full count.  mask[p] as defined there, refined[p] (nullable) = 1 exactly where the

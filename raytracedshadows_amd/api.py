@@ -233,6 +233,46 @@ class AoParams(C.Structure):
         return SoftLightList.make([(Light.POINT, (0.0, 0.0, 0.0), self.samples, 0, 0.0)])
 
 
+class AoFalloff(C.Structure):
+    """``rts_ao_falloff``: the falloff of ``trace_ambient_occlusion_distance`` -- ``weight[b]`` says how open (0: a full occluder,
+    255: no occlusion) a sample counts whose nearest blocker lies in the b-th 64th of its segment."""
+    _fields_ = [("weight", C.c_uint8 * 64)]
+
+    @classmethod
+    def make(cls, curve):
+        """``curve``: a callable on [0, 1), evaluated at the 64 bin centres ``(b + 0.5) / 64``, clipped to [0, 1] and rounded to
+        0..255; or 64 bytes taken as they are."""
+        if callable(curve):
+            w = np.rint(np.clip([float(curve((b + 0.5) / 64.0)) for b in range(64)], 0.0, 1.0) * 255.0)
+        else:
+            w = np.asarray(curve)
+            if w.shape != (64,) or (w < 0).any() or (w > 255).any():
+                raise RtsError(1, "AoFalloff.make: a callable, or 64 values in 0..255")
+        f = cls()
+        for b in range(64):
+            f.weight[b] = int(w[b])
+        return f
+
+    @classmethod
+    def zeros(cls):
+        """Every blocker a full occluder: the obscurance is the count times S."""
+        return cls.make(np.zeros(64, np.uint8))
+
+    @classmethod
+    def linear(cls):
+        """Occlusion fades linearly to nothing at the end of the segment."""
+        return cls.make(lambda t: t)
+
+    @classmethod
+    def quadratic(cls):
+        """Occlusion ``(1 - t)^2``: it fades faster than linearly."""
+        return cls.make(lambda t: 1.0 - (1.0 - t) * (1.0 - t))
+
+    def weights(self):
+        """``uint8[64]``, a copy."""
+        return np.ctypeslib.as_array(self.weight).astype(np.uint8).copy()
+
+
 class SkyAmbient(C.Structure):
     """``rtsh_sky_ambient``: the hemispheric sky of ``combine_visibility_list_ao_bent`` -- the ambient light's colour where a pixel's
     bent vector points along ``up`` (``sky``) and against it (``ground``)."""
@@ -483,6 +523,17 @@ _sig("rts_trace_ambient_occlusion_bent_stripes_device", C.c_int, C.c_void_p, C.P
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_ambient_occlusion_bent", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rts_trace_ambient_occlusion_distance", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams), C.POINTER(AoFalloff),
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rts_trace_ambient_occlusion_distance_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams),
+     C.POINTER(AoFalloff), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p)
+_sig("rts_trace_ambient_occlusion_distance_stripes_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(AoParams),
+     C.POINTER(AoFalloff), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_ambient_occlusion_distance", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(RayTracingConstants), C.POINTER(AoParams),
+     C.POINTER(AoFalloff), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_int)
 _sig("rtsh_combine_visibility_list_ao_bent", C.c_int, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SkyAmbient), C.c_uint32, C.c_uint32, C.c_void_p)
 _sig("rtsh_combine_visibility_list_ao_bent_device", C.c_int, C.c_void_p, C.POINTER(RayTracingConstants), C.POINTER(LightList), C.c_void_p,
@@ -1241,6 +1292,50 @@ class ShadowContext:
                                                                     C.c_void_p(d_bent or 0), C.c_void_p(stream or 0)),
                "rts_trace_ambient_occlusion_bent_stripes_device")
 
+    # -- AO distance and falloff (include/rts.h): the AO trace with the nearest blocker and the falloff-weighted obscurance --
+    def trace_ambient_occlusion_distance(self, constants, ao, falloff, positions, normals, width, height, row_begin=0, row_end=None,
+                                         active=None, out=None, distance=None, obscurance=None, want_counts=True, want_distance=True,
+                                         want_obscurance=True):
+        """Host-pointer dispatch; returns ``(uint8[H, W] counts, float32[H, W] distance, uint16[H, W] obscurance)``, each None where
+        its ``want_`` is False: the AO count, the nearest blocker over the pixel's samples as a fraction of the segment (+Inf where
+        every sample is free) and the obscurance in the wide filter's fixed point.  ``out`` / ``distance`` / ``obscurance``: arrays to
+        write into (rows outside the range keep their contents)."""
+        positions, active = _frame_inputs("trace_ambient_occlusion_distance", positions, width, height, active)
+        normals, _ = _frame_inputs("trace_ambient_occlusion_distance (normals)", normals, width, height)
+        row_end = height if row_end is None else row_end
+        counts = out if out is not None else (np.zeros((height, width), dtype=np.uint8) if want_counts else None)
+        if distance is None and want_distance:
+            distance = np.zeros((height, width), dtype=np.float32)
+        if obscurance is None and want_obscurance:
+            obscurance = np.zeros((height, width), dtype=np.uint16)
+        _check(_lib.rts_trace_ambient_occlusion_distance(self._h, C.byref(constants), _ref(ao), _ref(falloff), _ptr(positions),
+                                                         _ptr(normals), _ptr_or_none(active), width, height, row_begin, row_end,
+                                                         _ptr_or_none(counts), _ptr_or_none(distance), _ptr_or_none(obscurance)),
+               "rts_trace_ambient_occlusion_distance")
+        return counts, distance, obscurance
+
+    def trace_ambient_occlusion_distance_device(self, constants, ao, falloff, d_positions, d_normals, width, height, d_counts, d_distance,
+                                                d_obscurance, row_begin=0, row_end=None, stream=None, d_active=None):
+        """Device pointers, asynchronous: d_positions / d_normals = width * height RGBA32F, d_counts (or None) / d_active (or None) =
+        width * height bytes, d_distance (or None) = width * height floats, d_obscurance (or None) = width * height uint16."""
+        row_end = height if row_end is None else row_end
+        _check(_lib.rts_trace_ambient_occlusion_distance_device(self._h, C.byref(constants), _ref(ao), _ref(falloff),
+                                                                C.c_void_p(d_positions or 0), C.c_void_p(d_normals or 0),
+                                                                C.c_void_p(d_active or 0), width, height, row_begin, row_end,
+                                                                C.c_void_p(d_counts or 0), C.c_void_p(d_distance or 0),
+                                                                C.c_void_p(d_obscurance or 0), C.c_void_p(stream or 0)),
+               "rts_trace_ambient_occlusion_distance_device")
+
+    def trace_ambient_occlusion_distance_stripes_device(self, constants, ao, falloff, d_positions, d_normals, width, height, d_counts,
+                                                        d_distance, d_obscurance, band_rows, n_stripes, stripe, stream=None, d_active=None):
+        """One dispatch over the interleaved bands `stripe, stripe + n_stripes, ...` of band_rows rows each."""
+        _check(_lib.rts_trace_ambient_occlusion_distance_stripes_device(self._h, C.byref(constants), _ref(ao), _ref(falloff),
+                                                                        C.c_void_p(d_positions or 0), C.c_void_p(d_normals or 0),
+                                                                        C.c_void_p(d_active or 0), width, height, band_rows, n_stripes,
+                                                                        stripe, C.c_void_p(d_counts or 0), C.c_void_p(d_distance or 0),
+                                                                        C.c_void_p(d_obscurance or 0), C.c_void_p(stream or 0)),
+               "rts_trace_ambient_occlusion_distance_stripes_device")
+
     # -- light lists (include/rts.h): up to 8 hard lights in one dispatch, light l in bit l of the mask byte --
     def trace_light_list(self, constants, lights, positions, width, height, lights_map=None, row_begin=0, row_end=None, out=None):
         """Host-pointer dispatch; returns ``uint8[H, W]``: bit ``l`` = light ``l``'s shadow byte where ``lights_map`` (uint8[H, W], or
@@ -1871,6 +1966,28 @@ def ambient_occlusion_bent(packed, constants, ao, positions, normals, width, hei
                                             _ptr_or_none(active), width, height, row_begin, row_end, _ptr_or_none(counts), _ptr(bent),
                                             threads), "rtsh_ambient_occlusion_bent")
     return counts, bent
+
+
+def ambient_occlusion_distance(packed, constants, ao, falloff, positions, normals, width, height, active=None, row_begin=0, row_end=None,
+                               out=None, distance=None, obscurance=None, threads=0, want_counts=True, want_distance=True,
+                               want_obscurance=True):
+    """AO distance and falloff on the host (rtsh_ambient_occlusion_distance, no GPU): ``(uint8[H, W] counts, float32[H, W] distance,
+    uint16[H, W] obscurance)``, each None where its ``want_`` is False -- what ``ShadowContext.trace_ambient_occlusion_distance``
+    returns, bit for bit."""
+    packed = np.ascontiguousarray(packed, np.uint32).reshape(-1, 4)
+    positions, active = _frame_inputs("ambient_occlusion_distance", positions, width, height, active)
+    normals, _ = _frame_inputs("ambient_occlusion_distance (normals)", normals, width, height)
+    row_end = height if row_end is None else row_end
+    counts = out if out is not None else (np.zeros((height, width), np.uint8) if want_counts else None)
+    if distance is None and want_distance:
+        distance = np.zeros((height, width), np.float32)
+    if obscurance is None and want_obscurance:
+        obscurance = np.zeros((height, width), np.uint16)
+    _check(_lib.rtsh_ambient_occlusion_distance(_ptr(packed), packed.shape[0], C.byref(constants), _ref(ao), _ref(falloff), _ptr(positions),
+                                                _ptr(normals), _ptr_or_none(active), width, height, row_begin, row_end,
+                                                _ptr_or_none(counts), _ptr_or_none(distance), _ptr_or_none(obscurance), threads),
+           "rtsh_ambient_occlusion_distance")
+    return counts, distance, obscurance
 
 
 def ao_rays(constants, ao, positions, normals, width, height, active=None):

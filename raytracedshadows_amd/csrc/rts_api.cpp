@@ -8,6 +8,7 @@
 #include "rts_ao.h"
 #include "rts_ao_adaptive.h"
 #include "rts_ao_bent.h"
+#include "rts_ao_distance.h"
 #include "rts_light_list.h"
 #include "rts_adaptive.h"
 #include "rts_soft_light_list.h"
@@ -59,6 +60,7 @@ struct rts_ctx {
     uint64_t aoTraces = 0;                            // launches of an ambient occlusion kernel (get-only option "ao_traces")
     uint64_t aoAdaptiveTraces = 0;                    // launches of an adaptive ambient occlusion kernel (get-only option "ao_adaptive_traces")
     uint64_t aoBentTraces = 0;                        // launches of a bent-normal ambient occlusion kernel (get-only option "ao_bent_traces")
+    uint64_t aoDistanceTraces = 0;                    // launches of an AO distance kernel (get-only option "ao_distance_traces")
     uint64_t sparseListTraces = 0;                    // launches of a sparse light list kernel, hard or soft (get-only option "sparse_list_traces")
     const char* lastKernel = "";
     int packetBudget = 16;
@@ -592,6 +594,7 @@ int rts_ctx_get_option(rts_ctx* c, const char* key, int* value) {
     if (!strcmp(key, "ao_traces")) { *value = (int)(c->aoTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "ao_adaptive_traces")) { *value = (int)(c->aoAdaptiveTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "ao_bent_traces")) { *value = (int)(c->aoBentTraces & 0x7FFFFFFF); return RTS_OK; }
+    if (!strcmp(key, "ao_distance_traces")) { *value = (int)(c->aoDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "sparse_list_traces")) { *value = (int)(c->sparseListTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "soft_list_distance_traces")) { *value = (int)(c->softListDistanceTraces & 0x7FFFFFFF); return RTS_OK; }
     if (!strcmp(key, "tile_order")) { *value = c->useTileOrder; return RTS_OK; }
@@ -1004,12 +1007,19 @@ int rts_trace_soft_distance_stripes_device(rts_ctx* c, const rts_constants* k, c
 // slots rts_ao_adaptive.h names, counted by "ao_adaptive_traces" alone.
 // bent: the bent-normal form (rts_ao_bent.inc): the bent plane in the slot rts_ao_bent.h names, required, the counts optional; counted by
 // "ao_bent_traces" alone.
+// dist: the distance form (rts_ao_distance.inc): the distance plane, the obscurance plane and the falloff's weights in the slots
+// rts_ao_distance.h names, one of the two planes required, the counts optional; counted by "ao_distance_traces" alone.
+struct AoDistanceOut { float* d_distance; uint16_t* d_obscurance; const rts_ao_falloff* falloff; };
+static bool aoDistanceOutOk(const AoDistanceOut& o) {
+    return (o.d_distance || o.d_obscurance) && (!o.d_obscurance || o.falloff) && ((uintptr_t)o.d_obscurance & 1u) == 0 &&
+           ((uintptr_t)o.d_distance & 3u) == 0;
+}
 static int traceAmbientOcclusionImpl(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const float* d_positions,
                                      const float* d_normals, const uint8_t* d_active, const Dispatch& g, uint8_t* d_counts, void* stream,
                                      bool adaptive = false, uint32_t probe = 0, uint8_t* d_refined = nullptr, bool bent = false,
-                                     float* d_bent = nullptr) {
+                                     float* d_bent = nullptr, const AoDistanceOut* dist = nullptr) {
     TraceParams p; uint32_t rows = 0; int s;
-    const bool ownOk = (bent ? d_bent != nullptr : d_counts != nullptr) && d_normals &&
+    const bool ownOk = (dist ? aoDistanceOutOk(*dist) : bent ? d_bent != nullptr : d_counts != nullptr) && d_normals &&
                        (adaptive ? rts::aoAdaptiveOk(ao, probe) : rts::aoParamsOk(ao));
     if (beginFrame(c, k, d_positions, d_counts, ownOk, g, p, &rows, &s) != Begin::Go) return s;
     rts::setAoNormals(p, d_normals);
@@ -1028,6 +1038,10 @@ static int traceAmbientOcclusionImpl(rts_ctx* c, const rts_constants* k, const r
     if (bent) {
         rts::setAoBent(p, d_bent);
         return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::aoBentTraces, rts::launchAmbientOcclusionBent, stream);
+    }
+    if (dist) {
+        rts::setAoDistance(p, dist->d_distance, dist->d_obscurance, dist->falloff ? dist->falloff->weight : nullptr);
+        return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::aoDistanceTraces, rts::launchAmbientOcclusionDistance, stream);
     }
     return launchBlocks(c, p, g, blockFamily(c, (uint64_t)g.W * rows), &rts_ctx::aoTraces, rts::launchAmbientOcclusion, stream);
 }
@@ -1078,6 +1092,26 @@ int rts_trace_ambient_occlusion_bent_stripes_device(rts_ctx* c, const rts_consta
                                      d_counts, stream, false, 0, nullptr, true, d_bent);
 }
 
+int rts_trace_ambient_occlusion_distance_device(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const rts_ao_falloff* falloff,
+                                                const float* d_positions, const float* d_normals, const uint8_t* d_active, uint32_t W,
+                                                uint32_t H, uint32_t row_begin, uint32_t row_end, uint8_t* d_counts, float* d_distance,
+                                                uint16_t* d_obscurance, void* stream) {
+    const AoDistanceOut out{ d_distance, d_obscurance, falloff };
+    return traceAmbientOcclusionImpl(c, k, ao, d_positions, d_normals, d_active, Dispatch::ofRows(W, H, row_begin, row_end), d_counts, stream,
+                                     false, 0, nullptr, false, nullptr, &out);
+}
+
+int rts_trace_ambient_occlusion_distance_stripes_device(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao,
+                                                        const rts_ao_falloff* falloff, const float* d_positions, const float* d_normals,
+                                                        const uint8_t* d_active, uint32_t W, uint32_t H, uint32_t band_rows,
+                                                        uint32_t n_stripes, uint32_t stripe, uint8_t* d_counts, float* d_distance,
+                                                        uint16_t* d_obscurance, void* stream) {
+    if (!rts::stripeArgsOk(band_rows, n_stripes, stripe)) return RTS_ERR_INVALID_ARG;
+    const AoDistanceOut out{ d_distance, d_obscurance, falloff };
+    return traceAmbientOcclusionImpl(c, k, ao, d_positions, d_normals, d_active, Dispatch::ofStripe(W, H, band_rows, n_stripes, stripe),
+                                     d_counts, stream, false, 0, nullptr, false, nullptr, &out);
+}
+
 // ---- adaptive soft shadows (include/rts.h): a probe of a few samples per pixel, the others only where the probe disagrees ------------
 // One launch of an adaptive kernel (rts_adaptive.inc) with the geometry, the family rule and the tail of a distance trace.  The probe
 // count and the refined plane travel in the generic rays' slots of the argument block (rts_adaptive.h).
@@ -1125,7 +1159,7 @@ int rts_trace_rays_distance_device(rts_ctx* c, const rts_ray* d_rays, size_t n, 
 // frame of their own, to the device entry of what is being traced.  StagedRows names what a host entry hands over: the first nine
 // members every entry gives, in this order; the others it sets by name, and what it leaves alone is NULL.
 enum class Staged { Mask, Distance, SoftDistance, LightList, Adaptive, SoftLightList, SoftListAdaptive, SoftListDistance, AmbientOcclusion,
-                    AoAdaptive, AoBent };
+                    AoAdaptive, AoBent, AoDistance };
 struct StagedRows {
     Staged what;
     const rts_constants* k;
@@ -1144,6 +1178,9 @@ struct StagedRows {
     const uint32_t* tables = nullptr;    // ... its jittered form, whose hash pixelBase makes that of the caller's frame
     const float* normals = nullptr;      // Staged::AmbientOcclusion, Staged::AoAdaptive, Staged::AoBent: staged in the distances' buffer
     float* bent = nullptr;               // Staged::AoBent: W x H RGBA32F, behind the normals there (its counts, `mask`, are optional)
+    float* aoDistance = nullptr;         // Staged::AoDistance (optional): W x H floats, behind the normals there
+    uint16_t* obscurance = nullptr;      // Staged::AoDistance (optional): W x H uint16_t, behind that plane's place
+    const rts_ao_falloff* falloff = nullptr;   // ... and its falloff
 };
 static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     if (!c->d_bvh) return RTS_ERR_NO_BVH;
@@ -1157,7 +1194,8 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     const size_t distPlanes = r.what == Staged::SoftListDistance ? planes : 1u;
     if (s == RTS_OK && r.distance) s = ensure(&c->d_dist, &c->distBytes, pixels * 4 * distPlanes);
     if (s == RTS_OK && r.refined) s = ensure(&c->d_dist, &c->distBytes, pixels);
-    if (s == RTS_OK && r.normals) s = ensure(&c->d_dist, &c->distBytes, pixels * 16 + (r.refined ? pixels : 0u) + (r.bent ? pixels * 16 : 0u));
+    if (s == RTS_OK && r.normals) s = ensure(&c->d_dist, &c->distBytes, pixels * 16 + (r.refined ? pixels : 0u) + (r.bent ? pixels * 16 : 0u) +
+                                                (r.what == Staged::AoDistance ? pixels * 6 : 0u));
     if (s == RTS_OK && r.mask) s = ensure(&c->d_out, &c->outBytes, pixels * planes);
     if (s == RTS_OK && r.active) s = ensure(&c->d_act, &c->actBytes, pixels);
     if (s != RTS_OK) return s;
@@ -1173,6 +1211,8 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     const float* d_in = (const float*)c->d_in;
     float* d_dist = (float*)c->d_dist;
     float* d_bent = r.bent ? d_dist + pixels * 4 : nullptr;
+    float* d_aoDistance = r.aoDistance ? d_dist + pixels * 4 : nullptr;
+    uint16_t* d_obscurance = r.obscurance ? (uint16_t*)(d_dist + pixels * 5) : nullptr;
     // per-pixel jitter hashes the pixel's index in the caller's frame (sampleIndex, rts_kernels.hip: the one reader, and only of a
     // light with a table -- several samples, so in a mask trace or a soft distance trace; of the lists the jittered one alone reads it)
     c->pixelBase = r.rowBegin * W;
@@ -1203,6 +1243,9 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
     case Staged::AoBent:
         s = rts_trace_ambient_occlusion_bent_device(c, k, (const rts_ao_params*)r.lights, d_in, d_dist, d_active, W, rows, 0, rows, d_mask,
                                                     d_bent, nullptr); break;
+    case Staged::AoDistance:
+        s = rts_trace_ambient_occlusion_distance_device(c, k, (const rts_ao_params*)r.lights, r.falloff, d_in, d_dist, d_active, W, rows, 0,
+                                                        rows, d_mask, d_aoDistance, d_obscurance, nullptr); break;
     }
     c->pixelBase = 0;
     if (s != RTS_OK) return s;
@@ -1210,6 +1253,8 @@ static int traceStagedRows(rts_ctx* c, const StagedRows& r) {
         RTS_HIP(hipMemcpy(r.distance + l * frame + first, (const float*)c->d_dist + l * pixels, pixels * 4, hipMemcpyDeviceToHost));
     if (r.refined) RTS_HIP(hipMemcpy(r.refined + first, d_refined, pixels, hipMemcpyDeviceToHost));
     if (r.bent) RTS_HIP(hipMemcpy(r.bent + first * 4, d_bent, pixels * 16, hipMemcpyDeviceToHost));
+    if (r.aoDistance) RTS_HIP(hipMemcpy(r.aoDistance + first, d_aoDistance, pixels * 4, hipMemcpyDeviceToHost));
+    if (r.obscurance) RTS_HIP(hipMemcpy(r.obscurance + first, d_obscurance, pixels * 2, hipMemcpyDeviceToHost));
     for (size_t l = 0; r.mask && l < planes; ++l)
         RTS_HIP(hipMemcpy(r.mask + l * frame + first, (const uint8_t*)c->d_out + l * pixels, pixels, hipMemcpyDeviceToHost));
     return RTS_OK;
@@ -1277,6 +1322,17 @@ int rts_trace_ambient_occlusion_bent(rts_ctx* c, const rts_constants* k, const r
     if (!rts::aoParamsOk(ao) || (uint64_t)W * H > (1ull << 31)) return RTS_ERR_INVALID_ARG;
     StagedRows r{ Staged::AoBent, k, ao, positions, active, W, H, row_begin, row_end };
     r.mask = counts; r.normals = normals; r.bent = bent;
+    return traceStagedRows(c, r);
+}
+
+int rts_trace_ambient_occlusion_distance(rts_ctx* c, const rts_constants* k, const rts_ao_params* ao, const rts_ao_falloff* falloff,
+                                         const float* positions, const float* normals, const uint8_t* active, uint32_t W, uint32_t H,
+                                         uint32_t row_begin, uint32_t row_end, uint8_t* counts, float* distance, uint16_t* obscurance) {
+    if (!c || !k || !positions || !normals || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::aoParamsOk(ao) || (uint64_t)W * H > (1ull << 31) || !aoDistanceOutOk(AoDistanceOut{ distance, obscurance, falloff }))
+        return RTS_ERR_INVALID_ARG;
+    StagedRows r{ Staged::AoDistance, k, ao, positions, active, W, H, row_begin, row_end };
+    r.mask = counts; r.normals = normals; r.aoDistance = distance; r.obscurance = obscurance; r.falloff = falloff;
     return traceStagedRows(c, r);
 }
 

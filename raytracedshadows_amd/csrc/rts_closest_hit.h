@@ -1309,4 +1309,26 @@ RTS_HD void skyAmbient3(float ambient, float ao, const float* sky9, const float*
     for (int c = 0; c < 3; ++c) out3[c] = scaled * tint[c];
 }
 
+// AO DISTANCE AND FALLOFF (include/rts.h, rts_trace_ambient_occlusion_distance*): how OPEN a sample counts, looked up from its one-ray
+// distance quantised to 64ths of the segment -- an integer per (pixel, sample), so the per-pixel sum A is as order-free as the count is.
+// aoFalloffBin is b_j of the header: bits is a blocked sample's distance, a bit pattern in [+0, +Inf); min(d, 1) * 64 is exact (a power
+// of two) and the conversion truncates, so bin k starts exactly at k / 64 and d >= 63 / 64 (1.0 included) falls in bin 63.
+// aoOpenness is a_j: 255 for a free sample, else the table's byte; weightOf(b) reads weight[b] wherever the caller keeps the table.
+// aoObscurance is the quotient: A <= 48 * 255 and S = 65535 / n, so 2 * A * S + 255 < 2^26, and the result never exceeds n * S.
+// Shared by the host twin (rts_scene.cpp) and the kernels (rts_ao_distance.inc).
+RTS_HD uint32_t aoFalloffBin(uint32_t bits) {
+    const float d = asFloat(bits);
+    const float c = d < 1.0f ? d : 1.0f;
+    const uint32_t b = (uint32_t)(c * 64.0f);
+    return b < 63u ? b : 63u;
+}
+template <class WeightOf>
+RTS_HD uint32_t aoOpenness(uint32_t bits, WeightOf weightOf) {
+    return bits == 0x7F800000u ? 255u : (uint32_t)weightOf(aoFalloffBin(bits));
+}
+RTS_HD uint32_t aoObscurance(uint32_t A, uint32_t n) {
+    const uint32_t S = 65535u / n;
+    return (2u * A * S + 255u) / 510u;
+}
+
 } // namespace rts_harness

@@ -304,3 +304,5 @@ hipError_t launchTraceRaysDistance(const TraceParams& p, hipStream_t stream) {
 #include "rts_ao_adaptive.inc"
 // bent normals: the AO trace with the integer sum of its unoccluded directions beside the count (its launch is declared in rts_ao_bent.h)
 #include "rts_ao_bent.inc"
+// AO distance and falloff: the AO trace with the nearest blocker and the falloff-weighted obscurance beside the count (its launch is declared in rts_ao_distance.h)
+#include "rts_ao_distance.inc"

@@ -463,6 +463,37 @@ extern "C" int rtsh_ambient_occlusion_bent(const rts_vec4u* packed, size_t count
     return RTS_OK;
 }
 
+// ---- AO distance and falloff on the host (include/rts_scene.h): the checker of rts_trace_ambient_occlusion_distance* ----
+// rtsh_ambient_occlusion's loop with the minimum and the weighted sum beside the count: aoOpenness of the sample's one-ray distance,
+// aoObscurance on the finished sum (rts_closest_hit.h: the kernels' own source).
+extern "C" int rtsh_ambient_occlusion_distance(const rts_vec4u* packed, size_t count_vec4, const rts_constants* k, const rts_ao_params* ao,
+                                               const rts_ao_falloff* falloff, const float* positions, const float* normals,
+                                               const uint8_t* active, uint32_t W, uint32_t H, uint32_t row_begin, uint32_t row_end,
+                                               uint8_t* counts, float* distance, uint16_t* obscurance, int threads) {
+    if (!packed || !k || !positions || !normals || !rts::frameRowsOk(W, H, row_begin, row_end)) return RTS_ERR_INVALID_ARG;
+    if (!rts::aoParamsOk(ao) || (!distance && !obscurance) || (obscurance && !falloff)) return RTS_ERR_INVALID_ARG;
+    if (((uintptr_t)obscurance & 1u) != 0 || ((uintptr_t)distance & 3u) != 0) return RTS_ERR_INVALID_ARG;
+    const int s = rts_bvh_validate(packed, count_vec4, nullptr);
+    if (s != RTS_OK) return s;
+    const uint32_t* bvh = (const uint32_t*)packed;
+    const uint32_t n = ao->nsamples > 1 ? ao->nsamples : 1u;
+    const size_t first = (size_t)row_begin * W;
+    parallelFor((size_t)(row_end - row_begin) * W, 64, threads, [&](size_t at) {
+        const size_t i = first + at;
+        uint32_t best = 0x7F800000u, lit = 0, open = 0;
+        const bool live = aoPixelRays(k, ao, n, positions, normals, active, i, [&](uint32_t, const DRay& r) {
+            const uint32_t one = rayDistanceBits(bvh, r);                // d_j
+            lit += one == 0x7F800000u ? 1u : 0u;                         // u_j: comp:148, per sample
+            if (one < best) best = one;
+            if (obscurance) open += aoOpenness(one, [&](uint32_t b) { return falloff->weight[b]; });
+        });
+        if (counts) counts[i] = (uint8_t)lit;
+        if (distance) distance[i] = live ? asFloat(best) : 0.0f;
+        if (obscurance) obscurance[i] = live ? (uint16_t)aoObscurance(open, n) : (uint16_t)0;
+    });
+    return RTS_OK;
+}
+
 // ---- adaptive soft shadows on the host (include/rts_scene.h): the checker of rts_trace_shadow_mask_adaptive* ----
 // The definition of include/rts.h applied literally, one straight loop over (pixel, sample) on frameDistance's walk: the probe's
 // samples, then the others only where the probe disagrees.

@@ -136,6 +136,7 @@ def parse_ao(text, wl):
 
 AO_ADAPTIVE = {"probe": 0, "refined_out": ""}           # --ao-adaptive K [--ao-refined FILE.ppm], set by main()
 AO_BENT = {"on": False, "sky": None, "out": "", "d_bent": None}   # --ao-bent [--sky --ground --up --bent-out], set by main()
+AO_FALLOFF = {"falloff": None, "name": "", "distance_out": ""}    # --ao-falloff NAME [--ao-distance FILE.ppm], set by main()
 
 
 def ao_combine(ctx, api, constants, hard_list, d_pos, d_nrm, d_vis, d_ao, W, H, d_rgb, **kw):
@@ -152,8 +153,23 @@ def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
     With --ao-adaptive K the counts come from rts_trace_ambient_occlusion_adaptive_device: the same kind of plane, nothing behind it changes."""
     d_counts, d_ao = ctx.malloc(W * H), ctx.malloc(W * H * 4)
     probe = AO_ADAPTIVE["probe"]
+    d_obscurance = None
     t0 = time.time()
-    if probe:
+    if AO_FALLOFF["falloff"] is not None:                # the falloff-weighted obscurance (and the nearest blocker) beside the counts
+        d_obscurance = ctx.malloc(W * H * 2)
+        d_distance = ctx.malloc(W * H * 4) if AO_FALLOFF["distance_out"] else None
+        ctx.trace_ambient_occlusion_distance_device(wl.constants, ao, AO_FALLOFF["falloff"], d_pos, d_nrm, W, H, d_counts, d_distance,
+                                                    d_obscurance)
+        ctx.synchronize()
+        if d_distance:
+            distance = np.zeros((H, W), np.float32)
+            ctx.d2h(distance, d_distance)
+            ctx.free(d_distance)
+            near = np.where(np.isfinite(distance), np.clip(distance, 0, 1), 1.0)      # (+Inf: no blocker inside the radius -- white)
+            os.makedirs(os.path.dirname(os.path.abspath(AO_FALLOFF["distance_out"])), exist_ok=True)
+            api.write_ppm(AO_FALLOFF["distance_out"], np.repeat((near * 255).astype(np.uint8)[..., None], 3, axis=2))
+            print(f"wrote {AO_FALLOFF['distance_out']}: the nearest blocker as a fraction of the radius")
+    elif probe:
         d_refined = ctx.malloc(W * H)
         ctx.trace_ambient_occlusion_adaptive_device(wl.constants, ao, d_pos, d_nrm, W, H, d_counts, probe, d_refined=d_refined)
         ctx.synchronize()
@@ -183,7 +199,12 @@ def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
     print(f"ambient occlusion: {ao.samples} segments of {ao.radius:g} per pixel{f', table {ao.table}' if ao.table else ''}: "
           f"{(time.time() - t0) * 1e3:.2f} ms (first call, incl. launch); {ctx.last_kernel_name()}")
     stand_in = ao.stand_in_list()
-    if isinstance(filt, api.WideFilterParams):
+    if d_obscurance is not None:                         # the plane IS in the wide filter's fixed point: no conversion pass (passes 0 converts)
+        wide = filt if isinstance(filt, api.WideFilterParams) else api.WideFilterParams.make(0, 0.9, 0.05)
+        d_scratch = ctx.malloc(api.wide_filter_scratch_bytes(1, W, H)) if wide.passes >= 2 else None
+        api.wide_filter_mean_soft_light_list_device(ctx, stand_in, wide, d_pos, d_nrm, d_obscurance, W, H, d_ao, d_scratch=d_scratch)
+        print(f"ambient occlusion: falloff {AO_FALLOFF['name']}, {wide.passes} wide filter passes over the obscurance plane")
+    elif isinstance(filt, api.WideFilterParams):
         d_scratch = ctx.malloc(api.wide_filter_scratch_bytes(1, W, H)) if filt.passes >= 2 else None
         api.wide_filter_soft_light_list_device(ctx, stand_in, filt, d_pos, d_nrm, d_counts, W, H, d_ao, d_scratch=d_scratch)
     else:
@@ -527,6 +548,12 @@ def main():
     ap.add_argument("--ao-bent", action="store_true",
                     help="with --ao N: trace the bent normals beside the counts (rts_trace_ambient_occlusion_bent_device) and tint the "
                          "ambient term between --ground and --sky by where they point (rtsh_combine_visibility_list_ao_bent_device)")
+    ap.add_argument("--ao-falloff", default="", choices=("", "linear", "quadratic", "zeros"),
+                    help="with --ao N: trace the falloff-weighted obscurance (rts_trace_ambient_occlusion_distance_device) -- a blocker "
+                         "near the end of a segment darkens less than one at its start -- and feed it to the wide mean filter "
+                         "(--filter-passes K, default 0) under the stand-in list, then to the AO combine; zeros is the plain count")
+    ap.add_argument("--ao-distance", default="", metavar="FILE.ppm",
+                    help="with --ao-falloff: also write the nearest blocker over the hemisphere, as a fraction of the radius, as an image")
     ap.add_argument("--sky", default="0.55,0.7,1.0", metavar="r,g,b", help="with --ao-bent: the ambient colour towards --up")
     ap.add_argument("--ground", default="0.45,0.35,0.25", metavar="r,g,b", help="with --ao-bent: the ambient colour against --up")
     ap.add_argument("--up", default="0,1,0", metavar="x,y,z", help="with --ao-bent: the direction of the sky (normalised here)")
@@ -562,6 +589,16 @@ def main():
             except (ValueError, AssertionError):
                 sys.exit("render: --sky, --ground and --up take three numbers r,g,b / x,y,z (up not zero)")
             AO_BENT.update(on=True, out=args.bent_out, sky=api.SkyAmbient.make(up=np.asarray(up) / np.linalg.norm(up), sky=sky, ground=ground))
+        if (args.ao_falloff or args.ao_distance) and ao is None:
+            sys.exit("render: --ao-falloff and --ao-distance go with --ao")
+        if args.ao_distance and not args.ao_falloff:
+            sys.exit("render: --ao-distance goes with --ao-falloff")
+        if args.ao_falloff and (args.ao_adaptive or args.ao_bent):
+            sys.exit("render: --ao-falloff does not go with --ao-adaptive or --ao-bent (neither has a distance form)")
+        if args.ao_falloff and args.filter >= 0:
+            sys.exit("render: --ao-falloff goes with --filter-passes (the obscurance plane feeds the wide mean filter), not with --filter")
+        if args.ao_falloff:
+            AO_FALLOFF.update(falloff=getattr(api.AoFalloff, args.ao_falloff)(), name=args.ao_falloff, distance_out=args.ao_distance)
         if ao is not None and args.temporal:
             sys.exit("render: --ao does not go with --temporal")
         if args.soft_list:
