@@ -562,6 +562,51 @@ int rtsh_wide_filter_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_l
                                             const uint8_t* d_counts, uint32_t W, uint32_t H, float* d_visibility, uint16_t* d_scratch,
                                             void* stream);
 
+/* THE WIDE FILTER OF THE BENT PLANE: the a-trous filter above over rts_trace_ambient_occlusion_bent*'s plane -- W x H
+ * RGBA32F, (frame * sum of free directions, count) per pixel --, so that the direction an ambient term is aimed by is as smooth as the
+ * AO term beside it.  The world-space vector is QUANTISED ONCE, to 16-bit signed integers, and from there every sum across pixels is an
+ * INTEGER sum: the rule above with signed values, and as order-free.  One geometry test and one byte decide a tap for all four
+ * channels.  Inputs: rtsh_wide_filter_params (unchanged); nsamples, n = max(1, nsamples) <= RTS_AO_MAX_SAMPLES (the trace's sample
+ * count: |bent.xyz| <= n up to rounding, bent.w = the count); positions, normals; `active`, W x H bytes or NULL; `bent`, any float allowed.
+ *   ACTIVE: a pixel is active when it is not bg(p) and (active == NULL or active[p] != 0).  bg, geom(p, q), the 25 taps, the weights
+ *     b = {6, 4, 1} and the in-frame rule are the wide filter's above, word for word.  A tap is accepted when it is the centre, or when
+ *     geom(p, q) holds and q is active.  An INACTIVE pixel carries four zeros in every pass and is never accepted.
+ *   INPUT: S_b = 32767 / n, S_l = 65535 / n, both by integer division.  Per component c of xyz: t = bent.c * (float)S_b, ONE rounded
+ *     multiply, no contraction; a NaN gives 0; clamp to [-(n * S_b), n * S_b]; X_0.c = (int32) rint(t), ties to even: it fits int16.
+ *     For .w: a NaN gives 0; clamp to [0, n]; rint; V_0 = that * S_l -- uint16, the wide filter's V_0 of the count.
+ *   PASS k (step 1 << k): den = sum of w over the accepted taps; per signed component num = sum of w * X_k.c (|num| <= 32767 * 256 <
+ *     2^23) and X_(k+1).c = sign(num) * ((2 * |num| + den) / (2 * den)) by integer division: the ROUNDED MEAN, HALF AWAY FROM ZERO, so
+ *     that negating the input negates the output.  The .w channel is the wide filter's pass unchanged.
+ *   OUTPUT (formed by the last pass; from X_0 when passes == 0): out[p].c = (float)X.c / (float)(n * S_b), one correctly rounded
+ *     division, a zero numerator gives +0;  out[p].w = (float)V / (float)(n * S_l);  ao[p], when given, holds out[p].w's bits.  An
+ *     inactive pixel gets four +0 (and ao[p] = +0).  So out.xyz is the mean free direction PER SAMPLE, inside [-1, 1], out.w the AO
+ *     visibility in [0, 1], and |xyz| / w keeps the trace's measure of how narrow the open cone is.
+ * ANCHORS: (1) out.w and ao equal, bit for bit, rtsh_wide_filter_soft_light_list*'s plane of the bent trace's own `counts` under a
+ * one-entry soft list of n samples, the same parameters and a map of 0 / 1 bytes, for every passes.  (2) Negating every bent.xyz negates
+ * every out.xyz exactly (a zero stays +0: the division gives it).  (3) RANGE: every X_(k+1).c lies between the smallest and the largest
+ * accepted X_k.c.  (4) Thresholds that accept no neighbour give the passes == 0 plane at any passes.  (5) Equal accepted texels give
+ * that texel.  (6) rtsh_combine_visibility_list_ao_bent* over (ao, out) with passes == 0 gives the h of the raw plane wherever the raw
+ * vector quantises exactly; NOT BIT-EQUAL IN GENERAL: the direction is rounded to 1 / (n S_b).
+ *   * out: W x H RGBA32F, required; ao: W x H floats or NULL.  Host form: multi-threaded (threads: 0 = all host threads), allocates
+ *     its own intermediates.
+ *   * device form: DEVICE buffers, asynchronous on `stream`, allocates nothing and reads nothing back.  d_scratch:
+ *     rtsh_wide_filter_bent_scratch_bytes(W, H) = 2 * W * H * 8 bytes, ALIGNED TO 8 BYTES: two ping-pong planes of one 8-byte texel per
+ *     pixel (int16 x, y, z and uint16 V; the second begins W * H texels in); NULL allowed when passes <= 1, nothing of it is touched
+ *     then, and passes == 2 leaves its second half untouched.  d_bent and d_out are ALIGNED TO 16 BYTES (they are read and written as
+ *     whole texels).  Under graph capture a call adds exactly max(1, passes) KERNEL nodes on one chain, parameters by value.  No BVH.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the wide filter above refuses of its parameters and sizes;
+ *     NULL positions, normals, bent or out; nsamples > RTS_AO_MAX_SAMPLES; in the device form a NULL ctx, H above 16 * 65535, a NULL
+ *     d_scratch with passes >= 2, d_out or d_ao equal to d_bent, to d_scratch or to its second half, a d_bent or d_out that is not
+ *     aligned to 16 bytes, a d_scratch not aligned to 8.
+ *   * OUT OF SCOPE: temporal accumulation of the bent plane, variance guidance, a bent form of the adaptive or distance traces, stripes
+ *     and row ranges. */
+size_t rtsh_wide_filter_bent_scratch_bytes(uint32_t W, uint32_t H);   /* 2 * W * H * 8; 0 where W or H is 0 */
+int rtsh_wide_filter_bent(const rtsh_wide_filter_params* params, uint32_t nsamples, const float* positions, const float* normals,
+                          const uint8_t* active, const float* bent, uint32_t W, uint32_t H, float* out, float* ao, int threads);
+int rtsh_wide_filter_bent_device(rts_ctx* ctx, const rtsh_wide_filter_params* params, uint32_t nsamples, const float* d_positions,
+                                 const float* d_normals, const uint8_t* d_active, const float* d_bent, uint32_t W, uint32_t H, float* d_out,
+                                 float* d_ao, void* d_scratch, void* stream);
+
 /* THE VARIANCE-GUIDED WIDE FILTER OF A SOFT LIGHT LIST'S PLANES: rtsh_wide_filter_soft_light_list above with SVGF's luminance stop, so
  * that the passes blur noise and stop at a sharp shadow edge.  A tap is accepted for a light only if its value lies within a tolerance
  * T of the centre's, and T comes from the count plane itself: a pixel with c of n samples unoccluded has a Bernoulli variance

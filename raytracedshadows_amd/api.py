@@ -756,6 +756,11 @@ _sig("rtsh_wide_filter_light_list_device", C.c_int, C.c_void_p, C.POINTER(LightL
      C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_wide_filter_soft_light_list_device", C.c_int, C.c_void_p, C.POINTER(SoftLightList), C.POINTER(WideFilterParams), C.c_void_p,
      C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_wide_filter_bent_scratch_bytes", C.c_size_t, C.c_uint32, C.c_uint32)
+_sig("rtsh_wide_filter_bent", C.c_int, C.POINTER(WideFilterParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+     C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rtsh_wide_filter_bent_device", C.c_int, C.c_void_p, C.POINTER(WideFilterParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_wide_filter_guided_scratch_bytes", C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32)
 _sig("rtsh_wide_guide_threshold", C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32)
 _sig("rtsh_wide_filter_guided_soft_light_list", C.c_int, C.POINTER(SoftLightList), C.POINTER(WideGuideParams), C.c_void_p, C.c_void_p,
@@ -2517,6 +2522,43 @@ def wide_filter_soft_light_list_device(ctx, lights, params, d_positions, d_norma
                                                         height, C.c_void_p(d_visibility), C.c_void_p(d_scratch or 0),
                                                         C.c_void_p(stream or 0)),
            "rtsh_wide_filter_soft_light_list_device")
+
+
+def wide_filter_bent_scratch_bytes(width, height):
+    """The bytes of ``d_scratch`` of ``wide_filter_bent_device`` (rtsh_wide_filter_bent_scratch_bytes): 2 * width * height texels of 8
+    bytes, aligned to 8."""
+    return int(_lib.rtsh_wide_filter_bent_scratch_bytes(width, height))
+
+
+def wide_filter_bent(params, nsamples, positions, normals, bent, active=None, threads=0):
+    """The wide (a-trous) filter of a bent trace's plane on the host (rtsh_wide_filter_bent): ``(float32[H, W, 4] out, float32[H, W]
+    ao)`` -- ``out.xyz`` the mean free direction per sample after ``params.passes`` passes (a ``WideFilterParams``) over 16-bit integer
+    vectors, ``out.w`` the AO visibility, ``ao`` its copy.  ``nsamples``: the trace's sample count; ``bent``: ``float32[H, W, 4]``, any
+    float; ``active``: ``uint8[H, W]`` or None."""
+    name = "rtsh_wide_filter_bent"
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    bent = np.ascontiguousarray(bent, np.float32) if bent is not None else None
+    active = np.ascontiguousarray(active, np.uint8) if active is not None else None
+    if (positions is not None and positions.size != H * W * 4) or (bent is not None and bent.size != H * W * 4) or \
+            (active is not None and active.size != H * W):
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    out, ao = np.zeros((H, W, 4), np.float32), np.zeros((H, W), np.float32)
+    _check(_lib.rtsh_wide_filter_bent(_ref(params), nsamples, _ptr_or_none(positions), _ptr(normals), _ptr_or_none(active), _ptr_or_none(bent),
+                                      W, H, _ptr(out), _ptr(ao), threads), name)
+    return out, ao
+
+
+def wide_filter_bent_device(ctx, params, nsamples, d_positions, d_normals, d_bent, width, height, d_out, d_ao=None, d_scratch=None,
+                            d_active=None, stream=None):
+    """The wide filter of a bent trace's plane on the GPU: device pointers, d_bent and d_out = width*height RGBA32F (aligned to 16
+    bytes), d_ao = width*height floats or None, d_scratch = ``wide_filter_bent_scratch_bytes(width, height)`` bytes aligned to 8 (None
+    allowed for passes <= 1); max(1, passes) kernels, asynchronous."""
+    _check(_lib.rtsh_wide_filter_bent_device(ctx.handle, _ref(params), nsamples, C.c_void_p(d_positions or 0), C.c_void_p(d_normals or 0),
+                                             C.c_void_p(d_active or 0), C.c_void_p(d_bent or 0), width, height, C.c_void_p(d_out or 0),
+                                             C.c_void_p(d_ao or 0), C.c_void_p(d_scratch or 0), C.c_void_p(stream or 0)),
+           "rtsh_wide_filter_bent_device")
 
 
 def wide_filter_guided_scratch_bytes(count, width, height):

@@ -443,6 +443,85 @@ RTS_HD void wideFilterPassPixel(const WideFilterList& f, const Texels& t, int x,
     }
 }
 
+// The WIDE FILTER OF THE BENT PLANE (include/rts_scene.h, rtsh_wide_filter_bent): the pass above over one texel of FOUR
+// 16-bit integers -- the bent vector's components, signed, in units of 1 / S_b, and V of the count, unsigned, in units of 1 / S_l --,
+// one geometry test and one `active` byte per tap for all four.  The three small rules (quantise, rounded signed mean, quotient) and the
+// texel's packing are the source of the host twin and of the kernels alike.
+struct BentFilterList { uint32_t passes, samples, scaleB, scaleL; float normalCosMin, planeEps; };       // n, S_b, S_l
+struct BentTexel { int32_t x, y, z; uint32_t v; };                                                      // each fits 16 bits
+
+RTS_HD uint32_t bentFilterScale(uint32_t samples) { return 32767u / samples; }                            // S_b
+// X_0.c: one rounded multiply, a NaN is 0, the clamp to +-(n * S_b), rint (ties to even)
+RTS_HD int32_t bentFilterQuantise(float c, uint32_t samples, uint32_t scaleB) {
+    const float t = c * (float)scaleB;
+    if (t != t) return 0;
+    const float lim = (float)(samples * scaleB);
+    return (int32_t)__builtin_rintf(t < -lim ? -lim : (t > lim ? lim : t));
+}
+// V_0 from bent.w: a NaN is 0, the clamp to [0, n], rint, times S_l -- wideFilterInput of the count wherever .w is that count
+RTS_HD uint32_t bentFilterCount(float w, uint32_t samples, uint32_t scaleL) {
+    if (w != w) return 0u;
+    const float lim = (float)samples;
+    return (uint32_t)(int32_t)__builtin_rintf(w < 0.0f ? 0.0f : (w > lim ? lim : w)) * scaleL;
+}
+// the rounded mean of a signed sum, half away from zero: the mean of the negated values is the negated mean
+RTS_HD int32_t bentFilterMean(int32_t num, uint32_t den) {
+    const uint32_t a = num < 0 ? (uint32_t)(-num) : (uint32_t)num;
+    const int32_t q = (int32_t)((2u * a + den) / (2u * den));
+    return num < 0 ? -q : q;
+}
+// out.c = (float)X.c / (float)(n * S_b): one rounded division; a zero numerator gives +0
+RTS_HD float bentFilterOutput(int32_t x, uint32_t samples, uint32_t scaleB) { return (float)x / (float)(samples * scaleB); }
+
+// The 8-byte texel between passes: int16 x, y, z and uint16 V, lowest bits first; unpacked with integer operations alone.
+RTS_HD uint64_t bentFilterPack(const BentTexel& t) {
+    return (uint64_t)((uint32_t)t.x & 0xFFFFu) | ((uint64_t)((uint32_t)t.y & 0xFFFFu) << 16) | ((uint64_t)((uint32_t)t.z & 0xFFFFu) << 32) |
+           ((uint64_t)(t.v & 0xFFFFu) << 48);
+}
+RTS_HD BentTexel bentFilterUnpack(uint64_t u) {
+    const uint32_t lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
+    return BentTexel{ (int32_t)(int16_t)(uint16_t)(lo & 0xFFFFu), (int32_t)(int16_t)(uint16_t)(lo >> 16), (int32_t)(int16_t)(uint16_t)(hi & 0xFFFFu),
+                      hi >> 16 };
+}
+RTS_HD BentTexel bentFilterInput(float bx, float by, float bz, float bw, const BentFilterList& f) {
+    return BentTexel{ bentFilterQuantise(bx, f.samples, f.scaleB), bentFilterQuantise(by, f.samples, f.scaleB),
+                      bentFilterQuantise(bz, f.samples, f.scaleB), bentFilterCount(bw, f.samples, f.scaleL) };
+}
+
+// One pass at one pixel.  `Texels`: V3 normal(x, y), V3 position(x, y); bool active(x, y) (the byte, true without a plane);
+// BentTexel texel(x, y): X_k and V_k -- the first pass's from bentFilterInput of the float texel, later the unpacked 8 bytes.  Returns
+// whether the pixel is active; an inactive pixel gets four zeros and reads nothing beyond its normal and its byte.  A tap's byte is
+// looked at before its geometry (the verdict is the conjunction either way; the byte is the cheaper read).  step == 0 walks no tap.
+template <class Texels>
+RTS_HD bool bentFilterPassPixel(const BentFilterList& f, const Texels& t, int x, int y, int W, int H, int step, BentTexel* result) {
+    const V3 np = t.normal(x, y);
+    *result = BentTexel{ 0, 0, 0, 0u };
+    if (isBackground(np) || !t.active(x, y)) return false;
+    const BentTexel c = t.texel(x, y);
+    int32_t sx = 36 * c.x, sy = 36 * c.y, sz = 36 * c.z;                            // the centre tap: always accepted
+    uint32_t sv = 36u * c.v, den = 36u;
+    if (step > 0) {
+        const V3 pp = t.position(x, y);
+        for (int dy = -2; dy <= 2; ++dy) {
+            const int qy = y + dy * step;
+            if (qy < 0 || qy >= H) continue;
+            const int32_t wy = dy == 0 ? 6 : ((dy == 1 || dy == -1) ? 4 : 1);
+            for (int dx = -2; dx <= 2; ++dx) {
+                const int qx = x + dx * step;
+                if (qx < 0 || qx >= W || (dx == 0 && dy == 0)) continue;
+                if (!t.active(qx, qy)) continue;
+                if (!wideFilterGeom(t, np, pp, qx, qy, f.normalCosMin, f.planeEps)) continue;
+                const int32_t w = wy * (dx == 0 ? 6 : ((dx == 1 || dx == -1) ? 4 : 1));
+                const BentTexel q = t.texel(qx, qy);
+                sx += w * q.x; sy += w * q.y; sz += w * q.z;                        // |sum| <= 256 * 32767 < 2^23
+                sv += (uint32_t)w * q.v; den += (uint32_t)w;
+            }
+        }
+    }
+    *result = BentTexel{ bentFilterMean(sx, den), bentFilterMean(sy, den), bentFilterMean(sz, den), (2u * sv + den) / (2u * den) };
+    return true;
+}
+
 // The VARIANCE-GUIDED wide filter of a soft light list's planes (include/rts_scene.h, rtsh_wide_filter_guided_soft_light_list): the
 // threshold T(p, l) of the header from the 3 x 3 neighbourhood of V_0, and one pass that accepts a tap for light l only where
 // |V_k(q, l) - V_k(p, l)| <= T(p, l).  Integers throughout, so header, host twin, numpy rule and kernels agree bit for bit.

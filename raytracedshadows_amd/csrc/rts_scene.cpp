@@ -1057,6 +1057,78 @@ extern "C" int rtsh_wide_filter_soft_light_list(const rts_soft_light_list* list,
     return widePassChain(f, positions, normals, lights_map, WideSoftInput{ counts }, W, H, visibility, threads, nullptr);
 }
 
+// ---- the wide filter of the bent plane (include/rts_scene.h; per-pixel rule in rts_closest_hit.h: bentFilterPassPixel) ----
+namespace rts_harness {
+// Shared by the host and device forms: the refusals of the parameters, of the frame and of the sample count, and n, S_b, S_l.
+int makeBentFilterList(const rtsh_wide_filter_params* p, uint32_t nsamples, uint32_t W, uint32_t H, BentFilterList* out) {
+    WideFilterList w;
+    const int s = makeWideFilterList(1, &nsamples, p, W, H, &w);
+    if (s != RTS_OK) return s;
+    if (!out || nsamples > (uint32_t)RTS_AO_MAX_SAMPLES) return RTS_ERR_INVALID_ARG;
+    *out = BentFilterList{ w.passes, w.samples[0], bentFilterScale(w.samples[0]), w.scale[0], w.normalCosMin, w.planeEps };
+    return RTS_OK;
+}
+
+namespace {
+// The frame as a pass reads it on the host: the first pass quantises the float texel, later ones unpack the previous pass's 8 bytes.
+struct BentFrameTexels {
+    const float *positions, *normals, *bent;
+    const uint8_t* map;
+    const uint64_t* values;                      // the previous pass's plane; NULL: the first pass
+    const BentFilterList& f;
+    size_t W;
+    size_t at(int x, int y) const { return (size_t)y * W + (size_t)x; }
+    V3 normal(int x, int y) const { const float* v = normals + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
+    V3 position(int x, int y) const { const float* v = positions + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
+    bool active(int x, int y) const { return !map || map[at(x, y)] != 0; }
+    BentTexel texel(int x, int y) const {
+        if (values) return bentFilterUnpack(values[at(x, y)]);
+        const float* b = bent + at(x, y) * 4;
+        return bentFilterInput(b[0], b[1], b[2], b[3], f);
+    }
+};
+} // namespace
+} // namespace rts_harness
+
+extern "C" size_t rtsh_wide_filter_bent_scratch_bytes(uint32_t W, uint32_t H) {
+    return W == 0 || H == 0 ? 0 : 2 * (size_t)W * (size_t)H * sizeof(uint64_t);
+}
+
+extern "C" int rtsh_wide_filter_bent(const rtsh_wide_filter_params* params, uint32_t nsamples, const float* positions, const float* normals,
+                                     const uint8_t* active, const float* bent, uint32_t W, uint32_t H, float* out, float* ao, int threads) {
+    if (!positions || !normals || !bent || !out) return RTS_ERR_INVALID_ARG;
+    BentFilterList f;
+    const int s = makeBentFilterList(params, nsamples, W, H, &f);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    std::vector<uint64_t> scratch;
+    try {
+        if (f.passes >= 2u) scratch.resize(2 * n);
+    } catch (const std::bad_alloc&) {
+        return RTS_ERR_CAPACITY;
+    }
+    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
+    for (uint32_t k = 0; k < launches; ++k) {
+        const bool first = k == 0u, last = k + 1u == launches;
+        const int step = f.passes == 0u ? 0 : 1 << k;
+        const uint64_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * n;
+        uint64_t* mid = last ? nullptr : scratch.data() + (k & 1u) * n;
+        const BentFrameTexels t{ positions, normals, bent, active, in, f, W };
+        parallelFor(n, 256, threads, [&](size_t i) {
+            BentTexel v;
+            bentFilterPassPixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H, step, &v);
+            if (!last) { mid[i] = bentFilterPack(v); return; }
+            float* o = out + i * 4;
+            o[0] = bentFilterOutput(v.x, f.samples, f.scaleB);
+            o[1] = bentFilterOutput(v.y, f.samples, f.scaleB);
+            o[2] = bentFilterOutput(v.z, f.samples, f.scaleB);
+            o[3] = wideFilterOutput(v.v, f.samples, f.scaleL);
+            if (ao) ao[i] = o[3];
+        });
+    }
+    return RTS_OK;
+}
+
 // ---- the variance-guided wide filter of a soft light list's planes (include/rts_scene.h; per-pixel rule in rts_closest_hit.h:
 // wideGuideThresholdPixel, wideGuidedPassPixel) ----
 namespace rts_harness {

@@ -135,7 +135,7 @@ def parse_ao(text, wl):
 
 
 AO_ADAPTIVE = {"probe": 0, "refined_out": ""}           # --ao-adaptive K [--ao-refined FILE.ppm], set by main()
-AO_BENT = {"on": False, "sky": None, "out": "", "d_bent": None}   # --ao-bent [--sky --ground --up --bent-out], set by main()
+AO_BENT = {"on": False, "sky": None, "out": "", "d_bent": None, "filter": False}   # --ao-bent [--sky --ground --up --bent-out --bent-filter]
 AO_FALLOFF = {"falloff": None, "name": "", "distance_out": ""}    # --ao-falloff NAME [--ao-distance FILE.ppm], set by main()
 
 
@@ -145,6 +145,17 @@ def ao_combine(ctx, api, constants, hard_list, d_pos, d_nrm, d_vis, d_ao, W, H, 
         return api.combine_visibility_list_ao_bent_device(ctx, constants, hard_list, d_pos, d_nrm, d_vis, d_ao, AO_BENT["d_bent"],
                                                           AO_BENT["sky"], W, H, d_rgb, **kw)
     return api.combine_visibility_list_ao_device(ctx, constants, hard_list, d_pos, d_nrm, d_vis, d_ao, W, H, d_rgb, **kw)
+
+
+def write_bent(ctx, api, d_bent, W, H, what):
+    """--bent-out: 0.5 + 0.5 * unit(xyz) of an RGBA32F plane on the device, as an image."""
+    bent = np.zeros((H, W, 4), np.float32)
+    ctx.d2h(bent, d_bent)
+    length = np.linalg.norm(bent[..., :3], axis=-1, keepdims=True)
+    unit = np.divide(bent[..., :3], length, out=np.zeros((H, W, 3), np.float32), where=length > 0)
+    os.makedirs(os.path.dirname(os.path.abspath(AO_BENT["out"])), exist_ok=True)
+    api.write_ppm(AO_BENT["out"], (np.clip(0.5 + 0.5 * unit, 0, 1) * 255).astype(np.uint8))
+    print(f"wrote {AO_BENT['out']}: 0.5 + 0.5 * unit({what})")
 
 
 def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
@@ -185,14 +196,8 @@ def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
         AO_BENT["d_bent"] = ctx.malloc(W * H * 16)
         ctx.trace_ambient_occlusion_bent_device(wl.constants, ao, d_pos, d_nrm, W, H, d_counts, AO_BENT["d_bent"])
         ctx.synchronize()
-        if AO_BENT["out"]:
-            bent = np.zeros((H, W, 4), np.float32)
-            ctx.d2h(bent, AO_BENT["d_bent"])
-            length = np.linalg.norm(bent[..., :3], axis=-1, keepdims=True)
-            unit = np.divide(bent[..., :3], length, out=np.zeros((H, W, 3), np.float32), where=length > 0)
-            os.makedirs(os.path.dirname(os.path.abspath(AO_BENT["out"])), exist_ok=True)
-            api.write_ppm(AO_BENT["out"], (np.clip(0.5 + 0.5 * unit, 0, 1) * 255).astype(np.uint8))
-            print(f"wrote {AO_BENT['out']}: 0.5 + 0.5 * unit(bent)")
+        if AO_BENT["out"] and not AO_BENT["filter"]:
+            write_bent(ctx, api, AO_BENT["d_bent"], W, H, "bent")
     else:
         ctx.trace_ambient_occlusion_device(wl.constants, ao, d_pos, d_nrm, W, H, d_counts)
         ctx.synchronize()
@@ -204,6 +209,17 @@ def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
         d_scratch = ctx.malloc(api.wide_filter_scratch_bytes(1, W, H)) if wide.passes >= 2 else None
         api.wide_filter_mean_soft_light_list_device(ctx, stand_in, wide, d_pos, d_nrm, d_obscurance, W, H, d_ao, d_scratch=d_scratch)
         print(f"ambient occlusion: falloff {AO_FALLOFF['name']}, {wide.passes} wide filter passes over the obscurance plane")
+    elif isinstance(filt, api.WideFilterParams) and AO_BENT["on"] and AO_BENT["filter"]:
+        # --bent-filter: ONE chain filters the direction and the AO term together; the combine is then aimed by the filtered vector
+        d_scratch = ctx.malloc(api.wide_filter_bent_scratch_bytes(W, H)) if filt.passes >= 2 else None
+        d_filtered = ctx.malloc(W * H * 16)
+        api.wide_filter_bent_device(ctx, filt, ao.samples, d_pos, d_nrm, AO_BENT["d_bent"], W, H, d_filtered, d_ao=d_ao, d_scratch=d_scratch)
+        ctx.synchronize()
+        ctx.free(AO_BENT["d_bent"])
+        AO_BENT["d_bent"] = d_filtered
+        print(f"ambient occlusion: {filt.passes} wide filter passes over the bent plane (direction and count together)")
+        if AO_BENT["out"]:
+            write_bent(ctx, api, d_filtered, W, H, "the filtered bent vector")
     elif isinstance(filt, api.WideFilterParams):
         d_scratch = ctx.malloc(api.wide_filter_scratch_bytes(1, W, H)) if filt.passes >= 2 else None
         api.wide_filter_soft_light_list_device(ctx, stand_in, filt, d_pos, d_nrm, d_counts, W, H, d_ao, d_scratch=d_scratch)
@@ -558,6 +574,10 @@ def main():
     ap.add_argument("--ground", default="0.45,0.35,0.25", metavar="r,g,b", help="with --ao-bent: the ambient colour against --up")
     ap.add_argument("--up", default="0,1,0", metavar="x,y,z", help="with --ao-bent: the direction of the sky (normalised here)")
     ap.add_argument("--bent-out", default="", metavar="FILE.ppm", help="with --ao-bent: also write 0.5 + 0.5 * unit(bent) as an image")
+    ap.add_argument("--bent-filter", action="store_true",
+                    help="with --ao-bent --filter-passes K: run the wide filter of the bent plane (rtsh_wide_filter_bent_device) in place of "
+                         "the count-plane filter -- its ao feeds the AO term, its out aims the tint, and --bent-out writes the filtered "
+                         "direction")
     args = ap.parse_args()
     from raytracedshadows_amd import api, workloads
     scene, W, H, light, spp = workloads.CONFIGS[args.config]
@@ -582,13 +602,15 @@ def main():
             sys.exit("render: --bent-out goes with --ao-bent")
         if args.ao_bent and args.ao_adaptive:
             sys.exit("render: --ao-bent does not go with --ao-adaptive (a unanimous pixel has no traced sum)")
+        if args.bent_filter and not (args.ao_bent and args.filter_passes >= 0):
+            sys.exit("render: --bent-filter goes with --ao-bent and --filter-passes K")
         if args.ao_bent:
             try:
                 sky, ground, up = ([float(v) for v in t.split(",")] for t in (args.sky, args.ground, args.up))
                 assert len(sky) == len(ground) == len(up) == 3 and np.linalg.norm(up) > 0
             except (ValueError, AssertionError):
                 sys.exit("render: --sky, --ground and --up take three numbers r,g,b / x,y,z (up not zero)")
-            AO_BENT.update(on=True, out=args.bent_out, sky=api.SkyAmbient.make(up=np.asarray(up) / np.linalg.norm(up), sky=sky, ground=ground))
+            AO_BENT.update(on=True, out=args.bent_out, filter=args.bent_filter, sky=api.SkyAmbient.make(up=np.asarray(up) / np.linalg.norm(up), sky=sky, ground=ground))
         if (args.ao_falloff or args.ao_distance) and ao is None:
             sys.exit("render: --ao-falloff and --ao-distance go with --ao")
         if args.ao_distance and not args.ao_falloff:
