@@ -598,14 +598,96 @@ int rtsh_wide_filter_soft_light_list_device(rts_ctx* ctx, const rts_soft_light_l
  *     NULL positions, normals, bent or out; nsamples > RTS_AO_MAX_SAMPLES; in the device form a NULL ctx, H above 16 * 65535, a NULL
  *     d_scratch with passes >= 2, d_out or d_ao equal to d_bent, to d_scratch or to its second half, a d_bent or d_out that is not
  *     aligned to 16 bytes, a d_scratch not aligned to 8.
- *   * OUT OF SCOPE: temporal accumulation of the bent plane, variance guidance, a bent form of the adaptive or distance traces, stripes
- *     and row ranges. */
+ *   * OUT OF SCOPE: ~~temporal accumulation of the bent plane~~ (rtsh_accumulate_bent* and rtsh_wide_filter_bent_mean* below, DESIGN.md
+ *     4.39), variance guidance, a bent form of the adaptive or distance traces, stripes and row ranges. */
 size_t rtsh_wide_filter_bent_scratch_bytes(uint32_t W, uint32_t H);   /* 2 * W * H * 8; 0 where W or H is 0 */
 int rtsh_wide_filter_bent(const rtsh_wide_filter_params* params, uint32_t nsamples, const float* positions, const float* normals,
                           const uint8_t* active, const float* bent, uint32_t W, uint32_t H, float* out, float* ao, int threads);
 int rtsh_wide_filter_bent_device(rts_ctx* ctx, const rtsh_wide_filter_params* params, uint32_t nsamples, const float* d_positions,
                                  const float* d_normals, const uint8_t* d_active, const float* d_bent, uint32_t W, uint32_t H, float* d_out,
                                  float* d_ao, void* d_scratch, void* stream);
+
+/* THE TEMPORAL ACCUMULATION OF THE BENT TEXEL: the wide bent filter's 8-byte texel over reprojected frames, in FIXED
+ * POINT -- what rtsh_accumulate_moments_soft_light_list* (further down) does for a count plane, for the vector that aims the sky tint.  A
+ * spatial filter cannot remove an error every pixel of a surface shares (a trace without a direction table); different directions on
+ * different frames, averaged at the same surface point, can: the caller varies rts_ao_params.dirs per frame, no frame term is added to the
+ * trace.  The current value is an integer and the bilinear weights are integers, so every sum is an integer sum: THE RESULT DOES NOT
+ * DEPEND ON THE ORDER OF THE TAPS, and the host form checks the device form bit for bit.
+ *   THE TEXEL, owned by the caller from here on: 8 bytes, int16 x, y, z then uint16 V, lowest bits first (little endian: a uint64_t
+ *     whose bits 0..15 are x, 16..31 y, 32..47 z, 48..63 V).  x, y, z: the bent vector in units of 1 / S_b, S_b = 32767 / n; V: the count
+ *     in units of 1 / S_l, S_l = 65535 / n; both by integer division -- the wide bent filter's fixed point above.
+ *   CURRENT frame: params (rtsh_temporal_params, the struct and the meaning of rtsh_accumulate_visibility_list); nsamples, n = max(1,
+ *     nsamples) <= RTS_AO_MAX_SAMPLES; positions, normals; `active`, W x H bytes or NULL: a pixel is ACTIVE when it is not bg(p) and
+ *     (active == NULL or active[p] != 0), the wide bent filter's rule; `bent`: the trace's W x H RGBA32F plane, any float allowed.
+ *   PREVIOUS frame: prev_positions, prev_normals, prev_texels (W x H texels), prev_lengths (W x H bytes).  All four NULL: the FIRST
+ *     FRAME; all four or none.  Any 8 bytes are legal in the history, components 0x8000 and a V above n * S_l included.
+ *   Outputs: texels_out (W x H texels), lengths_out (W x H bytes).
+ *   CURRENT VALUE: X_0 and V_0 are the wide bent filter's INPUT rule exactly: per component one rounded multiply by S_b, a NaN gives 0,
+ *     the clamp to +-(n * S_b), rint; .w: a NaN gives 0, the clamp to [0, n], rint, times S_l.
+ *   GEOMETRY: INACTIVE (above), REPROJECT, the four taps in their order, their integer weights and the acceptance of a tap are
+ *     rtsh_accumulate_visibility_list's, word for word, with ONE plane: prev_lengths[q] != 0 stands in for the per-light length, bit 0 of
+ *     reset_lights is the reset.  An inactive pixel gets an all-zero texel and length 0.
+ *   PASS-THROUGH: on the first frame, with the reset bit, off screen, with no accepted tap, or with n_f == 1: pack(X_0, V_0), length 1.
+ *   BLEND: sw = the sum of the accepted weights, m = the smallest accepted length, n_f = min(m + 1, max_length), lengths_out = n_f;
+ *     den = n_f * sw < 2^18.  Per signed component c: s = the integer sum of w * X'(q).c over the accepted taps (|s| <= 2^25),
+ *     num = (n_f - 1) * s + sw * X_0.c (|num| < 2^34), out.c = sign(num) * ((2 * |num| + den) / (2 * den)) by integer division: the
+ *     ROUNDED MEAN, HALF AWAY FROM ZERO, so that the pass commutes with negation.  V: the moments pass's mean rule unchanged,
+ *     (2 * ((n_f - 1) * s + sw * V_0) + den) / (2 * den).  Everything fits 64 bits.
+ * ANCHORS: (1) lengths_out and the V channel equal, byte for byte, lengths_out and mean_out of rtsh_accumulate_moments_soft_light_list*
+ * over the trace's own `counts` under a one-entry soft list of n samples, a map of 0 / 1 bytes made from `active`, the same reset bit
+ * and a history whose V channel is that prev_mean.  (2) Negating every bent.xyz and every history x, y, z negates every output x, y, z
+ * (no history component being -32768, which has no negative).  (3) A still camera (one tap of weight 1024) gives, per component,
+ * h_k = sign * ((2 * |(n_f - 1) * h_(k-1) + cur| + n_f) / (2 * n_f)).  (4) max_length == 1, the reset bit and the first frame give
+ * pack(X_0, V_0) and length 1 at active pixels.  (5) RANGE: every output component lies between the smallest and the largest of its
+ * accepted history values and the current one; so the output stays inside int16 / uint16.  (6) Equal accepted values give that value.
+ *   * motion forms: prev_points and prev_point_normals of this frame's motion G-buffer pass; REPROJECT and TAP ACCEPTANCE change as in
+ *     rtsh_accumulate_visibility_list_motion, word for word (Q = prev_points[p], the taps are tested with M_p = prev_point_normals[p], a
+ *     background M_p accepts no tap).
+ *   * host forms: multi-threaded (threads: 0 = all host threads).  Device forms: DEVICE buffers, asynchronous on `stream`, allocate
+ *     nothing, read nothing back; under graph capture ONE kernel node, params by value.  No BVH.  d_bent is ALIGNED TO 16 BYTES, both
+ *     texel planes TO 8 (they are read and written whole).
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: what rtsh_accumulate_moments_soft_light_list* refuses of params, the frame
+ *     and the buffers (bent in the place of counts, the texel planes in the place of the mean planes); nsamples > RTS_AO_MAX_SAMPLES;
+ *     some but not all of the four prev_*; texels_out == prev_texels or lengths_out == prev_lengths (history must ping-pong); in the
+ *     device forms a NULL ctx, a d_bent not aligned to 16 bytes, a texel plane not aligned to 8, H above 16 * 65535; in the motion forms,
+ *     with a history, a NULL prev_points or prev_point_normals.
+ *   * OUT OF SCOPE: a second moment or variance guidance for the vector, a history clamp for it, a frame term inside the trace's table
+ *     hash, bent forms of the adaptive or distance traces, stripes and row ranges. */
+int rtsh_accumulate_bent(const rtsh_temporal_params* params, uint32_t nsamples, const float* positions, const float* normals,
+                         const uint8_t* active, const float* bent, const float* prev_positions, const float* prev_normals,
+                         const void* prev_texels, const uint8_t* prev_lengths, uint32_t W, uint32_t H, void* texels_out,
+                         uint8_t* lengths_out, int threads);
+int rtsh_accumulate_bent_device(rts_ctx* ctx, const rtsh_temporal_params* params, uint32_t nsamples, const float* d_positions,
+                                const float* d_normals, const uint8_t* d_active, const float* d_bent, const float* d_prev_positions,
+                                const float* d_prev_normals, const void* d_prev_texels, const uint8_t* d_prev_lengths, uint32_t W,
+                                uint32_t H, void* d_texels_out, uint8_t* d_lengths_out, void* stream);
+int rtsh_accumulate_bent_motion(const rtsh_temporal_params* params, uint32_t nsamples, const float* positions, const float* normals,
+                                const uint8_t* active, const float* bent, const float* prev_positions, const float* prev_normals,
+                                const void* prev_texels, const uint8_t* prev_lengths, const float* prev_points,
+                                const float* prev_point_normals, uint32_t W, uint32_t H, void* texels_out, uint8_t* lengths_out,
+                                int threads);
+int rtsh_accumulate_bent_motion_device(rts_ctx* ctx, const rtsh_temporal_params* params, uint32_t nsamples, const float* d_positions,
+                                       const float* d_normals, const uint8_t* d_active, const float* d_bent,
+                                       const float* d_prev_positions, const float* d_prev_normals, const void* d_prev_texels,
+                                       const uint8_t* d_prev_lengths, const float* d_prev_points, const float* d_prev_point_normals,
+                                       uint32_t W, uint32_t H, void* d_texels_out, uint8_t* d_lengths_out, void* stream);
+
+/* THE WIDE BENT FILTER FED FROM THE ACCUMULATED TEXEL: SVGF's order -- integrate over time, then filter.
+ * rtsh_wide_filter_bent*'s rule word for word with ONE change, of INPUT: at an active pixel X_0'.c = clamp(texel.c, -(n * S_b), n * S_b)
+ * and V_0' = min(texel.V, n * S_l), read from the 8-byte plane `texels` (rtsh_accumulate_bent*'s output for THIS frame) at active pixels
+ * only.  The CLAMP is this form's own: the accumulate never writes more (its RANGE anchor), but any 8 bytes are allowed and out.xyz must
+ * stay in [-1, 1], out.w in [0, 1].  The argument list is the parent's with `const void* texels` in the place of bent; the scratch
+ * (rtsh_wide_filter_bent_scratch_bytes), the refusals and the max(1, passes) kernel nodes are unchanged; only the first kernel differs.
+ * ANCHORS: (1) over the texels of a first-frame accumulate, out and ao are bit for bit rtsh_wide_filter_bent*'s of the float plane, for
+ * every passes.  (2) passes == 0 gives the two quotients of the clamped texel.  (3) The parent's negation, range, closed-threshold and
+ * equal-texel anchors hold.
+ *   * RTS_ERR_INVALID_ARG, nothing launched, nothing written: everything the parent refuses (texels in the place of bent); in the device
+ *     form a d_texels not aligned to 8 bytes, or equal to d_out, d_ao, d_scratch or its second half. */
+int rtsh_wide_filter_bent_mean(const rtsh_wide_filter_params* params, uint32_t nsamples, const float* positions, const float* normals,
+                               const uint8_t* active, const void* texels, uint32_t W, uint32_t H, float* out, float* ao, int threads);
+int rtsh_wide_filter_bent_mean_device(rts_ctx* ctx, const rtsh_wide_filter_params* params, uint32_t nsamples, const float* d_positions,
+                                      const float* d_normals, const uint8_t* d_active, const void* d_texels, uint32_t W, uint32_t H,
+                                      float* d_out, float* d_ao, void* d_scratch, void* stream);
 
 /* THE VARIANCE-GUIDED WIDE FILTER OF A SOFT LIGHT LIST'S PLANES: rtsh_wide_filter_soft_light_list above with SVGF's luminance stop, so
  * that the passes blur noise and stop at a sharp shadow edge.  A tap is accepted for a light only if its value lies within a tolerance

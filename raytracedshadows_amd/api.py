@@ -188,6 +188,10 @@ class SoftLightList(C.Structure):
         return LightList.make([(self.lights[l].type, list(self.lights[l].xyz)) for l in range(self.count)])
 
 
+#: the turn of ``AoParams.rotated`` per frame, in radians
+GOLDEN_ANGLE = float(np.pi * (3.0 - np.sqrt(5.0)))
+
+
 class AoParams(C.Structure):
     """``rts_ao_params``: an ambient occlusion trace -- ``nsamples`` segment rays of length ``radius`` per pixel, aimed by the
     tangent-space directions ``dirs`` (x, y in the tangent plane, z along the normal) through the frame around the G-buffer's normal."""
@@ -226,6 +230,16 @@ class AoParams(C.Structure):
     def dirs_array(self):
         """``float32[64, 4]``, a copy."""
         return np.ctypeslib.as_array(self.dirs).reshape(64, 4).astype(np.float32).copy()
+
+    def rotated(self, frame):
+        """A copy whose ``dirs`` are turned about the normal (tangent-space z) by ``frame`` times the golden angle, formed in float64
+        and rounded once: a frame loop's direction set for frame ``frame`` (``accumulate_bent`` averages them; frame 0 is ``self``)."""
+        out = type(self).from_buffer_copy(self)
+        if frame:
+            d = self.dirs_array().astype(np.float64)
+            c, s = np.cos(frame * GOLDEN_ANGLE), np.sin(frame * GOLDEN_ANGLE)
+            np.ctypeslib.as_array(out.dirs)[:, :2] = np.stack([c * d[:, 0] - s * d[:, 1], s * d[:, 0] + c * d[:, 1]], axis=1)
+        return out
 
     def stand_in_list(self):
         """The one-entry ``SoftLightList`` of the same ``nsamples``: what the filters, the moments pass and the upsample take an AO
@@ -760,6 +774,19 @@ _sig("rtsh_wide_filter_bent_scratch_bytes", C.c_size_t, C.c_uint32, C.c_uint32)
 _sig("rtsh_wide_filter_bent", C.c_int, C.POINTER(WideFilterParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
      C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
 _sig("rtsh_wide_filter_bent_device", C.c_int, C.c_void_p, C.POINTER(WideFilterParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_accumulate_bent", C.c_int, C.POINTER(TemporalParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rtsh_accumulate_bent_device", C.c_int, C.c_void_p, C.POINTER(TemporalParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_sig("rtsh_accumulate_bent_motion", C.c_int, C.POINTER(TemporalParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rtsh_accumulate_bent_motion_device", C.c_int, C.c_void_p, C.POINTER(TemporalParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+     C.c_void_p)
+_sig("rtsh_wide_filter_bent_mean", C.c_int, C.POINTER(WideFilterParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int)
+_sig("rtsh_wide_filter_bent_mean_device", C.c_int, C.c_void_p, C.POINTER(WideFilterParams), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
      C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 _sig("rtsh_wide_filter_guided_scratch_bytes", C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32)
 _sig("rtsh_wide_guide_threshold", C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32)
@@ -2559,6 +2586,84 @@ def wide_filter_bent_device(ctx, params, nsamples, d_positions, d_normals, d_ben
                                              C.c_void_p(d_active or 0), C.c_void_p(d_bent or 0), width, height, C.c_void_p(d_out or 0),
                                              C.c_void_p(d_ao or 0), C.c_void_p(d_scratch or 0), C.c_void_p(stream or 0)),
            "rtsh_wide_filter_bent_device")
+
+
+def wide_filter_bent_mean(params, nsamples, positions, normals, texels, active=None, threads=0):
+    """The wide bent filter over the accumulated texels on the host (rtsh_wide_filter_bent_mean): ``wide_filter_bent`` with ``texels``,
+    the ``uint64[H, W]`` plane of ``accumulate_bent`` for this frame, in the place of ``bent``; the same ``(out, ao)``."""
+    name = "rtsh_wide_filter_bent_mean"
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    texels = np.ascontiguousarray(texels, np.uint64) if texels is not None else None
+    active = np.ascontiguousarray(active, np.uint8) if active is not None else None
+    if (positions is not None and positions.size != H * W * 4) or (texels is not None and texels.size != H * W) or \
+            (active is not None and active.size != H * W):
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    out, ao = np.zeros((H, W, 4), np.float32), np.zeros((H, W), np.float32)
+    _check(_lib.rtsh_wide_filter_bent_mean(_ref(params), nsamples, _ptr_or_none(positions), _ptr(normals), _ptr_or_none(active),
+                                           _ptr_or_none(texels), W, H, _ptr(out), _ptr(ao), threads), name)
+    return out, ao
+
+
+def wide_filter_bent_mean_device(ctx, params, nsamples, d_positions, d_normals, d_texels, width, height, d_out, d_ao=None, d_scratch=None,
+                                 d_active=None, stream=None):
+    """The wide bent filter over the accumulated texels on the GPU: ``wide_filter_bent_device`` with d_texels = width*height texels of 8
+    bytes (aligned to 8; not d_out, d_ao, d_scratch or its second half) in the place of d_bent; max(1, passes) kernels, asynchronous."""
+    _check(_lib.rtsh_wide_filter_bent_mean_device(ctx.handle, _ref(params), nsamples, C.c_void_p(d_positions or 0),
+                                                  C.c_void_p(d_normals or 0), C.c_void_p(d_active or 0), C.c_void_p(d_texels or 0), width,
+                                                  height, C.c_void_p(d_out or 0), C.c_void_p(d_ao or 0), C.c_void_p(d_scratch or 0),
+                                                  C.c_void_p(stream or 0)), "rtsh_wide_filter_bent_mean_device")
+
+
+def accumulate_bent(params, nsamples, positions, normals, bent, prev=None, active=None, motion=None, threads=0):
+    """The temporal accumulation of the bent texel on the host (rtsh_accumulate_bent, rtsh_accumulate_bent_motion): ``(uint64[H, W]
+    texels, uint8[H, W] lengths)``.  A texel is int16 x, y, z and uint16 V, lowest bits first.  ``params``: a ``TemporalParams`` (bit 0
+    of ``reset_lights`` resets); ``nsamples``: the trace's sample count; ``bent``: this frame's ``float32[H, W, 4]``, any float;
+    ``prev``: None on the first frame, else ``(prev_positions, prev_normals, prev_texels, prev_lengths)`` of the previous frame (its
+    G-buffer and what this call returned for it); ``active``: ``uint8[H, W]`` or None; ``motion``: None, or ``(prev_points,
+    prev_point_normals)`` of this frame's motion G-buffer pass for the motion form."""
+    name = "rtsh_accumulate_bent" + ("_motion" if motion is not None else "")
+    normals = np.ascontiguousarray(normals, np.float32)
+    H, W = normals.shape[:2]
+    positions = np.ascontiguousarray(positions, np.float32) if positions is not None else None
+    bent = np.ascontiguousarray(bent, np.float32) if bent is not None else None
+    active = np.ascontiguousarray(active, np.uint8) if active is not None else None
+    fits = (positions is None or positions.size == H * W * 4) and (bent is None or bent.size == H * W * 4) and \
+        (active is None or active.size == H * W)
+    if prev is not None:
+        prev = tuple(np.ascontiguousarray(a, t) for a, t in zip(prev, (np.float32, np.float32, np.uint64, np.uint8)))
+        fits = fits and len(prev) == 4 and prev[0].size == H * W * 4 and prev[1].size == H * W * 4 and \
+            all(a.size == H * W for a in prev[2:])
+    if not fits:
+        raise RtsError(1, name + ": a buffer does not fit the frame of the normals")
+    texels, lengths = np.zeros((H, W), np.uint64), np.zeros((H, W), np.uint8)
+    pp = [_ptr(a) for a in prev] if prev is not None else [None] * 4
+    head = (_ref(params), nsamples, _ptr_or_none(positions), _ptr(normals), _ptr_or_none(active), _ptr_or_none(bent), *pp)
+    if motion is not None:
+        mp = _motion_planes(motion, H, W, name)
+        _check(_lib.rtsh_accumulate_bent_motion(*head, _ptr_or_none(mp[0]), _ptr_or_none(mp[1]), W, H, _ptr(texels), _ptr(lengths), threads),
+               name)
+        return texels, lengths
+    _check(_lib.rtsh_accumulate_bent(*head, W, H, _ptr(texels), _ptr(lengths), threads), name)
+    return texels, lengths
+
+
+def accumulate_bent_device(ctx, params, nsamples, d_positions, d_normals, d_bent, width, height, d_texels_out, d_lengths_out, d_prev=None,
+                           d_active=None, d_motion=None, stream=None):
+    """The accumulation of the bent texel on the GPU: device pointers; d_bent = width*height RGBA32F aligned to 16 bytes; d_texels_out =
+    width*height texels of 8 bytes aligned to 8, d_lengths_out of bytes; ``d_prev``: None on the first frame, else the device pointers
+    ``(prev_positions, prev_normals, prev_texels, prev_lengths)``, which the outputs may not be.  ``d_motion``: None, or the device
+    pointers ``(prev_points, prev_point_normals)`` for the motion form.  One kernel, asynchronous."""
+    pp = tuple(d_prev) if d_prev is not None else (0, 0, 0, 0)
+    head = (ctx.handle, _ref(params), nsamples, C.c_void_p(d_positions or 0), C.c_void_p(d_normals or 0), C.c_void_p(d_active or 0),
+            C.c_void_p(d_bent or 0), C.c_void_p(pp[0] or 0), C.c_void_p(pp[1] or 0), C.c_void_p(pp[2] or 0), C.c_void_p(pp[3] or 0))
+    tail = (width, height, C.c_void_p(d_texels_out or 0), C.c_void_p(d_lengths_out or 0), C.c_void_p(stream or 0))
+    if d_motion is not None:
+        _check(_lib.rtsh_accumulate_bent_motion_device(*head, C.c_void_p(d_motion[0] or 0), C.c_void_p(d_motion[1] or 0), *tail),
+               "rtsh_accumulate_bent_motion_device")
+        return
+    _check(_lib.rtsh_accumulate_bent_device(*head, *tail), "rtsh_accumulate_bent_device")
 
 
 def wide_filter_guided_scratch_bytes(count, width, height):

@@ -876,6 +876,103 @@ RTS_HD void accumulateMomentsPixel(const MomentsList& g, const Frames& t, int x,
     }
 }
 
+// The TEMPORAL ACCUMULATION OF THE BENT TEXEL (include/rts_scene.h, rtsh_accumulate_bent), one pixel: the geometry of
+// accumulateMomentsPixel for ONE plane -- INACTIVE by the bent filter's rule (not background, byte non-zero), REPROJECT, the four taps,
+// their integer weights and their acceptance, a COPY of its statements once more (accumulateMomentsKernel keeps its instruction text)
+// -- in front of an integer blend of the wide bent filter's 8-byte texel: V by the moments pass's rounded mean, x, y, z by the same mean
+// of the magnitude with the sign put back (half away from zero), so the pass commutes with negation.  |s| <= 1024 * 32768 = 2^25,
+// |num| <= 254 * 2^25 + 2^10 * 2^15 < 2^34, den = n * sw < 2^18: exact in 64 bits, and no order of taps can change a bit.  `Frames`:
+// V3 normal(x, y), position(x, y); bool active(x, y) (the byte, true without a plane); BentTexel current(x, y) (X_0, V_0: bentFilterInput
+// of this frame's float texel); V3 prevNormal(x, y), prevPosition(x, y); uint32_t prevLength(x, y); BentTexel prevTexel(x, y) (the
+// unpacked 8 bytes, whatever they hold); void store(x, y, uint64_t texel, uint32_t length); with Motion also prevPoint, prevPointNormal.
+struct BentTemporalList { TemporalList t; BentFilterList q; };                                     // q: n, S_b, S_l (its thresholds unused)
+
+RTS_HD int32_t bentTemporalMean(int64_t num, uint32_t den) {
+    const uint64_t a = num < 0 ? (uint64_t)(-num) : (uint64_t)num;
+    const int32_t q = (int32_t)momentsQuotient(2u * a + den, 2u * den);
+    return num < 0 ? -q : q;
+}
+
+template <bool Motion = false, class Frames>
+RTS_HD void accumulateBentPixel(const BentTemporalList& g, const Frames& t, int x, int y, int W, int H) {
+    const TemporalList& f = g.t;
+    const V3 np = t.normal(x, y);
+    if (isBackground(np) || !t.active(x, y)) { t.store(x, y, 0u, 0u); return; }
+    int qx[4] = { 0, 0, 0, 0 }, qy[4] = { 0, 0, 0, 0 };
+    uint32_t w[4] = { 0, 0, 0, 0 }, taps = 0;                                                      // taps: bit k = tap k passes the geometry
+    if (f.history != 0u && !(f.resetLights & 1u)) {
+        V3 q, mp;                                                                                  // Q, and the normal the taps are tested with
+        if constexpr (Motion) { q = t.prevPoint(x, y); mp = t.prevPointNormal(x, y); }
+        else { q = add(t.position(x, y), f.eyeDelta); mp = np; }
+        const float z = dotGrouped(q, f.fwd);
+        const float a = dotGrouped(q, f.right) / z, b = dotGrouped(q, f.up) / z;
+        const float fx = (a / f.scaleX + 1.0f) * (0.5f * (float)W) - 0.5f;
+        const float fy = (1.0f - b / f.scaleY) * (0.5f * (float)H) - 0.5f;
+        const float gx = fx * 32.0f + 0.5f, gy = fy * 32.0f + 0.5f;
+        if (z > 0.0f && gx >= -32.0f && gx < (float)W * 32.0f && gy >= -32.0f && gy < (float)H * 32.0f && !(Motion && isBackground(mp))) {
+            const int32_t ix = (int32_t)__builtin_floorf(gx), iy = (int32_t)__builtin_floorf(gy);
+            const int x0 = ix >> 5, y0 = iy >> 5;
+            const uint32_t ax = (uint32_t)(ix & 31), ay = (uint32_t)(iy & 31);
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+            for (int k = 0; k < 4; ++k) {
+                qx[k] = x0 + (k & 1); qy[k] = y0 + (k >> 1);
+                w[k] = ((k & 1) ? ax : 32u - ax) * ((k >> 1) ? ay : 32u - ay);
+                if (w[k] == 0u || qx[k] < 0 || qx[k] >= W || qy[k] < 0 || qy[k] >= H) continue;
+                const V3 nq = t.prevNormal(qx[k], qy[k]);
+                if (isBackground(nq)) continue;
+                if (!(dotGrouped(mp, nq) >= f.normalCosMin)) continue;
+                const float h = dotGrouped(mp, sub(t.prevPosition(qx[k], qy[k]), q));
+                if (!(__builtin_fabsf(h) <= f.planeEps)) continue;
+                taps |= 1u << k;
+            }
+        }
+    }
+    const BentTexel cur = t.current(x, y);
+    uint32_t sw = 0, m = 255u, sv = 0;
+    int32_t sx = 0, sy = 0, sz = 0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < 4; ++k) {
+        if (!((taps >> k) & 1u)) continue;
+        const uint32_t len = t.prevLength(qx[k], qy[k]);
+        if (len == 0u) continue;
+        const BentTexel h = t.prevTexel(qx[k], qy[k]);
+        const int32_t wk = (int32_t)w[k];
+        sw += w[k];
+        sx += wk * h.x; sy += wk * h.y; sz += wk * h.z;                                            // |sum| <= 1024 * 32768 = 2^25
+        sv += w[k] * h.v;                                                                          // 1024 * 65535 < 2^26
+        if (len < m) m = len;
+    }
+    const uint32_t n = sw == 0u ? 1u : (m + 1u < f.maxLength ? m + 1u : f.maxLength);
+    BentTexel out = cur;
+    if (n != 1u) {
+        const uint32_t den = n * sw;                                                               // <= 255 * 1024
+        const int64_t k = (int64_t)(n - 1u), c = (int64_t)sw;
+        out.x = bentTemporalMean(k * sx + c * cur.x, den);
+        out.y = bentTemporalMean(k * sy + c * cur.y, den);
+        out.z = bentTemporalMean(k * sz + c * cur.z, den);
+        out.v = (uint32_t)momentsQuotient(2u * ((uint64_t)(n - 1u) * sv + (uint64_t)sw * cur.v) + den, 2u * den);
+    }
+    t.store(x, y, bentFilterPack(out), n);
+}
+
+// INPUT of the wide bent filter fed from the accumulated texel (rtsh_wide_filter_bent_mean): the 8 bytes clamped to what the trace can
+// give -- the accumulate never writes more (its RANGE anchor), but any 8 bytes are allowed and out.xyz must stay in [-1, 1], out.w in
+// [0, 1] (a component 0x8000 is -32768 < -(n * S_b); 65535 > n * S_l for n = 48).
+RTS_HD BentTexel bentFilterMeanInput(uint64_t texel, const BentFilterList& f) {
+    BentTexel v = bentFilterUnpack(texel);
+    const int32_t lim = (int32_t)(f.samples * f.scaleB);
+    const uint32_t full = f.samples * f.scaleL;
+    v.x = v.x < -lim ? -lim : (v.x > lim ? lim : v.x);
+    v.y = v.y < -lim ? -lim : (v.y > lim ? lim : v.y);
+    v.z = v.z < -lim ? -lim : (v.z > lim ? lim : v.z);
+    v.v = v.v < full ? v.v : full;
+    return v;
+}
+
 // The TEMPORAL THRESHOLD of the guided wide filter (include/rts_scene.h, rtsh_wide_filter_guided_temporal_soft_light_list):
 // wideGuideThresholdPixel with one change, in the energy of a counted pixel q: n_l * max(0, square - mean^2) where the moments'
 // history at q is at least minHistory frames long, else the Bernoulli energy V_0 * (n S - V_0) as there.  The planes are read where

@@ -204,3 +204,4 @@ extern "C" int rtsh_combine_soft_light_list_device(rts_ctx* ctx, const rts_const
 #include "rts_upsample.inc" // half-resolution light lists: subsample, retrace map, upsample
 #include "rts_compact.inc" // a light map compacted into the list of its marked pixels, for the sparse list traces
 #include "rts_wide_bent.inc" // the wide filter of the bent plane: a-trous over integer vectors
+#include "rts_bent_temporal.inc" // the bent texel accumulated over frames, and the wide bent filter fed from it

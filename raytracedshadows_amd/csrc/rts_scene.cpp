@@ -1456,6 +1456,142 @@ extern "C" int rtsh_accumulate_moments_soft_light_list_motion(const rts_soft_lig
     return RTS_OK;
 }
 
+// ---- the temporal accumulation of the bent texel and the wide bent filter fed from it (include/rts_scene.h; per-pixel
+// rules in rts_closest_hit.h: accumulateBentPixel, bentFilterMeanInput) ----
+namespace rts_harness {
+// Shared by the host and device forms: makeTemporalList's refusals over a one-entry stand-in list (bent in the place of visibility, the
+// texel planes in the place of the float history), the sample count's, and n, S_b, S_l.
+int makeBentTemporalList(const rtsh_temporal_params* p, uint32_t nsamples, const void* positions, const void* normals, const void* bent,
+                         const void* prevPositions, const void* prevNormals, const void* prevTexels, const void* prevLengths, uint32_t W,
+                         uint32_t H, const void* texelsOut, const void* lengthsOut, BentTemporalList* out) {
+    if (!out || nsamples > (uint32_t)RTS_AO_MAX_SAMPLES) return RTS_ERR_INVALID_ARG;
+    rts_light_list one;
+    std::memset(&one, 0, sizeof(one));
+    one.count = 1;
+    const int s = makeTemporalList(&one, p, positions, normals, bent, prevPositions, prevNormals, prevTexels, prevLengths, W, H, texelsOut,
+                                   lengthsOut, &out->t);
+    if (s != RTS_OK) return s;
+    const uint32_t n = nsamples > 1u ? nsamples : 1u;
+    out->q = BentFilterList{ 0u, n, bentFilterScale(n), wideFilterScale(n), 0.0f, 0.0f };
+    return RTS_OK;
+}
+
+namespace {
+// Both frames as accumulateBentPixel reads them on the host: straight from the buffers.
+struct BentTemporalFrames {
+    const float *positions, *normals, *bent, *prevPositions, *prevNormals;
+    const uint8_t *map, *prevLengths;
+    const uint64_t* prevTexels;
+    uint64_t* texelsOut;
+    uint8_t* lengthsOut;
+    const BentFilterList& f;
+    size_t W;
+    size_t at(int x, int y) const { return (size_t)y * W + (size_t)x; }
+    static V3 xyz(const float* base, size_t i) { const float* v = base + i * 4; return V3{ v[0], v[1], v[2] }; }
+    V3 normal(int x, int y) const { return xyz(normals, at(x, y)); }
+    V3 position(int x, int y) const { return xyz(positions, at(x, y)); }
+    bool active(int x, int y) const { return !map || map[at(x, y)] != 0; }
+    BentTexel current(int x, int y) const { const float* b = bent + at(x, y) * 4; return bentFilterInput(b[0], b[1], b[2], b[3], f); }
+    V3 prevNormal(int x, int y) const { return xyz(prevNormals, at(x, y)); }
+    V3 prevPosition(int x, int y) const { return xyz(prevPositions, at(x, y)); }
+    uint32_t prevLength(int x, int y) const { return prevLengths[at(x, y)]; }
+    BentTexel prevTexel(int x, int y) const { return bentFilterUnpack(prevTexels[at(x, y)]); }
+    void store(int x, int y, uint64_t texel, uint32_t length) const { texelsOut[at(x, y)] = texel; lengthsOut[at(x, y)] = (uint8_t)length; }
+};
+
+int accumulateBentHost(bool motion, const rtsh_temporal_params* params, uint32_t nsamples, const float* positions, const float* normals,
+                       const uint8_t* active, const float* bent, const float* prev_positions, const float* prev_normals,
+                       const void* prev_texels, const uint8_t* prev_lengths, const float* prev_points, const float* prev_point_normals,
+                       uint32_t W, uint32_t H, void* texels_out, uint8_t* lengths_out, int threads) {
+    BentTemporalList f;
+    int s = makeBentTemporalList(params, nsamples, positions, normals, bent, prev_positions, prev_normals, prev_texels, prev_lengths, W, H,
+                                 texels_out, lengths_out, &f);
+    if (s == RTS_OK && motion) s = checkMotionPlanes(f.t.history, prev_points, prev_point_normals);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    const MotionOf<BentTemporalFrames> t{ { positions, normals, bent, prev_positions, prev_normals, active, prev_lengths,
+                                            (const uint64_t*)prev_texels, (uint64_t*)texels_out, lengths_out, f.q, W },
+                                          prev_points, prev_point_normals };
+    if (motion) parallelFor(n, 256, threads, [&](size_t i) { accumulateBentPixel<true>(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H); });
+    else parallelFor(n, 256, threads, [&](size_t i) { accumulateBentPixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H); });
+    return RTS_OK;
+}
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_accumulate_bent(const rtsh_temporal_params* params, uint32_t nsamples, const float* positions, const float* normals,
+                                    const uint8_t* active, const float* bent, const float* prev_positions, const float* prev_normals,
+                                    const void* prev_texels, const uint8_t* prev_lengths, uint32_t W, uint32_t H, void* texels_out,
+                                    uint8_t* lengths_out, int threads) {
+    return accumulateBentHost(false, params, nsamples, positions, normals, active, bent, prev_positions, prev_normals, prev_texels,
+                              prev_lengths, nullptr, nullptr, W, H, texels_out, lengths_out, threads);
+}
+
+extern "C" int rtsh_accumulate_bent_motion(const rtsh_temporal_params* params, uint32_t nsamples, const float* positions,
+                                           const float* normals, const uint8_t* active, const float* bent, const float* prev_positions,
+                                           const float* prev_normals, const void* prev_texels, const uint8_t* prev_lengths,
+                                           const float* prev_points, const float* prev_point_normals, uint32_t W, uint32_t H,
+                                           void* texels_out, uint8_t* lengths_out, int threads) {
+    return accumulateBentHost(true, params, nsamples, positions, normals, active, bent, prev_positions, prev_normals, prev_texels,
+                              prev_lengths, prev_points, prev_point_normals, W, H, texels_out, lengths_out, threads);
+}
+
+// The passes of rtsh_wide_filter_bent over the accumulated texel: its loop, statement for statement, with a frame of its own whose
+// first pass reads and clamps the 8-byte texels (the parent's host form keeps its text, as its kernels do).
+namespace rts_harness {
+namespace {
+struct BentMeanFrameTexels {
+    const float *positions, *normals;
+    const uint64_t* mean;                        // the accumulated texels: the first pass's input
+    const uint8_t* map;
+    const uint64_t* values;                      // the previous pass's plane; NULL: the first pass
+    const BentFilterList& f;
+    size_t W;
+    size_t at(int x, int y) const { return (size_t)y * W + (size_t)x; }
+    V3 normal(int x, int y) const { const float* v = normals + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
+    V3 position(int x, int y) const { const float* v = positions + at(x, y) * 4; return V3{ v[0], v[1], v[2] }; }
+    bool active(int x, int y) const { return !map || map[at(x, y)] != 0; }
+    BentTexel texel(int x, int y) const { return values ? bentFilterUnpack(values[at(x, y)]) : bentFilterMeanInput(mean[at(x, y)], f); }
+};
+} // namespace
+} // namespace rts_harness
+
+extern "C" int rtsh_wide_filter_bent_mean(const rtsh_wide_filter_params* params, uint32_t nsamples, const float* positions,
+                                          const float* normals, const uint8_t* active, const void* texels, uint32_t W, uint32_t H, float* out,
+                                          float* ao, int threads) {
+    if (!positions || !normals || !texels || !out) return RTS_ERR_INVALID_ARG;
+    BentFilterList f;
+    const int s = makeBentFilterList(params, nsamples, W, H, &f);
+    if (s != RTS_OK) return s;
+    const size_t n = (size_t)W * H;
+    std::vector<uint64_t> scratch;
+    try {
+        if (f.passes >= 2u) scratch.resize(2 * n);
+    } catch (const std::bad_alloc&) {
+        return RTS_ERR_CAPACITY;
+    }
+    const uint32_t launches = f.passes == 0u ? 1u : f.passes;
+    for (uint32_t k = 0; k < launches; ++k) {
+        const bool first = k == 0u, last = k + 1u == launches;
+        const int step = f.passes == 0u ? 0 : 1 << k;
+        const uint64_t* in = first ? nullptr : scratch.data() + ((k - 1u) & 1u) * n;
+        uint64_t* mid = last ? nullptr : scratch.data() + (k & 1u) * n;
+        const BentMeanFrameTexels t{ positions, normals, (const uint64_t*)texels, active, in, f, W };
+        parallelFor(n, 256, threads, [&](size_t i) {
+            BentTexel v;
+            bentFilterPassPixel(f, t, (int)(i % W), (int)(i / W), (int)W, (int)H, step, &v);
+            if (!last) { mid[i] = bentFilterPack(v); return; }
+            float* o = out + i * 4;
+            o[0] = bentFilterOutput(v.x, f.samples, f.scaleB);
+            o[1] = bentFilterOutput(v.y, f.samples, f.scaleB);
+            o[2] = bentFilterOutput(v.z, f.samples, f.scaleB);
+            o[3] = wideFilterOutput(v.v, f.samples, f.scaleL);
+            if (ao) ao[i] = o[3];
+        });
+    }
+    return RTS_OK;
+}
+
 // ---- the clamped forms of the moments pass (include/rts_scene.h): accumulateMomentsPixel<Motion, true> ----
 namespace rts_harness {
 // The clamp's own refusals, beside makeMomentsList's: shared by the host and device forms.

@@ -6,6 +6,7 @@ PARENT_NAME=NEW_NAME: a kernel that only changed its mangled name (it gained a t
 LOG = the output of `make -C raytracedshadows_amd/csrc asm` in that tree, S = the build/rts_kernels.s it writes.  A kernel counts as
 the same when every figure of its resource remark and the hash of its instructions and labels agree."""
 import hashlib
+import os
 import re
 import sys
 def remarks(path):
@@ -37,7 +38,8 @@ for old, new in (a.split("=") for a in sys.argv[5:]):
     print("# renamed:", old, "is this commit's", new)
 keys = ["VGPRs", "TotalSGPRs", "ScratchSize", "Occupancy", "LDS Size"]
 def row(r): return " ".join(f"{k.split()[0]}={r.get(k, r.get(k+' [bytes/lane]', '?'))}" for k in keys)
-print("# hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (`make asm`) of rts_kernels.hip, parent commit and this commit.")
+unit = os.path.splitext(os.path.basename(sys.argv[4]))[0] + ".hip"
+print(f"# hipcc -O3 --offload-arch=gfx950 -Rpass-analysis=kernel-resource-usage (`make asm` and its flags) of {unit}, parent commit and this commit.")
 print("# text = first 12 hex digits of the sha1 over the kernel's instructions and labels in the generated assembly.")
 print("## kernels this commit adds")
 for k in sorted(nr):

@@ -6,6 +6,11 @@
                                           [--filter R [--spread S] | --filter-passes K [--filter-guide K4 [--guide-history M]]] [--plane-eps E] [--normal-cos C]
                                                       [--temporal F [--orbit DEG] [--max-length L] [--clamp R [--clamp-margin M]] [--moments-clamp R[:K4[:MARGIN]]] [--move SPEC]]]]
 
+--bent-temporal F (with --ao N:R:T --ao-bent [--bent-filter --filter-passes K] [--orbit DEG] [--max-length L]): a frame loop of its own
+-- per frame the G-buffer, the bent trace with its directions turned about the normal by k golden angles, rtsh_accumulate_bent_device with
+ping-pong history; on the last frame the passes run over the accumulated texels (rtsh_wide_filter_bent_mean_device) and the bent combine
+is aimed by the result.  --ao with --temporal stays refused.
+
 --temporal F (with --soft-list N --filter R): F frames are rendered -- trace, filter, rtsh_accumulate_visibility_list_device with
 ping-pong history -- and the LAST frame is lit from the accumulated visibility.  Frame k traces with the shared offsets table rotated
 by k entries; --orbit DEG turns the eye around the target by DEG per frame (default 0: a still camera); --max-length L (default 32) is
@@ -135,7 +140,8 @@ def parse_ao(text, wl):
 
 
 AO_ADAPTIVE = {"probe": 0, "refined_out": ""}           # --ao-adaptive K [--ao-refined FILE.ppm], set by main()
-AO_BENT = {"on": False, "sky": None, "out": "", "d_bent": None, "filter": False}   # --ao-bent [--sky --ground --up --bent-out --bent-filter]
+AO_BENT = {"on": False, "sky": None, "out": "", "d_bent": None, "filter": False, "frames": 0, "orbit": 0.0, "max_length": 32,
+           "thresholds": (0.9, 0.05)}   # --ao-bent [--sky --ground --up --bent-out --bent-filter --bent-temporal F [--orbit DEG]]
 AO_FALLOFF = {"falloff": None, "name": "", "distance_out": ""}    # --ao-falloff NAME [--ao-distance FILE.ppm], set by main()
 
 
@@ -156,6 +162,57 @@ def write_bent(ctx, api, d_bent, W, H, what):
     os.makedirs(os.path.dirname(os.path.abspath(AO_BENT["out"])), exist_ok=True)
     api.write_ppm(AO_BENT["out"], (np.clip(0.5 + 0.5 * unit, 0, 1) * 255).astype(np.uint8))
     print(f"wrote {AO_BENT['out']}: 0.5 + 0.5 * unit({what})")
+
+
+def bent_temporal(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, d_counts, d_ao):
+    """--bent-temporal F [--orbit DEG]: a frame loop of its own.  Per frame k: the G-buffer of eye k (the last frame is the scene's own
+    camera, whose G-buffer the caller has rendered into d_pos, d_nrm), the bent trace with ao.dirs turned about z by k golden angles
+    (AoParams.rotated), rtsh_accumulate_bent_device with ping-pong.  Then the passes of --bent-filter over the accumulated texels
+    (rtsh_wide_filter_bent_mean_device; passes 0 -- the two quotients -- without it) -> the float plane that aims the tint; d_ao is
+    written beside it."""
+    from list_temporal_ab import orbit
+    frames, sc = AO_BENT["frames"], wl.scene
+    if not 1 <= frames <= 255 or not 1 <= AO_BENT["max_length"] <= 255:
+        sys.exit("render: --bent-temporal F takes 1 <= F <= 255 and 1 <= --max-length <= 255")
+    eyes = [orbit(sc.eye, sc.target, AO_BENT["orbit"] * (k - (frames - 1))) for k in range(frames)]
+    n = W * H
+    gbuf = [(ctx.malloc(n * 16), ctx.malloc(n * 16)) for _ in range(2)] if frames > 1 else []
+    history = [(ctx.malloc(n * 8), ctx.malloc(n)) for _ in range(2)]
+    d_bent = ctx.malloc(n * 16)
+    cos_min, plane_eps = AO_BENT["thresholds"]
+    prev = None
+    for k in range(frames):
+        last = k == frames - 1
+        d_p, d_n = (d_pos, d_nrm) if last else gbuf[k % 2]
+        if not last:
+            api.primary_gbuffer_device(ctx, eyes[k], sc.target, sc.fovy, W, H, d_p, d_n)
+        constants = api.RayTracingConstants.make(eyes[k], sc.light_direction, W, H)     # positions are relative to THIS frame's eye
+        ctx.trace_ambient_occlusion_bent_device(constants, ao.rotated(k), d_p, d_n, W, H, d_counts, d_bent)
+        params = None
+        if k:
+            b = api.camera_basis(eyes[k - 1], sc.target, sc.fovy, W, H)
+            params = api.TemporalParams.make(np.asarray(eyes[k], np.float32) - np.asarray(eyes[k - 1], np.float32), b["right"], b["up"], b["fwd"],
+                                             np.float32(b["tan_half"] * b["aspect"]), b["tan_half"], cos_min, plane_eps, AO_BENT["max_length"], 0)
+        else:
+            params = api.TemporalParams.make((0, 0, 0), (1, 0, 0), (0, 1, 0), (0, 0, 1), 1.0, 1.0, cos_min, plane_eps, AO_BENT["max_length"], 0)
+        api.accumulate_bent_device(ctx, params, ao.samples, d_p, d_n, d_bent, W, H, history[k % 2][0], history[k % 2][1], d_prev=prev)
+        prev = (d_p, d_n, history[k % 2][0], history[k % 2][1])
+    wide = filt if AO_BENT["filter"] and isinstance(filt, api.WideFilterParams) else api.WideFilterParams.make(0, cos_min, plane_eps)
+    d_scratch = ctx.malloc(api.wide_filter_bent_scratch_bytes(W, H)) if wide.passes >= 2 else None
+    api.wide_filter_bent_mean_device(ctx, wide, ao.samples, d_pos, d_nrm, prev[2], W, H, d_bent, d_ao=d_ao, d_scratch=d_scratch)
+    ctx.synchronize()
+    lengths = np.zeros((H, W), np.uint8)
+    ctx.d2h(lengths, prev[3])
+    print(f"ambient occlusion: the bent texel accumulated over {frames} frames, dirs turned by the golden angle per frame, orbit "
+          f"{AO_BENT['orbit']:g} degree per frame; mean history {float(lengths[lengths > 0].mean()) if (lengths > 0).any() else 0.0:.2f} frames; "
+          f"{wide.passes} wide filter passes over the accumulated texels")
+    for a, b in gbuf + history:
+        ctx.free(a); ctx.free(b)
+    if d_scratch:
+        ctx.free(d_scratch)
+    AO_BENT["d_bent"] = d_bent
+    if AO_BENT["out"]:
+        write_bent(ctx, api, d_bent, W, H, "the accumulated bent vector")
 
 
 def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
@@ -192,6 +249,8 @@ def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
             os.makedirs(os.path.dirname(os.path.abspath(AO_ADAPTIVE["refined_out"])), exist_ok=True)
             api.write_ppm(AO_ADAPTIVE["refined_out"], np.repeat((refined * 255).astype(np.uint8)[..., None], 3, axis=2))
             print(f"wrote {AO_ADAPTIVE['refined_out']}")
+    elif AO_BENT["on"] and AO_BENT["frames"]:            # --bent-temporal: trace, accumulate and filter in a frame loop of its own
+        bent_temporal(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, d_counts, d_ao)
     elif AO_BENT["on"]:                                  # the same counts, and the bent plane beside them
         AO_BENT["d_bent"] = ctx.malloc(W * H * 16)
         ctx.trace_ambient_occlusion_bent_device(wl.constants, ao, d_pos, d_nrm, W, H, d_counts, AO_BENT["d_bent"])
@@ -204,7 +263,9 @@ def ambient_plane(ctx, api, wl, ao, filt, d_pos, d_nrm, W, H, ao_out=""):
     print(f"ambient occlusion: {ao.samples} segments of {ao.radius:g} per pixel{f', table {ao.table}' if ao.table else ''}: "
           f"{(time.time() - t0) * 1e3:.2f} ms (first call, incl. launch); {ctx.last_kernel_name()}")
     stand_in = ao.stand_in_list()
-    if d_obscurance is not None:                         # the plane IS in the wide filter's fixed point: no conversion pass (passes 0 converts)
+    if AO_BENT["on"] and AO_BENT["frames"]:
+        pass                                             # (d_ao is the loop's: the mean-fed bent filter wrote it)
+    elif d_obscurance is not None:                         # the plane IS in the wide filter's fixed point: no conversion pass (passes 0 converts)
         wide = filt if isinstance(filt, api.WideFilterParams) else api.WideFilterParams.make(0, 0.9, 0.05)
         d_scratch = ctx.malloc(api.wide_filter_scratch_bytes(1, W, H)) if wide.passes >= 2 else None
         api.wide_filter_mean_soft_light_list_device(ctx, stand_in, wide, d_pos, d_nrm, d_obscurance, W, H, d_ao, d_scratch=d_scratch)
@@ -564,6 +625,10 @@ def main():
     ap.add_argument("--ao-bent", action="store_true",
                     help="with --ao N: trace the bent normals beside the counts (rts_trace_ambient_occlusion_bent_device) and tint the "
                          "ambient term between --ground and --sky by where they point (rtsh_combine_visibility_list_ao_bent_device)")
+    ap.add_argument("--bent-temporal", type=int, default=0, metavar="F",
+                    help="with --ao N:R:T --ao-bent: render F frames (--orbit DEG per frame, --max-length L), trace each with the directions "
+                         "turned by the golden angle, accumulate the bent texel over them (rtsh_accumulate_bent_device) and, with "
+                         "--bent-filter, run the passes over the accumulated texels (rtsh_wide_filter_bent_mean_device)")
     ap.add_argument("--ao-falloff", default="", choices=("", "linear", "quadratic", "zeros"),
                     help="with --ao N: trace the falloff-weighted obscurance (rts_trace_ambient_occlusion_distance_device) -- a blocker "
                          "near the end of a segment darkens less than one at its start -- and feed it to the wide mean filter "
@@ -604,13 +669,20 @@ def main():
             sys.exit("render: --ao-bent does not go with --ao-adaptive (a unanimous pixel has no traced sum)")
         if args.bent_filter and not (args.ao_bent and args.filter_passes >= 0):
             sys.exit("render: --bent-filter goes with --ao-bent and --filter-passes K")
+        if args.bent_temporal and not args.ao_bent:
+            sys.exit("render: --bent-temporal F goes with --ao N:R:T --ao-bent")
+        if args.bent_temporal and args.filter >= 0:
+            sys.exit("render: --bent-temporal takes --filter-passes K --bent-filter, not --filter R (the tent filter has no texel form)")
+        if args.bent_temporal and args.filter_passes >= 0 and not args.bent_filter:
+            sys.exit("render: --bent-temporal with --filter-passes K needs --bent-filter (the passes run over the accumulated texels)")
         if args.ao_bent:
             try:
                 sky, ground, up = ([float(v) for v in t.split(",")] for t in (args.sky, args.ground, args.up))
                 assert len(sky) == len(ground) == len(up) == 3 and np.linalg.norm(up) > 0
             except (ValueError, AssertionError):
                 sys.exit("render: --sky, --ground and --up take three numbers r,g,b / x,y,z (up not zero)")
-            AO_BENT.update(on=True, out=args.bent_out, filter=args.bent_filter, sky=api.SkyAmbient.make(up=np.asarray(up) / np.linalg.norm(up), sky=sky, ground=ground))
+            AO_BENT.update(on=True, out=args.bent_out, filter=args.bent_filter, frames=args.bent_temporal, orbit=args.orbit, max_length=args.max_length,
+                           thresholds=(args.normal_cos, args.plane_eps), sky=api.SkyAmbient.make(up=np.asarray(up) / np.linalg.norm(up), sky=sky, ground=ground))
         if (args.ao_falloff or args.ao_distance) and ao is None:
             sys.exit("render: --ao-falloff and --ao-distance go with --ao")
         if args.ao_distance and not args.ao_falloff:
